@@ -1,15 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- the A_mul_B / At_mul_B path on MI355X, one rank per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload all|c2|c3|c4|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no launcher starts the N ranks ITSELF (fresh child processes, before this
 process touches the GPU) and fails loudly if the world it finds is not N.
 
-ONE JSON line on rank 0.  The line itself is BASELINE config 2 (`metric`, `value`, `roofline`, `cpu_baseline` exactly as
-before); with the default `--workload all` its key "also" holds one sub-record per other BASELINE config, each with its own
-`value`, `roofline` (+ `traffic`), `self_check` and, at N = 1, `cpu_baseline`:
+A plain run (no --full) does only what the headline needs: it builds the workload's matrix, runs W untimed and K timed steps,
+writes the outputs of the last step if --dump-outputs DIR is given, and prints ONE short JSON line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, the kernels, `roofline` from the event pair around the timed steps).  --dump-outputs
+writes every vector the timed step returns (config 2: y = A x as y.npy, z = A' u as z.npy) in float64; a vector larger than its
+share of 48 MB is written as a fixed seeded sample of its elements (sample_index), so that two builds compare element for element.
+
+--full runs everything below as well: the self-checks, the per-product and per-launch timings, the probes and bounds, the live
+PMC traffic, the fixed-order cost, the CPU baselines and the other workloads.  ONE JSON line on rank 0.  The line itself is
+BASELINE config 2 (`metric`, `value`, `roofline`, `cpu_baseline` exactly as before); with --full and the default `--workload all`
+its key "also" holds one sub-record per other BASELINE config, each with its own `value`, `roofline` (+ `traffic`), `self_check`
+and, at N = 1, `cpu_baseline`:
     N = 1:  c3, c4 (k = 32, with k = 2 / 4 / 8 beside it), c5 as ONE real shard, and the path's consumer: CG and
             2-right-hand-side block CG on config 2's pattern
     N > 1:  c2 strong scaling (the one 10 M-row matrix cut over the ranks), c5 across the N ranks (with and without the
@@ -324,6 +332,30 @@ def csr_bytes(nnz, nrow, ncol, valued=True, k=1):
     return (12 if valued else 4) * nnz + 4 * (nrow + 1) + 8 * k * nrow + 8 * k * ncol
 
 
+DUMP_BYTES = 48 << 20         # --dump-outputs: bytes of all the files of one run together
+DUMP_SEED = 0x5EED00D0
+
+
+def sample_index(n, m):
+    """the m of n elements a dump keeps: seeded, ascending, the same in every run"""
+    import numpy as np
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+
+
+def dump_outputs(dirpath, arrays):
+    """--dump-outputs DIR: `arrays` (name -> device tensor, what the timed step returned) as DIR/<name>.npy in float64; an array
+    larger than its share of DUMP_BYTES keeps the elements sample_index picks from it, flattened in row-major order"""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    cap = DUMP_BYTES // 8 // max(1, len(arrays))
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > cap:
+            flat = flat[torch.from_numpy(sample_index(flat.numel(), cap)).to(flat.device)]
+        np.save(os.path.join(dirpath, name + ".npy"), flat.to(torch.float64).cpu().numpy())
+
+
 # ------------------------------------------------------------------------------------------------------------
 # CPU baselines (the ONLY place bench.py touches oracle/: the checker timed as the reported baseline, never the product)
 # ------------------------------------------------------------------------------------------------------------
@@ -546,7 +578,7 @@ def _live_pmc_traffic(args, workload, kernels):
         try:
             cmd = [exe, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", tmp, "-o", "p", "--", "python3",
                    os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "3", "--warmup", "1", "--rows", str(args.rows), "--per-row", str(args.per_row),
-                   "--c5-rows", str(args.c5_rows), "--lean", "--no-cpu-baseline", "--no-reproducible-cost"]
+                   "--c5-rows", str(args.c5_rows), "--full", "--lean", "--no-cpu-baseline", "--no-reproducible-cost"]
             env = dict(os.environ, TMPDIR="/tmp")
             for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
                 env.pop(k, None)
@@ -577,7 +609,8 @@ def _live_pmc_traffic(args, workload, kernels):
         tmp = tempfile.mkdtemp(prefix="fs_trace_", dir="/tmp")
         try:
             cmd = [exe, "--kernel-trace", "--output-format", "csv", "-d", tmp, "-o", "p", "--", "python3", os.path.join(ROOT, "bench.py"), "--workload", workload,
-                   "--steps", "10", "--warmup", "2", "--rows", str(args.rows), "--per-row", str(args.per_row), "--lean", "--no-cpu-baseline", "--no-reproducible-cost"]
+                   "--steps", "10", "--warmup", "2", "--rows", str(args.rows), "--per-row", str(args.per_row), "--full", "--lean", "--no-cpu-baseline",
+                   "--no-reproducible-cost"]
             env = dict(os.environ, TMPDIR="/tmp")
             for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
                 env.pop(k, None)
@@ -607,7 +640,7 @@ def _live_pmc_traffic(args, workload, kernels):
         "dispatches_averaged": {kn: per_counter["FETCH_SIZE"][kn][1] for kn in kernels},
         "kernel_trace_ms": durations,
         "how": "two children after the timed region: rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) -- python3 bench.py "
-               "--workload %s --steps 3 --warmup 1 --lean; per product: sum over its kernels of the mean per dispatch of 2 x FETCH_SIZE + WRITE_SIZE (KB; "
+               "--workload %s --steps 3 --warmup 1 --full --lean; per product: sum over its kernels of the mean per dispatch of 2 x FETCH_SIZE + WRITE_SIZE (KB; "
                "the x 2 is the gfx950 correction of MI355X_MICROARCH.md); the dispatches include the builder's own timing runs of the same kernels" % workload,
         "seconds": round(time.perf_counter() - t0, 1)}
 
@@ -615,7 +648,7 @@ def _live_pmc_traffic(args, workload, kernels):
 def apply_live_traffic(rec, args, workload, kernels, alg_bytes):
     """replace roofline.traffic (and the ceiling derived from it) by what two rocprofv3 --pmc children of THIS run measure; the value
     of profiles/ stays beside it for comparison; a failure leaves the record as it was and says why"""
-    if getattr(args, "lean", False) or getattr(args, "no_live_traffic", False):
+    if not args.full or getattr(args, "lean", False) or getattr(args, "no_live_traffic", False):
         return
     if "rocprof" in os.environ.get("LD_PRELOAD", "") or any(k.startswith(("ROCPROF", "ROCP_TOOL")) for k in os.environ):
         rec["roofline"]["traffic_live_measurement_failed"] = {"error": "not tried: this run is itself under a profiler"}
@@ -967,6 +1000,8 @@ def run_c2(args, prov, world, rank, nccl, strong=False, out=None):
             hz.wait()
 
     elapsed, evs, region_ms = timed_steps(prov, step, lambda: None, args.steps, args.warmup, world, nccl)
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"y": y, "z": z})
     launches = 2 * args.steps
     if not _multi(world):
         avg_ms = region_ms / launches                # ONE event pair around the K steps
@@ -982,7 +1017,7 @@ def run_c2(args, prov, world, rank, nccl, strong=False, out=None):
 
     # the two products apart (outside the timed region): A x and A' u, a few runs each
     split = {}
-    if not _multi(world):
+    if not _multi(world) and args.full:
         e = [prov.event() for _ in range(3)]
         e[0].record()
         for _ in range(5):
@@ -1026,11 +1061,11 @@ def run_c2(args, prov, world, rank, nccl, strong=False, out=None):
                 del xh, yh
             except Exception as ex:
                 split["host_pointer_call"] = {"error": repr(ex)}
-    else:
+    elif _multi(world):
         split = {"A_mul_B_ms": sum(prov.elapsed_ms(e[0], e[1]) for e in evs) / len(evs),
                  "At_mul_B_ms": sum(prov.elapsed_ms(e[2], e[3]) for e in evs) / len(evs)}
     noex = piped = None
-    if _multi(world):   # the same loop without any exchange: what the exchanges cost on top of the local products
+    if _multi(world) and args.full:   # the same loop without any exchange: what the exchanges cost on top of the local products
         noex, _, _ = timed_steps(prov, lambda ev=None: step(None, exchange=False), lambda: None, args.steps, 1, world, nccl)
         # and with the two products of a step treated as what BASELINE config 2 defines -- INDEPENDENT (x and u are given vectors):
         # y's exchange then runs under the local product of A' u, and only the end of the step waits for both vectors.  Reported
@@ -1050,32 +1085,34 @@ def run_c2(args, prov, world, rank, nccl, strong=False, out=None):
     # self-check outside the timed region (no oracle here: that is the tests' job): the products the timed loop left in
     # y and z against the storage-order chunk-streaming kernel on the same operands, and, at N > 1, every rank holding
     # the same gathered y / z
-    self_check = {}
-    try:
-        if _multi(world):
-            step(None)                                                # y, z of a complete step (the no-exchange loop ran last)
-        y_ref = prov.empty(n_local)
-        prov.spmv_strict(A, y_ref, x)
-        self_check["A_mul_B_max_abs_diff_vs_storage_order_kernel"] = float((y[lo:lo + n_local] - y_ref).abs().max())
-        if z_scheme == "gather":
-            z_ref = prov.empty(cb[rank + 1] - cb[rank])
-            prov.spmv_strict(At, z_ref, u)
-            dz = float((z[cb[rank]:cb[rank + 1]] - z_ref).abs().max()) if z_ref.numel() else 0.0
-        else:
-            z_ref = prov.empty(ncol)
-            prov.spmv_strict(A, z_ref, u[lo:lo + n_local], transposed=True)
+    self_check = None
+    if args.full:
+        self_check = {}
+        try:
             if _multi(world):
-                fsd.all_reduce_sum(z_ref)                             # sum of the ranks' partial products
-            dz = float((z - z_ref).abs().max())
-        self_check["At_mul_B_max_abs_diff_vs_storage_order_kernel"] = dz
-        if _multi(world):
-            self_check["ranks_hold_identical_y_and_z"] = _same_on_all_ranks([float(y.sum()), float(z.sum())], cdev)
-        self_check["ok"] = bool(self_check["A_mul_B_max_abs_diff_vs_storage_order_kernel"] <= 1e-11 and
-                                dz <= 1e-11 * max(1, world if z_scheme == "reduce" else 8) and
-                                self_check.get("ranks_hold_identical_y_and_z", True))
-        del y_ref, z_ref
-    except Exception as ex:   # a failed check must show in the line, not kill it
-        self_check = {"ok": False, "error": repr(ex)}
+                step(None)                                                # y, z of a complete step (the no-exchange loop ran last)
+            y_ref = prov.empty(n_local)
+            prov.spmv_strict(A, y_ref, x)
+            self_check["A_mul_B_max_abs_diff_vs_storage_order_kernel"] = float((y[lo:lo + n_local] - y_ref).abs().max())
+            if z_scheme == "gather":
+                z_ref = prov.empty(cb[rank + 1] - cb[rank])
+                prov.spmv_strict(At, z_ref, u)
+                dz = float((z[cb[rank]:cb[rank + 1]] - z_ref).abs().max()) if z_ref.numel() else 0.0
+            else:
+                z_ref = prov.empty(ncol)
+                prov.spmv_strict(A, z_ref, u[lo:lo + n_local], transposed=True)
+                if _multi(world):
+                    fsd.all_reduce_sum(z_ref)                             # sum of the ranks' partial products
+                dz = float((z - z_ref).abs().max())
+            self_check["At_mul_B_max_abs_diff_vs_storage_order_kernel"] = dz
+            if _multi(world):
+                self_check["ranks_hold_identical_y_and_z"] = _same_on_all_ranks([float(y.sum()), float(z.sum())], cdev)
+            self_check["ok"] = bool(self_check["A_mul_B_max_abs_diff_vs_storage_order_kernel"] <= 1e-11 and
+                                    dz <= 1e-11 * max(1, world if z_scheme == "reduce" else 8) and
+                                    self_check.get("ranks_hold_identical_y_and_z", True))
+            del y_ref, z_ref
+        except Exception as ex:   # a failed check must show in the line, not kill it
+            self_check = {"ok": False, "error": repr(ex)}
     if out is not None:
         out["y"], out["z"], out["bounds"], out["z_scheme"] = y, z, bounds, z_scheme
 
@@ -1083,7 +1120,7 @@ def run_c2(args, prov, world, rank, nccl, strong=False, out=None):
     # have a fixed order -- since round 3 the two-pass pair itself with a pass 2 that walks a panel's products in stream order, one
     # wave per panel (the default pass 2 adds with sixteen waves in arrival order)
     repro = None
-    if not _multi(world) and hasattr(prov, "capi") and not args.no_reproducible_cost:
+    if not _multi(world) and hasattr(prov, "capi") and args.full and not args.no_reproducible_cost:
         repro = fixed_order_cost(prov, prov.capi, lambda: A.spmv(y, x, prov.stream()), lambda: A.kernel_name(),
                                  "the same handle with option reproducible = 1: pass 2 of the two-pass pair then runs one wave per panel "
                                  "and adds in stream order (bit-identical run to run); ten products each")
@@ -1096,7 +1133,7 @@ def run_c2(args, prov, world, rank, nccl, strong=False, out=None):
                                           "avg_local_product_ms": avg_ms})
     if rank != 0:
         return None
-    stream_gbs = stream_probe(prov) if hasattr(prov, "torch") else None
+    stream_gbs = stream_probe(prov) if hasattr(prov, "torch") and args.full else None
     kname = prov.kernel_name(A)
     kname_t = prov.kernel_name(At) if z_scheme == "gather" else prov.kernel_name(A, True)
     F8 = 8.0 * ncol
@@ -1118,28 +1155,29 @@ def run_c2(args, prov, world, rank, nccl, strong=False, out=None):
         "scaling": "strong" if (strong and _multi(world)) else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": what,
                    "rows_per_gpu": n_local, "nnz_per_gpu": nnz_local, "parallelism": "rows x%d" % world,
-                   "pct_of_hbm_peak": 100.0 * value / (HBM_PEAK_GBS * world),
-                   "stream_read_GBs_measured": stream_gbs,
-                   "pct_of_measured_stream_read": 100.0 * achieved / stream_gbs if stream_gbs else None,
-                   "A_mul_B_ms": split["A_mul_B_ms"], "At_mul_B_ms": split["At_mul_B_ms"],
-                   "per_launch_ms": split.get("per_launch_ms"), "host_pointer_call": split.get("host_pointer_call"),
-                   "self_check": self_check,
-                   "kernel_A": kname, "kernel_At": kname_t,
-                   "builder_timed_ms_A": prov.candidate_ms(A),
-                   "builder_timed_ms_At": prov.candidate_ms(At) if z_scheme == "gather" else prov.candidate_ms(A, True)},
+                   "pct_of_hbm_peak": 100.0 * value / (HBM_PEAK_GBS * world)},
         "roofline": _roofline(_klabel(kname, kname_t), achieved, traffic, bytes_per_launch, avg_ms, launches,
                               "profiles/traffic_spmv_%s.json" % kname.replace("-", "_")),
     }
+    if args.full or _multi(world):          # (at N > 1 the two products' times come from the timed steps' own events)
+        rec["config"].update({"A_mul_B_ms": split["A_mul_B_ms"], "At_mul_B_ms": split["At_mul_B_ms"]})
+    if args.full:
+        rec["config"].update({"stream_read_GBs_measured": stream_gbs,
+                              "pct_of_measured_stream_read": 100.0 * achieved / stream_gbs if stream_gbs else None,
+                              "per_launch_ms": split.get("per_launch_ms"), "host_pointer_call": split.get("host_pointer_call"),
+                              "self_check": self_check})
+    rec["config"].update({"kernel_A": kname, "kernel_At": kname_t, "builder_timed_ms_A": prov.candidate_ms(A),
+                          "builder_timed_ms_At": prov.candidate_ms(At) if z_scheme == "gather" else prov.candidate_ms(A, True)})
     if repro is not None:
         rec["config"]["fixed_order_sums"] = repro
         rec["config"]["reproducible_cost_pct"] = repro.get("reproducible_cost_pct")
-    if hasattr(A, "build_ms"):
+    if hasattr(A, "build_ms") and args.full:
         rec["config"]["one_time"] = one_time_costs(
             [("A", A, False), ("At", At, False) if z_scheme == "gather" else ("At", A, True)],
             "device arrays in (borrowed in place: phase 0 is validation only; a drop-in caller adds the PCIe upload of 12 B per entry); "
             "A' = fs_matrix_build_transpose (device sort by column) or, at N > 1, this rank's row shard of A' from exchanged entries; "
             "one step = A x + A' u")
-    if not _multi(world) and not strong and n_global == 10_000_000 and per == 16 and not getattr(args, "lean", False):
+    if not _multi(world) and not strong and n_global == 10_000_000 and per == 16 and args.full and not getattr(args, "lean", False):
         rec["roofline"].update(config2_bound(bytes_per_launch, prov))
     if not _multi(world) and not strong and kname == "two-pass" and kname_t == "two-pass" and hasattr(prov, "capi"):
         apply_live_traffic(rec, args, "c2", ("fs::spmv_expand_kernel", "fs::spmv_reduce_"), bytes_per_launch)
@@ -1167,7 +1205,7 @@ def run_c2(args, prov, world, rank, nccl, strong=False, out=None):
         rec["aggregate_frac_of_hbm_peak"] = value / (HBM_PEAK_GBS * world)
         if fault:
             rec["exchange_fault"] = fault
-    if not _multi(world) and not args.no_cpu_baseline and hasattr(prov, "capi"):
+    if not _multi(world) and args.full and not args.no_cpu_baseline and hasattr(prov, "capi"):
         try:
             rec["cpu_baseline"] = cpu_baseline_c2(n_local, ncol, per)
         except Exception as ex:  # the baseline is a reported extra; its failure must not hide the GPU number
@@ -1210,7 +1248,25 @@ def run_c3(args, prov, world, rank, nccl):
         At.spmv(z, u, st)
 
     elapsed, _, region_ms = timed_steps(prov, step, lambda: None, args.steps, args.warmup, 1, nccl)
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"y": y, "z": z})
     avg_ms = region_ms / (2 * args.steps)            # ONE event pair around the K steps
+    bpl = (bytes_a + bytes_t) / 2.0
+    achieved = bpl / (avg_ms * 1e-3) / 1e9
+    value = (bytes_a + bytes_t) * args.steps / elapsed / 1e9
+    ka_name, kt_name = A.kernel_name(), At.kernel_name()
+    rec = {
+        "metric": "binary SpMV (A_mul_B + At_mul_B) effective GB/s (% HBM3E peak)", "value": value, "unit": "GB/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "BASELINE config 3: SparseBinaryMatrix %d x %d, %d nnz/row, COO -> A_mul_B + At_mul_B, "
+                               "integer-valued x" % (nrow, ncol, per)},
+        "roofline": _roofline(_klabel(ka_name, kt_name), achieved, _traffic((ka_name,), "c3", nrow, per), bpl, avg_ms,
+                              2 * args.steps, "profiles/traffic_c3_%s.json" % ka_name.replace("-", "_")),
+    }
+    if not args.full:
+        rec["config"].update({"kernel_A": ka_name, "kernel_At": kt_name})
+        return rec
     e = [prov.event() for _ in range(3)]             # the two products apart, outside the timed region
     e[0].record()
     for _ in range(5):
@@ -1221,9 +1277,6 @@ def run_c3(args, prov, world, rank, nccl):
     e[2].record()
     prov.synchronize()
     ka, kt = [prov.elapsed_ms(e[0], e[1]) / 5], [prov.elapsed_ms(e[1], e[2]) / 5]
-    bpl = (bytes_a + bytes_t) / 2.0
-    achieved = bpl / (avg_ms * 1e-3) / 1e9
-    value = (bytes_a + bytes_t) * args.steps / elapsed / 1e9
     # self-check: integer data, so the storage-order kernel must give the same bits
     sc = {}
     try:
@@ -1244,7 +1297,6 @@ def run_c3(args, prov, world, rank, nccl):
         sc["ok"] = all(sc.values())
     except Exception as ex:
         sc = {"ok": False, "error": repr(ex)}
-    ka_name, kt_name = A.kernel_name(), At.kernel_name()
     repro = None
     if not args.no_reproducible_cost:
         xs_, us_ = prov.sin_vector(ncol, 7.0, 0.3), prov.sin_vector(nrow, 11.0, -0.2)      # non-integer data: the order matters
@@ -1265,21 +1317,12 @@ def run_c3(args, prov, world, rank, nccl):
             finally:
                 capi.set_option("reproducible", 0)
         del xs_, us_
-    rec = {
-        "metric": "binary SpMV (A_mul_B + At_mul_B) effective GB/s (% HBM3E peak)", "value": value, "unit": "GB/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "BASELINE config 3: SparseBinaryMatrix %d x %d, %d nnz/row, COO -> A_mul_B + At_mul_B, "
-                               "integer-valued x" % (nrow, ncol, per),
-                   "A_mul_B_ms": sum(ka) / len(ka), "At_mul_B_ms": sum(kt) / len(kt),
-                   "A_mul_B_GBs": bytes_a / (sum(ka) / len(ka) * 1e-3) / 1e9,
-                   "At_mul_B_GBs": bytes_t / (sum(kt) / len(kt) * 1e-3) / 1e9,
-                   "device_coo_to_csr_and_format_s": {"A": t_build_a, "At": t_build_t},
-                   "kernel_A": ka_name, "kernel_At": kt_name,
-                   "builder_timed_ms_A": A.candidate_ms(), "builder_timed_ms_At": At.candidate_ms(), "self_check": sc},
-        "roofline": _roofline(_klabel(ka_name, kt_name), achieved, _traffic((ka_name,), "c3", nrow, per), bpl, avg_ms,
-                              2 * args.steps, "profiles/traffic_c3_%s.json" % ka_name.replace("-", "_")),
-    }
+    rec["config"].update({"A_mul_B_ms": sum(ka) / len(ka), "At_mul_B_ms": sum(kt) / len(kt),
+                          "A_mul_B_GBs": bytes_a / (sum(ka) / len(ka) * 1e-3) / 1e9,
+                          "At_mul_B_GBs": bytes_t / (sum(kt) / len(kt) * 1e-3) / 1e9,
+                          "device_coo_to_csr_and_format_s": {"A": t_build_a, "At": t_build_t},
+                          "kernel_A": ka_name, "kernel_At": kt_name,
+                          "builder_timed_ms_A": A.candidate_ms(), "builder_timed_ms_At": At.candidate_ms(), "self_check": sc})
     if repro is not None:
         rec["config"]["fixed_order_sums"] = repro
         rec["config"]["reproducible_cost_pct"] = repro.get("reproducible_cost_pct")
@@ -1327,9 +1370,21 @@ def run_c4(args, prov, world, rank, nccl):
         A.spmm(Y, X, k, st)
 
     elapsed, _, region_ms = timed_steps(prov, step, lambda: None, args.steps, args.warmup, 1, nccl)
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"Y": Y})
     avg_ms = region_ms / args.steps
     achieved = nbytes / (avg_ms * 1e-3) / 1e9
     value = nbytes * args.steps / elapsed / 1e9
+    roofline = _roofline("fs::spmm_kernel<valued, 5> (32 lanes per row)" if args.spmm_kernel != 4 else
+                         "fs::spmm_mfma_kernel<valued>", achieved, _traffic(("spmm_k32",), "c4", n, per), nbytes, avg_ms,
+                         args.steps, "profiles/traffic_c4_spmm_k32.json")
+    what = "BASELINE config 4: CSR %d x %d, %d nnz/row, times X %d x %d row-major (csr_A_mul_Bn)" % (n, n, per, n, k)
+    if not args.full:
+        capi.set_option("spmm_kernel", 0)
+        return {"metric": "fp64 CSR SpMM (k = 32) effective GB/s (% HBM3E peak)", "value": value, "unit": "GB/s", "n_gpus": 1,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+                "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+                "config": {"workload": what, "spmm_kernel_option": args.spmm_kernel}, "roofline": roofline}
     sc = {}
     try:     # column j of Y against the single-vector product of column j of X, both in storage order: identical bits
         yj = torch.empty(n, dtype=torch.float64, device=dev)
@@ -1371,16 +1426,14 @@ def run_c4(args, prov, world, rank, nccl):
         "metric": "fp64 CSR SpMM (k = 32) effective GB/s (% HBM3E peak)", "value": value, "unit": "GB/s", "n_gpus": 1,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "BASELINE config 4: CSR %d x %d, %d nnz/row, times X %d x %d row-major (csr_A_mul_Bn)" % (n, n, per, n, k),
+        "config": {"workload": what,
                    "gather_traffic_model_bytes": n * per * 8 * k, "flops_per_product": 2 * k * n * per,
                    "small_k": small, "spmm_kernel_option": args.spmm_kernel,
                    "mfma": "none: the product's k = 32 kernel is VALU (profiles/r02_c4_*: SQ_INSTS_VALU_MFMA_F64 = 0); "
                            "--spmm-kernel 4 runs the v_mfma_f64_16x16x4_f64 experiment" if args.spmm_kernel != 4 else
                            "v_mfma_f64_16x16x4_f64 row kernel (1/16 of each instruction's multiply-adds useful)",
                    "self_check": sc},
-        "roofline": _roofline("fs::spmm_kernel<valued, 5> (32 lanes per row)" if args.spmm_kernel != 4 else
-                              "fs::spmm_mfma_kernel<valued>", achieved, _traffic(("spmm_k32",), "c4", n, per), nbytes, avg_ms,
-                              args.steps, "profiles/traffic_c4_spmm_k32.json"),
+        "roofline": roofline,
     }
     if args.spmm_kernel != 4:
         apply_live_traffic(rec, args, "c4", ("fs::spmm_kernel<true, 5>",), nbytes)
@@ -1392,7 +1445,7 @@ def run_c4(args, prov, world, rank, nccl):
     released = A.release_prepared(0)
     rec["config"]["hbm_held_after_release_prepared_bytes"] = dict(zip(("csr_and_schedule", "kept_single_vector_copy", "k_column_copies_and_scratch"),
                                                                       A.device_bytes()), released=released)
-    if not args.no_cpu_baseline:
+    if not args.no_cpu_baseline:      # (a plain run returned above)
         try:
             rec["cpu_baseline"] = cpu_baseline_c4(n, per, k, sample_rows=args.cpu_sample_rows or 400_000)
         except Exception as ex:
@@ -1535,6 +1588,8 @@ def run_c5(args, prov, world, rank, nccl, out=None):
                 hz.wait()
 
     elapsed, evs, region_ms = timed_steps(prov, step, lambda: None, args.steps, args.warmup, world, nccl)
+    if rank == 0 and getattr(args, "dump_outputs", None):
+        dump_outputs(args.dump_outputs, {"y": y})
     local_ms = region_ms / args.steps if not _multi(world) else sum(prov.elapsed_ms(e[0], e[1]) for e in evs) / len(evs)
 
     def all_ranks(v):
@@ -1546,9 +1601,9 @@ def run_c5(args, prov, world, rank, nccl, out=None):
     bytes_all = all_ranks(bytes_local)
     value = bytes_all * args.steps / elapsed / 1e9
     noex = with_t = None
-    if _multi(world):   # the same loop without any exchange: what the all-gather costs on top of the local products
+    if _multi(world) and args.full:   # the same loop without any exchange: what the all-gather costs on top of the local products
         noex, _, _ = timed_steps(prov, lambda ev=None: step(None, exchange=False), lambda: None, args.steps, 1, world, nccl)
-    if opt is not None:
+    if opt is not None and args.full:
         el_t, evs_t, _ = timed_steps(prov, lambda ev=None: step(ev, transpose=True), lambda: None, args.steps, 1, world, nccl)
         noex_t, _, _ = timed_steps(prov, lambda ev=None: step(None, exchange=False, transpose=True), lambda: None, args.steps, 1,
                                    world, nccl)
@@ -1559,24 +1614,28 @@ def run_c5(args, prov, world, rank, nccl, out=None):
                   "pct_of_hbm_peak": 100.0 * bytes_both * args.steps / el_t / 1e9 / (HBM_PEAK_GBS * world),
                   "step": "y = A x, then z = A' u on row shards of A' (all-gather of y and of z inside the products)"}
 
-    sc = {}
-    try:
-        if _multi(world):
-            step(None, transpose=opt is not None)     # complete vectors (a no-exchange loop ran last)
-        if out is not None:
-            out["y"], out["z"], out["bounds"] = y, (z if opt is not None else None), bounds
-        if _multi(world):
-            sc["ranks_hold_identical_y"] = _same_on_all_ranks([float(y.sum())], cdev)
-        y_ref = prov.empty(n_local)
-        prov.spmv_strict(A, y_ref, x)
-        mine_y = y[lo:hi] if _multi(world) else y
-        lens = (rp[1:] - rp[:-1]).to(torch.float64).clamp(min=1.0)
-        sc["rows_within_1e-12_x_row_length_of_storage_order_kernel"] = bool(((mine_y - y_ref).abs() <= 1e-12 * lens).all())
-        sc["ok"] = all(v for v in sc.values())
-    except Exception as ex:
-        sc = {"ok": False, "error": repr(ex)}
+    sc = None
+    if args.full:
+        sc = {}
+        try:
+            if _multi(world):
+                step(None, transpose=opt is not None)     # complete vectors (a no-exchange loop ran last)
+            if out is not None:
+                out["y"], out["z"], out["bounds"] = y, (z if opt is not None else None), bounds
+            if _multi(world):
+                sc["ranks_hold_identical_y"] = _same_on_all_ranks([float(y.sum())], cdev)
+            y_ref = prov.empty(n_local)
+            prov.spmv_strict(A, y_ref, x)
+            mine_y = y[lo:hi] if _multi(world) else y
+            lens = (rp[1:] - rp[:-1]).to(torch.float64).clamp(min=1.0)
+            sc["rows_within_1e-12_x_row_length_of_storage_order_kernel"] = bool(((mine_y - y_ref).abs() <= 1e-12 * lens).all())
+            sc["ok"] = all(v for v in sc.values())
+        except Exception as ex:
+            sc = {"ok": False, "error": repr(ex)}
+    elif out is not None:
+        out["y"], out["z"], out["bounds"] = y, None, bounds
     repro = None
-    if not _multi(world) and hasattr(prov, "capi") and not args.no_reproducible_cost:
+    if not _multi(world) and hasattr(prov, "capi") and args.full and not args.no_reproducible_cost:
         repro = fixed_order_cost(prov, prov.capi, lambda: prov.spmv(A, y, x), lambda: prov.kernel_name(A),
                                  "the same handle with option reproducible = 1: one-wave pass 2 in stream order, the long rows each with "
                                  "one wave of a workgroup and the workgroups' sums added in workgroup order; ten products each")
@@ -1592,7 +1651,7 @@ def run_c5(args, prov, world, rank, nccl, out=None):
     # what the handle holds, and what is left once the plain CSR is given back: the products of this matrix run on
     # the kept copy alone; strict_order -- the self-check above -- was the last user of the plain arrays
     release = None
-    if hasattr(A, "release_csr") and not _multi(world):
+    if hasattr(A, "release_csr") and not _multi(world) and args.full:
         try:
             import torch
             before = A.device_bytes()
@@ -1640,17 +1699,19 @@ def run_c5(args, prov, world, rank, nccl, out=None):
                    "local_A_mul_B_ms_rank0": local_ms,
                    "ms_per_step_without_exchanges": noex / args.steps * 1e3 if noex else None,
                    "with_transpose": with_t, "transpose_error": t_err, "kernel": kname,
-                   "builder_timed_ms": prov.candidate_ms(A), "self_check": sc},
+                   "builder_timed_ms": prov.candidate_ms(A)},
         "roofline": _roofline(_klabel(kname), achieved, _traffic((kname,), "c5", n_local, 0) if not _multi(world) else None, bytes_local,
                               local_ms, args.steps, "profiles/traffic_c5_%s.json" % kname.replace("-", "_")),
     }
+    if sc is not None:
+        rec["config"]["self_check"] = sc
     if repro is not None:
         rec["config"]["fixed_order_sums"] = repro
         rec["config"]["reproducible_cost_pct"] = repro.get("reproducible_cost_pct")
     if not _multi(world) and kname == "two-pass" and hasattr(prov, "capi"):
         apply_live_traffic(rec, args, "c5", ("fs::spmv_expand_kernel", "fs::spmv_longrows_kernel", "fs::spmv_reduce_", "fs::tiled_combine_kernel"),
                            bytes_local)
-    if hasattr(A, "build_ms"):
+    if hasattr(A, "build_ms") and args.full:
         rec["config"]["one_time"] = one_time_costs([("A", A, False)], "this rank's shard: device arrays in (borrowed), candidates built and timed")
     if release is not None:
         rec["config"]["release_csr"] = release
@@ -1662,7 +1723,7 @@ def run_c5(args, prov, world, rank, nccl, out=None):
         rec["aggregate_frac_of_hbm_peak"] = value / (HBM_PEAK_GBS * world)
         if fault:
             rec["exchange_fault"] = fault
-    if not _multi(world) and not args.no_cpu_baseline and hasattr(prov, "capi"):
+    if not _multi(world) and args.full and not args.no_cpu_baseline and hasattr(prov, "capi"):
         try:
             rec["cpu_baseline"] = cpu_baseline_c5(lo, ncol, sample_rows=args.cpu_sample_rows or 1_000_000)
         except Exception as ex:
@@ -1924,7 +1985,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="all", choices=["all", "c2", "c3", "c4", "c5"],
-                    help="all (default): the config-2 line with the other BASELINE configs under its key \"also\"")
+                    help="all (default): the config-2 line, with --full the other BASELINE configs under its key \"also\"")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the timed steps: self-checks, per-product / per-launch timings, probes and bounds, live "
+                         "PMC traffic, fixed-order cost, CPU baselines and, with --workload all, the other workloads (default: the "
+                         "timed steps and the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the vectors the last step computed as DIR/<name>.npy (float64, 48 MB at most: "
+                         "larger vectors as a fixed seeded sample of their elements)")
     ap.add_argument("--rows", type=int, default=10_000_000, help="rows per GPU (config 2 / 3 / 4: 10M)")
     ap.add_argument("--per-row", type=int, default=16)
     ap.add_argument("--c5-rows", type=int, default=100_000_000, help="rows = columns of the config-5 matrix")
@@ -1943,7 +2011,7 @@ def main():
                          "the timed loops) print ONE JSON line with \"error\" and the failing part / rank / row range and exit 3; default: "
                          "say so in the line (exchange_fault), switch every rank to the conservative exchange and measure that")
     ap.add_argument("--lean", action="store_true",
-                    help="profiling runs (tools/profile.sh): the timed products and the self-check only -- no per-launch events, no "
+                    help="with --full, profiling runs (tools/profile.sh): the timed products and the self-check only -- no per-launch events, no "
                          "host-pointer call, no probes, so that the per-kernel means of a PMC pass are the full products'")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-traffic", action="store_true",
@@ -2020,7 +2088,7 @@ def main():
         if _multi(world) and not os.environ.get("FS_BENCH_WATCHDOG"):
             import faulthandler
             faulthandler.cancel_dump_traceback_later()      # the headline exists: from here on the budget watchdog prints it
-        if args.workload == "all":
+        if args.workload == "all" and args.full:
             also, state = [], {}
             budget = float(os.environ.get("FS_BENCH_BUDGET_S", "480")) - (time.perf_counter() - t_start)
             dog = budget_watchdog(max(budget, 5.0), rank, rec, also, state)

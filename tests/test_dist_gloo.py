@@ -331,7 +331,7 @@ def _c5_worker(rank, world, port, n, ret):
         from oracle import pyoracle as O
         from oracle import pysynth
         prov = OracleProvider()
-        args = argparse.Namespace(c5_rows=n, steps=2, warmup=1, transpose=True, parts=3, no_cpu_baseline=True, cpu_sample_rows=0)
+        args = argparse.Namespace(c5_rows=n, steps=2, warmup=1, transpose=True, parts=3, no_cpu_baseline=True, cpu_sample_rows=0, full=True)
         out = {}
         rec = bench.run_c5(args, prov, world, rank, False, out=out)
         # the whole matrix on every rank (it is small here) with the same generator: the gathered y must be the
@@ -379,7 +379,8 @@ def _c2_worker(rank, world, port, z_scheme, ret):
         n, per = 2500, 16
         args = argparse.Namespace(rows=n, per_row=per, c5_rows=9000, steps=2, warmup=1, transpose=False, strong=False, parts=3,
                                   z_scheme=z_scheme, no_cpu_baseline=True, no_reproducible_cost=True, cpu_sample_rows=0,
-                                  spmm_kernel=0, exchange="direct" if z_scheme == "reduce" else "allgather")   # both ways of shipping a part
+                                  spmm_kernel=0, exchange="direct" if z_scheme == "reduce" else "allgather",   # both ways of shipping a part
+                                  full=True)
         out = {}
         rec = bench.run_c2(args, prov, world, rank, False, out=out)
         # weak scaling: the global matrix is (world * n) x n with the same generator row by row; y and z must be the oracle's
@@ -428,7 +429,7 @@ def _fault_worker(rank, world, port, strict, ret):
         prov = OracleProvider()
         args = argparse.Namespace(rows=2500, per_row=16, c5_rows=9000, steps=2, warmup=1, transpose=False, strong=False, parts=3,
                                   z_scheme="gather", no_cpu_baseline=True, no_reproducible_cost=True, cpu_sample_rows=0,
-                                  spmm_kernel=0, exchange="allgather", strict_exchange=strict)
+                                  spmm_kernel=0, exchange="allgather", strict_exchange=strict, full=True)
         try:
             rec = bench.run_c2(args, prov, world, rank, False)
             info = None

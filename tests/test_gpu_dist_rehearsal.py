@@ -167,7 +167,7 @@ def test_bench_runs_its_multi_rank_plan_on_one_rccl_rank():
     env = dict(os.environ, FS_BENCH_FORCE_MULTI="1", FS_DIST_FORCE_COLLECTIVES="1", FS_BENCH_WATCHDOG="300")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full",
                         "--rows", "2000000", "--c5-rows", "3000000"], env=env, capture_output=True, text=True, timeout=400)
     assert p.returncode == 0, p.stderr[-3000:]
     rec = json.loads(p.stdout.strip().splitlines()[-1])

@@ -13,9 +13,9 @@ run() {  # name, rocprof args...
     > "$out/${tag}_$name.log" 2>&1
   echo "$tag $name rc $?"
 }
-BENCH_ARGS=("$@" --steps 10 --no-cpu-baseline)
+BENCH_ARGS=("$@" --full --steps 10 --no-cpu-baseline)
 run stats --stats
-BENCH_ARGS=("$@" --steps 5 --warmup 1 --no-cpu-baseline)
+BENCH_ARGS=("$@" --full --steps 5 --warmup 1 --no-cpu-baseline)
 run fetch --pmc FETCH_SIZE
 run write --pmc WRITE_SIZE
 run tcc --pmc TCC_HIT_sum TCC_MISS_sum

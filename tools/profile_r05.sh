@@ -6,6 +6,6 @@ set -u
 out=gpurun_out/r5p
 mkdir -p $out
 for w in ${@:-c2 c3 c4 c5}; do
-  bash tools/profile.sh r05_$w $out bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline --no-reproducible-cost --lean
+  bash tools/profile.sh r05_$w $out bench.py --workload $w --full --steps 10 --warmup 2 --no-cpu-baseline --no-reproducible-cost --lean
 done
 ls -la $out
