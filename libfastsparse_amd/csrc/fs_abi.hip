@@ -201,6 +201,12 @@ int fs_get_option(const char *name)
   if (name && !strcmp(name, "cg_fixed_order")) return fs::options().cg_fixed_order;
   if (name && !strcmp(name, "dist_cg_scheme")) return fs::options().dist_cg_scheme;
   if (name && !strcmp(name, "release_csr")) return fs::options().release_csr;
+  if (name && !strcmp(name, "tiled_flags")) return fs::options().tiled_flags;
+  if (name && !strcmp(name, "bin_wgs")) return fs::options().bin_wgs;
+  if (name && !strcmp(name, "bin_flags")) return fs::options().bin_flags;
+  if (name && !strcmp(name, "bin_rows")) return fs::options().bin_rows;
+  if (name && !strcmp(name, "long_min_len")) return fs::options().long_min_len;
+  if (name && !strcmp(name, "long_geometry")) return fs::options().long_geometry;
   return FS_ERR_ARG;
 }
 

@@ -27,12 +27,17 @@ class Case:
         self.rows, self.cols, self.vals = rows, cols, vals
         self.xs = xs                      # {tag: x over columns}
         self.block_sizes, self.colblocks, self.kmax = block_sizes, colblocks, kmax
+        self.cg = True                    # run the solvers too (their iterates are not exact: tests/_exact.py cases turn them off)
 
     def xt(self, tag):
         """matching vector over rows for the transposed products"""
         if tag == "int":
             return S.x_int(77, self.nrow)
         return S.x_sin(self.nrow, 11.0, -0.2)
+
+    def X(self, k):
+        """right-hand sides of the k-column products, row-major ncol x k"""
+        return S.X_sin(self.ncol, k)
 
 
 def _kat_sbm():
@@ -120,22 +125,22 @@ def run_case(be, case, tags=None, light=False, absolute=False):
     for name, k in BIN_SPMM + BIN_SPMM_VAR:
         if k > c.kmax:
             continue
-        X = ab(S.X_sin(c.ncol, k))
+        X = ab(c.X(k))
         res[f"{name}/k{k}"] = be.csr_mul_n(c.nrow, c.ncol, c.rows, c.cols, None, X, k, name)
     bs = c.block_sizes[0]
     for name, k in [("bsbm_A_mul_B2", 2), ("bsbm_A_mul_B4", 4), ("bsbm_A_mul_Bn", 3)]:
-        X = ab(S.X_sin(c.ncol, k))
+        X = ab(c.X(k))
         res[f"{name}/bs{bs}"] = be.blocked_mul(c.nrow, c.ncol, c.rows, c.cols, None, bs, X, k, name)
     if c.vals is not None:
         for k in VAL_SPMM:
             if k > c.kmax:
                 continue
-            X = ab(S.X_sin(c.ncol, k))
+            X = ab(c.X(k))
             res[f"csr_A_mul_Bn/k{k}"] = be.csr_mul_n(c.nrow, c.ncol, c.rows, c.cols, cvals, X, k, "csr_A_mul_Bn")
     # --- the consumers of the path: CG on (A'A + lambda I), one and two right-hand sides ---
     # (F >= 16: on a 3-column matrix the second 2-column search block is rank deficient and the 2x2 solves of
     #  bsbm_cg2 divide by rounding noise -- in the reference too)
-    if 16 <= c.ncol <= 2100 and hasattr(be, "cg") and not absolute:
+    if 16 <= c.ncol <= 2100 and c.cg and hasattr(be, "cg") and not absolute:
         b1, b2 = cg_rhs(c.ncol)
         x, it = be.cg(c.nrow, c.ncol, c.rows, c.cols, b1, CG_LAMBDA, CG_TOL, False)
         res["bsbm_cg/x"], res["bsbm_cg/iter"] = x, np.array([float(it)])

@@ -2,7 +2,8 @@
 library reads them once): EVERY reference-named product entry point -- A_mul_B, At_mul_B, sdm_*, bsbm_*, bsdm_*, bcsr_*, csr_*,
 cbcsr_*, bcsr_AA_mul_B, bsbm_cg / bsbm_cg2 -- through HipDropinBackend on the row-sharded path (three virtual ranks on one GPU),
 against the goldens made from the real reference, with the bars of the single-GPU run (tests/test_gpu_parity.py:_check).
-Modes: golden (host vectors), resident (x / y in HBM: nothing may be staged through the host)."""
+Modes: golden (host vectors), resident (x / y in HBM: nothing may be staged through the host), exact (tests/_exact.py data, bit for
+bit against the exact reference)."""
 import ctypes as C
 import os
 import sys
@@ -239,5 +240,24 @@ def fullsize():
     L.fs_release_all()
 
 
-{"golden": golden, "resident": resident, "edges": edges, "fullsize": fullsize}[sys.argv[1].split("+")[0]]()
+def exact():
+    """the exactly summable data of tests/_exact.py through every entry point on the row-sharded path: every output the exact
+    reference's bits (any order of additions across ranks gives them), y pre-poisoned, and from sharded products"""
+    import _exact as E
+    be = H.HipDropinBackend()
+    for d in (E.wide_range(), E.long_rows(nrow=1500), E.subnormal(), E.zeros()):
+        case = d.case()
+        want = _cases.run_case(E.ExactBackend(), case)
+        before = L.fs_debug_dist_products()
+        got = _cases.run_case(be, case)
+        assert got.keys() == want.keys()
+        bad = [f"{k}: {E.first_mismatch(got[k], want[k])}" for k in sorted(got) if not E.bits_equal(got[k], want[k])]
+        assert not bad, (d.name, bad)
+        n = L.fs_debug_dist_products() - before
+        assert n >= len(got) // 2, (d.name, n, len(got))
+        print("exact", d.name, len(got), "outputs,", n, "sharded products", flush=True)
+    L.fs_release_all()
+
+
+{"golden": golden, "resident": resident, "edges": edges, "fullsize": fullsize, "exact": exact}[sys.argv[1].split("+")[0]]()
 print("OK")
