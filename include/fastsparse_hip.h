@@ -76,7 +76,9 @@ int  fs_set_device(int device);
  * are unrestricted.  (fs_spmv_host / fs_spmv_t_host order themselves behind the handle's last device-vector product.)
  * Options are read at the call, on the calling thread, without a lock: set them before other threads create or multiply.
  * "spmm_kernel" (multi-column products: 0 auto, 1 row kernel, 2 k-column two-pass sweep for k = 2..4, 3 one single-vector sweep
- * per column, 4 the v_mfma_f64_16x16x4_f64 experiment), "ata_kernel" (fs_ata_mul: 0 two products, 2 the fused single kernel),
+ * per column, 4 the v_mfma_f64_16x16x4_f64 experiment; "strict_order" wins over every choice: its products run on the row
+ * kernel, 4 included, whose fused multiply-adds would break the storage-order bits), "ata_kernel" (fs_ata_mul: 0 two products,
+ * 2 the fused single kernel),
  * "device_build" (format constructors: 0 host loops, 1 on the device from 4 M entries, 2 on the device always).
  * "tile_split": rows longer than this are cut into virtual rows in the tiled copy (0 = 256).
  * "cg_fixed_order" (default 1; FS_CG_FIXED_ORDER): fs_cg / fs_cg2 / fs_dist_cg run their products with fixed-order sums, as under

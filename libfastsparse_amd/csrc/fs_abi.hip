@@ -427,6 +427,21 @@ int fs_copy_segments(int nseg, const int64_t *table_dev, int64_t max_count, cons
 
 // ---- diagnostics (not part of include/fastsparse_hip.h; used by tools/trace_tiled.py and the tests) --------
 int fs_debug_last_host_path(void) { return fs::last_host_path(); }
+// the plan (fs_matrix_spmm_plan codes) of the last multi-column product launched since the previous call; 0 if none
+int fs_debug_last_spmm_plan(void) { return fs::last_spmm_plan(); }
+// the row kernel of the last multi-column product since the previous call: 1 with 16-byte loads (spmm_wide_kernel), 0 without, -1 none
+int fs_debug_last_spmm_wide(void) { return fs::last_spmm_wide(); }
+
+// the kept tiled copy (LDS-staged or L2-tiled) of A or A': bit 0 it has cut rows (a combine pass follows its kernel), bit 1 chunks
+// share panels (sums go through its scratch vector); FS_ERR_ARG without one
+int fs_debug_tiled_layout(fs_matrix_t A, int transposed)
+{
+  if (!A || (transposed && !A->has_t)) return FS_ERR_ARG;
+  const fs::DeviceCsr &a = transposed ? A->at : A->a;
+  const fs::TiledCsr *T = (a.tiledx && a.tiledx->built) ? a.tiledx : (a.tiled && a.tiled->built) ? a.tiled : nullptr;
+  if (!T) return FS_ERR_ARG;
+  return (T->split ? 1 : 0) | (T->shared ? 2 : 0);
+}
 
 // rows taken out of the two-pass copy (LongRows) and their entries incl. padding; 0 / 0 when the copy has none
 int fs_debug_long_rows(fs_matrix_t A, int transposed, int64_t *out2)

@@ -357,6 +357,7 @@ int spmm_part_bounds(DeviceCsr &A, int k, int nparts, const int **rows_out, cons
 int launch_spmm_part(DeviceCsr &A, double *Y, const double *X, int k, int part, int nparts, hipStream_t s);
 int launch_tiled_combine(int row_end, const int *vfirst, const double *yv, double *y, int ys, int row0, hipStream_t s);   // rows row0 .. row_end
 int launch_strided_copy(int n, const double *v, double *y, int ys, hipStream_t s);
+int launch_zero(void *p, size_t bytes, hipStream_t s);   // a kernel that zeroes whole 4-byte words (products never use hipMemsetAsync)
 int launch_expand_groups(const DeviceCsr &A, const double *x, unsigned g0, unsigned g1, int wgs, hipStream_t s);   // pass 1, groups g0 .. g1
 int launch_reduce_panels(const DeviceCsr &A, double *y, int p0, int p1, hipStream_t s);                             // pass 2, panels p0 .. p1
 int launch_copy_segments(int nseg, const int64_t *tab_dev, int64_t max_count, const double *src, double *dst, hipStream_t s);
@@ -364,6 +365,8 @@ int launch_ata_fused(const DeviceCsr &A, double *y, const double *x, hipStream_t
 // y_host = A x_host: copies and kernels overlapped where the kept copy allows it (two-pass copy without cut rows)
 int spmv_host_vectors(const DeviceCsr &A, HostPipe &H, double *y_host, const double *x_host);
 int last_host_path();
+int last_spmm_plan();   // the plan (kPlan*) of the last multi-column product launched since the previous call, 0 if none
+int last_spmm_wide();   // the row kernel of the last one: 1 with 16-byte loads, 0 without, -1 none since the previous call
 
 // ---- the vector steps of CG (fs_cg.hip) for callers with their own products; every step leaves its dot / norm in red[0]
 constexpr int kCgPartDoubles = 3 * 1024;

@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <vector>
 
@@ -984,8 +985,9 @@ __global__ __launch_bounds__(kBlock) void columns_to_rows_kernel(int64_t n, int 
 //           12.5 ms for any k from 4 to 16; 10 M rows x 16 with X of 131 K rows, k = 8: 3.5 ms in sweeps, 2.05 ms on
 //           the row kernel, X in L2)
 //   plan 6 / 7  k <= 2 strided sweeps of the LDS-staged / L2-tiled kernel
-//   plan 4  the v_mfma_f64_16x16x4_f64 experiment (option spmm_kernel = 4)
-//   plan 1  the row kernel: k >= 5 on two-pass matrices, k > 16, strict_order / reproducible, small matrices
+//   plan 4  the v_mfma_f64_16x16x4_f64 experiment (option spmm_kernel = 4; not under strict_order: fused multiply-adds)
+//   plan 1  the row kernel: k >= 5 on two-pass matrices, k > 16, strict_order (whatever spmm_kernel asks for), a copy that
+//           cannot take fixed-order sums under reproducible, small matrices
 // ------------------------------------------------------------------------------------------
 constexpr int kLdsxSweepMaxK = 16;
 enum { kPlanRow = 1, kPlanBinnedK = 2, kPlanBinnedCols = 3, kPlanMfma = 4, kPlanLdsxColumns = 5, kPlanLdsxStrided = 6,
@@ -1043,7 +1045,8 @@ int spmm_plan(const DeviceCsr &A, int k, int *needs_prepare)
   }
   if (want != 1 && k <= 2 && hx && free_order && ldsx_ok) return kPlanLdsxStrided;
   if (want != 1 && k <= 2 && ht && !o.strict_order && (o.spmv_kernel == 0 || o.spmv_kernel == 6)) return kPlanTiledStrided;
-  return want == 4 ? kPlanMfma : kPlanRow;
+  // (the MFMA experiment fuses multiply and add: never under strict_order, which promises the storage-order bits)
+  return want == 4 && !o.strict_order ? kPlanMfma : kPlanRow;
 }
 
 static int spmm_scratch_alloc(DeviceCsr &A, int k)      // prepare_spmm only
@@ -1059,6 +1062,10 @@ static int spmm_scratch_alloc(DeviceCsr &A, int k)      // prepare_spmm only
   return FS_OK;
 }
 
+static std::atomic<int> g_last_spmm_plan{0}, g_last_spmm_wide{-1};   // diagnostics, read and cleared by the getters below
+int last_spmm_plan() { return g_last_spmm_plan.exchange(0, std::memory_order_relaxed); }
+int last_spmm_wide() { return g_last_spmm_wide.exchange(-1, std::memory_order_relaxed); }
+
 static int launch_spmm_row(const DeviceCsr &A, double *Y, const double *X, int k, hipStream_t s)
 {
   if (int rc = need_plain_csr(A, "the row kernel of multi-column products")) return rc;
@@ -1068,6 +1075,7 @@ static int launch_spmm_row(const DeviceCsr &A, double *Y, const double *X, int k
   // legal, -1 never
   const int wide = options().spmm_wide;
   if (wide >= 0 && (k & 1) == 0 && (wide > 0 || (k >= 4 && k <= 14)) && (((uintptr_t)X | (uintptr_t)Y) & 15) == 0) {
+    g_last_spmm_wide.store(1, std::memory_order_relaxed);
     const int kh = k >> 1;
     const int lg = ceil_log2(kh > 64 ? 64 : kh);
     const int gpb = kBlock >> lg;
@@ -1086,6 +1094,7 @@ static int launch_spmm_row(const DeviceCsr &A, double *Y, const double *X, int k
     FS_HIP(hipGetLastError());
     return FS_OK;
   }
+  g_last_spmm_wide.store(0, std::memory_order_relaxed);
   const int lg = ceil_log2(k > 64 ? 64 : k);
   const int gpb = kBlock >> lg;
   const unsigned grid = (unsigned)(((int64_t)A.nrow + gpb - 1) / gpb);
@@ -1160,7 +1169,9 @@ static int launch_spmm_plan(DeviceCsr &A, int plan, double *Y, const double *X, 
 int launch_spmm(DeviceCsr &A, double *Y, const double *X, int k, hipStream_t s)
 {
   if (A.nrow == 0) return FS_OK;
-  return launch_spmm_plan(A, spmm_plan(A, k, nullptr), Y, X, k, s);
+  const int plan = spmm_plan(A, k, nullptr);
+  g_last_spmm_plan.store(plan, std::memory_order_relaxed);
+  return launch_spmm_plan(A, plan, Y, X, k, s);
 }
 
 // The k-column product in parts: only the one-sweep plan (k = 2, 4 on the k-column two-pass copy) is cut, like the single-vector
@@ -1198,6 +1209,7 @@ int launch_spmm_part(DeviceCsr &A, double *Y, const double *X, int k, int part, 
   const int *rows = nullptr, *units = nullptr;
   int plan = 0;
   if (int rc = spmm_part_bounds(A, k, nparts, &rows, &units, &plan)) return rc;
+  g_last_spmm_plan.store(plan, std::memory_order_relaxed);
   if (!A.partk[k == 4 ? 1 : 0].cut) return part == 0 ? launch_spmm_plan(A, plan, Y, X, k, s) : FS_OK;
   return launch_spmm_binned(A, k == 4 ? *A.binned4 : *A.binned2, Y, X, s, k, k, units[part], units[part + 1], rows[part], rows[part + 1]);
 }

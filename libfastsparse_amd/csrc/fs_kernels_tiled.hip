@@ -731,6 +731,25 @@ int launch_tiled_combine(int row_end, const int *vfirst, const double *yv, doubl
   return FS_OK;
 }
 
+// p[0 .. n) = 0 in 4-byte words: the zeroing a product does on the stream.  A kernel, not hipMemsetAsync: captured into a
+// graph (torch.cuda.graph, hipStreamBeginCapture), a hipMemsetAsync at the head of the graph was seen to leave half of its
+// buffer unzeroed on the second and later replays, with no library code involved; products must stay capturable
+// (tests/test_gpu_spmm_plans.py::test_products_captured_in_a_graph)
+__global__ __launch_bounds__(kBlock) void zero_words_kernel(int64_t n, unsigned *__restrict__ p)
+{
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i < n) p[i] = 0u;
+}
+
+int launch_zero(void *p, size_t bytes, hipStream_t s)
+{
+  const int64_t n = (int64_t)(bytes / 4);        // callers zero doubles and ints: whole words
+  if (n <= 0) return FS_OK;
+  hipLaunchKernelGGL(zero_words_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, n, static_cast<unsigned *>(p));
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
 int launch_strided_copy(int n, const double *v, double *y, int ys, hipStream_t s)
 {
   if (n <= 0) return FS_OK;
@@ -757,8 +776,8 @@ int launch_spmv_tiled(const DeviceCsr &A, const TiledCsr &T, double *y, const do
     // fixed-order sums: the chunks of a panel take turns (a ticket per panel, zeroed here) -- see ldsx_store_slice
     const bool ordered = reproducible_now() && T.orderable;
     if (T.shared) {
-      if (!part) FS_HIP(hipMemsetAsync(T.yv, 0, sizeof(double) * (size_t)A.nrow, s));
-      if (!part && ordered) FS_HIP(hipMemsetAsync(T.ticket, 0, sizeof(int) * (size_t)T.P, s));
+      if (!part) if (int rc = launch_zero(T.yv, sizeof(double) * (size_t)A.nrow, s)) return rc;
+      if (!part && ordered) if (int rc = launch_zero(T.ticket, sizeof(int) * (size_t)T.P, s)) return rc;
       out = T.yv;
     }
     const int ost = T.shared ? 1 : ys;
@@ -816,7 +835,7 @@ int launch_spmv_tiled(const DeviceCsr &A, const TiledCsr &T, double *y, const do
 int launch_ata_fused(const DeviceCsr &A, double *y, const double *x, hipStream_t s)
 {
   if (A.ncol == 0) return FS_OK;
-  FS_HIP(hipMemsetAsync(y, 0, sizeof(double) * (size_t)A.ncol, s));
+  if (int rc = launch_zero(y, sizeof(double) * (size_t)A.ncol, s)) return rc;
   if (A.nrow == 0 || A.nnz == 0) return FS_OK;
   const TiledCsr *T = A.tiledx;
   if (T && T->built && !T->shared && T->nchunks > 0) {

@@ -416,7 +416,8 @@ __global__ __launch_bounds__(kBlock) void longrows_scatter_kernel(int nlong, con
 static int launch_longrows(const DeviceCsr &A, const LongRows &L, const double *x, int xs, hipStream_t s)
 {
   const bool ordered = reproducible_now();
-  if (!ordered || L.n == 0 || L.nwg == 0) FS_HIP(hipMemsetAsync(L.ylong, 0, sizeof(double) * (size_t)L.nlong, s));
+  if (!ordered || L.n == 0 || L.nwg == 0)
+    if (int rc = launch_zero(L.ylong, sizeof(double) * (size_t)L.nlong, s)) return rc;
   if (L.n == 0 || L.nwg == 0) return FS_OK;
 #define FS_LONG(V, BC, NA, ORD)                                                                                              \
   hipLaunchKernelGGL((spmv_longrows_kernel<V, BC, NA, ORD>), dim3(L.nwg), dim3(kBinBlock), 0, s, A.ncol, L.B, L.nlong, L.band_ptr, \

@@ -8,8 +8,10 @@ exact sum, with +0.0 for a zero sum (the reference starts every sum from `tmp = 
 
 `exact_sum` checks the rule on the data and fails loudly when it does not hold; a generator that breaks it is a bug.
 
-Data sets (seeded, deterministic), each a `Data` with the matrix in row-major COO / CSR and its vectors:
-  D1 `wide_range`   signed powers of two, <= 64 entries a row, a row's smallest product 2^-46 of its largest
+Data sets (seeded, deterministic), each a `Data` with the matrix in row-major COO / CSR and its vectors (x over columns, u over
+rows, the k-column panels X(k) and U(k), and the exact A x, A' u, A X(k), A' U(k)):
+  D1 `wide_range`   signed powers of two, <= 64 entries a row, a row's smallest product 2^-46 of its largest;
+     `wide_range_odd` the same with an odd number of rows and of columns
   D2 `long_rows`    odd integers 1..15 x 2^[-4, 4] times integers |x| <= 1023, rows of up to 50 000 entries
   D3 `subnormal`    every product of a row a subnormal multiple of 2^-1074; some row sums cross 2^-1022;
      `subnormal_pattern` the pattern-only form with subnormal x
@@ -122,6 +124,7 @@ class Data:
         self.rows, self.cols = rows.astype(np.int32), cols.astype(np.int32)
         self.vals = None if vals is None else np.ascontiguousarray(vals, np.float64)
         self.x, self.u, self._xcol = x, u, xcol
+        self._cache = {}
         self.rp = np.zeros(nrow + 1, np.int32)
         np.cumsum(np.bincount(self.rows, minlength=nrow), out=self.rp[1:])
 
@@ -133,6 +136,18 @@ class Data:
         """row-major ncol x k right-hand sides, column 0 = x"""
         return np.ascontiguousarray(np.stack([self.x] + [self._xcol(j) for j in range(1, k)], 1))
 
+    def ucol(self, j):
+        """column j of U: u with seeded per-element sign flips, the whole column scaled by 2^(j % 4).  A flip keeps every |a u| and
+        a power of two scales every term of a sum alike (the sets keep their terms far from overflow and, scaled up, from 2^-1074),
+        so the exactness rule holds for every column that it holds for with u -- exact_sum checks it all the same."""
+        if j == 0:
+            return self.u
+        return _signs(np.random.default_rng(7000 + j), self.nrow) * self.u * 2.0 ** (j % 4)
+
+    def U(self, k):
+        """row-major nrow x k right-hand sides of A' products, column 0 = u"""
+        return np.ascontiguousarray(np.stack([self.ucol(j) for j in range(k)], 1))
+
     def y(self):
         return spmv(self.nrow, self.rows, self.cols, self.vals, self.x)
 
@@ -140,7 +155,22 @@ class Data:
         return spmv_t(self.ncol, self.rows, self.cols, self.vals, self.u)
 
     def Y(self, k):
-        return spmm(self.nrow, self.rows, self.cols, self.vals, self.X(k))
+        """exact A X(k); columns are computed once per data set (X(k) is a prefix of X(k + 1))"""
+        cols = self._cache.setdefault("Y", [])
+        for j in range(len(cols), k):
+            cols.append(spmv(self.nrow, self.rows, self.cols, self.vals, self.x if j == 0 else self._xcol(j)))
+        return np.ascontiguousarray(np.stack(cols[:k], 1))
+
+    def Z(self, k):
+        """exact A' U(k), column by column"""
+        cols = self._cache.setdefault("Z", [])
+        for j in range(len(cols), k):
+            cols.append(spmv_t(self.ncol, self.rows, self.cols, self.vals, self.ucol(j)))
+        return np.ascontiguousarray(np.stack(cols[:k], 1))
+
+    def pattern(self):
+        """the same pattern without values (its sums obey the rule on every set built for it: see the set's docstring)"""
+        return Data(self.name + "_pattern", self.nrow, self.ncol, self.rows, self.cols, None, self.x, self.u, self._xcol)
 
     def case(self, kmax=8, block_sizes=(8, 1024), colblocks=(64,)):
         """the data as a tests/_cases.Case: run_case pushes it through every reference-named entry point"""
@@ -195,7 +225,7 @@ def _signs(rng, n):
     return np.where(rng.uniform(size=n) < 0.5, -1.0, 1.0)
 
 
-def wide_range(seed=1, nrow=2000, ncol=1500, maxlen=64, X0=-3):
+def wide_range(seed=1, nrow=2000, ncol=1500, maxlen=64, X0=-3, name="wide_range"):
     """D1: a = +-2^(r_i + w - X0), x = +-2^X0, so a row's products are +-2^(r_i + w), w in [0, 46] with both ends taken in every
     row of two entries or more: the smallest term is 2^-46 of the largest, below the 1e-12 row-scaled bar.  r_i in [-23, 23].
     u_i = +-2^(5 - r_i): a column's products are +-2^(5 - X0 + w), the same 46-bit spread (columns hold < 128 entries), and so
@@ -213,7 +243,13 @@ def wide_range(seed=1, nrow=2000, ncol=1500, maxlen=64, X0=-3):
     x = _signs(rng, ncol) * 2.0 ** X0
     u = _signs(rng, nrow) * np.ldexp(1.0, 5 - r)
     xcol = lambda j: _signs(np.random.default_rng(seed * 1000 + j), ncol) * 2.0 ** X0        # noqa: E731
-    return Data("wide_range", nrow, ncol, rows, cols, vals, x, u, xcol)
+    return Data(name, nrow, ncol, rows, cols, vals, x, u, xcol)
+
+
+def wide_range_odd():
+    """D1 with an odd number of rows AND of columns: x (A) and u (A') both have odd length, the LDS-staged kernel's slices of
+    either side then go without LDS DMA (it needs an even ncol)"""
+    return wide_range(seed=13, nrow=2001, ncol=1499, name="wide_range_odd")
 
 
 def _odd(rng, n, hi):
@@ -322,4 +358,4 @@ def zeros(seed=5, nrow=1200, ncol=900, valued=True):
 def all_sets():
     """the data sets at the small shapes the CPU tests and the entry-point sweep use"""
     return [wide_range(), long_rows(), long_rows(profile="heavy", nrow=4000, seed=6), long_rows(valued=False, seed=7),
-            subnormal(), subnormal_pattern(), zeros(), zeros(valued=False)]
+            subnormal(), subnormal_pattern(), zeros(), zeros(valued=False), wide_range_odd()]

@@ -71,3 +71,51 @@ def test_exact_sum_refuses_data_that_breaks_the_rule():
     assert E.bits_equal(y, np.zeros(4))
     assert E.bits_equal(E.exact_sum(np.zeros(4, int), 1, [1.0] * 4, [2.0 ** -1074] * 3 + [2.0 ** -1022]),
                         np.array([3 * 2.0 ** -1074 + 2.0 ** -1022]))
+
+
+def _k_column_refs(be, data, k):
+    """A X(k) through the backend's k-column product, A' U(k) column by column through its A' product"""
+    Y = be.csr_mul_n(data.nrow, data.ncol, data.rows, data.cols, data.vals, data.X(k), k,
+                     "csr_A_mul_Bn" if data.vals is not None else "bcsr_A_mul_Bn")
+    U = data.U(k)
+    Z = np.stack([be.coo_tmul(data.nrow, data.ncol, data.rows, data.cols, data.vals, U[:, j].copy()) for j in range(k)], 1)
+    return Y, Z
+
+
+K_REF = 6            # U(6): every scale 2^(j % 4) and several sign patterns
+
+
+@pytest.mark.parametrize("data", SETS + [SETS[0].pattern()], ids=lambda d: d.name)
+def test_k_column_references_are_the_oracle_bit_for_bit(data):
+    """Y(k) = A X(k) against the oracle's csr_mul_n, Z(k) = A' U(k) column by column against its coo_tmul (the serial loop of
+    At_mul_B / sdm_At_mul_B)"""
+    from oracle import pyoracle as O
+    Y, Z = _k_column_refs(_cases.OracleBackend(), data, K_REF)
+    rp, cc, vv = O.coo_to_csr(data.nrow, data.rows, data.cols, data.vals)
+    assert np.array_equal(rp, data.rp) and np.array_equal(cc, data.cols)
+    assert E.bits_equal(data.Y(K_REF), Y), (data.name, E.first_mismatch(data.Y(K_REF), Y))
+    assert E.bits_equal(data.Z(K_REF), Z), (data.name, E.first_mismatch(data.Z(K_REF), Z))
+    assert E.bits_equal(data.Y(K_REF)[:, :3], data.Y(3)) and E.bits_equal(data.Z(K_REF)[:, 0], data.z())
+
+
+@pytest.mark.ref
+@pytest.mark.skipif(not _refbind.available(), reason="oracle/_ref not built (no reference sources here)")
+@pytest.mark.parametrize("data", SETS + [SETS[0].pattern()], ids=lambda d: d.name)
+def test_k_column_references_are_the_strict_reference_bit_for_bit(data):
+    Y, Z = _k_column_refs(_cases.RefBackend(fast=False), data, K_REF)
+    assert E.bits_equal(data.Y(K_REF), Y), (data.name, E.first_mismatch(data.Y(K_REF), Y))
+    assert E.bits_equal(data.Z(K_REF), Z), (data.name, E.first_mismatch(data.Z(K_REF), Z))
+
+
+def test_u_panels_keep_the_edges_of_their_sets():
+    """U(k) varies signs and scales and nothing else: the subnormal set's A' sums stay subnormal in every column, the zeros set's
+    stay +0.0, the odd set is odd on both sides"""
+    d3 = E.subnormal()
+    U = d3.U(K_REF)
+    assert np.array_equal(np.abs(U[:, 1]), np.abs(d3.u) * 2.0) and (np.signbit(U[:, 1]) != np.signbit(d3.u)).sum() > d3.nrow // 4
+    Z = d3.Z(K_REF)
+    assert all(((Z[:, j] != 0) & (np.abs(Z[:, j]) < 2.0 ** -1022)).sum() > 100 for j in range(K_REF))
+    for d in (E.zeros(), E.zeros(valued=False)):
+        assert np.all(d.Z(K_REF).view(np.int64) == 0)
+    odd = E.wide_range_odd()
+    assert odd.nrow % 2 == 1 and odd.ncol % 2 == 1 and odd.nnz > 0
