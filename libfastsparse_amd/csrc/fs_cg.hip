@@ -464,6 +464,15 @@ int cg2_dev_finish(int n, const double *norms, double *X, hipStream_t s)        
   return FS_OK;
 }
 
+static thread_local double g_last_cg_state[kStDoubles];
+static thread_local bool g_last_cg_state_set = false;
+
+void note_cg_state(const double *st_host)
+{
+  for (int i = 0; i < kStDoubles; ++i) g_last_cg_state[i] = st_host[i];
+  g_last_cg_state_set = true;
+}
+
 int CgFlags::init()
 {
   FS_HIP(hipHostMalloc((void **)&h, sizeof(double) * 4));
@@ -534,10 +543,11 @@ int fs_cg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lamb
     if (int rc = fl.after_iteration(iter, st, s, &stop)) return rc;
     if (stop) break;
   }
-  double fin[2] = {0.0, 0.0};
-  FS_HIP(hipMemcpyAsync(fin, st + kStDone, sizeof(fin), hipMemcpyDeviceToHost, s));
+  double fin[kStDoubles] = {0.0};
+  FS_HIP(hipMemcpyAsync(fin, st, sizeof(fin), hipMemcpyDeviceToHost, s));
   FS_HIP(hipStreamSynchronize(s));
-  if (out_iter) *out_iter = (int)fin[1];
+  note_cg_state(fin);
+  if (out_iter) *out_iter = (int)fin[kStIter];
   return FS_OK;
 }
 
@@ -574,11 +584,23 @@ int fs_cg2(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, double lam
     if (stop) break;
   }
   if (int rc = cg2_dev_finish(F, norms, X, s)) return rc;
-  double fin[2] = {0.0, 0.0};
-  FS_HIP(hipMemcpyAsync(fin, st + kStDone, sizeof(fin), hipMemcpyDeviceToHost, s));
+  double fin[kStDoubles] = {0.0};
+  FS_HIP(hipMemcpyAsync(fin, st, sizeof(fin), hipMemcpyDeviceToHost, s));
   FS_HIP(hipStreamSynchronize(s));
-  if (out_iter) *out_iter = (int)fin[1];
+  note_cg_state(fin);
+  if (out_iter) *out_iter = (int)fin[kStIter];
   return FS_OK;
+}
+
+// the final st[] (kCgStateDoubles doubles, layout of the enum above final_step_kernel) of the last solve on the calling thread:
+// fs_cg / fs_cg2, or rank 0's of fs_dist_cg / fs_dist_cg2.  Returns the number of doubles written, 0 before the first solve.
+// Diagnostics, not in include/fastsparse_hip.h.
+int fs_debug_last_cg_state(double *out)
+{
+  if (!out) { set_error("fs_debug_last_cg_state: NULL argument"); return FS_ERR_ARG; }
+  if (!g_last_cg_state_set) return 0;
+  for (int i = 0; i < kStDoubles; ++i) out[i] = g_last_cg_state[i];
+  return kStDoubles;
 }
 
 }  // extern "C"

@@ -389,6 +389,8 @@ int cg_dev_step_b(int n, double *x, double *r, const double *p, const double *q,
                   hipStream_t s);
 int cg_dev_step_c(int n, double *p, const double *r, const double *st, hipStream_t s);
 int cg_dev_final(int mode, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s);
+// the final st[] of a solve, kCgStateDoubles doubles copied back to the host: kept for the calling thread (fs_debug_last_cg_state)
+void note_cg_state(const double *st_host);
 // the host's view of a running solve: {done, iterations} of the two most recent iterations, in pinned memory
 struct CgFlags {
   double *h = nullptr;

@@ -1581,6 +1581,16 @@ int fs_dist_swap_xy(fs_dist_matrix_t M)
   return FS_OK;
 }
 
+// the final st[] of rank 0, for fs_debug_last_cg_state (after the ranks were found to agree on {done, iterations})
+static int note_rank0_state(fs_dist_t D, const double *st)
+{
+  double h[fs::kCgStateDoubles];
+  FS_HIP(hipSetDevice(D->dev[0]));
+  FS_HIP(hipMemcpy(h, st, sizeof(h), hipMemcpyDeviceToHost));
+  fs::note_cg_state(h);
+  return FS_OK;
+}
+
 // (A'A + lambda I) x = b on the row-sharded matrix: bsbm_cg (cg.h:25-82) across the GPUs, everything resident, the scalars of
 // the iteration on the devices (fs_cg.hip).  Per iteration y = A p and q = A' y; two schemes for everything else (option
 // "dist_cg_scheme"):
@@ -1735,6 +1745,7 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
       return FS_ERR_HIP;
     }
   }
+  if (int rc = note_rank0_state(D, W.st[0])) return rc;
   if (vector_device(x_host) >= 0)
     if (int rc = wait_for_caller(vector_device(x_host))) return rc;
   if (!gather) {
@@ -1856,6 +1867,7 @@ int fs_dist_cg2(fs_dist_matrix_t M, double *X_host, const double *B_host, double
       return FS_ERR_HIP;
     }
   }
+  if (int rc = note_rank0_state(D, W.st[0])) return rc;
   if (vector_device(X_host) >= 0)
     if (int rc = wait_for_caller(vector_device(X_host))) return rc;
   if (int rc = vec_store(M, 0, X_host, W.sol[0], (size_t)F * 2)) return rc;

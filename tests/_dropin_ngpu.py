@@ -3,7 +3,7 @@ library reads them once): EVERY reference-named product entry point -- A_mul_B, 
 cbcsr_*, bcsr_AA_mul_B, bsbm_cg / bsbm_cg2 -- through HipDropinBackend on the row-sharded path (three virtual ranks on one GPU),
 against the goldens made from the real reference, with the bars of the single-GPU run (tests/test_gpu_parity.py:_check).
 Modes: golden (host vectors), resident (x / y in HBM: nothing may be staged through the host), exact (tests/_exact.py data, bit for
-bit against the exact reference)."""
+bit against the exact reference), cg (bsbm_cg / bsbm_cg2 bit for bit against tests/_cg_model.py, child of tests/test_gpu_cg.py)."""
 import ctypes as C
 import os
 import sys
@@ -259,5 +259,32 @@ def exact():
     L.fs_release_all()
 
 
-{"golden": golden, "resident": resident, "edges": edges, "fullsize": fullsize, "exact": exact}[sys.argv[1].split("+")[0]]()
+def cg():
+    """bsbm_cg / bsbm_cg2 on the row-sharded path (fs_dist_cg / fs_dist_cg2 on the pair of A and At): under strict_order the bits
+    of the CPU model (tests/_cg_model.py) over the CSRs the library holds; on the exact systems of tests/test_gpu_cg.py the exact
+    answer in every mode"""
+    import _cg_model as CM
+    import test_gpu_cg as G
+    with G.options(strict_order=1):
+        for name in ("fixture_100x50", "binary_F257", "ill_conditioned", "cap_tol0", "zero_rhs", "cg2_equal_columns"):
+            s = G.SYSTEMS[name]
+            for two in ((False, True) if s.two else (False,)):
+                before = L.fs_debug_dist_products()
+                x, it, st, (a_csr, t_csr) = G.dropin_run(L, s, two)
+                assert L.fs_debug_dist_products() - before >= 2 * max(it, 1), (name, two, it)
+                am, atm, am2, atm2 = CM.csr_products(s.nrow, s.ncol, a_csr, t_csr)
+                model = CM.cg2(s.ncol, am2, atm2, s.B, s.lam, s.tol) if two else CM.cg(s.ncol, am, atm, s.b, s.lam, s.tol)
+                G._assert_model(f"bsbm_cg{'2' if two else ''}, 3 ranks", s, two, x, it, st, model)
+                print("cg", name, "cg2" if two else "cg", it, "iterations, bit for bit", flush=True)
+    for mode in G.MODES:
+        for s, scale in G.EXACT[:2]:
+            for two in (False, True):
+                with G._mode(mode):
+                    x, it, st, _ = G.dropin_run(L, s, two)
+                G._assert_exact("bsbm_cg, 3 ranks", mode, s, scale, two, x, it, st)
+        print("cg exact", mode, flush=True)
+    L.fs_release_all()
+
+
+{"golden": golden, "resident": resident, "edges": edges, "fullsize": fullsize, "exact": exact, "cg": cg}[sys.argv[1].split("+")[0]]()
 print("OK")
