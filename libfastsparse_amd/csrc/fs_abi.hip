@@ -432,6 +432,20 @@ int fs_debug_last_spmm_plan(void) { return fs::last_spmm_plan(); }
 // the row kernel of the last multi-column product since the previous call: 1 with 16-byte loads (spmm_wide_kernel), 0 without, -1 none
 int fs_debug_last_spmm_wide(void) { return fs::last_spmm_wide(); }
 
+// what fs_matrix_prepare(A, k, transposed) would still do under the current options (spmm_plan's needs_prepare): bit 0 build the
+// k-column two-pass copy -- the one step that reads the plain CSR, so the one that FS_ERR_RELEASED refuses --, bit 1 time column
+// sweeps against the row kernel, bit 2 allocate the column-major scratch; 0: nothing left to do
+int fs_debug_spmm_needs(fs_matrix_t A, int k, int transposed)
+{
+  if (!A || k < 1 || (transposed && !A->has_t)) return FS_ERR_ARG;
+  std::lock_guard<std::mutex> g(A->lock);
+  const fs::DeviceCsr &a = transposed ? A->at : A->a;
+  int needs = 0;
+  if (a.nrow == 0 || a.nnz == 0 || k < 2) return 0;     // prepare_spmm returns before it looks
+  (void)fs::spmm_plan(a, k, &needs);
+  return needs;
+}
+
 // the kept tiled copy (LDS-staged or L2-tiled) of A or A': bit 0 it has cut rows (a combine pass follows its kernel), bit 1 chunks
 // share panels (sums go through its scratch vector); FS_ERR_ARG without one
 int fs_debug_tiled_layout(fs_matrix_t A, int transposed)

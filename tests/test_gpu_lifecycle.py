@@ -1,0 +1,327 @@
+"""Long-lived handles on the real library: random operation walks with every vector inside guard zones (tests/_lifecycle.py).
+
+The other GPU tests run one fixed script on a fresh handle.  Here a handle lives through a walk of legal calls -- products of every
+kind, prepare / release, release_csr / restore_csr, option flips, stream changes, neighbours created and destroyed -- and after
+every operation the guards of all vectors are untouched, the inputs unchanged, the outputs exact, the statuses what the header
+promises and the bookkeeping what the debug hooks saw.  tests/test_lifecycle_model.py shows on a numpy stand-in that these checks
+catch the faults they are meant for, and that the seeds used here reach every operation."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import _cg_model as M
+import _exact as E
+import _lifecycle as LC
+from test_gpu_exact import PATHS, options
+
+pytestmark = pytest.mark.gpu
+
+SEEDS = (1, 2)
+STEPS = 150
+SET_NAMES = LC.GPU_SET_NAMES           # (why these two: see there)
+COPIES = list(PATHS) + [LC.AUTO]
+# the mid-size set with panels of 32 rows: more generations of resident workgroups than the largest nparts
+SMALL_PANELS = {"two-pass, panels of 32 rows": (dict(binning=2, ldsx=0, tiling=0, bin_rows=32), "two-pass"),
+                "lds-staged, panels of 32 rows": (dict(ldsx=2, binning=0, tiling=0, tile_rows=32), "lds-staged")}
+
+
+@pytest.fixture(scope="module")
+def backend():
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    return LC.HipBackend(dict(PATHS, **SMALL_PANELS), options)
+
+
+@pytest.fixture(scope="module")
+def mid():
+    d = LC.mid_size()
+    return d, LC.refs_of(d, nc=2, ata_cols=0)
+
+
+@pytest.mark.parametrize("copy", COPIES)
+@pytest.mark.parametrize("name", SET_NAMES)
+def test_walks_are_exact_and_stay_inside_their_vectors(backend, name, copy):
+    d = LC.data_sets()[name]
+    for seed in SEEDS:
+        w = LC.run_walk(backend, d, copy, seed, steps=STEPS, copies=COPIES)
+        assert sum(w.counts["ops"].values()) == STEPS
+
+
+@pytest.mark.parametrize("copy", list(SMALL_PANELS))
+def test_products_in_parts_survive_plan_eviction(backend, mid, copy):
+    """the mid-size set, really cut (asserted): nparts 2..12 in random order on A and on A', and again in reverse -- eleven plans
+    through a cache of eight, with `reproducible` flipped half way so that one nparts owns two -- every product exact after every
+    part, and the rows fs_spmv_part_rows reports for an nparts the same before and after its plan was pushed out"""
+    d, _ = mid
+    w = LC.Walk(backend, d, copy, seed=5, steps=0, kmax=2, nc=2, ata_cols=0)
+    with w.session():
+        H = w.create(first=True, with_t=True, borrow=False)
+        rng = np.random.default_rng(5)
+        for side in (0, 1):
+            n = H.refs.n_out[side]
+            first = {}
+            order = [int(v) for v in rng.permutation(np.arange(2, 13))]
+            for i, nparts in enumerate(order + order[::-1]):
+                w.step = i
+                if i == len(order) // 2:
+                    w.flip("reproducible", 1)
+                if i == len(order):
+                    w.flip("reproducible", 0)
+                rows = H.A.part_rows(nparts, bool(side))
+                assert any(0 < r < n for r in rows), (copy, side, nparts, rows, "the product is not cut: the set has too few panels")
+                assert first.setdefault(nparts, rows) == rows, (copy, side, nparts, first[nparts], rows)
+                assert w.one_product_in_parts(H, side, 1, nparts) == LC.FS_OK
+        # one nparts owns a plan per kernel: first met under strict_order (the chunk-streaming kernel: everything with part 0), then
+        # under the default options it must get the cuts of the kept copy, not the plan filed under the same nparts
+        for side, nparts in ((0, 13), (1, 14)):
+            w.step = 50 + side
+            w.flip("strict_order", 1)
+            rows = H.A.part_rows(nparts, bool(side))
+            assert rows == [0] + [H.refs.n_out[side]] * nparts, (copy, side, rows)
+            assert w.one_product_in_parts(H, side, 1, nparts) == LC.FS_OK
+            w.flip("strict_order", 0)
+            rows = H.A.part_rows(nparts, bool(side))
+            assert any(0 < r < H.refs.n_out[side] for r in rows), (copy, side, nparts, rows, "the cuts of another kernel's plan")
+            assert w.one_product_in_parts(H, side, 1, nparts) == LC.FS_OK
+        assert w.op_prepare(H, 2, 0) == LC.FS_OK
+        for i, nparts in enumerate((3, 12, 5, 12, 2)):
+            w.step = 100 + i
+            assert w.one_product_in_parts(H, 0, 2, nparts) == LC.FS_OK
+        if SMALL_PANELS[copy][1] == "two-pass":
+            rows = H.A.part_rows(12, False, 2)
+            assert any(0 < r < d.nrow for r in rows), (rows, "the 2-column sweep is not cut")
+
+
+@pytest.mark.parametrize("copy", ["two-pass", "lds-staged"])
+def test_release_prepared_k_by_k_gives_everything_back(backend, copy):
+    """prepare for several k, release them one by one in another order: products exact in between, and once the last is gone
+    fs_matrix_device_bytes()[2] is 0 again (the column-major scratch of the LDS-staged copy goes with the last k that used it)"""
+    d = LC.data_sets()["subnormal"]
+    w = LC.Walk(backend, d, copy, seed=9, steps=0)
+    with w.session():
+        H = w.create(first=True, with_t=True, borrow=False)
+        assert H.A.device_bytes()[2] == 0
+        for i, k in enumerate((3, 5, 8, 2, 4)):
+            w.step = i
+            assert w.op_prepare(H, k, i & 1) == LC.FS_OK
+            w.op_spmm(H, i & 1)
+        assert H.A.device_bytes()[2] > 0
+        for i, k in enumerate((8, 5, 4, 3, 2)):
+            w.step = 10 + i
+            w.op_release_prepared(H, k)
+            w.op_spmm(H, i & 1)
+        assert H.A.device_bytes()[2] == 0, H.A.device_bytes()
+
+
+def test_first_fixed_order_product_late_in_life(backend):
+    """the two-byte row ids a one-byte two-pass copy writes on its first fixed-order product: after many default products the handle
+    meets `reproducible`, then a solver's scope (fs_cg on a system whose every sum is exact: x = b / 2^e at iteration 0), then the
+    default mode again.  Exact each time; fs_matrix_device_bytes grows once per copy, by at most 2 bytes per padded entry, and the
+    growth is there right after the first such product"""
+    import torch
+    from libfastsparse_amd import capi
+    L = backend.L
+    s = M.exact_system(m=3, lam=1.0, F=2000, seed=23)
+    (arp, acc, _), (trp, tcc, _) = s.a_csr(), s.t_csr_sorted()
+    rows = np.repeat(np.arange(s.nrow), np.diff(arp))
+    mem = backend.mem
+    xs = [s.b] + [s.b * 2.0 ** j * np.where(np.random.default_rng(j).uniform(size=s.ncol) < 0.5, -1.0, 1.0) for j in range(1, 6)]
+    us = [np.random.default_rng(50 + j).integers(-512, 513, s.nrow).astype(np.float64) for j in range(6)]
+    ys = [E.spmv(s.nrow, rows, acc, None, x) for x in xs]
+    zs = [E.spmv_t(s.ncol, rows, acc, None, u) for u in us]
+    with options(**PATHS["two-pass one-byte"][0]):
+        A = capi.Matrix.from_csr(s.nrow, s.ncol, mem.const(arp), mem.const(acc), None)
+        At = capi.Matrix.from_csr(s.ncol, s.nrow, mem.const(trp), mem.const(tcc), None)
+    padded = []
+    for X in (A, At):
+        assert X.kernel_name() == "two-pass" and L.fs_debug_two_pass_rows8(X.h, 0) >= 0, "not a one-byte two-pass copy"
+        out8 = (C.c_ulonglong * 8)()
+        assert L.fs_debug_two_pass_layout(X.h, 0, out8) == 0
+        padded.append(int(out8[5]))
+    gin = {X: LC.Guarded(mem, f"x of {n}", max(s.nrow, s.ncol)) for X, n in ((A, "A"), (At, "At"))}
+    gout = {X: LC.Guarded(mem, f"y of {n}", max(s.nrow, s.ncol)) for X, n in ((A, "A"), (At, "At"))}
+    st = capi.current_stream()
+    count = [0]
+
+    def product(X, what):
+        j = count[0] % 6
+        count[0] += 1
+        x, want = (xs[j], ys[j]) if X is A else (us[j], zs[j])
+        mem.put(gin[X].place(x.size, count[0] & 1), x)
+        mem.fill_bits(gout[X].place(want.size, (count[0] >> 1) & 1), LC.PREFILLS["nan"])
+        X.spmv(gout[X].view, gin[X].view, st)
+        got = mem.get(gout[X].view)
+        assert E.bits_equal(got, want), (what, count[0], E.first_mismatch(got, want))
+        assert gin[X].guards_ok() and gout[X].guards_ok() and mem.eq(gin[X].view, mem.const(x)), (what, count[0])
+
+    for _ in range(12):
+        product(A, "default, early in life")
+        product(At, "default, early in life")
+    before = (A.device_bytes(), At.device_bytes())
+    with options(reproducible=1):
+        product(A, "the first fixed-order product")
+        grown = A.device_bytes()
+        assert 0 < grown[1] - before[0][1] <= 2 * padded[0] and grown[0] == before[0][0] and grown[2] == before[0][2], (before[0], grown, padded)
+        for _ in range(3):
+            product(A, "reproducible")
+        assert A.device_bytes() == grown, "the copy grew a second time"
+    assert At.device_bytes() == before[1]
+    b = mem.const(s.b)
+    x = LC.Guarded(mem, "x of fs_cg", s.ncol)
+    mem.fill_bits(x.place(s.ncol, 1), LC.PREFILLS["nan"])
+    it = C.c_int(-1)
+    capi.check(L.fs_cg(A.h, At.h, x.view.data_ptr(), b.data_ptr(), s.lam, s.tol, C.byref(it), st), "fs_cg")
+    torch.cuda.synchronize()
+    assert it.value == 0 and E.bits_equal(mem.get(x.view), s.b / (3 + s.lam)) and x.guards_ok(), (it.value, E.first_mismatch(mem.get(x.view), s.b / (3 + s.lam)))
+    grown_t = At.device_bytes()
+    assert 0 < grown_t[1] - before[1][1] <= 2 * padded[1], (before[1], grown_t, padded)          # the solver's scope met A' first
+    assert A.device_bytes() == grown
+    for _ in range(6):
+        product(A, "default again")
+        product(At, "default again")
+    assert A.device_bytes() == grown and At.device_bytes() == grown_t
+
+
+@pytest.mark.parametrize("copy", list(PATHS))
+def test_captured_walk_replays(backend, copy):
+    """spmv, spmv_t, spmm k = 2 and 8, ata captured once on the test's stream, replayed three times with new right-hand sides copied
+    into the captured input vectors: guards and exact bits after every replay (a replay that serves the rows of the capture, or of
+    the replay before, fails: the columns change every time)"""
+    import torch
+    from libfastsparse_amd import capi
+    d = LC.data_sets()["subnormal_pattern"]
+    r = LC.refs_of(d)
+    mem = backend.mem
+    s = torch.cuda.Stream()
+    with options(**PATHS[copy][0]):
+        A = capi.Matrix.from_csr(d.nrow, d.ncol, mem.const(d.rp), mem.const(d.cols), None)
+        A.build_transpose(capi.current_stream())
+        for k in (2, 8):
+            A.prepare(k, capi.current_stream())
+    torch.cuda.synchronize()
+    # (name, side of the input, side of the output, k)
+    calls = [("spmv", 0, 0, 1), ("spmv_t", 1, 1, 1), ("spmm2", 0, 0, 2), ("spmm8", 0, 0, 8), ("spmm_t2", 1, 1, 2), ("ata", 0, 1, 1)]
+    with torch.cuda.stream(s):
+        gi, go = {}, {}
+        for i, (name, si, so, k) in enumerate(calls):
+            gi[name] = LC.Guarded(mem, f"input of {name}", r.n_in[si] * k)
+            go[name] = LC.Guarded(mem, f"output of {name}", r.n_out[so] * k)
+            gi[name].place(r.n_in[si] * k, i & 1)
+            go[name].place(r.n_out[so] * k, (i >> 1) & 1)
+        tmp = LC.Guarded(mem, "tmp of ata", d.nrow)
+        tmp.place(d.nrow, 1)
+
+        def launch():
+            st = capi.current_stream()
+            A.spmv(go["spmv"].view, gi["spmv"].view, st)
+            A.spmv(go["spmv_t"].view, gi["spmv_t"].view, st, transposed=True)
+            A.spmm(go["spmm2"].view, gi["spmm2"].view, 2, st)
+            A.spmm(go["spmm8"].view, gi["spmm8"].view, 8, st)
+            A.spmm(go["spmm_t2"].view, gi["spmm_t2"].view, 2, st, transposed=True)
+            A.ata(go["ata"].view, gi["ata"].view, tmp.view, st)
+
+        def load(j):
+            want = {}
+            for name, si, so, k in calls:
+                mem.put(gi[name].view, r.run("in", si, j, k))
+                mem.fill_bits(go[name].view, LC.PREFILLS["nan"])
+                want[name] = r.ata[j] if name == "ata" else r.run("out", so, j, k)
+            return want
+
+        def check(want, what):
+            s.synchronize()
+            for name, si, so, k in calls:
+                got = mem.get(go[name].view)
+                assert E.bits_equal(got, want[name]), (copy, what, name, E.first_mismatch(got, want[name]))
+                assert mem.eq(gi[name].view, mem.const(r.run("in", si, want["j"], k))), (copy, what, name, "input modified")
+            for g in list(gi.values()) + list(go.values()) + [tmp]:
+                assert g.guards_ok(), (copy, what, g.first_broken())
+
+        want = load(0)
+        want["j"] = 0
+        launch()
+        check(want, "eager")
+        g = torch.cuda.CUDAGraph()
+        s.synchronize()
+        with torch.cuda.graph(g, stream=s):
+            launch()
+        for j in (1, 2, 1):
+            want = load(j)
+            want["j"] = j
+            g.replay()
+            check(want, f"replay with columns {j}..")
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("name", ["wide_range", "subnormal_pattern", "wide_range_mid"])
+def test_walk_on_three_virtual_ranks(backend, mid, name):
+    """fs_dist_spmv / _t / fs_dist_spmm / _t / fs_dist_ata on one matrix across three virtual ranks, vectors in guarded HBM arenas
+    and in guarded host arrays, options flipped between the calls (every flip moves the option epoch: the parts are planned again
+    for the kernel that runs now), expected bits from tests/_exact.py.  On the mid-size set with panels of 32 rows every rank's
+    product is really cut, and the walk opens with products under strict_order (everything with part 0) followed by products under
+    the default options: a plan kept from the first would ship rows that the second has not finished"""
+    from libfastsparse_amd import capi
+    L = backend.L
+    big = name == "wide_range_mid"
+    d, r = mid if big else (LC.data_sets()[name], LC.refs_of(LC.data_sets()[name]))
+    ks = (2,) if big else (2, 4, 5)
+    vals = None if d.vals is None else d.vals.ctypes.data
+    rng = np.random.default_rng(77)
+    devs = (C.c_int * 3)(0, 0, 0)
+    D = L.fs_dist_create(3, devs)
+    assert D, L.fs_last_error()
+    flips = {"reproducible": (0, 1), "strict_order": (0, 1), "spmv_kernel": (0, 1, 7), "spmm_kernel": (0, 1, 3), "cg_fixed_order": (1, 0)}
+    log = []
+    try:
+        # (the mid-size matrix is created under strict_order: the builder does not read it, the parts are planned for the kernel
+        # it selects -- everything with part 0 -- and the first product under the default options needs the plan made again)
+        with options(binning=2, bin_rows=32 if big else 256, strict_order=int(big)):
+            Mx = L.fs_dist_csr_create(D, d.nrow, d.ncol, d.nnz, d.rp.ctypes.data, d.cols.ctypes.data, vals)
+            assert Mx, L.fs_last_error()
+            assert L.fs_dist_matrix_build_transpose(Mx, d.rp.ctypes.data, d.cols.ctypes.data, vals) == 0, L.fs_last_error()
+        n = max(d.nrow, d.ncol)
+        vec = {(where, role): LC.Guarded(backend.mem if where == "hbm" else backend.hostmem, f"{role} vector in {where}", n * 5)
+               for where in ("hbm", "host") for role in ("in", "out")}
+        try:
+            with options(**{k: L.fs_get_option(k.encode()) for k in flips}):
+                opening = [("spmv",), ("spmv_t",), ("flip", "strict_order", 1), ("spmv",), ("spmv_t",), ("flip", "strict_order", 0), ("spmv",), ("spmv_t",)]
+                for step in range(20 if big else 60):
+                    forced = opening[step] if step < len(opening) else None
+                    op = forced[0] if forced else ("spmv", "spmv_t", "spmm", "spmm_t", "ata", "flip")[int(rng.integers(6))]
+                    if op == "flip" or (op == "ata" and not r.ata):
+                        k_, vs = list(flips.items())[int(rng.integers(len(flips)))]
+                        v = vs[int(rng.integers(len(vs)))]
+                        if forced:
+                            k_, v = forced[1:]
+                        log.append(f"{step} {k_} = {v}")
+                        capi.set_option(k_, v)
+                        continue
+                    side = int(op.endswith("_t"))
+                    k = int(rng.choice(ks)) if op.startswith("spmm") else 1
+                    where = "host" if k > 1 or rng.integers(2) else "hbm"       # (the k-column entry points take host matrices)
+                    wi, wo = (where, "hbm")[int(rng.integers(2))] if k == 1 else "host", where
+                    j = int(rng.integers(len(r.ata) if op == "ata" else r.nc - k + 1))
+                    gi, go = vec[(wi, "in")], vec[(wo, "out")]
+                    xin = r.run("in", side, j, k)
+                    want = r.ata[j] if op == "ata" else r.run("out", side, j, k)
+                    gi.mem.put(gi.place(xin.size, int(rng.integers(2))), xin)
+                    go.mem.fill_bits(go.place(want.size, int(rng.integers(2))), LC.PREFILLS["nan"])
+                    log.append(f"{step} {op} k {k} column {j} in {wi} out {wo}")
+                    pi, po = gi.mem.ptr(gi.view), go.mem.ptr(go.view)
+                    if op == "ata":
+                        rc = L.fs_dist_ata(Mx, po, pi, 0.0)
+                    elif k == 1:
+                        rc = (L.fs_dist_spmv_t if side else L.fs_dist_spmv)(Mx, po, pi)
+                    else:
+                        rc = (L.fs_dist_spmm_t if side else L.fs_dist_spmm)(Mx, po, pi, k)
+                    assert rc == 0, (rc, L.fs_last_error(), log[-12:])
+                    got = go.mem.get(go.view)
+                    assert E.bits_equal(got, want), (name, E.first_mismatch(got, want), log[-12:])
+                    assert gi.mem.eq(gi.view, gi.mem.const(xin)), ("input modified", log[-12:])
+                    for g in vec.values():
+                        assert g.guards_ok(), (g.first_broken(), log[-12:])
+        finally:
+            L.fs_dist_matrix_destroy(Mx)
+    finally:
+        L.fs_dist_destroy(D)

@@ -1,0 +1,525 @@
+"""The lifecycle harness (tests/_lifecycle.py) has teeth, shown without a GPU.
+
+A numpy stand-in for the library -- the method names of capi.Matrix, vectors as numpy views into guarded arenas, products by
+bincount over the COO entries (exact on exactly summable data, whatever the order), the status rules of the header, the
+bookkeeping the walk asks about -- runs the SAME walk code as the GPU tests.  The honest stand-in passes; each injected fault makes
+a walk fail at the step where it first matters, with a message that names it; and the operation mix of the seeds the GPU test uses
+is checked, so that a generator that stops reaching an operation is a failing test and not a silent loss."""
+import contextlib
+
+import numpy as np
+import pytest
+
+import _lifecycle as LC
+
+COPIES = ["stream", "two-pass", "two-pass one-byte", "long rows", "lds-staged", "tiled cut rows", LC.AUTO]
+CODES = {"stream": 1, "two-pass": 7, "two-pass one-byte": 7, "long rows": 7, "lds-staged": 8, "tiled cut rows": 6, LC.AUTO: 1}
+DEFAULTS = {"reproducible": 0, "strict_order": 0, "cg_fixed_order": 1, "spmv_kernel": 0, "spmm_kernel": 0, "spmm_wide": 0, "ata_kernel": 0,
+            "tiled_flags": 0, "binning": 1}
+SEEDS = (1, 2)                      # the seeds of tests/test_gpu_lifecycle.py
+STEPS = 150
+
+
+class StandInError(RuntimeError):
+    pass
+
+
+def _raise(rc, what):
+    raise StandInError(f"{what} failed ({rc}): stand-in")
+
+
+def _where(v):
+    """(the allocation a view lies in, its offset in doubles)"""
+    base = v
+    while base.base is not None:
+        base = base.base
+    base = base.view(np.float64)
+    return base, (v.ctypes.data - base.ctypes.data) // 8
+
+
+class StandInMatrix:
+    def __init__(self, lib, d, code, borrow):
+        self.lib, self.d, self.h = lib, d, True
+        self.code = [code, code]
+        self.has_t = False
+        self.released = [False, False]
+        self.owned = [not borrow, True]
+        self.slot = [set(), set()]              # k-column two-pass copies built: 2 (serves k = 2, 3), 4
+        self.scratch_k = [0, 0]                 # columns the column-major scratch of the LDS-staged copy holds
+        self.choice = [dict(), dict()]
+        self.part_plans = [[], []]
+        self.last = {}
+        self.stale = {}
+
+    # -- bookkeeping ----
+    def _o(self):
+        return self.lib.opt
+
+    def kernel_code(self, side):
+        o, kept = self._o(), self.code[side]
+        if not o["strict_order"] and kept >= 6 and o["spmv_kernel"] in (0, kept):
+            return kept
+        return 2 if o["spmv_kernel"] == 2 else 1
+
+    def spmm_plan(self, k, transposed=False):
+        side, o = int(transposed), self._o()
+        kept, want = self.code[side], o["spmm_kernel"]
+        if o["strict_order"] or want == 1:
+            return 1
+        if kept == 7 and o["spmv_kernel"] in (0, 7):
+            if 2 <= k <= 4 and (4 if k == 4 else 2) in self.slot[side]:
+                return 2
+            return 3 if (k <= 3 or want == 3) else 1
+        if kept == 8 and k <= 16 and o["spmv_kernel"] in (0, 8):
+            if self.scratch_k[side] >= k:
+                return 1 if (want == 0 and k > 2 and self.choice[side].get(k) == 2) else 5
+            return 6 if k <= 2 else 1
+        if kept == 6 and k <= 2 and o["spmv_kernel"] in (0, 6):
+            return 7
+        return 1
+
+    def spmm_needs(self, k, side):
+        o, n = self._o(), 0
+        if k < 2:
+            return 0
+        if (self.code[side] == 7 and 2 <= k <= 4 and not o["strict_order"] and o["spmm_kernel"] in (0, 2) and o["spmv_kernel"] in (0, 7)
+                and (4 if k == 4 else 2) not in self.slot[side]):
+            n |= 1
+        if self.code[side] == 8 and k <= 16 and not o["strict_order"] and o["spmm_kernel"] != 1 and o["spmv_kernel"] in (0, 8):
+            if self.scratch_k[side] < k:
+                n |= 4
+            if k > 2 and o["spmm_kernel"] == 0 and k not in self.choice[side]:
+                n |= 2                                              # sweeps timed against the row kernel: reads the plain CSR
+        return n
+
+    def device_bytes(self):
+        b = [0, 0, 0]
+        for s in (0, 1) if self.has_t else (0,):
+            b[0] += 0 if self.released[s] else (12 * self.d.nnz if self.owned[s] else 0) + 64
+            b[1] += 20 * self.d.nnz if self.code[s] >= 6 else 0
+            b[2] += sum(10 * kk * self.d.nnz for kk in self.slot[s]) + 8 * self.scratch_k[s] * (self.d.nrow + self.d.ncol)
+        return tuple(b)
+
+    # -- the products ----
+    def _sides(self, side):
+        d = self.d
+        return (d.rows, d.cols, d.nrow, d.ncol) if side == 0 else (d.cols, d.rows, d.ncol, d.nrow)
+
+    def _mul(self, y, x, side, k, r0=0, r1=None):
+        lib = self.lib
+        out_idx, in_idx, n_out, n_in = self._sides(side)
+        w = 1.0 if self.d.vals is None else self.d.vals
+        X = np.array(x).reshape(n_in, k)
+        key = (side, k, x.ctypes.data)
+        if True:
+            G = X[in_idx]
+            if lib.fault == "guard value read" and n_in > 0:
+                base, off = _where(x)
+                hit = in_idx == 0
+                if hit.any():
+                    lib.fired()
+                    G = G.copy()
+                    G[hit, 0] = base[off - 1]                      # one double in front of x instead of x[0]
+            Y = np.stack([np.bincount(out_idx, weights=w * G[:, j], minlength=n_out) for j in range(k)], 1)
+        if lib.fault == "cached output":                            # the same input pointer again: the output of last time
+            old = self.last.get(key)
+            self.last[key] = Y
+            if old is not None and not np.array_equal(old.view(np.int64), Y.view(np.int64)):
+                lib.fired()
+                Y = old
+        if lib.fault == "x modified" and lib.calls >= 3 and n_in > 2:
+            lib.fired()
+            x[n_in // 2] = 1.5
+        r1 = n_out if r1 is None else r1
+        y.reshape(n_out, k)[r0:r1] = Y[r0:r1]
+        if r1 == n_out and r0 == 0:
+            base, off = _where(y)
+            if lib.fault == "store past y" and k == 1 and lib.calls >= 3:
+                lib.fired()
+                base[off + y.size] = 1.0
+            if lib.fault == "store before Y" and k > 1 and y.ctypes.data % 16 == 8:
+                lib.fired()
+                base[off - 1] = Y[0, 0]
+        lib.calls += 1
+
+    def _single(self, side, what):
+        if side and not self.has_t:
+            _raise(LC.FS_ERR_NO_TRANSPOSE, what)
+        if self.released[side] and self.kernel_code(side) < 6:
+            if self.lib.fault == "released answers" and self._o()["strict_order"]:
+                self.lib.fired()
+                return
+            _raise(LC.FS_ERR_RELEASED, what)
+
+    def spmv(self, y, x, stream=None, transposed=False):
+        if y is None or x is None:
+            _raise(LC.FS_ERR_ARG, "fs_spmv")
+        self._single(int(transposed), "fs_spmv")
+        self._mul(y, x, int(transposed), 1)
+
+    def spmv_host(self, y, x, transposed=False):
+        self.spmv(y, x, None, transposed)
+
+    def _multi(self, Y, X, k, side):
+        if side and not self.has_t:
+            _raise(LC.FS_ERR_NO_TRANSPOSE, "fs_spmm")
+        plan = self.spmm_plan(k, side)
+        self.lib.last_plan = plan
+        if plan == 1 and self.released[side]:
+            _raise(LC.FS_ERR_RELEASED, "fs_spmm")
+        return plan
+
+    def spmm(self, Y, X, k, stream=None, transposed=False):
+        if k < 1:
+            _raise(LC.FS_ERR_ARG, "fs_spmm")
+        side = int(transposed)
+        plan = self._multi(Y, X, k, side)
+        self.lib.last_plan = plan
+        self._mul(Y, X, side, k)
+        if plan == 5:
+            # the product goes through column-major scratch: columns the scratch has no room for come out stale
+            n_out = self._sides(side)[2]
+            cap = self.stale.get(side)
+            if cap is not None and cap < k:
+                self.lib.fired()
+                Y.reshape(n_out, k)[:, cap:] = 0.0
+
+    def ata(self, y, x, tmp, stream=None):
+        o = self._o()
+        if o["ata_kernel"] == 2 and not o["strict_order"] and not o["reproducible"]:
+            if self.released[0] and self.code[0] != 8:
+                _raise(LC.FS_ERR_RELEASED, "fs_ata_mul")
+            self._mul(tmp, x, 0, 1)                                 # (tmp is the caller's scratch: the fused form may use it)
+            self._mul(y, tmp, 1, 1)
+            return
+        self.build_transpose()
+        self.spmv(tmp, x)
+        self.spmv(y, tmp, None, True)
+
+    # -- in parts ----
+    def _cuts(self, side, nparts, kind):
+        n = self._sides(side)[2]
+        if kind < 6 or nparts < 2:
+            return [0] + [n] * nparts
+        return [min(n, (n * p // nparts) // 32 * 32) for p in range(nparts)] + [n]
+
+    def _bounds(self, side, nparts):
+        kind = self.kernel_code(side)
+        plans = self.part_plans[side]
+        for n, kd, rows in plans:
+            if n == nparts and kd == kind:
+                return rows
+        rows = self._cuts(side, nparts, kind)
+        if len(plans) >= 8:
+            old = plans.pop(0)
+            if self.lib.fault == "evicted cuts" and kind >= 6 and nparts > 1:
+                self.evicted = (nparts, kind, old[2])
+        plans.append((nparts, kind, rows))
+        return rows
+
+    def part_rows(self, nparts, transposed=False, k=1):
+        side = int(transposed)
+        if nparts < 1 or nparts > 64 or k < 1:
+            _raise(LC.FS_ERR_ARG, "fs_spmm_part_rows")
+        if side and not self.has_t:
+            _raise(LC.FS_ERR_NO_TRANSPOSE, "fs_spmm_part_rows")
+        if k == 1:
+            return list(self._bounds(side, nparts))
+        cut = k in (2, 4) and self.spmm_plan(k, side) == 2
+        return self._cuts(side, nparts, 7 if cut else 1)
+
+    def spmv_part(self, y, x, part, nparts, stream=None, transposed=False):
+        side = int(transposed)
+        if nparts < 1 or nparts > 64 or part < 0 or part >= nparts:
+            _raise(LC.FS_ERR_ARG, "fs_spmv_part")
+        if side and not self.has_t:
+            _raise(LC.FS_ERR_NO_TRANSPOSE, "fs_spmv_part")
+        rows = self._bounds(side, nparts)
+        ev = getattr(self, "evicted", None)
+        if ev and ev[:2] == (nparts, self.kernel_code(side)):       # the fault: the cuts of the plan that was pushed out
+            old = ev[2]
+            wrong = [old[min(p, len(old) - 2)] for p in range(nparts)] + [old[-1]]
+            if wrong != rows:
+                self.lib.fired()
+                rows = wrong
+        if rows[1] == rows[-1] and nparts > 1 or nparts == 1:
+            if part == 0:
+                self._single(side, "fs_spmv_part")
+                self._mul(y, x, side, 1)
+            return
+        self._mul(y, x, side, 1, rows[part], rows[part + 1])
+
+    def spmm_part(self, Y, X, k, part, nparts, stream=None, transposed=False):
+        side = int(transposed)
+        if k < 1 or nparts < 1 or nparts > 64 or part < 0 or part >= nparts:
+            _raise(LC.FS_ERR_ARG, "fs_spmm_part")
+        rows = self.part_rows(nparts, transposed, k)
+        plan = self._multi(Y, X, k, side) if part == 0 or rows[1] != rows[-1] else None
+        if rows[1] == rows[-1]:
+            if part == 0:
+                self.lib.last_plan = plan
+                self._mul(Y, X, side, k)
+            return
+        self._mul(Y, X, side, k, rows[part], rows[part + 1])
+
+    # -- one-time work, release, restore ----
+    def build_transpose(self, stream=None):
+        if self.has_t:
+            return
+        if self.released[0]:
+            _raise(LC.FS_ERR_RELEASED, "fs_matrix_build_transpose")
+        self.has_t = True
+
+    def prepare(self, k, stream=None, transposed=False):
+        side = int(transposed)
+        if k < 1:
+            _raise(LC.FS_ERR_ARG, "fs_matrix_prepare")
+        if side and not self.has_t:
+            _raise(LC.FS_ERR_NO_TRANSPOSE, "fs_matrix_prepare")
+        needs = self.spmm_needs(k, side)
+        if needs & 1:
+            if self.released[side]:
+                _raise(LC.FS_ERR_RELEASED, "fs_matrix_prepare")
+            self.slot[side].add(4 if k == 4 else 2)
+        if needs & 4:
+            if self.lib.fault == "scratch not grown" and 0 < self.scratch_k[side] < k:
+                self.stale[side] = self.scratch_k[side]
+            self.scratch_k[side] = max(self.scratch_k[side], k)
+        if needs & 2:
+            if self.released[side]:
+                _raise(LC.FS_ERR_RELEASED, "fs_matrix_prepare")
+            self.choice[side][k] = 1
+
+    def release_prepared(self, k=0):
+        n = 0
+        if self.lib.fault == "release_prepared keeps":
+            if any((k in (0, 2, 3) and 2 in self.slot[s]) or (k in (0, 4) and 4 in self.slot[s]) or (k == 0 and self.scratch_k[s]) for s in (0, 1)):
+                self.lib.fired()
+            return 1
+        for s in (0, 1):
+            if k in (0, 2, 3) and 2 in self.slot[s]:
+                self.slot[s].discard(2)
+                n += 1
+            if k in (0, 4) and 4 in self.slot[s]:
+                self.slot[s].discard(4)
+                n += 1
+            if self.scratch_k[s] and (k == 0 or 2 <= k <= 16):
+                self.choice[s].pop(k, None)
+                if k == 0 or not self.choice[s]:
+                    self.scratch_k[s], self.choice[s] = 0, {}
+                    self.stale.pop(s, None)
+                    n += 1
+        return n
+
+    def release_csr(self):
+        n = 0
+        for s in (0, 1) if self.has_t else (0,):
+            if self.code[s] >= 6 and not self.released[s]:
+                self.released[s] = True
+                n += 1
+        return n
+
+    def restore_csr(self, row_ptr, cols, vals=None, transposed=False, borrow=False):
+        side = int(transposed)
+        if row_ptr is None or (side and not self.has_t):
+            _raise(LC.FS_ERR_ARG, "fs_matrix_restore_csr")
+        if self.released[side]:
+            self.released[side] = False
+            self.owned[side] = not borrow
+
+    def download(self, transposed=False):
+        side = int(transposed)
+        if side and not self.has_t:
+            _raise(LC.FS_ERR_NO_TRANSPOSE, "fs_matrix_download")
+        if self.released[side]:
+            _raise(LC.FS_ERR_RELEASED, "fs_matrix_download")
+        rp, cc, vv = LC.refs_of(self.d, self.lib.nc).csr[side]
+        return rp.copy(), cc.copy(), None if vv is None else vv.copy()
+
+    def close(self):
+        self.h = None
+
+
+class StandIn:
+    """the backend of a walk: a library of StandInMatrix handles with process-wide options and, optionally, one injected fault"""
+    Error = StandInError
+
+    def __init__(self, fault=None, nc=LC.NC):
+        self.fault, self.nc = fault, nc
+        self.opt = dict(DEFAULTS)
+        self.mem = self.hostmem = LC.NumpyMem()
+        self.last_plan = 0
+        self.calls = 0
+        self.step = -1
+        self.first_fired = None
+        self.cur = 0
+
+    def fired(self):
+        if self.first_fired is None:
+            self.first_fired = self.step
+
+    def copies(self):
+        return list(COPIES)
+
+    def creation_options(self, copy):
+        return {}
+
+    def get_option(self, name):
+        return self.opt[name]
+
+    def set_option(self, name, value):
+        self.opt[name] = value
+
+    @contextlib.contextmanager
+    def options(self, **kw):
+        old = {k: self.opt[k] for k in kw}
+        try:
+            self.opt.update(kw)
+            yield
+        finally:
+            self.opt.update(old)
+
+    @contextlib.contextmanager
+    def walk_scope(self):
+        yield
+
+    def begin_step(self, i):
+        self.step = i
+
+    def stream(self):
+        return self.cur
+
+    def stream_index(self):
+        return self.cur
+
+    def switch_stream(self):
+        self.cur ^= 1
+
+    def create(self, d, copy, arrays, borrow):
+        return StandInMatrix(self, d, CODES[copy], borrow)
+
+    def kernel_code(self, A, side):
+        return A.kernel_code(side)
+
+    def has_transpose(self, A):
+        return int(A.has_t)
+
+    def ldsx_orderable(self, A, side):
+        return 1
+
+    def tiled_layout(self, A, side):
+        return 0
+
+    def spmm_plan(self, A, k, side):
+        return A.spmm_plan(k, side)
+
+    def spmm_needs(self, A, k, side, creation):
+        return A.spmm_needs(k, side)
+
+    def last_spmm_plan(self):
+        p, self.last_plan = self.last_plan, 0
+        return p
+
+    def lazy_growth(self, A):
+        return 0
+
+
+@pytest.fixture(scope="module")
+def sets():
+    return {n: LC.data_sets()[n] for n in LC.SET_NAMES}
+
+
+@pytest.fixture(scope="module")
+def gpu_walks(sets):
+    """the walks of tests/test_gpu_lifecycle.py (data set x copy x seed) on the honest stand-in, run once"""
+    return [LC.run_walk(StandIn(), sets[name], copy, seed, steps=STEPS) for name in sets for copy in COPIES for seed in SEEDS]
+
+
+def test_the_honest_stand_in_passes_walks_of_every_data_set_and_copy(sets, gpu_walks):
+    assert len(gpu_walks) == len(sets) * len(COPIES) * len(SEEDS) and all(len(w.log) > STEPS for w in gpu_walks)
+    for seed in (3, 4, 5, 6):
+        LC.run_walk(StandIn(), sets["subnormal"], "lds-staged", seed, steps=STEPS)
+
+
+# fault -> (the kind of failure the message must carry, words it must contain)
+FAULTS = {
+    "store past y": (("guard",), "1 double(s) past its end"),
+    "store before Y": (("guard",), "1 double(s) before it"),
+    "x modified": (("input modified",), "in vector of"),
+    "guard value read": (("guard value read",), "a guard value of"),
+    "evicted cuts": (("rows below the cut", "rows above the cut"), "cuts"),
+    "scratch not grown": (("not exact",), "plan 5"),
+    "released answers": (("status",), "FS_ERR_RELEASED"),
+    "release_prepared keeps": (("release_prepared", "device bytes"), "release_prepared("),
+    "cached output": (("not exact", "rows below the cut"), "differ"),
+}
+
+
+@pytest.mark.parametrize("fault", list(FAULTS))
+def test_an_injected_fault_fails_the_walk_at_the_step_where_it_first_matters(sets, fault):
+    kind, words = FAULTS[fault]
+    copy = {"scratch not grown": "lds-staged", "evicted cuts": "two-pass"}.get(fault, "two-pass")
+    kw = dict(copies=[copy], nhandles=2) if fault in ("scratch not grown", "evicted cuts", "release_prepared keeps") else {}     # (rare orders)
+    caught = 0
+    for seed in range(1, 13):
+        lib = StandIn(fault)
+        try:
+            LC.run_walk(lib, sets["wide_range"], copy, seed, steps=STEPS, **kw)
+        except LC.WalkFailure as ex:
+            assert lib.first_fired is not None, (fault, seed, str(ex))
+            assert ex.kind in kind and words in str(ex), (fault, seed, ex.kind, str(ex)[:600])
+            assert ex.step == lib.first_fired, (fault, seed, ex.step, lib.first_fired, str(ex)[:600])
+            assert f"seed {seed}" in str(ex) and f"step {ex.step}" in str(ex) and "last operations" in str(ex)
+            # the replay of the failing prefix fails at the same step, one step less passes
+            with pytest.raises(LC.WalkFailure) as again:
+                LC.run_walk(StandIn(fault), sets["wide_range"], copy, seed, steps=STEPS, upto=ex.step + 1, **kw)
+            assert again.value.step == ex.step
+            caught += 1
+        else:
+            assert lib.first_fired is None, (fault, seed, "the fault fired at step", lib.first_fired, "and the walk passed")
+    assert caught >= 2, (fault, caught)
+
+
+def test_the_operation_mix_reaches_everything(sets, gpu_walks):
+    """over the walks the GPU test runs: every operation, every predicted status, more than eight distinct nparts on one handle,
+    every k on both sides, a host-vector product directly behind a device-vector product, restores copied and borrowed"""
+    ops, status, ks, nparts, behind, restore, recovered, between = {}, {}, [set(), set()], 0, 0, set(), 0, 0
+    assert set(LC.GPU_SET_NAMES) <= set(sets)
+    for w in gpu_walks:
+        if w.data.name not in LC.GPU_SET_NAMES:
+            continue
+        c = w.counts
+        for k, v in c["ops"].items():
+            ops[k] = ops.get(k, 0) + v
+        for k, v in c["status"].items():
+            status[k] = status.get(k, 0) + v
+        for s in (0, 1):
+            ks[s] |= c["k"][s]
+        nparts = max([nparts] + list(c["nparts"].values()))
+        behind += c["host_behind_device"]
+        restore |= c["restore"]
+        recovered += c["recovered"]
+        between += c["part_between"]
+        assert sum(c["ops"].values()) == STEPS
+    missing = [o for o in LC.OPS if ops.get(o, 0) < 5]
+    assert not missing, (missing, ops)
+    for s in (LC.FS_OK, LC.FS_ERR_ARG, LC.FS_ERR_NO_TRANSPOSE, LC.FS_ERR_RELEASED):
+        assert status.get(s, 0) >= 10, status
+    assert ks[0] == set(LC.KS) and ks[1] == set(LC.KS), ks
+    assert nparts > 8, nparts
+    assert behind >= 5 and restore == {"copied", "borrowed"} and recovered >= 10 and between >= 5, (behind, restore, recovered, between)
+
+
+def test_guarded_vectors_sit_where_they_say(sets):
+    mem = LC.NumpyMem()
+    g = LC.Guarded(mem, "probe", 100)
+    for off8 in (0, 1):
+        v = g.place(37, off8)
+        assert v.ctypes.data % 16 == 8 * off8 and g.lo >= LC.GUARD and g.store.size - g.hi >= LC.GUARD
+        assert g.guards_ok() and LC.guard_tag(g.store.view(np.int64)[0]) == g.tag and np.isnan(g.store[0])
+        g.store[g.hi] = 0.0
+        assert not g.guards_ok() and "1 double(s) past its end" in g.first_broken()
+        g.place(37, off8)
+        g.store[g.lo - 1] = 0.0
+        assert not g.guards_ok() and "1 double(s) before it" in g.first_broken()
+    assert LC.guard_tag(np.float64(np.nan).view(np.int64)) is None
