@@ -47,7 +47,8 @@ enum fs_status {
   FS_ERR_ARG = -2,        /* bad argument (NULL handle, negative size, k < 1, ...)          */
   FS_ERR_NO_DEVICE = -3,  /* no gfx950 device visible                                        */
   FS_ERR_NO_TRANSPOSE = -4, /* transposed product asked for before fs_matrix_build_transpose */
-  FS_ERR_RELEASED = -5     /* the operation reads the plain CSR arrays, which fs_matrix_release_csr gave back */
+  FS_ERR_RELEASED = -5     /* the operation reads the plain CSR arrays, which fs_matrix_release_csr gave back (products that run on
+                            * them, fs_matrix_download, fs_gram_diag and fs_pcg with FS_PRECOND_JACOBI, ...: see there) */
 };
 
 enum fs_memspace { FS_HOST = 0, FS_DEVICE = 1 };
@@ -184,7 +185,8 @@ int fs_matrix_device_bytes(fs_matrix_t A, int64_t *bytes3);
  * shard: 4.8 of 12.9 GB).  Applies to A and, when built, A'; returns the number of sides released (0: no kept copy, nothing done).
  * What still needs the plain arrays afterwards fails with FS_ERR_RELEASED: strict_order and spmv_kernel 1 / 2 / 3 products, the row
  * kernel of multi-column products (k >= 5 on two-pass matrices, k > 16), fs_matrix_prepare for a new k, fs_matrix_build_transpose,
- * fs_matrix_download, the fused A'A kernel, and option "reproducible" on an LDS-staged copy that is not orderable.
+ * fs_matrix_download, the fused A'A kernel, fs_gram_diag (and with it fs_pcg with FS_PRECOND_JACOBI), and option "reproducible" on an
+ * LDS-staged copy that is not orderable.
  * fs_matrix_restore_csr hands the same arrays back (same meaning of space / borrow as fs_csr_create; they are NOT validated or
  * compared again) -- "rebuild on demand" is the caller's: the re-ordered copies do not keep the storage order of a row.
  * Option "release_csr" (FS_RELEASE_CSR, default 0) = 1 releases at the end of fs_csr_create / fs_coo_create /
@@ -215,6 +217,47 @@ int fs_cg2(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, double lam
            fs_stream_t stream);
 /* y += a x on device vectors (the "+ lambda x" of bsbm_AtA, cg.h:17-21) */
 int fs_axpy(int n, double a, const double *x, double *y, fs_stream_t stream);
+
+/* ---- preconditioned solve (no counterpart in the reference: bsbm_cg is unpreconditioned, starts from 0, reports a count) ---- */
+/* d[j] = lambda + sum of v^2 over row j of At (v = 1 for a pattern-only matrix): the diagonal of A'A + lambda I, column j of A
+ * taken from the transpose handle the caller of fs_cg already holds.  d: fs_matrix_nrow(At) doubles in HBM.  Stream-ordered, no
+ * allocation.  Reads the plain CSR: FS_ERR_RELEASED after fs_matrix_release_csr.  The sum has a fixed shape and repeats its bits:
+ * one wave per row; lane l starts at +0.0 and adds v * v (one multiply, one add, never fused) of entries l, l + 64, ... in
+ * increasing order; the 64 lanes are folded by the __shfl_xor butterfly (32, 16, ..., 1); lambda is added last. */
+int fs_gram_diag(fs_matrix_t At, double lambda, double *d, fs_stream_t stream);
+enum { FS_PRECOND_NONE = 0, FS_PRECOND_JACOBI = 1, FS_PRECOND_DIAG = 2 };
+typedef struct fs_pcg_params {
+  double tol;          /* stop at ||r|| <= tol ||b||; negative or NaN: FS_ERR_ARG */
+  int max_iter;        /* <= 0: ncol(A), the reference's cap (cg.h:55) */
+  int precond;         /* FS_PRECOND_* */
+  int warm_start;      /* 0: start from x = 0, x's contents ignored; 1: x holds x0 */
+  const double *diag;  /* FS_PRECOND_DIAG: the caller's positive diagonal, ncol doubles in HBM; else ignored */
+} fs_pcg_params;
+typedef struct fs_pcg_info {
+  int iterations;      /* counted as bsbm_cg counts */
+  int converged;
+  double rnorm, bnorm; /* sqrt of the recurrence's last r.r; sqrt(b.b) */
+} fs_pcg_info;
+/* (A'A + lambda I) x = b by conjugate gradients with a diagonal preconditioner M = diag(d): FS_PRECOND_JACOBI takes d from
+ * fs_gram_diag(At, lambda), FS_PRECOND_DIAG from the caller, FS_PRECOND_NONE has none (z is r; no such vector is read).  A, At, x, b
+ * as for fs_cg; synchronous like fs_cg; info may be NULL.  Every line is one IEEE double operation per element, `red` the
+ * two-stage sum of fs_cg:
+ *   dinv[j] = d[j] == 0 ? 1 : 1 / d[j], once per solve
+ *   cold start: x = 0, r = b;  warm start: t = A x, q = A' t, q = q + lambda x, r = b - q
+ *   bb = red(b b), rr = red(r r), stop = tol sqrt(bb);  sqrt(rr) <= stop: done, 0 iterations, x as it is (b = 0: x = 0, converged,
+ *   where fs_cg returns NaN -- the only place where FS_PRECOND_NONE from a cold start with max_iter <= 0 departs from fs_cg)
+ *   z = r dinv, p = z, rz = red(r z)
+ *   while fewer than max_iter iterations have run:
+ *     t = A p, q = A' t, q = q + lambda p, alpha = rz / red(q p), x = x + alpha p, r = r - alpha q, rr = red(r r)
+ *     sqrt(rr) <= stop: done;  else z = r dinv, rzn = red(r z), beta = rzn / rz, rz = rzn, ++iterations, p = z + beta p
+ * The scalars live on the device and the host learns of convergence one iteration behind, as in fs_cg; a solve that is done before
+ * its first iteration enqueues no product.  Per iteration the preconditioned solve moves 14 F doubles of vector traffic (dinv is
+ * read twice, z is never stored), fs_cg and FS_PRECOND_NONE 12 F.  Products add in a fixed order unless option "cg_fixed_order"
+ * is 0.  FS_ERR_ARG: a NULL A, At, x, b or prm; At not of the transposed shape; precond outside 0..2; FS_PRECOND_DIAG with a NULL
+ * diag; tol negative or NaN.  FS_ERR_RELEASED: FS_PRECOND_JACOBI on an At whose plain CSR was released -- raised before anything is
+ * written to x (FS_PRECOND_DIAG with a diagonal kept from an earlier fs_gram_diag still works on such a handle). */
+int fs_pcg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lambda, const fs_pcg_params *prm, fs_pcg_info *info,
+           fs_stream_t stream);
 
 /* ---- column-blocked binary CSR (cbcsr.h) -------------------------------------------- */
 fs_cbcsr_t fs_cbcsr_create(int nrow, int ncol, int nblocks, int colblocksize, const int *row_ptr,

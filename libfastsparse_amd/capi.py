@@ -26,7 +26,7 @@ DEVICE_API = [
     "fs_matrix_release_csr", "fs_matrix_restore_csr", "fs_matrix_release_prepared",
     "fs_matrix_prepare", "fs_matrix_spmm_plan", "fs_matrix_device_bytes", "fs_spmv_part", "fs_spmv_part_rows", "fs_spmm_part", "fs_spmm_part_rows", "fs_copy_segments",
     "fs_matrix_nrow", "fs_matrix_ncol", "fs_matrix_nnz", "fs_matrix_algorithmic_bytes", "fs_matrix_download",
-    "fs_spmv", "fs_spmv_t", "fs_spmv_host", "fs_spmv_t_host", "fs_spmm", "fs_spmm_t", "fs_ata_mul", "fs_cg", "fs_cg2", "fs_axpy",
+    "fs_spmv", "fs_spmv_t", "fs_spmv_host", "fs_spmv_t_host", "fs_spmm", "fs_spmm_t", "fs_ata_mul", "fs_cg", "fs_cg2", "fs_axpy", "fs_gram_diag", "fs_pcg",
     "fs_cbcsr_create", "fs_cbcsr_destroy", "fs_cbcsr_spmv", "fs_invalidate", "fs_release_all", "fs_cache_entries",
     "fs_synth_uniform", "fs_synth_powerlaw_lengths", "fs_synth_fill", "fs_bucket_coo", "fs_device_build_wanted",
     "fs_dist_create", "fs_dist_destroy", "fs_dist_ndev", "fs_dist_uses_rccl", "fs_dist_csr_create", "fs_dist_matrix_destroy",
@@ -57,6 +57,19 @@ REFERENCE_API = [
     # samplers of sparse.h, timing.h, omp_util.h
     "exprand", "randexp", "randsubseq", "timing", "thread_num", "nthreads", "thread_limit", "threads_init",
 ]
+
+
+FS_PRECOND_NONE, FS_PRECOND_JACOBI, FS_PRECOND_DIAG = 0, 1, 2
+
+
+class PcgParams(C.Structure):
+    """struct fs_pcg_params"""
+    _fields_ = [("tol", C.c_double), ("max_iter", C.c_int), ("precond", C.c_int), ("warm_start", C.c_int), ("diag", vp)]
+
+
+class PcgInfo(C.Structure):
+    """struct fs_pcg_info"""
+    _fields_ = [("iterations", C.c_int), ("converged", C.c_int), ("rnorm", C.c_double), ("bnorm", C.c_double)]
 
 
 class FastsparseError(RuntimeError):
@@ -130,6 +143,8 @@ def lib():
     for f in ("fs_cg", "fs_cg2"):
         getattr(L, f).argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.POINTER(C.c_int), vp]
     L.fs_axpy.argtypes = [C.c_int, C.c_double, vp, vp, vp]
+    L.fs_gram_diag.argtypes = [vp, C.c_double, vp, vp]
+    L.fs_pcg.argtypes = [vp, vp, vp, vp, C.c_double, C.POINTER(PcgParams), C.POINTER(PcgInfo), vp]
     L.fs_cbcsr_create.restype = vp
     L.fs_cbcsr_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]
     L.fs_cbcsr_destroy.argtypes = [vp]
@@ -369,6 +384,20 @@ class ColBlockMatrix:
             self.close()
         except Exception:
             pass
+
+
+def gram_diag(At, lam, d, stream=None):
+    """d = the diagonal of A'A + lam I from the handle of A' (fs_gram_diag); d: ncol(A) doubles on the device"""
+    check(lib().fs_gram_diag(At.h, float(lam), _ptr(d), stream), "fs_gram_diag")
+
+
+def pcg(A, At, x, b, lam, tol, max_iter=0, precond=FS_PRECOND_JACOBI, warm_start=False, diag=None, stream=None):
+    """(A'A + lam I) x = b by preconditioned conjugate gradients (fs_pcg) on the handles of A and A'; x, b (and diag, for
+    FS_PRECOND_DIAG) device vectors of ncol(A) doubles.  Returns the PcgInfo of the solve."""
+    prm = PcgParams(float(tol), int(max_iter), int(precond), int(bool(warm_start)), _ptr(diag))
+    info = PcgInfo()
+    check(lib().fs_pcg(A.h, At.h, _ptr(x), _ptr(b), float(lam), C.byref(prm), C.byref(info), stream), "fs_pcg")
+    return info
 
 
 _option_epoch = 0

@@ -194,7 +194,8 @@ __global__ __launch_bounds__(kRedThreads) void cg2_scale_kernel(int n, double n0
 
 // ---- the same steps with their scalars in device memory (fs_cg / fs_cg2) ---------------------------------
 // state of one solve, doubles.  One right-hand side: rsq_old, alpha, beta, stop; two: RtR[3], Alpha[4], Psi[4], tolsq
-enum { kStDone = kCgStateDone, kStIter = kCgStateIter, kStRsq = 2, kStAlpha = 3, kStBeta = 4, kStStop = 5,
+// fs_pcg: kStRsq holds r.z (rsq_old's role), kStRr the recurrence's last r.r, kStBb b.b
+enum { kStDone = kCgStateDone, kStIter = kCgStateIter, kStRsq = 2, kStAlpha = 3, kStBeta = 4, kStStop = 5, kStRr = 6, kStBb = 7,
        kSt2RtR = 2, kSt2Alpha = 5, kSt2Psi = 9, kSt2Tolsq = 13, kStDoubles = kCgStateDoubles };
 
 __device__ __forceinline__ void solve2sym_dev(double *X, const double *A, const double *RHS)  // linalg.h:77-88
@@ -213,11 +214,15 @@ __device__ __forceinline__ void solve2sym_dev(double *X, const double *A, const 
 //   MODE 2  r.r: converged -> done; else beta = rsq_new / rsq_old, rsq_old = rsq_new, ++iter
 //   MODE 3  P'KP: Alpha = solve2sym(P'KP, R'R)
 //   MODE 4  R'R new: both <= tol^2 -> done; else Psi = solve2sym(R'R, R'R new), R'R = R'R new, ++iter
+// fs_pcg (r.z in kStRsq; NV = 1 without a preconditioner, where z is r and r.z is r.r):
+//   MODE 5  {b.b, r.r}: stop = tol sqrt(b.b), iter = 0, done = (||r|| <= stop)                  (tol in `arg`)
+//   MODE 6  r.z of the first direction
+//   MODE 7  {r.r[, r.z]}: converged -> done; else beta = r.z new / r.z, r.z = r.z new, ++iter
 template <int NV, int MODE>
 __global__ __launch_bounds__(kRedThreads) void final_step_kernel(const double *__restrict__ part, int nblocks,
                                                                 double *__restrict__ red, double *__restrict__ st, double arg)
 {
-  if (MODE != 0 && st[kStDone] != 0.0) return;
+  if (MODE != 0 && MODE != 5 && st[kStDone] != 0.0) return;
   double v[NV];
 #pragma unroll
   for (int j = 0; j < NV; ++j) {
@@ -235,6 +240,17 @@ __global__ __launch_bounds__(kRedThreads) void final_step_kernel(const double *_
     const double rsq_new = red[0];
     if (sqrt(rsq_new) <= st[kStStop]) st[kStDone] = 1.0;
     else { st[kStBeta] = rsq_new / st[kStRsq]; st[kStRsq] = rsq_new; st[kStIter] += 1.0; }
+  } else if (MODE == 5) {
+    const double stop = arg * sqrt(red[0]);
+    st[kStBb] = red[0]; st[kStRr] = red[1]; st[kStStop] = stop; st[kStIter] = 0.0;
+    st[kStDone] = sqrt(red[1]) <= stop ? 1.0 : 0.0;
+  } else if (MODE == 6) {
+    st[kStRsq] = red[0];
+  } else if (MODE == 7) {
+    const double rr = red[0], rz_new = red[NV - 1];
+    st[kStRr] = rr;
+    if (sqrt(rr) <= st[kStStop]) st[kStDone] = 1.0;
+    else { st[kStBeta] = rz_new / st[kStRsq]; st[kStRsq] = rz_new; st[kStIter] += 1.0; }
   } else if (MODE == 3) {
     const double rhs[4] = {st[kSt2RtR], st[kSt2RtR + 2], st[kSt2RtR + 2], st[kSt2RtR + 1]};
     double a[4];
@@ -336,6 +352,107 @@ __global__ __launch_bounds__(kRedThreads) void cg2_direction_dev_kernel(int n, d
     const double pa = P[2 * i], pb = P[2 * i + 1];
     P[2 * i] = R[2 * i] + s0 * pa + s1 * pb;
     P[2 * i + 1] = R[2 * i + 1] + s2 * pa + s3 * pb;
+  }
+}
+
+// ---- fs_pcg: Jacobi-preconditioned CG with a warm start (one right-hand side) ----------------------------------------
+// d[row] = lambda + sum of v^2 over the row (v = 1 for a pattern-only matrix): one wave per row, the grid strides over the rows.
+// Lane l adds v * v of entries l, l + 64, ... to +0.0 in that order, the wave folds like block_sum, lambda goes in last.
+__global__ __launch_bounds__(kRedThreads) void gram_diag_kernel(int nrow, const int *__restrict__ row_ptr,
+                                                               const double *__restrict__ vals, double lambda,
+                                                               double *__restrict__ d)
+{
+  const int lane = threadIdx.x & 63;
+  const int nwaves = gridDim.x * (kRedThreads / 64);
+  for (int row = blockIdx.x * (kRedThreads / 64) + (threadIdx.x >> 6); row < nrow; row += nwaves) {   // (wave-uniform)
+    const int lo = row_ptr[row], hi = row_ptr[row + 1];
+    double s = 0.0;
+    for (int e = lo + lane; e < hi; e += 64) {
+      const double v = vals ? vals[e] : 1.0;
+      s += v * v;
+    }
+    for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m);
+    if (lane == 0) d[row] = s + lambda;
+  }
+}
+
+// dinv = 1 / d, 1 where d is 0 (an empty column with lambda = 0: r stays, as without a preconditioner); in place or not
+__global__ __launch_bounds__(kRedThreads) void pcg_dinv_kernel(int n, const double *d, double *dinv)
+{
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    const double di = d[i];
+    dinv[i] = di == 0.0 ? 1.0 : 1.0 / di;
+  }
+}
+
+// cold: x = 0, r = b.  warm (q = A'(A x) on entry): q += lambda x, r = b - q.  Partials {b.b, r.r}
+template <bool WARM>
+__global__ __launch_bounds__(kRedThreads) void pcg_init_kernel(int n, double lambda, const double *__restrict__ b,
+                                                              double *__restrict__ x, double *__restrict__ r,
+                                                              double *__restrict__ q, double *__restrict__ part)
+{
+  double v[2] = {0.0, 0.0};
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    const double bi = b[i];
+    double ri = bi;
+    if (WARM) {
+      const double qi = q[i] + lambda * x[i];
+      q[i] = qi;
+      ri = bi - qi;
+    } else {
+      x[i] = 0.0;
+    }
+    r[i] = ri;
+    v[0] += bi * bi; v[1] += ri * ri;
+  }
+  block_sum<2>(v, part);
+}
+
+// p = z = r dinv (PRE) or r, partial r.z
+template <bool PRE>
+__global__ __launch_bounds__(kRedThreads) void pcg_start_kernel(int n, const double *__restrict__ r, const double *__restrict__ dinv,
+                                                               double *__restrict__ p, double *__restrict__ part,
+                                                               const double *__restrict__ st)
+{
+  if (st[kStDone] != 0.0) return;
+  double v[1] = {0.0};
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    const double ri = r[i];
+    const double zi = PRE ? ri * dinv[i] : ri;
+    p[i] = zi;
+    v[0] += ri * zi;
+  }
+  block_sum<1>(v, part);
+}
+
+// x += alpha p, r -= alpha q, z = r dinv, partials {r.r, r.z} in one pass (without a preconditioner: cg_update_dev_kernel)
+__global__ __launch_bounds__(kRedThreads) void pcg_update_kernel(int n, double *__restrict__ x, double *__restrict__ r,
+                                                                const double *__restrict__ p, const double *__restrict__ q,
+                                                                const double *__restrict__ dinv, double *__restrict__ part,
+                                                                const double *__restrict__ st)
+{
+  if (st[kStDone] != 0.0) return;
+  const double alpha = st[kStAlpha];
+  double v[2] = {0.0, 0.0};
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    x[i] += alpha * p[i];
+    const double ri = r[i] - alpha * q[i];
+    r[i] = ri;
+    const double zi = ri * dinv[i];
+    v[0] += ri * ri; v[1] += ri * zi;
+  }
+  block_sum<2>(v, part);
+}
+
+// p = z + beta p with z = r dinv formed on the fly: no z vector is stored (without a preconditioner: cg_direction_dev_kernel)
+__global__ __launch_bounds__(kRedThreads) void pcg_direction_kernel(int n, double *__restrict__ p, const double *__restrict__ r,
+                                                                   const double *__restrict__ dinv, const double *__restrict__ st)
+{
+  if (st[kStDone] != 0.0) return;
+  const double beta = st[kStBeta];
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    const double zi = r[i] * dinv[i];
+    p[i] = zi + beta * p[i];
   }
 }
 
@@ -548,6 +665,102 @@ int fs_cg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lamb
   FS_HIP(hipStreamSynchronize(s));
   note_cg_state(fin);
   if (out_iter) *out_iter = (int)fin[kStIter];
+  return FS_OK;
+}
+
+// d[j] = lambda + sum of v^2 over row j of At = the diagonal of A'A + lambda I, from the transpose handle a caller of fs_cg holds
+// (the rows of A' are the columns of A: no atomics, no second pass over A).  Stream-ordered, no allocation.
+int fs_gram_diag(fs_matrix_t At, double lambda, double *d, fs_stream_t stream)
+{
+  FS_RANGE("fs_gram_diag");
+  if (!At || !d) { set_error("fs_gram_diag: NULL argument"); return FS_ERR_ARG; }
+  if (int rc = need_plain_csr(At->a, "fs_gram_diag")) return rc;
+  const int n = At->a.nrow, waves = kRedThreads / 64;
+  // few rows per wave; 10 M rows of 16 entries take 1.3 ms (a wave per short row is what costs, not the stride: 1.4 ms with
+  // 4096 workgroups) -- one-time work, about one iteration of the solve it serves
+  const int blocks = n / waves + 1 < (1 << 20) ? n / waves + 1 : 1 << 20;
+  hipLaunchKernelGGL(gram_diag_kernel, dim3(blocks), dim3(kRedThreads), 0, (hipStream_t)stream, n, At->a.row_ptr, At->a.vals, lambda, d);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// (A'A + lambda I) x = b by conjugate gradients with a diagonal preconditioner, a warm start and an iteration cap: see
+// include/fastsparse_hip.h for the arithmetic.  Without a preconditioner, from a cold start and with the cap at F, the iterations
+// launch fs_cg's own kernels on the same data (the scalar step of the convergence test also keeps r.r and b.b for fs_pcg_info).
+int fs_pcg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lambda, const fs_pcg_params *prm, fs_pcg_info *info,
+           fs_stream_t stream)
+{
+  FS_RANGE("fs_pcg");
+  if (!A || !At || !x || !b || !prm) { set_error("fs_pcg: NULL argument"); return FS_ERR_ARG; }
+  const int N = A->a.nrow, F = A->a.ncol;
+  if (At->a.nrow != F || At->a.ncol != N) { set_error("fs_pcg: At is not the transpose shape of A"); return FS_ERR_ARG; }
+  if (prm->precond != FS_PRECOND_NONE && prm->precond != FS_PRECOND_JACOBI && prm->precond != FS_PRECOND_DIAG) {
+    set_error("fs_pcg: precond is none of FS_PRECOND_NONE / _JACOBI / _DIAG"); return FS_ERR_ARG;
+  }
+  if (prm->precond == FS_PRECOND_DIAG && !prm->diag) { set_error("fs_pcg: FS_PRECOND_DIAG without a diagonal"); return FS_ERR_ARG; }
+  if (!(prm->tol >= 0.0)) { set_error("fs_pcg: tol is negative or NaN"); return FS_ERR_ARG; }
+  if (prm->precond == FS_PRECOND_JACOBI)                     // before anything is written to x
+    if (int rc = need_plain_csr(At->a, "fs_pcg with FS_PRECOND_JACOBI (fs_gram_diag)")) return rc;
+  const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
+  const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
+  hipStream_t s = (hipStream_t)stream;
+  FixedOrderScope fixed(options().cg_fixed_order != 0);   // the products of a solve add in a fixed order: bit-identical run to run
+  Workspace ws;
+  double *r = ws.get(F), *p = ws.get(F), *q = ws.get(F), *tmp = ws.get(N), *part = ws.get(kRedBlocks * 3), *red = ws.get(4);
+  double *dinv = pre ? ws.get(F) : nullptr;
+  double *st = ws.get(kStDoubles);
+  if (!r || !p || !q || !tmp || !part || !red || (pre && !dinv) || !st) { set_error("fs_pcg: out of device memory"); return FS_ERR_HIP; }
+  CgFlags fl;
+  if (int rc = fl.init()) return rc;
+  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
+  if (prm->precond == FS_PRECOND_JACOBI)
+    if (int rc = fs_gram_diag(At, lambda, dinv, stream)) return rc;
+  if (pre) hipLaunchKernelGGL(pcg_dinv_kernel, g, blk, 0, s, F, prm->precond == FS_PRECOND_DIAG ? prm->diag : dinv, dinv);
+  if (warm) {                                                // r = b - (A'(A x) + lambda x)
+    if (int rc = fs_spmv(A, tmp, x, stream)) return rc;
+    if (int rc = fs_spmv(At, q, tmp, stream)) return rc;
+    hipLaunchKernelGGL(pcg_init_kernel<true>, g, blk, 0, s, F, lambda, b, x, r, q, part);
+  } else {
+    hipLaunchKernelGGL(pcg_init_kernel<false>, g, blk, 0, s, F, lambda, b, x, r, q, part);
+  }
+  hipLaunchKernelGGL((final_step_kernel<2, 5>), one, blk, 0, s, part, kRedBlocks, red, st, prm->tol);   // b.b, r.r, stop, done?
+  if (pre) hipLaunchKernelGGL(pcg_start_kernel<true>, g, blk, 0, s, F, r, dinv, p, part, st);
+  else     hipLaunchKernelGGL(pcg_start_kernel<false>, g, blk, 0, s, F, r, dinv, p, part, st);
+  hipLaunchKernelGGL((final_step_kernel<1, 6>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);         // r.z
+  FS_HIP(hipGetLastError());
+  // a solve that is done before it starts (b = 0, a warm start from a converged x) enqueues no product: one look at the flag
+  FS_HIP(hipMemcpyAsync(fl.h, st + kCgStateDone, sizeof(double) * 2, hipMemcpyDeviceToHost, s));
+  FS_HIP(hipStreamSynchronize(s));
+  const bool done_at_start = fl.h[0] != 0.0;
+  for (int iter = 0; iter < cap && !done_at_start; iter++) {
+    if (int rc = fs_spmv(A, tmp, p, stream)) return rc;
+    if (int rc = fs_spmv(At, q, tmp, stream)) return rc;
+    hipLaunchKernelGGL(cg_shift_dot_dev_kernel, g, blk, 0, s, F, lambda, q, p, part, st);
+    hipLaunchKernelGGL((final_step_kernel<1, 1>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);       // alpha = r.z / p.q
+    if (pre) {
+      hipLaunchKernelGGL(pcg_update_kernel, g, blk, 0, s, F, x, r, p, q, dinv, part, st);
+      hipLaunchKernelGGL((final_step_kernel<2, 7>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);     // converged? beta
+      hipLaunchKernelGGL(pcg_direction_kernel, g, blk, 0, s, F, p, r, dinv, st);
+    } else {
+      hipLaunchKernelGGL(cg_update_dev_kernel, g, blk, 0, s, F, x, r, p, q, part, st);
+      hipLaunchKernelGGL((final_step_kernel<1, 7>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);
+      hipLaunchKernelGGL(cg_direction_dev_kernel, g, blk, 0, s, F, p, r, st);
+    }
+    FS_HIP(hipGetLastError());
+    bool stop = false;
+    if (int rc = fl.after_iteration(iter, st, s, &stop)) return rc;
+    if (stop) break;
+  }
+  double fin[kStDoubles] = {0.0};
+  FS_HIP(hipMemcpyAsync(fin, st, sizeof(fin), hipMemcpyDeviceToHost, s));
+  FS_HIP(hipStreamSynchronize(s));
+  note_cg_state(fin);
+  if (info) {
+    info->iterations = (int)fin[kStIter];
+    info->converged = fin[kStDone] != 0.0;
+    info->rnorm = sqrt(fin[kStRr]);
+    info->bnorm = sqrt(fin[kStBb]);
+  }
   return FS_OK;
 }
 
