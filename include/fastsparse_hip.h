@@ -259,6 +259,51 @@ typedef struct fs_pcg_info {
 int fs_pcg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lambda, const fs_pcg_params *prm, fs_pcg_info *info,
            fs_stream_t stream);
 
+/* ---- a ladder of lambdas in one solve (no counterpart in the reference) ---- */
+enum { FS_MSCG_MAX_SHIFTS = 16 };
+/* (A'A + lambda[i] I) x_i = b for i < m by multi-shift conjugate gradients: ONE Krylov sequence, two products per iteration
+ * whatever m is.  X: m vectors of F = ncol(A) doubles in HBM, x_i at X + i * ldx (ldx >= F); b: F doubles in HBM; lambda: m
+ * doubles on the HOST, any order, duplicates allowed; tol, max_iter as in fs_pcg_params; info: m entries or NULL (fs_pcg_info,
+ * per shift).  Cold start only, no preconditioner.  Synchronous like fs_cg.
+ * The Krylov space of A'A + lambda I from b is the same for every lambda, and the residuals of all the systems stay collinear:
+ * r_i = z_i r.  So CG runs on the smallest lambda (`base`) and every other system follows from scalar recurrences on z_i and two
+ * vector updates per iteration (Frommer; Jegerlehner, hep-lat/9612014).  Every line is one IEEE double operation per element,
+ * `red` the two-stage sum of fs_cg:
+ *   host:  base = min lambda[i];  sigma_i = lambda[i] - base            (exactly 0 for the minimum and its duplicates)
+ *   start: x_i = 0, r = p = b, P_i = b;  bb = red(b b), stop = tol sqrt(bb), rsq = bb
+ *          z_i = zp_i = 1, live_i = 1, count_i = 0, rn_i = sqrt(bb);  aprev = 1, bprev = 0
+ *          sqrt(bb) <= stop: done -- every shift converged, 0 iterations, X = 0 (b = 0 gives 0, not NaN, as in fs_pcg);
+ *          no product is enqueued
+ *   iteration n = 0, 1, ... while n < cap (max_iter <= 0: F):
+ *     t = A p, q = A' t, q = q + base p, alpha = rsq / red(q p)                                 -- fs_cg's kernels, fs_cg's bits
+ *     S1, per live shift:  u = alpha * bprev; u = u * (zp - z);  w = sigma * alpha; w = 1 + w;  v = zp * aprev; v = v * w;
+ *                          den = u + v;  zn = z * zp; zn = zn * aprev; zn = zn / den;  ratio = zn / z;  a_i = alpha * ratio
+ *     update:  r = r - alpha q, rr = red(r r);  every live shift: x_i = x_i + a_i P_i
+ *     S2:  s = sqrt(rr);  s <= stop: done (fs_cg MODE 2), else beta = rr / rsq, rsq = rr, ++iter
+ *          per live shift: rn_i = fabs(zn) * s;
+ *            !(rn_i > stop) or fabs(zn) < 2^-500 or done:  live_i = 0, converged_i = (rn_i <= stop), count_i = n   (frozen: x_i
+ *            is final)
+ *            else: b_i = ratio * ratio; b_i = beta * b_i;  zp = z, z = zn;  count_i = n + 1
+ *          aprev = alpha, bprev = beta;  no shift live any more (only a NaN gets here without `done`): done as well
+ *     direction (not done):  p = r + beta p;  every live shift: P_i = z_i r + b_i P_i   (two multiplies, one add; z_i the new one)
+ *   info[i] = { count_i, converged_i, rn_i, sqrt(bb) };  a shift still live at the cap: converged 0, count = cap
+ * A shift with sigma_i = 0 keeps z = 1 exactly (den = aprev, zn = 1, ratio = 1, a_i = alpha, b_i = beta): its P_i is p and its x_i
+ * is fs_cg's x at that lambda, bit for bit; such shifts read p and own no direction vector.  With m = 1 the solve is fs_pcg with
+ * FS_PRECOND_NONE from a cold start, info included.  Freezing is required, not an optimisation: z of a large shift underflows to
+ * 0, and the next zn would be 0 / 0; the 2^-500 guard covers tol = 0, which is legal when the cap ends the solve.  A frozen shift
+ * costs no traffic: per iteration with L live shifts of sigma != 0 the vector kernels move (12 + 5 L) F doubles, fs_cg 12 F,
+ * plus F for every further group of four such shifts (the direction kernel reads r once per group): 3 F more at L = 15.
+ * Work space per solve: 3 F + N doubles and one direction of F per shift with sigma != 0.
+ * No preconditioner: a diagonal M does not commute with the shift (M^-1 (K + sigma I) is not M^-1 K + sigma I), so the
+ * preconditioned Krylov spaces differ per lambda and one sequence cannot serve them.  No warm start: from x0 != 0 the residuals
+ * b - (K + sigma_i I) x0 are no longer collinear, which the recurrences rest on.
+ * The scalars live on the device and the host learns of convergence one iteration behind, as in fs_cg.  Products add in a fixed
+ * order unless option "cg_fixed_order" is 0.  FS_ERR_ARG, raised before anything is written to X: a NULL A, At, X, b or lambda; At
+ * not of the transposed shape; m outside 1..FS_MSCG_MAX_SHIFTS; ldx < F; tol negative or NaN; a lambda that is NaN or infinite.  A
+ * product's own error (FS_ERR_RELEASED under "strict_order" after fs_matrix_release_csr) is passed through. */
+int fs_mscg(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double *b, int m, const double *lambda,
+            double tol, int max_iter, fs_pcg_info *info, fs_stream_t stream);
+
 /* ---- column-blocked binary CSR (cbcsr.h) -------------------------------------------- */
 fs_cbcsr_t fs_cbcsr_create(int nrow, int ncol, int nblocks, int colblocksize, const int *row_ptr,
                            const int *cols, int space);

@@ -26,7 +26,7 @@ DEVICE_API = [
     "fs_matrix_release_csr", "fs_matrix_restore_csr", "fs_matrix_release_prepared",
     "fs_matrix_prepare", "fs_matrix_spmm_plan", "fs_matrix_device_bytes", "fs_spmv_part", "fs_spmv_part_rows", "fs_spmm_part", "fs_spmm_part_rows", "fs_copy_segments",
     "fs_matrix_nrow", "fs_matrix_ncol", "fs_matrix_nnz", "fs_matrix_algorithmic_bytes", "fs_matrix_download",
-    "fs_spmv", "fs_spmv_t", "fs_spmv_host", "fs_spmv_t_host", "fs_spmm", "fs_spmm_t", "fs_ata_mul", "fs_cg", "fs_cg2", "fs_axpy", "fs_gram_diag", "fs_pcg",
+    "fs_spmv", "fs_spmv_t", "fs_spmv_host", "fs_spmv_t_host", "fs_spmm", "fs_spmm_t", "fs_ata_mul", "fs_cg", "fs_cg2", "fs_axpy", "fs_gram_diag", "fs_pcg", "fs_mscg",
     "fs_cbcsr_create", "fs_cbcsr_destroy", "fs_cbcsr_spmv", "fs_invalidate", "fs_release_all", "fs_cache_entries",
     "fs_synth_uniform", "fs_synth_powerlaw_lengths", "fs_synth_fill", "fs_bucket_coo", "fs_device_build_wanted",
     "fs_dist_create", "fs_dist_destroy", "fs_dist_ndev", "fs_dist_uses_rccl", "fs_dist_csr_create", "fs_dist_matrix_destroy",
@@ -145,6 +145,7 @@ def lib():
     L.fs_axpy.argtypes = [C.c_int, C.c_double, vp, vp, vp]
     L.fs_gram_diag.argtypes = [vp, C.c_double, vp, vp]
     L.fs_pcg.argtypes = [vp, vp, vp, vp, C.c_double, C.POINTER(PcgParams), C.POINTER(PcgInfo), vp]
+    L.fs_mscg.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(PcgInfo), vp]
     L.fs_cbcsr_create.restype = vp
     L.fs_cbcsr_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]
     L.fs_cbcsr_destroy.argtypes = [vp]
@@ -398,6 +399,21 @@ def pcg(A, At, x, b, lam, tol, max_iter=0, precond=FS_PRECOND_JACOBI, warm_start
     info = PcgInfo()
     check(lib().fs_pcg(A.h, At.h, _ptr(x), _ptr(b), float(lam), C.byref(prm), C.byref(info), stream), "fs_pcg")
     return info
+
+
+def mscg(A, At, X, b, lams, tol, max_iter=0, stream=None):
+    """(A'A + lams[i] I) x_i = b for every i by multi-shift conjugate gradients (fs_mscg): one Krylov sequence, two products per
+    iteration however many lambdas.  X: device tensor (m, F) with unit inner stride (rows may be padded: ldx = X.stride(0)), b: F
+    doubles on the device, lams: m <= FS_MSCG_MAX_SHIFTS host values.  Returns the list of the m PcgInfo, one per shift."""
+    lams = [float(v) for v in lams]
+    m = len(lams)
+    if X.dim() != 2 or X.shape[0] != m or (X.shape[1] > 1 and X.stride(1) != 1):
+        raise ValueError("mscg: X must be (len(lams), F) with unit inner stride")
+    ldx = X.stride(0) if m > 1 else max(X.stride(0), X.shape[1])
+    infos = (PcgInfo * max(m, 1))()
+    check(lib().fs_mscg(A.h, At.h, X.data_ptr(), int(ldx), _ptr(b), m, (C.c_double * max(m, 1))(*lams), float(tol), int(max_iter), infos,
+                        stream), "fs_mscg")
+    return list(infos)[:m]
 
 
 _option_epoch = 0

@@ -456,6 +456,240 @@ __global__ __launch_bounds__(kRedThreads) void pcg_direction_kernel(int n, doubl
   }
 }
 
+// ---- fs_mscg: multi-shift CG, (A'A + lambda_i I) x_i = b for up to kMscgMaxShifts lambdas from ONE Krylov sequence ---------
+// The base system (the smallest lambda) runs fs_cg's iteration on fs_cg's kernels and bits; every other shift sigma_i = lambda_i -
+// base follows by scalar recurrences (include/fastsparse_hip.h spells the arithmetic out).  st[] keeps the base scalars, ms[] the
+// per-shift ones, kMsStride doubles each.  ms[k * kMsStride + kMsList], k < st[kStNBase] + st[kStNLive], is the compacted list of
+// live shifts: those with sigma = 0 first (their direction IS p: no vector of their own), then the others (direction P + pslot ldp).
+constexpr int kMscgMaxShifts = FS_MSCG_MAX_SHIFTS;
+enum { kStAprev = 8, kStBprev = 9, kStNLive = 10, kStNBase = 11 };
+enum { kMsSigma = 0, kMsZ = 1, kMsZp = 2, kMsZn = 3, kMsRatio = 4, kMsA = 5, kMsB = 6, kMsRn = 7, kMsLive = 8, kMsConverged = 9,
+       kMsCount = 10, kMsList = 11, kMsPslot = 12, kMsStride = 16 };
+constexpr int kMscgGroup = 4;              // shifts whose loads one thread keeps in flight together
+struct MscgSigma { double v[kMscgMaxShifts]; };
+
+// x_i = 0 for the m shifts, r = p = b, P = b for the nslots shifts with sigma != 0, partial b.b
+__global__ __launch_bounds__(kRedThreads) void mscg_init_kernel(int n, const double *__restrict__ b, double *__restrict__ r,
+                                                               double *__restrict__ p, double *X, long long ldx, int m, double *P,
+                                                               long long ldp, int nslots, double *__restrict__ part)
+{
+  double v[1] = {0.0};
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    const double bi = b[i];
+    r[i] = bi; p[i] = bi;
+    for (int j = 0; j < m; ++j) X[j * ldx + i] = 0.0;
+    for (int j = 0; j < nslots; ++j) P[j * ldp + i] = bi;
+    v[0] += bi * bi;
+  }
+  block_sum<1>(v, part);
+}
+
+// the compacted list of live shifts, by one thread: sigma = 0 first, then the others, each in the caller's order
+__device__ __forceinline__ void mscg_list(int m, double *__restrict__ st, double *__restrict__ ms)
+{
+  int nb = 0, nl = 0;
+  for (int i = 0; i < m; ++i)
+    if (ms[i * kMsStride + kMsLive] != 0.0 && ms[i * kMsStride + kMsSigma] == 0.0) ms[(nb++) * kMsStride + kMsList] = (double)i;
+  for (int i = 0; i < m; ++i)
+    if (ms[i * kMsStride + kMsLive] != 0.0 && ms[i * kMsStride + kMsSigma] != 0.0) ms[(nb + nl++) * kMsStride + kMsList] = (double)i;
+  st[kStNBase] = (double)nb; st[kStNLive] = (double)nl;
+  if (nb + nl == 0) st[kStDone] = 1.0;     // nothing left to iterate for (besides convergence: every shift frozen by a NaN)
+}
+
+// start: b.b, stop, the scalars of the base system and of every shift (one thread per shift)
+__global__ __launch_bounds__(kRedThreads) void mscg_start_kernel(const double *__restrict__ part, int nblocks, double *__restrict__ red,
+                                                                double *__restrict__ st, double *__restrict__ ms, double tol, int m,
+                                                                MscgSigma sg)
+{
+  double v[1] = {0.0};
+  for (int b = threadIdx.x; b < nblocks; b += kRedThreads) v[0] += part[b];
+  block_sum<1>(v, red);
+  __syncthreads();
+  const double bb = red[0];
+  const double stop = tol * sqrt(bb);
+  const bool done = sqrt(bb) <= stop;
+  if ((int)threadIdx.x < m) {
+    double *e = ms + threadIdx.x * kMsStride;
+    e[kMsSigma] = sg.v[threadIdx.x];
+    e[kMsZ] = 1.0; e[kMsZp] = 1.0; e[kMsZn] = 1.0; e[kMsRatio] = 1.0; e[kMsA] = 0.0; e[kMsB] = 0.0;
+    e[kMsRn] = sqrt(bb); e[kMsLive] = done ? 0.0 : 1.0; e[kMsConverged] = done ? 1.0 : 0.0; e[kMsCount] = 0.0;
+    e[kMsList] = -1.0; e[kMsPslot] = -1.0;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  st[kStBb] = bb; st[kStRr] = bb; st[kStRsq] = bb; st[kStStop] = stop; st[kStIter] = 0.0; st[kStDone] = done ? 1.0 : 0.0;
+  st[kStAprev] = 1.0; st[kStBprev] = 0.0;
+  int slots = 0;
+  for (int i = 0; i < m; ++i)
+    if (ms[i * kMsStride + kMsSigma] != 0.0) ms[i * kMsStride + kMsPslot] = (double)(slots++);
+  if (done) { st[kStNBase] = 0.0; st[kStNLive] = 0.0; }
+  else mscg_list(m, st, ms);
+}
+
+// S1: finishes q.p, alpha = rsq / q.p, then per live shift (one thread each) zn, ratio and the step a_i
+__global__ __launch_bounds__(kRedThreads) void mscg_s1_kernel(const double *__restrict__ part, int nblocks, double *__restrict__ red,
+                                                             double *__restrict__ st, double *__restrict__ ms, int m)
+{
+  if (st[kStDone] != 0.0) return;
+  double s[1] = {0.0};
+  for (int b = threadIdx.x; b < nblocks; b += kRedThreads) s[0] += part[b];
+  block_sum<1>(s, red);
+  __syncthreads();
+  const double alpha = st[kStRsq] / red[0];
+  if (threadIdx.x == 0) st[kStAlpha] = alpha;
+  if ((int)threadIdx.x >= m) return;
+  double *e = ms + threadIdx.x * kMsStride;
+  if (e[kMsLive] == 0.0) return;
+  const double aprev = st[kStAprev], bprev = st[kStBprev], sigma = e[kMsSigma], z = e[kMsZ], zp = e[kMsZp];
+  double u = alpha * bprev; u = u * (zp - z);
+  double w = sigma * alpha; w = 1.0 + w;
+  double v = zp * aprev; v = v * w;
+  const double den = u + v;
+  double zn = z * zp; zn = zn * aprev; zn = zn / den;
+  const double ratio = zn / z;
+  e[kMsZn] = zn; e[kMsRatio] = ratio; e[kMsA] = alpha * ratio;
+}
+
+// update: r = r - alpha q with the partials of r.r in cg_update_dev_kernel's shape, x_i = x_i + a_i P_i for every live shift, kMscgGroup
+// shifts at a time (CNT of them in this group: their loads are in flight together); the first group rides in the pass over r and
+// q (FIRST).  A shift with sigma = 0 reads p.  Frozen shifts are not in the list: they cost no traffic.
+template <int CNT, bool FIRST>
+__device__ __forceinline__ void mscg_update_group(int n, int k0, double alpha, double *__restrict__ r, const double *__restrict__ p,
+                                                  const double *__restrict__ q, double *X, long long ldx, const double *P,
+                                                  long long ldp, const double *__restrict__ ms, double &sum)
+{
+  double av[CNT + 1]; double *xp[CNT + 1]; const double *pp[CNT + 1];
+#pragma unroll
+  for (int u = 0; u < CNT; ++u) {
+    const int sh = __builtin_amdgcn_readfirstlane((int)ms[(k0 + u) * kMsStride + kMsList]);
+    const int slot = __builtin_amdgcn_readfirstlane((int)ms[sh * kMsStride + kMsPslot]);
+    av[u] = ms[sh * kMsStride + kMsA];
+    xp[u] = X + sh * ldx;
+    pp[u] = slot < 0 ? p : P + slot * ldp;
+  }
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    double pv[CNT + 1], xv[CNT + 1];
+#pragma unroll
+    for (int u = 0; u < CNT; ++u) { pv[u] = pp[u][i]; xv[u] = xp[u][i]; }
+    if (FIRST) {
+      const double ri = r[i] - alpha * q[i];
+      r[i] = ri;
+      sum += ri * ri;
+    }
+#pragma unroll
+    for (int u = 0; u < CNT; ++u) xp[u][i] = xv[u] + av[u] * pv[u];
+  }
+}
+
+template <bool FIRST, typename... T>
+__device__ __forceinline__ void mscg_update_groups(int cnt, T &&...a)
+{
+  if (cnt >= 4)      mscg_update_group<4, FIRST>(a...);
+  else if (cnt == 3) mscg_update_group<3, FIRST>(a...);
+  else if (cnt == 2) mscg_update_group<2, FIRST>(a...);
+  else if (cnt == 1) mscg_update_group<1, FIRST>(a...);
+  else if (FIRST)    mscg_update_group<0, FIRST>(a...);
+}
+
+__global__ __launch_bounds__(kRedThreads) void mscg_update_kernel(int n, double *__restrict__ r, const double *__restrict__ p,
+                                                                 const double *__restrict__ q, double *X, long long ldx,
+                                                                 const double *P, long long ldp, double *__restrict__ part,
+                                                                 const double *__restrict__ st, const double *__restrict__ ms)
+{
+  static_assert(kMscgGroup == 4, "mscg_update_groups dispatches on 0..4");
+  if (st[kStDone] != 0.0) return;
+  const double alpha = st[kStAlpha];
+  const int nall = __builtin_amdgcn_readfirstlane((int)st[kStNBase] + (int)st[kStNLive]);
+  double v[1] = {0.0};
+  mscg_update_groups<true>(nall, n, 0, alpha, r, p, q, X, ldx, P, ldp, ms, v[0]);
+  for (int k0 = kMscgGroup; k0 < nall; k0 += kMscgGroup) mscg_update_groups<false>(nall - k0, n, k0, alpha, r, p, q, X, ldx, P, ldp, ms, v[0]);
+  block_sum<1>(v, part);
+}
+
+// S2: finishes r.r; the base system's convergence test and beta (fs_cg MODE 2, fs_pcg's r.r kept); per live shift (one thread
+// each) its residual norm, freeze or b_i and the new z; then the list of the shifts that stay live
+__global__ __launch_bounds__(kRedThreads) void mscg_s2_kernel(const double *__restrict__ part, int nblocks, double *__restrict__ red,
+                                                             double *__restrict__ st, double *__restrict__ ms, int m)
+{
+  if (st[kStDone] != 0.0) return;
+  double v[1] = {0.0};
+  for (int b = threadIdx.x; b < nblocks; b += kRedThreads) v[0] += part[b];
+  block_sum<1>(v, red);
+  __syncthreads();
+  const double rr = red[0], rsq = st[kStRsq], stop = st[kStStop], alpha = st[kStAlpha], n = st[kStIter];
+  const double s = sqrt(rr);
+  const bool done = s <= stop;
+  const double beta = rr / rsq;
+  __syncthreads();                         // every thread has read st[] before thread 0 moves it on
+  if (threadIdx.x == 0) {
+    st[kStRr] = rr;
+    if (done) st[kStDone] = 1.0;
+    else { st[kStBeta] = beta; st[kStRsq] = rr; st[kStIter] = n + 1.0; st[kStAprev] = alpha; st[kStBprev] = beta; }
+  }
+  if ((int)threadIdx.x < m) {
+    double *e = ms + threadIdx.x * kMsStride;
+    if (e[kMsLive] != 0.0) {
+      const double zn = e[kMsZn], ratio = e[kMsRatio];
+      const double rn = fabs(zn) * s;
+      e[kMsRn] = rn;
+      if (!(rn > stop) || fabs(zn) < 0x1p-500 || done) {
+        e[kMsLive] = 0.0; e[kMsConverged] = rn <= stop ? 1.0 : 0.0; e[kMsCount] = n;
+      } else {
+        double bi = ratio * ratio; bi = beta * bi;
+        e[kMsB] = bi; e[kMsZp] = e[kMsZ]; e[kMsZ] = zn; e[kMsCount] = n + 1.0;
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && !done) mscg_list(m, st, ms);
+}
+
+// direction: p = r + beta p, P_i = z_i r + b_i P_i for every live shift with sigma != 0 (z_i the new one), kMscgGroup shifts at a
+// time; the first group rides in the pass over r and p (FIRST).  `at` is the group's place in the list.
+template <int CNT, bool FIRST>
+__device__ __forceinline__ void mscg_direction_group(int n, int at, double beta, double *__restrict__ p, const double *__restrict__ r,
+                                                     double *P, long long ldp, const double *__restrict__ ms)
+{
+  double zv[CNT + 1], bv[CNT + 1]; double *pp[CNT + 1];
+#pragma unroll
+  for (int u = 0; u < CNT; ++u) {
+    const int sh = __builtin_amdgcn_readfirstlane((int)ms[(at + u) * kMsStride + kMsList]);
+    const int slot = __builtin_amdgcn_readfirstlane((int)ms[sh * kMsStride + kMsPslot]);
+    zv[u] = ms[sh * kMsStride + kMsZ]; bv[u] = ms[sh * kMsStride + kMsB];
+    pp[u] = P + slot * ldp;
+  }
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    double pv[CNT + 1];
+#pragma unroll
+    for (int u = 0; u < CNT; ++u) pv[u] = pp[u][i];
+    const double ri = r[i];
+    if (FIRST) p[i] = ri + beta * p[i];
+#pragma unroll
+    for (int u = 0; u < CNT; ++u) { const double t1 = zv[u] * ri, t2 = bv[u] * pv[u]; pp[u][i] = t1 + t2; }
+  }
+}
+
+template <bool FIRST, typename... T>
+__device__ __forceinline__ void mscg_direction_groups(int cnt, T &&...a)
+{
+  if (cnt >= 4)      mscg_direction_group<4, FIRST>(a...);
+  else if (cnt == 3) mscg_direction_group<3, FIRST>(a...);
+  else if (cnt == 2) mscg_direction_group<2, FIRST>(a...);
+  else if (cnt == 1) mscg_direction_group<1, FIRST>(a...);
+  else if (FIRST)    mscg_direction_group<0, FIRST>(a...);
+}
+
+__global__ __launch_bounds__(kRedThreads) void mscg_direction_kernel(int n, double *__restrict__ p, const double *__restrict__ r,
+                                                                    double *P, long long ldp, const double *__restrict__ st,
+                                                                    const double *__restrict__ ms)
+{
+  if (st[kStDone] != 0.0) return;
+  const double beta = st[kStBeta];
+  const int nb = __builtin_amdgcn_readfirstlane((int)st[kStNBase]), nl = __builtin_amdgcn_readfirstlane((int)st[kStNLive]);
+  mscg_direction_groups<true>(nl, n, nb, beta, p, r, P, ldp, ms);
+  for (int k0 = kMscgGroup; k0 < nl; k0 += kMscgGroup) mscg_direction_groups<false>(nl - k0, n, nb + k0, beta, p, r, P, ldp, ms);
+}
+
 struct Workspace {
   std::vector<void *> bufs;
   double *get(size_t n)
@@ -583,6 +817,9 @@ int cg2_dev_finish(int n, const double *norms, double *X, hipStream_t s)        
 
 static thread_local double g_last_cg_state[kStDoubles];
 static thread_local bool g_last_cg_state_set = false;
+
+static thread_local double g_last_mscg_state[kMscgMaxShifts * kMsStride];
+static thread_local int g_last_mscg_doubles = 0;
 
 void note_cg_state(const double *st_host)
 {
@@ -764,6 +1001,77 @@ int fs_pcg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lam
   return FS_OK;
 }
 
+// (A'A + lambda[i] I) x_i = b for i < m by multi-shift conjugate gradients: one Krylov sequence on the smallest lambda, two products
+// per iteration whatever m is; see include/fastsparse_hip.h for the arithmetic.  The base system's steps are fs_cg's (its kernels
+// for q += base p and the partial sums' shape for r.r), so the columns of the smallest lambda have fs_cg's bits.
+int fs_mscg(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double *b, int m, const double *lambda, double tol,
+            int max_iter, fs_pcg_info *info, fs_stream_t stream)
+{
+  FS_RANGE("fs_mscg");
+  if (!A || !At || !X || !b || !lambda) { set_error("fs_mscg: NULL argument"); return FS_ERR_ARG; }
+  const int N = A->a.nrow, F = A->a.ncol;
+  if (At->a.nrow != F || At->a.ncol != N) { set_error("fs_mscg: At is not the transpose shape of A"); return FS_ERR_ARG; }
+  if (m < 1 || m > kMscgMaxShifts) { set_error("fs_mscg: m outside 1..FS_MSCG_MAX_SHIFTS"); return FS_ERR_ARG; }
+  if (ldx < F) { set_error("fs_mscg: ldx < ncol(A)"); return FS_ERR_ARG; }
+  if (!(tol >= 0.0)) { set_error("fs_mscg: tol is negative or NaN"); return FS_ERR_ARG; }
+  for (int i = 0; i < m; ++i)
+    if (!isfinite(lambda[i])) { set_error("fs_mscg: a lambda is NaN or infinite"); return FS_ERR_ARG; }
+  double base = lambda[0];
+  for (int i = 1; i < m; ++i) if (lambda[i] < base) base = lambda[i];
+  MscgSigma sg;
+  int nslots = 0;
+  for (int i = 0; i < kMscgMaxShifts; ++i) {
+    sg.v[i] = i < m ? lambda[i] - base : 0.0;                 // exactly 0 for the minimum and its duplicates
+    if (sg.v[i] != 0.0) ++nslots;
+  }
+  const int cap = max_iter > 0 ? max_iter : F;               // cg.h:55
+  const long long ldp = ((long long)F + 1) & ~1LL;           // every P_i 16-byte aligned
+  hipStream_t s = (hipStream_t)stream;
+  FixedOrderScope fixed(options().cg_fixed_order != 0);   // the products of a solve add in a fixed order: bit-identical run to run
+  Workspace ws;
+  double *r = ws.get(F), *p = ws.get(F), *q = ws.get(F), *tmp = ws.get(N), *part = ws.get(kRedBlocks * 3), *red = ws.get(4);
+  double *P = ws.get((size_t)ldp * nslots), *st = ws.get(kStDoubles), *ms = ws.get(kMscgMaxShifts * kMsStride);
+  if (!r || !p || !q || !tmp || !part || !red || !P || !st || !ms) { set_error("fs_mscg: out of device memory"); return FS_ERR_HIP; }
+  CgFlags fl;
+  if (int rc = fl.init()) return rc;
+  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
+  hipLaunchKernelGGL(mscg_init_kernel, g, blk, 0, s, F, b, r, p, X, (long long)ldx, m, P, ldp, nslots, part);
+  hipLaunchKernelGGL(mscg_start_kernel, one, blk, 0, s, part, kRedBlocks, red, st, ms, tol, m, sg);
+  FS_HIP(hipGetLastError());
+  // a solve that is done before it starts (b = 0) enqueues no product: one look at the flag
+  FS_HIP(hipMemcpyAsync(fl.h, st + kCgStateDone, sizeof(double) * 2, hipMemcpyDeviceToHost, s));
+  FS_HIP(hipStreamSynchronize(s));
+  const bool done_at_start = fl.h[0] != 0.0;
+  for (int iter = 0; iter < cap && !done_at_start; iter++) {
+    if (int rc = fs_spmv(A, tmp, p, stream)) return rc;
+    if (int rc = fs_spmv(At, q, tmp, stream)) return rc;
+    hipLaunchKernelGGL(cg_shift_dot_dev_kernel, g, blk, 0, s, F, base, q, p, part, st);
+    hipLaunchKernelGGL(mscg_s1_kernel, one, blk, 0, s, part, kRedBlocks, red, st, ms, m);               // alpha, the a_i
+    hipLaunchKernelGGL(mscg_update_kernel, g, blk, 0, s, F, r, p, q, X, (long long)ldx, P, ldp, part, st, ms);
+    hipLaunchKernelGGL(mscg_s2_kernel, one, blk, 0, s, part, kRedBlocks, red, st, ms, m);               // converged? beta, freezes
+    hipLaunchKernelGGL(mscg_direction_kernel, g, blk, 0, s, F, p, r, P, ldp, st, ms);
+    FS_HIP(hipGetLastError());
+    bool stop = false;
+    if (int rc = fl.after_iteration(iter, st, s, &stop)) return rc;
+    if (stop) break;
+  }
+  double fin[kStDoubles] = {0.0}, fms[kMscgMaxShifts * kMsStride] = {0.0};
+  FS_HIP(hipMemcpyAsync(fin, st, sizeof(fin), hipMemcpyDeviceToHost, s));
+  FS_HIP(hipMemcpyAsync(fms, ms, sizeof(double) * m * kMsStride, hipMemcpyDeviceToHost, s));
+  FS_HIP(hipStreamSynchronize(s));
+  note_cg_state(fin);
+  for (int i = 0; i < m * kMsStride; ++i) g_last_mscg_state[i] = fms[i];
+  g_last_mscg_doubles = m * kMsStride;
+  for (int i = 0; info && i < m; ++i) {
+    const double *e = fms + i * kMsStride;
+    info[i].iterations = (int)e[kMsCount];                   // a shift still live at the cap: count = cap, converged 0
+    info[i].converged = e[kMsConverged] != 0.0;
+    info[i].rnorm = e[kMsRn];
+    info[i].bnorm = sqrt(fin[kStBb]);
+  }
+  return FS_OK;
+}
+
 // two right-hand sides, X and B row-major F x 2 (cg.h:85-187)
 int fs_cg2(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, double lambda, double tol, int *out_iter,
            fs_stream_t stream)
@@ -814,6 +1122,16 @@ int fs_debug_last_cg_state(double *out)
   if (!g_last_cg_state_set) return 0;
   for (int i = 0; i < kStDoubles; ++i) out[i] = g_last_cg_state[i];
   return kStDoubles;
+}
+
+// the final per-shift array of the last fs_mscg on the calling thread: m * kMsStride doubles (layout of the kMs enum), at most
+// max_doubles of them.  Returns the number of doubles written, 0 before the first solve.  Diagnostics, not in the header.
+int fs_debug_last_mscg_state(double *out, int max_doubles)
+{
+  if (!out || max_doubles < 0) { set_error("fs_debug_last_mscg_state: bad argument"); return FS_ERR_ARG; }
+  const int n = g_last_mscg_doubles < max_doubles ? g_last_mscg_doubles : max_doubles;
+  for (int i = 0; i < n; ++i) out[i] = g_last_mscg_state[i];
+  return n;
 }
 
 }  // extern "C"
