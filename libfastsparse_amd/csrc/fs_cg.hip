@@ -7,7 +7,7 @@
 // there: nothing in an iteration waits for the host.  The host only has to learn WHEN to stop enqueuing: the
 // "done" flag of iteration i is copied to pinned memory behind it and looked at while iteration i + 1 runs; the
 // vector kernels of iterations enqueued past the end see the flag and do nothing (their products are wasted
-// work: at most two iterations' worth).  Round 2 fetched every reduction to the host: two stream
+// work: at most two iterations' worth).  Fetching every reduction to the host instead costs two stream
 // synchronisations per iteration, 0.1-0.2 ms of idle GPU in a 1.5 ms iteration.
 //
 // Reductions are two-stage with a fixed shape (1024 workgroup partials, then one workgroup), so results are
@@ -43,9 +43,10 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double *__restrict__ 
   }
 }
 
-template <int NV>
-__global__ __launch_bounds__(kRedThreads) void final_sum_kernel(const double *__restrict__ part, int nblocks,
-                                                               double *__restrict__ out)
+// the one workgroup that finishes a reduction: the nblocks partials of stage 1 -> red[0..NV), which every thread may read on
+// return (SYNC; a kernel that ends here needs no barrier)
+template <int NV, bool SYNC = true>
+__device__ __forceinline__ void finish_sum(const double *__restrict__ part, int nblocks, double *__restrict__ red)
 {
   double v[NV];
 #pragma unroll
@@ -53,7 +54,15 @@ __global__ __launch_bounds__(kRedThreads) void final_sum_kernel(const double *__
     v[j] = 0.0;
     for (int b = threadIdx.x; b < nblocks; b += kRedThreads) v[j] += part[b * NV + j];
   }
-  block_sum<NV>(v, out);  // gridDim == 1: out[0..NV)
+  block_sum<NV>(v, red);  // gridDim == 1: red[0..NV)
+  if (SYNC) __syncthreads();
+}
+
+template <int NV>
+__global__ __launch_bounds__(kRedThreads) void final_sum_kernel(const double *__restrict__ part, int nblocks,
+                                                               double *__restrict__ out)
+{
+  finish_sum<NV, false>(part, nblocks, out);
 }
 
 // ---- one right-hand side --------------------------------------------------------------------------------
@@ -69,42 +78,6 @@ __global__ __launch_bounds__(kRedThreads) void cg_init_kernel(int n, const doubl
     v[0] += bi * bi;
   }
   block_sum<1>(v, part);
-}
-
-// q += lambda p, partial q.p                                      (cg.h:17-21, :59)
-__global__ __launch_bounds__(kRedThreads) void cg_shift_dot_kernel(int n, double lambda, double *__restrict__ q,
-                                                                  const double *__restrict__ p, double *__restrict__ part)
-{
-  double v[1] = {0.0};
-  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
-    const double pi = p[i];
-    const double qi = q[i] + lambda * pi;
-    q[i] = qi;
-    v[0] += qi * pi;
-  }
-  block_sum<1>(v, part);
-}
-
-// x += alpha p, r -= alpha q, partial r.r                         (cg.h:61-67)
-__global__ __launch_bounds__(kRedThreads) void cg_update_kernel(int n, double alpha, double *__restrict__ x,
-                                                               double *__restrict__ r, const double *__restrict__ p,
-                                                               const double *__restrict__ q, double *__restrict__ part)
-{
-  double v[1] = {0.0};
-  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
-    x[i] += alpha * p[i];
-    const double ri = r[i] - alpha * q[i];
-    r[i] = ri;
-    v[0] += ri * ri;
-  }
-  block_sum<1>(v, part);
-}
-
-// p = r + beta p                                                  (cg.h:71-75)
-__global__ __launch_bounds__(kRedThreads) void cg_direction_kernel(int n, double beta, double *__restrict__ p,
-                                                                  const double *__restrict__ r)
-{
-  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) p[i] = r[i] + beta * p[i];
 }
 
 // ---- two right-hand sides, row-major -------------------------------------------------------------------
@@ -135,49 +108,6 @@ __global__ __launch_bounds__(kRedThreads) void cg2_init_kernel(int n, double in0
   block_sum<3>(v, part);
 }
 
-// Q += lambda P, partial P'Q (symmetric form)                      (cg.h:136-142)
-__global__ __launch_bounds__(kRedThreads) void cg2_shift_dot_kernel(int n, double lambda, double *__restrict__ Q,
-                                                                   const double *__restrict__ P, double *__restrict__ part)
-{
-  double v[3] = {0.0, 0.0, 0.0};
-  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
-    const double pa = P[2 * i], pb = P[2 * i + 1];
-    const double qa = Q[2 * i] + lambda * pa, qb = Q[2 * i + 1] + lambda * pb;
-    Q[2 * i] = qa; Q[2 * i + 1] = qb;
-    v[0] += pa * qa; v[1] += pb * qb; v[2] += pa * qb;
-  }
-  block_sum<3>(v, part);
-}
-
-// X += Alpha' P, R -= Alpha' Q, partial R'R                        (cg.h:148-157)
-__global__ __launch_bounds__(kRedThreads) void cg2_update_kernel(int n, double a0, double a1, double a2, double a3,
-                                                                double *__restrict__ X, double *__restrict__ R,
-                                                                const double *__restrict__ P, const double *__restrict__ Q,
-                                                                double *__restrict__ part)
-{
-  double v[3] = {0.0, 0.0, 0.0};
-  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
-    const double pa = P[2 * i], pb = P[2 * i + 1], qa = Q[2 * i], qb = Q[2 * i + 1];
-    X[2 * i] += a0 * pa + a1 * pb;
-    X[2 * i + 1] += a2 * pa + a3 * pb;
-    const double ra = R[2 * i] - (a0 * qa + a1 * qb), rb = R[2 * i + 1] - (a2 * qa + a3 * qb);
-    R[2 * i] = ra; R[2 * i + 1] = rb;
-    v[0] += ra * ra; v[1] += rb * rb; v[2] += ra * rb;
-  }
-  block_sum<3>(v, part);
-}
-
-// P = R + Psi' P                                                   (cg.h:165-171)
-__global__ __launch_bounds__(kRedThreads) void cg2_direction_kernel(int n, double s0, double s1, double s2, double s3,
-                                                                   double *__restrict__ P, const double *__restrict__ R)
-{
-  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
-    const double pa = P[2 * i], pb = P[2 * i + 1];
-    P[2 * i] = R[2 * i] + s0 * pa + s1 * pb;
-    P[2 * i + 1] = R[2 * i + 1] + s2 * pa + s3 * pb;
-  }
-}
-
 // y += a x
 __global__ __launch_bounds__(kRedThreads) void axpy_kernel(int n, double a, const double *__restrict__ x, double *__restrict__ y)
 {
@@ -192,7 +122,7 @@ __global__ __launch_bounds__(kRedThreads) void cg2_scale_kernel(int n, double n0
   }
 }
 
-// ---- the same steps with their scalars in device memory (fs_cg / fs_cg2) ---------------------------------
+// ---- the steps of an iteration, their scalars in device memory ---------------------------------------------
 // state of one solve, doubles.  One right-hand side: rsq_old, alpha, beta, stop; two: RtR[3], Alpha[4], Psi[4], tolsq
 // fs_pcg: kStRsq holds r.z (rsq_old's role), kStRr the recurrence's last r.r, kStBb b.b
 enum { kStDone = kCgStateDone, kStIter = kCgStateIter, kStRsq = 2, kStAlpha = 3, kStBeta = 4, kStStop = 5, kStRr = 6, kStBb = 7,
@@ -208,55 +138,30 @@ __device__ __forceinline__ void solve2sym_dev(double *X, const double *A, const 
   X[3] = i2 * RHS[2] + i1 * RHS[3];
 }
 
-// the one workgroup that finishes a reduction, then does the iteration's scalar step (cg.h:59-76, 143-172):
-//   MODE 0  b.b: rsq_old, stop = tol sqrt(b.b), done = 0, iter = 0           (tol in `arg`)
-//   MODE 1  p.q: alpha = rsq_old / p.q
-//   MODE 2  r.r: converged -> done; else beta = rsq_new / rsq_old, rsq_old = rsq_new, ++iter
-//   MODE 3  P'KP: Alpha = solve2sym(P'KP, R'R)
-//   MODE 4  R'R new: both <= tol^2 -> done; else Psi = solve2sym(R'R, R'R new), R'R = R'R new, ++iter
-// fs_pcg (r.z in kStRsq; NV = 1 without a preconditioner, where z is r and r.z is r.r):
-//   MODE 5  {b.b, r.r}: stop = tol sqrt(b.b), iter = 0, done = (||r|| <= stop)                  (tol in `arg`)
-//   MODE 6  r.z of the first direction
-//   MODE 7  {r.r[, r.z]}: converged -> done; else beta = r.z new / r.z, r.z = r.z new, ++iter
-template <int NV, int MODE>
+// the one workgroup that finishes a reduction, then does the iteration's scalar step STEP (CgStep, fs_common.h; cg.h:59-76,
+// 143-172).  tol in `arg` for the two start steps.  fs_pcg keeps r.z in kStRsq; its steps run with NV = 1 without a
+// preconditioner, where z is r and r.z is r.r
+template <int NV, CgStep STEP>
 __global__ __launch_bounds__(kRedThreads) void final_step_kernel(const double *__restrict__ part, int nblocks,
                                                                 double *__restrict__ red, double *__restrict__ st, double arg)
 {
-  if (MODE != 0 && MODE != 5 && st[kStDone] != 0.0) return;
-  double v[NV];
-#pragma unroll
-  for (int j = 0; j < NV; ++j) {
-    v[j] = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += kRedThreads) v[j] += part[b * NV + j];
-  }
-  block_sum<NV>(v, red);
-  __syncthreads();
+  if (STEP != kStepCgStart && STEP != kStepPcgStart && st[kStDone] != 0.0) return;
+  finish_sum<NV>(part, nblocks, red);
   if (threadIdx.x != 0) return;
-  if (MODE == 0) {
+  if (STEP == kStepCgStart) {
     st[kStRsq] = red[0]; st[kStStop] = arg * sqrt(red[0]); st[kStDone] = 0.0; st[kStIter] = 0.0;
-  } else if (MODE == 1) {
+  } else if (STEP == kStepCgAlpha) {
     st[kStAlpha] = st[kStRsq] / red[0];
-  } else if (MODE == 2) {
+  } else if (STEP == kStepCgBeta) {
     const double rsq_new = red[0];
     if (sqrt(rsq_new) <= st[kStStop]) st[kStDone] = 1.0;
     else { st[kStBeta] = rsq_new / st[kStRsq]; st[kStRsq] = rsq_new; st[kStIter] += 1.0; }
-  } else if (MODE == 5) {
-    const double stop = arg * sqrt(red[0]);
-    st[kStBb] = red[0]; st[kStRr] = red[1]; st[kStStop] = stop; st[kStIter] = 0.0;
-    st[kStDone] = sqrt(red[1]) <= stop ? 1.0 : 0.0;
-  } else if (MODE == 6) {
-    st[kStRsq] = red[0];
-  } else if (MODE == 7) {
-    const double rr = red[0], rz_new = red[NV - 1];
-    st[kStRr] = rr;
-    if (sqrt(rr) <= st[kStStop]) st[kStDone] = 1.0;
-    else { st[kStBeta] = rz_new / st[kStRsq]; st[kStRsq] = rz_new; st[kStIter] += 1.0; }
-  } else if (MODE == 3) {
+  } else if (STEP == kStepCg2Alpha) {
     const double rhs[4] = {st[kSt2RtR], st[kSt2RtR + 2], st[kSt2RtR + 2], st[kSt2RtR + 1]};
     double a[4];
     solve2sym_dev(a, red, rhs);
     st[kSt2Alpha] = a[0]; st[kSt2Alpha + 1] = a[1]; st[kSt2Alpha + 2] = a[2]; st[kSt2Alpha + 3] = a[3];
-  } else {
+  } else if (STEP == kStepCg2Psi) {
     const double n0 = red[0], n1 = red[1], n2 = red[2], tolsq = st[kSt2Tolsq];
     if (n0 <= tolsq && n1 <= tolsq) st[kStDone] = 1.0;
     else {
@@ -268,9 +173,21 @@ __global__ __launch_bounds__(kRedThreads) void final_step_kernel(const double *_
       st[kSt2RtR] = n0; st[kSt2RtR + 1] = n1; st[kSt2RtR + 2] = n2;
       st[kStIter] += 1.0;
     }
+  } else if (STEP == kStepPcgStart) {
+    const double stop = arg * sqrt(red[0]);
+    st[kStBb] = red[0]; st[kStRr] = red[1]; st[kStStop] = stop; st[kStIter] = 0.0;
+    st[kStDone] = sqrt(red[1]) <= stop ? 1.0 : 0.0;
+  } else if (STEP == kStepPcgRz) {
+    st[kStRsq] = red[0];
+  } else if (STEP == kStepPcgBeta) {
+    const double rr = red[0], rz_new = red[NV - 1];
+    st[kStRr] = rr;
+    if (sqrt(rr) <= st[kStStop]) st[kStDone] = 1.0;
+    else { st[kStBeta] = rz_new / st[kStRsq]; st[kStRsq] = rz_new; st[kStIter] += 1.0; }
   }
 }
 
+// q += lambda p, partial q.p                                      (cg.h:17-21, :59)
 __global__ __launch_bounds__(kRedThreads) void cg_shift_dot_dev_kernel(int n, double lambda, double *__restrict__ q,
                                                                       const double *__restrict__ p, double *__restrict__ part,
                                                                       const double *__restrict__ st)
@@ -286,6 +203,7 @@ __global__ __launch_bounds__(kRedThreads) void cg_shift_dot_dev_kernel(int n, do
   block_sum<1>(v, part);
 }
 
+// x += alpha p, r -= alpha q, partial r.r                         (cg.h:61-67)
 __global__ __launch_bounds__(kRedThreads) void cg_update_dev_kernel(int n, double *__restrict__ x, double *__restrict__ r,
                                                                    const double *__restrict__ p, const double *__restrict__ q,
                                                                    double *__restrict__ part, const double *__restrict__ st)
@@ -302,6 +220,7 @@ __global__ __launch_bounds__(kRedThreads) void cg_update_dev_kernel(int n, doubl
   block_sum<1>(v, part);
 }
 
+// p = r + beta p                                                  (cg.h:71-75)
 __global__ __launch_bounds__(kRedThreads) void cg_direction_dev_kernel(int n, double *__restrict__ p, const double *__restrict__ r,
                                                                       const double *__restrict__ st)
 {
@@ -310,6 +229,7 @@ __global__ __launch_bounds__(kRedThreads) void cg_direction_dev_kernel(int n, do
   for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) p[i] = r[i] + beta * p[i];
 }
 
+// Q += lambda P, partial P'Q (symmetric form)                      (cg.h:136-142)
 __global__ __launch_bounds__(kRedThreads) void cg2_shift_dot_dev_kernel(int n, double lambda, double *__restrict__ Q,
                                                                        const double *__restrict__ P, double *__restrict__ part,
                                                                        const double *__restrict__ st)
@@ -325,6 +245,7 @@ __global__ __launch_bounds__(kRedThreads) void cg2_shift_dot_dev_kernel(int n, d
   block_sum<3>(v, part);
 }
 
+// X += Alpha' P, R -= Alpha' Q, partial R'R                        (cg.h:148-157)
 __global__ __launch_bounds__(kRedThreads) void cg2_update_dev_kernel(int n, double *__restrict__ X, double *__restrict__ R,
                                                                     const double *__restrict__ P, const double *__restrict__ Q,
                                                                     double *__restrict__ part, const double *__restrict__ st)
@@ -343,6 +264,7 @@ __global__ __launch_bounds__(kRedThreads) void cg2_update_dev_kernel(int n, doub
   block_sum<3>(v, part);
 }
 
+// P = R + Psi' P                                                   (cg.h:165-171)
 __global__ __launch_bounds__(kRedThreads) void cg2_direction_dev_kernel(int n, double *__restrict__ P, const double *__restrict__ R,
                                                                        const double *__restrict__ st)
 {
@@ -501,10 +423,7 @@ __global__ __launch_bounds__(kRedThreads) void mscg_start_kernel(const double *_
                                                                 double *__restrict__ st, double *__restrict__ ms, double tol, int m,
                                                                 MscgSigma sg)
 {
-  double v[1] = {0.0};
-  for (int b = threadIdx.x; b < nblocks; b += kRedThreads) v[0] += part[b];
-  block_sum<1>(v, red);
-  __syncthreads();
+  finish_sum<1>(part, nblocks, red);
   const double bb = red[0];
   const double stop = tol * sqrt(bb);
   const bool done = sqrt(bb) <= stop;
@@ -531,10 +450,7 @@ __global__ __launch_bounds__(kRedThreads) void mscg_s1_kernel(const double *__re
                                                              double *__restrict__ st, double *__restrict__ ms, int m)
 {
   if (st[kStDone] != 0.0) return;
-  double s[1] = {0.0};
-  for (int b = threadIdx.x; b < nblocks; b += kRedThreads) s[0] += part[b];
-  block_sum<1>(s, red);
-  __syncthreads();
+  finish_sum<1>(part, nblocks, red);
   const double alpha = st[kStRsq] / red[0];
   if (threadIdx.x == 0) st[kStAlpha] = alpha;
   if ((int)threadIdx.x >= m) return;
@@ -606,16 +522,13 @@ __global__ __launch_bounds__(kRedThreads) void mscg_update_kernel(int n, double 
   block_sum<1>(v, part);
 }
 
-// S2: finishes r.r; the base system's convergence test and beta (fs_cg MODE 2, fs_pcg's r.r kept); per live shift (one thread
-// each) its residual norm, freeze or b_i and the new z; then the list of the shifts that stay live
+// S2: finishes r.r; the base system's convergence test and beta (fs_cg's kStepCgBeta, fs_pcg's r.r kept); per live shift (one
+// thread each) its residual norm, freeze or b_i and the new z; then the list of the shifts that stay live
 __global__ __launch_bounds__(kRedThreads) void mscg_s2_kernel(const double *__restrict__ part, int nblocks, double *__restrict__ red,
                                                              double *__restrict__ st, double *__restrict__ ms, int m)
 {
   if (st[kStDone] != 0.0) return;
-  double v[1] = {0.0};
-  for (int b = threadIdx.x; b < nblocks; b += kRedThreads) v[0] += part[b];
-  block_sum<1>(v, red);
-  __syncthreads();
+  finish_sum<1>(part, nblocks, red);
   const double rr = red[0], rsq = st[kStRsq], stop = st[kStStop], alpha = st[kStAlpha], n = st[kStIter];
   const double s = sqrt(rr);
   const bool done = s <= stop;
@@ -709,20 +622,23 @@ int cg_dev_init(int n, const double *b, double *x, double *r, double *p, double 
                 hipStream_t s)
 {
   hipLaunchKernelGGL(cg_init_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, b, x, r, p, part);
-  hipLaunchKernelGGL((final_step_kernel<1, 0>), dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red, st, tol);
+  hipLaunchKernelGGL((final_step_kernel<1, kStepCgStart>), dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red, st, tol);
   FS_HIP(hipGetLastError());
   return FS_OK;
 }
 
-// behind q = A'(A p): q += lambda p, alpha, x and r, the convergence test and beta, the new p -- all on the device
+// behind q = A'(A p): q += lambda p, alpha, x and r, the convergence test and beta, the new p -- all on the device.
+// fs_pcg without a preconditioner runs these launches with its own convergence step (it also keeps r.r)
 int cg_dev_steps(int n, double lambda, double *x, double *r, double *p, double *q, double *part, double *red, double *st,
-                 hipStream_t s)
+                 hipStream_t s, CgStep beta)
 {
   const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
   hipLaunchKernelGGL(cg_shift_dot_dev_kernel, g, blk, 0, s, n, lambda, q, p, part, st);
-  hipLaunchKernelGGL((final_step_kernel<1, 1>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);   // alpha
+  hipLaunchKernelGGL((final_step_kernel<1, kStepCgAlpha>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);   // alpha
   hipLaunchKernelGGL(cg_update_dev_kernel, g, blk, 0, s, n, x, r, p, q, part, st);
-  hipLaunchKernelGGL((final_step_kernel<1, 2>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);   // converged? beta
+  // converged? beta
+  if (beta == kStepPcgBeta) hipLaunchKernelGGL((final_step_kernel<1, kStepPcgBeta>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);
+  else                      hipLaunchKernelGGL((final_step_kernel<1, kStepCgBeta>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);
   hipLaunchKernelGGL(cg_direction_dev_kernel, g, blk, 0, s, n, p, r, st);
   FS_HIP(hipGetLastError());
   return FS_OK;
@@ -760,12 +676,13 @@ int cg_dev_step_c(int n, double *p, const double *r, const double *st, hipStream
   return FS_OK;
 }
 
-int cg_dev_final(int mode, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s)
+int cg_dev_final(CgStep step, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s)
 {
   const dim3 one(1), blk(kRedThreads);
-  if (mode == 0)      hipLaunchKernelGGL((final_step_kernel<1, 0>), one, blk, 0, s, partials, count, red_out, st, arg);
-  else if (mode == 1) hipLaunchKernelGGL((final_step_kernel<1, 1>), one, blk, 0, s, partials, count, red_out, st, arg);
-  else                hipLaunchKernelGGL((final_step_kernel<1, 2>), one, blk, 0, s, partials, count, red_out, st, arg);
+  if (step == kStepCgStart)      hipLaunchKernelGGL((final_step_kernel<1, kStepCgStart>), one, blk, 0, s, partials, count, red_out, st, arg);
+  else if (step == kStepCgAlpha) hipLaunchKernelGGL((final_step_kernel<1, kStepCgAlpha>), one, blk, 0, s, partials, count, red_out, st, arg);
+  else if (step == kStepCgBeta)  hipLaunchKernelGGL((final_step_kernel<1, kStepCgBeta>), one, blk, 0, s, partials, count, red_out, st, arg);
+  else { set_error("cg_dev_final: not a step of fs_cg"); return FS_ERR_ARG; }
   FS_HIP(hipGetLastError());
   return FS_OK;
 }
@@ -800,9 +717,9 @@ int cg2_dev_steps(int n, double lambda, double *X, double *R, double *P, double 
 {
   const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
   hipLaunchKernelGGL(cg2_shift_dot_dev_kernel, g, blk, 0, s, n, lambda, Q, P, part, st);
-  hipLaunchKernelGGL((final_step_kernel<3, 3>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);   // Alpha
+  hipLaunchKernelGGL((final_step_kernel<3, kStepCg2Alpha>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);   // Alpha
   hipLaunchKernelGGL(cg2_update_dev_kernel, g, blk, 0, s, n, X, R, P, Q, part, st);
-  hipLaunchKernelGGL((final_step_kernel<3, 4>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);   // converged? Psi
+  hipLaunchKernelGGL((final_step_kernel<3, kStepCg2Psi>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);   // converged? Psi
   hipLaunchKernelGGL(cg2_direction_dev_kernel, g, blk, 0, s, n, P, R, st);
   FS_HIP(hipGetLastError());
   return FS_OK;
@@ -858,6 +775,72 @@ int CgFlags::after_iteration(int iter, const double *st, hipStream_t s, bool *st
 
 using namespace fs;
 
+// ---- the host frame of the four single-device solvers: the shape check, fixed-order products, the work space every solve has
+// (r, p, q of k F doubles, tmp of k N, part, red, st), the iterations and the final st[] on the host.  A solver brings its own
+// argument checks, its own buffers (through alloc(), which keeps the order of the allocations), its start and its steps.  The
+// fixed-order scope opens with the struct, before the shape check: a thread-local count that every return path gives back.
+struct CgSolve {
+  const char *who;
+  fs_matrix_t A, At;
+  int k;                                                  // right-hand sides: the products are fs_spmv (1) or fs_spmm (2)
+  fs_stream_t stream;
+  FixedOrderScope fixed{options().cg_fixed_order != 0};   // the products of a solve add in a fixed order: bit-identical run to run
+  Workspace ws;
+  CgFlags fl;
+  int N = 0, F = 0;
+  double *r = nullptr, *p = nullptr, *q = nullptr, *tmp = nullptr, *part = nullptr, *red = nullptr, *st = nullptr;
+  double fin[kStDoubles] = {0.0};                         // the final st[], after finish()
+
+  int shape()
+  {
+    N = A->a.nrow; F = A->a.ncol;
+    if (At->a.nrow != F || At->a.ncol != N) { set_error(std::string(who) + ": At is not the transpose shape of A"); return FS_ERR_ARG; }
+    return FS_OK;
+  }
+  // the work space, st[] (the scalars live on the device from the first iteration on) and the host's flags.  A solver's own
+  // buffers keep their places in the order of the allocations: *own (n_own doubles) before st, *own2 behind it
+  int alloc(double **own = nullptr, size_t n_own = 0, double **own2 = nullptr, size_t n_own2 = 0)
+  {
+    r = ws.get((size_t)k * F); p = ws.get((size_t)k * F); q = ws.get((size_t)k * F); tmp = ws.get((size_t)k * N);
+    part = ws.get(kRedBlocks * 3); red = ws.get(4);
+    if (own) *own = ws.get(n_own);
+    st = ws.get(kStDoubles);
+    if (own2) *own2 = ws.get(n_own2);
+    if (!r || !p || !q || !tmp || !part || !red || !st || (own && !*own) || (own2 && !*own2)) {
+      set_error(std::string(who) + ": out of device memory"); return FS_ERR_HIP;
+    }
+    return fl.init();
+  }
+  // up to cap iterations: tmp = A p, q = A' tmp, the solver's steps, the flags behind them.  look_first: a solve that is done
+  // before it starts (b = 0, a warm start from a converged x) enqueues no product -- one synchronous look at the flag
+  template <typename Steps>
+  int iterate(int cap, bool look_first, Steps steps)
+  {
+    hipStream_t s = (hipStream_t)stream;
+    if (look_first) {
+      FS_HIP(hipMemcpyAsync(fl.h, st + kCgStateDone, sizeof(double) * 2, hipMemcpyDeviceToHost, s));
+      FS_HIP(hipStreamSynchronize(s));
+      if (fl.h[0] != 0.0) return FS_OK;
+    }
+    for (int iter = 0; iter < cap; iter++) {
+      if (int rc = k == 1 ? fs_spmv(A, tmp, p, stream) : fs_spmm(A, tmp, p, k, stream)) return rc;
+      if (int rc = k == 1 ? fs_spmv(At, q, tmp, stream) : fs_spmm(At, q, tmp, k, stream)) return rc;
+      if (int rc = steps()) return rc;
+      bool stop = false;
+      if (int rc = fl.after_iteration(iter, st, s, &stop)) return rc;
+      if (stop) break;
+    }
+    return FS_OK;
+  }
+  int finish()
+  {
+    FS_HIP(hipMemcpyAsync(fin, st, sizeof(fin), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    FS_HIP(hipStreamSynchronize((hipStream_t)stream));
+    note_cg_state(fin);
+    return FS_OK;
+  }
+};
+
 extern "C" {
 
 // y += a x on device vectors (the "+ lambda x" of bsbm_AtA, cg.h:17-21)
@@ -877,31 +860,15 @@ int fs_cg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lamb
 {
   FS_RANGE("fs_cg");
   if (!A || !At || !x || !b) { set_error("fs_cg: NULL argument"); return FS_ERR_ARG; }
-  const int N = A->a.nrow, F = A->a.ncol;
-  if (At->a.nrow != F || At->a.ncol != N) { set_error("fs_cg: At is not the transpose shape of A"); return FS_ERR_ARG; }
+  CgSolve f{"fs_cg", A, At, 1, stream};
+  if (int rc = f.shape()) return rc;
+  if (int rc = f.alloc()) return rc;
+  const int F = f.F;
   hipStream_t s = (hipStream_t)stream;
-  FixedOrderScope fixed(options().cg_fixed_order != 0);   // the products of a solve add in a fixed order: bit-identical run to run
-  Workspace ws;
-  double *r = ws.get(F), *p = ws.get(F), *q = ws.get(F), *tmp = ws.get(N), *part = ws.get(kRedBlocks * 3), *red = ws.get(4);
-  if (!r || !p || !q || !tmp || !part || !red) { set_error("fs_cg: out of device memory"); return FS_ERR_HIP; }
-  double *st = ws.get(kStDoubles);
-  CgFlags fl;
-  if (!st) { set_error("fs_cg: out of device memory"); return FS_ERR_HIP; }
-  if (int rc = fl.init()) return rc;
-  if (int rc = cg_dev_init(F, b, x, r, p, part, red, st, tol, s)) return rc;
-  for (int iter = 0; iter < F; iter++) {
-    if (int rc = fs_spmv(A, tmp, p, stream)) return rc;
-    if (int rc = fs_spmv(At, q, tmp, stream)) return rc;
-    if (int rc = cg_dev_steps(F, lambda, x, r, p, q, part, red, st, s)) return rc;
-    bool stop = false;
-    if (int rc = fl.after_iteration(iter, st, s, &stop)) return rc;
-    if (stop) break;
-  }
-  double fin[kStDoubles] = {0.0};
-  FS_HIP(hipMemcpyAsync(fin, st, sizeof(fin), hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  note_cg_state(fin);
-  if (out_iter) *out_iter = (int)fin[kStIter];
+  if (int rc = cg_dev_init(F, b, x, f.r, f.p, f.part, f.red, f.st, tol, s)) return rc;
+  if (int rc = f.iterate(F, false, [&] { return cg_dev_steps(F, lambda, x, f.r, f.p, f.q, f.part, f.red, f.st, s); })) return rc;
+  if (int rc = f.finish()) return rc;
+  if (out_iter) *out_iter = (int)f.fin[kStIter];
   return FS_OK;
 }
 
@@ -929,8 +896,8 @@ int fs_pcg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lam
 {
   FS_RANGE("fs_pcg");
   if (!A || !At || !x || !b || !prm) { set_error("fs_pcg: NULL argument"); return FS_ERR_ARG; }
-  const int N = A->a.nrow, F = A->a.ncol;
-  if (At->a.nrow != F || At->a.ncol != N) { set_error("fs_pcg: At is not the transpose shape of A"); return FS_ERR_ARG; }
+  CgSolve f{"fs_pcg", A, At, 1, stream};
+  if (int rc = f.shape()) return rc;
   if (prm->precond != FS_PRECOND_NONE && prm->precond != FS_PRECOND_JACOBI && prm->precond != FS_PRECOND_DIAG) {
     set_error("fs_pcg: precond is none of FS_PRECOND_NONE / _JACOBI / _DIAG"); return FS_ERR_ARG;
   }
@@ -939,59 +906,41 @@ int fs_pcg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lam
   if (prm->precond == FS_PRECOND_JACOBI)                     // before anything is written to x
     if (int rc = need_plain_csr(At->a, "fs_pcg with FS_PRECOND_JACOBI (fs_gram_diag)")) return rc;
   const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
+  const int F = f.F;
   const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
   hipStream_t s = (hipStream_t)stream;
-  FixedOrderScope fixed(options().cg_fixed_order != 0);   // the products of a solve add in a fixed order: bit-identical run to run
-  Workspace ws;
-  double *r = ws.get(F), *p = ws.get(F), *q = ws.get(F), *tmp = ws.get(N), *part = ws.get(kRedBlocks * 3), *red = ws.get(4);
-  double *dinv = pre ? ws.get(F) : nullptr;
-  double *st = ws.get(kStDoubles);
-  if (!r || !p || !q || !tmp || !part || !red || (pre && !dinv) || !st) { set_error("fs_pcg: out of device memory"); return FS_ERR_HIP; }
-  CgFlags fl;
-  if (int rc = fl.init()) return rc;
+  double *dinv = nullptr;
+  if (int rc = f.alloc(pre ? &dinv : nullptr, F)) return rc;
+  double *r = f.r, *p = f.p, *q = f.q, *part = f.part, *red = f.red, *st = f.st;
   const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
   if (prm->precond == FS_PRECOND_JACOBI)
     if (int rc = fs_gram_diag(At, lambda, dinv, stream)) return rc;
   if (pre) hipLaunchKernelGGL(pcg_dinv_kernel, g, blk, 0, s, F, prm->precond == FS_PRECOND_DIAG ? prm->diag : dinv, dinv);
   if (warm) {                                                // r = b - (A'(A x) + lambda x)
-    if (int rc = fs_spmv(A, tmp, x, stream)) return rc;
-    if (int rc = fs_spmv(At, q, tmp, stream)) return rc;
+    if (int rc = fs_spmv(A, f.tmp, x, stream)) return rc;
+    if (int rc = fs_spmv(At, q, f.tmp, stream)) return rc;
     hipLaunchKernelGGL(pcg_init_kernel<true>, g, blk, 0, s, F, lambda, b, x, r, q, part);
   } else {
     hipLaunchKernelGGL(pcg_init_kernel<false>, g, blk, 0, s, F, lambda, b, x, r, q, part);
   }
-  hipLaunchKernelGGL((final_step_kernel<2, 5>), one, blk, 0, s, part, kRedBlocks, red, st, prm->tol);   // b.b, r.r, stop, done?
+  hipLaunchKernelGGL((final_step_kernel<2, kStepPcgStart>), one, blk, 0, s, part, kRedBlocks, red, st, prm->tol);   // b.b, r.r, stop, done?
   if (pre) hipLaunchKernelGGL(pcg_start_kernel<true>, g, blk, 0, s, F, r, dinv, p, part, st);
   else     hipLaunchKernelGGL(pcg_start_kernel<false>, g, blk, 0, s, F, r, dinv, p, part, st);
-  hipLaunchKernelGGL((final_step_kernel<1, 6>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);         // r.z
+  hipLaunchKernelGGL((final_step_kernel<1, kStepPcgRz>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);           // r.z
   FS_HIP(hipGetLastError());
-  // a solve that is done before it starts (b = 0, a warm start from a converged x) enqueues no product: one look at the flag
-  FS_HIP(hipMemcpyAsync(fl.h, st + kCgStateDone, sizeof(double) * 2, hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  const bool done_at_start = fl.h[0] != 0.0;
-  for (int iter = 0; iter < cap && !done_at_start; iter++) {
-    if (int rc = fs_spmv(A, tmp, p, stream)) return rc;
-    if (int rc = fs_spmv(At, q, tmp, stream)) return rc;
+  auto steps = [&]() -> int {
+    if (!pre) return cg_dev_steps(F, lambda, x, r, p, q, part, red, st, s, kStepPcgBeta);   // fs_cg's launches
     hipLaunchKernelGGL(cg_shift_dot_dev_kernel, g, blk, 0, s, F, lambda, q, p, part, st);
-    hipLaunchKernelGGL((final_step_kernel<1, 1>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);       // alpha = r.z / p.q
-    if (pre) {
-      hipLaunchKernelGGL(pcg_update_kernel, g, blk, 0, s, F, x, r, p, q, dinv, part, st);
-      hipLaunchKernelGGL((final_step_kernel<2, 7>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);     // converged? beta
-      hipLaunchKernelGGL(pcg_direction_kernel, g, blk, 0, s, F, p, r, dinv, st);
-    } else {
-      hipLaunchKernelGGL(cg_update_dev_kernel, g, blk, 0, s, F, x, r, p, q, part, st);
-      hipLaunchKernelGGL((final_step_kernel<1, 7>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);
-      hipLaunchKernelGGL(cg_direction_dev_kernel, g, blk, 0, s, F, p, r, st);
-    }
+    hipLaunchKernelGGL((final_step_kernel<1, kStepCgAlpha>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);       // alpha = r.z / p.q
+    hipLaunchKernelGGL(pcg_update_kernel, g, blk, 0, s, F, x, r, p, q, dinv, part, st);
+    hipLaunchKernelGGL((final_step_kernel<2, kStepPcgBeta>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);       // converged? beta
+    hipLaunchKernelGGL(pcg_direction_kernel, g, blk, 0, s, F, p, r, dinv, st);
     FS_HIP(hipGetLastError());
-    bool stop = false;
-    if (int rc = fl.after_iteration(iter, st, s, &stop)) return rc;
-    if (stop) break;
-  }
-  double fin[kStDoubles] = {0.0};
-  FS_HIP(hipMemcpyAsync(fin, st, sizeof(fin), hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  note_cg_state(fin);
+    return FS_OK;
+  };
+  if (int rc = f.iterate(cap, true, steps)) return rc;
+  if (int rc = f.finish()) return rc;
+  const double *fin = f.fin;
   if (info) {
     info->iterations = (int)fin[kStIter];
     info->converged = fin[kStDone] != 0.0;
@@ -1009,8 +958,9 @@ int fs_mscg(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double 
 {
   FS_RANGE("fs_mscg");
   if (!A || !At || !X || !b || !lambda) { set_error("fs_mscg: NULL argument"); return FS_ERR_ARG; }
-  const int N = A->a.nrow, F = A->a.ncol;
-  if (At->a.nrow != F || At->a.ncol != N) { set_error("fs_mscg: At is not the transpose shape of A"); return FS_ERR_ARG; }
+  CgSolve f{"fs_mscg", A, At, 1, stream};
+  if (int rc = f.shape()) return rc;
+  const int F = f.F;
   if (m < 1 || m > kMscgMaxShifts) { set_error("fs_mscg: m outside 1..FS_MSCG_MAX_SHIFTS"); return FS_ERR_ARG; }
   if (ldx < F) { set_error("fs_mscg: ldx < ncol(A)"); return FS_ERR_ARG; }
   if (!(tol >= 0.0)) { set_error("fs_mscg: tol is negative or NaN"); return FS_ERR_ARG; }
@@ -1027,39 +977,27 @@ int fs_mscg(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double 
   const int cap = max_iter > 0 ? max_iter : F;               // cg.h:55
   const long long ldp = ((long long)F + 1) & ~1LL;           // every P_i 16-byte aligned
   hipStream_t s = (hipStream_t)stream;
-  FixedOrderScope fixed(options().cg_fixed_order != 0);   // the products of a solve add in a fixed order: bit-identical run to run
-  Workspace ws;
-  double *r = ws.get(F), *p = ws.get(F), *q = ws.get(F), *tmp = ws.get(N), *part = ws.get(kRedBlocks * 3), *red = ws.get(4);
-  double *P = ws.get((size_t)ldp * nslots), *st = ws.get(kStDoubles), *ms = ws.get(kMscgMaxShifts * kMsStride);
-  if (!r || !p || !q || !tmp || !part || !red || !P || !st || !ms) { set_error("fs_mscg: out of device memory"); return FS_ERR_HIP; }
-  CgFlags fl;
-  if (int rc = fl.init()) return rc;
+  double *P = nullptr, *ms = nullptr;
+  if (int rc = f.alloc(&P, (size_t)ldp * nslots, &ms, kMscgMaxShifts * kMsStride)) return rc;
+  double *r = f.r, *p = f.p, *q = f.q, *part = f.part, *red = f.red, *st = f.st;
   const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
   hipLaunchKernelGGL(mscg_init_kernel, g, blk, 0, s, F, b, r, p, X, (long long)ldx, m, P, ldp, nslots, part);
   hipLaunchKernelGGL(mscg_start_kernel, one, blk, 0, s, part, kRedBlocks, red, st, ms, tol, m, sg);
   FS_HIP(hipGetLastError());
-  // a solve that is done before it starts (b = 0) enqueues no product: one look at the flag
-  FS_HIP(hipMemcpyAsync(fl.h, st + kCgStateDone, sizeof(double) * 2, hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  const bool done_at_start = fl.h[0] != 0.0;
-  for (int iter = 0; iter < cap && !done_at_start; iter++) {
-    if (int rc = fs_spmv(A, tmp, p, stream)) return rc;
-    if (int rc = fs_spmv(At, q, tmp, stream)) return rc;
+  auto steps = [&]() -> int {
     hipLaunchKernelGGL(cg_shift_dot_dev_kernel, g, blk, 0, s, F, base, q, p, part, st);
     hipLaunchKernelGGL(mscg_s1_kernel, one, blk, 0, s, part, kRedBlocks, red, st, ms, m);               // alpha, the a_i
     hipLaunchKernelGGL(mscg_update_kernel, g, blk, 0, s, F, r, p, q, X, (long long)ldx, P, ldp, part, st, ms);
     hipLaunchKernelGGL(mscg_s2_kernel, one, blk, 0, s, part, kRedBlocks, red, st, ms, m);               // converged? beta, freezes
     hipLaunchKernelGGL(mscg_direction_kernel, g, blk, 0, s, F, p, r, P, ldp, st, ms);
     FS_HIP(hipGetLastError());
-    bool stop = false;
-    if (int rc = fl.after_iteration(iter, st, s, &stop)) return rc;
-    if (stop) break;
-  }
-  double fin[kStDoubles] = {0.0}, fms[kMscgMaxShifts * kMsStride] = {0.0};
-  FS_HIP(hipMemcpyAsync(fin, st, sizeof(fin), hipMemcpyDeviceToHost, s));
+    return FS_OK;
+  };
+  if (int rc = f.iterate(cap, true, steps)) return rc;
+  double fms[kMscgMaxShifts * kMsStride] = {0.0};
   FS_HIP(hipMemcpyAsync(fms, ms, sizeof(double) * m * kMsStride, hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  note_cg_state(fin);
+  if (int rc = f.finish()) return rc;
+  const double *fin = f.fin;
   for (int i = 0; i < m * kMsStride; ++i) g_last_mscg_state[i] = fms[i];
   g_last_mscg_doubles = m * kMsStride;
   for (int i = 0; info && i < m; ++i) {
@@ -1078,38 +1016,20 @@ int fs_cg2(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, double lam
 {
   FS_RANGE("fs_cg2");
   if (!A || !At || !X || !B) { set_error("fs_cg2: NULL argument"); return FS_ERR_ARG; }
-  const int N = A->a.nrow, F = A->a.ncol;
-  if (At->a.nrow != F || At->a.ncol != N) { set_error("fs_cg2: At is not the transpose shape of A"); return FS_ERR_ARG; }
-  FixedOrderScope fixed(options().cg_fixed_order != 0);   // the products of a solve add in a fixed order: bit-identical run to run
+  CgSolve f{"fs_cg2", A, At, 2, stream};
+  if (int rc = f.shape()) return rc;
   // the two-column copies of both matrices, before the first iteration (fs_spmm itself never builds)
   if (int rc = fs_matrix_prepare(A, 2, 0, stream)) return rc;
   if (int rc = fs_matrix_prepare(At, 2, 0, stream)) return rc;
+  if (int rc = f.alloc()) return rc;
+  const int F = f.F;
   hipStream_t s = (hipStream_t)stream;
-  Workspace ws;
-  double *R = ws.get(2 * (size_t)F), *P = ws.get(2 * (size_t)F), *Q = ws.get(2 * (size_t)F), *tmp = ws.get(2 * (size_t)N);
-  double *part = ws.get(kRedBlocks * 3), *red = ws.get(4);
-  if (!R || !P || !Q || !tmp || !part || !red) { set_error("fs_cg2: out of device memory"); return FS_ERR_HIP; }
-  // the scalars live on the device from the first iteration on (see the head of this file)
-  double *st = ws.get(kStDoubles);
-  CgFlags fl;
-  if (!st) { set_error("fs_cg2: out of device memory"); return FS_ERR_HIP; }
-  if (int rc = fl.init()) return rc;
   double norms[2];
-  if (int rc = cg2_dev_init(F, B, X, R, P, part, red, st, tol, norms, s)) return rc;
-  for (int iter = 0; iter < F; iter++) {
-    if (int rc = fs_spmm(A, tmp, P, 2, stream)) return rc;
-    if (int rc = fs_spmm(At, Q, tmp, 2, stream)) return rc;
-    if (int rc = cg2_dev_steps(F, lambda, X, R, P, Q, part, red, st, s)) return rc;
-    bool stop = false;
-    if (int rc = fl.after_iteration(iter, st, s, &stop)) return rc;
-    if (stop) break;
-  }
+  if (int rc = cg2_dev_init(F, B, X, f.r, f.p, f.part, f.red, f.st, tol, norms, s)) return rc;
+  if (int rc = f.iterate(F, false, [&] { return cg2_dev_steps(F, lambda, X, f.r, f.p, f.q, f.part, f.red, f.st, s); })) return rc;
   if (int rc = cg2_dev_finish(F, norms, X, s)) return rc;
-  double fin[kStDoubles] = {0.0};
-  FS_HIP(hipMemcpyAsync(fin, st, sizeof(fin), hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  note_cg_state(fin);
-  if (out_iter) *out_iter = (int)fin[kStIter];
+  if (int rc = f.finish()) return rc;
+  if (out_iter) *out_iter = (int)f.fin[kStIter];
   return FS_OK;
 }
 

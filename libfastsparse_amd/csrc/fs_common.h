@@ -371,10 +371,22 @@ int last_spmm_wide();   // the row kernel of the last one: 1 with 16-byte loads,
 // ---- the vector steps of CG (fs_cg.hip) for callers with their own products; every step leaves its dot / norm in red[0]
 constexpr int kCgPartDoubles = 3 * 1024;
 constexpr int kCgStateDoubles = 16, kCgStateDone = 0, kCgStateIter = 1;   // device state of a solve: st[done], st[iterations], scalars
+// the scalar step a one-workgroup kernel (final_step_kernel) takes behind the reduction it finishes
+enum CgStep {
+  kStepCgStart,    // fs_cg   b.b: rsq_old, stop = tol sqrt(b.b), done = 0, iter = 0
+  kStepCgAlpha,    //         p.q: alpha = rsq_old / p.q (fs_pcg: r.z / p.q)
+  kStepCgBeta,     //         r.r: converged -> done; else beta = rsq_new / rsq_old, rsq_old = rsq_new, ++iter
+  kStepCg2Alpha,   // fs_cg2  P'KP: Alpha = solve2sym(P'KP, R'R)
+  kStepCg2Psi,     //         R'R new: both <= tol^2 -> done; else Psi = solve2sym(R'R, R'R new), R'R = R'R new, ++iter
+  kStepPcgStart,   // fs_pcg  {b.b, r.r}: stop = tol sqrt(b.b), iter = 0, done = (||r|| <= stop)
+  kStepPcgRz,      //         r.z of the first direction
+  kStepPcgBeta     //         {r.r[, r.z]}: r.r kept; converged -> done; else beta = r.z new / r.z, r.z = r.z new, ++iter
+};
 int cg_dev_init(int n, const double *b, double *x, double *r, double *p, double *part, double *red, double *st, double tol,
                 hipStream_t s);                                                // x = 0, r = p = b; b.b, the stopping threshold
+// everything of an iteration behind q = A'(A p); `beta` is its convergence step: kStepCgBeta, or fs_pcg's kStepPcgBeta
 int cg_dev_steps(int n, double lambda, double *x, double *r, double *p, double *q, double *part, double *red, double *st,
-                 hipStream_t s);                                               // everything of an iteration behind q = A'(A p)
+                 hipStream_t s, CgStep beta = kStepCgBeta);
 // two right-hand sides, row-major n x 2 (bsbm_cg2, cg.h:85-187): init is synchronous and returns the column norms of B for finish
 int cg2_dev_init(int n, const double *B, double *X, double *R, double *P, double *part, double *red, double *st, double tol,
                  double *norms, hipStream_t s);
@@ -382,13 +394,13 @@ int cg2_dev_steps(int n, double lambda, double *X, double *R, double *P, double 
 int cg2_dev_finish(int n, const double *norms, double *X, hipStream_t s);
 // the same steps for a SLICE of the unknowns (fs_dist_cg, scheme "gather"): every step leaves this rank's partial dot in
 // *red_out; the partials of all ranks, gathered, go through cg_dev_final, which adds them in rank order and does the scalar step
-// `mode` of final_step_kernel (0 b.b and the threshold, 1 alpha, 2 convergence and beta)
+// `step` (one of fs_cg's: kStepCgStart, kStepCgAlpha, kStepCgBeta)
 int cg_dev_init_partial(int n, const double *b, double *x, double *r, double *p, double *part, double *red_out, hipStream_t s);
 int cg_dev_step_a(int n, double lambda, const double *p, double *q, double *part, double *red_out, const double *st, hipStream_t s);
 int cg_dev_step_b(int n, double *x, double *r, const double *p, const double *q, double *part, double *red_out, const double *st,
                   hipStream_t s);
 int cg_dev_step_c(int n, double *p, const double *r, const double *st, hipStream_t s);
-int cg_dev_final(int mode, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s);
+int cg_dev_final(CgStep step, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s);
 // the final st[] of a solve, kCgStateDoubles doubles copied back to the host: kept for the calling thread (fs_debug_last_cg_state)
 void note_cg_state(const double *st_host);
 // the host's view of a running solve: {done, iterations} of the two most recent iterations, in pinned memory

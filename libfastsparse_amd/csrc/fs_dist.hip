@@ -1581,13 +1581,45 @@ int fs_dist_swap_xy(fs_dist_matrix_t M)
   return FS_OK;
 }
 
-// the final st[] of rank 0, for fs_debug_last_cg_state (after the ranks were found to agree on {done, iterations})
-static int note_rank0_state(fs_dist_t D, const double *st)
+// behind iteration `iter`, rank by rank: steps(d) (what the caller still has to enqueue on rank d, in the same pass), then the
+// rank's flags on their way to the host and a look at those of iteration iter - 1.  Returns kRanksGoOn, kRanksStopped (every rank
+// saw the end), kRanksDisagree (only some did: identical arithmetic rules that out, a faulty device or exchange does not; the
+// error text is set in `who`'s name) or, < 0, the code of a call that failed
+enum { kRanksGoOn = 0, kRanksStopped = 1, kRanksDisagree = 2 };
+static_assert(FS_ERR_HIP < 0 && FS_ERR_ARG < 0 && FS_ERR_RELEASED < 0, "error codes are negative: they share an int with kRanks*");
+static int ranks_after_iteration(fs_dist_t D, std::vector<fs::CgFlags> &fl, const std::vector<double *> &st, int iter, const char *who,
+                                 const std::function<int(int)> &steps)
+{
+  int stops = 0;
+  for (int d = 0; d < D->n; ++d) {
+    bool stop = false;
+    FS_HIP(hipSetDevice(D->dev[d]));
+    if (int rc = steps(d)) return rc;
+    if (int rc = fl[(size_t)d].after_iteration(iter, st[(size_t)d], D->stream[d], &stop)) return rc;
+    stops += stop ? 1 : 0;
+  }
+  if (stops == 0 || stops == D->n) return stops ? kRanksStopped : kRanksGoOn;
+  fs::set_error(std::string(who) + ": the devices disagree about convergence (a device or an exchange returned different bits)");
+  return kRanksDisagree;
+}
+
+// every rank's final {done, iterations} must agree as well; then the final st[] of rank 0 for fs_debug_last_cg_state
+static int ranks_final_state(fs_dist_t D, const std::vector<double *> &st, const char *who, int *iterations)
 {
   double h[fs::kCgStateDoubles];
+  std::vector<double> fin(2 * (size_t)D->n, 0.0);
+  for (int d = 0; d < D->n; ++d) {
+    FS_HIP(hipSetDevice(D->dev[d]));
+    FS_HIP(hipMemcpy(&fin[2 * (size_t)d], st[(size_t)d] + fs::kCgStateDone, sizeof(double) * 2, hipMemcpyDeviceToHost));
+    if (fin[2 * (size_t)d] != fin[0] || fin[2 * (size_t)d + 1] != fin[1]) {
+      fs::set_error(std::string(who) + ": the devices finished in different states");
+      return FS_ERR_HIP;
+    }
+  }
   FS_HIP(hipSetDevice(D->dev[0]));
-  FS_HIP(hipMemcpy(h, st, sizeof(h), hipMemcpyDeviceToHost));
+  FS_HIP(hipMemcpy(h, st[0], sizeof(h), hipMemcpyDeviceToHost));
   fs::note_cg_state(h);
+  *iterations = (int)fin[1];
   return FS_OK;
 }
 
@@ -1649,11 +1681,11 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
     if (int rc = fl[(size_t)d].init()) return rc;
   }
   std::vector<hipEvent_t> none((size_t)n, nullptr);
-  // the sum over the ranks of every rank's red[0] (left there by a partial reduction), in rank order, then the scalar step `mode`
+  // the sum over the ranks of every rank's red[0] (left there by a partial reduction), in rank order, then the scalar step `step`
   // (send slots red[0] / red[1] alternate: a rank may be one exchange ahead of another that still reads its previous partial;
   // the scalar step leaves its sum in red[2])
   int slot = 0;
-  auto combine = [&](int mode, double arg) -> int {
+  auto combine = [&](fs::CgStep step, double arg) -> int {
     std::vector<const double *> send((size_t)n);
     std::vector<hipEvent_t> ready((size_t)n);
     for (int d = 0; d < n; ++d) {
@@ -1665,7 +1697,7 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
     if (int rc = exchange_equal(D, send, W.redall, 1, D->stream, ready)) return rc;
     for (int d = 0; d < n; ++d) {
       FS_HIP(hipSetDevice(D->dev[d]));
-      if (int rc = fs::cg_dev_final(mode, W.redall[(size_t)d], n, W.red[(size_t)d] + 2, W.st[(size_t)d], arg, D->stream[d])) return rc;
+      if (int rc = fs::cg_dev_final(step, W.redall[(size_t)d], n, W.red[(size_t)d] + 2, W.st[(size_t)d], arg, D->stream[d])) return rc;
     }
     slot ^= 1;
     return FS_OK;
@@ -1683,10 +1715,10 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
       if (int rc = fs::cg_dev_init_partial(nl, W.b[(size_t)d] + lo, W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.part[(size_t)d], W.red[(size_t)d] + slot,
                                            D->stream[d])) return rc;
     }
-    if (int rc = combine(0, tol)) return rc;
+    if (int rc = combine(fs::kStepCgStart, tol)) return rc;
     if (int rc = dist_gather(D, T, W.p, M->x)) return rc;                // the whole p on every rank
   }
-  int rc_loop = FS_OK;
+  int seen = kRanksGoOn;
   for (int iter = 0; iter < F; iter++) {
     if (int rc = dist_product(D, M->a, M->x, M->y)) return rc;           // y = A p, its all-gather inside
     if (!gather) {
@@ -1704,14 +1736,14 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
           if (int rc = fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], M->y[(size_t)d], D->stream[d])) return rc;
         if (int rc = fs::cg_dev_step_a(nl, lambda, W.p[(size_t)d], W.q[(size_t)d], W.part[(size_t)d], W.red[(size_t)d] + slot, W.st[(size_t)d], D->stream[d])) return rc;
       }
-      if (int rc = combine(1, 0.0)) return rc;                            // alpha
+      if (int rc = combine(fs::kStepCgAlpha, 0.0)) return rc;             // alpha
       for (int d = 0; d < n; ++d) {
         const int nl = T.bounds[(size_t)d + 1] - T.bounds[(size_t)d];
         FS_HIP(hipSetDevice(D->dev[d]));
         if (int rc = fs::cg_dev_step_b(nl, W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.q[(size_t)d], W.part[(size_t)d], W.red[(size_t)d] + slot,
                                        W.st[(size_t)d], D->stream[d])) return rc;
       }
-      if (int rc = combine(2, 0.0)) return rc;                            // converged?  beta
+      if (int rc = combine(fs::kStepCgBeta, 0.0)) return rc;              // converged?  beta
       for (int d = 0; d < n; ++d) {
         const int nl = T.bounds[(size_t)d + 1] - T.bounds[(size_t)d];
         FS_HIP(hipSetDevice(D->dev[d]));
@@ -1719,33 +1751,14 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
       }
       if (int rc = dist_gather(D, T, W.p, M->x)) return rc;              // the new p on every rank
     }
-    int stops = 0;
-    for (int d = 0; d < n; ++d) {
-      bool stop = false;
-      FS_HIP(hipSetDevice(D->dev[d]));
-      if (int rc = fl[(size_t)d].after_iteration(iter, W.st[(size_t)d], D->stream[d], &stop)) return rc;
-      stops += stop ? 1 : 0;
-    }
-    if (stops != 0 && stops != n) {
-      fs::set_error("fs_dist_cg: the devices disagree about convergence (a device or an exchange returned different bits)");
-      rc_loop = FS_ERR_HIP;
-      break;
-    }
-    if (stops == n) break;
+    seen = ranks_after_iteration(D, fl, W.st, iter, "fs_dist_cg", [](int) { return FS_OK; });
+    if (seen < 0) return seen;
+    if (seen != kRanksGoOn) break;
   }
   if (int rc = dist_sync(D)) return rc;
-  if (rc_loop != FS_OK) return rc_loop;
-  // every device's final {done, iterations} must agree as well
-  std::vector<double> fin(2 * (size_t)n, 0.0);
-  for (int d = 0; d < n; ++d) {
-    FS_HIP(hipSetDevice(D->dev[d]));
-    FS_HIP(hipMemcpy(&fin[2 * (size_t)d], W.st[(size_t)d] + fs::kCgStateDone, sizeof(double) * 2, hipMemcpyDeviceToHost));
-    if (fin[2 * (size_t)d] != fin[0] || fin[2 * (size_t)d + 1] != fin[1]) {
-      fs::set_error("fs_dist_cg: the devices finished in different states");
-      return FS_ERR_HIP;
-    }
-  }
-  if (int rc = note_rank0_state(D, W.st[0])) return rc;
+  if (seen == kRanksDisagree) return FS_ERR_HIP;
+  int iterations = 0;
+  if (int rc = ranks_final_state(D, W.st, "fs_dist_cg", &iterations)) return rc;
   if (vector_device(x_host) >= 0)
     if (int rc = wait_for_caller(vector_device(x_host))) return rc;
   if (!gather) {
@@ -1758,7 +1771,7 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
     }
   }
   if (int rc = dist_sync(D)) return rc;
-  if (out_iter) *out_iter = (int)fin[1];
+  if (out_iter) *out_iter = iterations;
   return FS_OK;
 }
 
@@ -1832,47 +1845,30 @@ int fs_dist_cg2(fs_dist_matrix_t M, double *X_host, const double *B_host, double
       return FS_ERR_HIP;
     }
   }
-  int rc_loop = FS_OK;
+  int seen = kRanksGoOn;
   for (int iter = 0; iter < F; iter++) {
     if (int rc = dist_product_k(M, false, W.x, W.y)) return rc;          // TMP = A P
     if (int rc = dist_product_k(M, true, W.y, W.z)) return rc;           // Q = A' TMP
-    int stops = 0;
-    for (int d = 0; d < n; ++d) {
-      FS_HIP(hipSetDevice(D->dev[d]));
-      if (int rc = fs::cg2_dev_steps(F, lambda, W.sol[(size_t)d], W.r[(size_t)d], W.x[(size_t)d], W.z[(size_t)d], W.part[(size_t)d],
-                                     W.red[(size_t)d], W.st[(size_t)d], D->stream[d])) return rc;
-      bool stop = false;
-      if (int rc = fl[(size_t)d].after_iteration(iter, W.st[(size_t)d], D->stream[d], &stop)) return rc;
-      stops += stop ? 1 : 0;
-    }
-    if (stops != 0 && stops != n) {
-      fs::set_error("fs_dist_cg2: the devices disagree about convergence (a device or an exchange returned different bits)");
-      rc_loop = FS_ERR_HIP;
-      break;
-    }
-    if (stops == n) break;
+    seen = ranks_after_iteration(D, fl, W.st, iter, "fs_dist_cg2", [&](int d) {   // a rank's steps and its flags in one pass
+      return fs::cg2_dev_steps(F, lambda, W.sol[(size_t)d], W.r[(size_t)d], W.x[(size_t)d], W.z[(size_t)d], W.part[(size_t)d],
+                               W.red[(size_t)d], W.st[(size_t)d], D->stream[d]);
+    });
+    if (seen < 0) return seen;
+    if (seen != kRanksGoOn) break;
   }
-  for (int d = 0; d < n && rc_loop == FS_OK; ++d) {
+  for (int d = 0; d < n && seen != kRanksDisagree; ++d) {
     FS_HIP(hipSetDevice(D->dev[d]));
     if (int rc = fs::cg2_dev_finish(F, &norms[2 * (size_t)d], W.sol[(size_t)d], D->stream[d])) return rc;
   }
   if (int rc = dist_sync(D)) return rc;
-  if (rc_loop != FS_OK) return rc_loop;
-  std::vector<double> fin(2 * (size_t)n, 0.0);
-  for (int d = 0; d < n; ++d) {
-    FS_HIP(hipSetDevice(D->dev[d]));
-    FS_HIP(hipMemcpy(&fin[2 * (size_t)d], W.st[(size_t)d] + fs::kCgStateDone, sizeof(double) * 2, hipMemcpyDeviceToHost));
-    if (fin[2 * (size_t)d] != fin[0] || fin[2 * (size_t)d + 1] != fin[1]) {
-      fs::set_error("fs_dist_cg2: the devices finished in different states");
-      return FS_ERR_HIP;
-    }
-  }
-  if (int rc = note_rank0_state(D, W.st[0])) return rc;
+  if (seen == kRanksDisagree) return FS_ERR_HIP;
+  int iterations = 0;
+  if (int rc = ranks_final_state(D, W.st, "fs_dist_cg2", &iterations)) return rc;
   if (vector_device(X_host) >= 0)
     if (int rc = wait_for_caller(vector_device(X_host))) return rc;
   if (int rc = vec_store(M, 0, X_host, W.sol[0], (size_t)F * 2)) return rc;
   if (int rc = dist_sync(D)) return rc;
-  if (out_iter) *out_iter = (int)fin[1];
+  if (out_iter) *out_iter = iterations;
   return FS_OK;
 }
 

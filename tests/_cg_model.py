@@ -11,11 +11,11 @@ Reductions have the fixed launch shape of fs_cg.hip:
            nblocks partials, then the same block tree.  Three sums (cg2) are three independent trees.
 A running sum that starts at +0.0 is never -0.0, so padding a thread's terms with +0.0 changes nothing.
 
-The scalar steps are final_step_kernel MODE 0-4 and solve2sym_dev; the two-column solve takes its column norms and scale factors
-on the host (cg2_dev_init).  Products are parameters: the oracle's storage-order products over the CSR the library holds stand
-in for the device's strict_order products.  tree="serial" makes every sum one left-to-right loop, as oracle/fs_oracle_cg.c does;
-`bounds` (the row cuts of A') gives the "gather" scheme of fs_dist_cg: every rank reduces its own slice, and the rank values are
-added by stage 2 with nblocks = number of ranks."""
+The scalar steps are final_step_kernel's kStepCgStart .. kStepCg2Psi (CgStep, fs_common.h) and solve2sym_dev; the two-column
+solve takes its column norms and scale factors on the host (cg2_dev_init).  Products are parameters: the oracle's storage-order
+products over the CSR the library holds stand in for the device's strict_order products.  tree="serial" makes every sum one
+left-to-right loop, as oracle/fs_oracle_cg.c does; `bounds` (the row cuts of A') gives the "gather" scheme of fs_dist_cg: every
+rank reduces its own slice, and the rank values are added by stage 2 with nblocks = number of ranks."""
 import collections
 import os
 import re
@@ -136,17 +136,17 @@ def cg(F, amul, atmul, b, lam, tol, tree="device", bounds=None):
     b = np.asarray(b, np.float64).reshape(F)
     with np.errstate(all="ignore"):
         x, r, p = np.zeros(F), b.copy(), b.copy()
-        rsq = red(b * b)                                           # MODE 0
+        rsq = red(b * b)                                           # kStepCgStart
         stop = tol * np.sqrt(rsq)
         state = {"done": 0.0, "iter": 0.0, "rsq": rsq, "stop": stop}
         for _ in range(F):
             q = atmul(amul(p))
             q = q + lam * p                                        # cg_shift_dot_dev_kernel
-            state["alpha"] = alpha = state["rsq"] / red(q * p)     # MODE 1
+            state["alpha"] = alpha = state["rsq"] / red(q * p)     # kStepCgAlpha
             x = x + alpha * p                                      # cg_update_dev_kernel
             r = r - alpha * q
             rr = red(r * r)
-            if np.sqrt(rr) <= stop:                                # MODE 2
+            if np.sqrt(rr) <= stop:                                # kStepCgBeta
                 state["done"] = 1.0
                 break
             state["beta"] = beta = rr / state["rsq"]
@@ -180,12 +180,12 @@ def cg2(F, amul2, atmul2, B, lam, tol, tree="device"):
             pa, pb = P[:, 0], P[:, 1]
             Q = np.stack([Q[:, 0] + lam * pa, Q[:, 1] + lam * pb], 1)
             qa, qb = Q[:, 0], Q[:, 1]
-            Alpha = solve2sym(red3(P, Q), [RtR[0], RtR[2], RtR[2], RtR[1]])    # MODE 3
+            Alpha = solve2sym(red3(P, Q), [RtR[0], RtR[2], RtR[2], RtR[1]])    # kStepCg2Alpha
             a0, a1, a2, a3 = Alpha
             X = np.stack([X[:, 0] + (a0 * pa + a1 * pb), X[:, 1] + (a2 * pa + a3 * pb)], 1)
             R = np.stack([R[:, 0] - (a0 * qa + a1 * qb), R[:, 1] - (a2 * qa + a3 * qb)], 1)
             n = red3(R, R)
-            if n[0] <= tol * tol and n[1] <= tol * tol:                          # MODE 4
+            if n[0] <= tol * tol and n[1] <= tol * tol:                          # kStepCg2Psi
                 done = 1.0
                 break
             Psi = solve2sym(RtR, [n[0], n[2], n[2], n[1]])

@@ -61,7 +61,7 @@ def pcg(F, amul, atmul, b, lam, tol, max_iter, dinv=None, x0=None, tree="device"
             q = atmul(amul(x))
             q = q + lam * x                                        # pcg_init_kernel<true>
             r = b - q
-        bb, rr = red(b * b), red(r * r)                            # MODE 5
+        bb, rr = red(b * b), red(r * r)                            # kStepPcgStart
         stop = tol * np.sqrt(bb)
         state = {"done": 0.0, "iter": 0.0, "stop": stop, "rr": rr, "bb": bb}
         if np.sqrt(rr) <= stop:
@@ -69,15 +69,15 @@ def pcg(F, amul, atmul, b, lam, tol, max_iter, dinv=None, x0=None, tree="device"
             return M.Result(x, 0, state)
         z = r if dinv is None else r * dinv                        # pcg_start_kernel
         p = z.copy()
-        state["rsq"] = red(r * z)                                  # MODE 6
+        state["rsq"] = red(r * z)                                  # kStepPcgRz
         for _ in range(cap):
             q = atmul(amul(p))
             q = q + lam * p                                        # cg_shift_dot_dev_kernel
-            state["alpha"] = alpha = state["rsq"] / red(q * p)     # MODE 1
+            state["alpha"] = alpha = state["rsq"] / red(q * p)     # kStepCgAlpha
             x = x + alpha * p                                      # pcg_update_kernel / cg_update_dev_kernel
             r = r - alpha * q
             state["rr"] = rr = red(r * r)
-            if np.sqrt(rr) <= stop:                                # MODE 7
+            if np.sqrt(rr) <= stop:                                # kStepPcgBeta
                 state["done"] = 1.0
                 break
             z = r if dinv is None else r * dinv

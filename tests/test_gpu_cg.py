@@ -362,6 +362,31 @@ def test_default_modes_within_the_bars_of_the_model(L, name, two):
             assert runs[1][1] == it and M.same_bits(runs[1][0], x).all(), what
 
 
+# ---- statuses ----------------------------------------------------------------------------------------------------------------
+def test_statuses(L):
+    """fs_cg / fs_cg2 refuse a NULL argument and an At of A's own shape with FS_ERR_ARG and a message, before anything is written
+    to x; out_iter = NULL is legal"""
+    import torch
+    from libfastsparse_amd import capi
+    s = SYSTEMS["fixture_100x50"]
+    A = capi.Matrix.from_coo(s.nrow, s.ncol, _d(s.rows), _d(s.cols), None)
+    At = capi.Matrix.from_coo(s.ncol, s.nrow, _d(s.cols), _d(s.rows), None)
+    st = capi.current_stream()
+    for f, rhs in ((L.fs_cg, s.b), (L.fs_cg2, s.B)):
+        b = _d(rhs.reshape(-1))
+        x = torch.full((rhs.size,), float("nan"), dtype=torch.float64, device="cuda")
+        x_bits = x.cpu().numpy().view(np.int64).copy()
+        good = dict(A=A.h, At=At.h, x=x.data_ptr(), b=b.data_ptr())
+        for what, kw in (("NULL A", dict(A=None)), ("NULL At", dict(At=None)), ("NULL x", dict(x=None)), ("NULL b", dict(b=None)),
+                         ("At is A", dict(At=A.h))):
+            a = dict(good, **kw)
+            rc = f(a["A"], a["At"], a["x"], a["b"], s.lam, s.tol, None, st)
+            assert rc == FS_ERR_ARG, (f.__name__, what, rc)
+            assert L.fs_last_error().startswith(f.__name__.encode() + b":"), (f.__name__, what, L.fs_last_error())   # its own message
+        assert np.array_equal(x.cpu().numpy().view(np.int64), x_bits), f"{f.__name__}: a refused call wrote to x"
+        assert f(A.h, At.h, x.data_ptr(), b.data_ptr(), s.lam, s.tol, None, st) == 0, L.fs_last_error()   # out_iter NULL is legal
+
+
 # ---- the drop-in on three virtual ranks -----------------------------------------------------------------------------------
 def test_dropin_cg_across_three_ranks_in_a_child_process(L):
     """FASTSPARSE_NGPU=3 FASTSPARSE_DEVICES=0,0,0: bsbm_cg / bsbm_cg2 on the row-sharded path -- strict_order bits against the

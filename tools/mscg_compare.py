@@ -4,8 +4,8 @@
   c2        on config 2's pattern (10 M x 10 M, 16 per row, pattern-only, lambda 5 + 0.01 i, tol 0 so that no shift freezes): ms per
             iteration as the slope between caps 8 and 32 (a solve's one-time work -- work space, start, final copy -- taken out), for
             fs_mscg with m = 1, 2, 4, 8, 16 and, as the capped baseline, for fs_pcg without a preconditioner (key
-            "fs_pcg_none_capped": it launches fs_cg's kernels and takes a cap, but it is NOT fs_cg: its last step is another mode of
-            final_step_kernel), five repeats each, interleaved.  fs_cg ITSELF takes no cap, so its ms per iteration (key "fs_cg")
+            "fs_pcg_none_capped": it launches fs_cg's kernels and takes a cap, but it is NOT fs_cg: its last step is another step of
+            final_step_kernel, kStepPcgBeta), five repeats each, interleaved.  fs_cg ITSELF takes no cap, so its ms per iteration (key "fs_cg")
             is the slope between two of its own solves that stop at tol 1e-3 and 1e-8, (t2 - t1) / (count2 - count1).  m = 1 runs
             fs_cg's vector traffic plus two one-workgroup launches: its difference to fs_cg, and to the capped baseline, is given
             beside the spread of the fs_cg repeats.  The cost per extra shift,
