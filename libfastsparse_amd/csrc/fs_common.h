@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "fastsparse_hip.h"
+#include "fs_geometry.h"   // the kernels' geometry constants (kTiled*, kLdsx*, kBin*, kLong*)
 
 namespace fs {
 
@@ -72,18 +73,6 @@ struct DeviceCsr {
 // columns (x slice L2-resident).  Entries are ordered by (panel, band), then row, then CSR order.
 // An entry is one 32-bit word  local row:(32-lcol_bits) | local col:lcol_bits  plus its value.
 // Work items are runs of at most kTiledItem consecutive entries of one (panel, band) tile.
-constexpr int kTiledBlock = 1024;      // threads per workgroup of the tiled kernel: ONE workgroup per CU (two
-                                       // co-resident workgroups were measured to run at different speeds -- the
-                                       // older one wins issue arbitration, 401 vs 450 us per panel -- which pulls
-                                       // the band sweep of an XCD apart and out of its L2)
-constexpr int kTiledProd = 512;        // waves 0-7 produce (stream + gather), waves 8-15 consume (LDS reduction)
-constexpr int kTiledItem = 2048;       // entries per work item (4 per producer thread)
-constexpr int kTiledRowsMax = 13056;   // R <= this: 102 KiB of y per workgroup
-constexpr int kTiledColBits = 18;      // W <= 262144 columns (2 MiB of x); the other 14 bits are the local row
-
-constexpr int kLdsxRows = 14336;       // LDS-staged kernel: rows per panel (112 KiB of y in LDS, + 3 x 16 KiB slices = 160 KiB)
-constexpr int kLdsxCols = 2048;        //                    columns per band: one 16 KiB slice of x, two slices in LDS
-
 struct TiledCsr {
   bool built = false;
   bool ldsx = false;           // geometry of the LDS-staged kernel (W <= kLdsxCols, R <= kLdsxRows)
@@ -129,35 +118,12 @@ struct TiledCsr {
 //   pass 2 streams the products of one panel, which are now contiguous, with their local row ids, and adds them
 //          into the y slice.
 // No access of either pass leaves LDS except the two sequential streams.
-constexpr int kBinBlock = 1024;        // threads per workgroup, both passes
-constexpr int kBinCols = 16384;        // columns per band: 128 KiB of x in LDS, one pass-1 workgroup per CU
-constexpr int kBinRowsMax = 16384;     // rows per panel: 128 KiB of y in LDS, one pass-2 workgroup per CU (measured equal to
-                                       // 8192 rows x two workgroups; larger panels mean longer runs, less padding)
-// short runs (a power-law shard with a very wide x: config 5, 66 entries per run) pay 7.5 padding entries per run: such
-// matrices get bands and panels as large as LDS allows, 19 % fewer bands and panels, 29 % fewer runs (config-5 shard 2.84 ->
-// 2.72 ms; config 2, 344 entries per run, was measured 1 % slower with them and keeps the power-of-two sizes)
-constexpr int kBinColsBig = 19456, kBinRowsBig = 19456;   // 152 KiB of x / of y in LDS
-constexpr int kBinBigRunEntries = 192;                     // chosen below this many entries per run (single-vector copies)
-static_assert(kBinColsBig % 1024 == 0 && kBinColsBig < 65536, "band loads are 1024 threads wide; 16-bit local ids");
-static_assert(kBinCols % 1024 == 0 && kBinCols % 4 == 0 && kBinRowsMax % 4 == 0 && kBinCols < 65536 && kBinRowsMax <= 65536,
-              "band loads are 1024 threads wide; 16-bit local ids; k-column copies divide both by 2 and 4");
-#ifndef FS_BIN_GROUP_LOG          // (experiment builds only, FS_HIPCC_EXTRA=-DFS_BIN_GROUP_LOG=5: 256-byte groups, profiles/r05_c2_group32_ab.txt)
-#define FS_BIN_GROUP_LOG 4
-#endif
-constexpr int kBinGroupLog = FS_BIN_GROUP_LOG;
-constexpr int kBinGroup = 1 << kBinGroupLog;  // entries per group = one 128-byte L2 line of products (runs that start on half
-                                               // lines were measured 19 % slower in pass 1: 0.459 vs 0.386 ms)
-constexpr int kBinShareMin = 8192;     // a pass-1 workgroup streams at least this many entries
 
 // The longest rows of a heavy-tailed matrix (BASELINE config 5: power-law lengths up to 10^6), taken OUT of the two-pass copy.
 // A row with many more entries than there are column bands has several entries per band; the two-pass pair would ship each of
 // them through the product stream (16 bytes written and read back per entry).  A few thousand such rows hold 40 % of a config-5
 // shard's entries, and their accumulators -- 8 bytes each -- fit into LDS NEXT TO a band of x: spmv_longrows_kernel sweeps the
 // bands like pass 1 and adds every product straight into its row's LDS accumulator, no intermediate at all (10 bytes per entry).
-// two geometries of the 152 KiB of LDS: a wide band with few accumulators, or a narrower band with four times as many rows
-constexpr int kLongBandA = 16384, kLongRowsA = 3072;      // 128 KiB of x + 24 KiB of accumulators
-constexpr int kLongBandB = 8192, kLongRowsB = 12032;      //  64 KiB of x + 94 KiB of accumulators (160 KiB with the zero slots)
-constexpr int kLongOwners = kBinBlock / 64;               // the waves of a workgroup: every long row belongs to one of them
 struct LongRows {
   int nlong = 0;                // rows taken out
   int64_t n = 0;                // their entries, every (band, owner) segment padded to an even count
@@ -414,7 +380,8 @@ struct CgFlags {
   int after_iteration(int iter, const double *st, hipStream_t s, bool *stop);
 };
 
-// ---- format work implemented in fs_format.hip --------------------------------------------
+// ---- format work: fs_format.hip (schedule, validation, COO -> CSR, transposes, what frees a handle) and fs_copies.hip (the
+// build_* functions of the re-ordered copies, choose_copy) ------------------------------------------------------------
 int build_schedule(DeviceCsr &A, hipStream_t s, bool allow_tiled = true);
 int build_tiled(DeviceCsr &A, hipStream_t s);       // no-op unless options/heuristic ask for it
 int build_tiledx(DeviceCsr &A, hipStream_t s);      // the same for the LDS-staged kernel's geometry

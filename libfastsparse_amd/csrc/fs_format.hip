@@ -1,5 +1,7 @@
-// fs_format.hip -- one-time format work on the device: chunk schedule of the streaming
-// SpMV kernel, stable COO -> CSR, CSR -> CSR of the transpose, synthetic generators.
+// fs_format.hip -- one-time format work on the device: the builders' scratch pool and what frees a handle's arrays, chunk
+// schedule of the streaming SpMV kernel, index validation, stable COO -> CSR, bucketing, CSR -> CSR of the transpose, the
+// partition behind the distributed transpose, synthetic generators.  The re-ordered device copies and the timed choice
+// between them are built in fs_copies.hip; the idioms both files share are in fs_format_util.h.
 //
 // The reference builds its CSRs on the host with a stable counting sort (new_csr csr.h:375-422,
 // new_bcsr csr.h:30-67).  Here the same result (entries of a row kept in input order) comes
@@ -10,40 +12,13 @@
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
-#include <cstdlib>
 #include <vector>
 
 #include <rocprim/rocprim.hpp>
 
-#include "fs_common.h"
+#include "fs_format_util.h"
 
 namespace fs {
-
-// ---- small helpers -------------------------------------------------------------------------
-// hipMalloc / hipFree with a stopwatch: with FS_TRACE_BUILD set, any single call that takes longer than 50 ms is reported
-static bool trace_build() { static const bool v = getenv("FS_TRACE_BUILD") != nullptr; return v; }
-
-template <typename T>
-static hipError_t traced_malloc(T **p, size_t bytes)
-{
-  if (!trace_build()) return hipMalloc(p, bytes);
-  const auto t0 = std::chrono::steady_clock::now();
-  const hipError_t e = hipMalloc(p, bytes);
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (ms > 50.0) fprintf(stderr, "[fastsparse] hipMalloc of %.1f MB took %.0f ms\n", bytes / 1048576.0, ms);
-  return e;
-}
-
-static hipError_t traced_free(void *p)
-{
-  if (!trace_build()) return hipFree(p);
-  const auto t0 = std::chrono::steady_clock::now();
-  const hipError_t e = hipFree(p);
-  const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (ms > 50.0) fprintf(stderr, "[fastsparse] hipFree took %.0f ms\n", ms);
-  return e;
-}
 
 // Device scratch of the format builders goes through a small pool: building one matrix takes three candidate copies,
 // each with half a dozen temporaries of nnz elements, and hipMalloc of a multi-GB block now and then stalls for SECONDS on
@@ -54,7 +29,7 @@ struct PoolBlock { void *p; size_t bytes; bool used; int device; };   // a block
 static std::mutex g_pool_lock;
 static std::vector<PoolBlock> g_pool;
 
-static hipError_t pool_alloc(void **out, size_t bytes)
+hipError_t pool_alloc(void **out, size_t bytes)
 {
   if (bytes == 0) bytes = 1;
   int dev = 0;
@@ -80,7 +55,7 @@ static hipError_t pool_alloc(void **out, size_t bytes)
   return hipSuccess;
 }
 
-static void pool_free(void *p)
+void pool_free(void *p)
 {
   std::lock_guard<std::mutex> g(g_pool_lock);
   for (PoolBlock &b : g_pool)
@@ -108,19 +83,7 @@ void pool_trim(bool everything)
   }
 }
 
-// device scratch that is released (to the pool) on every exit path
-template <typename T>
-struct Scratch {
-  T *p = nullptr;
-  Scratch() = default;
-  Scratch(const Scratch &) = delete;
-  Scratch &operator=(const Scratch &) = delete;
-  ~Scratch() { if (p) pool_free(p); }
-  hipError_t alloc(size_t n) { return pool_alloc(reinterpret_cast<void **>(&p), sizeof(T) * (n ? n : 1)); }
-  operator T *() const { return p; }
-};
-
-static void free_tiled_slot(TiledCsr *&T)
+void free_tiled_slot(TiledCsr *&T)
 {
   if (!T) return;
   void *owned[] = {T->pk, T->vals, T->items, T->item_ptr, T->panel_row, T->vfirst, T->yv, T->chunk_panel, T->chunk_item,
@@ -134,10 +97,7 @@ static void free_tiled_slot(TiledCsr *&T)
   T = nullptr;
 }
 
-static void free_tiled(DeviceCsr &A) { free_tiled_slot(A.tiled); }
-static void free_tiledx(DeviceCsr &A) { free_tiled_slot(A.tiledx); }
-
-static void free_long_rows(LongRows *&L)
+void free_long_rows(LongRows *&L)
 {
   if (!L) return;
   void *owned[] = {L->row, L->lcol, L->lrow, L->vals, L->band_ptr, L->seg_ptr, L->ylong, L->ypart};
@@ -147,7 +107,7 @@ static void free_long_rows(LongRows *&L)
   L = nullptr;
 }
 
-static void free_binned_slot(BinnedCsr *&N)
+void free_binned_slot(BinnedCsr *&N)
 {
   if (!N) return;
   free_long_rows(N->lr);
@@ -161,8 +121,6 @@ static void free_binned_slot(BinnedCsr *&N)
   N = nullptr;
 }
 
-static void free_binned(DeviceCsr &A) { free_binned_slot(A.binned); }
-
 void free_csr(DeviceCsr &A)
 {
   if (A.owns) {
@@ -173,9 +131,9 @@ void free_csr(DeviceCsr &A)
   if (A.first_row) (void)traced_free(A.first_row);
   if (A.head) (void)traced_free(A.head);
   if (A.tail) (void)traced_free(A.tail);
-  free_tiled(A);
-  free_tiledx(A);
-  free_binned(A);
+  free_tiled_slot(A.tiled);
+  free_tiled_slot(A.tiledx);
+  free_binned_slot(A.binned);
   free_binned_slot(A.binned2);
   free_binned_slot(A.binned4);
   if (A.spmm_scratch) { (void)traced_free(A.spmm_scratch); A.spmm_scratch = nullptr; A.spmm_scratch_doubles = 0; }
@@ -285,31 +243,6 @@ __global__ void count_spanning_kernel(int nchunks, int64_t nnz, const int *__res
   if ((int64_t)row_ptr[r1] > e) atomicAdd(count, 1);
 }
 
-constexpr float kLdsxClearWin = 1000.f;    // entries per tile from which the LDS-staged copy is not raced against the others
-
-namespace {
-struct BuildClock {
-  hipStream_t s;
-  std::chrono::steady_clock::time_point t;
-  explicit BuildClock(hipStream_t st) : s(st) { (void)hipStreamSynchronize(s); t = std::chrono::steady_clock::now(); }
-  float lap()      // ms since the last lap, the stream drained (a handful of synchronisations per matrix built)
-  {
-    (void)hipStreamSynchronize(s);
-    const auto n = std::chrono::steady_clock::now();
-    const float ms = std::chrono::duration<float, std::milli>(n - t).count();
-    t = n;
-    return ms;
-  }
-};
-}  // namespace
-
-// The L2-tiled kernel gathers from an L2-resident band of x: it has never run faster than 152 G entries per second on a matrix whose x
-// does not fit L2 (config 2: 1.05 ms for 160 M entries; its gathers alone are bound at 205 G/s, profiles/r04_probe_gather.jsonl), where the
-// two-pass pair streams 200 G valued / 280 G pattern entries per second.  So on a large matrix whose two-pass copy, just built, already
-// beats that rate, the L2-tiled copy is not built at all (config 2: 34 + 6 of 115 ms per matrix, and its transient HBM), and the
-// streaming kernel -- three to four times slower there -- is timed once instead of five times.  Auto mode only.
-constexpr double kTiledBestEntriesPerMs = 152e6;          // valued; pattern-only: 200e6 (config 2's pattern: 0.817 ms = 196 G/s, profiles/r03_cg_kernel_stats.csv)
-static int two_pass_clear_win(DeviceCsr &A, hipStream_t s, bool *win);
 
 int build_schedule(DeviceCsr &A, hipStream_t s, bool allow_tiled)
 {
@@ -331,12 +264,10 @@ int build_schedule(DeviceCsr &A, hipStream_t s, bool allow_tiled)
   hipLaunchKernelGGL(count_spanning_kernel, dim3((A.nchunks + 255) / 256), dim3(256), 0, s, A.nchunks, A.nnz,
                      A.row_ptr, A.first_row, cnt);
   FS_HIP(hipGetLastError());
-  FS_HIP(hipMemcpyAsync(&A.spanning, cnt, sizeof(int), hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
+  if (int rc = read_back(&A.spanning, cnt.p, s)) return rc;
   A.build_ms[2] = clock.lap();
   if (!allow_tiled) return FS_OK;
   // where the one-time format work goes: kept per matrix (fs_matrix_build_ms); FS_TRACE_BUILD=1 also prints it
-  static const bool trace = getenv("FS_TRACE_BUILD") != nullptr;
   // The LDS-staged copy first: where its tiles are dense (config 3: 1 700 entries per tile) it beats the two-pass pair and the
   // L2-tiled kernel two- to threefold (0.68 against 2.2 and 1.9 ms, measured by this builder for four rounds), and building and
   // timing those two only to free them again cost 135 of config 3's 475 ms per matrix and 13 GB of transient HBM.  From
@@ -359,7 +290,7 @@ int build_schedule(DeviceCsr &A, hipStream_t s, bool allow_tiled)
   const int rc = choose_copy(A, s);        // fills build_ms[6] (timing) and starts [7] (freeing the losers)
   pool_trim();
   A.build_ms[7] += clock.lap() - A.build_ms[6];
-  if (trace)
+  if (trace_build())
     fprintf(stderr, "[fastsparse] %d x %d, %lld nnz: schedule %.1f ms, two-pass copy %.1f ms, tiled copy %.1f ms, LDS-staged copy %.1f ms, "
             "candidates timed %.1f ms, losers freed %.1f ms\n", A.nrow, A.ncol, (long long)A.nnz, A.build_ms[2], A.build_ms[3], A.build_ms[4],
             A.build_ms[5], A.build_ms[6], A.build_ms[7]);
@@ -372,6 +303,64 @@ __global__ void iota_kernel(int64_t n, unsigned *__restrict__ idx)
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) idx[i] = (unsigned)i;
 }
+
+int device_iota(int64_t n, unsigned *idx, hipStream_t s)
+{
+  hipLaunchKernelGGL(iota_kernel, dim3(grid_for(n)), dim3(256), 0, s, n, idx);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// The two-call rocPRIM pattern, once per primitive: size query, temporary storage from the caller's Scratch, the real call.
+template <typename KeysIn, typename K>
+static int sort_indexed(Scratch<char> &tmp, KeysIn keys_in, K *keys_out, unsigned *idx_in, unsigned *idx_out, size_t n, int bits, hipStream_t s)
+{
+  if (int rc = device_iota((int64_t)n, idx_in, s)) return rc;
+  size_t tmp_bytes = 0;
+  FS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_in, keys_out, idx_in, idx_out, n, 0, bits, s));
+  FS_HIP(tmp.alloc(tmp_bytes));
+  FS_HIP(rocprim::radix_sort_pairs((void *)tmp.p, tmp_bytes, keys_in, keys_out, idx_in, idx_out, n, 0, bits, s));
+  return FS_OK;
+}
+
+int device_sort_indexed(Scratch<char> &tmp, const int *keys_in, int *keys_out, unsigned *idx_in, unsigned *idx_out, size_t n, int bits,
+                      hipStream_t s)
+{
+  return sort_indexed(tmp, keys_in, keys_out, idx_in, idx_out, n, bits, s);
+}
+
+int device_sort_indexed(Scratch<char> &tmp, unsigned char *keys_in, unsigned char *keys_out, unsigned *idx_in, unsigned *idx_out, size_t n,
+                      int bits, hipStream_t s)
+{
+  return sort_indexed(tmp, keys_in, keys_out, idx_in, idx_out, n, bits, s);
+}
+
+int device_sort_pairs(Scratch<char> &tmp, unsigned *k0, unsigned *k1, unsigned *v0, unsigned *v1, size_t n, int bits, hipStream_t s,
+                      const unsigned **keys, const unsigned **vals)
+{
+  rocprim::double_buffer<unsigned> dk(k0, k1), dv(v0, v1);
+  size_t tmp_bytes = 0;
+  FS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, dk, dv, n, 0, bits, s));     // stable: input order inside a run
+  FS_HIP(tmp.alloc(tmp_bytes));
+  FS_HIP(rocprim::radix_sort_pairs((void *)tmp.p, tmp_bytes, dk, dv, n, 0, bits, s));
+  *keys = dk.current();
+  *vals = dv.current();
+  return FS_OK;
+}
+
+template <typename T>
+static int exclusive_scan(Scratch<char> &tmp, T *in, T *out, size_t n, hipStream_t s)
+{
+  size_t tmp_bytes = 0;
+  FS_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, in, out, (T)0, n, rocprim::plus<T>(), s));
+  if (!tmp.p) FS_HIP(tmp.alloc(tmp_bytes));
+  if (tmp.bytes < tmp_bytes) { set_error("exclusive_scan: the shared temporary is too small for this scan"); return FS_ERR_ARG; }
+  FS_HIP(rocprim::exclusive_scan((void *)tmp.p, tmp_bytes, in, out, (T)0, n, rocprim::plus<T>(), s));
+  return FS_OK;
+}
+
+int device_exclusive_scan(Scratch<char> &tmp, int *in, int *out, size_t n, hipStream_t s) { return exclusive_scan(tmp, in, out, n, s); }
+int device_exclusive_scan(Scratch<char> &tmp, unsigned *in, unsigned *out, size_t n, hipStream_t s) { return exclusive_scan(tmp, in, out, n, s); }
 
 __global__ void permute_kernel(int64_t n, const unsigned *__restrict__ perm, const int *__restrict__ cols_in,
                                const double *__restrict__ vals_in, int *__restrict__ cols_out,
@@ -397,7 +386,12 @@ __global__ void row_ptr_kernel(int nrow, int64_t nnz, const int *__restrict__ so
   row_ptr[r] = (int)lo;
 }
 
-static unsigned grid_for(int64_t n) { return (unsigned)((n + 255) / 256 > 0 ? (n + 255) / 256 : 1); }
+static int device_row_ptr(int nrow, int64_t nnz, const int *sorted_rows, int *row_ptr, hipStream_t s)
+{
+  hipLaunchKernelGGL(row_ptr_kernel, dim3(grid_for((int64_t)nrow + 1)), dim3(256), 0, s, nrow, nnz, sorted_rows, row_ptr);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
 
 // ---- index validation at upload -------------------------------------------------------------------------
 // The reference validates nothing and a bad index there is a host segfault.  Here it would be a GPU
@@ -431,8 +425,7 @@ int validate_indices(int nrow, int ncol, int64_t nnz, const int *row_ptr_dev, co
   hipLaunchKernelGGL(validate_kernel, dim3(grid_for(n)), dim3(256), 0, s, nnz, ncol, nrow, cols_dev, rows_dev, row_ptr_dev, bad.p);
   FS_HIP(hipGetLastError());
   int h = 0;
-  FS_HIP(hipMemcpyAsync(&h, bad, sizeof(int), hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
+  if (int rc = read_back(&h, bad.p, s)) return rc;
   if (h) {
     set_error("matrix arrays are inconsistent: a column or row index is out of range, or row_ptr does not run from 0 to nnz "
               "without decreasing");
@@ -454,25 +447,16 @@ int coo_to_csr_device(DeviceCsr &out, int nrow, int ncol, int64_t nnz, const int
   Scratch<int> keys_out;
   Scratch<unsigned> idx_in, idx_out;
   Scratch<char> tmp;
-  size_t tmp_bytes = 0;
   FS_HIP(keys_out.alloc(n));
   FS_HIP(idx_in.alloc(n));
   FS_HIP(idx_out.alloc(n));
   if (nnz > 0) {
-    hipLaunchKernelGGL(iota_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, nnz, idx_in);
-    FS_HIP(hipGetLastError());
-    int bits = 1;
-    while (bits < 31 && (1ll << bits) < (long long)nrow) ++bits;
-    FS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, rows_dev, keys_out.p, idx_in.p, idx_out.p, (size_t)nnz, 0, bits, s));
-    FS_HIP(tmp.alloc(tmp_bytes));
-    FS_HIP(rocprim::radix_sort_pairs((void *)tmp.p, tmp_bytes, rows_dev, keys_out.p, idx_in.p, idx_out.p, (size_t)nnz, 0, bits, s));
+    if (int rc = device_sort_indexed(tmp, rows_dev, keys_out.p, idx_in.p, idx_out.p, (size_t)nnz, sort_bits((uint64_t)nrow, 31), s)) return rc;
     hipLaunchKernelGGL(permute_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, nnz, idx_out.p, cols_dev, vals_dev,
                        out.cols, out.vals);
     FS_HIP(hipGetLastError());
   }
-  hipLaunchKernelGGL(row_ptr_kernel, dim3(grid_for((int64_t)nrow + 1)), dim3(256), 0, s, nrow, nnz, keys_out.p,
-                     out.row_ptr);
-  FS_HIP(hipGetLastError());
+  if (int rc = device_row_ptr(nrow, nnz, keys_out.p, out.row_ptr, s)) return rc;
   FS_HIP(hipStreamSynchronize(s));
   const float order_ms = clock.lap();
   const int rc = build_schedule(out, s);   // the temporaries above go back to the pool when this function returns; the next
@@ -534,17 +518,9 @@ static int bucket_coo_impl(int kind, int param, int nrow, int ncol, int64_t nbuc
   FS_HIP(idx_out.alloc(n));
   FS_HIP(d_off.alloc((size_t)nbuckets + 1));
   if (nnz > 0) {
-    hipLaunchKernelGGL(iota_kernel, dim3(grid_for(nnz)), dim3(256), 0, s, nnz, idx_in.p);
-    FS_HIP(hipGetLastError());
-    int bits = 1;
-    while (bits < 31 && (1ll << bits) < (long long)nbuckets) ++bits;
-    size_t tmp_bytes = 0;
-    FS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, d_skeys.p, idx_in.p, idx_out.p, (size_t)nnz, 0, bits, s));
-    FS_HIP(tmp.alloc(tmp_bytes));
-    FS_HIP(rocprim::radix_sort_pairs((void *)tmp.p, tmp_bytes, keys, d_skeys.p, idx_in.p, idx_out.p, (size_t)nnz, 0, bits, s));
+    if (int rc = device_sort_indexed(tmp, keys, d_skeys.p, idx_in.p, idx_out.p, (size_t)nnz, sort_bits((uint64_t)nbuckets, 31), s)) return rc;
   }
-  hipLaunchKernelGGL(row_ptr_kernel, dim3(grid_for(nbuckets + 1)), dim3(256), 0, s, (int)nbuckets, nnz, d_skeys.p, d_off.p);
-  FS_HIP(hipGetLastError());
+  if (int rc = device_row_ptr((int)nbuckets, nnz, d_skeys.p, d_off.p, s)) return rc;
   FS_HIP(d_cols_o.alloc(n));
   if (rows_out) FS_HIP(d_rows_o.alloc(n));
   if (vals) {
@@ -681,6 +657,17 @@ __global__ void cut_kernel(int n_items, const int64_t *__restrict__ inc, int npa
 
 struct IntToI64 { __device__ int64_t operator()(int v) const { return (int64_t)v; } };
 
+// inclusive prefix sums of int counts in 64 bits, in the manner of exclusive_scan above
+static int device_inclusive_scan(Scratch<char> &tmp, const int *in, int64_t *out, size_t n, hipStream_t s)
+{
+  size_t tmp_bytes = 0;
+  auto it = rocprim::make_transform_iterator(in, IntToI64());
+  FS_HIP(rocprim::inclusive_scan(nullptr, tmp_bytes, it, out, n, rocprim::plus<int64_t>(), s));
+  FS_HIP(tmp.alloc(tmp_bytes));
+  FS_HIP(rocprim::inclusive_scan((void *)tmp.p, tmp_bytes, it, out, n, rocprim::plus<int64_t>(), s));
+  return FS_OK;
+}
+
 int cut_by_counts(int n_items, const int *counts_dev, int nparts, int *bounds_host, int64_t *total, hipStream_t s)
 {
   Scratch<int64_t> inc;
@@ -688,13 +675,8 @@ int cut_by_counts(int n_items, const int *counts_dev, int nparts, int *bounds_ho
   Scratch<char> tmp;
   FS_HIP(inc.alloc((size_t)n_items + 1));
   FS_HIP(bd.alloc((size_t)nparts + 1));
-  if (n_items > 0) {
-    size_t tmp_bytes = 0;
-    auto in = rocprim::make_transform_iterator(counts_dev, IntToI64());
-    FS_HIP(rocprim::inclusive_scan(nullptr, tmp_bytes, in, inc.p, (size_t)n_items, rocprim::plus<int64_t>(), s));
-    FS_HIP(tmp.alloc(tmp_bytes));
-    FS_HIP(rocprim::inclusive_scan((void *)tmp.p, tmp_bytes, in, inc.p, (size_t)n_items, rocprim::plus<int64_t>(), s));
-  }
+  if (n_items > 0)
+    if (int rc = device_inclusive_scan(tmp, counts_dev, inc.p, (size_t)n_items, s)) return rc;
   hipLaunchKernelGGL(cut_kernel, dim3(grid_for((int64_t)nparts + 1)), dim3(256), 0, s, n_items, inc.p, nparts, bd.p);
   FS_HIP(hipGetLastError());
   FS_HIP(hipMemcpyAsync(bounds_host, bd.p, sizeof(int) * ((size_t)nparts + 1), hipMemcpyDeviceToHost, s));
@@ -773,14 +755,7 @@ int shard_transpose_partition(const DeviceCsr &A, int row_lo, int nparts, const 
   FS_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long) * (size_t)nparts, s));
   hipLaunchKernelGGL(expand_rows_kernel, dim3(grid_for(A.nnz)), dim3(256), 0, s, A.nrow, A.nnz, A.row_ptr, rows.p);
   hipLaunchKernelGGL(dest_key_kernel, dim3(grid_for(A.nnz)), dim3(256), 0, s, A.nnz, nparts, bd.p, A.cols, key.p, cnt.p);
-  hipLaunchKernelGGL(iota_kernel, dim3(grid_for(A.nnz)), dim3(256), 0, s, A.nnz, idx_in.p);
-  FS_HIP(hipGetLastError());
-  int bits = 1;
-  while ((1 << bits) < nparts) ++bits;
-  size_t tmp_bytes = 0;
-  FS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, key.p, skey.p, idx_in.p, idx_out.p, (size_t)A.nnz, 0, bits, s));
-  FS_HIP(tmp.alloc(tmp_bytes));
-  FS_HIP(rocprim::radix_sort_pairs((void *)tmp.p, tmp_bytes, key.p, skey.p, idx_in.p, idx_out.p, (size_t)A.nnz, 0, bits, s));
+  if (int rc = device_sort_indexed(tmp, key.p, skey.p, idx_in.p, idx_out.p, (size_t)A.nnz, sort_bits((uint64_t)nparts, 31), s)) return rc;
   hipLaunchKernelGGL(transpose_gather_kernel, dim3(grid_for(A.nnz)), dim3(256), 0, s, A.nnz, row_lo, bd.p, skey.p, idx_out.p, rows.p,
                      A.cols, A.vals, *trow, *tcol, *tval);
   FS_HIP(hipGetLastError());
@@ -791,69 +766,7 @@ int shard_transpose_partition(const DeviceCsr &A, int row_lo, int nparts, const 
   return FS_OK;
 }
 
-// ---- L2-tiled copy ---------------------------------------------------------------------------------
-// Long rows are cut into pieces of at most `split` consecutive entries ("virtual rows"): the tiled kernel then
-// never meets a row that dwarfs a panel or a run that one lane has to walk for long, and the pieces' sums are
-// added per row, in storage order, by a combine pass.  A matrix without long rows is its own virtual matrix.
-__global__ void piece_count_kernel(int nrow, int split, const int *__restrict__ row_ptr, int *__restrict__ cnt)
-{
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r > nrow) return;
-  if (r == nrow) { cnt[r] = 0; return; }
-  const int len = row_ptr[r + 1] - row_ptr[r];
-  cnt[r] = len <= split ? 1 : (len + split - 1) / split;
-}
-
-__global__ void vrow_fill_kernel(int nrow, int split, const int *__restrict__ row_ptr, const int *__restrict__ vfirst,
-                                 int *__restrict__ vrow_ptr)
-{
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r > nrow) return;
-  if (r == nrow) { vrow_ptr[vfirst[nrow]] = row_ptr[nrow]; return; }
-  const int a = row_ptr[r], v0 = vfirst[r], k = vfirst[r + 1] - v0;
-  for (int i = 0; i < k; ++i) vrow_ptr[v0 + i] = a + i * split;
-}
-
-// last index i in [0, n] with a[i] <= key (a non-decreasing, a[0] <= key)
-__device__ __forceinline__ int last_le(const int *__restrict__ a, int n, int64_t key)
-{
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo + 1) >> 1);
-    if ((int64_t)a[mid] <= key) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// key of entry e = panel(virtual row) * J + band(col); a stable sort by key starting from CSR order leaves every
-// (panel, band) tile ordered by virtual row and, inside a row, in CSR storage order.
-__global__ void tile_key_kernel(int nvrow, int64_t nnz, int P, int W, int J, const int *__restrict__ vrow_ptr,
-                                const int *__restrict__ panel_row, const int *__restrict__ cols,
-                                int *__restrict__ vrows, unsigned *__restrict__ keys)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nnz) return;
-  const int v = last_le(vrow_ptr, nvrow, i);      // empty virtual rows share a start: take the last, non-empty one
-  vrows[i] = v;
-  const int p = last_le(panel_row, P, v);
-  keys[i] = (unsigned)p * (unsigned)J + (unsigned)(cols[i] / W);
-}
-
-__global__ void tile_pack_kernel(int64_t nnz, int W, int J, int lcol_bits, const unsigned *__restrict__ skeys,
-                                 const unsigned *__restrict__ perm, const int *__restrict__ vrows,
-                                 const int *__restrict__ panel_row, const int *__restrict__ cols,
-                                 const double *__restrict__ vals, unsigned *__restrict__ pk, double *__restrict__ vals_out)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nnz) return;
-  const unsigned src = perm[i];
-  const unsigned key = skeys[i];
-  const unsigned p = key / (unsigned)J, j = key % (unsigned)J;
-  const unsigned lrow = (unsigned)(vrows[src] - panel_row[p]), lcol = (unsigned)(cols[src] - (int)j * W);
-  pk[i] = (lrow << lcol_bits) | lcol;
-  if (vals) vals_out[i] = vals[src];
-}
-
+// ---- run pointers of the copies' sorted keys (fs_copies.hip, through device_run_ptr) -------------------------------------
 // tile_ptr[k] = first sorted position whose key is >= k, k = 0 .. ntiles
 __global__ void tile_ptr_kernel(int64_t ntiles, int64_t nnz, const unsigned *__restrict__ skeys, int *__restrict__ tile_ptr)
 {
@@ -867,1583 +780,10 @@ __global__ void tile_ptr_kernel(int64_t ntiles, int64_t nnz, const unsigned *__r
   tile_ptr[k] = (int)lo;
 }
 
-__global__ void max_row_len_kernel(int nrow, const int *__restrict__ row_ptr, int *__restrict__ out)
+int device_run_ptr(int64_t nruns, int64_t n, const unsigned *sorted_keys, int *run_ptr, hipStream_t s)
 {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  int len = r < nrow ? row_ptr[r + 1] - row_ptr[r] : 0;
-  for (int m = 32; m > 0; m >>= 1) { const int o = __shfl_xor(len, m); len = o > len ? o : len; }
-  // one atomic per wave on ONE address cost 1.8 ms for 10 M rows (156 K serialised atomics); a wave whose maximum is not above what is
-  // already there has nothing to add -- on uniform rows all but the first few skip
-  if ((threadIdx.x & 63) == 0 && len > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, len);
-}
-
-// virtual rows of A for rows longer than `split`: vrow_ptr (nvrow + 1 entry offsets), vfirst (first virtual row of
-// every row) and the vector of virtual sums; the two device arrays are handed to the caller's structure at once so
-// that its destructor releases them on every path
-static int make_virtual_rows(const DeviceCsr &A, int split, hipStream_t s, Scratch<int> &vrow_ptr, int *nvrow_out,
-                             int **vfirst_out, double **yv_out, int kw = 1)
-{
-  Scratch<int> cnt;
-  Scratch<char> tmp;
-  size_t tmp_bytes = 0;
-  int nvrow = 0;
-  FS_HIP(cnt.alloc((size_t)A.nrow + 1));
-  FS_HIP(traced_malloc(vfirst_out, sizeof(int) * ((size_t)A.nrow + 1)));
-  int *vfirst = *vfirst_out;
-  hipLaunchKernelGGL(piece_count_kernel, dim3(grid_for((int64_t)A.nrow + 1)), dim3(256), 0, s, A.nrow, split, A.row_ptr,
-                     cnt.p);
+  hipLaunchKernelGGL(tile_ptr_kernel, dim3(grid_for(nruns + 1)), dim3(256), 0, s, nruns, n, sorted_keys, run_ptr);
   FS_HIP(hipGetLastError());
-  FS_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, cnt.p, vfirst, 0, (size_t)A.nrow + 1, rocprim::plus<int>(), s));
-  FS_HIP(tmp.alloc(tmp_bytes));
-  FS_HIP(rocprim::exclusive_scan((void *)tmp.p, tmp_bytes, cnt.p, vfirst, 0, (size_t)A.nrow + 1, rocprim::plus<int>(), s));
-  FS_HIP(hipMemcpyAsync(&nvrow, vfirst + A.nrow, sizeof(int), hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  FS_HIP(vrow_ptr.alloc((size_t)nvrow + 1));
-  hipLaunchKernelGGL(vrow_fill_kernel, dim3(grid_for((int64_t)A.nrow + 1)), dim3(256), 0, s, A.nrow, split, A.row_ptr,
-                     vfirst, vrow_ptr.p);
-  FS_HIP(hipGetLastError());
-  FS_HIP(traced_malloc(yv_out, sizeof(double) * (size_t)nvrow * (size_t)kw));
-  *nvrow_out = nvrow;
-  return FS_OK;
-}
-
-static int max_row_len(const DeviceCsr &A, hipStream_t s, int *out)
-{
-  if (A.max_row_len >= 0) { *out = A.max_row_len; return FS_OK; }       // (every candidate builder asks)
-  Scratch<int> mx;
-  FS_HIP(mx.alloc(1));
-  FS_HIP(hipMemsetAsync(mx, 0, sizeof(int), s));
-  hipLaunchKernelGGL(max_row_len_kernel, dim3(grid_for(A.nrow)), dim3(256), 0, s, A.nrow, A.row_ptr, mx.p);
-  FS_HIP(hipGetLastError());
-  FS_HIP(hipMemcpyAsync(out, mx, sizeof(int), hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  A.max_row_len = *out;
-  return FS_OK;
-}
-
-// LDS-staged kernel only: inside a work item the order of the entries is free (the kernel adds with LDS atomics), so
-// every item is rearranged for the LDS banks.  A half-wave (32 lanes) of the kernel takes 32 consecutive members of a
-// SEQUENCE built here; its ds_add_f64 into the y slice is conflict-free when the 32 local rows differ mod 32 (bank pairs),
-// its ds_read_b64 from the x slice when the 32 local columns differ mod 32.
-//   Rows: round-robin over the row classes (local row mod 32) -- round r holds one entry of every class that still has
-//     one, in class order, so lane l of a half-wave adds into bank pair l until the classes start to run out.
-//   Columns (ARRANGE; FS_LDSX_ARRANGE=0 turns it off): WHICH entry of its class goes into round r is free.  The classes
-//     of a round choose together so that their column banks differ: every class proposes a bank it still has entries for
-//     and that the round has not used (starting from the diagonal (class + round) mod 32), the lowest class wins a
-//     contested bank, the losers propose again; a class left without a free bank takes any.  Random columns cost 3.5
-//     cycles per half-wave gather in stored order and about 2 this way (simulated).  Measured on config 3 with a serial
-//     greedy of the same quality (which took 570 ms per matrix; this one works a round with 32 lanes at once):
-//     A 0.79 -> 0.745 ms, A' 0.866 -> 0.824 ms.
-// Sequence place s goes to stored position 2s (first half) or 2(s - half) + 1: the kernel's thread t takes the ADJACENT
-// entries 2t and 2t + 1 (one 8-byte load), so the lanes of a wave see, for their first entry, every other stored
-// position, and each of the two adds of a wave walks consecutive members of the sequence.
-__device__ __forceinline__ int rot_ffs(unsigned m, int rot)   // lowest set bit of m at or after bit `rot`, cyclically (m != 0)
-{
-  const unsigned rr = rot ? ((m >> rot) | (m << (32 - rot))) : m;
-  return (__ffs((int)rr) - 1 + rot) & 31;
-}
-
-// orders the LDS accesses of the lanes of ONE wave (the hardware runs a wave's LDS instructions in order; this keeps the
-// compiler from moving them across and waits for the ones in flight)
-__device__ __forceinline__ void wave_lds_fence()
-{
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-}
-
-constexpr int kReorderThreads = 256;
-constexpr int kReorderSegs = kReorderThreads / 32;               // the item is counted in 8 segments at once
-constexpr int kReorderPer = kTiledItem / kReorderThreads;        // entries per thread when the item is copied out
-
-// Fixed-order sums (TiledCsr::orderable): a half of the sequence of 64 places is what ONE wave of the kernel adds with one
-// instruction (thread = stored position / 2, wave = thread / 64), and a wave's LDS adds execute in program order.  So when all
-// entries of a row inside an item sit with one wave, the row's y slot receives them in a fixed order whatever the other waves do.
-// Rows with more than one entry in an item are few (config 3: 1 700 entries over 13 000 rows, ~110 of them) -- after the
-// rounds, every such row is brought together: its entries swap places with single-entry rows of the same class (the class
-// decides the LDS bank, so the bank arrangement of the rows is untouched; the column banks of the swapped pair change).
-// *bad counts the items where that was not possible (a row with more entries than a wave has places for its class, a class
-// too large to search): fixed-order products then leave this copy alone.
-constexpr int kRepairMaxClass = 256;   // entries of one class the repair searches (2048 / 32 = 64 on average)
-constexpr int kRepairMaxGroup = 8;     // entries of one row inside an item the per-class pass handles
-constexpr int kRepairMaxLeft = 128;    // rows of an item left to the any-class pass
-constexpr int kRepairMaxBig = 96;      // entries of one row inside an item at most (a wave holds 128 entries of an item)
-
-template <bool ARRANGE>
-__global__ __launch_bounds__(kReorderThreads) void ldsx_reorder_kernel(const int4 *__restrict__ items, int lcol_bits,
-                                                                      unsigned *__restrict__ pk, double *__restrict__ vals,
-                                                                      int *__restrict__ bad, unsigned long long *__restrict__ clk)
-{
-  // clk (FS_LDSX_REORDER_PROFILE=1, else nullptr): core clocks of thread 0 per phase, summed over the workgroups -- [0] load + count,
-  // [1] prefixes + lists, [2] the rounds (wave 0), [3] repair: rows and leaders, [4] repair per class, [5] repair of what is left,
-  // [6] copy out
-  long long tick = clk ? clock64() : 0;
-  auto lap = [&](int phase) {
-    if (clk && threadIdx.x == 0) { const long long now = clock64(); atomicAdd(&clk[phase], (unsigned long long)(now - tick)); tick = now; }
-  };
-  __shared__ unsigned w[kTiledItem];
-  __shared__ unsigned short lst[kTiledItem];   // entries grouped by (row class, column bank), stored order inside a group
-  __shared__ unsigned short seq[kTiledItem];   // first: rank of an entry inside its (segment, class, bank); then the sequence
-  __shared__ unsigned short segcnt[kReorderSegs][32 * 32];   // entries of (class, bank) per segment, then their prefix
-  __shared__ unsigned short left[32 * 32];     // entries of (class, bank) not placed yet
-  __shared__ unsigned short size[32 * 32];     // entries of (class, bank)
-  __shared__ unsigned short off[32 * 32];      // first entry of (class, bank) in lst
-  __shared__ int owner[32];
-  // the repair: per class (entries of class c are indices off[c * 32] .. of these arrays, in round order).  They live in the
-  // storage of segcnt, which is dead once lst is filled (with 14 KiB more LDS only two workgroups fit a CU instead of four, and
-  // the kernel took twice as long: 219 -> 458 ms on config 3)
-  static_assert(kReorderSegs * 32 * 32 >= 3 * kTiledItem + kTiledItem / 2, "the repair arrays are carved out of segcnt");
-  unsigned short *const cplace = &segcnt[0][0];                   // place in the sequence
-  unsigned short *const crow = &segcnt[0][0] + kTiledItem;        // local row
-  unsigned short *const lead = &segcnt[0][0] + 2 * kTiledItem;    // first index of the class with the same row
-  unsigned char *const flag = reinterpret_cast<unsigned char *>(&segcnt[0][0] + 3 * kTiledItem);   // bit 0: a leader whose row has
-                                                                  // further entries; bit 1: placed for good
-  __shared__ unsigned short unres[kRepairMaxLeft]; // leaders of the rows the per-class pass could not bring together
-  __shared__ unsigned short pmem[kRepairMaxBig];  // the entries of one such row
-  __shared__ int nunres, ndup, wcount[32];
-  const int4 d = items[blockIdx.x];
-  const int n = d.y, t = threadIdx.x;
-  for (int i = t; i < n; i += kReorderThreads) w[i] = pk[(int64_t)d.x + i];
-  for (int i = t; i < kReorderSegs * 32 * 32; i += kReorderThreads) (&segcnt[0][0])[i] = 0;
-  __syncthreads();
-  // thread (segment, class) walks its segment of the item and ranks the entries of its class per column bank
-  {
-    const int sg = t >> 5, c = t & 31;
-    const int per = (n + kReorderSegs - 1) / kReorderSegs;
-    const int i0 = sg * per, i1 = (i0 + per < n) ? i0 + per : n;
-    for (int i = i0; i < i1; ++i)
-      if ((int)((w[i] >> lcol_bits) & 31u) == c) {
-        const int k = c * 32 + (ARRANGE ? (int)(w[i] & 31u) : 0);
-        seq[i] = segcnt[sg][k]++;
-      }
-  }
-  __syncthreads();
-  lap(0);
-  // per (class, bank): prefix over the segments, total
-  for (int k = t; k < 32 * 32; k += kReorderThreads) {
-    int a = 0;
-    for (int sg = 0; sg < kReorderSegs; ++sg) { const int m = segcnt[sg][k]; segcnt[sg][k] = (unsigned short)a; a += m; }
-    size[k] = (unsigned short)a;
-    left[k] = (unsigned short)a;
-  }
-  __syncthreads();
-  // lane c of wave 0 owns row class c: offsets of its banks in lst (class totals by a wave scan)
-  unsigned avail = 0;                           // banks this class still has entries for
-  int mine = 0;
-  if (t < 64) {
-    if (t < 32)
-      for (int b = 0; b < 32; ++b) mine += size[t * 32 + b];
-    int base = mine;
-    for (int m = 1; m < 32; m <<= 1) {
-      const int o = __shfl_up(base, m);
-      if (t >= m) base += o;
-    }
-    base -= mine;
-    if (t < 32) {
-      int a = base;
-      for (int b = 0; b < 32; ++b) {
-        off[t * 32 + b] = (unsigned short)a;
-        a += size[t * 32 + b];
-        if (size[t * 32 + b]) avail |= 1u << b;
-      }
-    }
-  }
-  __syncthreads();
-  {
-    const int per = (n + kReorderSegs - 1) / kReorderSegs;
-    for (int i = t; i < n; i += kReorderThreads) {
-      const int k = (int)((w[i] >> lcol_bits) & 31u) * 32 + (ARRANGE ? (int)(w[i] & 31u) : 0);
-      lst[off[k] + segcnt[i / per][k] + seq[i]] = (unsigned short)i;
-    }
-  }
-  __syncthreads();
-  lap(1);
-  if (t < 64) {                                 // the rounds: wave 0, lanes 32-63 only take part in the ballots
-    int remaining = t < 32 ? mine : 0, placed = 0;
-    for (int r = 0;; ++r) {
-      const unsigned nonempty = (unsigned)__ballot(remaining > 0);
-      if (!nonempty) break;
-      unsigned used = 0;
-      int bank = -1;
-      bool pending = remaining > 0;
-      for (int iter = 0;; ++iter) {
-        int prop = -1;
-        if (pending) {
-          const unsigned free_banks = avail & ~used;
-          const int rot = (t + r + 7 * iter) & 31;
-          if (!ARRANGE || free_banks == 0u) { bank = rot_ffs(avail, rot); pending = false; }
-          else prop = rot_ffs(free_banks, rot);
-        }
-        if (!__ballot(prop >= 0)) break;        // everybody is settled
-        if (t < 32) owner[t] = 255;
-        wave_lds_fence();
-        if (prop >= 0) atomicMin(&owner[prop], t);
-        wave_lds_fence();
-        if (prop >= 0 && owner[prop] == t) { bank = prop; pending = false; }
-        used |= (unsigned)__ballot(t < 32 && owner[t & 31] != 255);    // lane index = bank index
-        wave_lds_fence();
-      }
-      if (bank >= 0) {
-        const int k = t * 32 + bank;
-        const int before = left[k];
-        left[k] = (unsigned short)(before - 1);
-        if (before == 1) avail &= ~(1u << bank);
-        const int place = placed + __popc(nonempty & ((1u << t) - 1u));
-        seq[place] = lst[off[k] + (size[k] - before)];
-        cplace[off[t * 32] + (mine - remaining)] = (unsigned short)place;
-        --remaining;
-      }
-      placed += __popc(nonempty);
-    }
-  }
-  __syncthreads();
-  lap(2);
-  const int half = (n + 1) >> 1;
-  // ---- the repair: the entries of a row with one wave ----------------------------------------------------------------------
-  {
-    // (a) every index: its row, and the first index of its class with the same row
-    for (int g = t; g < n; g += kReorderThreads) crow[g] = (unsigned short)(w[seq[cplace[g]]] >> lcol_bits);
-    __syncthreads();
-    bool too_large = false;
-    const int wv = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
-    auto rdlane = [](int v, int l) { return __builtin_amdgcn_readlane(v, __builtin_amdgcn_readfirstlane(l)); };
-    // wave wv takes the classes 8 wv .. 8 wv + 7, one after the other, 64 entries of the class with its lanes at a time: the rows
-    // travel between the lanes through v_readlane (a thread per entry scanning its class in LDS was 83 K of the kernel's clocks)
-    for (int q8 = 0; q8 < 8; ++q8) {
-      const int c = wv * 8 + q8;
-      // (wave-uniform values read from LDS: said so, or the loops over a class run under exec masks with their counters in VGPRs --
-      // that alone was 70 K clocks per item)
-      const int base = __builtin_amdgcn_readfirstlane((int)off[c * 32]);
-      const int msize = __builtin_amdgcn_readfirstlane((c < 31 ? (int)off[(c + 1) * 32] : n) - base);
-      const int m = msize < kRepairMaxClass ? msize : kRepairMaxClass;
-      int row[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int idx = 64 * e + lane;
-        row[e] = idx < m ? (int)crow[base + idx] : -1 - idx;              // (no row is negative: a lane outside the class matches nothing)
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (64 * e < m) {
-          int first = -1;                                                  // place in the class of the first earlier entry of this row
-#pragma unroll
-          for (int e2 = 0; e2 < 4; ++e2) {
-            if (e2 <= e) {
-              const int lim = e2 < e ? 64 : lane;
-              const int cnt = m - 64 * e2 < 64 ? m - 64 * e2 : 64;
-              for (int l = 0; l < cnt; ++l) {
-                const int rl = rdlane(row[e2], l);
-                if (first < 0 && rl == row[e] && l < lim) first = 64 * e2 + l;
-              }
-            }
-          }
-          const int idx = 64 * e + lane;
-          if (idx < m) {
-            lead[base + idx] = (unsigned short)(base + (first < 0 ? idx : first));
-            flag[base + idx] = 0;
-          }
-        }
-      }
-      for (int idx = kRepairMaxClass + lane; idx < msize; idx += 64) {     // a class beyond what the repair searches
-        lead[base + idx] = (unsigned short)(base + idx);
-        flag[base + idx] = 0;
-        too_large = true;
-      }
-    }
-    __syncthreads();
-    if (t == 0) { nunres = 0; ndup = 0; }
-    __syncthreads();
-    {
-      int mydup = 0;
-      for (int g = t; g < n; g += kReorderThreads)
-        if (lead[g] != g) { flag[lead[g]] = 1; ++mydup; }          // (several writers, one value)
-      if (mydup) atomicAdd(&ndup, mydup);
-    }
-    __syncthreads();
-    // an item in which every fourth entry repeats a row (dense rows: long rows of a short panel) is not worth the search: the
-    // copy then simply has no fixed-order form
-    lap(3);
-    const bool hopeless = 4 * ndup > n && n > 128;   // (up to 128 entries all sit with wave 0 anyway)
-    // (b) lane c of wave 0 brings the rows of class c together, one after the other, trading places with single-entry rows of
-    // the SAME class only (the lanes work on disjoint lists); what does not fit that way goes on the list of (c)
-    bool failed = too_large || hopeless;
-    auto wave_of = [&](int g) { const int sp = cplace[g]; return (sp < half ? sp : sp - half) >> 6; };
-    auto trade = [&](int j, int k, int g) {                     // member at index j <-> single-entry row at index k
-      const unsigned short ej = seq[cplace[j]], ek = seq[cplace[k]];
-      seq[cplace[j]] = ek; seq[cplace[k]] = ej;
-      const unsigned short rj = crow[j]; crow[j] = crow[k]; crow[k] = rj;
-      lead[k] = (unsigned short)g; flag[k] = 2;                  // the member now lives at k, for good
-      lead[j] = (unsigned short)j; flag[j] = 0;                  // j holds the single-entry row
-    };
-    // Wave wv takes the classes 8 wv .. 8 wv + 7 one after the other with its lanes holding the class's entries (four per lane:
-    // up to kRepairMaxClass): which row is next, who its members are, which wave holds most of them and where that wave has a free
-    // single-entry row are BALLOTS over the lanes, a handful of instructions each, where one lane per class used to walk 64-entry
-    // lists in LDS (0.28 M of the kernel's 0.59 M clocks per item).  Same choices as that serial form, so the same arrangement:
-    // rows in ascending leader order, the wave that holds most members (the lowest on a tie), free rows lowest index first.
-    if (!hopeless) {
-      for (int q8 = 0; q8 < 8; ++q8) {
-        const int c = wv * 8 + q8;
-        const int base = __builtin_amdgcn_readfirstlane((int)off[c * 32]);
-        const int msize = __builtin_amdgcn_readfirstlane((c < 31 ? (int)off[(c + 1) * 32] : n) - base);
-        const int m = msize < kRepairMaxClass ? msize : kRepairMaxClass;
-        if (m <= 0) continue;
-        int wof[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) wof[e] = 64 * e + lane < m ? wave_of(base + 64 * e + lane) : 31;
-        int myfree = 0;                                              // lane v < 16: free single-entry rows of this class with wave v
-        {
-          bool fr[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int g = base + 64 * e + lane;
-            fr[e] = 64 * e + lane < m && lead[g] == g && !(flag[g] & 3);
-          }
-          for (int v = 0; v < 16; ++v) {
-            int cnt = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) cnt += __popcll(__ballot(fr[e] && wof[e] == v));
-            if (lane == v) myfree = cnt;
-          }
-        }
-        int cursor = -1;                                             // place in the class of the last row handled
-        for (;;) {
-          int G = -1;                                                // the next leader of a row with several entries
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const int idx = 64 * e + lane, g = base + idx;
-            const bool d = idx < m && idx > cursor && lead[g] == g && (flag[g] & 1) && !(flag[g] & 2);
-            const unsigned long long mk = __ballot(d);
-            if (G < 0 && mk) G = 64 * e + __ffsll((long long)mk) - 1;
-          }
-          if (G < 0) break;
-          cursor = G;
-          const int gG = base + G;
-          bool mem[4];
-          int gs = 0;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            mem[e] = 64 * e + lane < m && lead[base + 64 * e + lane] == gG;
-            gs += __popcll(__ballot(mem[e]));
-          }
-          int best = -1;
-          if (gs <= kRepairMaxGroup) {
-            int have = 0;                                            // lane v < 16: members already with wave v
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-              unsigned long long bits = __ballot(mem[e]);
-              while (bits) {
-                const int l = __ffsll((long long)bits) - 1;
-                bits &= bits - 1;
-                if (lane == rdlane(wof[e], l)) ++have;
-              }
-            }
-            int key = (lane < 16 && have + myfree >= gs) ? ((have << 8) | (15 - lane)) : -1;   // most members; the lowest wave on a tie
-            for (int o = 32; o > 0; o >>= 1) { const int other = __shfl_xor(key, o); key = other > key ? other : key; }
-            if (key >= 0) best = 15 - (key & 255);
-          }
-          if (best < 0) {                                            // too many entries, or no wave with room: left to (c)
-            if (lane == 0) {
-              const int slot = atomicAdd(&nunres, 1);
-              if (slot < kRepairMaxLeft) unres[slot] = (unsigned short)gG; else failed = true;
-            }
-            continue;
-          }
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            unsigned long long bits = __ballot(mem[e]);
-            while (bits) {
-              const int l = __ffsll((long long)bits) - 1;
-              bits &= bits - 1;
-              const int j = base + 64 * e + l;
-              const int wj = rdlane(wof[e], l);
-              if (wj == best) {
-                if (lane == 0) flag[j] |= 2;
-                wave_lds_fence();
-                continue;
-              }
-              int k = -1;                                            // the lowest free single-entry row with that wave
-#pragma unroll
-              for (int e2 = 0; e2 < 4; ++e2) {
-                const int g2 = base + 64 * e2 + lane;
-                const bool f = 64 * e2 + lane < m && wof[e2] == best && lead[g2] == g2 && !(flag[g2] & 3);
-                const unsigned long long fm = __ballot(f);
-                if (k < 0 && fm) k = base + 64 * e2 + __ffsll((long long)fm) - 1;
-              }
-              if (k < 0) { failed = true; break; }                   // (cannot happen: myfree counted it)
-              if (lane == 0) trade(j, k, gG);
-              wave_lds_fence();
-              if (lane == best) --myfree;
-              if (lane == wj) ++myfree;                              // j now holds the single-entry row
-            }
-          }
-          wave_lds_fence();
-        }
-      }
-    }
-    __syncthreads();
-    // the rows left to (c) in ascending order whichever wave listed them first: the arrangement must not depend on timing
-    {
-      const int cnt = nunres < kRepairMaxLeft ? nunres : kRepairMaxLeft;
-      int mine_u = 0, rank = 0;
-      if (t < cnt) {
-        mine_u = unres[t];
-        for (int j = 0; j < cnt; ++j) rank += unres[j] < mine_u;
-      }
-      __syncthreads();
-      if (t < cnt) unres[rank] = (unsigned short)mine_u;
-    }
-    __syncthreads();
-    lap(4);
-    // (c) what is left -- rows with more entries than a wave has places for their class, or an unlucky packing -- trades places
-    // with single-entry rows of ANY class of the chosen wave (a few lanes of that wave then share a bank: rare).  One row after
-    // the other; the whole workgroup counts the members and the free single-entry rows per wave, thread 0 chooses and trades.
-    {
-      const int left = hopeless ? 0 : (nunres < kRepairMaxLeft ? nunres : kRepairMaxLeft);    // (uniform: nunres is in LDS)
-      if (!hopeless && nunres > kRepairMaxLeft) failed = true;
-      for (int u = 0; u < left; ++u) {
-        const int g = unres[u];
-        if (t < 32) wcount[t] = 0;                               // [0, 16): members per wave, [16, 32): free single-entry rows
-        __syncthreads();
-        for (int j = t; j < n; j += kReorderThreads) {
-          const int v = wave_of(j);
-          if (lead[j] == g) atomicAdd(&wcount[v], 1);
-          else if (lead[j] == j && !(flag[j] & 3)) atomicAdd(&wcount[16 + v], 1);
-        }
-        __syncthreads();
-        if (t == 0 && !failed) {
-          const int c = crow[g] & 31, base = off[c * 32];
-          int m = (c < 31 ? (int)off[(c + 1) * 32] : n) - base;
-          if (m > kRepairMaxClass) m = kRepairMaxClass;
-          int gs = 0;
-          for (int j = g; j < base + m; ++j)
-            if (lead[j] == g) { if (gs < kRepairMaxBig) pmem[gs] = (unsigned short)j; ++gs; }
-          int best = -1;                                         // the wave that already holds most of the row, among those with room
-          for (int v = 0; v < 16; ++v)
-            if (wcount[v] + wcount[16 + v] >= gs && (best < 0 || wcount[v] > wcount[best])) best = v;
-          if (gs > kRepairMaxBig || best < 0) failed = true;
-          else {
-            int next = 0;
-            for (int q = 0; q < gs; ++q) {
-              const int j = pmem[q];
-              if (wave_of(j) == best) { flag[j] |= 2; continue; }
-              while (next < n && !(wave_of(next) == best && lead[next] == next && !(flag[next] & 3))) ++next;
-              if (next >= n) { failed = true; break; }
-              trade(j, next, g);
-            }
-          }
-        }
-        __syncthreads();
-      }
-    }
-    if (failed) atomicAdd(bad, 1);
-  }
-  __syncthreads();
-  lap(5);
-  // copy out: sources into registers first (the item is permuted in place)
-  double v[kReorderPer];
-#pragma unroll
-  for (int j = 0; j < kReorderPer; ++j) {
-    const int q = t + j * kReorderThreads;
-    v[j] = (vals && q < n) ? vals[(int64_t)d.x + seq[q]] : 0.0;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < kReorderPer; ++j) {
-    const int q = t + j * kReorderThreads;
-    if (q < n) {
-      const int pos = q < half ? 2 * q : 2 * (q - half) + 1;
-      pk[(int64_t)d.x + pos] = w[seq[q]];
-      if (vals) vals[(int64_t)d.x + pos] = v[j];
-    }
-  }
-  lap(6);
-}
-
-// how many column bands of W columns do the entries of panel (blockIdx.x * stride) touch?  out[2b] = bands, out[2b + 1] = entries
-constexpr int kPanelBandWords = 8192;    // 262 144 bands: 32 KiB of LDS
-__global__ __launch_bounds__(256) void panel_bands_kernel(int stride, int W, int words, const int *__restrict__ panel_row,
-                                                          const int *__restrict__ row_ptr, const int *__restrict__ cols,
-                                                          int *__restrict__ out)
-{
-  __shared__ unsigned bits[kPanelBandWords];
-  __shared__ int total;
-  const int p = blockIdx.x * stride, t = threadIdx.x;
-  for (int i = t; i < words; i += 256) bits[i] = 0u;
-  if (t == 0) total = 0;
-  __syncthreads();
-  const int64_t e0 = row_ptr[panel_row[p]], e1 = row_ptr[panel_row[p + 1]];
-  for (int64_t e = e0 + t; e < e1; e += 256) {
-    const int b = cols[e] / W;
-    atomicOr(&bits[b >> 5], 1u << (b & 31));
-  }
-  __syncthreads();
-  int c = 0;
-  for (int i = t; i < words; i += 256) c += __popc(bits[i]);
-  atomicAdd(&total, c);
-  __syncthreads();
-  if (t == 0) { out[2 * blockIdx.x] = total; out[2 * blockIdx.x + 1] = (int)(e1 - e0); }
-}
-
-static int build_tiled_impl(DeviceCsr &A, hipStream_t s, TiledCsr *&slot, bool ldsx);
-
-// The tiled copies are optimisations: if building one fails (typically: not enough HBM for another copy) the
-// matrix stays usable on the other kernels.
-int build_tiled(DeviceCsr &A, hipStream_t s)
-{
-  const int rc = build_tiled_impl(A, s, A.tiled, false);
-  if (rc != FS_OK || (A.tiled && !A.tiled->built)) {
-    free_tiled(A);
-    (void)hipGetLastError();
-  }
-  return FS_OK;
-}
-
-// the same layout with the geometry of the LDS-staged kernel (x slices of kLdsxCols columns)
-int build_tiledx(DeviceCsr &A, hipStream_t s)
-{
-  const int rc = build_tiled_impl(A, s, A.tiledx, true);
-  if (rc != FS_OK || (A.tiledx && !A.tiledx->built)) {
-    free_tiledx(A);
-    (void)hipGetLastError();
-  }
-  return FS_OK;
-}
-
-static int build_tiled_impl(DeviceCsr &A, hipStream_t s, TiledCsr *&slot, bool ldsx)
-{
-  const Options &o = options();
-  const int mode = ldsx ? o.ldsx : o.tiling;   // 0 never, 1 when the estimates do not rule it out, 2 always
-  if (mode == 0 || A.nrow == 0 || A.nnz == 0) return FS_OK;
-  int dev = 0, ncu = 256;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-  const int slots = (ncu > 8 ? ncu : 256) / 8 * 8;  // one workgroup per CU, a multiple of the 8 XCDs
-  const int rows_max = ldsx ? kLdsxRows : kTiledRowsMax;
-
-  // ---- cheap rejections first (auto mode) ----------------------------------------------------------
-  const int64_t x_bytes = (int64_t)A.ncol * 8;
-  if (mode == 1) {
-    // pays when x does not fit the 32 KiB L1 of a CU many times over ...
-    // (measured, config-2 rows and non-zeros: x of 0.5-2 MB 0.75-0.82 ms tiled vs 0.92 ms streaming -- narrow
-    // bands are L1 resident; x of 4-80 MB 0.70-1.06 ms vs 1.07-2.99 ms; x of 64 KB 1.3 ms vs 0.8 ms)
-    if (x_bytes <= (256 << 10) || A.nnz < (4 << 20)) return FS_OK;
-  }
-
-  // ---- virtual rows ------------------------------------------------------------------------------------
-  int max_len = 0;
-  if (int rc = max_row_len(A, s, &max_len)) return rc;
-  int split = o.tile_split > 0 ? o.tile_split : 256;
-  const bool virt = !ldsx && max_len > split;   // the LDS-staged kernel balances by chunks of work items instead
-  TiledCsr *T = new TiledCsr();
-  slot = T;
-  T->ldsx = ldsx;
-  T->slots = slots; T->lcol_bits = kTiledColBits; T->split = virt ? split : 0;
-  Scratch<int> vrow_ptr_own;
-  const int *vrow_ptr = A.row_ptr;
-  int nvrow = A.nrow;
-  if (virt) {
-    if (int rc = make_virtual_rows(A, split, s, vrow_ptr_own, &nvrow, &T->vfirst, &T->yv)) return rc;
-    vrow_ptr = vrow_ptr_own.p;
-  }
-  T->nvrow = nvrow;
-
-  // ---- panels: at most R virtual rows; with cut rows, panels of EQUAL non-zero count (0.8x what R average
-  // rows hold, so that nearly every panel is bounded by non-zeros, not by rows): the band sweep stays in step
-  // only if all workgroups of a generation carry the same work -------------------------------------------
-  int R = o.tile_rows;
-  if (R <= 0) {
-    const int64_t g = ((int64_t)nvrow + (int64_t)slots * rows_max - 1) / ((int64_t)slots * rows_max);
-    R = (int)(((int64_t)nvrow + slots * g - 1) / (slots * g));
-    if (R < 256) R = nvrow < 256 ? nvrow : 256;
-    // few rows: full-height panels (dense tiles), cut into chunks below so that every CU still has work
-    // (as equal as the row count allows: a remainder panel of a few hundred rows still sweeps every band -- 1 M rows under a limit
-    // of 14 272 rows left one of 960 rows whose single chunk of 4 883 nearly empty phases took as long as everything else
-    // together: config 3 transposed 0.75 -> 1.10 ms, profiles/r03_c3_kernel_variants_and_panel_cliff.jsonl)
-    if (ldsx && (int64_t)nvrow < (int64_t)slots * rows_max / 2) {
-      const int np = (int)(((int64_t)nvrow + rows_max - 1) / rows_max);
-      R = (int)(((int64_t)nvrow + np - 1) / (np > 0 ? np : 1));
-    }
-  }
-  if (R > rows_max) R = rows_max;
-  std::vector<int> panel_row;
-  if (!virt) {
-    for (int r = 0; r < nvrow; r += R) panel_row.push_back(r);
-  } else {
-    std::vector<int> vp((size_t)nvrow + 1);
-    FS_HIP(hipMemcpyAsync(vp.data(), vrow_ptr, sizeof(int) * vp.size(), hipMemcpyDeviceToHost, s));
-    FS_HIP(hipStreamSynchronize(s));
-    const int64_t cap = (int64_t)(0.8 * (double)A.nnz * R / nvrow) + split;
-    for (int r = 0; r < nvrow;) {
-      panel_row.push_back(r);
-      int e = (r + R < nvrow) ? r + R : nvrow;
-      if ((int64_t)vp[e] - vp[r] > cap) {  // largest e with nnz(r..e) <= cap, at least one row
-        e = (int)(std::upper_bound(vp.begin() + r + 1, vp.begin() + e + 1, (int)(vp[r] + cap)) - vp.begin()) - 1;
-        if (e <= r) e = r + 1;
-      }
-      r = e;
-    }
-  }
-  const int P = (int)panel_row.size();
-  panel_row.push_back(nvrow);
-
-  // ---- band width: tiles of about 0.9 work items on average, at most 2 MiB of x (L2-resident bands) or one
-  // LDS slice (LDS-staged kernel) -----------------------------------------------------------------------
-  const int w_max = ldsx ? kLdsxCols : (1 << kTiledColBits);
-  int W = o.tile_cols;
-  if (W <= 0) {
-    // (LDS-staged: 0.95 -- a slice costs its 16 KiB whatever the tile holds; config 3 transposed 0.777 -> 0.752 ms with
-    // 2048-column slices instead of the 1904 that 0.85 gave, 1800 / 1600: 0.80 / 0.86)
-    double w = (ldsx ? 0.95 : 0.9) * kTiledItem * (double)A.ncol * P / (double)A.nnz;
-    if (w < (ldsx ? 256 : 4096)) w = ldsx ? 256 : 4096;
-    if (w > w_max) w = w_max;
-    W = (int)w;
-  }
-  if (W > w_max) W = w_max;
-  if (W > A.ncol) W = A.ncol;
-  if (ldsx && (W & 1) && W < w_max) ++W;   // slices are loaded two columns per thread
-  const int J = (A.ncol + W - 1) / W;
-  const int64_t ntiles = (int64_t)P * J;
-  if (mode == 1 && ldsx) {
-    // every tile costs one barrier phase and one slice of x from L2: worth it only when the tiles are reasonably
-    // full (config 3, 10 M x 1 M x 64 per row: 1 700 entries per tile; config 2: 43).  Beyond that the choice is
-    // measured (choose_copy).  With the DMA kernel the crossover against the L2-tiled kernel lies near 500 entries per
-    // tile (10 M rows x 16: 786 K columns, 543 per tile: 0.64 against 0.71 ms; 1 M columns, 407: 0.79 against 0.74)
-    // Structured matrices (banded, block-diagonal: x close to the diagonal) fill few of a panel's tiles, and those densely:
-    // count the bands a sample of panels really touches before giving up on the average over ALL tiles
-    if ((double)A.nnz / ntiles < 450.0) {
-      constexpr int kSample = 64;
-      const int words = (J + 31) / 32;
-      if (words > kPanelBandWords || P < 1) return FS_OK;
-      const int ns = P < kSample ? P : kSample, stride = P / ns;
-      Scratch<int> prow, cnt;
-      FS_HIP(prow.alloc(panel_row.size()));
-      FS_HIP(cnt.alloc(2 * (size_t)ns));
-      FS_HIP(hipMemcpyAsync(prow.p, panel_row.data(), sizeof(int) * panel_row.size(), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(panel_bands_kernel, dim3(ns), dim3(256), 0, s, stride, W, words, prow.p, vrow_ptr, A.cols, cnt.p);
-      FS_HIP(hipGetLastError());
-      std::vector<int> hc(2 * (size_t)ns);
-      FS_HIP(hipMemcpyAsync(hc.data(), cnt.p, sizeof(int) * hc.size(), hipMemcpyDeviceToHost, s));
-      FS_HIP(hipStreamSynchronize(s));
-      double tiles = 0, entries = 0;
-      for (int i = 0; i < ns; ++i) { tiles += hc[2 * i]; entries += hc[2 * i + 1]; }
-      if (tiles < 1 || entries / tiles < 450.0) return FS_OK;
-    }
-  }
-  if (mode == 1 && !ldsx) {
-    // tiles must not be hopelessly thin, and re-reading x once per generation of resident workgroups must
-    // cost less than the L2 misses it saves.  Measured: tiled ~150 G entries/s; one generation's sweep of x
-    // costs ~x_bytes / 2.7 TB/s (the XCDs sweep in step, so a band leaves HBM once and the other seven L2s are
-    // filled from the Infinity Cache: 10 M rows x 16, x of 80 / 160 / 320 / 800 MB: 1.06 / 1.22 / 1.52 / 1.96 ms);
-    // streaming kernel ~172 G entries/s while x stays L2 resident, ~53 G entries/s once every gather misses.
-    if ((double)A.nnz / ntiles < 256.0) return FS_OK;
-    const double gens = (double)((P + slots - 1) / slots);
-    const double t_tiled = (double)A.nnz / 150e9 + gens * (double)x_bytes / 2.7e12;
-    const double t_stream = (double)A.nnz / (x_bytes <= (3 << 20) ? 172e9 : 53e9);
-    if (t_tiled > 0.95 * t_stream) return FS_OK;
-  }
-  if (ntiles >= (1ll << 31)) return FS_OK;
-  T->R = R; T->W = W; T->P = P; T->J = J;
-  T->entries_per_tile = (float)((double)A.nnz / (double)ntiles);
-  FS_HIP(traced_malloc(&T->panel_row, sizeof(int) * panel_row.size()));
-  FS_HIP(hipMemcpyAsync(T->panel_row, panel_row.data(), sizeof(int) * panel_row.size(), hipMemcpyHostToDevice, s));
-
-  // ---- sort the entries by (panel, band), pack them, cut the work items -----------------------------------
-  const size_t n = (size_t)A.nnz;
-  Scratch<int> vrows, tile_ptr;
-  Scratch<unsigned> keys, skeys, idx_in, idx_out;
-  Scratch<char> tmp;
-  size_t tmp_bytes = 0;
-  FS_HIP(vrows.alloc(n));
-  FS_HIP(keys.alloc(n));
-  FS_HIP(skeys.alloc(n));
-  FS_HIP(idx_in.alloc(n));
-  FS_HIP(idx_out.alloc(n));
-  FS_HIP(tile_ptr.alloc((size_t)ntiles + 1));
-  FS_HIP(traced_malloc(&T->pk, sizeof(unsigned) * (n + 8)));          // + slack: the LDS-staged kernel loads entries in pairs
-  if (A.vals) FS_HIP(traced_malloc(&T->vals, sizeof(double) * (n + 8)));
-  hipLaunchKernelGGL(tile_key_kernel, dim3(grid_for(A.nnz)), dim3(256), 0, s, nvrow, A.nnz, P, W, J, vrow_ptr, T->panel_row,
-                     A.cols, vrows.p, keys.p);
-  hipLaunchKernelGGL(iota_kernel, dim3(grid_for(A.nnz)), dim3(256), 0, s, A.nnz, idx_in.p);
-  FS_HIP(hipGetLastError());
-  int bits = 1;
-  while (bits < 32 && (1ll << bits) < ntiles) ++bits;
-  // ping-pong sort between the two key / index buffers we already hold (rocprim's plain form would allocate a third
-  // pair as temporary storage: 4.9 GB at config 3's size, and hipMalloc of such a block was caught taking 4 s)
-  rocprim::double_buffer<unsigned> dk(keys.p, skeys.p), dv(idx_in.p, idx_out.p);
-  FS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, dk, dv, n, 0, bits, s));
-  FS_HIP(tmp.alloc(tmp_bytes));
-  FS_HIP(rocprim::radix_sort_pairs((void *)tmp.p, tmp_bytes, dk, dv, n, 0, bits, s));
-  const unsigned *sorted_keys = dk.current(), *perm = dv.current();
-  hipLaunchKernelGGL(tile_pack_kernel, dim3(grid_for(A.nnz)), dim3(256), 0, s, A.nnz, W, J, T->lcol_bits, sorted_keys, perm,
-                     vrows.p, T->panel_row, A.cols, A.vals, T->pk, T->vals);
-  hipLaunchKernelGGL(tile_ptr_kernel, dim3(grid_for(ntiles + 1)), dim3(256), 0, s, ntiles, A.nnz, sorted_keys, tile_ptr.p);
-  FS_HIP(hipGetLastError());
-  // work items are cut on the host from the tile pointers (P*J ints)
-  std::vector<int> tp((size_t)ntiles + 1);
-  FS_HIP(hipMemcpyAsync(tp.data(), tile_ptr.p, sizeof(int) * tp.size(), hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  std::vector<int4> items;
-  std::vector<int> item_ptr((size_t)P + 1);
-  items.reserve((size_t)(A.nnz / kTiledItem + ntiles / 4 + 16));
-  for (int p = 0; p < P; ++p) {
-    item_ptr[p] = (int)items.size();
-    for (int j = 0; j < J; ++j) {
-      // 64-bit offsets: with nnz within 2 047 of INT_MAX `off += cap` wrapped around and this loop never ended
-      // (caught by test_pattern_matrix_at_the_int32_limit: 270 GB of work items on the host)
-      const int64_t a = tp[(size_t)p * J + j], b = tp[(size_t)p * J + j + 1];
-      for (int64_t off = a; off < b; off += kTiledItem) {
-        int4 it;
-        it.x = (int)off; it.y = (int)((b - off < kTiledItem) ? b - off : kTiledItem); it.z = j; it.w = 0;
-        items.push_back(it);
-      }
-    }
-  }
-  item_ptr[P] = (int)items.size();
-  T->nitems = (int)items.size();
-  FS_HIP(traced_malloc(&T->items, sizeof(int4) * (items.size() ? items.size() : 1)));
-  FS_HIP(traced_malloc(&T->item_ptr, sizeof(int) * item_ptr.size()));
-  if (!items.empty()) FS_HIP(hipMemcpy(T->items, items.data(), sizeof(int4) * items.size(), hipMemcpyHostToDevice));
-  FS_HIP(hipMemcpy(T->item_ptr, item_ptr.data(), sizeof(int) * item_ptr.size(), hipMemcpyHostToDevice));
-  if (ldsx && T->nitems > 0) {
-    static const bool arrange = [] { const char *v = getenv("FS_LDSX_ARRANGE"); return !(v && *v == '0'); }();
-    static const bool profile = [] { const char *v = getenv("FS_LDSX_REORDER_PROFILE"); return v && *v == '1'; }();
-    Scratch<int> bad;
-    Scratch<unsigned long long> clk;
-    FS_HIP(bad.alloc(1));
-    FS_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
-    if (profile) { FS_HIP(clk.alloc(8)); FS_HIP(hipMemsetAsync(clk, 0, 8 * sizeof(unsigned long long), s)); }
-    if (arrange)
-      hipLaunchKernelGGL(ldsx_reorder_kernel<true>, dim3(T->nitems), dim3(kReorderThreads), 0, s, T->items, T->lcol_bits, T->pk, T->vals, bad.p, profile ? clk.p : nullptr);
-    else
-      hipLaunchKernelGGL(ldsx_reorder_kernel<false>, dim3(T->nitems), dim3(kReorderThreads), 0, s, T->items, T->lcol_bits, T->pk, T->vals, bad.p, profile ? clk.p : nullptr);
-    FS_HIP(hipGetLastError());
-    if (profile) {
-      unsigned long long h[8] = {};
-      FS_HIP(hipMemcpyAsync(h, clk, sizeof h, hipMemcpyDeviceToHost, s));
-      FS_HIP(hipStreamSynchronize(s));
-      fprintf(stderr, "[fastsparse] ldsx_reorder_kernel, %d items, mean clocks per item: load+count %.0f, lists %.0f, rounds %.0f, repair rows+leaders %.0f, "
-              "per class %.0f, leftovers %.0f, copy out %.0f\n", T->nitems, (double)h[0] / T->nitems, (double)h[1] / T->nitems, (double)h[2] / T->nitems,
-              (double)h[3] / T->nitems, (double)h[4] / T->nitems, (double)h[5] / T->nitems, (double)h[6] / T->nitems);
-    }
-    int hbad = 0;
-    FS_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    FS_HIP(hipStreamSynchronize(s));
-    T->orderable = hbad == 0;                       // every row of every item with one wave: fixed-order sums possible
-    if (trace_build() && hbad) fprintf(stderr, "[fastsparse] LDS-staged copy: %d of %d work items hold a row that does not fit one wave -- no fixed-order sums on this copy\n", hbad, T->nitems);
-  }
-  if (ldsx) {
-    // chunks: exactly `total` of them (a whole number of generations of resident workgroups: 264 equal chunks on 256
-    // CUs take as long as 512) with entry counts as equal as the panels allow; a panel gets its share, at least one,
-    // cut at item boundaries.  Measured on config 3 transposed (66 panels): 1 / 2 / 4 / 8 chunks per CU 3.7 / 3.7 /
-    // 2.3 / 1.9 ms with rounded shares.
-    // (a chunk costs its PHASES: a work item takes about the same time whatever it holds, so panels are given chunks, and
-    // chunks are cut, by numbers of work items)
-    const int64_t total = (P >= slots) ? P : 8 * (int64_t)slots;
-    std::vector<int64_t> nnz_p((size_t)P, 0);
-    std::vector<int> k_p((size_t)P, 1);
-    std::vector<std::pair<double, int>> frac;
-    int64_t given = 0;
-    for (int p = 0; p < P; ++p) {
-      nnz_p[p] = item_ptr[p + 1] - item_ptr[p];
-      const double share = (double)nnz_p[p] * (double)total / (double)(items.empty() ? 1 : items.size());
-      const int cap = item_ptr[p + 1] - item_ptr[p] > 0 ? item_ptr[p + 1] - item_ptr[p] : 1;
-      int k = (int)share;
-      if (k < 1) k = 1;
-      if (k > cap) k = cap;
-      k_p[p] = k;
-      given += k;
-      if (k < cap) frac.push_back(std::make_pair(share - (double)(int)share, p));
-    }
-    std::sort(frac.begin(), frac.end(), [](const std::pair<double, int> &a, const std::pair<double, int> &b) {
-      return a.first > b.first || (a.first == b.first && a.second < b.second);
-    });
-    for (size_t f = 0; f < frac.size() && given < total; ++f, ++given) ++k_p[frac[f].second];
-    // chunk = (panel | shared flag, first item, one past the last item)
-    struct Chunk { int panel, first, last, ordinal; };
-    std::vector<Chunk> chunks;
-    for (int p = 0; p < P; ++p) {
-      const int i0 = item_ptr[p], i1 = item_ptr[p + 1], k = k_p[p];
-      const int flag = k > 1 ? (int)0x80000000u : 0;
-      if (k > 1) T->shared = true;
-      int i = i0;
-      int64_t done = 0;
-      for (int c = 0; c < k; ++c) {
-        const int first = i;
-        const int64_t goal = nnz_p[p] * (c + 1) / k;
-        while (i < i1 && (done < goal || c == k - 1)) { ++i; ++done; }
-        chunks.push_back(Chunk{p | flag, first, i, c});
-      }
-    }
-    // Launch order.  Workgroups that run together should sweep the SAME column bands, so that a band's slice of x
-    // comes out of the XCD's L2 for all but the first of them: with several chunks per panel (few, long rows: config
-    // 3 transposed, 66 panels x 31 chunks) the c-th chunks of all panels -- the same stretch of bands -- are launched
-    // next to each other instead of panel by panel.  Blocks b and b + 8 share an XCD, so every XCD gets a share of
-    // each stretch.  (Panel-major order read every slice from the Infinity Cache 66 times: 5.3 GB of slices against
-    // 2.6 GB of entries, 1.84 ms; this order 1.06 ms.)
-    // (second refinement: blocks b, b + 8, b + 16, ... land on the same XCD, so within a group of eight stretches the
-    // order is panel-major with the stretch as the fastest index: an XCD then sees ONE stretch of bands for all panels
-    // and is the only XCD that fetches its slices.  FS_LDSX_ORDER=1 keeps the plain stretch-major order.)
-    if (T->shared) {
-      static const bool plain = [] { const char *v = getenv("FS_LDSX_ORDER"); return v && *v == '1'; }();
-      if (plain)
-        std::stable_sort(chunks.begin(), chunks.end(), [](const Chunk &a, const Chunk &b) { return a.ordinal < b.ordinal; });
-      else
-        std::stable_sort(chunks.begin(), chunks.end(), [](const Chunk &a, const Chunk &b) {
-          const int ga = a.ordinal >> 3, gb = b.ordinal >> 3;
-          if (ga != gb) return ga < gb;
-          const int pa = a.panel & 0x7fffffff, pb = b.panel & 0x7fffffff;
-          if (pa != pb) return pa < pb;
-          return (a.ordinal & 7) < (b.ordinal & 7);
-        });
-    }
-    std::vector<int> chunk_panel, chunk_item, chunk_ord;
-    for (const Chunk &c : chunks) {
-      chunk_panel.push_back(c.panel);
-      chunk_item.push_back(c.first);
-      chunk_item.push_back(c.last);
-      chunk_ord.push_back(c.ordinal);
-    }
-    T->nchunks = (int)chunk_panel.size();
-    FS_HIP(traced_malloc(&T->chunk_panel, sizeof(int) * (chunk_panel.size() ? chunk_panel.size() : 1)));
-    FS_HIP(traced_malloc(&T->chunk_item, sizeof(int) * (chunk_item.size() ? chunk_item.size() : 2)));
-    FS_HIP(traced_malloc(&T->chunk_ord, sizeof(int) * (chunk_ord.size() ? chunk_ord.size() : 1)));
-    {   // ticket[-1]: chunks that gave up waiting for their turn (ldsx_store_slice), ever; ticket[0 .. P): whose turn it is
-      int *base = nullptr;
-      FS_HIP(traced_malloc(&base, sizeof(int) * ((size_t)(P > 0 ? P : 1) + 1)));
-      FS_HIP(hipMemset(base, 0, sizeof(int)));
-      T->ticket = base + 1;
-    }
-    if (!chunk_panel.empty()) {
-      FS_HIP(hipMemcpy(T->chunk_panel, chunk_panel.data(), sizeof(int) * chunk_panel.size(), hipMemcpyHostToDevice));
-      FS_HIP(hipMemcpy(T->chunk_item, chunk_item.data(), sizeof(int) * chunk_item.size(), hipMemcpyHostToDevice));
-      FS_HIP(hipMemcpy(T->chunk_ord, chunk_ord.data(), sizeof(int) * chunk_ord.size(), hipMemcpyHostToDevice));
-    }
-    if (T->shared && !T->yv) FS_HIP(traced_malloc(&T->yv, sizeof(double) * (size_t)A.nrow));
-  }
-  T->built = true;
-  return FS_OK;
-}
-
-// ---- two-pass copy ------------------------------------------------------------------------------------
-// key of entry e = band(col) * P + panel(virtual row): a stable sort by key starting from CSR order leaves every
-// (band, panel) run in CSR storage order
-__global__ void bin_key_kernel(int nvrow, int64_t nnz, int P, int bcols, const int *__restrict__ vrow_ptr,
-                               const int *__restrict__ panel_row, const int *__restrict__ cols,
-                               int *__restrict__ vrows, unsigned *__restrict__ keys)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nnz) return;
-  const int v = last_le(vrow_ptr, nvrow, i);
-  vrows[i] = v;
-  keys[i] = (unsigned)(cols[i] / bcols) * (unsigned)P + (unsigned)last_le(panel_row, P, v);
-}
-
-// group counts of the padded runs in pass-1 order (g1[band*P + panel]) and pass-2 order (g2[panel*B + band]);
-// slot nruns of both is the zero that turns the exclusive scans into B*P + 1 offsets
-__global__ void bin_groups_kernel(int B, int P, int ge, const int *__restrict__ run_ptr, unsigned *__restrict__ g1,
-                                  unsigned *__restrict__ g2, const unsigned *__restrict__ xs = nullptr)
-{
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t nruns = (int64_t)B * P;
-  if (k > nruns) return;
-  if (k == nruns) { g1[k] = 0; g2[k] = 0; return; }
-  const int b = (int)(k / P), p = (int)(k % P);
-  const unsigned dum = xs ? xs[run_ptr[k + 1]] - xs[run_ptr[k]] : 0u;                   // (one-byte row steps: the run's dummy entries)
-  const unsigned g = ((unsigned)(run_ptr[k + 1] - run_ptr[k]) + dum + (unsigned)ge - 1u) / (unsigned)ge;   // ge entries per group
-  g1[k] = g;
-  g2[(int64_t)p * B + b] = g;
-}
-
-__global__ void bin_scatter_kernel(int64_t nnz, int B, int P, int bcols, int ge, const unsigned *__restrict__ skeys,
-                                   const unsigned *__restrict__ perm, const int *__restrict__ vrows,
-                                   const int *__restrict__ panel_row, const int *__restrict__ cols,
-                                   const double *__restrict__ vals, const int *__restrict__ run_ptr,
-                                   const unsigned *__restrict__ start1, const unsigned *__restrict__ start2,
-                                   uint16_t *__restrict__ lcol, double *__restrict__ vals1, uint16_t *__restrict__ lrow)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nnz) return;
-  const unsigned key = skeys[i], src = perm[i];
-  const int b = (int)(key / (unsigned)P), p = (int)(key % (unsigned)P);
-  const int64_t rank = i - run_ptr[key];
-  const int64_t pos1 = (int64_t)start1[key] * ge + rank;
-  const int64_t pos2 = (int64_t)start2[(int64_t)p * B + b] * ge + rank;
-  lcol[pos1] = (uint16_t)(cols[src] - b * bcols);
-  if (vals) vals1[pos1] = vals[src];
-  lrow[pos2] = (uint16_t)(vrows[src] - panel_row[p]);
-}
-
-// ---- one-byte row steps (BinnedCsr::lrow8) ----
-// extra[i] = dummy entries in front of sorted entry i: its step from the entry before it in the same run, walked 255 rows at a time
-// (the first entry of a run starts from its own row: no step).  extra[nnz] = 0 closes the scan.
-__global__ void bin_gap_kernel(int64_t nnz, int P, const unsigned *__restrict__ skeys, const unsigned *__restrict__ perm,
-                               const int *__restrict__ vrows, const int *__restrict__ run_ptr, unsigned *__restrict__ extra)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i > nnz) return;
-  if (i == nnz) { extra[i] = 0; return; }
-  const unsigned key = skeys[i];
-  unsigned e = 0;
-  if (i > run_ptr[key]) {
-    const int gap = vrows[perm[i]] - vrows[perm[i - 1]];       // same panel: the difference of the local rows
-    if (gap > 255) e = (unsigned)(gap - 1) / 255u;
-  }
-  extra[i] = e;
-}
-
-// the scatter of both orders with the dummies in place: slot = rank in the run + the dummies in front of it
-__global__ void bin_scatter8_kernel(int64_t nnz, int B, int P, int bcols, int ge, const unsigned *__restrict__ skeys,
-                                    const unsigned *__restrict__ perm, const int *__restrict__ vrows,
-                                    const int *__restrict__ panel_row, const int *__restrict__ cols,
-                                    const double *__restrict__ vals, const int *__restrict__ run_ptr,
-                                    const unsigned *__restrict__ xs, const unsigned *__restrict__ start1,
-                                    const unsigned *__restrict__ start2, uint16_t *__restrict__ lcol, double *__restrict__ vals1,
-                                    uint8_t *__restrict__ lrow8, uint16_t *__restrict__ gbase)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nnz) return;
-  const unsigned key = skeys[i], src = perm[i];
-  const int b = (int)(key / (unsigned)P), p = (int)(key % (unsigned)P);
-  const int64_t first = run_ptr[key];
-  const unsigned dum = xs[i + 1] - xs[i];                       // dummies in front of this entry
-  const int64_t slot = (i - first) + (int64_t)(xs[i] - xs[first]) + dum;
-  const int64_t base1 = (int64_t)start1[key] * ge, base2 = (int64_t)start2[(int64_t)p * B + b] * ge;
-  const int row = vrows[src] - panel_row[p];
-  const int prev = i > first ? vrows[perm[i - 1]] - panel_row[p] : row;    // the row in front of the first slot of a run: its own
-  // the dummies: zero slot of the band (lcol = bcols and vals = 0 are the arrays' fill), step 255 each
-  for (unsigned m = 0; m < dum; ++m) {
-    const int64_t sl = slot - dum + m;
-    lrow8[base2 + sl] = 255;
-    if ((sl & (ge - 1)) == 0) gbase[(base2 + sl) / ge] = (uint16_t)(prev + 255 * (int)m);
-  }
-  const int before = prev + 255 * (int)dum;
-  lcol[base1 + slot] = (uint16_t)(cols[src] - b * bcols);
-  if (vals) vals1[base1 + slot] = vals[src];
-  lrow8[base2 + slot] = (uint8_t)(row - before);
-  if ((slot & (ge - 1)) == 0) gbase[(base2 + slot) / ge] = (uint16_t)before;
-}
-
-// gdst[g] = pass-2 group of pass-1 group g (one thread per run walks the run's groups)
-__global__ void bin_gdst_kernel(int B, int P, const unsigned *__restrict__ start1, const unsigned *__restrict__ start2,
-                                unsigned *__restrict__ gdst)
-{
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= (int64_t)B * P) return;
-  const int b = (int)(k / P), p = (int)(k % P);
-  const unsigned a = start1[k], n = start1[k + 1] - a, d = start2[(int64_t)p * B + b];
-  for (unsigned j = 0; j < n; ++j) gdst[a + j] = d + j;
-}
-
-// band_ptr[b] = first pass-1 group of band b (B + 1 values), bin_ptr[p] = first pass-2 group of panel p (P + 1)
-__global__ void bin_ptr_kernel(int B, int P, const unsigned *__restrict__ start1, const unsigned *__restrict__ start2,
-                               unsigned *__restrict__ band_ptr, unsigned *__restrict__ bin_ptr)
-{
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k <= B) band_ptr[k] = start1[k * P];
-  if (k <= P) bin_ptr[k] = start2[k * B];
-}
-
-static int build_binned_impl(DeviceCsr &A, hipStream_t s, BinnedCsr *&slot, int kw);
-
-// ---- the longest rows of a heavy-tailed matrix, outside the two-pass copy (LongRows, fs_common.h) -------------------------
-__global__ void long_candidates_kernel(int nrow, int minlen, const int *__restrict__ row_ptr, int *__restrict__ count, int cap,
-                                       int2 *__restrict__ out)
-{
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= nrow) return;
-  const int len = row_ptr[r + 1] - row_ptr[r];
-  if (len < minlen) return;
-  const int k = atomicAdd(count, 1);
-  if (k < cap) out[k] = make_int2(r, len);
-}
-
-__global__ void long_mark_kernel(int nlong, const int *__restrict__ rows, int *__restrict__ row_to_long)
-{
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nlong) row_to_long[rows[i]] = i;
-}
-
-__global__ void main_len_kernel(int nrow, const int *__restrict__ row_ptr, const int *__restrict__ row_to_long, int *__restrict__ len)
-{
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r > nrow) return;
-  len[r] = (r == nrow || row_to_long[r] >= 0) ? 0 : row_ptr[r + 1] - row_ptr[r];
-}
-
-// every entry goes either to its place in the CSR without the long rows or, as (key = band * nlong + long row, source index),
-// to the list the long rows' copy is sorted from
-__global__ void split_entries_kernel(int nrow, int64_t nnz, int nlong, int bcols, const int *__restrict__ row_ptr, const int *__restrict__ cols,
-                                     const double *__restrict__ vals, const int *__restrict__ row_to_long,
-                                     const int *__restrict__ main_rp, const int64_t *__restrict__ long_ptr,
-                                     int *__restrict__ main_cols, double *__restrict__ main_vals, unsigned *__restrict__ lkey,
-                                     unsigned *__restrict__ lsrc)
-{
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nnz) return;
-  const int r = last_le(row_ptr, nrow, i);
-  const int64_t k = i - row_ptr[r];
-  const int l = row_to_long[r];
-  if (l < 0) {
-    const int64_t d = (int64_t)main_rp[r] + k;
-    main_cols[d] = cols[i];
-    if (vals) main_vals[d] = vals[i];
-  } else {
-    const int64_t d = long_ptr[l] + k;
-    lkey[d] = (unsigned)(cols[i] / bcols) * (unsigned)nlong + (unsigned)l;
-    lsrc[d] = (unsigned)i;
-  }
-}
-
-// first sorted entry of every (band, owner) segment: seg = b * kLongOwners + w starts at the first key >= b * nlong + own_first[w]
-__global__ void long_seg_start_kernel(int B, int nlong, int64_t n, const int *__restrict__ own_first, const unsigned *__restrict__ skeys,
-                                      int64_t *__restrict__ start)
-{
-  const int64_t sg = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (sg > (int64_t)B * kLongOwners) return;
-  const int b = (int)(sg / kLongOwners), w = (int)(sg % kLongOwners);
-  const uint64_t key = (uint64_t)b * (uint64_t)nlong + (uint64_t)(b < B ? own_first[w] : 0);
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if ((uint64_t)skeys[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  start[sg] = lo;
-}
-
-// owner_of[l]: the owner of long row l; shift[seg]: padded position - sorted position of the segment's entries
-__global__ void long_scatter_kernel(int64_t n, int nlong, int bcols, const unsigned *__restrict__ skeys, const unsigned *__restrict__ ssrc,
-                                    const unsigned char *__restrict__ owner_of, const int64_t *__restrict__ shift,
-                                    const int *__restrict__ cols, const double *__restrict__ vals, uint16_t *__restrict__ lcol,
-                                    uint16_t *__restrict__ lrow, double *__restrict__ lvals)
-{
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const unsigned key = skeys[k], src = ssrc[k];
-  const unsigned b = key / (unsigned)nlong, l = key - b * (unsigned)nlong;
-  const int64_t d = k + shift[(int64_t)b * kLongOwners + owner_of[l]];
-  lcol[d] = (uint16_t)(cols[src] - (int)b * bcols);
-  lrow[d] = (uint16_t)l;
-  if (lvals) lvals[d] = vals[src];
-}
-
-// a segment with an odd number of entries ends in one padding entry: column = the zero slot, value 0, row = its neighbour's
-__global__ void long_pad_kernel(int64_t nseg, int bcols, const int64_t *__restrict__ start, const int64_t *__restrict__ shift,
-                                uint16_t *__restrict__ lcol, uint16_t *__restrict__ lrow, double *__restrict__ lvals)
-{
-  const int64_t sg = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (sg >= nseg) return;
-  const int64_t cnt = start[sg + 1] - start[sg];
-  if (cnt & 1) {
-    const int64_t d = start[sg] + shift[sg] + cnt;
-    lcol[d] = (uint16_t)bcols;
-    lrow[d] = lrow[d - 1];
-    if (lvals) lvals[d] = 0.0;
-  }
-}
-
-// Takes the longest rows out: on success *out holds their copy and main_* a CSR of the same shape without their entries
-// (temporaries of the caller's build).  *out stays NULL when the matrix has no such rows or they would not pay.
-static int split_long_rows(const DeviceCsr &A, hipStream_t s, LongRows **out, Scratch<int> &main_rp, Scratch<int> &main_cols,
-                           Scratch<double> &main_vals, int64_t *main_nnz)
-{
-  *out = nullptr;
-  const Options &o = options();
-  if (o.long_rows == 0 || o.binning == 0 || A.nrow == 0 || A.nnz < (4 << 20)) return FS_OK;
-  // geometry: the narrow band with 12032 accumulators covers more entries (a config-5 shard: 50 % against 40 %) at twice the
-  // number of band loads; measured on the config-5 shard: 2.24 ms against 2.29 (and 2.71 without this path), so it is the
-  // default; long_geometry / FS_LONG_GEOMETRY force either
-  const bool narrow = o.long_geometry != 1;
-  const int bcols = narrow ? kLongBandB : kLongBandA, cap_rows = narrow ? kLongRowsB : kLongRowsA;
-  const int B = (A.ncol + bcols - 1) / bcols;
-  // ANY row saves its intermediate products here; what limits the path is the number of accumulators, so the longest rows
-  // are taken.  Candidates: rows of at least 512 entries (shorter ones are too many to be worth collecting).
-  const int minlen = o.long_min_len > 0 ? o.long_min_len : 512;
-  constexpr int kCap = 1 << 18;
-  Scratch<int> cnt;
-  Scratch<int2> cand;
-  FS_HIP(cnt.alloc(1));
-  FS_HIP(cand.alloc(kCap));
-  FS_HIP(hipMemsetAsync(cnt, 0, sizeof(int), s));
-  hipLaunchKernelGGL(long_candidates_kernel, dim3(grid_for(A.nrow)), dim3(256), 0, s, A.nrow, minlen, A.row_ptr, cnt.p, kCap, cand.p);
-  FS_HIP(hipGetLastError());
-  int ncand = 0;
-  FS_HIP(hipMemcpyAsync(&ncand, cnt, sizeof(int), hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  if (ncand == 0 || ncand > kCap) return FS_OK;     // none, or so many that "long" means nothing here
-  std::vector<int2> h((size_t)ncand);
-  FS_HIP(hipMemcpy(h.data(), cand, sizeof(int2) * (size_t)ncand, hipMemcpyDeviceToHost));
-  std::sort(h.begin(), h.end(), [](const int2 &a, const int2 &b) { return a.y != b.y ? a.y > b.y : a.x < b.x; });
-  if ((int)h.size() > cap_rows) h.resize((size_t)cap_rows);          // the longest ones
-  const int nlong = (int)h.size();
-  // owners: the rows, longest first, are dealt out to the kLongOwners waves in a snake (0 .. 15, 15 .. 0, ...), so that every
-  // owner carries about the same number of entries; inside an owner's block the rows ascend.  Long row index = position in
-  // the concatenation of the blocks.
-  std::vector<int> own_first((size_t)kLongOwners + 1, 0);
-  {
-    std::vector<std::vector<int2>> blk((size_t)kLongOwners);
-    for (int i = 0; i < nlong; ++i) {
-      const int lap = i / kLongOwners, pos = i % kLongOwners;
-      blk[(size_t)((lap & 1) ? kLongOwners - 1 - pos : pos)].push_back(h[(size_t)i]);
-    }
-    h.clear();
-    for (int w = 0; w < kLongOwners; ++w) {
-      std::sort(blk[(size_t)w].begin(), blk[(size_t)w].end(), [](const int2 &a, const int2 &b) { return a.x < b.x; });
-      own_first[(size_t)w] = (int)h.size();
-      h.insert(h.end(), blk[(size_t)w].begin(), blk[(size_t)w].end());
-    }
-    own_first[(size_t)kLongOwners] = (int)h.size();
-  }
-  std::vector<unsigned char> owner_of((size_t)nlong);
-  for (int w = 0; w < kLongOwners; ++w)
-    for (int i = own_first[(size_t)w]; i < own_first[(size_t)w + 1]; ++i) owner_of[(size_t)i] = (unsigned char)w;
-  int64_t nl = 0;
-  std::vector<int> rows((size_t)nlong);
-  std::vector<int64_t> lptr((size_t)nlong + 1, 0);
-  for (int i = 0; i < nlong; ++i) { rows[(size_t)i] = h[(size_t)i].x; lptr[(size_t)i + 1] = lptr[(size_t)i] + h[(size_t)i].y; }
-  nl = lptr[(size_t)nlong];
-  // worth a second kernel (and a second sweep over x: 8 bytes per column against 18 saved per entry)?
-  if (o.long_rows == 1 && ((double)nl < 0.10 * (double)A.nnz || 18.0 * (double)nl < 16.0 * (double)A.ncol)) return FS_OK;
-  if ((uint64_t)B * (uint64_t)nlong >= (1ull << 32)) return FS_OK;
-
-  LongRows *L = new LongRows();
-  struct Guard { LongRows *&p; bool keep = false; ~Guard() { if (!keep) free_long_rows(p); } } guard{L};
-  L->nlong = nlong; L->B = B; L->bcols = bcols;
-  FS_HIP(traced_malloc(&L->row, sizeof(int) * (size_t)nlong));
-  FS_HIP(hipMemcpyAsync(L->row, rows.data(), sizeof(int) * (size_t)nlong, hipMemcpyHostToDevice, s));
-  FS_HIP(traced_malloc(&L->ylong, sizeof(double) * (size_t)nlong));
-
-  // ---- split the entries -------------------------------------------------------------------------------------------
-  Scratch<int> row_to_long, mlen;
-  Scratch<int64_t> long_ptr, start, shift;
-  Scratch<unsigned> lkey, lsrc, skey, ssrc;
-  Scratch<char> tmp;
-  FS_HIP(row_to_long.alloc((size_t)A.nrow));
-  FS_HIP(mlen.alloc((size_t)A.nrow + 1));
-  FS_HIP(main_rp.alloc((size_t)A.nrow + 1));
-  FS_HIP(long_ptr.alloc((size_t)nlong + 1));
-  FS_HIP(hipMemsetAsync(row_to_long, 0xff, sizeof(int) * (size_t)A.nrow, s));
-  FS_HIP(hipMemcpyAsync(long_ptr, lptr.data(), sizeof(int64_t) * lptr.size(), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(long_mark_kernel, dim3(grid_for(nlong)), dim3(256), 0, s, nlong, L->row, row_to_long.p);
-  hipLaunchKernelGGL(main_len_kernel, dim3(grid_for((int64_t)A.nrow + 1)), dim3(256), 0, s, A.nrow, A.row_ptr, row_to_long.p, mlen.p);
-  FS_HIP(hipGetLastError());
-  size_t tmp_bytes = 0;
-  FS_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, mlen.p, main_rp.p, 0, (size_t)A.nrow + 1, rocprim::plus<int>(), s));
-  FS_HIP(tmp.alloc(tmp_bytes));
-  FS_HIP(rocprim::exclusive_scan((void *)tmp.p, tmp_bytes, mlen.p, main_rp.p, 0, (size_t)A.nrow + 1, rocprim::plus<int>(), s));
-  const int64_t nm = A.nnz - nl;
-  *main_nnz = nm;
-  FS_HIP(main_cols.alloc((size_t)(nm > 0 ? nm : 1)));
-  if (A.vals) FS_HIP(main_vals.alloc((size_t)(nm > 0 ? nm : 1)));
-  FS_HIP(lkey.alloc((size_t)nl));
-  FS_HIP(lsrc.alloc((size_t)nl));
-  FS_HIP(skey.alloc((size_t)nl));
-  FS_HIP(ssrc.alloc((size_t)nl));
-  hipLaunchKernelGGL(split_entries_kernel, dim3(grid_for(A.nnz)), dim3(256), 0, s, A.nrow, A.nnz, nlong, bcols, A.row_ptr, A.cols, A.vals,
-                     row_to_long.p, main_rp.p, long_ptr.p, main_cols.p, A.vals ? main_vals.p : nullptr, lkey.p, lsrc.p);
-  FS_HIP(hipGetLastError());
-  int bits = 1;
-  while (bits < 32 && (1ull << bits) < (uint64_t)B * (uint64_t)nlong) ++bits;
-  rocprim::double_buffer<unsigned> dk(lkey.p, skey.p), dv(lsrc.p, ssrc.p);
-  Scratch<char> tmp2;
-  tmp_bytes = 0;
-  FS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, dk, dv, (size_t)nl, 0, bits, s));     // stable: CSR order inside a run
-  FS_HIP(tmp2.alloc(tmp_bytes));
-  FS_HIP(rocprim::radix_sort_pairs((void *)tmp2.p, tmp_bytes, dk, dv, (size_t)nl, 0, bits, s));
-  // the segments: (band, owner) in that order, each padded to an even count
-  const int64_t nseg = (int64_t)B * kLongOwners;
-  Scratch<int> d_own_first;
-  Scratch<unsigned char> d_owner_of;
-  FS_HIP(start.alloc((size_t)nseg + 1));
-  FS_HIP(shift.alloc((size_t)nseg + 1));
-  FS_HIP(d_own_first.alloc((size_t)kLongOwners + 1));
-  FS_HIP(d_owner_of.alloc((size_t)nlong));
-  FS_HIP(hipMemcpyAsync(d_own_first, own_first.data(), sizeof(int) * own_first.size(), hipMemcpyHostToDevice, s));
-  FS_HIP(hipMemcpyAsync(d_owner_of, owner_of.data(), owner_of.size(), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(long_seg_start_kernel, dim3(grid_for(nseg + 1)), dim3(256), 0, s, B, nlong, nl, d_own_first.p, dk.current(), start.p);
-  FS_HIP(hipGetLastError());
-  std::vector<int64_t> hs((size_t)nseg + 1), hp((size_t)B + 1, 0), hsh((size_t)nseg + 1, 0);
-  std::vector<unsigned> hseg((size_t)B * (kLongOwners + 1), 0u);
-  FS_HIP(hipMemcpyAsync(hs.data(), start, sizeof(int64_t) * hs.size(), hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  {
-    int64_t at = 0;                                 // padded position of the next segment
-    for (int b = 0; b < B; ++b) {
-      hp[(size_t)b] = at;
-      for (int w = 0; w < kLongOwners; ++w) {
-        const int64_t sg = (int64_t)b * kLongOwners + w;
-        const int64_t c = hs[(size_t)sg + 1] - hs[(size_t)sg];
-        hseg[(size_t)b * (kLongOwners + 1) + (size_t)w] = (unsigned)(at - hp[(size_t)b]);
-        hsh[(size_t)sg] = at - hs[(size_t)sg];
-        at += (c + 1) & ~(int64_t)1;
-      }
-      hseg[(size_t)b * (kLongOwners + 1) + (size_t)kLongOwners] = (unsigned)(at - hp[(size_t)b]);
-      if (at - hp[(size_t)b] >= (1ll << 32)) return FS_OK;   // (a band of 4 G entries: not this path)
-    }
-    hp[(size_t)B] = at;
-  }
-  L->n = hp[(size_t)B];
-  FS_HIP(traced_malloc(&L->band_ptr, sizeof(int64_t) * ((size_t)B + 1)));
-  FS_HIP(traced_malloc(&L->seg_ptr, sizeof(unsigned) * hseg.size()));
-  FS_HIP(hipMemcpyAsync(L->band_ptr, hp.data(), sizeof(int64_t) * hp.size(), hipMemcpyHostToDevice, s));
-  FS_HIP(hipMemcpyAsync(L->seg_ptr, hseg.data(), sizeof(unsigned) * hseg.size(), hipMemcpyHostToDevice, s));
-  FS_HIP(hipMemcpyAsync(shift, hsh.data(), sizeof(int64_t) * hsh.size(), hipMemcpyHostToDevice, s));
-  FS_HIP(traced_malloc(&L->lcol, sizeof(uint16_t) * (size_t)(L->n + 2)));
-  FS_HIP(traced_malloc(&L->lrow, sizeof(uint16_t) * (size_t)(L->n + 2)));
-  if (A.vals) FS_HIP(traced_malloc(&L->vals, sizeof(double) * (size_t)(L->n + 2)));
-  hipLaunchKernelGGL(long_scatter_kernel, dim3(grid_for(nl)), dim3(256), 0, s, nl, nlong, bcols, dk.current(), dv.current(), d_owner_of.p,
-                     shift.p, A.cols, A.vals, L->lcol, L->lrow, L->vals);
-  hipLaunchKernelGGL(long_pad_kernel, dim3(grid_for(nseg)), dim3(256), 0, s, nseg, bcols, start.p, shift.p, L->lcol, L->lrow, L->vals);
-  FS_HIP(hipGetLastError());
-  int dev = 0, ncu = 256;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-  const int64_t by_size = (L->n + kBinShareMin - 1) / kBinShareMin;
-  L->nwg = (int)(by_size < ncu ? by_size : ncu);
-  FS_HIP(traced_malloc(&L->ypart, sizeof(double) * (size_t)(L->nwg > 0 ? L->nwg : 1) * (size_t)nlong));
-  FS_HIP(hipStreamSynchronize(s));
-  guard.keep = true;
-  *out = L;
-  return FS_OK;
-}
-
-// Like the tiled copy, an optimisation: a failed build leaves the matrix on the other kernels.
-int build_binned(DeviceCsr &A, hipStream_t s)
-{
-  LongRows *lr = nullptr;
-  Scratch<int> main_rp, main_cols;
-  Scratch<double> main_vals;
-  int64_t main_nnz = 0;
-  if (split_long_rows(A, s, &lr, main_rp, main_cols, main_vals, &main_nnz) != FS_OK) {
-    free_long_rows(lr);
-    (void)hipGetLastError();
-  }
-  int rc;
-  if (lr) {
-    // the copy is built from the CSR WITHOUT the long rows (a temporary of this build: the copy keeps nothing of it)
-    DeviceCsr M;
-    M.nrow = A.nrow; M.ncol = A.ncol; M.nnz = main_nnz;
-    M.row_ptr = main_rp.p; M.cols = main_cols.p; M.vals = A.vals ? main_vals.p : nullptr; M.owns = false;
-    rc = build_binned_impl(M, s, A.binned, 1);
-    if (rc == FS_OK && A.binned && A.binned->built) { A.binned->lr = lr; lr = nullptr; }
-    M = DeviceCsr();
-  } else {
-    rc = build_binned_impl(A, s, A.binned, 1);
-  }
-  free_long_rows(lr);
-  if (rc != FS_OK || (A.binned && !A.binned->built)) {
-    free_binned(A);
-    (void)hipGetLastError();
-  }
-  return FS_OK;
-}
-
-// the copy that serves kw = 2 or 4 right-hand sides in one sweep (bsbm_A_mul_B2 / _B4, bcsr_A_mul_B2 / _B4, block CG):
-// the north_star's "LDS-tiled dense B panel" -- a band of kBinCols / kw rows of the row-major X lives in LDS
-int build_binned_k(DeviceCsr &A, int kw, hipStream_t s)
-{
-  if (kw != 2 && kw != 4) return FS_ERR_ARG;
-  BinnedCsr *&slot = kw == 2 ? A.binned2 : A.binned4;
-  (kw == 2 ? A.tried2 : A.tried4) = true;
-  const int rc = build_binned_impl(A, s, slot, kw);
-  if (rc != FS_OK || (slot && !slot->built)) {
-    free_binned_slot(slot);
-    (void)hipGetLastError();
-  }
-  return FS_OK;
-}
-
-static int build_binned_impl(DeviceCsr &A, hipStream_t s, BinnedCsr *&slot, int kw)
-{
-  const Options &o = options();
-  // short runs: the large bands and panels (fs_common.h kBinColsBig).  FS_BIN_BIG=0 / 1 never / always (A/B runs)
-  static const int big_env = [] { const char *v = getenv("FS_BIN_BIG"); return v && *v ? atoi(v) : -1; }();
-  const double per_run = (double)A.nnz / ((double)((A.ncol + kBinCols - 1) / kBinCols) * (double)((A.nrow + kBinRowsMax - 1) / kBinRowsMax));
-  const bool big = kw == 1 && o.bin_rows == 0 && (big_env >= 0 ? big_env != 0 : per_run < kBinBigRunEntries);
-  const int bcols = big ? kBinColsBig : kBinCols / kw;   // columns per band: kw * 8 bytes of X per column in LDS
-  const int rmax = big ? kBinRowsBig : kBinRowsMax / kw; // rows per panel: kw * 8 bytes of Y per row in LDS
-  const int ge = kBinGroup / kw;       // entries per group: a group of products is one 128-byte line
-  // ("reproducible": the copies stay in the race -- their pass 2 then adds in stream order, one wave per panel)
-  if (o.binning == 0 || A.nrow == 0 || A.nnz == 0) return FS_OK;
-  // (measured on 10 M x 10 M x 16: 0.75 ms against 1.06 ms tiled and 2.99 ms streaming; the two passes move
-  // 20.5 bytes per entry at stream speed whatever the size of x, so the copy pays once the matrix is large
-  // enough to fill the chip)
-  if (o.binning == 1 && A.nnz < (4 << 20)) return FS_OK;
-  int dev = 0, ncu = 256;
-  hipDeviceProp_t prop;
-  if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ncu = prop.multiProcessorCount;
-  const int slots = ncu > 0 ? ncu : 256;   // pass-2 workgroups resident together (one per CU)
-
-  // ---- virtual rows (long rows are cut exactly as for the tiled copy) ------------------------------------
-  int max_len = 0;
-  if (int rc = max_row_len(A, s, &max_len)) return rc;
-  const int split = o.tile_split > 0 ? o.tile_split : 256;
-  const bool virt = max_len > split;
-  BinnedCsr *N = new BinnedCsr();
-  slot = N;
-  N->kw = kw;
-  N->bcols = bcols;
-  N->split = virt ? split : 0;
-  Scratch<int> vrow_ptr_own;
-  const int *vrow_ptr = A.row_ptr;
-  int nvrow = A.nrow;
-  if (virt) {
-    if (int rc = make_virtual_rows(A, split, s, vrow_ptr_own, &nvrow, &N->vfirst, &N->yv, kw)) return rc;
-    vrow_ptr = vrow_ptr_own.p;
-  }
-  N->nvrow = nvrow;
-
-  // ---- panels of equal non-zero count, at most R rows: pass 2 runs one workgroup per panel and they all
-  // have to finish together; the count is a whole number of generations of resident workgroups -----------
-  int R = o.bin_rows > 0 ? o.bin_rows : rmax;
-  if (R > rmax) R = rmax;
-  std::vector<int> vp((size_t)nvrow + 1);
-  FS_HIP(hipMemcpyAsync(vp.data(), vrow_ptr, sizeof(int) * vp.size(), hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  static const double fill = [] { const char *v = getenv("FS_BIN_FILL"); return v && *v ? atof(v) / 100.0 : 0.8; }();
-  int64_t want = (int64_t)((double)nvrow / (fill * R)) + 1;
-  if (want > slots) want = (want + slots - 1) / slots * slots;
-  // fewer panels than CUs (a shard of 1-3 M rows: strong scaling cuts config 2 into such): pass 2 would leave most of the chip
-  // idle, so the panels are made smaller until every CU has one (FS_BIN_MIN_PANELS=0 keeps the tall panels: A/B runs)
-  static const int min_panels = [] { const char *v = getenv("FS_BIN_MIN_PANELS"); return v && *v ? atoi(v) : 1; }();
-  if (min_panels && want < slots && (int64_t)nvrow >= (int64_t)slots * 256 && kw == 1) want = slots;
-  std::vector<int> panel_row;
-  {
-    int r = 0;
-    for (int64_t k = 1; k <= want && r < nvrow; ++k) {
-      // the row boundary nearest to k/want of the non-zeros (so that rounding never adds up), then the row cap
-      const int64_t goal = (int64_t)((double)A.nnz * (double)k / (double)want);
-      int e = (int)(std::lower_bound(vp.begin() + r, vp.end(), goal,
-                                     [](int a, int64_t b) { return (int64_t)a < b; }) - vp.begin());
-      if (e > r && e <= nvrow && (int64_t)vp[e] - goal > goal - (int64_t)vp[e - 1] && e - 1 > r) --e;
-      if (k == want || e > nvrow) e = nvrow;
-      while (r < e) {
-        panel_row.push_back(r);
-        r = (e - r > R) ? r + R : e;
-      }
-    }
-    if (panel_row.empty()) panel_row.push_back(0);
-  }
-  const int P = (int)panel_row.size();
-  panel_row.push_back(nvrow);
-  const int B = (A.ncol + bcols - 1) / bcols;
-  const int64_t nruns = (int64_t)P * B;
-  if (nruns >= (1ll << 28)) return FS_OK;
-  // padding would dominate (a run is padded to whole groups: (ge - 1) / 2 entries on average)
-  if (o.binning == 1 && (double)A.nnz / (double)nruns < 1.5 * ge) return FS_OK;
-  N->P = P; N->B = B; N->slots = slots;
-  FS_HIP(traced_malloc(&N->panel_row, sizeof(int) * panel_row.size()));
-  FS_HIP(hipMemcpyAsync(N->panel_row, panel_row.data(), sizeof(int) * panel_row.size(), hipMemcpyHostToDevice, s));
-
-  // ---- sort the entries by (band, panel) and size the padded runs ------------------------------------------
-  const size_t n = (size_t)A.nnz;
-  Scratch<int> vrows, run_ptr;
-  Scratch<unsigned> keys, skeys, idx_in, idx_out, g1, g2, start1, start2;
-  Scratch<char> tmp, tmp2;
-  size_t tmp_bytes = 0;
-  FS_HIP(vrows.alloc(n));
-  FS_HIP(keys.alloc(n));
-  FS_HIP(skeys.alloc(n));
-  FS_HIP(idx_in.alloc(n));
-  FS_HIP(idx_out.alloc(n));
-  FS_HIP(run_ptr.alloc((size_t)nruns + 1));
-  FS_HIP(g1.alloc((size_t)nruns + 1));
-  FS_HIP(g2.alloc((size_t)nruns + 1));
-  FS_HIP(start1.alloc((size_t)nruns + 1));
-  FS_HIP(start2.alloc((size_t)nruns + 1));
-  FS_HIP(traced_malloc(&N->band_ptr, sizeof(unsigned) * ((size_t)B + 1)));
-  FS_HIP(traced_malloc(&N->bin_ptr, sizeof(unsigned) * ((size_t)P + 1)));
-  hipLaunchKernelGGL(bin_key_kernel, dim3(grid_for(A.nnz)), dim3(256), 0, s, nvrow, A.nnz, P, bcols, vrow_ptr, N->panel_row,
-                     A.cols, vrows.p, keys.p);
-  hipLaunchKernelGGL(iota_kernel, dim3(grid_for(A.nnz)), dim3(256), 0, s, A.nnz, idx_in.p);
-  FS_HIP(hipGetLastError());
-  int bits = 1;
-  while (bits < 32 && (1ll << bits) < nruns) ++bits;
-  rocprim::double_buffer<unsigned> dk(keys.p, skeys.p), dv(idx_in.p, idx_out.p);   // ping-pong: see build_tiled_impl
-  FS_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, dk, dv, n, 0, bits, s));
-  FS_HIP(tmp.alloc(tmp_bytes));
-  FS_HIP(rocprim::radix_sort_pairs((void *)tmp.p, tmp_bytes, dk, dv, n, 0, bits, s));
-  const unsigned *sorted_keys = dk.current(), *perm = dv.current();
-  hipLaunchKernelGGL(tile_ptr_kernel, dim3(grid_for(nruns + 1)), dim3(256), 0, s, nruns, A.nnz, sorted_keys, run_ptr.p);
-  // ---- one byte per row id where the cells are dense (BinnedCsr::lrow8): the dummies that walk steps above 255, counted first ----
-  Scratch<unsigned> extra, xs;
-  Scratch<char> tmp3;
-  bool rows8 = false;
-  int64_t dummies = 0;
-  if (kw == 1 && bcols == kBinCols && !(o.bin_flags & 64) && A.nnz > 0) {
-    FS_HIP(extra.alloc(n + 1));
-    FS_HIP(xs.alloc(n + 1));
-    hipLaunchKernelGGL(bin_gap_kernel, dim3(grid_for(A.nnz + 1)), dim3(256), 0, s, A.nnz, P, sorted_keys, perm, vrows.p, run_ptr.p, extra.p);
-    FS_HIP(hipGetLastError());
-    size_t b3 = 0;
-    FS_HIP(rocprim::exclusive_scan(nullptr, b3, extra.p, xs.p, 0u, n + 1, rocprim::plus<unsigned>(), s));
-    FS_HIP(tmp3.alloc(b3));
-    FS_HIP(rocprim::exclusive_scan((void *)tmp3.p, b3, extra.p, xs.p, 0u, n + 1, rocprim::plus<unsigned>(), s));
-    unsigned total = 0;
-    FS_HIP(hipMemcpyAsync(&total, xs.p + n, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    FS_HIP(hipStreamSynchronize(s));
-    dummies = total;
-    rows8 = (o.bin_flags & 128) || (double)total <= 0.01 * (double)A.nnz;
-  }
-  hipLaunchKernelGGL(bin_groups_kernel, dim3(grid_for(nruns + 1)), dim3(256), 0, s, B, P, ge, run_ptr.p, g1.p, g2.p,
-                     rows8 ? (const unsigned *)xs.p : (const unsigned *)nullptr);
-  FS_HIP(hipGetLastError());
-  tmp_bytes = 0;
-  FS_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, g1.p, start1.p, 0u, (size_t)nruns + 1, rocprim::plus<unsigned>(), s));
-  FS_HIP(tmp2.alloc(tmp_bytes));
-  FS_HIP(rocprim::exclusive_scan((void *)tmp2.p, tmp_bytes, g1.p, start1.p, 0u, (size_t)nruns + 1, rocprim::plus<unsigned>(), s));
-  FS_HIP(rocprim::exclusive_scan((void *)tmp2.p, tmp_bytes, g2.p, start2.p, 0u, (size_t)nruns + 1, rocprim::plus<unsigned>(), s));
-  hipLaunchKernelGGL(bin_ptr_kernel, dim3(grid_for((B > P ? B : P) + 1)), dim3(256), 0, s, B, P, start1.p, start2.p, N->band_ptr,
-                     N->bin_ptr);
-  FS_HIP(hipGetLastError());
-  unsigned total_groups = 0;
-  FS_HIP(hipMemcpyAsync(&total_groups, N->band_ptr + B, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  FS_HIP(hipStreamSynchronize(s));
-  const int64_t groups = total_groups;
-  // every padded run adds at most ge - 1 entries: n <= nnz + 15 * nruns < 2^31 + 2^32
-  if (groups >= (1ll << 28) * (int64_t)kw) return FS_OK;   // group indices are 32-bit, entry offsets 64-bit
-  if (groups >= (1ll << 32) - 1) return FS_OK;
-  N->n = groups * ge;
-  if (o.binning == 1 && kw == 1) {
-    // two streaming passes (measured 4.6-5.0 TB/s) against what the other kernels reach on this shape
-    const double x_bytes = (double)A.ncol * 8;
-    const double t_bin = ((double)N->n * (A.vals ? 28.5 : 20.5) + (double)(B + ncu) * bcols * 8 + (double)nvrow * 8) / 4.6e12;
-    const double t_stream = (double)A.nnz / (x_bytes <= (3 << 20) ? 172e9 : 53e9);
-    if (t_bin > 0.95 * t_stream) return FS_OK;   // hopeless; between the survivors choose_copy measures
-  }
-
-  // ---- lay out both orders ------------------------------------------------------------------------------------
-  const size_t np = (size_t)N->n;
-  FS_HIP(traced_malloc(&N->lcol, sizeof(uint16_t) * np));
-  if (rows8) {
-    FS_HIP(traced_malloc(&N->lrow8, np));
-    FS_HIP(traced_malloc(&N->gbase, sizeof(uint16_t) * (size_t)(groups ? groups : 1)));
-    N->dummies = dummies;
-  } else {
-    FS_HIP(traced_malloc(&N->lrow, sizeof(uint16_t) * np));
-  }
-  FS_HIP(traced_malloc(&N->gdst, sizeof(unsigned) * (size_t)groups));
-  FS_HIP(traced_malloc(&N->prod, sizeof(double) * np * (size_t)kw));
-  if (A.vals) {
-    FS_HIP(traced_malloc(&N->vals, sizeof(double) * np));
-    FS_HIP(hipMemsetAsync(N->vals, 0, sizeof(double) * np, s));
-  }
-  FS_HIP(hipMemsetD16Async((hipDeviceptr_t)N->lcol, (unsigned short)bcols, np, s));   // padding: the zero row behind the band
-  if (rows8) {
-    FS_HIP(hipMemsetAsync(N->lrow8, 0, np, s));
-    FS_HIP(hipMemsetAsync(N->gbase, 0, sizeof(uint16_t) * (size_t)(groups ? groups : 1), s));
-    hipLaunchKernelGGL(bin_scatter8_kernel, dim3(grid_for(A.nnz)), dim3(256), 0, s, A.nnz, B, P, bcols, ge, sorted_keys, perm, vrows.p,
-                       N->panel_row, A.cols, A.vals, run_ptr.p, xs.p, start1.p, start2.p, N->lcol, N->vals, N->lrow8, N->gbase);
-  } else {
-    FS_HIP(hipMemsetAsync(N->lrow, 0, sizeof(uint16_t) * np, s));
-    hipLaunchKernelGGL(bin_scatter_kernel, dim3(grid_for(A.nnz)), dim3(256), 0, s, A.nnz, B, P, bcols, ge, sorted_keys, perm, vrows.p,
-                       N->panel_row, A.cols, A.vals, run_ptr.p, start1.p, start2.p, N->lcol, N->vals, N->lrow);
-  }
-  hipLaunchKernelGGL(bin_gdst_kernel, dim3(grid_for(nruns)), dim3(256), 0, s, B, P, start1.p, start2.p, N->gdst);
-  FS_HIP(hipGetLastError());
-
-  // ---- pass-1 work: one persistent workgroup per CU, fewer when the shares would be tiny --------------------
-  {
-    const int64_t by_size = (N->n * kw + kBinShareMin - 1) / kBinShareMin;
-    N->nwg1 = (int)(by_size < ncu ? by_size : ncu);
-  }
-  FS_HIP(hipStreamSynchronize(s));
-  N->built = true;
-  return FS_OK;
-}
-
-// ---- which copy to keep ---------------------------------------------------------------------------------
-// The estimates in the builders only weed out hopeless candidates.  Between the survivors (and the chunk-streaming
-// kernel, which needs no copy) the choice is measured: every candidate runs the product on a zero vector -- same
-// addresses and traffic as any x -- and the fastest keeps its copy; the others are released.  (Callers who need
-// sums that are bit-identical from run to run set "reproducible": the LDS-staged copy leaves the race and the two-pass copy is
-// timed with its ordered pass 2.)
-template <typename F>
-static int time_product(F launch, hipStream_t s, hipEvent_t e0, hipEvent_t e1, float *median, int reps = 5)
-{
-  float t[5] = {1e30f, 1e30f, 1e30f, 1e30f, 1e30f};
-  for (int rep = -1; rep < reps; ++rep) {   // run -1 warms the instruction cache and the TLB
-    FS_HIP(hipEventRecord(e0, s));
-    if (int rc = launch()) return rc;
-    FS_HIP(hipEventRecord(e1, s));
-    FS_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    FS_HIP(hipEventElapsedTime(&ms, e0, e1));
-    if (rep >= 0) t[rep] = ms;
-  }
-  std::sort(t, t + reps);
-  *median = t[reps / 2];                   // the tiled kernel's fastest run is not typical of it; its median is
-  return FS_OK;
-}
-
-static int two_pass_clear_win(DeviceCsr &A, hipStream_t s, bool *win)
-{
-  *win = false;
-  const Options &o = options();
-  if (!(A.binned && A.binned->built) || o.binning != 1 || o.tiling != 1 || A.nnz < (32ll << 20) || 8.0 * (double)A.ncol <= (double)(4 << 20)) return FS_OK;
-  Scratch<double> x, y;
-  if (x.alloc((size_t)A.ncol) != hipSuccess || y.alloc((size_t)A.nrow) != hipSuccess) { (void)hipGetLastError(); return FS_OK; }
-  FS_HIP(hipMemsetAsync(x, 0, sizeof(double) * (size_t)A.ncol, s));
-  hipEvent_t e0, e1;
-  FS_HIP(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return FS_OK; }
-  float t = 1e30f;
-  const int rc = time_product([&] { return launch_spmv_binned(A, y, x, s); }, s, e0, e1, &t, 2);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (rc != FS_OK) return rc;
-  *win = (double)t <= (double)A.nnz / (A.vals ? kTiledBestEntriesPerMs : 200e6);
-  return FS_OK;
-}
-
-int choose_copy(DeviceCsr &A, hipStream_t s)
-{
-  BuildClock clock(s);
-  const Options &o = options();
-  const bool hb = A.binned && A.binned->built, ht = A.tiled && A.tiled->built, hx = A.tiledx && A.tiledx->built;
-  if (!hb && !ht && !hx) return FS_OK;
-  if (o.tiling == 2 || o.binning == 2 || o.ldsx == 2) {   // the caller chose: keep what was asked for, nothing else
-    if (o.binning != 2) free_binned(A);
-    if (o.ldsx != 2) free_tiledx(A);
-    if (o.tiling != 2) free_tiled(A);
-    return FS_OK;
-  }
-  Scratch<double> x, y;
-  if (x.alloc((size_t)A.ncol) != hipSuccess || y.alloc((size_t)A.nrow) != hipSuccess) {
-    (void)hipGetLastError();
-    return FS_OK;                                                       // no room to measure: keep the estimate's order
-  }
-  FS_HIP(hipMemsetAsync(x, 0, sizeof(double) * (size_t)A.ncol, s));
-  hipEvent_t e0, e1;
-  FS_HIP(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return FS_OK; }
-  float t_stream = 1e30f, t_tiled = 1e30f, t_bin = 1e30f, t_ldsx = 1e30f;
-  // (a lone LDS-staged copy with dense tiles -- build_schedule did not build its rivals -- is 8 to 15 times faster than the
-  // streaming kernel: one timed run of that one is enough to say so, five cost 25-50 ms of a 230 ms build on config 3)
-  const bool lone_ldsx = hx && !hb && !ht && A.tiledx->entries_per_tile >= kLdsxClearWin;
-  int rc = time_product([&] { return launch_spmv(A, y, x, s, true); }, s, e0, e1, &t_stream, (lone_ldsx || A.two_pass_clear_win) ? 1 : 5);
-  if (rc == FS_OK && ht) rc = time_product([&] { return launch_spmv_tiled(A, *A.tiled, y, x, s); }, s, e0, e1, &t_tiled);
-  if (rc == FS_OK && hx) rc = time_product([&] { return launch_spmv_tiled(A, *A.tiledx, y, x, s); }, s, e0, e1, &t_ldsx);
-  if (rc == FS_OK && hb) rc = time_product([&] { return launch_spmv_binned(A, y, x, s); }, s, e0, e1, &t_bin);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  if (rc != FS_OK) return rc;
-  A.build_ms[6] = clock.lap();
-  A.candidate_ms[0] = t_stream;
-  A.candidate_ms[1] = ht ? t_tiled : 0.f;
-  A.candidate_ms[2] = hx ? t_ldsx : 0.f;
-  A.candidate_ms[3] = hb ? t_bin : 0.f;
-  float best = t_stream;
-  if (t_tiled < best) best = t_tiled;
-  if (t_ldsx < best) best = t_ldsx;
-  if (t_bin < best) best = t_bin;
-  // Candidates within 5 % of the fastest count as equal (box-to-box and run-to-run differences are of that size) and a
-  // fixed priority decides between them -- two-pass, LDS-staged, L2-tiled, streaming -- so that the same matrix gets the
-  // same kernel (and the same summation order) on every run and for A as for A' unless one kernel really is faster.
-  const float tie = best * 1.05f;
-  const int keep = (hb && t_bin <= tie) ? 3 : (hx && t_ldsx <= tie) ? 2 : (ht && t_tiled <= tie) ? 1 : 0;
-  if (keep != 3) free_binned(A);
-  if (keep != 2) free_tiledx(A);
-  if (keep != 1) free_tiled(A);
-  A.build_ms[7] = clock.lap();
   return FS_OK;
 }
 

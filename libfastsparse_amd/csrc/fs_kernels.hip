@@ -16,7 +16,7 @@
 //                           strict_order), spmv_vector_kernel (lanes per row, A/B alternative), spmm_kernel / spmm_wide_kernel /
 //                           spmm_mfma_kernel (k right-hand sides, one lane per output column), cbcsr_kernel, and everything that
 //                           decides: spmv_choice, spmm_plan, products in parts, host-vector products
-//   (which copy a matrix keeps is the format builder's measured choice: fs_format.hip, choose_copy)
+//   (which copy a matrix keeps is the format builder's measured choice: fs_copies.hip, choose_copy)
 #include <stdlib.h>
 
 #include <algorithm>
@@ -781,7 +781,7 @@ int spmv_host_vectors(const DeviceCsr &A, HostPipe &H, double *y_host, const dou
     }
     if (T && T->ldsx && T->shared && T->nchunks >= 2 * want_chunks && A.ncol >= (1 << 20)) {
       // Few, long rows (config 3 transposed: x 80 MB, y 8 MB): several chunks per panel, launched stretch of bands by
-      // stretch of bands (fs_format.hip "Launch order"), so the chunks at the front of the order only read the front of x.
+      // stretch of bands (fs_plan.h, plan_ldsx_chunks: "Launch order"), so the chunks at the front of the order only read the front of x.
       // need[w] = columns the chunks 0 .. w read; x goes up in ranges and the chunks a range completes are launched behind it.
       TiledCsr &M = const_cast<TiledCsr &>(*T);
       if (!M.h_chunk_need) {

@@ -4,7 +4,7 @@
  * sparse.h:215, sort_bsdm dsparse.h:193), row-major order inside blocks (sort_bsbm_byrow sparse.h:238) and the
  * curve helpers of hilbert.h.  Host code: these only permute the entries of a matrix (results of every product are
  * unchanged up to rounding, test_sparse.c:275-280).  On the GPU the locality they were written for is provided by
- * the L2-tiled device copy (row panels x column bands, fs_format.hip); they are here so that callers of the
+ * the L2-tiled device copy (row panels x column bands, fs_copies.hip); they are here so that callers of the
  * reference find the same API, and each one drops the matrix's cached device copy because it changes the arrays.
  *
  * Implementation: one generic "order entries by a 64-bit key" routine (LSD radix sort of (key, position) pairs,

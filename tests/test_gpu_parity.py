@@ -2998,3 +2998,70 @@ def test_native_multi_gpu_k_column_products_and_block_cg(hip, ranks):
         capi.set_option("binning", 1)
         capi.set_option("bin_rows", 0)
         L.fs_dist_destroy(D)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["syn_u16_2048", "syn_long_800x5000", "syn_wide_300x40000"])
+def test_copy_geometry_matches_the_plan_model(hip, name):
+    """The geometry the device builders really laid out equals what tests/_plan_model.py -- the restatement of fs_plan.h that
+    tests/test_format_plans.py holds the C++ to on the CPU -- predicts from the CSR and the device's CU count, on three forced
+    paths: the L2-tiled copy with cut rows and small tiles, the LDS-staged copy, the two-pass copy."""
+    import ctypes as C
+    import torch
+    import _plan_model as M
+    from libfastsparse_amd import capi
+    c = next(k for k in CASES if k.name == name)
+    rp, cc, vv = O.coo_to_csr(c.nrow, c.rows, c.cols, c.vals)
+    nnz, ncu = int(rp[-1]), torch.cuda.get_device_properties(0).multi_processor_count
+    slots = M.tiled_slots(ncu)
+    L = capi.lib()
+    L.fs_debug_tiled_geometry.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.fs_debug_tiled_layout.argtypes = [C.c_void_p, C.c_int]
+    L.fs_debug_two_pass_layout.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_ulonglong)]
+
+    def build(**opts):
+        for k, v in opts.items():
+            capi.set_option(k, v)
+        try:
+            return capi.Matrix.from_csr(c.nrow, c.ncol, rp, cc, vv)
+        finally:
+            for k in opts:
+                capi.set_option(k, 1 if k in ("tiling", "ldsx", "binning") else 0)
+
+    def tiled(A, ldsx, tile_rows, tile_cols, split):
+        vp, cut = M.virtual_rows(rp, split) if not ldsx else ([int(v) for v in rp], False)
+        nvrow = len(vp) - 1
+        R = M.plan_tiled_rows(nvrow, slots, M.K_LDSX_ROWS if ldsx else M.K_TILED_ROWS_MAX, ldsx, tile_rows)
+        panel_row = M.plan_tiled_panels(nvrow, R, cut, vp, nnz, split)
+        P = len(panel_row) - 1
+        W, J = M.plan_band_width(c.ncol, nnz, P, ldsx, tile_cols)
+        tp = M.tile_pointers(vp, panel_row, cc, W, J)
+        items, item_ptr = M.cut_work_items(tp, P, J)
+        shared = bool(ldsx) and M.plan_ldsx_chunks(item_ptr, len(items), P, slots, os.environ.get("FS_LDSX_ORDER", "")[:1] == "1")["shared"] == [1]
+        g = (C.c_int * 6)()
+        assert L.fs_debug_tiled_geometry(A.h, g) == 0
+        print(name, "lds-staged" if ldsx else "tiled", "R W P J nitems", list(g)[:5], "predicted", [R, W, P, J, len(items)], "cut", cut, "shared", shared)
+        assert list(g)[:5] == [R, W, P, J, len(items)]
+        assert L.fs_debug_tiled_layout(A.h, 0) == (1 if cut else 0) | (2 if shared else 0)
+        return cut
+
+    A = build(tiling=2, tile_rows=64, tile_cols=128, tile_split=5)
+    assert A.kernel_name() == "tiled"
+    assert tiled(A, False, 64, 128, 5) == (np.diff(rp).max() > 5)
+    A.close()
+    A = build(ldsx=2)
+    assert A.kernel_name() == "lds-staged"
+    tiled(A, True, 0, 0, 256)
+    A.close()
+    A = build(binning=2, bin_flags=64)
+    assert A.kernel_name() == "two-pass"
+    g = M.plan_two_pass_geometry(c.nrow, c.ncol, nnz, 1, 0, int(os.environ.get("FS_BIN_BIG") or -1))
+    vp, cut = M.virtual_rows(rp, 256)
+    panel_row = M.plan_two_pass_panels(vp, len(vp) - 1, nnz, g["R"], ncu if ncu > 0 else 256, float(os.environ.get("FS_BIN_FILL") or 80) / 100.0,
+                                       int(os.environ.get("FS_BIN_MIN_PANELS") or 1), 1)
+    lay = (C.c_ulonglong * 8)()
+    assert L.fs_debug_two_pass_layout(A.h, 0, lay) == 0
+    print(name, "two-pass B P", int(lay[6]), int(lay[7]), "predicted", -(-c.ncol // g["bcols"]), len(panel_row) - 1, "cut", cut)
+    assert (int(lay[6]), int(lay[7])) == (-(-c.ncol // g["bcols"]), len(panel_row) - 1)
+    assert cut == (name == "syn_long_800x5000")
+    A.close()
