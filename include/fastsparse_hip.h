@@ -84,6 +84,8 @@ int  fs_set_device(int device);
  * "tile_split": rows longer than this are cut into virtual rows in the tiled copy (0 = 256).
  * "cg_fixed_order" (default 1; FS_CG_FIXED_ORDER): fs_cg / fs_cg2 / fs_dist_cg run their products with fixed-order sums, as under
  * "reproducible", so that a solve is bit-identical from run to run like the reference's loops (cg.h:25-187); 0 = the default kernels.
+ * "pcgn_kernel": fs_pcgn's per-iteration vector kernels, 0 = auto (see fs_pcgn), 1 = a lane per row, 2 = the 256-row panels staged
+ * through LDS with coalesced accesses; both give the same bits.
  * "dist_cg_scheme" (FS_DIST_CG_SCHEME): fs_dist_cg, 0 every device keeps whole vectors, 1 every device keeps its slice (see there). */
 int  fs_set_option(const char *name, int value);
 int  fs_get_option(const char *name);
@@ -303,6 +305,52 @@ enum { FS_MSCG_MAX_SHIFTS = 16 };
  * product's own error (FS_ERR_RELEASED under "strict_order" after fs_matrix_release_csr) is passed through. */
 int fs_mscg(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double *b, int m, const double *lambda,
             double tol, int max_iter, fs_pcg_info *info, fs_stream_t stream);
+
+/* ---- k right-hand sides per solve (no counterpart in the reference) ---- */
+enum { FS_PCGN_MAX_RHS = 32 };
+/* (A'A + lambda I) X = B for k right-hand sides on the same A (the latent dimensions of a sample, 8 to 32 of them): k INDEPENDENT
+ * fs_pcg recurrences that share only the products, which run over all k columns at once (fs_spmm; k = 1: fs_spmv).  This is not
+ * block CG: no shared Krylov space, no k x k solve, no breakdown when columns are dependent.  X, B: row-major F x k panels in HBM,
+ * F = ncol(A), the layout of fs_spmm and fs_cg2, 8-byte aligned (16-byte aligned panels of an even k are read and written 16 bytes
+ * at a time); one lambda and one prm (fs_pcg_params, as for fs_pcg: tol, max_iter, precond, warm_start -- X holds X0 --, diag) for
+ * all columns, one dinv, as the matrix is the same; info: k entries or NULL.  Synchronous like fs_pcg.
+ * Column j follows fs_pcg's arithmetic line by line with scalars of its own; every line is one IEEE double operation per element,
+ * `red_j` the two-stage sum of fs_cg over column j's F terms -- stage 1: 1024 x 256 threads, thread (b, t) adds rows b * 256 + t,
+ * + 262144, ... to +0.0 in increasing order, one multiply and one add per term, never fused, then the wave butterfly, then the four
+ * waves in order; stage 2: one workgroup over the 1024 partials:
+ *   dinv[i] = d[i] == 0 ? 1 : 1 / d[i], once per solve
+ *   cold start: X = 0, R = B;  warm start: T = A X, Q = A' T (one pair of k-column products), Q = Q + lambda X, R = B - Q
+ *   per column: bb_j = red_j(b b), rr_j = red_j(r r), stop_j = tol sqrt(bb_j), count_j = 0;
+ *               sqrt(rr_j) <= stop_j: column j is frozen from the start, converged_j = 1 (b_j = 0: x_j = 0, as in fs_pcg)
+ *   Z = R dinv, P = Z (every column, so that P is finite where it rides along);  live columns: rz_j = red_j(r z)
+ *   every column frozen: done, no product is enqueued
+ *   while fewer than max_iter iterations have run and a column is live:
+ *     T = A P, Q = A' T over all k columns;  live columns: q = q + lambda p, alpha_j = rz_j / red_j(q p),
+ *       x = x + alpha_j p, r = r - alpha_j q, rr_j = red_j(r r)
+ *       sqrt(rr_j) <= stop_j: column j freezes, converged_j = 1
+ *       else z = r dinv, rzn = red_j(r z), beta_j = rzn / rz_j, rz_j = rzn, ++count_j, p = z + beta_j p
+ *   info[j] = { count_j, converged_j, sqrt(rr_j), sqrt(bb_j) };  a column still live at the cap: converged 0, count = the cap
+ * Without a preconditioner z is r, r.z is r.r and no second sum runs, as in fs_pcg.  So column j is fs_pcg on B[:, j] wherever the
+ * k-column product has the single-vector product's bits: bit for bit under "strict_order", and for k = 1 in every mode.
+ * Freezing: once a column is frozen no kernel writes its column of X, R or P again; count_j and converged_j are final; its column
+ * of P stays as it is and keeps riding through the products (wasted work of a fixed shape: live columns are not compacted into
+ * a narrower product).  In a row-major panel a frozen column shares its cache lines with live ones, so freezing saves stores and
+ * arithmetic, not lines.  The vector kernels of an iteration come in two forms with the same bits (option "pcgn_kernel"): a lane per
+ * row (k <= 4), which stops loading a cache line's worth of neighbouring columns (16 j .. 16 j + 15) once ALL of them are frozen,
+ * and, for k > 4, the workgroup's 256-row panels staged through LDS with coalesced accesses, which load every line.  A column
+ * whose numbers go NaN runs to the cap and changes nothing in the other columns (the products and the sums are per column).
+ * The scalars live on the device (one thread per column in the one-workgroup step that finishes the sums) and the host learns of
+ * `done` -- no column live -- one iteration behind, as in fs_cg.  Per iteration the vector kernels move 12 k F doubles, 14 k F
+ * with a preconditioner (the formula of fs_pcg; dinv itself is read once per row, not per column).  Products add in a fixed order
+ * unless option "cg_fixed_order" is 0.  Work space per solve: 3 k F + k N doubles, F more with a preconditioner, 2048 k for the
+ * partial sums and 512 for the per-column scalars.
+ * One-time work: for k >= 2 fs_matrix_prepare(A, k, 0) and fs_matrix_prepare(At, k, 0) run before the first iteration; their
+ * errors (FS_ERR_RELEASED for a k never prepared before fs_matrix_release_csr) are raised before anything is written to X, as is
+ * FS_ERR_RELEASED for FS_PRECOND_JACOBI on an At whose plain CSR was released.  FS_ERR_ARG, raised before anything is written: a
+ * NULL A, At, X, B or prm; At not of the transposed shape; k outside 1..FS_PCGN_MAX_RHS; precond outside 0..2; FS_PRECOND_DIAG
+ * with a NULL diag; tol negative or NaN.  A product's own error is passed through. */
+int fs_pcgn(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k, double lambda, const fs_pcg_params *prm,
+            fs_pcg_info *info /* k entries or NULL */, fs_stream_t stream);
 
 /* ---- column-blocked binary CSR (cbcsr.h) -------------------------------------------- */
 fs_cbcsr_t fs_cbcsr_create(int nrow, int ncol, int nblocks, int colblocksize, const int *row_ptr,

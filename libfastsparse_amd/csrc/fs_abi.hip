@@ -176,6 +176,7 @@ int fs_set_option(const char *name, int value)
   if (!strcmp(name, "spmm_wide")) { fs::options().spmm_wide = value; return FS_OK; }
   if (!strcmp(name, "ata_kernel")) { fs::options().ata_kernel = value; return FS_OK; }
   if (!strcmp(name, "device_build")) { fs::options().device_build = value; return FS_OK; }
+  if (!strcmp(name, "pcgn_kernel")) { fs::options().pcgn_kernel = value; return FS_OK; }
   if (!strcmp(name, "cg_fixed_order")) { fs::options().cg_fixed_order = value; return FS_OK; }
   if (!strcmp(name, "dist_cg_scheme")) { fs::options().dist_cg_scheme = value; return FS_OK; }
   set_error(std::string("fs_set_option: unknown option ") + name);
@@ -198,6 +199,7 @@ int fs_get_option(const char *name)
   if (name && !strcmp(name, "spmm_wide")) return fs::options().spmm_wide;
   if (name && !strcmp(name, "ata_kernel")) return fs::options().ata_kernel;
   if (name && !strcmp(name, "device_build")) return fs::options().device_build;
+  if (name && !strcmp(name, "pcgn_kernel")) return fs::options().pcgn_kernel;
   if (name && !strcmp(name, "cg_fixed_order")) return fs::options().cg_fixed_order;
   if (name && !strcmp(name, "dist_cg_scheme")) return fs::options().dist_cg_scheme;
   if (name && !strcmp(name, "release_csr")) return fs::options().release_csr;

@@ -603,6 +603,561 @@ __global__ __launch_bounds__(kRedThreads) void mscg_direction_kernel(int n, doub
   for (int k0 = kMscgGroup; k0 < nl; k0 += kMscgGroup) mscg_direction_groups<false>(nl - k0, n, nb + k0, beta, p, r, P, ldp, ms);
 }
 
+// ---- fs_pcgn: (A'A + lambda I) X = B for k right-hand sides, k INDEPENDENT fs_pcg recurrences that share only the k-column products
+// (include/fastsparse_hip.h spells the arithmetic out).  X, B, R, P, Q are row-major F x k panels.  st[] keeps done, the iteration
+// count of the longest column and the mask of live columns; cs[] the per-column scalars, kPnStride doubles each.  Every per-column
+// sum has fs_cg's tree over that column's F terms: row i belongs to thread (i / kRedThreads % kRedBlocks, i % kRedThreads), so a
+// thread owns whole rows and keeps one (two: r.r and r.z) running sum per column in registers, KMAX columns at most.  The partials
+// of sum v = column * ns + s (ns sums per column) are part[v * kRedBlocks + block]: the finisher reads them coalesced.
+// A column that has converged is frozen: nothing writes its X, R or P again (its P rides through the products unchanged).  The
+// columns of a row share cache lines, so a frozen column saves stores and arithmetic, not lines; only a tile of kPcgnTile columns
+// (one 128-byte line per array) that are ALL frozen skips its loads: k > kPcgnTile only.
+constexpr int kPcgnMaxRhs = FS_PCGN_MAX_RHS;
+constexpr int kPcgnTile = 16;
+constexpr int kPcgnRowsMaxK = 4;           // up to this k the lane-per-row kernels serve under "pcgn_kernel" = 0, beyond it the LDS-staged ones
+enum { kStLiveMask = 12 };                 // bit j: column j is live (32 bits, exact in a double)
+enum { kPnBb = 0, kPnRr = 1, kPnStop = 2, kPnRz = 3, kPnAlpha = 4, kPnBeta = 5, kPnCount = 6, kPnLive = 7, kPnConverged = 8,
+       kPnStride = 16 };
+enum PcgnStep { kPnStepStart, kPnStepRz, kPnStepAlpha, kPnStepBeta };
+struct Pair { double a, b; };
+
+// two neighbouring columns of a row: one 16-byte access (V: the address is 16-byte aligned, so k is even) or two of 8 bytes
+template <bool V>
+__device__ __forceinline__ Pair pn_ld(const double *p, bool two)
+{
+  if (V) { const double2 v = *reinterpret_cast<const double2 *>(p); return {v.x, v.y}; }
+  return {p[0], two ? p[1] : 0.0};
+}
+
+template <bool V>
+__device__ __forceinline__ void pn_st(double *p, Pair v, bool l0, bool l1)
+{
+  if (V && l0 && l1) { *reinterpret_cast<double2 *>(p) = make_double2(v.a, v.b); return; }
+  if (l0) p[0] = v.a;
+  if (l1) p[1] = v.b;
+}
+
+// the columns of a row that the lane-per-row kernels take together: at most kPcgnTile, one 128-byte line per array
+template <int KMAX> constexpr int pcgn_tile() { return KMAX < kPcgnTile ? KMAX : kPcgnTile; }
+
+// f(c0) for the tiles c0 = 0, tile, ... < k that hold a live column (wave-uniform branches; c0 is a constant once the loop is
+// unrolled, so sums indexed by it stay in registers)
+template <int KMAX, typename F>
+__device__ __forceinline__ void pcgn_tiles(int k, unsigned live, F f)
+{
+  constexpr int T = pcgn_tile<KMAX>();
+#pragma unroll
+  for (int t = 0; t < KMAX / T; ++t)
+    if (T * t < k && ((live >> (T * t)) & ((1u << T) - 1u)) != 0u) f(T * t);
+}
+
+// v[h] = the column pair c0 + 2 h of one array, for every pair of the tile.  A kernel calls this array by array before it computes
+// or stores anything, so that all the 16-byte pieces a thread takes from a line are requested back to back (asked for one pair at
+// a time, with stores in between, a line is evicted from the CU's 32 KB cache between its pieces)
+template <int KMAX, bool V>
+__device__ __forceinline__ void pcgn_ld_tile(Pair (&v)[pcgn_tile<KMAX>() / 2 + 1], const double *p, int c0, int k)
+{
+#pragma unroll
+  for (int h = 0; h < pcgn_tile<KMAX>() / 2; ++h)
+    if (c0 + 2 * h < k) v[h] = pn_ld<V>(p + c0 + 2 * h, c0 + 2 * h + 1 < k);
+}
+
+// g(h, c, column c is live, column c + 1 exists and is live) for the column pairs c = c0 + 2 h of a tile
+template <int KMAX, typename G>
+__device__ __forceinline__ void pcgn_tile_pairs(int c0, int k, unsigned live, G g)
+{
+#pragma unroll
+  for (int h = 0; h < pcgn_tile<KMAX>() / 2; ++h) {
+    const int c = c0 + 2 * h;
+    if (c < k) g(h, c, ((live >> c) & 1u) != 0u, c + 1 < k && ((live >> (c + 1)) & 1u) != 0u);
+  }
+}
+
+__device__ __forceinline__ unsigned pcgn_live(const double *__restrict__ st)
+{
+  return (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)st[kStLiveMask]);
+}
+
+// block_sum per live column: s0[c] (and s1[c] with ns = 2) over the workgroup -> part[(c * ns + s) * kRedBlocks + blockIdx]
+template <int KMAX>
+__device__ __forceinline__ void pcgn_block_sums(int k, unsigned live, int ns, const double (&s0)[KMAX], const double (&s1)[KMAX],
+                                                double *__restrict__ part)
+{
+  __shared__ double sm[2 * KMAX][kRedThreads / 64];
+#pragma unroll
+  for (int c = 0; c < KMAX; ++c) {
+    if (c < k && ((live >> c) & 1u) != 0u) {
+      double s = s0[c];
+      for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m);
+      if ((threadIdx.x & 63) == 0) sm[2 * c][threadIdx.x >> 6] = s;
+      if (ns == 2) {
+        double z = s1[c];
+        for (int m = 32; m > 0; m >>= 1) z += __shfl_xor(z, m);
+        if ((threadIdx.x & 63) == 0) sm[2 * c + 1][threadIdx.x >> 6] = z;
+      }
+    }
+  }
+  __syncthreads();
+  const int v = threadIdx.x, c = v / ns;
+  if (v < ns * k && ((live >> c) & 1u) != 0u) {
+    double s = 0.0;
+    for (int w = 0; w < kRedThreads / 64; ++w) s += sm[2 * c + v % ns][w];
+    part[(size_t)v * kRedBlocks + blockIdx.x] = s;
+  }
+}
+
+// cold: X = 0, R = B.  warm (Q = A'(A X) on entry): Q += lambda X, R = B - Q.  Partials {b.b, r.r} per column (pcg_init_kernel).
+// VEC: 0 every access is 8 bytes (odd k), 1 16-byte accesses to the solve's own R, P, Q, 2 to the caller's X and B too
+template <int KMAX, int VEC>
+__global__ __launch_bounds__(kRedThreads) void pcgn_init_kernel(int n, int k, int warm, double lambda, const double *__restrict__ B,
+                                                               double *__restrict__ X, double *__restrict__ R,
+                                                               double *__restrict__ Q, double *__restrict__ part)
+{
+  constexpr int TP = pcgn_tile<KMAX>() / 2;
+  double bb[KMAX], rr[KMAX];
+#pragma unroll
+  for (int c = 0; c < KMAX; ++c) { bb[c] = 0.0; rr[c] = 0.0; }
+  const unsigned live = k < 32 ? (1u << k) - 1u : ~0u;
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    const size_t row = (size_t)i * k;
+    pcgn_tiles<KMAX>(k, live, [&](int c0) {
+      Pair bv[TP + 1] = {}, xv[TP + 1] = {}, qv[TP + 1] = {};
+      pcgn_ld_tile<KMAX, VEC == 2>(bv, B + row, c0, k);
+      if (warm) {
+        pcgn_ld_tile<KMAX, VEC == 2>(xv, X + row, c0, k);
+        pcgn_ld_tile<KMAX, VEC >= 1>(qv, Q + row, c0, k);
+      }
+      pcgn_tile_pairs<KMAX>(c0, k, live, [&](int h, int c, bool l0, bool l1) {
+        const Pair b = bv[h], x = xv[h], q0 = qv[h];
+        Pair r = b;
+        if (warm) {
+          const Pair q = {q0.a + lambda * x.a, q0.b + lambda * x.b};
+          pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
+          r = {b.a - q.a, b.b - q.b};
+        } else {
+          pn_st<VEC == 2>(X + row + c, {0.0, 0.0}, l0, l1);
+        }
+        pn_st<VEC >= 1>(R + row + c, r, l0, l1);
+        bb[c] += b.a * b.a; bb[c + 1] += b.b * b.b;
+        rr[c] += r.a * r.a; rr[c + 1] += r.b * r.b;
+      });
+    });
+  }
+  pcgn_block_sums<KMAX>(k, live, 2, bb, rr, part);
+}
+
+// P = Z = R dinv (dinv != NULL) or R, partial r.z per live column (pcg_start_kernel).  Every column gets its first direction, the
+// ones that are done at the start too: their P is finite when it rides through the products
+template <int KMAX, int VEC>
+__global__ __launch_bounds__(kRedThreads) void pcgn_start_kernel(int n, int k, const double *__restrict__ R,
+                                                                const double *__restrict__ dinv, double *__restrict__ P,
+                                                                double *__restrict__ part, const double *__restrict__ st)
+{
+  if (st[kStDone] != 0.0) return;
+  constexpr int TP = pcgn_tile<KMAX>() / 2;
+  const unsigned live = pcgn_live(st), all = k < 32 ? (1u << k) - 1u : ~0u;
+  double rz[KMAX];
+#pragma unroll
+  for (int c = 0; c < KMAX; ++c) rz[c] = 0.0;
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    const size_t row = (size_t)i * k;
+    const double di = dinv ? dinv[i] : 1.0;
+    pcgn_tiles<KMAX>(k, all, [&](int c0) {
+      Pair rv[TP + 1] = {};
+      pcgn_ld_tile<KMAX, VEC >= 1>(rv, R + row, c0, k);
+      pcgn_tile_pairs<KMAX>(c0, k, all, [&](int h, int c, bool l0, bool l1) {
+        const Pair r = rv[h];
+        const Pair z = {dinv ? r.a * di : r.a, dinv ? r.b * di : r.b};
+        pn_st<VEC >= 1>(P + row + c, z, l0, l1);
+        rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;
+      });
+    });
+  }
+  pcgn_block_sums<KMAX>(k, live, 1, rz, rz, part);
+}
+
+// Q += lambda P, partial q.p per live column (cg_shift_dot_dev_kernel)
+template <int KMAX, int VEC>
+__global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_kernel(int n, int k, double lambda, double *__restrict__ Q,
+                                                                    const double *__restrict__ P, double *__restrict__ part,
+                                                                    const double *__restrict__ st)
+{
+  if (st[kStDone] != 0.0) return;
+  constexpr int TP = pcgn_tile<KMAX>() / 2;
+  const unsigned live = pcgn_live(st);
+  double qp[KMAX];
+#pragma unroll
+  for (int c = 0; c < KMAX; ++c) qp[c] = 0.0;
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    const size_t row = (size_t)i * k;
+    pcgn_tiles<KMAX>(k, live, [&](int c0) {
+      Pair pv[TP + 1] = {}, qv[TP + 1] = {};
+      pcgn_ld_tile<KMAX, VEC >= 1>(pv, P + row, c0, k);
+      pcgn_ld_tile<KMAX, VEC >= 1>(qv, Q + row, c0, k);
+      pcgn_tile_pairs<KMAX>(c0, k, live, [&](int h, int c, bool l0, bool l1) {
+        const Pair p = pv[h], q0 = qv[h];
+        const Pair q = {q0.a + lambda * p.a, q0.b + lambda * p.b};
+        pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
+        qp[c] += q.a * p.a; qp[c + 1] += q.b * p.b;
+      });
+    });
+  }
+  pcgn_block_sums<KMAX>(k, live, 1, qp, qp, part);
+}
+
+// per live column: x += alpha p, r -= alpha q, partial r.r; with a preconditioner z = r dinv and partial r.z in the same pass
+// (pcg_update_kernel / cg_update_dev_kernel)
+template <int KMAX, int VEC>
+__global__ __launch_bounds__(kRedThreads) void pcgn_update_kernel(int n, int k, double *__restrict__ X, double *__restrict__ R,
+                                                                 const double *__restrict__ P, const double *__restrict__ Q,
+                                                                 const double *__restrict__ dinv, double *__restrict__ part,
+                                                                 const double *__restrict__ st, const double *__restrict__ cs)
+{
+  if (st[kStDone] != 0.0) return;
+  constexpr int TP = pcgn_tile<KMAX>() / 2;
+  const unsigned live = pcgn_live(st);
+  double rr[KMAX], rz[KMAX], al[KMAX];
+#pragma unroll
+  for (int c = 0; c < KMAX; ++c) { rr[c] = 0.0; rz[c] = 0.0; al[c] = cs[c * kPnStride + kPnAlpha]; }
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    const size_t row = (size_t)i * k;
+    const double di = dinv ? dinv[i] : 1.0;
+    pcgn_tiles<KMAX>(k, live, [&](int c0) {
+      Pair pv[TP + 1] = {}, qv[TP + 1] = {}, xv[TP + 1] = {}, rv[TP + 1] = {};
+      pcgn_ld_tile<KMAX, VEC >= 1>(pv, P + row, c0, k);
+      pcgn_ld_tile<KMAX, VEC >= 1>(qv, Q + row, c0, k);
+      pcgn_ld_tile<KMAX, VEC == 2>(xv, X + row, c0, k);
+      pcgn_ld_tile<KMAX, VEC >= 1>(rv, R + row, c0, k);
+      pcgn_tile_pairs<KMAX>(c0, k, live, [&](int h, int c, bool l0, bool l1) {
+        const Pair p = pv[h], q = qv[h], x0 = xv[h], r0 = rv[h];
+        const Pair x = {x0.a + al[c] * p.a, x0.b + al[c + 1] * p.b};
+        const Pair r = {r0.a - al[c] * q.a, r0.b - al[c + 1] * q.b};
+        pn_st<VEC == 2>(X + row + c, x, l0, l1);
+        pn_st<VEC >= 1>(R + row + c, r, l0, l1);
+        rr[c] += r.a * r.a; rr[c + 1] += r.b * r.b;
+        if (dinv) {
+          const Pair z = {r.a * di, r.b * di};
+          rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;
+        }
+      });
+    });
+  }
+  pcgn_block_sums<KMAX>(k, live, dinv ? 2 : 1, rr, rz, part);
+}
+
+// per live column: p = z + beta p with z = r dinv formed on the fly, or p = r + beta p (pcg_direction_kernel / cg_direction_dev_kernel)
+template <int KMAX, int VEC>
+__global__ __launch_bounds__(kRedThreads) void pcgn_direction_kernel(int n, int k, double *__restrict__ P, const double *__restrict__ R,
+                                                                    const double *__restrict__ dinv, const double *__restrict__ st,
+                                                                    const double *__restrict__ cs)
+{
+  if (st[kStDone] != 0.0) return;
+  constexpr int TP = pcgn_tile<KMAX>() / 2;
+  const unsigned live = pcgn_live(st);
+  double be[KMAX];
+#pragma unroll
+  for (int c = 0; c < KMAX; ++c) be[c] = cs[c * kPnStride + kPnBeta];
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    const size_t row = (size_t)i * k;
+    const double di = dinv ? dinv[i] : 1.0;
+    pcgn_tiles<KMAX>(k, live, [&](int c0) {
+      Pair rv[TP + 1] = {}, pv[TP + 1] = {};
+      pcgn_ld_tile<KMAX, VEC >= 1>(rv, R + row, c0, k);
+      pcgn_ld_tile<KMAX, VEC >= 1>(pv, P + row, c0, k);
+      pcgn_tile_pairs<KMAX>(c0, k, live, [&](int h, int c, bool l0, bool l1) {
+        const Pair r = rv[h], p0 = pv[h];
+        const Pair z = {dinv ? r.a * di : r.a, dinv ? r.b * di : r.b};
+        const Pair p = {z.a + be[c] * p0.a, z.b + be[c + 1] * p0.b};
+        pn_st<VEC >= 1>(P + row + c, p, l0, l1);
+      });
+    });
+  }
+}
+
+// ---- the per-iteration kernels again, the panels staged through LDS (option "pcgn_kernel" = 2; auto for k > kPcgnRowsMaxK).  A
+// workgroup's 256 rows of a row-major panel are one contiguous piece of 256 k doubles: it is read with coalesced 16-byte loads
+// (every line touched once, by neighbouring lanes) into a tile of LDS padded to an odd row length, where every thread then works on
+// its own row without bank conflicts, and goes back the same way.  Two tiles: the array that is updated and the one it is updated
+// with.  Row i still belongs to thread (i / 256 % 1024, i % 256) and a thread still adds its
+// rows' terms in increasing order to sums in registers: the same tree, the same bits.  Nothing is skipped for frozen columns but
+// their arithmetic and their stores (a column's doubles share every line with its neighbours').
+// rows of a tile: all 256 of the workgroup up to KMAX = 8, then fewer, so that the two tiles stay at 35 KB and four workgroups share
+// a CU (with 256 rows at KMAX = 32 -- 135 KB, one workgroup per CU, loading, computing and storing in turn -- the kernels reached
+// 2.1 TB/s where the lane-per-row kernels reach 2.7)
+template <int KMAX> constexpr int pl_rows() { return KMAX <= 8 ? kRedThreads : kRedThreads * 8 / KMAX; }
+
+template <int KMAX>
+__device__ __forceinline__ void pl_in(double *__restrict__ tile, const double *__restrict__ g, int ne, int k)
+{
+  constexpr int LD = KMAX + 1;
+  if (((uintptr_t)g & 15) == 0) {
+#pragma unroll 4
+    for (int e = 2 * threadIdx.x; e < ne; e += 2 * kRedThreads) {
+      const int r = e / k, c = e - r * k;
+      if (e + 1 < ne) {
+        const double2 d = *reinterpret_cast<const double2 *>(g + e);
+        tile[r * LD + c] = d.x;
+        tile[c + 1 < k ? r * LD + c + 1 : (r + 1) * LD] = d.y;
+      } else {
+        tile[r * LD + c] = g[e];
+      }
+    }
+  } else {
+#pragma unroll 4
+    for (int e = threadIdx.x; e < ne; e += kRedThreads) {
+      const int r = e / k;
+      tile[r * LD + e - r * k] = g[e];
+    }
+  }
+}
+
+// the live columns of the tile back to the panel (a frozen column is not written)
+template <int KMAX>
+__device__ __forceinline__ void pl_out(double *__restrict__ g, const double *__restrict__ tile, int ne, int k, unsigned live)
+{
+  constexpr int LD = KMAX + 1;
+  if (((uintptr_t)g & 15) == 0) {
+    for (int e = 2 * threadIdx.x; e < ne; e += 2 * kRedThreads) {
+      const int r = e / k, c = e - r * k;
+      const bool two = e + 1 < ne;
+      const int c1 = c + 1 < k ? c + 1 : 0;
+      const double a = tile[r * LD + c], b = two ? tile[c + 1 < k ? r * LD + c + 1 : (r + 1) * LD] : 0.0;
+      const bool l0 = ((live >> c) & 1u) != 0u, l1 = two && ((live >> c1) & 1u) != 0u;
+      if (l0 && l1) *reinterpret_cast<double2 *>(g + e) = make_double2(a, b);
+      else if (l0) g[e] = a;
+      else if (l1) g[e + 1] = b;
+    }
+  } else {
+    for (int e = threadIdx.x; e < ne; e += kRedThreads) {
+      const int r = e / k, c = e - r * k;
+      if (((live >> c) & 1u) != 0u) g[e] = tile[r * LD + c];
+    }
+  }
+}
+
+// Q += lambda P, partial q.p per live column
+template <int KMAX>
+__global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_lds_kernel(int n, int k, double lambda, double *__restrict__ Q,
+                                                                        const double *__restrict__ P, double *__restrict__ part,
+                                                                        const double *__restrict__ st)
+{
+  if (st[kStDone] != 0.0) return;
+  constexpr int LD = KMAX + 1;
+  constexpr int TR = pl_rows<KMAX>();
+  __shared__ double t0[TR * LD], t1[TR * LD];
+  const unsigned live = pcgn_live(st);
+  double qp[KMAX];
+#pragma unroll
+  for (int c = 0; c < KMAX; ++c) qp[c] = 0.0;
+  for (int blk0 = blockIdx.x * kRedThreads; blk0 < n; blk0 += gridDim.x * kRedThreads)      // (workgroup-uniform)
+  for (int row0 = blk0; row0 < blk0 + kRedThreads && row0 < n; row0 += TR) {                // the workgroup's 256 rows, TR at a time
+    const int nr = n - row0 < TR ? n - row0 : TR, ne = nr * k, lt = (int)threadIdx.x - (row0 - blk0);
+    const size_t at = (size_t)row0 * k;
+    pl_in<KMAX>(t0, Q + at, ne, k);
+    pl_in<KMAX>(t1, P + at, ne, k);
+    __syncthreads();
+    if (lt >= 0 && lt < nr) {                                 // the thread that owns row row0 + lt
+      double *q = t0 + lt * LD;
+      const double *p = t1 + lt * LD;
+#pragma unroll
+      for (int c = 0; c < KMAX; ++c)
+        if (c < k && ((live >> c) & 1u) != 0u) {
+          const double pi = p[c];
+          const double qi = q[c] + lambda * pi;
+          q[c] = qi;
+          qp[c] += qi * pi;
+        }
+    }
+    __syncthreads();
+    pl_out<KMAX>(Q + at, t0, ne, k, live);
+    __syncthreads();
+  }
+  pcgn_block_sums<KMAX>(k, live, 1, qp, qp, part);
+}
+
+// per live column: x += alpha p, then r -= alpha q with the partials of r.r and, with a preconditioner, of r.z (z = r dinv)
+template <int KMAX>
+__global__ __launch_bounds__(kRedThreads) void pcgn_update_lds_kernel(int n, int k, double *__restrict__ X, double *__restrict__ R,
+                                                                     const double *__restrict__ P, const double *__restrict__ Q,
+                                                                     const double *__restrict__ dinv, double *__restrict__ part,
+                                                                     const double *__restrict__ st, const double *__restrict__ cs)
+{
+  if (st[kStDone] != 0.0) return;
+  constexpr int LD = KMAX + 1;
+  constexpr int TR = pl_rows<KMAX>();
+  __shared__ double t0[TR * LD], t1[TR * LD];
+  const unsigned live = pcgn_live(st);
+  double rr[KMAX], rz[KMAX], al[KMAX];
+#pragma unroll
+  for (int c = 0; c < KMAX; ++c) { rr[c] = 0.0; rz[c] = 0.0; al[c] = cs[c * kPnStride + kPnAlpha]; }
+  for (int blk0 = blockIdx.x * kRedThreads; blk0 < n; blk0 += gridDim.x * kRedThreads)      // (workgroup-uniform)
+  for (int row0 = blk0; row0 < blk0 + kRedThreads && row0 < n; row0 += TR) {                // the workgroup's 256 rows, TR at a time
+    const int nr = n - row0 < TR ? n - row0 : TR, ne = nr * k, lt = (int)threadIdx.x - (row0 - blk0);
+    const size_t at = (size_t)row0 * k;
+    pl_in<KMAX>(t0, X + at, ne, k);
+    pl_in<KMAX>(t1, P + at, ne, k);
+    __syncthreads();
+    if (lt >= 0 && lt < nr) {                                 // the thread that owns row row0 + lt
+      double *x = t0 + lt * LD;
+      const double *p = t1 + lt * LD;
+#pragma unroll
+      for (int c = 0; c < KMAX; ++c)
+        if (c < k && ((live >> c) & 1u) != 0u) x[c] = x[c] + al[c] * p[c];
+    }
+    __syncthreads();
+    pl_out<KMAX>(X + at, t0, ne, k, live);
+    __syncthreads();
+    pl_in<KMAX>(t0, R + at, ne, k);
+    pl_in<KMAX>(t1, Q + at, ne, k);
+    __syncthreads();
+    if (lt >= 0 && lt < nr) {                                 // the thread that owns row row0 + lt
+      double *r = t0 + lt * LD;
+      const double *q = t1 + lt * LD;
+      const double di = dinv ? dinv[row0 + lt] : 1.0;
+#pragma unroll
+      for (int c = 0; c < KMAX; ++c)
+        if (c < k && ((live >> c) & 1u) != 0u) {
+          const double ri = r[c] - al[c] * q[c];
+          r[c] = ri;
+          rr[c] += ri * ri;
+          if (dinv) { const double zi = ri * di; rz[c] += ri * zi; }
+        }
+    }
+    __syncthreads();
+    pl_out<KMAX>(R + at, t0, ne, k, live);
+    __syncthreads();
+  }
+  pcgn_block_sums<KMAX>(k, live, dinv ? 2 : 1, rr, rz, part);
+}
+
+// per live column: p = z + beta p with z = r dinv formed on the fly, or p = r + beta p
+template <int KMAX>
+__global__ __launch_bounds__(kRedThreads) void pcgn_direction_lds_kernel(int n, int k, double *__restrict__ P, const double *__restrict__ R,
+                                                                        const double *__restrict__ dinv, const double *__restrict__ st,
+                                                                        const double *__restrict__ cs)
+{
+  if (st[kStDone] != 0.0) return;
+  constexpr int LD = KMAX + 1;
+  constexpr int TR = pl_rows<KMAX>();
+  __shared__ double t0[TR * LD], t1[TR * LD];
+  const unsigned live = pcgn_live(st);
+  double be[KMAX];
+#pragma unroll
+  for (int c = 0; c < KMAX; ++c) be[c] = cs[c * kPnStride + kPnBeta];
+  for (int blk0 = blockIdx.x * kRedThreads; blk0 < n; blk0 += gridDim.x * kRedThreads)      // (workgroup-uniform)
+  for (int row0 = blk0; row0 < blk0 + kRedThreads && row0 < n; row0 += TR) {                // the workgroup's 256 rows, TR at a time
+    const int nr = n - row0 < TR ? n - row0 : TR, ne = nr * k, lt = (int)threadIdx.x - (row0 - blk0);
+    const size_t at = (size_t)row0 * k;
+    pl_in<KMAX>(t0, P + at, ne, k);
+    pl_in<KMAX>(t1, R + at, ne, k);
+    __syncthreads();
+    if (lt >= 0 && lt < nr) {                                 // the thread that owns row row0 + lt
+      double *p = t0 + lt * LD;
+      const double *r = t1 + lt * LD;
+      const double di = dinv ? dinv[row0 + lt] : 1.0;
+#pragma unroll
+      for (int c = 0; c < KMAX; ++c)
+        if (c < k && ((live >> c) & 1u) != 0u) {
+          const double zi = dinv ? r[c] * di : r[c];
+          p[c] = zi + be[c] * p[c];
+        }
+    }
+    __syncthreads();
+    pl_out<KMAX>(P + at, t0, ne, k, live);
+    __syncthreads();
+  }
+}
+
+// the one workgroup that finishes the ns sums of every live column -- each is fs_cg's stage 2 over its kRedBlocks partials, kPcgnGroup
+// sums' loads in flight together -- and then does the scalar step of fs_pcg per column, one thread each (final_step_kernel's
+// kStepPcgStart, kStepPcgRz, kStepCgAlpha, kStepPcgBeta with `done` per column); thread 0 then packs the live mask.  done: no
+// column is live; st[kStIter] counts the iterations after which a column was still live (the longest column's count)
+constexpr int kPcgnGroup = 8;
+template <PcgnStep STEP>
+__global__ __launch_bounds__(kRedThreads) void pcgn_step_kernel(const double *__restrict__ part, double *st, double *cs, int k, int ns,
+                                                               double tol)
+{
+  if (STEP != kPnStepStart && st[kStDone] != 0.0) return;
+  __shared__ double sm[2 * kPcgnMaxRhs][kRedThreads / 64];
+  __shared__ double red[2 * kPcgnMaxRhs];
+  const unsigned live = STEP == kPnStepStart ? (k < 32 ? (1u << k) - 1u : ~0u) : pcgn_live(st);
+  const int nv = ns * k;
+  for (int v0 = 0; v0 < nv; v0 += kPcgnGroup) {
+    double a[kPcgnGroup];
+#pragma unroll
+    for (int u = 0; u < kPcgnGroup; ++u) {
+      const int v = v0 + u;
+      a[u] = 0.0;
+      if (v < nv && ((live >> (v / ns)) & 1u) != 0u)
+        for (int b = threadIdx.x; b < kRedBlocks; b += kRedThreads) a[u] += part[(size_t)v * kRedBlocks + b];
+    }
+#pragma unroll
+    for (int u = 0; u < kPcgnGroup; ++u) {
+      double s = a[u];
+      for (int m = 32; m > 0; m >>= 1) s += __shfl_xor(s, m);
+      if ((threadIdx.x & 63) == 0 && v0 + u < nv) sm[v0 + u][threadIdx.x >> 6] = s;
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < nv) {
+    double s = 0.0;
+    for (int w = 0; w < kRedThreads / 64; ++w) s += sm[threadIdx.x][w];
+    red[threadIdx.x] = s;
+  }
+  __syncthreads();
+  const int c = threadIdx.x;
+  if (c < k && ((live >> c) & 1u) != 0u) {
+    double *e = cs + c * kPnStride;
+    const double s0 = red[c * ns], s1 = red[c * ns + ns - 1];
+    if (STEP == kPnStepStart) {                              // {b.b, r.r}
+      const double stop = tol * sqrt(s0);
+      const bool done = sqrt(s1) <= stop;
+      e[kPnBb] = s0; e[kPnRr] = s1; e[kPnStop] = stop; e[kPnCount] = 0.0;
+      e[kPnLive] = done ? 0.0 : 1.0; e[kPnConverged] = done ? 1.0 : 0.0;
+    } else if (STEP == kPnStepRz) {
+      e[kPnRz] = s0;
+    } else if (STEP == kPnStepAlpha) {                       // q.p
+      e[kPnAlpha] = e[kPnRz] / s0;
+    } else {                                                 // {r.r[, r.z]}
+      const double rr = s0, rz_new = s1;
+      e[kPnRr] = rr;
+      if (sqrt(rr) <= e[kPnStop]) { e[kPnLive] = 0.0; e[kPnConverged] = 1.0; }
+      else { e[kPnBeta] = rz_new / e[kPnRz]; e[kPnRz] = rz_new; e[kPnCount] += 1.0; }
+    }
+  }
+  if (STEP != kPnStepStart && STEP != kPnStepBeta) return;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  unsigned m = 0u;
+  for (int j = 0; j < k; ++j)
+    if (cs[j * kPnStride + kPnLive] != 0.0) m |= 1u << j;
+  st[kStLiveMask] = (double)m;
+  if (STEP == kPnStepStart) { st[kStIter] = 0.0; st[kStDone] = m ? 0.0 : 1.0; }
+  else if (m == 0u) st[kStDone] = 1.0;
+  else st[kStIter] += 1.0;
+}
+
+// the kernels' shape for k columns: KMAX = 4, 8, 16 or 32 sums per thread, VEC as in pcgn_init_kernel
+template <int KMAX, int VEC> struct PcgnShape { static constexpr int kmax = KMAX, vec = VEC; };
+template <typename F>
+int pcgn_dispatch(int k, int vec, F f)
+{
+  switch ((k <= 4 ? 0 : k <= 8 ? 1 : k <= 16 ? 2 : 3) * 3 + vec) {
+    case 0: return f(PcgnShape<4, 0>{});
+    case 1: return f(PcgnShape<4, 1>{});
+    case 2: return f(PcgnShape<4, 2>{});
+    case 3: return f(PcgnShape<8, 0>{});
+    case 4: return f(PcgnShape<8, 1>{});
+    case 5: return f(PcgnShape<8, 2>{});
+    case 6: return f(PcgnShape<16, 0>{});
+    case 7: return f(PcgnShape<16, 1>{});
+    case 8: return f(PcgnShape<16, 2>{});
+    case 9: return f(PcgnShape<32, 0>{});
+    case 10: return f(PcgnShape<32, 1>{});
+    default: return f(PcgnShape<32, 2>{});
+  }
+}
+
 struct Workspace {
   std::vector<void *> bufs;
   double *get(size_t n)
@@ -737,6 +1292,9 @@ static thread_local bool g_last_cg_state_set = false;
 
 static thread_local double g_last_mscg_state[kMscgMaxShifts * kMsStride];
 static thread_local int g_last_mscg_doubles = 0;
+
+static thread_local double g_last_pcgn_state[kPcgnMaxRhs * kPnStride];
+static thread_local int g_last_pcgn_doubles = 0;
 
 void note_cg_state(const double *st_host)
 {
@@ -1010,6 +1568,93 @@ int fs_mscg(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double 
   return FS_OK;
 }
 
+// (A'A + lambda I) X = B for k right-hand sides, X and B row-major F x k: k independent fs_pcg recurrences on shared k-column
+// products; see include/fastsparse_hip.h for the arithmetic.  Column j has the bits of fs_pcg on B[:, j] wherever the k-column
+// product has the bits of the single-vector one ("strict_order"; k = 1 in every mode: the products are fs_spmv).
+int fs_pcgn(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k, double lambda, const fs_pcg_params *prm,
+            fs_pcg_info *info, fs_stream_t stream)
+{
+  FS_RANGE("fs_pcgn");
+  if (!A || !At || !X || !B || !prm) { set_error("fs_pcgn: NULL argument"); return FS_ERR_ARG; }
+  if (k < 1 || k > kPcgnMaxRhs) { set_error("fs_pcgn: k outside 1..FS_PCGN_MAX_RHS"); return FS_ERR_ARG; }
+  CgSolve f{"fs_pcgn", A, At, k, stream};
+  if (int rc = f.shape()) return rc;
+  if (prm->precond != FS_PRECOND_NONE && prm->precond != FS_PRECOND_JACOBI && prm->precond != FS_PRECOND_DIAG) {
+    set_error("fs_pcgn: precond is none of FS_PRECOND_NONE / _JACOBI / _DIAG"); return FS_ERR_ARG;
+  }
+  if (prm->precond == FS_PRECOND_DIAG && !prm->diag) { set_error("fs_pcgn: FS_PRECOND_DIAG without a diagonal"); return FS_ERR_ARG; }
+  if (!(prm->tol >= 0.0)) { set_error("fs_pcgn: tol is negative or NaN"); return FS_ERR_ARG; }
+  if (prm->precond == FS_PRECOND_JACOBI)                     // before anything is written to X
+    if (int rc = need_plain_csr(At->a, "fs_pcgn with FS_PRECOND_JACOBI (fs_gram_diag)")) return rc;
+  if (k >= 2) {                                              // the k-column copies of both matrices (fs_spmm itself never builds)
+    if (int rc = fs_matrix_prepare(A, k, 0, stream)) return rc;
+    if (int rc = fs_matrix_prepare(At, k, 0, stream)) return rc;
+  }
+  const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
+  const int F = f.F;
+  const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
+  hipStream_t s = (hipStream_t)stream;
+  double *dinv = nullptr, *own = nullptr;
+  const size_t npart = (size_t)kRedBlocks * 2 * k;
+  if (int rc = f.alloc(pre ? &dinv : nullptr, F, &own, npart + kPcgnMaxRhs * kPnStride)) return rc;
+  double *r = f.r, *p = f.p, *q = f.q, *st = f.st, *part = own, *cs = own + npart;
+  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
+  FS_HIP(hipMemsetAsync(cs, 0, sizeof(double) * kPcgnMaxRhs * kPnStride, s));   // slots a column never writes read as 0 in the debug getter
+  // 16-byte accesses: r, p, q are the solve's own (rows of an even k stay aligned), X and B are the caller's
+  const int vec = (k & 1) ? 0 : ((((uintptr_t)X | (uintptr_t)B) & 15) == 0 ? 2 : 1);
+  if (prm->precond == FS_PRECOND_JACOBI)
+    if (int rc = fs_gram_diag(At, lambda, dinv, stream)) return rc;
+  if (pre) hipLaunchKernelGGL(pcg_dinv_kernel, g, blk, 0, s, F, prm->precond == FS_PRECOND_DIAG ? prm->diag : dinv, dinv);
+  if (warm) {                                                // R = B - (A'(A X) + lambda X): one pair of k-column products
+    if (int rc = k == 1 ? fs_spmv(A, f.tmp, X, stream) : fs_spmm(A, f.tmp, X, k, stream)) return rc;
+    if (int rc = k == 1 ? fs_spmv(At, q, f.tmp, stream) : fs_spmm(At, q, f.tmp, k, stream)) return rc;
+  }
+  if (int rc = pcgn_dispatch(k, vec, [&](auto sh) -> int {
+        using S = decltype(sh);
+        hipLaunchKernelGGL((pcgn_init_kernel<S::kmax, S::vec>), g, blk, 0, s, F, k, (int)warm, lambda, B, X, r, q, part);
+        hipLaunchKernelGGL(pcgn_step_kernel<kPnStepStart>, one, blk, 0, s, part, st, cs, k, 2, prm->tol);   // b.b, r.r, stop, live?
+        hipLaunchKernelGGL((pcgn_start_kernel<S::kmax, S::vec>), g, blk, 0, s, F, k, r, dinv, p, part, st);
+        hipLaunchKernelGGL(pcgn_step_kernel<kPnStepRz>, one, blk, 0, s, part, st, cs, k, 1, 0.0);           // r.z
+        FS_HIP(hipGetLastError());
+        return FS_OK;
+      })) return rc;
+  const int which = options().pcgn_kernel;
+  const bool staged = which == 2 || (which == 0 && k > kPcgnRowsMaxK);
+  auto steps = [&]() -> int {
+    return pcgn_dispatch(k, vec, [&](auto sh) -> int {
+      using S = decltype(sh);
+      if (staged) hipLaunchKernelGGL(pcgn_shift_dot_lds_kernel<S::kmax>, g, blk, 0, s, F, k, lambda, q, p, part, st);
+      else        hipLaunchKernelGGL((pcgn_shift_dot_kernel<S::kmax, S::vec>), g, blk, 0, s, F, k, lambda, q, p, part, st);
+      hipLaunchKernelGGL(pcgn_step_kernel<kPnStepAlpha>, one, blk, 0, s, part, st, cs, k, 1, 0.0);          // alpha = r.z / p.q
+      if (staged) hipLaunchKernelGGL(pcgn_update_lds_kernel<S::kmax>, g, blk, 0, s, F, k, X, r, p, q, dinv, part, st, cs);
+      else        hipLaunchKernelGGL((pcgn_update_kernel<S::kmax, S::vec>), g, blk, 0, s, F, k, X, r, p, q, dinv, part, st, cs);
+      hipLaunchKernelGGL(pcgn_step_kernel<kPnStepBeta>, one, blk, 0, s, part, st, cs, k, pre ? 2 : 1, 0.0); // converged? beta
+      if (staged) hipLaunchKernelGGL(pcgn_direction_lds_kernel<S::kmax>, g, blk, 0, s, F, k, p, r, dinv, st, cs);
+      else        hipLaunchKernelGGL((pcgn_direction_kernel<S::kmax, S::vec>), g, blk, 0, s, F, k, p, r, dinv, st, cs);
+      FS_HIP(hipGetLastError());
+      return FS_OK;
+    });
+  };
+  if (int rc = f.iterate(cap, true, steps)) return rc;
+  double fcs[kPcgnMaxRhs * kPnStride] = {0.0};
+  FS_HIP(hipMemcpyAsync(fcs, cs, sizeof(double) * k * kPnStride, hipMemcpyDeviceToHost, s));
+  if (int rc = f.finish()) return rc;
+  // fs_pcg's slots of the st[] kept for fs_debug_last_cg_state carry column 0's scalars: with k = 1 it is fs_pcg's st[]
+  f.fin[kStRsq] = fcs[kPnRz]; f.fin[kStAlpha] = fcs[kPnAlpha]; f.fin[kStBeta] = fcs[kPnBeta]; f.fin[kStStop] = fcs[kPnStop];
+  f.fin[kStRr] = fcs[kPnRr]; f.fin[kStBb] = fcs[kPnBb];
+  note_cg_state(f.fin);
+  for (int i = 0; i < k * kPnStride; ++i) g_last_pcgn_state[i] = fcs[i];
+  g_last_pcgn_doubles = k * kPnStride;
+  for (int j = 0; info && j < k; ++j) {
+    const double *e = fcs + j * kPnStride;
+    info[j].iterations = (int)e[kPnCount];                   // a column still live at the cap: count = cap, converged 0
+    info[j].converged = e[kPnConverged] != 0.0;
+    info[j].rnorm = sqrt(e[kPnRr]);
+    info[j].bnorm = sqrt(e[kPnBb]);
+  }
+  return FS_OK;
+}
+
 // two right-hand sides, X and B row-major F x 2 (cg.h:85-187)
 int fs_cg2(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, double lambda, double tol, int *out_iter,
            fs_stream_t stream)
@@ -1051,6 +1696,17 @@ int fs_debug_last_mscg_state(double *out, int max_doubles)
   if (!out || max_doubles < 0) { set_error("fs_debug_last_mscg_state: bad argument"); return FS_ERR_ARG; }
   const int n = g_last_mscg_doubles < max_doubles ? g_last_mscg_doubles : max_doubles;
   for (int i = 0; i < n; ++i) out[i] = g_last_mscg_state[i];
+  return n;
+}
+
+// the final per-column array of the last fs_pcgn on the calling thread: k * kPnStride doubles (layout of the kPn enum), at most
+// max_doubles of them; a slot its column never wrote (rz, alpha of a column that is done at the start; beta before a second
+// iteration) is 0.  Returns the number of doubles written, 0 before the first solve.  Diagnostics, not in the header.
+int fs_debug_last_pcgn_state(double *out, int max_doubles)
+{
+  if (!out || max_doubles < 0) { set_error("fs_debug_last_pcgn_state: bad argument"); return FS_ERR_ARG; }
+  const int n = g_last_pcgn_doubles < max_doubles ? g_last_pcgn_doubles : max_doubles;
+  for (int i = 0; i < n; ++i) out[i] = g_last_pcgn_state[i];
   return n;
 }
 

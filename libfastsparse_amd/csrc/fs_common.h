@@ -279,6 +279,7 @@ struct Options {
   int spmm_wide = 0;     // row SpMM kernel with two columns per lane and 16-byte loads: 0 auto (even k from 4 to 14, 16-byte aligned X / Y), 1 wherever legal, -1 never
   int spmm_kernel = 0;   // multi-column products: 0 auto, 1 row kernel, 2 k-column two-pass sweep (k = 2..4), 3 one
                          // single-vector sweep per column, 4 the MFMA row kernel (experiment, see spmm_mfma_kernel)
+  int pcgn_kernel = 0;     // fs_pcgn's per-iteration vector kernels: 0 auto, 1 a lane per row, 2 panels staged through LDS
   int cg_fixed_order = 1;  // fs_cg / fs_cg2 / fs_dist_cg run their products with fixed-order sums (as under "reproducible"), so
                            // that a solve is bit-identical from run to run like the reference's (cg.h:25-187); 0: the default kernels
   int release_csr = 0;     // 1: fs_csr_create / fs_coo_create / fs_matrix_build_transpose give the plain CSR arrays back once a re-ordered
