@@ -211,7 +211,10 @@ int fs_spmv_t_host(fs_matrix_t A, double *y_host, const double *x_host);
 
 /* ---- consumers of the path, device resident (cg.h of the reference) -------------------- */
 /* (A'A + lambda I) x = b by conjugate gradients; A and the handle of its transpose as the reference passes
- * them (bsbm_cg cg.h:25); x, b: F = ncol(A) doubles in HBM; stops at ||r|| <= tol ||b|| or after F iterations */
+ * them (bsbm_cg cg.h:25); x, b: F = ncol(A) doubles in HBM; stops at ||r|| <= tol ||b|| or after F iterations.
+ * Every solver below (fs_cg, fs_cg2, fs_pcg, fs_mscg, fs_pcgn) looks at its two products before it writes anything: where one of
+ * them would read plain CSR arrays that fs_matrix_release_csr gave back ("strict_order", spmv_kernel 1 / 2 / 3, the row kernel of
+ * a k-column product) the solve returns FS_ERR_RELEASED with x untouched -- also a solve that would have needed no product. */
 int fs_cg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lambda, double tol, int *out_iter,
           fs_stream_t stream);
 /* the same for two right-hand sides, X and B row-major F x 2 (bsbm_cg2 cg.h:85) */
@@ -302,7 +305,8 @@ enum { FS_MSCG_MAX_SHIFTS = 16 };
  * The scalars live on the device and the host learns of convergence one iteration behind, as in fs_cg.  Products add in a fixed
  * order unless option "cg_fixed_order" is 0.  FS_ERR_ARG, raised before anything is written to X: a NULL A, At, X, b or lambda; At
  * not of the transposed shape; m outside 1..FS_MSCG_MAX_SHIFTS; ldx < F; tol negative or NaN; a lambda that is NaN or infinite.  A
- * product's own error (FS_ERR_RELEASED under "strict_order" after fs_matrix_release_csr) is passed through. */
+ * product's own error is passed through; FS_ERR_RELEASED under "strict_order" after fs_matrix_release_csr is raised before anything
+ * is written to X (see fs_cg). */
 int fs_mscg(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double *b, int m, const double *lambda,
             double tol, int max_iter, fs_pcg_info *info, fs_stream_t stream);
 

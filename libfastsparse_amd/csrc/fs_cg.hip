@@ -1355,6 +1355,23 @@ struct CgSolve {
     if (At->a.nrow != F || At->a.ncol != N) { set_error(std::string(who) + ": At is not the transpose shape of A"); return FS_ERR_ARG; }
     return FS_OK;
   }
+  // before anything is written to the caller's x: a solve whose products would read plain CSR arrays that fs_matrix_release_csr
+  // gave back (strict_order, spmv_kernel 1-3, the row kernel of k columns) ends here and not behind its start kernels.  For
+  // k >= 2 after the solver's fs_matrix_prepare calls: they settle the plan
+  int ready()
+  {
+    for (fs_matrix_t M : {A, At}) {
+      if (M->a.nrow == 0) continue;
+      bool plain;
+      {
+        std::lock_guard<std::mutex> g(M->lock);
+        plain = k == 1 ? spmv_choice(M->a, options()) < 6 : spmm_reads_plain_csr(M->a, k);
+      }
+      if (plain)
+        if (int rc = need_plain_csr(M->a, who)) return rc;
+    }
+    return FS_OK;
+  }
   // the work space, st[] (the scalars live on the device from the first iteration on) and the host's flags.  A solver's own
   // buffers keep their places in the order of the allocations: *own (n_own doubles) before st, *own2 behind it
   int alloc(double **own = nullptr, size_t n_own = 0, double **own2 = nullptr, size_t n_own2 = 0)
@@ -1420,6 +1437,7 @@ int fs_cg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lamb
   if (!A || !At || !x || !b) { set_error("fs_cg: NULL argument"); return FS_ERR_ARG; }
   CgSolve f{"fs_cg", A, At, 1, stream};
   if (int rc = f.shape()) return rc;
+  if (int rc = f.ready()) return rc;
   if (int rc = f.alloc()) return rc;
   const int F = f.F;
   hipStream_t s = (hipStream_t)stream;
@@ -1463,6 +1481,7 @@ int fs_pcg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lam
   if (!(prm->tol >= 0.0)) { set_error("fs_pcg: tol is negative or NaN"); return FS_ERR_ARG; }
   if (prm->precond == FS_PRECOND_JACOBI)                     // before anything is written to x
     if (int rc = need_plain_csr(At->a, "fs_pcg with FS_PRECOND_JACOBI (fs_gram_diag)")) return rc;
+  if (int rc = f.ready()) return rc;
   const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
   const int F = f.F;
   const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
@@ -1524,6 +1543,7 @@ int fs_mscg(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double 
   if (!(tol >= 0.0)) { set_error("fs_mscg: tol is negative or NaN"); return FS_ERR_ARG; }
   for (int i = 0; i < m; ++i)
     if (!isfinite(lambda[i])) { set_error("fs_mscg: a lambda is NaN or infinite"); return FS_ERR_ARG; }
+  if (int rc = f.ready()) return rc;
   double base = lambda[0];
   for (int i = 1; i < m; ++i) if (lambda[i] < base) base = lambda[i];
   MscgSigma sg;
@@ -1590,6 +1610,7 @@ int fs_pcgn(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k, do
     if (int rc = fs_matrix_prepare(A, k, 0, stream)) return rc;
     if (int rc = fs_matrix_prepare(At, k, 0, stream)) return rc;
   }
+  if (int rc = f.ready()) return rc;
   const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
   const int F = f.F;
   const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
@@ -1666,6 +1687,7 @@ int fs_cg2(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, double lam
   // the two-column copies of both matrices, before the first iteration (fs_spmm itself never builds)
   if (int rc = fs_matrix_prepare(A, 2, 0, stream)) return rc;
   if (int rc = fs_matrix_prepare(At, 2, 0, stream)) return rc;
+  if (int rc = f.ready()) return rc;
   if (int rc = f.alloc()) return rc;
   const int F = f.F;
   hipStream_t s = (hipStream_t)stream;

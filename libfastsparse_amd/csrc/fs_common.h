@@ -316,6 +316,7 @@ int debug_dma_trace(unsigned long long *out8, int reset);   // defined in -DFS_L
 int launch_spmm(DeviceCsr &A, double *Y, const double *X, int k, hipStream_t s);   // never builds, never waits: see prepare_spmm
 int prepare_spmm(DeviceCsr &A, int k, hipStream_t s);   // k-column copy, scratch, measured choice: synchronous, idempotent
 int spmm_plan(const DeviceCsr &A, int k, int *needs_prepare);   // which kernel launch_spmm runs for this k (kPlan* in fs_kernels.hip)
+bool spmm_reads_plain_csr(const DeviceCsr &A, int k);   // launch_spmm would run a kernel that reads the plain CSR arrays (row kernel, MFMA)
 int launch_cbcsr(const fs_cbcsr_s &A, double *y, const double *x, hipStream_t s);
 int spmv_choice(const DeviceCsr &A, const Options &o);   // 7 two-pass, 8 LDS-staged, 6 L2-tiled, 2 lanes per row, 1 chunk-streaming
 int spmv_part_bounds(DeviceCsr &A, int nparts, const int **rows_out, const int **units_out, int *kind_out = nullptr, bool *cut_out = nullptr);

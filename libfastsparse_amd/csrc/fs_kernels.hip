@@ -1049,6 +1049,13 @@ int spmm_plan(const DeviceCsr &A, int k, int *needs_prepare)
   return want == 4 && !o.strict_order ? kPlanMfma : kPlanRow;
 }
 
+// a k-column product on A would read the plain CSR arrays right now (the row kernel, the matrix-core experiment)
+bool spmm_reads_plain_csr(const DeviceCsr &A, int k)
+{
+  const int plan = spmm_plan(A, k, nullptr);
+  return plan == kPlanRow || plan == kPlanMfma;
+}
+
 static int spmm_scratch_alloc(DeviceCsr &A, int k)      // prepare_spmm only
 {
   int64_t ldx, ldy;

@@ -372,3 +372,94 @@ def exact_system(m=3, lam=1.0, F=300, seed=16, nrow=None):
     B[0::2, 0], B[1::2, 1] = b[0::2], b[1::2] * 0.5
     return System(f"exact_m{m}_F{F}" + ("_norows" if nrow == 0 else ""), F * m if nrow is None else nrow, F, rows, cols, None,
                   b, B, lam, 1e-6)
+
+
+class ExactFamily:
+    """exact_system and what goes with it, for solves that are exact under ANY order of additions (the long-lived-handle walks run
+    them in whatever mode the option flips have left).  A'A = d I with columns on disjoint rows and d + lam = c a power of two:
+      binary   d = 3, lam = 1, c = 4;   valued   the same pattern with values +-2, so that v * v is 4: d = 12, lam = 4, c = 16
+    b and every column of a panel are dyadic with few bits, so A p, A'(A p), q + lam p = c p and every dot are exact; alpha is a
+    power of two (1 / c without a preconditioner, 1 with Jacobi, 2 / c with the caller's diagonal c / 2), x = b / c, r = +0.0.
+      diag     the caller's diagonal: c / 2 everywhere (a power of two that is not Jacobi's; a diagonal that varies along j would make
+               r inexact after the first step)
+      x0       "exact" b / c: done before the first iteration;  "other" 2 b / c: r = -b, one pass
+      ladders  every d + lambda_i a power of two: w = 1 + sigma_i alpha = (d + lambda_i) / c is one, so den, zn, ratio, a_i are exact
+      B2       fs_cg2: +-2^a on 256 rows and +-2^a' on 64 other rows: the column norms are powers of two, R = B / norm is dyadic
+    tests/test_lifecycle_model.py runs every solver's model on all of this with the device's sums and with serial sums and asserts
+    equal bits: what fails there is not used."""
+
+    def __init__(self, valued=False, F=2000, seed=23):
+        rng = np.random.default_rng([seed, int(valued)])
+        s = exact_system(m=3, lam=4.0 if valued else 1.0, F=F, seed=seed)
+        if valued:
+            s.vals = np.where(rng.uniform(size=s.rows.size) < 0.5, -2.0, 2.0)
+            s.name += "_valued"
+        self.s, self.valued, self.F = s, valued, F
+        self.d = 12.0 if valued else 3.0
+        self.c = self.d + s.lam
+        self.diag = np.full(F, self.c / 2)
+        top = [2.0 ** e - self.d for e in range(int(np.log2(self.c)) + 1, int(np.log2(self.c)) + 9)]
+        self.ladders = {"m1": [s.lam], "m3": [top[0], s.lam, s.lam],
+                        "m16": [top[1], s.lam, top[0], top[7], s.lam, top[2], top[3], top[0], top[4], s.lam, top[5], top[6], top[2], top[7],
+                                top[1], top[4]]}
+        B2 = np.zeros((F, 2))
+        at = rng.permutation(F)[:320]
+        B2[at[:256], 0] = np.where(rng.uniform(size=256) < 0.5, -0.125, 0.125)
+        B2[at[256:], 1] = np.where(rng.uniform(size=64) < 0.5, -4.0, 4.0)
+        self.B2 = B2
+        self._signs = np.where(rng.uniform(size=(F, 32)) < 0.5, -1.0, 1.0)
+
+    def panel(self, k):
+        """dyadic B (F, k): column j is b with signs of its own times 2^(j % 5 - 2); from k >= 2 column k // 2 is zero (frozen from
+        the start), from k >= 8 the last one too"""
+        B = self.s.b[:, None] * self._signs[:, :k] * 2.0 ** (np.arange(k) % 5 - 2)[None, :]
+        if k >= 2:
+            B[:, k // 2] = 0.0
+        if k >= 8:
+            B[:, k - 1] = 0.0
+        return np.ascontiguousarray(B)
+
+    def x0(self, B, how):
+        """how: "exact", "other", or "mixed" (panels: the columns take turns -- exact, other, a cold column's zeros)"""
+        B = np.asarray(B, np.float64)
+        if how == "exact":
+            return B / self.c
+        if how == "other":
+            return B * (2.0 / self.c)
+        X0 = np.zeros(B.shape)
+        X0[:, 0::3], X0[:, 1::3] = B[:, 0::3] / self.c, B[:, 1::3] * (2.0 / self.c)
+        return X0
+
+    def a_csr(self):
+        order = np.argsort(self.s.rows, kind="stable")
+        return _csr_of(self.s.nrow, self.s.rows[order], self.s.cols[order], None if self.s.vals is None else self.s.vals[order])
+
+    def t_csr(self):
+        """A' with every row in the caller's entry order, as fs_coo_create(ncol, nrow, cols, rows) holds it"""
+        order = np.argsort(self.s.cols, kind="stable")
+        return _csr_of(self.s.ncol, self.s.cols[order], self.s.rows[order], None if self.s.vals is None else self.s.vals[order])
+
+    def products(self):
+        """(A p, A' y, A P, A' Y) by bincount: exact on this data, so the order of its additions is nobody's business"""
+        s = self.s
+        w = 1.0 if s.vals is None else s.vals
+        am = lambda p: np.bincount(s.rows, weights=w * np.asarray(p, np.float64)[s.cols], minlength=s.nrow)
+        atm = lambda y: np.bincount(s.cols, weights=w * np.asarray(y, np.float64)[s.rows], minlength=s.ncol)
+        two = lambda f, n: (lambda Pm: np.stack([f(np.asarray(Pm).reshape(n, 2)[:, 0]), f(np.asarray(Pm).reshape(n, 2)[:, 1])], 1))
+        return am, atm, two(am, s.ncol), two(atm, s.nrow)
+
+
+def _csr_of(nrow, rows, cols, vals):
+    rp = np.zeros(nrow + 1, np.int32)
+    np.cumsum(np.bincount(rows, minlength=nrow), out=rp[1:])
+    return rp, np.ascontiguousarray(cols, np.int32), None if vals is None else np.ascontiguousarray(vals, np.float64)
+
+
+_FAMILIES = {}
+
+
+def exact_family(valued=False, F=2000, seed=23):
+    key = (bool(valued), F, seed)
+    if key not in _FAMILIES:
+        _FAMILIES[key] = ExactFamily(*key)
+    return _FAMILIES[key]

@@ -5,6 +5,16 @@ include/fastsparse_hip.h: products (one vector, k columns, A'A, in parts, host v
 release_csr / restore_csr / download, option flips, stream changes, handles destroyed and created mid-walk.  The data are the
 exactly summable sets of tests/_exact.py, so ONE bar -- equality of bits -- serves every mode and every order of additions.
 
+Solver pairs: next to these handles a walk keeps two pairs (A, At) of SEPARATE handles, as fs_cg takes them (At made from the
+transposed arrays), which live through the same operations and, besides, through fs_gram_diag, fs_cg, fs_cg2, fs_pcg, fs_mscg and
+fs_pcgn.  One pair holds a system of _cg_model.ExactFamily (binary, or its twin with values +-2), on which every solve is exact in
+whatever mode the flips have left; the other the general system binary_F257, for solves under strict_order that are compared with
+the models bit for bit (x, counts, info and the state of the fs_debug_last_*_state hooks).  Products on the pairs use
+integer-valued vectors.  After every solver operation: guards, inputs unchanged, the expected bits -- or, on an error, x still its
+prefill: "raised before anything is written" --, the options and fs_matrix_spmv_kernel as before, fs_matrix_device_bytes as the
+header says, the next product on either handle exact.  Half of the solves run right after poison_heap, which fills freed device
+memory of the sizes the solve will ask for with a tagged NaN: a work vector read before it is written shows as that tag in x.
+
 Guarded vectors: every vector handed to the library (x, u, X, U, y, z, Y, Z, tmp, the arrays of a borrowed matrix, the host
 vectors of fs_spmv_host) lies inside a larger allocation of its own, with at least GUARD doubles of a quiet NaN on both sides
 whose payload names the vector.  After EVERY operation: the guards of all vectors are untouched, the inputs are unchanged, the
@@ -20,13 +30,18 @@ which is how the harness is shown to have teeth without a GPU.
 
 Replay: a WalkFailure carries data set, copy, seed, the failing step and the last 20 log lines; run_walk(..., upto=N) replays
 the first N steps of the same seed.  Nothing is retried: the first failing check ends the walk."""
+import collections
 import contextlib
 import re
 import zlib
 
 import numpy as np
 
+import _cg_model as M
 import _exact as E
+import _mscg_model as S
+import _pcg_model as P
+import _pcgn_model as N
 
 GUARD = 4096                        # doubles on either side of a vector: 32 KiB, wider than one 1024-thread store of doubles
 FS_OK, FS_ERR_ARG, FS_ERR_NO_TRANSPOSE, FS_ERR_RELEASED = 0, -2, -4, -5
@@ -46,7 +61,13 @@ AUTO = "auto"
 
 OPS = {"spmv": 10, "spmv_t": 10, "spmm": 12, "spmm_t": 12, "ata": 6, "spmv_part": 12, "spmm_part": 5, "spmv_host": 3, "spmv_t_host": 3,
        "dev_then_host": 3, "prepare": 6, "release_prepared": 4, "prepare_roundtrip": 2, "release_csr": 5, "restore_csr": 5, "download": 2,
-       "flip": 10, "stream": 4, "churn": 2, "build_transpose": 3, "bad_arg": 2}
+       "flip": 10, "stream": 4, "churn": 2, "build_transpose": 3, "bad_arg": 2,
+       # on the handles of a solver pair only (elsewhere their weight is 0)
+       "gram_diag": 5, "cg": 6, "cg2": 5, "pcg": 8, "mscg": 5, "pcgn": 8, "solve_strict": 8, "solve_bad_arg": 4}
+SOLVER_OPS = ("gram_diag", "cg", "cg2", "pcg", "mscg", "pcgn", "solve_strict", "solve_bad_arg")
+EXACT_ONLY = ("cg", "cg2", "pcg", "mscg", "pcgn")      # solves that need the exact family
+PCGN_KS = (1, 2, 3, 4, 5, 8, 16, 17, 32)
+POISON_TAG = 0x7E57AB1E                                # the tag of poison_heap's NaN
 
 
 class WalkFailure(AssertionError):
@@ -158,7 +179,7 @@ class TorchMem:
         return v.view(self.t.int32)
 
 
-TAGS = {}                           # tag -> name of the guarded vector (for the message of a guard value found in a sum)
+TAGS = {POISON_TAG: "poison (solver work space read before it was written)"}     # tag -> name, for a guard value found in a sum
 
 
 class Guarded:
@@ -265,6 +286,155 @@ def mid_size():
     return E.wide_range(seed=21, nrow=140000, ncol=40000, name="wide_range_mid")
 
 
+# ---- the systems of the solver pairs and the models of their solves -----------------------------------------------------------
+class PairSystem:
+    """a system of _cg_model with the CSR of A and of A' as the pair's two handles hold them, the products the models run on
+    (exact bincounts for the exact family, the oracle's storage-order sums for the general system) and, per handle, a Data with
+    integer-valued vectors for the walk's products"""
+    def __init__(self, kind, valued=False):
+        self.kind = kind
+        if kind == "exact":
+            self.fam = M.exact_family(valued)
+            self.s = self.fam.s
+            self.a_csr, self.t_csr = self.fam.a_csr(), self.fam.t_csr()
+            self.products = self.fam.products()
+        else:
+            self.fam = None
+            self.s = M.systems(large=False)["binary_F257"]
+            self.a_csr, self.t_csr = self.s.a_csr(), self.s.t_csr_coo()
+            self.products = M.csr_products(self.s.nrow, self.s.ncol, self.a_csr, self.t_csr)
+        self.name = self.s.name
+        self.data = tuple(self._data(side) for side in (0, 1))
+
+    def _data(self, side):
+        rp, cc, vv = (self.a_csr, self.t_csr)[side]
+        nrow, ncol = (self.s.nrow, self.s.ncol) if side == 0 else (self.s.ncol, self.s.nrow)
+        rng = np.random.default_rng([31, side, zlib.crc32(self.name.encode())])
+        ints = lambda n: rng.integers(-512, 513, n).astype(np.float64)
+        cols = [ints(ncol) for _ in range(NC)]
+        d = E.Data(f"{self.name}_{'At' if side else 'A'}", nrow, ncol, np.repeat(np.arange(nrow), np.diff(rp)), cc, vv, cols[0], ints(nrow),
+                   lambda j: cols[j])
+        d.system = self
+        return d
+
+
+_PAIR_SYSTEMS = {}
+
+
+def pair_system(kind, valued=False):
+    key = (kind, bool(valued) and kind == "exact")
+    if key not in _PAIR_SYSTEMS:
+        _PAIR_SYSTEMS[key] = PairSystem(*key)
+    return _PAIR_SYSTEMS[key]
+
+
+Solved = collections.namedtuple("Solved", "x iters infos state extra")     # x: (F,), (F, k) or (m, F); extra: shifts / columns
+_SOLVED = {}
+
+
+def _key(a):
+    return None if a is None else hash(np.ascontiguousarray(a, np.float64).tobytes())
+
+
+def solve_model(ps, solver, b, lam, tol, max_iter=0, precond=P.PRECOND_NONE, x0=None, diag=None, lams=None, tree="device"):
+    """the model's solve (tests/_cg_model.py, _pcg_model.py, _mscg_model.py, _pcgn_model.py) of a pair's system; kept by its
+    arguments: the walk and the stand-in ask for the same solves again and again"""
+    F = ps.s.ncol
+    key = (ps.name, solver, _key(b), float(lam), float(tol), max_iter, precond, _key(x0), _key(diag), None if lams is None else tuple(lams), tree)
+    if key in _SOLVED:
+        return _SOLVED[key]
+    am, atm, am2, atm2 = ps.products
+    dinv = None
+    if precond == P.PRECOND_JACOBI:
+        dinv = P.dinv_of(P.gram_diag(ps.t_csr, lam))
+    elif precond == P.PRECOND_DIAG:
+        dinv = P.dinv_of(diag)
+    if solver == "cg":
+        r = M.cg(F, am, atm, b, lam, tol, tree)
+        out = Solved(r.x, [r.iterations], None, r.state, None)
+    elif solver == "cg2":
+        r = M.cg2(F, am2, atm2, np.asarray(b).reshape(F, 2), lam, tol, tree)
+        out = Solved(r.x, [r.iterations], None, r.state, None)
+    elif solver == "pcg":
+        r = P.pcg(F, am, atm, b, lam, tol, max_iter, dinv, x0, tree)
+        out = Solved(r.x, [r.iterations], [N.info_of(r)], r.state, None)
+    elif solver == "mscg":
+        r = S.mscg(F, am, atm, b, lams, tol, max_iter, tree)
+        out = Solved(r.X, [i.iterations for i in r.infos], list(r.infos), r.state, r.shifts)
+    else:
+        B = np.asarray(b, np.float64).reshape(F, -1)
+        cols = [solve_model(ps, "pcg", np.ascontiguousarray(B[:, j]), lam, tol, max_iter, precond,
+                            None if x0 is None else np.ascontiguousarray(np.asarray(x0).reshape(F, -1)[:, j]), diag, None, tree)
+                for j in range(B.shape[1])]
+        out = Solved(np.stack([c.x for c in cols], 1), [c.iters[0] for c in cols], [c.infos[0] for c in cols], cols[0].state,
+                     [c.state for c in cols])
+    _SOLVED[key] = out
+    return out
+
+
+def exact_cases(fam):
+    """every solve the walk runs on the exact family: (solver, what, keyword arguments of solve_model)"""
+    s = fam.s
+    out = [("cg", "fs_cg", dict(b=s.b)), ("cg2", "fs_cg2", dict(b=fam.B2.reshape(-1)))]
+    for pname, precond in (("none", P.PRECOND_NONE), ("jacobi", P.PRECOND_JACOBI), ("diag", P.PRECOND_DIAG)):
+        diag = fam.diag if precond == P.PRECOND_DIAG else None
+        for start in ("cold", "exact", "other", "b = 0"):
+            b = np.zeros(fam.F) if start == "b = 0" else s.b
+            x0 = fam.x0(s.b, start) if start in ("exact", "other") else None
+            out.append(("pcg", f"fs_pcg {pname} {start}", dict(b=b, precond=precond, diag=diag, x0=x0)))
+        for k in PCGN_KS:
+            B = fam.panel(k)
+            for start in ("cold", "mixed"):
+                out.append(("pcgn", f"fs_pcgn k {k} {pname} {start}",
+                            dict(b=B.reshape(-1), precond=precond, diag=diag, x0=fam.x0(B, "mixed").reshape(-1) if start == "mixed" else None)))
+    for name, lams in fam.ladders.items():
+        out.append(("mscg", f"fs_mscg {name}", dict(b=s.b, lams=list(lams))))
+    return out
+
+
+_STRICT = {}
+
+
+def strict_cases(ps):
+    if ps.name not in _STRICT:
+        _STRICT[ps.name] = _strict_cases(ps)
+    return _STRICT[ps.name]
+
+
+def _strict_cases(ps):
+    """the solves under strict_order on the general system: caps of at most 12, so that columns and shifts freeze at different
+    iterations or meet the cap; fs_cg at a tol its model meets within about 20 iterations"""
+    s = ps.s
+    i = np.arange(s.ncol, dtype=np.float64)
+    B5 = np.stack([s.b, s.b, np.zeros(s.ncol), s.b * 1.5 + np.sin(i * 0.22 + 0.6), np.cos(i * 0.05) * 1e-3], 1)
+    X3 = np.stack([0.25 * np.sin(i * 0.37 + 0.2), np.zeros(s.ncol), 0.125 * np.cos(i * 0.11)], 1)
+    dg = P.gram_diag(ps.t_csr, s.lam) * (1.0 + 0.5 * np.cos(i * 1.7)) + 0.125
+    # warm columns that freeze at different iterations: cold, four iterations in, zero, done before the first product, cold
+    X5 = np.zeros(B5.shape)
+    X5[:, 1] = solve_model(ps, "pcg", s.b, s.lam, 1e-4, 4, P.PRECOND_JACOBI).x
+    X5[:, 3] = solve_model(ps, "pcg", np.ascontiguousarray(B5[:, 3]), s.lam, 1e-6, 0, P.PRECOND_JACOBI).x
+    return [("cg", "fs_cg", dict(b=s.b, tol=1e-4)),
+            ("pcg", "fs_pcg jacobi cap 12", dict(b=s.b, precond=P.PRECOND_JACOBI, max_iter=12, tol=s.tol)),
+            ("pcg", "fs_pcg none warm cap 5", dict(b=s.b, x0=X3[:, 0], max_iter=5, tol=s.tol)),
+            ("mscg", "fs_mscg ladder of 8 cap 12", dict(b=s.b, lams=[s.lam * f for f in (1e3, 10.0, 1e6, 1.0, 30.0, 1e4, 3.0, 1.0)], max_iter=12, tol=1e-6)),
+            ("pcgn", "fs_pcgn k 5 jacobi warm cap 12", dict(b=B5.reshape(-1), precond=P.PRECOND_JACOBI, x0=X5.reshape(-1), max_iter=12, tol=1e-4)),
+            ("pcgn", "fs_pcgn k 3 diag warm cap 4", dict(b=np.ascontiguousarray(B5[:, 2:5]).reshape(-1), precond=P.PRECOND_DIAG, diag=dg,
+                                                         x0=X3.reshape(-1), max_iter=4, tol=s.tol))]
+
+
+def work_space(solver, F, Nrow, k=1, pre=False, nslots=0):
+    """the doubles of every device buffer a solve asks for (include/fastsparse_hip.h: 3 k F + k N, F for dinv, one F per shift with
+    sigma != 0, 2048 k and 512 for fs_pcgn; the partial sums kRedBlocks * 3, the sums and st[] of every solver)"""
+    out = [k * F, k * F, k * F, k * Nrow, M.RED_BLOCKS * 3, 4, M.CG_STATE_DOUBLES]
+    if pre:
+        out.append(F)
+    if solver == "mscg":
+        out += [((F + 1) & ~1) * nslots, S.MAX_SHIFTS * S.MS_STRIDE]
+    if solver == "pcgn":
+        out.append(2 * M.RED_BLOCKS * k + N.MAX_RHS * N.PN_STRIDE)
+    return [n for n in out if n > 0]
+
+
 # ---- the model of a handle -----------------------------------------------------------------------------------------------
 class Model:
     """what include/fastsparse_hip.h promises about one handle, from the calls made on it"""
@@ -336,11 +506,19 @@ class Handle:
         self.nparts_seen = set()
         self.base_bytes = None
         self.prove = False              # the last call was refused: the next product must be exact
+        self.pair = None                # the solver pair this handle is half of
+
+
+class Pair:
+    """a solver pair: the handle of A and the handle of A', two separate handles as fs_cg takes them"""
+    def __init__(self, ps, HA, HT):
+        self.ps, self.A, self.At = ps, HA, HT
+        self.saved_diag = None          # the d of the last successful fs_gram_diag(At, the system's lambda)
 
 
 class Walk:
-    def __init__(self, backend, data, copy, seed, steps=150, upto=None, copies=None, kmax=17, nc=NC, nhandles=3, ata_cols=3):
-        self.b, self.data, self.copy, self.seed = backend, data, copy, seed
+    def __init__(self, backend, data, copy, seed, steps=150, upto=None, copies=None, kmax=17, nc=NC, nhandles=3, ata_cols=3, solvers=True):
+        self.b, self.data, self.copy, self.seed, self.solvers = backend, data, copy, seed, solvers
         self.steps = steps if upto is None else min(steps, upto)
         self.rng = np.random.default_rng([seed, zlib.crc32(f"{data.name}/{copy}".encode())])     # every (set, copy) walks its own way
         self.copies = list(copies or backend.copies())
@@ -352,7 +530,9 @@ class Walk:
         self.o = {}                     # the flippable options as the walk has set them
         self.neutral = {}
         self.counts = {"ops": {}, "status": {}, "k": [set(), set()], "nparts": {}, "host_behind_device": 0, "restore": set(),
-                       "recovered": 0, "part_between": 0}
+                       "recovered": 0, "part_between": 0, "poison_seen": 0, "poison_probed": 0, "poisoned": 0, "solves": {},
+                       "solver_status": {}}
+        self.pairs = []
 
     # -- bookkeeping ----
     def fail(self, kind, msg):
@@ -385,12 +565,14 @@ class Walk:
             H.prove = True
 
     # -- handles ----
-    def create(self, first=False, with_t=None, borrow=None):
+    def create(self, first=False, with_t=None, borrow=None, data=None):
         i = self.made
         self.made += 1
-        d = self.data
+        d = self.data if data is None else data
         if first:
             copy, pattern = self.copy, False
+        elif data is not None:              # half of a solver pair: any copy the builder makes of it, no built transpose
+            copy, pattern, with_t = self.copies[int(self.rng.integers(len(self.copies)))], False, False
         else:
             copy = self.copies[int(self.rng.integers(len(self.copies)))]
             pattern = i == 1 or bool(self.rng.integers(3) == 0)      # at least one handle of every walk is pattern-only
@@ -407,7 +589,7 @@ class Walk:
         H.vec["tmp"] = Guarded(self.b.mem, f"tmp of {H.name}", d.nrow)
         arrays = self.arrays_for(H, 0) if borrow else r.csr[0]
         with self.b.options(**self.neutral), self.b.options(**self.b.creation_options(copy)):
-            H.A = self.b.create(d, copy, arrays, borrow)
+            H.A = self.b.create(d, copy, arrays, borrow, must=data is None)
             H.model = Model(False)
             self.learn_side(H, 0)
             if with_t:
@@ -693,8 +875,9 @@ class Walk:
         rc, n = self.call(H.A.release_prepared, k)
         self.expect(H, "fs_matrix_release_prepared", rc, FS_OK)
         m = H.model
-        gone = set(self.ks) if k == 0 else {2, 3} if k in (2, 3) else {k}
         for side in (0, 1) if m.has_t else (0,):
+            # k = 2 and 3 share the two-column two-pass copy; the column-major scratch of an LDS-staged copy goes k by k
+            gone = set(self.ks) if k == 0 else {2, 3} if k in (2, 3) and m.kept[side] != 8 else {k}
             m.prepared[side] -= gone
             for kk in sorted(gone):
                 plan = self.b.spmm_plan(H.A, kk, side)
@@ -784,6 +967,15 @@ class Walk:
         self.note(f"stream {self.b.stream_index()}")
 
     def op_churn(self, H):
+        if H.pair is not None:              # a pair goes and comes as a whole; the exact one comes back as its twin
+            pair = H.pair
+            self.note(f"destroy the pair {pair.A.name}, {pair.At.name}")
+            self.destroy(pair.A)
+            self.destroy(pair.At)
+            self.pairs.remove(pair)
+            self.check_all(None)
+            self.create_pair(pair.ps.kind, valued=not pair.ps.fam.valued if pair.ps.fam else False)
+            return
         self.note(f"destroy {H.name}")
         self.destroy(H)
         self.check_all(None)
@@ -817,6 +1009,252 @@ class Walk:
         self.check_all(H, [(gi, wi, "x")])
         if not go.mem.all_bits(go.view, go.prefill):
             self.fail("not exact", f"a refused call wrote into {go.name}")
+
+    # -- solver pairs ----
+    def create_pair(self, kind, valued=False):
+        ps = pair_system(kind, valued)
+        HA, HT = self.create(data=ps.data[0]), self.create(data=ps.data[1])
+        pair = Pair(ps, HA, HT)
+        HA.pair = HT.pair = pair
+        F = ps.s.ncol
+        for role, cap in (("x", max(N.MAX_RHS * F, S.MAX_SHIFTS * (F + 3))), ("b", N.MAX_RHS * F), ("diag", F), ("d", F)):
+            HA.vec["solve " + role] = Guarded(self.b.mem, f"{role} of the solvers on {HA.name}", cap)
+        self.pairs.append(pair)
+        return pair
+
+    def pair_state(self, pair):
+        return ({n: self.b.get_option(n) for n in FLIPS}, [self.b.kernel_code(h.A, 0) for h in (pair.A, pair.At)],
+                [h.A.device_bytes() for h in (pair.A, pair.At)])
+
+    def poison(self, pair, sizes):
+        seen, probed = self.b.poison_heap(sizes)
+        self.counts["poison_seen"] += seen
+        self.counts["poison_probed"] += probed
+        self.counts["poisoned"] += 1
+        self.log.append(f"{self.step:4d} poison_heap({sorted(set(sizes))}): the probe saw {seen} of {probed}")
+
+    def products_status(self, pair, k, jacobi=False):
+        """what the header promises for a solve whose products take k columns, from the state of the two handles: FS_ERR_RELEASED for
+        Jacobi on a released At, from fs_matrix_prepare for a k that still needs the plain arrays of a released side, and from
+        the products themselves.  For k >= 2 the last is known once the solver's own prepare has settled the plan: None then"""
+        if jacobi and pair.At.model.released[0]:
+            return FS_ERR_RELEASED
+        if k == 1:
+            return FS_ERR_RELEASED if any(h.model.product(0, self.o) != FS_OK for h in (pair.A, pair.At)) else FS_OK
+        for h in (pair.A, pair.At):
+            if h.model.released[0] and (self.b.spmm_needs(h.A, k, 0, {}) & 3):
+                h.model.prepared[0].add(k)                  # (refused half way: see op_prepare)
+                return FS_ERR_RELEASED
+            h.model.prepared[0].add(k)
+        return None
+
+    def run_solver(self, pair, solver, what, kw, want_x=None, x0=None, ldx=None, off8=None, k=1, jacobi=False, want=None, poison=None,
+                   null=(), raw=None):
+        """one solver call on the pair inside the frame of checks.  kw: the arguments of solve_model (b, lam, tol, max_iter, precond,
+        x0, diag, lams); want: the status, or None for what products_status says; raw: arguments of backend.solve that replace
+        the ones derived from kw (the bad arguments).  Returns (status, Solved or None)."""
+        b_, mem, s = self.b, self.b.mem, pair.ps.s
+        F, hA = s.ncol, pair.A
+        m = len(kw["lams"]) if solver == "mscg" else 1
+        ldx = F if ldx is None else ldx
+        off8 = int(self.rng.integers(2)) if off8 is None else off8
+        nx = (m - 1) * ldx + F if solver == "mscg" else F * (2 if solver == "cg2" else k)
+        gx, gb, gd = hA.vec["solve x"], hA.vec["solve b"], hA.vec["solve diag"]
+        before_x = np.full(nx, PREFILLS["nan"], np.int64).view(np.float64)
+        if x0 is not None:
+            before_x = np.array(x0, np.float64).reshape(-1)
+        mem.put(gx.place(nx, off8), before_x)
+        b = np.ascontiguousarray(kw["b"], np.float64).reshape(-1)
+        mem.put(gb.place(b.size, off8 if solver in ("pcgn", "cg2") else int(self.rng.integers(2))), b)
+        ins = [(gb, b, "b")]
+        diag = kw.get("diag")
+        if diag is not None:
+            mem.put(gd.place(F, int(self.rng.integers(2))), diag)
+            ins.append((gd, diag, "diag"))
+        args = dict(lam=kw.get("lam", s.lam), tol=kw.get("tol", s.tol), max_iter=kw.get("max_iter", 0), precond=kw.get("precond", P.PRECOND_NONE),
+                    warm=x0 is not None, diag=None if diag is None else gd.view, k=m if solver == "mscg" else k, lams=kw.get("lams", ()), ldx=ldx, null=null)
+        args.update(raw or {})
+        if want is None:
+            want = self.products_status(pair, 2 if solver == "cg2" else k, jacobi)
+        kk = 2 if solver == "cg2" else k                    # the columns of the solve's products
+        needs = [self.b.spmm_needs(h.A, kk, 0, {}) if kk >= 2 else 0 for h in (pair.A, pair.At)]
+        before = self.pair_state(pair)
+        if poison if poison is not None else bool(self.rng.integers(2)):
+            nslots = len([v for v in kw.get("lams", ()) if v != min(kw["lams"])])
+            self.poison(pair, work_space(solver, F, s.nrow, 2 if solver == "cg2" else k, args["precond"] != P.PRECOND_NONE, nslots))
+        self.note(f"{what} on {hA.name} / {pair.At.name}, x {nx} doubles 8 * {off8} off, ldx {ldx}")
+        self.counts["solves"][solver] = self.counts["solves"].get(solver, 0) + 1
+        rc, res = self.call(b_.solve, solver, pair.A.A, pair.At.A, gx.view, gb.view, **args)
+        if want is None:                                    # the solver's prepare went through: the plans say what the products need
+            plans = [b_.spmm_plan(h.A, kk, 0) for h in (pair.A, pair.At)]
+            want = FS_ERR_RELEASED if any(h.model.multi(0, pl) != FS_OK for h, pl in zip((pair.A, pair.At), plans)) else FS_OK
+        self.expect(hA, what, rc, want)
+        self.counts["solver_status"][(solver, want)] = self.counts["solver_status"].get((solver, want), 0) + 1
+        self.check_all(hA, ins)
+        got = mem.get(gx.view)
+        model = None
+        if rc != FS_OK:
+            if not E.bits_equal(got, before_x):
+                self.fail("x written", f"{what} returned {STATUS_NAMES.get(rc, rc)} and wrote to x all the same: {E.first_mismatch(got, before_x)}")
+        else:
+            model = solve_model(pair.ps, solver, b, args["lam"], args["tol"], args["max_iter"], args["precond"], x0, diag, kw.get("lams"))
+            full = before_x.copy()
+            if solver == "mscg":
+                gaps = np.ones(nx, bool)
+                for i in range(m):
+                    full[i * ldx:i * ldx + F] = model.x[i]
+                    gaps[i * ldx:i * ldx + F] = False
+                if not np.array_equal(got.view(np.int64)[gaps], before_x.view(np.int64)[gaps]):
+                    self.fail("gap written", f"{what}: a gap between the vectors of X (ldx {ldx}, F {F}) was written, first at "
+                              f"{int(np.flatnonzero(gaps & (got.view(np.int64) != before_x.view(np.int64)))[0])}")
+            else:
+                full = np.ascontiguousarray(model.x).reshape(-1)
+            if not E.bits_equal(got, full):
+                self.wrong(gx, got, full, what)
+            if res["iters"] != model.iters:
+                self.fail("not exact", f"{what}: iterations {res['iters']}, the model {model.iters}")
+            for j, (g, w) in enumerate(zip(res["infos"] or [], model.infos or [])):
+                if (g[0], g[1]) != (w.iterations, w.converged) or not (M.same_bits(g[2], w.rnorm)[0] and M.same_bits(g[3], w.bnorm)[0]):
+                    self.fail("not exact", f"{what}: fs_pcg_info[{j}] = {g}, the model {tuple(w)}")
+        after = self.pair_state(pair)
+        if after[0] != before[0]:
+            self.fail("option", f"{what} changed options: {[(n, before[0][n], after[0][n]) for n in FLIPS if before[0][n] != after[0][n]]}")
+        if after[1] != before[1]:
+            self.fail("bookkeeping", f"fs_matrix_spmv_kernel of the pair was {before[1]} before {what} and is {after[1]} after it (a scope "
+                      "that was not given back?)")
+        for h, b0, b1, nd in zip((pair.A, pair.At), before[2], after[2], needs):
+            grew = rc == FS_OK and kk >= 2 and (nd & 5)
+            if b1[2] < b0[2] or (b1[2] != b0[2] and not (kk >= 2 and (nd & 5))) or b1[1] < b0[1] or b1[1] > h.base_bytes[1] + self.b.lazy_growth(h.A):
+                self.fail("device bytes", f"{h.name} reported {b0} before {what} and {b1} after it (prepare needs {nd}, after creation {h.base_bytes})")
+            if grew and (self.b.spmm_needs(h.A, kk, 0, {}) & 5):
+                self.fail("bookkeeping", f"after {what} fs_matrix_prepare({kk}) still has work on {h.name}: the solve did not do its one-time work")
+        pair.A.prove = pair.At.prove = True                 # the next product on either handle: exact
+        return rc, model
+
+    def op_gram_diag(self, H):
+        pair = H.pair
+        lam = float((0.0, 0.75, pair.ps.s.lam)[int(self.rng.integers(3))])
+        gd = pair.A.vec["solve d"]
+        F = pair.ps.s.ncol
+        self.b.mem.fill_bits(gd.place(F, int(self.rng.integers(2))), PREFILLS["nan"])
+        want = FS_ERR_RELEASED if pair.At.model.released[0] else FS_OK
+        before = self.pair_state(pair)
+        self.note(f"fs_gram_diag({pair.At.name}, {lam})")
+        rc, _ = self.call(self.b.gram_diag, pair.At.A, lam, gd.view)
+        self.expect(pair.At, "fs_gram_diag", rc, want)
+        self.counts["solver_status"][("gram_diag", want)] = self.counts["solver_status"].get(("gram_diag", want), 0) + 1
+        self.check_all(pair.A)
+        got = self.b.mem.get(gd.view)
+        if rc == FS_OK:
+            d = P.gram_diag(pair.ps.t_csr, lam)
+            if not E.bits_equal(got, d):
+                self.wrong(gd, got, d, f"fs_gram_diag lambda {lam}")
+            if lam == pair.ps.s.lam:
+                pair.saved_diag = d                         # the caller's diagonal of later FS_PRECOND_DIAG solves
+        elif not (got.view(np.int64) == PREFILLS["nan"]).all():
+            self.fail("x written", "the refused fs_gram_diag wrote to d")
+        if self.pair_state(pair) != before:
+            self.fail("bookkeeping", f"fs_gram_diag changed options, kernels or device bytes: {before} -> {self.pair_state(pair)}")
+
+    def exact_solve(self, H, solver, poison=None, pick=None):
+        pair = H.pair
+        fam = pair.ps.fam
+        cases = [c for c in exact_cases(fam) if c[0] == solver]
+        _, what, kw = cases[int(self.rng.integers(len(cases))) if pick is None else pick % len(cases)]
+        kw = dict(kw, lam=fam.s.lam, tol=fam.s.tol)
+        if kw.get("precond") == P.PRECOND_DIAG and pair.saved_diag is not None and self.rng.integers(2):
+            kw["diag"], what = pair.saved_diag, what + " (the diagonal of an earlier fs_gram_diag)"
+        k = kw["b"].size // fam.F if solver == "pcgn" else 1
+        ldx = fam.F + 3 * int(self.rng.integers(2)) if solver == "mscg" else None
+        return self.run_solver(pair, solver, what, kw, x0=kw.get("x0"), ldx=ldx, k=k, jacobi=kw.get("precond") == P.PRECOND_JACOBI, poison=poison)
+
+    def op_cg(self, H):
+        self.exact_solve(H, "cg")
+
+    def op_cg2(self, H):
+        self.exact_solve(H, "cg2")
+
+    def op_pcg(self, H):
+        self.exact_solve(H, "pcg")
+
+    def op_mscg(self, H):
+        self.exact_solve(H, "mscg")
+
+    def op_pcgn(self, H):
+        self.exact_solve(H, "pcgn")
+
+    def op_solve_strict(self, H, pick=None, poison=None):
+        """strict_order on through the walk's own flip (the Model knows), one solver on the general system against its model, x,
+        counts, info and the state of the debug hooks bit for bit; then the option as it was"""
+        pair = H.pair
+        saved = self.o["strict_order"]
+        self.flip("strict_order", 1)
+        try:
+            cases = strict_cases(pair.ps)
+            solver, what, kw = cases[int(self.rng.integers(len(cases))) if pick is None else pick % len(cases)]
+            k = kw["b"].size // pair.ps.s.ncol if solver == "pcgn" else 1
+            rc, model = self.run_solver(pair, solver, what + " under strict_order", kw, x0=kw.get("x0"), k=k,
+                                        jacobi=kw.get("precond") == P.PRECOND_JACOBI, poison=poison)
+            if rc == FS_OK:
+                bad = self.state_mismatch(solver, model, len(kw.get("lams", ())), k)
+                if bad:
+                    self.fail("not exact", f"{what} under strict_order, the state of the debug hooks: {bad}")
+        finally:
+            self.flip("strict_order", saved)
+        return rc
+
+    def state_mismatch(self, solver, model, m, k):
+        st = self.b.last_state(solver, m if solver == "mscg" else k)
+        if st is None:
+            return None
+        state, extra = st
+        bad = M.mismatch(np.zeros(0), np.zeros(0), None, None, state, model.state if solver != "pcgn" else None)
+        if bad or solver in ("cg", "pcg"):
+            return bad
+        if solver == "mscg":
+            return S.shifts_mismatch(extra, model.extra)
+        for j, want in enumerate(model.extra):              # fs_pcgn: the scalars of every column against its fs_pcg model
+            for key, name in (("rr", "rr"), ("bb", "bb"), ("stop", "stop"), ("rsq", "rz"), ("alpha", "alpha"), ("beta", "beta")):
+                if key in want and not M.same_bits(extra[j][name], want[key])[0]:
+                    return f"column {j} {name}: got {float(extra[j][name])!r} want {float(want[key])!r}"
+            if extra[j]["count"] != want["iter"] or extra[j]["converged"] != want["done"]:
+                return f"column {j}: count {extra[j]['count']} converged {extra[j]['converged']}, the model {want['iter']} {want['done']}"
+        return None
+
+    BAD_ARGS = [("pcg", "NULL A", dict(null=("A",))), ("mscg", "NULL At", dict(null=("At",))), ("pcgn", "NULL x", dict(null=("x",))),
+                ("cg", "NULL b", dict(null=("b",))), ("pcg", "NULL prm", dict(null=("prm",))), ("pcgn", "NULL prm", dict(null=("prm",))),
+                ("mscg", "NULL lambda", dict(null=("lambda",))), ("cg2", "NULL x", dict(null=("x",))),
+                ("cg", "A twice", dict(twice=True)), ("pcg", "A twice", dict(twice=True)), ("mscg", "A twice", dict(twice=True)),
+                ("pcgn", "A twice", dict(twice=True)), ("cg2", "A twice", dict(twice=True)),
+                ("pcgn", "k = 0", dict(k=0)), ("pcgn", "k = 33", dict(k=33)), ("mscg", "m = 0", dict(k=0)), ("mscg", "m = 17", dict(k=17)),
+                ("mscg", "ldx < F", dict(ldx=-1)), ("pcg", "tol < 0", dict(tol=-1e-8)), ("pcgn", "tol NaN", dict(tol=float("nan"))),
+                ("mscg", "tol NaN", dict(tol=float("nan"))), ("mscg", "tol < 0", dict(tol=-1.0)),
+                ("mscg", "lambda NaN", dict(lams=[1.0, float("nan"), 5.0])), ("mscg", "lambda inf", dict(lams=[float("inf"), 1.0, 5.0])),
+                ("pcg", "precond = 3", dict(precond=3)), ("pcgn", "precond = 3", dict(precond=3)),
+                ("pcg", "DIAG with NULL diag", dict(precond=P.PRECOND_DIAG)), ("pcgn", "DIAG with NULL diag", dict(precond=P.PRECOND_DIAG))]
+
+    def op_solve_bad_arg(self, H, pick=None):
+        pair = H.pair
+        s = pair.ps.s
+        solver, what, raw = self.BAD_ARGS[int(self.rng.integers(len(self.BAD_ARGS))) if pick is None else pick % len(self.BAD_ARGS)]
+        raw = dict(raw)
+        k = 3 if solver == "pcgn" else 1
+        i = np.arange(s.ncol * max(k, 2), dtype=np.float64)
+        kw = dict(b=(i % 7 - 3.0)[:s.ncol * (2 if solver == "cg2" else k)], lam=s.lam, tol=1e-6, max_iter=2)
+        if solver == "mscg":
+            kw["lams"] = [s.lam + 4.0, s.lam, s.lam + 12.0]
+            if "k" in raw or "lams" in raw:
+                raw.setdefault("lams", [s.lam] * 17)
+            if raw.get("ldx") == -1:
+                raw["ldx"] = s.ncol - 1
+        twice = raw.pop("twice", False)
+        if twice:
+            pair = Pair(pair.ps, pair.A, pair.A)            # At not of the transposed shape
+        try:
+            self.run_solver(pair, solver, f"fs_{solver} with {what}", kw, k=k, want=FS_ERR_ARG, raw=raw, null=raw.pop("null", ()))
+        finally:
+            H.pair.At.prove = True
+
 
     def recover(self, H):
         """the very next product on a handle that has just refused a call: exact.  Under the options of the moment where the model
@@ -858,6 +1296,10 @@ class Walk:
                 w[i] = 0.5
             if n == "churn" and (self.step < 10 or H is self.handles[0]):      # the copy the walk is named for stays to the end
                 w[i] = 0
+            if n in SOLVER_OPS:
+                kind = None if H.pair is None else H.pair.ps.kind
+                if kind is None or (kind == "exact" and n == "solve_strict") or (kind == "general" and n in EXACT_ONLY):
+                    w[i] = 0
         return names[int(self.rng.choice(len(names), p=w / w.sum()))]
 
     @contextlib.contextmanager
@@ -874,7 +1316,7 @@ class Walk:
             finally:
                 for h in list(self.handles):
                     h.A.close()
-                self.handles = []
+                self.handles, self.pairs = [], []
 
     def flip(self, name, value):
         self.note(f"option {name} = {value}")
@@ -888,6 +1330,9 @@ class Walk:
                 self.create(first=True)
                 for _ in range(self.nhandles - 1):
                     self.create()
+                if self.solvers:
+                    self.create_pair("exact", valued=bool(self.rng.integers(2)))
+                    self.create_pair("general")
                 for self.step in range(self.steps):
                     b.begin_step(self.step)
                     H = self.handles[int(self.rng.integers(len(self.handles) + 1)) % len(self.handles)]    # (the first one twice as often)
@@ -986,12 +1431,12 @@ class HipBackend:
         self.streams[self.cur].wait_event(ev)
         self.torch.cuda.set_stream(self.streams[self.cur])
 
-    def create(self, d, copy, arrays, borrow):
+    def create(self, d, copy, arrays, borrow, must=True):
         rp, cc, vv = arrays
         if not borrow:
             rp, cc, vv = (None if a is None else self.mem.const(a) for a in arrays)
         A = self.capi.Matrix.from_csr(d.nrow, d.ncol, rp, cc, vv, borrow=borrow)
-        if copy != AUTO:
+        if copy != AUTO and must:
             want = {"stream": 1, "two-pass": 7, "lds-staged": 8, "tiled": 6}[self.paths[copy][1]]
             assert self.kernel_code(A, 0) == want, (copy, self.kernel_code(A, 0))
         return A
@@ -1027,3 +1472,77 @@ class HipBackend:
                 assert self.L.fs_debug_two_pass_layout(A.h, side, out) == 0
                 n += 2 * int(out[5])
         return n
+
+    # -- the solvers ----
+    def gram_diag(self, At, lam, d):
+        self.capi.gram_diag(At, lam, d, self.stream())
+
+    def solve(self, solver, A, At, x, b, lam=0.0, tol=1e-6, max_iter=0, precond=0, warm=False, diag=None, k=1, lams=(), ldx=0, null=()):
+        """one solver call; null names arguments handed over as NULL.  {"iters": [...], "infos": [(iterations, converged, rnorm,
+        bnorm), ...] or None}; a negative status raises like every binding"""
+        C, L, capi = self.C, self.L, self.capi
+        pa, pt = None if "A" in null else A.h, None if "At" in null else At.h
+        px, pb = None if "x" in null else x.data_ptr(), None if "b" in null else b.data_ptr()
+        st = self.stream()
+        if solver in ("cg", "cg2"):
+            it = C.c_int(-1)
+            capi.check(getattr(L, "fs_" + solver)(pa, pt, px, pb, lam, tol, C.byref(it), st), "fs_" + solver)
+            return {"iters": [it.value], "infos": None}
+        prm = capi.PcgParams(tol, max_iter, precond, int(warm), None if diag is None else diag.data_ptr())
+        pp = None if "prm" in null else C.byref(prm)
+        n = 1 if solver == "pcg" else max(k, 1)
+        infos = (capi.PcgInfo * max(n, len(lams), 1))()
+        if solver == "pcg":
+            rc = L.fs_pcg(pa, pt, px, pb, lam, pp, infos, st)
+        elif solver == "pcgn":
+            rc = L.fs_pcgn(pa, pt, px, pb, k, lam, pp, infos, st)
+        else:
+            arr = None if "lambda" in null else (C.c_double * max(len(lams), 1))(*lams)
+            rc = L.fs_mscg(pa, pt, px, ldx, pb, k, arr, tol, max_iter, infos, st)
+        capi.check(rc, "fs_" + solver)
+        out = [(i.iterations, i.converged, i.rnorm, i.bnorm) for i in list(infos)[:n]]
+        return {"iters": [i[0] for i in out], "infos": out}
+
+    def last_state(self, solver, n):
+        """(st[] by name, the per-shift / per-column scalars by name) of the last solve, from the fs_debug_last_*_state hooks"""
+        C, L = self.C, self.L
+        L.fs_debug_last_cg_state.argtypes = [C.c_void_p]
+        st = np.full(M.CG_STATE_DOUBLES, np.nan)
+        assert L.fs_debug_last_cg_state(st.ctypes.data) == M.CG_STATE_DOUBLES
+        if solver == "cg":
+            return M.state_from_device(st, False), None
+        if solver == "pcg":
+            return P.state_from_device(st), None
+        hook = L.fs_debug_last_mscg_state if solver == "mscg" else L.fs_debug_last_pcgn_state
+        hook.argtypes = [C.c_void_p, C.c_int]
+        raw = np.full(32 * 16, np.nan)
+        stride = S.MS_STRIDE if solver == "mscg" else N.PN_STRIDE
+        assert hook(raw.ctypes.data, raw.size) == n * stride
+        if solver == "mscg":
+            return S.state_from_device(st), S.shifts_from_device(raw, n)
+        return P.state_from_device(st), N.state_from_device(raw, n)
+
+    def poison_heap(self, sizes):
+        """fs_device_alloc every size a solve is about to ask for and two neighbours of it, fill with a quiet NaN tagged as poison,
+        fs_device_free -- not through torch, whose allocator never hands memory back.  Then the probe: allocate the largest size
+        again and count the doubles that still carry the poison.  (doubles seen, doubles probed)"""
+        L = self.L
+        self.torch.cuda.synchronize()
+        want = sorted({n + d for n in sizes for d in (0, 2, 64)})
+        host = np.full(max(want), guard_bits(POISON_TAG), np.int64)
+        ptrs = []
+        for n in want:
+            p = L.fs_device_alloc(8 * n)
+            assert p, "fs_device_alloc failed"
+            ptrs.append(p)
+            assert L.fs_copy_to_device(p, host.ctypes.data, 8 * n) == 0
+        for p in reversed(ptrs):
+            L.fs_device_free(p)
+        n = max(sizes)
+        p = L.fs_device_alloc(8 * n)
+        assert p, "fs_device_alloc failed"
+        back = np.zeros(n, np.int64)
+        rc = L.fs_copy_to_host(back.ctypes.data, p, 8 * n)
+        L.fs_device_free(p)
+        assert rc == 0
+        return int((back == host[0]).sum()), n

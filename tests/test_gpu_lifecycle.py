@@ -3,8 +3,10 @@
 The other GPU tests run one fixed script on a fresh handle.  Here a handle lives through a walk of legal calls -- products of every
 kind, prepare / release, release_csr / restore_csr, option flips, stream changes, neighbours created and destroyed -- and after
 every operation the guards of all vectors are untouched, the inputs unchanged, the outputs exact, the statuses what the header
-promises and the bookkeeping what the debug hooks saw.  tests/test_lifecycle_model.py shows on a numpy stand-in that these checks
-catch the faults they are meant for, and that the seeds used here reach every operation."""
+promises and the bookkeeping what the debug hooks saw.  Two solver pairs (A, At) live through the same walks and through
+fs_gram_diag, fs_cg, fs_cg2, fs_pcg, fs_mscg and fs_pcgn, half of the solves on work space that was poisoned just before (see
+tests/_lifecycle.py).  tests/test_lifecycle_model.py shows on a numpy stand-in that these checks catch the faults they are meant
+for, and that the seeds used here reach every operation."""
 import ctypes as C
 
 import numpy as np
@@ -22,6 +24,7 @@ STEPS = 150
 SET_NAMES = LC.GPU_SET_NAMES           # (why these two: see there)
 COPIES = list(PATHS) + [LC.AUTO]
 # the mid-size set with panels of 32 rows: more generations of resident workgroups than the largest nparts
+POISON = {"seen": 0, "probed": 0, "poisoned": 0}       # what the probes of poison_heap saw, summed over this module's walks
 SMALL_PANELS = {"two-pass, panels of 32 rows": (dict(binning=2, ldsx=0, tiling=0, bin_rows=32), "two-pass"),
                 "lds-staged, panels of 32 rows": (dict(ldsx=2, binning=0, tiling=0, tile_rows=32), "lds-staged")}
 
@@ -46,6 +49,94 @@ def test_walks_are_exact_and_stay_inside_their_vectors(backend, name, copy):
     for seed in SEEDS:
         w = LC.run_walk(backend, d, copy, seed, steps=STEPS, copies=COPIES)
         assert sum(w.counts["ops"].values()) == STEPS
+        _count_poison(w)
+
+
+def _count_poison(w):
+    for k in POISON:
+        POISON[k] += w.counts["poison_" + k if k != "poisoned" else k]
+
+
+def test_solvers_on_poisoned_work_space(backend):
+    """every solver right behind poison_heap: freed device memory of the sizes the solve is about to ask for holds a tagged NaN, so a
+    work vector (r, p, q, tmp, part, red, st, dinv, the directions of fs_mscg, the partials and scalars of fs_pcgn) that is read
+    before it is written puts that tag into x.  The exact family in the default mode (both twins: every fs_pcg start and
+    preconditioner, the ladders with ldx > F, fs_pcgn at every k with columns frozen from the start), the general system under
+    strict_order against the models, state included.  The bar is the walks': exact bits"""
+    w = LC.Walk(backend, LC.data_sets()["wide_range_odd"], LC.AUTO, seed=11, steps=0, copies=COPIES)
+    with w.session():
+        w.create(first=True)
+        for valued in (False, True):
+            pair = w.create_pair("exact", valued=valued)
+            cases = LC.exact_cases(pair.ps.fam)
+            nth = {}
+            for solver, what, _ in cases:
+                j = nth[solver] = nth.get(solver, -1) + 1
+                if solver == "pcgn" and (j + valued) % 5:             # (a fifth of the 54 panels per twin: every k is met)
+                    continue
+                w.step += 1
+                rc, _ = w.exact_solve(pair.A, solver, poison=True, pick=j)
+                assert rc == LC.FS_OK, what
+                for h in (pair.A, pair.At):
+                    w.recover(h)
+            w.step += 1
+            w.op_gram_diag(pair.A)
+        pair = w.create_pair("general")
+        for i in range(len(LC.strict_cases(pair.ps))):
+            w.step += 1
+            assert w.op_solve_strict(pair.A, pick=i, poison=True) == LC.FS_OK
+            for h in (pair.A, pair.At):
+                w.recover(h)
+        met = {kw["b"].size // pair.ps.s.ncol for sv, _, kw in LC.strict_cases(pair.ps) if sv == "pcgn"}
+        assert met == {3, 5} and w.counts["poisoned"] >= 40, (met, w.counts["poisoned"])
+    _count_poison(w)
+    print(f"poison probes: {w.counts['poison_seen']} of {w.counts['poison_probed']} doubles still held the poison")
+
+
+def test_solver_work_space_is_given_back(backend):
+    """one pair, no walk: after two warm-up solves, 50 fs_pcgn solves (k = 32, Jacobi, F = 2000) and 50 fs_mscg solves (m = 16) leave
+    free device memory no lower than by ONE solve's work space (the header's formula: 3 k F + k N + F + 2048 k + 512 doubles, about
+    2 MB; a leak of a solve's work space per solve would be a hundred times that).  CgFlags' pinned memory and events cannot be seen
+    in free memory: for them 1000 solves that are done before their first iteration (b = 0: no product) all return FS_OK"""
+    import torch
+    from libfastsparse_amd import capi
+    ps = LC.pair_system("exact")
+    fam, s, mem = ps.fam, ps.s, backend.mem
+    (arp, acc, _), (trp, tcc, _) = ps.a_csr, ps.t_csr
+    A = capi.Matrix.from_csr(s.nrow, s.ncol, mem.const(arp), mem.const(acc), None)
+    At = capi.Matrix.from_csr(s.ncol, s.nrow, mem.const(trp), mem.const(tcc), None)
+    st = capi.current_stream()
+    k, lams = 32, fam.ladders["m16"]
+    B, b = mem.const(fam.panel(k)), mem.const(s.b)
+    X, Xm, x = torch.empty_like(B), torch.empty((16, s.ncol), dtype=torch.float64, device="cuda"), torch.empty_like(b)
+    zero = torch.zeros_like(b)
+    want_n, want_m = mem.const(fam.panel(k) / fam.c), mem.const(np.stack([s.b / (fam.d + l) for l in lams]))
+
+    def both():
+        infos = capi.pcgn(A, At, X, B, s.lam, s.tol, precond=capi.FS_PRECOND_JACOBI, stream=st)
+        assert all(i.converged == 1 for i in infos) and mem.eq(X, want_n)
+        infos = capi.mscg(A, At, Xm, b, lams, s.tol, stream=st)
+        assert all(i.converged == 1 for i in infos) and mem.eq(Xm, want_m)
+
+    both()
+    both()
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for _ in range(50):
+        both()
+    torch.cuda.synchronize()
+    free1 = torch.cuda.mem_get_info()[0]
+    one_solve = 8 * (3 * k * s.ncol + k * s.nrow + s.ncol + 2048 * k + 512)
+    print(f"free device memory: {free0} bytes after the warm-up, {free1} after 100 solves more; one solve's work space {one_solve} bytes")
+    assert free0 - free1 <= one_solve, (free0, free1, one_solve)
+    for _ in range(1000):
+        info = capi.pcg(A, At, x, zero, s.lam, s.tol, precond=capi.FS_PRECOND_NONE, stream=st)
+        assert info.converged == 1 and info.iterations == 0
+    assert not x.any().item()
+    torch.cuda.synchronize()
+    free2 = torch.cuda.mem_get_info()[0]
+    print(f"free device memory after 1000 solves without an iteration: {free2} bytes")
+    assert free0 - free2 <= one_solve, (free0, free2, one_solve)
 
 
 @pytest.mark.parametrize("copy", list(SMALL_PANELS))
@@ -325,3 +416,19 @@ def test_walk_on_three_virtual_ranks(backend, mid, name):
             L.fs_dist_matrix_destroy(Mx)
     finally:
         L.fs_dist_destroy(D)
+
+
+def test_the_poison_probe_saw_poison(backend):
+    """last in the file: what poison_heap freed came back to a later allocation with its contents at least once over this module's
+    walks -- else the poisoned solves above showed nothing.  (Run alone, the test poisons a few solves of its own first.)"""
+    if not POISON["probed"]:
+        w = LC.Walk(backend, LC.data_sets()["wide_range_odd"], LC.AUTO, seed=12, steps=0, copies=COPIES)
+        with w.session():
+            w.create(first=True)
+            pair = w.create_pair("exact")
+            for i in range(8):
+                w.step += 1
+                w.exact_solve(pair.A, "pcg", poison=True, pick=i)
+        _count_poison(w)
+    print(f"poison probes: {POISON['seen']} of {POISON['probed']} doubles still held the poison, {POISON['poisoned']} poisoned solves")
+    assert POISON["probed"] > 0 and POISON["seen"] >= 1, POISON

@@ -10,7 +10,9 @@ import contextlib
 import numpy as np
 import pytest
 
+import _cg_model as M
 import _lifecycle as LC
+import _pcg_model as P
 
 COPIES = ["stream", "two-pass", "two-pass one-byte", "long rows", "lds-staged", "tiled cut rows", LC.AUTO]
 CODES = {"stream": 1, "two-pass": 7, "two-pass one-byte": 7, "long rows": 7, "lds-staged": 8, "tiled cut rows": 6, LC.AUTO: 1}
@@ -353,6 +355,7 @@ class StandIn:
         self.step = -1
         self.first_fired = None
         self.cur = 0
+        self.pool = np.zeros(1)
 
     def fired(self):
         if self.first_fired is None:
@@ -395,8 +398,84 @@ class StandIn:
     def switch_stream(self):
         self.cur ^= 1
 
-    def create(self, d, copy, arrays, borrow):
+    def create(self, d, copy, arrays, borrow, must=True):
         return StandInMatrix(self, d, CODES[copy], borrow)
+
+    # -- the solvers: the status rules of the header, then the models ----
+    def gram_diag(self, At, lam, d):
+        if At.released[0]:
+            _raise(LC.FS_ERR_RELEASED, "fs_gram_diag")
+        d[...] = P.gram_diag(At.d.system.t_csr, lam)
+
+    def _ready(self, Mx, k, what):
+        """a product of the solve would read plain arrays that were released"""
+        if Mx.released[0] and (Mx.kernel_code(0) < 6 if k == 1 else Mx.spmm_plan(k, 0) in (LC.ROW_PLAN, LC.MFMA_PLAN)):
+            _raise(LC.FS_ERR_RELEASED, what)
+
+    def solve(self, solver, A, At, x, b, lam=0.0, tol=1e-6, max_iter=0, precond=0, warm=False, diag=None, k=1, lams=(), ldx=0, null=()):
+        what, fault, answers = "fs_" + solver, self.fault, False
+        if null or (At is not None and A is not None and (At.d.nrow, At.d.ncol) != (A.d.ncol, A.d.nrow)):
+            _raise(LC.FS_ERR_ARG, what)
+        F = A.d.ncol
+        if solver == "pcgn" and not 1 <= k <= 32 or solver == "mscg" and (not 1 <= k <= 16 or ldx < F or not np.isfinite(lams).all()):
+            _raise(LC.FS_ERR_ARG, what)
+        if solver in ("pcg", "pcgn", "mscg") and not tol >= 0.0 or solver in ("pcg", "pcgn") and (precond not in (0, 1, 2) or precond == 2 and diag is None):
+            _raise(LC.FS_ERR_ARG, what)
+        if precond == P.PRECOND_JACOBI and At.released[0]:
+            if fault == "jacobi on a released At zeroes x":
+                self.fired()
+                x[...] = 0.0
+            if fault != "jacobi on a released At answers":
+                _raise(LC.FS_ERR_RELEASED, what)
+            answers = True
+        kk = 2 if solver == "cg2" else k if solver == "pcgn" else 1
+        if kk >= 2:
+            unprepared = fault == "pcgn leaves k unprepared" and ((A.spmm_needs(kk, 0) | At.spmm_needs(kk, 0)) & 5)
+            if fault != "pcgn leaves k unprepared":
+                A.prepare(kk)
+                At.prepare(kk)
+        self._ready(A, kk, what)
+        self._ready(At, kk, what)
+        if kk >= 2 and unprepared or answers:
+            self.fired()
+        ps = A.d.system
+        x0 = np.array(x) if warm else None
+        r = LC.solve_model(ps, solver, np.array(b), lam, tol, max_iter, precond, x0, None if diag is None else np.array(diag), list(lams) or None)
+        pool, self.pool = self.pool, np.zeros(1)            # the work space of this solve: whatever its last owner left
+        if solver == "mscg":
+            for i in range(k):
+                x[i * ldx:i * ldx + F] = r.x[i]
+            if fault == "mscg writes into the gap" and ldx > F and k > 1:
+                self.fired()
+                x[F] = 0.0
+        else:
+            x[...] = np.ascontiguousarray(r.x).reshape(-1)
+        if fault == "work space read before it is written" and x[0] != 0.0 and pool.view(np.int64)[0] != 0:
+            self.fired()
+            x[0] = x[0] + pool[0]
+        if fault == "pcgn writes a frozen column" and solver == "pcgn" and k >= 2:
+            self.fired()
+            x.reshape(F, k)[3, k // 2] = -0.0               # (the zero column: frozen from the start)
+        base, off = _where(x)
+        if fault == "solver stores past x" and self.calls >= 3:
+            self.fired()
+            base[off + x.size] = 1.0
+        if fault == "solver writes into b" and self.calls >= 3:
+            self.fired()
+            b[b.size // 2] = 1.5
+        if fault == "scope left on" and self.calls >= 3 and not self.opt["reproducible"]:
+            self.fired()
+            self.opt["reproducible"] = 1
+        self.calls += 1
+        infos = None if r.infos is None else [(i.iterations, i.converged, i.rnorm, i.bnorm) for i in r.infos]
+        return {"iters": list(r.iters), "infos": infos}
+
+    def last_state(self, solver, n):
+        return None                                         # (the stand-in's scalars ARE the model's)
+
+    def poison_heap(self, sizes):
+        self.pool = np.full(1, LC.guard_bits(LC.POISON_TAG), np.int64).view(np.float64)
+        return 1, 1
 
     def kernel_code(self, A, side):
         return A.kernel_code(side)
@@ -452,16 +531,33 @@ FAULTS = {
     "released answers": (("status",), "FS_ERR_RELEASED"),
     "release_prepared keeps": (("release_prepared", "device bytes"), "release_prepared("),
     "cached output": (("not exact", "rows below the cut"), "differ"),
+    # the solvers on the pairs
+    "solver stores past x": (("guard",), "1 double(s) past its end"),
+    "solver writes into b": (("input modified",), "b of the solvers"),
+    "jacobi on a released At answers": (("status",), "FS_ERR_RELEASED"),
+    "jacobi on a released At zeroes x": (("x written",), "wrote to x all the same"),
+    "pcgn leaves k unprepared": (("bookkeeping", "status"), "fs_"),
+    "pcgn writes a frozen column": (("not exact",), "fs_pcgn"),
+    "scope left on": (("option", "bookkeeping"), "reproducible"),
+    "work space read before it is written": (("guard value read",), "a guard value of poison"),
+    "mscg writes into the gap": (("gap written",), "a gap between the vectors of X"),
 }
+RARE = ("jacobi on a released At answers", "jacobi on a released At zeroes x", "pcgn leaves k unprepared")     # (need a released pair)
 
 
 @pytest.mark.parametrize("fault", list(FAULTS))
 def test_an_injected_fault_fails_the_walk_at_the_step_where_it_first_matters(sets, fault):
     kind, words = FAULTS[fault]
     copy = {"scratch not grown": "lds-staged", "evicted cuts": "two-pass"}.get(fault, "two-pass")
-    kw = dict(copies=[copy], nhandles=2) if fault in ("scratch not grown", "evicted cuts", "release_prepared keeps") else {}     # (rare orders)
+    kw = {}
+    if fault in ("scratch not grown", "evicted cuts", "release_prepared keeps"):     # (rare orders of product operations: no solver pairs)
+        kw = dict(copies=[copy], nhandles=2, solvers=False)
+    elif fault in RARE:
+        kw = dict(copies=[copy], nhandles=1)
     caught = 0
-    for seed in range(1, 13):
+    for seed in range(1, 41 if fault in RARE else 13):
+        if caught >= 2 and seed > 12:
+            break
         lib = StandIn(fault)
         try:
             LC.run_walk(lib, sets["wide_range"], copy, seed, steps=STEPS, **kw)
@@ -523,3 +619,77 @@ def test_guarded_vectors_sit_where_they_say(sets):
         g.store[g.lo - 1] = 0.0
         assert not g.guards_ok() and "1 double(s) before it" in g.first_broken()
     assert LC.guard_tag(np.float64(np.nan).view(np.int64)) is None
+
+
+# ---- the solvers on the pairs ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("valued", (False, True), ids=("binary", "valued"))
+def test_the_exact_family_is_exact_in_any_order_of_additions(valued):
+    """every solve the walks run on the exact family, by each solver's model, once with the device's reduction tree and once with
+    serial sums: identical bits in x, the counts and the info -- the solves can run in whatever mode a walk is in.  And they are
+    the solves they are meant to be: converged at iteration 0, x = b / 2^e"""
+    ps = LC.pair_system("exact", valued)
+    fam = ps.fam
+    cases = LC.exact_cases(fam)
+    assert {c[0] for c in cases} == set(LC.EXACT_ONLY)
+    assert {kw["b"].size // fam.F for sv, _, kw in cases if sv == "pcgn"} == set(LC.PCGN_KS)
+    assert fam.c == 2.0 ** int(np.log2(fam.c)) and all(np.log2(fam.d + l) % 1 == 0 for ls in fam.ladders.values() for l in ls)
+    assert fam.ladders["m16"].count(min(fam.ladders["m16"])) >= 2 and len(fam.ladders["m16"]) == 16
+    assert np.array_equal(P.gram_diag(ps.t_csr, fam.s.lam), np.full(fam.F, fam.c)) and (valued == (fam.s.vals is not None))
+    for solver, what, kw in cases:
+        dev = LC.solve_model(ps, solver, lam=fam.s.lam, tol=fam.s.tol, **kw)
+        ser = LC.solve_model(ps, solver, lam=fam.s.lam, tol=fam.s.tol, tree="serial", **kw)
+        assert M.same_bits(dev.x, ser.x).all() and np.isfinite(dev.x).all(), (what, "x depends on the order of the additions")
+        assert dev.iters == ser.iters == [0] * len(dev.iters), (what, dev.iters, ser.iters)
+        for a, b in zip(dev.infos or [], ser.infos or []):
+            assert (a.iterations, a.converged) == (b.iterations, b.converged) == (0, 1), (what, a, b)
+            assert M.same_bits(a.rnorm, b.rnorm)[0] and M.same_bits(a.bnorm, b.bnorm)[0], (what, a, b)
+        B = kw["b"]
+        want = np.stack([B / (fam.d + l) for l in kw["lams"]]) if solver == "mscg" else B / fam.c
+        assert M.same_bits(dev.x, want).all(), (what, "x is not b / 2^e")
+        if solver == "pcgn":
+            X = dev.x.reshape(fam.F, -1)
+            k = X.shape[1]
+            assert k == 1 or (M.same_bits(X[:, k // 2], np.zeros(fam.F)).all() and not kw["b"].reshape(fam.F, k)[:, k // 2].any()), (what, "the zero column")
+
+
+def test_the_strict_solves_freeze_at_different_iterations():
+    """the solves of solve_strict on the general system: caps of at most 12 that some column / shift meets while another is done
+    before; fs_cg within about 20 iterations"""
+    ps = LC.pair_system("general")
+    for solver, what, kw in LC.strict_cases(ps):
+        kw = dict(kw)
+        r = LC.solve_model(ps, solver, lam=ps.s.lam, **kw)
+        if solver == "cg":
+            assert 2 <= r.iters[0] <= 20 and r.state["done"] == 1.0, (what, r.iters)
+        else:
+            assert 0 < kw["max_iter"] <= 12 and max(r.iters) <= kw["max_iter"], (what, r.iters)
+        if solver == "mscg" or "jacobi" in what and solver == "pcgn":
+            assert len(set(r.iters)) >= 3, (what, r.iters)
+            if solver == "pcgn":
+                assert r.infos[3].iterations == 0 and r.infos[3].converged == 1, "a column that is done before the first product"
+
+
+def test_the_solver_operations_reach_everything(sets, gpu_walks):
+    """over the walks the GPU test runs, per data set: every solver operation, every solver, solves refused with each status the
+    header names and solves that went through on a released pair, the poison before about half of the solves"""
+    for name in sets:
+        ops, solves, status, poisoned, total = {}, {}, {}, 0, 0
+        for w in gpu_walks:
+            if w.data.name != name:
+                continue
+            for k, v in w.counts["ops"].items():
+                ops[k] = ops.get(k, 0) + v
+            for k, v in w.counts["solves"].items():
+                solves[k] = solves.get(k, 0) + v
+            for k, v in w.counts["solver_status"].items():
+                status[k] = status.get(k, 0) + v
+            poisoned += w.counts["poisoned"]
+            total += sum(w.counts["solves"].values())
+            assert w.counts["poison_seen"] == w.counts["poisoned"]            # (the stand-in's probe sees its one double)
+        missing = [o for o in LC.SOLVER_OPS if ops.get(o, 0) < 5]
+        assert not missing, (name, missing, ops)
+        assert all(solves.get(sv, 0) >= 5 for sv in ("cg", "cg2", "pcg", "mscg", "pcgn")), (name, solves)
+        for sv in ("gram_diag", "pcg", "pcgn"):
+            assert status.get((sv, LC.FS_ERR_RELEASED), 0) >= 1 and status.get((sv, LC.FS_OK), 0) >= 5, (name, sv, status)
+        assert sum(v for (sv, rc), v in status.items() if rc == LC.FS_ERR_ARG) >= 5, (name, status)
+        assert total // 4 <= poisoned <= 3 * total // 4, (name, poisoned, total)
