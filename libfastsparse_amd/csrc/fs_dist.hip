@@ -15,14 +15,31 @@
 // A matrix comes from ONE host CSR (fs_dist_csr_create: int row_ptr, < 2^31 entries in total) or from per-rank shards
 // (fs_dist_csr_create_from_shards: every shard < 2^31 entries, the total is 64-bit -- BASELINE config 5 only exists this way).
 //
-// One product (dist_product): the local product runs in parts (fs_spmv_part: pass 2 of the two-pass pair by ranges of panels)
-// on the rank's compute stream; behind every part an event lets the rank's COMMUNICATION stream all-gather the rows that
-// part finished -- one ncclAllGather per part on a padded buffer (counts differ between ranks), all ranks' calls of a part
-// in one ncclGroupStart/End -- while the next part computes; one fs_copy_segments launch per rank unpacks the padded buffer
-// into the full vector at the end.  No n^2 broadcasts, no host round trip.
-// The CONSERVATIVE mode (FS_DIST_PARTS=1; on virtual ranks also after an exchange of the overlapped mode failed) is one whole-shard
-// all-gather behind the finished local product: no send window ever reaches into rows that are still being written.  With RCCL a
-// group call that failed aborts the communicators (no second collective on a half-issued group): the context then returns errors.
+// ONE PLAN: the layout of an exchange -- which window of a rank's local output every all-gather sends, where rank r's rows land in the
+// padded buffer, the tables of the unpack, the buffer sizes -- is fs::plan_exchange (fs_dist_plan.h: plain C++, tested without a
+// GPU) for every k; the cuts it starts from come from the kernels (fs_spmv_part_rows, fs_spmm_part_rows).  A DistSide owns the
+// k = 1 plan of its side, KWork one plan per side for the handle's current k > 1.
+// ONE ENGINE: run_product runs a product for any k, run_gather the whole-shard exchange, on a small view (Exchange).  The local
+// product runs in parts (fs_spmv_part / fs_spmm_part) on the rank's compute stream; behind every part an event lets the rank's
+// COMMUNICATION stream all-gather the rows that part finished -- one ncclAllGather per part on a padded buffer (counts differ
+// between ranks) -- while the next part computes; one fs_copy_segments launch per rank unpacks the padded buffer into the full
+// vector at the end.  No n^2 broadcasts, no host round trip.  Every step is "for every rank do f(r)" (each_rank): on the calling
+// thread, or on one issuing thread per rank (RankWorkers).  What differs between the modes is behaviour, each kept in one place:
+//   1  whole-shard mode (ONE all-gather behind the finished local product: no send window reaches into rows still being written):
+//      k = 1 when conservative || np == 1, launched as all np calls of fs_spmv_part; k > 1 when conservative || np <= 1 || !real,
+//      launched as ONE fs_spmm (dist_product);
+//   2  replan_if_moved runs for k = 1 products only; ensure_k rebuilds the k-column plans on any option-epoch change (dist_product);
+//   3  RCCL from the calling thread: ncclGroupStart, one ncclAllGather per rank in rank order, ncclGroupEnd; issuing threads: each
+//      its own call, no group; virtual ranks: per destination, wait for every rank's event, then copy (exchange_equal);
+//   4  a failed exchange, calling thread: conservative = true; with RCCL the communicators are aborted (abort_communicators: no
+//      second collective on a half-issued group) and the context returns errors from then on; on virtual ranks the remaining parts
+//      run, then dist_sync, then one whole-shard gather.  Issuing threads: the error is returned, no fallback.  FS_DIST_FAIL_PART is
+//      honoured only when the calling thread issues (run_product);
+//   5  k > 1 under FS_DIST_THREADS=1 is issued by the calling thread: an inherited asymmetry, not a decision (dist_product);
+//   6  the broken check first, then ++g_products, once per product (dist_product);
+//   7  events: whole-shard mode uses ev[r][0], overlapped mode ev[r][p]; done[r] follows the unpack and the compute stream waits
+//      for it (run_gather, run_product).
+// The CONSERVATIVE mode is FS_DIST_PARTS=1, or what a context falls to after a failed exchange (4).
 // The caller's vectors may live in host memory or in the HBM of any device (vec_in / vec_out): a vector in HBM is read in place by
 // the ranks of its device, travels device to device to the others, and an output in HBM is written by the unpack launch itself.
 //
@@ -51,6 +68,7 @@
 
 #include "csr.h"
 #include "fs_common.h"
+#include "fs_dist_plan.h"
 
 namespace {
 
@@ -218,53 +236,71 @@ struct DistSide {
   std::vector<int> bounds;            // rank r owns rows [bounds[r], bounds[r + 1]) of M
   std::vector<int64_t> shard_nnz;
   std::vector<fs_matrix_t> shard;
-  int max_rows = 0;                   // the tallest shard
+  fs::ExchangePlan plan;              // of the single-vector product (k = 1): cuts from fs_spmv_part_rows
   // per rank, on its device: the shard's rows of the output (room for a padded window behind the last row), the padded
-  // receive buffer, the tables of the unpack launches, one event per part
+  // receive buffer, the table of the unpack launches (plan.table), one event per part
   std::vector<double *> local, pad;
-  std::vector<int64_t *> table;       // [rank]: the overlapped layout (nseg segments), then the whole-shard layout (nseg1)
-  std::vector<std::vector<hipEvent_t>> ev;   // [rank][part]
+  std::vector<int64_t *> table;
+  std::vector<std::vector<hipEvent_t>> ev;   // [rank][part]; the k-column products of the side use them too
   std::vector<hipEvent_t> done;              // [rank]: the unpack on the communication stream
-  int nparts = 0;
-  std::vector<std::vector<int>> cut;  // [rank][part]: row cuts of the local product (fs_spmv_part_rows)
-  std::vector<int> maxc;              // [part]: the largest count of any rank
-  std::vector<int64_t> off;           // [part]: first element of the part's region of the padded buffer
-  int nseg = 0, nseg1 = 0;
-  int64_t max_seg = 0;
   bool built = false;
   unsigned epoch = 0;                 // fs::option_epoch() when the cuts were last checked against the kernels (replan_if_moved)
 };
 
+// Device buffers of one work space, per rank: each allocated with the rank's device current and freed there.  `ready` only after
+// every allocation of a fill succeeded: a failure leaves it false, and the next call frees what exists and starts over.
+struct RankBuffers {
+  std::vector<std::vector<void *>> held;   // [rank], in the order of allocation
+  bool ready = false;
+
+  // `count` elements at v[r], on the current device (rank r's)
+  template <typename T>
+  int get(int r, std::vector<T *> &v, size_t count)
+  {
+    v.resize(held.size(), nullptr);
+    FS_HIP(hipMalloc(&v[(size_t)r], sizeof(T) * count));
+    held[(size_t)r].push_back(v[(size_t)r]);
+    return FS_OK;
+  }
+  // per_rank(r) makes rank r's allocations (and whatever fills them), its device current
+  int fill(fs_dist_t D, const std::function<int(int)> &per_rank)
+  {
+    held.assign((size_t)D->n, std::vector<void *>());
+    for (int r = 0; r < D->n; ++r) {
+      FS_HIP(hipSetDevice(D->dev[r]));
+      if (int rc = per_rank(r)) return rc;
+    }
+    ready = true;
+    return FS_OK;
+  }
+  void release(fs_dist_t D)
+  {
+    for (size_t r = 0; r < held.size(); ++r) {
+      (void)hipSetDevice(D->dev[r]);
+      for (void *p : held[r]) (void)hipFree(p);
+    }
+    held.clear();
+    ready = false;
+  }
+};
+
 struct CgWork {                       // vectors of fs_dist_cg, kept on the handle between solves
   int F = 0;
-  bool ready = false;                 // every allocation below succeeded
+  RankBuffers mem;
   std::vector<double *> sol, r, b, p, q, part, red, redall, st;
 };
 
 // k row-major columns on the sharded matrix (fs_dist_spmm, fs_dist_cg2): the replicated X / Y / Z, the shards' local outputs, the
-// padded receive buffer, the unpack tables (offsets and counts times k) and the work vectors of the block solver, per rank
-// the k-column local product of one side in parts (fs_spmm_part: the one-sweep plan of k = 2, 4 is cut like the single-vector pair),
-// with the padded layout of the exchange of every part -- the k-column twin of DistSide's plan; counts in ROWS (x k doubles)
-struct KParts {
-  int np = 1;
-  bool real = false;                    // some rank finishes rows in more than one part: the overlapped exchange has something to hide
-  std::vector<std::vector<int>> cut;    // [rank][part]
-  std::vector<int> maxc;                // [part]
-  std::vector<int64_t> off;             // [part]: first ROW of the part's region of the padded buffer
-  int nseg = 0;
-  int64_t max_seg = 0;                  // in doubles
-  size_t tab_at = 0;                    // where this side's (dst, src, cnt) table starts in KWork::tab
-};
-
+// padded receive buffer (one, for both sides), the unpack tables and the work vectors of the block solver, per rank; one plan per
+// side, its cuts from fs_spmm_part_rows (the one-sweep plan of k = 2, 4 is cut like the single-vector pair)
 struct KWork {
   int k = 0;
   bool with_t = false;
-  bool ready = false;                   // every allocation and prepare below succeeded
   unsigned epoch = 0;                   // fs::option_epoch() when the parts were planned
+  RankBuffers mem;                      // ready: every prepare and allocation of ensure_k succeeded
+  fs::ExchangePlan pa, pt;
   std::vector<double *> x, y, z, la, lt, pad;
-  std::vector<int64_t *> tab;           // [A whole-shard: dst, src, cnt][A' whole-shard][A in parts][A' in parts]
-  int nseg_a = 0, nseg_t = 0;
-  KParts pa, pt;
+  std::vector<int64_t *> tab;           // [rank]: pa.table, then pt.table
   std::vector<double *> sol, r, b, part, red, st;
 };
 
@@ -301,26 +337,8 @@ void free_side(fs_dist_t D, DistSide &S)
   S = DistSide();
 }
 
-void free_cg(fs_dist_t D, CgWork &W)
-{
-  for (size_t d = 0; d < W.sol.size(); ++d) {
-    (void)hipSetDevice(D->dev[d]);
-    for (double *p : {W.sol[d], W.r[d], W.b[d], W.p[d], W.q[d], W.part[d], W.red[d], W.redall[d], W.st[d]})
-      if (p) (void)hipFree(p);
-  }
-  W = CgWork();
-}
-
-void free_k(fs_dist_t D, KWork &W)
-{
-  for (size_t d = 0; d < W.x.size(); ++d) {
-    (void)hipSetDevice(D->dev[d]);
-    for (void *p : {(void *)W.x[d], (void *)W.y[d], (void *)W.z[d], (void *)W.la[d], (void *)W.lt[d], (void *)W.pad[d], (void *)W.tab[d], (void *)W.sol[d],
-                    (void *)W.r[d], (void *)W.b[d], (void *)W.part[d], (void *)W.red[d], (void *)W.st[d]})
-      if (p) (void)hipFree(p);
-  }
-  W = KWork();
-}
+void free_cg(fs_dist_t D, CgWork &W) { W.mem.release(D); W = CgWork(); }
+void free_k(fs_dist_t D, KWork &W) { W.mem.release(D); W = KWork(); }
 
 // row cuts with (almost) equal numbers of non-zeros: bounds[r] = first row whose row_ptr is >= r/n of nnz -- the cut
 // libfastsparse_amd/dist.py nnz_balanced_partition makes, essential for power-law matrices (BASELINE config 5)
@@ -339,8 +357,8 @@ void nnz_cut(std::vector<int> &bounds, int n, int nrow, const RP *row_ptr)
 }
 
 int dist_sync(fs_dist_t D);
-int dist_product_threaded(fs_dist_t D, DistSide &S, const std::vector<double *> &in, const std::vector<double *> &out);
 
+// the buffers, table and events of the side's k = 1 plan (the plan itself stays: replan_if_moved reads its part count)
 void free_plan(fs_dist_t D, DistSide &S)
 {
   for (size_t r = 0; r < S.local.size(); ++r) {
@@ -352,61 +370,29 @@ void free_plan(fs_dist_t D, DistSide &S)
     if (r < S.done.size() && S.done[r]) (void)hipEventDestroy(S.done[r]);
   }
   S.local.clear(); S.pad.clear(); S.table.clear(); S.ev.clear(); S.done.clear();
-  S.nseg = 0; S.nseg1 = 0; S.max_seg = 0;
 }
 
-// after the shards exist: the parts of every rank's local product, the padded layouts (overlapped: one region per part;
-// whole-shard: one region of max_rows per rank), buffers, events
+// The exchange plan of the side's product with k columns in np parts: the cuts come from the kernels that will run (device-handle
+// calls: fs_spmv_part_rows, fs_spmm_part_rows on the prepared k-column copy), everything else is fs::plan_exchange
+int side_plan(fs_dist_t D, const DistSide &S, int k, int np, fs::ExchangePlan &P)
+{
+  std::vector<std::vector<int>> cut((size_t)D->n, std::vector<int>((size_t)np + 1, 0));
+  for (int r = 0; r < D->n; ++r) {
+    if (S.bounds[(size_t)r + 1] == S.bounds[(size_t)r]) continue;
+    FS_HIP(hipSetDevice(D->dev[r]));
+    if (int rc = k == 1 ? fs_spmv_part_rows(S.shard[(size_t)r], 0, np, cut[(size_t)r].data())
+                        : fs_spmm_part_rows(S.shard[(size_t)r], 0, k, np, cut[(size_t)r].data())) return rc;
+  }
+  P = fs::plan_exchange(D->n, k, S.bounds, std::move(cut));
+  return FS_OK;
+}
+
+// after the shards exist: the k = 1 plan of the side, its buffers, table and events
 int plan_side(fs_dist_t D, DistSide &S, int nparts)
 {
   const int n = D->n;
-  S.nparts = nparts;
-  S.cut.assign((size_t)n, std::vector<int>((size_t)nparts + 1, 0));
-  for (int r = 0; r < n; ++r) {
-    FS_HIP(hipSetDevice(D->dev[r]));
-    const int nl = S.bounds[(size_t)r + 1] - S.bounds[(size_t)r];
-    if (nl > 0) {
-      if (int rc = fs_spmv_part_rows(S.shard[(size_t)r], 0, nparts, S.cut[(size_t)r].data())) return rc;
-    }
-  }
-  S.maxc.assign((size_t)nparts, 0);
-  S.off.assign((size_t)nparts + 1, 0);
-  S.max_rows = 0;
-  for (int r = 0; r < n; ++r) S.max_rows = std::max(S.max_rows, S.bounds[(size_t)r + 1] - S.bounds[(size_t)r]);
-  for (int p = 0; p < nparts; ++p) {
-    for (int r = 0; r < n; ++r) S.maxc[(size_t)p] = std::max(S.maxc[(size_t)p], S.cut[(size_t)r][(size_t)p + 1] - S.cut[(size_t)r][(size_t)p]);
-    S.off[(size_t)p + 1] = S.off[(size_t)p] + (int64_t)n * S.maxc[(size_t)p];
-  }
-  std::vector<int64_t> dst, src, cnt;
-  S.max_seg = 0;
-  for (int p = 0; p < nparts; ++p)
-    for (int r = 0; r < n; ++r) {
-      const int c = S.cut[(size_t)r][(size_t)p + 1] - S.cut[(size_t)r][(size_t)p];
-      if (!c) continue;
-      dst.push_back((int64_t)S.bounds[(size_t)r] + S.cut[(size_t)r][(size_t)p]);
-      src.push_back(S.off[(size_t)p] + (int64_t)r * S.maxc[(size_t)p]);
-      cnt.push_back(c);
-      S.max_seg = std::max<int64_t>(S.max_seg, c);
-    }
-  S.nseg = (int)cnt.size();
-  std::vector<int64_t> tab;
-  tab.insert(tab.end(), dst.begin(), dst.end());
-  tab.insert(tab.end(), src.begin(), src.end());
-  tab.insert(tab.end(), cnt.begin(), cnt.end());
-  // the whole-shard layout: rank r's rows at r * max_rows
-  dst.clear(); src.clear(); cnt.clear();
-  for (int r = 0; r < n; ++r) {
-    const int c = S.bounds[(size_t)r + 1] - S.bounds[(size_t)r];
-    if (!c) continue;
-    dst.push_back(S.bounds[(size_t)r]);
-    src.push_back((int64_t)r * S.max_rows);
-    cnt.push_back(c);
-  }
-  S.nseg1 = (int)cnt.size();
-  tab.insert(tab.end(), dst.begin(), dst.end());
-  tab.insert(tab.end(), src.begin(), src.end());
-  tab.insert(tab.end(), cnt.begin(), cnt.end());
-  const int64_t pad_doubles = std::max<int64_t>(S.off[(size_t)nparts], (int64_t)n * S.max_rows);
+  if (int rc = side_plan(D, S, 1, nparts, S.plan)) return rc;
+  const fs::ExchangePlan &P = S.plan;
   S.local.assign((size_t)n, nullptr);
   S.pad.assign((size_t)n, nullptr);
   S.table.assign((size_t)n, nullptr);
@@ -414,11 +400,10 @@ int plan_side(fs_dist_t D, DistSide &S, int nparts)
   S.done.assign((size_t)n, nullptr);
   for (int r = 0; r < n; ++r) {
     FS_HIP(hipSetDevice(D->dev[r]));
-    // the send window of a part starts at its first row and is maxc[p] long: it may run past the shard's last row
-    FS_HIP(hipMalloc(&S.local[(size_t)r], sizeof(double) * (size_t)(2 * (int64_t)S.max_rows + 1)));
-    FS_HIP(hipMalloc(&S.pad[(size_t)r], sizeof(double) * (size_t)(pad_doubles + 1)));
-    FS_HIP(hipMalloc(&S.table[(size_t)r], sizeof(int64_t) * (tab.size() + 1)));
-    if (!tab.empty()) FS_HIP(hipMemcpy(S.table[(size_t)r], tab.data(), sizeof(int64_t) * tab.size(), hipMemcpyHostToDevice));
+    FS_HIP(hipMalloc(&S.local[(size_t)r], sizeof(double) * (size_t)P.local_rows));
+    FS_HIP(hipMalloc(&S.pad[(size_t)r], sizeof(double) * (size_t)(P.pad_rows + 1)));
+    FS_HIP(hipMalloc(&S.table[(size_t)r], sizeof(int64_t) * (P.table.size() + 1)));
+    if (!P.table.empty()) FS_HIP(hipMemcpy(S.table[(size_t)r], P.table.data(), sizeof(int64_t) * P.table.size(), hipMemcpyHostToDevice));
     for (int p = 0; p < nparts; ++p) {
       hipEvent_t e = nullptr;
       FS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -431,16 +416,62 @@ int plan_side(fs_dist_t D, DistSide &S, int nparts)
   return FS_OK;
 }
 
+int context_usable(fs_dist_t D)
+{
+  if (!D->broken) return FS_OK;
+  fs::set_error("fs_dist: this context is unusable after an RCCL error (its communicators were aborted)");
+  return FS_ERR_HIP;
+}
+
+// An RCCL call that failed (its error is the current one, `rc` its code) may have launched the collective on some ranks only:
+// nothing issued on these communicators can be relied on to finish, and a new collective on them is undefined.  Abort them (that
+// also ends what is in flight) and leave the context unusable: this product and every later one return the error.
+// (no second collective on a failed group.)
+int abort_communicators(fs_dist_t D, int rc)
+{
+  const std::string why = fs_last_error();
+  for (ncclComm_t &c : D->comm)
+    if (c) { if (rccl().CommAbort) (void)rccl().CommAbort(c); c = nullptr; }
+  D->broken = true;
+  fs::set_error(why + "; the RCCL communicators were aborted: create a new context");
+  return rc;
+}
+
+// for every rank r do f(r): on the calling thread, rank after rank with the rank's device current, or (`threads`) on the ranks'
+// issuing threads, all at once -- returns when every rank is back
+int each_rank(fs_dist_t D, bool threads, const std::function<int(int)> &f)
+{
+  if (threads) return D->workers->run(f);
+  for (int r = 0; r < D->n; ++r) {
+    FS_HIP(hipSetDevice(D->dev[r]));
+    if (int rc = f(r)) return rc;
+  }
+  return FS_OK;
+}
+
 // `count` doubles from every rank's send[r] to every rank's recv[d] + r * count, on the streams `st` (ordered behind the
-// events ready[r], one per rank, recorded on whatever stream produced send[r]).  RCCL: one ncclAllGather per rank in one group;
-// virtual ranks: device-to-device copies leaving the same layout.  *failed_call (RCCL only): the all-gather call returned an
-// error -- the group was closed, nothing of this exchange can be relied on.
+// events ready[r], one per rank, recorded on whatever stream produced send[r]).
+//   RCCL, calling thread    ncclGroupStart, one ncclAllGather per rank in rank order, ncclGroupEnd;
+//   RCCL, issuing threads   every rank's thread makes ITS communicator's call, no group (many threads, one device each);
+//   virtual ranks           per destination d (either way of issuing): wait for every rank's event, then copy -- the same layout.
+// An RCCL call that returned an error aborts the communicators: nothing of this exchange can be relied on.
+// inject_failure (tests, calling thread only): the exchange fails half-issued.
 int exchange_equal(fs_dist_t D, const std::vector<const double *> &send, const std::vector<double *> &recv, size_t count,
-                   const std::vector<hipStream_t> &st, const std::vector<hipEvent_t> &ready, bool inject_failure = false)
+                   const std::vector<hipStream_t> &st, const std::vector<hipEvent_t> &ready, bool threads = false, bool inject_failure = false)
 {
   const int n = D->n;
-  if (D->broken) { fs::set_error("fs_dist: this context is unusable after an RCCL error (its communicators were aborted)"); return FS_ERR_HIP; }
+  if (int rc = context_usable(D)) return rc;
   if (!count) return FS_OK;
+  if (D->use_rccl && threads) {
+    std::vector<ncclResult_t> res((size_t)n, ncclSuccess);
+    (void)D->workers->run([&](int r) -> int {
+      res[(size_t)r] = rccl().AllGather(send[(size_t)r], recv[(size_t)r], count, ncclDouble, D->comm[(size_t)r], st[(size_t)r]);
+      return FS_OK;
+    });
+    for (int r = 0; r < n; ++r)
+      if (res[(size_t)r] != ncclSuccess) return abort_communicators(D, nccl_fail(res[(size_t)r], "ncclAllGather (issuing threads)"));
+    return FS_OK;
+  }
   if (D->use_rccl) {
     // every rank's call in one group; an error inside the group still closes it
     ncclResult_t first = rccl().GroupStart();
@@ -451,117 +482,115 @@ int exchange_equal(fs_dist_t D, const std::vector<const double *> &send, const s
     }
     const ncclResult_t end = rccl().GroupEnd();
     if (first == ncclSuccess && end == ncclSuccess) return FS_OK;
-    // A group call that failed may have launched the collective on some ranks only: nothing issued on these communicators can be
-    // relied on to finish, and a new collective on them is undefined.  Abort them (that also ends what is in flight) and leave the
-    // context unusable: this product and every later one return the error.  (no second collective on a failed group.)
-    const int rc = first != ncclSuccess ? nccl_fail(first, "ncclAllGather") : nccl_fail(end, "ncclGroupEnd");
-    const std::string why = fs_last_error();
-    for (ncclComm_t &c : D->comm)
-      if (c) { if (rccl().CommAbort) (void)rccl().CommAbort(c); c = nullptr; }
-    D->broken = true;
-    fs::set_error(why + "; the RCCL communicators were aborted: create a new context");
-    return rc;
+    return abort_communicators(D, first != ncclSuccess ? nccl_fail(first, "ncclAllGather") : nccl_fail(end, "ncclGroupEnd"));
   }
-  for (int d = 0; d < n; ++d) {
+  return each_rank(D, threads, [&](int d) -> int {
     // (tests: the failure comes with the first destination's copies already enqueued -- a half-issued exchange)
     if (inject_failure && d == (n > 1 ? 1 : 0)) { fs::set_error("injected failure of an exchange (FS_DIST_FAIL_PART)"); return FS_ERR_HIP; }
-    FS_HIP(hipSetDevice(D->dev[d]));
     for (int r = 0; r < n; ++r) {
-      if (ready[(size_t)r]) FS_HIP(hipStreamWaitEvent(st[(size_t)d], ready[(size_t)r], 0));
+      FS_HIP(hipStreamWaitEvent(st[(size_t)d], ready[(size_t)r], 0));
       FS_HIP(hipMemcpyAsync(recv[(size_t)d] + (int64_t)r * (int64_t)count, send[(size_t)r], sizeof(double) * count, hipMemcpyDeviceToDevice,
                             st[(size_t)d]));
     }
-  }
-  return FS_OK;
+    return FS_OK;
+  });
 }
 
 // the cuts belong to the kernel the options select NOW (strict_order / reproducible / spmv_kernel set since the plan was
 // made move the product to another kernel, which finishes its rows elsewhere): plan again when they moved
 int replan_if_moved(fs_dist_t D, DistSide &S)
 {
-  const int n = D->n;
+  const int n = D->n, np = S.plan.np;
   const unsigned epoch = fs::option_epoch();
   if (S.epoch == epoch) return FS_OK;     // no option was set since the last check: the products run on the same kernels
   bool same = true;
-  std::vector<int> now((size_t)S.nparts + 1);
+  std::vector<int> now((size_t)np + 1);
   for (int r = 0; same && r < n; ++r) {
     if (S.bounds[(size_t)r + 1] == S.bounds[(size_t)r]) continue;
     FS_HIP(hipSetDevice(D->dev[r]));
-    if (int rc = fs_spmv_part_rows(S.shard[(size_t)r], 0, S.nparts, now.data())) return rc;
-    same = now == S.cut[(size_t)r];
+    if (int rc = fs_spmv_part_rows(S.shard[(size_t)r], 0, np, now.data())) return rc;
+    same = now == S.plan.cut[(size_t)r];
   }
   if (!same) {
     if (int rc = dist_sync(D)) return rc;
     free_plan(D, S);
-    if (int rc = plan_side(D, S, S.nparts)) return rc;
+    if (int rc = plan_side(D, S, np)) return rc;
   }
   S.epoch = epoch;
   return FS_OK;
 }
 
-// the whole-shard all-gather: rank r's rows [bounds[r], bounds[r + 1]) from src[r] (room for max_rows doubles) into out[d] on
-// every rank d.  Runs on the communication streams behind the compute streams' work so far; the compute streams wait for it.
-int dist_gather(fs_dist_t D, DistSide &S, const std::vector<double *> &src, const std::vector<double *> &out)
+// What the engine below works on: one side's product with k columns -- its plan, the per-rank buffers the plan was sized for,
+// the side's events, and how a rank's local product is launched (on its compute stream, the rank's device current).
+struct Exchange {
+  const fs::ExchangePlan &P;
+  int k;
+  const std::vector<double *> &local, &pad;
+  const std::vector<int64_t *> &table;             // [rank]: the device copy of P.table starts at table[r] + table_at
+  size_t table_at;
+  const std::vector<std::vector<hipEvent_t>> &ev;  // [rank][part]
+  const std::vector<hipEvent_t> &done;             // [rank]
+  std::function<int(int, int)> part;               // (r, p): part p of rank r's local product
+  std::function<int(int)> whole;                   // (r): the whole local product of rank r
+};
+
+// The whole-shard all-gather: rank r's rows from src[r] (room for max_rows * k doubles) into out[d] on every rank d -- after
+// launch(r), the rank's whole local product, where one is given.  Runs on the communication streams behind the compute streams'
+// work so far (events ev[r][0]); the unpack is followed by done[r], which the compute stream waits for.
+int run_gather(fs_dist_t D, const Exchange &X, const std::vector<double *> &src, const std::vector<double *> &out, bool threads,
+               const std::function<int(int)> *launch = nullptr)
 {
+  const fs::ExchangePlan &P = X.P;
   const int n = D->n;
   std::vector<const double *> send((size_t)n);
   std::vector<hipEvent_t> ready((size_t)n);
-  for (int r = 0; r < n; ++r) {
-    FS_HIP(hipSetDevice(D->dev[r]));
-    FS_HIP(hipEventRecord(S.ev[(size_t)r][0], D->stream[r]));
-    FS_HIP(hipStreamWaitEvent(D->comm_stream[r], S.ev[(size_t)r][0], 0));
-    send[(size_t)r] = src[(size_t)r];
-    ready[(size_t)r] = S.ev[(size_t)r][0];
-  }
-  if (int rc = exchange_equal(D, send, S.pad, (size_t)S.max_rows, D->comm_stream, ready)) return rc;
-  for (int r = 0; r < n; ++r) {
-    FS_HIP(hipSetDevice(D->dev[r]));
-    if (int rc = fs_copy_segments(S.nseg1, S.table[(size_t)r] + 3 * (size_t)S.nseg, S.max_rows, S.pad[(size_t)r], out[(size_t)r], D->comm_stream[r])) return rc;
-    FS_HIP(hipEventRecord(S.done[(size_t)r], D->comm_stream[r]));
-    FS_HIP(hipStreamWaitEvent(D->stream[r], S.done[(size_t)r], 0));
-  }
-  return FS_OK;
+  if (int rc = each_rank(D, threads, [&](int r) -> int {
+        if (launch)
+          if (int rc2 = (*launch)(r)) return rc2;
+        FS_HIP(hipEventRecord(X.ev[(size_t)r][0], D->stream[r]));
+        FS_HIP(hipStreamWaitEvent(D->comm_stream[r], X.ev[(size_t)r][0], 0));
+        send[(size_t)r] = src[(size_t)r];
+        ready[(size_t)r] = X.ev[(size_t)r][0];
+        return FS_OK;
+      })) return rc;
+  if (int rc = exchange_equal(D, send, X.pad, (size_t)P.window_rows * (size_t)X.k, D->comm_stream, ready, threads)) return rc;
+  return each_rank(D, threads, [&](int r) -> int {
+    if (int rc = fs_copy_segments(P.nseg1, P.whole_shard_table(X.table[(size_t)r] + X.table_at), P.window_rows * X.k, X.pad[(size_t)r],
+                                  out[(size_t)r], D->comm_stream[r])) return rc;
+    FS_HIP(hipEventRecord(X.done[(size_t)r], D->comm_stream[r]));
+    FS_HIP(hipStreamWaitEvent(D->stream[r], X.done[(size_t)r], 0));
+    return FS_OK;
+  });
 }
 
-// out = M in on every rank: local products in parts, the all-gather of every finished part under the later parts, one unpack
-// per rank.  in[r] / out[r]: the replicated input and the gathered output on rank r's device.  Asynchronous: the caller
-// waits for the compute streams (dist_sync), which wait for the unpacks.
-int dist_product(fs_dist_t D, DistSide &S, const std::vector<double *> &in, const std::vector<double *> &out)
+// THE ENGINE: out = M in on every rank, for any k.  whole_shard: every rank's whole local product, then run_gather -- no send
+// window ever reaches into rows that are still being written.  Otherwise the local products run in parts; behind part p the event
+// ev[r][p] lets the communication streams all-gather the rows the part finished (a window of maxc[p] rows from the part's first
+// row into its region of the padded buffer) under the later parts, and ONE unpack per rank ends the product.  Every step is "for
+// every rank do f(r)" (each_rank), so the calling thread and the issuing threads make the same calls per stream, in the same
+// order.  Asynchronous: the caller waits for the compute streams (dist_sync), which wait for the unpacks (done[r]).
+int run_product(fs_dist_t D, const Exchange &X, const std::vector<double *> &out, bool whole_shard, bool threads)
 {
-  const int n = D->n;
-  if (D->broken) { fs::set_error("fs_dist: this context is unusable after an RCCL error (its communicators were aborted)"); return FS_ERR_HIP; }
-  ++g_products;
-  if (int rc = replan_if_moved(D, S)) return rc;
-  if (D->workers) return dist_product_threaded(D, S, in, out);
-  const int np = S.nparts;
-  if (D->conservative || np == 1) {
-    // one whole-shard all-gather behind the finished local product: no window reaches into rows still being written
-    for (int r = 0; r < n; ++r) {
-      const int nl = S.bounds[(size_t)r + 1] - S.bounds[(size_t)r];
-      FS_HIP(hipSetDevice(D->dev[r]));
-      if (nl > 0)
-        for (int p = 0; p < np; ++p)
-          if (int rc = fs_spmv_part(S.shard[(size_t)r], 0, S.local[(size_t)r], in[(size_t)r], p, np, D->stream[r])) return rc;
-    }
-    return dist_gather(D, S, S.local, out);
-  }
+  const fs::ExchangePlan &P = X.P;
+  const int n = D->n, np = P.np;
+  if (whole_shard) return run_gather(D, X, X.local, out, threads, &X.whole);
   for (int p = 0; p < np; ++p) {
     std::vector<const double *> send((size_t)n);
     std::vector<double *> recv((size_t)n);
     std::vector<hipEvent_t> ready((size_t)n);
-    for (int r = 0; r < n; ++r) {
-      const int nl = S.bounds[(size_t)r + 1] - S.bounds[(size_t)r];
-      FS_HIP(hipSetDevice(D->dev[r]));
-      if (nl > 0)
-        if (int rc = fs_spmv_part(S.shard[(size_t)r], 0, S.local[(size_t)r], in[(size_t)r], p, np, D->stream[r])) return rc;
-      FS_HIP(hipEventRecord(S.ev[(size_t)r][(size_t)p], D->stream[r]));
-      FS_HIP(hipStreamWaitEvent(D->comm_stream[r], S.ev[(size_t)r][(size_t)p], 0));
-      send[(size_t)r] = S.local[(size_t)r] + S.cut[(size_t)r][(size_t)p];
-      recv[(size_t)r] = S.pad[(size_t)r] + S.off[(size_t)p];
-      ready[(size_t)r] = S.ev[(size_t)r][(size_t)p];
-    }
-    const bool inject = take_injection(p);
-    if (int rc = exchange_equal(D, send, recv, (size_t)S.maxc[(size_t)p], D->comm_stream, ready, inject)) {
+    if (int rc = each_rank(D, threads, [&](int r) -> int {
+          if (int rc2 = X.part(r, p)) return rc2;
+          FS_HIP(hipEventRecord(X.ev[(size_t)r][(size_t)p], D->stream[r]));
+          FS_HIP(hipStreamWaitEvent(D->comm_stream[r], X.ev[(size_t)r][(size_t)p], 0));
+          send[(size_t)r] = X.local[(size_t)r] + (int64_t)P.cut[(size_t)r][(size_t)p] * X.k;
+          recv[(size_t)r] = X.pad[(size_t)r] + P.off[(size_t)p] * X.k;
+          ready[(size_t)r] = X.ev[(size_t)r][(size_t)p];
+          return FS_OK;
+        })) return rc;
+    // A failed exchange.  With issuing threads the error is returned: no injection, no fallback on that path.
+    const bool inject = !threads && take_injection(p);
+    if (int rc = exchange_equal(D, send, recv, (size_t)P.maxc[(size_t)p] * (size_t)X.k, D->comm_stream, ready, threads, inject)) {
+      if (threads) return rc;
       static const bool trace = getenv("FS_TRACE_BUILD") != nullptr;
       D->conservative = true;
       if (D->use_rccl) {            // exchange_equal aborted the communicators: nothing to finish this product with
@@ -572,77 +601,15 @@ int dist_product(fs_dist_t D, DistSide &S, const std::vector<double *> &in, cons
       // with ONE whole-shard exchange behind the finished local product -- and the context stays conservative from now on
       if (trace) fprintf(stderr, "[fastsparse] the exchange of part %d failed (%s): conservative mode from here on\n", p, fs_last_error());
       for (int q = p + 1; q < np; ++q)
-        for (int r = 0; r < n; ++r) {
-          if (S.bounds[(size_t)r + 1] == S.bounds[(size_t)r]) continue;
-          FS_HIP(hipSetDevice(D->dev[r]));
-          if (int rc2 = fs_spmv_part(S.shard[(size_t)r], 0, S.local[(size_t)r], in[(size_t)r], q, np, D->stream[r])) return rc2;
-        }
+        if (int rc2 = each_rank(D, false, [&](int r) { return X.part(r, q); })) return rc2;
       if (int rc2 = dist_sync(D)) return rc2;        // whatever of the failed exchange was enqueued has drained
-      return dist_gather(D, S, S.local, out);
+      return run_gather(D, X, X.local, out, false);
     }
   }
-  for (int r = 0; r < n; ++r) {
-    FS_HIP(hipSetDevice(D->dev[r]));
-    if (int rc = fs_copy_segments(S.nseg, S.table[(size_t)r], S.max_seg, S.pad[(size_t)r], out[(size_t)r], D->comm_stream[r])) return rc;
-    FS_HIP(hipEventRecord(S.done[(size_t)r], D->comm_stream[r]));
-    FS_HIP(hipStreamWaitEvent(D->stream[r], S.done[(size_t)r], 0));   // whatever follows on the compute stream sees the whole vector
-  }
-  return FS_OK;
-}
-
-// dist_product with one issuing thread per rank (RankWorkers): the same launches, events and exchange calls, every rank's from its
-// own thread.  The rounds end in a meeting of all threads, so a rank's event is recorded before another rank's stream is told to
-// wait for it (virtual ranks), and every thread reaches its all-gather of a part (RCCL).  No failure injection on this path.
-int dist_product_threaded(fs_dist_t D, DistSide &S, const std::vector<double *> &in, const std::vector<double *> &out)
-{
-  RankWorkers &W = *D->workers;
-  const int n = D->n, np = S.nparts;
-  const bool whole = D->conservative || np == 1;
-  auto exchange = [&](const std::function<const double *(int)> &send, const std::function<double *(int)> &recv, size_t count, int evp) -> int {
-    if (!count) return FS_OK;
-    if (D->use_rccl) {
-      std::vector<ncclResult_t> res((size_t)n, ncclSuccess);
-      (void)W.run([&](int r) -> int { res[(size_t)r] = rccl().AllGather(send(r), recv(r), count, ncclDouble, D->comm[(size_t)r], D->comm_stream[r]); return FS_OK; });
-      for (int r = 0; r < n; ++r)
-        if (res[(size_t)r] != ncclSuccess) {           // as in exchange_equal: no second collective on communicators in doubt
-          const int rc = nccl_fail(res[(size_t)r], "ncclAllGather (issuing threads)");
-          const std::string why = fs_last_error();
-          for (ncclComm_t &c : D->comm)
-            if (c) { if (rccl().CommAbort) (void)rccl().CommAbort(c); c = nullptr; }
-          D->broken = true;
-          fs::set_error(why + "; the RCCL communicators were aborted: create a new context");
-          return rc;
-        }
-      return FS_OK;
-    }
-    return W.run([&](int d) -> int {
-      for (int r = 0; r < n; ++r) {
-        FS_HIP(hipStreamWaitEvent(D->comm_stream[d], S.ev[(size_t)r][(size_t)evp], 0));
-        FS_HIP(hipMemcpyAsync(recv(d) + (int64_t)r * (int64_t)count, send(r), sizeof(double) * count, hipMemcpyDeviceToDevice, D->comm_stream[d]));
-      }
-      return FS_OK;
-    });
-  };
-  for (int p = 0; p < (whole ? 1 : np); ++p) {
-    if (int rc = W.run([&](int r) -> int {
-          const int nl = S.bounds[(size_t)r + 1] - S.bounds[(size_t)r];
-          for (int q = whole ? 0 : p; q < (whole ? np : p + 1); ++q)
-            if (nl > 0)
-              if (int rc2 = fs_spmv_part(S.shard[(size_t)r], 0, S.local[(size_t)r], in[(size_t)r], q, np, D->stream[r])) return rc2;
-          FS_HIP(hipEventRecord(S.ev[(size_t)r][(size_t)p], D->stream[r]));
-          FS_HIP(hipStreamWaitEvent(D->comm_stream[r], S.ev[(size_t)r][(size_t)p], 0));
-          return FS_OK;
-        })) return rc;
-    const int rc = whole ? exchange([&](int r) { return (const double *)S.local[(size_t)r]; }, [&](int r) { return S.pad[(size_t)r]; }, (size_t)S.max_rows, 0)
-                         : exchange([&](int r) { return (const double *)(S.local[(size_t)r] + S.cut[(size_t)r][(size_t)p]); },
-                                    [&](int r) { return S.pad[(size_t)r] + S.off[(size_t)p]; }, (size_t)S.maxc[(size_t)p], p);
-    if (rc) return rc;
-  }
-  return W.run([&](int r) -> int {
-    if (int rc = whole ? fs_copy_segments(S.nseg1, S.table[(size_t)r] + 3 * (size_t)S.nseg, S.max_rows, S.pad[(size_t)r], out[(size_t)r], D->comm_stream[r])
-                       : fs_copy_segments(S.nseg, S.table[(size_t)r], S.max_seg, S.pad[(size_t)r], out[(size_t)r], D->comm_stream[r])) return rc;
-    FS_HIP(hipEventRecord(S.done[(size_t)r], D->comm_stream[r]));
-    FS_HIP(hipStreamWaitEvent(D->stream[r], S.done[(size_t)r], 0));
+  return each_rank(D, threads, [&](int r) -> int {
+    if (int rc = fs_copy_segments(P.nseg, X.table[(size_t)r] + X.table_at, P.max_seg, X.pad[(size_t)r], out[(size_t)r], D->comm_stream[r])) return rc;
+    FS_HIP(hipEventRecord(X.done[(size_t)r], D->comm_stream[r]));
+    FS_HIP(hipStreamWaitEvent(D->stream[r], X.done[(size_t)r], 0));   // whatever follows on the compute stream sees the whole vector
     return FS_OK;
   });
 }
@@ -852,12 +819,10 @@ int ensure_k(fs_dist_matrix_t M, int k)
   const int n = D->n;
   KWork &W = M->kw;
   const bool with_t = M->t.built;
-  if (W.ready && W.k == k && W.with_t == with_t && W.epoch == fs::option_epoch()) return FS_OK;
+  if (W.mem.ready && W.k == k && W.with_t == with_t && W.epoch == fs::option_epoch()) return FS_OK;
   if (int rc = dist_sync(D)) return rc;
   free_k(D, W);
   W.k = k; W.with_t = with_t; W.epoch = fs::option_epoch();
-  for (auto *v : {&W.x, &W.y, &W.z, &W.la, &W.lt, &W.pad, &W.sol, &W.r, &W.b, &W.part, &W.red, &W.st}) v->assign((size_t)n, nullptr);
-  W.tab.assign((size_t)n, nullptr);
   // the k-column copies of the shards first (fs_spmm itself never builds): the parts below belong to the plan they leave
   for (int r = 0; r < n; ++r) {
     FS_HIP(hipSetDevice(D->dev[r]));
@@ -866,180 +831,75 @@ int ensure_k(fs_dist_matrix_t M, int k)
     if (with_t && M->t.shard[(size_t)r])
       if (int rc = fs_matrix_prepare(M->t.shard[(size_t)r], k, 0, D->stream[r])) return rc;
   }
-  const int64_t mr = std::max<int64_t>(M->a.max_rows, with_t ? M->t.max_rows : 0);
-  std::vector<int64_t> tab;
-  auto side_table = [&](const DistSide &S, int *nseg) {
-    std::vector<int64_t> dst, src, cnt;
-    for (int r = 0; r < n; ++r) {
-      const int64_t c = S.bounds[(size_t)r + 1] - S.bounds[(size_t)r];
-      if (!c) continue;
-      dst.push_back((int64_t)S.bounds[(size_t)r] * k);
-      src.push_back((int64_t)r * S.max_rows * k);
-      cnt.push_back(c * k);
-    }
-    *nseg = (int)cnt.size();
-    tab.insert(tab.end(), dst.begin(), dst.end());
-    tab.insert(tab.end(), src.begin(), src.end());
-    tab.insert(tab.end(), cnt.begin(), cnt.end());
+  if (int rc = side_plan(D, M->a, k, M->a.plan.np > 0 ? M->a.plan.np : 1, W.pa)) return rc;
+  if (with_t)
+    if (int rc = side_plan(D, M->t, k, M->t.plan.np > 0 ? M->t.plan.np : 1, W.pt)) return rc;
+  std::vector<int64_t> tab(W.pa.table);
+  tab.insert(tab.end(), W.pt.table.begin(), W.pt.table.end());
+  const size_t pad_rows = (size_t)std::max(W.pa.pad_rows, W.pt.pad_rows);
+  const size_t F = (size_t)(M->ncol ? M->ncol : 1) * k, N = (size_t)(M->nrow ? M->nrow : 1) * k;
+  return W.mem.fill(D, [&](int r) -> int {
+    if (int rc = W.mem.get(r, W.x, F)) return rc;
+    if (int rc = W.mem.get(r, W.y, N)) return rc;
+    if (int rc = W.mem.get(r, W.z, F)) return rc;
+    if (int rc = W.mem.get(r, W.la, (size_t)W.pa.local_rows * k)) return rc;
+    if (int rc = W.mem.get(r, W.lt, (size_t)W.pt.local_rows * k)) return rc;      // (one row when A' is not built)
+    if (int rc = W.mem.get(r, W.pad, (pad_rows + 1) * k)) return rc;
+    if (int rc = W.mem.get(r, W.tab, tab.size() + 1)) return rc;
+    if (!tab.empty()) FS_HIP(hipMemcpy(W.tab[(size_t)r], tab.data(), sizeof(int64_t) * tab.size(), hipMemcpyHostToDevice));
+    if (int rc = W.mem.get(r, W.sol, F)) return rc;
+    if (int rc = W.mem.get(r, W.r, F)) return rc;
+    if (int rc = W.mem.get(r, W.b, F)) return rc;
+    if (int rc = W.mem.get(r, W.part, (size_t)fs::kCgPartDoubles)) return rc;
+    if (int rc = W.mem.get(r, W.red, 4)) return rc;
+    return W.mem.get(r, W.st, (size_t)fs::kCgStateDoubles);
+  });
+}
+
+// one side of the matrix as the engine sees it: k = 1 on the side's own plan and buffers, k > 1 (after ensure_k(M, k)) on KWork's
+Exchange exchange_of(fs_dist_matrix_t M, bool transposed, int k)
+{
+  DistSide &S = transposed ? M->t : M->a;
+  KWork &W = M->kw;
+  if (k == 1) return Exchange{S.plan, 1, S.local, S.pad, S.table, 0, S.ev, S.done, nullptr, nullptr};
+  return Exchange{transposed ? W.pt : W.pa, k, transposed ? W.lt : W.la, W.pad, W.tab, transposed ? W.pa.table.size() : 0, S.ev, S.done, nullptr, nullptr};
+}
+
+// out = M in (M: A, or A' when `transposed`) for k row-major columns on every rank, through the one engine (run_product).  in[r] /
+// out[r]: the replicated input and the gathered output on rank r's device.  What differs between k = 1 and k > 1 is here:
+int dist_product(fs_dist_matrix_t M, bool transposed, int k, const std::vector<double *> &in, const std::vector<double *> &out)
+{
+  fs_dist_t D = M->D;
+  DistSide &S = transposed ? M->t : M->a;
+  if (int rc = context_usable(D)) return rc;         // the broken check first, then every product counts once
+  ++g_products;
+  if (k == 1)                                        // the cuts of the single-vector product follow the options; the k-column plan
+    if (int rc = replan_if_moved(D, S)) return rc;   // is rebuilt by ensure_k on any epoch change
+  Exchange X = exchange_of(M, transposed, k);
+  const int np = X.P.np;
+  const std::vector<double *> &local = X.local;
+  auto rows = [&S](int r) { return S.bounds[(size_t)r + 1] - S.bounds[(size_t)r]; };
+  X.part = [&, k, np](int r, int p) -> int {
+    if (rows(r) <= 0) return FS_OK;
+    return k == 1 ? fs_spmv_part(S.shard[(size_t)r], 0, local[(size_t)r], in[(size_t)r], p, np, D->stream[r])
+                  : fs_spmm_part(S.shard[(size_t)r], 0, local[(size_t)r], in[(size_t)r], k, p, np, D->stream[r]);
   };
-  side_table(M->a, &W.nseg_a);
-  if (with_t) side_table(M->t, &W.nseg_t);
-  // the local products in parts and the padded layout of every part's exchange (rows; the tables are in doubles)
-  auto side_parts = [&](DistSide &S, KParts &P) -> int {
-    P = KParts();
-    P.np = S.nparts > 0 ? S.nparts : 1;
-    P.cut.assign((size_t)n, std::vector<int>((size_t)P.np + 1, 0));
-    for (int r = 0; r < n; ++r) {
-      const int nl = S.bounds[(size_t)r + 1] - S.bounds[(size_t)r];
-      if (nl <= 0) continue;
-      FS_HIP(hipSetDevice(D->dev[r]));
-      if (int rc = fs_spmm_part_rows(S.shard[(size_t)r], 0, k, P.np, P.cut[(size_t)r].data())) return rc;
-      int busy = 0;
-      for (int p = 0; p < P.np; ++p) busy += P.cut[(size_t)r][(size_t)p + 1] > P.cut[(size_t)r][(size_t)p];
-      P.real = P.real || busy > 1;
-    }
-    P.maxc.assign((size_t)P.np, 0);
-    P.off.assign((size_t)P.np + 1, 0);
-    for (int p = 0; p < P.np; ++p) {
-      for (int r = 0; r < n; ++r) P.maxc[(size_t)p] = std::max(P.maxc[(size_t)p], P.cut[(size_t)r][(size_t)p + 1] - P.cut[(size_t)r][(size_t)p]);
-      P.off[(size_t)p + 1] = P.off[(size_t)p] + (int64_t)n * P.maxc[(size_t)p];
-    }
-    std::vector<int64_t> dst, src, cnt;
-    for (int p = 0; p < P.np; ++p)
-      for (int r = 0; r < n; ++r) {
-        const int64_t c = P.cut[(size_t)r][(size_t)p + 1] - P.cut[(size_t)r][(size_t)p];
-        if (!c) continue;
-        dst.push_back(((int64_t)S.bounds[(size_t)r] + P.cut[(size_t)r][(size_t)p]) * k);
-        src.push_back((P.off[(size_t)p] + (int64_t)r * P.maxc[(size_t)p]) * k);
-        cnt.push_back(c * k);
-        P.max_seg = std::max<int64_t>(P.max_seg, c * k);
-      }
-    P.nseg = (int)cnt.size();
-    P.tab_at = tab.size();
-    tab.insert(tab.end(), dst.begin(), dst.end());
-    tab.insert(tab.end(), src.begin(), src.end());
-    tab.insert(tab.end(), cnt.begin(), cnt.end());
+  // whole-shard mode launches the single-vector product as all np calls of fs_spmv_part (the two-pass pair by ranges of panels
+  // IS the product), the k-column product as ONE fs_spmm (whatever plan the prepare left: row kernel, column sweeps, one sweep)
+  X.whole = [&, k, np](int r) -> int {
+    if (rows(r) <= 0) return FS_OK;
+    if (k > 1) return fs_spmm(S.shard[(size_t)r], local[(size_t)r], in[(size_t)r], k, D->stream[r]);
+    for (int p = 0; p < np; ++p)
+      if (int rc = fs_spmv_part(S.shard[(size_t)r], 0, local[(size_t)r], in[(size_t)r], p, np, D->stream[r])) return rc;
     return FS_OK;
   };
-  if (int rc = side_parts(M->a, W.pa)) return rc;
-  if (with_t)
-    if (int rc = side_parts(M->t, W.pt)) return rc;
-  const int64_t pad_rows = std::max<int64_t>((int64_t)n * mr, std::max<int64_t>(W.pa.off[(size_t)W.pa.np], with_t ? W.pt.off[(size_t)W.pt.np] : 0));
-  const size_t F = (size_t)(M->ncol ? M->ncol : 1) * k, N = (size_t)(M->nrow ? M->nrow : 1) * k;
-  for (int r = 0; r < n; ++r) {
-    FS_HIP(hipSetDevice(D->dev[r]));
-    FS_HIP(hipMalloc(&W.x[(size_t)r], sizeof(double) * F));
-    FS_HIP(hipMalloc(&W.y[(size_t)r], sizeof(double) * N));
-    FS_HIP(hipMalloc(&W.z[(size_t)r], sizeof(double) * F));
-    // (the send window of a part starts at its first row and is maxc[p] rows long: it may run past the shard's last row)
-    FS_HIP(hipMalloc(&W.la[(size_t)r], sizeof(double) * (size_t)(2 * (int64_t)M->a.max_rows + 1) * k));
-    FS_HIP(hipMalloc(&W.lt[(size_t)r], sizeof(double) * (size_t)(2 * (int64_t)(with_t ? M->t.max_rows : 0) + 1) * k));
-    FS_HIP(hipMalloc(&W.pad[(size_t)r], sizeof(double) * (size_t)(pad_rows + 1) * k));
-    FS_HIP(hipMalloc(&W.tab[(size_t)r], sizeof(int64_t) * (tab.size() + 1)));
-    if (!tab.empty()) FS_HIP(hipMemcpy(W.tab[(size_t)r], tab.data(), sizeof(int64_t) * tab.size(), hipMemcpyHostToDevice));
-    FS_HIP(hipMalloc(&W.sol[(size_t)r], sizeof(double) * F));
-    FS_HIP(hipMalloc(&W.r[(size_t)r], sizeof(double) * F));
-    FS_HIP(hipMalloc(&W.b[(size_t)r], sizeof(double) * F));
-    FS_HIP(hipMalloc(&W.part[(size_t)r], sizeof(double) * fs::kCgPartDoubles));
-    FS_HIP(hipMalloc(&W.red[(size_t)r], sizeof(double) * 4));
-    FS_HIP(hipMalloc(&W.st[(size_t)r], sizeof(double) * fs::kCgStateDoubles));
-  }
-  W.ready = true;      // (a failure above leaves ready = false: the next call frees what exists and starts over)
-  return FS_OK;
-}
-
-// the whole-shard exchange of a k-column product: ONE all-gather of max_rows * k doubles per rank behind the finished local product
-int dist_gather_k(fs_dist_matrix_t M, bool transposed, const std::vector<double *> &out)
-{
-  fs_dist_t D = M->D;
-  const int n = D->n;
-  KWork &W = M->kw;
-  DistSide &S = transposed ? M->t : M->a;
-  const int k = W.k;
-  const std::vector<double *> &loc = transposed ? W.lt : W.la;
-  std::vector<const double *> send((size_t)n);
-  std::vector<hipEvent_t> ready((size_t)n);
-  for (int r = 0; r < n; ++r) {
-    FS_HIP(hipSetDevice(D->dev[r]));
-    FS_HIP(hipEventRecord(S.ev[(size_t)r][0], D->stream[r]));
-    FS_HIP(hipStreamWaitEvent(D->comm_stream[r], S.ev[(size_t)r][0], 0));
-    send[(size_t)r] = loc[(size_t)r];
-    ready[(size_t)r] = S.ev[(size_t)r][0];
-  }
-  // (the send window is max_rows * k doubles from the start of the local output; the buffer has that room)
-  if (int rc = exchange_equal(D, send, W.pad, (size_t)S.max_rows * (size_t)k, D->comm_stream, ready)) return rc;
-  const int nseg = transposed ? W.nseg_t : W.nseg_a;
-  for (int r = 0; r < n; ++r) {
-    FS_HIP(hipSetDevice(D->dev[r]));
-    const int64_t *tab = W.tab[(size_t)r] + (transposed ? 3 * (size_t)W.nseg_a : 0);
-    if (int rc = fs_copy_segments(nseg, tab, (int64_t)S.max_rows * k, W.pad[(size_t)r], out[(size_t)r], D->comm_stream[r])) return rc;
-    FS_HIP(hipEventRecord(S.done[(size_t)r], D->comm_stream[r]));
-    FS_HIP(hipStreamWaitEvent(D->stream[r], S.done[(size_t)r], 0));
-  }
-  return FS_OK;
-}
-
-// out = M in for k row-major columns on every rank.  Where the local k-column product finishes its rows part by part (fs_spmm_part:
-// the one-sweep plan of k = 2, 4 -- the block-CG products) the exchange runs INSIDE the product like dist_product's: the all-gather
-// of the rows part p finished under part p + 1, one unpack at the end.  Every other plan (row kernel, column sweeps), FS_DIST_PARTS=1
-// and a context gone conservative: the local product, then ONE whole-shard all-gather.
-int dist_product_k(fs_dist_matrix_t M, bool transposed, const std::vector<double *> &in, const std::vector<double *> &out)
-{
-  fs_dist_t D = M->D;
-  const int n = D->n;
-  KWork &W = M->kw;
-  DistSide &S = transposed ? M->t : M->a;
-  KParts &P = transposed ? W.pt : W.pa;
-  const int k = W.k;
-  const std::vector<double *> &loc = transposed ? W.lt : W.la;
-  if (D->broken) { fs::set_error("fs_dist: this context is unusable after an RCCL error (its communicators were aborted)"); return FS_ERR_HIP; }
-  ++g_products;
-  if (D->conservative || P.np <= 1 || !P.real) {
-    for (int r = 0; r < n; ++r) {
-      const int nl = S.bounds[(size_t)r + 1] - S.bounds[(size_t)r];
-      FS_HIP(hipSetDevice(D->dev[r]));
-      if (nl > 0)
-        if (int rc = fs_spmm(S.shard[(size_t)r], loc[(size_t)r], in[(size_t)r], k, D->stream[r])) return rc;
-    }
-    return dist_gather_k(M, transposed, out);
-  }
-  const int np = P.np;
-  for (int p = 0; p < np; ++p) {
-    std::vector<const double *> send((size_t)n);
-    std::vector<double *> recv((size_t)n);
-    std::vector<hipEvent_t> ready((size_t)n);
-    for (int r = 0; r < n; ++r) {
-      const int nl = S.bounds[(size_t)r + 1] - S.bounds[(size_t)r];
-      FS_HIP(hipSetDevice(D->dev[r]));
-      if (nl > 0)
-        if (int rc = fs_spmm_part(S.shard[(size_t)r], 0, loc[(size_t)r], in[(size_t)r], k, p, np, D->stream[r])) return rc;
-      FS_HIP(hipEventRecord(S.ev[(size_t)r][(size_t)p], D->stream[r]));
-      FS_HIP(hipStreamWaitEvent(D->comm_stream[r], S.ev[(size_t)r][(size_t)p], 0));
-      send[(size_t)r] = loc[(size_t)r] + (int64_t)P.cut[(size_t)r][(size_t)p] * k;
-      recv[(size_t)r] = W.pad[(size_t)r] + P.off[(size_t)p] * k;
-      ready[(size_t)r] = S.ev[(size_t)r][(size_t)p];
-    }
-    if (int rc = exchange_equal(D, send, recv, (size_t)P.maxc[(size_t)p] * (size_t)k, D->comm_stream, ready, take_injection(p))) {
-      D->conservative = true;
-      if (D->use_rccl) return rc;          // exchange_equal aborted the communicators
-      // virtual ranks: finish the local product, then the whole-shard exchange (see dist_product)
-      for (int q = p + 1; q < np; ++q)
-        for (int r = 0; r < n; ++r) {
-          if (S.bounds[(size_t)r + 1] == S.bounds[(size_t)r]) continue;
-          FS_HIP(hipSetDevice(D->dev[r]));
-          if (int rc2 = fs_spmm_part(S.shard[(size_t)r], 0, loc[(size_t)r], in[(size_t)r], k, q, np, D->stream[r])) return rc2;
-        }
-      if (int rc2 = dist_sync(D)) return rc2;
-      return dist_gather_k(M, transposed, out);
-    }
-  }
-  for (int r = 0; r < n; ++r) {
-    FS_HIP(hipSetDevice(D->dev[r]));
-    if (int rc = fs_copy_segments(P.nseg, W.tab[(size_t)r] + P.tab_at, P.max_seg, W.pad[(size_t)r], out[(size_t)r], D->comm_stream[r])) return rc;
-    FS_HIP(hipEventRecord(S.done[(size_t)r], D->comm_stream[r]));
-    FS_HIP(hipStreamWaitEvent(D->stream[r], S.done[(size_t)r], 0));
-  }
-  return FS_OK;
+  // k > 1 also goes whole-shard when no rank finishes rows in more than one part (!real: every plan but the one sweep of k = 2, 4):
+  // np all-gathers would hide nothing.  k = 1 asks only for the part count.
+  const bool whole_shard = D->conservative || np <= 1 || (k > 1 && !X.P.real);
+  // FS_DIST_THREADS=1 moves only the k = 1 products to the issuing threads; the k-column products have always been issued by the
+  // calling thread.  An inherited asymmetry, not a decision.
+  const bool threads = D->workers != nullptr && k == 1;
+  return run_product(D, X, out, whole_shard, threads);
 }
 
 }  // namespace
@@ -1113,15 +973,8 @@ long fs_debug_dist_products(void) { return g_products.load(); }   // diagnostics
 // follows the product; 0: no k-column product was made yet)
 int fs_debug_dist_k_parts(fs_dist_matrix_t M, int transposed)
 {
-  if (!M || !M->kw.ready) return 0;
-  const KParts &P = transposed ? M->kw.pt : M->kw.pa;
-  int most = 0;
-  for (const std::vector<int> &c : P.cut) {
-    int busy = 0;
-    for (size_t p = 0; p + 1 < c.size(); ++p) busy += c[p + 1] > c[p];
-    most = std::max(most, busy);
-  }
-  return most;
+  if (!M || !M->kw.mem.ready) return 0;
+  return fs::most_busy_parts((transposed ? M->kw.pt : M->kw.pa).cut);
 }
 
 // the same for the single-vector product of one side (0: no product made on that side yet)
@@ -1129,14 +982,7 @@ int fs_debug_dist_parts(fs_dist_matrix_t M, int transposed)
 {
   if (!M) return 0;
   const DistSide &S = transposed ? M->t : M->a;
-  if (!S.built) return 0;
-  int most = 0;
-  for (const std::vector<int> &c : S.cut) {
-    int busy = 0;
-    for (size_t p = 0; p + 1 < c.size(); ++p) busy += c[p + 1] > c[p];
-    most = std::max(most, busy);
-  }
-  return most;
+  return S.built ? fs::most_busy_parts(S.plan.cut) : 0;
 }
 
 int fs_dist_ndev(fs_dist_t D) { return D ? D->n : FS_ERR_ARG; }
@@ -1491,36 +1337,40 @@ fs_matrix_t fs_dist_matrix_shard(fs_dist_matrix_t M, int rank, int transposed)
   return (transposed ? M->t : M->a).shard[(size_t)rank];
 }
 
-// y = M x with the caller's vectors in host memory or in HBM (vec_in / vec_out): one direction of the matrix
-static int dist_apply(fs_dist_matrix_t M, bool transposed, double *y, const double *x)
+// Y[rows of M, k] = M X, row-major, with the caller's vectors in host memory or in HBM (vec_in / vec_out): one direction of the
+// matrix.  k = 1 works on the handle's x / y / z, k > 1 on the k-column work space (prepared on first use of a k: ensure_k).
+static int dist_apply(fs_dist_matrix_t M, bool transposed, double *y, const double *x, int k)
 {
   std::lock_guard<std::mutex> g(M->lock);
   std::lock_guard<std::mutex> gd(M->D->lock);
   DeviceGuard guard;
+  if (k > 1)
+    if (int rc = ensure_k(M, k)) return rc;
   DistSide &S = transposed ? M->t : M->a;
+  const std::vector<double *> &vx = k > 1 ? M->kw.x : M->x, &vy = k > 1 ? M->kw.y : M->y, &vz = k > 1 ? M->kw.z : M->z;
   // (u of z = A' u lives where y does: A then A' chains without a copy)
-  const std::vector<double *> &own_in = transposed ? M->y : M->x, &own_out = transposed ? M->z : M->y;
+  const std::vector<double *> &own_in = transposed ? vy : vx, &own_out = transposed ? vz : vy;
   std::vector<double *> in, out;
   int direct = -1;
-  if (int rc = vec_in(M, own_in, x, (size_t)S.ncol, in, true)) return rc;
+  if (int rc = vec_in(M, own_in, x, (size_t)S.ncol * k, in, true)) return rc;
   if (int rc = vec_out(M, own_out, y, out, &direct)) return rc;
-  if (int rc = dist_product(M->D, S, in, out)) return rc;
+  if (int rc = dist_product(M, transposed, k, in, out)) return rc;
   if (direct < 0)
-    if (int rc = vec_store(M, 0, y, own_out[0], (size_t)S.nrow)) return rc;
+    if (int rc = vec_store(M, 0, y, own_out[0], (size_t)S.nrow * k)) return rc;
   return dist_sync(M->D);
 }
 
 int fs_dist_spmv(fs_dist_matrix_t M, double *y, const double *x)
 {
   if (!M || !y || !x) { fs::set_error("fs_dist_spmv: NULL argument"); return FS_ERR_ARG; }
-  return dist_apply(M, false, y, x);
+  return dist_apply(M, false, y, x, 1);
 }
 
 int fs_dist_spmv_t(fs_dist_matrix_t M, double *z, const double *u)
 {
   if (!M || !z || !u) { fs::set_error("fs_dist_spmv_t: NULL argument"); return FS_ERR_ARG; }
   if (!M->t.built) { fs::set_error("fs_dist_spmv_t: call fs_dist_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
-  return dist_apply(M, true, z, u);
+  return dist_apply(M, true, z, u, 1);
 }
 
 // z[ncol] = A'(A x[ncol]) + lambda x (bcsr_AA_mul_B, csr.h:305-319, with lambda = 0; bsbm_AtA, cg.h:9-22, across the GPUs): y = A x
@@ -1536,8 +1386,8 @@ int fs_dist_ata(fs_dist_matrix_t M, double *z, const double *x, double lambda)
   int direct = -1;
   if (int rc = vec_in(M, M->x, x, (size_t)M->ncol, in, true)) return rc;
   if (int rc = vec_out(M, M->z, z, out, &direct)) return rc;
-  if (int rc = dist_product(M->D, M->a, in, M->y)) return rc;
-  if (int rc = dist_product(M->D, M->t, M->y, out)) return rc;
+  if (int rc = dist_product(M, false, 1, in, M->y)) return rc;
+  if (int rc = dist_product(M, true, 1, M->y, out)) return rc;
   if (lambda != 0.0) {
     const int r = direct < 0 ? 0 : direct;
     FS_HIP(hipSetDevice(M->D->dev[r]));
@@ -1557,7 +1407,7 @@ int fs_dist_spmv_resident(fs_dist_matrix_t M)
   std::lock_guard<std::mutex> g(M->lock);
   std::lock_guard<std::mutex> gd(M->D->lock);
   DeviceGuard guard;
-  if (int rc = dist_product(M->D, M->a, M->x, M->y)) return rc;
+  if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;
   return dist_sync(M->D);
 }
 
@@ -1568,7 +1418,7 @@ int fs_dist_spmv_t_resident(fs_dist_matrix_t M)
   std::lock_guard<std::mutex> g(M->lock);
   std::lock_guard<std::mutex> gd(M->D->lock);
   DeviceGuard guard;
-  if (int rc = dist_product(M->D, M->t, M->y, M->z)) return rc;
+  if (int rc = dist_product(M, true, 1, M->y, M->z)) return rc;
   return dist_sync(M->D);
 }
 
@@ -1651,24 +1501,18 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
   const bool gather = fs::options().dist_cg_scheme == 1 && n > 1;
   DistSide &T = M->t;
   CgWork &W = M->cg;
-  if (!W.ready || W.F != F) {
+  if (!W.mem.ready || W.F != F) {
     free_cg(D, W);
-    for (auto *v : {&W.sol, &W.r, &W.b, &W.p, &W.q, &W.part, &W.red, &W.redall, &W.st}) v->assign((size_t)n, nullptr);
     W.F = F;
-    const size_t fl = (size_t)(F ? F : 1) + (size_t)T.max_rows + 1;       // (a slice is sent as a window of max_rows doubles)
-    for (int d = 0; d < n; ++d) {
-      FS_HIP(hipSetDevice(D->dev[d]));
-      FS_HIP(hipMalloc(&W.sol[(size_t)d], sizeof(double) * fl));
-      FS_HIP(hipMalloc(&W.r[(size_t)d], sizeof(double) * fl));
-      FS_HIP(hipMalloc(&W.b[(size_t)d], sizeof(double) * fl));
-      FS_HIP(hipMalloc(&W.p[(size_t)d], sizeof(double) * fl));
-      FS_HIP(hipMalloc(&W.q[(size_t)d], sizeof(double) * fl));
-      FS_HIP(hipMalloc(&W.part[(size_t)d], sizeof(double) * fs::kCgPartDoubles));
-      FS_HIP(hipMalloc(&W.red[(size_t)d], sizeof(double) * 4));
-      FS_HIP(hipMalloc(&W.redall[(size_t)d], sizeof(double) * (size_t)(n + 1)));
-      FS_HIP(hipMalloc(&W.st[(size_t)d], sizeof(double) * fs::kCgStateDoubles));
-    }
-    W.ready = true;
+    const size_t fl = (size_t)(F ? F : 1) + (size_t)T.plan.max_rows + 1;       // (a slice is sent as a window of max_rows doubles)
+    if (int rc = W.mem.fill(D, [&](int d) -> int {
+          for (std::vector<double *> *v : {&W.sol, &W.r, &W.b, &W.p, &W.q})
+            if (int rc2 = W.mem.get(d, *v, fl)) return rc2;
+          if (int rc2 = W.mem.get(d, W.part, (size_t)fs::kCgPartDoubles)) return rc2;
+          if (int rc2 = W.mem.get(d, W.red, 4)) return rc2;
+          if (int rc2 = W.mem.get(d, W.redall, (size_t)(n + 1))) return rc2;
+          return W.mem.get(d, W.st, (size_t)fs::kCgStateDoubles);
+        })) return rc;
   }
   {
     std::vector<double *> unused;
@@ -1680,7 +1524,6 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
     FS_HIP(hipSetDevice(D->dev[d]));
     if (int rc = fl[(size_t)d].init()) return rc;
   }
-  std::vector<hipEvent_t> none((size_t)n, nullptr);
   // the sum over the ranks of every rank's red[0] (left there by a partial reduction), in rank order, then the scalar step `step`
   // (send slots red[0] / red[1] alternate: a rank may be one exchange ahead of another that still reads its previous partial;
   // the scalar step leaves its sum in red[2])
@@ -1716,13 +1559,13 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
                                            D->stream[d])) return rc;
     }
     if (int rc = combine(fs::kStepCgStart, tol)) return rc;
-    if (int rc = dist_gather(D, T, W.p, M->x)) return rc;                // the whole p on every rank
+    if (int rc = run_gather(D, exchange_of(M, true, 1), W.p, M->x, false)) return rc;     // the whole p on every rank
   }
   int seen = kRanksGoOn;
   for (int iter = 0; iter < F; iter++) {
-    if (int rc = dist_product(D, M->a, M->x, M->y)) return rc;           // y = A p, its all-gather inside
+    if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;       // y = A p, its all-gather inside
     if (!gather) {
-      if (int rc = dist_product(D, T, M->y, M->z)) return rc;            // q = A' y, its all-gather inside
+      if (int rc = dist_product(M, true, 1, M->y, M->z)) return rc;      // q = A' y, its all-gather inside
       for (int d = 0; d < n; ++d) {
         FS_HIP(hipSetDevice(D->dev[d]));
         if (int rc = fs::cg_dev_steps(F, lambda, W.sol[(size_t)d], W.r[(size_t)d], M->x[(size_t)d], M->z[(size_t)d], W.part[(size_t)d],
@@ -1749,7 +1592,7 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
         FS_HIP(hipSetDevice(D->dev[d]));
         if (int rc = fs::cg_dev_step_c(nl, W.p[(size_t)d], W.r[(size_t)d], W.st[(size_t)d], D->stream[d])) return rc;
       }
-      if (int rc = dist_gather(D, T, W.p, M->x)) return rc;              // the new p on every rank
+      if (int rc = run_gather(D, exchange_of(M, true, 1), W.p, M->x, false)) return rc;   // the new p on every rank
     }
     seen = ranks_after_iteration(D, fl, W.st, iter, "fs_dist_cg", [](int) { return FS_OK; });
     if (seen < 0) return seen;
@@ -1777,31 +1620,13 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
 
 // Y[nrow, k] = A X[ncol, k], row-major host matrices (csr_A_mul_Bn / bcsr_A_mul_Bn / bsbm_A_mul_Bn across the GPUs, csr.h:441,
 // 257; sparse.h:318): every device multiplies its shard (the k-column kernels of fs_spmm, prepared on first use of a k) and the
-// Y shards are all-gathered, one whole-shard exchange behind the local product.  fs_dist_spmm_t: Z[ncol, k] = A' U[nrow, k].
-static int dist_apply_k(fs_dist_matrix_t M, bool transposed, double *Y, const double *X, int k)
-{
-  std::lock_guard<std::mutex> g(M->lock);
-  std::lock_guard<std::mutex> gd(M->D->lock);
-  DeviceGuard guard;
-  if (int rc = ensure_k(M, k)) return rc;
-  DistSide &S = transposed ? M->t : M->a;
-  KWork &W = M->kw;
-  const std::vector<double *> &own_in = transposed ? W.y : W.x, &own_out = transposed ? W.z : W.y;
-  std::vector<double *> in, out;
-  int direct = -1;
-  if (int rc = vec_in(M, own_in, X, (size_t)S.ncol * k, in, true)) return rc;
-  if (int rc = vec_out(M, own_out, Y, out, &direct)) return rc;
-  if (int rc = dist_product_k(M, transposed, in, out)) return rc;
-  if (direct < 0)
-    if (int rc = vec_store(M, 0, Y, own_out[0], (size_t)S.nrow * k)) return rc;
-  return dist_sync(M->D);
-}
-
+// Y shards are all-gathered -- inside the product where the plan finishes rows part by part, else behind it (dist_product).
+// fs_dist_spmm_t: Z[ncol, k] = A' U[nrow, k].
 int fs_dist_spmm(fs_dist_matrix_t M, double *Y, const double *X, int k)
 {
   if (!M || !Y || !X || k < 1) { fs::set_error("fs_dist_spmm: bad argument"); return FS_ERR_ARG; }
   if (k == 1) return fs_dist_spmv(M, Y, X);
-  return dist_apply_k(M, false, Y, X, k);
+  return dist_apply(M, false, Y, X, k);
 }
 
 int fs_dist_spmm_t(fs_dist_matrix_t M, double *Z, const double *U, int k)
@@ -1809,7 +1634,7 @@ int fs_dist_spmm_t(fs_dist_matrix_t M, double *Z, const double *U, int k)
   if (!M || !Z || !U || k < 1) { fs::set_error("fs_dist_spmm_t: bad argument"); return FS_ERR_ARG; }
   if (!M->t.built) { fs::set_error("fs_dist_spmm_t: build the transpose first"); return FS_ERR_NO_TRANSPOSE; }
   if (k == 1) return fs_dist_spmv_t(M, Z, U);
-  return dist_apply_k(M, true, Z, U, k);
+  return dist_apply(M, true, Z, U, k);
 }
 
 // (A'A + lambda I) X = B for two right-hand sides, row-major ncol x 2: bsbm_cg2 (cg.h:85-187) across the GPUs, everything
@@ -1847,8 +1672,8 @@ int fs_dist_cg2(fs_dist_matrix_t M, double *X_host, const double *B_host, double
   }
   int seen = kRanksGoOn;
   for (int iter = 0; iter < F; iter++) {
-    if (int rc = dist_product_k(M, false, W.x, W.y)) return rc;          // TMP = A P
-    if (int rc = dist_product_k(M, true, W.y, W.z)) return rc;           // Q = A' TMP
+    if (int rc = dist_product(M, false, 2, W.x, W.y)) return rc;         // TMP = A P
+    if (int rc = dist_product(M, true, 2, W.y, W.z)) return rc;          // Q = A' TMP
     seen = ranks_after_iteration(D, fl, W.st, iter, "fs_dist_cg2", [&](int d) {   // a rank's steps and its flags in one pass
       return fs::cg2_dev_steps(F, lambda, W.sol[(size_t)d], W.r[(size_t)d], W.x[(size_t)d], W.z[(size_t)d], W.part[(size_t)d],
                                W.red[(size_t)d], W.st[(size_t)d], D->stream[d]);
@@ -1875,5 +1700,13 @@ int fs_dist_cg2(fs_dist_matrix_t M, double *X_host, const double *B_host, double
 double *fs_dist_x(fs_dist_matrix_t M, int rank) { return (M && rank >= 0 && rank < M->D->n) ? M->x[(size_t)rank] : nullptr; }
 double *fs_dist_y(fs_dist_matrix_t M, int rank) { return (M && rank >= 0 && rank < M->D->n) ? M->y[(size_t)rank] : nullptr; }
 double *fs_dist_z(fs_dist_matrix_t M, int rank) { return (M && rank >= 0 && rank < M->D->n) ? M->z[(size_t)rank] : nullptr; }
+
+// diagnostics, not in include/fastsparse_hip.h: rank's resident copy of the k-column X (0), Y (1) or Z (2) of the handle's current
+// k -- what fs_dist_x / _y / _z are to the single-vector products -- or NULL before the first k-column product
+double *fs_debug_dist_k_vector(fs_dist_matrix_t M, int rank, int which)
+{
+  if (!M || !M->kw.mem.ready || rank < 0 || rank >= M->D->n || which < 0 || which > 2) return nullptr;
+  return (which == 0 ? M->kw.x : which == 1 ? M->kw.y : M->kw.z)[(size_t)rank];
+}
 
 }  // extern "C"

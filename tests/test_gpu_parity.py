@@ -2741,6 +2741,87 @@ print("OK")
     assert p.returncode == 0 and "OK" in p.stdout, ("k2first", p.stdout[-1500:] + p.stderr[-1500:])
 
 
+_FAILED_EXCHANGE_CHILD = r'''
+import ctypes as C, os, sys, numpy as np
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+from libfastsparse_amd import capi
+from oracle import pyoracle as O, pysynth
+L = capi.lib()
+k, transposed, ranks = int(sys.argv[1]), int(sys.argv[2]), 3
+nrow, ncol = 196_608, 589_824
+for f in (L.fs_debug_dist_parts, L.fs_debug_dist_k_parts):
+    f.argtypes = [C.c_void_p, C.c_int]
+L.fs_debug_dist_k_vector.argtypes = [C.c_void_p, C.c_int, C.c_int]
+L.fs_debug_dist_k_vector.restype = C.c_void_p
+rp, cc, _ = pysynth.powerlaw(nrow, ncol, 1.1, 1000, 0xFA11, valued=False)
+assert 7.0 <= len(cc) / nrow <= 9.0
+rows_all = np.repeat(np.arange(nrow, dtype=np.int32), np.diff(rp))
+n_in, n_out = (nrow, ncol) if transposed else (ncol, nrow)
+X = np.ascontiguousarray(np.stack([(np.arange(n_in) * (j + 3) %% 13 - 6).astype(np.float64) for j in range(k)], 1))
+ref = np.stack([O.coo_tmul(ncol, rows_all, cc, None, np.ascontiguousarray(X[:, j])) if transposed else
+                O.csr_mul(nrow, rp, cc, None, np.ascontiguousarray(X[:, j])) for j in range(k)], 1)
+capi.set_option("binning", 2)
+capi.set_option("bin_rows", 256)     # many panels: the local products really run in parts
+D = L.fs_dist_create(ranks, (C.c_int * ranks)(*([0] * ranks)))
+assert D, L.fs_last_error()
+assert L.fs_dist_uses_rccl(D) == 0 and L.fs_dist_is_conservative(D) == 0
+M = L.fs_dist_csr_create(D, nrow, ncol, len(cc), rp.ctypes.data, cc.ctypes.data, None)
+assert M, L.fs_last_error()
+if transposed:
+    assert L.fs_dist_matrix_build_transpose_device(M) == 0, L.fs_last_error()
+parts1 = L.fs_debug_dist_parts(M, transposed)
+print("parts of the single-vector product on the side:", parts1, flush=True)
+if k != 3:
+    assert parts1 >= 2, parts1
+for rep in range(2):                 # the product that meets the injected failure (the first of the process), then one more
+    Y = np.full((n_out, k), -1.0)
+    rc = (L.fs_dist_spmm_t if transposed else L.fs_dist_spmm)(M, Y.ctypes.data, X.ctypes.data, k)
+    assert rc == 0, L.fs_last_error()
+    assert np.array_equal(Y, ref), rep
+    for r in range(ranks):
+        if k == 1:
+            ptr = (L.fs_dist_z if transposed else L.fs_dist_y)(M, r)
+        else:
+            ptr = L.fs_debug_dist_k_vector(M, r, 2 if transposed else 1)
+        g = np.empty((n_out, k)); assert ptr and L.fs_copy_to_host(g.ctypes.data, ptr, 8 * n_out * k) == 0
+        assert np.array_equal(g, ref), (rep, r)
+    if k > 1:                        # (the k-column plan exists from the first k-column product on: the plan that product ran on)
+        kparts = L.fs_debug_dist_k_parts(M, transposed)
+        print("parts of the k-column product on the side:", kparts, flush=True)
+        assert kparts <= 1 if k == 3 else kparts >= 2, kparts
+    # k = 3 finishes no rows in parts: whole-shard mode, the injection never fires, the context stays as it was
+    assert L.fs_dist_is_conservative(D) == (0 if k == 3 else 1), rep
+L.fs_dist_matrix_destroy(M); L.fs_dist_destroy(D)
+print("OK")
+''' % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize("k,side,fail_part", [(1, "A'", "0"), (2, "A'", "1"), (4, "A", "0"), (4, "A'", "last"), (3, "A", "1")])
+def test_native_multi_gpu_failed_exchange_every_k_and_side(hip, k, side, fail_part):
+    """One engine runs the product of every k on both sides, so every (k, side) meets the injected failure of an exchange
+    (FS_DIST_FAIL_PART, virtual ranks) the same way: the remaining parts run, the streams drain, ONE whole-shard gather finishes the
+    product and the context stays conservative.  Per case, in a child process of its own (the environment and the injection are
+    read once per process), on 3 virtual ranks and a binary power-law matrix with about 8 entries per row (binning 2, bin_rows
+    256; integer-valued x, so sums are exact): the product that meets the failure -- the first of the
+    process -- is the oracle's bit for bit, so is every rank's resident copy, fs_dist_is_conservative is 1 afterwards, and a
+    second product is exact again.  Before the product the side's single-vector product must finish rows in >= 2 parts
+    (fs_debug_dist_parts); for k > 1 the k-column plan only exists once the first k-column product made it, so
+    fs_debug_dist_k_parts >= 2 is asserted right behind that product, on the plan it ran on.  k = 3 finishes no rows in parts
+    (<= 1): the injection must not fire and the context must stay non-conservative.  "last": the last of the FS_DIST_PARTS
+    (default 4) parts.
+
+    Shape: 196 608 x 589 824 (grown from 12 288 x 4 096, where every product finished its rows in ONE part).  A two-pass
+    product is cut by generations of resident workgroups, so a shard finishes rows in parts only with more panels than the 256 CUs:
+    at bin_rows 256 (about 205 rows per panel) more than 52 224 rows -- A's shards hold about 65 000 (2 parts).  Failing the LAST
+    of 4 parts needs rows in all 4: more than 768 panels, 157 082 rows -- the shards of A' hold about 196 000."""
+    import subprocess
+    import sys
+    part = str(int(os.environ.get("FS_DIST_PARTS", "4")) - 1) if fail_part == "last" else fail_part
+    p = subprocess.run([sys.executable, "-c", _FAILED_EXCHANGE_CHILD, str(k), str(int(side == "A'"))], env=dict(os.environ, FS_DIST_FAIL_PART=part),
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0 and "OK" in p.stdout, (k, side, fail_part, p.stdout[-1500:] + p.stderr[-1500:])
+
+
 @pytest.mark.parametrize("valued", [False, True])
 def test_lds_staged_kernel_fixed_order_sums(hip, valued):
     """VERDICT r3 item 2: the LDS-staged kernel under fixed-order sums.  A config-3-shaped matrix (tall, dense tiles; binary like
