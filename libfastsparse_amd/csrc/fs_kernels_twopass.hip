@@ -148,7 +148,39 @@ __device__ __forceinline__ v4u row_ids(v4u raw)
   return v4u{(off + s0) | ((off + s1) << 16), (off + s2) | ((off + s3) << 16), (off + s4) | ((off + s5) << 16), (off + s6) | ((off + s7) << 16)};
 }
 
+// the same ids for the sixteen-wave pass 2 (reduce_panel), where a lane owns the entry pair {e, e + 1} (e even) and the 64 lanes of a wave
+// read 128 consecutive entries: one 4-byte load of two 16-bit ids, or (L8) the pair's two step bytes with the group's gbase in
+// the upper half.  A group of 16 entries is 8 neighbouring lanes (a panel's entries start on a group boundary), so the row in
+// front of a lane's pair is gbase + the steps of the lanes below it in the group: a prefix over 8 lanes, three DPP row_shr steps
+// (rows of 16 lanes hold two groups: a value shifted in from the lower group is masked out).
+template <bool L8>
+__device__ __forceinline__ unsigned line_ids_load(const uint16_t *__restrict__ lrow, const uint8_t *__restrict__ lrow8,
+                                                  const uint16_t *__restrict__ gbase, int64_t e)
+{
+  if (!L8) return *(const unsigned *)(lrow + e);
+  return (unsigned)*(const uint16_t *)(lrow8 + e) | ((unsigned)gbase[e >> kBinGroupLog] << 16);
+}
+
+template <bool L8>
+__device__ __forceinline__ unsigned line_ids(unsigned raw)
+{
+  if (!L8) return raw;
+  const unsigned d0 = raw & 0xffu, own = d0 + ((raw >> 8) & 0xffu), l = threadIdx.x & 7u;
+  unsigned s = own, u;
+  u = (unsigned)__builtin_amdgcn_update_dpp(0, (int)s, 0x111 /* row_shr:1 */, 0xf, 0xf, false); s += l >= 1 ? u : 0u;
+  u = (unsigned)__builtin_amdgcn_update_dpp(0, (int)s, 0x112 /* row_shr:2 */, 0xf, 0xf, false); s += l >= 2 ? u : 0u;
+  u = (unsigned)__builtin_amdgcn_update_dpp(0, (int)s, 0x114 /* row_shr:4 */, 0xf, 0xf, false); s += l >= 4 ? u : 0u;
+  const unsigned off = (raw >> 16) + s - own;
+  return (off + d0) | ((off + own) << 16);
+}
+
 // pass 2: workgroup = one row panel; its products are contiguous.  ytile: the panel's slice of y in LDS.
+// The stream is read LINE-WISE: a wave takes 512 consecutive entries per step and each of its four load instructions 128 of them,
+// lane l the pair at 2 l -- 1 KiB of consecutive products per instruction, so every 128-byte line of the stream is asked for by ONE
+// instruction.  That is what lets the products, read once, be loaded non-temporal (NTLD, the default: config 2 - 3.6 % per product;
+// with a lane reading 64 consecutive bytes in four loads, four instructions asked for every line and the same policy cost + 14 %).
+// The ids stay plain loads: an instruction takes a fraction of a line of them.  Two steps (16 entries per lane) in flight in whole
+// rounds (straight-line code: see expand_share); what is left after the whole rounds is guarded.
 template <bool NTLD, bool L8 = false>
 __device__ __forceinline__ void reduce_panel(double *__restrict__ ytile, int panel, const unsigned *__restrict__ bin_ptr,
                                              const int *__restrict__ panel_row, const uint16_t *__restrict__ lrow,
@@ -160,44 +192,51 @@ __device__ __forceinline__ void reduce_panel(double *__restrict__ ytile, int pan
   for (int i = t; i < nr; i += kBinBlock) ytile[i] = 0.0;
   __syncthreads();
   const int64_t e0 = (int64_t)bin_ptr[panel] * kBinGroup, e1 = (int64_t)bin_ptr[panel + 1] * kBinGroup;
-  // 8 entries (64 bytes of products) per lane and step, two steps in flight in whole rounds (straight-line code:
-  // see expand_share); the last, partial round is guarded
 #define FS_ADD(idx, val) __hip_atomic_fetch_add(&ytile[idx], val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#define FS_ADD8(A, P)                                                  \
-  FS_ADD(A.x & 0xffffu, P[0].x); FS_ADD(A.x >> 16, P[0].y);            \
-  FS_ADD(A.y & 0xffffu, P[1].x); FS_ADD(A.y >> 16, P[1].y);            \
-  FS_ADD(A.z & 0xffffu, P[2].x); FS_ADD(A.z >> 16, P[2].y);            \
-  FS_ADD(A.w & 0xffffu, P[3].x); FS_ADD(A.w >> 16, P[3].y);
-  constexpr int64_t kRound = 16 * kBinBlock;
-  int64_t e = e0 + 8 * t;
-  for (; e - 8 * t + kRound <= e1; e += kRound) {
-    v4u a[2];
+#define FS_ADD2(A, P) FS_ADD((A) & 0xffffu, (P).x); FS_ADD((A) >> 16, (P).y);
+  constexpr int64_t kStep = 8 * kBinBlock, kRound = 2 * kStep;
+  const int wave0 = (t >> 6) * 512, lane0 = wave0 + 2 * (t & 63);   // inside a step: the wave's first entry, the lane's first pair
+  int64_t eb = e0;
+  for (; eb + kRound <= e1; eb += kRound) {
+    const int64_t e = eb + lane0;
+    unsigned a[2][4];
     v2d p[2][4];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int64_t ek = e + (int64_t)k * 8 * kBinBlock;
-      a[k] = row_ids_load<NTLD, L8>(lrow, lrow8, gbase, ek);
+    for (int k = 0; k < 2; ++k)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) p[k][j] = stream_load<NTLD>((const v2d *)(prod + ek + 2 * j));
-    }
+      for (int j = 0; j < 4; ++j) {
+        const int64_t ek = e + k * kStep + 128 * j;
+        a[k][j] = line_ids_load<L8>(lrow, lrow8, gbase, ek);
+        p[k][j] = stream_load<NTLD>((const v2d *)(prod + ek));
+      }
     __builtin_amdgcn_sched_barrier(0);
-    a[0] = row_ids<L8>(a[0]);
-    a[1] = row_ids<L8>(a[1]);
-    FS_ADD8(a[0], p[0])
-    FS_ADD8(a[1], p[1])
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned r = line_ids<L8>(a[k][j]);
+        FS_ADD2(r, p[k][j])
+      }
   }
-  // the last, partial round: whole waves stay together (the one-byte row ids shift a value between neighbouring lanes), the lanes
-  // past the end read the panel's last eight entries and skip their adds
-  for (; e - 8 * (t & 63) < e1; e += 8 * kBinBlock) {
-    const int64_t ec = e < e1 ? e : e1 - 8;
-    const v4u raw = row_ids_load<NTLD, L8>(lrow, lrow8, gbase, ec);
+  // the last, partial round: whole waves stay together (the one-byte row ids shift values between neighbouring lanes), the lanes
+  // past the end read the panel's last pair and skip their adds
+  for (; eb + wave0 < e1; eb += kStep) {
+    const int64_t e = eb + lane0;
+    unsigned a[4];
     v2d p[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) p[j] = stream_load<NTLD>((const v2d *)(prod + ec + 2 * j));
-    const v4u a = row_ids<L8>(raw);
-    if (e < e1) { FS_ADD8(a, p) }
+    for (int j = 0; j < 4; ++j) {
+      const int64_t ej = e + 128 * j, ec = ej < e1 ? ej : e1 - 2;
+      a[j] = line_ids_load<L8>(lrow, lrow8, gbase, ec);
+      p[j] = stream_load<NTLD>((const v2d *)(prod + ec));
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned r = line_ids<L8>(a[j]);
+      if (e + 128 * j < e1) { FS_ADD2(r, p[j]) }
+    }
   }
-#undef FS_ADD8
+#undef FS_ADD2
 #undef FS_ADD
   __syncthreads();
   for (int i = t; i < nr; i += kBinBlock) y[(int64_t)(r0 + i) * ys] = ytile[i];
@@ -705,6 +744,20 @@ static void ensure_two_byte_ids(BinnedCsr &N, hipStream_t s)
   N.lrow = p;       // (behind the synchronize: a later product on another stream finds the ids complete)
 }
 
+// the sixteen-wave pass 2 for the panels p0 .. p1; bit 8 of bin_flags (A/B runs): product loads plain instead of non-temporal
+static void launch_reduce(const BinnedCsr &N, double *out, int os, int p0, int p1, int flags, hipStream_t s)
+{
+#define FS_REDUCE(NT, RM, L8)                                                                                               \
+  hipLaunchKernelGGL((spmv_reduce_kernel<NT, RM, L8>), dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row, N.lrow, \
+                     N.prod, out, os, p0, N.lrow8, N.gbase)
+#define FS_REDUCE2(RM, L8) do { if (flags & 256) FS_REDUCE(false, RM, L8); else FS_REDUCE(true, RM, L8); } while (0)
+  if (N.bcols == kBinColsBig) FS_REDUCE2(kBinRowsBig, false);
+  else if (N.lrow8)           FS_REDUCE2(kBinRowsMax, true);       // one byte per row id (BinnedCsr::lrow8)
+  else                        FS_REDUCE2(kBinRowsMax, false);
+#undef FS_REDUCE2
+#undef FS_REDUCE
+}
+
 int launch_spmv_binned(const DeviceCsr &A, double *y, const double *x, hipStream_t s, int xs, int ys, int p0, int p1, int row0,
                        int row1)
 {
@@ -715,10 +768,11 @@ int launch_spmv_binned(const DeviceCsr &A, double *y, const double *x, hipStream
   if (!part) { p0 = 0; p1 = N.P; row0 = 0; row1 = A.nrow; }
   const int nwg1 = (options().bin_wgs > 0 && options().bin_wgs < N.nwg1) ? options().bin_wgs : N.nwg1;
   if (nwg1 > 0 && p0 == 0) {
-    // tuning switches (A/B runs): bits 0-1 pass-1 unroll (1: 8, 2: 2 steps; default 4), bit 2 pass-2 loads
-    // non-temporal, bit 3 pass-1 stores plain, bit 4 pass-1 loads non-temporal.  Defaults, measured on config 2
-    // (valued / pattern-only, ms per product): plain loads in both passes and non-temporal stores 0.95 / 0.69;
-    // non-temporal loads in pass 1 0.98 / 0.73, in pass 2 as well 1.09 / 0.84; plain stores 1.01 / 0.75
+    // tuning switches (A/B runs): bits 0-1 pass-1 unroll (1: 8, 2: 2 steps; default 4), bit 3 pass-1 stores plain,
+    // bit 4 pass-1 loads non-temporal (bit 8, pass-2 product loads plain: launch_reduce).  Defaults, measured on config 2
+    // (valued / pattern-only, ms per product): plain loads in pass 1 and non-temporal stores 0.95 / 0.69; non-temporal
+    // loads in pass 1 0.98 / 0.73; plain stores 1.01 / 0.75.  (Bit 2, pass-2 loads non-temporal, went with the pass 2
+    // whose lanes read 64 consecutive bytes: 1.09 / 0.84 there; on the line-wise pass 2 they are the default.)
     const int flags = options().bin_flags;
 #define FS_EXPAND4(V, U)                                                                                          \
   do {                                                                                                            \
@@ -751,24 +805,14 @@ int launch_spmv_binned(const DeviceCsr &A, double *y, const double *x, hipStream
     if (N.bcols == kBinColsBig && ordered)
       hipLaunchKernelGGL((spmv_reduce_ordered_kernel<false, kBinRowsBig, FS_ORDERED_DEPTH>), dim3(p1 - p0), dim3(64), 0, s, N.bin_ptr,
                          N.panel_row, N.lrow, N.prod, out, os, p0);
-    else if (N.bcols == kBinColsBig)
-      hipLaunchKernelGGL((spmv_reduce_kernel<false, kBinRowsBig>), dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row,
-                         N.lrow, N.prod, out, os, p0);
     else if (ordered && N.lrow8 && !N.lrow)
       hipLaunchKernelGGL((spmv_reduce_ordered_kernel<false, kBinRowsMax, FS_ORDERED_DEPTH, true>), dim3(p1 - p0), dim3(64), 0, s, N.bin_ptr,
                          N.panel_row, N.lrow, N.prod, out, os, p0, N.lrow8, N.gbase);
     else if (ordered)
       hipLaunchKernelGGL((spmv_reduce_ordered_kernel<false, kBinRowsMax, FS_ORDERED_DEPTH>), dim3(p1 - p0), dim3(64), 0, s, N.bin_ptr,
                          N.panel_row, N.lrow, N.prod, out, os, p0);
-    else if (N.lrow8)       // one byte per row id (BinnedCsr::lrow8): default loads only
-      hipLaunchKernelGGL((spmv_reduce_kernel<false, kBinRowsMax, true>), dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row, N.lrow,
-                         N.prod, out, os, p0, N.lrow8, N.gbase);
-    else if (options().bin_flags & 4)
-      hipLaunchKernelGGL(spmv_reduce_kernel<true>, dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row, N.lrow, N.prod,
-                         out, os, p0);
     else
-      hipLaunchKernelGGL(spmv_reduce_kernel<false>, dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row, N.lrow, N.prod,
-                         out, os, p0);
+      launch_reduce(N, out, os, p0, p1, options().bin_flags, s);
     FS_HIP(hipGetLastError());
   }
   if (N.split && row1 > row0) {
@@ -802,14 +846,7 @@ int launch_reduce_panels(const DeviceCsr &A, double *y, int p0, int p1, hipStrea
 {
   const BinnedCsr &N = *A.binned;
   if (p1 <= p0) return FS_OK;
-  if (N.bcols == kBinColsBig)
-    hipLaunchKernelGGL((spmv_reduce_kernel<false, kBinRowsBig>), dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row, N.lrow, N.prod,
-                       y, 1, p0);
-  else if (N.lrow8)
-    hipLaunchKernelGGL((spmv_reduce_kernel<false, kBinRowsMax, true>), dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row, N.lrow, N.prod,
-                       y, 1, p0, N.lrow8, N.gbase);
-  else
-    hipLaunchKernelGGL(spmv_reduce_kernel<false>, dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row, N.lrow, N.prod, y, 1, p0);
+  launch_reduce(N, y, 1, p0, p1, 0, s);
   FS_HIP(hipGetLastError());
   return FS_OK;
 }

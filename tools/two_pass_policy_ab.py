@@ -17,6 +17,6 @@ def t(flags, reps=40):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
 for rnd in range(2):
-    for flags, name in ((0, "default: plain loads, nt stores"), (8, "plain stores"), (4, "pass-2 nt loads"), (16, "pass-1 nt loads"), (24, "pass-1 nt loads + plain stores"), (1, "unroll 8"), (2, "unroll 2")):
+    for flags, name in ((0, "default: plain pass-1 loads, nt stores, nt pass-2 product loads"), (8, "plain stores"), (256, "pass-2 plain product loads"), (16, "pass-1 nt loads"), (24, "pass-1 nt loads + plain stores"), (1, "unroll 8"), (2, "unroll 2")):
         print(json.dumps({"what": "two-pass cache-policy A/B, config 2 A x", "bin_flags": flags, "name": name, "ms": t(flags)}), flush=True)
 capi.set_option("bin_flags", 0)
