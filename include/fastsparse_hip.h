@@ -86,7 +86,7 @@ int  fs_set_device(int device);
  * "reproducible", so that a solve is bit-identical from run to run like the reference's loops (cg.h:25-187); 0 = the default kernels.
  * "pcgn_kernel": fs_pcgn's per-iteration vector kernels, 0 = auto (see fs_pcgn), 1 = a lane per row, 2 = the 256-row panels staged
  * through LDS with coalesced accesses; both give the same bits.
- * "dist_cg_scheme" (FS_DIST_CG_SCHEME): fs_dist_cg, 0 every device keeps whole vectors, 1 every device keeps its slice (see there). */
+ * "dist_cg_scheme" (FS_DIST_CG_SCHEME): fs_dist_cg and fs_dist_pcg, 0 every device keeps whole vectors, 1 every device keeps its slice (see there). */
 int  fs_set_option(const char *name, int value);
 int  fs_get_option(const char *name);
 
@@ -451,6 +451,46 @@ int  fs_dist_swap_xy(fs_dist_matrix_t M);
  * option "cg_fixed_order" is 0.  b_host, x_host: ncol doubles; stops at ||r|| <= tol ||b||.
  * CLOBBERS fs_dist_x / fs_dist_y / fs_dist_z (they are the solver's work vectors): upload x again before the next resident product. */
 int  fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double lambda, double tol, int *out_iter);
+/* The preconditioned solvers on the sharded matrix.  Their arithmetic is that of fs_gram_diag / fs_pcg / fs_pcgn above, whose text
+ * is the single statement of it; what follows says only what differs.  All three need the transposed side (FS_ERR_NO_TRANSPOSE; it
+ * may come from fs_dist_matrix_build_transpose, _device or fs_dist_matrix_pair), are synchronous like fs_dist_cg, and take their
+ * vectors (x, b, d, prm->diag, the row-major ncol x k panels X, B) in host memory or in HBM of any device, like fs_dist_spmv:
+ * nothing in HBM is staged through the host.  The caller's x / X is written once, at the end of a solve that succeeded.
+ *
+ * fs_dist_gram_diag: d[ncol] = fs_gram_diag of A'.  Rank r runs it over the rows of A' it owns; one whole-shard all-gather gives
+ * every rank the whole d.  A row of A' lives on one rank, so the bits are fs_gram_diag's on the same A', for any number of ranks,
+ * in every mode.  FS_ERR_ARG: a NULL M or d.  FS_ERR_RELEASED: a rank's shard of A' gave its plain CSR back (fs_matrix_release_csr
+ * on a fs_dist_matrix_shard handle) -- raised before anything is written.  CLOBBERS fs_dist_z. */
+int  fs_dist_gram_diag(fs_dist_matrix_t M, double lambda, double *d /* ncol */);
+/* fs_dist_pcg: fs_pcg with fs_pcg_params / fs_pcg_info unchanged (tol, max_iter, precond, warm_start -- x holds x0 --, diag).
+ * Option "dist_cg_scheme" as for fs_dist_cg:
+ *   0  every rank holds whole x, r, p, q, dinv and launches fs_pcg's own kernels on them: identical kernels on identical data, no
+ *      exchange for the sums.  `red` is fs_pcg's: under "strict_order" x, fs_pcg_info and the scalars are fs_pcg's on the same CSRs,
+ *      bit for bit, for any number of ranks.  FS_PRECOND_JACOBI costs the one all-gather of d per solve, a warm start one pair of
+ *      sharded products on x0 in front.
+ *   1  rank r keeps its slice of x, r, p, q, dinv: the rows of A' it owns.  Jacobi's slice of d is the rank's own launch: no
+ *      exchange.  `red` is the slice tree of fs_dist_cg: every rank reduces its slice with fs_cg's two stages, the rank values are
+ *      all-gathered and every rank adds them in rank order with the second stage (an empty slice contributes +0.0).  The sums fs_pcg
+ *      takes in one pass travel in one exchange of two doubles per rank ({bb, rr} at the start; {rr, rzn} with a preconditioner),
+ *      so an iteration has two small exchanges and the all-gather of the new p, like fs_dist_cg.  Every other line is fs_pcg's.
+ * Either way every rank decides convergence for itself and the host compares the flags of all of them one iteration behind, as in
+ * fs_dist_cg: a disagreement is an error return (FS_ERR_HIP).  A solve that is done before its first iteration enqueues no product
+ * for an iteration and leaves x as fs_pcg does (b = 0: x = 0, converged, where fs_dist_cg returns NaN).  Products add in a fixed
+ * order unless option "cg_fixed_order" is 0.  Work vectors stay on the handle between solves.  FS_ERR_ARG: a NULL M, x, b or prm;
+ * precond outside 0..2; FS_PRECOND_DIAG with a NULL diag; tol negative or NaN.  FS_ERR_RELEASED: FS_PRECOND_JACOBI when a rank's
+ * shard of A' gave its plain CSR back (FS_PRECOND_DIAG with a diagonal kept from before still solves).  Every one of them is raised
+ * before anything is written to x.  CLOBBERS fs_dist_x / fs_dist_y / fs_dist_z like fs_dist_cg. */
+int  fs_dist_pcg(fs_dist_matrix_t M, double *x, const double *b, double lambda, const fs_pcg_params *prm, fs_pcg_info *info /* or NULL */);
+/* fs_dist_pcgn: fs_pcgn, k in 1..FS_PCGN_MAX_RHS.  Replicated on every rank WHATEVER "dist_cg_scheme" says (there is no slice-wise
+ * form of the k-column vector kernels): whole ncol x k panels per rank, fs_pcgn's own kernels (option "pcgn_kernel", the live mask,
+ * freezing) on them, T = A P and Q = A' T as the sharded k-column products of fs_dist_spmm (k = 1: fs_dist_spmv's).  Column j is
+ * fs_pcgn's column j and therefore fs_pcg on B[:, j] wherever the sharded k-column product has the single-vector product's bits
+ * ("strict_order"; k = 1 in every mode).  Convergence across the ranks, a solve done before its first iteration, the fixed order of
+ * the products, the work space and the clobbered vectors as for fs_dist_pcg (the k-column vectors of fs_dist_spmm for k > 1).
+ * FS_ERR_ARG: those of fs_dist_pcg (X, B for x, b) and k out of range; FS_ERR_RELEASED as there; raised before anything is written
+ * to X. */
+int  fs_dist_pcgn(fs_dist_matrix_t M, double *X, const double *B, int k, double lambda, const fs_pcg_params *prm,
+                  fs_pcg_info *info /* k entries or NULL */);
 /* k row-major columns across the GPUs (csr_A_mul_Bn csr.h:441, bcsr_A_mul_Bn csr.h:257, bsbm_A_mul_Bn sparse.h:318): every device
  * multiplies its shard with the k-column kernels of fs_spmm (prepared on the first call with a new k: synchronous) and the Y shards
  * are all-gathered -- inside the product, part by part, where the k-column product finishes its rows that way (the one-sweep plan

@@ -34,7 +34,7 @@ DEVICE_API = [
     "fs_dist_matrix_build_transpose", "fs_dist_matrix_has_transpose", "fs_dist_spmv_t", "fs_dist_spmv_t_resident", "fs_dist_swap_xy",
     "fs_dist_z", "fs_dist_cg", "fs_dist_is_conservative", "fs_dist_csr_create_from_shards", "fs_dist_matrix_build_transpose_device",
     "fs_dist_matrix_bounds_t", "fs_dist_matrix_nnz", "fs_dist_matrix_shard", "fs_dist_spmm", "fs_dist_spmm_t", "fs_dist_cg2",
-    "fs_dist_coo_create", "fs_dist_matrix_pair", "fs_dist_ata",
+    "fs_dist_coo_create", "fs_dist_matrix_pair", "fs_dist_ata", "fs_dist_gram_diag", "fs_dist_pcg", "fs_dist_pcgn",
 ]
 REFERENCE_API = [
     # sparse.h
@@ -191,6 +191,9 @@ def lib():
     L.fs_dist_matrix_pair.restype = vp
     L.fs_dist_matrix_pair.argtypes = [vp, vp]
     L.fs_dist_ata.argtypes = [vp, vp, vp, C.c_double]
+    L.fs_dist_gram_diag.argtypes = [vp, C.c_double, vp]
+    L.fs_dist_pcg.argtypes = [vp, vp, vp, C.c_double, C.POINTER(PcgParams), C.POINTER(PcgInfo)]
+    L.fs_dist_pcgn.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.POINTER(PcgParams), C.POINTER(PcgInfo)]
     L.fs_dist_spmm.argtypes = [vp, vp, vp, C.c_int]
     L.fs_dist_spmm_t.argtypes = [vp, vp, vp, C.c_int]
     for f in ("fs_dist_spmv_resident", "fs_dist_spmv_t_resident", "fs_dist_swap_xy"):
@@ -427,6 +430,33 @@ def pcgn(A, At, X, B, lam, tol, max_iter=0, precond=FS_PRECOND_JACOBI, warm_star
     prm = PcgParams(float(tol), int(max_iter), int(precond), int(bool(warm_start)), _ptr(diag))
     infos = (PcgInfo * max(k, 1))()
     check(lib().fs_pcgn(A.h, At.h, X.data_ptr(), B.data_ptr(), k, float(lam), C.byref(prm), infos, stream), "fs_pcgn")
+    return list(infos)[:k]
+
+
+def dist_gram_diag(M, lam, d):
+    """d = the diagonal of A'A + lam I on a row-sharded matrix (fs_dist_gram_diag); M: the fs_dist_matrix_t handle, d: ncol doubles,
+    a numpy array in host memory or a tensor on any device of the context"""
+    check(lib().fs_dist_gram_diag(M, float(lam), _ptr(d)), "fs_dist_gram_diag")
+
+
+def dist_pcg(M, x, b, lam, tol, max_iter=0, precond=FS_PRECOND_JACOBI, warm_start=False, diag=None):
+    """fs_pcg on a row-sharded matrix (fs_dist_pcg); M: the fs_dist_matrix_t handle (transposed side built); x, b (and diag, for
+    FS_PRECOND_DIAG): ncol doubles, numpy arrays in host memory or tensors on any device of the context.  Returns the PcgInfo."""
+    prm = PcgParams(float(tol), int(max_iter), int(precond), int(bool(warm_start)), _ptr(diag))
+    info = PcgInfo()
+    check(lib().fs_dist_pcg(M, _ptr(x), _ptr(b), float(lam), C.byref(prm), C.byref(info)), "fs_dist_pcg")
+    return info
+
+
+def dist_pcgn(M, X, B, lam, tol, max_iter=0, precond=FS_PRECOND_JACOBI, warm_start=False, diag=None):
+    """fs_pcgn on a row-sharded matrix (fs_dist_pcgn); X, B: contiguous (F, k) numpy arrays or tensors of the same shape,
+    k <= FS_PCGN_MAX_RHS (1-d: one column).  Returns the list of the k PcgInfo, one per column."""
+    if len(B.shape) not in (1, 2) or tuple(X.shape) != tuple(B.shape):
+        raise ValueError("dist_pcgn: X and B must be contiguous (F, k) arrays of the same shape")
+    k = 1 if len(B.shape) == 1 else int(B.shape[1])
+    prm = PcgParams(float(tol), int(max_iter), int(precond), int(bool(warm_start)), _ptr(diag))
+    infos = (PcgInfo * max(k, 1))()
+    check(lib().fs_dist_pcgn(M, _ptr(X), _ptr(B), k, float(lam), C.byref(prm), infos), "fs_dist_pcgn")
     return list(infos)[:k]
 
 

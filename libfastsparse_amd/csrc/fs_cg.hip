@@ -619,6 +619,7 @@ enum { kStLiveMask = 12 };                 // bit j: column j is live (32 bits, 
 enum { kPnBb = 0, kPnRr = 1, kPnStop = 2, kPnRz = 3, kPnAlpha = 4, kPnBeta = 5, kPnCount = 6, kPnLive = 7, kPnConverged = 8,
        kPnStride = 16 };
 enum PcgnStep { kPnStepStart, kPnStepRz, kPnStepAlpha, kPnStepBeta };
+static_assert(kPcgnStateDoubles == kPcgnMaxRhs * kPnStride && pcgn_part_doubles(1) == (size_t)kRedBlocks * 2, "fs_common.h sizes the callers' buffers");
 struct Pair { double a, b; };
 
 // two neighbouring columns of a row: one 16-byte access (V: the address is 16-byte aligned, so k is even) or two of 8 bytes
@@ -1231,15 +1232,179 @@ int cg_dev_step_c(int n, double *p, const double *r, const double *st, hipStream
   return FS_OK;
 }
 
-int cg_dev_final(CgStep step, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s)
+// `partials`: count x nv doubles, rank-major as the exchange leaves them -- block_sum<NV>'s own layout, so every one of the nv sums
+// is finish_sum's tree (stage 2) over its count values.  nv = 2 for kStepPcgStart {b.b, r.r} and for kStepPcgBeta with a
+// preconditioner {r.r, r.z}; red_out has room for nv doubles
+int cg_dev_final(CgStep step, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s, int nv)
 {
   const dim3 one(1), blk(kRedThreads);
-  if (step == kStepCgStart)      hipLaunchKernelGGL((final_step_kernel<1, kStepCgStart>), one, blk, 0, s, partials, count, red_out, st, arg);
-  else if (step == kStepCgAlpha) hipLaunchKernelGGL((final_step_kernel<1, kStepCgAlpha>), one, blk, 0, s, partials, count, red_out, st, arg);
-  else if (step == kStepCgBeta)  hipLaunchKernelGGL((final_step_kernel<1, kStepCgBeta>), one, blk, 0, s, partials, count, red_out, st, arg);
-  else { set_error("cg_dev_final: not a step of fs_cg"); return FS_ERR_ARG; }
+  const bool pcg2 = (step == kStepPcgStart) || (step == kStepPcgBeta && nv == 2);
+  if (nv != (pcg2 ? 2 : 1)) { set_error("cg_dev_final: the step does not take this many sums"); return FS_ERR_ARG; }
+  if (step == kStepCgStart)       hipLaunchKernelGGL((final_step_kernel<1, kStepCgStart>), one, blk, 0, s, partials, count, red_out, st, arg);
+  else if (step == kStepCgAlpha)  hipLaunchKernelGGL((final_step_kernel<1, kStepCgAlpha>), one, blk, 0, s, partials, count, red_out, st, arg);
+  else if (step == kStepCgBeta)   hipLaunchKernelGGL((final_step_kernel<1, kStepCgBeta>), one, blk, 0, s, partials, count, red_out, st, arg);
+  else if (step == kStepPcgStart) hipLaunchKernelGGL((final_step_kernel<2, kStepPcgStart>), one, blk, 0, s, partials, count, red_out, st, arg);
+  else if (step == kStepPcgRz)    hipLaunchKernelGGL((final_step_kernel<1, kStepPcgRz>), one, blk, 0, s, partials, count, red_out, st, arg);
+  else if (step == kStepPcgBeta && nv == 2) hipLaunchKernelGGL((final_step_kernel<2, kStepPcgBeta>), one, blk, 0, s, partials, count, red_out, st, arg);
+  else if (step == kStepPcgBeta)  hipLaunchKernelGGL((final_step_kernel<1, kStepPcgBeta>), one, blk, 0, s, partials, count, red_out, st, arg);
+  else { set_error("cg_dev_final: not a step of fs_cg or fs_pcg"); return FS_ERR_ARG; }
   FS_HIP(hipGetLastError());
   return FS_OK;
+}
+
+// ---- fs_pcg's steps as launchers: fs_pcg calls them on whole vectors, fs_dist_pcg on every rank (scheme "replicate": whole
+// vectors; scheme "gather": the *_partial / step_b / step_c forms on the rank's slice, the sums finished by cg_dev_final).
+// dinv = 1 / d, 1 where d is 0; in place or not
+int pcg_dev_dinv(int n, const double *d, double *dinv, hipStream_t s)
+{
+  hipLaunchKernelGGL(pcg_dinv_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, d, dinv);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+static void pcg_launch_init(int n, bool warm, double lambda, const double *b, double *x, double *r, double *q, double *part, hipStream_t s)
+{
+  if (warm) hipLaunchKernelGGL(pcg_init_kernel<true>, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, lambda, b, x, r, q, part);
+  else      hipLaunchKernelGGL(pcg_init_kernel<false>, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, lambda, b, x, r, q, part);
+}
+
+static void pcg_launch_start(int n, const double *r, const double *dinv, double *p, double *part, const double *st, hipStream_t s)
+{
+  if (dinv) hipLaunchKernelGGL(pcg_start_kernel<true>, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, r, dinv, p, part, st);
+  else      hipLaunchKernelGGL(pcg_start_kernel<false>, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, r, dinv, p, part, st);
+}
+
+// cold: x = 0, r = b; warm (q = A'(A x) on entry): q += lambda x, r = b - q; then b.b, r.r, stop, done?
+int pcg_dev_init(int n, bool warm, double lambda, const double *b, double *x, double *r, double *q, double *part, double *red, double *st,
+                 double tol, hipStream_t s)
+{
+  pcg_launch_init(n, warm, lambda, b, x, r, q, part, s);
+  hipLaunchKernelGGL((final_step_kernel<2, kStepPcgStart>), dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red, st, tol);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// p = z = r dinv (dinv NULL: r), r.z
+int pcg_dev_start(int n, const double *r, const double *dinv, double *p, double *part, double *red, double *st, hipStream_t s)
+{
+  pcg_launch_start(n, r, dinv, p, part, st, s);
+  hipLaunchKernelGGL((final_step_kernel<1, kStepPcgRz>), dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red, st, 0.0);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// everything of an iteration behind q = A'(A p).  dinv NULL: fs_cg's launches with fs_pcg's convergence step
+int pcg_dev_steps(int n, double lambda, double *x, double *r, double *p, double *q, const double *dinv, double *part, double *red,
+                  double *st, hipStream_t s)
+{
+  if (!dinv) return cg_dev_steps(n, lambda, x, r, p, q, part, red, st, s, kStepPcgBeta);
+  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
+  hipLaunchKernelGGL(cg_shift_dot_dev_kernel, g, blk, 0, s, n, lambda, q, p, part, st);
+  hipLaunchKernelGGL((final_step_kernel<1, kStepCgAlpha>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);       // alpha = r.z / p.q
+  hipLaunchKernelGGL(pcg_update_kernel, g, blk, 0, s, n, x, r, p, q, dinv, part, st);
+  hipLaunchKernelGGL((final_step_kernel<2, kStepPcgBeta>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);       // converged? beta
+  hipLaunchKernelGGL(pcg_direction_kernel, g, blk, 0, s, n, p, r, dinv, st);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// the slice forms: red_out[0..2) = {b.b, r.r} of the slice
+int pcg_dev_init_partial(int n, bool warm, double lambda, const double *b, double *x, double *r, double *q, double *part, double *red_out,
+                         hipStream_t s)
+{
+  pcg_launch_init(n, warm, lambda, b, x, r, q, part, s);
+  hipLaunchKernelGGL(final_sum_kernel<2>, dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red_out);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// red_out[0] = r.z of the slice
+int pcg_dev_start_partial(int n, const double *r, const double *dinv, double *p, double *part, double *red_out, const double *st,
+                          hipStream_t s)
+{
+  pcg_launch_start(n, r, dinv, p, part, st, s);
+  hipLaunchKernelGGL(final_sum_kernel<1>, dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red_out);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// red_out[0..2) = {r.r, r.z} of the slice (without a preconditioner: cg_dev_step_b)
+int pcg_dev_step_b(int n, double *x, double *r, const double *p, const double *q, const double *dinv, double *part, double *red_out,
+                   const double *st, hipStream_t s)
+{
+  hipLaunchKernelGGL(pcg_update_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, x, r, p, q, dinv, part, st);
+  hipLaunchKernelGGL(final_sum_kernel<2>, dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red_out);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// (without a preconditioner: cg_dev_step_c)
+int pcg_dev_step_c(int n, double *p, const double *r, const double *dinv, const double *st, hipStream_t s)
+{
+  hipLaunchKernelGGL(pcg_direction_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, p, r, dinv, st);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// fs_pcg_info from the final st[] of a solve
+void pcg_info_of(const double *fin, fs_pcg_info *info)
+{
+  if (!info) return;
+  info->iterations = (int)fin[kStIter];
+  info->converged = fin[kStDone] != 0.0;
+  info->rnorm = sqrt(fin[kStRr]);
+  info->bnorm = sqrt(fin[kStBb]);
+}
+
+// ---- fs_pcgn's steps as launchers (fs_pcgn; fs_dist_pcgn on every rank).  part: pcgn_part_doubles(k), cs: kPcgnStateDoubles.
+// 16-byte accesses: R, P, Q are the solve's own (rows of an even k stay aligned), X and B may be the caller's
+static int pcgn_vec(int k, const double *X, const double *B)
+{
+  return (k & 1) ? 0 : ((((uintptr_t)X | (uintptr_t)B) & 15) == 0 ? 2 : 1);
+}
+
+int pcgn_dev_clear(double *cs, hipStream_t s)     // slots a column never writes read as 0 in the debug getter
+{
+  FS_HIP(hipMemsetAsync(cs, 0, sizeof(double) * kPcgnMaxRhs * kPnStride, s));
+  return FS_OK;
+}
+
+// cold: X = 0, R = B; warm (Q = A'(A X) on entry): Q += lambda X, R = B - Q; b.b, r.r, stop, live? per column; P = Z = R dinv, r.z
+int pcgn_dev_init(int n, int k, bool warm, double lambda, const double *B, double *X, double *R, double *P, double *Q, const double *dinv,
+                  double *part, double *st, double *cs, double tol, hipStream_t s)
+{
+  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
+  return pcgn_dispatch(k, pcgn_vec(k, X, B), [&](auto sh) -> int {
+    using S = decltype(sh);
+    hipLaunchKernelGGL((pcgn_init_kernel<S::kmax, S::vec>), g, blk, 0, s, n, k, (int)warm, lambda, B, X, R, Q, part);
+    hipLaunchKernelGGL(pcgn_step_kernel<kPnStepStart>, one, blk, 0, s, part, st, cs, k, 2, tol);           // b.b, r.r, stop, live?
+    hipLaunchKernelGGL((pcgn_start_kernel<S::kmax, S::vec>), g, blk, 0, s, n, k, R, dinv, P, part, st);
+    hipLaunchKernelGGL(pcgn_step_kernel<kPnStepRz>, one, blk, 0, s, part, st, cs, k, 1, 0.0);              // r.z
+    FS_HIP(hipGetLastError());
+    return FS_OK;
+  });
+}
+
+// everything of an iteration behind Q = A'(A P); option "pcgn_kernel" picks the form of the vector kernels
+int pcgn_dev_steps(int n, int k, double lambda, double *X, const double *B, double *R, double *P, double *Q, const double *dinv,
+                   double *part, double *st, double *cs, hipStream_t s)
+{
+  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
+  const int which = options().pcgn_kernel;
+  const bool staged = which == 2 || (which == 0 && k > kPcgnRowsMaxK);
+  return pcgn_dispatch(k, pcgn_vec(k, X, B), [&](auto sh) -> int {
+    using S = decltype(sh);
+    if (staged) hipLaunchKernelGGL(pcgn_shift_dot_lds_kernel<S::kmax>, g, blk, 0, s, n, k, lambda, Q, P, part, st);
+    else        hipLaunchKernelGGL((pcgn_shift_dot_kernel<S::kmax, S::vec>), g, blk, 0, s, n, k, lambda, Q, P, part, st);
+    hipLaunchKernelGGL(pcgn_step_kernel<kPnStepAlpha>, one, blk, 0, s, part, st, cs, k, 1, 0.0);          // alpha = r.z / p.q
+    if (staged) hipLaunchKernelGGL(pcgn_update_lds_kernel<S::kmax>, g, blk, 0, s, n, k, X, R, P, Q, dinv, part, st, cs);
+    else        hipLaunchKernelGGL((pcgn_update_kernel<S::kmax, S::vec>), g, blk, 0, s, n, k, X, R, P, Q, dinv, part, st, cs);
+    hipLaunchKernelGGL(pcgn_step_kernel<kPnStepBeta>, one, blk, 0, s, part, st, cs, k, dinv ? 2 : 1, 0.0); // converged? beta
+    if (staged) hipLaunchKernelGGL(pcgn_direction_lds_kernel<S::kmax>, g, blk, 0, s, n, k, P, R, dinv, st, cs);
+    else        hipLaunchKernelGGL((pcgn_direction_kernel<S::kmax, S::vec>), g, blk, 0, s, n, k, P, R, dinv, st, cs);
+    FS_HIP(hipGetLastError());
+    return FS_OK;
+  });
 }
 
 // ---- the same for two right-hand sides (fs_cg2, fs_dist_cg2).  cg2_dev_init is synchronous (two reductions go to the host: the
@@ -1300,6 +1465,27 @@ void note_cg_state(const double *st_host)
 {
   for (int i = 0; i < kStDoubles; ++i) g_last_cg_state[i] = st_host[i];
   g_last_cg_state_set = true;
+}
+
+// the end of an fs_pcgn solve on the host: fin = the final st[], fcs = the final cs[] of the k columns.  fs_pcg's slots of the st[]
+// kept for fs_debug_last_cg_state carry column 0's scalars (with k = 1 it is fs_pcg's st[]); cs[] is kept for
+// fs_debug_last_pcgn_state; info: k entries or NULL
+void pcgn_note_state(const double *fin_in, const double *fcs, int k, fs_pcg_info *info)
+{
+  double fin[kStDoubles];
+  for (int i = 0; i < kStDoubles; ++i) fin[i] = fin_in[i];
+  fin[kStRsq] = fcs[kPnRz]; fin[kStAlpha] = fcs[kPnAlpha]; fin[kStBeta] = fcs[kPnBeta]; fin[kStStop] = fcs[kPnStop];
+  fin[kStRr] = fcs[kPnRr]; fin[kStBb] = fcs[kPnBb];
+  note_cg_state(fin);
+  for (int i = 0; i < k * kPnStride; ++i) g_last_pcgn_state[i] = fcs[i];
+  g_last_pcgn_doubles = k * kPnStride;
+  for (int j = 0; info && j < k; ++j) {
+    const double *e = fcs + j * kPnStride;
+    info[j].iterations = (int)e[kPnCount];                   // a column still live at the cap: count = cap, converged 0
+    info[j].converged = e[kPnConverged] != 0.0;
+    info[j].rnorm = sqrt(e[kPnRr]);
+    info[j].bnorm = sqrt(e[kPnBb]);
+  }
 }
 
 int CgFlags::init()
@@ -1489,41 +1675,19 @@ int fs_pcg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lam
   double *dinv = nullptr;
   if (int rc = f.alloc(pre ? &dinv : nullptr, F)) return rc;
   double *r = f.r, *p = f.p, *q = f.q, *part = f.part, *red = f.red, *st = f.st;
-  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
   if (prm->precond == FS_PRECOND_JACOBI)
     if (int rc = fs_gram_diag(At, lambda, dinv, stream)) return rc;
-  if (pre) hipLaunchKernelGGL(pcg_dinv_kernel, g, blk, 0, s, F, prm->precond == FS_PRECOND_DIAG ? prm->diag : dinv, dinv);
+  if (pre)
+    if (int rc = pcg_dev_dinv(F, prm->precond == FS_PRECOND_DIAG ? prm->diag : dinv, dinv, s)) return rc;
   if (warm) {                                                // r = b - (A'(A x) + lambda x)
     if (int rc = fs_spmv(A, f.tmp, x, stream)) return rc;
     if (int rc = fs_spmv(At, q, f.tmp, stream)) return rc;
-    hipLaunchKernelGGL(pcg_init_kernel<true>, g, blk, 0, s, F, lambda, b, x, r, q, part);
-  } else {
-    hipLaunchKernelGGL(pcg_init_kernel<false>, g, blk, 0, s, F, lambda, b, x, r, q, part);
   }
-  hipLaunchKernelGGL((final_step_kernel<2, kStepPcgStart>), one, blk, 0, s, part, kRedBlocks, red, st, prm->tol);   // b.b, r.r, stop, done?
-  if (pre) hipLaunchKernelGGL(pcg_start_kernel<true>, g, blk, 0, s, F, r, dinv, p, part, st);
-  else     hipLaunchKernelGGL(pcg_start_kernel<false>, g, blk, 0, s, F, r, dinv, p, part, st);
-  hipLaunchKernelGGL((final_step_kernel<1, kStepPcgRz>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);           // r.z
-  FS_HIP(hipGetLastError());
-  auto steps = [&]() -> int {
-    if (!pre) return cg_dev_steps(F, lambda, x, r, p, q, part, red, st, s, kStepPcgBeta);   // fs_cg's launches
-    hipLaunchKernelGGL(cg_shift_dot_dev_kernel, g, blk, 0, s, F, lambda, q, p, part, st);
-    hipLaunchKernelGGL((final_step_kernel<1, kStepCgAlpha>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);       // alpha = r.z / p.q
-    hipLaunchKernelGGL(pcg_update_kernel, g, blk, 0, s, F, x, r, p, q, dinv, part, st);
-    hipLaunchKernelGGL((final_step_kernel<2, kStepPcgBeta>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);       // converged? beta
-    hipLaunchKernelGGL(pcg_direction_kernel, g, blk, 0, s, F, p, r, dinv, st);
-    FS_HIP(hipGetLastError());
-    return FS_OK;
-  };
-  if (int rc = f.iterate(cap, true, steps)) return rc;
+  if (int rc = pcg_dev_init(F, warm, lambda, b, x, r, q, part, red, st, prm->tol, s)) return rc;   // b.b, r.r, stop, done?
+  if (int rc = pcg_dev_start(F, r, dinv, p, part, red, st, s)) return rc;                          // p = z, r.z
+  if (int rc = f.iterate(cap, true, [&] { return pcg_dev_steps(F, lambda, x, r, p, q, dinv, part, red, st, s); })) return rc;
   if (int rc = f.finish()) return rc;
-  const double *fin = f.fin;
-  if (info) {
-    info->iterations = (int)fin[kStIter];
-    info->converged = fin[kStDone] != 0.0;
-    info->rnorm = sqrt(fin[kStRr]);
-    info->bnorm = sqrt(fin[kStBb]);
-  }
+  pcg_info_of(f.fin, info);
   return FS_OK;
 }
 
@@ -1619,60 +1783,21 @@ int fs_pcgn(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k, do
   const size_t npart = (size_t)kRedBlocks * 2 * k;
   if (int rc = f.alloc(pre ? &dinv : nullptr, F, &own, npart + kPcgnMaxRhs * kPnStride)) return rc;
   double *r = f.r, *p = f.p, *q = f.q, *st = f.st, *part = own, *cs = own + npart;
-  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
-  FS_HIP(hipMemsetAsync(cs, 0, sizeof(double) * kPcgnMaxRhs * kPnStride, s));   // slots a column never writes read as 0 in the debug getter
-  // 16-byte accesses: r, p, q are the solve's own (rows of an even k stay aligned), X and B are the caller's
-  const int vec = (k & 1) ? 0 : ((((uintptr_t)X | (uintptr_t)B) & 15) == 0 ? 2 : 1);
+  if (int rc = pcgn_dev_clear(cs, s)) return rc;
   if (prm->precond == FS_PRECOND_JACOBI)
     if (int rc = fs_gram_diag(At, lambda, dinv, stream)) return rc;
-  if (pre) hipLaunchKernelGGL(pcg_dinv_kernel, g, blk, 0, s, F, prm->precond == FS_PRECOND_DIAG ? prm->diag : dinv, dinv);
+  if (pre)
+    if (int rc = pcg_dev_dinv(F, prm->precond == FS_PRECOND_DIAG ? prm->diag : dinv, dinv, s)) return rc;
   if (warm) {                                                // R = B - (A'(A X) + lambda X): one pair of k-column products
     if (int rc = k == 1 ? fs_spmv(A, f.tmp, X, stream) : fs_spmm(A, f.tmp, X, k, stream)) return rc;
     if (int rc = k == 1 ? fs_spmv(At, q, f.tmp, stream) : fs_spmm(At, q, f.tmp, k, stream)) return rc;
   }
-  if (int rc = pcgn_dispatch(k, vec, [&](auto sh) -> int {
-        using S = decltype(sh);
-        hipLaunchKernelGGL((pcgn_init_kernel<S::kmax, S::vec>), g, blk, 0, s, F, k, (int)warm, lambda, B, X, r, q, part);
-        hipLaunchKernelGGL(pcgn_step_kernel<kPnStepStart>, one, blk, 0, s, part, st, cs, k, 2, prm->tol);   // b.b, r.r, stop, live?
-        hipLaunchKernelGGL((pcgn_start_kernel<S::kmax, S::vec>), g, blk, 0, s, F, k, r, dinv, p, part, st);
-        hipLaunchKernelGGL(pcgn_step_kernel<kPnStepRz>, one, blk, 0, s, part, st, cs, k, 1, 0.0);           // r.z
-        FS_HIP(hipGetLastError());
-        return FS_OK;
-      })) return rc;
-  const int which = options().pcgn_kernel;
-  const bool staged = which == 2 || (which == 0 && k > kPcgnRowsMaxK);
-  auto steps = [&]() -> int {
-    return pcgn_dispatch(k, vec, [&](auto sh) -> int {
-      using S = decltype(sh);
-      if (staged) hipLaunchKernelGGL(pcgn_shift_dot_lds_kernel<S::kmax>, g, blk, 0, s, F, k, lambda, q, p, part, st);
-      else        hipLaunchKernelGGL((pcgn_shift_dot_kernel<S::kmax, S::vec>), g, blk, 0, s, F, k, lambda, q, p, part, st);
-      hipLaunchKernelGGL(pcgn_step_kernel<kPnStepAlpha>, one, blk, 0, s, part, st, cs, k, 1, 0.0);          // alpha = r.z / p.q
-      if (staged) hipLaunchKernelGGL(pcgn_update_lds_kernel<S::kmax>, g, blk, 0, s, F, k, X, r, p, q, dinv, part, st, cs);
-      else        hipLaunchKernelGGL((pcgn_update_kernel<S::kmax, S::vec>), g, blk, 0, s, F, k, X, r, p, q, dinv, part, st, cs);
-      hipLaunchKernelGGL(pcgn_step_kernel<kPnStepBeta>, one, blk, 0, s, part, st, cs, k, pre ? 2 : 1, 0.0); // converged? beta
-      if (staged) hipLaunchKernelGGL(pcgn_direction_lds_kernel<S::kmax>, g, blk, 0, s, F, k, p, r, dinv, st, cs);
-      else        hipLaunchKernelGGL((pcgn_direction_kernel<S::kmax, S::vec>), g, blk, 0, s, F, k, p, r, dinv, st, cs);
-      FS_HIP(hipGetLastError());
-      return FS_OK;
-    });
-  };
-  if (int rc = f.iterate(cap, true, steps)) return rc;
+  if (int rc = pcgn_dev_init(F, k, warm, lambda, B, X, r, p, q, dinv, part, st, cs, prm->tol, s)) return rc;
+  if (int rc = f.iterate(cap, true, [&] { return pcgn_dev_steps(F, k, lambda, X, B, r, p, q, dinv, part, st, cs, s); })) return rc;
   double fcs[kPcgnMaxRhs * kPnStride] = {0.0};
   FS_HIP(hipMemcpyAsync(fcs, cs, sizeof(double) * k * kPnStride, hipMemcpyDeviceToHost, s));
   if (int rc = f.finish()) return rc;
-  // fs_pcg's slots of the st[] kept for fs_debug_last_cg_state carry column 0's scalars: with k = 1 it is fs_pcg's st[]
-  f.fin[kStRsq] = fcs[kPnRz]; f.fin[kStAlpha] = fcs[kPnAlpha]; f.fin[kStBeta] = fcs[kPnBeta]; f.fin[kStStop] = fcs[kPnStop];
-  f.fin[kStRr] = fcs[kPnRr]; f.fin[kStBb] = fcs[kPnBb];
-  note_cg_state(f.fin);
-  for (int i = 0; i < k * kPnStride; ++i) g_last_pcgn_state[i] = fcs[i];
-  g_last_pcgn_doubles = k * kPnStride;
-  for (int j = 0; info && j < k; ++j) {
-    const double *e = fcs + j * kPnStride;
-    info[j].iterations = (int)e[kPnCount];                   // a column still live at the cap: count = cap, converged 0
-    info[j].converged = e[kPnConverged] != 0.0;
-    info[j].rnorm = sqrt(e[kPnRr]);
-    info[j].bnorm = sqrt(e[kPnBb]);
-  }
+  pcgn_note_state(f.fin, fcs, k, info);
   return FS_OK;
 }
 

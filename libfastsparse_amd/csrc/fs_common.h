@@ -284,7 +284,7 @@ struct Options {
                            // that a solve is bit-identical from run to run like the reference's (cg.h:25-187); 0: the default kernels
   int release_csr = 0;     // 1: fs_csr_create / fs_coo_create / fs_matrix_build_transpose give the plain CSR arrays back once a re-ordered
                            // copy was kept (fs_matrix_release_csr); FS_RELEASE_CSR presets it; the drop-in layer never releases
-  int dist_cg_scheme = 0;  // fs_dist_cg: 0 every device keeps whole vectors (no exchange for the dots), 1 every device keeps its
+  int dist_cg_scheme = 0;  // fs_dist_cg, fs_dist_pcg: 0 every device keeps whole vectors (no exchange for the dots), 1 every device keeps its
                            // slice of the unknowns (vector work divided by the devices; see fs_dist.hip)
 };
 Options &options();
@@ -368,7 +368,33 @@ int cg_dev_step_a(int n, double lambda, const double *p, double *q, double *part
 int cg_dev_step_b(int n, double *x, double *r, const double *p, const double *q, double *part, double *red_out, const double *st,
                   hipStream_t s);
 int cg_dev_step_c(int n, double *p, const double *r, const double *st, hipStream_t s);
-int cg_dev_final(CgStep step, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s);
+// nv sums per rank, rank-major: 2 for kStepPcgStart {b.b, r.r} and for kStepPcgBeta behind pcg_dev_step_b {r.r, r.z}, else 1
+int cg_dev_final(CgStep step, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s, int nv = 1);
+// ---- fs_pcg's steps (dinv NULL: no preconditioner, z is r) on whole vectors, and on a slice like the cg_dev_* forms above
+int pcg_dev_dinv(int n, const double *d, double *dinv, hipStream_t s);           // dinv = 1 / d, 1 where d is 0; in place or not
+int pcg_dev_init(int n, bool warm, double lambda, const double *b, double *x, double *r, double *q, double *part, double *red, double *st,
+                 double tol, hipStream_t s);                                     // x, r; b.b, r.r, stop, done?
+int pcg_dev_start(int n, const double *r, const double *dinv, double *p, double *part, double *red, double *st, hipStream_t s);
+int pcg_dev_steps(int n, double lambda, double *x, double *r, double *p, double *q, const double *dinv, double *part, double *red,
+                  double *st, hipStream_t s);
+int pcg_dev_init_partial(int n, bool warm, double lambda, const double *b, double *x, double *r, double *q, double *part, double *red_out,
+                         hipStream_t s);                                         // red_out[0..2) = {b.b, r.r} of the slice
+int pcg_dev_start_partial(int n, const double *r, const double *dinv, double *p, double *part, double *red_out, const double *st,
+                          hipStream_t s);                                        // red_out[0] = r.z
+int pcg_dev_step_b(int n, double *x, double *r, const double *p, const double *q, const double *dinv, double *part, double *red_out,
+                   const double *st, hipStream_t s);                             // red_out[0..2) = {r.r, r.z}
+int pcg_dev_step_c(int n, double *p, const double *r, const double *dinv, const double *st, hipStream_t s);
+void pcg_info_of(const double *st_host, fs_pcg_info *info);                      // info may be NULL
+// ---- fs_pcgn's steps on row-major n x k panels; part: pcgn_part_doubles(k) doubles, cs: kPcgnStateDoubles, st as above
+constexpr int kPcgnStateDoubles = FS_PCGN_MAX_RHS * 16;
+constexpr size_t pcgn_part_doubles(int k) { return (size_t)1024 * 2 * (size_t)k; }
+int pcgn_dev_clear(double *cs, hipStream_t s);
+int pcgn_dev_init(int n, int k, bool warm, double lambda, const double *B, double *X, double *R, double *P, double *Q, const double *dinv,
+                  double *part, double *st, double *cs, double tol, hipStream_t s);
+int pcgn_dev_steps(int n, int k, double lambda, double *X, const double *B, double *R, double *P, double *Q, const double *dinv,
+                   double *part, double *st, double *cs, hipStream_t s);
+// the final st[] and cs[] (k columns) on the host: kept for the debug getters, info (k entries or NULL) filled
+void pcgn_note_state(const double *st_host, const double *cs_host, int k, fs_pcg_info *info);
 // the final st[] of a solve, kCgStateDoubles doubles copied back to the host: kept for the calling thread (fs_debug_last_cg_state)
 void note_cg_state(const double *st_host);
 // the host's view of a running solve: {done, iterations} of the two most recent iterations, in pinned memory

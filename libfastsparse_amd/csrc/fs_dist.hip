@@ -284,10 +284,20 @@ struct RankBuffers {
   }
 };
 
-struct CgWork {                       // vectors of fs_dist_cg, kept on the handle between solves
+struct CgWork {                       // vectors of fs_dist_cg / fs_dist_pcg, kept on the handle between solves
   int F = 0;
   RankBuffers mem;
-  std::vector<double *> sol, r, b, p, q, part, red, redall, st;
+  // red: two send slots of kCgSendDoubles and the finished sums behind them; redall: every rank's slot, gathered
+  std::vector<double *> sol, r, b, p, q, dinv, part, red, redall, st;
+};
+constexpr int kCgSendDoubles = 2;     // sums one exchange carries per rank: {b.b, r.r} and {r.r, r.z} of fs_dist_pcg
+
+// fs_dist_pcgn's own vectors for k columns (whole panels on every rank), kept like CgWork; P, T, Q are the product vectors of the
+// handle (x / y / z, or KWork's for k > 1)
+struct PnWork {
+  int F = 0, k = 0;
+  RankBuffers mem;
+  std::vector<double *> sol, r, b, dinv, part, cs, st;
 };
 
 // k row-major columns on the sharded matrix (fs_dist_spmm, fs_dist_cg2): the replicated X / Y / Z, the shards' local outputs, the
@@ -319,6 +329,7 @@ struct fs_dist_matrix_s {
   double *pin = nullptr;              // pinned staging of host vectors
   size_t pin_doubles = 0;
   CgWork cg;
+  PnWork pn;
   KWork kw;
   std::mutex lock;                    // products on one matrix are serialised (x, y, z and the part buffers are per matrix)
 };
@@ -339,6 +350,7 @@ void free_side(fs_dist_t D, DistSide &S)
 
 void free_cg(fs_dist_t D, CgWork &W) { W.mem.release(D); W = CgWork(); }
 void free_k(fs_dist_t D, KWork &W) { W.mem.release(D); W = KWork(); }
+void free_pn(fs_dist_t D, PnWork &W) { W.mem.release(D); W = PnWork(); }
 
 // row cuts with (almost) equal numbers of non-zeros: bounds[r] = first row whose row_ptr is >= r/n of nnz -- the cut
 // libfastsparse_amd/dist.py nnz_balanced_partition makes, essential for power-law matrices (BASELINE config 5)
@@ -996,6 +1008,7 @@ void fs_dist_matrix_destroy(fs_dist_matrix_t M)
   DeviceGuard guard;
   (void)dist_sync(M->D);
   free_cg(M->D, M->cg);
+  free_pn(M->D, M->pn);
   free_k(M->D, M->kw);
   for (size_t r = 0; r < (size_t)M->D->n; ++r) {
     (void)hipSetDevice(M->D->dev[r]);
@@ -1454,7 +1467,7 @@ static int ranks_after_iteration(fs_dist_t D, std::vector<fs::CgFlags> &fl, cons
 }
 
 // every rank's final {done, iterations} must agree as well; then the final st[] of rank 0 for fs_debug_last_cg_state
-static int ranks_final_state(fs_dist_t D, const std::vector<double *> &st, const char *who, int *iterations)
+static int ranks_final_state(fs_dist_t D, const std::vector<double *> &st, const char *who, int *iterations, double *st0 = nullptr)
 {
   double h[fs::kCgStateDoubles];
   std::vector<double> fin(2 * (size_t)D->n, 0.0);
@@ -1469,9 +1482,80 @@ static int ranks_final_state(fs_dist_t D, const std::vector<double *> &st, const
   FS_HIP(hipSetDevice(D->dev[0]));
   FS_HIP(hipMemcpy(h, st[0], sizeof(h), hipMemcpyDeviceToHost));
   fs::note_cg_state(h);
+  for (int i = 0; st0 && i < fs::kCgStateDoubles; ++i) st0[i] = h[i];
   *iterations = (int)fin[1];
   return FS_OK;
 }
+
+// a solve that may be done before its first iteration (fs_dist_pcg / fs_dist_pcgn: b = 0, a warm start from a converged x): one
+// synchronous look at every rank's flag.  kRanksStopped, kRanksGoOn, kRanksDisagree, or < 0
+static int ranks_done_at_start(fs_dist_t D, const std::vector<double *> &st, const char *who)
+{
+  if (int rc = dist_sync(D)) return rc;
+  int stops = 0;
+  for (int d = 0; d < D->n; ++d) {
+    double done = 0.0;
+    FS_HIP(hipSetDevice(D->dev[d]));
+    FS_HIP(hipMemcpy(&done, st[(size_t)d] + fs::kCgStateDone, sizeof(double), hipMemcpyDeviceToHost));
+    stops += done != 0.0 ? 1 : 0;
+  }
+  if (stops == 0 || stops == D->n) return stops ? kRanksStopped : kRanksGoOn;
+  fs::set_error(std::string(who) + ": the devices disagree about convergence at the start");
+  return kRanksDisagree;
+}
+
+// fs_dist_cg's and fs_dist_pcg's vectors on the handle: whole vectors (scheme "replicate") or slices (scheme "gather") of F doubles
+// with room for a slice to be sent as a window of max_rows doubles
+static int ensure_cg_work(fs_dist_matrix_t M)
+{
+  fs_dist_t D = M->D;
+  const int n = D->n, F = M->ncol;
+  CgWork &W = M->cg;
+  if (W.mem.ready && W.F == F) return FS_OK;
+  free_cg(D, W);
+  W.F = F;
+  const size_t fl = (size_t)(F ? F : 1) + (size_t)M->t.plan.max_rows + 1;
+  return W.mem.fill(D, [&](int d) -> int {
+    for (std::vector<double *> *v : {&W.sol, &W.r, &W.b, &W.p, &W.q, &W.dinv})
+      if (int rc2 = W.mem.get(d, *v, fl)) return rc2;
+    if (int rc2 = W.mem.get(d, W.part, (size_t)fs::kCgPartDoubles)) return rc2;
+    if (int rc2 = W.mem.get(d, W.red, (size_t)(3 * kCgSendDoubles))) return rc2;
+    if (int rc2 = W.mem.get(d, W.redall, (size_t)(kCgSendDoubles * n + 1))) return rc2;
+    return W.mem.get(d, W.st, (size_t)fs::kCgStateDoubles);
+  });
+}
+
+// Scheme "gather": the sums over the ranks.  A partial reduction leaves a rank's nv sums (1, or 2 that fs_pcg takes in one pass)
+// in send(d); combine() all-gathers them, nv doubles per rank, every rank adds each sum over the ranks in rank order (stage 2's
+// tree) and does the scalar step `step`.  The two send slots alternate: a rank may be one exchange ahead of another that still
+// reads its previous partial; the scalar step leaves its sums behind the slots.
+struct SliceSums {
+  fs_dist_matrix_t M;
+  int slot = 0;
+  double *send(int d) const { return M->cg.red[(size_t)d] + kCgSendDoubles * slot; }
+  int combine(fs::CgStep step, double arg, int nv)
+  {
+    fs_dist_t D = M->D;
+    const int n = D->n;
+    CgWork &W = M->cg;
+    DistSide &T = M->t;
+    std::vector<const double *> from((size_t)n);
+    std::vector<hipEvent_t> ready((size_t)n);
+    for (int d = 0; d < n; ++d) {
+      FS_HIP(hipSetDevice(D->dev[d]));
+      from[(size_t)d] = send(d);
+      FS_HIP(hipEventRecord(T.ev[(size_t)d][0], D->stream[d]));
+      ready[(size_t)d] = T.ev[(size_t)d][0];
+    }
+    if (int rc = exchange_equal(D, from, W.redall, (size_t)nv, D->stream, ready)) return rc;
+    for (int d = 0; d < n; ++d) {
+      FS_HIP(hipSetDevice(D->dev[d]));
+      if (int rc = fs::cg_dev_final(step, W.redall[(size_t)d], n, W.red[(size_t)d] + 2 * kCgSendDoubles, W.st[(size_t)d], arg, D->stream[d], nv)) return rc;
+    }
+    slot ^= 1;
+    return FS_OK;
+  }
+};
 
 // (A'A + lambda I) x = b on the row-sharded matrix: bsbm_cg (cg.h:25-82) across the GPUs, everything resident, the scalars of
 // the iteration on the devices (fs_cg.hip).  Per iteration y = A p and q = A' y; two schemes for everything else (option
@@ -1501,19 +1585,7 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
   const bool gather = fs::options().dist_cg_scheme == 1 && n > 1;
   DistSide &T = M->t;
   CgWork &W = M->cg;
-  if (!W.mem.ready || W.F != F) {
-    free_cg(D, W);
-    W.F = F;
-    const size_t fl = (size_t)(F ? F : 1) + (size_t)T.plan.max_rows + 1;       // (a slice is sent as a window of max_rows doubles)
-    if (int rc = W.mem.fill(D, [&](int d) -> int {
-          for (std::vector<double *> *v : {&W.sol, &W.r, &W.b, &W.p, &W.q})
-            if (int rc2 = W.mem.get(d, *v, fl)) return rc2;
-          if (int rc2 = W.mem.get(d, W.part, (size_t)fs::kCgPartDoubles)) return rc2;
-          if (int rc2 = W.mem.get(d, W.red, 4)) return rc2;
-          if (int rc2 = W.mem.get(d, W.redall, (size_t)(n + 1))) return rc2;
-          return W.mem.get(d, W.st, (size_t)fs::kCgStateDoubles);
-        })) return rc;
-  }
+  if (int rc = ensure_cg_work(M)) return rc;
   {
     std::vector<double *> unused;
     if (int rc = vec_in(M, W.b, b_host, (size_t)F, unused, false)) return rc;    // (host memory or HBM; always a copy: b is read all solve long)
@@ -1524,27 +1596,8 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
     FS_HIP(hipSetDevice(D->dev[d]));
     if (int rc = fl[(size_t)d].init()) return rc;
   }
-  // the sum over the ranks of every rank's red[0] (left there by a partial reduction), in rank order, then the scalar step `step`
-  // (send slots red[0] / red[1] alternate: a rank may be one exchange ahead of another that still reads its previous partial;
-  // the scalar step leaves its sum in red[2])
-  int slot = 0;
-  auto combine = [&](fs::CgStep step, double arg) -> int {
-    std::vector<const double *> send((size_t)n);
-    std::vector<hipEvent_t> ready((size_t)n);
-    for (int d = 0; d < n; ++d) {
-      FS_HIP(hipSetDevice(D->dev[d]));
-      send[(size_t)d] = W.red[(size_t)d] + slot;
-      FS_HIP(hipEventRecord(T.ev[(size_t)d][0], D->stream[d]));
-      ready[(size_t)d] = T.ev[(size_t)d][0];
-    }
-    if (int rc = exchange_equal(D, send, W.redall, 1, D->stream, ready)) return rc;
-    for (int d = 0; d < n; ++d) {
-      FS_HIP(hipSetDevice(D->dev[d]));
-      if (int rc = fs::cg_dev_final(step, W.redall[(size_t)d], n, W.red[(size_t)d] + 2, W.st[(size_t)d], arg, D->stream[d])) return rc;
-    }
-    slot ^= 1;
-    return FS_OK;
-  };
+  SliceSums sums{M};
+  auto combine = [&](fs::CgStep step, double arg) { return sums.combine(step, arg, 1); };
   if (!gather) {
     for (int d = 0; d < n; ++d) {
       FS_HIP(hipSetDevice(D->dev[d]));
@@ -1555,7 +1608,7 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
     for (int d = 0; d < n; ++d) {
       const int lo = T.bounds[(size_t)d], nl = T.bounds[(size_t)d + 1] - lo;
       FS_HIP(hipSetDevice(D->dev[d]));
-      if (int rc = fs::cg_dev_init_partial(nl, W.b[(size_t)d] + lo, W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.part[(size_t)d], W.red[(size_t)d] + slot,
+      if (int rc = fs::cg_dev_init_partial(nl, W.b[(size_t)d] + lo, W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.part[(size_t)d], sums.send(d),
                                            D->stream[d])) return rc;
     }
     if (int rc = combine(fs::kStepCgStart, tol)) return rc;
@@ -1577,13 +1630,13 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
         FS_HIP(hipSetDevice(D->dev[d]));
         if (nl > 0)
           if (int rc = fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], M->y[(size_t)d], D->stream[d])) return rc;
-        if (int rc = fs::cg_dev_step_a(nl, lambda, W.p[(size_t)d], W.q[(size_t)d], W.part[(size_t)d], W.red[(size_t)d] + slot, W.st[(size_t)d], D->stream[d])) return rc;
+        if (int rc = fs::cg_dev_step_a(nl, lambda, W.p[(size_t)d], W.q[(size_t)d], W.part[(size_t)d], sums.send(d), W.st[(size_t)d], D->stream[d])) return rc;
       }
       if (int rc = combine(fs::kStepCgAlpha, 0.0)) return rc;             // alpha
       for (int d = 0; d < n; ++d) {
         const int nl = T.bounds[(size_t)d + 1] - T.bounds[(size_t)d];
         FS_HIP(hipSetDevice(D->dev[d]));
-        if (int rc = fs::cg_dev_step_b(nl, W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.q[(size_t)d], W.part[(size_t)d], W.red[(size_t)d] + slot,
+        if (int rc = fs::cg_dev_step_b(nl, W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.q[(size_t)d], W.part[(size_t)d], sums.send(d),
                                        W.st[(size_t)d], D->stream[d])) return rc;
       }
       if (int rc = combine(fs::kStepCgBeta, 0.0)) return rc;              // converged?  beta
@@ -1615,6 +1668,328 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
   }
   if (int rc = dist_sync(D)) return rc;
   if (out_iter) *out_iter = iterations;
+  return FS_OK;
+}
+
+// ---- the preconditioned solvers on the row-sharded matrix: fs_gram_diag, fs_pcg, fs_pcgn across the ranks ------------------
+// what fs_pcg / fs_pcgn refuse, in their order, in `who`'s name -- before a lock is taken or anything is copied
+static int pcg_params_ok(const char *who, const fs_pcg_params *prm)
+{
+  const std::string w(who);
+  if (prm->precond != FS_PRECOND_NONE && prm->precond != FS_PRECOND_JACOBI && prm->precond != FS_PRECOND_DIAG) {
+    fs::set_error(w + ": precond is none of FS_PRECOND_NONE / _JACOBI / _DIAG"); return FS_ERR_ARG;
+  }
+  if (prm->precond == FS_PRECOND_DIAG && !prm->diag) { fs::set_error(w + ": FS_PRECOND_DIAG without a diagonal"); return FS_ERR_ARG; }
+  if (!(prm->tol >= 0.0)) { fs::set_error(w + ": tol is negative or NaN"); return FS_ERR_ARG; }
+  return FS_OK;
+}
+
+// a second and third input vector of one call: the uploads of the one before still read the pinned staging buffer (upload_all)
+static int next_vec_in(fs_dist_matrix_t M, const std::vector<double *> &own, const double *src, size_t count)
+{
+  std::vector<double *> unused;
+  if (int rc = dist_sync(M->D)) return rc;
+  return vec_in(M, own, src, count, unused, false);
+}
+
+// Jacobi reads the plain CSR of every rank's shard of A': FS_ERR_RELEASED before anything else happens
+static int gram_diag_ready(fs_dist_matrix_t M, const char *who)
+{
+  DistSide &T = M->t;
+  for (int r = 0; r < M->D->n; ++r)
+    if (T.bounds[(size_t)r + 1] > T.bounds[(size_t)r])
+      if (int rc = fs::need_plain_csr(T.shard[(size_t)r]->a, who)) return rc;
+  return FS_OK;
+}
+
+// rank r: gram_diag_kernel over the rows of A' it owns, into dst[r] (slice-local)
+static int gram_diag_slices(fs_dist_matrix_t M, double lambda, const std::vector<double *> &dst)
+{
+  fs_dist_t D = M->D;
+  DistSide &T = M->t;
+  for (int r = 0; r < D->n; ++r) {
+    if (T.bounds[(size_t)r + 1] == T.bounds[(size_t)r]) continue;
+    FS_HIP(hipSetDevice(D->dev[r]));
+    if (int rc = fs_gram_diag(T.shard[(size_t)r], lambda, dst[(size_t)r], D->stream[r])) return rc;
+  }
+  return FS_OK;
+}
+
+// the whole d on every rank, in out[r]: the slices into the side's local buffers, then one whole-shard gather
+static int gram_diag_everywhere(fs_dist_matrix_t M, double lambda, const std::vector<double *> &out)
+{
+  if (int rc = context_usable(M->D)) return rc;
+  if (int rc = gram_diag_slices(M, lambda, M->t.local)) return rc;
+  return run_gather(M->D, exchange_of(M, true, 1), M->t.local, out, false);
+}
+
+// d = the diagonal of A'A + lambda I: fs_gram_diag on every rank's rows of A'.  CLOBBERS fs_dist_z (unless d itself is in HBM
+// of a rank's device: then the gather writes it)
+int fs_dist_gram_diag(fs_dist_matrix_t M, double lambda, double *d)
+{
+  if (!M || !d) { fs::set_error("fs_dist_gram_diag: NULL argument"); return FS_ERR_ARG; }
+  if (!M->t.built) { fs::set_error("fs_dist_gram_diag: call fs_dist_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
+  std::lock_guard<std::mutex> g(M->lock);
+  std::lock_guard<std::mutex> gd(M->D->lock);
+  DeviceGuard guard;
+  if (int rc = gram_diag_ready(M, "fs_dist_gram_diag")) return rc;
+  std::vector<double *> out;
+  int direct = -1;
+  if (int rc = vec_out(M, M->z, d, out, &direct)) return rc;
+  if (int rc = gram_diag_everywhere(M, lambda, out)) return rc;
+  if (direct < 0)
+    if (int rc = vec_store(M, 0, d, M->z[0], (size_t)M->ncol)) return rc;
+  return dist_sync(M->D);
+}
+
+// fs_pcg across the ranks; the schemes are fs_dist_cg's (option "dist_cg_scheme"):
+//   0 "replicate"  every rank holds whole x, r, p, q, dinv and launches fs_pcg's own kernels on them (pcg_dev_*): no exchange for
+//                  the sums.  Jacobi costs one gather of d per solve, a warm start one pair of sharded products on x0.
+//   1 "gather"     rank r keeps its slice -- the rows of A' it owns -- of x, r, p, q, dinv.  Jacobi's slice of d is the rank's own
+//                  gram_diag launch: no exchange.  Every sum is the slice tree of fs_dist_cg (SliceSums); the sums fs_pcg takes in one
+//                  pass travel together: {b.b, r.r} at the start, {r.r, r.z} behind the update with a preconditioner.
+// The caller's x is written once, at the end: whatever fails before leaves it as it was.
+int fs_dist_pcg(fs_dist_matrix_t M, double *x, const double *b, double lambda, const fs_pcg_params *prm, fs_pcg_info *info)
+{
+  const char *who = "fs_dist_pcg";
+  if (!M || !x || !b || !prm) { fs::set_error("fs_dist_pcg: NULL argument"); return FS_ERR_ARG; }
+  if (int rc = pcg_params_ok(who, prm)) return rc;
+  if (!M->t.built) { fs::set_error("fs_dist_pcg: call fs_dist_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
+  std::lock_guard<std::mutex> g(M->lock);
+  std::lock_guard<std::mutex> gd(M->D->lock);
+  DeviceGuard guard;
+  if (prm->precond == FS_PRECOND_JACOBI)
+    if (int rc = gram_diag_ready(M, "fs_dist_pcg with FS_PRECOND_JACOBI (fs_gram_diag)")) return rc;
+  fs::FixedOrderScope fixed(fs::options().cg_fixed_order != 0);
+  fs_dist_t D = M->D;
+  const int n = D->n, F = M->ncol;
+  const bool gather = fs::options().dist_cg_scheme == 1 && n > 1;
+  const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
+  const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
+  DistSide &T = M->t;
+  CgWork &W = M->cg;
+  if (int rc = ensure_cg_work(M)) return rc;
+  // d is staged in the vector that holds q later: the handle's z (whole) or the rank's slice buffer
+  const std::vector<double *> &stage = gather ? W.q : M->z;
+  auto lo_of = [&T](int d) { return T.bounds[(size_t)d]; };
+  auto rows_of = [&T](int d) { return T.bounds[(size_t)d + 1] - T.bounds[(size_t)d]; };
+  {
+    std::vector<double *> unused;
+    if (int rc = vec_in(M, W.b, b, (size_t)F, unused, false)) return rc;          // (always a copy: b is read all solve long)
+    if (warm)                                                                    // x0, whole, on every rank
+      if (int rc = next_vec_in(M, gather ? M->x : W.sol, x, (size_t)F)) return rc;
+    if (prm->precond == FS_PRECOND_DIAG)
+      if (int rc = next_vec_in(M, stage, prm->diag, (size_t)F)) return rc;
+  }
+  std::vector<fs::CgFlags> fl((size_t)n);
+  for (int d = 0; d < n; ++d) {
+    FS_HIP(hipSetDevice(D->dev[d]));
+    if (int rc = fl[(size_t)d].init()) return rc;
+  }
+  SliceSums sums{M};
+  auto dinv_of = [&](int d) -> const double * { return pre ? W.dinv[(size_t)d] : nullptr; };
+  if (!gather) {
+    if (prm->precond == FS_PRECOND_JACOBI)
+      if (int rc = gram_diag_everywhere(M, lambda, stage)) return rc;
+    for (int d = 0; d < n && pre; ++d) {
+      FS_HIP(hipSetDevice(D->dev[d]));
+      if (int rc = fs::pcg_dev_dinv(F, stage[(size_t)d], W.dinv[(size_t)d], D->stream[d])) return rc;
+    }
+    if (warm) {                                                                  // q = A'(A x0)
+      if (int rc = dist_product(M, false, 1, W.sol, M->y)) return rc;
+      if (int rc = dist_product(M, true, 1, M->y, M->z)) return rc;
+    }
+    for (int d = 0; d < n; ++d) {
+      FS_HIP(hipSetDevice(D->dev[d]));
+      if (int rc = fs::pcg_dev_init(F, warm, lambda, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], M->z[(size_t)d], W.part[(size_t)d],
+                                    W.red[(size_t)d], W.st[(size_t)d], prm->tol, D->stream[d])) return rc;
+      if (int rc = fs::pcg_dev_start(F, W.r[(size_t)d], dinv_of(d), M->x[(size_t)d], W.part[(size_t)d], W.red[(size_t)d], W.st[(size_t)d],
+                                     D->stream[d])) return rc;
+    }
+  } else {
+    if (prm->precond == FS_PRECOND_JACOBI)
+      if (int rc = gram_diag_slices(M, lambda, stage)) return rc;
+    for (int d = 0; d < n && pre; ++d) {
+      FS_HIP(hipSetDevice(D->dev[d]));
+      const double *dd = stage[(size_t)d] + (prm->precond == FS_PRECOND_DIAG ? lo_of(d) : 0);
+      if (int rc = fs::pcg_dev_dinv(rows_of(d), dd, W.dinv[(size_t)d], D->stream[d])) return rc;
+    }
+    if (warm) {                                                                  // the rank's slice of x0; q_r = A'_r (A x0)
+      for (int d = 0; d < n; ++d) {
+        FS_HIP(hipSetDevice(D->dev[d]));
+        if (rows_of(d) > 0)
+          FS_HIP(hipMemcpyAsync(W.sol[(size_t)d], M->x[(size_t)d] + lo_of(d), sizeof(double) * (size_t)rows_of(d), hipMemcpyDeviceToDevice, D->stream[d]));
+      }
+      if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;
+      for (int d = 0; d < n; ++d) {
+        FS_HIP(hipSetDevice(D->dev[d]));
+        if (rows_of(d) > 0)
+          if (int rc = fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], M->y[(size_t)d], D->stream[d])) return rc;
+      }
+    }
+    for (int d = 0; d < n; ++d) {
+      FS_HIP(hipSetDevice(D->dev[d]));
+      if (int rc = fs::pcg_dev_init_partial(rows_of(d), warm, lambda, W.b[(size_t)d] + lo_of(d), W.sol[(size_t)d], W.r[(size_t)d], W.q[(size_t)d],
+                                            W.part[(size_t)d], sums.send(d), D->stream[d])) return rc;
+    }
+    if (int rc = sums.combine(fs::kStepPcgStart, prm->tol, 2)) return rc;         // b.b, r.r, stop, done?
+    for (int d = 0; d < n; ++d) {
+      FS_HIP(hipSetDevice(D->dev[d]));
+      if (int rc = fs::pcg_dev_start_partial(rows_of(d), W.r[(size_t)d], dinv_of(d), W.p[(size_t)d], W.part[(size_t)d], sums.send(d),
+                                             W.st[(size_t)d], D->stream[d])) return rc;
+    }
+    if (int rc = sums.combine(fs::kStepPcgRz, 0.0, 1)) return rc;                 // r.z
+  }
+  int seen = ranks_done_at_start(D, W.st, who);              // done before the first iteration: no product is enqueued
+  if (seen < 0) return seen;
+  if (seen == kRanksGoOn && gather)
+    if (int rc = run_gather(D, exchange_of(M, true, 1), W.p, M->x, false)) return rc;     // the whole p on every rank
+  for (int iter = 0; seen == kRanksGoOn && iter < cap; iter++) {
+    if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;       // y = A p, its all-gather inside
+    if (!gather) {
+      if (int rc = dist_product(M, true, 1, M->y, M->z)) return rc;      // q = A' y, its all-gather inside
+      for (int d = 0; d < n; ++d) {
+        FS_HIP(hipSetDevice(D->dev[d]));
+        if (int rc = fs::pcg_dev_steps(F, lambda, W.sol[(size_t)d], W.r[(size_t)d], M->x[(size_t)d], M->z[(size_t)d], dinv_of(d),
+                                       W.part[(size_t)d], W.red[(size_t)d], W.st[(size_t)d], D->stream[d])) return rc;
+      }
+    } else {
+      for (int d = 0; d < n; ++d) {                                      // q_r = A'_r y: this rank's rows of A', no exchange
+        FS_HIP(hipSetDevice(D->dev[d]));
+        if (rows_of(d) > 0)
+          if (int rc = fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], M->y[(size_t)d], D->stream[d])) return rc;
+        if (int rc = fs::cg_dev_step_a(rows_of(d), lambda, W.p[(size_t)d], W.q[(size_t)d], W.part[(size_t)d], sums.send(d), W.st[(size_t)d],
+                                       D->stream[d])) return rc;
+      }
+      if (int rc = sums.combine(fs::kStepCgAlpha, 0.0, 1)) return rc;     // alpha = r.z / p.q
+      for (int d = 0; d < n; ++d) {
+        FS_HIP(hipSetDevice(D->dev[d]));
+        if (int rc = pre ? fs::pcg_dev_step_b(rows_of(d), W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.q[(size_t)d], W.dinv[(size_t)d],
+                                              W.part[(size_t)d], sums.send(d), W.st[(size_t)d], D->stream[d])
+                         : fs::cg_dev_step_b(rows_of(d), W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.q[(size_t)d], W.part[(size_t)d],
+                                             sums.send(d), W.st[(size_t)d], D->stream[d])) return rc;
+      }
+      if (int rc = sums.combine(fs::kStepPcgBeta, 0.0, pre ? 2 : 1)) return rc;   // r.r kept; converged?  beta
+      for (int d = 0; d < n; ++d) {
+        FS_HIP(hipSetDevice(D->dev[d]));
+        if (int rc = pre ? fs::pcg_dev_step_c(rows_of(d), W.p[(size_t)d], W.r[(size_t)d], W.dinv[(size_t)d], W.st[(size_t)d], D->stream[d])
+                         : fs::cg_dev_step_c(rows_of(d), W.p[(size_t)d], W.r[(size_t)d], W.st[(size_t)d], D->stream[d])) return rc;
+      }
+      if (int rc = run_gather(D, exchange_of(M, true, 1), W.p, M->x, false)) return rc;   // the new p on every rank
+    }
+    seen = ranks_after_iteration(D, fl, W.st, iter, who, [](int) { return FS_OK; });
+    if (seen < 0) return seen;
+  }
+  if (int rc = dist_sync(D)) return rc;
+  if (seen == kRanksDisagree) return FS_ERR_HIP;
+  int iterations = 0;
+  double st0[fs::kCgStateDoubles];
+  if (int rc = ranks_final_state(D, W.st, who, &iterations, st0)) return rc;
+  if (vector_device(x) >= 0)
+    if (int rc = wait_for_caller(vector_device(x))) return rc;
+  if (!gather) {
+    if (int rc = vec_store(M, 0, x, W.sol[0], (size_t)F)) return rc;
+  } else {
+    for (int d = 0; d < n; ++d)
+      if (rows_of(d) > 0)
+        if (int rc = vec_store(M, d, x + lo_of(d), W.sol[(size_t)d], (size_t)rows_of(d))) return rc;
+  }
+  if (int rc = dist_sync(D)) return rc;
+  fs::pcg_info_of(st0, info);
+  return FS_OK;
+}
+
+// fs_pcgn across the ranks, replicated whatever "dist_cg_scheme" says: every rank holds the whole F x k panels and launches
+// fs_pcgn's own kernels on them (pcgn_dev_*); T = A P and Q = A' T are the sharded k-column products (k = 1: the single-vector
+// ones).  The caller's X is written once, at the end.
+int fs_dist_pcgn(fs_dist_matrix_t M, double *X, const double *B, int k, double lambda, const fs_pcg_params *prm, fs_pcg_info *info)
+{
+  const char *who = "fs_dist_pcgn";
+  if (!M || !X || !B || !prm) { fs::set_error("fs_dist_pcgn: NULL argument"); return FS_ERR_ARG; }
+  if (k < 1 || k > FS_PCGN_MAX_RHS) { fs::set_error("fs_dist_pcgn: k outside 1..FS_PCGN_MAX_RHS"); return FS_ERR_ARG; }
+  if (int rc = pcg_params_ok(who, prm)) return rc;
+  if (!M->t.built) { fs::set_error("fs_dist_pcgn: call fs_dist_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
+  std::lock_guard<std::mutex> g(M->lock);
+  std::lock_guard<std::mutex> gd(M->D->lock);
+  DeviceGuard guard;
+  if (prm->precond == FS_PRECOND_JACOBI)
+    if (int rc = gram_diag_ready(M, "fs_dist_pcgn with FS_PRECOND_JACOBI (fs_gram_diag)")) return rc;
+  fs::FixedOrderScope fixed(fs::options().cg_fixed_order != 0);
+  fs_dist_t D = M->D;
+  const int n = D->n, F = M->ncol;
+  const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
+  const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
+  if (k > 1)
+    if (int rc = ensure_k(M, k)) return rc;
+  PnWork &W = M->pn;
+  if (!W.mem.ready || W.F != F || W.k != k) {
+    if (int rc = dist_sync(D)) return rc;
+    free_pn(D, W);
+    W.F = F; W.k = k;
+    const size_t fk = (size_t)(F ? F : 1) * (size_t)k;
+    if (int rc = W.mem.fill(D, [&](int d) -> int {
+          for (std::vector<double *> *v : {&W.sol, &W.r, &W.b})
+            if (int rc2 = W.mem.get(d, *v, fk)) return rc2;
+          if (int rc2 = W.mem.get(d, W.dinv, (size_t)(F ? F : 1))) return rc2;
+          if (int rc2 = W.mem.get(d, W.part, fs::pcgn_part_doubles(k))) return rc2;
+          if (int rc2 = W.mem.get(d, W.cs, (size_t)fs::kPcgnStateDoubles)) return rc2;
+          return W.mem.get(d, W.st, (size_t)fs::kCgStateDoubles);
+        })) return rc;
+  }
+  // the product vectors: P (replicated input of A), T = A P, Q = A' T
+  const std::vector<double *> &vp = k > 1 ? M->kw.x : M->x, &vt = k > 1 ? M->kw.y : M->y, &vq = k > 1 ? M->kw.z : M->z;
+  {
+    std::vector<double *> unused;
+    if (int rc = vec_in(M, W.b, B, (size_t)F * k, unused, false)) return rc;
+    if (warm)
+      if (int rc = next_vec_in(M, W.sol, X, (size_t)F * k)) return rc;
+    if (prm->precond == FS_PRECOND_DIAG)
+      if (int rc = next_vec_in(M, vq, prm->diag, (size_t)F)) return rc;            // (d is staged where Q lives later)
+  }
+  std::vector<fs::CgFlags> fl((size_t)n);
+  for (int d = 0; d < n; ++d) {
+    FS_HIP(hipSetDevice(D->dev[d]));
+    if (int rc = fl[(size_t)d].init()) return rc;
+    if (int rc = fs::pcgn_dev_clear(W.cs[(size_t)d], D->stream[d])) return rc;
+  }
+  if (prm->precond == FS_PRECOND_JACOBI)
+    if (int rc = gram_diag_everywhere(M, lambda, vq)) return rc;
+  for (int d = 0; d < n && pre; ++d) {
+    FS_HIP(hipSetDevice(D->dev[d]));
+    if (int rc = fs::pcg_dev_dinv(F, vq[(size_t)d], W.dinv[(size_t)d], D->stream[d])) return rc;
+  }
+  if (warm) {                                                // Q = A'(A X0): one pair of k-column products
+    if (int rc = dist_product(M, false, k, W.sol, vt)) return rc;
+    if (int rc = dist_product(M, true, k, vt, vq)) return rc;
+  }
+  for (int d = 0; d < n; ++d) {
+    FS_HIP(hipSetDevice(D->dev[d]));
+    if (int rc = fs::pcgn_dev_init(F, k, warm, lambda, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d],
+                                   pre ? W.dinv[(size_t)d] : nullptr, W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], prm->tol,
+                                   D->stream[d])) return rc;
+  }
+  int seen = ranks_done_at_start(D, W.st, who);
+  if (seen < 0) return seen;
+  for (int iter = 0; seen == kRanksGoOn && iter < cap; iter++) {
+    if (int rc = dist_product(M, false, k, vp, vt)) return rc;           // T = A P
+    if (int rc = dist_product(M, true, k, vt, vq)) return rc;            // Q = A' T
+    seen = ranks_after_iteration(D, fl, W.st, iter, who, [&](int d) {    // a rank's steps and its flags in one pass
+      return fs::pcgn_dev_steps(F, k, lambda, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d],
+                                pre ? W.dinv[(size_t)d] : nullptr, W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], D->stream[d]);
+    });
+    if (seen < 0) return seen;
+  }
+  if (int rc = dist_sync(D)) return rc;
+  if (seen == kRanksDisagree) return FS_ERR_HIP;
+  int iterations = 0;
+  double st0[fs::kCgStateDoubles], cs0[fs::kPcgnStateDoubles] = {0.0};
+  if (int rc = ranks_final_state(D, W.st, who, &iterations, st0)) return rc;
+  FS_HIP(hipMemcpy(cs0, W.cs[0], sizeof(double) * (size_t)k * (fs::kPcgnStateDoubles / FS_PCGN_MAX_RHS), hipMemcpyDeviceToHost));   // (rank 0's device is current)
+  if (vector_device(X) >= 0)
+    if (int rc = wait_for_caller(vector_device(X))) return rc;
+  if (int rc = vec_store(M, 0, X, W.sol[0], (size_t)F * k)) return rc;
+  if (int rc = dist_sync(D)) return rc;
+  fs::pcgn_note_state(st0, cs0, k, info);
   return FS_OK;
 }
 
