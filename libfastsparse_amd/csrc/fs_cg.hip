@@ -1171,89 +1171,115 @@ struct Workspace {
   ~Workspace() { for (void *p : bufs) (void)hipFree(p); }
 };
 
-// ---- the vector steps of CG as launchers, for callers that bring their own products (fs_dist_cg: the same steps, replicated,
-// on every device of a row-sharded matrix -- same kernels on the same data, so every device takes the same decisions).
-// part: kCgPartDoubles doubles of scratch, red: 4 doubles, st: kCgStateDoubles doubles (st[kCgStateDone], st[kCgStateIter]).
-int cg_dev_init(int n, const double *b, double *x, double *r, double *p, double *part, double *red, double *st, double tol,
-                hipStream_t s)
-{
-  hipLaunchKernelGGL(cg_init_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, b, x, r, p, part);
-  hipLaunchKernelGGL((final_step_kernel<1, kStepCgStart>), dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red, st, tol);
-  FS_HIP(hipGetLastError());
-  return FS_OK;
-}
+// ---- the vector steps of fs_cg and fs_pcg as launchers, for callers that bring their own products (fs_dist_cg, fs_dist_pcg: the
+// same steps on every rank of a row-sharded matrix -- same kernels on the same data, so every rank takes the same decisions).
+// Every step that takes sums has ONE launcher and is told where they go (CgSums): whole-vector sums are finished by
+// final_step_kernel, a slice's sums by final_sum_kernel into the rank's send slot -- and, gathered, by cg_dev_final.
 
-// behind q = A'(A p): q += lambda p, alpha, x and r, the convergence test and beta, the new p -- all on the device.
-// fs_pcg without a preconditioner runs these launches with its own convergence step (it also keeps r.r)
-int cg_dev_steps(int n, double lambda, double *x, double *r, double *p, double *q, double *part, double *red, double *st,
-                 hipStream_t s, CgStep beta)
-{
-  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
-  hipLaunchKernelGGL(cg_shift_dot_dev_kernel, g, blk, 0, s, n, lambda, q, p, part, st);
-  hipLaunchKernelGGL((final_step_kernel<1, kStepCgAlpha>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);   // alpha
-  hipLaunchKernelGGL(cg_update_dev_kernel, g, blk, 0, s, n, x, r, p, q, part, st);
-  // converged? beta
-  if (beta == kStepPcgBeta) hipLaunchKernelGGL((final_step_kernel<1, kStepPcgBeta>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);
-  else                      hipLaunchKernelGGL((final_step_kernel<1, kStepCgBeta>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);
-  hipLaunchKernelGGL(cg_direction_dev_kernel, g, blk, 0, s, n, p, r, st);
-  FS_HIP(hipGetLastError());
-  return FS_OK;
-}
-
-int cg_dev_init_partial(int n, const double *b, double *x, double *r, double *p, double *part, double *red_out, hipStream_t s)
-{
-  hipLaunchKernelGGL(cg_init_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, b, x, r, p, part);
-  hipLaunchKernelGGL(final_sum_kernel<1>, dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red_out);
-  FS_HIP(hipGetLastError());
-  return FS_OK;
-}
-
-int cg_dev_step_a(int n, double lambda, const double *p, double *q, double *part, double *red_out, const double *st, hipStream_t s)
-{
-  hipLaunchKernelGGL(cg_shift_dot_dev_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, lambda, q, p, part, st);
-  hipLaunchKernelGGL(final_sum_kernel<1>, dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red_out);
-  FS_HIP(hipGetLastError());
-  return FS_OK;
-}
-
-int cg_dev_step_b(int n, double *x, double *r, const double *p, const double *q, double *part, double *red_out, const double *st,
-                  hipStream_t s)
-{
-  hipLaunchKernelGGL(cg_update_dev_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, x, r, p, q, part, st);
-  hipLaunchKernelGGL(final_sum_kernel<1>, dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red_out);
-  FS_HIP(hipGetLastError());
-  return FS_OK;
-}
-
-int cg_dev_step_c(int n, double *p, const double *r, const double *st, hipStream_t s)
-{
-  hipLaunchKernelGGL(cg_direction_dev_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, p, r, st);
-  FS_HIP(hipGetLastError());
-  return FS_OK;
-}
-
-// `partials`: count x nv doubles, rank-major as the exchange leaves them -- block_sum<NV>'s own layout, so every one of the nv sums
-// is finish_sum's tree (stage 2) over its count values.  nv = 2 for kStepPcgStart {b.b, r.r} and for kStepPcgBeta with a
-// preconditioner {r.r, r.z}; red_out has room for nv doubles
-int cg_dev_final(CgStep step, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s, int nv)
+// The one-workgroup kernel that finishes nv sums of `count` partials each and takes the scalar step: false where fs_cg and fs_pcg
+// have no such step
+static bool launch_final_step(CgStep step, int nv, const double *partials, int count, double *red, double *st, double arg, hipStream_t s)
 {
   const dim3 one(1), blk(kRedThreads);
-  const bool pcg2 = (step == kStepPcgStart) || (step == kStepPcgBeta && nv == 2);
-  if (nv != (pcg2 ? 2 : 1)) { set_error("cg_dev_final: the step does not take this many sums"); return FS_ERR_ARG; }
-  if (step == kStepCgStart)       hipLaunchKernelGGL((final_step_kernel<1, kStepCgStart>), one, blk, 0, s, partials, count, red_out, st, arg);
-  else if (step == kStepCgAlpha)  hipLaunchKernelGGL((final_step_kernel<1, kStepCgAlpha>), one, blk, 0, s, partials, count, red_out, st, arg);
-  else if (step == kStepCgBeta)   hipLaunchKernelGGL((final_step_kernel<1, kStepCgBeta>), one, blk, 0, s, partials, count, red_out, st, arg);
-  else if (step == kStepPcgStart) hipLaunchKernelGGL((final_step_kernel<2, kStepPcgStart>), one, blk, 0, s, partials, count, red_out, st, arg);
-  else if (step == kStepPcgRz)    hipLaunchKernelGGL((final_step_kernel<1, kStepPcgRz>), one, blk, 0, s, partials, count, red_out, st, arg);
-  else if (step == kStepPcgBeta && nv == 2) hipLaunchKernelGGL((final_step_kernel<2, kStepPcgBeta>), one, blk, 0, s, partials, count, red_out, st, arg);
-  else if (step == kStepPcgBeta)  hipLaunchKernelGGL((final_step_kernel<1, kStepPcgBeta>), one, blk, 0, s, partials, count, red_out, st, arg);
-  else { set_error("cg_dev_final: not a step of fs_cg or fs_pcg"); return FS_ERR_ARG; }
+  switch ((int)step * 4 + nv) {
+    case kStepCgStart * 4 + 1:  hipLaunchKernelGGL((final_step_kernel<1, kStepCgStart>), one, blk, 0, s, partials, count, red, st, arg); return true;
+    case kStepCgAlpha * 4 + 1:  hipLaunchKernelGGL((final_step_kernel<1, kStepCgAlpha>), one, blk, 0, s, partials, count, red, st, arg); return true;
+    case kStepCgBeta * 4 + 1:   hipLaunchKernelGGL((final_step_kernel<1, kStepCgBeta>), one, blk, 0, s, partials, count, red, st, arg); return true;
+    case kStepPcgStart * 4 + 2: hipLaunchKernelGGL((final_step_kernel<2, kStepPcgStart>), one, blk, 0, s, partials, count, red, st, arg); return true;
+    case kStepPcgRz * 4 + 1:    hipLaunchKernelGGL((final_step_kernel<1, kStepPcgRz>), one, blk, 0, s, partials, count, red, st, arg); return true;
+    case kStepPcgBeta * 4 + 1:  hipLaunchKernelGGL((final_step_kernel<1, kStepPcgBeta>), one, blk, 0, s, partials, count, red, st, arg); return true;
+    case kStepPcgBeta * 4 + 2:  hipLaunchKernelGGL((final_step_kernel<2, kStepPcgBeta>), one, blk, 0, s, partials, count, red, st, arg); return true;
+    default: return false;
+  }
+}
+
+// behind a vector kernel that left nv sums per workgroup in S.part
+static int finish_sums(const CgSums &S, CgStep step, int nv, double arg, hipStream_t s)
+{
+  if (S.slice) {
+    if (nv == 2) hipLaunchKernelGGL(final_sum_kernel<2>, dim3(1), dim3(kRedThreads), 0, s, S.part, kRedBlocks, S.slice);
+    else         hipLaunchKernelGGL(final_sum_kernel<1>, dim3(1), dim3(kRedThreads), 0, s, S.part, kRedBlocks, S.slice);
+  } else if (!launch_final_step(step, nv, S.part, kRedBlocks, S.red, S.st, arg, s)) {
+    set_error("CG launcher: no scalar step for these sums"); return FS_ERR_ARG;
+  }
   FS_HIP(hipGetLastError());
   return FS_OK;
 }
 
-// ---- fs_pcg's steps as launchers: fs_pcg calls them on whole vectors, fs_dist_pcg on every rank (scheme "replicate": whole
-// vectors; scheme "gather": the *_partial / step_b / step_c forms on the rank's slice, the sums finished by cg_dev_final).
+// fs_cg's start: x = 0, r = p = b; b.b, the stopping threshold
+int cg_dev_init(int n, const double *b, double *x, double *r, double *p, const CgSums &S, double tol, hipStream_t s)
+{
+  hipLaunchKernelGGL(cg_init_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, b, x, r, p, S.part);
+  return finish_sums(S, kStepCgStart, 1, tol, s);
+}
+
+// fs_pcg's.  cold: x = 0, r = b; warm (q = A'(A x) on entry): q += lambda x, r = b - q; then {b.b, r.r}, stop, done?
+int pcg_dev_init(int n, bool warm, double lambda, const double *b, double *x, double *r, double *q, const CgSums &S, double tol,
+                 hipStream_t s)
+{
+  if (warm) hipLaunchKernelGGL(pcg_init_kernel<true>, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, lambda, b, x, r, q, S.part);
+  else      hipLaunchKernelGGL(pcg_init_kernel<false>, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, lambda, b, x, r, q, S.part);
+  return finish_sums(S, kStepPcgStart, 2, tol, s);
+}
+
+// p = z = r dinv (dinv NULL: r), r.z
+int pcg_dev_start(int n, const double *r, const double *dinv, double *p, const CgSums &S, hipStream_t s)
+{
+  if (dinv) hipLaunchKernelGGL(pcg_start_kernel<true>, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, r, dinv, p, S.part, S.st);
+  else      hipLaunchKernelGGL(pcg_start_kernel<false>, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, r, dinv, p, S.part, S.st);
+  return finish_sums(S, kStepPcgRz, 1, 0.0, s);
+}
+
+// behind q = A'(A p): q += lambda p, p.q; alpha = rsq_old / p.q (fs_pcg: r.z / p.q)
+int cg_dev_shift_dot(int n, double lambda, const double *p, double *q, const CgSums &S, hipStream_t s)
+{
+  hipLaunchKernelGGL(cg_shift_dot_dev_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, lambda, q, p, S.part, S.st);
+  return finish_sums(S, kStepCgAlpha, 1, 0.0, s);
+}
+
+// x and r; r.r, or {r.r, r.z} with a preconditioner; `beta` is the convergence step: kStepCgBeta, or fs_pcg's kStepPcgBeta (it
+// also keeps r.r)
+int cg_dev_update(int n, double *x, double *r, const double *p, const double *q, const double *dinv, const CgSums &S, CgStep beta,
+                  hipStream_t s)
+{
+  if (dinv) hipLaunchKernelGGL(pcg_update_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, x, r, p, q, dinv, S.part, S.st);
+  else      hipLaunchKernelGGL(cg_update_dev_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, x, r, p, q, S.part, S.st);
+  return finish_sums(S, beta, dinv ? 2 : 1, 0.0, s);
+}
+
+// the new p = z + beta p
+int cg_dev_direction(int n, double *p, const double *r, const double *dinv, const double *st, hipStream_t s)
+{
+  if (dinv) hipLaunchKernelGGL(pcg_direction_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, p, r, dinv, st);
+  else      hipLaunchKernelGGL(cg_direction_dev_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, p, r, st);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// everything of an iteration behind q = A'(A p) on whole vectors, all on the device.  fs_cg: (NULL, kStepCgBeta); fs_pcg:
+// kStepPcgBeta -- without a preconditioner it runs fs_cg's launches with its own convergence step
+int cg_dev_steps(int n, double lambda, double *x, double *r, double *p, double *q, const double *dinv, const CgSums &S, CgStep beta,
+                 hipStream_t s)
+{
+  if (int rc = cg_dev_shift_dot(n, lambda, p, q, S, s)) return rc;
+  if (int rc = cg_dev_update(n, x, r, p, q, dinv, S, beta, s)) return rc;
+  return cg_dev_direction(n, p, r, dinv, S.st, s);
+}
+
+// the sums of every rank's slice, gathered.  `partials`: count x nv doubles, rank-major as the exchange leaves them --
+// block_sum<NV>'s own layout, so every one of the nv sums is finish_sum's tree (stage 2) over its count values.  nv = 2 for
+// kStepPcgStart {b.b, r.r} and for kStepPcgBeta with a preconditioner {r.r, r.z}; red_out has room for nv doubles
+int cg_dev_final(CgStep step, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s, int nv)
+{
+  const bool pcg2 = (step == kStepPcgStart) || (step == kStepPcgBeta && nv == 2);
+  if (nv != (pcg2 ? 2 : 1)) { set_error("cg_dev_final: the step does not take this many sums"); return FS_ERR_ARG; }
+  if (!launch_final_step(step, nv, partials, count, red_out, st, arg, s)) {
+    set_error("cg_dev_final: not a step of fs_cg or fs_pcg"); return FS_ERR_ARG;
+  }
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
 // dinv = 1 / d, 1 where d is 0; in place or not
 int pcg_dev_dinv(int n, const double *d, double *dinv, hipStream_t s)
 {
@@ -1262,87 +1288,15 @@ int pcg_dev_dinv(int n, const double *d, double *dinv, hipStream_t s)
   return FS_OK;
 }
 
-static void pcg_launch_init(int n, bool warm, double lambda, const double *b, double *x, double *r, double *q, double *part, hipStream_t s)
+// what fs_pcg, fs_pcgn and their sharded forms refuse in a fs_pcg_params, in this order, in `who`'s name
+int pcg_params_ok(const char *who, const fs_pcg_params *prm)
 {
-  if (warm) hipLaunchKernelGGL(pcg_init_kernel<true>, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, lambda, b, x, r, q, part);
-  else      hipLaunchKernelGGL(pcg_init_kernel<false>, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, lambda, b, x, r, q, part);
-}
-
-static void pcg_launch_start(int n, const double *r, const double *dinv, double *p, double *part, const double *st, hipStream_t s)
-{
-  if (dinv) hipLaunchKernelGGL(pcg_start_kernel<true>, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, r, dinv, p, part, st);
-  else      hipLaunchKernelGGL(pcg_start_kernel<false>, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, r, dinv, p, part, st);
-}
-
-// cold: x = 0, r = b; warm (q = A'(A x) on entry): q += lambda x, r = b - q; then b.b, r.r, stop, done?
-int pcg_dev_init(int n, bool warm, double lambda, const double *b, double *x, double *r, double *q, double *part, double *red, double *st,
-                 double tol, hipStream_t s)
-{
-  pcg_launch_init(n, warm, lambda, b, x, r, q, part, s);
-  hipLaunchKernelGGL((final_step_kernel<2, kStepPcgStart>), dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red, st, tol);
-  FS_HIP(hipGetLastError());
-  return FS_OK;
-}
-
-// p = z = r dinv (dinv NULL: r), r.z
-int pcg_dev_start(int n, const double *r, const double *dinv, double *p, double *part, double *red, double *st, hipStream_t s)
-{
-  pcg_launch_start(n, r, dinv, p, part, st, s);
-  hipLaunchKernelGGL((final_step_kernel<1, kStepPcgRz>), dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red, st, 0.0);
-  FS_HIP(hipGetLastError());
-  return FS_OK;
-}
-
-// everything of an iteration behind q = A'(A p).  dinv NULL: fs_cg's launches with fs_pcg's convergence step
-int pcg_dev_steps(int n, double lambda, double *x, double *r, double *p, double *q, const double *dinv, double *part, double *red,
-                  double *st, hipStream_t s)
-{
-  if (!dinv) return cg_dev_steps(n, lambda, x, r, p, q, part, red, st, s, kStepPcgBeta);
-  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
-  hipLaunchKernelGGL(cg_shift_dot_dev_kernel, g, blk, 0, s, n, lambda, q, p, part, st);
-  hipLaunchKernelGGL((final_step_kernel<1, kStepCgAlpha>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);       // alpha = r.z / p.q
-  hipLaunchKernelGGL(pcg_update_kernel, g, blk, 0, s, n, x, r, p, q, dinv, part, st);
-  hipLaunchKernelGGL((final_step_kernel<2, kStepPcgBeta>), one, blk, 0, s, part, kRedBlocks, red, st, 0.0);       // converged? beta
-  hipLaunchKernelGGL(pcg_direction_kernel, g, blk, 0, s, n, p, r, dinv, st);
-  FS_HIP(hipGetLastError());
-  return FS_OK;
-}
-
-// the slice forms: red_out[0..2) = {b.b, r.r} of the slice
-int pcg_dev_init_partial(int n, bool warm, double lambda, const double *b, double *x, double *r, double *q, double *part, double *red_out,
-                         hipStream_t s)
-{
-  pcg_launch_init(n, warm, lambda, b, x, r, q, part, s);
-  hipLaunchKernelGGL(final_sum_kernel<2>, dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red_out);
-  FS_HIP(hipGetLastError());
-  return FS_OK;
-}
-
-// red_out[0] = r.z of the slice
-int pcg_dev_start_partial(int n, const double *r, const double *dinv, double *p, double *part, double *red_out, const double *st,
-                          hipStream_t s)
-{
-  pcg_launch_start(n, r, dinv, p, part, st, s);
-  hipLaunchKernelGGL(final_sum_kernel<1>, dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red_out);
-  FS_HIP(hipGetLastError());
-  return FS_OK;
-}
-
-// red_out[0..2) = {r.r, r.z} of the slice (without a preconditioner: cg_dev_step_b)
-int pcg_dev_step_b(int n, double *x, double *r, const double *p, const double *q, const double *dinv, double *part, double *red_out,
-                   const double *st, hipStream_t s)
-{
-  hipLaunchKernelGGL(pcg_update_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, x, r, p, q, dinv, part, st);
-  hipLaunchKernelGGL(final_sum_kernel<2>, dim3(1), dim3(kRedThreads), 0, s, part, kRedBlocks, red_out);
-  FS_HIP(hipGetLastError());
-  return FS_OK;
-}
-
-// (without a preconditioner: cg_dev_step_c)
-int pcg_dev_step_c(int n, double *p, const double *r, const double *dinv, const double *st, hipStream_t s)
-{
-  hipLaunchKernelGGL(pcg_direction_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, p, r, dinv, st);
-  FS_HIP(hipGetLastError());
+  const std::string w(who);
+  if (prm->precond != FS_PRECOND_NONE && prm->precond != FS_PRECOND_JACOBI && prm->precond != FS_PRECOND_DIAG) {
+    set_error(w + ": precond is none of FS_PRECOND_NONE / _JACOBI / _DIAG"); return FS_ERR_ARG;
+  }
+  if (prm->precond == FS_PRECOND_DIAG && !prm->diag) { set_error(w + ": FS_PRECOND_DIAG without a diagonal"); return FS_ERR_ARG; }
+  if (!(prm->tol >= 0.0)) { set_error(w + ": tol is negative or NaN"); return FS_ERR_ARG; }
   return FS_OK;
 }
 
@@ -1627,8 +1581,9 @@ int fs_cg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lamb
   if (int rc = f.alloc()) return rc;
   const int F = f.F;
   hipStream_t s = (hipStream_t)stream;
-  if (int rc = cg_dev_init(F, b, x, f.r, f.p, f.part, f.red, f.st, tol, s)) return rc;
-  if (int rc = f.iterate(F, false, [&] { return cg_dev_steps(F, lambda, x, f.r, f.p, f.q, f.part, f.red, f.st, s); })) return rc;
+  const CgSums sums{f.part, f.red, f.st};
+  if (int rc = cg_dev_init(F, b, x, f.r, f.p, sums, tol, s)) return rc;
+  if (int rc = f.iterate(F, false, [&] { return cg_dev_steps(F, lambda, x, f.r, f.p, f.q, nullptr, sums, kStepCgBeta, s); })) return rc;
   if (int rc = f.finish()) return rc;
   if (out_iter) *out_iter = (int)f.fin[kStIter];
   return FS_OK;
@@ -1660,11 +1615,7 @@ int fs_pcg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lam
   if (!A || !At || !x || !b || !prm) { set_error("fs_pcg: NULL argument"); return FS_ERR_ARG; }
   CgSolve f{"fs_pcg", A, At, 1, stream};
   if (int rc = f.shape()) return rc;
-  if (prm->precond != FS_PRECOND_NONE && prm->precond != FS_PRECOND_JACOBI && prm->precond != FS_PRECOND_DIAG) {
-    set_error("fs_pcg: precond is none of FS_PRECOND_NONE / _JACOBI / _DIAG"); return FS_ERR_ARG;
-  }
-  if (prm->precond == FS_PRECOND_DIAG && !prm->diag) { set_error("fs_pcg: FS_PRECOND_DIAG without a diagonal"); return FS_ERR_ARG; }
-  if (!(prm->tol >= 0.0)) { set_error("fs_pcg: tol is negative or NaN"); return FS_ERR_ARG; }
+  if (int rc = pcg_params_ok("fs_pcg", prm)) return rc;
   if (prm->precond == FS_PRECOND_JACOBI)                     // before anything is written to x
     if (int rc = need_plain_csr(At->a, "fs_pcg with FS_PRECOND_JACOBI (fs_gram_diag)")) return rc;
   if (int rc = f.ready()) return rc;
@@ -1674,7 +1625,8 @@ int fs_pcg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lam
   hipStream_t s = (hipStream_t)stream;
   double *dinv = nullptr;
   if (int rc = f.alloc(pre ? &dinv : nullptr, F)) return rc;
-  double *r = f.r, *p = f.p, *q = f.q, *part = f.part, *red = f.red, *st = f.st;
+  double *r = f.r, *p = f.p, *q = f.q;
+  const CgSums sums{f.part, f.red, f.st};
   if (prm->precond == FS_PRECOND_JACOBI)
     if (int rc = fs_gram_diag(At, lambda, dinv, stream)) return rc;
   if (pre)
@@ -1683,9 +1635,9 @@ int fs_pcg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lam
     if (int rc = fs_spmv(A, f.tmp, x, stream)) return rc;
     if (int rc = fs_spmv(At, q, f.tmp, stream)) return rc;
   }
-  if (int rc = pcg_dev_init(F, warm, lambda, b, x, r, q, part, red, st, prm->tol, s)) return rc;   // b.b, r.r, stop, done?
-  if (int rc = pcg_dev_start(F, r, dinv, p, part, red, st, s)) return rc;                          // p = z, r.z
-  if (int rc = f.iterate(cap, true, [&] { return pcg_dev_steps(F, lambda, x, r, p, q, dinv, part, red, st, s); })) return rc;
+  if (int rc = pcg_dev_init(F, warm, lambda, b, x, r, q, sums, prm->tol, s)) return rc;            // b.b, r.r, stop, done?
+  if (int rc = pcg_dev_start(F, r, dinv, p, sums, s)) return rc;                                   // p = z, r.z
+  if (int rc = f.iterate(cap, true, [&] { return cg_dev_steps(F, lambda, x, r, p, q, dinv, sums, kStepPcgBeta, s); })) return rc;
   if (int rc = f.finish()) return rc;
   pcg_info_of(f.fin, info);
   return FS_OK;
@@ -1763,11 +1715,7 @@ int fs_pcgn(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k, do
   if (k < 1 || k > kPcgnMaxRhs) { set_error("fs_pcgn: k outside 1..FS_PCGN_MAX_RHS"); return FS_ERR_ARG; }
   CgSolve f{"fs_pcgn", A, At, k, stream};
   if (int rc = f.shape()) return rc;
-  if (prm->precond != FS_PRECOND_NONE && prm->precond != FS_PRECOND_JACOBI && prm->precond != FS_PRECOND_DIAG) {
-    set_error("fs_pcgn: precond is none of FS_PRECOND_NONE / _JACOBI / _DIAG"); return FS_ERR_ARG;
-  }
-  if (prm->precond == FS_PRECOND_DIAG && !prm->diag) { set_error("fs_pcgn: FS_PRECOND_DIAG without a diagonal"); return FS_ERR_ARG; }
-  if (!(prm->tol >= 0.0)) { set_error("fs_pcgn: tol is negative or NaN"); return FS_ERR_ARG; }
+  if (int rc = pcg_params_ok("fs_pcgn", prm)) return rc;
   if (prm->precond == FS_PRECOND_JACOBI)                     // before anything is written to X
     if (int rc = need_plain_csr(At->a, "fs_pcgn with FS_PRECOND_JACOBI (fs_gram_diag)")) return rc;
   if (k >= 2) {                                              // the k-column copies of both matrices (fs_spmm itself never builds)

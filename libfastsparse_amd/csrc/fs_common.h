@@ -350,41 +350,34 @@ enum CgStep {
   kStepPcgRz,      //         r.z of the first direction
   kStepPcgBeta     //         {r.r[, r.z]}: r.r kept; converged -> done; else beta = r.z new / r.z, r.z = r.z new, ++iter
 };
-int cg_dev_init(int n, const double *b, double *x, double *r, double *p, double *part, double *red, double *st, double tol,
-                hipStream_t s);                                                // x = 0, r = p = b; b.b, the stopping threshold
-// everything of an iteration behind q = A'(A p); `beta` is its convergence step: kStepCgBeta, or fs_pcg's kStepPcgBeta
-int cg_dev_steps(int n, double lambda, double *x, double *r, double *p, double *q, double *part, double *red, double *st,
-                 hipStream_t s, CgStep beta = kStepCgBeta);
+// where a step's sums go.  part: kCgPartDoubles doubles of scratch, red: 4 doubles, st: kCgStateDoubles.  slice NULL: the vectors
+// are whole, the one-workgroup kernel behind the step finishes the sums and takes the scalar step on st[].  slice set: the vectors
+// are one rank's SLICE of the unknowns (fs_dist_cg / fs_dist_pcg, scheme "gather"), the rank's partial sums are left in slice[0..nv);
+// the partials of all ranks, gathered, go through cg_dev_final, which adds them in rank order and takes the scalar step
+struct CgSums { double *part, *red, *st, *slice = nullptr; };
+// fs_cg's and fs_pcg's steps; dinv NULL: no preconditioner, z is r, fs_cg's kernels.  One launcher per step
+int cg_dev_init(int n, const double *b, double *x, double *r, double *p, const CgSums &S, double tol, hipStream_t s);   // fs_cg: x = 0, r = p = b; b.b
+int pcg_dev_init(int n, bool warm, double lambda, const double *b, double *x, double *r, double *q, const CgSums &S, double tol,
+                 hipStream_t s);                                                 // fs_pcg: x, r; {b.b, r.r}, stop, done?
+int pcg_dev_start(int n, const double *r, const double *dinv, double *p, const CgSums &S, hipStream_t s);               // p = z; r.z
+int cg_dev_shift_dot(int n, double lambda, const double *p, double *q, const CgSums &S, hipStream_t s);                 // q += lambda p; p.q: alpha
+// x, r; r.r or, with dinv, {r.r, r.z}: `beta` is the convergence step, kStepCgBeta (fs_cg) or kStepPcgBeta
+int cg_dev_update(int n, double *x, double *r, const double *p, const double *q, const double *dinv, const CgSums &S, CgStep beta,
+                  hipStream_t s);
+int cg_dev_direction(int n, double *p, const double *r, const double *dinv, const double *st, hipStream_t s);           // p = z + beta p
+// everything of an iteration behind q = A'(A p) on whole vectors: shift_dot, update, direction
+int cg_dev_steps(int n, double lambda, double *x, double *r, double *p, double *q, const double *dinv, const CgSums &S, CgStep beta,
+                 hipStream_t s);
+// nv sums per rank, rank-major: 2 for kStepPcgStart {b.b, r.r} and for kStepPcgBeta with a preconditioner {r.r, r.z}, else 1
+int cg_dev_final(CgStep step, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s, int nv = 1);
+int pcg_dev_dinv(int n, const double *d, double *dinv, hipStream_t s);           // dinv = 1 / d, 1 where d is 0; in place or not
+int pcg_params_ok(const char *who, const fs_pcg_params *prm);                    // FS_ERR_ARG with the text in `who`'s name, before anything is done
+void pcg_info_of(const double *st_host, fs_pcg_info *info);                      // info may be NULL
 // two right-hand sides, row-major n x 2 (bsbm_cg2, cg.h:85-187): init is synchronous and returns the column norms of B for finish
 int cg2_dev_init(int n, const double *B, double *X, double *R, double *P, double *part, double *red, double *st, double tol,
                  double *norms, hipStream_t s);
 int cg2_dev_steps(int n, double lambda, double *X, double *R, double *P, double *Q, double *part, double *red, double *st, hipStream_t s);
 int cg2_dev_finish(int n, const double *norms, double *X, hipStream_t s);
-// the same steps for a SLICE of the unknowns (fs_dist_cg, scheme "gather"): every step leaves this rank's partial dot in
-// *red_out; the partials of all ranks, gathered, go through cg_dev_final, which adds them in rank order and does the scalar step
-// `step` (one of fs_cg's: kStepCgStart, kStepCgAlpha, kStepCgBeta)
-int cg_dev_init_partial(int n, const double *b, double *x, double *r, double *p, double *part, double *red_out, hipStream_t s);
-int cg_dev_step_a(int n, double lambda, const double *p, double *q, double *part, double *red_out, const double *st, hipStream_t s);
-int cg_dev_step_b(int n, double *x, double *r, const double *p, const double *q, double *part, double *red_out, const double *st,
-                  hipStream_t s);
-int cg_dev_step_c(int n, double *p, const double *r, const double *st, hipStream_t s);
-// nv sums per rank, rank-major: 2 for kStepPcgStart {b.b, r.r} and for kStepPcgBeta behind pcg_dev_step_b {r.r, r.z}, else 1
-int cg_dev_final(CgStep step, const double *partials, int count, double *red_out, double *st, double arg, hipStream_t s, int nv = 1);
-// ---- fs_pcg's steps (dinv NULL: no preconditioner, z is r) on whole vectors, and on a slice like the cg_dev_* forms above
-int pcg_dev_dinv(int n, const double *d, double *dinv, hipStream_t s);           // dinv = 1 / d, 1 where d is 0; in place or not
-int pcg_dev_init(int n, bool warm, double lambda, const double *b, double *x, double *r, double *q, double *part, double *red, double *st,
-                 double tol, hipStream_t s);                                     // x, r; b.b, r.r, stop, done?
-int pcg_dev_start(int n, const double *r, const double *dinv, double *p, double *part, double *red, double *st, hipStream_t s);
-int pcg_dev_steps(int n, double lambda, double *x, double *r, double *p, double *q, const double *dinv, double *part, double *red,
-                  double *st, hipStream_t s);
-int pcg_dev_init_partial(int n, bool warm, double lambda, const double *b, double *x, double *r, double *q, double *part, double *red_out,
-                         hipStream_t s);                                         // red_out[0..2) = {b.b, r.r} of the slice
-int pcg_dev_start_partial(int n, const double *r, const double *dinv, double *p, double *part, double *red_out, const double *st,
-                          hipStream_t s);                                        // red_out[0] = r.z
-int pcg_dev_step_b(int n, double *x, double *r, const double *p, const double *q, const double *dinv, double *part, double *red_out,
-                   const double *st, hipStream_t s);                             // red_out[0..2) = {r.r, r.z}
-int pcg_dev_step_c(int n, double *p, const double *r, const double *dinv, const double *st, hipStream_t s);
-void pcg_info_of(const double *st_host, fs_pcg_info *info);                      // info may be NULL
 // ---- fs_pcgn's steps on row-major n x k panels; part: pcgn_part_doubles(k) doubles, cs: kPcgnStateDoubles, st as above
 constexpr int kPcgnStateDoubles = FS_PCGN_MAX_RHS * 16;
 constexpr size_t pcgn_part_doubles(int k) { return (size_t)1024 * 2 * (size_t)k; }

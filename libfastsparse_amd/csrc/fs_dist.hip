@@ -1444,65 +1444,124 @@ int fs_dist_swap_xy(fs_dist_matrix_t M)
   return FS_OK;
 }
 
-// behind iteration `iter`, rank by rank: steps(d) (what the caller still has to enqueue on rank d, in the same pass), then the
-// rank's flags on their way to the host and a look at those of iteration iter - 1.  Returns kRanksGoOn, kRanksStopped (every rank
-// saw the end), kRanksDisagree (only some did: identical arithmetic rules that out, a faulty device or exchange does not; the
-// error text is set in `who`'s name) or, < 0, the code of a call that failed
+// ---- the CG solvers on the row-sharded matrix: fs_dist_cg, fs_dist_pcg, fs_dist_pcgn, fs_dist_cg2 ---------------------------
+// Everything of a solve is resident and the scalars of the iteration live on the devices (fs_cg.hip's launchers); per iteration
+// y = A p and q = A' y.  EVERY rank decides convergence for itself and the host compares the flags of all of them one iteration
+// behind: a disagreement (which identical arithmetic rules out, and a faulty device or exchange does not) is an error return,
+// never a rank waiting in a collective for one that left.  Products run with fixed-order sums unless option "cg_fixed_order" is
+// 0.  Work vectors are kept on the handle between solves.  A solve CLOBBERS fs_dist_x / fs_dist_y / fs_dist_z of the handle and
+// writes the caller's x once, at the end: whatever fails before leaves it as it was.
+//
+// DistSolve is the host frame the four share, the counterpart of CgSolve in fs_cg.hip: open() (the transpose is there, both
+// locks, the caller's device kept, fixed-order products, one set of host-visible flags per rank), stage() (the caller's vectors
+// onto the ranks), iterate() and finish() (the agreed final state, then x to the caller).  A solver brings its argument checks,
+// its work space (st: every rank's st[]), its start and what an iteration enqueues.
 enum { kRanksGoOn = 0, kRanksStopped = 1, kRanksDisagree = 2 };
-static_assert(FS_ERR_HIP < 0 && FS_ERR_ARG < 0 && FS_ERR_RELEASED < 0, "error codes are negative: they share an int with kRanks*");
-static int ranks_after_iteration(fs_dist_t D, std::vector<fs::CgFlags> &fl, const std::vector<double *> &st, int iter, const char *who,
-                                 const std::function<int(int)> &steps)
-{
-  int stops = 0;
-  for (int d = 0; d < D->n; ++d) {
-    bool stop = false;
-    FS_HIP(hipSetDevice(D->dev[d]));
-    if (int rc = steps(d)) return rc;
-    if (int rc = fl[(size_t)d].after_iteration(iter, st[(size_t)d], D->stream[d], &stop)) return rc;
-    stops += stop ? 1 : 0;
-  }
-  if (stops == 0 || stops == D->n) return stops ? kRanksStopped : kRanksGoOn;
-  fs::set_error(std::string(who) + ": the devices disagree about convergence (a device or an exchange returned different bits)");
-  return kRanksDisagree;
-}
+struct DistSolve {
+  const char *who;
+  fs_dist_matrix_t M;
+  fs_dist_t D = M->D;
+  const int n = D->n, F = M->ncol;
+  std::unique_lock<std::mutex> matrix_lock{M->lock, std::defer_lock}, context_lock{D->lock, std::defer_lock};
+  DeviceGuard guard;
+  fs::FixedOrderScope fixed{fs::options().cg_fixed_order != 0};
+  std::vector<fs::CgFlags> fl = std::vector<fs::CgFlags>((size_t)n);
+  const std::vector<double *> *st = nullptr;
+  int staged = 0;
+  int seen = kRanksGoOn;                                   // what the ranks' flags said last: go on, all stopped, or only some did
+  int iterations = 0;                                      // after finish(): the agreed count, and rank 0's final st[]
+  double st0[fs::kCgStateDoubles];
 
-// every rank's final {done, iterations} must agree as well; then the final st[] of rank 0 for fs_debug_last_cg_state
-static int ranks_final_state(fs_dist_t D, const std::vector<double *> &st, const char *who, int *iterations, double *st0 = nullptr)
-{
-  double h[fs::kCgStateDoubles];
-  std::vector<double> fin(2 * (size_t)D->n, 0.0);
-  for (int d = 0; d < D->n; ++d) {
-    FS_HIP(hipSetDevice(D->dev[d]));
-    FS_HIP(hipMemcpy(&fin[2 * (size_t)d], st[(size_t)d] + fs::kCgStateDone, sizeof(double) * 2, hipMemcpyDeviceToHost));
-    if (fin[2 * (size_t)d] != fin[0] || fin[2 * (size_t)d + 1] != fin[1]) {
-      fs::set_error(std::string(who) + ": the devices finished in different states");
-      return FS_ERR_HIP;
+  int open(const char *no_transpose)
+  {
+    if (!M->t.built) { fs::set_error(std::string(who) + ": " + no_transpose); return FS_ERR_NO_TRANSPOSE; }
+    matrix_lock.lock();
+    context_lock.lock();
+    return each_rank(D, false, [&](int d) { return fl[(size_t)d].init(); });
+  }
+  // `count` doubles of the caller's (host memory or HBM) into own[r] on every rank: always a copy, they are read all solve long.
+  // A second and third vector of one call wait for the uploads of the one before, which still read the pinned staging buffer
+  int stage(const std::vector<double *> &own, const double *src, size_t count)
+  {
+    std::vector<double *> unused;
+    if (staged++)
+      if (int rc = dist_sync(D)) return rc;
+    return vec_in(M, own, src, count, unused, false);
+  }
+  // all ranks said the same (the answer is in `seen`), or only `stops` of them did
+  void agreed(int stops, const char *when)
+  {
+    seen = stops == 0 ? kRanksGoOn : stops == n ? kRanksStopped : kRanksDisagree;
+    if (seen == kRanksDisagree) fs::set_error(std::string(who) + ": the devices disagree about convergence" + when);
+  }
+  // a solve that may be done before its first iteration (b = 0, a warm start from a converged x): one synchronous look at every
+  // rank's flag
+  int look()
+  {
+    if (int rc = dist_sync(D)) return rc;
+    int stops = 0;
+    if (int rc = each_rank(D, false, [&](int d) -> int {
+          double done = 0.0;
+          FS_HIP(hipMemcpy(&done, (*st)[(size_t)d] + fs::kCgStateDone, sizeof(double), hipMemcpyDeviceToHost));
+          stops += done != 0.0 ? 1 : 0;
+          return FS_OK;
+        })) return rc;
+    agreed(stops, " at the start");
+    return FS_OK;
+  }
+  // up to cap iterations, as long as the ranks go on: products() (whatever spans the ranks), then rank by rank in one pass
+  // steps(d), the rank's flags on their way to the host and a look at those of the iteration before.  look_first: see look()
+  int iterate(int cap, bool look_first, const std::function<int()> &products, const std::function<int(int)> &steps)
+  {
+    if (look_first)
+      if (int rc = look()) return rc;
+    for (int iter = 0; seen == kRanksGoOn && iter < cap; iter++) {
+      if (int rc = products()) return rc;
+      int stops = 0;
+      if (int rc = each_rank(D, false, [&](int d) -> int {
+            bool stop = false;
+            if (int rc2 = steps(d)) return rc2;
+            if (int rc2 = fl[(size_t)d].after_iteration(iter, (*st)[(size_t)d], D->stream[d], &stop)) return rc2;
+            stops += stop ? 1 : 0;
+            return FS_OK;
+          })) return rc;
+      agreed(stops, " (a device or an exchange returned different bits)");
     }
+    return FS_OK;
   }
-  FS_HIP(hipSetDevice(D->dev[0]));
-  FS_HIP(hipMemcpy(h, st[0], sizeof(h), hipMemcpyDeviceToHost));
-  fs::note_cg_state(h);
-  for (int i = 0; st0 && i < fs::kCgStateDoubles; ++i) st0[i] = h[i];
-  *iterations = (int)fin[1];
-  return FS_OK;
-}
-
-// a solve that may be done before its first iteration (fs_dist_pcg / fs_dist_pcgn: b = 0, a warm start from a converged x): one
-// synchronous look at every rank's flag.  kRanksStopped, kRanksGoOn, kRanksDisagree, or < 0
-static int ranks_done_at_start(fs_dist_t D, const std::vector<double *> &st, const char *who)
-{
-  if (int rc = dist_sync(D)) return rc;
-  int stops = 0;
-  for (int d = 0; d < D->n; ++d) {
-    double done = 0.0;
-    FS_HIP(hipSetDevice(D->dev[d]));
-    FS_HIP(hipMemcpy(&done, st[(size_t)d] + fs::kCgStateDone, sizeof(double), hipMemcpyDeviceToHost));
-    stops += done != 0.0 ? 1 : 0;
+  // every rank's final {done, iterations} must agree as well; rank 0's final st[] is kept for fs_debug_last_cg_state.  Then x:
+  // count doubles from rank 0's sol, or (slices) every rank's rows of A' from its own
+  int finish(double *x, const std::vector<double *> &sol, size_t count, bool slices = false)
+  {
+    if (int rc = dist_sync(D)) return rc;
+    if (seen == kRanksDisagree) return FS_ERR_HIP;
+    double fin0[2] = {0.0, 0.0};
+    if (int rc = each_rank(D, false, [&](int d) -> int {
+          double fin[2];
+          FS_HIP(hipMemcpy(fin, (*st)[(size_t)d] + fs::kCgStateDone, sizeof(fin), hipMemcpyDeviceToHost));
+          if (d == 0) { fin0[0] = fin[0]; fin0[1] = fin[1]; }
+          if (fin[0] != fin0[0] || fin[1] != fin0[1]) {
+            fs::set_error(std::string(who) + ": the devices finished in different states");
+            return FS_ERR_HIP;
+          }
+          return FS_OK;
+        })) return rc;
+    FS_HIP(hipSetDevice(D->dev[0]));
+    FS_HIP(hipMemcpy(st0, (*st)[0], sizeof(st0), hipMemcpyDeviceToHost));
+    fs::note_cg_state(st0);
+    iterations = (int)fin0[1];
+    if (vector_device(x) >= 0)
+      if (int rc = wait_for_caller(vector_device(x))) return rc;
+    if (!slices)
+      if (int rc = vec_store(M, 0, x, sol[0], count)) return rc;
+    for (int d = 0; slices && d < n; ++d) {
+      const int lo = M->t.bounds[(size_t)d], rows = M->t.bounds[(size_t)d + 1] - lo;
+      if (rows > 0)
+        if (int rc = vec_store(M, d, x + lo, sol[(size_t)d], (size_t)rows)) return rc;
+    }
+    return dist_sync(D);
   }
-  if (stops == 0 || stops == D->n) return stops ? kRanksStopped : kRanksGoOn;
-  fs::set_error(std::string(who) + ": the devices disagree about convergence at the start");
-  return kRanksDisagree;
-}
+};
 
 // fs_dist_cg's and fs_dist_pcg's vectors on the handle: whole vectors (scheme "replicate") or slices (scheme "gather") of F doubles
 // with room for a slice to be sent as a window of max_rows doubles
@@ -1533,6 +1592,12 @@ struct SliceSums {
   fs_dist_matrix_t M;
   int slot = 0;
   double *send(int d) const { return M->cg.red[(size_t)d] + kCgSendDoubles * slot; }
+  // where rank d's launchers leave their sums: scheme "gather" in the send slot, scheme "replicate" (whole vectors) finished
+  fs::CgSums of(int d, bool gather) const
+  {
+    const CgWork &W = M->cg;
+    return fs::CgSums{W.part[(size_t)d], W.red[(size_t)d], W.st[(size_t)d], gather ? send(d) : nullptr};
+  }
   int combine(fs::CgStep step, double arg, int nv)
   {
     fs_dist_t D = M->D;
@@ -1541,25 +1606,63 @@ struct SliceSums {
     DistSide &T = M->t;
     std::vector<const double *> from((size_t)n);
     std::vector<hipEvent_t> ready((size_t)n);
-    for (int d = 0; d < n; ++d) {
-      FS_HIP(hipSetDevice(D->dev[d]));
-      from[(size_t)d] = send(d);
-      FS_HIP(hipEventRecord(T.ev[(size_t)d][0], D->stream[d]));
-      ready[(size_t)d] = T.ev[(size_t)d][0];
-    }
+    if (int rc = each_rank(D, false, [&](int d) -> int {
+          from[(size_t)d] = send(d);
+          FS_HIP(hipEventRecord(T.ev[(size_t)d][0], D->stream[d]));
+          ready[(size_t)d] = T.ev[(size_t)d][0];
+          return FS_OK;
+        })) return rc;
     if (int rc = exchange_equal(D, from, W.redall, (size_t)nv, D->stream, ready)) return rc;
-    for (int d = 0; d < n; ++d) {
-      FS_HIP(hipSetDevice(D->dev[d]));
-      if (int rc = fs::cg_dev_final(step, W.redall[(size_t)d], n, W.red[(size_t)d] + 2 * kCgSendDoubles, W.st[(size_t)d], arg, D->stream[d], nv)) return rc;
-    }
+    if (int rc = each_rank(D, false, [&](int d) {
+          return fs::cg_dev_final(step, W.redall[(size_t)d], n, W.red[(size_t)d] + 2 * kCgSendDoubles, W.st[(size_t)d], arg, D->stream[d], nv);
+        })) return rc;
     slot ^= 1;
     return FS_OK;
   }
 };
 
-// (A'A + lambda I) x = b on the row-sharded matrix: bsbm_cg (cg.h:25-82) across the GPUs, everything resident, the scalars of
-// the iteration on the devices (fs_cg.hip).  Per iteration y = A p and q = A' y; two schemes for everything else (option
-// "dist_cg_scheme"):
+// the iterations of fs_dist_cg and fs_dist_pcg, which differ in the preconditioner (`pre`: rank d's is cg.dinv[d]) and in the
+// convergence step `beta`.  Scheme "replicate": both products carry their all-gather, every rank runs the whole-vector steps.
+// Scheme "gather": q_r = A'_r y is the rank's own rows of A', no exchange; the slice steps with their sums combined over the
+// ranks; the new p slice all-gathered for the next product
+static int cg_iterations(DistSolve &f, SliceSums &sums, bool gather, int cap, double lambda, bool pre, fs::CgStep beta)
+{
+  fs_dist_matrix_t M = f.M;
+  fs_dist_t D = f.D;
+  DistSide &T = M->t;
+  CgWork &W = M->cg;
+  auto dinv_of = [&](int d) -> const double * { return pre ? W.dinv[(size_t)d] : nullptr; };
+  auto rows_of = [&T](int d) { return T.bounds[(size_t)d + 1] - T.bounds[(size_t)d]; };
+  if (!gather)
+    return f.iterate(cap, false, [&]() -> int {
+      if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;       // y = A p
+      return dist_product(M, true, 1, M->y, M->z);                         // q = A' y
+    }, [&](int d) {
+      return fs::cg_dev_steps(f.F, lambda, W.sol[(size_t)d], W.r[(size_t)d], M->x[(size_t)d], M->z[(size_t)d], dinv_of(d), sums.of(d, false),
+                              beta, D->stream[d]);
+    });
+  return f.iterate(cap, false, [&]() -> int {
+    if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;         // y = A p
+    if (int rc = each_rank(D, false, [&](int d) -> int {
+          if (rows_of(d) > 0)
+            if (int rc2 = fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], M->y[(size_t)d], D->stream[d])) return rc2;
+          return fs::cg_dev_shift_dot(rows_of(d), lambda, W.p[(size_t)d], W.q[(size_t)d], sums.of(d, true), D->stream[d]);
+        })) return rc;
+    if (int rc = sums.combine(fs::kStepCgAlpha, 0.0, 1)) return rc;        // alpha
+    if (int rc = each_rank(D, false, [&](int d) {
+          return fs::cg_dev_update(rows_of(d), W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.q[(size_t)d], dinv_of(d), sums.of(d, true),
+                                   beta, D->stream[d]);
+        })) return rc;
+    if (int rc = sums.combine(beta, 0.0, pre ? 2 : 1)) return rc;          // converged?  beta
+    if (int rc = each_rank(D, false, [&](int d) {
+          return fs::cg_dev_direction(rows_of(d), W.p[(size_t)d], W.r[(size_t)d], dinv_of(d), W.st[(size_t)d], D->stream[d]);
+        })) return rc;
+    return run_gather(D, exchange_of(M, true, 1), W.p, M->x, false);       // the new p on every rank
+  }, [](int) { return FS_OK; });
+}
+
+// (A'A + lambda I) x = b on the row-sharded matrix: bsbm_cg (cg.h:25-82) across the GPUs.  Two schemes for everything but
+// y = A p (option "dist_cg_scheme"):
 //   0 "replicate"  every device keeps the WHOLE x, r, p, q and runs the same fused vector kernels on them -- identical inputs,
 //                  identical kernels, identical vectors: the dots need no exchange.  Both products carry their all-gather.
 //                  The O(F) vector work is done N times over.
@@ -1568,130 +1671,36 @@ struct SliceSums {
 //                  rank) and every rank adds the N values in rank order, so all ranks hold identical scalars; the new p slice is
 //                  all-gathered (whole-shard exchange) for the next product.  The vector work is divided by N; two tiny
 //                  exchanges per iteration are added.
-// Either way EVERY device decides convergence for itself and the host compares the flags of all of them one iteration behind:
-// a disagreement (which identical arithmetic rules out, and a faulty device or exchange does not) is an error return, never a
-// rank waiting in a collective for one that left.  Products run with fixed-order sums unless option "cg_fixed_order" is 0.
-// Work vectors are kept on the handle between solves.  CLOBBERS fs_dist_x / fs_dist_y / fs_dist_z of the handle.
 int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double lambda, double tol, int *out_iter)
 {
   if (!M || !x_host || !b_host) { fs::set_error("fs_dist_cg: NULL argument"); return FS_ERR_ARG; }
-  if (!M->t.built) { fs::set_error("fs_dist_cg: call fs_dist_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
-  std::lock_guard<std::mutex> g(M->lock);
-  std::lock_guard<std::mutex> gd(M->D->lock);
-  DeviceGuard guard;
-  fs::FixedOrderScope fixed(fs::options().cg_fixed_order != 0);
-  fs_dist_t D = M->D;
-  const int n = D->n, F = M->ncol;
-  const bool gather = fs::options().dist_cg_scheme == 1 && n > 1;
+  DistSolve f{"fs_dist_cg", M};
+  if (int rc = f.open("call fs_dist_matrix_build_transpose first")) return rc;
+  fs_dist_t D = f.D;
+  const int F = f.F;
+  const bool gather = fs::options().dist_cg_scheme == 1 && f.n > 1;
   DistSide &T = M->t;
   CgWork &W = M->cg;
   if (int rc = ensure_cg_work(M)) return rc;
-  {
-    std::vector<double *> unused;
-    if (int rc = vec_in(M, W.b, b_host, (size_t)F, unused, false)) return rc;    // (host memory or HBM; always a copy: b is read all solve long)
-  }
-  // one set of host-visible flags per device
-  std::vector<fs::CgFlags> fl((size_t)n);
-  for (int d = 0; d < n; ++d) {
-    FS_HIP(hipSetDevice(D->dev[d]));
-    if (int rc = fl[(size_t)d].init()) return rc;
-  }
+  f.st = &W.st;
+  if (int rc = f.stage(W.b, b_host, (size_t)F)) return rc;
   SliceSums sums{M};
-  auto combine = [&](fs::CgStep step, double arg) { return sums.combine(step, arg, 1); };
-  if (!gather) {
-    for (int d = 0; d < n; ++d) {
-      FS_HIP(hipSetDevice(D->dev[d]));
-      if (int rc = fs::cg_dev_init(F, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], M->x[(size_t)d], W.part[(size_t)d], W.red[(size_t)d],
-                                   W.st[(size_t)d], tol, D->stream[d])) return rc;
-    }
-  } else {
-    for (int d = 0; d < n; ++d) {
-      const int lo = T.bounds[(size_t)d], nl = T.bounds[(size_t)d + 1] - lo;
-      FS_HIP(hipSetDevice(D->dev[d]));
-      if (int rc = fs::cg_dev_init_partial(nl, W.b[(size_t)d] + lo, W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.part[(size_t)d], sums.send(d),
-                                           D->stream[d])) return rc;
-    }
-    if (int rc = combine(fs::kStepCgStart, tol)) return rc;
+  if (int rc = each_rank(D, false, [&](int d) {                          // cg_init_kernel writes p itself: whole into x, or the slice
+        const int lo = gather ? T.bounds[(size_t)d] : 0, rows = gather ? T.bounds[(size_t)d + 1] - lo : F;
+        return fs::cg_dev_init(rows, W.b[(size_t)d] + lo, W.sol[(size_t)d], W.r[(size_t)d], (gather ? W.p : M->x)[(size_t)d], sums.of(d, gather),
+                               tol, D->stream[d]);
+      })) return rc;
+  if (gather) {
+    if (int rc = sums.combine(fs::kStepCgStart, tol, 1)) return rc;
     if (int rc = run_gather(D, exchange_of(M, true, 1), W.p, M->x, false)) return rc;     // the whole p on every rank
   }
-  int seen = kRanksGoOn;
-  for (int iter = 0; iter < F; iter++) {
-    if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;       // y = A p, its all-gather inside
-    if (!gather) {
-      if (int rc = dist_product(M, true, 1, M->y, M->z)) return rc;      // q = A' y, its all-gather inside
-      for (int d = 0; d < n; ++d) {
-        FS_HIP(hipSetDevice(D->dev[d]));
-        if (int rc = fs::cg_dev_steps(F, lambda, W.sol[(size_t)d], W.r[(size_t)d], M->x[(size_t)d], M->z[(size_t)d], W.part[(size_t)d],
-                                      W.red[(size_t)d], W.st[(size_t)d], D->stream[d])) return rc;
-      }
-    } else {
-      for (int d = 0; d < n; ++d) {                                      // q_r = A'_r y: this rank's rows of A', no exchange
-        const int nl = T.bounds[(size_t)d + 1] - T.bounds[(size_t)d];
-        FS_HIP(hipSetDevice(D->dev[d]));
-        if (nl > 0)
-          if (int rc = fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], M->y[(size_t)d], D->stream[d])) return rc;
-        if (int rc = fs::cg_dev_step_a(nl, lambda, W.p[(size_t)d], W.q[(size_t)d], W.part[(size_t)d], sums.send(d), W.st[(size_t)d], D->stream[d])) return rc;
-      }
-      if (int rc = combine(fs::kStepCgAlpha, 0.0)) return rc;             // alpha
-      for (int d = 0; d < n; ++d) {
-        const int nl = T.bounds[(size_t)d + 1] - T.bounds[(size_t)d];
-        FS_HIP(hipSetDevice(D->dev[d]));
-        if (int rc = fs::cg_dev_step_b(nl, W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.q[(size_t)d], W.part[(size_t)d], sums.send(d),
-                                       W.st[(size_t)d], D->stream[d])) return rc;
-      }
-      if (int rc = combine(fs::kStepCgBeta, 0.0)) return rc;              // converged?  beta
-      for (int d = 0; d < n; ++d) {
-        const int nl = T.bounds[(size_t)d + 1] - T.bounds[(size_t)d];
-        FS_HIP(hipSetDevice(D->dev[d]));
-        if (int rc = fs::cg_dev_step_c(nl, W.p[(size_t)d], W.r[(size_t)d], W.st[(size_t)d], D->stream[d])) return rc;
-      }
-      if (int rc = run_gather(D, exchange_of(M, true, 1), W.p, M->x, false)) return rc;   // the new p on every rank
-    }
-    seen = ranks_after_iteration(D, fl, W.st, iter, "fs_dist_cg", [](int) { return FS_OK; });
-    if (seen < 0) return seen;
-    if (seen != kRanksGoOn) break;
-  }
-  if (int rc = dist_sync(D)) return rc;
-  if (seen == kRanksDisagree) return FS_ERR_HIP;
-  int iterations = 0;
-  if (int rc = ranks_final_state(D, W.st, "fs_dist_cg", &iterations)) return rc;
-  if (vector_device(x_host) >= 0)
-    if (int rc = wait_for_caller(vector_device(x_host))) return rc;
-  if (!gather) {
-    if (int rc = vec_store(M, 0, x_host, W.sol[0], (size_t)F)) return rc;
-  } else {
-    for (int d = 0; d < n; ++d) {
-      const int lo = T.bounds[(size_t)d], nl = T.bounds[(size_t)d + 1] - lo;
-      if (nl > 0)
-        if (int rc = vec_store(M, d, x_host + lo, W.sol[(size_t)d], (size_t)nl)) return rc;
-    }
-  }
-  if (int rc = dist_sync(D)) return rc;
-  if (out_iter) *out_iter = iterations;
+  if (int rc = cg_iterations(f, sums, gather, F, lambda, false, fs::kStepCgBeta)) return rc;
+  if (int rc = f.finish(x_host, W.sol, (size_t)F, gather)) return rc;
+  if (out_iter) *out_iter = f.iterations;
   return FS_OK;
 }
 
 // ---- the preconditioned solvers on the row-sharded matrix: fs_gram_diag, fs_pcg, fs_pcgn across the ranks ------------------
-// what fs_pcg / fs_pcgn refuse, in their order, in `who`'s name -- before a lock is taken or anything is copied
-static int pcg_params_ok(const char *who, const fs_pcg_params *prm)
-{
-  const std::string w(who);
-  if (prm->precond != FS_PRECOND_NONE && prm->precond != FS_PRECOND_JACOBI && prm->precond != FS_PRECOND_DIAG) {
-    fs::set_error(w + ": precond is none of FS_PRECOND_NONE / _JACOBI / _DIAG"); return FS_ERR_ARG;
-  }
-  if (prm->precond == FS_PRECOND_DIAG && !prm->diag) { fs::set_error(w + ": FS_PRECOND_DIAG without a diagonal"); return FS_ERR_ARG; }
-  if (!(prm->tol >= 0.0)) { fs::set_error(w + ": tol is negative or NaN"); return FS_ERR_ARG; }
-  return FS_OK;
-}
-
-// a second and third input vector of one call: the uploads of the one before still read the pinned staging buffer (upload_all)
-static int next_vec_in(fs_dist_matrix_t M, const std::vector<double *> &own, const double *src, size_t count)
-{
-  std::vector<double *> unused;
-  if (int rc = dist_sync(M->D)) return rc;
-  return vec_in(M, own, src, count, unused, false);
-}
-
 // Jacobi reads the plain CSR of every rank's shard of A': FS_ERR_RELEASED before anything else happens
 static int gram_diag_ready(fs_dist_matrix_t M, const char *who)
 {
@@ -1705,14 +1714,11 @@ static int gram_diag_ready(fs_dist_matrix_t M, const char *who)
 // rank r: gram_diag_kernel over the rows of A' it owns, into dst[r] (slice-local)
 static int gram_diag_slices(fs_dist_matrix_t M, double lambda, const std::vector<double *> &dst)
 {
-  fs_dist_t D = M->D;
   DistSide &T = M->t;
-  for (int r = 0; r < D->n; ++r) {
-    if (T.bounds[(size_t)r + 1] == T.bounds[(size_t)r]) continue;
-    FS_HIP(hipSetDevice(D->dev[r]));
-    if (int rc = fs_gram_diag(T.shard[(size_t)r], lambda, dst[(size_t)r], D->stream[r])) return rc;
-  }
-  return FS_OK;
+  return each_rank(M->D, false, [&](int r) -> int {
+    if (T.bounds[(size_t)r + 1] == T.bounds[(size_t)r]) return FS_OK;
+    return fs_gram_diag(T.shard[(size_t)r], lambda, dst[(size_t)r], M->D->stream[r]);
+  });
 }
 
 // the whole d on every rank, in out[r]: the slices into the side's local buffers, then one whole-shard gather
@@ -1742,181 +1748,99 @@ int fs_dist_gram_diag(fs_dist_matrix_t M, double lambda, double *d)
   return dist_sync(M->D);
 }
 
-// fs_pcg across the ranks; the schemes are fs_dist_cg's (option "dist_cg_scheme"):
-//   0 "replicate"  every rank holds whole x, r, p, q, dinv and launches fs_pcg's own kernels on them (pcg_dev_*): no exchange for
-//                  the sums.  Jacobi costs one gather of d per solve, a warm start one pair of sharded products on x0.
+// fs_pcg across the ranks; the schemes are fs_dist_cg's (option "dist_cg_scheme"), and so are the iterations (cg_iterations):
+//   0 "replicate"  every rank holds whole x, r, p, q, dinv and launches fs_pcg's own kernels on them: no exchange for the sums.
+//                  Jacobi costs one gather of d per solve, a warm start one pair of sharded products on x0.
 //   1 "gather"     rank r keeps its slice -- the rows of A' it owns -- of x, r, p, q, dinv.  Jacobi's slice of d is the rank's own
 //                  gram_diag launch: no exchange.  Every sum is the slice tree of fs_dist_cg (SliceSums); the sums fs_pcg takes in one
 //                  pass travel together: {b.b, r.r} at the start, {r.r, r.z} behind the update with a preconditioner.
-// The caller's x is written once, at the end: whatever fails before leaves it as it was.
 int fs_dist_pcg(fs_dist_matrix_t M, double *x, const double *b, double lambda, const fs_pcg_params *prm, fs_pcg_info *info)
 {
-  const char *who = "fs_dist_pcg";
   if (!M || !x || !b || !prm) { fs::set_error("fs_dist_pcg: NULL argument"); return FS_ERR_ARG; }
-  if (int rc = pcg_params_ok(who, prm)) return rc;
-  if (!M->t.built) { fs::set_error("fs_dist_pcg: call fs_dist_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
-  std::lock_guard<std::mutex> g(M->lock);
-  std::lock_guard<std::mutex> gd(M->D->lock);
-  DeviceGuard guard;
+  if (int rc = fs::pcg_params_ok("fs_dist_pcg", prm)) return rc;
+  DistSolve f{"fs_dist_pcg", M};
+  if (int rc = f.open("call fs_dist_matrix_build_transpose first")) return rc;
   if (prm->precond == FS_PRECOND_JACOBI)
     if (int rc = gram_diag_ready(M, "fs_dist_pcg with FS_PRECOND_JACOBI (fs_gram_diag)")) return rc;
-  fs::FixedOrderScope fixed(fs::options().cg_fixed_order != 0);
-  fs_dist_t D = M->D;
-  const int n = D->n, F = M->ncol;
-  const bool gather = fs::options().dist_cg_scheme == 1 && n > 1;
+  fs_dist_t D = f.D;
+  const int F = f.F;
+  const bool gather = fs::options().dist_cg_scheme == 1 && f.n > 1;
   const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
   const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
   DistSide &T = M->t;
   CgWork &W = M->cg;
   if (int rc = ensure_cg_work(M)) return rc;
-  // d is staged in the vector that holds q later: the handle's z (whole) or the rank's slice buffer
-  const std::vector<double *> &stage = gather ? W.q : M->z;
-  auto lo_of = [&T](int d) { return T.bounds[(size_t)d]; };
-  auto rows_of = [&T](int d) { return T.bounds[(size_t)d + 1] - T.bounds[(size_t)d]; };
-  {
-    std::vector<double *> unused;
-    if (int rc = vec_in(M, W.b, b, (size_t)F, unused, false)) return rc;          // (always a copy: b is read all solve long)
-    if (warm)                                                                    // x0, whole, on every rank
-      if (int rc = next_vec_in(M, gather ? M->x : W.sol, x, (size_t)F)) return rc;
-    if (prm->precond == FS_PRECOND_DIAG)
-      if (int rc = next_vec_in(M, stage, prm->diag, (size_t)F)) return rc;
-  }
-  std::vector<fs::CgFlags> fl((size_t)n);
-  for (int d = 0; d < n; ++d) {
-    FS_HIP(hipSetDevice(D->dev[d]));
-    if (int rc = fl[(size_t)d].init()) return rc;
-  }
-  SliceSums sums{M};
+  f.st = &W.st;
+  // a rank works on whole vectors or on its slice; q and p are the handle's z and x (whole) or the rank's slice buffers, and d is
+  // staged in the vector that holds q later
+  const std::vector<double *> &vq = gather ? W.q : M->z, &vp = gather ? W.p : M->x;
+  auto lo_of = [&](int d) { return gather ? T.bounds[(size_t)d] : 0; };
+  auto rows_of = [&](int d) { return gather ? T.bounds[(size_t)d + 1] - T.bounds[(size_t)d] : F; };
   auto dinv_of = [&](int d) -> const double * { return pre ? W.dinv[(size_t)d] : nullptr; };
-  if (!gather) {
-    if (prm->precond == FS_PRECOND_JACOBI)
-      if (int rc = gram_diag_everywhere(M, lambda, stage)) return rc;
-    for (int d = 0; d < n && pre; ++d) {
-      FS_HIP(hipSetDevice(D->dev[d]));
-      if (int rc = fs::pcg_dev_dinv(F, stage[(size_t)d], W.dinv[(size_t)d], D->stream[d])) return rc;
-    }
-    if (warm) {                                                                  // q = A'(A x0)
-      if (int rc = dist_product(M, false, 1, W.sol, M->y)) return rc;
-      if (int rc = dist_product(M, true, 1, M->y, M->z)) return rc;
-    }
-    for (int d = 0; d < n; ++d) {
-      FS_HIP(hipSetDevice(D->dev[d]));
-      if (int rc = fs::pcg_dev_init(F, warm, lambda, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], M->z[(size_t)d], W.part[(size_t)d],
-                                    W.red[(size_t)d], W.st[(size_t)d], prm->tol, D->stream[d])) return rc;
-      if (int rc = fs::pcg_dev_start(F, W.r[(size_t)d], dinv_of(d), M->x[(size_t)d], W.part[(size_t)d], W.red[(size_t)d], W.st[(size_t)d],
-                                     D->stream[d])) return rc;
-    }
-  } else {
-    if (prm->precond == FS_PRECOND_JACOBI)
-      if (int rc = gram_diag_slices(M, lambda, stage)) return rc;
-    for (int d = 0; d < n && pre; ++d) {
-      FS_HIP(hipSetDevice(D->dev[d]));
-      const double *dd = stage[(size_t)d] + (prm->precond == FS_PRECOND_DIAG ? lo_of(d) : 0);
-      if (int rc = fs::pcg_dev_dinv(rows_of(d), dd, W.dinv[(size_t)d], D->stream[d])) return rc;
-    }
-    if (warm) {                                                                  // the rank's slice of x0; q_r = A'_r (A x0)
-      for (int d = 0; d < n; ++d) {
-        FS_HIP(hipSetDevice(D->dev[d]));
-        if (rows_of(d) > 0)
-          FS_HIP(hipMemcpyAsync(W.sol[(size_t)d], M->x[(size_t)d] + lo_of(d), sizeof(double) * (size_t)rows_of(d), hipMemcpyDeviceToDevice, D->stream[d]));
-      }
-      if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;
-      for (int d = 0; d < n; ++d) {
-        FS_HIP(hipSetDevice(D->dev[d]));
-        if (rows_of(d) > 0)
-          if (int rc = fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], M->y[(size_t)d], D->stream[d])) return rc;
-      }
-    }
-    for (int d = 0; d < n; ++d) {
-      FS_HIP(hipSetDevice(D->dev[d]));
-      if (int rc = fs::pcg_dev_init_partial(rows_of(d), warm, lambda, W.b[(size_t)d] + lo_of(d), W.sol[(size_t)d], W.r[(size_t)d], W.q[(size_t)d],
-                                            W.part[(size_t)d], sums.send(d), D->stream[d])) return rc;
-    }
-    if (int rc = sums.combine(fs::kStepPcgStart, prm->tol, 2)) return rc;         // b.b, r.r, stop, done?
-    for (int d = 0; d < n; ++d) {
-      FS_HIP(hipSetDevice(D->dev[d]));
-      if (int rc = fs::pcg_dev_start_partial(rows_of(d), W.r[(size_t)d], dinv_of(d), W.p[(size_t)d], W.part[(size_t)d], sums.send(d),
-                                             W.st[(size_t)d], D->stream[d])) return rc;
-    }
-    if (int rc = sums.combine(fs::kStepPcgRz, 0.0, 1)) return rc;                 // r.z
+  if (int rc = f.stage(W.b, b, (size_t)F)) return rc;
+  if (warm)                                                                      // x0, whole, on every rank
+    if (int rc = f.stage(gather ? M->x : W.sol, x, (size_t)F)) return rc;
+  if (prm->precond == FS_PRECOND_DIAG)
+    if (int rc = f.stage(vq, prm->diag, (size_t)F)) return rc;
+  SliceSums sums{M};
+  if (prm->precond == FS_PRECOND_JACOBI)                                         // whole: one gather of d; else the rank's own rows
+    if (int rc = gather ? gram_diag_slices(M, lambda, vq) : gram_diag_everywhere(M, lambda, vq)) return rc;
+  if (pre)
+    if (int rc = each_rank(D, false, [&](int d) {                               // (a staged d is whole, Jacobi's is the slice)
+          const double *dd = vq[(size_t)d] + (prm->precond == FS_PRECOND_DIAG ? lo_of(d) : 0);
+          return fs::pcg_dev_dinv(rows_of(d), dd, W.dinv[(size_t)d], D->stream[d]);
+        })) return rc;
+  if (warm && !gather) {                                                         // q = A'(A x0)
+    if (int rc = dist_product(M, false, 1, W.sol, M->y)) return rc;
+    if (int rc = dist_product(M, true, 1, M->y, M->z)) return rc;
   }
-  int seen = ranks_done_at_start(D, W.st, who);              // done before the first iteration: no product is enqueued
-  if (seen < 0) return seen;
-  if (seen == kRanksGoOn && gather)
+  if (warm && gather) {                                                          // the rank's slice of x0; q_r = A'_r (A x0)
+    if (int rc = each_rank(D, false, [&](int d) -> int {
+          if (rows_of(d) > 0)
+            FS_HIP(hipMemcpyAsync(W.sol[(size_t)d], M->x[(size_t)d] + lo_of(d), sizeof(double) * (size_t)rows_of(d), hipMemcpyDeviceToDevice, D->stream[d]));
+          return FS_OK;
+        })) return rc;
+    if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;
+    if (int rc = each_rank(D, false, [&](int d) -> int {
+          return rows_of(d) > 0 ? fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], M->y[(size_t)d], D->stream[d]) : FS_OK;
+        })) return rc;
+  }
+  // b.b, r.r, stop, done?  then p = z, r.z.  Whole vectors: a rank's two steps in one pass; slices: each with its sums combined
+  if (int rc = each_rank(D, false, [&](int d) -> int {
+        if (int rc2 = fs::pcg_dev_init(rows_of(d), warm, lambda, W.b[(size_t)d] + lo_of(d), W.sol[(size_t)d], W.r[(size_t)d], vq[(size_t)d],
+                                       sums.of(d, gather), prm->tol, D->stream[d])) return rc2;
+        return gather ? FS_OK : fs::pcg_dev_start(F, W.r[(size_t)d], dinv_of(d), vp[(size_t)d], sums.of(d, false), D->stream[d]);
+      })) return rc;
+  if (gather) {
+    if (int rc = sums.combine(fs::kStepPcgStart, prm->tol, 2)) return rc;
+    if (int rc = each_rank(D, false, [&](int d) {
+          return fs::pcg_dev_start(rows_of(d), W.r[(size_t)d], dinv_of(d), vp[(size_t)d], sums.of(d, true), D->stream[d]);
+        })) return rc;
+    if (int rc = sums.combine(fs::kStepPcgRz, 0.0, 1)) return rc;
+  }
+  if (int rc = f.look()) return rc;                          // done before the first iteration: no product is enqueued
+  if (gather && f.seen == kRanksGoOn)
     if (int rc = run_gather(D, exchange_of(M, true, 1), W.p, M->x, false)) return rc;     // the whole p on every rank
-  for (int iter = 0; seen == kRanksGoOn && iter < cap; iter++) {
-    if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;       // y = A p, its all-gather inside
-    if (!gather) {
-      if (int rc = dist_product(M, true, 1, M->y, M->z)) return rc;      // q = A' y, its all-gather inside
-      for (int d = 0; d < n; ++d) {
-        FS_HIP(hipSetDevice(D->dev[d]));
-        if (int rc = fs::pcg_dev_steps(F, lambda, W.sol[(size_t)d], W.r[(size_t)d], M->x[(size_t)d], M->z[(size_t)d], dinv_of(d),
-                                       W.part[(size_t)d], W.red[(size_t)d], W.st[(size_t)d], D->stream[d])) return rc;
-      }
-    } else {
-      for (int d = 0; d < n; ++d) {                                      // q_r = A'_r y: this rank's rows of A', no exchange
-        FS_HIP(hipSetDevice(D->dev[d]));
-        if (rows_of(d) > 0)
-          if (int rc = fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], M->y[(size_t)d], D->stream[d])) return rc;
-        if (int rc = fs::cg_dev_step_a(rows_of(d), lambda, W.p[(size_t)d], W.q[(size_t)d], W.part[(size_t)d], sums.send(d), W.st[(size_t)d],
-                                       D->stream[d])) return rc;
-      }
-      if (int rc = sums.combine(fs::kStepCgAlpha, 0.0, 1)) return rc;     // alpha = r.z / p.q
-      for (int d = 0; d < n; ++d) {
-        FS_HIP(hipSetDevice(D->dev[d]));
-        if (int rc = pre ? fs::pcg_dev_step_b(rows_of(d), W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.q[(size_t)d], W.dinv[(size_t)d],
-                                              W.part[(size_t)d], sums.send(d), W.st[(size_t)d], D->stream[d])
-                         : fs::cg_dev_step_b(rows_of(d), W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.q[(size_t)d], W.part[(size_t)d],
-                                             sums.send(d), W.st[(size_t)d], D->stream[d])) return rc;
-      }
-      if (int rc = sums.combine(fs::kStepPcgBeta, 0.0, pre ? 2 : 1)) return rc;   // r.r kept; converged?  beta
-      for (int d = 0; d < n; ++d) {
-        FS_HIP(hipSetDevice(D->dev[d]));
-        if (int rc = pre ? fs::pcg_dev_step_c(rows_of(d), W.p[(size_t)d], W.r[(size_t)d], W.dinv[(size_t)d], W.st[(size_t)d], D->stream[d])
-                         : fs::cg_dev_step_c(rows_of(d), W.p[(size_t)d], W.r[(size_t)d], W.st[(size_t)d], D->stream[d])) return rc;
-      }
-      if (int rc = run_gather(D, exchange_of(M, true, 1), W.p, M->x, false)) return rc;   // the new p on every rank
-    }
-    seen = ranks_after_iteration(D, fl, W.st, iter, who, [](int) { return FS_OK; });
-    if (seen < 0) return seen;
-  }
-  if (int rc = dist_sync(D)) return rc;
-  if (seen == kRanksDisagree) return FS_ERR_HIP;
-  int iterations = 0;
-  double st0[fs::kCgStateDoubles];
-  if (int rc = ranks_final_state(D, W.st, who, &iterations, st0)) return rc;
-  if (vector_device(x) >= 0)
-    if (int rc = wait_for_caller(vector_device(x))) return rc;
-  if (!gather) {
-    if (int rc = vec_store(M, 0, x, W.sol[0], (size_t)F)) return rc;
-  } else {
-    for (int d = 0; d < n; ++d)
-      if (rows_of(d) > 0)
-        if (int rc = vec_store(M, d, x + lo_of(d), W.sol[(size_t)d], (size_t)rows_of(d))) return rc;
-  }
-  if (int rc = dist_sync(D)) return rc;
-  fs::pcg_info_of(st0, info);
+  if (int rc = cg_iterations(f, sums, gather, cap, lambda, pre, fs::kStepPcgBeta)) return rc;
+  if (int rc = f.finish(x, W.sol, (size_t)F, gather)) return rc;
+  fs::pcg_info_of(f.st0, info);
   return FS_OK;
 }
 
 // fs_pcgn across the ranks, replicated whatever "dist_cg_scheme" says: every rank holds the whole F x k panels and launches
 // fs_pcgn's own kernels on them (pcgn_dev_*); T = A P and Q = A' T are the sharded k-column products (k = 1: the single-vector
-// ones).  The caller's X is written once, at the end.
+// ones).
 int fs_dist_pcgn(fs_dist_matrix_t M, double *X, const double *B, int k, double lambda, const fs_pcg_params *prm, fs_pcg_info *info)
 {
-  const char *who = "fs_dist_pcgn";
   if (!M || !X || !B || !prm) { fs::set_error("fs_dist_pcgn: NULL argument"); return FS_ERR_ARG; }
   if (k < 1 || k > FS_PCGN_MAX_RHS) { fs::set_error("fs_dist_pcgn: k outside 1..FS_PCGN_MAX_RHS"); return FS_ERR_ARG; }
-  if (int rc = pcg_params_ok(who, prm)) return rc;
-  if (!M->t.built) { fs::set_error("fs_dist_pcgn: call fs_dist_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
-  std::lock_guard<std::mutex> g(M->lock);
-  std::lock_guard<std::mutex> gd(M->D->lock);
-  DeviceGuard guard;
+  if (int rc = fs::pcg_params_ok("fs_dist_pcgn", prm)) return rc;
+  DistSolve f{"fs_dist_pcgn", M};
+  if (int rc = f.open("call fs_dist_matrix_build_transpose first")) return rc;
   if (prm->precond == FS_PRECOND_JACOBI)
     if (int rc = gram_diag_ready(M, "fs_dist_pcgn with FS_PRECOND_JACOBI (fs_gram_diag)")) return rc;
-  fs::FixedOrderScope fixed(fs::options().cg_fixed_order != 0);
-  fs_dist_t D = M->D;
-  const int n = D->n, F = M->ncol;
+  fs_dist_t D = f.D;
+  const int F = f.F;
   const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
   const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
   if (k > 1)
@@ -1936,60 +1860,40 @@ int fs_dist_pcgn(fs_dist_matrix_t M, double *X, const double *B, int k, double l
           return W.mem.get(d, W.st, (size_t)fs::kCgStateDoubles);
         })) return rc;
   }
+  f.st = &W.st;
   // the product vectors: P (replicated input of A), T = A P, Q = A' T
   const std::vector<double *> &vp = k > 1 ? M->kw.x : M->x, &vt = k > 1 ? M->kw.y : M->y, &vq = k > 1 ? M->kw.z : M->z;
-  {
-    std::vector<double *> unused;
-    if (int rc = vec_in(M, W.b, B, (size_t)F * k, unused, false)) return rc;
-    if (warm)
-      if (int rc = next_vec_in(M, W.sol, X, (size_t)F * k)) return rc;
-    if (prm->precond == FS_PRECOND_DIAG)
-      if (int rc = next_vec_in(M, vq, prm->diag, (size_t)F)) return rc;            // (d is staged where Q lives later)
-  }
-  std::vector<fs::CgFlags> fl((size_t)n);
-  for (int d = 0; d < n; ++d) {
-    FS_HIP(hipSetDevice(D->dev[d]));
-    if (int rc = fl[(size_t)d].init()) return rc;
-    if (int rc = fs::pcgn_dev_clear(W.cs[(size_t)d], D->stream[d])) return rc;
-  }
+  auto dinv_of = [&](int d) -> const double * { return pre ? W.dinv[(size_t)d] : nullptr; };
+  if (int rc = f.stage(W.b, B, (size_t)F * k)) return rc;
+  if (warm)
+    if (int rc = f.stage(W.sol, X, (size_t)F * k)) return rc;
+  if (prm->precond == FS_PRECOND_DIAG)
+    if (int rc = f.stage(vq, prm->diag, (size_t)F)) return rc;                     // (d is staged where Q lives later)
+  if (int rc = each_rank(D, false, [&](int d) { return fs::pcgn_dev_clear(W.cs[(size_t)d], D->stream[d]); })) return rc;
   if (prm->precond == FS_PRECOND_JACOBI)
     if (int rc = gram_diag_everywhere(M, lambda, vq)) return rc;
-  for (int d = 0; d < n && pre; ++d) {
-    FS_HIP(hipSetDevice(D->dev[d]));
-    if (int rc = fs::pcg_dev_dinv(F, vq[(size_t)d], W.dinv[(size_t)d], D->stream[d])) return rc;
-  }
+  if (pre)
+    if (int rc = each_rank(D, false, [&](int d) { return fs::pcg_dev_dinv(F, vq[(size_t)d], W.dinv[(size_t)d], D->stream[d]); })) return rc;
   if (warm) {                                                // Q = A'(A X0): one pair of k-column products
     if (int rc = dist_product(M, false, k, W.sol, vt)) return rc;
     if (int rc = dist_product(M, true, k, vt, vq)) return rc;
   }
-  for (int d = 0; d < n; ++d) {
-    FS_HIP(hipSetDevice(D->dev[d]));
-    if (int rc = fs::pcgn_dev_init(F, k, warm, lambda, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d],
-                                   pre ? W.dinv[(size_t)d] : nullptr, W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], prm->tol,
-                                   D->stream[d])) return rc;
-  }
-  int seen = ranks_done_at_start(D, W.st, who);
-  if (seen < 0) return seen;
-  for (int iter = 0; seen == kRanksGoOn && iter < cap; iter++) {
-    if (int rc = dist_product(M, false, k, vp, vt)) return rc;           // T = A P
-    if (int rc = dist_product(M, true, k, vt, vq)) return rc;            // Q = A' T
-    seen = ranks_after_iteration(D, fl, W.st, iter, who, [&](int d) {    // a rank's steps and its flags in one pass
-      return fs::pcgn_dev_steps(F, k, lambda, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d],
-                                pre ? W.dinv[(size_t)d] : nullptr, W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], D->stream[d]);
-    });
-    if (seen < 0) return seen;
-  }
-  if (int rc = dist_sync(D)) return rc;
-  if (seen == kRanksDisagree) return FS_ERR_HIP;
-  int iterations = 0;
-  double st0[fs::kCgStateDoubles], cs0[fs::kPcgnStateDoubles] = {0.0};
-  if (int rc = ranks_final_state(D, W.st, who, &iterations, st0)) return rc;
-  FS_HIP(hipMemcpy(cs0, W.cs[0], sizeof(double) * (size_t)k * (fs::kPcgnStateDoubles / FS_PCGN_MAX_RHS), hipMemcpyDeviceToHost));   // (rank 0's device is current)
-  if (vector_device(X) >= 0)
-    if (int rc = wait_for_caller(vector_device(X))) return rc;
-  if (int rc = vec_store(M, 0, X, W.sol[0], (size_t)F * k)) return rc;
-  if (int rc = dist_sync(D)) return rc;
-  fs::pcgn_note_state(st0, cs0, k, info);
+  if (int rc = each_rank(D, false, [&](int d) {
+        return fs::pcgn_dev_init(F, k, warm, lambda, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d], dinv_of(d),
+                                 W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], prm->tol, D->stream[d]);
+      })) return rc;
+  if (int rc = f.iterate(cap, true, [&]() -> int {
+        if (int rc2 = dist_product(M, false, k, vp, vt)) return rc2;       // T = A P
+        return dist_product(M, true, k, vt, vq);                           // Q = A' T
+      }, [&](int d) {
+        return fs::pcgn_dev_steps(F, k, lambda, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d], dinv_of(d),
+                                  W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], D->stream[d]);
+      })) return rc;
+  if (int rc = f.finish(X, W.sol, (size_t)F * k)) return rc;
+  double cs0[fs::kPcgnStateDoubles] = {0.0};
+  FS_HIP(hipSetDevice(D->dev[0]));
+  FS_HIP(hipMemcpy(cs0, W.cs[0], sizeof(double) * (size_t)k * (fs::kPcgnStateDoubles / FS_PCGN_MAX_RHS), hipMemcpyDeviceToHost));
+  fs::pcgn_note_state(f.st0, cs0, k, info);
   return FS_OK;
 }
 
@@ -2012,63 +1916,41 @@ int fs_dist_spmm_t(fs_dist_matrix_t M, double *Z, const double *U, int k)
   return dist_apply(M, true, Z, U, k);
 }
 
-// (A'A + lambda I) X = B for two right-hand sides, row-major ncol x 2: bsbm_cg2 (cg.h:85-187) across the GPUs, everything
-// resident.  Every device keeps whole X, R, P, Q and runs the same block-CG steps on them (identical inputs, identical kernels:
-// the 2x2 algebra needs no exchange); per iteration TMP = A P and Q = A' TMP as two-column products with their all-gathers.
-// Convergence is decided on every device and compared on the host like fs_dist_cg.  Products add in a fixed order unless
-// option "cg_fixed_order" is 0.
+// (A'A + lambda I) X = B for two right-hand sides, row-major ncol x 2: bsbm_cg2 (cg.h:85-187) across the GPUs.  Every device
+// keeps whole X, R, P, Q and runs the same block-CG steps on them (identical inputs, identical kernels: the 2x2 algebra needs no
+// exchange); per iteration TMP = A P and Q = A' TMP as two-column products with their all-gathers.
 int fs_dist_cg2(fs_dist_matrix_t M, double *X_host, const double *B_host, double lambda, double tol, int *out_iter)
 {
   if (!M || !X_host || !B_host) { fs::set_error("fs_dist_cg2: NULL argument"); return FS_ERR_ARG; }
-  if (!M->t.built) { fs::set_error("fs_dist_cg2: build the transpose first"); return FS_ERR_NO_TRANSPOSE; }
-  std::lock_guard<std::mutex> g(M->lock);
-  std::lock_guard<std::mutex> gd(M->D->lock);
-  DeviceGuard guard;
-  fs::FixedOrderScope fixed(fs::options().cg_fixed_order != 0);
-  fs_dist_t D = M->D;
-  const int n = D->n, F = M->ncol;
+  DistSolve f{"fs_dist_cg2", M};
+  if (int rc = f.open("build the transpose first")) return rc;
+  fs_dist_t D = f.D;
+  const int F = f.F;
   if (int rc = ensure_k(M, 2)) return rc;
   KWork &W = M->kw;
-  {
-    std::vector<double *> unused;
-    if (int rc = vec_in(M, W.b, B_host, (size_t)F * 2, unused, false)) return rc;
-  }
-  std::vector<fs::CgFlags> fl((size_t)n);
-  std::vector<double> norms(2 * (size_t)n, 0.0);
-  for (int d = 0; d < n; ++d) {
-    FS_HIP(hipSetDevice(D->dev[d]));
-    if (int rc = fl[(size_t)d].init()) return rc;
-    if (int rc = fs::cg2_dev_init(F, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], W.x[(size_t)d], W.part[(size_t)d], W.red[(size_t)d],
-                                  W.st[(size_t)d], tol, &norms[2 * (size_t)d], D->stream[d])) return rc;
-    if (norms[2 * (size_t)d] != norms[0] || norms[2 * (size_t)d + 1] != norms[1]) {
-      fs::set_error("fs_dist_cg2: the devices disagree about the norms of the right-hand sides");
-      return FS_ERR_HIP;
-    }
-  }
-  int seen = kRanksGoOn;
-  for (int iter = 0; iter < F; iter++) {
-    if (int rc = dist_product(M, false, 2, W.x, W.y)) return rc;         // TMP = A P
-    if (int rc = dist_product(M, true, 2, W.y, W.z)) return rc;          // Q = A' TMP
-    seen = ranks_after_iteration(D, fl, W.st, iter, "fs_dist_cg2", [&](int d) {   // a rank's steps and its flags in one pass
-      return fs::cg2_dev_steps(F, lambda, W.sol[(size_t)d], W.r[(size_t)d], W.x[(size_t)d], W.z[(size_t)d], W.part[(size_t)d],
-                               W.red[(size_t)d], W.st[(size_t)d], D->stream[d]);
-    });
-    if (seen < 0) return seen;
-    if (seen != kRanksGoOn) break;
-  }
-  for (int d = 0; d < n && seen != kRanksDisagree; ++d) {
-    FS_HIP(hipSetDevice(D->dev[d]));
-    if (int rc = fs::cg2_dev_finish(F, &norms[2 * (size_t)d], W.sol[(size_t)d], D->stream[d])) return rc;
-  }
-  if (int rc = dist_sync(D)) return rc;
-  if (seen == kRanksDisagree) return FS_ERR_HIP;
-  int iterations = 0;
-  if (int rc = ranks_final_state(D, W.st, "fs_dist_cg2", &iterations)) return rc;
-  if (vector_device(X_host) >= 0)
-    if (int rc = wait_for_caller(vector_device(X_host))) return rc;
-  if (int rc = vec_store(M, 0, X_host, W.sol[0], (size_t)F * 2)) return rc;
-  if (int rc = dist_sync(D)) return rc;
-  if (out_iter) *out_iter = iterations;
+  f.st = &W.st;
+  if (int rc = f.stage(W.b, B_host, (size_t)F * 2)) return rc;
+  std::vector<double> norms(2 * (size_t)f.n, 0.0);           // cg2_dev_init is synchronous: the norms of B's columns, per rank
+  if (int rc = each_rank(D, false, [&](int d) -> int {
+        if (int rc2 = fs::cg2_dev_init(F, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], W.x[(size_t)d], W.part[(size_t)d], W.red[(size_t)d],
+                                       W.st[(size_t)d], tol, &norms[2 * (size_t)d], D->stream[d])) return rc2;
+        if (norms[2 * (size_t)d] != norms[0] || norms[2 * (size_t)d + 1] != norms[1]) {
+          fs::set_error("fs_dist_cg2: the devices disagree about the norms of the right-hand sides");
+          return FS_ERR_HIP;
+        }
+        return FS_OK;
+      })) return rc;
+  if (int rc = f.iterate(F, false, [&]() -> int {
+        if (int rc2 = dist_product(M, false, 2, W.x, W.y)) return rc2;     // TMP = A P
+        return dist_product(M, true, 2, W.y, W.z);                         // Q = A' TMP
+      }, [&](int d) {
+        return fs::cg2_dev_steps(F, lambda, W.sol[(size_t)d], W.r[(size_t)d], W.x[(size_t)d], W.z[(size_t)d], W.part[(size_t)d],
+                                 W.red[(size_t)d], W.st[(size_t)d], D->stream[d]);
+      })) return rc;
+  if (f.seen != kRanksDisagree)                              // X back in B's scale
+    if (int rc = each_rank(D, false, [&](int d) { return fs::cg2_dev_finish(F, &norms[2 * (size_t)d], W.sol[(size_t)d], D->stream[d]); })) return rc;
+  if (int rc = f.finish(X_host, W.sol, (size_t)F * 2)) return rc;
+  if (out_iter) *out_iter = f.iterations;
   return FS_OK;
 }
 

@@ -14,8 +14,8 @@ import _pcg_model as P
 
 # the launchers fs_pcg and fs_dist_pcg share and the scalar steps cg_dev_final learnt; test_dist_pcg_model.py asserts them against
 # the sources
-LAUNCHERS = ("pcg_dev_dinv", "pcg_dev_init", "pcg_dev_start", "pcg_dev_steps", "pcg_dev_init_partial", "pcg_dev_start_partial",
-             "pcg_dev_step_b", "pcg_dev_step_c", "pcgn_dev_init", "pcgn_dev_steps")
+LAUNCHERS = ("pcg_dev_dinv", "cg_dev_init", "pcg_dev_init", "pcg_dev_start", "cg_dev_shift_dot", "cg_dev_update", "cg_dev_direction",
+             "cg_dev_steps", "pcgn_dev_init", "pcgn_dev_steps")
 FINAL_STEPS = ("kStepPcgStart", "kStepPcgRz", "kStepPcgBeta")
 SEND_DOUBLES = 2                                          # kCgSendDoubles: sums per rank in one exchange
 

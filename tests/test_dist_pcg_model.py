@@ -115,19 +115,22 @@ def test_names_are_the_sources():
         assert re.search(r"\bint " + name + r"\(", src["fs_cg.hip"]), name           # defined once, beside cg_dev_*
         assert re.search(r"\bint " + name + r"\(", src["fs_common.h"]), name
         assert len(re.findall(r"\bint " + name + r"\(", src["fs_cg.hip"])) == 1, name
-    for name in ("pcg_dev_dinv", "pcg_dev_init", "pcg_dev_start", "pcg_dev_steps", "pcg_dev_init_partial", "pcg_dev_start_partial",
-                 "pcg_dev_step_b", "pcg_dev_step_c", "pcgn_dev_init", "pcgn_dev_steps"):
+    for name in DP.LAUNCHERS:
         assert "fs::" + name + "(" in src["fs_dist.hip"], name                       # the sharded solvers call the same launchers
-    # one copy of each step: the kernels are launched from the launchers only
-    # (the update and the direction have a whole-vector and a slice launcher, like cg_dev_steps and cg_dev_step_b / _c)
-    for kernel, times in (("pcg_init_kernel<true>", 1), ("pcg_start_kernel<true>", 1), ("pcg_dinv_kernel,", 1), ("pcg_update_kernel,", 2),
-                          ("pcg_direction_kernel,", 2)):
-        assert src["fs_cg.hip"].count("hipLaunchKernelGGL(" + kernel) == times, kernel
+    # one copy of each step: every vector kernel is launched from ONE launcher, for whole vectors and slices alike
+    for kernel in ("cg_init_kernel,", "pcg_init_kernel<true>", "pcg_start_kernel<true>", "pcg_dinv_kernel,", "cg_update_dev_kernel,",
+                   "pcg_update_kernel,", "cg_direction_dev_kernel,", "pcg_direction_kernel,"):
+        assert src["fs_cg.hip"].count("hipLaunchKernelGGL(" + kernel) == 1, kernel
     for kernel in ("pcgn_init_kernel", "pcgn_start_kernel", "pcgn_update_kernel", "pcgn_update_lds_kernel", "pcgn_direction_kernel"):
         assert len(re.findall(r"hipLaunchKernelGGL\(\(?" + kernel + "<", src["fs_cg.hip"])) == 1, kernel
-    for step in DP.FINAL_STEPS:                                                      # cg_dev_final learnt fs_pcg's scalar steps
-        assert re.search(r"step == " + step + r"\b[^;]*final_step_kernel<[12], " + step + ">", src["fs_cg.hip"]), step
-    assert "final_step_kernel<2, kStepPcgStart>" in src["fs_cg.hip"] and "final_step_kernel<2, kStepPcgBeta>" in src["fs_cg.hip"]
+    # one dispatch from (step, sums) to the scalar step, for the whole-vector path and cg_dev_final: it knows fs_pcg's steps, each once
+    for step, nvs in (("kStepPcgStart", "2"), ("kStepPcgRz", "1"), ("kStepPcgBeta", "12")):
+        assert step in DP.FINAL_STEPS
+        for nv in nvs:
+            inst = f"final_step_kernel<{nv}, {step}>"
+            assert re.search(r"case " + step + r" \* 4 \+ " + nv + r": hipLaunchKernelGGL\(\(" + inst, src["fs_cg.hip"]), inst
+            assert src["fs_cg.hip"].count(inst) == 1, inst
+    assert len(DP.FINAL_STEPS) == 3 and src["fs_cg.hip"].count("launch_final_step(") == 3             # defined, and its two users
     assert f"constexpr int kCgSendDoubles = {DP.SEND_DOUBLES};" in src["fs_dist.hip"]
     # the gathered rank values have block_sum<NV>'s layout: finish_sum reads part[b * NV + j], the exchange leaves rank b's NV sums
     # at b * NV

@@ -11,7 +11,8 @@ test_gpu_pcg.py.  A' of every model is dist.t_csr(): the shards' own rows, downl
 6  a solve that is done before its first iteration enqueues no product for an iteration.
 7  fs_dist_pcgn: every column is fs_pcgn's on one device and the model's; k = 1 is fs_dist_pcg; "dist_cg_scheme" changes no bit.
 8  statuses, with x / X untouched by every refused call.
-9  guard zones, interleaved solves on one handle, device memory given back."""
+9  guard zones, interleaved solves on one handle, device memory given back.
+10 the number of sharded products per solve, for all four sharded solvers."""
 import ctypes as C
 
 import numpy as np
@@ -587,3 +588,69 @@ def test_interleaved_solves_share_the_work_space_and_give_it_back(L):
     one_solve = 8 * (3 * k * s.ncol + k * s.nrow + s.ncol + 2048 * k + 512)
     print(f"free device memory: {free0} bytes before the handle, {free1} after its destroy; allowance {one_solve}")
     assert free0 - free1 <= one_solve, (free0, free1, one_solve)
+
+
+# ---- 10 --------------------------------------------------------------------------------------------------------------------
+# the three smallest systems of GC.DIST_SET (three unknowns on three ranks; tol = 0: every solve ends at its cap) and the seed0 recipes
+PRODUCT_SET = ("three_eigenvalues", "cap_tol0", "fixture_100x50") + tuple(RECIPES0)
+
+
+def _loops(cap, iterations, at_start=False):
+    """iterations the host enqueues: the device sets `done` in loop iteration j and reports iterations == j; the host sees the flags of
+    iteration j synchronously behind iteration j + 1, so j + 2 iterations were enqueued -- or the cap; none for a solve done at its start"""
+    return 0 if at_start else min(cap, iterations + 2)
+
+
+@pytest.mark.parametrize("name", PRODUCT_SET)
+def test_sharded_products_per_solve(L, name):
+    """fs_debug_dist_products() per solve, strict mode, three ranks: per_iter x min(cap, iterations + 2) + warm, with per_iter = 2 sharded
+    products (replicate, fs_dist_pcgn, fs_dist_cg2) or 1 (gather: A' is the rank's own shard), and as many once in front of a warm start"""
+    s = ALL[name]
+    F = s.ncol
+    dist = GC.Dist(L, s, 3, False)
+
+    def counted(f):
+        before = L.fs_debug_dist_products()
+        out = f()
+        return L.fs_debug_dist_products() - before, out
+
+    try:
+        for scheme, per_iter in ((0, 2), (1, 1)):
+            with options(strict_order=1, dist_cg_scheme=scheme):
+                n, (_, it, st) = counted(lambda: dist.cg(False))
+                print(f"{name} scheme {scheme} fs_dist_cg: {n} products, {it} iterations, done {st['done']}")
+                assert n == per_iter * _loops(F, it), (name, scheme, "fs_dist_cg", n, it)
+                for precond in (P.PRECOND_NONE, P.PRECOND_JACOBI):
+                    for x0 in (None, G._x0(s)):
+                        for max_iter in (0, 2):
+                            n, (x, info, _) = counted(lambda: dpcg(L, dist, s, precond, x0, max_iter))
+                            start = np.zeros(F) if x0 is None else x0
+                            at_start = info.converged == 1 and info.iterations == 0 and bool(M.same_bits(x, start).all())
+                            what = (name, scheme, "fs_dist_pcg", precond, x0 is not None, max_iter, n, info.iterations, info.converged, at_start)
+                            print(*what)
+                            assert n == per_iter * (_loops(max_iter or F, info.iterations, at_start) + (x0 is not None)), what
+                            assert at_start or max_iter or info.converged == 1 or info.iterations == F, what
+                n, (x, info, _) = counted(lambda: dpcg(L, dist, s, P.PRECOND_JACOBI, b=np.zeros(F)))      # done at the start
+                assert n == 0 and info.converged == 1 and info.iterations == 0, (name, scheme, n)
+                if s.tol > 0.0:                                      # a warm start from a converged x: only the products in front
+                    x1, info1, _ = dpcg(L, dist, s, P.PRECOND_JACOBI)
+                    assert info1.converged == 1, (name, scheme)
+                    n, (x2, info2, _) = counted(lambda: dpcg(L, dist, s, P.PRECOND_JACOBI, x0=x1, tol=s.tol * 10))
+                    assert n == per_iter and info2.iterations == 0 and M.same_bits(x2, x1).all(), (name, scheme, n)
+        with options(strict_order=1):
+            for k in (1, 3):
+                B = GN.columns(s, k)
+                for X0, max_iter in ((None, 0), (GN.x0_columns(s, B), 2)):
+                    n, (X, infos, st, _) = counted(lambda: dpcgn(L, dist, s, B, P.PRECOND_JACOBI, X0, max_iter))
+                    start = np.zeros(B.shape) if X0 is None else X0
+                    at_start = st["done"] == 1.0 and st["iter"] == 0.0 and bool(M.same_bits(X, start).all())
+                    what = (name, "fs_dist_pcgn", k, X0 is not None, max_iter, n, st["iter"], st["done"], at_start)
+                    print(*what)
+                    assert st["iter"] == max(i.iterations for i in infos), what
+                    assert n == 2 * (_loops(max_iter or F, int(st["iter"]), at_start) + (X0 is not None)), what
+            if s.two:
+                n, (_, it, st) = counted(lambda: dist.cg(True))
+                print(f"{name} fs_dist_cg2: {n} products, {it} iterations")
+                assert n == 2 * _loops(F, it), (name, "fs_dist_cg2", n, it)
+    finally:
+        dist.close()

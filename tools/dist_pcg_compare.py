@@ -13,6 +13,10 @@ On config 2's pattern (10 M x 10 M, 16 per row, pattern-only, lambda 5), vectors
   three ranks   virtual ranks on the one device: host-issue-bound by construction, NOT a scaling result.  Scheme 0 against scheme 1,
                 without a preconditioner and with Jacobi; recorded without a bar.
 
+Both also record the other two sharded solvers, without a bar: fs_dist_cg2 (the slope between tol 1e-3 and 1e-8, like fs_dist_cg)
+and fs_dist_pcgn with Jacobi at k = 4 (the slope between caps 8 and 32) -- all four are in one record when two builds are
+compared (FS_LIB_PATH names the other build's library).
+
     python tools/dist_pcg_compare.py --out profiles/dist_pcg_compare.json"""
 import argparse
 import ctypes as C
@@ -62,20 +66,40 @@ class Sharded:
         capi.lib().fs_dist_destroy(self.D)
 
 
-def dist_cg(S, x, b, tol):
+def dist_cg(S, x, b, tol, two=False):
+    """fs_dist_cg, or (two: x, b of n x 2) fs_dist_cg2"""
     it = C.c_int(0)
-    _, ms = wall(lambda: capi.check(capi.lib().fs_dist_cg(S.M, x.data_ptr(), b.data_ptr(), LAM, tol, C.byref(it)), "fs_dist_cg"))
+    f = capi.lib().fs_dist_cg2 if two else capi.lib().fs_dist_cg
+    _, ms = wall(lambda: capi.check(f(S.M, x.data_ptr(), b.data_ptr(), LAM, tol, C.byref(it)), "fs_dist_cg2" if two else "fs_dist_cg"))
     return it.value + 1, ms
 
 
-def dist_cg_slope(S, x, b, tols=(1e-3, 1e-8)):
-    (n1, t1), (n2, t2) = (dist_cg(S, x, b, tol) for tol in tols)
+def dist_cg_slope(S, x, b, tols=(1e-3, 1e-8), two=False):
+    if two:                                                          # (the handle's k-column work space is fs_dist_pcgn's k = 4 by now:
+        dist_cg(S, x, b, tols[0], two)                               #  the switch back to k = 2 is one-time work, outside the timed pair)
+    (n1, t1), (n2, t2) = (dist_cg(S, x, b, tol, two) for tol in tols)
     assert n2 > n1, (n1, n2)
     return (t2 - t1) / (n2 - n1), [n1 - 1, n2 - 1]
 
 
+def panels(b, k):
+    """k right-hand sides, n x k row-major: b, then columns no two of which are parallel; and the X of the same shape"""
+    i = torch.arange(b.numel(), device="cuda", dtype=torch.float64)
+    B = torch.stack([b] + [torch.cos((7.0 + 3.0 * j) * i + 0.1 * j) for j in range(1, k)], 1).contiguous()
+    return torch.empty_like(B), B
+
+
+def dist_pcgn(S, X, B, cap):
+    """fs_dist_pcgn with Jacobi at tol 0: every column runs to the cap; the info of column 0"""
+    infos = capi.dist_pcgn(S.M, X, B, LAM, 0.0, max_iter=cap, precond=capi.FS_PRECOND_JACOBI)
+    assert all(i.iterations == cap and i.converged == 0 for i in infos), [(i.iterations, i.converged) for i in infos]
+    return infos[0]
+
+
 def capped_slope(solve, lo=8, hi=32):
-    """ms per iteration between two solves at tol 0 that run exactly lo and hi iterations, and what is left of the shorter one"""
+    """ms per iteration between two solves at tol 0 that run exactly lo and hi iterations, and what is left of the shorter one.
+    One untimed iteration first: a solve that follows one of another k switches the handle's k-column work space, once"""
+    solve(1)
     t = {}
     for n in (lo, hi):
         info, t[n] = wall(lambda: solve(n))
@@ -106,21 +130,28 @@ def one_rank(args, out):
         "fs_dist_pcg_none": lambda c: capi.dist_pcg(S.M, x, b, LAM, 0.0, max_iter=c, precond=capi.FS_PRECOND_NONE),
         "fs_dist_pcg_jacobi": lambda c: capi.dist_pcg(S.M, x, b, LAM, 0.0, max_iter=c, precond=capi.FS_PRECOND_JACOBI),
     }
+    X2, B2 = panels(b, 2)
+    X4, B4 = panels(b, 4)
+    solves["fs_dist_pcgn_k4_jacobi"] = lambda c: dist_pcgn(S, X4, B4, c)
     dist_cg(S, x, b, 1e-3)                                           # warm: every kernel, every work space
+    dist_cg(S, X2, B2, 1e-3, two=True)
     for f in solves.values():
         f(3)
-    per = {k: [] for k in ["fs_dist_cg"] + list(solves)}
+    per = {k: [] for k in ["fs_dist_cg", "fs_dist_cg2"] + list(solves)}
     once = {k: [] for k in solves}
-    counts = None
+    counts = counts2 = None
     for _ in range(args.repeats):                                    # interleaved, so that drift meets all of them alike
         p, counts = dist_cg_slope(S, x, b)
         per["fs_dist_cg"].append(p)
+        p, counts2 = dist_cg_slope(S, X2, B2, two=True)
+        per["fs_dist_cg2"].append(p)
         for k, f in solves.items():
             p, o = capped_slope(f)
             per[k].append(p)
             once[k].append(o)
     rec = {"system": f"config 2 pattern, {n} x {n}, {PER_ROW} per row, lambda {LAM}; one rank; slopes between caps 8 and 32 at tol 0",
-           "kernels": {"fs_pcg": [A.kernel_name(), At.kernel_name()]}, "fs_dist_cg_counts_at_tol_1e-3_1e-8": counts}
+           "kernels": {"fs_pcg": [A.kernel_name(), At.kernel_name()]}, "fs_dist_cg_counts_at_tol_1e-3_1e-8": counts,
+           "fs_dist_cg2_counts_at_tol_1e-3_1e-8": counts2}
     for k, v in per.items():
         rec[k] = stats(v)
         if k in once:
@@ -151,10 +182,17 @@ def three_ranks(args, out):
                 finally:
                     capi.set_option("dist_cg_scheme", 0)
             solves[f"scheme{scheme}_{name}"] = f
+    X2, B2 = panels(b, 2)
+    X4, B4 = panels(b, 4)
+    solves["fs_dist_pcgn_k4_jacobi"] = lambda c: dist_pcgn(S, X4, B4, c)         # (replicated whatever the scheme)
+    dist_cg(S, x, b, 1e-3)
+    dist_cg(S, X2, B2, 1e-3, two=True)
     for f in solves.values():
         f(3)
-    per = {k: [] for k in solves}
+    per = {k: [] for k in ["fs_dist_cg", "fs_dist_cg2"] + list(solves)}
     for _ in range(args.repeats):
+        per["fs_dist_cg"].append(dist_cg_slope(S, x, b)[0])
+        per["fs_dist_cg2"].append(dist_cg_slope(S, X2, B2, two=True)[0])
         for k, f in solves.items():
             per[k].append(capped_slope(f)[0])
     rec = {"system": f"config 2 pattern, {n} x {n}, {PER_ROW} per row, lambda {LAM}; three VIRTUAL ranks on one device",
