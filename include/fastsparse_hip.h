@@ -397,8 +397,13 @@ fs_dist_matrix_t fs_dist_csr_create(fs_dist_t D, int nrow, int ncol, int64_t nnz
 fs_dist_matrix_t fs_dist_coo_create(fs_dist_t D, int nrow, int ncol, int64_t nnz, const int *rows, const int *cols, const double *vals);
 /* A and its transpose as the caller holds them -- TWO matrices, like bsbm_cg(x, B, Bt, ...) cg.h:25 -- as one handle for fs_dist_cg /
  * fs_dist_cg2 / fs_dist_ata / the *_t products: direct side = A's, transposed side = At's direct side (a row of A' adds in the order
- * the caller's own At stores it).  Shares the shards of both (no copy; they live until the last of the three handles is destroyed);
- * own vectors and solver work space. */
+ * the caller's own At stores it).  Shares the shards of both (no copy; they live until the last of the three handles is destroyed, in
+ * any order); own vectors and solver work space.  The cuts of its transposed side are At's row cuts, whatever the caller chose
+ * (fs_dist_matrix_bounds_t; empty shards anywhere, one-row shards): scheme 1 of fs_dist_cg / fs_dist_pcg slices by them.  It HAS its
+ * transposed side: fs_dist_matrix_build_transpose[_device] on a pair return FS_OK and build nothing.  NULL with a message in
+ * fs_last_error(): a NULL handle, handles of two contexts, shapes that are not each other's transposes.  The single-vector exchange
+ * buffers belong to a side, so to every handle that shares it: products on different handles of one context are ordered by the
+ * context's lock. */
 fs_dist_matrix_t fs_dist_matrix_pair(fs_dist_matrix_t A, fs_dist_matrix_t At);
 /* The matrix as per-rank shards -- no whole-matrix array anywhere, so the TOTAL may exceed 2^31 - 1 entries (every shard stays
  * below it: int row_ptr, csr.h:358-366); BASELINE config 5 (3.2 G entries, 8 shards) enters this way.  Shard r = the next

@@ -433,6 +433,16 @@ def pcgn(A, At, X, B, lam, tol, max_iter=0, precond=FS_PRECOND_JACOBI, warm_star
     return list(infos)[:k]
 
 
+def dist_matrix_pair(A, At):
+    """A and the caller's own A' (two fs_dist_matrix_t handles of one context) as one handle for the transposed products and the
+    sharded solvers (fs_dist_matrix_pair): the shards are shared, not copied.  Returns the new handle; the caller destroys it with
+    fs_dist_matrix_destroy, before or after A and At."""
+    M = lib().fs_dist_matrix_pair(A, At)
+    if not M:
+        raise FastsparseError("fs_dist_matrix_pair failed: " + lib().fs_last_error().decode())
+    return M
+
+
 def dist_gram_diag(M, lam, d):
     """d = the diagonal of A'A + lam I on a row-sharded matrix (fs_dist_gram_diag); M: the fs_dist_matrix_t handle, d: ncol doubles,
     a numpy array in host memory or a tensor on any device of the context"""

@@ -102,8 +102,9 @@ def _case_args(s, case, t_csr):
 
 
 def _model(s, case, t_csr, bounds=None):
-    """the (slice) model of a case on the A' the shards hold; the sorted A' is the same for every rank count and either build"""
-    key = (s.name, case, None if bounds is None else tuple(bounds))
+    """the (slice) model of a case on the A' the shards hold; the sorted A' is the same for every rank count and either build (the
+    entries of A' are part of the key: a pair handle holds the caller's order, tests/test_gpu_dist_pair.py)"""
+    key = (s.name, case, None if bounds is None else tuple(bounds), t_csr[1].tobytes(), None if t_csr[2] is None else t_csr[2].tobytes())
     if key not in _MODELS:
         _, precond, x0, max_iter, diag = _case_args(s, case, t_csr)
         _MODELS[key] = DP.run(s, precond, max_iter=max_iter, x0=x0, t_csr=t_csr, diag=diag, bounds=bounds)
@@ -234,27 +235,34 @@ def test_scheme1_with_empty_slices(L):
 @pytest.mark.parametrize("name", [n for n in G.RECIPES if n.startswith("scaled")])
 def test_default_mode_jacobi_converges_where_plain_cg_does_not(L, name):
     s = G.RECIPES[name]
-    model = P.run(s, P.PRECOND_JACOBI)
-    assert model.state["done"] == 1.0
     dist = GC.Dist(L, s, 3, False)
     try:
-        for scheme in (0, 1):
-            with options(dist_cg_scheme=scheme):
-                runs = [dpcg(L, dist, s, P.PRECOND_JACOBI) for _ in range(2)]
-                plain = dpcg(L, dist, s)
-            x, info, _ = runs[0]
-            res = G._residual(s, x)
-            print(f"{name} scheme {scheme}: jacobi {info.iterations} iterations (model {model.iterations}), true residual {res:.3g} "
-                  f"= {res / s.tol:.2f} tol; plain {plain[1].iterations} iterations, converged {plain[1].converged}")
-            what = (name, scheme, info.iterations, model.iterations, res)
-            assert info.converged == 1, what
-            assert res <= 2 * s.tol, what
-            assert abs(info.iterations - model.iterations) <= 1, what
-            assert info.rnorm <= s.tol * info.bnorm, what
-            assert runs[1][1].iterations == info.iterations and M.same_bits(runs[1][0], x).all(), what
-            assert plain[1].converged == 0 and plain[1].iterations == s.ncol, (what, plain[1].iterations)
+        assert_default_mode_bars(L, dist, s)
     finally:
         dist.close()
+
+
+def assert_default_mode_bars(L, dist, s):
+    """the bars of a column-scaled recipe in the default mode, both schemes, on any handle with a transposed side (a built one here,
+    a pair in test_gpu_dist_pair.py)"""
+    name = s.name
+    model = P.run(s, P.PRECOND_JACOBI)
+    assert model.state["done"] == 1.0
+    for scheme in (0, 1):
+        with options(dist_cg_scheme=scheme):
+            runs = [dpcg(L, dist, s, P.PRECOND_JACOBI) for _ in range(2)]
+            plain = dpcg(L, dist, s)
+        x, info, _ = runs[0]
+        res = G._residual(s, x)
+        print(f"{name} scheme {scheme}: jacobi {info.iterations} iterations (model {model.iterations}), true residual {res:.3g} "
+              f"= {res / s.tol:.2f} tol; plain {plain[1].iterations} iterations, converged {plain[1].converged}")
+        what = (name, scheme, info.iterations, model.iterations, res)
+        assert info.converged == 1, what
+        assert res <= 2 * s.tol, what
+        assert abs(info.iterations - model.iterations) <= 1, what
+        assert info.rnorm <= s.tol * info.bnorm, what
+        assert runs[1][1].iterations == info.iterations and M.same_bits(runs[1][0], x).all(), what
+        assert plain[1].converged == 0 and plain[1].iterations == s.ncol, (what, plain[1].iterations)
 
 
 # ---- 5 ---------------------------------------------------------------------------------------------------------------------
