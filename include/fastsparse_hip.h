@@ -86,7 +86,7 @@ int  fs_set_device(int device);
  * "reproducible", so that a solve is bit-identical from run to run like the reference's loops (cg.h:25-187); 0 = the default kernels.
  * "pcgn_kernel": fs_pcgn's per-iteration vector kernels, 0 = auto (see fs_pcgn), 1 = a lane per row, 2 = the 256-row panels staged
  * through LDS with coalesced accesses; both give the same bits.
- * "dist_cg_scheme" (FS_DIST_CG_SCHEME): fs_dist_cg and fs_dist_pcg, 0 every device keeps whole vectors, 1 every device keeps its slice (see there). */
+ * "dist_cg_scheme" (FS_DIST_CG_SCHEME): fs_dist_cg, fs_dist_pcg and fs_dist_mscg, 0 every device keeps whole vectors, 1 every device keeps its slice (see there). */
 int  fs_set_option(const char *name, int value);
 int  fs_get_option(const char *name);
 
@@ -496,6 +496,34 @@ int  fs_dist_pcg(fs_dist_matrix_t M, double *x, const double *b, double lambda, 
  * to X. */
 int  fs_dist_pcgn(fs_dist_matrix_t M, double *X, const double *B, int k, double lambda, const fs_pcg_params *prm,
                   fs_pcg_info *info /* k entries or NULL */);
+/* fs_dist_mscg: fs_mscg on the sharded matrix -- (A'A + lambda[i] I) x_i = b for i < m from one Krylov sequence, m in
+ * 1..FS_MSCG_MAX_SHIFTS.  Its arithmetic is fs_mscg's above, whose text is the single statement of it; this says only what differs.
+ * x_i at X + i * ldx (ldx >= ncol); X and b in host memory or in HBM of any device of the context, decided per vector as for
+ * fs_dist_pcg: nothing in HBM is staged through the host.  lambda: m doubles on the host; info: m entries or NULL.  Needs the
+ * transposed side (FS_ERR_NO_TRANSPOSE; from fs_dist_matrix_build_transpose, _device or fs_dist_matrix_pair), is synchronous, cold
+ * start only and without a preconditioner, for fs_mscg's reasons.  Option "dist_cg_scheme" as for fs_dist_pcg; slices only with more
+ * than one rank:
+ *   0  every rank holds whole r, p, q, the m x_i and the directions P_i and launches fs_mscg's own kernels on them; both products
+ *      carry their all-gather, nothing is exchanged for the sums.  `red` is fs_mscg's: under "strict_order" X, fs_pcg_info, the
+ *      scalars and the per-shift array are fs_mscg's on the same CSRs, bit for bit, for any number of ranks.
+ *   1  rank r keeps its slice -- the rows of A' it owns -- of r, p, q, every x_i and every P_i.  The x_i and P_i never leave their
+ *      rank: only p enters a product, so an iteration costs fs_dist_cg's exchanges (two sums of 8 bytes per rank, one all-gather of
+ *      p) however many shifts there are, and the (12 + 5 L) F doubles the vector kernels move are divided by the ranks, as is the
+ *      (m + nslots) F work space.  q_r = A'_r y is the rank's own shard.  `red` (b b, q p, r r) is the slice tree of fs_dist_cg: the
+ *      rank reduces its slice with both stages, the rank values are all-gathered and added in rank order by the second stage (an
+ *      empty slice gives +0.0); start, S1 and S2 then run on every rank over the same N values, so every rank holds identical
+ *      alpha, zn, a_i, b_i, freezes and list of live shifts.  The first p is b, which every rank holds whole: no gather before the
+ *      first product.
+ * Every rank decides convergence for itself as in fs_dist_cg; besides {done, iterations} every rank's per-shift {live, converged,
+ * count} must agree with rank 0's: a disagreement is an error return (FS_ERR_HIP).  X is written ONCE, at the end of a solve that
+ * succeeded: every refusal and every product error leaves all of X untouched.  A solve that is done at its start (b = 0, tol >= 1)
+ * enqueues no product: X = 0, every shift converged, 0 iterations.  The x_i, the P_i and the per-shift array stay on the handle
+ * between solves (re-made when a solve needs more or longer vectors, freed by fs_dist_matrix_destroy); r, b, p, q are fs_dist_pcg's.
+ * FS_ERR_ARG, raised before anything else happens: a NULL M, X, b or lambda; m outside 1..FS_MSCG_MAX_SHIFTS; ldx < ncol; tol
+ * negative or NaN; a lambda that is NaN or infinite.  A product's own error is passed through (FS_ERR_RELEASED under "strict_order"
+ * on a shard that gave its plain CSR back).  CLOBBERS fs_dist_x / fs_dist_y / fs_dist_z like fs_dist_cg. */
+int  fs_dist_mscg(fs_dist_matrix_t M, double *X, int64_t ldx, const double *b, int m, const double *lambda /* host */,
+                  double tol, int max_iter, fs_pcg_info *info /* m entries or NULL */);
 /* k row-major columns across the GPUs (csr_A_mul_Bn csr.h:441, bcsr_A_mul_Bn csr.h:257, bsbm_A_mul_Bn sparse.h:318): every device
  * multiplies its shard with the k-column kernels of fs_spmm (prepared on the first call with a new k: synchronous) and the Y shards
  * are all-gathered -- inside the product, part by part, where the k-column product finishes its rows that way (the one-sweep plan

@@ -34,7 +34,7 @@ DEVICE_API = [
     "fs_dist_matrix_build_transpose", "fs_dist_matrix_has_transpose", "fs_dist_spmv_t", "fs_dist_spmv_t_resident", "fs_dist_swap_xy",
     "fs_dist_z", "fs_dist_cg", "fs_dist_is_conservative", "fs_dist_csr_create_from_shards", "fs_dist_matrix_build_transpose_device",
     "fs_dist_matrix_bounds_t", "fs_dist_matrix_nnz", "fs_dist_matrix_shard", "fs_dist_spmm", "fs_dist_spmm_t", "fs_dist_cg2",
-    "fs_dist_coo_create", "fs_dist_matrix_pair", "fs_dist_ata", "fs_dist_gram_diag", "fs_dist_pcg", "fs_dist_pcgn",
+    "fs_dist_coo_create", "fs_dist_matrix_pair", "fs_dist_ata", "fs_dist_gram_diag", "fs_dist_pcg", "fs_dist_pcgn", "fs_dist_mscg",
 ]
 REFERENCE_API = [
     # sparse.h
@@ -194,6 +194,7 @@ def lib():
     L.fs_dist_gram_diag.argtypes = [vp, C.c_double, vp]
     L.fs_dist_pcg.argtypes = [vp, vp, vp, C.c_double, C.POINTER(PcgParams), C.POINTER(PcgInfo)]
     L.fs_dist_pcgn.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.POINTER(PcgParams), C.POINTER(PcgInfo)]
+    L.fs_dist_mscg.argtypes = [vp, vp, C.c_int64, vp, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(PcgInfo)]
     L.fs_dist_spmm.argtypes = [vp, vp, vp, C.c_int]
     L.fs_dist_spmm_t.argtypes = [vp, vp, vp, C.c_int]
     for f in ("fs_dist_spmv_resident", "fs_dist_spmv_t_resident", "fs_dist_swap_xy"):
@@ -468,6 +469,27 @@ def dist_pcgn(M, X, B, lam, tol, max_iter=0, precond=FS_PRECOND_JACOBI, warm_sta
     infos = (PcgInfo * max(k, 1))()
     check(lib().fs_dist_pcgn(M, _ptr(X), _ptr(B), k, float(lam), C.byref(prm), infos), "fs_dist_pcgn")
     return list(infos)[:k]
+
+
+def dist_mscg(M, X, b, lams, tol, max_iter=0):
+    """fs_mscg on a row-sharded matrix (fs_dist_mscg); X: an (m, F) numpy array in host memory or a tensor on any device of the
+    context, with unit inner stride (rows may be padded: ldx comes from the stride of the first axis), b: F doubles, host or device,
+    lams: m <= FS_MSCG_MAX_SHIFTS host values.  Returns the list of the m PcgInfo, one per shift."""
+    lams = [float(v) for v in lams]
+    m = len(lams)
+    if len(X.shape) != 2 or X.shape[0] != m:
+        raise ValueError("dist_mscg: X must be (len(lams), F) with unit inner stride")
+    if hasattr(X, "data_ptr"):
+        at, s0, s1 = X.data_ptr(), X.stride(0), X.stride(1)
+    else:
+        at, s0, s1 = X.ctypes.data, X.strides[0] // X.itemsize, X.strides[1] // X.itemsize
+    if X.shape[1] > 1 and s1 != 1:
+        raise ValueError("dist_mscg: X must be (len(lams), F) with unit inner stride")
+    ldx = s0 if m > 1 else max(s0, X.shape[1])
+    infos = (PcgInfo * max(m, 1))()
+    check(lib().fs_dist_mscg(M, at, int(ldx), _ptr(b), m, (C.c_double * max(m, 1))(*lams), float(tol), int(max_iter), infos),
+          "fs_dist_mscg")
+    return list(infos)[:m]
 
 
 _option_epoch = 0

@@ -388,7 +388,7 @@ enum { kStAprev = 8, kStBprev = 9, kStNLive = 10, kStNBase = 11 };
 enum { kMsSigma = 0, kMsZ = 1, kMsZp = 2, kMsZn = 3, kMsRatio = 4, kMsA = 5, kMsB = 6, kMsRn = 7, kMsLive = 8, kMsConverged = 9,
        kMsCount = 10, kMsList = 11, kMsPslot = 12, kMsStride = 16 };
 constexpr int kMscgGroup = 4;              // shifts whose loads one thread keeps in flight together
-struct MscgSigma { double v[kMscgMaxShifts]; };
+static_assert(kMscgStateDoubles == kMscgMaxShifts * kMsStride, "fs_common.h sizes the callers' ms[]");
 
 // x_i = 0 for the m shifts, r = p = b, P = b for the nslots shifts with sigma != 0, partial b.b
 __global__ __launch_bounds__(kRedThreads) void mscg_init_kernel(int n, const double *__restrict__ b, double *__restrict__ r,
@@ -1361,6 +1361,105 @@ int pcgn_dev_steps(int n, int k, double lambda, double *X, const double *B, doub
   });
 }
 
+// ---- fs_mscg's steps as launchers (fs_mscg; fs_dist_mscg on every rank: whole vectors, or the rank's slice of r, p, q, the x_i
+// and the P_i).  The vector kernels take (n, part), the scalar kernels (partials, count): kRedBlocks partials of whole vectors, or
+// the ranks' values, gathered.  A slice's sums go through final_sum_kernel into the send slot, as in finish_sums.
+
+// what fs_mscg and fs_dist_mscg refuse in their arguments, in this order, in `who`'s name
+int mscg_args_ok(const char *who, int F, int64_t ldx, int m, const double *lambda, double tol)
+{
+  const std::string w(who);
+  if (m < 1 || m > kMscgMaxShifts) { set_error(w + ": m outside 1..FS_MSCG_MAX_SHIFTS"); return FS_ERR_ARG; }
+  if (ldx < F) { set_error(w + ": ldx < ncol(A)"); return FS_ERR_ARG; }
+  if (!(tol >= 0.0)) { set_error(w + ": tol is negative or NaN"); return FS_ERR_ARG; }
+  for (int i = 0; i < m; ++i)
+    if (!isfinite(lambda[i])) { set_error(w + ": a lambda is NaN or infinite"); return FS_ERR_ARG; }
+  return FS_OK;
+}
+
+// the host's part of a solve: the base system, every shift's sigma and the number of direction vectors
+MscgShifts mscg_shifts(int m, const double *lambda)
+{
+  double base = lambda[0];
+  for (int i = 1; i < m; ++i) if (lambda[i] < base) base = lambda[i];
+  MscgSigma sg;
+  int nslots = 0;
+  for (int i = 0; i < kMscgMaxShifts; ++i) {
+    sg.v[i] = i < m ? lambda[i] - base : 0.0;                 // exactly 0 for the minimum and its duplicates
+    if (sg.v[i] != 0.0) ++nslots;
+  }
+  return MscgShifts{base, sg, nslots};
+}
+
+// the one-workgroup kernel that finishes a sum of `count` partials and takes the scalar step
+static int mscg_scalar_step(MscgStep step, const double *partials, int count, double *red, double *st, const MscgScalars &K, hipStream_t s)
+{
+  const dim3 one(1), blk(kRedThreads);
+  if (step == kMscgStart)   hipLaunchKernelGGL(mscg_start_kernel, one, blk, 0, s, partials, count, red, st, K.ms, K.tol, K.m, K.sh->sg);
+  else if (step == kMscgS1) hipLaunchKernelGGL(mscg_s1_kernel, one, blk, 0, s, partials, count, red, st, K.ms, K.m);   // alpha, the a_i
+  else                      hipLaunchKernelGGL(mscg_s2_kernel, one, blk, 0, s, partials, count, red, st, K.ms, K.m);   // converged? beta, freezes
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// behind a vector kernel that left one sum per workgroup in S.part
+static int mscg_finish_sums(const CgSums &S, MscgStep step, const MscgScalars &K, hipStream_t s)
+{
+  if (!S.slice) return mscg_scalar_step(step, S.part, kRedBlocks, S.red, S.st, K, s);
+  hipLaunchKernelGGL(final_sum_kernel<1>, dim3(1), dim3(kRedThreads), 0, s, S.part, kRedBlocks, S.slice);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// x_i = 0 for the K.m shifts, r = p = b, P_i = b for the shifts with sigma != 0; b.b, stop, every shift's scalars, done?
+int mscg_dev_init(int n, const double *b, double *r, double *p, double *X, long long ldx, double *P, long long ldp, const CgSums &S,
+                  const MscgScalars &K, hipStream_t s)
+{
+  hipLaunchKernelGGL(mscg_init_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, b, r, p, X, ldx, K.m, P, ldp, K.sh->nslots, S.part);
+  return mscg_finish_sums(S, kMscgStart, K, s);
+}
+
+// behind q = A'(A p): q += base p, q.p on fs_cg's kernel; S1
+int mscg_dev_shift_dot(int F, double base, const double *p, double *q, const CgSums &S, const MscgScalars &K, hipStream_t s)
+{
+  const dim3 g(kRedBlocks), blk(kRedThreads);
+  double *part = S.part;
+  const double *st = S.st;
+  hipLaunchKernelGGL(cg_shift_dot_dev_kernel, g, blk, 0, s, F, base, q, p, part, st);
+  return mscg_finish_sums(S, kMscgS1, K, s);
+}
+
+// r and the x_i of the live shifts; r.r; S2
+int mscg_dev_update(int n, double *r, const double *p, const double *q, double *X, long long ldx, const double *P, long long ldp,
+                    const CgSums &S, const MscgScalars &K, hipStream_t s)
+{
+  hipLaunchKernelGGL(mscg_update_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, r, p, q, X, ldx, P, ldp, S.part, S.st, K.ms);
+  return mscg_finish_sums(S, kMscgS2, K, s);
+}
+
+// the new p and the new P_i of the live shifts
+int mscg_dev_direction(int n, double *p, const double *r, double *P, long long ldp, const double *st, const double *ms, hipStream_t s)
+{
+  hipLaunchKernelGGL(mscg_direction_kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, p, r, P, ldp, st, ms);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// everything of an iteration behind q = A'(A p) on whole vectors, all on the device
+int mscg_dev_steps(int n, double base, double *r, double *p, double *q, double *X, long long ldx, double *P, long long ldp, const CgSums &S,
+                   const MscgScalars &K, hipStream_t s)
+{
+  if (int rc = mscg_dev_shift_dot(n, base, p, q, S, K, s)) return rc;
+  if (int rc = mscg_dev_update(n, r, p, q, X, ldx, P, ldp, S, K, s)) return rc;
+  return mscg_dev_direction(n, p, r, P, ldp, S.st, K.ms, s);
+}
+
+// the sums of every rank's slice, gathered: `partials` holds one value per rank, finish_sum's tree (stage 2) adds them in rank order
+int mscg_dev_final(MscgStep step, const double *partials, int count, double *red_out, double *st, const MscgScalars &K, hipStream_t s)
+{
+  return mscg_scalar_step(step, partials, count, red_out, st, K, s);
+}
+
 // ---- the same for two right-hand sides (fs_cg2, fs_dist_cg2).  cg2_dev_init is synchronous (two reductions go to the host: the
 // norms of B's columns scale the system, cg.h:105-125); norms[2] is returned for the final cg2_dev_finish
 int cg2_dev_init(int n, const double *B, double *X, double *R, double *P, double *part, double *red, double *st, double tol,
@@ -1440,6 +1539,31 @@ void pcgn_note_state(const double *fin_in, const double *fcs, int k, fs_pcg_info
     info[j].rnorm = sqrt(e[kPnRr]);
     info[j].bnorm = sqrt(e[kPnBb]);
   }
+}
+
+// the end of an fs_mscg solve on the host: fin = the final st[] (kept for fs_debug_last_cg_state), fms = the final ms[] of the m
+// shifts (kept for fs_debug_last_mscg_state); info: m entries or NULL
+void mscg_note_state(const double *fin, const double *fms, int m, fs_pcg_info *info)
+{
+  note_cg_state(fin);
+  for (int i = 0; i < m * kMsStride; ++i) g_last_mscg_state[i] = fms[i];
+  g_last_mscg_doubles = m * kMsStride;
+  for (int i = 0; info && i < m; ++i) {
+    const double *e = fms + i * kMsStride;
+    info[i].iterations = (int)e[kMsCount];                   // a shift still live at the cap: count = cap, converged 0
+    info[i].converged = e[kMsConverged] != 0.0;
+    info[i].rnorm = e[kMsRn];
+    info[i].bnorm = sqrt(fin[kStBb]);
+  }
+}
+
+// two ranks' final ms[]: every shift ended live or not, converged or not, with the same count
+bool mscg_same_outcome(const double *a, const double *b, int m)
+{
+  for (int i = 0; i < m; ++i)
+    for (int at : {(int)kMsLive, (int)kMsConverged, (int)kMsCount})
+      if (a[i * kMsStride + at] != b[i * kMsStride + at]) return false;
+  return true;
 }
 
 int CgFlags::init()
@@ -1654,53 +1778,23 @@ int fs_mscg(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double 
   CgSolve f{"fs_mscg", A, At, 1, stream};
   if (int rc = f.shape()) return rc;
   const int F = f.F;
-  if (m < 1 || m > kMscgMaxShifts) { set_error("fs_mscg: m outside 1..FS_MSCG_MAX_SHIFTS"); return FS_ERR_ARG; }
-  if (ldx < F) { set_error("fs_mscg: ldx < ncol(A)"); return FS_ERR_ARG; }
-  if (!(tol >= 0.0)) { set_error("fs_mscg: tol is negative or NaN"); return FS_ERR_ARG; }
-  for (int i = 0; i < m; ++i)
-    if (!isfinite(lambda[i])) { set_error("fs_mscg: a lambda is NaN or infinite"); return FS_ERR_ARG; }
+  if (int rc = mscg_args_ok("fs_mscg", F, ldx, m, lambda, tol)) return rc;
   if (int rc = f.ready()) return rc;
-  double base = lambda[0];
-  for (int i = 1; i < m; ++i) if (lambda[i] < base) base = lambda[i];
-  MscgSigma sg;
-  int nslots = 0;
-  for (int i = 0; i < kMscgMaxShifts; ++i) {
-    sg.v[i] = i < m ? lambda[i] - base : 0.0;                 // exactly 0 for the minimum and its duplicates
-    if (sg.v[i] != 0.0) ++nslots;
-  }
+  const MscgShifts sh = mscg_shifts(m, lambda);
   const int cap = max_iter > 0 ? max_iter : F;               // cg.h:55
   const long long ldp = ((long long)F + 1) & ~1LL;           // every P_i 16-byte aligned
   hipStream_t s = (hipStream_t)stream;
   double *P = nullptr, *ms = nullptr;
-  if (int rc = f.alloc(&P, (size_t)ldp * nslots, &ms, kMscgMaxShifts * kMsStride)) return rc;
-  double *r = f.r, *p = f.p, *q = f.q, *part = f.part, *red = f.red, *st = f.st;
-  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
-  hipLaunchKernelGGL(mscg_init_kernel, g, blk, 0, s, F, b, r, p, X, (long long)ldx, m, P, ldp, nslots, part);
-  hipLaunchKernelGGL(mscg_start_kernel, one, blk, 0, s, part, kRedBlocks, red, st, ms, tol, m, sg);
-  FS_HIP(hipGetLastError());
-  auto steps = [&]() -> int {
-    hipLaunchKernelGGL(cg_shift_dot_dev_kernel, g, blk, 0, s, F, base, q, p, part, st);
-    hipLaunchKernelGGL(mscg_s1_kernel, one, blk, 0, s, part, kRedBlocks, red, st, ms, m);               // alpha, the a_i
-    hipLaunchKernelGGL(mscg_update_kernel, g, blk, 0, s, F, r, p, q, X, (long long)ldx, P, ldp, part, st, ms);
-    hipLaunchKernelGGL(mscg_s2_kernel, one, blk, 0, s, part, kRedBlocks, red, st, ms, m);               // converged? beta, freezes
-    hipLaunchKernelGGL(mscg_direction_kernel, g, blk, 0, s, F, p, r, P, ldp, st, ms);
-    FS_HIP(hipGetLastError());
-    return FS_OK;
-  };
-  if (int rc = f.iterate(cap, true, steps)) return rc;
+  if (int rc = f.alloc(&P, (size_t)ldp * sh.nslots, &ms, kMscgMaxShifts * kMsStride)) return rc;
+  double *r = f.r, *p = f.p, *q = f.q;
+  const CgSums sums{f.part, f.red, f.st};
+  const MscgScalars K{ms, m, tol, &sh};
+  if (int rc = mscg_dev_init(F, b, r, p, X, (long long)ldx, P, ldp, sums, K, s)) return rc;
+  if (int rc = f.iterate(cap, true, [&] { return mscg_dev_steps(F, sh.base, r, p, q, X, (long long)ldx, P, ldp, sums, K, s); })) return rc;
   double fms[kMscgMaxShifts * kMsStride] = {0.0};
   FS_HIP(hipMemcpyAsync(fms, ms, sizeof(double) * m * kMsStride, hipMemcpyDeviceToHost, s));
   if (int rc = f.finish()) return rc;
-  const double *fin = f.fin;
-  for (int i = 0; i < m * kMsStride; ++i) g_last_mscg_state[i] = fms[i];
-  g_last_mscg_doubles = m * kMsStride;
-  for (int i = 0; info && i < m; ++i) {
-    const double *e = fms + i * kMsStride;
-    info[i].iterations = (int)e[kMsCount];                   // a shift still live at the cap: count = cap, converged 0
-    info[i].converged = e[kMsConverged] != 0.0;
-    info[i].rnorm = e[kMsRn];
-    info[i].bnorm = sqrt(fin[kStBb]);
-  }
+  mscg_note_state(f.fin, fms, m, info);
   return FS_OK;
 }
 
@@ -1784,7 +1878,7 @@ int fs_debug_last_cg_state(double *out)
   return kStDoubles;
 }
 
-// the final per-shift array of the last fs_mscg on the calling thread: m * kMsStride doubles (layout of the kMs enum), at most
+// the final per-shift array of the last fs_mscg (or rank 0's of the last fs_dist_mscg) on the calling thread: m * kMsStride doubles (layout of the kMs enum), at most
 // max_doubles of them.  Returns the number of doubles written, 0 before the first solve.  Diagnostics, not in the header.
 int fs_debug_last_mscg_state(double *out, int max_doubles)
 {

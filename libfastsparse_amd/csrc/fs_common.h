@@ -388,6 +388,31 @@ int pcgn_dev_steps(int n, int k, double lambda, double *X, const double *B, doub
                    double *part, double *st, double *cs, hipStream_t s);
 // the final st[] and cs[] (k columns) on the host: kept for the debug getters, info (k entries or NULL) filled
 void pcgn_note_state(const double *st_host, const double *cs_host, int k, fs_pcg_info *info);
+// ---- fs_mscg's steps (fs_mscg; fs_dist_mscg on every rank, on whole vectors or on the rank's slice).  ms: kMscgStateDoubles, st
+// and the sums as above; X: m vectors ldx apart, P: sh.nslots directions ldp apart, each of n doubles
+constexpr int kMscgStateDoubles = FS_MSCG_MAX_SHIFTS * 16;
+struct MscgSigma { double v[FS_MSCG_MAX_SHIFTS]; };
+// what the host picks: base = the smallest lambda, sigma_i = lambda[i] - base, nslots = the shifts with sigma != 0
+struct MscgShifts { double base; MscgSigma sg; int nslots; };
+int mscg_args_ok(const char *who, int F, int64_t ldx, int m, const double *lambda, double tol);   // FS_ERR_ARG in `who`'s name, before anything is done
+MscgShifts mscg_shifts(int m, const double *lambda);
+// the scalar step behind a sum: start (b.b), S1 (q.p: alpha, the a_i), S2 (r.r: converged?  beta, freezes, the list)
+enum MscgStep { kMscgStart, kMscgS1, kMscgS2 };
+struct MscgScalars { double *ms; int m; double tol; const MscgShifts *sh; };        // what the scalar steps work on besides st[]
+int mscg_dev_init(int n, const double *b, double *r, double *p, double *X, long long ldx, double *P, long long ldp, const CgSums &S,
+                  const MscgScalars &K, hipStream_t s);                          // x_i = 0, r = p = P_i = b; b.b: start
+int mscg_dev_shift_dot(int F, double base, const double *p, double *q, const CgSums &S, const MscgScalars &K, hipStream_t s);   // q += base p; q.p: S1
+int mscg_dev_update(int n, double *r, const double *p, const double *q, double *X, long long ldx, const double *P, long long ldp,
+                    const CgSums &S, const MscgScalars &K, hipStream_t s);       // r, the live x_i; r.r: S2
+int mscg_dev_direction(int n, double *p, const double *r, double *P, long long ldp, const double *st, const double *ms, hipStream_t s);
+// everything of an iteration behind q = A'(A p) on whole vectors: shift_dot, update, direction
+int mscg_dev_steps(int n, double base, double *r, double *p, double *q, double *X, long long ldx, double *P, long long ldp, const CgSums &S,
+                   const MscgScalars &K, hipStream_t s);
+// the sums of every rank's slice, gathered: one per rank, added in rank order (stage 2's tree), then the scalar step
+int mscg_dev_final(MscgStep step, const double *partials, int count, double *red_out, double *st, const MscgScalars &K, hipStream_t s);
+bool mscg_same_outcome(const double *ms_a, const double *ms_b, int m);           // {live, converged, count} of every shift agree
+// the final st[] and ms[] (m shifts) on the host: kept for the debug getters, info (m entries or NULL) filled
+void mscg_note_state(const double *st_host, const double *ms_host, int m, fs_pcg_info *info);
 // the final st[] of a solve, kCgStateDoubles doubles copied back to the host: kept for the calling thread (fs_debug_last_cg_state)
 void note_cg_state(const double *st_host);
 // the host's view of a running solve: {done, iterations} of the two most recent iterations, in pinned memory

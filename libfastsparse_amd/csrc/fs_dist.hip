@@ -300,6 +300,15 @@ struct PnWork {
   std::vector<double *> sol, r, b, dinv, part, cs, st;
 };
 
+// fs_dist_mscg's own vectors, kept like CgWork: the x_i (X, room for m of them) and the directions P_i of the shifts with sigma != 0
+// (P, room for nslots), whole or the rank's slice, ld doubles apart; ms: the per-shift array.  r, b, p, q and the sums are CgWork's
+struct MsWork {
+  int F = 0, m = 0, nslots = 0;
+  long long ld = 0;
+  RankBuffers mem;
+  std::vector<double *> X, P, ms;
+};
+
 // k row-major columns on the sharded matrix (fs_dist_spmm, fs_dist_cg2): the replicated X / Y / Z, the shards' local outputs, the
 // padded receive buffer (one, for both sides), the unpack tables and the work vectors of the block solver, per rank; one plan per
 // side, its cuts from fs_spmm_part_rows (the one-sweep plan of k = 2, 4 is cut like the single-vector pair)
@@ -330,6 +339,7 @@ struct fs_dist_matrix_s {
   size_t pin_doubles = 0;
   CgWork cg;
   PnWork pn;
+  MsWork ms;
   KWork kw;
   std::mutex lock;                    // products on one matrix are serialised (x, y, z and the part buffers are per matrix)
 };
@@ -351,6 +361,7 @@ void free_side(fs_dist_t D, DistSide &S)
 void free_cg(fs_dist_t D, CgWork &W) { W.mem.release(D); W = CgWork(); }
 void free_k(fs_dist_t D, KWork &W) { W.mem.release(D); W = KWork(); }
 void free_pn(fs_dist_t D, PnWork &W) { W.mem.release(D); W = PnWork(); }
+void free_ms(fs_dist_t D, MsWork &W) { W.mem.release(D); W = MsWork(); }
 
 // row cuts with (almost) equal numbers of non-zeros: bounds[r] = first row whose row_ptr is >= r/n of nnz -- the cut
 // libfastsparse_amd/dist.py nnz_balanced_partition makes, essential for power-law matrices (BASELINE config 5)
@@ -1009,6 +1020,7 @@ void fs_dist_matrix_destroy(fs_dist_matrix_t M)
   (void)dist_sync(M->D);
   free_cg(M->D, M->cg);
   free_pn(M->D, M->pn);
+  free_ms(M->D, M->ms);
   free_k(M->D, M->kw);
   for (size_t r = 0; r < (size_t)M->D->n; ++r) {
     (void)hipSetDevice(M->D->dev[r]);
@@ -1444,7 +1456,7 @@ int fs_dist_swap_xy(fs_dist_matrix_t M)
   return FS_OK;
 }
 
-// ---- the CG solvers on the row-sharded matrix: fs_dist_cg, fs_dist_pcg, fs_dist_pcgn, fs_dist_cg2 ---------------------------
+// ---- the CG solvers on the row-sharded matrix: fs_dist_cg, fs_dist_pcg, fs_dist_pcgn, fs_dist_mscg, fs_dist_cg2 ---------------------------
 // Everything of a solve is resident and the scalars of the iteration live on the devices (fs_cg.hip's launchers); per iteration
 // y = A p and q = A' y.  EVERY rank decides convergence for itself and the host compares the flags of all of them one iteration
 // behind: a disagreement (which identical arithmetic rules out, and a faulty device or exchange does not) is an error return,
@@ -1452,9 +1464,9 @@ int fs_dist_swap_xy(fs_dist_matrix_t M)
 // 0.  Work vectors are kept on the handle between solves.  A solve CLOBBERS fs_dist_x / fs_dist_y / fs_dist_z of the handle and
 // writes the caller's x once, at the end: whatever fails before leaves it as it was.
 //
-// DistSolve is the host frame the four share, the counterpart of CgSolve in fs_cg.hip: open() (the transpose is there, both
+// DistSolve is the host frame the five share, the counterpart of CgSolve in fs_cg.hip: open() (the transpose is there, both
 // locks, the caller's device kept, fixed-order products, one set of host-visible flags per rank), stage() (the caller's vectors
-// onto the ranks), iterate() and finish() (the agreed final state, then x to the caller).  A solver brings its argument checks,
+// onto the ranks), iterate() and finish() (settle(): the agreed final state; then store(): x to the caller).  A solver brings its argument checks,
 // its work space (st: every rank's st[]), its start and what an iteration enqueues.
 enum { kRanksGoOn = 0, kRanksStopped = 1, kRanksDisagree = 2 };
 struct DistSolve {
@@ -1529,9 +1541,8 @@ struct DistSolve {
     }
     return FS_OK;
   }
-  // every rank's final {done, iterations} must agree as well; rank 0's final st[] is kept for fs_debug_last_cg_state.  Then x:
-  // count doubles from rank 0's sol, or (slices) every rank's rows of A' from its own
-  int finish(double *x, const std::vector<double *> &sol, size_t count, bool slices = false)
+  // every rank's final {done, iterations} must agree as well; rank 0's final st[] is kept for fs_debug_last_cg_state
+  int settle()
   {
     if (int rc = dist_sync(D)) return rc;
     if (seen == kRanksDisagree) return FS_ERR_HIP;
@@ -1550,15 +1561,26 @@ struct DistSolve {
     FS_HIP(hipMemcpy(st0, (*st)[0], sizeof(st0), hipMemcpyDeviceToHost));
     fs::note_cg_state(st0);
     iterations = (int)fin0[1];
-    if (vector_device(x) >= 0)
-      if (int rc = wait_for_caller(vector_device(x))) return rc;
-    if (!slices)
-      if (int rc = vec_store(M, 0, x, sol[0], count)) return rc;
-    for (int d = 0; slices && d < n; ++d) {
+    return FS_OK;
+  }
+  // one vector to the caller, asynchronously: count doubles from rank 0's sol + at, or (slices) every rank's rows of A' from its own
+  int store(double *x, const std::vector<double *> &sol, size_t at, size_t count, bool slices)
+  {
+    if (!slices) return vec_store(M, 0, x, sol[0] + at, count);
+    for (int d = 0; d < n; ++d) {
       const int lo = M->t.bounds[(size_t)d], rows = M->t.bounds[(size_t)d + 1] - lo;
       if (rows > 0)
-        if (int rc = vec_store(M, d, x + lo, sol[(size_t)d], (size_t)rows)) return rc;
+        if (int rc = vec_store(M, d, x + lo, sol[(size_t)d] + at, (size_t)rows)) return rc;
     }
+    return FS_OK;
+  }
+  // the agreed final state, then x
+  int finish(double *x, const std::vector<double *> &sol, size_t count, bool slices = false)
+  {
+    if (int rc = settle()) return rc;
+    if (vector_device(x) >= 0)
+      if (int rc = wait_for_caller(vector_device(x))) return rc;
+    if (int rc = store(x, sol, 0, count, slices)) return rc;
     return dist_sync(D);
   }
 };
@@ -1600,6 +1622,14 @@ struct SliceSums {
   }
   int combine(fs::CgStep step, double arg, int nv)
   {
+    const int n = M->D->n;
+    return combine(nv, [&](int d, const double *all, double *red_out) {
+      return fs::cg_dev_final(step, all, n, red_out, M->cg.st[(size_t)d], arg, M->D->stream[d], nv);
+    });
+  }
+  // final(d, the n x nv gathered values on rank d, where the finished sums go): the scalar step of rank d
+  int combine(int nv, const std::function<int(int, const double *, double *)> &final)
+  {
     fs_dist_t D = M->D;
     const int n = D->n;
     CgWork &W = M->cg;
@@ -1613,9 +1643,7 @@ struct SliceSums {
           return FS_OK;
         })) return rc;
     if (int rc = exchange_equal(D, from, W.redall, (size_t)nv, D->stream, ready)) return rc;
-    if (int rc = each_rank(D, false, [&](int d) {
-          return fs::cg_dev_final(step, W.redall[(size_t)d], n, W.red[(size_t)d] + 2 * kCgSendDoubles, W.st[(size_t)d], arg, D->stream[d], nv);
-        })) return rc;
+    if (int rc = each_rank(D, false, [&](int d) { return final(d, W.redall[(size_t)d], W.red[(size_t)d] + 2 * kCgSendDoubles); })) return rc;
     slot ^= 1;
     return FS_OK;
   }
@@ -1894,6 +1922,123 @@ int fs_dist_pcgn(fs_dist_matrix_t M, double *X, const double *B, int k, double l
   FS_HIP(hipSetDevice(D->dev[0]));
   FS_HIP(hipMemcpy(cs0, W.cs[0], sizeof(double) * (size_t)k * (fs::kPcgnStateDoubles / FS_PCGN_MAX_RHS), hipMemcpyDeviceToHost));
   fs::pcgn_note_state(f.st0, cs0, k, info);
+  return FS_OK;
+}
+
+// fs_dist_mscg's vectors on the handle: room for m x_i and nslots P_i of ld doubles each and the per-shift array, per rank.  Kept
+// between solves; re-made when a solve needs more vectors or a longer one than they hold
+static int ensure_ms_work(fs_dist_matrix_t M, int m, int nslots, long long ld)
+{
+  fs_dist_t D = M->D;
+  MsWork &W = M->ms;
+  if (W.mem.ready && W.F == M->ncol && W.m >= m && W.nslots >= nslots && W.ld >= ld) return FS_OK;
+  if (int rc = dist_sync(D)) return rc;
+  free_ms(D, W);
+  W.F = M->ncol; W.m = m; W.nslots = nslots; W.ld = ld;
+  return W.mem.fill(D, [&](int d) -> int {
+    if (int rc2 = W.mem.get(d, W.X, (size_t)ld * (size_t)m)) return rc2;
+    if (int rc2 = W.mem.get(d, W.P, (size_t)ld * (size_t)(nslots ? nslots : 1))) return rc2;
+    return W.mem.get(d, W.ms, (size_t)fs::kMscgStateDoubles);
+  });
+}
+
+// fs_mscg across the ranks; the schemes are fs_dist_cg's (option "dist_cg_scheme"):
+//   0 "replicate"  every rank holds whole r, p, q, the m x_i and the P_i and launches fs_mscg's own kernels on them (mscg_dev_*):
+//                  both products carry their all-gather, no exchange for the sums.
+//   1 "gather"     rank r keeps its slice -- the rows of A' it owns -- of r, p, q, every x_i and every P_i.  The x_i and P_i never
+//                  leave their rank: only p enters a product.  q_r = A'_r y is the rank's own shard; q.p and r.r are the slice tree
+//                  of fs_dist_cg (SliceSums), S1 and S2 run on every rank over the N gathered values; the new p is gathered.  The
+//                  first p is b, which every rank holds whole after staging.
+// The caller's X is written once, at the end, after every rank's {done, iterations} and per-shift {live, converged, count} agreed.
+int fs_dist_mscg(fs_dist_matrix_t M, double *X, int64_t ldx, const double *b, int m, const double *lambda, double tol, int max_iter,
+                 fs_pcg_info *info)
+{
+  if (!M || !X || !b || !lambda) { fs::set_error("fs_dist_mscg: NULL argument"); return FS_ERR_ARG; }
+  if (int rc = fs::mscg_args_ok("fs_dist_mscg", M->ncol, ldx, m, lambda, tol)) return rc;
+  DistSolve f{"fs_dist_mscg", M};
+  if (int rc = f.open("call fs_dist_matrix_build_transpose first")) return rc;
+  fs_dist_t D = f.D;
+  const int F = f.F, n = f.n;
+  const bool gather = fs::options().dist_cg_scheme == 1 && n > 1;
+  const fs::MscgShifts sh = fs::mscg_shifts(m, lambda);
+  const int cap = max_iter > 0 ? max_iter : F;               // cg.h:55
+  DistSide &T = M->t;
+  auto lo_of = [&](int d) { return gather ? T.bounds[(size_t)d] : 0; };
+  auto rows_of = [&](int d) { return gather ? T.bounds[(size_t)d + 1] - T.bounds[(size_t)d] : F; };
+  int longest = 1;                                           // of the vectors a rank keeps: every x_i and P_i 16-byte aligned
+  for (int d = 0; d < n; ++d) longest = std::max(longest, rows_of(d));
+  if (int rc = ensure_cg_work(M)) return rc;
+  if (int rc = ensure_ms_work(M, m, sh.nslots, ((long long)longest + 1) & ~1LL)) return rc;
+  CgWork &W = M->cg;
+  MsWork &S = M->ms;
+  const long long ld = S.ld;
+  f.st = &W.st;
+  // a rank works on whole vectors or on its slice; q and p are the handle's z and x (whole) or the rank's slice buffers
+  const std::vector<double *> &vq = gather ? W.q : M->z, &vp = gather ? W.p : M->x;
+  auto scalars_of = [&](int d) { return fs::MscgScalars{S.ms[(size_t)d], m, tol, &sh}; };
+  if (int rc = f.stage(W.b, b, (size_t)F)) return rc;
+  SliceSums sums{M};
+  if (int rc = each_rank(D, false, [&](int d) -> int {       // the init kernel writes p itself: whole into x, or the slice
+        if (gather && F > 0)                                 // the first product reads the whole p = b
+          FS_HIP(hipMemcpyAsync(M->x[(size_t)d], W.b[(size_t)d], sizeof(double) * (size_t)F, hipMemcpyDeviceToDevice, D->stream[d]));
+        return fs::mscg_dev_init(rows_of(d), W.b[(size_t)d] + lo_of(d), W.r[(size_t)d], vp[(size_t)d], S.X[(size_t)d], ld, S.P[(size_t)d], ld,
+                                 sums.of(d, gather), scalars_of(d), D->stream[d]);
+      })) return rc;
+  auto final_of = [&](fs::MscgStep step) {
+    return [&, step](int d, const double *all, double *red_out) {
+      return fs::mscg_dev_final(step, all, n, red_out, W.st[(size_t)d], scalars_of(d), D->stream[d]);
+    };
+  };
+  if (gather)
+    if (int rc = sums.combine(1, final_of(fs::kMscgStart))) return rc;
+  if (!gather) {
+    if (int rc = f.iterate(cap, true, [&]() -> int {
+          if (int rc2 = dist_product(M, false, 1, M->x, M->y)) return rc2;     // y = A p
+          return dist_product(M, true, 1, M->y, M->z);                         // q = A' y
+        }, [&](int d) {
+          return fs::mscg_dev_steps(F, sh.base, W.r[(size_t)d], M->x[(size_t)d], M->z[(size_t)d], S.X[(size_t)d], ld, S.P[(size_t)d], ld,
+                                    sums.of(d, false), scalars_of(d), D->stream[d]);
+        })) return rc;
+  } else {
+    if (int rc = f.iterate(cap, true, [&]() -> int {
+          if (int rc2 = dist_product(M, false, 1, M->x, M->y)) return rc2;     // y = A p
+          if (int rc2 = each_rank(D, false, [&](int d) -> int {
+                if (rows_of(d) > 0)
+                  if (int rc3 = fs_spmv(T.shard[(size_t)d], vq[(size_t)d], M->y[(size_t)d], D->stream[d])) return rc3;
+                return fs::mscg_dev_shift_dot(rows_of(d), sh.base, vp[(size_t)d], vq[(size_t)d], sums.of(d, true), scalars_of(d), D->stream[d]);
+              })) return rc2;
+          if (int rc2 = sums.combine(1, final_of(fs::kMscgS1))) return rc2;     // alpha, the a_i
+          if (int rc2 = each_rank(D, false, [&](int d) {
+                return fs::mscg_dev_update(rows_of(d), W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d], S.X[(size_t)d], ld, S.P[(size_t)d], ld,
+                                           sums.of(d, true), scalars_of(d), D->stream[d]);
+              })) return rc2;
+          if (int rc2 = sums.combine(1, final_of(fs::kMscgS2))) return rc2;     // converged?  beta, freezes
+          if (int rc2 = each_rank(D, false, [&](int d) {
+                return fs::mscg_dev_direction(rows_of(d), vp[(size_t)d], W.r[(size_t)d], S.P[(size_t)d], ld, W.st[(size_t)d], S.ms[(size_t)d],
+                                              D->stream[d]);
+              })) return rc2;
+          return run_gather(D, exchange_of(M, true, 1), W.p, M->x, false);     // the new p on every rank
+        }, [](int) { return FS_OK; })) return rc;
+  }
+  if (int rc = f.settle()) return rc;
+  // every rank froze every shift at the same iteration in the same way: rank 0's per-shift array speaks for all
+  double ms0[fs::kMscgStateDoubles] = {0.0};
+  const size_t nms = (size_t)m * (fs::kMscgStateDoubles / FS_MSCG_MAX_SHIFTS);
+  if (int rc = each_rank(D, false, [&](int d) -> int {
+        double msd[fs::kMscgStateDoubles] = {0.0};
+        FS_HIP(hipMemcpy(d == 0 ? ms0 : msd, S.ms[(size_t)d], sizeof(double) * nms, hipMemcpyDeviceToHost));
+        if (d > 0 && !fs::mscg_same_outcome(msd, ms0, m)) {
+          fs::set_error("fs_dist_mscg: the devices froze the shifts differently (a device or an exchange returned different bits)");
+          return FS_ERR_HIP;
+        }
+        return FS_OK;
+      })) return rc;
+  if (vector_device(X) >= 0)
+    if (int rc = wait_for_caller(vector_device(X))) return rc;
+  for (int i = 0; i < m; ++i)
+    if (int rc = f.store(X + (size_t)i * (size_t)ldx, S.X, (size_t)i * (size_t)ld, (size_t)F, gather)) return rc;
+  if (int rc = dist_sync(D)) return rc;
+  fs::mscg_note_state(f.st0, ms0, m, info);
   return FS_OK;
 }
 
