@@ -48,6 +48,23 @@ Options &options()
   return o;
 }
 
+// every option by name (fs_set_option, fs_get_option); nullptr: no such option
+static int *option_by_name(const char *name)
+{
+  static const struct { const char *name; int Options::*field; } table[] = {
+      {"strict_order", &Options::strict_order}, {"spmv_kernel", &Options::spmv_kernel}, {"tiling", &Options::tiling},
+      {"tile_rows", &Options::tile_rows}, {"tile_cols", &Options::tile_cols}, {"tile_split", &Options::tile_split},
+      {"tiled_flags", &Options::tiled_flags}, {"reproducible", &Options::reproducible}, {"bin_wgs", &Options::bin_wgs},
+      {"bin_flags", &Options::bin_flags}, {"bin_rows", &Options::bin_rows}, {"ldsx", &Options::ldsx}, {"binning", &Options::binning},
+      {"long_rows", &Options::long_rows}, {"long_min_len", &Options::long_min_len}, {"long_geometry", &Options::long_geometry},
+      {"device_build", &Options::device_build}, {"ata_kernel", &Options::ata_kernel}, {"spmm_wide", &Options::spmm_wide},
+      {"spmm_kernel", &Options::spmm_kernel}, {"pcgn_kernel", &Options::pcgn_kernel}, {"cg_fixed_order", &Options::cg_fixed_order},
+      {"release_csr", &Options::release_csr}, {"dist_cg_scheme", &Options::dist_cg_scheme}};
+  for (const auto &e : table)
+    if (!strcmp(name, e.name)) return &(options().*e.field);
+  return nullptr;
+}
+
 // ---- roctx (see fs_common.h) ---------------------------------------------------------------------------------
 namespace {
 struct Roctx {
@@ -95,6 +112,78 @@ static int to_device(T **dst, const T *src, size_t n, int space)
 }  // namespace fs
 
 using fs::set_error;
+
+// ---- what the entry points share ----------------------------------------------------------------------------------------------
+// The side of a handle an entry point works on: A (transposed == 0) or A', which must have been built.  side_or_null is silent
+// (the diagnostics answer FS_ERR_ARG to a NULL handle and to a missing A' alike); side_of, on a handle that is not NULL, says
+// "<who>: call fs_matrix_build_transpose first".
+static fs::DeviceCsr *side_or_null(fs_matrix_t A, int transposed)
+{
+  return !A || (transposed && !A->has_t) ? nullptr : transposed ? &A->at : &A->a;
+}
+
+static int side_of(fs_matrix_t A, int transposed, const char *who, fs::DeviceCsr **a)
+{
+  *a = side_or_null(A, transposed);
+  if (*a) return FS_OK;
+  set_error(std::string(who) + ": call fs_matrix_build_transpose first");
+  return FS_ERR_NO_TRANSPOSE;
+}
+
+// The host-vector path launches on the handle's own non-blocking stream but shares the handle's scratch (product stream of
+// the two-pass copy, sums of cut rows) with the device-vector products, which return right after an asynchronous launch:
+// wait for the stream the last of those went to (a non-blocking stream is not ordered against it, not even the null stream).
+static int order_behind_last(fs_matrix_t A)
+{
+  if (!A->last_async) return FS_OK;
+  A->last_async = false;
+  if (hipStreamSynchronize(A->last_stream) != hipSuccess) {   // e.g. the caller has destroyed that stream since
+    (void)hipGetLastError();
+    FS_HIP(hipDeviceSynchronize());
+  }
+  return FS_OK;
+}
+
+static int check_mul(fs_matrix_t A, const void *y, const void *x, const char *who)
+{
+  if (!A || !y || !x) { set_error(std::string(who) + ": NULL argument"); return FS_ERR_ARG; }
+  return FS_OK;
+}
+
+// The frame of the eight product entry points, in two steps.  product_side, before the lock: NULL arguments, the entry point's
+// own check (`bad`: the text behind "<who>: " when it failed), the side.  product_locked: the lock (products share the handle's
+// scratch); a product on device vectors leaves its stream for order_behind_last, one on host vectors waits there; the launch.
+static int product_side(const char *who, fs_matrix_t A, int transposed, const void *y, const void *x, const char *bad, fs::DeviceCsr **a)
+{
+  if (int rc = check_mul(A, y, x, who)) return rc;
+  if (bad) { set_error(std::string(who) + ": " + bad); return FS_ERR_ARG; }
+  return side_of(A, transposed, who, a);
+}
+
+enum Vectors { kDeviceVectors, kHostVectors };
+
+template <typename Launch>
+static int product_locked(fs_matrix_t A, Vectors where, fs_stream_t stream, Launch launch)
+{
+  std::lock_guard<std::mutex> g(A->lock);
+  if (where == kHostVectors) {
+    if (int rc = order_behind_last(A)) return rc;
+  } else {
+    A->last_stream = (hipStream_t)stream; A->last_async = true;
+  }
+  return launch();
+}
+
+// both steps under the roctx range `who`; launch(a, s): the product on that side
+template <typename Launch>
+static int product(const char *who, fs_matrix_t A, int transposed, const void *y, const void *x, const char *bad, Vectors where,
+                   fs_stream_t stream, Launch launch)
+{
+  FS_RANGE(who);
+  fs::DeviceCsr *a = nullptr;
+  if (int rc = product_side(who, A, transposed, y, x, bad, &a)) return rc;
+  return product_locked(A, where, stream, [&] { return launch(*a, (hipStream_t)stream); });
+}
 
 extern "C" {
 
@@ -147,7 +236,7 @@ int fs_device_synchronize(void)
 static void auto_release(fs::DeviceCsr &A)
 {
   if (!fs::options().release_csr || fs::tl_keep_csr != 0) return;
-  if (fs::spmv_choice(A, fs::options()) < 6) return;
+  if (fs::spmv_reads_plain_csr(A)) return;
   (void)fs::release_plain_csr(A);
 }
 
@@ -155,61 +244,30 @@ int fs_set_option(const char *name, int value)
 {
   if (!name) { set_error("fs_set_option: NULL name"); return FS_ERR_ARG; }
   fs::g_option_epoch.fetch_add(1, std::memory_order_relaxed);
-  if (!strcmp(name, "release_csr")) { fs::options().release_csr = value; return FS_OK; }
-  if (!strcmp(name, "strict_order")) { fs::options().strict_order = value; return FS_OK; }
-  if (!strcmp(name, "spmv_kernel")) { fs::options().spmv_kernel = value; return FS_OK; }
-  if (!strcmp(name, "tiling")) { fs::options().tiling = value; return FS_OK; }
-  if (!strcmp(name, "tile_rows")) { fs::options().tile_rows = value; return FS_OK; }
-  if (!strcmp(name, "tile_cols")) { fs::options().tile_cols = value; return FS_OK; }
-  if (!strcmp(name, "tile_split")) { fs::options().tile_split = value; return FS_OK; }
-  if (!strcmp(name, "tiled_flags")) { fs::options().tiled_flags = value; return FS_OK; }
-  if (!strcmp(name, "reproducible")) { fs::options().reproducible = value; return FS_OK; }
-  if (!strcmp(name, "bin_wgs")) { fs::options().bin_wgs = value; return FS_OK; }
-  if (!strcmp(name, "bin_flags")) { fs::options().bin_flags = value; return FS_OK; }
-  if (!strcmp(name, "bin_rows")) { fs::options().bin_rows = value; return FS_OK; }
-  if (!strcmp(name, "ldsx")) { fs::options().ldsx = value; return FS_OK; }
-  if (!strcmp(name, "binning")) { fs::options().binning = value; return FS_OK; }
-  if (!strcmp(name, "long_rows")) { fs::options().long_rows = value; return FS_OK; }
-  if (!strcmp(name, "long_min_len")) { fs::options().long_min_len = value; return FS_OK; }
-  if (!strcmp(name, "long_geometry")) { fs::options().long_geometry = value; return FS_OK; }
-  if (!strcmp(name, "spmm_kernel")) { fs::options().spmm_kernel = value; return FS_OK; }
-  if (!strcmp(name, "spmm_wide")) { fs::options().spmm_wide = value; return FS_OK; }
-  if (!strcmp(name, "ata_kernel")) { fs::options().ata_kernel = value; return FS_OK; }
-  if (!strcmp(name, "device_build")) { fs::options().device_build = value; return FS_OK; }
-  if (!strcmp(name, "pcgn_kernel")) { fs::options().pcgn_kernel = value; return FS_OK; }
-  if (!strcmp(name, "cg_fixed_order")) { fs::options().cg_fixed_order = value; return FS_OK; }
-  if (!strcmp(name, "dist_cg_scheme")) { fs::options().dist_cg_scheme = value; return FS_OK; }
-  set_error(std::string("fs_set_option: unknown option ") + name);
-  return FS_ERR_ARG;
+  int *slot = fs::option_by_name(name);
+  if (!slot) { set_error(std::string("fs_set_option: unknown option ") + name); return FS_ERR_ARG; }
+  *slot = value;
+  return FS_OK;
 }
 
 int fs_get_option(const char *name)
 {
-  if (name && !strcmp(name, "strict_order")) return fs::options().strict_order;
-  if (name && !strcmp(name, "spmv_kernel")) return fs::options().spmv_kernel;
-  if (name && !strcmp(name, "tiling")) return fs::options().tiling;
-  if (name && !strcmp(name, "tile_rows")) return fs::options().tile_rows;
-  if (name && !strcmp(name, "tile_cols")) return fs::options().tile_cols;
-  if (name && !strcmp(name, "tile_split")) return fs::options().tile_split;
-  if (name && !strcmp(name, "binning")) return fs::options().binning;
-  if (name && !strcmp(name, "long_rows")) return fs::options().long_rows;
-  if (name && !strcmp(name, "ldsx")) return fs::options().ldsx;
-  if (name && !strcmp(name, "reproducible")) return fs::options().reproducible;
-  if (name && !strcmp(name, "spmm_kernel")) return fs::options().spmm_kernel;
-  if (name && !strcmp(name, "spmm_wide")) return fs::options().spmm_wide;
-  if (name && !strcmp(name, "ata_kernel")) return fs::options().ata_kernel;
-  if (name && !strcmp(name, "device_build")) return fs::options().device_build;
-  if (name && !strcmp(name, "pcgn_kernel")) return fs::options().pcgn_kernel;
-  if (name && !strcmp(name, "cg_fixed_order")) return fs::options().cg_fixed_order;
-  if (name && !strcmp(name, "dist_cg_scheme")) return fs::options().dist_cg_scheme;
-  if (name && !strcmp(name, "release_csr")) return fs::options().release_csr;
-  if (name && !strcmp(name, "tiled_flags")) return fs::options().tiled_flags;
-  if (name && !strcmp(name, "bin_wgs")) return fs::options().bin_wgs;
-  if (name && !strcmp(name, "bin_flags")) return fs::options().bin_flags;
-  if (name && !strcmp(name, "bin_rows")) return fs::options().bin_rows;
-  if (name && !strcmp(name, "long_min_len")) return fs::options().long_min_len;
-  if (name && !strcmp(name, "long_geometry")) return fs::options().long_geometry;
-  return FS_ERR_ARG;
+  const int *slot = name ? fs::option_by_name(name) : nullptr;
+  return slot ? *slot : FS_ERR_ARG;
+}
+
+// row_ptr / cols / vals of a handle (nrow and nnz set): the caller's device arrays as they are (`borrow`; cols and vals 16-byte
+// aligned), or copies of them
+static int adopt_or_upload(fs::DeviceCsr &a, const int *row_ptr, const int *cols, const double *vals, int space, int borrow)
+{
+  a.owns = !(space == FS_DEVICE && borrow && fs::aligned16(cols) && (!vals || fs::aligned16(vals)));
+  if (!a.owns) {
+    a.row_ptr = const_cast<int *>(row_ptr); a.cols = const_cast<int *>(cols); a.vals = const_cast<double *>(vals);
+    return FS_OK;
+  }
+  if (int rc = fs::to_device(&a.row_ptr, row_ptr, (size_t)a.nrow + 1, space)) return rc;
+  if (int rc = fs::to_device(&a.cols, cols, (size_t)a.nnz, space)) return rc;
+  return vals ? fs::to_device(&a.vals, vals, (size_t)a.nnz, space) : FS_OK;
 }
 
 fs_matrix_t fs_csr_create(int nrow, int ncol, int64_t nnz, const int *row_ptr, const int *cols, const double *vals,
@@ -224,19 +282,8 @@ fs_matrix_t fs_csr_create(int nrow, int ncol, int64_t nnz, const int *row_ptr, c
   if (hipGetDevice(&M->device) != hipSuccess) { set_error("fs_csr_create: no HIP device"); delete M; return nullptr; }
   fs::DeviceCsr &A = M->a;
   A.nrow = nrow; A.ncol = ncol; A.nnz = nnz;
-  int rc = FS_OK;
   const auto t0 = std::chrono::steady_clock::now();
-  if (space == FS_DEVICE && borrow && fs::aligned16(cols) && (!vals || fs::aligned16(vals))) {
-    A.owns = false;
-    A.row_ptr = const_cast<int *>(row_ptr);
-    A.cols = const_cast<int *>(cols);
-    A.vals = const_cast<double *>(vals);
-  } else {
-    A.owns = true;
-    rc = fs::to_device(&A.row_ptr, row_ptr, (size_t)nrow + 1, space);
-    if (!rc) rc = fs::to_device(&A.cols, cols, (size_t)nnz, space);
-    if (!rc && vals) rc = fs::to_device(&A.vals, vals, (size_t)nnz, space);
-  }
+  int rc = adopt_or_upload(A, row_ptr, cols, vals, space, borrow);
   if (!rc) rc = fs::validate_indices(nrow, ncol, nnz, A.row_ptr, nullptr, A.cols, nullptr);
   const float up_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();   // (validation ends in a synchronisation)
   if (!rc) rc = fs::build_schedule(A, nullptr);
@@ -310,23 +357,23 @@ int fs_matrix_has_transpose(fs_matrix_t A) { return A && A->has_t; }
 
 int fs_matrix_spmv_kernel(fs_matrix_t A, int transposed)
 {
-  if (!A || (transposed && !A->has_t)) return FS_ERR_ARG;
-  return fs::spmv_choice(transposed ? A->at : A->a, fs::options());
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  return a ? fs::spmv_choice(*a, fs::options()) : FS_ERR_ARG;
 }
 
 int fs_matrix_candidate_ms(fs_matrix_t A, int transposed, float *ms4)
 {
-  if (!A || !ms4 || (transposed && !A->has_t)) return FS_ERR_ARG;
-  const fs::DeviceCsr &a = transposed ? A->at : A->a;
-  for (int i = 0; i < 4; ++i) ms4[i] = a.candidate_ms[i];
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a || !ms4) return FS_ERR_ARG;
+  for (int i = 0; i < 4; ++i) ms4[i] = a->candidate_ms[i];
   return FS_OK;
 }
 
 int fs_matrix_build_ms(fs_matrix_t A, int transposed, float *ms8)
 {
-  if (!A || !ms8 || (transposed && !A->has_t)) return FS_ERR_ARG;
-  const fs::DeviceCsr &a = transposed ? A->at : A->a;
-  for (int i = 0; i < 8; ++i) ms8[i] = a.build_ms[i];
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a || !ms8) return FS_ERR_ARG;
+  for (int i = 0; i < 8; ++i) ms8[i] = a->build_ms[i];
   return FS_OK;
 }
 
@@ -344,67 +391,79 @@ int64_t fs_matrix_algorithmic_bytes(fs_matrix_t A, int k)
 int fs_matrix_download(fs_matrix_t A, int transposed, int *row_ptr, int *cols, double *vals)
 {
   if (!A) { set_error("fs_matrix_download: NULL handle"); return FS_ERR_ARG; }
-  if (transposed && !A->has_t) { set_error("fs_matrix_download: transpose not built"); return FS_ERR_NO_TRANSPOSE; }
-  const fs::DeviceCsr &a = transposed ? A->at : A->a;
-  if (int rc = fs::need_plain_csr(a, "fs_matrix_download")) return rc;
-  if (row_ptr) FS_HIP(hipMemcpy(row_ptr, a.row_ptr, sizeof(int) * ((size_t)a.nrow + 1), hipMemcpyDeviceToHost));
-  if (cols && a.nnz) FS_HIP(hipMemcpy(cols, a.cols, sizeof(int) * (size_t)a.nnz, hipMemcpyDeviceToHost));
-  if (vals && a.vals && a.nnz) FS_HIP(hipMemcpy(vals, a.vals, sizeof(double) * (size_t)a.nnz, hipMemcpyDeviceToHost));
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a) { set_error("fs_matrix_download: transpose not built"); return FS_ERR_NO_TRANSPOSE; }
+  if (int rc = fs::need_plain_csr(*a, "fs_matrix_download")) return rc;
+  if (row_ptr) FS_HIP(hipMemcpy(row_ptr, a->row_ptr, sizeof(int) * ((size_t)a->nrow + 1), hipMemcpyDeviceToHost));
+  if (cols && a->nnz) FS_HIP(hipMemcpy(cols, a->cols, sizeof(int) * (size_t)a->nnz, hipMemcpyDeviceToHost));
+  if (vals && a->vals && a->nnz) FS_HIP(hipMemcpy(vals, a->vals, sizeof(double) * (size_t)a->nnz, hipMemcpyDeviceToHost));
   return FS_OK;
 }
 
-static int check_mul(fs_matrix_t A, const void *y, const void *x, const char *who)
+// ---- the products: each is the frame around its launcher; the _t entry points are the transposed case -------------------------
+static int spmv_entry(const char *who, fs_matrix_t A, int transposed, double *y, const double *x, fs_stream_t stream)
 {
-  if (!A || !y || !x) { set_error(std::string(who) + ": NULL argument"); return FS_ERR_ARG; }
-  return FS_OK;
+  return product(who, A, transposed, y, x, nullptr, kDeviceVectors, stream,
+                 [&](fs::DeviceCsr &a, hipStream_t s) { return fs::launch_spmv(a, y, x, s); });
 }
+int fs_spmv(fs_matrix_t A, double *y, const double *x, fs_stream_t stream) { return spmv_entry("fs_spmv", A, 0, y, x, stream); }
+int fs_spmv_t(fs_matrix_t A, double *y, const double *x, fs_stream_t stream) { return spmv_entry("fs_spmv_t", A, 1, y, x, stream); }
 
-int fs_spmv(fs_matrix_t A, double *y, const double *x, fs_stream_t stream)
+// (k == 1: the single-vector product under its own name, once the arguments stand)
+static int spmm_entry(const char *who, fs_matrix_t A, int transposed, double *Y, const double *X, int k, fs_stream_t stream)
 {
-  FS_RANGE("fs_spmv");
-  if (int rc = check_mul(A, y, x, "fs_spmv")) return rc;
-  std::lock_guard<std::mutex> g(A->lock);
-  A->last_stream = (hipStream_t)stream; A->last_async = true;
-  return fs::launch_spmv(A->a, y, x, (hipStream_t)stream);
+  fs::DeviceCsr *a = nullptr;
+  if (int rc = product_side(who, A, transposed, Y, X, k < 1 ? "k < 1" : nullptr, &a)) return rc;
+  if (k == 1) return transposed ? fs_spmv_t(A, Y, X, stream) : fs_spmv(A, Y, X, stream);
+  FS_RANGE(who);
+  return product_locked(A, kDeviceVectors, stream, [&] { return fs::launch_spmm(*a, Y, X, k, (hipStream_t)stream); });
 }
+int fs_spmm(fs_matrix_t A, double *Y, const double *X, int k, fs_stream_t stream) { return spmm_entry("fs_spmm", A, 0, Y, X, k, stream); }
+int fs_spmm_t(fs_matrix_t A, double *Y, const double *X, int k, fs_stream_t stream) { return spmm_entry("fs_spmm_t", A, 1, Y, X, k, stream); }
+
+// products with HOST vectors: synchronous; the copies of x and y overlap the kernels where the kept copy allows it
+static int host_entry(const char *who, fs_matrix_t A, int transposed, double *y_host, const double *x_host)
+{
+  return product(who, A, transposed, y_host, x_host, nullptr, kHostVectors, nullptr,
+                 [&](fs::DeviceCsr &a, hipStream_t) { return fs::spmv_host_vectors(a, A->pipe, y_host, x_host); });
+}
+int fs_spmv_host(fs_matrix_t A, double *y_host, const double *x_host) { return host_entry("fs_spmv_host", A, 0, y_host, x_host); }
+int fs_spmv_t_host(fs_matrix_t A, double *y_host, const double *x_host) { return host_entry("fs_spmv_t_host", A, 1, y_host, x_host); }
 
 // y = A x (transposed != 0: A' x) in nparts parts: see include/fastsparse_hip.h and launch_spmv_part
 int fs_spmv_part_rows(fs_matrix_t A, int transposed, int nparts, int *rows)
 {
   if (!A || !rows || nparts < 1 || nparts > 64) { set_error("fs_spmv_part_rows: bad argument (1 <= nparts <= 64)"); return FS_ERR_ARG; }
-  if (transposed && !A->has_t) { set_error("fs_spmv_part_rows: call fs_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
+  fs::DeviceCsr *a = nullptr;
+  if (int rc = side_of(A, transposed, "fs_spmv_part_rows", &a)) return rc;
   std::lock_guard<std::mutex> g(A->lock);
   const int *r = nullptr;
-  if (int rc = fs::spmv_part_bounds(transposed ? A->at : A->a, nparts, &r, nullptr)) return rc;
+  if (int rc = fs::spmv_part_bounds(*a, nparts, &r, nullptr)) return rc;
   for (int p = 0; p <= nparts; ++p) rows[p] = r[p];
   return FS_OK;
 }
 
 int fs_spmv_part(fs_matrix_t A, int transposed, double *y, const double *x, int part, int nparts, fs_stream_t stream)
 {
-  FS_RANGE("fs_spmv_part");
-  if (int rc = check_mul(A, y, x, "fs_spmv_part")) return rc;
-  if (nparts < 1 || nparts > 64 || part < 0 || part >= nparts) { set_error("fs_spmv_part: bad part"); return FS_ERR_ARG; }
-  if (transposed && !A->has_t) { set_error("fs_spmv_part: call fs_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
-  std::lock_guard<std::mutex> g(A->lock);
-  A->last_stream = (hipStream_t)stream; A->last_async = true;
-  return fs::launch_spmv_part(transposed ? A->at : A->a, y, x, part, nparts, (hipStream_t)stream);
+  const bool bad = nparts < 1 || nparts > 64 || part < 0 || part >= nparts;
+  return product("fs_spmv_part", A, transposed, y, x, bad ? "bad part" : nullptr, kDeviceVectors, stream,
+                 [&](fs::DeviceCsr &a, hipStream_t s) { return fs::launch_spmv_part(a, y, x, part, nparts, s); });
 }
 
 int fs_spmm_part_rows(fs_matrix_t A, int transposed, int k, int nparts, int *rows)
 {
   if (!A || !rows || k < 1 || nparts < 1 || nparts > 64) { set_error("fs_spmm_part_rows: bad argument"); return FS_ERR_ARG; }
   if (k == 1) return fs_spmv_part_rows(A, transposed, nparts, rows);
-  if (transposed && !A->has_t) { set_error("fs_spmm_part_rows: call fs_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
+  fs::DeviceCsr *a = nullptr;
+  if (int rc = side_of(A, transposed, "fs_spmm_part_rows", &a)) return rc;
   std::lock_guard<std::mutex> g(A->lock);
-  fs::DeviceCsr &a = transposed ? A->at : A->a;
   const int *r = nullptr;
   if (k == 2 || k == 4) {
-    if (int rc = fs::spmm_part_bounds(a, k, nparts, &r, nullptr, nullptr)) return rc;
+    if (int rc = fs::spmm_part_bounds(*a, k, nparts, &r, nullptr, nullptr)) return rc;
     for (int p = 0; p <= nparts; ++p) rows[p] = r[p];
   } else {
     rows[0] = 0;
-    for (int p = 1; p <= nparts; ++p) rows[p] = a.nrow;
+    for (int p = 1; p <= nparts; ++p) rows[p] = a->nrow;
   }
   return FS_OK;
 }
@@ -412,13 +471,9 @@ int fs_spmm_part_rows(fs_matrix_t A, int transposed, int k, int nparts, int *row
 int fs_spmm_part(fs_matrix_t A, int transposed, double *Y, const double *X, int k, int part, int nparts, fs_stream_t stream)
 {
   if (k == 1) return fs_spmv_part(A, transposed, Y, X, part, nparts, stream);
-  FS_RANGE("fs_spmm_part");
-  if (int rc = check_mul(A, Y, X, "fs_spmm_part")) return rc;
-  if (k < 1 || nparts < 1 || nparts > 64 || part < 0 || part >= nparts) { set_error("fs_spmm_part: bad argument"); return FS_ERR_ARG; }
-  if (transposed && !A->has_t) { set_error("fs_spmm_part: call fs_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
-  std::lock_guard<std::mutex> g(A->lock);
-  A->last_stream = (hipStream_t)stream; A->last_async = true;
-  return fs::launch_spmm_part(transposed ? A->at : A->a, Y, X, k, part, nparts, (hipStream_t)stream);
+  const bool bad = k < 1 || nparts < 1 || nparts > 64 || part < 0 || part >= nparts;
+  return product("fs_spmm_part", A, transposed, Y, X, bad ? "bad argument" : nullptr, kDeviceVectors, stream,
+                 [&](fs::DeviceCsr &a, hipStream_t s) { return fs::launch_spmm_part(a, Y, X, k, part, nparts, s); });
 }
 
 int fs_copy_segments(int nseg, const int64_t *table_dev, int64_t max_count, const double *src, double *dst, fs_stream_t stream)
@@ -439,12 +494,12 @@ int fs_debug_last_spmm_wide(void) { return fs::last_spmm_wide(); }
 // sweeps against the row kernel, bit 2 allocate the column-major scratch; 0: nothing left to do
 int fs_debug_spmm_needs(fs_matrix_t A, int k, int transposed)
 {
-  if (!A || k < 1 || (transposed && !A->has_t)) return FS_ERR_ARG;
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a || k < 1) return FS_ERR_ARG;
   std::lock_guard<std::mutex> g(A->lock);
-  const fs::DeviceCsr &a = transposed ? A->at : A->a;
   int needs = 0;
-  if (a.nrow == 0 || a.nnz == 0 || k < 2) return 0;     // prepare_spmm returns before it looks
-  (void)fs::spmm_plan(a, k, &needs);
+  if (a->nrow == 0 || a->nnz == 0 || k < 2) return 0;     // prepare_spmm returns before it looks
+  (void)fs::spmm_plan(*a, k, &needs);
   return needs;
 }
 
@@ -452,9 +507,9 @@ int fs_debug_spmm_needs(fs_matrix_t A, int k, int transposed)
 // share panels (sums go through its scratch vector); FS_ERR_ARG without one
 int fs_debug_tiled_layout(fs_matrix_t A, int transposed)
 {
-  if (!A || (transposed && !A->has_t)) return FS_ERR_ARG;
-  const fs::DeviceCsr &a = transposed ? A->at : A->a;
-  const fs::TiledCsr *T = (a.tiledx && a.tiledx->built) ? a.tiledx : (a.tiled && a.tiled->built) ? a.tiled : nullptr;
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a) return FS_ERR_ARG;
+  const fs::TiledCsr *T = (a->tiledx && a->tiledx->built) ? a->tiledx : (a->tiled && a->tiled->built) ? a->tiled : nullptr;
   if (!T) return FS_ERR_ARG;
   return (T->split ? 1 : 0) | (T->shared ? 2 : 0);
 }
@@ -462,9 +517,9 @@ int fs_debug_tiled_layout(fs_matrix_t A, int transposed)
 // rows taken out of the two-pass copy (LongRows) and their entries incl. padding; 0 / 0 when the copy has none
 int fs_debug_long_rows(fs_matrix_t A, int transposed, int64_t *out2)
 {
-  if (!A || !out2 || (transposed && !A->has_t)) return FS_ERR_ARG;
-  const fs::DeviceCsr &a = transposed ? A->at : A->a;
-  const fs::LongRows *L = (a.binned && a.binned->built) ? a.binned->lr : nullptr;
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a || !out2) return FS_ERR_ARG;
+  const fs::LongRows *L = (a->binned && a->binned->built) ? a->binned->lr : nullptr;
   out2[0] = L ? L->nlong : 0;
   out2[1] = L ? L->n : 0;
   return FS_OK;
@@ -473,10 +528,10 @@ int fs_debug_long_rows(fs_matrix_t A, int transposed, int64_t *out2)
 // 1 when the LDS-staged copy of A (transposed != 0: of A') can give fixed-order sums (TiledCsr::orderable), 0 when not, < 0 without one
 int fs_debug_ldsx_orderable(fs_matrix_t A, int transposed)
 {
-  if (!A || (transposed && !A->has_t)) return FS_ERR_ARG;
-  const fs::DeviceCsr &a = transposed ? A->at : A->a;
-  if (!a.tiledx || !a.tiledx->built) return FS_ERR_ARG;
-  return a.tiledx->orderable ? 1 : 0;
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a) return FS_ERR_ARG;
+  if (!a->tiledx || !a->tiledx->built) return FS_ERR_ARG;
+  return a->tiledx->orderable ? 1 : 0;
 }
 
 // 1 when a product on A (transposed != 0: on A') inside a solver's fixed-order scope (cg_fixed_order) really adds in a fixed order,
@@ -484,23 +539,23 @@ int fs_debug_ldsx_orderable(fs_matrix_t A, int transposed)
 // not bit-identical from run to run; option "reproducible" = 1 forces a fixed-order kernel at the price of speed)
 int fs_debug_fixed_order_honoured(fs_matrix_t A, int transposed)
 {
-  if (!A || (transposed && !A->has_t)) return FS_ERR_ARG;
-  const fs::DeviceCsr &a = transposed ? A->at : A->a;
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a) return FS_ERR_ARG;
   fs::Options o = fs::options();
-  if (fs::spmv_choice(a, o) != 8) return 1;
-  return a.tiledx->orderable ? 1 : 0;
+  if (fs::spmv_choice(*a, o) != fs::kSpmvLdsx) return 1;
+  return a->tiledx->orderable ? 1 : 0;
 }
 
 // chunks of the LDS-staged copy that ever gave up waiting for their turn under fixed-order sums and added out of turn (a wrong order
 // of additions, not a wrong sum): 0 on a healthy run; < 0 without such a copy
 int fs_debug_ldsx_ticket_giveups(fs_matrix_t A, int transposed)
 {
-  if (!A || (transposed && !A->has_t)) return FS_ERR_ARG;
-  const fs::DeviceCsr &a = transposed ? A->at : A->a;
-  if (!a.tiledx || !a.tiledx->built || !a.tiledx->ticket) return FS_ERR_ARG;
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a) return FS_ERR_ARG;
+  if (!a->tiledx || !a->tiledx->built || !a->tiledx->ticket) return FS_ERR_ARG;
   int n = 0;
   FS_HIP(hipDeviceSynchronize());
-  FS_HIP(hipMemcpy(&n, a.tiledx->ticket - 1, sizeof(int), hipMemcpyDeviceToHost));
+  FS_HIP(hipMemcpy(&n, a->tiledx->ticket - 1, sizeof(int), hipMemcpyDeviceToHost));
   return n;
 }
 
@@ -508,10 +563,10 @@ int fs_debug_ldsx_ticket_giveups(fs_matrix_t A, int transposed)
 // (tools/placement_probe.py: identical copies run at different speeds depending on where their arrays land)
 int fs_debug_two_pass_layout(fs_matrix_t A, int transposed, unsigned long long *out8)
 {
-  if (!A || !out8 || (transposed && !A->has_t)) return FS_ERR_ARG;
-  const fs::DeviceCsr &a = transposed ? A->at : A->a;
-  if (!a.binned || !a.binned->built) { set_error("no two-pass copy"); return FS_ERR_ARG; }
-  const fs::BinnedCsr &N = *a.binned;
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a || !out8) return FS_ERR_ARG;
+  if (!a->binned || !a->binned->built) { set_error("no two-pass copy"); return FS_ERR_ARG; }
+  const fs::BinnedCsr &N = *a->binned;
   out8[0] = (unsigned long long)(uintptr_t)N.lcol; out8[1] = (unsigned long long)(uintptr_t)N.vals;
   out8[2] = (unsigned long long)(uintptr_t)N.gdst; out8[3] = (unsigned long long)(uintptr_t)(N.lrow ? (const void *)N.lrow : (const void *)N.lrow8);
   out8[4] = (unsigned long long)(uintptr_t)N.prod; out8[5] = (unsigned long long)N.n; out8[6] = (unsigned long long)N.B;
@@ -523,21 +578,21 @@ int fs_debug_two_pass_layout(fs_matrix_t A, int transposed, unsigned long long *
 // = the dummy entries that walk steps above 255 (diagnostics, not in include/fastsparse_hip.h)
 long long fs_debug_two_pass_rows8(fs_matrix_t A, int transposed)
 {
-  if (!A || (transposed && !A->has_t)) return -1;
-  const fs::DeviceCsr &a = transposed ? A->at : A->a;
-  if (!a.binned || !a.binned->built || !a.binned->lrow8) return -1;
-  return (long long)a.binned->dummies;
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a) return -1;
+  if (!a->binned || !a->binned->built || !a->binned->lrow8) return -1;
+  return (long long)a->binned->dummies;
 }
 
 // one pass of the two-pass pair alone (which = 1: pass 1, x -> the product stream; 2: pass 2, the product stream -> y)
 int fs_debug_two_pass_run(fs_matrix_t A, int transposed, int which, double *y, const double *x, fs_stream_t stream)
 {
-  if (!A || (transposed && !A->has_t)) return FS_ERR_ARG;
-  const fs::DeviceCsr &a = transposed ? A->at : A->a;
-  if (!a.binned || !a.binned->built || a.binned->split || a.binned->lr) { set_error("no plain two-pass copy"); return FS_ERR_ARG; }
-  const fs::BinnedCsr &N = *a.binned;
-  if (which == 1) return fs::launch_expand_groups(a, x, 0u, (unsigned)(N.n >> fs::kBinGroupLog), N.nwg1, (hipStream_t)stream);
-  return fs::launch_reduce_panels(a, y, 0, N.P, (hipStream_t)stream);
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a) return FS_ERR_ARG;
+  if (!a->binned || !a->binned->built || a->binned->split || a->binned->lr) { set_error("no plain two-pass copy"); return FS_ERR_ARG; }
+  const fs::BinnedCsr &N = *a->binned;
+  if (which == 1) return fs::launch_expand_groups(*a, x, 0u, (unsigned)(N.n >> fs::kBinGroupLog), N.nwg1, (hipStream_t)stream);
+  return fs::launch_reduce_panels(*a, y, 0, N.P, (hipStream_t)stream);
 }
 
 #ifdef FS_LAB
@@ -546,10 +601,9 @@ int fs_debug_two_pass_run(fs_matrix_t A, int transposed, int which, double *y, c
 int fs_debug_two_pass_realloc(fs_matrix_t A, int transposed, int which_and_flags)
 {
   if (which_and_flags & 32) {     // all five arrays into ONE fresh block (the old blocks and earlier arenas are dropped, not freed)
-    if (!A || (transposed && !A->has_t)) return FS_ERR_ARG;
-    fs::DeviceCsr &a0 = transposed ? A->at : A->a;
-    if (!a0.binned || !a0.binned->built) return FS_ERR_ARG;
-    fs::BinnedCsr &N0 = *a0.binned;
+    fs::DeviceCsr *a0 = side_or_null(A, transposed);
+    if (!a0 || !a0->binned || !a0->binned->built) return FS_ERR_ARG;
+    fs::BinnedCsr &N0 = *a0->binned;
     void **slots[5] = {(void **)&N0.lcol, (void **)&N0.vals, (void **)&N0.gdst, (void **)&N0.lrow, (void **)&N0.prod};
     const size_t sizes[5] = {(size_t)N0.n * 2, N0.vals ? (size_t)N0.n * 8 : 0, ((size_t)N0.n >> fs::kBinGroupLog) * 4, N0.lrow ? (size_t)N0.n * 2 : 0,
                              (size_t)N0.n * 8 * (size_t)N0.kw};
@@ -573,10 +627,10 @@ int fs_debug_two_pass_realloc(fs_matrix_t A, int transposed, int which_and_flags
   }
   const int which = which_and_flags & 15;
   const bool leak_old = (which_and_flags & 16) != 0;     // the probe keeps the old block allocated (distinct placements) and drops it
-  if (!A || (transposed && !A->has_t)) return FS_ERR_ARG;
-  fs::DeviceCsr &a = transposed ? A->at : A->a;
-  if (!a.binned || !a.binned->built) { set_error("no two-pass copy"); return FS_ERR_ARG; }
-  fs::BinnedCsr &N = *a.binned;
+  fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a) return FS_ERR_ARG;
+  if (!a->binned || !a->binned->built) { set_error("no two-pass copy"); return FS_ERR_ARG; }
+  fs::BinnedCsr &N = *a->binned;
   void **slot = which == 0 ? (void **)&N.lcol : which == 1 ? (void **)&N.vals : which == 2 ? (void **)&N.gdst : which == 3 ? (void **)&N.lrow : (void **)&N.prod;
   const size_t bytes = which == 0 || which == 3 ? (size_t)N.n * 2 : which == 2 ? ((size_t)N.n >> fs::kBinGroupLog) * 4 : (size_t)N.n * 8 * (which == 4 ? (size_t)N.kw : 1);
   if (!*slot) return FS_OK;
@@ -626,73 +680,6 @@ int fs_debug_tiled_trace(fs_matrix_t A, double *y, const double *x, long long *t
   return FS_OK;
 }
 
-// The host-vector path launches on the handle's own non-blocking stream but shares the handle's scratch (product stream of
-// the two-pass copy, sums of cut rows) with the device-vector products, which return right after an asynchronous launch:
-// wait for the stream the last of those went to (a non-blocking stream is not ordered against it, not even the null stream).
-static int order_behind_last(fs_matrix_t A)
-{
-  if (!A->last_async) return FS_OK;
-  A->last_async = false;
-  if (hipStreamSynchronize(A->last_stream) != hipSuccess) {   // e.g. the caller has destroyed that stream since
-    (void)hipGetLastError();
-    FS_HIP(hipDeviceSynchronize());
-  }
-  return FS_OK;
-}
-
-// products with HOST vectors: synchronous; the copies of x and y overlap the kernels where the kept copy allows it
-int fs_spmv_host(fs_matrix_t A, double *y_host, const double *x_host)
-{
-  FS_RANGE("fs_spmv_host");
-  if (int rc = check_mul(A, y_host, x_host, "fs_spmv_host")) return rc;
-  std::lock_guard<std::mutex> g(A->lock);
-  if (int rc = order_behind_last(A)) return rc;
-  return fs::spmv_host_vectors(A->a, A->pipe, y_host, x_host);
-}
-
-int fs_spmv_t_host(fs_matrix_t A, double *y_host, const double *x_host)
-{
-  if (int rc = check_mul(A, y_host, x_host, "fs_spmv_t_host")) return rc;
-  FS_RANGE("fs_spmv_t_host");
-  if (!A->has_t) { set_error("fs_spmv_t_host: call fs_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
-  std::lock_guard<std::mutex> g(A->lock);
-  if (int rc = order_behind_last(A)) return rc;
-  return fs::spmv_host_vectors(A->at, A->pipe, y_host, x_host);
-}
-
-int fs_spmv_t(fs_matrix_t A, double *y, const double *x, fs_stream_t stream)
-{
-  if (int rc = check_mul(A, y, x, "fs_spmv_t")) return rc;
-  FS_RANGE("fs_spmv_t");
-  if (!A->has_t) { set_error("fs_spmv_t: call fs_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
-  std::lock_guard<std::mutex> g(A->lock);
-  A->last_stream = (hipStream_t)stream; A->last_async = true;
-  return fs::launch_spmv(A->at, y, x, (hipStream_t)stream);
-}
-
-int fs_spmm(fs_matrix_t A, double *Y, const double *X, int k, fs_stream_t stream)
-{
-  if (int rc = check_mul(A, Y, X, "fs_spmm")) return rc;
-  if (k < 1) { set_error("fs_spmm: k < 1"); return FS_ERR_ARG; }
-  if (k == 1) return fs_spmv(A, Y, X, stream);
-  FS_RANGE("fs_spmm");
-  std::lock_guard<std::mutex> g(A->lock);   // the k-column sweeps use the handle's product scratch
-  A->last_stream = (hipStream_t)stream; A->last_async = true;
-  return fs::launch_spmm(A->a, Y, X, k, (hipStream_t)stream);
-}
-
-int fs_spmm_t(fs_matrix_t A, double *Y, const double *X, int k, fs_stream_t stream)
-{
-  if (int rc = check_mul(A, Y, X, "fs_spmm_t")) return rc;
-  if (k < 1) { set_error("fs_spmm_t: k < 1"); return FS_ERR_ARG; }
-  if (!A->has_t) { set_error("fs_spmm_t: call fs_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
-  if (k == 1) return fs_spmv_t(A, Y, X, stream);
-  FS_RANGE("fs_spmm_t");
-  std::lock_guard<std::mutex> g(A->lock);
-  A->last_stream = (hipStream_t)stream; A->last_async = true;
-  return fs::launch_spmm(A->at, Y, X, k, (hipStream_t)stream);
-}
-
 // Everything a k-column product on this handle needs beyond a launch -- the k-column two-pass copy (k = 2..4), the
 // column-major scratch and the measured sweeps-or-row-kernel choice (LDS-staged copy, k = 3..16) -- done now, so that
 // fs_spmm / fs_spmm_t never build, allocate a copy or wait inside a product.  Synchronous, idempotent.
@@ -700,22 +687,23 @@ int fs_matrix_prepare(fs_matrix_t A, int k, int transposed, fs_stream_t stream)
 {
   FS_RANGE("fs_matrix_prepare");
   if (!A || k < 1) { set_error("fs_matrix_prepare: bad argument"); return FS_ERR_ARG; }
-  if (transposed && !A->has_t) { set_error("fs_matrix_prepare: call fs_matrix_build_transpose first"); return FS_ERR_NO_TRANSPOSE; }
+  fs::DeviceCsr *a = nullptr;
+  if (int rc = side_of(A, transposed, "fs_matrix_prepare", &a)) return rc;
   std::lock_guard<std::mutex> g(A->lock);
-  fs::DeviceCsr &a = transposed ? A->at : A->a;
   int needs = 0;
-  (void)fs::spmm_plan(a, k, &needs);
-  const int rc = fs::prepare_spmm(a, k, (hipStream_t)stream);   // nothing left to do: a plan lookup (the drop-in asks on every call)
+  (void)fs::spmm_plan(*a, k, &needs);
+  const int rc = fs::prepare_spmm(*a, k, (hipStream_t)stream);   // nothing left to do: a plan lookup (the drop-in asks on every call)
   if (needs) fs::pool_trim();
   return rc;
 }
 
 int fs_matrix_spmm_plan(fs_matrix_t A, int k, int transposed)
 {
-  if (!A || k < 1 || (transposed && !A->has_t)) return FS_ERR_ARG;
+  const fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a || k < 1) return FS_ERR_ARG;
   if (k == 1) return 0;
   std::lock_guard<std::mutex> g(A->lock);
-  return fs::spmm_plan(transposed ? A->at : A->a, k, nullptr);
+  return fs::spmm_plan(*a, k, nullptr);
 }
 
 int fs_matrix_device_bytes(fs_matrix_t A, int64_t *bytes3)
@@ -741,25 +729,16 @@ int fs_matrix_release_csr(fs_matrix_t A)
 
 int fs_matrix_restore_csr(fs_matrix_t A, int transposed, const int *row_ptr, const int *cols, const double *vals, int space, int borrow)
 {
-  if (!A || !row_ptr || (transposed && !A->has_t)) { set_error("fs_matrix_restore_csr: bad argument"); return FS_ERR_ARG; }
+  fs::DeviceCsr *a = side_or_null(A, transposed);
+  if (!a || !row_ptr) { set_error("fs_matrix_restore_csr: bad argument"); return FS_ERR_ARG; }
   std::lock_guard<std::mutex> g(A->lock);
-  fs::DeviceCsr &a = transposed ? A->at : A->a;
-  if (!a.released) return FS_OK;
-  if ((a.nnz > 0 && !cols) || (a.released_valued != (vals != nullptr))) { set_error("fs_matrix_restore_csr: these are not the arrays that were released"); return FS_ERR_ARG; }
-  int rc = FS_OK;
-  if (space == FS_DEVICE && borrow && fs::aligned16(cols) && (!vals || fs::aligned16(vals))) {
-    a.owns = false;
-    a.row_ptr = const_cast<int *>(row_ptr); a.cols = const_cast<int *>(cols); a.vals = const_cast<double *>(vals);
-  } else {
-    a.owns = true;
-    rc = fs::to_device(&a.row_ptr, row_ptr, (size_t)a.nrow + 1, space);
-    if (!rc) rc = fs::to_device(&a.cols, cols, (size_t)a.nnz, space);
-    if (!rc && vals) rc = fs::to_device(&a.vals, vals, (size_t)a.nnz, space);
-  }
-  a.released = false;
-  a.max_row_len = -1;
-  if (!rc) rc = fs::build_schedule(a, nullptr, /*allow_tiled=*/false);     // the chunk schedule of the streaming kernel only: the kept copy stays
-  if (rc) { (void)fs::release_plain_csr(a); return rc; }
+  if (!a->released) return FS_OK;
+  if ((a->nnz > 0 && !cols) || (a->released_valued != (vals != nullptr))) { set_error("fs_matrix_restore_csr: these are not the arrays that were released"); return FS_ERR_ARG; }
+  int rc = adopt_or_upload(*a, row_ptr, cols, vals, space, borrow);
+  a->released = false;
+  a->max_row_len = -1;
+  if (!rc) rc = fs::build_schedule(*a, nullptr, /*allow_tiled=*/false);     // the chunk schedule of the streaming kernel only: the kept copy stays
+  if (rc) { (void)fs::release_plain_csr(*a); return rc; }
   return FS_OK;
 }
 

@@ -1629,7 +1629,7 @@ struct CgSolve {
       bool plain;
       {
         std::lock_guard<std::mutex> g(M->lock);
-        plain = k == 1 ? spmv_choice(M->a, options()) < 6 : spmm_reads_plain_csr(M->a, k);
+        plain = k == 1 ? spmv_reads_plain_csr(M->a) : spmm_reads_plain_csr(M->a, k);
       }
       if (plain)
         if (int rc = need_plain_csr(M->a, who)) return rc;

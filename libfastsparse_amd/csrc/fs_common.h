@@ -19,6 +19,40 @@ constexpr int kBlock = 256;            // threads per workgroup = 4 wave64
 constexpr int kChunk = 2048;           // non-zeros one workgroup streams through LDS
 constexpr int kPerThread = kChunk / kBlock;
 
+// ---- error plumbing -------------------------------------------------------------------
+void set_error(const std::string &msg);
+int hip_fail(hipError_t e, const char *what, const char *file, int line);
+
+#define FS_HIP(call)                                                   \
+  do {                                                                 \
+    hipError_t e_ = (call);                                            \
+    if (e_ != hipSuccess) return ::fs::hip_fail(e_, #call, __FILE__, __LINE__); \
+  } while (0)
+
+// Host mirror of a device table of a re-ordered copy (first rows of the panels, first groups of the bands, ...), owned by the
+// copy: absent until the first product in parts or with host vectors fetches it (a synchronous download: callers that time
+// call fs_spmv_part_rows first), whole ever after, gone with the copy.
+template <typename T>
+struct HostMirror {
+  std::vector<T> v;
+  bool fetched = false;
+  int fetch(const T *dev, size_t n, const char *what)
+  {
+    if (fetched) return FS_OK;
+    std::vector<T> t(n);
+    const hipError_t e = n ? hipMemcpy(t.data(), dev, sizeof(T) * n, hipMemcpyDeviceToHost) : hipSuccess;
+    if (e != hipSuccess) return hip_fail(e, what, __FILE__, __LINE__);
+    v.swap(t);
+    fetched = true;
+    return FS_OK;
+  }
+  const T &operator[](size_t i) const { return v[i]; }
+};
+
+// which kernel a single-vector product runs (spmv_choice); the values are public (fs_matrix_spmv_kernel, option "spmv_kernel").
+// Auto: the option only.  Stream (chunk-streaming) and Vector (lanes per row) read the plain CSR, the others their copy
+enum SpmvKind { kSpmvAuto = 0, kSpmvStream = 1, kSpmvVector = 2, kSpmvTiled = 6, kSpmvTwoPass = 7, kSpmvLdsx = 8 };
+
 struct TiledCsr;
 struct BinnedCsr;
 
@@ -90,9 +124,9 @@ struct TiledCsr {
   int *vfirst = nullptr;       // nrow + 1: first virtual row of every row (only when split > 0)
   double *yv = nullptr;        // nvrow: sums of the virtual rows, combined per row after the kernel
   int slots = 256;             // workgroups resident together (1 per CU)
-  int *h_panel_row = nullptr;  // host mirrors of panel_row / chunk_panel, fetched by the first product with host vectors
-  int *h_chunk_panel = nullptr;
-  int *h_chunk_need = nullptr; // nchunks: columns of x the chunks 0 .. w of the launch order read (chunks sharing panels)
+  HostMirror<int> h_panel_row, h_chunk_panel;   // of panel_row (P + 1) and, LDS-staged, chunk_panel (nchunks)
+  std::vector<int> h_chunk_need;   // nchunks, worked out by the first product with host vectors on chunks sharing panels: columns
+                                   // of x the chunks 0 .. w of the launch order read
   // LDS-staged kernel only: a workgroup takes a CHUNK = a contiguous range of one panel's work items.  Normally a
   // panel is one chunk; a panel that holds far more than its share of the entries (few, long rows; a monster row) is
   // cut into several, whose y slices are then added up in HBM.  Rows are never cut into virtual rows here.
@@ -175,11 +209,10 @@ struct BinnedCsr {
   int split = 0, nvrow = 0;    // virtual rows, as in TiledCsr
   int *vfirst = nullptr;
   double *yv = nullptr;
-  // host mirrors of band_ptr / panel_row / bin_ptr, fetched on the first product with host vectors (fs_spmv_host
-  // cuts both passes into ranges of bands / panels so that the PCIe copies of x and y overlap them)
-  unsigned *h_band_ptr = nullptr;
-  int *h_panel_row = nullptr;
-  int *h_vfirst = nullptr;     // host mirror of vfirst (cut rows: the row cuts of products in parts)
+  // fs_spmv_host cuts both passes into ranges of bands / panels so that the PCIe copies of x and y overlap them; products in
+  // parts cut pass 2 (with cut rows: the row cuts come from vfirst)
+  HostMirror<unsigned> h_band_ptr;             // of band_ptr (B + 1)
+  HostMirror<int> h_panel_row, h_vfirst;       // of panel_row (P + 1), vfirst (nrow + 1)
 };
 
 // staging vectors, stream and events of products with HOST vectors (fs_spmv_host); one set per handle, made on first use
@@ -227,16 +260,6 @@ struct fs_cbcsr_s {
 
 namespace fs {
 
-// ---- error plumbing -------------------------------------------------------------------
-void set_error(const std::string &msg);
-int hip_fail(hipError_t e, const char *what, const char *file, int line);
-
-#define FS_HIP(call)                                                   \
-  do {                                                                 \
-    hipError_t e_ = (call);                                            \
-    if (e_ != hipSuccess) return ::fs::hip_fail(e_, #call, __FILE__, __LINE__); \
-  } while (0)
-
 // ---- roctx ranges around the C-ABI entry points ("roctx ranges around each C-ABI entry") -----------------
 // librocprofiler-sdk-roctx.so.1 is dlopen'ed on first use when FS_ROCTX=1 or the process runs under rocprofv3 (its tool
 // library is preloaded); otherwise a range costs one predictable branch.  `rocprofv3 --marker-trace -- <program>` shows them.
@@ -254,8 +277,8 @@ struct Range {
 
 struct Options {
   int strict_order = 0;
-  int spmv_kernel = 0;   // 0 auto, 1 stream (nt loads), 2 lanes-per-row, 3 stream (cached loads), 6 tiled, 7 two-pass,
-                         // 8 LDS-staged tiled
+  int spmv_kernel = 0;   // a SpmvKind (0 auto, 1 stream (nt loads), 2 lanes-per-row, 6 tiled, 7 two-pass, 8 LDS-staged tiled), or
+                         // 3 stream (cached loads)
   int tiling = 1;        // 1: build the L2-tiled copy when the heuristic says it pays, 2: always, 0: never
   int tile_rows = 0;     // override R (0 = auto)
   int tile_cols = 0;     // override W (0 = auto)
@@ -318,7 +341,8 @@ int prepare_spmm(DeviceCsr &A, int k, hipStream_t s);   // k-column copy, scratc
 int spmm_plan(const DeviceCsr &A, int k, int *needs_prepare);   // which kernel launch_spmm runs for this k (kPlan* in fs_kernels.hip)
 bool spmm_reads_plain_csr(const DeviceCsr &A, int k);   // launch_spmm would run a kernel that reads the plain CSR arrays (row kernel, MFMA)
 int launch_cbcsr(const fs_cbcsr_s &A, double *y, const double *x, hipStream_t s);
-int spmv_choice(const DeviceCsr &A, const Options &o);   // 7 two-pass, 8 LDS-staged, 6 L2-tiled, 2 lanes per row, 1 chunk-streaming
+int spmv_choice(const DeviceCsr &A, const Options &o);   // a SpmvKind, never kSpmvAuto
+bool spmv_reads_plain_csr(const DeviceCsr &A);          // launch_spmv would, under the options now: the chunk-streaming or lanes-per-row kernel
 int spmv_part_bounds(DeviceCsr &A, int nparts, const int **rows_out, const int **units_out, int *kind_out = nullptr, bool *cut_out = nullptr);
 int launch_spmv_part(DeviceCsr &A, double *y, const double *x, int part, int nparts, hipStream_t s);
 int spmm_part_bounds(DeviceCsr &A, int k, int nparts, const int **rows_out, const int **units_out, int *plan_out);
@@ -331,7 +355,7 @@ int launch_reduce_panels(const DeviceCsr &A, double *y, int p0, int p1, hipStrea
 int launch_copy_segments(int nseg, const int64_t *tab_dev, int64_t max_count, const double *src, double *dst, hipStream_t s);
 int launch_ata_fused(const DeviceCsr &A, double *y, const double *x, hipStream_t s);   // y[ncol] = A'A x, one kernel
 // y_host = A x_host: copies and kernels overlapped where the kept copy allows it (two-pass copy without cut rows)
-int spmv_host_vectors(const DeviceCsr &A, HostPipe &H, double *y_host, const double *x_host);
+int spmv_host_vectors(DeviceCsr &A, HostPipe &H, double *y_host, const double *x_host);
 int last_host_path();
 int last_spmm_plan();   // the plan (kPlan*) of the last multi-column product launched since the previous call, 0 if none
 int last_spmm_wide();   // the row kernel of the last one: 1 with 16-byte loads, 0 without, -1 none since the previous call

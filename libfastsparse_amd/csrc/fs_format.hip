@@ -90,9 +90,6 @@ void free_tiled_slot(TiledCsr *&T)
                    T->chunk_ord, T->ticket ? T->ticket - 1 : nullptr};   // (ticket[-1] = the give-up counter: one block)
   for (void *q : owned)
     if (q) (void)traced_free(q);
-  free(T->h_panel_row);
-  free(T->h_chunk_panel);
-  free(T->h_chunk_need);
   delete T;
   T = nullptr;
 }
@@ -114,9 +111,6 @@ void free_binned_slot(BinnedCsr *&N)
   void *owned[] = {N->lcol, N->vals, N->gdst, N->lrow, N->lrow8, N->gbase, N->prod, N->band_ptr, N->bin_ptr, N->panel_row, N->vfirst, N->yv};
   for (void *q : owned)
     if (q) (void)traced_free(q);
-  free(N->h_band_ptr);
-  free(N->h_panel_row);
-  free(N->h_vfirst);
   delete N;
   N = nullptr;
 }

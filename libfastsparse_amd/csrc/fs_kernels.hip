@@ -15,7 +15,9 @@
 //   here                    spmv_stream_kernel + fix-ups (one workgroup per 2048-entry chunk, storage-order sums: small x,
 //                           strict_order), spmv_vector_kernel (lanes per row, A/B alternative), spmm_kernel / spmm_wide_kernel /
 //                           spmm_mfma_kernel (k right-hand sides, one lane per output column), cbcsr_kernel, and everything that
-//                           decides: spmv_choice, spmm_plan, products in parts, host-vector products
+//                           decides: spmv_choice (a SpmvKind, fs_common.h), spmm_plan, products in parts (spmv_part_bounds) and
+//                           products with host vectors (spmv_host_vectors).  Those two cut a launch by plan_generation_cuts
+//                           (fs_plan.h) and read rows from the copies' host mirrors (HostMirror, fs_common.h: owned by the copy)
 //   (which copy a matrix keeps is the format builder's measured choice: fs_copies.hip, choose_copy)
 #include <stdlib.h>
 
@@ -25,6 +27,7 @@
 #include <vector>
 
 #include "fs_kernel_util.h"
+#include "fs_plan.h"
 
 namespace fs {
 
@@ -512,43 +515,42 @@ static int ceil_log2(int v)
 //   L2-tiled / LDS-staged copy whose workgroups own their rows: ranges of whole generations of resident workgroups
 //   anything else      (chunk-streaming kernel, chunks sharing panels, strict_order): everything with part 0
 // spmv_part_bounds gives the row cuts rows[0 .. nparts] (rows [rows[p], rows[p+1]) are final after part p) and the unit
-// cuts (panels / workgroups) for a given nparts; cached per handle.
+// cuts (panels / workgroups) for a given nparts; cached per handle.  The unit cuts are plan_generation_cuts' (fs_plan.h), here
+// and for the products with host vectors below; the rows come from the copy's host mirrors (HostMirror, fs_common.h).
 // ------------------------------------------------------------------------------------------
-// cuts of a two-pass copy (single-vector or k-column): pass 2 by whole generations of resident workgroups, rows by the panels'
+// cuts of a two-pass copy (single-vector or k-column): pass 2 (one workgroup per panel) by whole generations, rows by the panels'
 // first rows (with cut rows: the rows whose every piece lies below the cut).  *cut = false: too few panels to cut.
 static int binned_part_cuts(const DeviceCsr &A, BinnedCsr &N, int nparts, std::vector<int> &rows, std::vector<int> &units, bool *cut)
 {
   *cut = false;
   const int slots = N.slots > 0 ? N.slots : 256;
   if (N.nwg1 <= 0 || nparts <= 1 || N.P <= slots) return FS_OK;
-  if (!N.h_panel_row) {
-    int *hp = (int *)malloc(sizeof(int) * ((size_t)N.P + 1));
-    if (!hp) { set_error("out of host memory"); return FS_ERR_HIP; }
-    const hipError_t e = hipMemcpy(hp, N.panel_row, sizeof(int) * ((size_t)N.P + 1), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { free(hp); return hip_fail(e, "hipMemcpy(panel_row)", __FILE__, __LINE__); }
-    N.h_panel_row = hp;
-  }
-  if (N.split && !N.h_vfirst) {
-    int *hv = (int *)malloc(sizeof(int) * ((size_t)A.nrow + 1));
-    if (!hv) { set_error("out of host memory"); return FS_ERR_HIP; }
-    const hipError_t e = hipMemcpy(hv, N.vfirst, sizeof(int) * ((size_t)A.nrow + 1), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { free(hv); return hip_fail(e, "hipMemcpy(vfirst)", __FILE__, __LINE__); }
-    N.h_vfirst = hv;
-  }
-  const int *vfirst = N.h_vfirst;
-  // one pass-2 workgroup per CU (its y slice fills LDS) and launches of one stream run one after the other: a part is a
-  // whole number of generations of resident workgroups -- 4 parts of 192 panels on 256 CUs would take 4 generations where
-  // the undivided pass takes 3 (config 2: 768 panels)
-  const int gens = (N.P + slots - 1) / slots;
-  const int c = nparts < gens ? nparts : gens;
+  if (int rc = N.h_panel_row.fetch(N.panel_row, (size_t)N.P + 1, "hipMemcpy(panel_row)")) return rc;
+  if (N.split)
+    if (int rc = N.h_vfirst.fetch(N.vfirst, (size_t)A.nrow + 1, "hipMemcpy(vfirst)")) return rc;
+  const std::vector<int> &vfirst = N.h_vfirst.v;
+  units = plan_generation_cuts(N.P, slots, nparts);
   for (int p = 0; p <= nparts; ++p) {
-    const int64_t w = p >= c ? N.P : (int64_t)slots * ((int64_t)gens * p / c);
-    units[(size_t)p] = (int)(w < N.P ? w : N.P);
-    const int vcut = N.h_panel_row[units[(size_t)p]];
+    const int vcut = N.h_panel_row[(size_t)units[(size_t)p]];
     rows[(size_t)p] = !N.split ? vcut : p == nparts ? A.nrow :
-                      (int)(std::upper_bound(vfirst, vfirst + A.nrow + 1, vcut) - vfirst) - 1;
+                      (int)(std::upper_bound(vfirst.begin(), vfirst.end(), vcut) - vfirst.begin()) - 1;
   }
   *cut = true;
+  return FS_OK;
+}
+
+// *own: every workgroup of the copy's kernel finishes the rows of its own panel, so that a range of workgroups finishes a range
+// of rows -- no cut rows, no chunks sharing a panel and (LDS-staged: one chunk per panel) chunk w is panel w.  Fetches the
+// mirrors that tell; h_panel_row then gives the rows.
+static int tiled_owns_rows(TiledCsr &M, bool *own)
+{
+  *own = false;
+  if (M.split || (M.ldsx && M.shared)) return FS_OK;
+  if (int rc = M.h_panel_row.fetch(M.panel_row, (size_t)M.P + 1, "hipMemcpy(panel_row)")) return rc;
+  if (M.ldsx && M.nchunks > 0)
+    if (int rc = M.h_chunk_panel.fetch(M.chunk_panel, (size_t)M.nchunks, "hipMemcpy(chunk_panel)")) return rc;
+  *own = !M.ldsx || M.nchunks == M.P;
+  for (int w = 0; *own && M.ldsx && w < M.P; ++w) *own = M.h_chunk_panel[(size_t)w] == w;
   return FS_OK;
 }
 
@@ -566,36 +568,17 @@ int spmv_part_bounds(DeviceCsr &A, int nparts, const int **rows_out, const int *
   std::vector<int> rows((size_t)nparts + 1, A.nrow), units((size_t)nparts + 1, 0);
   rows[0] = 0;
   bool cut = false;
-  if (kind == 7) {
+  if (kind == kSpmvTwoPass) {
     if (int rc = binned_part_cuts(A, *A.binned, nparts, rows, units, &cut)) return rc;
-  } else if ((kind == 8 || kind == 6) && nparts > 1) {
-    TiledCsr &M = kind == 8 ? *A.tiledx : *A.tiled;
-    if (!M.split && !(M.ldsx && M.shared)) {
-      if (!M.h_panel_row) {
-        int *hp = (int *)malloc(sizeof(int) * ((size_t)M.P + 1));
-        int *hc = (int *)malloc(sizeof(int) * (size_t)(M.nchunks > 0 ? M.nchunks : 1));
-        if (!hp || !hc) { free(hp); free(hc); set_error("out of host memory"); return FS_ERR_HIP; }
-        hipError_t e = hipMemcpy(hp, M.panel_row, sizeof(int) * ((size_t)M.P + 1), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && M.ldsx && M.nchunks > 0)
-          e = hipMemcpy(hc, M.chunk_panel, sizeof(int) * (size_t)M.nchunks, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(hp); free(hc); return hip_fail(e, "hipMemcpy(panel tables)", __FILE__, __LINE__); }
-        M.h_panel_row = hp; M.h_chunk_panel = hc;
-      }
-      const int nwg = M.P;
-      bool own = !M.ldsx || M.nchunks == M.P;      // workgroup w owns panel w
-      for (int w = 0; own && M.ldsx && w < nwg; ++w) own = M.h_chunk_panel[w] == w;
-      const int slots = M.slots > 0 ? M.slots : 256;
-      const int gens = (nwg + slots - 1) / slots;
-      if (own && gens >= 2) {
-        // one workgroup per CU and launches of one stream run one after the other: a part is a whole number of generations
-        const int c = nparts < gens ? nparts : gens;
-        for (int p = 0; p <= nparts; ++p) {
-          const int64_t w = p >= c ? nwg : (int64_t)slots * ((int64_t)gens * p / c);
-          units[(size_t)p] = (int)(w < nwg ? w : nwg);
-          rows[(size_t)p] = M.h_panel_row[units[(size_t)p]];
-        }
-        cut = true;
-      }
+  } else if ((kind == kSpmvLdsx || kind == kSpmvTiled) && nparts > 1) {
+    TiledCsr &M = kind == kSpmvLdsx ? *A.tiledx : *A.tiled;
+    const int slots = M.slots > 0 ? M.slots : 256;
+    bool own = false;
+    if (int rc = tiled_owns_rows(M, &own)) return rc;
+    if (own && M.P > slots) {                        // at least two generations
+      units = plan_generation_cuts(M.P, slots, nparts);
+      for (int p = 0; p <= nparts; ++p) rows[(size_t)p] = M.h_panel_row[(size_t)units[(size_t)p]];
+      cut = true;
     }
   }
   if (!cut) {                                        // everything with part 0: rows = {0, nrow, nrow, ...}
@@ -622,13 +605,13 @@ int launch_spmv_part(DeviceCsr &A, double *y, const double *x, int part, int npa
   bool cut = false;
   if (int rc = spmv_part_bounds(A, nparts, &rows, &units, &kind, &cut)) return rc;
   if (!cut) return part == 0 ? launch_spmv(A, y, x, s) : FS_OK;
-  if (kind == 7) return launch_spmv_binned(A, y, x, s, 1, 1, units[part], units[part + 1], rows[part], rows[part + 1]);
+  if (kind == kSpmvTwoPass) return launch_spmv_binned(A, y, x, s, 1, 1, units[part], units[part + 1], rows[part], rows[part + 1]);
   if (units[part + 1] <= units[part]) return FS_OK;
-  return launch_spmv_tiled(A, kind == 8 ? *A.tiledx : *A.tiled, y, x, s, 1, 1, units[part], units[part + 1]);
+  return launch_spmv_tiled(A, kind == kSpmvLdsx ? *A.tiledx : *A.tiled, y, x, s, 1, 1, units[part], units[part + 1]);
 }
 
-// which kernel a single-vector product on A runs under the options o: 7 two-pass, 8 LDS-staged, 6 L2-tiled, 2 lanes per
-// row, 1 chunk-streaming.  The copy the format builder kept unless the caller asked for storage-order (strict_order) or
+// which kernel (SpmvKind) a single-vector product on A runs under the options o.
+// The copy the format builder kept unless the caller asked for storage-order (strict_order) or
 // run-to-run identical (reproducible) sums, which the kernels that add in arrival order cannot give (LDS-staged; the k-column
 // sweeps; the long-row path).
 int spmv_choice(const DeviceCsr &A, const Options &o)
@@ -641,29 +624,36 @@ int spmv_choice(const DeviceCsr &A, const Options &o)
   // not orderable -- instead of silently moving every product of a solve to the chunk-streaming kernel;
   // fs_debug_fixed_order_honoured tells which it is.
   const bool must = o.reproducible != 0;
-  if (A.binned && A.binned->built && !o.strict_order && (o.spmv_kernel == 0 || o.spmv_kernel == 7)) return 7;
-  if (A.tiledx && A.tiledx->built && !o.strict_order && (!must || A.tiledx->orderable) && (o.spmv_kernel == 0 || o.spmv_kernel == 8)) return 8;
-  if (A.tiled && A.tiled->built && !o.strict_order && (o.spmv_kernel == 0 || o.spmv_kernel == 6)) return 6;
-  return o.spmv_kernel == 2 ? 2 : 1;
+  const auto may = [&o](SpmvKind kind) { return o.spmv_kernel == kSpmvAuto || o.spmv_kernel == kind; };
+  if (A.binned && A.binned->built && !o.strict_order && may(kSpmvTwoPass)) return kSpmvTwoPass;
+  if (A.tiledx && A.tiledx->built && !o.strict_order && (!must || A.tiledx->orderable) && may(kSpmvLdsx)) return kSpmvLdsx;
+  if (A.tiled && A.tiled->built && !o.strict_order && may(kSpmvTiled)) return kSpmvTiled;
+  return o.spmv_kernel == kSpmvVector ? kSpmvVector : kSpmvStream;
+}
+
+bool spmv_reads_plain_csr(const DeviceCsr &A)
+{
+  const int kind = spmv_choice(A, options());
+  return kind == kSpmvStream || kind == kSpmvVector;
 }
 
 int launch_spmv(const DeviceCsr &A, double *y, const double *x, hipStream_t s, bool force_stream)
 {
   if (A.nrow == 0) return FS_OK;
   Options o = options();
-  if (force_stream) o.spmv_kernel = 1;
+  if (force_stream) o.spmv_kernel = kSpmvStream;
   const bool valued = A.vals != nullptr;
   switch (spmv_choice(A, o)) {
-    case 7: return launch_spmv_binned(A, y, x, s);
-    case 8: return launch_spmv_tiled(A, *A.tiledx, y, x, s);
-    case 6: return launch_spmv_tiled(A, *A.tiled, y, x, s);
+    case kSpmvTwoPass: return launch_spmv_binned(A, y, x, s);
+    case kSpmvLdsx: return launch_spmv_tiled(A, *A.tiledx, y, x, s);
+    case kSpmvTiled: return launch_spmv_tiled(A, *A.tiled, y, x, s);
     default: break;
   }
   if (int rc = need_plain_csr(A, "this product (strict_order, spmv_kernel 1-3, or \"reproducible\" on a copy that cannot give fixed-order sums)")) return rc;
   // strict_order (storage-order sums: only the chunk-streaming kernel gives them), or "reproducible" on a matrix whose kept
   // LDS-staged copy could not be arranged row-per-wave: the product runs on the chunk-streaming kernel (correct, fixed order, but
   // slow on large matrices).  Said once under FS_TRACE_BUILD.
-  if ((o.reproducible || o.strict_order) && o.spmv_kernel == 0 && ((A.binned && A.binned->built) || (A.tiledx && A.tiledx->built))) {
+  if ((o.reproducible || o.strict_order) && o.spmv_kernel == kSpmvAuto && ((A.binned && A.binned->built) || (A.tiledx && A.tiledx->built))) {
     static const bool trace = getenv("FS_TRACE_BUILD") != nullptr;
     static bool said = false;
     if (trace && !said) {
@@ -673,7 +663,7 @@ int launch_spmv(const DeviceCsr &A, double *y, const double *x, hipStream_t s, b
               o.strict_order ? "" : " (some work item holds more of one row than one wave can take: TiledCsr::orderable)");
     }
   }
-  if (o.spmv_kernel == 2) {
+  if (o.spmv_kernel == kSpmvVector) {
     const double avg = A.nrow ? (double)A.nnz / A.nrow : 0.0;
     int lg = o.strict_order ? 0 : ceil_log2((int)(avg < 1 ? 1 : (avg > 64 ? 64 : avg)));
     if (lg > 6) lg = 6;
@@ -753,13 +743,14 @@ static int host_pipe_ready(HostPipe &H, size_t nx, size_t ny, int nev)
 }
 
 // which way the last product with host vectors went (diagnostics / tests): 0 copy + product + copy, 1 two-pass in ranges
-// of bands and panels, 2 a panel kernel in ranges of workgroups
-static int g_last_host_path = 0;
-int last_host_path() { return g_last_host_path; }
+// of bands and panels, 2 a panel kernel in ranges of workgroups, 3 chunks sharing panels behind ranges of x
+static std::atomic<int> g_last_host_path{0};
+int last_host_path() { return g_last_host_path.load(std::memory_order_relaxed); }
 
-int spmv_host_vectors(const DeviceCsr &A, HostPipe &H, double *y_host, const double *x_host)
+int spmv_host_vectors(DeviceCsr &A, HostPipe &H, double *y_host, const double *x_host)
 {
-  g_last_host_path = 0;
+  const auto took_path = [](int path) { g_last_host_path.store(path, std::memory_order_relaxed); };
+  took_path(0);
   if (A.nrow == 0) return FS_OK;
   static const int want_chunks = [] {
     const char *e = getenv("FS_HOST_CHUNKS");
@@ -770,45 +761,38 @@ int spmv_host_vectors(const DeviceCsr &A, HostPipe &H, double *y_host, const dou
   const size_t nx = A.ncol > 0 ? (size_t)A.ncol : 1, ny = (size_t)A.nrow;
   if (int rc = host_pipe_ready(H, nx, ny, want_chunks)) return rc;
   const bool two_pass = A.binned && A.binned->built && !A.binned->split && !A.binned->lr && A.binned->nwg1 > 0 && !o.strict_order &&
-                        !reproducible_now() && (o.spmv_kernel == 0 || o.spmv_kernel == 7) && o.bin_flags == 0 && want_chunks > 1;
+                        !reproducible_now() && (o.spmv_kernel == kSpmvAuto || o.spmv_kernel == kSpmvTwoPass) && o.bin_flags == 0 &&
+                        want_chunks > 1;
   if (!two_pass) {
     // the panel kernels (LDS-staged, L2-tiled) need all of x, but a workgroup that owns its rows finishes them: launched in
     // ranges of workgroups, y comes down range by range under the later ranges (a tall matrix: config 3, y 80 MB, x 8 MB)
-    const TiledCsr *T = nullptr;
+    TiledCsr *T = nullptr;
     if (!(A.binned && A.binned->built) && !o.strict_order && want_chunks > 1) {
-      if (A.tiledx && A.tiledx->built && !reproducible_now() && (o.spmv_kernel == 0 || o.spmv_kernel == 8)) T = A.tiledx;
-      else if (A.tiled && A.tiled->built && (o.spmv_kernel == 0 || o.spmv_kernel == 6)) T = A.tiled;
+      if (A.tiledx && A.tiledx->built && !reproducible_now() && (o.spmv_kernel == kSpmvAuto || o.spmv_kernel == kSpmvLdsx)) T = A.tiledx;
+      else if (A.tiled && A.tiled->built && (o.spmv_kernel == kSpmvAuto || o.spmv_kernel == kSpmvTiled)) T = A.tiled;
     }
     if (T && T->ldsx && T->shared && T->nchunks >= 2 * want_chunks && A.ncol >= (1 << 20)) {
       // Few, long rows (config 3 transposed: x 80 MB, y 8 MB): several chunks per panel, launched stretch of bands by
       // stretch of bands (fs_plan.h, plan_ldsx_chunks: "Launch order"), so the chunks at the front of the order only read the front of x.
       // need[w] = columns the chunks 0 .. w read; x goes up in ranges and the chunks a range completes are launched behind it.
-      TiledCsr &M = const_cast<TiledCsr &>(*T);
-      if (!M.h_chunk_need) {
-        std::vector<int> ci(2 * (size_t)M.nchunks);
+      TiledCsr &M = *T;
+      if (M.h_chunk_need.empty()) {
+        std::vector<int> ci(2 * (size_t)M.nchunks), need((size_t)M.nchunks);
         std::vector<int4> it((size_t)M.nitems > 0 ? (size_t)M.nitems : 1);
-        int *need = (int *)malloc(sizeof(int) * (size_t)M.nchunks);
-        if (!need) { set_error("out of host memory"); return FS_ERR_HIP; }
-        hipError_t e = hipMemcpy(ci.data(), M.chunk_item, sizeof(int) * ci.size(), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && M.nitems > 0) e = hipMemcpy(it.data(), M.items, sizeof(int4) * (size_t)M.nitems, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(need); return hip_fail(e, "hipMemcpy(chunk tables)", __FILE__, __LINE__); }
+        FS_HIP(hipMemcpy(ci.data(), M.chunk_item, sizeof(int) * ci.size(), hipMemcpyDeviceToHost));
+        if (M.nitems > 0) FS_HIP(hipMemcpy(it.data(), M.items, sizeof(int4) * (size_t)M.nitems, hipMemcpyDeviceToHost));
+        if (int rc = M.h_chunk_panel.fetch(M.chunk_panel, (size_t)M.nchunks, "hipMemcpy(chunk_panel)")) return rc;
         int64_t most = 0;
         for (int w = 0; w < M.nchunks; ++w) {
           for (int i = ci[2 * (size_t)w]; i < ci[2 * (size_t)w + 1]; ++i) {
             const int64_t end = ((int64_t)it[(size_t)i].z + 1) * M.W;
             if (end > most) most = end;
           }
-          need[w] = (int)(most < A.ncol ? most : A.ncol);
+          need[(size_t)w] = (int)(most < A.ncol ? most : A.ncol);
         }
-        int *hc = (int *)malloc(sizeof(int) * (size_t)M.nchunks);
-        if (!hc) { free(need); set_error("out of host memory"); return FS_ERR_HIP; }
-        e = hipMemcpy(hc, M.chunk_panel, sizeof(int) * (size_t)M.nchunks, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(need); free(hc); return hip_fail(e, "hipMemcpy(chunk tables)", __FILE__, __LINE__); }
-        free(M.h_chunk_panel);
-        M.h_chunk_panel = hc;
-        M.h_chunk_need = need;
+        M.h_chunk_need.swap(need);
       }
-      g_last_host_path = 3;
+      took_path(3);
       FS_HIP(hipMemsetAsync(M.yv, 0, sizeof(double) * (size_t)A.nrow, H.stream));
       // a range = one or more whole stretch groups of the launch order (the panel id falls back where the next group starts),
       // at least one generation of resident workgroups long
@@ -841,39 +825,24 @@ int spmv_host_vectors(const DeviceCsr &A, HostPipe &H, double *y_host, const dou
       return FS_OK;
     }
     if (A.ncol > 0) FS_HIP(hipMemcpy(H.sx, x_host, sizeof(double) * (size_t)A.ncol, hipMemcpyHostToDevice));
-    if (T && !T->split && !(T->ldsx && T->shared) && T->P >= 2 * want_chunks) {
-      TiledCsr &M = const_cast<TiledCsr &>(*T);
-      if (!M.h_panel_row) {
-        int *hp = (int *)malloc(sizeof(int) * ((size_t)M.P + 1));
-        int *hc = (int *)malloc(sizeof(int) * (size_t)(M.nchunks > 0 ? M.nchunks : 1));
-        if (!hp || !hc) { free(hp); free(hc); set_error("out of host memory"); return FS_ERR_HIP; }
-        hipError_t e = hipMemcpy(hp, M.panel_row, sizeof(int) * ((size_t)M.P + 1), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && M.ldsx && M.nchunks > 0)
-          e = hipMemcpy(hc, M.chunk_panel, sizeof(int) * (size_t)M.nchunks, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { free(hp); free(hc); return hip_fail(e, "hipMemcpy(panel tables)", __FILE__, __LINE__); }
-        M.h_panel_row = hp; M.h_chunk_panel = hc;
-      }
-      // workgroup w owns panel w (LDS-staged: one chunk per panel when no panel is shared)
-      const int nwg = M.P;
-      bool own = !M.ldsx || M.nchunks == M.P;
-      for (int w = 0; own && M.ldsx && w < nwg; ++w) own = M.h_chunk_panel[w] == w;
-      // One workgroup per CU and launches of one stream run one after the other, so a range is a whole number of
-      // generations of resident workgroups (config 3: 698 panels = 256 + 256 + 186; eight ranges of 87 were measured to
-      // take eight generations, 2.42 ms per call against 1.87): y starts to come down after the first generation
+    if (T && T->P >= 2 * want_chunks) {
+      TiledCsr &M = *T;
+      bool own = false;
+      if (int rc = tiled_owns_rows(M, &own)) return rc;
+      // a range is a whole number of generations of resident workgroups (plan_generation_cuts; config 3: 698 panels = 256 +
+      // 256 + 186): y starts to come down after the first generation
       const int slots = M.slots > 0 ? M.slots : 256;
-      const int gens = (nwg + slots - 1) / slots;
+      const int gens = (M.P + slots - 1) / slots;
       const int c = want_chunks < gens ? want_chunks : gens;
       if (own && c >= 2) {
-        g_last_host_path = 2;
-        auto cut = [&](int j) { const int64_t w = (int64_t)slots * ((int64_t)gens * j / c); return (int)(w < nwg ? w : nwg); };
+        took_path(2);
+        const std::vector<int> cut = plan_generation_cuts(M.P, slots, want_chunks);
         for (int j = 0; j < c; ++j) {
-          const int w0 = cut(j), w1 = j == c - 1 ? nwg : cut(j + 1);
-          if (int rc = launch_spmv_tiled(A, M, H.sy, H.sx, H.stream, 1, 1, w0, w1)) return rc;
+          if (int rc = launch_spmv_tiled(A, M, H.sy, H.sx, H.stream, 1, 1, cut[(size_t)j], cut[(size_t)j + 1])) return rc;
           FS_HIP(hipEventRecord(H.ev[j], H.stream));
         }
         for (int j = 0; j < c; ++j) {
-          const int w0 = cut(j), w1 = j == c - 1 ? nwg : cut(j + 1);
-          const int64_t r0 = M.h_panel_row[w0], r1 = M.h_panel_row[w1];
+          const int64_t r0 = M.h_panel_row[(size_t)cut[(size_t)j]], r1 = M.h_panel_row[(size_t)cut[(size_t)j + 1]];
           FS_HIP(hipEventSynchronize(H.ev[j]));
           if (r1 > r0) FS_HIP(hipMemcpy(y_host + r0, H.sy + r0, sizeof(double) * (size_t)(r1 - r0), hipMemcpyDeviceToHost));
         }
@@ -885,18 +854,10 @@ int spmv_host_vectors(const DeviceCsr &A, HostPipe &H, double *y_host, const dou
     FS_HIP(hipMemcpy(y_host, H.sy, sizeof(double) * ny, hipMemcpyDeviceToHost));
     return FS_OK;
   }
-  g_last_host_path = 1;
+  took_path(1);
   BinnedCsr &N = *A.binned;
-  if (!N.h_band_ptr) {
-    unsigned *hb = (unsigned *)malloc(sizeof(unsigned) * ((size_t)N.B + 1));
-    int *hp = (int *)malloc(sizeof(int) * ((size_t)N.P + 1));
-    if (!hb || !hp) { free(hb); free(hp); set_error("out of host memory"); return FS_ERR_HIP; }
-    hipError_t e = hipMemcpy(hb, N.band_ptr, sizeof(unsigned) * ((size_t)N.B + 1), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(hp, N.panel_row, sizeof(int) * ((size_t)N.P + 1), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { free(hb); free(hp); return hip_fail(e, "hipMemcpy(two-pass tables)", __FILE__, __LINE__); }
-    free(N.h_panel_row);                         // products in parts may have fetched it already
-    N.h_band_ptr = hb; N.h_panel_row = hp;
-  }
+  if (int rc = N.h_band_ptr.fetch(N.band_ptr, (size_t)N.B + 1, "hipMemcpy(band_ptr)")) return rc;
+  if (int rc = N.h_panel_row.fetch(N.panel_row, (size_t)N.P + 1, "hipMemcpy(panel_row)")) return rc;
   const int nwg1 = (o.bin_wgs > 0 && o.bin_wgs < N.nwg1) ? o.bin_wgs : N.nwg1;
   // pass 1, band range by band range
   const int c1 = want_chunks < N.B ? want_chunks : N.B;

@@ -759,7 +759,7 @@ int launch_strided_copy(int n, const double *v, double *y, int ys, hipStream_t s
 }
 
 // c0 .. c1: the workgroups of this launch (chunks of the LDS-staged kernel, panels of the L2-tiled one); c1 < 0 = all.
-// A part launch needs every workgroup to own its rows (no chunks sharing a panel, no cut rows): spmv_host_vectors
+// A part launch needs every workgroup to own its rows (no chunks sharing a panel, no cut rows): tiled_owns_rows, fs_kernels.hip
 int launch_spmv_tiled(const DeviceCsr &A, const TiledCsr &T, double *y, const double *x, hipStream_t s, int xs, int ys,
                       int c0, int c1)
 {

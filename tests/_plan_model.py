@@ -191,6 +191,13 @@ def pad_long_segments(hs, B):
     return {"ok": [1], "hp": hp, "hseg": hseg, "hsh": hsh}
 
 
+def plan_generation_cuts(nunits, slots, nparts):
+    """units[0 .. nparts] of a launch of nunits workgroups in parts: whole generations of `slots` resident workgroups"""
+    gens = (nunits + slots - 1) // slots
+    c = min(nparts, gens)
+    return [min(nunits, slots * (gens * p // c)) if p < c else nunits for p in range(nparts + 1)]
+
+
 # ---- what the device steps around the planners do, for predictions from a CSR (numpy) -------------------------------------
 def virtual_rows(rp, split):
     """entry offsets of the virtual rows (nvrow + 1): rows longer than `split` cut into pieces of `split` consecutive entries

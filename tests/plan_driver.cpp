@@ -116,6 +116,10 @@ int main()
       put("hp", hp);
       put("hseg", hseg);
       put("hsh", hsh);
+    } else if (cmd == "generation_cuts") {
+      int nunits, slots, nparts;
+      std::cin >> nunits >> slots >> nparts;
+      put("units", plan_generation_cuts(nunits, slots, nparts));
     } else {
       fprintf(stderr, "plan_driver: unknown command %s\n", cmd.c_str());
       return 2;

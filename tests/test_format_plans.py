@@ -142,7 +142,17 @@ def _cases():
                 counts.append(0 if kind == "empty band" and b == 1 else c)
         hs = _row_ptr(counts)
         out.append(("pad_segments %d %s" % (B, _vec(hs)), M.pad_long_segments(hs, B), {"segments": (hs, B)}))
+    for nunits, slots, nparts in GENERATION_CUTS:
+        out.append(("generation_cuts %d %d %d" % (nunits, slots, nparts), {"units": M.plan_generation_cuts(nunits, slots, nparts)},
+                    {"cuts": (nunits, slots, nparts)}))
     return out
+
+
+# (workgroups, resident together, parts) -> the cuts written out where they are short: config 2's 768 panels in 4 parts take its 3
+# generations; config 3's 698 = 256 + 256 + 186 in eight ranges; one workgroup more than a generation; exactly one generation; fewer
+# workgroups than slots; many small generations; a count at the int32 limit (64-bit intermediates)
+GENERATION_CUTS = {(768, 256, 4): [0, 256, 512, 768, 768], (698, 256, 8): [0, 256, 512] + [698] * 6, (257, 256, 2): [0, 256, 257],
+                   (256, 256, 2): None, (1, 8, 7): None, (5000, 8, 7): None, (2**31 - 2, 256, 64): None}
 
 
 @pytest.fixture(scope="module")
@@ -179,7 +189,7 @@ def test_every_planner_equals_its_model(results):
         kinds.add(cmd.split()[0])
         assert got == want, cmd[:200]
     assert kinds == {"consts", "tiled_rows", "tiled_panels", "band_width", "work_items", "ldsx_chunks", "two_pass_geometry", "two_pass_panels",
-                     "long_rows", "pad_segments"}
+                     "long_rows", "pad_segments", "generation_cuts"}
 
 
 def test_panels_partition_the_rows(results):
@@ -274,6 +284,22 @@ def test_every_long_row_has_one_owner(results):
             assert blk == sorted(blk) and all(o == w for o in owner_of[own_first[w]:own_first[w + 1]])
             assert len(blk) in (nlong // M.K_LONG_OWNERS, -(-nlong // M.K_LONG_OWNERS))
         assert lptr[0] == 0 and all(lptr[i + 1] - lptr[i] == length[rows[i]] for i in range(nlong))
+
+
+def test_generation_cuts_add_no_generation(results):
+    """plan_generation_cuts (products in parts, products with host vectors): the cuts run from 0 to nunits and never back, every
+    cut inside the launch is a multiple of `slots`, the parts' generations ceil(len / slots) add up to those of the undivided
+    launch, and exactly min(nparts, generations) parts are not empty"""
+    for cmd, (nunits, slots, nparts), got in _with(results, "cuts"):
+        units = got["units"]
+        if GENERATION_CUTS[(nunits, slots, nparts)] is not None:
+            assert units == GENERATION_CUTS[(nunits, slots, nparts)], cmd
+        gens = -(-nunits // slots)
+        lens = [b - a for a, b in zip(units[:-1], units[1:])]
+        assert len(units) == nparts + 1 and units[0] == 0 and units[-1] == nunits and all(n >= 0 for n in lens), cmd
+        assert all(u % slots == 0 for u in units[1:-1] if u < nunits), cmd
+        assert sum(-(-n // slots) for n in lens) == gens, cmd
+        assert sum(n > 0 for n in lens) == min(nparts, gens), cmd
 
 
 def test_padded_segments_are_even_and_consistent(results):

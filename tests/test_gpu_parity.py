@@ -2456,6 +2456,70 @@ def test_products_with_host_vectors_overlap_copies(hip, valued):
     assert np.array_equal(y, [1.5 - 6.0, 0.0, 8.0])
 
 
+@pytest.mark.parametrize("case", ["two-pass", "two-pass cut rows", "tiled"])
+def test_parts_and_host_vectors_share_a_copy_s_host_mirrors(hip, case):
+    """Products in parts and products with host vectors read the same host mirrors of a copy's tables (first rows of the panels;
+    with cut rows the rows' first virtual rows), whichever fetches them first: on one handle the product in 4 parts, then
+    fs_spmv_host; on a fresh handle the other way round.  The row cuts are the same list both times and really cut, y of the
+    parts is y of fs_spmv_host is the oracle's, bit for bit (pattern-only, integer x), and fs_spmv_host goes the way it always
+    did: 1 two-pass in ranges (600 panels of 100 rows, more than the 256 resident), 0 with a cut row, 2 the L2-tiled copy in
+    ranges of workgroups (400 panels of 1000 rows)."""
+    import torch
+    from libfastsparse_amd import capi
+    rng = np.random.default_rng(43)
+    if case == "tiled":
+        nrow, ncol, opts, host_path = 400_000, 100_000, {"ldsx": 0, "tiling": 2, "binning": 0, "tile_rows": 1000}, 2
+        lens = rng.integers(40, 90, nrow)
+    else:
+        nrow, ncol, opts, host_path = 60_000, 100_000, {"binning": 2, "bin_rows": 100}, 0 if "cut" in case else 1
+        lens = rng.integers(0, 61, nrow)
+        lens[rng.uniform(size=nrow) < 0.1] = 0
+        if "cut" in case:
+            lens[777] = 5000               # cut into virtual rows: the row cuts of the parts come from vfirst
+    rp = np.zeros(nrow + 1, np.int64)
+    np.cumsum(lens, out=rp[1:])
+    rp = rp.astype(np.int32)
+    cc = rng.integers(0, ncol, int(rp[-1])).astype(np.int32)
+    x = S.x_int(4, ncol)
+    ref = O.csr_mul(nrow, rp, cc, None, x)
+    xd = torch.from_numpy(x).cuda()
+    st = capi.current_stream()
+    defaults = {"ldsx": 1, "tiling": 1, "binning": 1, "tile_rows": 0, "bin_rows": 0}
+    cuts = []
+    for parts_first in (True, False):
+        for k, v in opts.items():
+            capi.set_option(k, v)
+        try:
+            A = capi.Matrix.from_csr(nrow, ncol, rp, cc, None)
+        finally:
+            for k in opts:
+                capi.set_option(k, defaults[k])
+        assert A.kernel_name() == case.split(" cut")[0], A.kernel_name()
+
+        def in_parts():
+            rows = A.part_rows(4)
+            y = torch.full((nrow,), -7.0, dtype=torch.float64, device="cuda")
+            for p in range(4):
+                A.spmv_part(y, xd, p, 4, st)
+            return rows, y.cpu().numpy()
+
+        def with_host_vectors():
+            y = np.full(nrow, -7.0)
+            A.spmv_host(y, x)
+            return y, capi.lib().fs_debug_last_host_path()
+
+        if parts_first:
+            (rows, y_parts), (y_host, path) = in_parts(), with_host_vectors()
+        else:
+            (y_host, path), (rows, y_parts) = with_host_vectors(), in_parts()
+        A.close()
+        assert path == host_path, (case, parts_first)
+        assert np.array_equal(y_parts, ref) and np.array_equal(y_host, ref) and np.array_equal(y_parts, y_host), (case, parts_first)
+        assert rows[0] == 0 and rows[-1] == nrow and sum(b > a for a, b in zip(rows, rows[1:])) >= 2, (case, rows)
+        cuts.append(rows)
+    assert cuts[0] == cuts[1], (case, cuts)
+
+
 def _shard_arrays(rp, cc, vv, cuts):
     """per-rank arrays of a CSR cut at the rows `cuts`: local row_ptr, global columns, values"""
     out = []
