@@ -212,7 +212,7 @@ int fs_spmv_t_host(fs_matrix_t A, double *y_host, const double *x_host);
 /* ---- consumers of the path, device resident (cg.h of the reference) -------------------- */
 /* (A'A + lambda I) x = b by conjugate gradients; A and the handle of its transpose as the reference passes
  * them (bsbm_cg cg.h:25); x, b: F = ncol(A) doubles in HBM; stops at ||r|| <= tol ||b|| or after F iterations.
- * Every solver below (fs_cg, fs_cg2, fs_pcg, fs_mscg, fs_pcgn) looks at its two products before it writes anything: where one of
+ * Every solver below (fs_cg, fs_cg2, fs_pcg, fs_mscg, fs_pcgn, fs_pcgn_lambdas) looks at its two products before it writes anything: where one of
  * them would read plain CSR arrays that fs_matrix_release_csr gave back ("strict_order", spmv_kernel 1 / 2 / 3, the row kernel of
  * a k-column product) the solve returns FS_ERR_RELEASED with x untouched -- also a solve that would have needed no product. */
 int fs_cg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lambda, double tol, int *out_iter,
@@ -355,6 +355,26 @@ enum { FS_PCGN_MAX_RHS = 32 };
  * with a NULL diag; tol negative or NaN.  A product's own error is passed through. */
 int fs_pcgn(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k, double lambda, const fs_pcg_params *prm,
             fs_pcg_info *info /* k entries or NULL */, fs_stream_t stream);
+
+/* (A'A + lambda[j] I) x_j = b_j for j < k: fs_pcgn with a lambda per column -- a ladder of lambdas on one b (B = b in every column),
+ * or targets x rungs -- where fs_mscg cannot serve because the data need a preconditioner.  lambda: k doubles on the HOST.  All of
+ * fs_pcgn's text holds (panels, alignment, prm, freezing and the live mask, option "pcgn_kernel", the one-time fs_matrix_prepare,
+ * synchronous, work space, traffic: the per-column diagonal adds arithmetic, not bytes) but for what follows.
+ * Arithmetic: column j follows fs_pcg at lambda[j] line by line: the warm start has Q = Q + lambda_j X, the iteration
+ * q = q + lambda_j p.  FS_PRECOND_JACOBI: column j's diagonal is fs_gram_diag(At, lambda[j]), formed as s + lambda_j from ONE
+ * s = fs_gram_diag(At, 0.0) per solve (the same bits: fs_gram_diag adds lambda last, and a sum of squares is never -0.0); there is
+ * no pass that inverts it: the work vector holds s, and wherever fs_pcgn multiplies by dinv[i] the kernels multiply by
+ *   dinv_j[i] = (s[i] + lambda_j) == 0 ? 1 : 1 / (s[i] + lambda_j)      (one IEEE addition, one IEEE division per element)
+ * FS_PRECOND_DIAG: one diagonal from the caller for all columns (a caller's M need not depend on lambda), inverted once per solve
+ * as in fs_pcgn.  FS_PRECOND_NONE: no diagonal is read.
+ * So column j IS fs_pcg at lambda[j] on B[:, j] wherever the k-column product has the single-vector product's bits: bit for bit
+ * under "strict_order", and for k = 1 in every mode.  With all lambda[j] equal the solve is fs_pcgn at that lambda, bit for bit,
+ * in every mode in which fs_pcgn repeats its own bits.
+ * FS_ERR_ARG, raised before anything is written to X: what fs_pcgn refuses; a NULL lambda; a lambda that is NaN or infinite.
+ * FS_ERR_RELEASED as in fs_pcgn. */
+int fs_pcgn_lambdas(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k,
+                    const double *lambda /* k doubles on the HOST */, const fs_pcg_params *prm,
+                    fs_pcg_info *info /* k entries or NULL */, fs_stream_t stream);
 
 /* ---- column-blocked binary CSR (cbcsr.h) -------------------------------------------- */
 fs_cbcsr_t fs_cbcsr_create(int nrow, int ncol, int nblocks, int colblocksize, const int *row_ptr,

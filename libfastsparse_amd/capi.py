@@ -26,7 +26,7 @@ DEVICE_API = [
     "fs_matrix_release_csr", "fs_matrix_restore_csr", "fs_matrix_release_prepared",
     "fs_matrix_prepare", "fs_matrix_spmm_plan", "fs_matrix_device_bytes", "fs_spmv_part", "fs_spmv_part_rows", "fs_spmm_part", "fs_spmm_part_rows", "fs_copy_segments",
     "fs_matrix_nrow", "fs_matrix_ncol", "fs_matrix_nnz", "fs_matrix_algorithmic_bytes", "fs_matrix_download",
-    "fs_spmv", "fs_spmv_t", "fs_spmv_host", "fs_spmv_t_host", "fs_spmm", "fs_spmm_t", "fs_ata_mul", "fs_cg", "fs_cg2", "fs_axpy", "fs_gram_diag", "fs_pcg", "fs_mscg", "fs_pcgn",
+    "fs_spmv", "fs_spmv_t", "fs_spmv_host", "fs_spmv_t_host", "fs_spmm", "fs_spmm_t", "fs_ata_mul", "fs_cg", "fs_cg2", "fs_axpy", "fs_gram_diag", "fs_pcg", "fs_mscg", "fs_pcgn", "fs_pcgn_lambdas",
     "fs_cbcsr_create", "fs_cbcsr_destroy", "fs_cbcsr_spmv", "fs_invalidate", "fs_release_all", "fs_cache_entries",
     "fs_synth_uniform", "fs_synth_powerlaw_lengths", "fs_synth_fill", "fs_bucket_coo", "fs_device_build_wanted",
     "fs_dist_create", "fs_dist_destroy", "fs_dist_ndev", "fs_dist_uses_rccl", "fs_dist_csr_create", "fs_dist_matrix_destroy",
@@ -146,6 +146,7 @@ def lib():
     L.fs_gram_diag.argtypes = [vp, C.c_double, vp, vp]
     L.fs_pcg.argtypes = [vp, vp, vp, vp, C.c_double, C.POINTER(PcgParams), C.POINTER(PcgInfo), vp]
     L.fs_pcgn.argtypes = [vp, vp, vp, vp, C.c_int, C.c_double, C.POINTER(PcgParams), C.POINTER(PcgInfo), vp]
+    L.fs_pcgn_lambdas.argtypes = [vp, vp, vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(PcgParams), C.POINTER(PcgInfo), vp]
     L.fs_mscg.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(PcgInfo), vp]
     L.fs_cbcsr_create.restype = vp
     L.fs_cbcsr_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]
@@ -431,6 +432,23 @@ def pcgn(A, At, X, B, lam, tol, max_iter=0, precond=FS_PRECOND_JACOBI, warm_star
     prm = PcgParams(float(tol), int(max_iter), int(precond), int(bool(warm_start)), _ptr(diag))
     infos = (PcgInfo * max(k, 1))()
     check(lib().fs_pcgn(A.h, At.h, X.data_ptr(), B.data_ptr(), k, float(lam), C.byref(prm), infos, stream), "fs_pcgn")
+    return list(infos)[:k]
+
+
+def pcgn_lambdas(A, At, X, B, lams, tol, max_iter=0, precond=FS_PRECOND_JACOBI, warm_start=False, diag=None, stream=None):
+    """(A'A + lams[j] I) x_j = b_j for the k columns of B in one solve (fs_pcgn_lambdas): pcgn with a lambda per column, and with
+    FS_PRECOND_JACOBI the diagonal of that column's lambda.  X, B, diag as in pcgn; lams: k host values.  Returns the list of the k
+    PcgInfo, one per column."""
+    if B.dim() not in (1, 2) or X.shape != B.shape or not X.is_contiguous() or not B.is_contiguous():
+        raise ValueError("pcgn_lambdas: X and B must be contiguous (F, k) tensors of the same shape")
+    k = 1 if B.dim() == 1 else int(B.shape[1])
+    lams = [float(v) for v in lams]
+    if len(lams) != k:
+        raise ValueError("pcgn_lambdas: one lambda per column of B")
+    prm = PcgParams(float(tol), int(max_iter), int(precond), int(bool(warm_start)), _ptr(diag))
+    infos = (PcgInfo * max(k, 1))()
+    check(lib().fs_pcgn_lambdas(A.h, At.h, X.data_ptr(), B.data_ptr(), k, (C.c_double * max(k, 1))(*lams), C.byref(prm), infos, stream),
+          "fs_pcgn_lambdas")
     return list(infos)[:k]
 
 

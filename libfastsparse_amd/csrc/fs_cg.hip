@@ -674,6 +674,18 @@ __device__ __forceinline__ void pcgn_tile_pairs(int c0, int k, unsigned live, G 
   }
 }
 
+// ---- the per-column form of the kernels (fs_pcgn_lambdas).  LAM = PcgnLambdas in place of double: column c is shifted by
+// lambda.v[c].  The kernels that see no lambda in fs_pcgn take the k lambdas as a trailing argument when the diagonal follows the
+// column (FS_PRECOND_JACOBI): `dinv` then holds s = diag(A'A), and column c's inverse is formed per element, pcg_dinv_kernel's
+// line on s + lambda_c.  The lambdas are a by-value argument, indexed by constants once the column loops are unrolled: scalar
+// loads from the kernel's arguments, wave-uniform like al[c] and be[c].  Without LAM a kernel is fs_pcgn's own instantiation.
+template <typename LAM> constexpr bool pn_cols = !std::is_same<LAM, double>::value;
+__device__ __forceinline__ double pn_inv(double s, double lambda)
+{
+  const double d = s + lambda;
+  return d == 0.0 ? 1.0 : 1.0 / d;
+}
+
 __device__ __forceinline__ unsigned pcgn_live(const double *__restrict__ st)
 {
   return (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)st[kStLiveMask]);
@@ -709,8 +721,8 @@ __device__ __forceinline__ void pcgn_block_sums(int k, unsigned live, int ns, co
 
 // cold: X = 0, R = B.  warm (Q = A'(A X) on entry): Q += lambda X, R = B - Q.  Partials {b.b, r.r} per column (pcg_init_kernel).
 // VEC: 0 every access is 8 bytes (odd k), 1 16-byte accesses to the solve's own R, P, Q, 2 to the caller's X and B too
-template <int KMAX, int VEC>
-__global__ __launch_bounds__(kRedThreads) void pcgn_init_kernel(int n, int k, int warm, double lambda, const double *__restrict__ B,
+template <int KMAX, int VEC, typename LAM = double>
+__global__ __launch_bounds__(kRedThreads) void pcgn_init_kernel(int n, int k, int warm, LAM lambda, const double *__restrict__ B,
                                                                double *__restrict__ X, double *__restrict__ R,
                                                                double *__restrict__ Q, double *__restrict__ part)
 {
@@ -732,9 +744,15 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_init_kernel(int n, int k, in
         const Pair b = bv[h], x = xv[h], q0 = qv[h];
         Pair r = b;
         if (warm) {
-          const Pair q = {q0.a + lambda * x.a, q0.b + lambda * x.b};
-          pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
-          r = {b.a - q.a, b.b - q.b};
+          if constexpr (pn_cols<LAM>) {
+            const Pair q = {q0.a + lambda.v[c] * x.a, q0.b + lambda.v[c + 1] * x.b};
+            pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
+            r = {b.a - q.a, b.b - q.b};
+          } else {
+            const Pair q = {q0.a + lambda * x.a, q0.b + lambda * x.b};
+            pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
+            r = {b.a - q.a, b.b - q.b};
+          }
         } else {
           pn_st<VEC == 2>(X + row + c, {0.0, 0.0}, l0, l1);
         }
@@ -749,10 +767,11 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_init_kernel(int n, int k, in
 
 // P = Z = R dinv (dinv != NULL) or R, partial r.z per live column (pcg_start_kernel).  Every column gets its first direction, the
 // ones that are done at the start too: their P is finite when it rides through the products
-template <int KMAX, int VEC>
+template <int KMAX, int VEC, typename... LAM>
 __global__ __launch_bounds__(kRedThreads) void pcgn_start_kernel(int n, int k, const double *__restrict__ R,
                                                                 const double *__restrict__ dinv, double *__restrict__ P,
-                                                                double *__restrict__ part, const double *__restrict__ st)
+                                                                double *__restrict__ part, const double *__restrict__ st,
+                                                                LAM... lambda)
 {
   if (st[kStDone] != 0.0) return;
   constexpr int TP = pcgn_tile<KMAX>() / 2;
@@ -768,9 +787,15 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_start_kernel(int n, int k, c
       pcgn_ld_tile<KMAX, VEC >= 1>(rv, R + row, c0, k);
       pcgn_tile_pairs<KMAX>(c0, k, all, [&](int h, int c, bool l0, bool l1) {
         const Pair r = rv[h];
-        const Pair z = {dinv ? r.a * di : r.a, dinv ? r.b * di : r.b};
-        pn_st<VEC >= 1>(P + row + c, z, l0, l1);
-        rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;
+        if constexpr (sizeof...(LAM) != 0) {
+          const Pair z = {r.a * pn_inv(di, lambda.v[c]...), r.b * pn_inv(di, lambda.v[c + 1]...)};
+          pn_st<VEC >= 1>(P + row + c, z, l0, l1);
+          rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;
+        } else {
+          const Pair z = {dinv ? r.a * di : r.a, dinv ? r.b * di : r.b};
+          pn_st<VEC >= 1>(P + row + c, z, l0, l1);
+          rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;
+        }
       });
     });
   }
@@ -778,8 +803,8 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_start_kernel(int n, int k, c
 }
 
 // Q += lambda P, partial q.p per live column (cg_shift_dot_dev_kernel)
-template <int KMAX, int VEC>
-__global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_kernel(int n, int k, double lambda, double *__restrict__ Q,
+template <int KMAX, int VEC, typename LAM = double>
+__global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_kernel(int n, int k, LAM lambda, double *__restrict__ Q,
                                                                     const double *__restrict__ P, double *__restrict__ part,
                                                                     const double *__restrict__ st)
 {
@@ -797,9 +822,15 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_kernel(int n, int 
       pcgn_ld_tile<KMAX, VEC >= 1>(qv, Q + row, c0, k);
       pcgn_tile_pairs<KMAX>(c0, k, live, [&](int h, int c, bool l0, bool l1) {
         const Pair p = pv[h], q0 = qv[h];
-        const Pair q = {q0.a + lambda * p.a, q0.b + lambda * p.b};
-        pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
-        qp[c] += q.a * p.a; qp[c + 1] += q.b * p.b;
+        if constexpr (pn_cols<LAM>) {
+          const Pair q = {q0.a + lambda.v[c] * p.a, q0.b + lambda.v[c + 1] * p.b};
+          pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
+          qp[c] += q.a * p.a; qp[c + 1] += q.b * p.b;
+        } else {
+          const Pair q = {q0.a + lambda * p.a, q0.b + lambda * p.b};
+          pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
+          qp[c] += q.a * p.a; qp[c + 1] += q.b * p.b;
+        }
       });
     });
   }
@@ -808,11 +839,12 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_kernel(int n, int 
 
 // per live column: x += alpha p, r -= alpha q, partial r.r; with a preconditioner z = r dinv and partial r.z in the same pass
 // (pcg_update_kernel / cg_update_dev_kernel)
-template <int KMAX, int VEC>
+template <int KMAX, int VEC, typename... LAM>
 __global__ __launch_bounds__(kRedThreads) void pcgn_update_kernel(int n, int k, double *__restrict__ X, double *__restrict__ R,
                                                                  const double *__restrict__ P, const double *__restrict__ Q,
                                                                  const double *__restrict__ dinv, double *__restrict__ part,
-                                                                 const double *__restrict__ st, const double *__restrict__ cs)
+                                                                 const double *__restrict__ st, const double *__restrict__ cs,
+                                                                 LAM... lambda)
 {
   if (st[kStDone] != 0.0) return;
   constexpr int TP = pcgn_tile<KMAX>() / 2;
@@ -836,7 +868,10 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_update_kernel(int n, int k, 
         pn_st<VEC == 2>(X + row + c, x, l0, l1);
         pn_st<VEC >= 1>(R + row + c, r, l0, l1);
         rr[c] += r.a * r.a; rr[c + 1] += r.b * r.b;
-        if (dinv) {
+        if constexpr (sizeof...(LAM) != 0) {
+          const Pair z = {r.a * pn_inv(di, lambda.v[c]...), r.b * pn_inv(di, lambda.v[c + 1]...)};
+          rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;
+        } else if (dinv) {
           const Pair z = {r.a * di, r.b * di};
           rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;
         }
@@ -847,10 +882,10 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_update_kernel(int n, int k, 
 }
 
 // per live column: p = z + beta p with z = r dinv formed on the fly, or p = r + beta p (pcg_direction_kernel / cg_direction_dev_kernel)
-template <int KMAX, int VEC>
+template <int KMAX, int VEC, typename... LAM>
 __global__ __launch_bounds__(kRedThreads) void pcgn_direction_kernel(int n, int k, double *__restrict__ P, const double *__restrict__ R,
                                                                     const double *__restrict__ dinv, const double *__restrict__ st,
-                                                                    const double *__restrict__ cs)
+                                                                    const double *__restrict__ cs, LAM... lambda)
 {
   if (st[kStDone] != 0.0) return;
   constexpr int TP = pcgn_tile<KMAX>() / 2;
@@ -867,9 +902,15 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_direction_kernel(int n, int 
       pcgn_ld_tile<KMAX, VEC >= 1>(pv, P + row, c0, k);
       pcgn_tile_pairs<KMAX>(c0, k, live, [&](int h, int c, bool l0, bool l1) {
         const Pair r = rv[h], p0 = pv[h];
-        const Pair z = {dinv ? r.a * di : r.a, dinv ? r.b * di : r.b};
-        const Pair p = {z.a + be[c] * p0.a, z.b + be[c + 1] * p0.b};
-        pn_st<VEC >= 1>(P + row + c, p, l0, l1);
+        if constexpr (sizeof...(LAM) != 0) {
+          const Pair z = {r.a * pn_inv(di, lambda.v[c]...), r.b * pn_inv(di, lambda.v[c + 1]...)};
+          const Pair p = {z.a + be[c] * p0.a, z.b + be[c + 1] * p0.b};
+          pn_st<VEC >= 1>(P + row + c, p, l0, l1);
+        } else {
+          const Pair z = {dinv ? r.a * di : r.a, dinv ? r.b * di : r.b};
+          const Pair p = {z.a + be[c] * p0.a, z.b + be[c + 1] * p0.b};
+          pn_st<VEC >= 1>(P + row + c, p, l0, l1);
+        }
       });
     });
   }
@@ -936,9 +977,18 @@ __device__ __forceinline__ void pl_out(double *__restrict__ g, const double *__r
   }
 }
 
-// Q += lambda P, partial q.p per live column
+// the staged kernels of the per-column form keep the k lambdas in LDS: a lane reads lam[c] as a broadcast, and no scalar registers
+// are held across the tile loop (with the lambdas in SGPRs the shift-dot kernel at KMAX = 32 went from 128 to 130 VGPRs, from four
+// waves per SIMD to three and from 1.6 to 2.7 ms).  Read behind the tile loop's first barrier
 template <int KMAX>
-__global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_lds_kernel(int n, int k, double lambda, double *__restrict__ Q,
+__device__ __forceinline__ void pl_lambdas(double *__restrict__ lam, const PcgnLambdas &lambda)
+{
+  if (threadIdx.x < KMAX) lam[threadIdx.x] = lambda.v[threadIdx.x];
+}
+
+// Q += lambda P, partial q.p per live column
+template <int KMAX, typename LAM = double>
+__global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_lds_kernel(int n, int k, LAM lambda, double *__restrict__ Q,
                                                                         const double *__restrict__ P, double *__restrict__ part,
                                                                         const double *__restrict__ st)
 {
@@ -946,6 +996,8 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_lds_kernel(int n, 
   constexpr int LD = KMAX + 1;
   constexpr int TR = pl_rows<KMAX>();
   __shared__ double t0[TR * LD], t1[TR * LD];
+  __shared__ double lam[pn_cols<LAM> ? KMAX : 1];
+  if constexpr (pn_cols<LAM>) pl_lambdas<KMAX>(lam, lambda);
   const unsigned live = pcgn_live(st);
   double qp[KMAX];
 #pragma unroll
@@ -964,9 +1016,15 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_lds_kernel(int n, 
       for (int c = 0; c < KMAX; ++c)
         if (c < k && ((live >> c) & 1u) != 0u) {
           const double pi = p[c];
-          const double qi = q[c] + lambda * pi;
-          q[c] = qi;
-          qp[c] += qi * pi;
+          if constexpr (pn_cols<LAM>) {
+            const double qi = q[c] + lam[c] * pi;
+            q[c] = qi;
+            qp[c] += qi * pi;
+          } else {
+            const double qi = q[c] + lambda * pi;
+            q[c] = qi;
+            qp[c] += qi * pi;
+          }
         }
     }
     __syncthreads();
@@ -977,16 +1035,19 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_lds_kernel(int n, 
 }
 
 // per live column: x += alpha p, then r -= alpha q with the partials of r.r and, with a preconditioner, of r.z (z = r dinv)
-template <int KMAX>
+template <int KMAX, typename... LAM>
 __global__ __launch_bounds__(kRedThreads) void pcgn_update_lds_kernel(int n, int k, double *__restrict__ X, double *__restrict__ R,
                                                                      const double *__restrict__ P, const double *__restrict__ Q,
                                                                      const double *__restrict__ dinv, double *__restrict__ part,
-                                                                     const double *__restrict__ st, const double *__restrict__ cs)
+                                                                     const double *__restrict__ st, const double *__restrict__ cs,
+                                                                     LAM... lambda)
 {
   if (st[kStDone] != 0.0) return;
   constexpr int LD = KMAX + 1;
   constexpr int TR = pl_rows<KMAX>();
   __shared__ double t0[TR * LD], t1[TR * LD];
+  __shared__ double lam[sizeof...(LAM) != 0 ? KMAX : 1];
+  if constexpr (sizeof...(LAM) != 0) pl_lambdas<KMAX>(lam, lambda...);
   const unsigned live = pcgn_live(st);
   double rr[KMAX], rz[KMAX], al[KMAX];
 #pragma unroll
@@ -1018,10 +1079,17 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_update_lds_kernel(int n, int
 #pragma unroll
       for (int c = 0; c < KMAX; ++c)
         if (c < k && ((live >> c) & 1u) != 0u) {
-          const double ri = r[c] - al[c] * q[c];
-          r[c] = ri;
-          rr[c] += ri * ri;
-          if (dinv) { const double zi = ri * di; rz[c] += ri * zi; }
+          if constexpr (sizeof...(LAM) != 0) {
+            const double ri = r[c] - al[c] * q[c];
+            r[c] = ri;
+            rr[c] += ri * ri;
+            const double zi = ri * pn_inv(di, lam[c]); rz[c] += ri * zi;
+          } else {
+            const double ri = r[c] - al[c] * q[c];
+            r[c] = ri;
+            rr[c] += ri * ri;
+            if (dinv) { const double zi = ri * di; rz[c] += ri * zi; }
+          }
         }
     }
     __syncthreads();
@@ -1032,15 +1100,17 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_update_lds_kernel(int n, int
 }
 
 // per live column: p = z + beta p with z = r dinv formed on the fly, or p = r + beta p
-template <int KMAX>
+template <int KMAX, typename... LAM>
 __global__ __launch_bounds__(kRedThreads) void pcgn_direction_lds_kernel(int n, int k, double *__restrict__ P, const double *__restrict__ R,
                                                                         const double *__restrict__ dinv, const double *__restrict__ st,
-                                                                        const double *__restrict__ cs)
+                                                                        const double *__restrict__ cs, LAM... lambda)
 {
   if (st[kStDone] != 0.0) return;
   constexpr int LD = KMAX + 1;
   constexpr int TR = pl_rows<KMAX>();
   __shared__ double t0[TR * LD], t1[TR * LD];
+  __shared__ double lam[sizeof...(LAM) != 0 ? KMAX : 1];
+  if constexpr (sizeof...(LAM) != 0) pl_lambdas<KMAX>(lam, lambda...);
   const unsigned live = pcgn_live(st);
   double be[KMAX];
 #pragma unroll
@@ -1059,8 +1129,13 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_direction_lds_kernel(int n, 
 #pragma unroll
       for (int c = 0; c < KMAX; ++c)
         if (c < k && ((live >> c) & 1u) != 0u) {
-          const double zi = dinv ? r[c] * di : r[c];
-          p[c] = zi + be[c] * p[c];
+          if constexpr (sizeof...(LAM) != 0) {
+            const double zi = r[c] * pn_inv(di, lam[c]);
+            p[c] = zi + be[c] * p[c];
+          } else {
+            const double zi = dinv ? r[c] * di : r[c];
+            p[c] = zi + be[c] * p[c];
+          }
         }
     }
     __syncthreads();
@@ -1323,42 +1398,59 @@ int pcgn_dev_clear(double *cs, hipStream_t s)     // slots a column never writes
   return FS_OK;
 }
 
-// cold: X = 0, R = B; warm (Q = A'(A X) on entry): Q += lambda X, R = B - Q; b.b, r.r, stop, live? per column; P = Z = R dinv, r.z
-int pcgn_dev_init(int n, int k, bool warm, double lambda, const double *B, double *X, double *R, double *P, double *Q, const double *dinv,
-                  double *part, double *st, double *cs, double tol, hipStream_t s)
+// cold: X = 0, R = B; warm (Q = A'(A X) on entry): Q += lambda X, R = B - Q; b.b, r.r, stop, live? per column; P = Z = R dinv, r.z.
+// LAM: the solve's one lambda (double: fs_pcgn's instantiations) or its k (PcgnLambdas: fs_pcgn_lambdas).  colj: nothing, or the
+// k lambdas again when dinv holds s = diag(A'A) and the kernels invert s + lambda_c per element; without it the kernels behind
+// the first one see no lambda and are fs_pcgn's own
+template <typename LAM, typename... CJ>
+static int pcgn_init_launch(int n, int k, bool warm, const LAM &lambda, const double *B, double *X, double *R, double *P, double *Q,
+                            const double *dinv, double *part, double *st, double *cs, double tol, hipStream_t s, CJ... colj)
 {
   const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
   return pcgn_dispatch(k, pcgn_vec(k, X, B), [&](auto sh) -> int {
     using S = decltype(sh);
-    hipLaunchKernelGGL((pcgn_init_kernel<S::kmax, S::vec>), g, blk, 0, s, n, k, (int)warm, lambda, B, X, R, Q, part);
+    hipLaunchKernelGGL((pcgn_init_kernel<S::kmax, S::vec, LAM>), g, blk, 0, s, n, k, (int)warm, lambda, B, X, R, Q, part);
     hipLaunchKernelGGL(pcgn_step_kernel<kPnStepStart>, one, blk, 0, s, part, st, cs, k, 2, tol);           // b.b, r.r, stop, live?
-    hipLaunchKernelGGL((pcgn_start_kernel<S::kmax, S::vec>), g, blk, 0, s, n, k, R, dinv, P, part, st);
+    hipLaunchKernelGGL((pcgn_start_kernel<S::kmax, S::vec, CJ...>), g, blk, 0, s, n, k, R, dinv, P, part, st, colj...);
     hipLaunchKernelGGL(pcgn_step_kernel<kPnStepRz>, one, blk, 0, s, part, st, cs, k, 1, 0.0);              // r.z
     FS_HIP(hipGetLastError());
     return FS_OK;
   });
 }
 
-// everything of an iteration behind Q = A'(A P); option "pcgn_kernel" picks the form of the vector kernels
-int pcgn_dev_steps(int n, int k, double lambda, double *X, const double *B, double *R, double *P, double *Q, const double *dinv,
-                   double *part, double *st, double *cs, hipStream_t s)
+// everything of an iteration behind Q = A'(A P); option "pcgn_kernel" picks the form of the vector kernels.  LAM, colj: as above
+template <typename LAM, typename... CJ>
+static int pcgn_steps_launch(int n, int k, const LAM &lambda, double *X, const double *B, double *R, double *P, double *Q,
+                             const double *dinv, double *part, double *st, double *cs, hipStream_t s, CJ... colj)
 {
   const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
   const int which = options().pcgn_kernel;
   const bool staged = which == 2 || (which == 0 && k > kPcgnRowsMaxK);
   return pcgn_dispatch(k, pcgn_vec(k, X, B), [&](auto sh) -> int {
     using S = decltype(sh);
-    if (staged) hipLaunchKernelGGL(pcgn_shift_dot_lds_kernel<S::kmax>, g, blk, 0, s, n, k, lambda, Q, P, part, st);
-    else        hipLaunchKernelGGL((pcgn_shift_dot_kernel<S::kmax, S::vec>), g, blk, 0, s, n, k, lambda, Q, P, part, st);
+    if (staged) hipLaunchKernelGGL((pcgn_shift_dot_lds_kernel<S::kmax, LAM>), g, blk, 0, s, n, k, lambda, Q, P, part, st);
+    else        hipLaunchKernelGGL((pcgn_shift_dot_kernel<S::kmax, S::vec, LAM>), g, blk, 0, s, n, k, lambda, Q, P, part, st);
     hipLaunchKernelGGL(pcgn_step_kernel<kPnStepAlpha>, one, blk, 0, s, part, st, cs, k, 1, 0.0);          // alpha = r.z / p.q
-    if (staged) hipLaunchKernelGGL(pcgn_update_lds_kernel<S::kmax>, g, blk, 0, s, n, k, X, R, P, Q, dinv, part, st, cs);
-    else        hipLaunchKernelGGL((pcgn_update_kernel<S::kmax, S::vec>), g, blk, 0, s, n, k, X, R, P, Q, dinv, part, st, cs);
+    if (staged) hipLaunchKernelGGL((pcgn_update_lds_kernel<S::kmax, CJ...>), g, blk, 0, s, n, k, X, R, P, Q, dinv, part, st, cs, colj...);
+    else        hipLaunchKernelGGL((pcgn_update_kernel<S::kmax, S::vec, CJ...>), g, blk, 0, s, n, k, X, R, P, Q, dinv, part, st, cs, colj...);
     hipLaunchKernelGGL(pcgn_step_kernel<kPnStepBeta>, one, blk, 0, s, part, st, cs, k, dinv ? 2 : 1, 0.0); // converged? beta
-    if (staged) hipLaunchKernelGGL(pcgn_direction_lds_kernel<S::kmax>, g, blk, 0, s, n, k, P, R, dinv, st, cs);
-    else        hipLaunchKernelGGL((pcgn_direction_kernel<S::kmax, S::vec>), g, blk, 0, s, n, k, P, R, dinv, st, cs);
+    if (staged) hipLaunchKernelGGL((pcgn_direction_lds_kernel<S::kmax, CJ...>), g, blk, 0, s, n, k, P, R, dinv, st, cs, colj...);
+    else        hipLaunchKernelGGL((pcgn_direction_kernel<S::kmax, S::vec, CJ...>), g, blk, 0, s, n, k, P, R, dinv, st, cs, colj...);
     FS_HIP(hipGetLastError());
     return FS_OK;
   });
+}
+
+int pcgn_dev_init(int n, int k, bool warm, double lambda, const double *B, double *X, double *R, double *P, double *Q, const double *dinv,
+                  double *part, double *st, double *cs, double tol, hipStream_t s)
+{
+  return pcgn_init_launch(n, k, warm, lambda, B, X, R, P, Q, dinv, part, st, cs, tol, s);
+}
+
+int pcgn_dev_steps(int n, int k, double lambda, double *X, const double *B, double *R, double *P, double *Q, const double *dinv,
+                   double *part, double *st, double *cs, hipStream_t s)
+{
+  return pcgn_steps_launch(n, k, lambda, X, B, R, P, Q, dinv, part, st, cs, s);
 }
 
 // ---- fs_mscg's steps as launchers (fs_mscg; fs_dist_mscg on every rank: whole vectors, or the rank's slice of r, p, q, the x_i
@@ -1680,6 +1772,62 @@ struct CgSolve {
   }
 };
 
+// fs_pcgn's frame, and fs_pcgn_lambdas' (lams: k doubles on the host; lambda is not read then).  The two differ in the lambda the
+// kernels take and in what FS_PRECOND_JACOBI leaves in `dinv`: the inverse of fs_gram_diag(At, lambda), or s = fs_gram_diag(At, 0)
+// itself, which the per-column kernels invert as s + lambda_c per element (no pcg_dev_dinv pass)
+static int pcgn_solve(const char *who, fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k, double lambda,
+                      const double *lams, const fs_pcg_params *prm, fs_pcg_info *info, fs_stream_t stream)
+{
+  const std::string w(who);
+  if (k < 1 || k > kPcgnMaxRhs) { set_error(w + ": k outside 1..FS_PCGN_MAX_RHS"); return FS_ERR_ARG; }
+  CgSolve f{who, A, At, k, stream};
+  if (int rc = f.shape()) return rc;
+  if (int rc = pcg_params_ok(who, prm)) return rc;
+  PcgnLambdas lv = {};
+  for (int j = 0; lams && j < k; ++j) {
+    if (!isfinite(lams[j])) { set_error(w + ": a lambda is NaN or infinite"); return FS_ERR_ARG; }
+    lv.v[j] = lams[j];
+  }
+  if (prm->precond == FS_PRECOND_JACOBI)                     // before anything is written to X
+    if (int rc = need_plain_csr(At->a, (w + " with FS_PRECOND_JACOBI (fs_gram_diag)").c_str())) return rc;
+  if (k >= 2) {                                              // the k-column copies of both matrices (fs_spmm itself never builds)
+    if (int rc = fs_matrix_prepare(A, k, 0, stream)) return rc;
+    if (int rc = fs_matrix_prepare(At, k, 0, stream)) return rc;
+  }
+  if (int rc = f.ready()) return rc;
+  const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
+  const bool colj = lams && prm->precond == FS_PRECOND_JACOBI;   // the diagonal follows the column: dinv holds s
+  const int F = f.F;
+  const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
+  hipStream_t s = (hipStream_t)stream;
+  double *dinv = nullptr, *own = nullptr;
+  const size_t npart = (size_t)kRedBlocks * 2 * k;
+  if (int rc = f.alloc(pre ? &dinv : nullptr, F, &own, npart + kPcgnMaxRhs * kPnStride)) return rc;
+  double *r = f.r, *p = f.p, *q = f.q, *st = f.st, *part = own, *cs = own + npart;
+  if (int rc = pcgn_dev_clear(cs, s)) return rc;
+  if (prm->precond == FS_PRECOND_JACOBI)
+    if (int rc = fs_gram_diag(At, colj ? 0.0 : lambda, dinv, stream)) return rc;
+  if (pre && !colj)
+    if (int rc = pcg_dev_dinv(F, prm->precond == FS_PRECOND_DIAG ? prm->diag : dinv, dinv, s)) return rc;
+  if (warm) {                                                // R = B - (A'(A X) + lambda X): one pair of k-column products
+    if (int rc = k == 1 ? fs_spmv(A, f.tmp, X, stream) : fs_spmm(A, f.tmp, X, k, stream)) return rc;
+    if (int rc = k == 1 ? fs_spmv(At, q, f.tmp, stream) : fs_spmm(At, q, f.tmp, k, stream)) return rc;
+  }
+  if (int rc = colj   ? pcgn_init_launch(F, k, warm, lv, B, X, r, p, q, dinv, part, st, cs, prm->tol, s, lv)
+               : lams ? pcgn_init_launch(F, k, warm, lv, B, X, r, p, q, dinv, part, st, cs, prm->tol, s)
+                      : pcgn_dev_init(F, k, warm, lambda, B, X, r, p, q, dinv, part, st, cs, prm->tol, s)) return rc;
+  if (int rc = f.iterate(cap, true, [&] {
+        return colj   ? pcgn_steps_launch(F, k, lv, X, B, r, p, q, dinv, part, st, cs, s, lv)
+               : lams ? pcgn_steps_launch(F, k, lv, X, B, r, p, q, dinv, part, st, cs, s)
+                      : pcgn_dev_steps(F, k, lambda, X, B, r, p, q, dinv, part, st, cs, s);
+      })) return rc;
+  double fcs[kPcgnMaxRhs * kPnStride] = {0.0};
+  FS_HIP(hipMemcpyAsync(fcs, cs, sizeof(double) * k * kPnStride, hipMemcpyDeviceToHost, s));
+  if (int rc = f.finish()) return rc;
+  pcgn_note_state(f.fin, fcs, k, info);
+  return FS_OK;
+}
+
 extern "C" {
 
 // y += a x on device vectors (the "+ lambda x" of bsbm_AtA, cg.h:17-21)
@@ -1806,41 +1954,17 @@ int fs_pcgn(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k, do
 {
   FS_RANGE("fs_pcgn");
   if (!A || !At || !X || !B || !prm) { set_error("fs_pcgn: NULL argument"); return FS_ERR_ARG; }
-  if (k < 1 || k > kPcgnMaxRhs) { set_error("fs_pcgn: k outside 1..FS_PCGN_MAX_RHS"); return FS_ERR_ARG; }
-  CgSolve f{"fs_pcgn", A, At, k, stream};
-  if (int rc = f.shape()) return rc;
-  if (int rc = pcg_params_ok("fs_pcgn", prm)) return rc;
-  if (prm->precond == FS_PRECOND_JACOBI)                     // before anything is written to X
-    if (int rc = need_plain_csr(At->a, "fs_pcgn with FS_PRECOND_JACOBI (fs_gram_diag)")) return rc;
-  if (k >= 2) {                                              // the k-column copies of both matrices (fs_spmm itself never builds)
-    if (int rc = fs_matrix_prepare(A, k, 0, stream)) return rc;
-    if (int rc = fs_matrix_prepare(At, k, 0, stream)) return rc;
-  }
-  if (int rc = f.ready()) return rc;
-  const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
-  const int F = f.F;
-  const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
-  hipStream_t s = (hipStream_t)stream;
-  double *dinv = nullptr, *own = nullptr;
-  const size_t npart = (size_t)kRedBlocks * 2 * k;
-  if (int rc = f.alloc(pre ? &dinv : nullptr, F, &own, npart + kPcgnMaxRhs * kPnStride)) return rc;
-  double *r = f.r, *p = f.p, *q = f.q, *st = f.st, *part = own, *cs = own + npart;
-  if (int rc = pcgn_dev_clear(cs, s)) return rc;
-  if (prm->precond == FS_PRECOND_JACOBI)
-    if (int rc = fs_gram_diag(At, lambda, dinv, stream)) return rc;
-  if (pre)
-    if (int rc = pcg_dev_dinv(F, prm->precond == FS_PRECOND_DIAG ? prm->diag : dinv, dinv, s)) return rc;
-  if (warm) {                                                // R = B - (A'(A X) + lambda X): one pair of k-column products
-    if (int rc = k == 1 ? fs_spmv(A, f.tmp, X, stream) : fs_spmm(A, f.tmp, X, k, stream)) return rc;
-    if (int rc = k == 1 ? fs_spmv(At, q, f.tmp, stream) : fs_spmm(At, q, f.tmp, k, stream)) return rc;
-  }
-  if (int rc = pcgn_dev_init(F, k, warm, lambda, B, X, r, p, q, dinv, part, st, cs, prm->tol, s)) return rc;
-  if (int rc = f.iterate(cap, true, [&] { return pcgn_dev_steps(F, k, lambda, X, B, r, p, q, dinv, part, st, cs, s); })) return rc;
-  double fcs[kPcgnMaxRhs * kPnStride] = {0.0};
-  FS_HIP(hipMemcpyAsync(fcs, cs, sizeof(double) * k * kPnStride, hipMemcpyDeviceToHost, s));
-  if (int rc = f.finish()) return rc;
-  pcgn_note_state(f.fin, fcs, k, info);
-  return FS_OK;
+  return pcgn_solve("fs_pcgn", A, At, X, B, k, lambda, nullptr, prm, info, stream);
+}
+
+// (A'A + lambda[j] I) x_j = b_j for j < k: fs_pcgn with a lambda per column, and under FS_PRECOND_JACOBI a diagonal per column.
+// Column j has the bits of fs_pcg at lambda[j] where fs_pcgn's column has those of fs_pcg; with equal lambdas it is fs_pcgn.
+int fs_pcgn_lambdas(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k, const double *lambda, const fs_pcg_params *prm,
+                    fs_pcg_info *info, fs_stream_t stream)
+{
+  FS_RANGE("fs_pcgn_lambdas");
+  if (!A || !At || !X || !B || !prm || !lambda) { set_error("fs_pcgn_lambdas: NULL argument"); return FS_ERR_ARG; }
+  return pcgn_solve("fs_pcgn_lambdas", A, At, X, B, k, 0.0, lambda, prm, info, stream);
 }
 
 // two right-hand sides, X and B row-major F x 2 (cg.h:85-187)

@@ -405,6 +405,7 @@ int cg2_dev_finish(int n, const double *norms, double *X, hipStream_t s);
 // ---- fs_pcgn's steps on row-major n x k panels; part: pcgn_part_doubles(k) doubles, cs: kPcgnStateDoubles, st as above
 constexpr int kPcgnStateDoubles = FS_PCGN_MAX_RHS * 16;
 constexpr size_t pcgn_part_doubles(int k) { return (size_t)1024 * 2 * (size_t)k; }
+struct PcgnLambdas { double v[FS_PCGN_MAX_RHS]; };   // fs_pcgn_lambdas' k lambdas, a kernel argument by value (like MscgSigma)
 int pcgn_dev_clear(double *cs, hipStream_t s);
 int pcgn_dev_init(int n, int k, bool warm, double lambda, const double *B, double *X, double *R, double *P, double *Q, const double *dinv,
                   double *part, double *st, double *cs, double tol, hipStream_t s);
