@@ -30,6 +30,18 @@ def _window_check(capi, O, rp, cc, vv, x, y, lo, hi, exact):
         assert np.all(np.abs(got - ref) <= 1e-12 * np.maximum(scale, 1e-300))
 
 
+def _assert_large_bands(capi, A, ncol):
+    """a kept two-pass copy of A is the large-band form: bands of 19 456 columns (fs_geometry.h kBinColsBig), not of 16 384"""
+    import ctypes as C
+    if A.kernel_name() != "two-pass":
+        return
+    L = capi.lib()
+    L.fs_debug_two_pass_layout.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_ulonglong)]
+    lay = (C.c_ulonglong * 8)()
+    assert L.fs_debug_two_pass_layout(A.h, 0, lay) == 0
+    assert int(lay[6]) == -(-ncol // 19456) != -(-ncol // 16384), (int(lay[6]), ncol)
+
+
 def test_config2_fp64_csr_10m(hip_env):
     """BASELINE config 2: CSR 10M x 10M, 16 nnz/row, A_mul_B and At_mul_B"""
     torch, capi, O = hip_env
@@ -177,6 +189,7 @@ def test_config5_one_real_shard_rank3_of_8(hip_env):
     nrow, ncol = hi - lo, n_global
     assert nnz == per[3] and 3.7e8 < nnz < 4.3e8 and 1.1e7 < nrow < 1.4e7
     A = capi.Matrix.from_csr(nrow, ncol, rp, cc, vv, borrow=True)
+    _assert_large_bands(capi, A, ncol)
     st = capi.current_stream()
     x = torch.sin(7.0 * torch.arange(ncol, device="cuda", dtype=torch.float64) + 0.3)
     y = torch.full((nrow,), -1.0, dtype=torch.float64, device="cuda")
@@ -199,6 +212,7 @@ def test_config5_one_real_shard_rank3_of_8(hip_env):
     kernel = A.kernel_name()
     del A, y2
     Ap = capi.Matrix.from_csr(nrow, ncol, rp, cc, None, borrow=True)
+    _assert_large_bands(capi, Ap, ncol)
     xi = _int_x(ncol, "cuda", 9)
     Ap.spmv(y, xi, st)
     total_i = 0
