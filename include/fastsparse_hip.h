@@ -506,8 +506,8 @@ int  fs_dist_gram_diag(fs_dist_matrix_t M, double lambda, double *d /* ncol */);
  * shard of A' gave its plain CSR back (FS_PRECOND_DIAG with a diagonal kept from before still solves).  Every one of them is raised
  * before anything is written to x.  CLOBBERS fs_dist_x / fs_dist_y / fs_dist_z like fs_dist_cg. */
 int  fs_dist_pcg(fs_dist_matrix_t M, double *x, const double *b, double lambda, const fs_pcg_params *prm, fs_pcg_info *info /* or NULL */);
-/* fs_dist_pcgn: fs_pcgn, k in 1..FS_PCGN_MAX_RHS.  Replicated on every rank WHATEVER "dist_cg_scheme" says (there is no slice-wise
- * form of the k-column vector kernels): whole ncol x k panels per rank, fs_pcgn's own kernels (option "pcgn_kernel", the live mask,
+/* fs_dist_pcgn: fs_pcgn, k in 1..FS_PCGN_MAX_RHS.  Replicated on every rank WHATEVER "dist_cg_scheme" says (the slice-wise form is
+ * fs_dist_pcgn_lambdas with equal lambdas): whole ncol x k panels per rank, fs_pcgn's own kernels (option "pcgn_kernel", the live mask,
  * freezing) on them, T = A P and Q = A' T as the sharded k-column products of fs_dist_spmm (k = 1: fs_dist_spmv's).  Column j is
  * fs_pcgn's column j and therefore fs_pcg on B[:, j] wherever the sharded k-column product has the single-vector product's bits
  * ("strict_order"; k = 1 in every mode).  Convergence across the ranks, a solve done before its first iteration, the fixed order of
@@ -516,6 +516,36 @@ int  fs_dist_pcg(fs_dist_matrix_t M, double *x, const double *b, double lambda, 
  * to X. */
 int  fs_dist_pcgn(fs_dist_matrix_t M, double *X, const double *B, int k, double lambda, const fs_pcg_params *prm,
                   fs_pcg_info *info /* k entries or NULL */);
+/* fs_dist_pcgn_lambdas: fs_pcgn_lambdas on the sharded matrix -- (A'A + lambda[j] I) x_j = b_j for j < k, k in
+ * 1..FS_PCGN_MAX_RHS.  Its arithmetic is fs_pcgn_lambdas' above, whose text is the single statement of it; this says only what
+ * differs.  X, B, the transposed side, the statuses, a solve done at its start, the work space kept on the handle and the clobbered
+ * vectors are fs_dist_pcgn's; lambda: k doubles on the host, a NULL, NaN or infinite one is FS_ERR_ARG.  Unlike fs_dist_pcgn it
+ * honours option "dist_cg_scheme"; slices only with more than one rank:
+ *   0  fs_dist_pcgn's frame with fs_pcgn_lambdas' instantiations of the kernels on whole panels.  Under FS_PRECOND_JACOBI the work
+ *      vector holds s = fs_gram_diag of A' at 0.0, all-gathered once; there is no inverse pass.  `red_j` is fs_pcgn's: under
+ *      "strict_order" X, the infos, st[] and the per-column scalars are fs_pcgn_lambdas' on the same CSRs, bit for bit, for any number
+ *      of ranks; with equal lambdas the solve is fs_dist_pcgn, bit for bit.
+ *   1  rank r keeps its rows [lo_r, hi_r) = fs_dist_matrix_bounds_t of X, R, B, Q and of s / dinv: contiguous (hi_r - lo_r) k
+ *      doubles of the row-major panels.  P and T = A P stay whole on every rank (the product's input and output); the rank's slice
+ *      of P lives in the exchange's own send buffer.  T = A P is one sharded k-column product with its all-gather, Q_r = A'_r T the
+ *      rank's own shard product (fs_spmm on fs_dist_matrix_shard(M, r, 1); fs_spmv for k = 1): no exchange.  Jacobi's slice of s is
+ *      the rank's own fs_gram_diag launch.  `red_j` is the slice tree of fs_dist_cg, per column: every rank reduces its slice with
+ *      fs_cg's two stages (row indices local to the slice, an empty slice gives +0.0), the rank values are all-gathered and every
+ *      rank adds them in rank order with the second stage.  The sums fs_pcgn takes in one pass travel in one exchange of ns k
+ *      doubles per rank ({bb_j, rr_j} at the start, {rr_j, rzn_j} with a preconditioner, one sum otherwise; a frozen column's slots
+ *      are sent as +0.0 and never read), so an iteration has two small exchanges and the all-gather of the new P slices, like
+ *      fs_dist_pcg.  The first P is Z = R dinv, which only the owner of a row can form: it is gathered too, also on a cold start.
+ *      Every rank runs the per-column scalar step over the same gathered values, so alpha_j, beta_j, the freezes and the live mask
+ *      are identical everywhere.  A warm start takes the whole X0 as the product's input plus the rank's slice; T = A X0 is one
+ *      sharded product, Q_r = A'_r T local.  Every other line is fs_pcgn_lambdas'.  Work space per rank: five slices of n_r k
+ *      doubles (X, R, B, Q, and P in the send buffer), the whole P (ncol k) and T (nrow k), the slice of s / dinv, the partials,
+ *      two send slots of 2 FS_PCGN_MAX_RHS doubles and N times that for the gathered values.
+ * Besides {done, iterations}, compared one iteration behind, every rank's final live mask and per-column {live, converged, count}
+ * must agree with rank 0's: a disagreement is an error return (FS_ERR_HIP).  A solve that is done at its start enqueues no product
+ * and freezes every column at its start as fs_pcgn does (b_j = 0: x_j = 0; a warm column keeps x0_j).  A product's own error is
+ * passed through with X untouched.  fs_debug_last_cg_state and fs_debug_last_pcgn_state report rank 0's. */
+int  fs_dist_pcgn_lambdas(fs_dist_matrix_t M, double *X, const double *B, int k, const double *lambda /* k doubles on the HOST */,
+                          const fs_pcg_params *prm, fs_pcg_info *info /* k entries or NULL */);
 /* fs_dist_mscg: fs_mscg on the sharded matrix -- (A'A + lambda[i] I) x_i = b for i < m from one Krylov sequence, m in
  * 1..FS_MSCG_MAX_SHIFTS.  Its arithmetic is fs_mscg's above, whose text is the single statement of it; this says only what differs.
  * x_i at X + i * ldx (ldx >= ncol); X and b in host memory or in HBM of any device of the context, decided per vector as for

@@ -35,6 +35,7 @@ DEVICE_API = [
     "fs_dist_z", "fs_dist_cg", "fs_dist_is_conservative", "fs_dist_csr_create_from_shards", "fs_dist_matrix_build_transpose_device",
     "fs_dist_matrix_bounds_t", "fs_dist_matrix_nnz", "fs_dist_matrix_shard", "fs_dist_spmm", "fs_dist_spmm_t", "fs_dist_cg2",
     "fs_dist_coo_create", "fs_dist_matrix_pair", "fs_dist_ata", "fs_dist_gram_diag", "fs_dist_pcg", "fs_dist_pcgn", "fs_dist_mscg",
+    "fs_dist_pcgn_lambdas",
 ]
 REFERENCE_API = [
     # sparse.h
@@ -195,6 +196,7 @@ def lib():
     L.fs_dist_gram_diag.argtypes = [vp, C.c_double, vp]
     L.fs_dist_pcg.argtypes = [vp, vp, vp, C.c_double, C.POINTER(PcgParams), C.POINTER(PcgInfo)]
     L.fs_dist_pcgn.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.POINTER(PcgParams), C.POINTER(PcgInfo)]
+    L.fs_dist_pcgn_lambdas.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(PcgParams), C.POINTER(PcgInfo)]
     L.fs_dist_mscg.argtypes = [vp, vp, C.c_int64, vp, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(PcgInfo)]
     L.fs_dist_spmm.argtypes = [vp, vp, vp, C.c_int]
     L.fs_dist_spmm_t.argtypes = [vp, vp, vp, C.c_int]
@@ -486,6 +488,23 @@ def dist_pcgn(M, X, B, lam, tol, max_iter=0, precond=FS_PRECOND_JACOBI, warm_sta
     prm = PcgParams(float(tol), int(max_iter), int(precond), int(bool(warm_start)), _ptr(diag))
     infos = (PcgInfo * max(k, 1))()
     check(lib().fs_dist_pcgn(M, _ptr(X), _ptr(B), k, float(lam), C.byref(prm), infos), "fs_dist_pcgn")
+    return list(infos)[:k]
+
+
+def dist_pcgn_lambdas(M, X, B, lams, tol, max_iter=0, precond=FS_PRECOND_JACOBI, warm_start=False, diag=None):
+    """fs_pcgn_lambdas on a row-sharded matrix (fs_dist_pcgn_lambdas): dist_pcgn with a lambda per column, whole panels on every
+    rank or (option dist_cg_scheme = 1) each rank's slice of them.  X, B, diag as in dist_pcgn; lams: k host values.  Returns the
+    list of the k PcgInfo, one per column."""
+    if len(B.shape) not in (1, 2) or tuple(X.shape) != tuple(B.shape):
+        raise ValueError("dist_pcgn_lambdas: X and B must be contiguous (F, k) arrays of the same shape")
+    k = 1 if len(B.shape) == 1 else int(B.shape[1])
+    lams = [float(v) for v in lams]
+    if len(lams) != k:
+        raise ValueError("dist_pcgn_lambdas: one lambda per column of B")
+    prm = PcgParams(float(tol), int(max_iter), int(precond), int(bool(warm_start)), _ptr(diag))
+    infos = (PcgInfo * max(k, 1))()
+    check(lib().fs_dist_pcgn_lambdas(M, _ptr(X), _ptr(B), k, (C.c_double * max(k, 1))(*lams), C.byref(prm), infos),
+          "fs_dist_pcgn_lambdas")
     return list(infos)[:k]
 
 

@@ -618,7 +618,7 @@ constexpr int kPcgnRowsMaxK = 4;           // up to this k the lane-per-row kern
 enum { kStLiveMask = 12 };                 // bit j: column j is live (32 bits, exact in a double)
 enum { kPnBb = 0, kPnRr = 1, kPnStop = 2, kPnRz = 3, kPnAlpha = 4, kPnBeta = 5, kPnCount = 6, kPnLive = 7, kPnConverged = 8,
        kPnStride = 16 };
-enum PcgnStep { kPnStepStart, kPnStepRz, kPnStepAlpha, kPnStepBeta };
+static_assert(kCgStateLiveMask == kStLiveMask, "fs_common.h names the slot for the sharded solvers");
 static_assert(kPcgnStateDoubles == kPcgnMaxRhs * kPnStride && pcgn_part_doubles(1) == (size_t)kRedBlocks * 2, "fs_common.h sizes the callers' buffers");
 struct Pair { double a, b; };
 
@@ -1144,28 +1144,24 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_direction_lds_kernel(int n, 
   }
 }
 
-// the one workgroup that finishes the ns sums of every live column -- each is fs_cg's stage 2 over its kRedBlocks partials, kPcgnGroup
-// sums' loads in flight together -- and then does the scalar step of fs_pcg per column, one thread each (final_step_kernel's
-// kStepPcgStart, kStepPcgRz, kStepCgAlpha, kStepPcgBeta with `done` per column); thread 0 then packs the live mask.  done: no
-// column is live; st[kStIter] counts the iterations after which a column was still live (the longest column's count)
+// stage 2 of the ns sums of every live column, kPcgnGroup sums' loads in flight together: sum v = column * ns + s is fs_cg's stage 2
+// over its kRedBlocks partials part[v * kRedBlocks + b], or (RANKS: the slice sums of `count` ranks, gathered, rank b's nv values at
+// b * nv) over the ranks' values in rank order.  Leaves the waves' sums in sm[v][]; a frozen column's are +0.0
 constexpr int kPcgnGroup = 8;
-template <PcgnStep STEP>
-__global__ __launch_bounds__(kRedThreads) void pcgn_step_kernel(const double *__restrict__ part, double *st, double *cs, int k, int ns,
-                                                               double tol)
+template <bool RANKS>
+__device__ __forceinline__ void pcgn_fold(const double *__restrict__ part, int count, unsigned live, int nv, int ns,
+                                          double (&sm)[2 * kPcgnMaxRhs][kRedThreads / 64])
 {
-  if (STEP != kPnStepStart && st[kStDone] != 0.0) return;
-  __shared__ double sm[2 * kPcgnMaxRhs][kRedThreads / 64];
-  __shared__ double red[2 * kPcgnMaxRhs];
-  const unsigned live = STEP == kPnStepStart ? (k < 32 ? (1u << k) - 1u : ~0u) : pcgn_live(st);
-  const int nv = ns * k;
   for (int v0 = 0; v0 < nv; v0 += kPcgnGroup) {
     double a[kPcgnGroup];
 #pragma unroll
     for (int u = 0; u < kPcgnGroup; ++u) {
       const int v = v0 + u;
       a[u] = 0.0;
-      if (v < nv && ((live >> (v / ns)) & 1u) != 0u)
-        for (int b = threadIdx.x; b < kRedBlocks; b += kRedThreads) a[u] += part[(size_t)v * kRedBlocks + b];
+      if (v < nv && ((live >> (v / ns)) & 1u) != 0u) {
+        if (RANKS) for (int b = threadIdx.x; b < count; b += kRedThreads) a[u] += part[(size_t)b * nv + v];
+        else for (int b = threadIdx.x; b < kRedBlocks; b += kRedThreads) a[u] += part[(size_t)v * kRedBlocks + b];
+      }
     }
 #pragma unroll
     for (int u = 0; u < kPcgnGroup; ++u) {
@@ -1174,6 +1170,41 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_step_kernel(const double *__
       if ((threadIdx.x & 63) == 0 && v0 + u < nv) sm[v0 + u][threadIdx.x >> 6] = s;
     }
   }
+}
+
+// a rank's slice sums into its send slot (fs_dist_pcgn_lambdas on slices): one workgroup, the first half of pcgn_step_kernel.
+// `start`: every column is live (behind pcgn_init_kernel).  A frozen column's slots are sent as +0.0
+__global__ __launch_bounds__(kRedThreads) void pcgn_fold_kernel(const double *__restrict__ part, double *__restrict__ send,
+                                                               const double *__restrict__ st, int k, int ns, int start)
+{
+  if (!start && st[kStDone] != 0.0) return;
+  __shared__ double sm[2 * kPcgnMaxRhs][kRedThreads / 64];
+  const unsigned live = start ? (k < 32 ? (1u << k) - 1u : ~0u) : pcgn_live(st);
+  const int nv = ns * k;
+  pcgn_fold<false>(part, kRedBlocks, live, nv, ns, sm);
+  __syncthreads();
+  if ((int)threadIdx.x < nv) {
+    double s = 0.0;
+    for (int w = 0; w < kRedThreads / 64; ++w) s += sm[threadIdx.x][w];
+    send[threadIdx.x] = s;
+  }
+}
+
+// the one workgroup that finishes the ns sums of every live column (pcgn_fold: over the kRedBlocks partials of whole panels, or
+// RANKS: over the gathered slice sums of `count` ranks) and then does the scalar step of fs_pcg per column, one thread each
+// (final_step_kernel's kStepPcgStart, kStepPcgRz, kStepCgAlpha, kStepPcgBeta with `done` per column); thread 0 then packs the live
+// mask.  done: no column is live; st[kStIter] counts the iterations after which a column was still live (the longest column's
+// count).  With RANKS every rank runs this over the same gathered values: identical scalars, freezes and masks everywhere
+template <PcgnStep STEP, bool RANKS = false>
+__global__ __launch_bounds__(kRedThreads) void pcgn_step_kernel(const double *__restrict__ part, int count, double *st, double *cs, int k,
+                                                               int ns, double tol)
+{
+  if (STEP != kPnStepStart && st[kStDone] != 0.0) return;
+  __shared__ double sm[2 * kPcgnMaxRhs][kRedThreads / 64];
+  __shared__ double red[2 * kPcgnMaxRhs];
+  const unsigned live = STEP == kPnStepStart ? (k < 32 ? (1u << k) - 1u : ~0u) : pcgn_live(st);
+  const int nv = ns * k;
+  pcgn_fold<RANKS>(part, count, live, nv, ns, sm);
   __syncthreads();
   if ((int)threadIdx.x < nv) {
     double s = 0.0;
@@ -1385,8 +1416,10 @@ void pcg_info_of(const double *fin, fs_pcg_info *info)
   info->bnorm = sqrt(fin[kStBb]);
 }
 
-// ---- fs_pcgn's steps as launchers (fs_pcgn; fs_dist_pcgn on every rank).  part: pcgn_part_doubles(k), cs: kPcgnStateDoubles.
-// 16-byte accesses: R, P, Q are the solve's own (rows of an even k stay aligned), X and B may be the caller's
+// ---- fs_pcgn's steps as launchers (fs_pcgn, fs_pcgn_lambdas; fs_dist_pcgn and fs_dist_pcgn_lambdas on every rank, on whole panels
+// or on the rank's slice).  part: pcgn_part_doubles(k), cs: kPcgnStateDoubles.
+// 16-byte accesses: R, P, Q are the solve's own (rows of an even k stay aligned, and a slice starts at its own allocation), X and B
+// may be the caller's
 static int pcgn_vec(int k, const double *X, const double *B)
 {
   return (k & 1) ? 0 : ((((uintptr_t)X | (uintptr_t)B) & 15) == 0 ? 2 : 1);
@@ -1398,47 +1431,140 @@ int pcgn_dev_clear(double *cs, hipStream_t s)     // slots a column never writes
   return FS_OK;
 }
 
-// cold: X = 0, R = B; warm (Q = A'(A X) on entry): Q += lambda X, R = B - Q; b.b, r.r, stop, live? per column; P = Z = R dinv, r.z.
-// LAM: the solve's one lambda (double: fs_pcgn's instantiations) or its k (PcgnLambdas: fs_pcgn_lambdas).  colj: nothing, or the
-// k lambdas again when dinv holds s = diag(A'A) and the kernels invert s + lambda_c per element; without it the kernels behind
-// the first one see no lambda and are fs_pcgn's own
+// One launcher per step, for whole panels and for a rank's slice alike (n rows on the slice's pointers).  LAM: the solve's one
+// lambda (double: fs_pcgn's instantiations) or its k (PcgnLambdas: fs_pcgn_lambdas).  colj: nothing, or the k lambdas again when
+// dinv holds s = diag(A'A) and the kernels invert s + lambda_c per element; without it the kernels behind the first one see no
+// lambda and are fs_pcgn's own.  vec: pcgn_vec of the solve's X and B.  Behind a step that takes sums, pcgn_sums_launch.
+
+// the scalar step behind ns sums per column: over the kRedBlocks partials of whole panels, or (RANKS) over `count` ranks' values
+template <bool RANKS>
+static void pcgn_step_launch(PcgnStep step, const double *part, int count, double *st, double *cs, int k, int ns, double tol, hipStream_t s)
+{
+  const dim3 one(1), blk(kRedThreads);
+  switch (step) {
+    case kPnStepStart: hipLaunchKernelGGL((pcgn_step_kernel<kPnStepStart, RANKS>), one, blk, 0, s, part, count, st, cs, k, ns, tol); break;
+    case kPnStepRz:    hipLaunchKernelGGL((pcgn_step_kernel<kPnStepRz, RANKS>), one, blk, 0, s, part, count, st, cs, k, ns, tol); break;
+    case kPnStepAlpha: hipLaunchKernelGGL((pcgn_step_kernel<kPnStepAlpha, RANKS>), one, blk, 0, s, part, count, st, cs, k, ns, tol); break;
+    default:           hipLaunchKernelGGL((pcgn_step_kernel<kPnStepBeta, RANKS>), one, blk, 0, s, part, count, st, cs, k, ns, tol); break;
+  }
+}
+
+// behind a vector kernel that left ns sums per live column and workgroup in U.part: whole panels are finished and the scalar
+// step taken; a slice's sums are folded into the rank's send slot
+static void pcgn_sums_launch(PcgnStep step, const PcgnSums &U, int k, int ns, double tol, hipStream_t s)
+{
+  if (U.send) hipLaunchKernelGGL(pcgn_fold_kernel, dim3(1), dim3(kRedThreads), 0, s, U.part, U.send, U.st, k, ns, (int)(step == kPnStepStart));
+  else pcgn_step_launch<false>(step, U.part, kRedBlocks, U.st, U.cs, k, ns, tol, s);
+}
+
+// cold: X = 0, R = B; warm (Q = A'(A X) on entry): Q += lambda X, R = B - Q; b.b, r.r, stop, live? per column
+template <typename LAM>
+static int pcgn_init_step(int n, int k, int vec, bool warm, const LAM &lambda, const double *B, double *X, double *R, double *Q,
+                          const PcgnSums &U, double tol, hipStream_t s)
+{
+  const int rc = pcgn_dispatch(k, vec, [&](auto sh) -> int {
+    using S = decltype(sh);
+    hipLaunchKernelGGL((pcgn_init_kernel<S::kmax, S::vec, LAM>), dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, k, (int)warm, lambda, B, X, R, Q, U.part);
+    return FS_OK;
+  });
+  pcgn_sums_launch(kPnStepStart, U, k, 2, tol, s);                                                           // b.b, r.r, stop, live?
+  return rc;
+}
+
+// P = Z = R dinv, r.z
+template <typename... CJ>
+static int pcgn_start_step(int n, int k, int vec, const double *R, const double *dinv, double *P, const PcgnSums &U, hipStream_t s, CJ... colj)
+{
+  const int rc = pcgn_dispatch(k, vec, [&](auto sh) -> int {
+    using S = decltype(sh);
+    hipLaunchKernelGGL((pcgn_start_kernel<S::kmax, S::vec, CJ...>), dim3(kRedBlocks), dim3(kRedThreads), 0, s, n, k, R, dinv, P, U.part, U.st, colj...);
+    return FS_OK;
+  });
+  pcgn_sums_launch(kPnStepRz, U, k, 1, 0.0, s);                                                              // r.z
+  return rc;
+}
+
+// option "pcgn_kernel" picks the form of the per-iteration vector kernels
+static bool pcgn_staged(int k)
+{
+  const int which = options().pcgn_kernel;
+  const bool staged = which == 2 || (which == 0 && k > kPcgnRowsMaxK);
+  return staged;
+}
+
+// behind Q = A'(A P): Q += lambda P, q.p; alpha = r.z / p.q
+template <typename LAM>
+static int pcgn_shift_dot_step(int n, int k, int vec, const LAM &lambda, double *Q, const double *P, const PcgnSums &U, hipStream_t s)
+{
+  const dim3 g(kRedBlocks), blk(kRedThreads);
+  const bool staged = pcgn_staged(k);
+  const int rc = pcgn_dispatch(k, vec, [&](auto sh) -> int {
+    using S = decltype(sh);
+    if (staged) hipLaunchKernelGGL((pcgn_shift_dot_lds_kernel<S::kmax, LAM>), g, blk, 0, s, n, k, lambda, Q, P, U.part, U.st);
+    else        hipLaunchKernelGGL((pcgn_shift_dot_kernel<S::kmax, S::vec, LAM>), g, blk, 0, s, n, k, lambda, Q, P, U.part, U.st);
+    return FS_OK;
+  });
+  pcgn_sums_launch(kPnStepAlpha, U, k, 1, 0.0, s);                                                           // alpha = r.z / p.q
+  return rc;
+}
+
+// X and R; r.r, or {r.r, r.z} with a preconditioner: converged? beta
+template <typename... CJ>
+static int pcgn_update_step(int n, int k, int vec, double *X, double *R, const double *P, const double *Q, const double *dinv,
+                            const PcgnSums &U, hipStream_t s, CJ... colj)
+{
+  const dim3 g(kRedBlocks), blk(kRedThreads);
+  const bool staged = pcgn_staged(k);
+  const int rc = pcgn_dispatch(k, vec, [&](auto sh) -> int {
+    using S = decltype(sh);
+    if (staged) hipLaunchKernelGGL((pcgn_update_lds_kernel<S::kmax, CJ...>), g, blk, 0, s, n, k, X, R, P, Q, dinv, U.part, U.st, U.cs, colj...);
+    else        hipLaunchKernelGGL((pcgn_update_kernel<S::kmax, S::vec, CJ...>), g, blk, 0, s, n, k, X, R, P, Q, dinv, U.part, U.st, U.cs, colj...);
+    return FS_OK;
+  });
+  pcgn_sums_launch(kPnStepBeta, U, k, dinv ? 2 : 1, 0.0, s);                                                 // converged? beta
+  return rc;
+}
+
+// the new P = Z + beta P
+template <typename... CJ>
+static int pcgn_direction_step(int n, int k, int vec, double *P, const double *R, const double *dinv, const PcgnSums &U, hipStream_t s,
+                               CJ... colj)
+{
+  const dim3 g(kRedBlocks), blk(kRedThreads);
+  const bool staged = pcgn_staged(k);
+  const int rc = pcgn_dispatch(k, vec, [&](auto sh) -> int {
+    using S = decltype(sh);
+    if (staged) hipLaunchKernelGGL((pcgn_direction_lds_kernel<S::kmax, CJ...>), g, blk, 0, s, n, k, P, R, dinv, U.st, U.cs, colj...);
+    else        hipLaunchKernelGGL((pcgn_direction_kernel<S::kmax, S::vec, CJ...>), g, blk, 0, s, n, k, P, R, dinv, U.st, U.cs, colj...);
+    return FS_OK;
+  });
+  FS_HIP(hipGetLastError());
+  return rc;
+}
+
+// the start of a solve on whole panels: the two steps in sequence, each with its scalar step behind it
 template <typename LAM, typename... CJ>
 static int pcgn_init_launch(int n, int k, bool warm, const LAM &lambda, const double *B, double *X, double *R, double *P, double *Q,
                             const double *dinv, double *part, double *st, double *cs, double tol, hipStream_t s, CJ... colj)
 {
-  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
-  return pcgn_dispatch(k, pcgn_vec(k, X, B), [&](auto sh) -> int {
-    using S = decltype(sh);
-    hipLaunchKernelGGL((pcgn_init_kernel<S::kmax, S::vec, LAM>), g, blk, 0, s, n, k, (int)warm, lambda, B, X, R, Q, part);
-    hipLaunchKernelGGL(pcgn_step_kernel<kPnStepStart>, one, blk, 0, s, part, st, cs, k, 2, tol);           // b.b, r.r, stop, live?
-    hipLaunchKernelGGL((pcgn_start_kernel<S::kmax, S::vec, CJ...>), g, blk, 0, s, n, k, R, dinv, P, part, st, colj...);
-    hipLaunchKernelGGL(pcgn_step_kernel<kPnStepRz>, one, blk, 0, s, part, st, cs, k, 1, 0.0);              // r.z
-    FS_HIP(hipGetLastError());
-    return FS_OK;
-  });
+  const PcgnSums U{part, st, cs, nullptr};
+  const int vec = pcgn_vec(k, X, B);
+  if (int rc = pcgn_init_step(n, k, vec, warm, lambda, B, X, R, Q, U, tol, s)) return rc;
+  if (int rc = pcgn_start_step(n, k, vec, R, dinv, P, U, s, colj...)) return rc;
+  FS_HIP(hipGetLastError());
+  return FS_OK;
 }
 
-// everything of an iteration behind Q = A'(A P); option "pcgn_kernel" picks the form of the vector kernels.  LAM, colj: as above
+// everything of an iteration behind Q = A'(A P) on whole panels.  LAM, colj: as above
 template <typename LAM, typename... CJ>
 static int pcgn_steps_launch(int n, int k, const LAM &lambda, double *X, const double *B, double *R, double *P, double *Q,
                              const double *dinv, double *part, double *st, double *cs, hipStream_t s, CJ... colj)
 {
-  const dim3 g(kRedBlocks), blk(kRedThreads), one(1);
-  const int which = options().pcgn_kernel;
-  const bool staged = which == 2 || (which == 0 && k > kPcgnRowsMaxK);
-  return pcgn_dispatch(k, pcgn_vec(k, X, B), [&](auto sh) -> int {
-    using S = decltype(sh);
-    if (staged) hipLaunchKernelGGL((pcgn_shift_dot_lds_kernel<S::kmax, LAM>), g, blk, 0, s, n, k, lambda, Q, P, part, st);
-    else        hipLaunchKernelGGL((pcgn_shift_dot_kernel<S::kmax, S::vec, LAM>), g, blk, 0, s, n, k, lambda, Q, P, part, st);
-    hipLaunchKernelGGL(pcgn_step_kernel<kPnStepAlpha>, one, blk, 0, s, part, st, cs, k, 1, 0.0);          // alpha = r.z / p.q
-    if (staged) hipLaunchKernelGGL((pcgn_update_lds_kernel<S::kmax, CJ...>), g, blk, 0, s, n, k, X, R, P, Q, dinv, part, st, cs, colj...);
-    else        hipLaunchKernelGGL((pcgn_update_kernel<S::kmax, S::vec, CJ...>), g, blk, 0, s, n, k, X, R, P, Q, dinv, part, st, cs, colj...);
-    hipLaunchKernelGGL(pcgn_step_kernel<kPnStepBeta>, one, blk, 0, s, part, st, cs, k, dinv ? 2 : 1, 0.0); // converged? beta
-    if (staged) hipLaunchKernelGGL((pcgn_direction_lds_kernel<S::kmax, CJ...>), g, blk, 0, s, n, k, P, R, dinv, st, cs, colj...);
-    else        hipLaunchKernelGGL((pcgn_direction_kernel<S::kmax, S::vec, CJ...>), g, blk, 0, s, n, k, P, R, dinv, st, cs, colj...);
-    FS_HIP(hipGetLastError());
-    return FS_OK;
-  });
+  const PcgnSums U{part, st, cs, nullptr};
+  const int vec = pcgn_vec(k, X, B);
+  if (int rc = pcgn_shift_dot_step(n, k, vec, lambda, Q, P, U, s)) return rc;
+  if (int rc = pcgn_update_step(n, k, vec, X, R, P, Q, dinv, U, s, colj...)) return rc;
+  return pcgn_direction_step(n, k, vec, P, R, dinv, U, s, colj...);
 }
 
 int pcgn_dev_init(int n, int k, bool warm, double lambda, const double *B, double *X, double *R, double *P, double *Q, const double *dinv,
@@ -1451,6 +1577,73 @@ int pcgn_dev_steps(int n, int k, double lambda, double *X, const double *B, doub
                    double *part, double *st, double *cs, hipStream_t s)
 {
   return pcgn_steps_launch(n, k, lambda, X, B, R, P, Q, dinv, part, st, cs, s);
+}
+
+// fs_pcgn_lambdas' instantiations on whole panels (fs_pcgn_lambdas; fs_dist_pcgn_lambdas replicated, on every rank).  colj: dinv
+// holds s = diag(A'A) at 0.0 and every column inverts s + lambda_c (FS_PRECOND_JACOBI)
+int pcgn_dev_init_lambdas(int n, int k, bool warm, const PcgnLambdas &lv, bool colj, const double *B, double *X, double *R, double *P,
+                          double *Q, const double *dinv, double *part, double *st, double *cs, double tol, hipStream_t s)
+{
+  return colj ? pcgn_init_launch(n, k, warm, lv, B, X, R, P, Q, dinv, part, st, cs, tol, s, lv)
+              : pcgn_init_launch(n, k, warm, lv, B, X, R, P, Q, dinv, part, st, cs, tol, s);
+}
+
+int pcgn_dev_steps_lambdas(int n, int k, const PcgnLambdas &lv, bool colj, double *X, const double *B, double *R, double *P, double *Q,
+                           const double *dinv, double *part, double *st, double *cs, hipStream_t s)
+{
+  return colj ? pcgn_steps_launch(n, k, lv, X, B, R, P, Q, dinv, part, st, cs, s, lv)
+              : pcgn_steps_launch(n, k, lv, X, B, R, P, Q, dinv, part, st, cs, s);
+}
+
+// the same steps one by one on a rank's slice of n rows (fs_dist_pcgn_lambdas on slices): U.send is the rank's send slot, the
+// exchange and pcgn_dev_rank_step follow each step that takes sums.  X, B, R, Q: the slice; P: the slice of the direction
+int pcgn_slice_init(int n, int k, bool warm, const PcgnLambdas &lv, const double *B, double *X, double *R, double *Q, const PcgnSums &U,
+                    hipStream_t s)
+{
+  if (int rc = pcgn_init_step(n, k, pcgn_vec(k, X, B), warm, lv, B, X, R, Q, U, 0.0, s)) return rc;
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+int pcgn_slice_start(int n, int k, const PcgnLambdas &lv, bool colj, const double *X, const double *B, const double *R, const double *dinv,
+                     double *P, const PcgnSums &U, hipStream_t s)
+{
+  if (int rc = colj ? pcgn_start_step(n, k, pcgn_vec(k, X, B), R, dinv, P, U, s, lv) : pcgn_start_step(n, k, pcgn_vec(k, X, B), R, dinv, P, U, s))
+    return rc;
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+int pcgn_slice_shift_dot(int n, int k, const PcgnLambdas &lv, const double *X, const double *B, double *Q, const double *P,
+                         const PcgnSums &U, hipStream_t s)
+{
+  if (int rc = pcgn_shift_dot_step(n, k, pcgn_vec(k, X, B), lv, Q, P, U, s)) return rc;
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+int pcgn_slice_update(int n, int k, const PcgnLambdas &lv, bool colj, double *X, const double *B, double *R, const double *P,
+                      const double *Q, const double *dinv, const PcgnSums &U, hipStream_t s)
+{
+  if (int rc = colj ? pcgn_update_step(n, k, pcgn_vec(k, X, B), X, R, P, Q, dinv, U, s, lv)
+                    : pcgn_update_step(n, k, pcgn_vec(k, X, B), X, R, P, Q, dinv, U, s)) return rc;
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+int pcgn_slice_direction(int n, int k, const PcgnLambdas &lv, bool colj, const double *X, const double *B, double *P, const double *R,
+                         const double *dinv, const PcgnSums &U, hipStream_t s)
+{
+  return colj ? pcgn_direction_step(n, k, pcgn_vec(k, X, B), P, R, dinv, U, s, lv) : pcgn_direction_step(n, k, pcgn_vec(k, X, B), P, R, dinv, U, s);
+}
+
+// the slice sums of every rank, gathered (`all`: rank r's ns * k values at r * ns * k): stage 2 over the ranks in rank order per
+// sum, then the scalar step.  ns: 2 for kPnStepStart {b.b, r.r} and for kPnStepBeta with a preconditioner {r.r, r.z}, else 1
+int pcgn_dev_rank_step(PcgnStep step, const double *all, int nranks, int k, int ns, double tol, double *st, double *cs, hipStream_t s)
+{
+  pcgn_step_launch<true>(step, all, nranks, st, cs, k, ns, tol, s);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
 }
 
 // ---- fs_mscg's steps as launchers (fs_mscg; fs_dist_mscg on every rank: whole vectors, or the rank's slice of r, p, q, the x_i
@@ -1647,6 +1840,15 @@ void mscg_note_state(const double *fin, const double *fms, int m, fs_pcg_info *i
     info[i].rnorm = e[kMsRn];
     info[i].bnorm = sqrt(fin[kStBb]);
   }
+}
+
+// two ranks' final cs[]: every column ended live or not, converged or not, with the same count
+bool pcgn_same_outcome(const double *a, const double *b, int k)
+{
+  for (int j = 0; j < k; ++j)
+    for (int at : {(int)kPnLive, (int)kPnConverged, (int)kPnCount})
+      if (a[j * kPnStride + at] != b[j * kPnStride + at]) return false;
+  return true;
 }
 
 // two ranks' final ms[]: every shift ended live or not, converged or not, with the same count

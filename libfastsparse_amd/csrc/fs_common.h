@@ -404,6 +404,7 @@ int cg2_dev_steps(int n, double lambda, double *X, double *R, double *P, double 
 int cg2_dev_finish(int n, const double *norms, double *X, hipStream_t s);
 // ---- fs_pcgn's steps on row-major n x k panels; part: pcgn_part_doubles(k) doubles, cs: kPcgnStateDoubles, st as above
 constexpr int kPcgnStateDoubles = FS_PCGN_MAX_RHS * 16;
+constexpr int kCgStateLiveMask = 12;                    // st[]: the mask of live columns (bit j: column j), exact in a double
 constexpr size_t pcgn_part_doubles(int k) { return (size_t)1024 * 2 * (size_t)k; }
 struct PcgnLambdas { double v[FS_PCGN_MAX_RHS]; };   // fs_pcgn_lambdas' k lambdas, a kernel argument by value (like MscgSigma)
 int pcgn_dev_clear(double *cs, hipStream_t s);
@@ -411,6 +412,30 @@ int pcgn_dev_init(int n, int k, bool warm, double lambda, const double *B, doubl
                   double *part, double *st, double *cs, double tol, hipStream_t s);
 int pcgn_dev_steps(int n, int k, double lambda, double *X, const double *B, double *R, double *P, double *Q, const double *dinv,
                    double *part, double *st, double *cs, hipStream_t s);
+// fs_pcgn_lambdas' instantiations of the same two (lv: the k lambdas; colj: dinv holds s = diag(A'A) at 0.0, inverted per column)
+int pcgn_dev_init_lambdas(int n, int k, bool warm, const PcgnLambdas &lv, bool colj, const double *B, double *X, double *R, double *P,
+                          double *Q, const double *dinv, double *part, double *st, double *cs, double tol, hipStream_t s);
+int pcgn_dev_steps_lambdas(int n, int k, const PcgnLambdas &lv, bool colj, double *X, const double *B, double *R, double *P, double *Q,
+                           const double *dinv, double *part, double *st, double *cs, hipStream_t s);
+// the steps one by one on a rank's SLICE of n rows (fs_dist_pcgn_lambdas, scheme "gather"): the same launchers, one launch site
+// per kernel.  A step that takes sums leaves the rank's ns sums per column in send[0 .. ns * k) (a frozen column's as +0.0); the
+// sums of all ranks, gathered rank-major, go through pcgn_dev_rank_step, which adds each in rank order (stage 2's tree) and takes
+// the scalar step of every column -- on every rank over the same values.  X, B: the slices (they decide the 16-byte forms)
+enum PcgnStep { kPnStepStart, kPnStepRz, kPnStepAlpha, kPnStepBeta };
+constexpr int kPcgnSendDoubles = 2 * FS_PCGN_MAX_RHS;   // sums one exchange carries per rank: {b.b, r.r} or {r.r, r.z} of every column
+struct PcgnSums { double *part, *st, *cs, *send = nullptr; };   // send NULL: whole panels, the scalar step follows the sums at once
+int pcgn_slice_init(int n, int k, bool warm, const PcgnLambdas &lv, const double *B, double *X, double *R, double *Q, const PcgnSums &U,
+                    hipStream_t s);                                              // X, R; {b.b, r.r}: kPnStepStart, ns = 2
+int pcgn_slice_start(int n, int k, const PcgnLambdas &lv, bool colj, const double *X, const double *B, const double *R, const double *dinv,
+                     double *P, const PcgnSums &U, hipStream_t s);               // P = Z; r.z: kPnStepRz
+int pcgn_slice_shift_dot(int n, int k, const PcgnLambdas &lv, const double *X, const double *B, double *Q, const double *P,
+                         const PcgnSums &U, hipStream_t s);                      // Q += lambda_c P; q.p: kPnStepAlpha
+int pcgn_slice_update(int n, int k, const PcgnLambdas &lv, bool colj, double *X, const double *B, double *R, const double *P,
+                      const double *Q, const double *dinv, const PcgnSums &U, hipStream_t s);   // r.r[, r.z]: kPnStepBeta, ns = dinv ? 2 : 1
+int pcgn_slice_direction(int n, int k, const PcgnLambdas &lv, bool colj, const double *X, const double *B, double *P, const double *R,
+                         const double *dinv, const PcgnSums &U, hipStream_t s);
+int pcgn_dev_rank_step(PcgnStep step, const double *all, int nranks, int k, int ns, double tol, double *st, double *cs, hipStream_t s);
+bool pcgn_same_outcome(const double *cs_a, const double *cs_b, int k);           // {live, converged, count} of every column agree
 // the final st[] and cs[] (k columns) on the host: kept for the debug getters, info (k entries or NULL) filled
 void pcgn_note_state(const double *st_host, const double *cs_host, int k, fs_pcg_info *info);
 // ---- fs_mscg's steps (fs_mscg; fs_dist_mscg on every rank, on whole vectors or on the rank's slice).  ms: kMscgStateDoubles, st

@@ -294,10 +294,14 @@ constexpr int kCgSendDoubles = 2;     // sums one exchange carries per rank: {b.
 
 // fs_dist_pcgn's own vectors for k columns (whole panels on every rank), kept like CgWork; P, T, Q are the product vectors of the
 // handle (x / y / z, or KWork's for k > 1)
+// fs_dist_pcgn_lambdas on slices keeps rank r's rows of A' of X, R, B, Q (q) and of s / dinv instead: n_r k doubles each; send: two
+// send slots of kPcgnSendDoubles and all: every rank's slot, gathered.  The slice of P is the transposed side's local buffer
 struct PnWork {
   int F = 0, k = 0;
+  bool slices = false;
   RankBuffers mem;
   std::vector<double *> sol, r, b, dinv, part, cs, st;
+  std::vector<double *> q, send, all;
 };
 
 // fs_dist_mscg's own vectors, kept like CgWork: the x_i (X, room for m of them) and the directions P_i of the shifts with sigma != 0
@@ -1456,7 +1460,7 @@ int fs_dist_swap_xy(fs_dist_matrix_t M)
   return FS_OK;
 }
 
-// ---- the CG solvers on the row-sharded matrix: fs_dist_cg, fs_dist_pcg, fs_dist_pcgn, fs_dist_mscg, fs_dist_cg2 ---------------------------
+// ---- the CG solvers on the row-sharded matrix: fs_dist_cg, fs_dist_pcg, fs_dist_pcgn, fs_dist_pcgn_lambdas, fs_dist_mscg, fs_dist_cg2 -----
 // Everything of a solve is resident and the scalars of the iteration live on the devices (fs_cg.hip's launchers); per iteration
 // y = A p and q = A' y.  EVERY rank decides convergence for itself and the host compares the flags of all of them one iteration
 // behind: a disagreement (which identical arithmetic rules out, and a faulty device or exchange does not) is an error return,
@@ -1464,7 +1468,7 @@ int fs_dist_swap_xy(fs_dist_matrix_t M)
 // 0.  Work vectors are kept on the handle between solves.  A solve CLOBBERS fs_dist_x / fs_dist_y / fs_dist_z of the handle and
 // writes the caller's x once, at the end: whatever fails before leaves it as it was.
 //
-// DistSolve is the host frame the five share, the counterpart of CgSolve in fs_cg.hip: open() (the transpose is there, both
+// DistSolve is the host frame the six share, the counterpart of CgSolve in fs_cg.hip: open() (the transpose is there, both
 // locks, the caller's device kept, fixed-order products, one set of host-visible flags per rank), stage() (the caller's vectors
 // onto the ranks), iterate() and finish() (settle(): the agreed final state; then store(): x to the caller).  A solver brings its argument checks,
 // its work space (st: every rank's st[]), its start and what an iteration enqueues.
@@ -1855,6 +1859,34 @@ int fs_dist_pcg(fs_dist_matrix_t M, double *x, const double *b, double lambda, c
   return FS_OK;
 }
 
+// the k-column solvers' vectors on the handle: whole F x k panels on every rank, or (slices) the rank's rows of A' of them with the
+// send slots and the gathered sums.  Kept between solves; re-made when k or the scheme changes
+static int ensure_pn_work(fs_dist_matrix_t M, int k, bool slices)
+{
+  fs_dist_t D = M->D;
+  const int n = D->n, F = M->ncol;
+  PnWork &W = M->pn;
+  if (W.mem.ready && W.F == F && W.k == k && W.slices == slices) return FS_OK;
+  if (int rc = dist_sync(D)) return rc;
+  free_pn(D, W);
+  W.F = F; W.k = k; W.slices = slices;
+  return W.mem.fill(D, [&](int d) -> int {
+    const size_t rows = slices ? (size_t)(M->t.bounds[(size_t)d + 1] - M->t.bounds[(size_t)d]) : (size_t)F;
+    const size_t fk = (rows ? rows : 1) * (size_t)k;
+    for (std::vector<double *> *v : {&W.sol, &W.r, &W.b})
+      if (int rc2 = W.mem.get(d, *v, fk)) return rc2;
+    if (int rc2 = W.mem.get(d, W.dinv, rows ? rows : 1)) return rc2;
+    if (int rc2 = W.mem.get(d, W.part, fs::pcgn_part_doubles(k))) return rc2;
+    if (int rc2 = W.mem.get(d, W.cs, (size_t)fs::kPcgnStateDoubles)) return rc2;
+    if (slices) {
+      if (int rc2 = W.mem.get(d, W.q, fk)) return rc2;
+      if (int rc2 = W.mem.get(d, W.send, (size_t)(2 * fs::kPcgnSendDoubles))) return rc2;
+      if (int rc2 = W.mem.get(d, W.all, (size_t)n * fs::kPcgnSendDoubles)) return rc2;
+    }
+    return W.mem.get(d, W.st, (size_t)fs::kCgStateDoubles);
+  });
+}
+
 // fs_pcgn across the ranks, replicated whatever "dist_cg_scheme" says: every rank holds the whole F x k panels and launches
 // fs_pcgn's own kernels on them (pcgn_dev_*); T = A P and Q = A' T are the sharded k-column products (k = 1: the single-vector
 // ones).
@@ -1874,20 +1906,7 @@ int fs_dist_pcgn(fs_dist_matrix_t M, double *X, const double *B, int k, double l
   if (k > 1)
     if (int rc = ensure_k(M, k)) return rc;
   PnWork &W = M->pn;
-  if (!W.mem.ready || W.F != F || W.k != k) {
-    if (int rc = dist_sync(D)) return rc;
-    free_pn(D, W);
-    W.F = F; W.k = k;
-    const size_t fk = (size_t)(F ? F : 1) * (size_t)k;
-    if (int rc = W.mem.fill(D, [&](int d) -> int {
-          for (std::vector<double *> *v : {&W.sol, &W.r, &W.b})
-            if (int rc2 = W.mem.get(d, *v, fk)) return rc2;
-          if (int rc2 = W.mem.get(d, W.dinv, (size_t)(F ? F : 1))) return rc2;
-          if (int rc2 = W.mem.get(d, W.part, fs::pcgn_part_doubles(k))) return rc2;
-          if (int rc2 = W.mem.get(d, W.cs, (size_t)fs::kPcgnStateDoubles)) return rc2;
-          return W.mem.get(d, W.st, (size_t)fs::kCgStateDoubles);
-        })) return rc;
-  }
+  if (int rc = ensure_pn_work(M, k, false)) return rc;
   f.st = &W.st;
   // the product vectors: P (replicated input of A), T = A P, Q = A' T
   const std::vector<double *> &vp = k > 1 ? M->kw.x : M->x, &vt = k > 1 ? M->kw.y : M->y, &vq = k > 1 ? M->kw.z : M->z;
@@ -1921,6 +1940,205 @@ int fs_dist_pcgn(fs_dist_matrix_t M, double *X, const double *B, int k, double l
   double cs0[fs::kPcgnStateDoubles] = {0.0};
   FS_HIP(hipSetDevice(D->dev[0]));
   FS_HIP(hipMemcpy(cs0, W.cs[0], sizeof(double) * (size_t)k * (fs::kPcgnStateDoubles / FS_PCGN_MAX_RHS), hipMemcpyDeviceToHost));
+  fs::pcgn_note_state(f.st0, cs0, k, info);
+  return FS_OK;
+}
+
+// Scheme "gather" for k columns: the sums over the ranks.  A slice step leaves a rank's ns sums per column in send(d); combine()
+// all-gathers them, ns * k doubles per rank, and every rank adds each sum over the ranks in rank order (stage 2's tree) and takes
+// the scalar step of every column.  The two send slots alternate as SliceSums' do
+struct PnSliceSums {
+  fs_dist_matrix_t M;
+  int k;
+  int slot = 0;
+  double *send(int d) const { return M->pn.send[(size_t)d] + fs::kPcgnSendDoubles * slot; }
+  fs::PcgnSums of(int d) const
+  {
+    const PnWork &W = M->pn;
+    return fs::PcgnSums{W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], send(d)};
+  }
+  int combine(fs::PcgnStep step, int ns, double tol)
+  {
+    fs_dist_t D = M->D;
+    const int n = D->n;
+    PnWork &W = M->pn;
+    DistSide &T = M->t;
+    std::vector<const double *> from((size_t)n);
+    std::vector<hipEvent_t> ready((size_t)n);
+    if (int rc = each_rank(D, false, [&](int d) -> int {
+          from[(size_t)d] = send(d);
+          FS_HIP(hipEventRecord(T.ev[(size_t)d][0], D->stream[d]));
+          ready[(size_t)d] = T.ev[(size_t)d][0];
+          return FS_OK;
+        })) return rc;
+    if (int rc = exchange_equal(D, from, W.all, (size_t)ns * (size_t)k, D->stream, ready)) return rc;
+    if (int rc = each_rank(D, false, [&](int d) {
+          return fs::pcgn_dev_rank_step(step, W.all[(size_t)d], n, k, ns, tol, W.st[(size_t)d], W.cs[(size_t)d], D->stream[d]);
+        })) return rc;
+    slot ^= 1;
+    return FS_OK;
+  }
+};
+
+// fs_pcgn_lambdas across the ranks; the schemes are fs_dist_pcg's (option "dist_cg_scheme"):
+//   0 "replicate"  fs_dist_pcgn's frame with fs_pcgn_lambdas' instantiations of the kernels on whole panels.  Jacobi: the work
+//                  vector holds s = fs_gram_diag of A' at 0.0, gathered once; no inverse pass.
+//   1 "gather"     rank r keeps its rows of A' of X, R, B, Q and s / dinv; P and T = A P stay whole (the product's input and
+//                  output).  Q_r = A'_r T is the rank's own shard product: no exchange.  Every sum is the slice tree of fs_dist_cg
+//                  per column (PnSliceSums); the new P slices are all-gathered for the next product -- the first P too: it is
+//                  Z = R dinv, which only the owner of a row can form.
+int fs_dist_pcgn_lambdas(fs_dist_matrix_t M, double *X, const double *B, int k, const double *lambda, const fs_pcg_params *prm,
+                         fs_pcg_info *info)
+{
+  if (!M || !X || !B || !prm || !lambda) { fs::set_error("fs_dist_pcgn_lambdas: NULL argument"); return FS_ERR_ARG; }
+  if (k < 1 || k > FS_PCGN_MAX_RHS) { fs::set_error("fs_dist_pcgn_lambdas: k outside 1..FS_PCGN_MAX_RHS"); return FS_ERR_ARG; }
+  if (int rc = fs::pcg_params_ok("fs_dist_pcgn_lambdas", prm)) return rc;
+  fs::PcgnLambdas lv = {};
+  for (int j = 0; j < k; ++j) {
+    if (!std::isfinite(lambda[j])) { fs::set_error("fs_dist_pcgn_lambdas: a lambda is NaN or infinite"); return FS_ERR_ARG; }
+    lv.v[j] = lambda[j];
+  }
+  DistSolve f{"fs_dist_pcgn_lambdas", M};
+  if (int rc = f.open("call fs_dist_matrix_build_transpose first")) return rc;
+  if (prm->precond == FS_PRECOND_JACOBI)
+    if (int rc = gram_diag_ready(M, "fs_dist_pcgn_lambdas with FS_PRECOND_JACOBI (fs_gram_diag)")) return rc;
+  fs_dist_t D = f.D;
+  const int F = f.F, n = f.n;
+  const bool gather = fs::options().dist_cg_scheme == 1 && n > 1;
+  const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
+  const bool colj = prm->precond == FS_PRECOND_JACOBI;       // the diagonal follows the column: dinv holds s
+  const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
+  if (k > 1)
+    if (int rc = ensure_k(M, k)) return rc;
+  PnWork &W = M->pn;
+  if (int rc = ensure_pn_work(M, k, gather)) return rc;
+  f.st = &W.st;
+  DistSide &T = M->t;
+  // the product vectors: P (replicated input of A), T = A P, Q = A' T (whole panels: scheme 0 only)
+  const std::vector<double *> &vp = k > 1 ? M->kw.x : M->x, &vt = k > 1 ? M->kw.y : M->y, &vq = k > 1 ? M->kw.z : M->z;
+  auto dinv_of = [&](int d) -> const double * { return pre ? W.dinv[(size_t)d] : nullptr; };
+  auto lo_of = [&](int d) { return gather ? T.bounds[(size_t)d] : 0; };
+  auto rows_of = [&](int d) { return gather ? T.bounds[(size_t)d + 1] - T.bounds[(size_t)d] : F; };
+  // a rank's slice of a whole panel that was staged in `whole`
+  auto take_slice = [&](const std::vector<double *> &dst, const std::vector<double *> &whole) {
+    return each_rank(D, false, [&](int d) -> int {
+      if (rows_of(d) > 0)
+        FS_HIP(hipMemcpyAsync(dst[(size_t)d], whole[(size_t)d] + (size_t)lo_of(d) * k, sizeof(double) * (size_t)rows_of(d) * k,
+                              hipMemcpyDeviceToDevice, D->stream[d]));
+      return FS_OK;
+    });
+  };
+  if (int rc = each_rank(D, false, [&](int d) { return fs::pcgn_dev_clear(W.cs[(size_t)d], D->stream[d]); })) return rc;
+  if (!gather) {
+    if (int rc = f.stage(W.b, B, (size_t)F * k)) return rc;
+    if (warm)
+      if (int rc = f.stage(W.sol, X, (size_t)F * k)) return rc;
+    if (prm->precond == FS_PRECOND_DIAG) {
+      if (int rc = f.stage(vq, prm->diag, (size_t)F)) return rc;                   // (d is staged where Q lives later)
+      if (int rc = each_rank(D, false, [&](int d) { return fs::pcg_dev_dinv(F, vq[(size_t)d], W.dinv[(size_t)d], D->stream[d]); })) return rc;
+    }
+    if (colj)
+      if (int rc = gram_diag_everywhere(M, 0.0, W.dinv)) return rc;
+    if (warm) {                                              // Q = A'(A X0): one pair of k-column products
+      if (int rc = dist_product(M, false, k, W.sol, vt)) return rc;
+      if (int rc = dist_product(M, true, k, vt, vq)) return rc;
+    }
+    if (int rc = each_rank(D, false, [&](int d) {
+          return fs::pcgn_dev_init_lambdas(F, k, warm, lv, colj, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d],
+                                           dinv_of(d), W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], prm->tol, D->stream[d]);
+        })) return rc;
+    if (int rc = f.iterate(cap, true, [&]() -> int {
+          if (int rc2 = dist_product(M, false, k, vp, vt)) return rc2;     // T = A P
+          return dist_product(M, true, k, vt, vq);                         // Q = A' T
+        }, [&](int d) {
+          return fs::pcgn_dev_steps_lambdas(F, k, lv, colj, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d],
+                                            dinv_of(d), W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], D->stream[d]);
+        })) return rc;
+    if (int rc = f.settle()) return rc;
+  } else {
+    // the slice of P: the local output buffer of the A' side, which no product of this scheme writes -- the gather's own source
+    const Exchange gp = exchange_of(M, true, k);
+    const std::vector<double *> &ps = gp.local;
+    // Q_r = A'_r T: the rank's own shard product
+    auto shard_product = [&](int d) -> int {
+      if (rows_of(d) <= 0) return FS_OK;
+      return k == 1 ? fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], vt[(size_t)d], D->stream[d])
+                    : fs_spmm(T.shard[(size_t)d], W.q[(size_t)d], vt[(size_t)d], k, D->stream[d]);
+    };
+    PnSliceSums sums{M, k};
+    if (int rc = f.stage(vp, B, (size_t)F * k)) return rc;                         // whole panels pass through P on their way to the slices
+    if (int rc = take_slice(W.b, vp)) return rc;
+    if (prm->precond == FS_PRECOND_DIAG) {
+      if (int rc = f.stage(vq, prm->diag, (size_t)F)) return rc;                   // (whole, in the product vector this scheme leaves idle)
+      if (int rc = each_rank(D, false, [&](int d) {
+            return fs::pcg_dev_dinv(rows_of(d), vq[(size_t)d] + lo_of(d), W.dinv[(size_t)d], D->stream[d]);
+          })) return rc;
+    }
+    if (colj)
+      if (int rc = gram_diag_slices(M, 0.0, W.dinv)) return rc;                    // the rank's own rows: no exchange
+    if (warm) {                                              // the whole X0 is the product's input; Q_r = A'_r (A X0)
+      if (int rc = f.stage(vp, X, (size_t)F * k)) return rc;
+      if (int rc = take_slice(W.sol, vp)) return rc;
+      if (int rc = dist_product(M, false, k, vp, vt)) return rc;
+      if (int rc = each_rank(D, false, shard_product)) return rc;
+    }
+    if (int rc = each_rank(D, false, [&](int d) {
+          return fs::pcgn_slice_init(rows_of(d), k, warm, lv, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], W.q[(size_t)d], sums.of(d),
+                                     D->stream[d]);
+        })) return rc;
+    if (int rc = sums.combine(fs::kPnStepStart, 2, prm->tol)) return rc;           // b.b, r.r, stop, live?
+    if (int rc = each_rank(D, false, [&](int d) {
+          return fs::pcgn_slice_start(rows_of(d), k, lv, colj, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], dinv_of(d), ps[(size_t)d],
+                                      sums.of(d), D->stream[d]);
+        })) return rc;
+    if (int rc = sums.combine(fs::kPnStepRz, 1, 0.0)) return rc;                   // r.z
+    if (int rc = f.look()) return rc;                        // done before the first iteration: no product is enqueued
+    if (f.seen == kRanksGoOn)
+      if (int rc = run_gather(D, gp, ps, vp, false)) return rc;                    // the whole P on every rank
+    if (int rc = f.iterate(cap, false, [&]() -> int {
+          if (int rc2 = dist_product(M, false, k, vp, vt)) return rc2;             // T = A P
+          if (int rc2 = each_rank(D, false, [&](int d) -> int {
+                if (int rc3 = shard_product(d)) return rc3;
+                return fs::pcgn_slice_shift_dot(rows_of(d), k, lv, W.sol[(size_t)d], W.b[(size_t)d], W.q[(size_t)d], ps[(size_t)d], sums.of(d),
+                                                D->stream[d]);
+              })) return rc2;
+          if (int rc2 = sums.combine(fs::kPnStepAlpha, 1, 0.0)) return rc2;        // alpha
+          if (int rc2 = each_rank(D, false, [&](int d) {
+                return fs::pcgn_slice_update(rows_of(d), k, lv, colj, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], ps[(size_t)d],
+                                             W.q[(size_t)d], dinv_of(d), sums.of(d), D->stream[d]);
+              })) return rc2;
+          if (int rc2 = sums.combine(fs::kPnStepBeta, pre ? 2 : 1, 0.0)) return rc2;   // converged?  beta
+          if (int rc2 = each_rank(D, false, [&](int d) {
+                return fs::pcgn_slice_direction(rows_of(d), k, lv, colj, W.sol[(size_t)d], W.b[(size_t)d], ps[(size_t)d], W.r[(size_t)d],
+                                                dinv_of(d), sums.of(d), D->stream[d]);
+              })) return rc2;
+          return run_gather(D, gp, ps, vp, false);                                 // the new P on every rank
+        }, [](int) { return FS_OK; })) return rc;
+    if (int rc = f.settle()) return rc;
+  }
+  // every rank froze every column at the same iteration in the same way: rank 0's per-column array speaks for all
+  double cs0[fs::kPcgnStateDoubles] = {0.0}, mask0 = 0.0;
+  const size_t ncs = (size_t)k * (fs::kPcgnStateDoubles / FS_PCGN_MAX_RHS);
+  if (int rc = each_rank(D, false, [&](int d) -> int {
+        double csd[fs::kPcgnStateDoubles] = {0.0}, std_[fs::kCgStateDoubles];
+        FS_HIP(hipMemcpy(d == 0 ? cs0 : csd, W.cs[(size_t)d], sizeof(double) * ncs, hipMemcpyDeviceToHost));
+        FS_HIP(hipMemcpy(std_, W.st[(size_t)d], sizeof(std_), hipMemcpyDeviceToHost));
+        if (d == 0) mask0 = std_[fs::kCgStateLiveMask];
+        if (d > 0 && (std_[fs::kCgStateLiveMask] != mask0 || !fs::pcgn_same_outcome(csd, cs0, k))) {
+          fs::set_error("fs_dist_pcgn_lambdas: the devices froze the columns differently (a device or an exchange returned different bits)");
+          return FS_ERR_HIP;
+        }
+        return FS_OK;
+      })) return rc;
+  if (vector_device(X) >= 0)
+    if (int rc = wait_for_caller(vector_device(X))) return rc;
+  if (!gather) {
+    if (int rc = vec_store(M, 0, X, W.sol[0], (size_t)F * k)) return rc;
+  } else {
+    for (int d = 0; d < n; ++d)
+      if (int rc = vec_store(M, d, X + (size_t)lo_of(d) * k, W.sol[(size_t)d], (size_t)rows_of(d) * k)) return rc;
+  }
+  if (int rc = dist_sync(D)) return rc;
   fs::pcgn_note_state(f.st0, cs0, k, info);
   return FS_OK;
 }
