@@ -86,6 +86,9 @@ int  fs_set_device(int device);
  * "reproducible", so that a solve is bit-identical from run to run like the reference's loops (cg.h:25-187); 0 = the default kernels.
  * "pcgn_kernel": fs_pcgn's per-iteration vector kernels, 0 = auto (see fs_pcgn), 1 = a lane per row, 2 = the 256-row panels staged
  * through LDS with coalesced accesses; both give the same bits.
+ * "pcgn_compact" (default 0; FS_PCGN_COMPACT): fs_pcgn and fs_pcgn_lambdas, 1 = the live columns of a solve move into a narrower
+ * panel whenever they fit the next of the widths 16, 8, 4, 2, 1, and the products run at that width (see fs_pcgn, "Narrowing");
+ * 0 = every iteration runs on all k columns.  fs_dist_pcgn and fs_dist_pcgn_lambdas do not read it.
  * "dist_cg_scheme" (FS_DIST_CG_SCHEME): fs_dist_cg, fs_dist_pcg and fs_dist_mscg, 0 every device keeps whole vectors, 1 every device keeps its slice (see there). */
 int  fs_set_option(const char *name, int value);
 int  fs_get_option(const char *name);
@@ -337,9 +340,9 @@ enum { FS_PCGN_MAX_RHS = 32 };
  * Without a preconditioner z is r, r.z is r.r and no second sum runs, as in fs_pcg.  So column j is fs_pcg on B[:, j] wherever the
  * k-column product has the single-vector product's bits: bit for bit under "strict_order", and for k = 1 in every mode.
  * Freezing: once a column is frozen no kernel writes its column of X, R or P again; count_j and converged_j are final; its column
- * of P stays as it is and keeps riding through the products (wasted work of a fixed shape: live columns are not compacted into
- * a narrower product).  In a row-major panel a frozen column shares its cache lines with live ones, so freezing saves stores and
- * arithmetic, not lines.  The vector kernels of an iteration come in two forms with the same bits (option "pcgn_kernel"): a lane per
+ * of P stays as it is and keeps riding through the products (wasted work of a fixed shape, unless option "pcgn_compact" moves the
+ * live columns into a narrower product: "Narrowing" below).  In a row-major panel a frozen column shares its cache lines with live
+ * ones, so freezing saves stores and arithmetic, not lines.  The vector kernels of an iteration come in two forms with the same bits (option "pcgn_kernel"): a lane per
  * row (k <= 4), which stops loading a cache line's worth of neighbouring columns (16 j .. 16 j + 15) once ALL of them are frozen,
  * and, for k > 4, the workgroup's 256-row panels staged through LDS with coalesced accesses, which load every line.  A column
  * whose numbers go NaN runs to the cap and changes nothing in the other columns (the products and the sums are per column).
@@ -352,7 +355,35 @@ enum { FS_PCGN_MAX_RHS = 32 };
  * errors (FS_ERR_RELEASED for a k never prepared before fs_matrix_release_csr) are raised before anything is written to X, as is
  * FS_ERR_RELEASED for FS_PRECOND_JACOBI on an At whose plain CSR was released.  FS_ERR_ARG, raised before anything is written: a
  * NULL A, At, X, B or prm; At not of the transposed shape; k outside 1..FS_PCGN_MAX_RHS; precond outside 0..2; FS_PRECOND_DIAG
- * with a NULL diag; tol negative or NaN.  A product's own error is passed through. */
+ * with a NULL diag; tol negative or NaN.  A product's own error is passed through.
+ * Narrowing (option "pcgn_compact" = 1; fs_pcgn and fs_pcgn_lambdas, not the sharded solvers): the solve runs in segments of
+ * non-increasing width.  W(L) is the smallest of {1, 2, 4, 8, 16, 32} that is at least L: the widths at which the k-column products
+ * change price.  The solve starts at width k on all k columns in the caller's X, as without the option.  m_n is the set of live
+ * columns the host knows when it enqueues iteration n = 0, 1, ...: m_0 is the set after the start (the one synchronous look a
+ * solve takes before its first product), m_1 = m_0, and for n >= 2 m_n is the set after iteration n - 2 (the host reads the
+ * flags one iteration behind).  Before it enqueues iteration n at width w, the solve looks for the narrowest usable width w' with
+ * W(|m_n|) <= w' < w; if there is one, the columns of m_n, in increasing original order, move into panels of w' columns (X, R, P;
+ * Q and the products' T are overwritten anyway), followed by padding columns whose X, R, P are +0.0 and which are frozen, and
+ * iteration n and those behind it run at width w' on these panels, with fs_pcgn's own kernels at k = w' (fs_pcgn_lambdas with
+ * the lambdas of those columns; dinv and s are per row and stay).  Otherwise nothing moves: columns that froze without crossing a
+ * width ride along as without the option.  A column that froze after the host's look travels along frozen; its scalars and its
+ * live flag move with it.  A column that is left behind is final: its x goes back into the caller's X then, the last panel's
+ * columns at the end, so a column of X is only ever written with values of its own recurrence, and at the return X, every info
+ * and the debug getters read in original numbering as without the option.  A repack that was enqueued together with an iteration
+ * which turns out not to exist (the solve was done one iteration earlier: the host learns it one behind) does nothing on the
+ * device, like that iteration's other kernels, and is no segment.  At most five repacks per solve.
+ * Usable widths are settled before anything is written to X: for every w < k of 16, 8, 4, 2 fs_matrix_prepare(A, w, 0) and
+ * fs_matrix_prepare(At, w, 0), then the look at the two products described above fs_cg, for width 1 too; a width that answers
+ * FS_ERR_RELEASED is left out, silently, and the solve is still FS_OK; any other error is returned with X untouched.
+ * Work space with the option: 3 w1 F + w2 F doubles more, w1 > w2 the two widest usable widths below k (so at most 3.5 w1 F with
+ * w1 the largest power of two below k: panels of X, R, P at w1 and one of X at w2; the second and fourth repack reuse the
+ * full-width r and p, Q and T stay where they are), and 512 doubles for the scalars in original numbering; all of it is allocated
+ * before the first iteration.  One launch per repack streams 3 (w + w') F doubles; one more, of one workgroup, moves the scalars.
+ * Bits: the vector kernels and red_j give a column the same bits at every k, so wherever a w-column product has the k-column
+ * product's bits -- under "strict_order", where every width runs the row kernel in storage order -- X, every info and every
+ * per-column scalar are bit for bit those of option 0.  In the other modes a w-column product need not have the k-column
+ * product's last bits and counts may move by rounding; the schedule depends on the counts alone, which repeat under fixed-order
+ * products, so a solve with the option repeats its own bits. */
 int fs_pcgn(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k, double lambda, const fs_pcg_params *prm,
             fs_pcg_info *info /* k entries or NULL */, fs_stream_t stream);
 
@@ -513,7 +544,8 @@ int  fs_dist_pcg(fs_dist_matrix_t M, double *x, const double *b, double lambda, 
  * ("strict_order"; k = 1 in every mode).  Convergence across the ranks, a solve done before its first iteration, the fixed order of
  * the products, the work space and the clobbered vectors as for fs_dist_pcg (the k-column vectors of fs_dist_spmm for k > 1).
  * FS_ERR_ARG: those of fs_dist_pcg (X, B for x, b) and k out of range; FS_ERR_RELEASED as there; raised before anything is written
- * to X. */
+ * to X.
+ * Option "pcgn_compact" is not read here nor by fs_dist_pcgn_lambdas: the sharded solves run every iteration on all k columns. */
 int  fs_dist_pcgn(fs_dist_matrix_t M, double *X, const double *B, int k, double lambda, const fs_pcg_params *prm,
                   fs_pcg_info *info /* k entries or NULL */);
 /* fs_dist_pcgn_lambdas: fs_pcgn_lambdas on the sharded matrix -- (A'A + lambda[j] I) x_j = b_j for j < k, k in

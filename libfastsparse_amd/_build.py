@@ -12,7 +12,7 @@ ARCH = "gfx950"
 
 HIP_SOURCES = ["fs_probes.hip", "fs_kernels.hip", "fs_kernels_tiled.hip", "fs_kernels_twopass.hip", "fs_format.hip", "fs_copies.hip", "fs_abi.hip", "fs_dropin.hip", "fs_cg.hip", "fs_dist.hip"]
 C_SOURCES = ["fs_host.c", "fs_sort.c"]
-HEADERS = [os.path.join(CSRC, h) for h in ("fs_common.h", "fs_geometry.h", "fs_kernel_util.h", "fs_format_util.h", "fs_plan.h", "fs_dist_plan.h")] + [os.path.join(ROOT, "include", h) for h in
+HEADERS = [os.path.join(CSRC, h) for h in ("fs_common.h", "fs_geometry.h", "fs_kernel_util.h", "fs_format_util.h", "fs_plan.h", "fs_dist_plan.h", "fs_pcgn_plan.h")] + [os.path.join(ROOT, "include", h) for h in
                                                  ("fastsparse_hip.h", "sparse.h", "dsparse.h", "csr.h", "cbcsr.h", "cg.h", "linalg.h", "hilbert.h", "quickSort.h", "quickSortD.h")]
 
 

@@ -454,6 +454,18 @@ def pcgn_lambdas(A, At, X, B, lams, tol, max_iter=0, precond=FS_PRECOND_JACOBI, 
     return list(infos)[:k]
 
 
+def pcgn_segments():
+    """The segments of the last pcgn / pcgn_lambdas on the calling thread (fs_debug_last_pcgn_segments): a list of (first iteration,
+    width, mask of the original columns the panel holds); [(0, k, all columns)] unless option "pcgn_compact" moved the live columns
+    into a narrower panel."""
+    L = lib()
+    L.fs_debug_last_pcgn_segments.argtypes = [C.POINTER(C.c_int), C.c_int]
+    out = (C.c_int * 24)()
+    n = L.fs_debug_last_pcgn_segments(out, 8)
+    check(min(n, 0), "fs_debug_last_pcgn_segments")
+    return [(out[3 * i], out[3 * i + 1], out[3 * i + 2] & 0xFFFFFFFF) for i in range(n)]
+
+
 def dist_matrix_pair(A, At):
     """A and the caller's own A' (two fs_dist_matrix_t handles of one context) as one handle for the transposed products and the
     sharded solvers (fs_dist_matrix_pair): the shards are shared, not copied.  Returns the new handle; the caller destroys it with

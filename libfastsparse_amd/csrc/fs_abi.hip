@@ -43,6 +43,7 @@ Options &options()
     if (const char *v = getenv("FS_CG_FIXED_ORDER")) q.cg_fixed_order = atoi(v);
     if (const char *v = getenv("FS_DIST_CG_SCHEME")) q.dist_cg_scheme = atoi(v);
     if (const char *v = getenv("FS_RELEASE_CSR")) q.release_csr = atoi(v);
+    if (const char *v = getenv("FS_PCGN_COMPACT")) q.pcgn_compact = atoi(v);
     return q;
   }();
   return o;
@@ -59,6 +60,7 @@ static int *option_by_name(const char *name)
       {"long_rows", &Options::long_rows}, {"long_min_len", &Options::long_min_len}, {"long_geometry", &Options::long_geometry},
       {"device_build", &Options::device_build}, {"ata_kernel", &Options::ata_kernel}, {"spmm_wide", &Options::spmm_wide},
       {"spmm_kernel", &Options::spmm_kernel}, {"pcgn_kernel", &Options::pcgn_kernel}, {"cg_fixed_order", &Options::cg_fixed_order},
+      {"pcgn_compact", &Options::pcgn_compact},
       {"release_csr", &Options::release_csr}, {"dist_cg_scheme", &Options::dist_cg_scheme}};
   for (const auto &e : table)
     if (!strcmp(name, e.name)) return &(options().*e.field);

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "fs_common.h"
+#include "fs_pcgn_plan.h"
 
 namespace fs {
 
@@ -1244,6 +1245,137 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_step_kernel(const double *__
   else st[kStIter] += 1.0;
 }
 
+// ---- option "pcgn_compact": the live columns of a solve move into a narrower panel (the schedule: fs_pcgn_plan.h).  One launch
+// takes up to three row-major n x ws panels (X, R, P) to three n x wd panels: destination column c is source column map.v[c], or,
+// where map.v[c] < 0, +0.0 (KEEP false: a padding column of the narrower panel) or left as it is (KEEP true: the way back, the
+// finished columns of a narrow X into the caller's n x k panel, whose other columns belong to other recurrences).  A pure stream
+// in the shape of the staged vector kernels: the workgroup's 256 rows, pl_rows at a time, come in with coalesced 16-byte loads
+// into a tile of LDS padded to an odd row length and leave in destination order with coalesced 16-byte stores; the 1024 x 256
+// grid with a grid stride.  tiles: bit t set when a column 16 t .. 16 t + 15 of the source is selected -- a 16-column tile (one
+// 128-byte line of an aligned row) without a selected column is not loaded.  st != NULL: a launch behind the end of the solve
+// does nothing, like the iteration it was enqueued with.
+struct PcgnColMap { signed char v[kPcgnMaxRhs]; };
+
+template <int KMAX>
+__device__ __forceinline__ void pr_in(double *__restrict__ tile, const double *__restrict__ g, int ne, int k, unsigned tiles)
+{
+  constexpr int LD = KMAX + 1;
+  if (((uintptr_t)g & 15) == 0) {
+#pragma unroll 4
+    for (int e = 2 * threadIdx.x; e < ne; e += 2 * kRedThreads) {
+      const int r = e / k, c = e - r * k, c1 = c + 1 < k ? c + 1 : 0;
+      if ((((tiles >> (c >> 4)) | (tiles >> (c1 >> 4))) & 1u) == 0u) continue;
+      if (e + 1 < ne) {
+        const double2 d = *reinterpret_cast<const double2 *>(g + e);
+        tile[r * LD + c] = d.x;
+        tile[c + 1 < k ? r * LD + c + 1 : (r + 1) * LD] = d.y;
+      } else {
+        tile[r * LD + c] = g[e];
+      }
+    }
+  } else {
+#pragma unroll 4
+    for (int e = threadIdx.x; e < ne; e += kRedThreads) {
+      const int r = e / k, c = e - r * k;
+      if (((tiles >> (c >> 4)) & 1u) != 0u) tile[r * LD + c] = g[e];
+    }
+  }
+}
+
+// ne = rows x wd doubles of the destination, from the tile's columns smap[c]
+template <int KMAX, bool KEEP>
+__device__ __forceinline__ void pr_out(double *__restrict__ g, const double *__restrict__ tile, int ne, int wd, const int *__restrict__ smap)
+{
+  constexpr int LD = KMAX + 1;
+  if (((uintptr_t)g & 15) == 0) {
+    for (int e = 2 * threadIdx.x; e < ne; e += 2 * kRedThreads) {
+      const int r = e / wd, c = e - r * wd;
+      const bool two = e + 1 < ne;
+      const int r1 = c + 1 < wd ? r : r + 1, c1 = c + 1 < wd ? c + 1 : 0;
+      const int s0 = smap[c], s1 = two ? smap[c1] : -1;
+      const double a = s0 >= 0 ? tile[r * LD + s0] : 0.0, b = s1 >= 0 ? tile[r1 * LD + s1] : 0.0;
+      const bool w0 = !KEEP || s0 >= 0, w1 = two && (!KEEP || s1 >= 0);
+      if (w0 && w1) *reinterpret_cast<double2 *>(g + e) = make_double2(a, b);
+      else if (w0) g[e] = a;
+      else if (w1) g[e + 1] = b;
+    }
+  } else {
+    for (int e = threadIdx.x; e < ne; e += kRedThreads) {
+      const int r = e / wd, s0 = smap[e - r * wd];
+      if (!KEEP || s0 >= 0) g[e] = s0 >= 0 ? tile[r * LD + s0] : 0.0;
+    }
+  }
+}
+
+// KMAX: the shape of the source width (ws <= KMAX)
+template <int KMAX, bool KEEP>
+__global__ __launch_bounds__(kRedThreads) void pcgn_repack_kernel(int n, int ws, int wd, PcgnColMap map, unsigned tiles,
+                                                                 const double *__restrict__ S0, const double *__restrict__ S1,
+                                                                 const double *__restrict__ S2, double *__restrict__ D0,
+                                                                 double *__restrict__ D1, double *__restrict__ D2,
+                                                                 const double *__restrict__ st)
+{
+  if (st && st[kStDone] != 0.0) return;
+  constexpr int LD = KMAX + 1;
+  constexpr int TR = pl_rows<KMAX>();
+  __shared__ double t0[TR * LD];
+  __shared__ int smap[kPcgnMaxRhs];
+  if (threadIdx.x < kPcgnMaxRhs) smap[threadIdx.x] = map.v[threadIdx.x];   // (read behind the tile loop's first barrier)
+  for (int blk0 = blockIdx.x * kRedThreads; blk0 < n; blk0 += gridDim.x * kRedThreads)      // (workgroup-uniform)
+  for (int row0 = blk0; row0 < blk0 + kRedThreads && row0 < n; row0 += TR) {                // the workgroup's 256 rows, TR at a time
+    const int nr = n - row0 < TR ? n - row0 : TR;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double *S = a == 0 ? S0 : a == 1 ? S1 : S2;
+      double *D = a == 0 ? D0 : a == 1 ? D1 : D2;
+      if (!S) continue;                                                                     // (a kernel argument: uniform)
+      pr_in<KMAX>(t0, S + (size_t)row0 * ws, nr * ws, ws, tiles);
+      __syncthreads();
+      pr_out<KMAX, KEEP>(D + (size_t)row0 * wd, t0, nr * wd, wd, smap);
+      __syncthreads();
+    }
+  }
+}
+
+// the scalars follow their columns: one workgroup.  cs[] holds the w_old columns of the panel the solve leaves, home[] every
+// column's scalars in ORIGINAL numbering.  First the columns of the old panel go home (home_of.v[c]: the original column of the
+// old panel's column c, < 0: padding) -- a column that stays behind is final there.  Then cs[] and st[kStLiveMask] are rewritten
+// for the new panel: its column c is the old panel's column from.v[c]; from.v[c] < 0: padding, all zeros, not live.  k_final > 0
+// (the end of the solve) instead leaves the mask of the k_final original columns in st[]: home[] is then the solve's cs[]
+__global__ __launch_bounds__(kRedThreads) void pcgn_remap_kernel(double *st, double *cs, double *home, PcgnColMap home_of, PcgnColMap from,
+                                                                int w_old, int w_new, int k_final, int check_done)
+{
+  if (check_done && st[kStDone] != 0.0) return;
+  __shared__ double a[kPcgnMaxRhs * kPnStride];
+  __shared__ int ho[kPcgnMaxRhs], fr[kPcgnMaxRhs];
+  for (int i = threadIdx.x; i < kPcgnMaxRhs * kPnStride; i += kRedThreads) a[i] = i < w_old * kPnStride ? cs[i] : 0.0;
+  if (threadIdx.x < kPcgnMaxRhs) { ho[threadIdx.x] = home_of.v[threadIdx.x]; fr[threadIdx.x] = from.v[threadIdx.x]; }
+  __syncthreads();
+  for (int i = threadIdx.x; i < w_old * kPnStride; i += kRedThreads) {
+    const int o = ho[i / kPnStride];
+    if (o >= 0) home[o * kPnStride + i % kPnStride] = a[i];
+  }
+  if (k_final > 0) {
+    __threadfence_block();
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    unsigned m = 0u;
+    for (int j = 0; j < k_final; ++j)
+      if (home[j * kPnStride + kPnLive] != 0.0) m |= 1u << j;
+    st[kStLiveMask] = (double)m;
+    return;
+  }
+  for (int i = threadIdx.x; i < kPcgnMaxRhs * kPnStride; i += kRedThreads) {
+    const int c = i / kPnStride, s = c < w_new ? fr[c] : -1;
+    cs[i] = s >= 0 ? a[s * kPnStride + i % kPnStride] : 0.0;
+  }
+  if (threadIdx.x != 0) return;
+  unsigned m = 0u;
+  for (int c = 0; c < w_new; ++c)
+    if (fr[c] >= 0 && a[fr[c] * kPnStride + kPnLive] != 0.0) m |= 1u << c;
+  st[kStLiveMask] = (double)m;
+}
+
 // the kernels' shape for k columns: KMAX = 4, 8, 16 or 32 sums per thread, VEC as in pcgn_init_kernel
 template <int KMAX, int VEC> struct PcgnShape { static constexpr int kmax = KMAX, vec = VEC; };
 template <typename F>
@@ -1646,6 +1778,27 @@ int pcgn_dev_rank_step(PcgnStep step, const double *all, int nranks, int k, int 
   return FS_OK;
 }
 
+// option "pcgn_compact": up to three n x ws panels into n x wd panels by `map` (pcgn_repack_kernel; a NULL source is skipped)
+static int pcgn_repack_launch(bool keep, int n, int ws, int wd, const PcgnColMap &map, const double *S0, const double *S1, const double *S2,
+                              double *D0, double *D1, double *D2, const double *st, hipStream_t s)
+{
+  unsigned tiles = 0u;
+  for (int c = 0; c < wd; ++c)
+    if (map.v[c] >= 0) tiles |= 1u << (map.v[c] >> 4);
+  const dim3 g(kRedBlocks), blk(kRedThreads);
+  auto go = [&](auto kmax) {
+    constexpr int KMAX = decltype(kmax)::value;
+    if (keep) hipLaunchKernelGGL((pcgn_repack_kernel<KMAX, true>), g, blk, 0, s, n, ws, wd, map, tiles, S0, S1, S2, D0, D1, D2, st);
+    else      hipLaunchKernelGGL((pcgn_repack_kernel<KMAX, false>), g, blk, 0, s, n, ws, wd, map, tiles, S0, S1, S2, D0, D1, D2, st);
+  };
+  if (ws <= 4) go(std::integral_constant<int, 4>{});
+  else if (ws <= 8) go(std::integral_constant<int, 8>{});
+  else if (ws <= 16) go(std::integral_constant<int, 16>{});
+  else go(std::integral_constant<int, 32>{});
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
 // ---- fs_mscg's steps as launchers (fs_mscg; fs_dist_mscg on every rank: whole vectors, or the rank's slice of r, p, q, the x_i
 // and the P_i).  The vector kernels take (n, part), the scalar kernels (partials, count): kRedBlocks partials of whole vectors, or
 // the ranks' values, gathered.  A slice's sums go through final_sum_kernel into the send slot, as in finish_sums.
@@ -1799,6 +1952,21 @@ static thread_local int g_last_mscg_doubles = 0;
 static thread_local double g_last_pcgn_state[kPcgnMaxRhs * kPnStride];
 static thread_local int g_last_pcgn_doubles = 0;
 
+// the segments of the last fs_pcgn / fs_pcgn_lambdas on the calling thread: {first iteration, width, mask of original columns} each
+constexpr int kPcgnMaxSegments = 8;
+static thread_local int g_last_pcgn_segments[3 * kPcgnMaxSegments];
+static thread_local int g_last_pcgn_nseg = 0;
+
+static void pcgn_note_segments(const std::vector<PcgnSegment> &segs)
+{
+  g_last_pcgn_nseg = (int)segs.size() < kPcgnMaxSegments ? (int)segs.size() : kPcgnMaxSegments;
+  for (int i = 0; i < g_last_pcgn_nseg; ++i) {
+    g_last_pcgn_segments[3 * i] = segs[(size_t)i].first;
+    g_last_pcgn_segments[3 * i + 1] = segs[(size_t)i].width;
+    g_last_pcgn_segments[3 * i + 2] = (int)segs[(size_t)i].mask;
+  }
+}
+
 void note_cg_state(const double *st_host)
 {
   for (int i = 0; i < kStDoubles; ++i) g_last_cg_state[i] = st_host[i];
@@ -1817,6 +1985,7 @@ void pcgn_note_state(const double *fin_in, const double *fcs, int k, fs_pcg_info
   note_cg_state(fin);
   for (int i = 0; i < k * kPnStride; ++i) g_last_pcgn_state[i] = fcs[i];
   g_last_pcgn_doubles = k * kPnStride;
+  pcgn_note_segments({PcgnSegment{0, k, pcgn_all_columns(k)}});   // a solve that narrowed says so behind this call
   for (int j = 0; info && j < k; ++j) {
     const double *e = fcs + j * kPnStride;
     info[j].iterations = (int)e[kPnCount];                   // a column still live at the cap: count = cap, converged 0
@@ -1916,14 +2085,16 @@ struct CgSolve {
   // before anything is written to the caller's x: a solve whose products would read plain CSR arrays that fs_matrix_release_csr
   // gave back (strict_order, spmv_kernel 1-3, the row kernel of k columns) ends here and not behind its start kernels.  For
   // k >= 2 after the solver's fs_matrix_prepare calls: they settle the plan
-  int ready()
+  int ready() { return ready_for(k); }
+  // the same look at the products of kk columns (option "pcgn_compact": the widths a solve may narrow to)
+  int ready_for(int kk)
   {
     for (fs_matrix_t M : {A, At}) {
       if (M->a.nrow == 0) continue;
       bool plain;
       {
         std::lock_guard<std::mutex> g(M->lock);
-        plain = k == 1 ? spmv_reads_plain_csr(M->a) : spmm_reads_plain_csr(M->a, k);
+        plain = kk == 1 ? spmv_reads_plain_csr(M->a) : spmm_reads_plain_csr(M->a, kk);
       }
       if (plain)
         if (int rc = need_plain_csr(M->a, who)) return rc;
@@ -1974,6 +2145,133 @@ struct CgSolve {
   }
 };
 
+// ---- option "pcgn_compact": what a narrowing solve holds besides CgSolve's work space, and its iterations ------------------------
+// A panel of the solve: w columns of X, R, P; orig.v[c]: the original column of its column c, < 0: padding
+struct PcgnPanel {
+  int w;
+  double *X, *R, *P;
+  PcgnColMap orig;
+};
+
+// The narrow panels: the first, third and fifth repack go to xa, ra, pa (w1 F doubles each, w1 the widest usable rung), the second
+// and fourth to xb (w2 F, the next rung) and to CgSolve's full-width r and p, which the first repack left free.  Q and the
+// products' T stay in CgSolve's q and tmp at every width.  home: every column's scalars in original numbering.  h: st[0 .. 12] of
+// the two most recent iterations in pinned memory -- CgFlags' look with the live mask next to `done`
+constexpr int kPcgnLookDoubles = kStLiveMask + 1;
+struct PcgnArena {
+  double *xa = nullptr, *ra = nullptr, *pa = nullptr, *xb = nullptr, *home = nullptr, *h = nullptr;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  int init(Workspace &ws, unsigned usable, int F, const char *who)
+  {
+    int w1 = 0, w2 = 0;
+    for (int w : kPcgnRungs)
+      if ((usable & (unsigned)w) != 0u) { w2 = w1; w1 = w; }
+    xa = ws.get((size_t)w1 * F); ra = ws.get((size_t)w1 * F); pa = ws.get((size_t)w1 * F);
+    xb = w2 ? ws.get((size_t)w2 * F) : xa;
+    home = ws.get(kPcgnMaxRhs * kPnStride);
+    if (!xa || !ra || !pa || !xb || !home) { set_error(std::string(who) + ": out of device memory"); return FS_ERR_HIP; }
+    FS_HIP(hipHostMalloc((void **)&h, sizeof(double) * 2 * kStDoubles));
+    FS_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
+    FS_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
+    return FS_OK;
+  }
+  ~PcgnArena()
+  {
+    if (h) (void)hipHostFree(h);
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// the rungs below k a solve may narrow to, settled before anything is written to X: the one-time work of every rung's products and
+// CgSolve's look at them.  A rung that answers FS_ERR_RELEASED is left out, silently; any other error ends the solve
+static int pcgn_usable_rungs(CgSolve &f, unsigned *usable)
+{
+  *usable = 0u;
+  for (int w : {16, 8, 4, 2, 1}) {
+    if (w >= f.k) continue;
+    int rc = FS_OK;
+    if (w >= 2) {
+      rc = fs_matrix_prepare(f.A, w, 0, f.stream);
+      if (!rc) rc = fs_matrix_prepare(f.At, w, 0, f.stream);
+    }
+    if (!rc) rc = f.ready_for(w);
+    if (rc == FS_ERR_RELEASED) continue;
+    if (rc) return rc;
+    *usable |= (unsigned)w;
+  }
+  return FS_OK;
+}
+
+// CgSolve::iterate for a solve that narrows.  steps(w, lambdas, X, B, R, P): everything of an iteration behind the products on a
+// panel of w columns.  *end: the panel the solve ends in (X the caller's: nothing moved)
+template <typename Steps>
+static int pcgn_iterate_narrowing(CgSolve &f, int cap, PcgnSchedule &S, double *X, const double *B, const PcgnLambdas &lv, double *cs,
+                                  PcgnArena &M, Steps steps, PcgnPanel *end)
+{
+  hipStream_t s = (hipStream_t)f.stream;
+  const int k = f.k, F = f.F;
+  double *st = f.st;
+  PcgnPanel cur{k, X, f.r, f.p, {}};
+  for (int c = 0; c < kPcgnMaxRhs; ++c) cur.orig.v[c] = (signed char)(c < k ? c : -1);
+  *end = cur;
+  FS_HIP(hipMemcpyAsync(M.h, st, sizeof(double) * kPcgnLookDoubles, hipMemcpyDeviceToHost, s));
+  FS_HIP(hipStreamSynchronize(s));
+  if (M.h[kStDone] != 0.0) return FS_OK;
+  auto original = [](const PcgnColMap &orig, int w, unsigned m) {          // a panel's mask in original numbering
+    unsigned o = 0u;
+    for (int c = 0; c < w; ++c)
+      if (((m >> c) & 1u) != 0u && orig.v[c] >= 0) o |= 1u << orig.v[c];
+    return o;
+  };
+  unsigned known = original(cur.orig, k, (unsigned)M.h[kStLiveMask]);        // m_0 = m_1; then the mask after iteration n - 2
+  PcgnPanel prev = cur, ran[2] = {cur, cur};                                 // ran[n & 1]: the panel iteration n ran on
+  PcgnLambdas lw = lv;
+  int repacks = 0;
+  for (int n = 0; n < cap; ++n) {
+    const int to = S.before_iteration(n, known);
+    if (to) {
+      prev = cur;
+      const bool first = (repacks & 1) == 0;
+      PcgnPanel nx{to, first ? M.xa : M.xb, first ? M.ra : f.r, first ? M.pa : f.p, {}};
+      PcgnColMap from, back;
+      for (int c = 0; c < kPcgnMaxRhs; ++c) from.v[c] = back.v[c] = nx.orig.v[c] = -1;
+      int at = 0;
+      bool leave = false;
+      for (int c = 0; c < cur.w; ++c) {
+        const int o = cur.orig.v[c];
+        if (o < 0) continue;
+        if (((known >> o) & 1u) != 0u) { from.v[at] = (signed char)c; nx.orig.v[at] = (signed char)o; ++at; }
+        else if (cur.X != X) { back.v[o] = (signed char)c; leave = true; }    // final: its x goes back to the caller's panel
+      }
+      if (leave)
+        if (int rc = pcgn_repack_launch(true, F, cur.w, k, back, cur.X, nullptr, nullptr, X, nullptr, nullptr, st, s)) return rc;
+      if (int rc = pcgn_repack_launch(false, F, cur.w, to, from, cur.X, cur.R, cur.P, nx.X, nx.R, nx.P, st, s)) return rc;
+      hipLaunchKernelGGL(pcgn_remap_kernel, dim3(1), dim3(kRedThreads), 0, s, st, cs, M.home, cur.orig, from, cur.w, to, 0, 1);
+      FS_HIP(hipGetLastError());
+      cur = nx;
+      ++repacks;
+    }
+    ran[n & 1] = cur;
+    for (int c = 0; c < kPcgnMaxRhs; ++c) lw.v[c] = cur.orig.v[c] >= 0 ? lv.v[(int)cur.orig.v[c]] : 0.0;
+    if (int rc = cur.w == 1 ? fs_spmv(f.A, f.tmp, cur.P, f.stream) : fs_spmm(f.A, f.tmp, cur.P, cur.w, f.stream)) return rc;
+    if (int rc = cur.w == 1 ? fs_spmv(f.At, f.q, f.tmp, f.stream) : fs_spmm(f.At, f.q, f.tmp, cur.w, f.stream)) return rc;
+    if (int rc = steps(cur.w, lw, cur.X, cur.X == X ? B : cur.X, cur.R, cur.P)) return rc;
+    FS_HIP(hipMemcpyAsync(M.h + kStDoubles * (n & 1), st, sizeof(double) * kPcgnLookDoubles, hipMemcpyDeviceToHost, s));
+    FS_HIP(hipEventRecord(M.ev[n & 1], s));
+    if (n >= 1) {
+      FS_HIP(hipEventSynchronize(M.ev[(n - 1) & 1]));
+      const double *h = M.h + kStDoubles * ((n - 1) & 1);
+      if (h[kStDone] != 0.0) {                              // done before iteration n: what was enqueued with it did nothing
+        if (to) { S.not_run(n); cur = prev; }
+        break;
+      }
+      known = original(ran[(n - 1) & 1].orig, ran[(n - 1) & 1].w, (unsigned)h[kStLiveMask]);
+    }
+  }
+  *end = cur;
+  return FS_OK;
+}
+
 // fs_pcgn's frame, and fs_pcgn_lambdas' (lams: k doubles on the host; lambda is not read then).  The two differ in the lambda the
 // kernels take and in what FS_PRECOND_JACOBI leaves in `dinv`: the inverse of fs_gram_diag(At, lambda), or s = fs_gram_diag(At, 0)
 // itself, which the per-column kernels invert as s + lambda_c per element (no pcg_dev_dinv pass)
@@ -1997,6 +2295,9 @@ static int pcgn_solve(const char *who, fs_matrix_t A, fs_matrix_t At, double *X,
     if (int rc = fs_matrix_prepare(At, k, 0, stream)) return rc;
   }
   if (int rc = f.ready()) return rc;
+  unsigned usable = 0u;                                      // option "pcgn_compact": the rungs below k the solve may narrow to
+  if (options().pcgn_compact != 0)
+    if (int rc = pcgn_usable_rungs(f, &usable)) return rc;
   const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
   const bool colj = lams && prm->precond == FS_PRECOND_JACOBI;   // the diagonal follows the column: dinv holds s
   const int F = f.F;
@@ -2005,6 +2306,9 @@ static int pcgn_solve(const char *who, fs_matrix_t A, fs_matrix_t At, double *X,
   double *dinv = nullptr, *own = nullptr;
   const size_t npart = (size_t)kRedBlocks * 2 * k;
   if (int rc = f.alloc(pre ? &dinv : nullptr, F, &own, npart + kPcgnMaxRhs * kPnStride)) return rc;
+  PcgnArena narrow;
+  if (usable)
+    if (int rc = narrow.init(f.ws, usable, F, who)) return rc;
   double *r = f.r, *p = f.p, *q = f.q, *st = f.st, *part = own, *cs = own + npart;
   if (int rc = pcgn_dev_clear(cs, s)) return rc;
   if (prm->precond == FS_PRECOND_JACOBI)
@@ -2018,15 +2322,35 @@ static int pcgn_solve(const char *who, fs_matrix_t A, fs_matrix_t At, double *X,
   if (int rc = colj   ? pcgn_init_launch(F, k, warm, lv, B, X, r, p, q, dinv, part, st, cs, prm->tol, s, lv)
                : lams ? pcgn_init_launch(F, k, warm, lv, B, X, r, p, q, dinv, part, st, cs, prm->tol, s)
                       : pcgn_dev_init(F, k, warm, lambda, B, X, r, p, q, dinv, part, st, cs, prm->tol, s)) return rc;
-  if (int rc = f.iterate(cap, true, [&] {
-        return colj   ? pcgn_steps_launch(F, k, lv, X, B, r, p, q, dinv, part, st, cs, s, lv)
-               : lams ? pcgn_steps_launch(F, k, lv, X, B, r, p, q, dinv, part, st, cs, s)
-                      : pcgn_dev_steps(F, k, lambda, X, B, r, p, q, dinv, part, st, cs, s);
-      })) return rc;
+  // everything of an iteration behind the products, on a panel of w columns (w = k: the caller's X, the solve's r and p)
+  auto steps = [&](int w, const PcgnLambdas &lw, double *Xw, const double *Bw, double *Rw, double *Pw) {
+    return colj   ? pcgn_steps_launch(F, w, lw, Xw, Bw, Rw, Pw, q, dinv, part, st, cs, s, lw)
+           : lams ? pcgn_steps_launch(F, w, lw, Xw, Bw, Rw, Pw, q, dinv, part, st, cs, s)
+                  : pcgn_dev_steps(F, w, lambda, Xw, Bw, Rw, Pw, q, dinv, part, st, cs, s);
+  };
+  PcgnSchedule sched(k, usable);
+  const double *fcs_dev = cs;
+  if (!usable) {
+    if (int rc = f.iterate(cap, true, [&] { return steps(k, lv, X, B, r, p); })) return rc;
+  } else {
+    PcgnPanel end;
+    if (int rc = pcgn_iterate_narrowing(f, cap, sched, X, B, lv, cs, narrow, steps, &end)) return rc;
+    if (end.X != X) {                                        // the last panel's x and every column's scalars back in original numbering
+      PcgnColMap back, none;
+      for (int c = 0; c < kPcgnMaxRhs; ++c) back.v[c] = none.v[c] = -1;
+      for (int c = 0; c < end.w; ++c)
+        if (end.orig.v[c] >= 0) back.v[(int)end.orig.v[c]] = (signed char)c;
+      if (int rc = pcgn_repack_launch(true, F, end.w, k, back, end.X, nullptr, nullptr, X, nullptr, nullptr, nullptr, s)) return rc;
+      hipLaunchKernelGGL(pcgn_remap_kernel, dim3(1), dim3(kRedThreads), 0, s, st, cs, narrow.home, end.orig, none, end.w, 0, k, 0);
+      FS_HIP(hipGetLastError());
+      fcs_dev = narrow.home;
+    }
+  }
   double fcs[kPcgnMaxRhs * kPnStride] = {0.0};
-  FS_HIP(hipMemcpyAsync(fcs, cs, sizeof(double) * k * kPnStride, hipMemcpyDeviceToHost, s));
+  FS_HIP(hipMemcpyAsync(fcs, fcs_dev, sizeof(double) * k * kPnStride, hipMemcpyDeviceToHost, s));
   if (int rc = f.finish()) return rc;
   pcgn_note_state(f.fin, fcs, k, info);
+  pcgn_note_segments(sched.segs);
   return FS_OK;
 }
 
@@ -2212,6 +2536,16 @@ int fs_debug_last_mscg_state(double *out, int max_doubles)
   const int n = g_last_mscg_doubles < max_doubles ? g_last_mscg_doubles : max_doubles;
   for (int i = 0; i < n; ++i) out[i] = g_last_mscg_state[i];
   return n;
+}
+
+// the segments of the last fs_pcgn / fs_pcgn_lambdas on the calling thread (option "pcgn_compact"): three ints per segment -- its first
+// iteration, its width, the mask of the original columns its panel holds -- for at most max_segments of them.  Returns the number
+// of segments, 0 before the first solve; one segment (0, k, all columns) when nothing moved.  Diagnostics, not in the header.
+int fs_debug_last_pcgn_segments(int *out, int max_segments)
+{
+  if (!out || max_segments < 0) { set_error("fs_debug_last_pcgn_segments: bad argument"); return FS_ERR_ARG; }
+  for (int i = 0; i < 3 * (g_last_pcgn_nseg < max_segments ? g_last_pcgn_nseg : max_segments); ++i) out[i] = g_last_pcgn_segments[i];
+  return g_last_pcgn_nseg;
 }
 
 // the final per-column array of the last fs_pcgn on the calling thread: k * kPnStride doubles (layout of the kPn enum), at most

@@ -303,6 +303,8 @@ struct Options {
   int spmm_kernel = 0;   // multi-column products: 0 auto, 1 row kernel, 2 k-column two-pass sweep (k = 2..4), 3 one
                          // single-vector sweep per column, 4 the MFMA row kernel (experiment, see spmm_mfma_kernel)
   int pcgn_kernel = 0;     // fs_pcgn's per-iteration vector kernels: 0 auto, 1 a lane per row, 2 panels staged through LDS
+  int pcgn_compact = 0;    // fs_pcgn / fs_pcgn_lambdas: 1 moves the live columns into a narrower panel whenever they fit the next rung of
+                           // {16, 8, 4, 2, 1} (fs_pcgn_plan.h); FS_PCGN_COMPACT presets it; the sharded solvers do not read it
   int cg_fixed_order = 1;  // fs_cg / fs_cg2 / fs_dist_cg run their products with fixed-order sums (as under "reproducible"), so
                            // that a solve is bit-identical from run to run like the reference's (cg.h:25-187); 0: the default kernels
   int release_csr = 0;     // 1: fs_csr_create / fs_coo_create / fs_matrix_build_transpose give the plain CSR arrays back once a re-ordered
