@@ -562,7 +562,8 @@ int fs_debug_ldsx_ticket_giveups(fs_matrix_t A, int transposed)
 }
 
 // the two-pass copy of A (transposed != 0: of A'): device addresses of lcol, vals, gdst, lrow, prod, then n (padded entries), B, P
-// (tools/placement_probe.py: identical copies run at different speeds depending on where their arrays land)
+// (tools/placement_probe.py: identical copies run at different speeds depending on where their arrays land).  vals is the same
+// pointer as ever, its order is pass 2's now (that of lrow and prod): pass 2 is its only reader.
 int fs_debug_two_pass_layout(fs_matrix_t A, int transposed, unsigned long long *out8)
 {
   const fs::DeviceCsr *a = side_or_null(A, transposed);
@@ -586,7 +587,8 @@ long long fs_debug_two_pass_rows8(fs_matrix_t A, int transposed)
   return (long long)a->binned->dummies;
 }
 
-// one pass of the two-pass pair alone (which = 1: pass 1, x -> the product stream; 2: pass 2, the product stream -> y)
+// one pass of the two-pass pair alone (which = 1: pass 1, x -> the stream of gathered x[col]; 2: pass 2, that stream times the
+// values -> y)
 int fs_debug_two_pass_run(fs_matrix_t A, int transposed, int which, double *y, const double *x, fs_stream_t stream)
 {
   const fs::DeviceCsr *a = side_or_null(A, transposed);

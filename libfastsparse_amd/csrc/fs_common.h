@@ -147,10 +147,10 @@ struct TiledCsr {
 // Columns are cut into bands of kBinCols columns (the x slice of a band lives in LDS), (virtual) rows into panels
 // of at most kBinRowsMax rows (the y slice of a panel lives in LDS).  A RUN is the set of entries of one
 // (band, panel) pair, kept in CSR storage order and padded to a multiple of kBinGroup entries.
-//   pass 1 streams the runs in (band, panel) order: local column ids in, products out -- each group of kBinGroup
-//          products goes to the place of its run in (panel, band) order (gdst), i.e. whole 128-byte lines;
-//   pass 2 streams the products of one panel, which are now contiguous, with their local row ids, and adds them
-//          into the y slice.
+//   pass 1 streams the runs in (band, panel) order: local column ids in, x[col] out -- each group of kBinGroup
+//          of them goes to the place of its run in (panel, band) order (gdst), i.e. whole 128-byte lines;
+//   pass 2 streams that stream of one panel, which is now contiguous, with the entries' values and local row ids:
+//          it multiplies and adds the products into the y slice.
 // No access of either pass leaves LDS except the two sequential streams.
 
 // The longest rows of a heavy-tailed matrix (BASELINE config 5: power-law lengths up to 10^6), taken OUT of the two-pass copy.
@@ -187,7 +187,8 @@ struct BinnedCsr {
   int B = 0, P = 0;            // bands, panels
   int64_t n = 0;               // padded entry count (multiple of kBinGroup)
   uint16_t *lcol = nullptr;    // n, pass-1 order: column - band*kBinCols; padding = kBinCols (a zero slot)
-  double *vals = nullptr;      // n, pass-1 order (nullptr: pattern-only); padding = 0
+  double *vals = nullptr;      // n, pass-2 order like prod and the row ids (nullptr: pattern-only); padding and dummies = 0.
+                               // Pass 1 never reads it: it writes x[col] to prod, pass 2 loads the value beside it and multiplies
   unsigned *gdst = nullptr;    // n / kBinGroup: pass-2 group index of every pass-1 group
   uint16_t *lrow = nullptr;    // n, pass-2 order: (virtual) row - first row of the panel; padding = 0
   // OR (kw = 1, dense cells: config 2 has 430 entries per (band, panel) cell, in ascending row order) one BYTE per entry: the step
@@ -200,7 +201,7 @@ struct BinnedCsr {
   int64_t dummies = 0;         // entries added to walk steps above 255
   bool lrow_tried = false;     // the first fixed-order product writes the two-byte ids out once (lrow beside lrow8: the one-wave pass 2
                                // reads those; fs_kernels_twopass.hip, ensure_two_byte_ids)
-  double *prod = nullptr;      // n * kw, pass-2 order: written by pass 1, read by pass 2
+  double *prod = nullptr;      // n * kw, pass-2 order: written by pass 1 (the gathered x), read by pass 2
   unsigned *band_ptr = nullptr;  // B + 1: first pass-1 group of every band
   int nwg1 = 0;                // pass-1 workgroups (persistent, one per CU)
   int slots = 0;               // pass-2 workgroups resident together (one per CU: the y slice fills LDS)

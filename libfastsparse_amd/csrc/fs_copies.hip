@@ -841,7 +841,7 @@ __global__ void bin_scatter_kernel(int64_t nnz, int B, int P, int bcols, int ge,
                                    const int *__restrict__ panel_row, const int *__restrict__ cols,
                                    const double *__restrict__ vals, const int *__restrict__ run_ptr,
                                    const unsigned *__restrict__ start1, const unsigned *__restrict__ start2,
-                                   uint16_t *__restrict__ lcol, double *__restrict__ vals1, uint16_t *__restrict__ lrow)
+                                   uint16_t *__restrict__ lcol, double *__restrict__ vals2, uint16_t *__restrict__ lrow)
 {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nnz) return;
@@ -851,7 +851,7 @@ __global__ void bin_scatter_kernel(int64_t nnz, int B, int P, int bcols, int ge,
   const int64_t pos1 = (int64_t)start1[key] * ge + rank;
   const int64_t pos2 = (int64_t)start2[(int64_t)p * B + b] * ge + rank;
   lcol[pos1] = (uint16_t)(cols[src] - b * bcols);
-  if (vals) vals1[pos1] = vals[src];
+  if (vals) vals2[pos2] = vals[src];                             // the values travel with the row ids: pass 2 multiplies
   lrow[pos2] = (uint16_t)(vrows[src] - panel_row[p]);
 }
 
@@ -879,7 +879,7 @@ __global__ void bin_scatter8_kernel(int64_t nnz, int B, int P, int bcols, int ge
                                     const int *__restrict__ panel_row, const int *__restrict__ cols,
                                     const double *__restrict__ vals, const int *__restrict__ run_ptr,
                                     const unsigned *__restrict__ xs, const unsigned *__restrict__ start1,
-                                    const unsigned *__restrict__ start2, uint16_t *__restrict__ lcol, double *__restrict__ vals1,
+                                    const unsigned *__restrict__ start2, uint16_t *__restrict__ lcol, double *__restrict__ vals2,
                                     uint8_t *__restrict__ lrow8, uint16_t *__restrict__ gbase)
 {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -900,7 +900,7 @@ __global__ void bin_scatter8_kernel(int64_t nnz, int B, int P, int bcols, int ge
   }
   const int before = prev + 255 * (int)dum;
   lcol[base1 + slot] = (uint16_t)(cols[src] - b * bcols);
-  if (vals) vals1[base1 + slot] = vals[src];
+  if (vals) vals2[base2 + slot] = vals[src];
   lrow8[base2 + slot] = (uint8_t)(row - before);
   if ((slot & (ge - 1)) == 0) gbase[(base2 + slot) / ge] = (uint16_t)before;
 }

@@ -14,8 +14,15 @@ namespace fs {
 // L2 answers 8-byte requests (measured 240 G/s when every request hits, 53 G/s when every one goes to HBM),
 // not by bytes.  Here every random access is an LDS access: pass 1 gathers x from a 128 KiB band held in LDS,
 // pass 2 scatters into a 128 KiB slice of y held in LDS, and what travels between them is a sequential stream
-// of products laid out so that each pass reads and writes whole lines.  20.5 bytes per entry at stream speed
-// beat 4 bytes per entry at gather speed.
+// laid out so that each pass reads and writes whole lines.  20.5 bytes per entry at stream speed beat 4 bytes
+// per entry at gather speed.
+//
+// Who multiplies: pass 2.  Pass 1 writes the gathered x[col] to the stream and never sees the values; pass 2 loads
+// an entry's value (BinnedCsr::vals, in pass-2 order) beside its stream slot, multiplies, then adds.  The product is
+// the same IEEE multiplication, rounded on its own (no fused multiply-add), and the additions keep their order, so
+// the bits are what they were when pass 1 multiplied.  The bytes are the same too; they moved from the pass that
+// reads AND writes, where a further read stream cost 4.3 TB/s at the margin, to the read-only pass that moves its
+// bytes at 6.2 TB/s: config 2 - 0.05 ms of 0.88 per product (profiles/values_in_pass2_ab.json).
 //
 // Sum order: a row's terms are added band by band, and inside a band by LDS atomics in no fixed order --
 // the result is exact for pattern matrices with integer-valued x and within the usual rounding bound
@@ -26,11 +33,11 @@ namespace fs {
 // groups and reloads its x band when the share crosses into the next band (every band is loaded once, plus once
 // per share boundary: cutting bands into many small workgroups instead re-reads x several times over)
 // xband: BC + 8 doubles of LDS; slot BC is the zero the padding entries point at.  The share is groups [g0, g1).
-template <bool VALUED, int U, bool NTLD, bool NTST, int BC>
+template <int U, bool NTLD, bool NTST, int BC>
 __device__ __forceinline__ void expand_share(double *__restrict__ xband, int ncol, int B, const unsigned *__restrict__ band_ptr,
-                                             const uint16_t *__restrict__ lcol, const double *__restrict__ vals,
-                                             const unsigned *__restrict__ gdst, const double *__restrict__ x, int xs,
-                                             double *__restrict__ prod, unsigned g0, unsigned g1)
+                                             const uint16_t *__restrict__ lcol, const unsigned *__restrict__ gdst,
+                                             const double *__restrict__ x, int xs, double *__restrict__ prod, unsigned g0,
+                                             unsigned g1)
 {
   const int t = threadIdx.x;
   if (g0 >= g1) return;
@@ -76,48 +83,41 @@ __device__ __forceinline__ void expand_share(double *__restrict__ xband, int nco
     int64_t o = e0 + 2 * t;
     for (; o - 2 * t + kRound <= e1; o += kRound) {
       unsigned a[U], d[U];
-      v2d v[U];
 #pragma unroll
       for (int k = 0; k < U; ++k) {
         const int64_t e = o + (int64_t)k * 2 * kBinBlock;
         a[k] = stream_load<NTLD>((const unsigned *)(lcol + e));
         d[k] = stream_load<NTLD>(gdst + (e >> kBinGroupLog));
-        if (VALUED) v[k] = stream_load<NTLD>((const v2d *)(vals + e));
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int k = 0; k < U; ++k) {
         const int64_t e = o + (int64_t)k * 2 * kBinBlock;
-        v2d p = {xband[a[k] & 0xffffu], xband[a[k] >> 16]};
-        if (VALUED) { p.x *= v[k].x; p.y *= v[k].y; }
+        const v2d p = {xband[a[k] & 0xffffu], xband[a[k] >> 16]};
         stream_store<NTST>(p, (v2d *)(prod + (int64_t)d[k] * kBinGroup + (e & (kBinGroup - 1))));
       }
     }
     for (; o < e1; o += 2 * kBinBlock) {
       const unsigned a = stream_load<NTLD>((const unsigned *)(lcol + o));
       const unsigned d = stream_load<NTLD>(gdst + (o >> kBinGroupLog));
-      v2d p = {xband[a & 0xffffu], xband[a >> 16]};
-      if (VALUED) {
-        const v2d v = stream_load<NTLD>((const v2d *)(vals + o));
-        p.x *= v.x; p.y *= v.y;
-      }
+      const v2d p = {xband[a & 0xffffu], xband[a >> 16]};
       stream_store<NTST>(p, (v2d *)(prod + (int64_t)d * kBinGroup + (o & (kBinGroup - 1))));
     }
     g = gb;
   }
 }
 
-template <bool VALUED, int U, bool NTLD, bool NTST, int BC = kBinCols>
+template <int U, bool NTLD, bool NTST, int BC = kBinCols>
 __global__ __launch_bounds__(kBinBlock) void spmv_expand_kernel(
     int ncol, int B, const unsigned *__restrict__ band_ptr, const uint16_t *__restrict__ lcol,
-    const double *__restrict__ vals, const unsigned *__restrict__ gdst, const double *__restrict__ x, int xs,
-    double *__restrict__ prod, unsigned gbeg, unsigned gend)
+    const unsigned *__restrict__ gdst, const double *__restrict__ x, int xs, double *__restrict__ prod, unsigned gbeg,
+    unsigned gend)
 {
   __shared__ double xband[BC + 8];
   // this launch covers the groups gbeg .. gend (everything, or the bands whose part of x has arrived: fs_spmv_host)
   const uint64_t groups = gend - gbeg;
   const unsigned g0 = gbeg + (unsigned)(groups * blockIdx.x / gridDim.x), g1 = gbeg + (unsigned)(groups * (blockIdx.x + 1) / gridDim.x);
-  expand_share<VALUED, U, NTLD, NTST, BC>(xband, ncol, B, band_ptr, lcol, vals, gdst, x, xs, prod, g0, g1);
+  expand_share<U, NTLD, NTST, BC>(xband, ncol, B, band_ptr, lcol, gdst, x, xs, prod, g0, g1);
 }
 
 // the local rows of the 8 entries e .. e + 7 (e a multiple of 8) as four pairs of 16-bit ids, in two steps so that the loads of
@@ -126,6 +126,7 @@ __global__ __launch_bounds__(kBinBlock) void spmv_expand_kernel(
 // A lane sums its 8 steps; the lane with the second half of a group (e = 8 mod 16: an ODD lane, since a panel's entries start on a
 // group boundary and lane t takes e0 + 8 t + whole rounds) adds the first half's total, fetched from the lane below it (DPP
 // row_shr:1 -- every lane of the wave executes the decode, and an odd lane inside the range has its even neighbour inside too).
+static_assert(kBinGroupLog == 4, "the one-byte row ids (row_ids, line_ids, rows8_decode_kernel) decode groups of 16 entries: two lanes of 8, eight lanes of 2, four words of 4");
 template <bool NTLD, bool L8>
 __device__ __forceinline__ v4u row_ids_load(const uint16_t *__restrict__ lrow, const uint8_t *__restrict__ lrow8,
                                             const uint16_t *__restrict__ gbase, int64_t e)
@@ -181,11 +182,16 @@ __device__ __forceinline__ unsigned line_ids(unsigned raw)
 // with a lane reading 64 consecutive bytes in four loads, four instructions asked for every line and the same policy cost + 14 %).
 // The ids stay plain loads: an instruction takes a fraction of a line of them.  Two steps (16 entries per lane) in flight in whole
 // rounds (straight-line code: see expand_share); what is left after the whole rounds is guarded.
-template <bool NTLD, bool L8 = false>
+// VALUED: what pass 1 left in the stream is x[col]; the entry's value sits at the same index of vals (BinnedCsr::vals is in pass-2
+// order) and is loaded exactly like the stream -- the same 1 KiB per instruction, the same cache policy -- then multiplied in
+// (p = x; p *= v: a product rounded on its own, then the add).  A read stream costs this read-only pass less than it cost pass 1,
+// which reads and writes (profiles/values_in_pass2_ab.json).
+template <bool VALUED, bool NTLD, bool L8 = false>
 __device__ __forceinline__ void reduce_panel(double *__restrict__ ytile, int panel, const unsigned *__restrict__ bin_ptr,
                                              const int *__restrict__ panel_row, const uint16_t *__restrict__ lrow,
-                                             const double *__restrict__ prod, double *__restrict__ y, int ys,
-                                             const uint8_t *__restrict__ lrow8 = nullptr, const uint16_t *__restrict__ gbase = nullptr)
+                                             const double *__restrict__ vals, const double *__restrict__ prod, double *__restrict__ y,
+                                             int ys, const uint8_t *__restrict__ lrow8 = nullptr,
+                                             const uint16_t *__restrict__ gbase = nullptr)
 {
   const int t = threadIdx.x;
   const int r0 = panel_row[panel], nr = panel_row[panel + 1] - r0;
@@ -200,7 +206,7 @@ __device__ __forceinline__ void reduce_panel(double *__restrict__ ytile, int pan
   for (; eb + kRound <= e1; eb += kRound) {
     const int64_t e = eb + lane0;
     unsigned a[2][4];
-    v2d p[2][4];
+    v2d p[2][4], v[2][4];
 #pragma unroll
     for (int k = 0; k < 2; ++k)
 #pragma unroll
@@ -208,6 +214,7 @@ __device__ __forceinline__ void reduce_panel(double *__restrict__ ytile, int pan
         const int64_t ek = e + k * kStep + 128 * j;
         a[k][j] = line_ids_load<L8>(lrow, lrow8, gbase, ek);
         p[k][j] = stream_load<NTLD>((const v2d *)(prod + ek));
+        if (VALUED) v[k][j] = stream_load<NTLD>((const v2d *)(vals + ek));
       }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -215,6 +222,7 @@ __device__ __forceinline__ void reduce_panel(double *__restrict__ ytile, int pan
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const unsigned r = line_ids<L8>(a[k][j]);
+        if (VALUED) { p[k][j].x *= v[k][j].x; p[k][j].y *= v[k][j].y; }
         FS_ADD2(r, p[k][j])
       }
   }
@@ -223,16 +231,18 @@ __device__ __forceinline__ void reduce_panel(double *__restrict__ ytile, int pan
   for (; eb + wave0 < e1; eb += kStep) {
     const int64_t e = eb + lane0;
     unsigned a[4];
-    v2d p[4];
+    v2d p[4], v[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int64_t ej = e + 128 * j, ec = ej < e1 ? ej : e1 - 2;
       a[j] = line_ids_load<L8>(lrow, lrow8, gbase, ec);
       p[j] = stream_load<NTLD>((const v2d *)(prod + ec));
+      if (VALUED) v[j] = stream_load<NTLD>((const v2d *)(vals + ec));
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const unsigned r = line_ids<L8>(a[j]);
+      if (VALUED) { p[j].x *= v[j].x; p[j].y *= v[j].y; }
       if (e + 128 * j < e1) { FS_ADD2(r, p[j]) }
     }
   }
@@ -242,14 +252,14 @@ __device__ __forceinline__ void reduce_panel(double *__restrict__ ytile, int pan
   for (int i = t; i < nr; i += kBinBlock) y[(int64_t)(r0 + i) * ys] = ytile[i];
 }
 
-template <bool NTLD, int RM = kBinRowsMax, bool L8 = false>
+template <bool VALUED, bool NTLD, int RM = kBinRowsMax, bool L8 = false>
 __global__ __launch_bounds__(kBinBlock) void spmv_reduce_kernel(
     const unsigned *__restrict__ bin_ptr, const int *__restrict__ panel_row, const uint16_t *__restrict__ lrow,
-    const double *__restrict__ prod, double *__restrict__ y, int ys, int pbase, const uint8_t *__restrict__ lrow8 = nullptr,
-    const uint16_t *__restrict__ gbase = nullptr)
+    const double *__restrict__ vals, const double *__restrict__ prod, double *__restrict__ y, int ys, int pbase,
+    const uint8_t *__restrict__ lrow8 = nullptr, const uint16_t *__restrict__ gbase = nullptr)
 {
   __shared__ double ytile[RM];
-  reduce_panel<NTLD, L8>(ytile, pbase + blockIdx.x, bin_ptr, panel_row, lrow, prod, y, ys, lrow8, gbase);
+  reduce_panel<VALUED, NTLD, L8>(ytile, pbase + blockIdx.x, bin_ptr, panel_row, lrow, vals, prod, y, ys, lrow8, gbase);
 }
 
 // pass 2 with a FIXED order of additions: ONE wave per panel walks the panel's products in stream order, 512 entries per step
@@ -262,11 +272,18 @@ __global__ __launch_bounds__(kBinBlock) void spmv_reduce_kernel(
 #ifndef FS_ORDERED_DEPTH
 #define FS_ORDERED_DEPTH 16   // steps of loads in flight (config 2: 4 / 6 / 8 / 12 / 16 / 20 -> +13 / +7 / +6 / +4.3 / +3.5 / +3 % over the 16-wave pass)
 #endif
-template <bool NTLD, int RM, int DEPTH, bool L8 = false>
+// VALUED (the values are multiplied in here, see reduce_panel): a step holds 144 bytes per lane, 36 registers, so 16 steps do
+// not fit the 512 registers of a lone wave and 12 spill (20 to 100 bytes of scratch per lane); 10 steps keep 1440 bytes per lane
+// in flight (pattern-only: 16 x 80 = 1280) in 442 to 464 registers, no scratch.  The k = 2 sweep (104 bytes a step) takes 12.
+// Config 2, fixed-order over arrival-order product: 8 / 10 / 12 steps -> + 10-11 / + 10-12 / + 15-19 % (profiles/values_in_pass2_ab.json)
+#ifndef FS_ORDERED_DEPTH_VALUED
+#define FS_ORDERED_DEPTH_VALUED 10
+#endif
+template <bool VALUED, bool NTLD, int RM, int DEPTH, bool L8 = false>
 __global__ __launch_bounds__(64) void spmv_reduce_ordered_kernel(
     const unsigned *__restrict__ bin_ptr, const int *__restrict__ panel_row, const uint16_t *__restrict__ lrow,
-    const double *__restrict__ prod, double *__restrict__ y, int ys, int pbase, const uint8_t *__restrict__ lrow8 = nullptr,
-    const uint16_t *__restrict__ gbase = nullptr)
+    const double *__restrict__ vals, const double *__restrict__ prod, double *__restrict__ y, int ys, int pbase,
+    const uint8_t *__restrict__ lrow8 = nullptr, const uint16_t *__restrict__ gbase = nullptr)
 {
   __shared__ __attribute__((aligned(16))) double ytile[RM];
   const int t = threadIdx.x;
@@ -282,13 +299,16 @@ __global__ __launch_bounds__(64) void spmv_reduce_ordered_kernel(
   FS_ADD(A.w & 0xffffu, P[3].x); FS_ADD(A.w >> 16, P[3].y);
   constexpr int64_t kStep = 8 * 64;
   v4u a[DEPTH];
-  v2d p[DEPTH][4];
+  v2d p[DEPTH][4], v[VALUED ? DEPTH : 1][4];
   // steps past the end re-read the segment's last eight entries (their adds are skipped): every load is unconditional
   auto fetch = [&](int k, int64_t e) {
     const int64_t ec = (e + 8 <= e1) ? e : (e1 - e0 >= 8 ? e1 - 8 : e0);
     a[k] = row_ids_load<NTLD, L8>(lrow, lrow8, gbase, ec);      // (decoded where it is used: the loads of DEPTH steps stay in flight)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) p[k][j] = stream_load<NTLD>((const v2d *)(prod + ec + 2 * j));
+    for (int j = 0; j < 4; ++j) {
+      p[k][j] = stream_load<NTLD>((const v2d *)(prod + ec + 2 * j));
+      if (VALUED) v[k][j] = stream_load<NTLD>((const v2d *)(vals + ec + 2 * j));
+    }
   };
   if (e1 > e0) {
     int64_t e = e0 + 8 * t;
@@ -300,6 +320,10 @@ __global__ __launch_bounds__(64) void spmv_reduce_ordered_kernel(
         const int64_t ek = e + (int64_t)k * kStep;
         const v4u ak = row_ids<L8>(a[k]);
         v2d pk[4] = {p[k][0], p[k][1], p[k][2], p[k][3]};
+        if (VALUED) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { pk[j].x *= v[k][j].x; pk[j].y *= v[k][j].y; }
+        }
         fetch(k, ek + (int64_t)DEPTH * kStep);
         if (ek + 8 <= e1) { FS_ADD8(ak, pk) }
       }
@@ -487,16 +511,16 @@ static int launch_longrows(const DeviceCsr &A, const LongRows &L, const double *
 //   bcsr_A_mul_Bn / bsbm_A_mul_Bn with ncol = 2, 4 (csr.h:441-465, 257-280, sparse.h:318-336) and the two
 //   products of every bsbm_cg2 iteration (cg.h:134-135).
 // Pass 1 keeps a band of X -- kBinCols / K rows of K doubles, 128 KiB -- in LDS; an entry is read once (2-byte
-// local column, value) and gives K products, written as one 128-byte line per group of kBinGroup / K entries to
-// the place of its run in (panel, band) order.  Pass 2 keeps the K-column Y slice of a panel (<= kBinRowsMax / K
-// rows) in LDS and adds the products up.  Per entry: 2 + 8 + 8K written + 8K read + 2 bytes, against K times
+// local column) and gives the K values of its X row, written as one 128-byte line per group of kBinGroup / K entries
+// to the place of its run in (panel, band) order.  Pass 2 keeps the K-column Y slice of a panel (<= kBinRowsMax / K
+// rows) in LDS, multiplies the K values by the entry's value (vals, pass-2 order: one load of 64 / K bytes per lane
+// and step) and adds the products up.  Per entry: 2 + 8K written + 8K read + 8 + 2 bytes, against K times
 // 28.25 for K sweeps of the single-vector pair.  Sum order as the single-vector pair (band-major, LDS atomics).
 // ------------------------------------------------------------------------------------------
-template <bool VALUED, int K, int U>
+template <int K, int U>
 __global__ __launch_bounds__(kBinBlock) void spmm_expand_kernel(
     int ncol, int B, const unsigned *__restrict__ band_ptr, const uint16_t *__restrict__ lcol,
-    const double *__restrict__ vals, const unsigned *__restrict__ gdst, const double *__restrict__ X, int xs,
-    double *__restrict__ prod)
+    const unsigned *__restrict__ gdst, const double *__restrict__ X, int xs, double *__restrict__ prod)
 {
   constexpr int BC = kBinCols / K;       // columns per band
   constexpr int GE = kBinGroup / K;      // entries per group
@@ -544,38 +568,34 @@ __global__ __launch_bounds__(kBinBlock) void spmm_expand_kernel(
     int64_t o = e0 + le;
     for (; o - le + kRound <= e1; o += kRound) {
       unsigned a[U], d[U];
-      double v[U];
 #pragma unroll
       for (int k = 0; k < U; ++k) {
         const int64_t e = o + (int64_t)k * EPS;
         a[k] = lcol[e];
         d[k] = gdst[e / GE];
-        if (VALUED) v[k] = vals[e];
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int k = 0; k < U; ++k) {
         const int64_t e = o + (int64_t)k * EPS;
-        v2d p = *reinterpret_cast<const v2d *>(&xband[a[k] * K + 2 * h]);
-        if (VALUED) { p.x *= v[k]; p.y *= v[k]; }
+        const v2d p = *reinterpret_cast<const v2d *>(&xband[a[k] * K + 2 * h]);
         __builtin_nontemporal_store(p, (v2d *)(prod + ((int64_t)d[k] * GE + (e % GE)) * K + 2 * h));
       }
     }
     for (; o < e1; o += EPS) {
       const unsigned a = lcol[o];
       const unsigned d = gdst[o / GE];
-      v2d p = *reinterpret_cast<const v2d *>(&xband[a * K + 2 * h]);
-      if (VALUED) { const double v = vals[o]; p.x *= v; p.y *= v; }
+      const v2d p = *reinterpret_cast<const v2d *>(&xband[a * K + 2 * h]);
       __builtin_nontemporal_store(p, (v2d *)(prod + ((int64_t)d * GE + (o % GE)) * K + 2 * h));
     }
     g = gb;
   }
 }
 
-template <int K>
+template <bool VALUED, int K>
 __global__ __launch_bounds__(kBinBlock) void spmm_reduce_kernel(
     const unsigned *__restrict__ bin_ptr_all, const int *__restrict__ panel_row_all, const uint16_t *__restrict__ lrow,
-    const double *__restrict__ prod, double *__restrict__ Y, int ys, int pbase)
+    const double *__restrict__ vals, const double *__restrict__ prod, double *__restrict__ Y, int ys, int pbase)
 {
   const unsigned *__restrict__ bin_ptr = bin_ptr_all + pbase;          // this launch covers the panels pbase .. pbase + gridDim.x
   const int *__restrict__ panel_row = panel_row_all + pbase;
@@ -588,15 +608,18 @@ __global__ __launch_bounds__(kBinBlock) void spmm_reduce_kernel(
   __syncthreads();
   const int64_t e0 = (int64_t)bin_ptr[blockIdx.x] * GE, e1 = (int64_t)bin_ptr[blockIdx.x + 1] * GE;
   typedef uint16_t rows_t __attribute__((ext_vector_type(EPL)));
+  typedef double vals_t __attribute__((ext_vector_type(EPL)));       // the lane's EPL values (VALUED: pass 2 multiplies, see reduce_panel)
 #define FS_ADD(idx, val) __hip_atomic_fetch_add(&ytile[idx], val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-  auto add8 = [&](const rows_t a, const v2d (&p)[4]) {
+  auto add8 = [&](const rows_t a, const v2d (&p)[4], const vals_t v) {
 #pragma unroll
     for (int q = 0; q < EPL; ++q) {
       const int base = (int)a[q] * K;
 #pragma unroll
       for (int j = 0; j < K; j += 2) {
-        FS_ADD(base + j, p[(q * K + j) / 2].x);
-        FS_ADD(base + j + 1, p[(q * K + j) / 2].y);
+        v2d t2 = p[(q * K + j) / 2];
+        if (VALUED) { t2.x *= v[q]; t2.y *= v[q]; }
+        FS_ADD(base + j, t2.x);
+        FS_ADD(base + j + 1, t2.y);
       }
     }
   };
@@ -606,23 +629,27 @@ __global__ __launch_bounds__(kBinBlock) void spmm_reduce_kernel(
   for (; e - EPL * t + kRound <= e1; e += kRound) {
     rows_t a[2];
     v2d p[2][4];
+    vals_t v[2] = {};
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int64_t ek = e + k * kStep;
       a[k] = *reinterpret_cast<const rows_t *>(lrow + ek);
+      if (VALUED) v[k] = *reinterpret_cast<const vals_t *>(vals + ek);
 #pragma unroll
       for (int j = 0; j < 4; ++j) p[k][j] = *reinterpret_cast<const v2d *>(prod + ek * K + 2 * j);
     }
     __builtin_amdgcn_sched_barrier(0);
-    add8(a[0], p[0]);
-    add8(a[1], p[1]);
+    add8(a[0], p[0], v[0]);
+    add8(a[1], p[1], v[1]);
   }
   for (; e < e1; e += kStep) {
     const rows_t a = *reinterpret_cast<const rows_t *>(lrow + e);
+    vals_t v = {};
+    if (VALUED) v = *reinterpret_cast<const vals_t *>(vals + e);
     v2d p[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) p[j] = *reinterpret_cast<const v2d *>(prod + e * K + 2 * j);
-    add8(a, p);
+    add8(a, p, v);
   }
 #undef FS_ADD
   __syncthreads();
@@ -630,10 +657,10 @@ __global__ __launch_bounds__(kBinBlock) void spmm_reduce_kernel(
 }
 
 // the same pass with a fixed order of additions: one wave per panel, stream order (see spmv_reduce_ordered_kernel)
-template <int K, int DEPTH>
+template <bool VALUED, int K, int DEPTH>
 __global__ __launch_bounds__(64) void spmm_reduce_ordered_kernel(
     const unsigned *__restrict__ bin_ptr_all, const int *__restrict__ panel_row_all, const uint16_t *__restrict__ lrow,
-    const double *__restrict__ prod, double *__restrict__ Y, int ys, int pbase)
+    const double *__restrict__ vals, const double *__restrict__ prod, double *__restrict__ Y, int ys, int pbase)
 {
   const unsigned *__restrict__ bin_ptr = bin_ptr_all + pbase;
   const int *__restrict__ panel_row = panel_row_all + pbase;
@@ -645,24 +672,29 @@ __global__ __launch_bounds__(64) void spmm_reduce_ordered_kernel(
   for (int i = t; i < nr * K; i += 64) ytile[i] = 0.0;
   const int64_t e0 = (int64_t)bin_ptr[blockIdx.x] * GE, e1 = (int64_t)bin_ptr[blockIdx.x + 1] * GE;
   typedef uint16_t rows_t __attribute__((ext_vector_type(EPL)));
+  typedef double vals_t __attribute__((ext_vector_type(EPL)));       // the lane's EPL values (VALUED: pass 2 multiplies, see reduce_panel)
 #define FS_ADD(idx, val) __hip_atomic_fetch_add(&ytile[idx], val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-  auto add8 = [&](const rows_t a, const v2d (&p)[4]) {
+  auto add8 = [&](const rows_t a, const v2d (&p)[4], const vals_t v) {
 #pragma unroll
     for (int q = 0; q < EPL; ++q) {
       const int base = (int)a[q] * K;
 #pragma unroll
       for (int j = 0; j < K; j += 2) {
-        FS_ADD(base + j, p[(q * K + j) / 2].x);
-        FS_ADD(base + j + 1, p[(q * K + j) / 2].y);
+        v2d t2 = p[(q * K + j) / 2];
+        if (VALUED) { t2.x *= v[q]; t2.y *= v[q]; }
+        FS_ADD(base + j, t2.x);
+        FS_ADD(base + j + 1, t2.y);
       }
     }
   };
   constexpr int64_t kStep = (int64_t)EPL * 64;
   rows_t a[DEPTH];
   v2d p[DEPTH][4];
+  vals_t v[VALUED ? DEPTH : 1] = {};
   auto fetch = [&](int k, int64_t e) {   // steps past the end re-read the segment's last entries (their adds are skipped)
     const int64_t ec = (e + EPL <= e1) ? e : (e1 - e0 >= EPL ? e1 - EPL : e0);
     a[k] = *reinterpret_cast<const rows_t *>(lrow + ec);
+    if (VALUED) v[k] = *reinterpret_cast<const vals_t *>(vals + ec);
 #pragma unroll
     for (int j = 0; j < 4; ++j) p[k][j] = *reinterpret_cast<const v2d *>(prod + ec * K + 2 * j);
   };
@@ -676,8 +708,9 @@ __global__ __launch_bounds__(64) void spmm_reduce_ordered_kernel(
         const int64_t ek = e + (int64_t)k * kStep;
         const rows_t ak = a[k];
         const v2d pk[4] = {p[k][0], p[k][1], p[k][2], p[k][3]};
+        const vals_t vk = v[VALUED ? k : 0];
         fetch(k, ek + (int64_t)DEPTH * kStep);
-        if (ek + EPL <= e1) add8(ak, pk);
+        if (ek + EPL <= e1) add8(ak, pk, vk);
       }
     }
   }
@@ -744,13 +777,18 @@ static void ensure_two_byte_ids(BinnedCsr &N, hipStream_t s)
   N.lrow = p;       // (behind the synchronize: a later product on another stream finds the ids complete)
 }
 
-// the sixteen-wave pass 2 for the panels p0 .. p1; bit 8 of bin_flags (A/B runs): product loads plain instead of non-temporal
+// the sixteen-wave pass 2 for the panels p0 .. p1; bit 8 of bin_flags (A/B runs): product AND value loads plain instead of
+// non-temporal.  A copy with values multiplies here (N.vals, pass-2 order).
 static void launch_reduce(const BinnedCsr &N, double *out, int os, int p0, int p1, int flags, hipStream_t s)
 {
-#define FS_REDUCE(NT, RM, L8)                                                                                               \
-  hipLaunchKernelGGL((spmv_reduce_kernel<NT, RM, L8>), dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row, N.lrow, \
-                     N.prod, out, os, p0, N.lrow8, N.gbase)
-#define FS_REDUCE2(RM, L8) do { if (flags & 256) FS_REDUCE(false, RM, L8); else FS_REDUCE(true, RM, L8); } while (0)
+#define FS_REDUCE(V, NT, RM, L8)                                                                                                \
+  hipLaunchKernelGGL((spmv_reduce_kernel<V, NT, RM, L8>), dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row, N.lrow, \
+                     N.vals, N.prod, out, os, p0, N.lrow8, N.gbase)
+#define FS_REDUCE2(RM, L8)                                                                       \
+  do {                                                                                           \
+    if (N.vals) { if (flags & 256) FS_REDUCE(true, false, RM, L8); else FS_REDUCE(true, true, RM, L8); }   \
+    else        { if (flags & 256) FS_REDUCE(false, false, RM, L8); else FS_REDUCE(false, true, RM, L8); } \
+  } while (0)
   if (N.bcols == kBinColsBig) FS_REDUCE2(kBinRowsBig, false);
   else if (N.lrow8)           FS_REDUCE2(kBinRowsMax, true);       // one byte per row id (BinnedCsr::lrow8)
   else                        FS_REDUCE2(kBinRowsMax, false);
@@ -774,24 +812,21 @@ int launch_spmv_binned(const DeviceCsr &A, double *y, const double *x, hipStream
     // loads in pass 1 0.98 / 0.73; plain stores 1.01 / 0.75.  (Bit 2, pass-2 loads non-temporal, went with the pass 2
     // whose lanes read 64 consecutive bytes: 1.09 / 0.84 there; on the line-wise pass 2 they are the default.)
     const int flags = options().bin_flags;
-#define FS_EXPAND4(V, U)                                                                                          \
-  do {                                                                                                            \
-    if (flags & 16) { if (flags & 8) FS_EXPAND(V, U, true, false);  else FS_EXPAND(V, U, true, true); }           \
-    else            { if (flags & 8) FS_EXPAND(V, U, false, false); else FS_EXPAND(V, U, false, true); }          \
+    // Pass 1 is the same kernel with and without values: it writes x[col], the values are multiplied in by pass 2.
+#define FS_EXPAND4(U)                                                                                       \
+  do {                                                                                                      \
+    if (flags & 16) { if (flags & 8) FS_EXPAND(U, true, false);  else FS_EXPAND(U, true, true); }           \
+    else            { if (flags & 8) FS_EXPAND(U, false, false); else FS_EXPAND(U, false, true); }          \
   } while (0)
-#define FS_EXPAND(V, U, NL, NS)                                                                                    \
-  hipLaunchKernelGGL((spmv_expand_kernel<V, U, NL, NS>), dim3(nwg1), dim3(kBinBlock), 0, s, A.ncol, N.B, N.band_ptr, \
-                     N.lcol, N.vals, N.gdst, x, xs, N.prod, 0u, (unsigned)(N.n >> kBinGroupLog))
-    if (N.bcols == kBinColsBig) {                // the large-band copy: default switches only
-      if (A.has_vals())
-        hipLaunchKernelGGL((spmv_expand_kernel<true, 4, false, true, kBinColsBig>), dim3(nwg1), dim3(kBinBlock), 0, s, A.ncol, N.B,
-                           N.band_ptr, N.lcol, N.vals, N.gdst, x, xs, N.prod, 0u, (unsigned)(N.n >> kBinGroupLog));
-      else
-        hipLaunchKernelGGL((spmv_expand_kernel<false, 4, false, true, kBinColsBig>), dim3(nwg1), dim3(kBinBlock), 0, s, A.ncol, N.B,
-                           N.band_ptr, N.lcol, N.vals, N.gdst, x, xs, N.prod, 0u, (unsigned)(N.n >> kBinGroupLog));
-    } else
-    if (A.has_vals()) { if ((flags & 3) == 1) FS_EXPAND4(true, 8); else if ((flags & 3) == 2) FS_EXPAND4(true, 2); else FS_EXPAND4(true, 4); }
-    else        { if ((flags & 3) == 1) FS_EXPAND4(false, 8); else if ((flags & 3) == 2) FS_EXPAND4(false, 2); else FS_EXPAND4(false, 4); }
+#define FS_EXPAND(U, NL, NS)                                                                                      \
+  hipLaunchKernelGGL((spmv_expand_kernel<U, NL, NS>), dim3(nwg1), dim3(kBinBlock), 0, s, A.ncol, N.B, N.band_ptr, \
+                     N.lcol, N.gdst, x, xs, N.prod, 0u, (unsigned)(N.n >> kBinGroupLog))
+    if (N.bcols == kBinColsBig)                  // the large-band copy: default switches only
+      hipLaunchKernelGGL((spmv_expand_kernel<4, false, true, kBinColsBig>), dim3(nwg1), dim3(kBinBlock), 0, s, A.ncol, N.B,
+                         N.band_ptr, N.lcol, N.gdst, x, xs, N.prod, 0u, (unsigned)(N.n >> kBinGroupLog));
+    else if ((flags & 3) == 1) FS_EXPAND4(8);
+    else if ((flags & 3) == 2) FS_EXPAND4(2);
+    else                       FS_EXPAND4(4);
 #undef FS_EXPAND4
 #undef FS_EXPAND
     FS_HIP(hipGetLastError());
@@ -802,17 +837,21 @@ int launch_spmv_binned(const DeviceCsr &A, double *y, const double *x, hipStream
     // "reproducible" (or bit 5 of bin_flags): one wave per panel, additions in stream order, bit-identical run to run
     const bool ordered = reproducible_now() || (options().bin_flags & 32);
     if (ordered && N.lrow8 && !N.lrow) ensure_two_byte_ids(*A.binned, s);
-    if (N.bcols == kBinColsBig && ordered)
-      hipLaunchKernelGGL((spmv_reduce_ordered_kernel<false, kBinRowsBig, FS_ORDERED_DEPTH>), dim3(p1 - p0), dim3(64), 0, s, N.bin_ptr,
-                         N.panel_row, N.lrow, N.prod, out, os, p0);
-    else if (ordered && N.lrow8 && !N.lrow)
-      hipLaunchKernelGGL((spmv_reduce_ordered_kernel<false, kBinRowsMax, FS_ORDERED_DEPTH, true>), dim3(p1 - p0), dim3(64), 0, s, N.bin_ptr,
-                         N.panel_row, N.lrow, N.prod, out, os, p0, N.lrow8, N.gbase);
-    else if (ordered)
-      hipLaunchKernelGGL((spmv_reduce_ordered_kernel<false, kBinRowsMax, FS_ORDERED_DEPTH>), dim3(p1 - p0), dim3(64), 0, s, N.bin_ptr,
-                         N.panel_row, N.lrow, N.prod, out, os, p0);
+#define FS_ORDERED(RM, L8)                                                                                                     \
+  do {                                                                                                                         \
+    if (N.vals)                                                                                                                \
+      hipLaunchKernelGGL((spmv_reduce_ordered_kernel<true, false, RM, FS_ORDERED_DEPTH_VALUED, L8>), dim3(p1 - p0), dim3(64), 0, s, \
+                         N.bin_ptr, N.panel_row, N.lrow, N.vals, N.prod, out, os, p0, N.lrow8, N.gbase);                       \
+    else                                                                                                                       \
+      hipLaunchKernelGGL((spmv_reduce_ordered_kernel<false, false, RM, FS_ORDERED_DEPTH, L8>), dim3(p1 - p0), dim3(64), 0, s,  \
+                         N.bin_ptr, N.panel_row, N.lrow, N.vals, N.prod, out, os, p0, N.lrow8, N.gbase);                       \
+  } while (0)
+    if (N.bcols == kBinColsBig && ordered)  FS_ORDERED(kBinRowsBig, false);
+    else if (ordered && N.lrow8 && !N.lrow) FS_ORDERED(kBinRowsMax, true);
+    else if (ordered)                       FS_ORDERED(kBinRowsMax, false);
     else
       launch_reduce(N, out, os, p0, p1, options().bin_flags, s);
+#undef FS_ORDERED
     FS_HIP(hipGetLastError());
   }
   if (N.split && row1 > row0) {
@@ -832,11 +871,11 @@ int launch_expand_groups(const DeviceCsr &A, const double *x, unsigned g0, unsig
 {
   const BinnedCsr &N = *A.binned;
   if (g1 <= g0 || wgs <= 0) return FS_OK;
-#define FS_XH(V, BC)                                                                                                    \
-  hipLaunchKernelGGL((spmv_expand_kernel<V, 4, false, true, BC>), dim3(wgs), dim3(kBinBlock), 0, s, A.ncol, N.B, N.band_ptr, \
-                     N.lcol, N.vals, N.gdst, x, 1, N.prod, g0, g1)
-  if (N.bcols == kBinColsBig) { if (A.has_vals()) FS_XH(true, kBinColsBig); else FS_XH(false, kBinColsBig); }
-  else                        { if (A.has_vals()) FS_XH(true, kBinCols); else FS_XH(false, kBinCols); }
+#define FS_XH(BC)                                                                                                         \
+  hipLaunchKernelGGL((spmv_expand_kernel<4, false, true, BC>), dim3(wgs), dim3(kBinBlock), 0, s, A.ncol, N.B, N.band_ptr, \
+                     N.lcol, N.gdst, x, 1, N.prod, g0, g1)
+  if (N.bcols == kBinColsBig) FS_XH(kBinColsBig);
+  else                        FS_XH(kBinCols);
 #undef FS_XH
   FS_HIP(hipGetLastError());
   return FS_OK;
@@ -861,25 +900,28 @@ int launch_spmm_binned(const DeviceCsr &A, const BinnedCsr &N, double *Y, const 
   const int os = N.split ? K : ys;
   if (p1 < 0) { p0 = 0; p1 = N.P; row0 = 0; row1 = A.nrow; }
   const int nwg1 = (p0 != 0) ? 0 : ((options().bin_wgs > 0 && options().bin_wgs < N.nwg1) ? options().bin_wgs : N.nwg1);
-#define FS_XP(V, KK)                                                                                                  \
-  hipLaunchKernelGGL((spmm_expand_kernel<V, KK, 4>), dim3(nwg1), dim3(kBinBlock), 0, s, A.ncol, N.B, N.band_ptr, N.lcol, \
-                     N.vals, N.gdst, X, xs, N.prod)
+#define FS_XP(KK)                                                                                                  \
+  hipLaunchKernelGGL((spmm_expand_kernel<KK, 4>), dim3(nwg1), dim3(kBinBlock), 0, s, A.ncol, N.B, N.band_ptr, N.lcol, \
+                     N.gdst, X, xs, N.prod)
   if (nwg1 > 0) {
-    if (K == 2) { if (A.has_vals()) FS_XP(true, 2); else FS_XP(false, 2); }
-    else        { if (A.has_vals()) FS_XP(true, 4); else FS_XP(false, 4); }
+    if (K == 2) FS_XP(2); else FS_XP(4);
     FS_HIP(hipGetLastError());
   }
 #undef FS_XP
   if (p1 > p0) {
     const bool ordered = reproducible_now() || (options().bin_flags & 32);   // one wave per panel, stream order
-    if (K == 2 && ordered)
-      hipLaunchKernelGGL((spmm_reduce_ordered_kernel<2, FS_ORDERED_DEPTH>), dim3(p1 - p0), dim3(64), 0, s, N.bin_ptr, N.panel_row, N.lrow, N.prod, out, os, p0);
-    else if (ordered)
-      hipLaunchKernelGGL((spmm_reduce_ordered_kernel<4, FS_ORDERED_DEPTH>), dim3(p1 - p0), dim3(64), 0, s, N.bin_ptr, N.panel_row, N.lrow, N.prod, out, os, p0);
-    else if (K == 2)
-      hipLaunchKernelGGL(spmm_reduce_kernel<2>, dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row, N.lrow, N.prod, out, os, p0);
-    else
-      hipLaunchKernelGGL(spmm_reduce_kernel<4>, dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row, N.lrow, N.prod, out, os, p0);
+#define FS_RP(V, KK)                                                                                                            \
+  do {                                                                                                                          \
+    if (ordered)                                                                                                                \
+      hipLaunchKernelGGL((spmm_reduce_ordered_kernel<V, KK, (V && KK == 2) ? 12 : FS_ORDERED_DEPTH>), dim3(p1 - p0), dim3(64), 0, s, N.bin_ptr, \
+                         N.panel_row, N.lrow, N.vals, N.prod, out, os, p0);                                                     \
+    else                                                                                                                        \
+      hipLaunchKernelGGL((spmm_reduce_kernel<V, KK>), dim3(p1 - p0), dim3(kBinBlock), 0, s, N.bin_ptr, N.panel_row, N.lrow,     \
+                         N.vals, N.prod, out, os, p0);                                                                          \
+  } while (0)
+    if (K == 2) { if (N.vals) FS_RP(true, 2); else FS_RP(false, 2); }
+    else        { if (N.vals) FS_RP(true, 4); else FS_RP(false, 4); }
+#undef FS_RP
     FS_HIP(hipGetLastError());
   }
   if (N.split && row1 > row0) {

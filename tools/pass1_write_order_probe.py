@@ -2,7 +2,9 @@
 """Is pass 1 of the two-pass pair held back by WHERE its products go?  Its stores are 3.4-KB runs (one (band, panel) cell) scattered
 over 610 panel regions; this probe times pass 1 alone (fs_debug_two_pass_run) as built and again after overwriting gdst with the
 identity, so that the same kernel stores the same bytes sequentially (the products then sit in pass-1 order: wrong for pass 2, a
-TIMING experiment).  Valued and pattern-only config 2.     python tools/pass1_write_order_probe.py"""
+TIMING experiment).  Valued and pattern-only config 2 -- since the values moved to pass 2 (profiles/values_in_pass2_ab.json) pass 1
+is the same value-free kernel on both and only pass2_ms differs; the numbers of profiles/r05_pass1_write_order_and_k2_ab.txt are
+from the pass 1 that still read them.     python tools/pass1_write_order_probe.py"""
 import ctypes as C
 import os
 import sys
