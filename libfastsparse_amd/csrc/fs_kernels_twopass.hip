@@ -262,10 +262,14 @@ __global__ __launch_bounds__(kBinBlock) void spmv_reduce_kernel(
   reduce_panel<VALUED, NTLD, L8>(ytile, pbase + blockIdx.x, bin_ptr, panel_row, lrow, vals, prod, y, ys, lrow8, gbase);
 }
 
-// pass 2 with a FIXED order of additions: ONE wave per panel walks the panel's products in stream order, 512 entries per step
-// (eight per lane, as above).  A wave's LDS instructions execute in program order, so every y slot receives its addends in the
-// order of the stream (band by band, inside a band in CSR order; lanes of one instruction that hit the same slot are
-// serialised by the LDS in a fixed order): the result is bit-identical run to run, which the sixteen-wave kernel above -- whose
+// pass 2 with a FIXED order of additions: ONE wave per panel walks the panel's products, 512 entries per step, lane l the eight
+// at 8 l.  A wave's LDS instructions execute in program order and add i of FS_ADD8 takes entry 8 l + i of EVERY lane, so with p
+// the slot counted from the panel's first one (the cells for ascending band, each in CSR order, padding at its end) a y slot
+// receives its addends by ascending step p / 512, then entry-in-lane p % 8, then lane (p % 512) / 8 -- NOT in the order of the
+// stream: a row at slots 5 .. 9 is added 8, 9, 5, 6, 7.  Lanes of one instruction that hit the same slot are added by the LDS in
+// ascending lane order (measured on gfx950; tests/test_gpu_fixed_order.py::test_model_on_l).  tests/_order_model.py restates the
+// order and tests/test_gpu_fixed_order.py holds this kernel to it bit for bit: moving an add changes bits of every solve.
+// The result is bit-identical run to run, which the sixteen-wave kernel above -- whose
 // waves add into the same slots concurrently -- is not.  One wave can do it because the pass is a stream: DEPTH steps of loads
 // (80 bytes per lane each) stay in flight in registers, and eight ds_add_f64 per 512 entries are far below what one wave may
 // issue.
@@ -656,7 +660,8 @@ __global__ __launch_bounds__(kBinBlock) void spmm_reduce_kernel(
   for (int i = t; i < nr * K; i += kBinBlock) Y[(int64_t)(r0 + i / K) * ys + (i % K)] = ytile[i];
 }
 
-// the same pass with a fixed order of additions: one wave per panel, stream order (see spmv_reduce_ordered_kernel)
+// the same pass with a fixed order of additions: one wave per panel; by step of 64 EPL entries, then entry-in-lane q, then lane
+// (see spmv_reduce_ordered_kernel; tests/_order_model.py two_pass_ordered_k)
 template <bool VALUED, int K, int DEPTH>
 __global__ __launch_bounds__(64) void spmm_reduce_ordered_kernel(
     const unsigned *__restrict__ bin_ptr_all, const int *__restrict__ panel_row_all, const uint16_t *__restrict__ lrow,
@@ -834,7 +839,7 @@ int launch_spmv_binned(const DeviceCsr &A, double *y, const double *x, hipStream
   if (N.lr && p0 == 0)          // behind pass 1, in front of pass 2: HBM-bound like both
     if (int rc = launch_longrows(A, *N.lr, x, xs, s)) return rc;
   if (p1 > p0) {
-    // "reproducible" (or bit 5 of bin_flags): one wave per panel, additions in stream order, bit-identical run to run
+    // "reproducible" (or bit 5 of bin_flags): one wave per panel, additions in a fixed order (see spmv_reduce_ordered_kernel), bit-identical run to run
     const bool ordered = reproducible_now() || (options().bin_flags & 32);
     if (ordered && N.lrow8 && !N.lrow) ensure_two_byte_ids(*A.binned, s);
 #define FS_ORDERED(RM, L8)                                                                                                     \
@@ -909,7 +914,7 @@ int launch_spmm_binned(const DeviceCsr &A, const BinnedCsr &N, double *Y, const 
   }
 #undef FS_XP
   if (p1 > p0) {
-    const bool ordered = reproducible_now() || (options().bin_flags & 32);   // one wave per panel, stream order
+    const bool ordered = reproducible_now() || (options().bin_flags & 32);   // one wave per panel, fixed order
 #define FS_RP(V, KK)                                                                                                            \
   do {                                                                                                                          \
     if (ordered)                                                                                                                \
