@@ -88,7 +88,7 @@ int  fs_set_device(int device);
  * through LDS with coalesced accesses; both give the same bits.
  * "pcgn_compact" (default 0; FS_PCGN_COMPACT): fs_pcgn and fs_pcgn_lambdas, 1 = the live columns of a solve move into a narrower
  * panel whenever they fit the next of the widths 16, 8, 4, 2, 1, and the products run at that width (see fs_pcgn, "Narrowing");
- * 0 = every iteration runs on all k columns.  fs_dist_pcgn and fs_dist_pcgn_lambdas do not read it.
+ * 0 = every iteration runs on all k columns.  fs_dist_pcgn, fs_dist_pcgn_lambdas and fs_mscgn do not read it.
  * "dist_cg_scheme" (FS_DIST_CG_SCHEME): fs_dist_cg, fs_dist_pcg and fs_dist_mscg, 0 every device keeps whole vectors, 1 every device keeps its slice (see there). */
 int  fs_set_option(const char *name, int value);
 int  fs_get_option(const char *name);
@@ -215,7 +215,7 @@ int fs_spmv_t_host(fs_matrix_t A, double *y_host, const double *x_host);
 /* ---- consumers of the path, device resident (cg.h of the reference) -------------------- */
 /* (A'A + lambda I) x = b by conjugate gradients; A and the handle of its transpose as the reference passes
  * them (bsbm_cg cg.h:25); x, b: F = ncol(A) doubles in HBM; stops at ||r|| <= tol ||b|| or after F iterations.
- * Every solver below (fs_cg, fs_cg2, fs_pcg, fs_mscg, fs_pcgn, fs_pcgn_lambdas) looks at its two products before it writes anything: where one of
+ * Every solver below (fs_cg, fs_cg2, fs_pcg, fs_mscg, fs_pcgn, fs_pcgn_lambdas, fs_mscgn) looks at its two products before it writes anything: where one of
  * them would read plain CSR arrays that fs_matrix_release_csr gave back ("strict_order", spmv_kernel 1 / 2 / 3, the row kernel of
  * a k-column product) the solve returns FS_ERR_RELEASED with x untouched -- also a solve that would have needed no product. */
 int fs_cg(fs_matrix_t A, fs_matrix_t At, double *x, const double *b, double lambda, double tol, int *out_iter,
@@ -406,6 +406,62 @@ int fs_pcgn(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k, do
 int fs_pcgn_lambdas(fs_matrix_t A, fs_matrix_t At, double *X, const double *B, int k,
                     const double *lambda /* k doubles on the HOST */, const fs_pcg_params *prm,
                     fs_pcg_info *info /* k entries or NULL */, fs_stream_t stream);
+
+/* (A'A + lambda[i] I) x_ij = b_j for i < m, j < k: a ladder of m lambdas, shared by all targets, for k right-hand sides in one solve
+ * -- targets x rungs on data that need no preconditioner -- on ONE pair of k-column products per iteration, where fs_pcgn_lambdas
+ * runs k m columns through the products.  Not block CG: column j is fs_mscg on B[:, j], line by line, with scalars of its own; the
+ * columns share only the products.  fs_mscg's text is the single statement of the shift recurrences; this says what differs.
+ * B: a row-major F x k panel in HBM, F = ncol(A), with the layout and alignment rules of fs_pcgn.  X: m such panels, the panel of
+ * lambda[i] at X + i * ldx, ldx >= F * k; doubles in the gaps are never touched.  A panel is accessed 16 bytes at a time only where
+ * k is even and that panel's address is 16-byte aligned; the results do not depend on this.  k in 1..FS_PCGN_MAX_RHS, m in
+ * 1..FS_MSCG_MAX_SHIFTS; lambda: m doubles on the HOST, any order, duplicates allowed; tol, max_iter as in fs_mscg; info: m * k
+ * entries, info[i * k + j], or NULL.  Cold start only, no preconditioner, for fs_mscg's reasons.  Synchronous like fs_mscg.  Option
+ * "pcgn_compact" is not read.
+ * Arithmetic.  The host forms base and the sigma_i once, for every column.  Per column j: bb_j, stop_j, rsq_j, alpha_j, beta_j,
+ * aprev_j, bprev_j and the iteration count; per pair (i, j): z, zp, zn, ratio, a, b, rn, live, converged, count -- fs_mscg's per-shift
+ * scalars.  `red_j` is fs_pcgn's: fs_cg's two-stage tree over column j's F terms.
+ *   start: X_i = 0 for all i, R = P = B, P_i = B for every shift with sigma_i != 0;  bb_j = red_j(b b), fs_mscg's start per column.
+ *          sqrt(bb_j) <= stop_j (b_j = 0; tol >= 1): column j is frozen from the start, all its pairs converged with count 0 and
+ *          x_ij = +0.0.  Every column frozen: done, no product is enqueued
+ *   iteration n = 0, 1, ... while n < cap (max_iter <= 0: F) and a column is live, over live columns and live pairs only:
+ *     T = A P, Q = A' T: one pair of k-column products (fs_spmm; k = 1: fs_spmv)
+ *     q_j = q_j + base p_j, alpha_j = rsq_j / red_j(q p)                                 -- fs_pcgn's kernels at lambda = base
+ *     S1 of fs_mscg for every live pair, with column j's alpha, aprev, bprev
+ *     r_j = r_j - alpha_j q_j, rr_j = red_j(r r)                                         -- fs_pcgn's kernel, X left alone
+ *     x_ij = x_ij + a_ij P_ij for every live pair (a pair with sigma_i = 0 reads column j of P)
+ *     S2 of fs_mscg per column, `done` being sqrt(rr_j) <= stop_j: a column that is done freezes, and with it every pair it still
+ *       has; so does a column that has no live pair left (only when a NaN froze them all: fs_mscg's freeze rule
+ *       !(rn > stop) or fabs(zn) < 2^-500 or done holds per pair, and a NaN fails rn > stop)
+ *     direction: p_j = r_j + beta_j p_j for the live columns;  P_ij = z_ij r_j + b_ij P_ij for the live pairs (two multiplies, one
+ *       add; z the new one)
+ *   info[i * k + j] = { count_ij, converged_ij, rn_ij, sqrt(bb_j) };  a pair still live at the cap: converged 0, count = cap
+ * So column j of panel i is fs_mscg's x_i on B[:, j] wherever the k-column product has the single-vector product's bits: bit for
+ * bit under "strict_order", and for k = 1 in every mode.  With m = 1 the solve is fs_pcgn with FS_PRECOND_NONE from a cold start at
+ * lambda[0], bit for bit, infos included, in every mode in which fs_pcgn repeats its own bits.  Pairs of the smallest lambda and its
+ * duplicates keep z = 1 exactly and own no direction panel.
+ * Freezing: no kernel changes a frozen pair's x_ij or P_ij again; a frozen column's columns of R and P keep their bits, and its P
+ * rides through the products as in fs_pcgn.  A shift none of whose pairs is live costs no traffic: its panels X_i and P_i are not
+ * read.  In a row-major panel a frozen pair shares its cache lines with live ones, so it saves stores and arithmetic, not lines.  A
+ * column whose numbers go NaN changes no bit of another column (the products and the sums are per column); its pairs freeze
+ * unconverged by fs_mscg's rule, at the count fs_mscg reports for that column.
+ * The scalars live on the device; the host learns of `done` -- no column live -- one iteration behind, as in fs_cg.  Products add in
+ * a fixed order unless option "cg_fixed_order" is 0; option "pcgn_kernel" picks the form of the two kernels that take sums.
+ * Traffic: the kernels that take sums move 6 k F doubles per iteration whatever is frozen (q + base p: 3, r - alpha q: 3).  The
+ * pair kernels stream whole panels flat: per shift that still has a live pair 3 k F for x (P_i or P, x_i in, x_i out) and, with
+ * sigma_i != 0, 2 k F for P_i; the direction pass moves 3 k F for P itself and reads R once more per further group of four shifts.
+ * With one sigma = 0 shift and L others live that is (12 + 5 L) k F, fs_mscg's formula per column, plus k F per further group of four
+ * and 3 k F per duplicate of the smallest lambda.  k = 8, L = 7, F = 10 M: 30 GB per iteration.
+ * Work space per solve: 3 k F + k N doubles (R, P, Q, T), one F x k direction panel per shift with sigma != 0, 2048 k doubles for
+ * the partial sums and 9344 for the scalars; all of it is allocated before the first store to X.  Mind the size: k = 8, m = 16,
+ * F = 10 M is 10 GB of X and 9.6 GB of directions.
+ * One-time work: for k >= 2 fs_matrix_prepare(A, k, 0) and fs_matrix_prepare(At, k, 0) run first, then the look at the two products
+ * described above fs_cg.  FS_ERR_ARG, raised before anything is written to X: a NULL A, At, X, B or lambda; At not of the transposed
+ * shape; k outside 1..FS_PCGN_MAX_RHS; m outside 1..FS_MSCG_MAX_SHIFTS; ldx < F * k; tol negative or NaN; a lambda that is NaN or
+ * infinite.  FS_ERR_RELEASED, with X untouched: under "strict_order" after fs_matrix_release_csr; for a k never prepared before the
+ * release.  A failed allocation of the work space returns FS_ERR_HIP with X untouched.  A product's own error is passed through. */
+int fs_mscgn(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double *B, int k, int m,
+             const double *lambda /* m doubles on the HOST */, double tol, int max_iter,
+             fs_pcg_info *info /* m * k entries, info[i * k + j], or NULL */, fs_stream_t stream);
 
 /* ---- column-blocked binary CSR (cbcsr.h) -------------------------------------------- */
 fs_cbcsr_t fs_cbcsr_create(int nrow, int ncol, int nblocks, int colblocksize, const int *row_ptr,

@@ -26,7 +26,7 @@ DEVICE_API = [
     "fs_matrix_release_csr", "fs_matrix_restore_csr", "fs_matrix_release_prepared",
     "fs_matrix_prepare", "fs_matrix_spmm_plan", "fs_matrix_device_bytes", "fs_spmv_part", "fs_spmv_part_rows", "fs_spmm_part", "fs_spmm_part_rows", "fs_copy_segments",
     "fs_matrix_nrow", "fs_matrix_ncol", "fs_matrix_nnz", "fs_matrix_algorithmic_bytes", "fs_matrix_download",
-    "fs_spmv", "fs_spmv_t", "fs_spmv_host", "fs_spmv_t_host", "fs_spmm", "fs_spmm_t", "fs_ata_mul", "fs_cg", "fs_cg2", "fs_axpy", "fs_gram_diag", "fs_pcg", "fs_mscg", "fs_pcgn", "fs_pcgn_lambdas",
+    "fs_spmv", "fs_spmv_t", "fs_spmv_host", "fs_spmv_t_host", "fs_spmm", "fs_spmm_t", "fs_ata_mul", "fs_cg", "fs_cg2", "fs_axpy", "fs_gram_diag", "fs_pcg", "fs_mscg", "fs_pcgn", "fs_pcgn_lambdas", "fs_mscgn",
     "fs_cbcsr_create", "fs_cbcsr_destroy", "fs_cbcsr_spmv", "fs_invalidate", "fs_release_all", "fs_cache_entries",
     "fs_synth_uniform", "fs_synth_powerlaw_lengths", "fs_synth_fill", "fs_bucket_coo", "fs_device_build_wanted",
     "fs_dist_create", "fs_dist_destroy", "fs_dist_ndev", "fs_dist_uses_rccl", "fs_dist_csr_create", "fs_dist_matrix_destroy",
@@ -149,6 +149,7 @@ def lib():
     L.fs_pcgn.argtypes = [vp, vp, vp, vp, C.c_int, C.c_double, C.POINTER(PcgParams), C.POINTER(PcgInfo), vp]
     L.fs_pcgn_lambdas.argtypes = [vp, vp, vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(PcgParams), C.POINTER(PcgInfo), vp]
     L.fs_mscg.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(PcgInfo), vp]
+    L.fs_mscgn.argtypes = [vp, vp, vp, C.c_int64, vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(PcgInfo), vp]
     L.fs_cbcsr_create.restype = vp
     L.fs_cbcsr_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]
     L.fs_cbcsr_destroy.argtypes = [vp]
@@ -422,6 +423,23 @@ def mscg(A, At, X, b, lams, tol, max_iter=0, stream=None):
     check(lib().fs_mscg(A.h, At.h, X.data_ptr(), int(ldx), _ptr(b), m, (C.c_double * max(m, 1))(*lams), float(tol), int(max_iter), infos,
                         stream), "fs_mscg")
     return list(infos)[:m]
+
+
+def mscgn(A, At, X, B, lams, tol, max_iter=0, stream=None):
+    """(A'A + lams[i] I) x_ij = b_j for every lambda i and every column j of B in one solve (fs_mscgn): mscg on every column, on one
+    pair of k-column products per iteration however many lambdas.  B: contiguous device tensor (F, k), k <= FS_PCGN_MAX_RHS; X:
+    device tensor (m, F, k) whose panels are contiguous (they may be padded: ldx = X.stride(0)); lams: m <= FS_MSCG_MAX_SHIFTS host
+    values.  Returns the m x k PcgInfo as a list of lists, infos[i][j]."""
+    lams = [float(v) for v in lams]
+    m = len(lams)
+    if B.dim() != 2 or not B.is_contiguous() or X.dim() != 3 or tuple(X.shape) != (m,) + tuple(B.shape) or not X[0].is_contiguous():
+        raise ValueError("mscgn: B must be a contiguous (F, k) tensor and X (len(lams), F, k) with contiguous panels")
+    k = int(B.shape[1])
+    ldx = X.stride(0) if m > 1 else max(X.stride(0), B.numel())
+    infos = (PcgInfo * max(m * k, 1))()
+    check(lib().fs_mscgn(A.h, At.h, X.data_ptr(), int(ldx), B.data_ptr(), k, m, (C.c_double * max(m, 1))(*lams), float(tol),
+                         int(max_iter), infos, stream), "fs_mscgn")
+    return [list(infos[i * k:(i + 1) * k]) for i in range(m)]
 
 
 def pcgn(A, At, X, B, lam, tol, max_iter=0, precond=FS_PRECOND_JACOBI, warm_start=False, diag=None, stream=None):

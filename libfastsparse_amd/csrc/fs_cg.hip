@@ -419,24 +419,25 @@ __device__ __forceinline__ void mscg_list(int m, double *__restrict__ st, double
   if (nb + nl == 0) st[kStDone] = 1.0;     // nothing left to iterate for (besides convergence: every shift frozen by a NaN)
 }
 
-// start: b.b, stop, the scalars of the base system and of every shift (one thread per shift)
-__global__ __launch_bounds__(kRedThreads) void mscg_start_kernel(const double *__restrict__ part, int nblocks, double *__restrict__ red,
-                                                                double *__restrict__ st, double *__restrict__ ms, double tol, int m,
-                                                                MscgSigma sg)
+// The three scalar steps as the work of one thread per shift (`lane`) on one right-hand side's st[] and ms[]: fs_mscg's kernels run
+// them with lane = threadIdx.x, fs_mscgn's run one per column side by side.  Every thread of the workgroup calls a step (it holds
+// barriers); `active` false: this thread's right-hand side takes no part (fs_mscgn: a frozen column, a lane past the last column).
+
+// start: stop, the scalars of the base system and of every shift
+__device__ __forceinline__ void mscg_start_step(double bb, double tol, double *__restrict__ st, double *__restrict__ ms, int m,
+                                                const MscgSigma &sg, int lane, bool active)
 {
-  finish_sum<1>(part, nblocks, red);
-  const double bb = red[0];
   const double stop = tol * sqrt(bb);
   const bool done = sqrt(bb) <= stop;
-  if ((int)threadIdx.x < m) {
-    double *e = ms + threadIdx.x * kMsStride;
-    e[kMsSigma] = sg.v[threadIdx.x];
+  if (active && lane < m) {
+    double *e = ms + lane * kMsStride;
+    e[kMsSigma] = sg.v[lane];
     e[kMsZ] = 1.0; e[kMsZp] = 1.0; e[kMsZn] = 1.0; e[kMsRatio] = 1.0; e[kMsA] = 0.0; e[kMsB] = 0.0;
     e[kMsRn] = sqrt(bb); e[kMsLive] = done ? 0.0 : 1.0; e[kMsConverged] = done ? 1.0 : 0.0; e[kMsCount] = 0.0;
     e[kMsList] = -1.0; e[kMsPslot] = -1.0;
   }
   __syncthreads();
-  if (threadIdx.x != 0) return;
+  if (!active || lane != 0) return;
   st[kStBb] = bb; st[kStRr] = bb; st[kStRsq] = bb; st[kStStop] = stop; st[kStIter] = 0.0; st[kStDone] = done ? 1.0 : 0.0;
   st[kStAprev] = 1.0; st[kStBprev] = 0.0;
   int slots = 0;
@@ -446,16 +447,15 @@ __global__ __launch_bounds__(kRedThreads) void mscg_start_kernel(const double *_
   else mscg_list(m, st, ms);
 }
 
-// S1: finishes q.p, alpha = rsq / q.p, then per live shift (one thread each) zn, ratio and the step a_i
-__global__ __launch_bounds__(kRedThreads) void mscg_s1_kernel(const double *__restrict__ part, int nblocks, double *__restrict__ red,
-                                                             double *__restrict__ st, double *__restrict__ ms, int m)
+// S1: alpha = rsq / q.p (red[0]), then per live shift zn, ratio and the step a_i
+__device__ __forceinline__ void mscg_s1_step(const double *__restrict__ red, double *__restrict__ st, double *__restrict__ ms, int m,
+                                             int lane, bool active)
 {
-  if (st[kStDone] != 0.0) return;
-  finish_sum<1>(part, nblocks, red);
   const double alpha = st[kStRsq] / red[0];
-  if (threadIdx.x == 0) st[kStAlpha] = alpha;
-  if ((int)threadIdx.x >= m) return;
-  double *e = ms + threadIdx.x * kMsStride;
+  if (!active) return;
+  if (lane == 0) st[kStAlpha] = alpha;
+  if (lane >= m) return;
+  double *e = ms + lane * kMsStride;
   if (e[kMsLive] == 0.0) return;
   const double aprev = st[kStAprev], bprev = st[kStBprev], sigma = e[kMsSigma], z = e[kMsZ], zp = e[kMsZp];
   double u = alpha * bprev; u = u * (zp - z);
@@ -465,6 +465,57 @@ __global__ __launch_bounds__(kRedThreads) void mscg_s1_kernel(const double *__re
   double zn = z * zp; zn = zn * aprev; zn = zn / den;
   const double ratio = zn / z;
   e[kMsZn] = zn; e[kMsRatio] = ratio; e[kMsA] = alpha * ratio;
+}
+
+// S2: r.r is red[0]; the base system's convergence test and beta (fs_cg's kStepCgBeta, fs_pcg's r.r kept); per live shift its
+// residual norm, freeze or b_i and the new z; then the list of the shifts that stay live
+__device__ __forceinline__ void mscg_s2_step(const double *__restrict__ red, double *__restrict__ st, double *__restrict__ ms, int m,
+                                             int lane, bool active)
+{
+  const double rr = red[0], rsq = st[kStRsq], stop = st[kStStop], alpha = st[kStAlpha], n = st[kStIter];
+  const double s = sqrt(rr);
+  const bool done = s <= stop;
+  const double beta = rr / rsq;
+  __syncthreads();                         // every thread has read st[] before lane 0 moves it on
+  if (active && lane == 0) {
+    st[kStRr] = rr;
+    if (done) st[kStDone] = 1.0;
+    else { st[kStBeta] = beta; st[kStRsq] = rr; st[kStIter] = n + 1.0; st[kStAprev] = alpha; st[kStBprev] = beta; }
+  }
+  if (active && lane < m) {
+    double *e = ms + lane * kMsStride;
+    if (e[kMsLive] != 0.0) {
+      const double zn = e[kMsZn], ratio = e[kMsRatio];
+      const double rn = fabs(zn) * s;
+      e[kMsRn] = rn;
+      if (!(rn > stop) || fabs(zn) < 0x1p-500 || done) {
+        e[kMsLive] = 0.0; e[kMsConverged] = rn <= stop ? 1.0 : 0.0; e[kMsCount] = n;
+      } else {
+        double bi = ratio * ratio; bi = beta * bi;
+        e[kMsB] = bi; e[kMsZp] = e[kMsZ]; e[kMsZ] = zn; e[kMsCount] = n + 1.0;
+      }
+    }
+  }
+  __syncthreads();
+  if (active && lane == 0 && !done) mscg_list(m, st, ms);
+}
+
+// start: b.b, stop, the scalars of the base system and of every shift (one thread per shift)
+__global__ __launch_bounds__(kRedThreads) void mscg_start_kernel(const double *__restrict__ part, int nblocks, double *__restrict__ red,
+                                                                double *__restrict__ st, double *__restrict__ ms, double tol, int m,
+                                                                MscgSigma sg)
+{
+  finish_sum<1>(part, nblocks, red);
+  mscg_start_step(red[0], tol, st, ms, m, sg, (int)threadIdx.x, true);
+}
+
+// S1: finishes q.p, alpha = rsq / q.p, then per live shift (one thread each) zn, ratio and the step a_i
+__global__ __launch_bounds__(kRedThreads) void mscg_s1_kernel(const double *__restrict__ part, int nblocks, double *__restrict__ red,
+                                                             double *__restrict__ st, double *__restrict__ ms, int m)
+{
+  if (st[kStDone] != 0.0) return;
+  finish_sum<1>(part, nblocks, red);
+  mscg_s1_step(red, st, ms, m, (int)threadIdx.x, true);
 }
 
 // update: r = r - alpha q with the partials of r.r in cg_update_dev_kernel's shape, x_i = x_i + a_i P_i for every live shift, kMscgGroup
@@ -523,39 +574,13 @@ __global__ __launch_bounds__(kRedThreads) void mscg_update_kernel(int n, double 
   block_sum<1>(v, part);
 }
 
-// S2: finishes r.r; the base system's convergence test and beta (fs_cg's kStepCgBeta, fs_pcg's r.r kept); per live shift (one
-// thread each) its residual norm, freeze or b_i and the new z; then the list of the shifts that stay live
+// S2: finishes r.r, then mscg_s2_step
 __global__ __launch_bounds__(kRedThreads) void mscg_s2_kernel(const double *__restrict__ part, int nblocks, double *__restrict__ red,
                                                              double *__restrict__ st, double *__restrict__ ms, int m)
 {
   if (st[kStDone] != 0.0) return;
   finish_sum<1>(part, nblocks, red);
-  const double rr = red[0], rsq = st[kStRsq], stop = st[kStStop], alpha = st[kStAlpha], n = st[kStIter];
-  const double s = sqrt(rr);
-  const bool done = s <= stop;
-  const double beta = rr / rsq;
-  __syncthreads();                         // every thread has read st[] before thread 0 moves it on
-  if (threadIdx.x == 0) {
-    st[kStRr] = rr;
-    if (done) st[kStDone] = 1.0;
-    else { st[kStBeta] = beta; st[kStRsq] = rr; st[kStIter] = n + 1.0; st[kStAprev] = alpha; st[kStBprev] = beta; }
-  }
-  if ((int)threadIdx.x < m) {
-    double *e = ms + threadIdx.x * kMsStride;
-    if (e[kMsLive] != 0.0) {
-      const double zn = e[kMsZn], ratio = e[kMsRatio];
-      const double rn = fabs(zn) * s;
-      e[kMsRn] = rn;
-      if (!(rn > stop) || fabs(zn) < 0x1p-500 || done) {
-        e[kMsLive] = 0.0; e[kMsConverged] = rn <= stop ? 1.0 : 0.0; e[kMsCount] = n;
-      } else {
-        double bi = ratio * ratio; bi = beta * bi;
-        e[kMsB] = bi; e[kMsZp] = e[kMsZ]; e[kMsZ] = zn; e[kMsCount] = n + 1.0;
-      }
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0 && !done) mscg_list(m, st, ms);
+  mscg_s2_step(red, st, ms, m, (int)threadIdx.x, true);
 }
 
 // direction: p = r + beta p, P_i = z_i r + b_i P_i for every live shift with sigma != 0 (z_i the new one), kMscgGroup shifts at a
@@ -839,8 +864,8 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_kernel(int n, int 
 }
 
 // per live column: x += alpha p, r -= alpha q, partial r.r; with a preconditioner z = r dinv and partial r.z in the same pass
-// (pcg_update_kernel / cg_update_dev_kernel)
-template <int KMAX, int VEC, typename... LAM>
+// (pcg_update_kernel / cg_update_dev_kernel).  XUP false: r and its sums only, X is not touched (fs_mscgn: its x_ij have steps of their own)
+template <int KMAX, int VEC, bool XUP, typename... LAM>
 __global__ __launch_bounds__(kRedThreads) void pcgn_update_kernel(int n, int k, double *__restrict__ X, double *__restrict__ R,
                                                                  const double *__restrict__ P, const double *__restrict__ Q,
                                                                  const double *__restrict__ dinv, double *__restrict__ part,
@@ -860,13 +885,13 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_update_kernel(int n, int k, 
       Pair pv[TP + 1] = {}, qv[TP + 1] = {}, xv[TP + 1] = {}, rv[TP + 1] = {};
       pcgn_ld_tile<KMAX, VEC >= 1>(pv, P + row, c0, k);
       pcgn_ld_tile<KMAX, VEC >= 1>(qv, Q + row, c0, k);
-      pcgn_ld_tile<KMAX, VEC == 2>(xv, X + row, c0, k);
+      if (XUP) pcgn_ld_tile<KMAX, VEC == 2>(xv, X + row, c0, k);
       pcgn_ld_tile<KMAX, VEC >= 1>(rv, R + row, c0, k);
       pcgn_tile_pairs<KMAX>(c0, k, live, [&](int h, int c, bool l0, bool l1) {
         const Pair p = pv[h], q = qv[h], x0 = xv[h], r0 = rv[h];
         const Pair x = {x0.a + al[c] * p.a, x0.b + al[c + 1] * p.b};
         const Pair r = {r0.a - al[c] * q.a, r0.b - al[c + 1] * q.b};
-        pn_st<VEC == 2>(X + row + c, x, l0, l1);
+        if (XUP) pn_st<VEC == 2>(X + row + c, x, l0, l1);
         pn_st<VEC >= 1>(R + row + c, r, l0, l1);
         rr[c] += r.a * r.a; rr[c + 1] += r.b * r.b;
         if constexpr (sizeof...(LAM) != 0) {
@@ -1035,8 +1060,8 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_lds_kernel(int n, 
   pcgn_block_sums<KMAX>(k, live, 1, qp, qp, part);
 }
 
-// per live column: x += alpha p, then r -= alpha q with the partials of r.r and, with a preconditioner, of r.z (z = r dinv)
-template <int KMAX, typename... LAM>
+// per live column: x += alpha p (XUP), then r -= alpha q with the partials of r.r and, with a preconditioner, of r.z (z = r dinv)
+template <int KMAX, bool XUP, typename... LAM>
 __global__ __launch_bounds__(kRedThreads) void pcgn_update_lds_kernel(int n, int k, double *__restrict__ X, double *__restrict__ R,
                                                                      const double *__restrict__ P, const double *__restrict__ Q,
                                                                      const double *__restrict__ dinv, double *__restrict__ part,
@@ -1057,19 +1082,21 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_update_lds_kernel(int n, int
   for (int row0 = blk0; row0 < blk0 + kRedThreads && row0 < n; row0 += TR) {                // the workgroup's 256 rows, TR at a time
     const int nr = n - row0 < TR ? n - row0 : TR, ne = nr * k, lt = (int)threadIdx.x - (row0 - blk0);
     const size_t at = (size_t)row0 * k;
-    pl_in<KMAX>(t0, X + at, ne, k);
-    pl_in<KMAX>(t1, P + at, ne, k);
-    __syncthreads();
-    if (lt >= 0 && lt < nr) {                                 // the thread that owns row row0 + lt
-      double *x = t0 + lt * LD;
-      const double *p = t1 + lt * LD;
+    if (XUP) {
+      pl_in<KMAX>(t0, X + at, ne, k);
+      pl_in<KMAX>(t1, P + at, ne, k);
+      __syncthreads();
+      if (lt >= 0 && lt < nr) {                               // the thread that owns row row0 + lt
+        double *x = t0 + lt * LD;
+        const double *p = t1 + lt * LD;
 #pragma unroll
-      for (int c = 0; c < KMAX; ++c)
-        if (c < k && ((live >> c) & 1u) != 0u) x[c] = x[c] + al[c] * p[c];
+        for (int c = 0; c < KMAX; ++c)
+          if (c < k && ((live >> c) & 1u) != 0u) x[c] = x[c] + al[c] * p[c];
+      }
+      __syncthreads();
+      pl_out<KMAX>(X + at, t0, ne, k, live);
+      __syncthreads();
     }
-    __syncthreads();
-    pl_out<KMAX>(X + at, t0, ne, k, live);
-    __syncthreads();
     pl_in<KMAX>(t0, R + at, ne, k);
     pl_in<KMAX>(t1, Q + at, ne, k);
     __syncthreads();
@@ -1376,6 +1403,242 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_remap_kernel(double *st, dou
   st[kStLiveMask] = (double)m;
 }
 
+// ---- fs_mscgn: fs_mscg on every column of a row-major F x k panel B, m lambdas shared by all columns, on ONE pair of k-column
+// products per iteration (include/fastsparse_hip.h says what differs from fs_mscg).  Column j has fs_mscg's scalars to itself:
+// cst[j * kStDoubles ..] in the layout of fs_mscg's st[], ms[j * kMscgStateDoubles ..] in that of its ms[], and the scalar steps
+// ARE fs_mscg's (mscg_start_step, mscg_s1_step, mscg_s2_step), one column per kMscgMaxShifts threads.  The per-column sums are
+// fs_pcgn's: its kernels form q + base p with q.p and r - alpha q with r.r (pcgn_update_kernel without its X), pcgn_fold_kernel
+// finishes them, so st[] carries fs_pcgn's done, iteration count and mask of live columns and cs[] column j's alpha where those
+// kernels read it.  What fs_mscg does per shift runs per PAIR (shift i, column j) here and needs no sum: x_ij += a_ij P_ij and
+// P_ij = z_ij r_j + b_ij P_ij stream the row-major panels flat -- element e of a panel belongs to column e % k, whose coefficient
+// comes from a table in LDS -- fully coalesced, 16 bytes at a time where k is even and the panel is 16-byte aligned.
+// sl[]: what the flat kernels need per SHIFT -- the compacted list of the shifts that still have a live pair (sigma = 0 first, then
+// the others, in the caller's order: kSlNBase + kSlNLive entries), every shift's mask of live columns and its direction slot.
+constexpr int kMscgnColumnsPerPass = kRedThreads / kMscgMaxShifts;
+enum { kSlNBase = 0, kSlNLive = 1, kSlList = 2, kSlMask = kSlList + kMscgMaxShifts, kSlPslot = kSlMask + kMscgMaxShifts, kSlDoubles = 64 };
+static_assert(kSlPslot + kMscgMaxShifts <= kSlDoubles && kSlDoubles == kMscgnListDoubles, "fs_common.h sizes sl[]");
+static_assert(kMscgnColumnsPerPass * kMscgMaxShifts == kRedThreads && kMscgGroup * kPcgnMaxRhs <= kRedThreads, "one thread per pair and per table entry");
+
+// the one-workgroup step behind the k finished sums red[j * ns] (pcgn_fold_kernel's): fs_mscg's scalar step for every live column,
+// one thread per pair, kMscgnColumnsPerPass columns at a time; then (start, S2) the masks and the list of sl[] and fs_pcgn's mask of
+// live columns.  A column is live while its fs_mscg is not done; done: no column is live
+template <MscgStep STEP>
+__global__ __launch_bounds__(kRedThreads) void mscgn_step_kernel(const double *__restrict__ red, double *st, double *cst, double *cs,
+                                                                double *ms, double *sl, int k, int m, double tol, MscgSigma sg)
+{
+  if (STEP != kMscgStart && st[kStDone] != 0.0) return;
+  const unsigned live = STEP == kMscgStart ? (k < 32 ? (1u << k) - 1u : ~0u) : pcgn_live(st);
+  const int ns = STEP == kMscgStart ? 2 : 1;                 // {b.b, r.r} behind pcgn_init_kernel
+  const int lane = threadIdx.x % kMscgMaxShifts;
+  for (int j0 = 0; j0 < k; j0 += kMscgnColumnsPerPass) {       // (workgroup-uniform: the steps hold barriers)
+    const int j = j0 + threadIdx.x / kMscgMaxShifts;
+    const bool active = j < k && ((live >> j) & 1u) != 0u;
+    const int ja = j < k ? j : 0;
+    double *stj = cst + ja * kStDoubles, *msj = ms + ja * kMscgStateDoubles;
+    const double *rj = red + ja * ns;
+    if (STEP == kMscgStart) {
+      mscg_start_step(rj[0], tol, stj, msj, m, sg, lane, active);
+    } else if (STEP == kMscgS1) {
+      mscg_s1_step(rj, stj, msj, m, lane, active);
+      if (active && lane == 0) cs[j * kPnStride + kPnAlpha] = stj[kStAlpha];
+    } else {
+      mscg_s2_step(rj, stj, msj, m, lane, active);
+    }
+  }
+  if (STEP == kMscgS1) return;
+  __syncthreads();
+  if ((int)threadIdx.x < m) {                                // per shift: the columns whose pair is live
+    unsigned mk = 0u;
+    for (int j = 0; j < k; ++j)
+      if (cst[j * kStDoubles + kStDone] == 0.0 && ms[j * kMscgStateDoubles + threadIdx.x * kMsStride + kMsLive] != 0.0) mk |= 1u << j;
+    sl[kSlMask + threadIdx.x] = (double)mk;
+    if (STEP == kMscgStart) sl[kSlPslot + threadIdx.x] = ms[threadIdx.x * kMsStride + kMsPslot];   // (the same in every column)
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  unsigned cm = 0u;
+  for (int j = 0; j < k; ++j)
+    if (cst[j * kStDoubles + kStDone] == 0.0) cm |= 1u << j;
+  int nb = 0, nl = 0;
+  for (int i = 0; i < m; ++i)
+    if (sl[kSlMask + i] != 0.0 && sg.v[i] == 0.0) sl[kSlList + nb++] = (double)i;
+  for (int i = 0; i < m; ++i)
+    if (sl[kSlMask + i] != 0.0 && sg.v[i] != 0.0) sl[kSlList + nb + nl++] = (double)i;
+  sl[kSlNBase] = (double)nb; sl[kSlNLive] = (double)nl;
+  st[kStLiveMask] = (double)cm;
+  if (STEP == kMscgStart) { st[kStIter] = 0.0; st[kStDone] = cm ? 0.0 : 1.0; }
+  else if (cm == 0u) st[kStDone] = 1.0;
+  else st[kStIter] += 1.0;
+}
+
+// one (V: two neighbouring, e even and k even, so both in one row) element of a panel streamed flat; al: 16-byte aligned panel
+template <bool V>
+__device__ __forceinline__ Pair fl_ld(const double *p, bool al)
+{
+  if (V && al) return pn_ld<true>(p, true);
+  return pn_ld<false>(p, V);
+}
+
+template <bool V>
+__device__ __forceinline__ void fl_st(double *p, Pair v, bool al, bool l0, bool l1)
+{
+  if (V && al) pn_st<true>(p, v, l0, V && l1);
+  else pn_st<false>(p, v, l0, V && l1);
+}
+
+__device__ __forceinline__ bool fl_aligned(const double *p) { return ((uintptr_t)p & 15) == 0; }
+
+// what fs_pcgn's start leaves to do: P = B, P_i = B for the nslots shifts with sigma != 0, X_i = 0 for the shifts behind the first
+// (pcgn_init_kernel wrote X_0 = 0 and R = B)
+template <bool V>
+__global__ __launch_bounds__(kRedThreads) void mscgn_fill_kernel(size_t ne, const double *__restrict__ B, double *__restrict__ P,
+                                                                double *__restrict__ Ps, size_t ldp, int nslots, double *__restrict__ X,
+                                                                size_t ldx, int m)
+{
+  constexpr int W = V ? 2 : 1;
+  const bool ba = fl_aligned(B);
+  for (size_t e = ((size_t)blockIdx.x * kRedThreads + threadIdx.x) * W; e < ne; e += (size_t)gridDim.x * kRedThreads * W) {
+    const Pair b = fl_ld<V>(B + e, ba);
+    fl_st<V>(P + e, b, true, true, true);
+    for (int s = 0; s < nslots; ++s) fl_st<V>(Ps + s * ldp + e, b, true, true, true);
+    for (int i = 1; i < m; ++i) fl_st<V>(X + i * ldx + e, {0.0, 0.0}, fl_aligned(X + i * ldx), true, true);
+  }
+}
+
+// the shifts of one group: their place in the list -> panel of X, direction (P itself for sigma = 0), mask of live columns
+struct MscgnShift { double *x; const double *p; double *pw; unsigned mask; bool xa; };
+__device__ __forceinline__ MscgnShift mscgn_shift(const double *__restrict__ sl, int at, double *X, size_t ldx, const double *P, double *Ps,
+                                                  size_t ldp)
+{
+  const int sh = __builtin_amdgcn_readfirstlane((int)sl[kSlList + at]);
+  const int slot = __builtin_amdgcn_readfirstlane((int)sl[kSlPslot + sh]);
+  const unsigned mask = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sl[kSlMask + sh]);
+  double *x = X ? X + sh * ldx : nullptr;
+  double *pw = slot < 0 ? nullptr : Ps + slot * ldp;
+  return {x, slot < 0 ? P : pw, pw, mask, fl_aligned(x)};
+}
+
+// x_ij = x_ij + a_ij P_ij for the live pairs of CNT shifts (their loads in flight together); co[u][c]: a of the group's shift u in
+// column c.  A frozen pair is not written
+template <int CNT, bool V>
+__device__ __forceinline__ void mscgn_update_group(size_t ne, int k, int at, double *X, size_t ldx, const double *P, double *Ps, size_t ldp,
+                                                   const double *__restrict__ sl, const double (&co)[kMscgGroup][kPcgnMaxRhs])
+{
+  constexpr int W = V ? 2 : 1;
+  MscgnShift g[CNT + 1];
+#pragma unroll
+  for (int u = 0; u < CNT; ++u) g[u] = mscgn_shift(sl, at + u, X, ldx, P, Ps, ldp);
+  const size_t stride = (size_t)gridDim.x * kRedThreads * W;
+  size_t e = ((size_t)blockIdx.x * kRedThreads + threadIdx.x) * W;
+  int c = (int)(e % (size_t)k);
+  const int cstep = (int)(stride % (size_t)k);
+  for (; e < ne; e += stride) {
+    Pair pv[CNT + 1], xv[CNT + 1];
+#pragma unroll
+    for (int u = 0; u < CNT; ++u) { pv[u] = fl_ld<V>(g[u].p + e, true); xv[u] = fl_ld<V>(g[u].x + e, g[u].xa); }
+#pragma unroll
+    for (int u = 0; u < CNT; ++u) {
+      const Pair x = {xv[u].a + co[u][c] * pv[u].a, V ? xv[u].b + co[u][V ? c + 1 : c] * pv[u].b : 0.0};
+      fl_st<V>(g[u].x + e, x, g[u].xa, ((g[u].mask >> c) & 1u) != 0u, V && ((g[u].mask >> (c + 1)) & 1u) != 0u);
+    }
+    c += cstep; if (c >= k) c -= k;
+  }
+}
+
+template <bool V>
+__global__ __launch_bounds__(kRedThreads) void mscgn_update_kernel(size_t ne, int k, double *X, size_t ldx, const double *P, double *Ps,
+                                                                  size_t ldp, const double *__restrict__ st, const double *__restrict__ ms,
+                                                                  const double *__restrict__ sl)
+{
+  static_assert(kMscgGroup == 4, "the dispatch below is on 1..4");
+  if (st[kStDone] != 0.0) return;
+  __shared__ double co[kMscgGroup][kPcgnMaxRhs];
+  const int nall = __builtin_amdgcn_readfirstlane((int)sl[kSlNBase] + (int)sl[kSlNLive]);
+  for (int at = 0; at < nall; at += kMscgGroup) {
+    const int cnt = nall - at < kMscgGroup ? nall - at : kMscgGroup;
+    __syncthreads();                                         // the group before has read its table
+    const int u = threadIdx.x / kPcgnMaxRhs, c = threadIdx.x % kPcgnMaxRhs;
+    if (u < cnt && c < k) co[u][c] = ms[c * kMscgStateDoubles + (int)sl[kSlList + at + u] * kMsStride + kMsA];
+    __syncthreads();
+    if (cnt == 4)      mscgn_update_group<4, V>(ne, k, at, X, ldx, P, Ps, ldp, sl, co);
+    else if (cnt == 3) mscgn_update_group<3, V>(ne, k, at, X, ldx, P, Ps, ldp, sl, co);
+    else if (cnt == 2) mscgn_update_group<2, V>(ne, k, at, X, ldx, P, Ps, ldp, sl, co);
+    else               mscgn_update_group<1, V>(ne, k, at, X, ldx, P, Ps, ldp, sl, co);
+  }
+}
+
+// p_j = r_j + beta_j p_j for the live columns (FIRST: the first group rides in this pass), P_ij = z_ij r_j + b_ij P_ij for the live
+// pairs of CNT shifts with sigma != 0 (z the new one): R is read once per group
+template <int CNT, bool V, bool FIRST>
+__device__ __forceinline__ void mscgn_direction_group(size_t ne, int k, int at, unsigned live, double *__restrict__ P,
+                                                      const double *__restrict__ R, double *Ps, size_t ldp, const double *__restrict__ sl,
+                                                      const double (&zc)[kMscgGroup][kPcgnMaxRhs], const double (&bc)[kMscgGroup][kPcgnMaxRhs],
+                                                      const double (&be)[kPcgnMaxRhs])
+{
+  constexpr int W = V ? 2 : 1;
+  MscgnShift g[CNT + 1];
+#pragma unroll
+  for (int u = 0; u < CNT; ++u) g[u] = mscgn_shift(sl, at + u, nullptr, 0, P, Ps, ldp);
+  const size_t stride = (size_t)gridDim.x * kRedThreads * W;
+  size_t e = ((size_t)blockIdx.x * kRedThreads + threadIdx.x) * W;
+  int c = (int)(e % (size_t)k);
+  const int cstep = (int)(stride % (size_t)k);
+  for (; e < ne; e += stride) {
+    const int c1 = V ? c + 1 : c;
+    Pair pv[CNT + 1], p0 = {0.0, 0.0};
+#pragma unroll
+    for (int u = 0; u < CNT; ++u) pv[u] = fl_ld<V>(g[u].pw + e, true);
+    const Pair r = fl_ld<V>(R + e, true);
+    if (FIRST) {
+      p0 = fl_ld<V>(P + e, true);
+      const Pair p = {r.a + be[c] * p0.a, V ? r.b + be[c1] * p0.b : 0.0};
+      fl_st<V>(P + e, p, true, ((live >> c) & 1u) != 0u, V && ((live >> c1) & 1u) != 0u);
+    }
+#pragma unroll
+    for (int u = 0; u < CNT; ++u) {
+      const double t1 = zc[u][c] * r.a, t2 = bc[u][c] * pv[u].a;
+      const double t3 = V ? zc[u][c1] * r.b : 0.0, t4 = V ? bc[u][c1] * pv[u].b : 0.0;
+      fl_st<V>(g[u].pw + e, {t1 + t2, t3 + t4}, true, ((g[u].mask >> c) & 1u) != 0u, V && ((g[u].mask >> c1) & 1u) != 0u);
+    }
+    c += cstep; if (c >= k) c -= k;
+  }
+}
+
+template <int CNT, bool V, typename... T>
+__device__ __forceinline__ void mscgn_direction_first(bool first, T &&...a)
+{
+  if (first) mscgn_direction_group<CNT, V, true>(a...);
+  else mscgn_direction_group<CNT, V, false>(a...);
+}
+
+template <bool V>
+__global__ __launch_bounds__(kRedThreads) void mscgn_direction_kernel(size_t ne, int k, double *__restrict__ P, const double *__restrict__ R,
+                                                                     double *Ps, size_t ldp, const double *__restrict__ st,
+                                                                     const double *__restrict__ cst, const double *__restrict__ ms,
+                                                                     const double *__restrict__ sl)
+{
+  if (st[kStDone] != 0.0) return;
+  __shared__ double zc[kMscgGroup][kPcgnMaxRhs], bc[kMscgGroup][kPcgnMaxRhs], be[kPcgnMaxRhs];
+  const unsigned live = pcgn_live(st);
+  const int nb = __builtin_amdgcn_readfirstlane((int)sl[kSlNBase]), nl = __builtin_amdgcn_readfirstlane((int)sl[kSlNLive]);
+  if ((int)threadIdx.x < k) be[threadIdx.x] = cst[threadIdx.x * kStDoubles + kStBeta];
+  for (int g0 = 0; g0 == 0 || g0 < nl; g0 += kMscgGroup) {
+    const int cnt = nl - g0 < kMscgGroup ? nl - g0 : kMscgGroup, at = nb + g0;
+    __syncthreads();                                         // the group before has read its tables
+    const int u = threadIdx.x / kPcgnMaxRhs, c = threadIdx.x % kPcgnMaxRhs;
+    if (u < cnt && c < k) {
+      const double *e = ms + c * kMscgStateDoubles + (int)sl[kSlList + at + u] * kMsStride;
+      zc[u][c] = e[kMsZ]; bc[u][c] = e[kMsB];
+    }
+    __syncthreads();
+    if (cnt == 4)      mscgn_direction_first<4, V>(g0 == 0, ne, k, at, live, P, R, Ps, ldp, sl, zc, bc, be);
+    else if (cnt == 3) mscgn_direction_first<3, V>(g0 == 0, ne, k, at, live, P, R, Ps, ldp, sl, zc, bc, be);
+    else if (cnt == 2) mscgn_direction_first<2, V>(g0 == 0, ne, k, at, live, P, R, Ps, ldp, sl, zc, bc, be);
+    else if (cnt == 1) mscgn_direction_first<1, V>(g0 == 0, ne, k, at, live, P, R, Ps, ldp, sl, zc, bc, be);
+    else               mscgn_direction_group<0, V, true>(ne, k, at, live, P, R, Ps, ldp, sl, zc, bc, be);
+  }
+}
+
 // the kernels' shape for k columns: KMAX = 4, 8, 16 or 32 sums per thread, VEC as in pcgn_init_kernel
 template <int KMAX, int VEC> struct PcgnShape { static constexpr int kmax = KMAX, vec = VEC; };
 template <typename F>
@@ -1640,7 +1903,7 @@ static int pcgn_shift_dot_step(int n, int k, int vec, const LAM &lambda, double 
   return rc;
 }
 
-// X and R; r.r, or {r.r, r.z} with a preconditioner: converged? beta
+// X (NULL: left to the caller's own steps) and R; r.r, or {r.r, r.z} with a preconditioner: converged? beta
 template <typename... CJ>
 static int pcgn_update_step(int n, int k, int vec, double *X, double *R, const double *P, const double *Q, const double *dinv,
                             const PcgnSums &U, hipStream_t s, CJ... colj)
@@ -1649,8 +1912,16 @@ static int pcgn_update_step(int n, int k, int vec, double *X, double *R, const d
   const bool staged = pcgn_staged(k);
   const int rc = pcgn_dispatch(k, vec, [&](auto sh) -> int {
     using S = decltype(sh);
-    if (staged) hipLaunchKernelGGL((pcgn_update_lds_kernel<S::kmax, CJ...>), g, blk, 0, s, n, k, X, R, P, Q, dinv, U.part, U.st, U.cs, colj...);
-    else        hipLaunchKernelGGL((pcgn_update_kernel<S::kmax, S::vec, CJ...>), g, blk, 0, s, n, k, X, R, P, Q, dinv, U.part, U.st, U.cs, colj...);
+    auto launch = [&](auto xup) {
+      constexpr bool XUP = decltype(xup)::value;
+      if (staged) hipLaunchKernelGGL((pcgn_update_lds_kernel<S::kmax, XUP, CJ...>), g, blk, 0, s, n, k, X, R, P, Q, dinv, U.part, U.st, U.cs, colj...);
+      else        hipLaunchKernelGGL((pcgn_update_kernel<S::kmax, S::vec, XUP, CJ...>), g, blk, 0, s, n, k, X, R, P, Q, dinv, U.part, U.st, U.cs, colj...);
+    };
+    if constexpr (sizeof...(CJ) == 0) {
+      if (X) launch(std::true_type{}); else launch(std::false_type{});   // X NULL (fs_mscgn): r and its sums only
+    } else {
+      launch(std::true_type{});
+    }
     return FS_OK;
   });
   pcgn_sums_launch(kPnStepBeta, U, k, dinv ? 2 : 1, 0.0, s);                                                 // converged? beta
@@ -1898,6 +2169,54 @@ int mscg_dev_final(MscgStep step, const double *partials, int count, double *red
   return mscg_scalar_step(step, partials, count, red_out, st, K, s);
 }
 
+// ---- fs_mscgn's steps as launchers: fs_pcgn's launchers for every step that takes per-column sums (U.send set: pcgn_fold_kernel
+// leaves the finished sums there), the scalar step of fs_mscg per column behind them, the flat kernels for the pairs.
+// ne = F k elements per panel; Ps: the direction panels of the shifts with sigma != 0, ldp doubles apart
+struct MscgnState { double *cst, *ms, *sl; int m; double tol; const MscgShifts *sh; };
+
+static int mscgn_scalar_step(MscgStep step, const PcgnSums &U, const MscgnState &K, int k, hipStream_t s)
+{
+  const dim3 one(1), blk(kRedThreads);
+  if (step == kMscgStart)   hipLaunchKernelGGL(mscgn_step_kernel<kMscgStart>, one, blk, 0, s, U.send, U.st, K.cst, U.cs, K.ms, K.sl, k, K.m, K.tol, K.sh->sg);
+  else if (step == kMscgS1) hipLaunchKernelGGL(mscgn_step_kernel<kMscgS1>, one, blk, 0, s, U.send, U.st, K.cst, U.cs, K.ms, K.sl, k, K.m, K.tol, K.sh->sg);
+  else                      hipLaunchKernelGGL(mscgn_step_kernel<kMscgS2>, one, blk, 0, s, U.send, U.st, K.cst, U.cs, K.ms, K.sl, k, K.m, K.tol, K.sh->sg);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// X_i = 0 for the K.m shifts, R = P = B, P_i = B for the shifts with sigma != 0; b.b per column, stop, every pair's scalars, live?
+static int mscgn_init(int F, int k, const double *B, double *X, long long ldx, double *R, double *P, double *Q, double *Ps, long long ldp,
+                      const PcgnSums &U, const MscgnState &K, hipStream_t s)
+{
+  if (int rc = pcgn_init_step(F, k, pcgn_vec(k, X, B), false, 0.0, B, X, R, Q, U, K.tol, s)) return rc;   // X_0 = 0, R = B; {b.b, r.r}
+  if (int rc = mscgn_scalar_step(kMscgStart, U, K, k, s)) return rc;
+  const size_t ne = (size_t)F * k;
+  const dim3 g(kRedBlocks), blk(kRedThreads);
+  if (k & 1) hipLaunchKernelGGL(mscgn_fill_kernel<false>, g, blk, 0, s, ne, B, P, Ps, (size_t)ldp, K.sh->nslots, X, (size_t)ldx, K.m);
+  else       hipLaunchKernelGGL(mscgn_fill_kernel<true>, g, blk, 0, s, ne, B, P, Ps, (size_t)ldp, K.sh->nslots, X, (size_t)ldx, K.m);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// everything of an iteration behind Q = A'(A P), all on the device
+static int mscgn_steps(int F, int k, double *X, long long ldx, double *R, double *P, double *Q, double *Ps, long long ldp, const PcgnSums &U,
+                       const MscgnState &K, hipStream_t s)
+{
+  const int vec = (k & 1) ? 0 : 1;                           // R, P, Q are the solve's own
+  const size_t ne = (size_t)F * k;
+  const dim3 g(kRedBlocks), blk(kRedThreads);
+  if (int rc = pcgn_shift_dot_step(F, k, vec, K.sh->base, Q, P, U, s)) return rc;                       // q += base p; q.p
+  if (int rc = mscgn_scalar_step(kMscgS1, U, K, k, s)) return rc;                                       // alpha_j, the a_ij
+  if (int rc = pcgn_update_step(F, k, vec, nullptr, R, P, Q, nullptr, U, s)) return rc;                 // r -= alpha q; r.r
+  if (k & 1) hipLaunchKernelGGL(mscgn_update_kernel<false>, g, blk, 0, s, ne, k, X, (size_t)ldx, P, Ps, (size_t)ldp, U.st, K.ms, K.sl);
+  else       hipLaunchKernelGGL(mscgn_update_kernel<true>, g, blk, 0, s, ne, k, X, (size_t)ldx, P, Ps, (size_t)ldp, U.st, K.ms, K.sl);
+  if (int rc = mscgn_scalar_step(kMscgS2, U, K, k, s)) return rc;                                       // converged? beta_j, freezes
+  if (k & 1) hipLaunchKernelGGL(mscgn_direction_kernel<false>, g, blk, 0, s, ne, k, P, R, Ps, (size_t)ldp, U.st, K.cst, K.ms, K.sl);
+  else       hipLaunchKernelGGL(mscgn_direction_kernel<true>, g, blk, 0, s, ne, k, P, R, Ps, (size_t)ldp, U.st, K.cst, K.ms, K.sl);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
 // ---- the same for two right-hand sides (fs_cg2, fs_dist_cg2).  cg2_dev_init is synchronous (two reductions go to the host: the
 // norms of B's columns scale the system, cg.h:105-125); norms[2] is returned for the final cg2_dev_finish
 int cg2_dev_init(int n, const double *B, double *X, double *R, double *P, double *part, double *red, double *st, double tol,
@@ -1951,6 +2270,10 @@ static thread_local int g_last_mscg_doubles = 0;
 
 static thread_local double g_last_pcgn_state[kPcgnMaxRhs * kPnStride];
 static thread_local int g_last_pcgn_doubles = 0;
+
+// the last fs_mscgn on the calling thread: every column's st[] (fs_mscg's layout) and ms[], k and m
+static thread_local std::vector<double> g_last_mscgn_cst, g_last_mscgn_ms;
+static thread_local int g_last_mscgn_k = 0, g_last_mscgn_m = 0;
 
 // the segments of the last fs_pcgn / fs_pcgn_lambdas on the calling thread: {first iteration, width, mask of original columns} each
 constexpr int kPcgnMaxSegments = 8;
@@ -2009,6 +2332,24 @@ void mscg_note_state(const double *fin, const double *fms, int m, fs_pcg_info *i
     info[i].rnorm = e[kMsRn];
     info[i].bnorm = sqrt(fin[kStBb]);
   }
+}
+
+// the end of an fs_mscgn solve on the host: fcst = the k columns' final st[], fms = their final ms[] (both kept for
+// fs_debug_last_mscgn_state); info: m * k entries, info[i * k + j], or NULL
+static void mscgn_note_state(const double *fcst, const double *fms, int k, int m, fs_pcg_info *info)
+{
+  g_last_mscgn_cst.assign(fcst, fcst + (size_t)k * kStDoubles);
+  g_last_mscgn_ms.assign(fms, fms + (size_t)k * kMscgStateDoubles);
+  g_last_mscgn_k = k; g_last_mscgn_m = m;
+  for (int i = 0; info && i < m; ++i)
+    for (int j = 0; j < k; ++j) {
+      const double *e = fms + (size_t)j * kMscgStateDoubles + i * kMsStride;
+      fs_pcg_info &o = info[(size_t)i * k + j];
+      o.iterations = (int)e[kMsCount];                       // a pair still live at the cap: count = cap, converged 0
+      o.converged = e[kMsConverged] != 0.0;
+      o.rnorm = e[kMsRn];
+      o.bnorm = sqrt(fcst[(size_t)j * kStDoubles + kStBb]);
+    }
 }
 
 // two ranks' final cs[]: every column ended live or not, converged or not, with the same count
@@ -2472,6 +2813,50 @@ int fs_mscg(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double 
   return FS_OK;
 }
 
+// (A'A + lambda[i] I) x_ij = b_j for i < m, j < k: fs_mscg on every column of B, on one pair of k-column products per iteration;
+// see include/fastsparse_hip.h for what differs from fs_mscg.  The per-column sums are formed by fs_pcgn's kernels, the scalar
+// steps are fs_mscg's, so column j of panel i has the bits of fs_mscg's x_i on B[:, j] wherever the k-column product has the
+// single-vector product's bits, and with m = 1 the solve is fs_pcgn without a preconditioner from a cold start.
+int fs_mscgn(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double *B, int k, int m, const double *lambda, double tol,
+             int max_iter, fs_pcg_info *info, fs_stream_t stream)
+{
+  FS_RANGE("fs_mscgn");
+  if (!A || !At || !X || !B || !lambda) { set_error("fs_mscgn: NULL argument"); return FS_ERR_ARG; }
+  if (k < 1 || k > kPcgnMaxRhs) { set_error("fs_mscgn: k outside 1..FS_PCGN_MAX_RHS"); return FS_ERR_ARG; }
+  CgSolve f{"fs_mscgn", A, At, k, stream};
+  if (int rc = f.shape()) return rc;
+  const int F = f.F;
+  if (ldx < (int64_t)F * k) { set_error("fs_mscgn: ldx < ncol(A) * k"); return FS_ERR_ARG; }
+  if (int rc = mscg_args_ok("fs_mscgn", 0, ldx, m, lambda, tol)) return rc;     // (ldx is settled above)
+  if (k >= 2) {                                              // the k-column copies of both matrices (fs_spmm itself never builds)
+    if (int rc = fs_matrix_prepare(A, k, 0, stream)) return rc;
+    if (int rc = fs_matrix_prepare(At, k, 0, stream)) return rc;
+  }
+  if (int rc = f.ready()) return rc;
+  const MscgShifts sh = mscg_shifts(m, lambda);
+  const int cap = max_iter > 0 ? max_iter : F;               // cg.h:55
+  const size_t ne = (size_t)F * k;
+  const long long ldp = (long long)((ne + 1) & ~(size_t)1);  // every P_i 16-byte aligned
+  hipStream_t s = (hipStream_t)stream;
+  const size_t npart = pcgn_part_doubles(k), nscal = kPcgnSendDoubles + kPcgnStateDoubles + (size_t)kPcgnMaxRhs * kStDoubles +
+                                                     kMscgnStateDoubles + kMscgnListDoubles;
+  double *Ps = nullptr, *own = nullptr;
+  if (int rc = f.alloc(&Ps, (size_t)ldp * sh.nslots, &own, npart + nscal)) return rc;   // all of it before the first store to X
+  double *part = own, *red = part + npart, *cs = red + kPcgnSendDoubles, *cst = cs + kPcgnStateDoubles;
+  double *ms = cst + (size_t)kPcgnMaxRhs * kStDoubles, *sl = ms + kMscgnStateDoubles;
+  FS_HIP(hipMemsetAsync(red, 0, sizeof(double) * nscal, s));  // slots a column never writes read as 0 in the debug getter
+  const PcgnSums U{part, f.st, cs, red};
+  const MscgnState K{cst, ms, sl, m, tol, &sh};
+  if (int rc = mscgn_init(F, k, B, X, (long long)ldx, f.r, f.p, f.q, Ps, ldp, U, K, s)) return rc;
+  if (int rc = f.iterate(cap, true, [&] { return mscgn_steps(F, k, X, (long long)ldx, f.r, f.p, f.q, Ps, ldp, U, K, s); })) return rc;
+  std::vector<double> fcst((size_t)k * kStDoubles), fms((size_t)k * kMscgStateDoubles);
+  FS_HIP(hipMemcpyAsync(fcst.data(), cst, sizeof(double) * fcst.size(), hipMemcpyDeviceToHost, s));
+  FS_HIP(hipMemcpyAsync(fms.data(), ms, sizeof(double) * fms.size(), hipMemcpyDeviceToHost, s));
+  if (int rc = f.finish()) return rc;
+  mscgn_note_state(fcst.data(), fms.data(), k, m, info);
+  return FS_OK;
+}
+
 // (A'A + lambda I) X = B for k right-hand sides, X and B row-major F x k: k independent fs_pcg recurrences on shared k-column
 // products; see include/fastsparse_hip.h for the arithmetic.  Column j has the bits of fs_pcg on B[:, j] wherever the k-column
 // product has the bits of the single-vector one ("strict_order"; k = 1 in every mode: the products are fs_spmv).
@@ -2536,6 +2921,20 @@ int fs_debug_last_mscg_state(double *out, int max_doubles)
   const int n = g_last_mscg_doubles < max_doubles ? g_last_mscg_doubles : max_doubles;
   for (int i = 0; i < n; ++i) out[i] = g_last_mscg_state[i];
   return n;
+}
+
+// column `column` of the last fs_mscgn on the calling thread in fs_mscg's own layouts: st (kCgStateDoubles doubles) as
+// fs_debug_last_cg_state hands out fs_mscg's, ms (m * kMsStride doubles, at most max_ms_doubles of them) as fs_debug_last_mscg_state
+// does.  Returns m * kMsStride, 0 before the first solve.  Diagnostics, not in the header.
+int fs_debug_last_mscgn_state(int column, double *st, double *ms, int max_ms_doubles)
+{
+  if (!st || !ms || max_ms_doubles < 0) { set_error("fs_debug_last_mscgn_state: bad argument"); return FS_ERR_ARG; }
+  if (g_last_mscgn_k == 0) return 0;
+  if (column < 0 || column >= g_last_mscgn_k) { set_error("fs_debug_last_mscgn_state: no such column"); return FS_ERR_ARG; }
+  for (int i = 0; i < kStDoubles; ++i) st[i] = g_last_mscgn_cst[(size_t)column * kStDoubles + i];
+  const int n = g_last_mscgn_m * kMsStride < max_ms_doubles ? g_last_mscgn_m * kMsStride : max_ms_doubles;
+  for (int i = 0; i < n; ++i) ms[i] = g_last_mscgn_ms[(size_t)column * kMscgStateDoubles + i];
+  return g_last_mscgn_m * kMsStride;
 }
 
 // the segments of the last fs_pcgn / fs_pcgn_lambdas on the calling thread (option "pcgn_compact"): three ints per segment -- its first

@@ -444,6 +444,8 @@ void pcgn_note_state(const double *st_host, const double *cs_host, int k, fs_pcg
 // ---- fs_mscg's steps (fs_mscg; fs_dist_mscg on every rank, on whole vectors or on the rank's slice).  ms: kMscgStateDoubles, st
 // and the sums as above; X: m vectors ldx apart, P: sh.nslots directions ldp apart, each of n doubles
 constexpr int kMscgStateDoubles = FS_MSCG_MAX_SHIFTS * 16;
+constexpr int kMscgnStateDoubles = FS_PCGN_MAX_RHS * kMscgStateDoubles;   // fs_mscgn: an ms[] per column
+constexpr int kMscgnListDoubles = 64;                                     // fs_mscgn's sl[]: the per-shift list, masks and slots
 struct MscgSigma { double v[FS_MSCG_MAX_SHIFTS]; };
 // what the host picks: base = the smallest lambda, sigma_i = lambda[i] - base, nslots = the shifts with sigma != 0
 struct MscgShifts { double base; MscgSigma sg; int nslots; };
