@@ -89,7 +89,7 @@ int  fs_set_device(int device);
  * "pcgn_compact" (default 0; FS_PCGN_COMPACT): fs_pcgn and fs_pcgn_lambdas, 1 = the live columns of a solve move into a narrower
  * panel whenever they fit the next of the widths 16, 8, 4, 2, 1, and the products run at that width (see fs_pcgn, "Narrowing");
  * 0 = every iteration runs on all k columns.  fs_dist_pcgn, fs_dist_pcgn_lambdas and fs_mscgn do not read it.
- * "dist_cg_scheme" (FS_DIST_CG_SCHEME): fs_dist_cg, fs_dist_pcg and fs_dist_mscg, 0 every device keeps whole vectors, 1 every device keeps its slice (see there). */
+ * "dist_cg_scheme" (FS_DIST_CG_SCHEME): fs_dist_cg, fs_dist_pcg, fs_dist_mscg and fs_dist_mscgn, 0 every device keeps whole vectors, 1 every device keeps its slice (see there). */
 int  fs_set_option(const char *name, int value);
 int  fs_get_option(const char *name);
 
@@ -662,6 +662,48 @@ int  fs_dist_pcgn_lambdas(fs_dist_matrix_t M, double *X, const double *B, int k,
  * on a shard that gave its plain CSR back).  CLOBBERS fs_dist_x / fs_dist_y / fs_dist_z like fs_dist_cg. */
 int  fs_dist_mscg(fs_dist_matrix_t M, double *X, int64_t ldx, const double *b, int m, const double *lambda /* host */,
                   double tol, int max_iter, fs_pcg_info *info /* m entries or NULL */);
+/* fs_dist_mscgn: fs_mscgn on the sharded matrix -- (A'A + lambda[i] I) x_ij = b_j for i < m, j < k on one pair of k-column products
+ * per iteration, m in 1..FS_MSCG_MAX_SHIFTS, k in 1..FS_PCGN_MAX_RHS.  Its arithmetic is fs_mscgn's above, whose text is the single
+ * statement of it; this says only what differs.  B: a row-major ncol x k panel; panel i of X at X + i * ldx (ldx >= ncol * k, the
+ * gaps are never touched); X and B in host memory or in HBM of any device of the context, decided per pointer as for fs_dist_mscg:
+ * nothing in HBM is staged through the host.  lambda: m doubles on the host.  Needs the transposed side (FS_ERR_NO_TRANSPOSE; from
+ * fs_dist_matrix_build_transpose, _device or fs_dist_matrix_pair), is synchronous, cold start only and without a preconditioner.
+ * Option "pcgn_compact" is not read.  Option "dist_cg_scheme" as for fs_dist_mscg; slices only with more than one rank:
+ *   0  every rank holds whole panels R, P, Q, the m X_i and the direction panels and launches fs_mscgn's own steps on them; T = A P
+ *      and Q = A' T are the sharded k-column products of fs_dist_spmm (k = 1: fs_dist_spmv's), nothing is exchanged for the sums.
+ *      `red_j` is fs_mscgn's: under "strict_order" X, every info and every column's scalars and per-shift array are fs_mscgn's on
+ *      the same CSRs, bit for bit, for any number of ranks.
+ *   1  rank r keeps its rows [lo_r, hi_r) = fs_dist_matrix_bounds_t of R, Q, every X_i and every P_i: contiguous (hi_r - lo_r) k
+ *      doubles of the row-major panels, which the flat pair kernels take as panels of fewer rows.  P and T = A P stay whole on every
+ *      rank; the rank's slice of P lives in the k-column exchange's own send buffer, as in fs_dist_pcgn_lambdas.  The X_i and P_i
+ *      never leave their rank: only P enters a product.  An iteration is one sharded product T = A P, the rank's own shard product
+ *      Q_r = A'_r T (fs_spmm on the shard; fs_spmv for k = 1), two small exchanges of k doubles per rank (q p, then r r) and the
+ *      all-gather of the new P slices, however many shifts there are; the (12 + 5 L) k F doubles the vector kernels move and the
+ *      (m + nslots) k F doubles of panels are divided by the ranks.  The first P is B, which every rank holds whole after staging:
+ *      no gather before the first product; the start exchanges {bb_j, rr_j}, 2 k doubles per rank.  `red_j` is the slice tree of
+ *      fs_dist_cg, per column, as in fs_dist_pcgn_lambdas: the rank's partial sums are finished into its send slot (row indices
+ *      local to the slice, an empty slice gives +0.0, a frozen column's slots are sent as +0.0 and never read), all-gathered and
+ *      added in rank order with the second stage.  Start, S1 and S2 of fs_mscg then run per column on every rank over the same
+ *      values, so alpha_j, the a_ij and b_ij, every freeze, the per-shift masks and the list of live shifts are identical everywhere.
+ * Work space per rank, kept on the handle between solves (the panels re-made when a solve needs more or longer ones, all of it
+ * freed by fs_dist_matrix_destroy), n_r = ncol under scheme 0 and hi_r - lo_r under scheme 1: m + nslots panels of n_r k doubles
+ * (rounded up to an even count) for the X_i and the P_i; fs_dist_pcgn_lambdas' own for k columns, of which this solve uses R, B
+ * (and Q under scheme 1) of n_r k doubles, 2048 k doubles of partial sums, two send slots of 2 FS_PCGN_MAX_RHS doubles and N times
+ * that for the gathered values; 9344 doubles of scalars; and the whole P (ncol k), T (nrow k) and Q (ncol k) of the sharded
+ * k-column products, with the slice of P in their send buffer.
+ * Every rank decides convergence for itself as in fs_dist_cg; {done, iterations} is compared one iteration behind, and at the end
+ * every rank's mask of live columns, every column's done flag and every pair's {live, converged, count} must agree with rank 0's: a
+ * disagreement is an error return (FS_ERR_HIP).  X is written ONCE, at the end of a solve that succeeded -- scheme 0: whole panels
+ * from rank 0; scheme 1: every rank stores its rows at X + i * ldx + lo_r k --: every refusal and every product error leaves all
+ * of X untouched.  A solve that is done at its start (B = 0, tol >= 1) enqueues no product: X = +0.0, every pair converged, 0
+ * iterations.  fs_debug_last_cg_state and fs_debug_last_mscgn_state report rank 0's.
+ * FS_ERR_ARG, raised before anything else happens: a NULL M, X, B or lambda; k outside 1..FS_PCGN_MAX_RHS; m outside
+ * 1..FS_MSCG_MAX_SHIFTS; ldx < ncol * k; tol negative or NaN; a lambda that is NaN or infinite.  A product's own error is passed
+ * through (FS_ERR_RELEASED under "strict_order" on a shard that gave its plain CSR back).  CLOBBERS fs_dist_x / fs_dist_y /
+ * fs_dist_z and the k-column vectors of fs_dist_spmm, like fs_dist_pcgn. */
+int fs_dist_mscgn(fs_dist_matrix_t M, double *X, int64_t ldx, const double *B, int k, int m,
+                  const double *lambda /* m doubles on the HOST */, double tol, int max_iter,
+                  fs_pcg_info *info /* m * k entries, info[i * k + j], or NULL */);
 /* k row-major columns across the GPUs (csr_A_mul_Bn csr.h:441, bcsr_A_mul_Bn csr.h:257, bsbm_A_mul_Bn sparse.h:318): every device
  * multiplies its shard with the k-column kernels of fs_spmm (prepared on the first call with a new k: synchronous) and the Y shards
  * are all-gathered -- inside the product, part by part, where the k-column product finishes its rows that way (the one-sweep plan

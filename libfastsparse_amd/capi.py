@@ -35,7 +35,7 @@ DEVICE_API = [
     "fs_dist_z", "fs_dist_cg", "fs_dist_is_conservative", "fs_dist_csr_create_from_shards", "fs_dist_matrix_build_transpose_device",
     "fs_dist_matrix_bounds_t", "fs_dist_matrix_nnz", "fs_dist_matrix_shard", "fs_dist_spmm", "fs_dist_spmm_t", "fs_dist_cg2",
     "fs_dist_coo_create", "fs_dist_matrix_pair", "fs_dist_ata", "fs_dist_gram_diag", "fs_dist_pcg", "fs_dist_pcgn", "fs_dist_mscg",
-    "fs_dist_pcgn_lambdas",
+    "fs_dist_pcgn_lambdas", "fs_dist_mscgn",
 ]
 REFERENCE_API = [
     # sparse.h
@@ -199,6 +199,7 @@ def lib():
     L.fs_dist_pcgn.argtypes = [vp, vp, vp, C.c_int, C.c_double, C.POINTER(PcgParams), C.POINTER(PcgInfo)]
     L.fs_dist_pcgn_lambdas.argtypes = [vp, vp, vp, C.c_int, C.POINTER(C.c_double), C.POINTER(PcgParams), C.POINTER(PcgInfo)]
     L.fs_dist_mscg.argtypes = [vp, vp, C.c_int64, vp, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(PcgInfo)]
+    L.fs_dist_mscgn.argtypes = [vp, vp, C.c_int64, vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_double, C.c_int, C.POINTER(PcgInfo)]
     L.fs_dist_spmm.argtypes = [vp, vp, vp, C.c_int]
     L.fs_dist_spmm_t.argtypes = [vp, vp, vp, C.c_int]
     for f in ("fs_dist_spmv_resident", "fs_dist_spmv_t_resident", "fs_dist_swap_xy"):
@@ -557,6 +558,29 @@ def dist_mscg(M, X, b, lams, tol, max_iter=0):
     check(lib().fs_dist_mscg(M, at, int(ldx), _ptr(b), m, (C.c_double * max(m, 1))(*lams), float(tol), int(max_iter), infos),
           "fs_dist_mscg")
     return list(infos)[:m]
+
+
+def dist_mscgn(M, X, B, lams, tol, max_iter=0):
+    """fs_mscgn on a row-sharded matrix (fs_dist_mscgn): dist_mscg on every column of B, on shared k-column products.  B: a
+    contiguous (F, k) numpy array in host memory or a tensor on any device of the context, k <= FS_PCGN_MAX_RHS; X: (m, F, k) with
+    contiguous panels (they may be padded: ldx comes from the stride of the first axis), host or device; lams: m <=
+    FS_MSCG_MAX_SHIFTS host values.  Returns the m x k PcgInfo as a list of lists, infos[i][j]."""
+    lams = [float(v) for v in lams]
+    m = len(lams)
+    if len(B.shape) != 2 or len(X.shape) != 3 or tuple(X.shape) != (m,) + tuple(B.shape):
+        raise ValueError("dist_mscgn: B must be a contiguous (F, k) array and X (len(lams), F, k) with contiguous panels")
+    F, k = int(B.shape[0]), int(B.shape[1])
+    if hasattr(X, "data_ptr"):
+        at, xs, bs = X.data_ptr(), tuple(X.stride()), tuple(B.stride())
+    else:
+        at, xs, bs = X.ctypes.data, tuple(v // X.itemsize for v in X.strides), tuple(v // B.itemsize for v in B.strides)
+    if F * k > 0 and ((F > 1 and (xs[1] != k or bs[0] != k)) or (k > 1 and (xs[2] != 1 or bs[1] != 1))):
+        raise ValueError("dist_mscgn: B must be a contiguous (F, k) array and X (len(lams), F, k) with contiguous panels")
+    ldx = xs[0] if m > 1 else max(xs[0], F * k)
+    infos = (PcgInfo * max(m * k, 1))()
+    check(lib().fs_dist_mscgn(M, at, int(ldx), _ptr(B), k, m, (C.c_double * max(m, 1))(*lams), float(tol), int(max_iter), infos),
+          "fs_dist_mscgn")
+    return [list(infos[i * k:(i + 1) * k]) for i in range(m)]
 
 
 _option_epoch = 0

@@ -1200,16 +1200,20 @@ __device__ __forceinline__ void pcgn_fold(const double *__restrict__ part, int c
   }
 }
 
-// a rank's slice sums into its send slot (fs_dist_pcgn_lambdas on slices): one workgroup, the first half of pcgn_step_kernel.
-// `start`: every column is live (behind pcgn_init_kernel).  A frozen column's slots are sent as +0.0
-__global__ __launch_bounds__(kRedThreads) void pcgn_fold_kernel(const double *__restrict__ part, double *__restrict__ send,
+// a rank's slice sums into its send slot (fs_dist_pcgn_lambdas, fs_dist_mscgn on slices): one workgroup, the first half of
+// pcgn_step_kernel.  `start`: every column is live (behind pcgn_init_kernel).  A frozen column's slots are sent as +0.0.
+// ranks > 0: `part` holds the gathered slots of that many ranks (rank r's ns * k values at r * ns * k), added in rank order into
+// send[] -- the first half of pcgn_step_kernel<STEP, true>, for a scalar step that is a kernel of its own (fs_dist_mscgn:
+// mscgn_step_kernel)
+__global__ __launch_bounds__(kRedThreads) void pcgn_fold_kernel(const double *__restrict__ part, int ranks, double *__restrict__ send,
                                                                const double *__restrict__ st, int k, int ns, int start)
 {
   if (!start && st[kStDone] != 0.0) return;
   __shared__ double sm[2 * kPcgnMaxRhs][kRedThreads / 64];
   const unsigned live = start ? (k < 32 ? (1u << k) - 1u : ~0u) : pcgn_live(st);
   const int nv = ns * k;
-  pcgn_fold<false>(part, kRedBlocks, live, nv, ns, sm);
+  if (ranks > 0) pcgn_fold<true>(part, ranks, live, nv, ns, sm);         // (a kernel argument: uniform)
+  else pcgn_fold<false>(part, kRedBlocks, live, nv, ns, sm);
   __syncthreads();
   if ((int)threadIdx.x < nv) {
     double s = 0.0;
@@ -1844,11 +1848,17 @@ static void pcgn_step_launch(PcgnStep step, const double *part, int count, doubl
   }
 }
 
+// ns finished sums per column into `send`: of the kRedBlocks partials in `part` (ranks = 0), or of `ranks` ranks' gathered slots
+static void pcgn_fold_launch(const double *part, int ranks, double *send, const double *st, int k, int ns, bool start, hipStream_t s)
+{
+  hipLaunchKernelGGL(pcgn_fold_kernel, dim3(1), dim3(kRedThreads), 0, s, part, ranks, send, st, k, ns, (int)start);
+}
+
 // behind a vector kernel that left ns sums per live column and workgroup in U.part: whole panels are finished and the scalar
 // step taken; a slice's sums are folded into the rank's send slot
 static void pcgn_sums_launch(PcgnStep step, const PcgnSums &U, int k, int ns, double tol, hipStream_t s)
 {
-  if (U.send) hipLaunchKernelGGL(pcgn_fold_kernel, dim3(1), dim3(kRedThreads), 0, s, U.part, U.send, U.st, k, ns, (int)(step == kPnStepStart));
+  if (U.send) pcgn_fold_launch(U.part, 0, U.send, U.st, k, ns, step == kPnStepStart, s);
   else pcgn_step_launch<false>(step, U.part, kRedBlocks, U.st, U.cs, k, ns, tol, s);
 }
 
@@ -2169,27 +2179,36 @@ int mscg_dev_final(MscgStep step, const double *partials, int count, double *red
   return mscg_scalar_step(step, partials, count, red_out, st, K, s);
 }
 
-// ---- fs_mscgn's steps as launchers: fs_pcgn's launchers for every step that takes per-column sums (U.send set: pcgn_fold_kernel
-// leaves the finished sums there), the scalar step of fs_mscg per column behind them, the flat kernels for the pairs.
-// ne = F k elements per panel; Ps: the direction panels of the shifts with sigma != 0, ldp doubles apart
-struct MscgnState { double *cst, *ms, *sl; int m; double tol; const MscgShifts *sh; };
-
-static int mscgn_scalar_step(MscgStep step, const PcgnSums &U, const MscgnState &K, int k, hipStream_t s)
+// ---- fs_mscgn's steps as launchers (fs_mscgn; fs_dist_mscgn on every rank: whole panels, or the rank's slice of R, Q, the X_i and
+// the P_i -- a slice starts on a row boundary, so it is a panel of fewer rows and the flat kernels take it as one).  fs_pcgn's
+// launchers serve every step that takes per-column sums: pcgn_fold_kernel leaves them finished in U.send.  U.send == K.red: whole
+// panels, the scalar step of fs_mscg per column (mscgn_step_kernel, which reads K.red) follows at once.  Else U.send is the rank's
+// send slot, and the step comes with mscgn_dev_rank_step once the slots of all ranks are gathered.  The flat kernels do the pairs.
+// F rows (a slice: its own), ne = F k elements per panel; Ps: the direction panels of the shifts with sigma != 0, ldp doubles apart
+static int mscgn_scalar_step(MscgStep step, const PcgnSums &U, const MscgnScalars &K, int k, hipStream_t s)
 {
   const dim3 one(1), blk(kRedThreads);
-  if (step == kMscgStart)   hipLaunchKernelGGL(mscgn_step_kernel<kMscgStart>, one, blk, 0, s, U.send, U.st, K.cst, U.cs, K.ms, K.sl, k, K.m, K.tol, K.sh->sg);
-  else if (step == kMscgS1) hipLaunchKernelGGL(mscgn_step_kernel<kMscgS1>, one, blk, 0, s, U.send, U.st, K.cst, U.cs, K.ms, K.sl, k, K.m, K.tol, K.sh->sg);
-  else                      hipLaunchKernelGGL(mscgn_step_kernel<kMscgS2>, one, blk, 0, s, U.send, U.st, K.cst, U.cs, K.ms, K.sl, k, K.m, K.tol, K.sh->sg);
+  if (step == kMscgStart)   hipLaunchKernelGGL(mscgn_step_kernel<kMscgStart>, one, blk, 0, s, K.red, U.st, K.cst, U.cs, K.ms, K.sl, k, K.m, K.tol, K.sh->sg);
+  else if (step == kMscgS1) hipLaunchKernelGGL(mscgn_step_kernel<kMscgS1>, one, blk, 0, s, K.red, U.st, K.cst, U.cs, K.ms, K.sl, k, K.m, K.tol, K.sh->sg);
+  else                      hipLaunchKernelGGL(mscgn_step_kernel<kMscgS2>, one, blk, 0, s, K.red, U.st, K.cst, U.cs, K.ms, K.sl, k, K.m, K.tol, K.sh->sg);
   FS_HIP(hipGetLastError());
   return FS_OK;
 }
 
-// X_i = 0 for the K.m shifts, R = P = B, P_i = B for the shifts with sigma != 0; b.b per column, stop, every pair's scalars, live?
-static int mscgn_init(int F, int k, const double *B, double *X, long long ldx, double *R, double *P, double *Q, double *Ps, long long ldp,
-                      const PcgnSums &U, const MscgnState &K, hipStream_t s)
+// behind a step whose finished sums pcgn_fold_kernel left in U.send
+static int mscgn_finish_sums(MscgStep step, const PcgnSums &U, const MscgnScalars &K, int k, hipStream_t s)
+{
+  if (U.send == K.red) return mscgn_scalar_step(step, U, K, k, s);
+  FS_HIP(hipGetLastError());
+  return FS_OK;
+}
+
+// X_i = 0 for the K.m shifts, R = P = B, P_i = B for the shifts with sigma != 0; {b.b, r.r} per column: start
+int mscgn_dev_init(int F, int k, const double *B, double *X, long long ldx, double *R, double *P, double *Q, double *Ps, long long ldp,
+                   const PcgnSums &U, const MscgnScalars &K, hipStream_t s)
 {
   if (int rc = pcgn_init_step(F, k, pcgn_vec(k, X, B), false, 0.0, B, X, R, Q, U, K.tol, s)) return rc;   // X_0 = 0, R = B; {b.b, r.r}
-  if (int rc = mscgn_scalar_step(kMscgStart, U, K, k, s)) return rc;
+  if (int rc = mscgn_finish_sums(kMscgStart, U, K, k, s)) return rc;
   const size_t ne = (size_t)F * k;
   const dim3 g(kRedBlocks), blk(kRedThreads);
   if (k & 1) hipLaunchKernelGGL(mscgn_fill_kernel<false>, g, blk, 0, s, ne, B, P, Ps, (size_t)ldp, K.sh->nslots, X, (size_t)ldx, K.m);
@@ -2198,23 +2217,55 @@ static int mscgn_init(int F, int k, const double *B, double *X, long long ldx, d
   return FS_OK;
 }
 
-// everything of an iteration behind Q = A'(A P), all on the device
-static int mscgn_steps(int F, int k, double *X, long long ldx, double *R, double *P, double *Q, double *Ps, long long ldp, const PcgnSums &U,
-                       const MscgnState &K, hipStream_t s)
+// behind Q = A'(A P): Q += base P, q.p per live column: S1 (alpha_j, the a_ij).  R, P, Q are the solve's own: 16-byte forms for even k
+int mscgn_dev_shift_dot(int F, int k, double *Q, const double *P, const PcgnSums &U, const MscgnScalars &K, hipStream_t s)
 {
-  const int vec = (k & 1) ? 0 : 1;                           // R, P, Q are the solve's own
+  const int vec = (k & 1) ? 0 : 1;
+  if (int rc = pcgn_shift_dot_step(F, k, vec, K.sh->base, Q, P, U, s)) return rc;
+  return mscgn_finish_sums(kMscgS1, U, K, k, s);
+}
+
+// R -= alpha Q with r.r per live column, then x_ij += a_ij P_ij for the live pairs: S2 (converged?  beta_j, freezes)
+int mscgn_dev_update(int F, int k, double *X, long long ldx, double *R, const double *P, const double *Q, double *Ps, long long ldp,
+                     const PcgnSums &U, const MscgnScalars &K, hipStream_t s)
+{
   const size_t ne = (size_t)F * k;
   const dim3 g(kRedBlocks), blk(kRedThreads);
-  if (int rc = pcgn_shift_dot_step(F, k, vec, K.sh->base, Q, P, U, s)) return rc;                       // q += base p; q.p
-  if (int rc = mscgn_scalar_step(kMscgS1, U, K, k, s)) return rc;                                       // alpha_j, the a_ij
-  if (int rc = pcgn_update_step(F, k, vec, nullptr, R, P, Q, nullptr, U, s)) return rc;                 // r -= alpha q; r.r
+  const int vec = (k & 1) ? 0 : 1;
+  if (int rc = pcgn_update_step(F, k, vec, nullptr, R, P, Q, nullptr, U, s)) return rc;
   if (k & 1) hipLaunchKernelGGL(mscgn_update_kernel<false>, g, blk, 0, s, ne, k, X, (size_t)ldx, P, Ps, (size_t)ldp, U.st, K.ms, K.sl);
   else       hipLaunchKernelGGL(mscgn_update_kernel<true>, g, blk, 0, s, ne, k, X, (size_t)ldx, P, Ps, (size_t)ldp, U.st, K.ms, K.sl);
-  if (int rc = mscgn_scalar_step(kMscgS2, U, K, k, s)) return rc;                                       // converged? beta_j, freezes
+  return mscgn_finish_sums(kMscgS2, U, K, k, s);
+}
+
+// the new P and the new P_ij of the live pairs
+int mscgn_dev_direction(int F, int k, double *P, const double *R, double *Ps, long long ldp, const PcgnSums &U, const MscgnScalars &K,
+                        hipStream_t s)
+{
+  const size_t ne = (size_t)F * k;
+  const dim3 g(kRedBlocks), blk(kRedThreads);
   if (k & 1) hipLaunchKernelGGL(mscgn_direction_kernel<false>, g, blk, 0, s, ne, k, P, R, Ps, (size_t)ldp, U.st, K.cst, K.ms, K.sl);
   else       hipLaunchKernelGGL(mscgn_direction_kernel<true>, g, blk, 0, s, ne, k, P, R, Ps, (size_t)ldp, U.st, K.cst, K.ms, K.sl);
   FS_HIP(hipGetLastError());
   return FS_OK;
+}
+
+// everything of an iteration behind Q = A'(A P) on whole panels, all on the device
+int mscgn_dev_steps(int F, int k, double *X, long long ldx, double *R, double *P, double *Q, double *Ps, long long ldp, const PcgnSums &U,
+                    const MscgnScalars &K, hipStream_t s)
+{
+  if (int rc = mscgn_dev_shift_dot(F, k, Q, P, U, K, s)) return rc;
+  if (int rc = mscgn_dev_update(F, k, X, ldx, R, P, Q, Ps, ldp, U, K, s)) return rc;
+  return mscgn_dev_direction(F, k, P, R, Ps, ldp, U, K, s);
+}
+
+// the send slots of every rank, gathered (`all`: rank r's ns * k values at r * ns * k; ns = 2 for the start, else 1): each sum
+// over the ranks in rank order into K.red -- pcgn_step_kernel<STEP, true>'s fold -- then the scalar step, on every rank over the
+// same values
+int mscgn_dev_rank_step(MscgStep step, const double *all, int nranks, int k, const PcgnSums &U, const MscgnScalars &K, hipStream_t s)
+{
+  pcgn_fold_launch(all, nranks, K.red, U.st, k, step == kMscgStart ? 2 : 1, step == kMscgStart, s);
+  return mscgn_scalar_step(step, U, K, k, s);
 }
 
 // ---- the same for two right-hand sides (fs_cg2, fs_dist_cg2).  cg2_dev_init is synchronous (two reductions go to the host: the
@@ -2336,7 +2387,7 @@ void mscg_note_state(const double *fin, const double *fms, int m, fs_pcg_info *i
 
 // the end of an fs_mscgn solve on the host: fcst = the k columns' final st[], fms = their final ms[] (both kept for
 // fs_debug_last_mscgn_state); info: m * k entries, info[i * k + j], or NULL
-static void mscgn_note_state(const double *fcst, const double *fms, int k, int m, fs_pcg_info *info)
+void mscgn_note_state(const double *fcst, const double *fms, int k, int m, fs_pcg_info *info)
 {
   g_last_mscgn_cst.assign(fcst, fcst + (size_t)k * kStDoubles);
   g_last_mscgn_ms.assign(fms, fms + (size_t)k * kMscgStateDoubles);
@@ -2846,9 +2897,9 @@ int fs_mscgn(fs_matrix_t A, fs_matrix_t At, double *X, int64_t ldx, const double
   double *ms = cst + (size_t)kPcgnMaxRhs * kStDoubles, *sl = ms + kMscgnStateDoubles;
   FS_HIP(hipMemsetAsync(red, 0, sizeof(double) * nscal, s));  // slots a column never writes read as 0 in the debug getter
   const PcgnSums U{part, f.st, cs, red};
-  const MscgnState K{cst, ms, sl, m, tol, &sh};
-  if (int rc = mscgn_init(F, k, B, X, (long long)ldx, f.r, f.p, f.q, Ps, ldp, U, K, s)) return rc;
-  if (int rc = f.iterate(cap, true, [&] { return mscgn_steps(F, k, X, (long long)ldx, f.r, f.p, f.q, Ps, ldp, U, K, s); })) return rc;
+  const MscgnScalars K{red, cst, ms, sl, m, tol, &sh};
+  if (int rc = mscgn_dev_init(F, k, B, X, (long long)ldx, f.r, f.p, f.q, Ps, ldp, U, K, s)) return rc;
+  if (int rc = f.iterate(cap, true, [&] { return mscgn_dev_steps(F, k, X, (long long)ldx, f.r, f.p, f.q, Ps, ldp, U, K, s); })) return rc;
   std::vector<double> fcst((size_t)k * kStDoubles), fms((size_t)k * kMscgStateDoubles);
   FS_HIP(hipMemcpyAsync(fcst.data(), cst, sizeof(double) * fcst.size(), hipMemcpyDeviceToHost, s));
   FS_HIP(hipMemcpyAsync(fms.data(), ms, sizeof(double) * fms.size(), hipMemcpyDeviceToHost, s));

@@ -468,6 +468,26 @@ int mscg_dev_final(MscgStep step, const double *partials, int count, double *red
 bool mscg_same_outcome(const double *ms_a, const double *ms_b, int m);           // {live, converged, count} of every shift agree
 // the final st[] and ms[] (m shifts) on the host: kept for the debug getters, info (m entries or NULL) filled
 void mscg_note_state(const double *st_host, const double *ms_host, int m, fs_pcg_info *info);
+// ---- fs_mscgn's steps on row-major n x k panels (fs_mscgn; fs_dist_mscgn on every rank, on whole panels or on the rank's slice: F
+// rows of R, Q, P, the X_i ldx apart and the P_i of the shifts with sigma != 0 ldp apart).  The per-column sums are fs_pcgn's (U as
+// above, U.send always set: the sums land there finished).  red: kPcgnSendDoubles doubles the scalar steps read; U.send == red: whole
+// panels, a launcher takes the scalar step behind its sums.  Else U.send is the rank's send slot: the slots of all ranks, gathered
+// rank-major, go through mscgn_dev_rank_step, which adds each sum in rank order into red and takes the step.  cst: a st[] per column
+// (FS_PCGN_MAX_RHS * kCgStateDoubles), ms: kMscgnStateDoubles, sl: kMscgnListDoubles
+struct MscgnScalars { double *red, *cst, *ms, *sl; int m; double tol; const MscgShifts *sh; };
+int mscgn_dev_init(int F, int k, const double *B, double *X, long long ldx, double *R, double *P, double *Q, double *Ps, long long ldp,
+                   const PcgnSums &U, const MscgnScalars &K, hipStream_t s);     // X_i = 0, R = P = P_i = B; {b.b, r.r}: start
+int mscgn_dev_shift_dot(int F, int k, double *Q, const double *P, const PcgnSums &U, const MscgnScalars &K, hipStream_t s);   // Q += base P; q.p: S1
+int mscgn_dev_update(int F, int k, double *X, long long ldx, double *R, const double *P, const double *Q, double *Ps, long long ldp,
+                     const PcgnSums &U, const MscgnScalars &K, hipStream_t s);   // R, r.r, then the live x_ij: S2
+int mscgn_dev_direction(int F, int k, double *P, const double *R, double *Ps, long long ldp, const PcgnSums &U, const MscgnScalars &K,
+                        hipStream_t s);
+// everything of an iteration behind Q = A'(A P) on whole panels: shift_dot, update, direction
+int mscgn_dev_steps(int F, int k, double *X, long long ldx, double *R, double *P, double *Q, double *Ps, long long ldp, const PcgnSums &U,
+                    const MscgnScalars &K, hipStream_t s);
+int mscgn_dev_rank_step(MscgStep step, const double *all, int nranks, int k, const PcgnSums &U, const MscgnScalars &K, hipStream_t s);
+// the k columns' final st[] and ms[] on the host: kept for fs_debug_last_mscgn_state, info (m * k entries, info[i * k + j], or NULL) filled
+void mscgn_note_state(const double *cst_host, const double *ms_host, int k, int m, fs_pcg_info *info);
 // the final st[] of a solve, kCgStateDoubles doubles copied back to the host: kept for the calling thread (fs_debug_last_cg_state)
 void note_cg_state(const double *st_host);
 // the host's view of a running solve: {done, iterations} of the two most recent iterations, in pinned memory

@@ -313,6 +313,19 @@ struct MsWork {
   std::vector<double *> X, P, ms;
 };
 
+// fs_dist_mscgn's own panels, kept like CgWork: the X_i (X, room for m of them) and the direction panels P_i of the shifts with
+// sigma != 0 (P, room for nslots), whole F x k panels or the rank's rows of A' of them, ld doubles apart (ld even); red: the
+// finished sums the scalar steps read, cst / ms / sl: every column's st[] and ms[] and the per-shift list -- one allocation, `red`
+// first, cleared at the start of a solve.  R, B, Q, the partials, the send slots and st are PnWork's
+struct MnWork {
+  int F = 0, m = 0, nslots = 0;
+  long long ld = 0;
+  RankBuffers mem;
+  std::vector<double *> X, P, red;
+};
+constexpr size_t kMnCstDoubles = (size_t)FS_PCGN_MAX_RHS * fs::kCgStateDoubles;
+constexpr size_t kMnScalarDoubles = (size_t)fs::kPcgnSendDoubles + kMnCstDoubles + fs::kMscgnStateDoubles + fs::kMscgnListDoubles;
+
 // k row-major columns on the sharded matrix (fs_dist_spmm, fs_dist_cg2): the replicated X / Y / Z, the shards' local outputs, the
 // padded receive buffer (one, for both sides), the unpack tables and the work vectors of the block solver, per rank; one plan per
 // side, its cuts from fs_spmm_part_rows (the one-sweep plan of k = 2, 4 is cut like the single-vector pair)
@@ -344,6 +357,7 @@ struct fs_dist_matrix_s {
   CgWork cg;
   PnWork pn;
   MsWork ms;
+  MnWork mn;
   KWork kw;
   std::mutex lock;                    // products on one matrix are serialised (x, y, z and the part buffers are per matrix)
 };
@@ -366,6 +380,7 @@ void free_cg(fs_dist_t D, CgWork &W) { W.mem.release(D); W = CgWork(); }
 void free_k(fs_dist_t D, KWork &W) { W.mem.release(D); W = KWork(); }
 void free_pn(fs_dist_t D, PnWork &W) { W.mem.release(D); W = PnWork(); }
 void free_ms(fs_dist_t D, MsWork &W) { W.mem.release(D); W = MsWork(); }
+void free_mn(fs_dist_t D, MnWork &W) { W.mem.release(D); W = MnWork(); }
 
 // row cuts with (almost) equal numbers of non-zeros: bounds[r] = first row whose row_ptr is >= r/n of nnz -- the cut
 // libfastsparse_amd/dist.py nnz_balanced_partition makes, essential for power-law matrices (BASELINE config 5)
@@ -1025,6 +1040,7 @@ void fs_dist_matrix_destroy(fs_dist_matrix_t M)
   free_cg(M->D, M->cg);
   free_pn(M->D, M->pn);
   free_ms(M->D, M->ms);
+  free_mn(M->D, M->mn);
   free_k(M->D, M->kw);
   for (size_t r = 0; r < (size_t)M->D->n; ++r) {
     (void)hipSetDevice(M->D->dev[r]);
@@ -1460,7 +1476,8 @@ int fs_dist_swap_xy(fs_dist_matrix_t M)
   return FS_OK;
 }
 
-// ---- the CG solvers on the row-sharded matrix: fs_dist_cg, fs_dist_pcg, fs_dist_pcgn, fs_dist_pcgn_lambdas, fs_dist_mscg, fs_dist_cg2 -----
+// ---- the CG solvers on the row-sharded matrix: fs_dist_cg, fs_dist_pcg, fs_dist_pcgn, fs_dist_pcgn_lambdas, fs_dist_mscg, fs_dist_mscgn,
+// fs_dist_cg2 ----
 // Everything of a solve is resident and the scalars of the iteration live on the devices (fs_cg.hip's launchers); per iteration
 // y = A p and q = A' y.  EVERY rank decides convergence for itself and the host compares the flags of all of them one iteration
 // behind: a disagreement (which identical arithmetic rules out, and a faulty device or exchange does not) is an error return,
@@ -1468,7 +1485,7 @@ int fs_dist_swap_xy(fs_dist_matrix_t M)
 // 0.  Work vectors are kept on the handle between solves.  A solve CLOBBERS fs_dist_x / fs_dist_y / fs_dist_z of the handle and
 // writes the caller's x once, at the end: whatever fails before leaves it as it was.
 //
-// DistSolve is the host frame the six share, the counterpart of CgSolve in fs_cg.hip: open() (the transpose is there, both
+// DistSolve is the host frame the seven share, the counterpart of CgSolve in fs_cg.hip: open() (the transpose is there, both
 // locks, the caller's device kept, fixed-order products, one set of host-visible flags per rank), stage() (the caller's vectors
 // onto the ranks), iterate() and finish() (settle(): the agreed final state; then store(): x to the caller).  A solver brings its argument checks,
 // its work space (st: every rank's st[]), its start and what an iteration enqueues.
@@ -2257,6 +2274,182 @@ int fs_dist_mscg(fs_dist_matrix_t M, double *X, int64_t ldx, const double *b, in
     if (int rc = f.store(X + (size_t)i * (size_t)ldx, S.X, (size_t)i * (size_t)ld, (size_t)F, gather)) return rc;
   if (int rc = dist_sync(D)) return rc;
   fs::mscg_note_state(f.st0, ms0, m, info);
+  return FS_OK;
+}
+
+// fs_dist_mscgn's panels on the handle: room for m X_i and nslots P_i of ld doubles each and the scalars, per rank.  Kept between
+// solves; re-made when a solve needs more panels or longer ones than they hold
+static int ensure_mn_work(fs_dist_matrix_t M, int m, int nslots, long long ld)
+{
+  fs_dist_t D = M->D;
+  MnWork &W = M->mn;
+  if (W.mem.ready && W.F == M->ncol && W.m >= m && W.nslots >= nslots && W.ld >= ld) return FS_OK;
+  if (int rc = dist_sync(D)) return rc;
+  free_mn(D, W);
+  W.F = M->ncol; W.m = m; W.nslots = nslots; W.ld = ld;
+  return W.mem.fill(D, [&](int d) -> int {
+    if (int rc2 = W.mem.get(d, W.X, (size_t)ld * (size_t)m)) return rc2;
+    if (int rc2 = W.mem.get(d, W.P, (size_t)ld * (size_t)(nslots ? nslots : 1))) return rc2;
+    return W.mem.get(d, W.red, kMnScalarDoubles);
+  });
+}
+
+// Scheme "gather" for fs_dist_mscgn: PnSliceSums' exchange with fs_mscgn's scalar step behind it.  A slice step leaves a rank's ns
+// sums per column in send(d); combine() all-gathers them and every rank takes mscgn_dev_rank_step over the same values
+struct MnSliceSums {
+  fs_dist_matrix_t M;
+  int k;
+  int slot = 0;
+  double *send(int d) const { return M->pn.send[(size_t)d] + fs::kPcgnSendDoubles * slot; }
+  // where rank d's launchers leave their sums: on slices in the send slot, on whole panels where the scalar steps read them
+  fs::PcgnSums of(int d, bool gather) const
+  {
+    const PnWork &W = M->pn;
+    return fs::PcgnSums{W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], gather ? send(d) : M->mn.red[(size_t)d]};
+  }
+  int combine(fs::MscgStep step, const std::function<fs::MscgnScalars(int)> &scalars_of)
+  {
+    fs_dist_t D = M->D;
+    const int n = D->n, ns = step == fs::kMscgStart ? 2 : 1;
+    PnWork &W = M->pn;
+    DistSide &T = M->t;
+    std::vector<const double *> from((size_t)n);
+    std::vector<hipEvent_t> ready((size_t)n);
+    if (int rc = each_rank(D, false, [&](int d) -> int {
+          from[(size_t)d] = send(d);
+          FS_HIP(hipEventRecord(T.ev[(size_t)d][0], D->stream[d]));
+          ready[(size_t)d] = T.ev[(size_t)d][0];
+          return FS_OK;
+        })) return rc;
+    if (int rc = exchange_equal(D, from, W.all, (size_t)ns * (size_t)k, D->stream, ready)) return rc;
+    if (int rc = each_rank(D, false, [&](int d) {
+          return fs::mscgn_dev_rank_step(step, W.all[(size_t)d], n, k, of(d, true), scalars_of(d), D->stream[d]);
+        })) return rc;
+    slot ^= 1;
+    return FS_OK;
+  }
+};
+
+// fs_mscgn across the ranks; the schemes are fs_dist_mscg's (option "dist_cg_scheme"):
+//   0 "replicate"  every rank holds whole panels R, P, Q, the m X_i and the P_i and launches fs_mscgn's own steps on them
+//                  (mscgn_dev_*): T = A P and Q = A' T are the sharded k-column products, no exchange for the sums.
+//   1 "gather"     rank r keeps its rows of A' of R, Q, every X_i and every P_i; P and T = A P stay whole, the rank's slice of P is
+//                  the k-column exchange's own send buffer.  The X_i and P_i never leave their rank: only P enters a product.
+//                  Q_r = A'_r T is the rank's own shard product; q.p and r.r are the slice tree of fs_dist_cg per column
+//                  (MnSliceSums), the scalar steps run on every rank over the gathered values; the new P is gathered.  The first P
+//                  is B, which every rank holds whole after staging.
+// The caller's X is written once, at the end, after every rank's {done, iterations}, mask of live columns and per-pair
+// {live, converged, count} agreed.
+int fs_dist_mscgn(fs_dist_matrix_t M, double *X, int64_t ldx, const double *B, int k, int m, const double *lambda, double tol, int max_iter,
+                  fs_pcg_info *info)
+{
+  if (!M || !X || !B || !lambda) { fs::set_error("fs_dist_mscgn: NULL argument"); return FS_ERR_ARG; }
+  if (k < 1 || k > FS_PCGN_MAX_RHS) { fs::set_error("fs_dist_mscgn: k outside 1..FS_PCGN_MAX_RHS"); return FS_ERR_ARG; }
+  if (ldx < (int64_t)M->ncol * k) { fs::set_error("fs_dist_mscgn: ldx < ncol * k"); return FS_ERR_ARG; }
+  if (int rc = fs::mscg_args_ok("fs_dist_mscgn", 0, ldx, m, lambda, tol)) return rc;     // (ldx is settled above)
+  DistSolve f{"fs_dist_mscgn", M};
+  if (int rc = f.open("call fs_dist_matrix_build_transpose first")) return rc;
+  fs_dist_t D = f.D;
+  const int F = f.F, n = f.n;
+  const bool gather = fs::options().dist_cg_scheme == 1 && n > 1;
+  const fs::MscgShifts sh = fs::mscg_shifts(m, lambda);
+  const int cap = max_iter > 0 ? max_iter : F;               // cg.h:55
+  DistSide &T = M->t;
+  auto lo_of = [&](int d) { return gather ? T.bounds[(size_t)d] : 0; };
+  auto rows_of = [&](int d) { return gather ? T.bounds[(size_t)d + 1] - T.bounds[(size_t)d] : F; };
+  int longest = 1;                                           // of the panels a rank keeps: every X_i and P_i 16-byte aligned
+  for (int d = 0; d < n; ++d) longest = std::max(longest, rows_of(d));
+  if (k > 1)
+    if (int rc = ensure_k(M, k)) return rc;
+  if (int rc = ensure_pn_work(M, k, gather)) return rc;
+  if (int rc = ensure_mn_work(M, m, sh.nslots, ((long long)longest * k + 1) & ~1LL)) return rc;
+  PnWork &W = M->pn;
+  MnWork &S = M->mn;
+  const long long ld = S.ld;
+  f.st = &W.st;
+  // the product vectors: P (replicated input of A), T = A P, Q = A' T (whole panels: scheme 0 only)
+  const std::vector<double *> &vp = k > 1 ? M->kw.x : M->x, &vt = k > 1 ? M->kw.y : M->y, &vz = k > 1 ? M->kw.z : M->z;
+  // the slice of P: the local output buffer of the A' side, which no product of scheme 1 writes -- the gather's own source
+  const Exchange gp = exchange_of(M, true, k);
+  const std::vector<double *> &dp = gather ? gp.local : vp, &dq = gather ? W.q : vz;
+  auto scalars_of = [&](int d) {
+    double *red = S.red[(size_t)d], *cst = red + fs::kPcgnSendDoubles, *ms = cst + kMnCstDoubles;
+    return fs::MscgnScalars{red, cst, ms, ms + fs::kMscgnStateDoubles, m, tol, &sh};
+  };
+  MnSliceSums sums{M, k};
+  if (int rc = f.stage(gather ? vp : W.b, B, (size_t)F * k)) return rc;     // slices: the whole B is the first P, where the product reads it
+  if (int rc = each_rank(D, false, [&](int d) -> int {
+        if (int rc2 = fs::pcgn_dev_clear(W.cs[(size_t)d], D->stream[d])) return rc2;
+        FS_HIP(hipMemsetAsync(S.red[(size_t)d], 0, sizeof(double) * kMnScalarDoubles, D->stream[d]));   // unwritten slots read as 0 in the debug getter
+        if (gather && rows_of(d) > 0)
+          FS_HIP(hipMemcpyAsync(W.b[(size_t)d], vp[(size_t)d] + (size_t)lo_of(d) * k, sizeof(double) * (size_t)rows_of(d) * k,
+                                hipMemcpyDeviceToDevice, D->stream[d]));
+        return fs::mscgn_dev_init(rows_of(d), k, W.b[(size_t)d], S.X[(size_t)d], ld, W.r[(size_t)d], dp[(size_t)d], dq[(size_t)d], S.P[(size_t)d], ld,
+                                  sums.of(d, gather), scalars_of(d), D->stream[d]);
+      })) return rc;
+  if (gather)
+    if (int rc = sums.combine(fs::kMscgStart, scalars_of)) return rc;        // b.b, r.r per column: stop, every pair's scalars, live?
+  if (!gather) {
+    if (int rc = f.iterate(cap, true, [&]() -> int {
+          if (int rc2 = dist_product(M, false, k, vp, vt)) return rc2;       // T = A P
+          return dist_product(M, true, k, vt, vz);                           // Q = A' T
+        }, [&](int d) {
+          return fs::mscgn_dev_steps(F, k, S.X[(size_t)d], ld, W.r[(size_t)d], vp[(size_t)d], vz[(size_t)d], S.P[(size_t)d], ld, sums.of(d, false),
+                                     scalars_of(d), D->stream[d]);
+        })) return rc;
+  } else {
+    if (int rc = f.iterate(cap, true, [&]() -> int {
+          if (int rc2 = dist_product(M, false, k, vp, vt)) return rc2;       // T = A P
+          if (int rc2 = each_rank(D, false, [&](int d) -> int {              // Q_r = A'_r T: the rank's own shard product
+                if (rows_of(d) > 0)
+                  if (int rc3 = k == 1 ? fs_spmv(T.shard[(size_t)d], dq[(size_t)d], vt[(size_t)d], D->stream[d])
+                                       : fs_spmm(T.shard[(size_t)d], dq[(size_t)d], vt[(size_t)d], k, D->stream[d])) return rc3;
+                return fs::mscgn_dev_shift_dot(rows_of(d), k, dq[(size_t)d], dp[(size_t)d], sums.of(d, true), scalars_of(d), D->stream[d]);
+              })) return rc2;
+          if (int rc2 = sums.combine(fs::kMscgS1, scalars_of)) return rc2;   // alpha_j, the a_ij
+          if (int rc2 = each_rank(D, false, [&](int d) {
+                return fs::mscgn_dev_update(rows_of(d), k, S.X[(size_t)d], ld, W.r[(size_t)d], dp[(size_t)d], dq[(size_t)d], S.P[(size_t)d], ld,
+                                            sums.of(d, true), scalars_of(d), D->stream[d]);
+              })) return rc2;
+          if (int rc2 = sums.combine(fs::kMscgS2, scalars_of)) return rc2;   // converged?  beta_j, freezes
+          if (int rc2 = each_rank(D, false, [&](int d) {
+                return fs::mscgn_dev_direction(rows_of(d), k, dp[(size_t)d], W.r[(size_t)d], S.P[(size_t)d], ld, sums.of(d, true), scalars_of(d),
+                                               D->stream[d]);
+              })) return rc2;
+          return run_gather(D, gp, dp, vp, false);                           // the new P on every rank
+        }, [](int) { return FS_OK; })) return rc;
+  }
+  if (int rc = f.settle()) return rc;
+  // every rank froze every column and every pair at the same iteration in the same way: rank 0's arrays speak for all
+  std::vector<double> cst0((size_t)k * fs::kCgStateDoubles), ms0((size_t)k * fs::kMscgStateDoubles), cstd(cst0.size()), msd(ms0.size());
+  double mask0 = 0.0;
+  if (int rc = each_rank(D, false, [&](int d) -> int {
+        const fs::MscgnScalars K = scalars_of(d);
+        double std_[fs::kCgStateDoubles];
+        FS_HIP(hipMemcpy(d == 0 ? cst0.data() : cstd.data(), K.cst, sizeof(double) * cst0.size(), hipMemcpyDeviceToHost));
+        FS_HIP(hipMemcpy(d == 0 ? ms0.data() : msd.data(), K.ms, sizeof(double) * ms0.size(), hipMemcpyDeviceToHost));
+        FS_HIP(hipMemcpy(std_, W.st[(size_t)d], sizeof(std_), hipMemcpyDeviceToHost));
+        if (d == 0) { mask0 = std_[fs::kCgStateLiveMask]; return FS_OK; }
+        bool same = std_[fs::kCgStateLiveMask] == mask0;
+        for (int j = 0; j < k; ++j)
+          same = same && cstd[(size_t)j * fs::kCgStateDoubles + fs::kCgStateDone] == cst0[(size_t)j * fs::kCgStateDoubles + fs::kCgStateDone] &&
+                 fs::mscg_same_outcome(msd.data() + (size_t)j * fs::kMscgStateDoubles, ms0.data() + (size_t)j * fs::kMscgStateDoubles, m);
+        if (!same) {
+          fs::set_error("fs_dist_mscgn: the devices froze the pairs differently (a device or an exchange returned different bits)");
+          return FS_ERR_HIP;
+        }
+        return FS_OK;
+      })) return rc;
+  if (vector_device(X) >= 0)
+    if (int rc = wait_for_caller(vector_device(X))) return rc;
+  for (int i = 0; i < m; ++i) {
+    double *xi = X + (size_t)i * (size_t)ldx;
+    for (int d = 0; d < (gather ? n : 1); ++d)
+      if (rows_of(d) > 0)
+        if (int rc = vec_store(M, d, xi + (size_t)lo_of(d) * k, S.X[(size_t)d] + (size_t)i * (size_t)ld, (size_t)rows_of(d) * k)) return rc;
+  }
+  if (int rc = dist_sync(D)) return rc;
+  fs::mscgn_note_state(cst0.data(), ms0.data(), k, m, info);
   return FS_OK;
 }
 
