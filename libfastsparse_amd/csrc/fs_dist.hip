@@ -304,24 +304,18 @@ struct PnWork {
   std::vector<double *> q, send, all;
 };
 
-// fs_dist_mscg's own vectors, kept like CgWork: the x_i (X, room for m of them) and the directions P_i of the shifts with sigma != 0
-// (P, room for nslots), whole or the rank's slice, ld doubles apart; ms: the per-shift array.  r, b, p, q and the sums are CgWork's
-struct MsWork {
+// A ladder solver's own vectors, kept like CgWork: the x_i (X, room for m of them) and the directions P_i of the shifts with
+// sigma != 0 (P, room for nslots), whole or the rank's slice, ld doubles apart (ld even); sc: the solver's scalars.  The handle
+// keeps one for each ladder solver, so interleaved solves of the two leave each other's vectors alone:
+//   ms  fs_dist_mscg's: vectors of F doubles; sc is the per-shift array.  r, b, p, q and the sums are CgWork's
+//   mn  fs_dist_mscgn's: F x k panels or the rank's rows of A' of them; sc holds the finished sums the scalar steps read, then
+//       cst / ms / sl: every column's st[] and ms[] and the per-shift list -- one allocation, cleared at the start of a solve.
+//       R, B, Q, the partials, the send slots and st are PnWork's
+struct LadderWork {
   int F = 0, m = 0, nslots = 0;
   long long ld = 0;
   RankBuffers mem;
-  std::vector<double *> X, P, ms;
-};
-
-// fs_dist_mscgn's own panels, kept like CgWork: the X_i (X, room for m of them) and the direction panels P_i of the shifts with
-// sigma != 0 (P, room for nslots), whole F x k panels or the rank's rows of A' of them, ld doubles apart (ld even); red: the
-// finished sums the scalar steps read, cst / ms / sl: every column's st[] and ms[] and the per-shift list -- one allocation, `red`
-// first, cleared at the start of a solve.  R, B, Q, the partials, the send slots and st are PnWork's
-struct MnWork {
-  int F = 0, m = 0, nslots = 0;
-  long long ld = 0;
-  RankBuffers mem;
-  std::vector<double *> X, P, red;
+  std::vector<double *> X, P, sc;
 };
 constexpr size_t kMnCstDoubles = (size_t)FS_PCGN_MAX_RHS * fs::kCgStateDoubles;
 constexpr size_t kMnScalarDoubles = (size_t)fs::kPcgnSendDoubles + kMnCstDoubles + fs::kMscgnStateDoubles + fs::kMscgnListDoubles;
@@ -356,8 +350,7 @@ struct fs_dist_matrix_s {
   size_t pin_doubles = 0;
   CgWork cg;
   PnWork pn;
-  MsWork ms;
-  MnWork mn;
+  LadderWork ms, mn;
   KWork kw;
   std::mutex lock;                    // products on one matrix are serialised (x, y, z and the part buffers are per matrix)
 };
@@ -376,11 +369,9 @@ void free_side(fs_dist_t D, DistSide &S)
   S = DistSide();
 }
 
-void free_cg(fs_dist_t D, CgWork &W) { W.mem.release(D); W = CgWork(); }
-void free_k(fs_dist_t D, KWork &W) { W.mem.release(D); W = KWork(); }
-void free_pn(fs_dist_t D, PnWork &W) { W.mem.release(D); W = PnWork(); }
-void free_ms(fs_dist_t D, MsWork &W) { W.mem.release(D); W = MsWork(); }
-void free_mn(fs_dist_t D, MnWork &W) { W.mem.release(D); W = MnWork(); }
+// a work space of the handle (CgWork, PnWork, LadderWork, KWork) back to its empty state
+template <typename Work>
+void free_work(fs_dist_t D, Work &W) { W.mem.release(D); W = Work(); }
 
 // row cuts with (almost) equal numbers of non-zeros: bounds[r] = first row whose row_ptr is >= r/n of nnz -- the cut
 // libfastsparse_amd/dist.py nnz_balanced_partition makes, essential for power-law matrices (BASELINE config 5)
@@ -863,7 +854,7 @@ int ensure_k(fs_dist_matrix_t M, int k)
   const bool with_t = M->t.built;
   if (W.mem.ready && W.k == k && W.with_t == with_t && W.epoch == fs::option_epoch()) return FS_OK;
   if (int rc = dist_sync(D)) return rc;
-  free_k(D, W);
+  free_work(D, W);
   W.k = k; W.with_t = with_t; W.epoch = fs::option_epoch();
   // the k-column copies of the shards first (fs_spmm itself never builds): the parts below belong to the plan they leave
   for (int r = 0; r < n; ++r) {
@@ -1037,11 +1028,11 @@ void fs_dist_matrix_destroy(fs_dist_matrix_t M)
   if (!M) return;
   DeviceGuard guard;
   (void)dist_sync(M->D);
-  free_cg(M->D, M->cg);
-  free_pn(M->D, M->pn);
-  free_ms(M->D, M->ms);
-  free_mn(M->D, M->mn);
-  free_k(M->D, M->kw);
+  free_work(M->D, M->cg);
+  free_work(M->D, M->pn);
+  free_work(M->D, M->ms);
+  free_work(M->D, M->mn);
+  free_work(M->D, M->kw);
   for (size_t r = 0; r < (size_t)M->D->n; ++r) {
     (void)hipSetDevice(M->D->dev[r]);
     if (r < M->x.size() && M->x[r]) (void)hipFree(M->x[r]);
@@ -1486,10 +1477,37 @@ int fs_dist_swap_xy(fs_dist_matrix_t M)
 // writes the caller's x once, at the end: whatever fails before leaves it as it was.
 //
 // DistSolve is the host frame the seven share, the counterpart of CgSolve in fs_cg.hip: open() (the transpose is there, both
-// locks, the caller's device kept, fixed-order products, one set of host-visible flags per rank), stage() (the caller's vectors
-// onto the ranks), iterate() and finish() (settle(): the agreed final state; then store(): x to the caller).  A solver brings its argument checks,
-// its work space (st: every rank's st[]), its start and what an iteration enqueues.
+// locks, the caller's device kept, fixed-order products, one set of host-visible flags per rank), slices() (the scheme: what
+// lo(), rows(), longest(), shard_product(), take_slices() and store() answer with), stage() (the caller's vectors onto the
+// ranks), iterate() and finish() (settle(): the agreed final state; agree(): whatever else the solver's ranks must have in
+// common; then store(): X to the caller).  A solver brings its argument checks, its work space (st: every rank's st[]; dinv:
+// every rank's inverse diagonal, where it has a preconditioner), its start and what an iteration enqueues.
 enum { kRanksGoOn = 0, kRanksStopped = 1, kRanksDisagree = 2 };
+
+// T = A P, then Q = A' T: the pair of sharded k-column products (k = 1: the single-vector ones) every solver is built on
+static int dist_pair(fs_dist_matrix_t M, int k, const std::vector<double *> &p, const std::vector<double *> &t, const std::vector<double *> &q)
+{
+  if (int rc = dist_product(M, false, k, p, t)) return rc;
+  return dist_product(M, true, k, t, q);
+}
+
+// the product vectors of the handle for k columns (x / y / z, or KWork's for k > 1, which ensure_k made): P (replicated input of
+// A), T = A P, Q = A' T
+struct ProductVectors { const std::vector<double *> &p, &t, &q; };
+static ProductVectors product_vectors(fs_dist_matrix_t M, int k)
+{
+  return k > 1 ? ProductVectors{M->kw.x, M->kw.y, M->kw.z} : ProductVectors{M->x, M->y, M->z};
+}
+
+// What a solver's ranks must have in common at the end beside {done, iterations}: on every rank d, count doubles at on[d] + at
+struct Outcome { const std::vector<double *> &on; size_t at, count; };
+struct Agreement {
+  std::vector<Outcome> what;                                   // fetched one behind the other into one host array per rank
+  std::function<bool(const double *, const double *)> same;    // (rank d's array, rank 0's)
+  const char *differ;                                          // the error text
+  std::vector<double> first;                                   // afterwards: rank 0's array, which speaks for all
+};
+
 struct DistSolve {
   const char *who;
   fs_dist_matrix_t M;
@@ -1499,7 +1517,8 @@ struct DistSolve {
   DeviceGuard guard;
   fs::FixedOrderScope fixed{fs::options().cg_fixed_order != 0};
   std::vector<fs::CgFlags> fl = std::vector<fs::CgFlags>((size_t)n);
-  const std::vector<double *> *st = nullptr;
+  const std::vector<double *> *st = nullptr, *dinv = nullptr;
+  bool sliced = false;
   int staged = 0;
   int seen = kRanksGoOn;                                   // what the ranks' flags said last: go on, all stopped, or only some did
   int iterations = 0;                                      // after finish(): the agreed count, and rank 0's final st[]
@@ -1511,6 +1530,34 @@ struct DistSolve {
     matrix_lock.lock();
     context_lock.lock();
     return each_rank(D, false, [&](int d) { return fl[(size_t)d].init(); });
+  }
+  // The scheme: a rank works on whole vectors (rows [0, F) on every rank), or (scheme "gather") on its slice -- the rows of A' it
+  // owns.  longest(): of the vectors a rank keeps, at least 1
+  void slices(bool gather) { sliced = gather; }
+  int lo(int d) const { return sliced ? M->t.bounds[(size_t)d] : 0; }
+  int rows(int d) const { return sliced ? M->t.bounds[(size_t)d + 1] - M->t.bounds[(size_t)d] : F; }
+  int longest() const
+  {
+    int longest = 1;
+    for (int d = 0; d < n; ++d) longest = std::max(longest, rows(d));
+    return longest;
+  }
+  const double *dinv_of(int d) const { return dinv ? (*dinv)[(size_t)d] : nullptr; }
+  // q_r = A'_r t on rank d (slices): the rank's own shard product, no exchange; an empty slice has none
+  int shard_product(int d, int k, double *q, const double *t)
+  {
+    if (rows(d) <= 0) return FS_OK;
+    return k == 1 ? fs_spmv(M->t.shard[(size_t)d], q, t, D->stream[d]) : fs_spmm(M->t.shard[(size_t)d], q, t, k, D->stream[d]);
+  }
+  // every rank's slice of a whole k-column panel that was staged in `whole`
+  int take_slices(const std::vector<double *> &dst, const std::vector<double *> &whole, int k)
+  {
+    return each_rank(D, false, [&](int d) -> int {
+      if (rows(d) > 0)
+        FS_HIP(hipMemcpyAsync(dst[(size_t)d], whole[(size_t)d] + (size_t)lo(d) * k, sizeof(double) * (size_t)rows(d) * k,
+                              hipMemcpyDeviceToDevice, D->stream[d]));
+      return FS_OK;
+    });
   }
   // `count` doubles of the caller's (host memory or HBM) into own[r] on every rank: always a copy, they are read all solve long.
   // A second and third vector of one call wait for the uploads of the one before, which still read the pinned staging buffer
@@ -1543,8 +1590,9 @@ struct DistSolve {
     return FS_OK;
   }
   // up to cap iterations, as long as the ranks go on: products() (whatever spans the ranks), then rank by rank in one pass
-  // steps(d), the rank's flags on their way to the host and a look at those of the iteration before.  look_first: see look()
-  int iterate(int cap, bool look_first, const std::function<int()> &products, const std::function<int(int)> &steps)
+  // steps(d) (none on slices: their steps span the ranks), the rank's flags on their way to the host and a look at those of the
+  // iteration before.  look_first: see look()
+  int iterate(int cap, bool look_first, const std::function<int()> &products, const std::function<int(int)> &steps = nullptr)
   {
     if (look_first)
       if (int rc = look()) return rc;
@@ -1553,7 +1601,8 @@ struct DistSolve {
       int stops = 0;
       if (int rc = each_rank(D, false, [&](int d) -> int {
             bool stop = false;
-            if (int rc2 = steps(d)) return rc2;
+            if (steps)
+              if (int rc2 = steps(d)) return rc2;
             if (int rc2 = fl[(size_t)d].after_iteration(iter, (*st)[(size_t)d], D->stream[d], &stop)) return rc2;
             stops += stop ? 1 : 0;
             return FS_OK;
@@ -1584,24 +1633,40 @@ struct DistSolve {
     iterations = (int)fin0[1];
     return FS_OK;
   }
-  // one vector to the caller, asynchronously: count doubles from rank 0's sol + at, or (slices) every rank's rows of A' from its own
-  int store(double *x, const std::vector<double *> &sol, size_t at, size_t count, bool slices)
+  // every rank's array of outcomes against rank 0's
+  int agree(Agreement &a)
   {
-    if (!slices) return vec_store(M, 0, x, sol[0] + at, count);
-    for (int d = 0; d < n; ++d) {
-      const int lo = M->t.bounds[(size_t)d], rows = M->t.bounds[(size_t)d + 1] - lo;
-      if (rows > 0)
-        if (int rc = vec_store(M, d, x + lo, sol[(size_t)d] + at, (size_t)rows)) return rc;
-    }
+    std::vector<double> other;
+    return each_rank(D, false, [&](int d) -> int {
+      std::vector<double> &mine = d == 0 ? a.first : other;
+      mine.clear();
+      for (const Outcome &o : a.what) {
+        mine.resize(mine.size() + o.count);
+        FS_HIP(hipMemcpy(mine.data() + mine.size() - o.count, o.on[(size_t)d] + o.at, sizeof(double) * o.count, hipMemcpyDeviceToHost));
+      }
+      if (d > 0 && !a.same(other.data(), a.first.data())) { fs::set_error(a.differ); return FS_ERR_HIP; }
+      return FS_OK;
+    });
+  }
+  // m vectors of k columns to the caller, asynchronously, ld doubles apart on the rank and ldx at the caller: whole from rank 0, or
+  // (slices) every rank's rows of A' from its own
+  int store(double *x, const std::vector<double *> &sol, int k, int m, size_t ld, size_t ldx)
+  {
+    for (int i = 0; i < m; ++i)
+      for (int d = 0; d < (sliced ? n : 1); ++d)
+        if (rows(d) > 0)
+          if (int rc = vec_store(M, d, x + (size_t)i * ldx + (size_t)lo(d) * k, sol[(size_t)d] + (size_t)i * ld, (size_t)rows(d) * k)) return rc;
     return FS_OK;
   }
-  // the agreed final state, then x
-  int finish(double *x, const std::vector<double *> &sol, size_t count, bool slices = false)
+  // The end of a solve: the agreed final state; what else the solver wants agreed; then, and only then, X to the caller
+  int finish(double *x, const std::vector<double *> &sol, int k = 1, Agreement *also = nullptr, int m = 1, size_t ld = 0, size_t ldx = 0)
   {
     if (int rc = settle()) return rc;
+    if (also)
+      if (int rc = agree(*also)) return rc;
     if (vector_device(x) >= 0)
       if (int rc = wait_for_caller(vector_device(x))) return rc;
-    if (int rc = store(x, sol, 0, count, slices)) return rc;
+    if (int rc = store(x, sol, k, m, ld, ldx)) return rc;
     return dist_sync(D);
   }
 };
@@ -1614,7 +1679,7 @@ static int ensure_cg_work(fs_dist_matrix_t M)
   const int n = D->n, F = M->ncol;
   CgWork &W = M->cg;
   if (W.mem.ready && W.F == F) return FS_OK;
-  free_cg(D, W);
+  free_work(D, W);
   W.F = F;
   const size_t fl = (size_t)(F ? F : 1) + (size_t)M->t.plan.max_rows + 1;
   return W.mem.fill(D, [&](int d) -> int {
@@ -1628,86 +1693,88 @@ static int ensure_cg_work(fs_dist_matrix_t M)
 }
 
 // Scheme "gather": the sums over the ranks.  A partial reduction leaves a rank's nv sums (1, or 2 that fs_pcg takes in one pass)
-// in send(d); combine() all-gathers them, nv doubles per rank, every rank adds each sum over the ranks in rank order (stage 2's
-// tree) and does the scalar step `step`.  The two send slots alternate: a rank may be one exchange ahead of another that still
-// reads its previous partial; the scalar step leaves its sums behind the slots.
+// in send(d); combine() all-gathers them, `count` doubles per rank (nv, or ns per column of a k-column solver: ns * k), and every
+// rank takes its scalar step over the gathered values, which adds each sum over the ranks in rank order (stage 2's tree).  The
+// two send slots, `stride` doubles apart in slots[d], alternate: a rank may be one exchange ahead of another that still reads its
+// previous partial.  The one exchange of sums of every solver: CgWork's (red, redall) or PnWork's (send, all) buffers
 struct SliceSums {
   fs_dist_matrix_t M;
+  const std::vector<double *> &slots, &all;
+  int stride;
   int slot = 0;
-  double *send(int d) const { return M->cg.red[(size_t)d] + kCgSendDoubles * slot; }
-  // where rank d's launchers leave their sums: scheme "gather" in the send slot, scheme "replicate" (whole vectors) finished
-  fs::CgSums of(int d, bool gather) const
-  {
-    const CgWork &W = M->cg;
-    return fs::CgSums{W.part[(size_t)d], W.red[(size_t)d], W.st[(size_t)d], gather ? send(d) : nullptr};
-  }
-  int combine(fs::CgStep step, double arg, int nv)
-  {
-    const int n = M->D->n;
-    return combine(nv, [&](int d, const double *all, double *red_out) {
-      return fs::cg_dev_final(step, all, n, red_out, M->cg.st[(size_t)d], arg, M->D->stream[d], nv);
-    });
-  }
-  // final(d, the n x nv gathered values on rank d, where the finished sums go): the scalar step of rank d
-  int combine(int nv, const std::function<int(int, const double *, double *)> &final)
+  double *send(int d) const { return slots[(size_t)d] + stride * slot; }
+  // step(d, the gathered values on rank d, rank-major): the scalar step of rank d
+  int combine(size_t count, const std::function<int(int, const double *)> &step)
   {
     fs_dist_t D = M->D;
-    const int n = D->n;
-    CgWork &W = M->cg;
     DistSide &T = M->t;
-    std::vector<const double *> from((size_t)n);
-    std::vector<hipEvent_t> ready((size_t)n);
+    std::vector<const double *> from((size_t)D->n);
+    std::vector<hipEvent_t> ready((size_t)D->n);
     if (int rc = each_rank(D, false, [&](int d) -> int {
           from[(size_t)d] = send(d);
           FS_HIP(hipEventRecord(T.ev[(size_t)d][0], D->stream[d]));
           ready[(size_t)d] = T.ev[(size_t)d][0];
           return FS_OK;
         })) return rc;
-    if (int rc = exchange_equal(D, from, W.redall, (size_t)nv, D->stream, ready)) return rc;
-    if (int rc = each_rank(D, false, [&](int d) { return final(d, W.redall[(size_t)d], W.red[(size_t)d] + 2 * kCgSendDoubles); })) return rc;
+    if (int rc = exchange_equal(D, from, all, count, D->stream, ready)) return rc;
+    if (int rc = each_rank(D, false, [&](int d) { return step(d, all[(size_t)d]); })) return rc;
     slot ^= 1;
     return FS_OK;
   }
 };
 
-// the iterations of fs_dist_cg and fs_dist_pcg, which differ in the preconditioner (`pre`: rank d's is cg.dinv[d]) and in the
+// CgWork's sums (fs_dist_cg, fs_dist_pcg, fs_dist_mscg): where rank d's launchers leave theirs -- in `send`, the rank's send slot
+// (scheme "gather"), or finished (nullptr: whole vectors) -- and where the scalar step behind an exchange leaves the finished
+// sums: behind the two slots
+static fs::CgSums cg_sums(const CgWork &W, int d, double *send)
+{
+  return fs::CgSums{W.part[(size_t)d], W.red[(size_t)d], W.st[(size_t)d], send};
+}
+static double *cg_finished_sums(const CgWork &W, int d) { return W.red[(size_t)d] + 2 * kCgSendDoubles; }
+static int cg_combine(SliceSums &sums, fs::CgStep step, double arg, int nv)
+{
+  fs_dist_matrix_t M = sums.M;
+  return sums.combine((size_t)nv, [&](int d, const double *all) {
+    return fs::cg_dev_final(step, all, M->D->n, cg_finished_sums(M->cg, d), M->cg.st[(size_t)d], arg, M->D->stream[d], nv);
+  });
+}
+// PnWork's sums (the k-column solvers)
+static fs::PcgnSums pn_sums(const PnWork &W, int d, double *send)
+{
+  return fs::PcgnSums{W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], send};
+}
+
+// the iterations of fs_dist_cg and fs_dist_pcg, which differ in the preconditioner (f.dinv: rank d's is cg.dinv[d]) and in the
 // convergence step `beta`.  Scheme "replicate": both products carry their all-gather, every rank runs the whole-vector steps.
 // Scheme "gather": q_r = A'_r y is the rank's own rows of A', no exchange; the slice steps with their sums combined over the
 // ranks; the new p slice all-gathered for the next product
-static int cg_iterations(DistSolve &f, SliceSums &sums, bool gather, int cap, double lambda, bool pre, fs::CgStep beta)
+static int cg_iterations(DistSolve &f, SliceSums &sums, int cap, double lambda, fs::CgStep beta)
 {
   fs_dist_matrix_t M = f.M;
   fs_dist_t D = f.D;
-  DistSide &T = M->t;
   CgWork &W = M->cg;
-  auto dinv_of = [&](int d) -> const double * { return pre ? W.dinv[(size_t)d] : nullptr; };
-  auto rows_of = [&T](int d) { return T.bounds[(size_t)d + 1] - T.bounds[(size_t)d]; };
-  if (!gather)
-    return f.iterate(cap, false, [&]() -> int {
-      if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;       // y = A p
-      return dist_product(M, true, 1, M->y, M->z);                         // q = A' y
-    }, [&](int d) {
-      return fs::cg_dev_steps(f.F, lambda, W.sol[(size_t)d], W.r[(size_t)d], M->x[(size_t)d], M->z[(size_t)d], dinv_of(d), sums.of(d, false),
-                              beta, D->stream[d]);
+  if (!f.sliced)
+    return f.iterate(cap, false, [&] { return dist_pair(M, 1, M->x, M->y, M->z); }, [&](int d) {      // y = A p, q = A' y
+      return fs::cg_dev_steps(f.F, lambda, W.sol[(size_t)d], W.r[(size_t)d], M->x[(size_t)d], M->z[(size_t)d], f.dinv_of(d),
+                              cg_sums(W, d, nullptr), beta, D->stream[d]);
     });
   return f.iterate(cap, false, [&]() -> int {
     if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;         // y = A p
     if (int rc = each_rank(D, false, [&](int d) -> int {
-          if (rows_of(d) > 0)
-            if (int rc2 = fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], M->y[(size_t)d], D->stream[d])) return rc2;
-          return fs::cg_dev_shift_dot(rows_of(d), lambda, W.p[(size_t)d], W.q[(size_t)d], sums.of(d, true), D->stream[d]);
+          if (int rc2 = f.shard_product(d, 1, W.q[(size_t)d], M->y[(size_t)d])) return rc2;
+          return fs::cg_dev_shift_dot(f.rows(d), lambda, W.p[(size_t)d], W.q[(size_t)d], cg_sums(W, d, sums.send(d)), D->stream[d]);
         })) return rc;
-    if (int rc = sums.combine(fs::kStepCgAlpha, 0.0, 1)) return rc;        // alpha
+    if (int rc = cg_combine(sums, fs::kStepCgAlpha, 0.0, 1)) return rc;    // alpha
     if (int rc = each_rank(D, false, [&](int d) {
-          return fs::cg_dev_update(rows_of(d), W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.q[(size_t)d], dinv_of(d), sums.of(d, true),
-                                   beta, D->stream[d]);
+          return fs::cg_dev_update(f.rows(d), W.sol[(size_t)d], W.r[(size_t)d], W.p[(size_t)d], W.q[(size_t)d], f.dinv_of(d),
+                                   cg_sums(W, d, sums.send(d)), beta, D->stream[d]);
         })) return rc;
-    if (int rc = sums.combine(beta, 0.0, pre ? 2 : 1)) return rc;          // converged?  beta
+    if (int rc = cg_combine(sums, beta, 0.0, f.dinv ? 2 : 1)) return rc;   // converged?  beta
     if (int rc = each_rank(D, false, [&](int d) {
-          return fs::cg_dev_direction(rows_of(d), W.p[(size_t)d], W.r[(size_t)d], dinv_of(d), W.st[(size_t)d], D->stream[d]);
+          return fs::cg_dev_direction(f.rows(d), W.p[(size_t)d], W.r[(size_t)d], f.dinv_of(d), W.st[(size_t)d], D->stream[d]);
         })) return rc;
     return run_gather(D, exchange_of(M, true, 1), W.p, M->x, false);       // the new p on every rank
-  }, [](int) { return FS_OK; });
+  });
 }
 
 // (A'A + lambda I) x = b on the row-sharded matrix: bsbm_cg (cg.h:25-82) across the GPUs.  Two schemes for everything but
@@ -1728,23 +1795,22 @@ int fs_dist_cg(fs_dist_matrix_t M, double *x_host, const double *b_host, double 
   fs_dist_t D = f.D;
   const int F = f.F;
   const bool gather = fs::options().dist_cg_scheme == 1 && f.n > 1;
-  DistSide &T = M->t;
+  f.slices(gather);
   CgWork &W = M->cg;
   if (int rc = ensure_cg_work(M)) return rc;
   f.st = &W.st;
   if (int rc = f.stage(W.b, b_host, (size_t)F)) return rc;
-  SliceSums sums{M};
+  SliceSums sums{M, W.red, W.redall, kCgSendDoubles};
   if (int rc = each_rank(D, false, [&](int d) {                          // cg_init_kernel writes p itself: whole into x, or the slice
-        const int lo = gather ? T.bounds[(size_t)d] : 0, rows = gather ? T.bounds[(size_t)d + 1] - lo : F;
-        return fs::cg_dev_init(rows, W.b[(size_t)d] + lo, W.sol[(size_t)d], W.r[(size_t)d], (gather ? W.p : M->x)[(size_t)d], sums.of(d, gather),
-                               tol, D->stream[d]);
+        return fs::cg_dev_init(f.rows(d), W.b[(size_t)d] + f.lo(d), W.sol[(size_t)d], W.r[(size_t)d], (gather ? W.p : M->x)[(size_t)d],
+                               cg_sums(W, d, gather ? sums.send(d) : nullptr), tol, D->stream[d]);
       })) return rc;
   if (gather) {
-    if (int rc = sums.combine(fs::kStepCgStart, tol, 1)) return rc;
+    if (int rc = cg_combine(sums, fs::kStepCgStart, tol, 1)) return rc;
     if (int rc = run_gather(D, exchange_of(M, true, 1), W.p, M->x, false)) return rc;     // the whole p on every rank
   }
-  if (int rc = cg_iterations(f, sums, gather, F, lambda, false, fs::kStepCgBeta)) return rc;
-  if (int rc = f.finish(x_host, W.sol, (size_t)F, gather)) return rc;
+  if (int rc = cg_iterations(f, sums, F, lambda, fs::kStepCgBeta)) return rc;
+  if (int rc = f.finish(x_host, W.sol)) return rc;
   if (out_iter) *out_iter = f.iterations;
   return FS_OK;
 }
@@ -1816,62 +1882,52 @@ int fs_dist_pcg(fs_dist_matrix_t M, double *x, const double *b, double lambda, c
   const bool gather = fs::options().dist_cg_scheme == 1 && f.n > 1;
   const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
   const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
-  DistSide &T = M->t;
+  f.slices(gather);
   CgWork &W = M->cg;
   if (int rc = ensure_cg_work(M)) return rc;
   f.st = &W.st;
+  f.dinv = pre ? &W.dinv : nullptr;
   // a rank works on whole vectors or on its slice; q and p are the handle's z and x (whole) or the rank's slice buffers, and d is
   // staged in the vector that holds q later
   const std::vector<double *> &vq = gather ? W.q : M->z, &vp = gather ? W.p : M->x;
-  auto lo_of = [&](int d) { return gather ? T.bounds[(size_t)d] : 0; };
-  auto rows_of = [&](int d) { return gather ? T.bounds[(size_t)d + 1] - T.bounds[(size_t)d] : F; };
-  auto dinv_of = [&](int d) -> const double * { return pre ? W.dinv[(size_t)d] : nullptr; };
   if (int rc = f.stage(W.b, b, (size_t)F)) return rc;
   if (warm)                                                                      // x0, whole, on every rank
     if (int rc = f.stage(gather ? M->x : W.sol, x, (size_t)F)) return rc;
   if (prm->precond == FS_PRECOND_DIAG)
     if (int rc = f.stage(vq, prm->diag, (size_t)F)) return rc;
-  SliceSums sums{M};
+  SliceSums sums{M, W.red, W.redall, kCgSendDoubles};
   if (prm->precond == FS_PRECOND_JACOBI)                                         // whole: one gather of d; else the rank's own rows
     if (int rc = gather ? gram_diag_slices(M, lambda, vq) : gram_diag_everywhere(M, lambda, vq)) return rc;
   if (pre)
     if (int rc = each_rank(D, false, [&](int d) {                               // (a staged d is whole, Jacobi's is the slice)
-          const double *dd = vq[(size_t)d] + (prm->precond == FS_PRECOND_DIAG ? lo_of(d) : 0);
-          return fs::pcg_dev_dinv(rows_of(d), dd, W.dinv[(size_t)d], D->stream[d]);
+          const double *dd = vq[(size_t)d] + (prm->precond == FS_PRECOND_DIAG ? f.lo(d) : 0);
+          return fs::pcg_dev_dinv(f.rows(d), dd, W.dinv[(size_t)d], D->stream[d]);
         })) return rc;
-  if (warm && !gather) {                                                         // q = A'(A x0)
-    if (int rc = dist_product(M, false, 1, W.sol, M->y)) return rc;
-    if (int rc = dist_product(M, true, 1, M->y, M->z)) return rc;
-  }
+  if (warm && !gather)                                                           // q = A'(A x0)
+    if (int rc = dist_pair(M, 1, W.sol, M->y, M->z)) return rc;
   if (warm && gather) {                                                          // the rank's slice of x0; q_r = A'_r (A x0)
-    if (int rc = each_rank(D, false, [&](int d) -> int {
-          if (rows_of(d) > 0)
-            FS_HIP(hipMemcpyAsync(W.sol[(size_t)d], M->x[(size_t)d] + lo_of(d), sizeof(double) * (size_t)rows_of(d), hipMemcpyDeviceToDevice, D->stream[d]));
-          return FS_OK;
-        })) return rc;
+    if (int rc = f.take_slices(W.sol, M->x, 1)) return rc;
     if (int rc = dist_product(M, false, 1, M->x, M->y)) return rc;
-    if (int rc = each_rank(D, false, [&](int d) -> int {
-          return rows_of(d) > 0 ? fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], M->y[(size_t)d], D->stream[d]) : FS_OK;
-        })) return rc;
+    if (int rc = each_rank(D, false, [&](int d) { return f.shard_product(d, 1, W.q[(size_t)d], M->y[(size_t)d]); })) return rc;
   }
   // b.b, r.r, stop, done?  then p = z, r.z.  Whole vectors: a rank's two steps in one pass; slices: each with its sums combined
   if (int rc = each_rank(D, false, [&](int d) -> int {
-        if (int rc2 = fs::pcg_dev_init(rows_of(d), warm, lambda, W.b[(size_t)d] + lo_of(d), W.sol[(size_t)d], W.r[(size_t)d], vq[(size_t)d],
-                                       sums.of(d, gather), prm->tol, D->stream[d])) return rc2;
-        return gather ? FS_OK : fs::pcg_dev_start(F, W.r[(size_t)d], dinv_of(d), vp[(size_t)d], sums.of(d, false), D->stream[d]);
+        if (int rc2 = fs::pcg_dev_init(f.rows(d), warm, lambda, W.b[(size_t)d] + f.lo(d), W.sol[(size_t)d], W.r[(size_t)d], vq[(size_t)d],
+                                       cg_sums(W, d, gather ? sums.send(d) : nullptr), prm->tol, D->stream[d])) return rc2;
+        return gather ? FS_OK : fs::pcg_dev_start(F, W.r[(size_t)d], f.dinv_of(d), vp[(size_t)d], cg_sums(W, d, nullptr), D->stream[d]);
       })) return rc;
   if (gather) {
-    if (int rc = sums.combine(fs::kStepPcgStart, prm->tol, 2)) return rc;
+    if (int rc = cg_combine(sums, fs::kStepPcgStart, prm->tol, 2)) return rc;
     if (int rc = each_rank(D, false, [&](int d) {
-          return fs::pcg_dev_start(rows_of(d), W.r[(size_t)d], dinv_of(d), vp[(size_t)d], sums.of(d, true), D->stream[d]);
+          return fs::pcg_dev_start(f.rows(d), W.r[(size_t)d], f.dinv_of(d), vp[(size_t)d], cg_sums(W, d, sums.send(d)), D->stream[d]);
         })) return rc;
-    if (int rc = sums.combine(fs::kStepPcgRz, 0.0, 1)) return rc;
+    if (int rc = cg_combine(sums, fs::kStepPcgRz, 0.0, 1)) return rc;
   }
   if (int rc = f.look()) return rc;                          // done before the first iteration: no product is enqueued
   if (gather && f.seen == kRanksGoOn)
     if (int rc = run_gather(D, exchange_of(M, true, 1), W.p, M->x, false)) return rc;     // the whole p on every rank
-  if (int rc = cg_iterations(f, sums, gather, cap, lambda, pre, fs::kStepPcgBeta)) return rc;
-  if (int rc = f.finish(x, W.sol, (size_t)F, gather)) return rc;
+  if (int rc = cg_iterations(f, sums, cap, lambda, fs::kStepPcgBeta)) return rc;
+  if (int rc = f.finish(x, W.sol)) return rc;
   fs::pcg_info_of(f.st0, info);
   return FS_OK;
 }
@@ -1885,7 +1941,7 @@ static int ensure_pn_work(fs_dist_matrix_t M, int k, bool slices)
   PnWork &W = M->pn;
   if (W.mem.ready && W.F == F && W.k == k && W.slices == slices) return FS_OK;
   if (int rc = dist_sync(D)) return rc;
-  free_pn(D, W);
+  free_work(D, W);
   W.F = F; W.k = k; W.slices = slices;
   return W.mem.fill(D, [&](int d) -> int {
     const size_t rows = slices ? (size_t)(M->t.bounds[(size_t)d + 1] - M->t.bounds[(size_t)d]) : (size_t)F;
@@ -1904,6 +1960,29 @@ static int ensure_pn_work(fs_dist_matrix_t M, int k, bool slices)
   });
 }
 
+// The replicated k-column frame of fs_dist_pcgn and of scheme 0 of fs_dist_pcgn_lambdas, from staging to the last iteration: every
+// rank holds the whole F x k panels (PnWork; ensure_k and ensure_pn_work are done) and launches the solver's own instantiations
+// of fs_pcgn's kernels on them -- init(d), then steps(d) behind every pair of sharded k-column products.  fill_dinv(): what the
+// solver enqueues between staging and the warm start's products -- its diagonal (a caller's d is staged in Q's vector) into dinv
+static int pcgn_replicated(DistSolve &f, double *X, const double *B, int k, const fs_pcg_params *prm, const std::function<int()> &fill_dinv,
+                           const std::function<int(int)> &init, const std::function<int(int)> &steps)
+{
+  fs_dist_matrix_t M = f.M;
+  PnWork &W = M->pn;
+  const size_t F = (size_t)f.F;
+  const ProductVectors v = product_vectors(M, k);
+  if (int rc = f.stage(W.b, B, F * k)) return rc;
+  if (prm->warm_start)
+    if (int rc = f.stage(W.sol, X, F * k)) return rc;
+  if (prm->precond == FS_PRECOND_DIAG)
+    if (int rc = f.stage(v.q, prm->diag, F)) return rc;                            // (d is staged where Q lives later)
+  if (int rc = fill_dinv()) return rc;
+  if (prm->warm_start)                                       // Q = A'(A X0): one pair of k-column products
+    if (int rc = dist_pair(M, k, W.sol, v.t, v.q)) return rc;
+  if (int rc = each_rank(f.D, false, init)) return rc;
+  return f.iterate(prm->max_iter > 0 ? prm->max_iter : f.F /* cg.h:55 */, true, [&] { return dist_pair(M, k, v.p, v.t, v.q); }, steps);
+}
+
 // fs_pcgn across the ranks, replicated whatever "dist_cg_scheme" says: every rank holds the whole F x k panels and launches
 // fs_pcgn's own kernels on them (pcgn_dev_*); T = A P and Q = A' T are the sharded k-column products (k = 1: the single-vector
 // ones).
@@ -1919,41 +1998,28 @@ int fs_dist_pcgn(fs_dist_matrix_t M, double *X, const double *B, int k, double l
   fs_dist_t D = f.D;
   const int F = f.F;
   const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
-  const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
   if (k > 1)
     if (int rc = ensure_k(M, k)) return rc;
   PnWork &W = M->pn;
   if (int rc = ensure_pn_work(M, k, false)) return rc;
   f.st = &W.st;
-  // the product vectors: P (replicated input of A), T = A P, Q = A' T
-  const std::vector<double *> &vp = k > 1 ? M->kw.x : M->x, &vt = k > 1 ? M->kw.y : M->y, &vq = k > 1 ? M->kw.z : M->z;
-  auto dinv_of = [&](int d) -> const double * { return pre ? W.dinv[(size_t)d] : nullptr; };
-  if (int rc = f.stage(W.b, B, (size_t)F * k)) return rc;
-  if (warm)
-    if (int rc = f.stage(W.sol, X, (size_t)F * k)) return rc;
-  if (prm->precond == FS_PRECOND_DIAG)
-    if (int rc = f.stage(vq, prm->diag, (size_t)F)) return rc;                     // (d is staged where Q lives later)
-  if (int rc = each_rank(D, false, [&](int d) { return fs::pcgn_dev_clear(W.cs[(size_t)d], D->stream[d]); })) return rc;
-  if (prm->precond == FS_PRECOND_JACOBI)
-    if (int rc = gram_diag_everywhere(M, lambda, vq)) return rc;
-  if (pre)
-    if (int rc = each_rank(D, false, [&](int d) { return fs::pcg_dev_dinv(F, vq[(size_t)d], W.dinv[(size_t)d], D->stream[d]); })) return rc;
-  if (warm) {                                                // Q = A'(A X0): one pair of k-column products
-    if (int rc = dist_product(M, false, k, W.sol, vt)) return rc;
-    if (int rc = dist_product(M, true, k, vt, vq)) return rc;
-  }
-  if (int rc = each_rank(D, false, [&](int d) {
-        return fs::pcgn_dev_init(F, k, warm, lambda, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d], dinv_of(d),
-                                 W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], prm->tol, D->stream[d]);
-      })) return rc;
-  if (int rc = f.iterate(cap, true, [&]() -> int {
-        if (int rc2 = dist_product(M, false, k, vp, vt)) return rc2;       // T = A P
-        return dist_product(M, true, k, vt, vq);                           // Q = A' T
+  f.dinv = pre ? &W.dinv : nullptr;
+  const ProductVectors v = product_vectors(M, k);
+  // the column state cleared; Jacobi at lambda goes where a caller's d is staged, and either through the inverse pass
+  if (int rc = pcgn_replicated(f, X, B, k, prm, [&]() -> int {
+        if (int rc2 = each_rank(D, false, [&](int d) { return fs::pcgn_dev_clear(W.cs[(size_t)d], D->stream[d]); })) return rc2;
+        if (prm->precond == FS_PRECOND_JACOBI)
+          if (int rc2 = gram_diag_everywhere(M, lambda, v.q)) return rc2;
+        if (!pre) return FS_OK;
+        return each_rank(D, false, [&](int d) { return fs::pcg_dev_dinv(F, v.q[(size_t)d], W.dinv[(size_t)d], D->stream[d]); });
       }, [&](int d) {
-        return fs::pcgn_dev_steps(F, k, lambda, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d], dinv_of(d),
-                                  W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], D->stream[d]);
+        return fs::pcgn_dev_init(F, k, warm, lambda, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], v.p[(size_t)d], v.q[(size_t)d],
+                                 f.dinv_of(d), W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], prm->tol, D->stream[d]);
+      }, [&](int d) {
+        return fs::pcgn_dev_steps(F, k, lambda, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], v.p[(size_t)d], v.q[(size_t)d],
+                                  f.dinv_of(d), W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], D->stream[d]);
       })) return rc;
-  if (int rc = f.finish(X, W.sol, (size_t)F * k)) return rc;
+  if (int rc = f.finish(X, W.sol, k)) return rc;
   double cs0[fs::kPcgnStateDoubles] = {0.0};
   FS_HIP(hipSetDevice(D->dev[0]));
   FS_HIP(hipMemcpy(cs0, W.cs[0], sizeof(double) * (size_t)k * (fs::kPcgnStateDoubles / FS_PCGN_MAX_RHS), hipMemcpyDeviceToHost));
@@ -1961,49 +2027,15 @@ int fs_dist_pcgn(fs_dist_matrix_t M, double *X, const double *B, int k, double l
   return FS_OK;
 }
 
-// Scheme "gather" for k columns: the sums over the ranks.  A slice step leaves a rank's ns sums per column in send(d); combine()
-// all-gathers them, ns * k doubles per rank, and every rank adds each sum over the ranks in rank order (stage 2's tree) and takes
-// the scalar step of every column.  The two send slots alternate as SliceSums' do
-struct PnSliceSums {
-  fs_dist_matrix_t M;
-  int k;
-  int slot = 0;
-  double *send(int d) const { return M->pn.send[(size_t)d] + fs::kPcgnSendDoubles * slot; }
-  fs::PcgnSums of(int d) const
-  {
-    const PnWork &W = M->pn;
-    return fs::PcgnSums{W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], send(d)};
-  }
-  int combine(fs::PcgnStep step, int ns, double tol)
-  {
-    fs_dist_t D = M->D;
-    const int n = D->n;
-    PnWork &W = M->pn;
-    DistSide &T = M->t;
-    std::vector<const double *> from((size_t)n);
-    std::vector<hipEvent_t> ready((size_t)n);
-    if (int rc = each_rank(D, false, [&](int d) -> int {
-          from[(size_t)d] = send(d);
-          FS_HIP(hipEventRecord(T.ev[(size_t)d][0], D->stream[d]));
-          ready[(size_t)d] = T.ev[(size_t)d][0];
-          return FS_OK;
-        })) return rc;
-    if (int rc = exchange_equal(D, from, W.all, (size_t)ns * (size_t)k, D->stream, ready)) return rc;
-    if (int rc = each_rank(D, false, [&](int d) {
-          return fs::pcgn_dev_rank_step(step, W.all[(size_t)d], n, k, ns, tol, W.st[(size_t)d], W.cs[(size_t)d], D->stream[d]);
-        })) return rc;
-    slot ^= 1;
-    return FS_OK;
-  }
-};
-
 // fs_pcgn_lambdas across the ranks; the schemes are fs_dist_pcg's (option "dist_cg_scheme"):
-//   0 "replicate"  fs_dist_pcgn's frame with fs_pcgn_lambdas' instantiations of the kernels on whole panels.  Jacobi: the work
-//                  vector holds s = fs_gram_diag of A' at 0.0, gathered once; no inverse pass.
+//   0 "replicate"  fs_dist_pcgn's frame (pcgn_replicated) with fs_pcgn_lambdas' instantiations of the kernels on whole panels.
+//                  Jacobi: the work vector holds s = fs_gram_diag of A' at 0.0, gathered once; no inverse pass.
 //   1 "gather"     rank r keeps its rows of A' of X, R, B, Q and s / dinv; P and T = A P stay whole (the product's input and
 //                  output).  Q_r = A'_r T is the rank's own shard product: no exchange.  Every sum is the slice tree of fs_dist_cg
-//                  per column (PnSliceSums); the new P slices are all-gathered for the next product -- the first P too: it is
-//                  Z = R dinv, which only the owner of a row can form.
+//                  per column: a slice step leaves a rank's ns sums per column in its send slot, SliceSums::combine gathers them,
+//                  ns * k doubles per rank, and every rank takes the scalar step of every column over them (pcgn_dev_rank_step).
+//                  The new P slices are all-gathered for the next product -- the first P too: it is Z = R dinv, which only the
+//                  owner of a row can form.
 int fs_dist_pcgn_lambdas(fs_dist_matrix_t M, double *X, const double *B, int k, const double *lambda, const fs_pcg_params *prm,
                          fs_pcg_info *info)
 {
@@ -2025,155 +2057,110 @@ int fs_dist_pcgn_lambdas(fs_dist_matrix_t M, double *X, const double *B, int k, 
   const bool pre = prm->precond != FS_PRECOND_NONE, warm = prm->warm_start != 0;
   const bool colj = prm->precond == FS_PRECOND_JACOBI;       // the diagonal follows the column: dinv holds s
   const int cap = prm->max_iter > 0 ? prm->max_iter : F;     // cg.h:55
+  f.slices(gather);
   if (k > 1)
     if (int rc = ensure_k(M, k)) return rc;
   PnWork &W = M->pn;
   if (int rc = ensure_pn_work(M, k, gather)) return rc;
   f.st = &W.st;
-  DistSide &T = M->t;
-  // the product vectors: P (replicated input of A), T = A P, Q = A' T (whole panels: scheme 0 only)
-  const std::vector<double *> &vp = k > 1 ? M->kw.x : M->x, &vt = k > 1 ? M->kw.y : M->y, &vq = k > 1 ? M->kw.z : M->z;
-  auto dinv_of = [&](int d) -> const double * { return pre ? W.dinv[(size_t)d] : nullptr; };
-  auto lo_of = [&](int d) { return gather ? T.bounds[(size_t)d] : 0; };
-  auto rows_of = [&](int d) { return gather ? T.bounds[(size_t)d + 1] - T.bounds[(size_t)d] : F; };
-  // a rank's slice of a whole panel that was staged in `whole`
-  auto take_slice = [&](const std::vector<double *> &dst, const std::vector<double *> &whole) {
-    return each_rank(D, false, [&](int d) -> int {
-      if (rows_of(d) > 0)
-        FS_HIP(hipMemcpyAsync(dst[(size_t)d], whole[(size_t)d] + (size_t)lo_of(d) * k, sizeof(double) * (size_t)rows_of(d) * k,
-                              hipMemcpyDeviceToDevice, D->stream[d]));
-      return FS_OK;
-    });
-  };
+  f.dinv = pre ? &W.dinv : nullptr;
+  const ProductVectors v = product_vectors(M, k);              // (Q as a whole panel: scheme 0 only)
   if (int rc = each_rank(D, false, [&](int d) { return fs::pcgn_dev_clear(W.cs[(size_t)d], D->stream[d]); })) return rc;
   if (!gather) {
-    if (int rc = f.stage(W.b, B, (size_t)F * k)) return rc;
-    if (warm)
-      if (int rc = f.stage(W.sol, X, (size_t)F * k)) return rc;
-    if (prm->precond == FS_PRECOND_DIAG) {
-      if (int rc = f.stage(vq, prm->diag, (size_t)F)) return rc;                   // (d is staged where Q lives later)
-      if (int rc = each_rank(D, false, [&](int d) { return fs::pcg_dev_dinv(F, vq[(size_t)d], W.dinv[(size_t)d], D->stream[d]); })) return rc;
-    }
-    if (colj)
-      if (int rc = gram_diag_everywhere(M, 0.0, W.dinv)) return rc;
-    if (warm) {                                              // Q = A'(A X0): one pair of k-column products
-      if (int rc = dist_product(M, false, k, W.sol, vt)) return rc;
-      if (int rc = dist_product(M, true, k, vt, vq)) return rc;
-    }
-    if (int rc = each_rank(D, false, [&](int d) {
-          return fs::pcgn_dev_init_lambdas(F, k, warm, lv, colj, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d],
-                                           dinv_of(d), W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], prm->tol, D->stream[d]);
-        })) return rc;
-    if (int rc = f.iterate(cap, true, [&]() -> int {
-          if (int rc2 = dist_product(M, false, k, vp, vt)) return rc2;     // T = A P
-          return dist_product(M, true, k, vt, vq);                         // Q = A' T
+    // a caller's d through the inverse pass; Jacobi: s at 0.0, as it is
+    if (int rc = pcgn_replicated(f, X, B, k, prm, [&]() -> int {
+          if (prm->precond == FS_PRECOND_DIAG)
+            if (int rc2 = each_rank(D, false, [&](int d) { return fs::pcg_dev_dinv(F, v.q[(size_t)d], W.dinv[(size_t)d], D->stream[d]); })) return rc2;
+          return colj ? gram_diag_everywhere(M, 0.0, W.dinv) : FS_OK;
         }, [&](int d) {
-          return fs::pcgn_dev_steps_lambdas(F, k, lv, colj, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d],
-                                            dinv_of(d), W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], D->stream[d]);
+          return fs::pcgn_dev_init_lambdas(F, k, warm, lv, colj, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], v.p[(size_t)d], v.q[(size_t)d],
+                                           f.dinv_of(d), W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], prm->tol, D->stream[d]);
+        }, [&](int d) {
+          return fs::pcgn_dev_steps_lambdas(F, k, lv, colj, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], v.p[(size_t)d], v.q[(size_t)d],
+                                            f.dinv_of(d), W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], D->stream[d]);
         })) return rc;
-    if (int rc = f.settle()) return rc;
   } else {
     // the slice of P: the local output buffer of the A' side, which no product of this scheme writes -- the gather's own source
     const Exchange gp = exchange_of(M, true, k);
     const std::vector<double *> &ps = gp.local;
-    // Q_r = A'_r T: the rank's own shard product
-    auto shard_product = [&](int d) -> int {
-      if (rows_of(d) <= 0) return FS_OK;
-      return k == 1 ? fs_spmv(T.shard[(size_t)d], W.q[(size_t)d], vt[(size_t)d], D->stream[d])
-                    : fs_spmm(T.shard[(size_t)d], W.q[(size_t)d], vt[(size_t)d], k, D->stream[d]);
+    SliceSums sums{M, W.send, W.all, fs::kPcgnSendDoubles};
+    auto combine = [&](fs::PcgnStep step, int ns, double tol) {
+      return sums.combine((size_t)ns * (size_t)k, [&](int d, const double *all) {
+        return fs::pcgn_dev_rank_step(step, all, n, k, ns, tol, W.st[(size_t)d], W.cs[(size_t)d], D->stream[d]);
+      });
     };
-    PnSliceSums sums{M, k};
-    if (int rc = f.stage(vp, B, (size_t)F * k)) return rc;                         // whole panels pass through P on their way to the slices
-    if (int rc = take_slice(W.b, vp)) return rc;
+    if (int rc = f.stage(v.p, B, (size_t)F * k)) return rc;                        // whole panels pass through P on their way to the slices
+    if (int rc = f.take_slices(W.b, v.p, k)) return rc;
     if (prm->precond == FS_PRECOND_DIAG) {
-      if (int rc = f.stage(vq, prm->diag, (size_t)F)) return rc;                   // (whole, in the product vector this scheme leaves idle)
+      if (int rc = f.stage(v.q, prm->diag, (size_t)F)) return rc;                  // (whole, in the product vector this scheme leaves idle)
       if (int rc = each_rank(D, false, [&](int d) {
-            return fs::pcg_dev_dinv(rows_of(d), vq[(size_t)d] + lo_of(d), W.dinv[(size_t)d], D->stream[d]);
+            return fs::pcg_dev_dinv(f.rows(d), v.q[(size_t)d] + f.lo(d), W.dinv[(size_t)d], D->stream[d]);
           })) return rc;
     }
     if (colj)
       if (int rc = gram_diag_slices(M, 0.0, W.dinv)) return rc;                    // the rank's own rows: no exchange
     if (warm) {                                              // the whole X0 is the product's input; Q_r = A'_r (A X0)
-      if (int rc = f.stage(vp, X, (size_t)F * k)) return rc;
-      if (int rc = take_slice(W.sol, vp)) return rc;
-      if (int rc = dist_product(M, false, k, vp, vt)) return rc;
-      if (int rc = each_rank(D, false, shard_product)) return rc;
+      if (int rc = f.stage(v.p, X, (size_t)F * k)) return rc;
+      if (int rc = f.take_slices(W.sol, v.p, k)) return rc;
+      if (int rc = dist_product(M, false, k, v.p, v.t)) return rc;
+      if (int rc = each_rank(D, false, [&](int d) { return f.shard_product(d, k, W.q[(size_t)d], v.t[(size_t)d]); })) return rc;
     }
     if (int rc = each_rank(D, false, [&](int d) {
-          return fs::pcgn_slice_init(rows_of(d), k, warm, lv, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], W.q[(size_t)d], sums.of(d),
-                                     D->stream[d]);
+          return fs::pcgn_slice_init(f.rows(d), k, warm, lv, W.b[(size_t)d], W.sol[(size_t)d], W.r[(size_t)d], W.q[(size_t)d],
+                                     pn_sums(W, d, sums.send(d)), D->stream[d]);
         })) return rc;
-    if (int rc = sums.combine(fs::kPnStepStart, 2, prm->tol)) return rc;           // b.b, r.r, stop, live?
+    if (int rc = combine(fs::kPnStepStart, 2, prm->tol)) return rc;                // b.b, r.r, stop, live?
     if (int rc = each_rank(D, false, [&](int d) {
-          return fs::pcgn_slice_start(rows_of(d), k, lv, colj, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], dinv_of(d), ps[(size_t)d],
-                                      sums.of(d), D->stream[d]);
+          return fs::pcgn_slice_start(f.rows(d), k, lv, colj, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], f.dinv_of(d), ps[(size_t)d],
+                                      pn_sums(W, d, sums.send(d)), D->stream[d]);
         })) return rc;
-    if (int rc = sums.combine(fs::kPnStepRz, 1, 0.0)) return rc;                   // r.z
+    if (int rc = combine(fs::kPnStepRz, 1, 0.0)) return rc;                        // r.z
     if (int rc = f.look()) return rc;                        // done before the first iteration: no product is enqueued
     if (f.seen == kRanksGoOn)
-      if (int rc = run_gather(D, gp, ps, vp, false)) return rc;                    // the whole P on every rank
+      if (int rc = run_gather(D, gp, ps, v.p, false)) return rc;                   // the whole P on every rank
     if (int rc = f.iterate(cap, false, [&]() -> int {
-          if (int rc2 = dist_product(M, false, k, vp, vt)) return rc2;             // T = A P
+          if (int rc2 = dist_product(M, false, k, v.p, v.t)) return rc2;           // T = A P
           if (int rc2 = each_rank(D, false, [&](int d) -> int {
-                if (int rc3 = shard_product(d)) return rc3;
-                return fs::pcgn_slice_shift_dot(rows_of(d), k, lv, W.sol[(size_t)d], W.b[(size_t)d], W.q[(size_t)d], ps[(size_t)d], sums.of(d),
-                                                D->stream[d]);
+                if (int rc3 = f.shard_product(d, k, W.q[(size_t)d], v.t[(size_t)d])) return rc3;
+                return fs::pcgn_slice_shift_dot(f.rows(d), k, lv, W.sol[(size_t)d], W.b[(size_t)d], W.q[(size_t)d], ps[(size_t)d],
+                                                pn_sums(W, d, sums.send(d)), D->stream[d]);
               })) return rc2;
-          if (int rc2 = sums.combine(fs::kPnStepAlpha, 1, 0.0)) return rc2;        // alpha
+          if (int rc2 = combine(fs::kPnStepAlpha, 1, 0.0)) return rc2;             // alpha
           if (int rc2 = each_rank(D, false, [&](int d) {
-                return fs::pcgn_slice_update(rows_of(d), k, lv, colj, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], ps[(size_t)d],
-                                             W.q[(size_t)d], dinv_of(d), sums.of(d), D->stream[d]);
+                return fs::pcgn_slice_update(f.rows(d), k, lv, colj, W.sol[(size_t)d], W.b[(size_t)d], W.r[(size_t)d], ps[(size_t)d],
+                                             W.q[(size_t)d], f.dinv_of(d), pn_sums(W, d, sums.send(d)), D->stream[d]);
               })) return rc2;
-          if (int rc2 = sums.combine(fs::kPnStepBeta, pre ? 2 : 1, 0.0)) return rc2;   // converged?  beta
+          if (int rc2 = combine(fs::kPnStepBeta, pre ? 2 : 1, 0.0)) return rc2;    // converged?  beta
           if (int rc2 = each_rank(D, false, [&](int d) {
-                return fs::pcgn_slice_direction(rows_of(d), k, lv, colj, W.sol[(size_t)d], W.b[(size_t)d], ps[(size_t)d], W.r[(size_t)d],
-                                                dinv_of(d), sums.of(d), D->stream[d]);
+                return fs::pcgn_slice_direction(f.rows(d), k, lv, colj, W.sol[(size_t)d], W.b[(size_t)d], ps[(size_t)d], W.r[(size_t)d],
+                                                f.dinv_of(d), pn_sums(W, d, sums.send(d)), D->stream[d]);
               })) return rc2;
-          return run_gather(D, gp, ps, vp, false);                                 // the new P on every rank
-        }, [](int) { return FS_OK; })) return rc;
-    if (int rc = f.settle()) return rc;
+          return run_gather(D, gp, ps, v.p, false);                                // the new P on every rank
+        })) return rc;
   }
-  // every rank froze every column at the same iteration in the same way: rank 0's per-column array speaks for all
-  double cs0[fs::kPcgnStateDoubles] = {0.0}, mask0 = 0.0;
+  // every rank froze every column at the same iteration in the same way: the per-column array, then st[] for the live mask
   const size_t ncs = (size_t)k * (fs::kPcgnStateDoubles / FS_PCGN_MAX_RHS);
-  if (int rc = each_rank(D, false, [&](int d) -> int {
-        double csd[fs::kPcgnStateDoubles] = {0.0}, std_[fs::kCgStateDoubles];
-        FS_HIP(hipMemcpy(d == 0 ? cs0 : csd, W.cs[(size_t)d], sizeof(double) * ncs, hipMemcpyDeviceToHost));
-        FS_HIP(hipMemcpy(std_, W.st[(size_t)d], sizeof(std_), hipMemcpyDeviceToHost));
-        if (d == 0) mask0 = std_[fs::kCgStateLiveMask];
-        if (d > 0 && (std_[fs::kCgStateLiveMask] != mask0 || !fs::pcgn_same_outcome(csd, cs0, k))) {
-          fs::set_error("fs_dist_pcgn_lambdas: the devices froze the columns differently (a device or an exchange returned different bits)");
-          return FS_ERR_HIP;
-        }
-        return FS_OK;
-      })) return rc;
-  if (vector_device(X) >= 0)
-    if (int rc = wait_for_caller(vector_device(X))) return rc;
-  if (!gather) {
-    if (int rc = vec_store(M, 0, X, W.sol[0], (size_t)F * k)) return rc;
-  } else {
-    for (int d = 0; d < n; ++d)
-      if (int rc = vec_store(M, d, X + (size_t)lo_of(d) * k, W.sol[(size_t)d], (size_t)rows_of(d) * k)) return rc;
-  }
-  if (int rc = dist_sync(D)) return rc;
-  fs::pcgn_note_state(f.st0, cs0, k, info);
+  Agreement froze{{Outcome{W.cs, 0, ncs}, Outcome{W.st, 0, (size_t)fs::kCgStateDoubles}}, [&](const double *mine, const double *first) {
+    return mine[ncs + fs::kCgStateLiveMask] == first[ncs + fs::kCgStateLiveMask] && fs::pcgn_same_outcome(mine, first, k);
+  }, "fs_dist_pcgn_lambdas: the devices froze the columns differently (a device or an exchange returned different bits)", {}};
+  if (int rc = f.finish(X, W.sol, k, &froze)) return rc;
+  fs::pcgn_note_state(f.st0, froze.first.data(), k, info);
   return FS_OK;
 }
 
-// fs_dist_mscg's vectors on the handle: room for m x_i and nslots P_i of ld doubles each and the per-shift array, per rank.  Kept
-// between solves; re-made when a solve needs more vectors or a longer one than they hold
-static int ensure_ms_work(fs_dist_matrix_t M, int m, int nslots, long long ld)
+// A ladder solver's vectors on the handle (W: M->ms or M->mn): room for m x_i and nslots P_i of ld doubles each and `scalars`
+// doubles, per rank.  Kept between solves; re-made when a solve needs more vectors or longer ones than they hold
+static int ensure_ladder_work(fs_dist_matrix_t M, LadderWork &W, int m, int nslots, long long ld, size_t scalars)
 {
   fs_dist_t D = M->D;
-  MsWork &W = M->ms;
   if (W.mem.ready && W.F == M->ncol && W.m >= m && W.nslots >= nslots && W.ld >= ld) return FS_OK;
   if (int rc = dist_sync(D)) return rc;
-  free_ms(D, W);
+  free_work(D, W);
   W.F = M->ncol; W.m = m; W.nslots = nslots; W.ld = ld;
   return W.mem.fill(D, [&](int d) -> int {
     if (int rc2 = W.mem.get(d, W.X, (size_t)ld * (size_t)m)) return rc2;
     if (int rc2 = W.mem.get(d, W.P, (size_t)ld * (size_t)(nslots ? nslots : 1))) return rc2;
-    return W.mem.get(d, W.ms, (size_t)fs::kMscgStateDoubles);
+    return W.mem.get(d, W.sc, scalars);
   });
 }
 
@@ -2197,138 +2184,65 @@ int fs_dist_mscg(fs_dist_matrix_t M, double *X, int64_t ldx, const double *b, in
   const bool gather = fs::options().dist_cg_scheme == 1 && n > 1;
   const fs::MscgShifts sh = fs::mscg_shifts(m, lambda);
   const int cap = max_iter > 0 ? max_iter : F;               // cg.h:55
-  DistSide &T = M->t;
-  auto lo_of = [&](int d) { return gather ? T.bounds[(size_t)d] : 0; };
-  auto rows_of = [&](int d) { return gather ? T.bounds[(size_t)d + 1] - T.bounds[(size_t)d] : F; };
-  int longest = 1;                                           // of the vectors a rank keeps: every x_i and P_i 16-byte aligned
-  for (int d = 0; d < n; ++d) longest = std::max(longest, rows_of(d));
-  if (int rc = ensure_cg_work(M)) return rc;
-  if (int rc = ensure_ms_work(M, m, sh.nslots, ((long long)longest + 1) & ~1LL)) return rc;
+  f.slices(gather);
+  if (int rc = ensure_cg_work(M)) return rc;                 // (ld: every x_i and P_i 16-byte aligned)
+  if (int rc = ensure_ladder_work(M, M->ms, m, sh.nslots, ((long long)f.longest() + 1) & ~1LL, (size_t)fs::kMscgStateDoubles)) return rc;
   CgWork &W = M->cg;
-  MsWork &S = M->ms;
+  LadderWork &S = M->ms;
   const long long ld = S.ld;
   f.st = &W.st;
   // a rank works on whole vectors or on its slice; q and p are the handle's z and x (whole) or the rank's slice buffers
   const std::vector<double *> &vq = gather ? W.q : M->z, &vp = gather ? W.p : M->x;
-  auto scalars_of = [&](int d) { return fs::MscgScalars{S.ms[(size_t)d], m, tol, &sh}; };
+  auto scalars_of = [&](int d) { return fs::MscgScalars{S.sc[(size_t)d], m, tol, &sh}; };
   if (int rc = f.stage(W.b, b, (size_t)F)) return rc;
-  SliceSums sums{M};
+  SliceSums sums{M, W.red, W.redall, kCgSendDoubles};
   if (int rc = each_rank(D, false, [&](int d) -> int {       // the init kernel writes p itself: whole into x, or the slice
         if (gather && F > 0)                                 // the first product reads the whole p = b
           FS_HIP(hipMemcpyAsync(M->x[(size_t)d], W.b[(size_t)d], sizeof(double) * (size_t)F, hipMemcpyDeviceToDevice, D->stream[d]));
-        return fs::mscg_dev_init(rows_of(d), W.b[(size_t)d] + lo_of(d), W.r[(size_t)d], vp[(size_t)d], S.X[(size_t)d], ld, S.P[(size_t)d], ld,
-                                 sums.of(d, gather), scalars_of(d), D->stream[d]);
+        return fs::mscg_dev_init(f.rows(d), W.b[(size_t)d] + f.lo(d), W.r[(size_t)d], vp[(size_t)d], S.X[(size_t)d], ld, S.P[(size_t)d], ld,
+                                 cg_sums(W, d, gather ? sums.send(d) : nullptr), scalars_of(d), D->stream[d]);
       })) return rc;
-  auto final_of = [&](fs::MscgStep step) {
-    return [&, step](int d, const double *all, double *red_out) {
-      return fs::mscg_dev_final(step, all, n, red_out, W.st[(size_t)d], scalars_of(d), D->stream[d]);
-    };
+  auto combine = [&](fs::MscgStep step) {
+    return sums.combine(1, [&](int d, const double *all) {
+      return fs::mscg_dev_final(step, all, n, cg_finished_sums(W, d), W.st[(size_t)d], scalars_of(d), D->stream[d]);
+    });
   };
   if (gather)
-    if (int rc = sums.combine(1, final_of(fs::kMscgStart))) return rc;
+    if (int rc = combine(fs::kMscgStart)) return rc;
   if (!gather) {
-    if (int rc = f.iterate(cap, true, [&]() -> int {
-          if (int rc2 = dist_product(M, false, 1, M->x, M->y)) return rc2;     // y = A p
-          return dist_product(M, true, 1, M->y, M->z);                         // q = A' y
-        }, [&](int d) {
+    if (int rc = f.iterate(cap, true, [&] { return dist_pair(M, 1, M->x, M->y, M->z); }, [&](int d) {     // y = A p, q = A' y
           return fs::mscg_dev_steps(F, sh.base, W.r[(size_t)d], M->x[(size_t)d], M->z[(size_t)d], S.X[(size_t)d], ld, S.P[(size_t)d], ld,
-                                    sums.of(d, false), scalars_of(d), D->stream[d]);
+                                    cg_sums(W, d, nullptr), scalars_of(d), D->stream[d]);
         })) return rc;
   } else {
     if (int rc = f.iterate(cap, true, [&]() -> int {
           if (int rc2 = dist_product(M, false, 1, M->x, M->y)) return rc2;     // y = A p
           if (int rc2 = each_rank(D, false, [&](int d) -> int {
-                if (rows_of(d) > 0)
-                  if (int rc3 = fs_spmv(T.shard[(size_t)d], vq[(size_t)d], M->y[(size_t)d], D->stream[d])) return rc3;
-                return fs::mscg_dev_shift_dot(rows_of(d), sh.base, vp[(size_t)d], vq[(size_t)d], sums.of(d, true), scalars_of(d), D->stream[d]);
+                if (int rc3 = f.shard_product(d, 1, vq[(size_t)d], M->y[(size_t)d])) return rc3;
+                return fs::mscg_dev_shift_dot(f.rows(d), sh.base, vp[(size_t)d], vq[(size_t)d], cg_sums(W, d, sums.send(d)), scalars_of(d),
+                                              D->stream[d]);
               })) return rc2;
-          if (int rc2 = sums.combine(1, final_of(fs::kMscgS1))) return rc2;     // alpha, the a_i
+          if (int rc2 = combine(fs::kMscgS1)) return rc2;                       // alpha, the a_i
           if (int rc2 = each_rank(D, false, [&](int d) {
-                return fs::mscg_dev_update(rows_of(d), W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d], S.X[(size_t)d], ld, S.P[(size_t)d], ld,
-                                           sums.of(d, true), scalars_of(d), D->stream[d]);
+                return fs::mscg_dev_update(f.rows(d), W.r[(size_t)d], vp[(size_t)d], vq[(size_t)d], S.X[(size_t)d], ld, S.P[(size_t)d], ld,
+                                           cg_sums(W, d, sums.send(d)), scalars_of(d), D->stream[d]);
               })) return rc2;
-          if (int rc2 = sums.combine(1, final_of(fs::kMscgS2))) return rc2;     // converged?  beta, freezes
+          if (int rc2 = combine(fs::kMscgS2)) return rc2;                       // converged?  beta, freezes
           if (int rc2 = each_rank(D, false, [&](int d) {
-                return fs::mscg_dev_direction(rows_of(d), vp[(size_t)d], W.r[(size_t)d], S.P[(size_t)d], ld, W.st[(size_t)d], S.ms[(size_t)d],
+                return fs::mscg_dev_direction(f.rows(d), vp[(size_t)d], W.r[(size_t)d], S.P[(size_t)d], ld, W.st[(size_t)d], S.sc[(size_t)d],
                                               D->stream[d]);
               })) return rc2;
           return run_gather(D, exchange_of(M, true, 1), W.p, M->x, false);     // the new p on every rank
-        }, [](int) { return FS_OK; })) return rc;
+        })) return rc;
   }
-  if (int rc = f.settle()) return rc;
-  // every rank froze every shift at the same iteration in the same way: rank 0's per-shift array speaks for all
-  double ms0[fs::kMscgStateDoubles] = {0.0};
-  const size_t nms = (size_t)m * (fs::kMscgStateDoubles / FS_MSCG_MAX_SHIFTS);
-  if (int rc = each_rank(D, false, [&](int d) -> int {
-        double msd[fs::kMscgStateDoubles] = {0.0};
-        FS_HIP(hipMemcpy(d == 0 ? ms0 : msd, S.ms[(size_t)d], sizeof(double) * nms, hipMemcpyDeviceToHost));
-        if (d > 0 && !fs::mscg_same_outcome(msd, ms0, m)) {
-          fs::set_error("fs_dist_mscg: the devices froze the shifts differently (a device or an exchange returned different bits)");
-          return FS_ERR_HIP;
-        }
-        return FS_OK;
-      })) return rc;
-  if (vector_device(X) >= 0)
-    if (int rc = wait_for_caller(vector_device(X))) return rc;
-  for (int i = 0; i < m; ++i)
-    if (int rc = f.store(X + (size_t)i * (size_t)ldx, S.X, (size_t)i * (size_t)ld, (size_t)F, gather)) return rc;
-  if (int rc = dist_sync(D)) return rc;
-  fs::mscg_note_state(f.st0, ms0, m, info);
+  // every rank froze every shift at the same iteration in the same way: the per-shift array
+  Agreement froze{{Outcome{S.sc, 0, (size_t)m * (fs::kMscgStateDoubles / FS_MSCG_MAX_SHIFTS)}}, [&](const double *mine, const double *first) {
+    return fs::mscg_same_outcome(mine, first, m);
+  }, "fs_dist_mscg: the devices froze the shifts differently (a device or an exchange returned different bits)", {}};
+  if (int rc = f.finish(X, S.X, 1, &froze, m, (size_t)ld, (size_t)ldx)) return rc;
+  fs::mscg_note_state(f.st0, froze.first.data(), m, info);
   return FS_OK;
 }
-
-// fs_dist_mscgn's panels on the handle: room for m X_i and nslots P_i of ld doubles each and the scalars, per rank.  Kept between
-// solves; re-made when a solve needs more panels or longer ones than they hold
-static int ensure_mn_work(fs_dist_matrix_t M, int m, int nslots, long long ld)
-{
-  fs_dist_t D = M->D;
-  MnWork &W = M->mn;
-  if (W.mem.ready && W.F == M->ncol && W.m >= m && W.nslots >= nslots && W.ld >= ld) return FS_OK;
-  if (int rc = dist_sync(D)) return rc;
-  free_mn(D, W);
-  W.F = M->ncol; W.m = m; W.nslots = nslots; W.ld = ld;
-  return W.mem.fill(D, [&](int d) -> int {
-    if (int rc2 = W.mem.get(d, W.X, (size_t)ld * (size_t)m)) return rc2;
-    if (int rc2 = W.mem.get(d, W.P, (size_t)ld * (size_t)(nslots ? nslots : 1))) return rc2;
-    return W.mem.get(d, W.red, kMnScalarDoubles);
-  });
-}
-
-// Scheme "gather" for fs_dist_mscgn: PnSliceSums' exchange with fs_mscgn's scalar step behind it.  A slice step leaves a rank's ns
-// sums per column in send(d); combine() all-gathers them and every rank takes mscgn_dev_rank_step over the same values
-struct MnSliceSums {
-  fs_dist_matrix_t M;
-  int k;
-  int slot = 0;
-  double *send(int d) const { return M->pn.send[(size_t)d] + fs::kPcgnSendDoubles * slot; }
-  // where rank d's launchers leave their sums: on slices in the send slot, on whole panels where the scalar steps read them
-  fs::PcgnSums of(int d, bool gather) const
-  {
-    const PnWork &W = M->pn;
-    return fs::PcgnSums{W.part[(size_t)d], W.st[(size_t)d], W.cs[(size_t)d], gather ? send(d) : M->mn.red[(size_t)d]};
-  }
-  int combine(fs::MscgStep step, const std::function<fs::MscgnScalars(int)> &scalars_of)
-  {
-    fs_dist_t D = M->D;
-    const int n = D->n, ns = step == fs::kMscgStart ? 2 : 1;
-    PnWork &W = M->pn;
-    DistSide &T = M->t;
-    std::vector<const double *> from((size_t)n);
-    std::vector<hipEvent_t> ready((size_t)n);
-    if (int rc = each_rank(D, false, [&](int d) -> int {
-          from[(size_t)d] = send(d);
-          FS_HIP(hipEventRecord(T.ev[(size_t)d][0], D->stream[d]));
-          ready[(size_t)d] = T.ev[(size_t)d][0];
-          return FS_OK;
-        })) return rc;
-    if (int rc = exchange_equal(D, from, W.all, (size_t)ns * (size_t)k, D->stream, ready)) return rc;
-    if (int rc = each_rank(D, false, [&](int d) {
-          return fs::mscgn_dev_rank_step(step, W.all[(size_t)d], n, k, of(d, true), scalars_of(d), D->stream[d]);
-        })) return rc;
-    slot ^= 1;
-    return FS_OK;
-  }
-};
 
 // fs_mscgn across the ranks; the schemes are fs_dist_mscg's (option "dist_cg_scheme"):
 //   0 "replicate"  every rank holds whole panels R, P, Q, the m X_i and the P_i and launches fs_mscgn's own steps on them
@@ -2336,7 +2250,7 @@ struct MnSliceSums {
 //   1 "gather"     rank r keeps its rows of A' of R, Q, every X_i and every P_i; P and T = A P stay whole, the rank's slice of P is
 //                  the k-column exchange's own send buffer.  The X_i and P_i never leave their rank: only P enters a product.
 //                  Q_r = A'_r T is the rank's own shard product; q.p and r.r are the slice tree of fs_dist_cg per column
-//                  (MnSliceSums), the scalar steps run on every rank over the gathered values; the new P is gathered.  The first P
+//                  (SliceSums), the scalar steps run on every rank over the gathered values; the new P is gathered.  The first P
 //                  is B, which every rank holds whole after staging.
 // The caller's X is written once, at the end, after every rank's {done, iterations}, mask of live columns and per-pair
 // {live, converged, count} agreed.
@@ -2354,102 +2268,84 @@ int fs_dist_mscgn(fs_dist_matrix_t M, double *X, int64_t ldx, const double *B, i
   const bool gather = fs::options().dist_cg_scheme == 1 && n > 1;
   const fs::MscgShifts sh = fs::mscg_shifts(m, lambda);
   const int cap = max_iter > 0 ? max_iter : F;               // cg.h:55
-  DistSide &T = M->t;
-  auto lo_of = [&](int d) { return gather ? T.bounds[(size_t)d] : 0; };
-  auto rows_of = [&](int d) { return gather ? T.bounds[(size_t)d + 1] - T.bounds[(size_t)d] : F; };
-  int longest = 1;                                           // of the panels a rank keeps: every X_i and P_i 16-byte aligned
-  for (int d = 0; d < n; ++d) longest = std::max(longest, rows_of(d));
+  f.slices(gather);
   if (k > 1)
     if (int rc = ensure_k(M, k)) return rc;
-  if (int rc = ensure_pn_work(M, k, gather)) return rc;
-  if (int rc = ensure_mn_work(M, m, sh.nslots, ((long long)longest * k + 1) & ~1LL)) return rc;
+  if (int rc = ensure_pn_work(M, k, gather)) return rc;      // (ld: every X_i and P_i 16-byte aligned)
+  if (int rc = ensure_ladder_work(M, M->mn, m, sh.nslots, ((long long)f.longest() * k + 1) & ~1LL, kMnScalarDoubles)) return rc;
   PnWork &W = M->pn;
-  MnWork &S = M->mn;
+  LadderWork &S = M->mn;
   const long long ld = S.ld;
   f.st = &W.st;
-  // the product vectors: P (replicated input of A), T = A P, Q = A' T (whole panels: scheme 0 only)
-  const std::vector<double *> &vp = k > 1 ? M->kw.x : M->x, &vt = k > 1 ? M->kw.y : M->y, &vz = k > 1 ? M->kw.z : M->z;
+  const ProductVectors v = product_vectors(M, k);              // (Q as a whole panel: scheme 0 only)
   // the slice of P: the local output buffer of the A' side, which no product of scheme 1 writes -- the gather's own source
   const Exchange gp = exchange_of(M, true, k);
-  const std::vector<double *> &dp = gather ? gp.local : vp, &dq = gather ? W.q : vz;
+  const std::vector<double *> &dp = gather ? gp.local : v.p, &dq = gather ? W.q : v.q;
   auto scalars_of = [&](int d) {
-    double *red = S.red[(size_t)d], *cst = red + fs::kPcgnSendDoubles, *ms = cst + kMnCstDoubles;
+    double *red = S.sc[(size_t)d], *cst = red + fs::kPcgnSendDoubles, *ms = cst + kMnCstDoubles;
     return fs::MscgnScalars{red, cst, ms, ms + fs::kMscgnStateDoubles, m, tol, &sh};
   };
-  MnSliceSums sums{M, k};
-  if (int rc = f.stage(gather ? vp : W.b, B, (size_t)F * k)) return rc;     // slices: the whole B is the first P, where the product reads it
+  // PnWork's send slots and gathered values with fs_mscgn's scalar step behind the exchange, every rank over the same values.
+  // Where rank d's launchers leave their sums: on slices in the send slot, on whole panels where the scalar steps read them
+  SliceSums sums{M, W.send, W.all, fs::kPcgnSendDoubles};
+  auto sums_of = [&](int d, bool slot) { return pn_sums(W, d, slot ? sums.send(d) : S.sc[(size_t)d]); };
+  auto combine = [&](fs::MscgStep step) {
+    return sums.combine((size_t)(step == fs::kMscgStart ? 2 : 1) * (size_t)k, [&](int d, const double *all) {
+      return fs::mscgn_dev_rank_step(step, all, n, k, sums_of(d, true), scalars_of(d), D->stream[d]);
+    });
+  };
+  if (int rc = f.stage(gather ? v.p : W.b, B, (size_t)F * k)) return rc;    // slices: the whole B is the first P, where the product reads it
   if (int rc = each_rank(D, false, [&](int d) -> int {
         if (int rc2 = fs::pcgn_dev_clear(W.cs[(size_t)d], D->stream[d])) return rc2;
-        FS_HIP(hipMemsetAsync(S.red[(size_t)d], 0, sizeof(double) * kMnScalarDoubles, D->stream[d]));   // unwritten slots read as 0 in the debug getter
-        if (gather && rows_of(d) > 0)
-          FS_HIP(hipMemcpyAsync(W.b[(size_t)d], vp[(size_t)d] + (size_t)lo_of(d) * k, sizeof(double) * (size_t)rows_of(d) * k,
-                                hipMemcpyDeviceToDevice, D->stream[d]));
-        return fs::mscgn_dev_init(rows_of(d), k, W.b[(size_t)d], S.X[(size_t)d], ld, W.r[(size_t)d], dp[(size_t)d], dq[(size_t)d], S.P[(size_t)d], ld,
-                                  sums.of(d, gather), scalars_of(d), D->stream[d]);
+        FS_HIP(hipMemsetAsync(S.sc[(size_t)d], 0, sizeof(double) * kMnScalarDoubles, D->stream[d]));   // unwritten slots read as 0 in the debug getter
+        return FS_OK;
       })) return rc;
   if (gather)
-    if (int rc = sums.combine(fs::kMscgStart, scalars_of)) return rc;        // b.b, r.r per column: stop, every pair's scalars, live?
+    if (int rc = f.take_slices(W.b, v.p, k)) return rc;
+  if (int rc = each_rank(D, false, [&](int d) {
+        return fs::mscgn_dev_init(f.rows(d), k, W.b[(size_t)d], S.X[(size_t)d], ld, W.r[(size_t)d], dp[(size_t)d], dq[(size_t)d], S.P[(size_t)d], ld,
+                                  sums_of(d, gather), scalars_of(d), D->stream[d]);
+      })) return rc;
+  if (gather)
+    if (int rc = combine(fs::kMscgStart)) return rc;                         // b.b, r.r per column: stop, every pair's scalars, live?
   if (!gather) {
-    if (int rc = f.iterate(cap, true, [&]() -> int {
-          if (int rc2 = dist_product(M, false, k, vp, vt)) return rc2;       // T = A P
-          return dist_product(M, true, k, vt, vz);                           // Q = A' T
-        }, [&](int d) {
-          return fs::mscgn_dev_steps(F, k, S.X[(size_t)d], ld, W.r[(size_t)d], vp[(size_t)d], vz[(size_t)d], S.P[(size_t)d], ld, sums.of(d, false),
+    if (int rc = f.iterate(cap, true, [&] { return dist_pair(M, k, v.p, v.t, v.q); }, [&](int d) {     // T = A P, Q = A' T
+          return fs::mscgn_dev_steps(F, k, S.X[(size_t)d], ld, W.r[(size_t)d], v.p[(size_t)d], v.q[(size_t)d], S.P[(size_t)d], ld, sums_of(d, false),
                                      scalars_of(d), D->stream[d]);
         })) return rc;
   } else {
     if (int rc = f.iterate(cap, true, [&]() -> int {
-          if (int rc2 = dist_product(M, false, k, vp, vt)) return rc2;       // T = A P
+          if (int rc2 = dist_product(M, false, k, v.p, v.t)) return rc2;     // T = A P
           if (int rc2 = each_rank(D, false, [&](int d) -> int {              // Q_r = A'_r T: the rank's own shard product
-                if (rows_of(d) > 0)
-                  if (int rc3 = k == 1 ? fs_spmv(T.shard[(size_t)d], dq[(size_t)d], vt[(size_t)d], D->stream[d])
-                                       : fs_spmm(T.shard[(size_t)d], dq[(size_t)d], vt[(size_t)d], k, D->stream[d])) return rc3;
-                return fs::mscgn_dev_shift_dot(rows_of(d), k, dq[(size_t)d], dp[(size_t)d], sums.of(d, true), scalars_of(d), D->stream[d]);
+                if (int rc3 = f.shard_product(d, k, dq[(size_t)d], v.t[(size_t)d])) return rc3;
+                return fs::mscgn_dev_shift_dot(f.rows(d), k, dq[(size_t)d], dp[(size_t)d], sums_of(d, true), scalars_of(d), D->stream[d]);
               })) return rc2;
-          if (int rc2 = sums.combine(fs::kMscgS1, scalars_of)) return rc2;   // alpha_j, the a_ij
+          if (int rc2 = combine(fs::kMscgS1)) return rc2;                    // alpha_j, the a_ij
           if (int rc2 = each_rank(D, false, [&](int d) {
-                return fs::mscgn_dev_update(rows_of(d), k, S.X[(size_t)d], ld, W.r[(size_t)d], dp[(size_t)d], dq[(size_t)d], S.P[(size_t)d], ld,
-                                            sums.of(d, true), scalars_of(d), D->stream[d]);
+                return fs::mscgn_dev_update(f.rows(d), k, S.X[(size_t)d], ld, W.r[(size_t)d], dp[(size_t)d], dq[(size_t)d], S.P[(size_t)d], ld,
+                                            sums_of(d, true), scalars_of(d), D->stream[d]);
               })) return rc2;
-          if (int rc2 = sums.combine(fs::kMscgS2, scalars_of)) return rc2;   // converged?  beta_j, freezes
+          if (int rc2 = combine(fs::kMscgS2)) return rc2;                    // converged?  beta_j, freezes
           if (int rc2 = each_rank(D, false, [&](int d) {
-                return fs::mscgn_dev_direction(rows_of(d), k, dp[(size_t)d], W.r[(size_t)d], S.P[(size_t)d], ld, sums.of(d, true), scalars_of(d),
+                return fs::mscgn_dev_direction(f.rows(d), k, dp[(size_t)d], W.r[(size_t)d], S.P[(size_t)d], ld, sums_of(d, true), scalars_of(d),
                                                D->stream[d]);
               })) return rc2;
-          return run_gather(D, gp, dp, vp, false);                           // the new P on every rank
-        }, [](int) { return FS_OK; })) return rc;
+          return run_gather(D, gp, dp, v.p, false);                          // the new P on every rank
+        })) return rc;
   }
-  if (int rc = f.settle()) return rc;
-  // every rank froze every column and every pair at the same iteration in the same way: rank 0's arrays speak for all
-  std::vector<double> cst0((size_t)k * fs::kCgStateDoubles), ms0((size_t)k * fs::kMscgStateDoubles), cstd(cst0.size()), msd(ms0.size());
-  double mask0 = 0.0;
-  if (int rc = each_rank(D, false, [&](int d) -> int {
-        const fs::MscgnScalars K = scalars_of(d);
-        double std_[fs::kCgStateDoubles];
-        FS_HIP(hipMemcpy(d == 0 ? cst0.data() : cstd.data(), K.cst, sizeof(double) * cst0.size(), hipMemcpyDeviceToHost));
-        FS_HIP(hipMemcpy(d == 0 ? ms0.data() : msd.data(), K.ms, sizeof(double) * ms0.size(), hipMemcpyDeviceToHost));
-        FS_HIP(hipMemcpy(std_, W.st[(size_t)d], sizeof(std_), hipMemcpyDeviceToHost));
-        if (d == 0) { mask0 = std_[fs::kCgStateLiveMask]; return FS_OK; }
-        bool same = std_[fs::kCgStateLiveMask] == mask0;
-        for (int j = 0; j < k; ++j)
-          same = same && cstd[(size_t)j * fs::kCgStateDoubles + fs::kCgStateDone] == cst0[(size_t)j * fs::kCgStateDoubles + fs::kCgStateDone] &&
-                 fs::mscg_same_outcome(msd.data() + (size_t)j * fs::kMscgStateDoubles, ms0.data() + (size_t)j * fs::kMscgStateDoubles, m);
-        if (!same) {
-          fs::set_error("fs_dist_mscgn: the devices froze the pairs differently (a device or an exchange returned different bits)");
-          return FS_ERR_HIP;
-        }
-        return FS_OK;
-      })) return rc;
-  if (vector_device(X) >= 0)
-    if (int rc = wait_for_caller(vector_device(X))) return rc;
-  for (int i = 0; i < m; ++i) {
-    double *xi = X + (size_t)i * (size_t)ldx;
-    for (int d = 0; d < (gather ? n : 1); ++d)
-      if (rows_of(d) > 0)
-        if (int rc = vec_store(M, d, xi + (size_t)lo_of(d) * k, S.X[(size_t)d] + (size_t)i * (size_t)ld, (size_t)rows_of(d) * k)) return rc;
-  }
-  if (int rc = dist_sync(D)) return rc;
-  fs::mscgn_note_state(cst0.data(), ms0.data(), k, m, info);
+  // every rank froze every column and every pair at the same iteration in the same way: every column's st[] and ms[], then the
+  // rank's st[] for the live mask
+  const size_t ncst = (size_t)k * fs::kCgStateDoubles, nms = (size_t)k * fs::kMscgStateDoubles;
+  Agreement froze{{Outcome{S.sc, (size_t)fs::kPcgnSendDoubles, ncst}, Outcome{S.sc, fs::kPcgnSendDoubles + kMnCstDoubles, nms},
+                   Outcome{W.st, 0, (size_t)fs::kCgStateDoubles}}, [&](const double *mine, const double *first) {
+    bool same = mine[ncst + nms + fs::kCgStateLiveMask] == first[ncst + nms + fs::kCgStateLiveMask];
+    for (int j = 0; j < k; ++j)
+      same = same && mine[(size_t)j * fs::kCgStateDoubles + fs::kCgStateDone] == first[(size_t)j * fs::kCgStateDoubles + fs::kCgStateDone] &&
+             fs::mscg_same_outcome(mine + ncst + (size_t)j * fs::kMscgStateDoubles, first + ncst + (size_t)j * fs::kMscgStateDoubles, m);
+    return same;
+  }, "fs_dist_mscgn: the devices froze the pairs differently (a device or an exchange returned different bits)", {}};
+  if (int rc = f.finish(X, S.X, k, &froze, m, (size_t)ld, (size_t)ldx)) return rc;
+  fs::mscgn_note_state(froze.first.data(), froze.first.data() + ncst, k, m, info);
   return FS_OK;
 }
 
@@ -2496,16 +2392,13 @@ int fs_dist_cg2(fs_dist_matrix_t M, double *X_host, const double *B_host, double
         }
         return FS_OK;
       })) return rc;
-  if (int rc = f.iterate(F, false, [&]() -> int {
-        if (int rc2 = dist_product(M, false, 2, W.x, W.y)) return rc2;     // TMP = A P
-        return dist_product(M, true, 2, W.y, W.z);                         // Q = A' TMP
-      }, [&](int d) {
+  if (int rc = f.iterate(F, false, [&] { return dist_pair(M, 2, W.x, W.y, W.z); }, [&](int d) {     // TMP = A P, Q = A' TMP
         return fs::cg2_dev_steps(F, lambda, W.sol[(size_t)d], W.r[(size_t)d], W.x[(size_t)d], W.z[(size_t)d], W.part[(size_t)d],
                                  W.red[(size_t)d], W.st[(size_t)d], D->stream[d]);
       })) return rc;
   if (f.seen != kRanksDisagree)                              // X back in B's scale
     if (int rc = each_rank(D, false, [&](int d) { return fs::cg2_dev_finish(F, &norms[2 * (size_t)d], W.sol[(size_t)d], D->stream[d]); })) return rc;
-  if (int rc = f.finish(X_host, W.sol, (size_t)F * 2)) return rc;
+  if (int rc = f.finish(X_host, W.sol, 2)) return rc;
   if (out_iter) *out_iter = f.iterations;
   return FS_OK;
 }

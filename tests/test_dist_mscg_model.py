@@ -138,7 +138,11 @@ def test_names_are_the_sources():
     assert src["fs_cg.hip"].count("sg.v[i] = i < m ? lambda[i] - base : 0.0;") == 1
     assert 'mscg_args_ok("fs_mscg"' in src["fs_cg.hip"] and 'mscg_args_ok("fs_dist_mscg"' in src["fs_dist.hip"]
     assert "int fs_dist_mscg(fs_dist_matrix_t M, double *X, int64_t ldx, const double *b, int m, const double *lambda, double tol, int max_iter," in src["fs_dist.hip"]
-    assert "struct MsWork {" in src["fs_dist.hip"] and "free_ms(M->D, M->ms);" in src["fs_dist.hip"]
+    # the solver's work space is on the handle (one struct for both ladder solvers, an instance each) and destroy frees it
+    assert src["fs_dist.hip"].count("struct LadderWork {") == 1 and "LadderWork ms, mn;" in src["fs_dist.hip"]
+    assert "ensure_ladder_work(M, M->ms, m, sh.nslots," in src["fs_dist.hip"]
+    destroy = src["fs_dist.hip"].split("void fs_dist_matrix_destroy(fs_dist_matrix_t M)")[1].split("delete M;")[0]
+    assert "free_work(M->D, M->ms);" in destroy
     capi = _squeezed(M.ROOT, "libfastsparse_amd", "capi.py")
     assert '"fs_dist_mscg"' in capi and "def dist_mscg(M, X, b, lams, tol, max_iter=0):" in capi and "L.fs_dist_mscg.argtypes" in capi
 

@@ -82,8 +82,21 @@ def test_names_are_the_sources():
     assert 'mscg_args_ok("fs_dist_mscgn"' in src["fs_dist.hip"]
     assert ("int fs_dist_mscgn(fs_dist_matrix_t M, double *X, int64_t ldx, const double *B, int k, int m, const double *lambda, double tol, "
             "int max_iter,") in src["fs_dist.hip"]
-    assert "struct MnWork {" in src["fs_dist.hip"] and "free_mn(M->D, M->mn);" in src["fs_dist.hip"]
-    assert 'DistSolve f{"fs_dist_mscgn", M};' in src["fs_dist.hip"] and "ensure_pn_work(M, k, gather)" in src["fs_dist.hip"]
+    # the solver's work space is on the handle (one struct for both ladder solvers, an instance each) and destroy frees both
+    dist = src["fs_dist.hip"]
+    assert dist.count("struct LadderWork {") == 1 and "LadderWork ms, mn;" in dist
+    assert "ensure_ladder_work(M, M->mn, m, sh.nslots," in dist
+    destroy = dist.split("void fs_dist_matrix_destroy(fs_dist_matrix_t M)")[1].split("delete M;")[0]
+    assert "free_work(M->D, M->ms);" in destroy and "free_work(M->D, M->mn);" in destroy
+    assert 'DistSolve f{"fs_dist_mscgn", M};' in dist and "ensure_pn_work(M, k, gather)" in dist
+    # what the sharded solvers share exists once: the exchange of sums (its event record, its slot flip), the slice geometry (no
+    # solver declares its own), and the host loop that holds every rank's outcome against rank 0's, with each solver's own text
+    assert dist.count("hipEventRecord(T.ev[") == 1 and dist.count("slot ^= 1;") == 1       # (the staged uploads flip a slot of their own)
+    assert "auto lo_of" not in dist and "auto rows_of" not in dist
+    for what in ("columns", "shifts", "pairs"):
+        assert dist.count("the devices froze the " + what + " differently (a device or an exchange returned different bits)") == 1, what
+    assert dist.count("int agree(Agreement &a)") == 1 and dist.count("fs::set_error(a.differ)") == 1
+    assert "if (int rc = agree(*also)) return rc;" in dist and dist.count("_same_outcome(") == 3      # finish() runs it; a comparison per solver
     capi = _squeezed(M.ROOT, "libfastsparse_amd", "capi.py")
     assert '"fs_dist_mscgn"' in capi and "def dist_mscgn(M, X, B, lams, tol, max_iter=0):" in capi and "L.fs_dist_mscgn.argtypes" in capi
 

@@ -53,7 +53,12 @@ def test_launchers_are_the_sources():
     # the gathered values: rank b's nv sums at b * nv, where the exchange leaves them
     assert "a[u] += part[(size_t)b * nv + v];" in cg
     assert "recv[(size_t)d] + (int64_t)r * (int64_t)count" in src["fs_dist.hip"]
-    assert "exchange_equal(D, from, W.all, (size_t)ns * (size_t)k, D->stream, ready)" in src["fs_dist.hip"]
+    # a k-column exchange carries ns * k doubles per rank, on the compute streams: the count the k-column callers hand to the one
+    # combine, whose exchange_equal call is the only one on D->stream
+    assert "SliceSums sums{M, W.send, W.all, fs::kPcgnSendDoubles};" in src["fs_dist.hip"]
+    assert "return sums.combine((size_t)ns * (size_t)k, [&](int d, const double *all) {" in src["fs_dist.hip"]
+    assert src["fs_dist.hip"].count("exchange_equal(D, from, all, count, D->stream, ready)") == 1
+    assert src["fs_dist.hip"].count("D->stream, ready)") == 1
     for name in ("pcgn_dev_init_lambdas", "pcgn_dev_steps_lambdas", "pcgn_slice_init", "pcgn_slice_start", "pcgn_slice_shift_dot",
                  "pcgn_slice_update", "pcgn_slice_direction", "pcgn_dev_rank_step"):
         assert len(re.findall(r"\bint " + name + r"\(", cg)) == 1, name
