@@ -705,11 +705,63 @@ __device__ __forceinline__ void pcgn_tile_pairs(int c0, int k, unsigned live, G 
 // column (FS_PRECOND_JACOBI): `dinv` then holds s = diag(A'A), and column c's inverse is formed per element, pcg_dinv_kernel's
 // line on s + lambda_c.  The lambdas are a by-value argument, indexed by constants once the column loops are unrolled: scalar
 // loads from the kernel's arguments, wave-uniform like al[c] and be[c].  Without LAM a kernel is fs_pcgn's own instantiation.
-template <typename LAM> constexpr bool pn_cols = !std::is_same<LAM, double>::value;
 __device__ __forceinline__ double pn_inv(double s, double lambda)
 {
   const double d = s + lambda;
   return d == 0.0 ? 1.0 : 1.0 / d;
+}
+
+// column c's lambda: the solve's one, one of the k by-value ones (lane-per-row kernels), one of the table in LDS (staged kernels)
+__device__ __forceinline__ double pn_lambda(double lambda, int) { return lambda; }
+__device__ __forceinline__ double pn_lambda(const PcgnLambdas &lambda, int c) { return lambda.v[c]; }
+__device__ __forceinline__ double pn_lambda(const double *lam, int c) { return lam[c]; }
+
+// a kernel's trailing LAM... as one value: the k lambdas, or PnOneDiag when the diagonal is the same for every column
+struct PnOneDiag {};
+__device__ __forceinline__ PnOneDiag pn_colj() { return {}; }
+__device__ __forceinline__ const PcgnLambdas &pn_colj(const PcgnLambdas &lambda) { return lambda; }
+
+// ---- the column steps: what one element of one column takes part in, each formula written here and nowhere else.  The
+// lane-per-row kernels call them for the two columns of a Pair, the staged kernels column by column; a new per-column variant
+// (another source of lambda, a weight) is added here.  Every product and sum rounds on its own, in this order (-ffp-contract=off)
+
+// behind the product: q = q0 + l p, and q.p
+__device__ __forceinline__ double pn_shift_dot(double q0, double l, double p, double &qp)
+{
+  const double q = q0 + l * p;
+  qp += q * p;
+  return q;
+}
+
+__device__ __forceinline__ double pn_x(double x0, double al, double p) { return x0 + al * p; }
+
+// r = r0 - al q, and r.r
+__device__ __forceinline__ double pn_r(double r0, double al, double q, double &rr)
+{
+  const double r = r0 - al * q;
+  rr += r * r;
+  return r;
+}
+
+// z of r: r without a preconditioner, r di with di = dinv[i], r / (di + lambda_c) with di = diag(A'A)[i] when the diagonal
+// follows the column (pcg_dinv_kernel's line)
+template <typename CJ>
+__device__ __forceinline__ double pn_z(double r, bool pre, double di, const CJ &colj, int c)
+{
+  if constexpr (std::is_same<CJ, PnOneDiag>::value) return pre ? r * di : r;
+  else return r * pn_inv(di, pn_lambda(colj, c));
+}
+
+__device__ __forceinline__ double pn_direction(double z, double be, double p0) { return z + be * p0; }
+
+// the start: r = b, or warm q = q + l x, r = b - q; b.b and r.r
+__device__ __forceinline__ double pn_init(bool warm, double &q, double l, double x, double b, double &bb, double &rr)
+{
+  if (warm) q = q + l * x;
+  const double r = warm ? b - q : b;
+  bb += b * b;
+  rr += r * r;
+  return r;
 }
 
 __device__ __forceinline__ unsigned pcgn_live(const double *__restrict__ st)
@@ -745,6 +797,28 @@ __device__ __forceinline__ void pcgn_block_sums(int k, unsigned live, int ns, co
   }
 }
 
+// an array that the lane-per-row sweep loads: V as in pn_ld; not on: it is not read and its pairs are 0
+template <bool V> struct PnArray { const double *p; bool on = true; };
+
+// The lane-per-row sweep: a thread's rows in increasing order, of each row the tiles that hold a live column, of each tile the
+// listed arrays loaded back to back (the comment above pcgn_ld_tile), then
+// g(row * k, h, c, column c is live, column c + 1 is, dinv[row] or 1, v) for its column pairs c = c0 + 2 h: v[a][h] is the
+// pair of the a-th array, and g stores what it changes
+template <int KMAX, typename G, bool... V>
+__device__ __forceinline__ void pcgn_rows(int n, int k, unsigned live, const double *dinv, G g, PnArray<V>... arr)
+{
+  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
+    const size_t row = (size_t)i * k;
+    const double di = dinv ? dinv[i] : 1.0;
+    pcgn_tiles<KMAX>(k, live, [&](int c0) {
+      Pair v[sizeof...(V)][pcgn_tile<KMAX>() / 2 + 1] = {};
+      int a = 0;
+      ((arr.on ? pcgn_ld_tile<KMAX, V>(v[a++], arr.p + row, c0, k) : (void)a++), ...);
+      pcgn_tile_pairs<KMAX>(c0, k, live, [&](int h, int c, bool l0, bool l1) { g(row, h, c, l0, l1, di, v); });
+    });
+  }
+}
+
 // cold: X = 0, R = B.  warm (Q = A'(A X) on entry): Q += lambda X, R = B - Q.  Partials {b.b, r.r} per column (pcg_init_kernel).
 // VEC: 0 every access is 8 bytes (odd k), 1 16-byte accesses to the solve's own R, P, Q, 2 to the caller's X and B too
 template <int KMAX, int VEC, typename LAM = double>
@@ -752,42 +826,19 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_init_kernel(int n, int k, in
                                                                double *__restrict__ X, double *__restrict__ R,
                                                                double *__restrict__ Q, double *__restrict__ part)
 {
-  constexpr int TP = pcgn_tile<KMAX>() / 2;
   double bb[KMAX], rr[KMAX];
 #pragma unroll
   for (int c = 0; c < KMAX; ++c) { bb[c] = 0.0; rr[c] = 0.0; }
   const unsigned live = k < 32 ? (1u << k) - 1u : ~0u;
-  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
-    const size_t row = (size_t)i * k;
-    pcgn_tiles<KMAX>(k, live, [&](int c0) {
-      Pair bv[TP + 1] = {}, xv[TP + 1] = {}, qv[TP + 1] = {};
-      pcgn_ld_tile<KMAX, VEC == 2>(bv, B + row, c0, k);
-      if (warm) {
-        pcgn_ld_tile<KMAX, VEC == 2>(xv, X + row, c0, k);
-        pcgn_ld_tile<KMAX, VEC >= 1>(qv, Q + row, c0, k);
-      }
-      pcgn_tile_pairs<KMAX>(c0, k, live, [&](int h, int c, bool l0, bool l1) {
-        const Pair b = bv[h], x = xv[h], q0 = qv[h];
-        Pair r = b;
-        if (warm) {
-          if constexpr (pn_cols<LAM>) {
-            const Pair q = {q0.a + lambda.v[c] * x.a, q0.b + lambda.v[c + 1] * x.b};
-            pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
-            r = {b.a - q.a, b.b - q.b};
-          } else {
-            const Pair q = {q0.a + lambda * x.a, q0.b + lambda * x.b};
-            pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
-            r = {b.a - q.a, b.b - q.b};
-          }
-        } else {
-          pn_st<VEC == 2>(X + row + c, {0.0, 0.0}, l0, l1);
-        }
-        pn_st<VEC >= 1>(R + row + c, r, l0, l1);
-        bb[c] += b.a * b.a; bb[c + 1] += b.b * b.b;
-        rr[c] += r.a * r.a; rr[c + 1] += r.b * r.b;
-      });
-    });
-  }
+  pcgn_rows<KMAX>(n, k, live, nullptr, [&](size_t row, int h, int c, bool l0, bool l1, double, const auto &v) {
+    const Pair b = v[0][h], x = v[1][h];
+    Pair q = v[2][h];
+    const Pair r = {pn_init(warm, q.a, pn_lambda(lambda, c), x.a, b.a, bb[c], rr[c]),
+                    pn_init(warm, q.b, pn_lambda(lambda, c + 1), x.b, b.b, bb[c + 1], rr[c + 1])};
+    if (warm) pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
+    else pn_st<VEC == 2>(X + row + c, {0.0, 0.0}, l0, l1);
+    pn_st<VEC >= 1>(R + row + c, r, l0, l1);
+  }, PnArray<VEC == 2>{B}, PnArray<VEC == 2>{X, warm != 0}, PnArray<VEC >= 1>{Q, warm != 0});
   pcgn_block_sums<KMAX>(k, live, 2, bb, rr, part);
 }
 
@@ -800,31 +851,16 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_start_kernel(int n, int k, c
                                                                 LAM... lambda)
 {
   if (st[kStDone] != 0.0) return;
-  constexpr int TP = pcgn_tile<KMAX>() / 2;
   const unsigned live = pcgn_live(st), all = k < 32 ? (1u << k) - 1u : ~0u;
+  const auto &colj = pn_colj(lambda...);
   double rz[KMAX];
 #pragma unroll
   for (int c = 0; c < KMAX; ++c) rz[c] = 0.0;
-  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
-    const size_t row = (size_t)i * k;
-    const double di = dinv ? dinv[i] : 1.0;
-    pcgn_tiles<KMAX>(k, all, [&](int c0) {
-      Pair rv[TP + 1] = {};
-      pcgn_ld_tile<KMAX, VEC >= 1>(rv, R + row, c0, k);
-      pcgn_tile_pairs<KMAX>(c0, k, all, [&](int h, int c, bool l0, bool l1) {
-        const Pair r = rv[h];
-        if constexpr (sizeof...(LAM) != 0) {
-          const Pair z = {r.a * pn_inv(di, lambda.v[c]...), r.b * pn_inv(di, lambda.v[c + 1]...)};
-          pn_st<VEC >= 1>(P + row + c, z, l0, l1);
-          rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;
-        } else {
-          const Pair z = {dinv ? r.a * di : r.a, dinv ? r.b * di : r.b};
-          pn_st<VEC >= 1>(P + row + c, z, l0, l1);
-          rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;
-        }
-      });
-    });
-  }
+  pcgn_rows<KMAX>(n, k, all, dinv, [&](size_t row, int h, int c, bool l0, bool l1, double di, const auto &v) {
+    const Pair r = v[0][h], z = {pn_z(r.a, dinv != nullptr, di, colj, c), pn_z(r.b, dinv != nullptr, di, colj, c + 1)};
+    pn_st<VEC >= 1>(P + row + c, z, l0, l1);
+    rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;
+  }, PnArray<VEC >= 1>{R});
   pcgn_block_sums<KMAX>(k, live, 1, rz, rz, part);
 }
 
@@ -835,31 +871,15 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_kernel(int n, int 
                                                                     const double *__restrict__ st)
 {
   if (st[kStDone] != 0.0) return;
-  constexpr int TP = pcgn_tile<KMAX>() / 2;
   const unsigned live = pcgn_live(st);
   double qp[KMAX];
 #pragma unroll
   for (int c = 0; c < KMAX; ++c) qp[c] = 0.0;
-  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
-    const size_t row = (size_t)i * k;
-    pcgn_tiles<KMAX>(k, live, [&](int c0) {
-      Pair pv[TP + 1] = {}, qv[TP + 1] = {};
-      pcgn_ld_tile<KMAX, VEC >= 1>(pv, P + row, c0, k);
-      pcgn_ld_tile<KMAX, VEC >= 1>(qv, Q + row, c0, k);
-      pcgn_tile_pairs<KMAX>(c0, k, live, [&](int h, int c, bool l0, bool l1) {
-        const Pair p = pv[h], q0 = qv[h];
-        if constexpr (pn_cols<LAM>) {
-          const Pair q = {q0.a + lambda.v[c] * p.a, q0.b + lambda.v[c + 1] * p.b};
-          pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
-          qp[c] += q.a * p.a; qp[c + 1] += q.b * p.b;
-        } else {
-          const Pair q = {q0.a + lambda * p.a, q0.b + lambda * p.b};
-          pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
-          qp[c] += q.a * p.a; qp[c + 1] += q.b * p.b;
-        }
-      });
-    });
-  }
+  pcgn_rows<KMAX>(n, k, live, nullptr, [&](size_t row, int h, int c, bool l0, bool l1, double, const auto &v) {
+    const Pair p = v[0][h], q0 = v[1][h];
+    const Pair q = {pn_shift_dot(q0.a, pn_lambda(lambda, c), p.a, qp[c]), pn_shift_dot(q0.b, pn_lambda(lambda, c + 1), p.b, qp[c + 1])};
+    pn_st<VEC >= 1>(Q + row + c, q, l0, l1);
+  }, PnArray<VEC >= 1>{P}, PnArray<VEC >= 1>{Q});
   pcgn_block_sums<KMAX>(k, live, 1, qp, qp, part);
 }
 
@@ -873,37 +893,21 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_update_kernel(int n, int k, 
                                                                  LAM... lambda)
 {
   if (st[kStDone] != 0.0) return;
-  constexpr int TP = pcgn_tile<KMAX>() / 2;
   const unsigned live = pcgn_live(st);
+  const auto &colj = pn_colj(lambda...);
   double rr[KMAX], rz[KMAX], al[KMAX];
 #pragma unroll
   for (int c = 0; c < KMAX; ++c) { rr[c] = 0.0; rz[c] = 0.0; al[c] = cs[c * kPnStride + kPnAlpha]; }
-  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
-    const size_t row = (size_t)i * k;
-    const double di = dinv ? dinv[i] : 1.0;
-    pcgn_tiles<KMAX>(k, live, [&](int c0) {
-      Pair pv[TP + 1] = {}, qv[TP + 1] = {}, xv[TP + 1] = {}, rv[TP + 1] = {};
-      pcgn_ld_tile<KMAX, VEC >= 1>(pv, P + row, c0, k);
-      pcgn_ld_tile<KMAX, VEC >= 1>(qv, Q + row, c0, k);
-      if (XUP) pcgn_ld_tile<KMAX, VEC == 2>(xv, X + row, c0, k);
-      pcgn_ld_tile<KMAX, VEC >= 1>(rv, R + row, c0, k);
-      pcgn_tile_pairs<KMAX>(c0, k, live, [&](int h, int c, bool l0, bool l1) {
-        const Pair p = pv[h], q = qv[h], x0 = xv[h], r0 = rv[h];
-        const Pair x = {x0.a + al[c] * p.a, x0.b + al[c + 1] * p.b};
-        const Pair r = {r0.a - al[c] * q.a, r0.b - al[c + 1] * q.b};
-        if (XUP) pn_st<VEC == 2>(X + row + c, x, l0, l1);
-        pn_st<VEC >= 1>(R + row + c, r, l0, l1);
-        rr[c] += r.a * r.a; rr[c + 1] += r.b * r.b;
-        if constexpr (sizeof...(LAM) != 0) {
-          const Pair z = {r.a * pn_inv(di, lambda.v[c]...), r.b * pn_inv(di, lambda.v[c + 1]...)};
-          rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;
-        } else if (dinv) {
-          const Pair z = {r.a * di, r.b * di};
-          rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;
-        }
-      });
-    });
-  }
+  pcgn_rows<KMAX>(n, k, live, dinv, [&](size_t row, int h, int c, bool l0, bool l1, double di, const auto &v) {
+    const Pair p = v[0][h], q = v[1][h], x0 = v[2][h], r0 = v[3][h];
+    const Pair x = {pn_x(x0.a, al[c], p.a), pn_x(x0.b, al[c + 1], p.b)};
+    const Pair r = {pn_r(r0.a, al[c], q.a, rr[c]), pn_r(r0.b, al[c + 1], q.b, rr[c + 1])};
+    if (XUP) pn_st<VEC == 2>(X + row + c, x, l0, l1);
+    pn_st<VEC >= 1>(R + row + c, r, l0, l1);
+    if (sizeof...(LAM) != 0 || dinv) {
+      rz[c] += r.a * pn_z(r.a, dinv != nullptr, di, colj, c); rz[c + 1] += r.b * pn_z(r.b, dinv != nullptr, di, colj, c + 1);
+    }
+  }, PnArray<VEC >= 1>{P}, PnArray<VEC >= 1>{Q}, PnArray<VEC == 2>{X, XUP}, PnArray<VEC >= 1>{R});
   pcgn_block_sums<KMAX>(k, live, dinv ? 2 : 1, rr, rz, part);
 }
 
@@ -914,32 +918,17 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_direction_kernel(int n, int 
                                                                     const double *__restrict__ cs, LAM... lambda)
 {
   if (st[kStDone] != 0.0) return;
-  constexpr int TP = pcgn_tile<KMAX>() / 2;
   const unsigned live = pcgn_live(st);
+  const auto &colj = pn_colj(lambda...);
   double be[KMAX];
 #pragma unroll
   for (int c = 0; c < KMAX; ++c) be[c] = cs[c * kPnStride + kPnBeta];
-  for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) {
-    const size_t row = (size_t)i * k;
-    const double di = dinv ? dinv[i] : 1.0;
-    pcgn_tiles<KMAX>(k, live, [&](int c0) {
-      Pair rv[TP + 1] = {}, pv[TP + 1] = {};
-      pcgn_ld_tile<KMAX, VEC >= 1>(rv, R + row, c0, k);
-      pcgn_ld_tile<KMAX, VEC >= 1>(pv, P + row, c0, k);
-      pcgn_tile_pairs<KMAX>(c0, k, live, [&](int h, int c, bool l0, bool l1) {
-        const Pair r = rv[h], p0 = pv[h];
-        if constexpr (sizeof...(LAM) != 0) {
-          const Pair z = {r.a * pn_inv(di, lambda.v[c]...), r.b * pn_inv(di, lambda.v[c + 1]...)};
-          const Pair p = {z.a + be[c] * p0.a, z.b + be[c + 1] * p0.b};
-          pn_st<VEC >= 1>(P + row + c, p, l0, l1);
-        } else {
-          const Pair z = {dinv ? r.a * di : r.a, dinv ? r.b * di : r.b};
-          const Pair p = {z.a + be[c] * p0.a, z.b + be[c + 1] * p0.b};
-          pn_st<VEC >= 1>(P + row + c, p, l0, l1);
-        }
-      });
-    });
-  }
+  pcgn_rows<KMAX>(n, k, live, dinv, [&](size_t row, int h, int c, bool l0, bool l1, double di, const auto &v) {
+    const Pair r = v[0][h], p0 = v[1][h];
+    const Pair z = {pn_z(r.a, dinv != nullptr, di, colj, c), pn_z(r.b, dinv != nullptr, di, colj, c + 1)};
+    const Pair p = {pn_direction(z.a, be[c], p0.a), pn_direction(z.b, be[c + 1], p0.b)};
+    pn_st<VEC >= 1>(P + row + c, p, l0, l1);
+  }, PnArray<VEC >= 1>{R}, PnArray<VEC >= 1>{P});
 }
 
 // ---- the per-iteration kernels again, the panels staged through LDS (option "pcgn_kernel" = 2; auto for k > kPcgnRowsMaxK).  A
@@ -1005,11 +994,48 @@ __device__ __forceinline__ void pl_out(double *__restrict__ g, const double *__r
 
 // the staged kernels of the per-column form keep the k lambdas in LDS: a lane reads lam[c] as a broadcast, and no scalar registers
 // are held across the tile loop (with the lambdas in SGPRs the shift-dot kernel at KMAX = 32 went from 128 to 130 VGPRs, from four
-// waves per SIMD to three and from 1.6 to 2.7 ms).  Read behind the tile loop's first barrier
+// waves per SIMD to three and from 1.6 to 2.7 ms).  Read behind the tile loop's first barrier.  What pn_lambda and pn_z take in a
+// staged kernel: that table for the k lambdas, the one lambda and no lambda as they are
 template <int KMAX>
-__device__ __forceinline__ void pl_lambdas(double *__restrict__ lam, const PcgnLambdas &lambda)
+__device__ __forceinline__ const double *pl_lambdas(const PcgnLambdas &lambda)
 {
+  __shared__ double lam[KMAX];
   if (threadIdx.x < KMAX) lam[threadIdx.x] = lambda.v[threadIdx.x];
+  return lam;
+}
+template <int KMAX> __device__ __forceinline__ double pl_lambdas(double lambda) { return lambda; }
+template <int KMAX> __device__ __forceinline__ PnOneDiag pl_lambdas() { return {}; }
+
+// The staged sweep: the workgroup's rows, 256 per grid stride and TR of them at a time, and for each such piece f(pass).
+// pass(A, B, dinv, col) is one trip through LDS: the piece of A and of B in, the thread that owns a row sets
+// a[c] = col(c, a[c], b[c], dinv[row] or 1) for its live columns, A's live columns out
+template <int KMAX, typename F>
+__device__ __forceinline__ void pl_sweep(int n, int k, unsigned live, F f)
+{
+  constexpr int LD = KMAX + 1;
+  constexpr int TR = pl_rows<KMAX>();
+  __shared__ double t0[TR * LD], t1[TR * LD];
+  for (int blk0 = blockIdx.x * kRedThreads; blk0 < n; blk0 += gridDim.x * kRedThreads)      // (workgroup-uniform)
+  for (int row0 = blk0; row0 < blk0 + kRedThreads && row0 < n; row0 += TR) {                // the workgroup's 256 rows, TR at a time
+    const int nr = n - row0 < TR ? n - row0 : TR, ne = nr * k, lt = (int)threadIdx.x - (row0 - blk0);
+    const size_t at = (size_t)row0 * k;
+    f([&](double *A, const double *B, const double *dinv, auto col) {
+      pl_in<KMAX>(t0, A + at, ne, k);
+      pl_in<KMAX>(t1, B + at, ne, k);
+      __syncthreads();
+      if (lt >= 0 && lt < nr) {                               // the thread that owns row row0 + lt
+        double *a = t0 + lt * LD;
+        const double *b = t1 + lt * LD;
+        const double di = dinv ? dinv[row0 + lt] : 1.0;
+#pragma unroll
+        for (int c = 0; c < KMAX; ++c)
+          if (c < k && ((live >> c) & 1u) != 0u) a[c] = col(c, a[c], b[c], di);
+      }
+      __syncthreads();
+      pl_out<KMAX>(A + at, t0, ne, k, live);
+      __syncthreads();
+    });
+  }
 }
 
 // Q += lambda P, partial q.p per live column
@@ -1019,44 +1045,14 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_shift_dot_lds_kernel(int n, 
                                                                         const double *__restrict__ st)
 {
   if (st[kStDone] != 0.0) return;
-  constexpr int LD = KMAX + 1;
-  constexpr int TR = pl_rows<KMAX>();
-  __shared__ double t0[TR * LD], t1[TR * LD];
-  __shared__ double lam[pn_cols<LAM> ? KMAX : 1];
-  if constexpr (pn_cols<LAM>) pl_lambdas<KMAX>(lam, lambda);
+  const auto lam = pl_lambdas<KMAX>(lambda);
   const unsigned live = pcgn_live(st);
   double qp[KMAX];
 #pragma unroll
   for (int c = 0; c < KMAX; ++c) qp[c] = 0.0;
-  for (int blk0 = blockIdx.x * kRedThreads; blk0 < n; blk0 += gridDim.x * kRedThreads)      // (workgroup-uniform)
-  for (int row0 = blk0; row0 < blk0 + kRedThreads && row0 < n; row0 += TR) {                // the workgroup's 256 rows, TR at a time
-    const int nr = n - row0 < TR ? n - row0 : TR, ne = nr * k, lt = (int)threadIdx.x - (row0 - blk0);
-    const size_t at = (size_t)row0 * k;
-    pl_in<KMAX>(t0, Q + at, ne, k);
-    pl_in<KMAX>(t1, P + at, ne, k);
-    __syncthreads();
-    if (lt >= 0 && lt < nr) {                                 // the thread that owns row row0 + lt
-      double *q = t0 + lt * LD;
-      const double *p = t1 + lt * LD;
-#pragma unroll
-      for (int c = 0; c < KMAX; ++c)
-        if (c < k && ((live >> c) & 1u) != 0u) {
-          const double pi = p[c];
-          if constexpr (pn_cols<LAM>) {
-            const double qi = q[c] + lam[c] * pi;
-            q[c] = qi;
-            qp[c] += qi * pi;
-          } else {
-            const double qi = q[c] + lambda * pi;
-            q[c] = qi;
-            qp[c] += qi * pi;
-          }
-        }
-    }
-    __syncthreads();
-    pl_out<KMAX>(Q + at, t0, ne, k, live);
-    __syncthreads();
-  }
+  pl_sweep<KMAX>(n, k, live, [&](auto pass) {
+    pass(Q, P, nullptr, [&](int c, double q0, double p, double) { return pn_shift_dot(q0, pn_lambda(lam, c), p, qp[c]); });
+  });
   pcgn_block_sums<KMAX>(k, live, 1, qp, qp, part);
 }
 
@@ -1069,61 +1065,19 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_update_lds_kernel(int n, int
                                                                      LAM... lambda)
 {
   if (st[kStDone] != 0.0) return;
-  constexpr int LD = KMAX + 1;
-  constexpr int TR = pl_rows<KMAX>();
-  __shared__ double t0[TR * LD], t1[TR * LD];
-  __shared__ double lam[sizeof...(LAM) != 0 ? KMAX : 1];
-  if constexpr (sizeof...(LAM) != 0) pl_lambdas<KMAX>(lam, lambda...);
+  const auto colj = pl_lambdas<KMAX>(lambda...);
   const unsigned live = pcgn_live(st);
   double rr[KMAX], rz[KMAX], al[KMAX];
 #pragma unroll
   for (int c = 0; c < KMAX; ++c) { rr[c] = 0.0; rz[c] = 0.0; al[c] = cs[c * kPnStride + kPnAlpha]; }
-  for (int blk0 = blockIdx.x * kRedThreads; blk0 < n; blk0 += gridDim.x * kRedThreads)      // (workgroup-uniform)
-  for (int row0 = blk0; row0 < blk0 + kRedThreads && row0 < n; row0 += TR) {                // the workgroup's 256 rows, TR at a time
-    const int nr = n - row0 < TR ? n - row0 : TR, ne = nr * k, lt = (int)threadIdx.x - (row0 - blk0);
-    const size_t at = (size_t)row0 * k;
-    if (XUP) {
-      pl_in<KMAX>(t0, X + at, ne, k);
-      pl_in<KMAX>(t1, P + at, ne, k);
-      __syncthreads();
-      if (lt >= 0 && lt < nr) {                               // the thread that owns row row0 + lt
-        double *x = t0 + lt * LD;
-        const double *p = t1 + lt * LD;
-#pragma unroll
-        for (int c = 0; c < KMAX; ++c)
-          if (c < k && ((live >> c) & 1u) != 0u) x[c] = x[c] + al[c] * p[c];
-      }
-      __syncthreads();
-      pl_out<KMAX>(X + at, t0, ne, k, live);
-      __syncthreads();
-    }
-    pl_in<KMAX>(t0, R + at, ne, k);
-    pl_in<KMAX>(t1, Q + at, ne, k);
-    __syncthreads();
-    if (lt >= 0 && lt < nr) {                                 // the thread that owns row row0 + lt
-      double *r = t0 + lt * LD;
-      const double *q = t1 + lt * LD;
-      const double di = dinv ? dinv[row0 + lt] : 1.0;
-#pragma unroll
-      for (int c = 0; c < KMAX; ++c)
-        if (c < k && ((live >> c) & 1u) != 0u) {
-          if constexpr (sizeof...(LAM) != 0) {
-            const double ri = r[c] - al[c] * q[c];
-            r[c] = ri;
-            rr[c] += ri * ri;
-            const double zi = ri * pn_inv(di, lam[c]); rz[c] += ri * zi;
-          } else {
-            const double ri = r[c] - al[c] * q[c];
-            r[c] = ri;
-            rr[c] += ri * ri;
-            if (dinv) { const double zi = ri * di; rz[c] += ri * zi; }
-          }
-        }
-    }
-    __syncthreads();
-    pl_out<KMAX>(R + at, t0, ne, k, live);
-    __syncthreads();
-  }
+  pl_sweep<KMAX>(n, k, live, [&](auto pass) {
+    if (XUP) pass(X, P, nullptr, [&](int c, double x0, double p, double) { return pn_x(x0, al[c], p); });
+    pass(R, Q, dinv, [&](int c, double r0, double q, double di) {
+      const double r = pn_r(r0, al[c], q, rr[c]);
+      if (sizeof...(LAM) != 0 || dinv) rz[c] += r * pn_z(r, dinv != nullptr, di, colj, c);
+      return r;
+    });
+  });
   pcgn_block_sums<KMAX>(k, live, dinv ? 2 : 1, rr, rz, part);
 }
 
@@ -1134,42 +1088,14 @@ __global__ __launch_bounds__(kRedThreads) void pcgn_direction_lds_kernel(int n, 
                                                                         const double *__restrict__ cs, LAM... lambda)
 {
   if (st[kStDone] != 0.0) return;
-  constexpr int LD = KMAX + 1;
-  constexpr int TR = pl_rows<KMAX>();
-  __shared__ double t0[TR * LD], t1[TR * LD];
-  __shared__ double lam[sizeof...(LAM) != 0 ? KMAX : 1];
-  if constexpr (sizeof...(LAM) != 0) pl_lambdas<KMAX>(lam, lambda...);
+  const auto colj = pl_lambdas<KMAX>(lambda...);
   const unsigned live = pcgn_live(st);
   double be[KMAX];
 #pragma unroll
   for (int c = 0; c < KMAX; ++c) be[c] = cs[c * kPnStride + kPnBeta];
-  for (int blk0 = blockIdx.x * kRedThreads; blk0 < n; blk0 += gridDim.x * kRedThreads)      // (workgroup-uniform)
-  for (int row0 = blk0; row0 < blk0 + kRedThreads && row0 < n; row0 += TR) {                // the workgroup's 256 rows, TR at a time
-    const int nr = n - row0 < TR ? n - row0 : TR, ne = nr * k, lt = (int)threadIdx.x - (row0 - blk0);
-    const size_t at = (size_t)row0 * k;
-    pl_in<KMAX>(t0, P + at, ne, k);
-    pl_in<KMAX>(t1, R + at, ne, k);
-    __syncthreads();
-    if (lt >= 0 && lt < nr) {                                 // the thread that owns row row0 + lt
-      double *p = t0 + lt * LD;
-      const double *r = t1 + lt * LD;
-      const double di = dinv ? dinv[row0 + lt] : 1.0;
-#pragma unroll
-      for (int c = 0; c < KMAX; ++c)
-        if (c < k && ((live >> c) & 1u) != 0u) {
-          if constexpr (sizeof...(LAM) != 0) {
-            const double zi = r[c] * pn_inv(di, lam[c]);
-            p[c] = zi + be[c] * p[c];
-          } else {
-            const double zi = dinv ? r[c] * di : r[c];
-            p[c] = zi + be[c] * p[c];
-          }
-        }
-    }
-    __syncthreads();
-    pl_out<KMAX>(P + at, t0, ne, k, live);
-    __syncthreads();
-  }
+  pl_sweep<KMAX>(n, k, live, [&](auto pass) {
+    pass(P, R, dinv, [&](int c, double p0, double r, double di) { return pn_direction(pn_z(r, dinv != nullptr, di, colj, c), be[c], p0); });
+  });
 }
 
 // stage 2 of the ns sums of every live column, kPcgnGroup sums' loads in flight together: sum v = column * ns + s is fs_cg's stage 2
@@ -1645,23 +1571,17 @@ __global__ __launch_bounds__(kRedThreads) void mscgn_direction_kernel(size_t ne,
 
 // the kernels' shape for k columns: KMAX = 4, 8, 16 or 32 sums per thread, VEC as in pcgn_init_kernel
 template <int KMAX, int VEC> struct PcgnShape { static constexpr int kmax = KMAX, vec = VEC; };
+template <int KMAX, typename F>
+int pcgn_dispatch_vec(int vec, F f)
+{
+  return vec == 0 ? f(PcgnShape<KMAX, 0>{}) : vec == 1 ? f(PcgnShape<KMAX, 1>{}) : f(PcgnShape<KMAX, 2>{});
+}
+
 template <typename F>
 int pcgn_dispatch(int k, int vec, F f)
 {
-  switch ((k <= 4 ? 0 : k <= 8 ? 1 : k <= 16 ? 2 : 3) * 3 + vec) {
-    case 0: return f(PcgnShape<4, 0>{});
-    case 1: return f(PcgnShape<4, 1>{});
-    case 2: return f(PcgnShape<4, 2>{});
-    case 3: return f(PcgnShape<8, 0>{});
-    case 4: return f(PcgnShape<8, 1>{});
-    case 5: return f(PcgnShape<8, 2>{});
-    case 6: return f(PcgnShape<16, 0>{});
-    case 7: return f(PcgnShape<16, 1>{});
-    case 8: return f(PcgnShape<16, 2>{});
-    case 9: return f(PcgnShape<32, 0>{});
-    case 10: return f(PcgnShape<32, 1>{});
-    default: return f(PcgnShape<32, 2>{});
-  }
+  return k <= 4 ? pcgn_dispatch_vec<4>(vec, f) : k <= 8 ? pcgn_dispatch_vec<8>(vec, f) : k <= 16 ? pcgn_dispatch_vec<16>(vec, f)
+                                                                                                   : pcgn_dispatch_vec<32>(vec, f);
 }
 
 struct Workspace {
@@ -1889,25 +1809,24 @@ static int pcgn_start_step(int n, int k, int vec, const double *R, const double 
   return rc;
 }
 
-// option "pcgn_kernel" picks the form of the per-iteration vector kernels
-static bool pcgn_staged(int k)
+// a per-iteration vector kernel in the form that option "pcgn_kernel" picks: the two forms of a step take the same arguments
+template <typename K, typename... A>
+static int pcgn_form_launch(int k, K *staged, K *rows, hipStream_t s, A... a)
 {
   const int which = options().pcgn_kernel;
-  const bool staged = which == 2 || (which == 0 && k > kPcgnRowsMaxK);
-  return staged;
+  K *const kernel = which == 2 || (which == 0 && k > kPcgnRowsMaxK) ? staged : rows;
+  hipLaunchKernelGGL(kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, a...);
+  return FS_OK;
 }
 
 // behind Q = A'(A P): Q += lambda P, q.p; alpha = r.z / p.q
 template <typename LAM>
 static int pcgn_shift_dot_step(int n, int k, int vec, const LAM &lambda, double *Q, const double *P, const PcgnSums &U, hipStream_t s)
 {
-  const dim3 g(kRedBlocks), blk(kRedThreads);
-  const bool staged = pcgn_staged(k);
   const int rc = pcgn_dispatch(k, vec, [&](auto sh) -> int {
     using S = decltype(sh);
-    if (staged) hipLaunchKernelGGL((pcgn_shift_dot_lds_kernel<S::kmax, LAM>), g, blk, 0, s, n, k, lambda, Q, P, U.part, U.st);
-    else        hipLaunchKernelGGL((pcgn_shift_dot_kernel<S::kmax, S::vec, LAM>), g, blk, 0, s, n, k, lambda, Q, P, U.part, U.st);
-    return FS_OK;
+    return pcgn_form_launch(k, pcgn_shift_dot_lds_kernel<S::kmax, LAM>, pcgn_shift_dot_kernel<S::kmax, S::vec, LAM>, s,
+                            n, k, lambda, Q, P, U.part, U.st);
   });
   pcgn_sums_launch(kPnStepAlpha, U, k, 1, 0.0, s);                                                           // alpha = r.z / p.q
   return rc;
@@ -1918,21 +1837,17 @@ template <typename... CJ>
 static int pcgn_update_step(int n, int k, int vec, double *X, double *R, const double *P, const double *Q, const double *dinv,
                             const PcgnSums &U, hipStream_t s, CJ... colj)
 {
-  const dim3 g(kRedBlocks), blk(kRedThreads);
-  const bool staged = pcgn_staged(k);
   const int rc = pcgn_dispatch(k, vec, [&](auto sh) -> int {
     using S = decltype(sh);
     auto launch = [&](auto xup) {
       constexpr bool XUP = decltype(xup)::value;
-      if (staged) hipLaunchKernelGGL((pcgn_update_lds_kernel<S::kmax, XUP, CJ...>), g, blk, 0, s, n, k, X, R, P, Q, dinv, U.part, U.st, U.cs, colj...);
-      else        hipLaunchKernelGGL((pcgn_update_kernel<S::kmax, S::vec, XUP, CJ...>), g, blk, 0, s, n, k, X, R, P, Q, dinv, U.part, U.st, U.cs, colj...);
+      return pcgn_form_launch(k, pcgn_update_lds_kernel<S::kmax, XUP, CJ...>, pcgn_update_kernel<S::kmax, S::vec, XUP, CJ...>, s,
+                              n, k, X, R, P, Q, dinv, U.part, U.st, U.cs, colj...);
     };
     if constexpr (sizeof...(CJ) == 0) {
-      if (X) launch(std::true_type{}); else launch(std::false_type{});   // X NULL (fs_mscgn): r and its sums only
-    } else {
-      launch(std::true_type{});
+      if (!X) return launch(std::false_type{});                          // X NULL (fs_mscgn): r and its sums only
     }
-    return FS_OK;
+    return launch(std::true_type{});
   });
   pcgn_sums_launch(kPnStepBeta, U, k, dinv ? 2 : 1, 0.0, s);                                                 // converged? beta
   return rc;
@@ -1943,13 +1858,10 @@ template <typename... CJ>
 static int pcgn_direction_step(int n, int k, int vec, double *P, const double *R, const double *dinv, const PcgnSums &U, hipStream_t s,
                                CJ... colj)
 {
-  const dim3 g(kRedBlocks), blk(kRedThreads);
-  const bool staged = pcgn_staged(k);
   const int rc = pcgn_dispatch(k, vec, [&](auto sh) -> int {
     using S = decltype(sh);
-    if (staged) hipLaunchKernelGGL((pcgn_direction_lds_kernel<S::kmax, CJ...>), g, blk, 0, s, n, k, P, R, dinv, U.st, U.cs, colj...);
-    else        hipLaunchKernelGGL((pcgn_direction_kernel<S::kmax, S::vec, CJ...>), g, blk, 0, s, n, k, P, R, dinv, U.st, U.cs, colj...);
-    return FS_OK;
+    return pcgn_form_launch(k, pcgn_direction_lds_kernel<S::kmax, CJ...>, pcgn_direction_kernel<S::kmax, S::vec, CJ...>, s,
+                            n, k, P, R, dinv, U.st, U.cs, colj...);
   });
   FS_HIP(hipGetLastError());
   return rc;
@@ -1993,19 +1905,24 @@ int pcgn_dev_steps(int n, int k, double lambda, double *X, const double *B, doub
 }
 
 // fs_pcgn_lambdas' instantiations on whole panels (fs_pcgn_lambdas; fs_dist_pcgn_lambdas replicated, on every rank).  colj: dinv
-// holds s = diag(A'A) at 0.0 and every column inverts s + lambda_c (FS_PRECOND_JACOBI)
+// holds s = diag(A'A) at 0.0 and every column inverts s + lambda_c (FS_PRECOND_JACOBI): f takes the k lambdas again as its
+// trailing argument, or none
+template <typename F>
+static int pcgn_with_colj(bool colj, const PcgnLambdas &lv, F f)
+{
+  return colj ? f(lv) : f();
+}
+
 int pcgn_dev_init_lambdas(int n, int k, bool warm, const PcgnLambdas &lv, bool colj, const double *B, double *X, double *R, double *P,
                           double *Q, const double *dinv, double *part, double *st, double *cs, double tol, hipStream_t s)
 {
-  return colj ? pcgn_init_launch(n, k, warm, lv, B, X, R, P, Q, dinv, part, st, cs, tol, s, lv)
-              : pcgn_init_launch(n, k, warm, lv, B, X, R, P, Q, dinv, part, st, cs, tol, s);
+  return pcgn_with_colj(colj, lv, [&](auto... cj) { return pcgn_init_launch(n, k, warm, lv, B, X, R, P, Q, dinv, part, st, cs, tol, s, cj...); });
 }
 
 int pcgn_dev_steps_lambdas(int n, int k, const PcgnLambdas &lv, bool colj, double *X, const double *B, double *R, double *P, double *Q,
                            const double *dinv, double *part, double *st, double *cs, hipStream_t s)
 {
-  return colj ? pcgn_steps_launch(n, k, lv, X, B, R, P, Q, dinv, part, st, cs, s, lv)
-              : pcgn_steps_launch(n, k, lv, X, B, R, P, Q, dinv, part, st, cs, s);
+  return pcgn_with_colj(colj, lv, [&](auto... cj) { return pcgn_steps_launch(n, k, lv, X, B, R, P, Q, dinv, part, st, cs, s, cj...); });
 }
 
 // the same steps one by one on a rank's slice of n rows (fs_dist_pcgn_lambdas on slices): U.send is the rank's send slot, the
@@ -2021,8 +1938,7 @@ int pcgn_slice_init(int n, int k, bool warm, const PcgnLambdas &lv, const double
 int pcgn_slice_start(int n, int k, const PcgnLambdas &lv, bool colj, const double *X, const double *B, const double *R, const double *dinv,
                      double *P, const PcgnSums &U, hipStream_t s)
 {
-  if (int rc = colj ? pcgn_start_step(n, k, pcgn_vec(k, X, B), R, dinv, P, U, s, lv) : pcgn_start_step(n, k, pcgn_vec(k, X, B), R, dinv, P, U, s))
-    return rc;
+  if (int rc = pcgn_with_colj(colj, lv, [&](auto... cj) { return pcgn_start_step(n, k, pcgn_vec(k, X, B), R, dinv, P, U, s, cj...); })) return rc;
   FS_HIP(hipGetLastError());
   return FS_OK;
 }
@@ -2038,8 +1954,8 @@ int pcgn_slice_shift_dot(int n, int k, const PcgnLambdas &lv, const double *X, c
 int pcgn_slice_update(int n, int k, const PcgnLambdas &lv, bool colj, double *X, const double *B, double *R, const double *P,
                       const double *Q, const double *dinv, const PcgnSums &U, hipStream_t s)
 {
-  if (int rc = colj ? pcgn_update_step(n, k, pcgn_vec(k, X, B), X, R, P, Q, dinv, U, s, lv)
-                    : pcgn_update_step(n, k, pcgn_vec(k, X, B), X, R, P, Q, dinv, U, s)) return rc;
+  if (int rc = pcgn_with_colj(colj, lv, [&](auto... cj) { return pcgn_update_step(n, k, pcgn_vec(k, X, B), X, R, P, Q, dinv, U, s, cj...); }))
+    return rc;
   FS_HIP(hipGetLastError());
   return FS_OK;
 }
@@ -2047,7 +1963,7 @@ int pcgn_slice_update(int n, int k, const PcgnLambdas &lv, bool colj, double *X,
 int pcgn_slice_direction(int n, int k, const PcgnLambdas &lv, bool colj, const double *X, const double *B, double *P, const double *R,
                          const double *dinv, const PcgnSums &U, hipStream_t s)
 {
-  return colj ? pcgn_direction_step(n, k, pcgn_vec(k, X, B), P, R, dinv, U, s, lv) : pcgn_direction_step(n, k, pcgn_vec(k, X, B), P, R, dinv, U, s);
+  return pcgn_with_colj(colj, lv, [&](auto... cj) { return pcgn_direction_step(n, k, pcgn_vec(k, X, B), P, R, dinv, U, s, cj...); });
 }
 
 // the slice sums of every rank, gathered (`all`: rank r's ns * k values at r * ns * k): stage 2 over the ranks in rank order per

@@ -122,7 +122,9 @@ def test_names_are_the_sources():
                    "pcg_update_kernel,", "cg_direction_dev_kernel,", "pcg_direction_kernel,"):
         assert src["fs_cg.hip"].count("hipLaunchKernelGGL(" + kernel) == 1, kernel
     for kernel in ("pcgn_init_kernel", "pcgn_start_kernel", "pcgn_update_kernel", "pcgn_update_lds_kernel", "pcgn_direction_kernel"):
-        assert len(re.findall(r"hipLaunchKernelGGL\(\(?" + kernel + "<", src["fs_cg.hip"])) == 1, kernel
+        # (an instantiation is named nowhere but in its launch: directly, or as one of the two forms pcgn_form_launch picks from)
+        assert len(re.findall(r"(?:hipLaunchKernelGGL\(\(?|pcgn_form_launch\(k, (?:\w+<[^>]*>, )?)" + kernel + "<", src["fs_cg.hip"])) == 1, kernel
+        assert len(re.findall(r"\b" + kernel + "<", src["fs_cg.hip"])) == 1, kernel
     # one dispatch from (step, sums) to the scalar step, for the whole-vector path and cg_dev_final: it knows fs_pcg's steps, each once
     for step, nvs in (("kStepPcgStart", "2"), ("kStepPcgRz", "1"), ("kStepPcgBeta", "12")):
         assert step in DP.FINAL_STEPS

@@ -45,7 +45,10 @@ def test_launchers_are_the_sources():
     # one launch site per vector kernel, for whole panels and slices, fs_pcgn and fs_pcgn_lambdas alike
     for kernel in ("pcgn_init_kernel", "pcgn_start_kernel", "pcgn_shift_dot_kernel", "pcgn_shift_dot_lds_kernel", "pcgn_update_kernel",
                    "pcgn_update_lds_kernel", "pcgn_direction_kernel", "pcgn_direction_lds_kernel"):
-        assert len(re.findall(r"hipLaunchKernelGGL\(\(?" + kernel + "<", cg)) == 1, kernel
+        # (an instantiation is named nowhere but in its launch: directly, or as one of the two forms pcgn_form_launch picks from)
+        assert len(re.findall(r"(?:hipLaunchKernelGGL\(\(?|pcgn_form_launch\(k, (?:\w+<[^>]*>, )?)" + kernel + "<", cg)) == 1, kernel
+        assert len(re.findall(r"\b" + kernel + "<", cg)) == 1, kernel
+    assert cg.count("hipLaunchKernelGGL(kernel, dim3(kRedBlocks), dim3(kRedThreads), 0, s, a...);") == 1
     assert cg.count("hipLaunchKernelGGL(pcgn_fold_kernel,") == 1
     # one copy of the scalar lines: the step kernel is defined once and instantiated for partials and for gathered rank values
     assert cg.count("void pcgn_step_kernel(") == 1 and cg.count("e[kPnAlpha] = e[kPnRz] / s0;") == 1

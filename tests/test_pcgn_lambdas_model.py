@@ -59,20 +59,30 @@ def test_arithmetic_is_the_sources():
     src = _squeezed(M.CSRC, "fs_cg.hip")
     for line in ("const double d = s + lambda; return d == 0.0 ? 1.0 : 1.0 / d;",
                  "dinv[i] = di == 0.0 ? 1.0 : 1.0 / di;",
-                 # init (warm), shift-dot
-                 "const Pair q = {q0.a + lambda.v[c] * x.a, q0.b + lambda.v[c + 1] * x.b};",
-                 "const Pair q = {q0.a + lambda.v[c] * p.a, q0.b + lambda.v[c + 1] * p.b};",
-                 "const double qi = q[c] + lam[c] * pi; q[c] = qi; qp[c] += qi * pi;",
-                 "if (threadIdx.x < KMAX) lam[threadIdx.x] = lambda.v[threadIdx.x];",
+                 # column c's lambda: by value in the lane-per-row kernels, from the table in LDS in the staged ones
+                 "double pn_lambda(const PcgnLambdas &lambda, int c) { return lambda.v[c]; }",
+                 "double pn_lambda(const double *lam, int c) { return lam[c]; }",
+                 "__shared__ double lam[KMAX]; if (threadIdx.x < KMAX) lam[threadIdx.x] = lambda.v[threadIdx.x]; return lam;",
+                 # init (warm), shift-dot: fs_pcgn's lines with pn_lambda(lambda, c)
+                 "const Pair r = {pn_init(warm, q.a, pn_lambda(lambda, c), x.a, b.a, bb[c], rr[c]), "
+                 "pn_init(warm, q.b, pn_lambda(lambda, c + 1), x.b, b.b, bb[c + 1], rr[c + 1])};",
+                 "const Pair q = {pn_shift_dot(q0.a, pn_lambda(lambda, c), p.a, qp[c]), pn_shift_dot(q0.b, pn_lambda(lambda, c + 1), p.b, qp[c + 1])};",
+                 "const auto lam = pl_lambdas<KMAX>(lambda);",
+                 "pass(Q, P, nullptr, [&](int c, double q0, double p, double) { return pn_shift_dot(q0, pn_lambda(lam, c), p, qp[c]); });",
                  # start, update, direction: z = r dinv_c
-                 "const Pair z = {r.a * pn_inv(di, lambda.v[c]...), r.b * pn_inv(di, lambda.v[c + 1]...)};",
-                 "const double zi = ri * pn_inv(di, lam[c]); rz[c] += ri * zi;",
-                 "const double zi = r[c] * pn_inv(di, lam[c]); p[c] = zi + be[c] * p[c];",
+                 "else return r * pn_inv(di, pn_lambda(colj, c));",
+                 "const auto &colj = pn_colj(lambda...);",
+                 "const auto colj = pl_lambdas<KMAX>(lambda...);",
+                 "const PcgnLambdas &pn_colj(const PcgnLambdas &lambda) { return lambda; }",
+                 "if (sizeof...(LAM) != 0 || dinv) rz[c] += r * pn_z(r, dinv != nullptr, di, colj, c);",
+                 "return pn_direction(pn_z(r, dinv != nullptr, di, colj, c), be[c], p0);",
                  # the host: one s per solve, no inverse pass
                  "if (int rc = fs_gram_diag(At, colj ? 0.0 : lambda, dinv, stream)) return rc;",
                  "if (pre && !colj)"):
         assert line in src, line
-    assert src.count("const Pair z = {r.a * pn_inv(di, lambda.v[c]...), r.b * pn_inv(di, lambda.v[c + 1]...)};") == 3
+    # one copy of the per-column inverse; the three lane-per-row kernels and the two staged ones that form z take it through pn_z
+    assert src.count("pn_inv(") == 2 and src.count("const auto &colj = pn_colj(lambda...);") == 3
+    assert src.count("const auto colj = pl_lambdas<KMAX>(lambda...);") == 2
     assert "-ffast-math" not in _squeezed(M.ROOT, "libfastsparse_amd", "_build.py")      # 1.0 / d stays an IEEE division
     assert "-ffp-contract=off" in _squeezed(M.ROOT, "libfastsparse_amd", "_build.py")
 

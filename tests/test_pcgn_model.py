@@ -43,32 +43,42 @@ def test_arithmetic_is_the_sources():
     """the lines of fs_cg.hip that fs_pcgn's model (fs_pcg's, per column) restates"""
     src = _squeezed(M.CSRC, "fs_cg.hip")
     for line in ("const int cap = prm->max_iter > 0 ? prm->max_iter : F;",
-                 # init: cold and warm
-                 "const Pair q = {q0.a + lambda * x.a, q0.b + lambda * x.b};",
-                 "r = {b.a - q.a, b.b - q.b};",
-                 "pn_st<VEC == 2>(X + row + c, {0.0, 0.0}, l0, l1);",
-                 "bb[c] += b.a * b.a; bb[c + 1] += b.b * b.b; rr[c] += r.a * r.a; rr[c + 1] += r.b * r.b;",
+                 # the column steps, each formula written once -- init: cold and warm
+                 "if (warm) q = q + l * x; const double r = warm ? b - q : b; bb += b * b; rr += r * r; return r;",
+                 # shift-dot
+                 "const double q = q0 + l * p; qp += q * p; return q;",
+                 # update
+                 "double pn_x(double x0, double al, double p) { return x0 + al * p; }",
+                 "const double r = r0 - al * q; rr += r * r; return r;",
+                 # z of r, direction
+                 "if constexpr (std::is_same<CJ, PnOneDiag>::value) return pre ? r * di : r;",
+                 "double pn_direction(double z, double be, double p0) { return z + be * p0; }",
+                 "double pn_lambda(double lambda, int) { return lambda; }",
+                 # the lane-per-row kernels: the steps on the two columns of a pair -- init
+                 "const Pair r = {pn_init(warm, q.a, pn_lambda(lambda, c), x.a, b.a, bb[c], rr[c]), "
+                 "pn_init(warm, q.b, pn_lambda(lambda, c + 1), x.b, b.b, bb[c + 1], rr[c + 1])};",
+                 "if (warm) pn_st<VEC >= 1>(Q + row + c, q, l0, l1); else pn_st<VEC == 2>(X + row + c, {0.0, 0.0}, l0, l1);",
                  # start
-                 "const Pair z = {dinv ? r.a * di : r.a, dinv ? r.b * di : r.b};",
+                 "const Pair r = v[0][h], z = {pn_z(r.a, dinv != nullptr, di, colj, c), pn_z(r.b, dinv != nullptr, di, colj, c + 1)};",
                  "rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;",
                  # shift-dot
-                 "const Pair q = {q0.a + lambda * p.a, q0.b + lambda * p.b};",
-                 "qp[c] += q.a * p.a; qp[c + 1] += q.b * p.b;",
+                 "const Pair q = {pn_shift_dot(q0.a, pn_lambda(lambda, c), p.a, qp[c]), pn_shift_dot(q0.b, pn_lambda(lambda, c + 1), p.b, qp[c + 1])};",
                  # update
-                 "const Pair x = {x0.a + al[c] * p.a, x0.b + al[c + 1] * p.b};",
-                 "const Pair r = {r0.a - al[c] * q.a, r0.b - al[c + 1] * q.b};",
-                 "rr[c] += r.a * r.a; rr[c + 1] += r.b * r.b;",
-                 "const Pair z = {r.a * di, r.b * di}; rz[c] += r.a * z.a; rz[c + 1] += r.b * z.b;",
+                 "const Pair x = {pn_x(x0.a, al[c], p.a), pn_x(x0.b, al[c + 1], p.b)};",
+                 "const Pair r = {pn_r(r0.a, al[c], q.a, rr[c]), pn_r(r0.b, al[c + 1], q.b, rr[c + 1])};",
+                 "if (sizeof...(LAM) != 0 || dinv) { rz[c] += r.a * pn_z(r.a, dinv != nullptr, di, colj, c); "
+                 "rz[c + 1] += r.b * pn_z(r.b, dinv != nullptr, di, colj, c + 1); }",
                  # direction
-                 "const Pair p = {z.a + be[c] * p0.a, z.b + be[c + 1] * p0.b};",
-                 # the same steps on the panels staged through LDS
-                 "const double qi = q[c] + lambda * pi; q[c] = qi; qp[c] += qi * pi;",
-                 "x[c] = x[c] + al[c] * p[c];",
-                 "const double ri = r[c] - al[c] * q[c]; r[c] = ri; rr[c] += ri * ri; if (dinv) { const double zi = ri * di; rz[c] += ri * zi; }",
-                 "const double zi = dinv ? r[c] * di : r[c]; p[c] = zi + be[c] * p[c];",
+                 "const Pair p = {pn_direction(z.a, be[c], p0.a), pn_direction(z.b, be[c + 1], p0.b)};",
+                 # the same steps on the panels staged through LDS, column by column on the owning thread's row
+                 "if (c < k && ((live >> c) & 1u) != 0u) a[c] = col(c, a[c], b[c], di);",
+                 "pass(Q, P, nullptr, [&](int c, double q0, double p, double) { return pn_shift_dot(q0, pn_lambda(lam, c), p, qp[c]); });",
+                 "if (XUP) pass(X, P, nullptr, [&](int c, double x0, double p, double) { return pn_x(x0, al[c], p); });",
+                 "const double r = pn_r(r0, al[c], q, rr[c]); if (sizeof...(LAM) != 0 || dinv) rz[c] += r * pn_z(r, dinv != nullptr, di, colj, c); return r;",
+                 "pass(P, R, dinv, [&](int c, double p0, double r, double di) { return pn_direction(pn_z(r, dinv != nullptr, di, colj, c), be[c], p0); });",
                  "for (int blk0 = blockIdx.x * kRedThreads; blk0 < n; blk0 += gridDim.x * kRedThreads)",
                  "for (int row0 = blk0; row0 < blk0 + kRedThreads && row0 < n; row0 += TR) {",
-                 "const bool staged = which == 2 || (which == 0 && k > kPcgnRowsMaxK);",
+                 "K *const kernel = which == 2 || (which == 0 && k > kPcgnRowsMaxK) ? staged : rows;",
                  # the row a thread owns and where its partial goes
                  "for (int i = blockIdx.x * kRedThreads + threadIdx.x; i < n; i += gridDim.x * kRedThreads) { const size_t row = (size_t)i * k;",
                  "part[(size_t)v * kRedBlocks + blockIdx.x] = s;",
@@ -85,6 +95,10 @@ def test_arithmetic_is_the_sources():
                  # one-time work before anything is written
                  "if (int rc = fs_matrix_prepare(A, k, 0, stream)) return rc; if (int rc = fs_matrix_prepare(At, k, 0, stream)) return rc;"):
         assert line in src, line
+    # one copy of each column formula and of each sweep, whatever the kernel, the form and the source of lambda
+    for once in ("q0 + l * p", "q + l * x", "x0 + al * p", "r0 - al * q", "z + be * p0", "pn_inv(di,",
+                 "i += gridDim.x * kRedThreads) { const size_t row = (size_t)i * k;", "pl_in<KMAX>(t1,", "pl_out<KMAX>("):
+        assert src.count(once) == 1, once
 
 
 @pytest.mark.parametrize("kind", list(N.KIND_ID))
