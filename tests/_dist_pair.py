@@ -9,16 +9,16 @@ import numpy as np
 import _cg_model as M
 import _pcg_model as P
 
-# the systems of test_gpu_cg.DIST_SET whose two transposes differ, and whose plain-CG model differs in bits between them
+# the systems of _solvers.DIST_SET whose two transposes differ, and whose plain-CG model differs in bits between them
 SIX = ("binary_F65", "ill_conditioned", "cap_tol0", "cg2_equal_columns", "lambda0_empty_column", "valued")
 # entry order differs, the model's x does not (b = 0) / A' has the same order either way
 SAME_X = ("zero_rhs",)
 SAME_ORDER = ("fixture_100x50", "three_eigenvalues")
 NAMED = ("fixture_100x50", "binary_F65", "ill_conditioned", "cap_tol0", "three_eigenvalues", "zero_rhs", "cg2_equal_columns",
-         "lambda0_empty_column", "valued")                   # test_gpu_cg.DIST_SET without binary_F262145
+         "lambda0_empty_column", "valued")                   # _solvers.DIST_SET without binary_F262145
 RECIPES0 = ("scaled_seed0", "powerlaw_seed0", "control_seed0")
 ROUTES = ("coo", "cuts", "dev")
-# the classes of fs_dist_pcg solves that each need a case whose bits tell the two transposes apart: case numbers of test_gpu_pcg.CASES
+# the classes of fs_dist_pcg solves that each need a case whose bits tell the two transposes apart: case numbers of _solvers.CASES
 CLASSES = {"no preconditioner": (0,), "Jacobi": (1, 5), "caller's diagonal": (2,), "warm start": (3, 4, 6)}
 _SYSTEMS = {}
 

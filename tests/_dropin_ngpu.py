@@ -261,27 +261,28 @@ def exact():
 
 def cg():
     """bsbm_cg / bsbm_cg2 on the row-sharded path (fs_dist_cg / fs_dist_cg2 on the pair of A and At): under strict_order the bits
-    of the CPU model (tests/_cg_model.py) over the CSRs the library holds; on the exact systems of tests/test_gpu_cg.py the exact
+    of the CPU model (tests/_cg_model.py) over the CSRs the library holds; on the exact systems of tests/_solvers.py the exact
     answer in every mode"""
     import _cg_model as CM
-    import test_gpu_cg as G
+    import _gpu as G
+    import _solvers as SV
     with G.options(strict_order=1):
         for name in ("fixture_100x50", "binary_F257", "ill_conditioned", "cap_tol0", "zero_rhs", "cg2_equal_columns"):
-            s = G.SYSTEMS[name]
+            s = SV.SYSTEMS[name]
             for two in ((False, True) if s.two else (False,)):
                 before = L.fs_debug_dist_products()
-                x, it, st, (a_csr, t_csr) = G.dropin_run(L, s, two)
+                x, it, st, (a_csr, t_csr) = SV.dropin_run(L, s, two)
                 assert L.fs_debug_dist_products() - before >= 2 * max(it, 1), (name, two, it)
                 am, atm, am2, atm2 = CM.csr_products(s.nrow, s.ncol, a_csr, t_csr)
                 model = CM.cg2(s.ncol, am2, atm2, s.B, s.lam, s.tol) if two else CM.cg(s.ncol, am, atm, s.b, s.lam, s.tol)
-                G._assert_model(f"bsbm_cg{'2' if two else ''}, 3 ranks", s, two, x, it, st, model)
+                SV.assert_cg_model(f"bsbm_cg{'2' if two else ''}, 3 ranks", s, two, x, it, st, model)
                 print("cg", name, "cg2" if two else "cg", it, "iterations, bit for bit", flush=True)
-    for mode in G.MODES:
-        for s, scale in G.EXACT[:2]:
+    for mode in G.SOLVER_MODES:
+        for s, scale in SV.EXACT[:2]:
             for two in (False, True):
-                with G._mode(mode):
-                    x, it, st, _ = G.dropin_run(L, s, two)
-                G._assert_exact("bsbm_cg, 3 ranks", mode, s, scale, two, x, it, st)
+                with G.mode_options(mode):
+                    x, it, st, _ = SV.dropin_run(L, s, two)
+                SV.assert_exact("bsbm_cg, 3 ranks", mode, s, scale, two, x, it, st)
         print("cg exact", mode, flush=True)
     L.fs_release_all()
 

@@ -22,6 +22,16 @@ import numpy as np
 
 import _cases
 
+# forced copy -> (options at creation, kernel name)
+PATHS = {
+    "stream": (dict(binning=0, ldsx=0, tiling=0), "stream"),
+    "two-pass": (dict(binning=2, bin_flags=64), "two-pass"),
+    "two-pass one-byte": (dict(binning=2, bin_flags=128), "two-pass"),
+    "long rows": (dict(binning=2, long_rows=2, long_min_len=32), "two-pass"),      # (a copy of >= 4 M entries: test_long_rows_are_exact)
+    "lds-staged": (dict(ldsx=2, binning=0, tiling=0), "lds-staged"),
+    "tiled cut rows": (dict(tiling=2, binning=0, ldsx=0, tile_rows=64, tile_cols=128, tile_split=5), "tiled"),
+}
+
 TWO53 = 2 ** 53
 
 

@@ -12,7 +12,6 @@ Shapes (both on exactly summable data, tests/_exact.py D2: a = +-odd(1..15) x 2^
              prints `OK <case>` (then `TIME <case> <seconds>`) per case, `FAIL <case>: <message>` at the first case that raises,
              and exits non-zero there.  tests/test_gpu_two_pass_large_bands.py starts it once and asserts case by case.
 tests/test_large_bands_shapes.py holds the shapes to what is said here, on the CPU, from tests/_plan_model.py."""
-import contextlib
 import ctypes as C
 import os
 import sys
@@ -27,10 +26,9 @@ if __name__ == "__main__":
 
 import _exact as E  # noqa: E402
 import _plan_model as M  # noqa: E402
+from _gpu import PRODUCT_MODES as MODES, mode_options as _mode, options, to_device as _d  # noqa: E402
 
 BIG, SMALL = M.K_BIN_COLS_BIG, M.K_BIN_COLS          # 19 456 and 16 384: band widths, and the tallest panels, of the two forms
-MODES = ("default", "reproducible", "strict_order")
-FS_ERR_ARG = -2
 BINNED_COLS = 3                                      # fs_matrix_spmm_plan: one single-vector two-pass sweep per column
 NAN_COL = 18_000                                     # D: a column of band 0 whose local id is above 16 383
 K = 3
@@ -154,32 +152,6 @@ def _lib():
     L.fs_debug_long_rows.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
     L.fs_debug_last_spmm_plan.argtypes = []
     return L
-
-
-@contextlib.contextmanager
-def options(**kw):
-    """set library options, restore the values they had on the way out (an option without a getter is refused)"""
-    from libfastsparse_amd import capi
-    L = capi.lib()
-    old = {k: L.fs_get_option(k.encode()) for k in kw}
-    assert all(v != FS_ERR_ARG for v in old.values()), old
-    try:
-        for k, v in kw.items():
-            capi.set_option(k, v)
-        yield
-    finally:
-        for k, v in old.items():
-            capi.set_option(k, v)
-
-
-def _mode(mode):
-    """"default" is arrival order, said so: a process started with FS_REPRODUCIBLE=1 runs these tests as well"""
-    return options(**({"reproducible": 0} if mode == "default" else {mode: 1}))
-
-
-def _d(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _poisoned(shape, fill):

@@ -18,8 +18,9 @@ import pytest
 import _cg_model as M
 import _dist_pair as DPair
 import _dist_pcg_model as DP
+import _dist_solvers as DV
 import _pcg_model as P
-import test_gpu_dist_pcg as GD
+import _solvers as SV
 
 SYSTEMS = DPair.systems()
 
@@ -44,24 +45,24 @@ def test_the_systems_that_are_no_evidence():
         assert not DPair.same_arrays(s.t_csr_coo(), s.t_csr_sorted())
         assert M.same_bits(s.model(False, t_csr=s.t_csr_coo()).x, s.model(False, t_csr=s.t_csr_sorted()).x).all()
     assert set(DPair.SIX + DPair.SAME_ORDER + DPair.SAME_X) == set(DPair.NAMED)
-    assert set(DPair.NAMED + DPair.RECIPES0) == set(GD.ALL) - {"binary_F262145"} == set(SYSTEMS)
+    assert set(DPair.NAMED + DPair.RECIPES0) == set(DV.ALL) - {"binary_F262145"} == set(SYSTEMS)
 
 
 # ---- (b) ------------------------------------------------------------------------------------------------------------------
 def test_every_class_of_pcg_solve_has_cases_that_differ():
     """the caller's diagonal and x0 are the GPU test's (from the caller's A'), the same for both models: only A' changes.  The recipes
     (300 unknowns, a shuffled COO) are solved in all seven cases; the named systems add to the count where they are quick"""
-    assert set(c for cs in DPair.CLASSES.values() for c in cs) == set(range(len(GD.CASES)))
+    assert set(c for cs in DPair.CLASSES.values() for c in cs) == set(range(len(SV.CASES)))
     differ = {}
     for name in DPair.RECIPES0 + ("binary_F65", "cap_tol0"):
         s = SYSTEMS[name]
         coo, srt = s.t_csr_coo(), s.t_csr_sorted()
-        for case in range(len(GD.CASES)):
-            what, precond, x0, max_iter, diag = GD._case_args(s, case, coo)
+        for case in range(len(SV.CASES)):
+            what, precond, x0, max_iter, diag = DV.case_args(s, case, coo)
             a, b = (DP.run(s, precond, max_iter=max_iter, x0=x0, t_csr=t, diag=diag) for t in (coo, srt))
             differ[(name, case)] = int((~M.same_bits(a.x, b.x)).sum())
     for cls, cases in DPair.CLASSES.items():
-        hits = sorted((n, GD.CASES[c][0]) for (n, c), d in differ.items() if c in cases and d >= 1)
+        hits = sorted((n, SV.CASES[c][0]) for (n, c), d in differ.items() if c in cases and d >= 1)
         print(f"{cls}: {len(hits)} of {sum(c in cases for _, c in differ)} (system, case) pairs differ in the bits of x")
         assert hits, cls
         assert {n for n, _ in hits} >= set(DPair.RECIPES0), (cls, hits)       # (every recipe is evidence for every class)

@@ -16,6 +16,7 @@ import pytest
 import _cg_model as M
 import _dist_pcg_model as DP
 import _pcg_model as P
+from _solvers import caller_diag as _caller_diag, x0 as _x0
 
 KINDS = ("scaled", "powerlaw", "control")
 SEEDS = (0, 1, 2)
@@ -30,15 +31,6 @@ def _recipe(kind, seed):
     if (kind, seed) not in _RECIPES:
         _RECIPES[(kind, seed)] = P.recipe(kind, seed)
     return _RECIPES[(kind, seed)]
-
-
-def _caller_diag(s):
-    d = P.gram_diag(s.t_csr_coo(), s.lam)
-    return np.abs(d) * (1.0 + 0.5 * np.cos(np.arange(s.ncol) * 1.7)) + 0.125
-
-
-def _x0(s):
-    return 0.5 * np.sin(np.arange(s.ncol) * 0.37 + 0.2) * np.linalg.norm(s.b) / max(1.0, np.sqrt(s.ncol))
 
 
 def _pair(s, case, bounds):

@@ -1,6 +1,6 @@
 """fs_dist_mscg on virtual ranks of one device (fs_dist_create(n, [0] * n)), against the CPU models (tests/_mscg_model.py,
-_dist_mscg_model.py) and against the single-device and the other sharded solvers, in the idioms of test_gpu_dist_pcg.py and
-test_gpu_mscg.py.  A' of every model is dist.t_csr(): the shards' own rows, downloaded.
+_dist_mscg_model.py) and against the single-device and the other sharded solvers, on the harness of tests/_solvers.py and
+tests/_dist_solvers.py.  A' of every model is dist.t_csr(): the shards' own rows, downloaded.
 
 1  strict_order, scheme 0: X, the infos, st[] and the per-shift array are the whole-tree model's on 1 and 3 ranks, A' built on the
    host and on the device, ladders m1 / m3 / m8 (shuffled), uncapped and under a cap of 5, X in host memory and in HBM, packed and
@@ -16,95 +16,32 @@ test_gpu_mscg.py.  A' of every model is dist.t_csr(): the shards' own rows, down
 8  statuses, with X untouched by every refused call; a product's own error is passed through.
 9  guard zones, interleaved solves on one handle, device memory given back.
 10 a pair handle: the caller's entry order of A' and the caller's cuts."""
+import contextlib
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import _cg_model as M
-import _dist_mscg_model as DS
 import _dist_pair as DPair
+import _dist_solvers as DV
+import _gpu as G
 import _lifecycle as LC
 import _mscg_model as S
 import _pcg_model as P
-import test_gpu_cg as GC
-import test_gpu_dist_pcg as GD
-import test_gpu_mscg as GM
-import test_gpu_pcg as G
+import _solvers as SV
+from _gpu import FS_ERR_ARG, FS_ERR_NO_TRANSPOSE, FS_ERR_RELEASED, FS_OK, L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-FS_OK, FS_ERR_ARG, FS_ERR_NO_TRANSPOSE, FS_ERR_RELEASED = 0, -2, -4, -5
-RECIPES0 = {n: G.RECIPES[n] for n in ("control_seed0", "powerlaw_seed0")}
-ALL = dict({n: GC.SYSTEMS[n] for n in GC.DIST_SET}, **RECIPES0)
-SMALL = [n for n in ALL if n != "binary_F262145"]                    # (the models are Python: the large system runs once per scheme)
-LADDERS = {k: GM.LADDERS[k] for k in ("m1", "m3", "m8")}
-lams_of = GM.lams_of
-options = GC.options
-GAP_BITS = LC.PREFILLS["nan"]
-_MODELS = {}
-
-
-@pytest.fixture(scope="module")
-def L():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    from libfastsparse_amd import capi
-    lib = capi.lib()
-    lib.fs_debug_last_cg_state.argtypes = [C.c_void_p]
-    lib.fs_debug_last_mscg_state.argtypes = [C.c_void_p, C.c_int]
-    lib.fs_debug_last_pcgn_state.argtypes = [C.c_void_p, C.c_int]
-    lib.fs_debug_dist_products.restype = C.c_long
-    lib.fs_debug_dist_products.argtypes = []
-    lib.fs_debug_last_spmm_plan.argtypes = []
-    return lib
-
-
-def dmscg(L, dist, s, lams, max_iter=0, tol=None, b=None, hbm=False, ldx=None):
-    """fs_dist_mscg through capi.dist_mscg: X (m, F), the infos, rank 0's st[] by name and per-shift array by name.  X lies in one
-    buffer of (m - 1) ldx + F doubles, host memory or HBM; the gaps between the x_i must keep their bits"""
-    from libfastsparse_amd import capi
-    m, F = len(lams), s.ncol
-    ldx = F if ldx is None else ldx
-    n = (m - 1) * ldx + F
-    if hbm:
-        import torch
-        buf = torch.empty(max(n, 1), dtype=torch.float64, device="cuda")
-        buf.view(torch.int64).fill_(GAP_BITS)
-        X = buf.as_strided((m, F), (ldx, 1))
-    else:
-        buf = np.full(max(n, 1), GAP_BITS, np.int64).view(np.float64)
-        X = np.lib.stride_tricks.as_strided(buf, (m, F), (ldx * 8, 8))
-    infos = capi.dist_mscg(dist.M, X, GD._put(s.b if b is None else b, hbm), lams, s.tol if tol is None else tol, max_iter)
-    raw = np.full(S.MAX_SHIFTS * S.MS_STRIDE, np.nan)
-    assert L.fs_debug_last_mscg_state(raw.ctypes.data, raw.size) == m * S.MS_STRIDE
-    got = GD._np(buf)
-    gaps = np.concatenate([got[i * ldx + F:(i + 1) * ldx] for i in range(m - 1)] + [np.zeros(0)])
-    assert (gaps.view(np.int64) == GAP_BITS).all(), "a gap between the x_i was written"
-    return np.stack([got[i * ldx:i * ldx + F] for i in range(m)]), infos, S.state_from_device(G._raw_state(L)), S.shifts_from_device(raw, m)
-
-
-def _model(s, ladder, cap, t_csr, bounds=None, lams=None, tol=None):
-    """the (slice) model of a solve on the A' the shards hold, once per case"""
-    key = (s.name, ladder, cap, tol, None if bounds is None else tuple(bounds), t_csr[1].tobytes(), None if t_csr[2] is None else t_csr[2].tobytes())
-    if key not in _MODELS:
-        _MODELS[key] = DS.run(s, lams_of(s, ladder) if lams is None else lams, max_iter=cap, tol=tol, t_csr=t_csr, bounds=bounds)
-    return _MODELS[key]
-
-
-def _assert_model(what, got, model):
-    X, infos, st, shifts = got
-    bad = M.mismatch(X, model.X, [i.iterations for i in infos], [i.iterations for i in model.infos], st, model.state)
-    assert bad is None, f"{what}: {bad}"
-    bad = S.shifts_mismatch(shifts, model.shifts)
-    assert bad is None, f"{what}: {bad}"
-    GM._assert_infos(what, infos, model.infos)
+SMALL = [n for n in DV.MSCG_ALL if n != "binary_F262145"]                    # (the models are Python: the large system runs once per scheme)
+LADDERS = {k: SV.LADDERS[k] for k in ("m1", "m3", "m8")}
 
 
 def _assert_same_solve(what, got, want):
     """two device solves: X, the infos and the per-shift array, bit for bit"""
     assert M.same_bits(got[0], want[0]).all(), what
-    GM._assert_infos(what, got[1], [S.Info(i.iterations, i.converged, i.rnorm, i.bnorm) for i in want[1]])
+    SV.assert_infos(what, got[1], [S.Info(i.iterations, i.converged, i.rnorm, i.bnorm) for i in want[1]])
     bad = S.shifts_mismatch(got[3], want[3])
     assert bad is None, (what, bad)
 
@@ -112,28 +49,28 @@ def _assert_same_solve(what, got, want):
 # ---- 1 ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", SMALL)
 def test_scheme0_strict_is_fs_mscg(L, name):
-    s = ALL[name]
+    s = DV.MSCG_ALL[name]
     F = s.ncol
     single = {}
     n = 0
     for ranks, device_t in ((1, False), (3, False), (3, True), (1, True)):
-        dist = GC.Dist(L, s, ranks, device_t)
+        dist = DV.Dist(L, s, ranks, device_t)
         try:
-            t_csr = GD._sorted_t(dist, s)
-            with options(strict_order=1, dist_cg_scheme=0):
+            t_csr = DV.sorted_t(dist, s)
+            with G.options(strict_order=1, dist_cg_scheme=0):
                 for ladder in LADDERS:
                     for cap in (0, 5):
                         n += 1
                         hbm, ldx = n % 2 == 1, F + 3 * (n // 2 % 2)
-                        lams = lams_of(s, ladder)
-                        got = dmscg(L, dist, s, lams, cap, hbm=hbm, ldx=ldx)
+                        lams = SV.lams_of(s, ladder)
+                        got = DV.dmscg(L, dist, s, lams, cap, hbm=hbm, ldx=ldx)
                         what = (f"fs_dist_mscg scheme 0 {ladder} cap {cap}, {ranks} ranks, {'device' if device_t else 'host'} A', "
                                 f"{'HBM' if hbm else 'host'} vectors, ldx {ldx}, on {name}")
-                        _assert_model(what, got, _model(s, ladder, cap, t_csr))
+                        DV.assert_dmscg_model(what, got, DV.dmscg_model(s, ladder, cap, t_csr))
                         if ranks == 3 and not device_t:              # a single-device fs_mscg on the same CSRs
                             if not single:
-                                single["h"] = GD._single_handles(L, s)
-                            _assert_same_solve(what + " vs fs_mscg", got, GM.mscg_run(L, single["h"][0], single["h"][1], s, lams, cap, ldx=ldx))
+                                single["h"] = SV.single_handles(L, s)
+                            _assert_same_solve(what + " vs fs_mscg", got, SV.mscg_run(L, single["h"][0], single["h"][1], s, lams, cap, ldx=ldx))
                         if name == "zero_rhs":
                             assert all(i.converged == 1 and i.iterations == 0 for i in got[1]) and M.same_bits(got[0], np.zeros(got[0].shape)).all()
         finally:
@@ -141,16 +78,16 @@ def test_scheme0_strict_is_fs_mscg(L, name):
 
 
 def test_scheme0_more_than_one_grid_stride_capped(L):
-    s = ALL["binary_F262145"]
-    lams = lams_of(s, "m3")
-    single = GD._single_handles(L, s)
-    dist = GC.Dist(L, s, 3, False)
+    s = DV.MSCG_ALL["binary_F262145"]
+    lams = SV.lams_of(s, "m3")
+    single = SV.single_handles(L, s)
+    dist = DV.Dist(L, s, 3, False)
     try:
-        t_csr = GD._sorted_t(dist, s)
-        with options(strict_order=1, dist_cg_scheme=0):
-            got = dmscg(L, dist, s, lams, 5, hbm=True, ldx=s.ncol + 3)
-            _assert_model("fs_dist_mscg scheme 0 m3 cap 5 on binary_F262145", got, _model(s, "m3", 5, t_csr))
-            _assert_same_solve("binary_F262145 vs fs_mscg", got, GM.mscg_run(L, single[0], single[1], s, lams, 5))
+        t_csr = DV.sorted_t(dist, s)
+        with G.options(strict_order=1, dist_cg_scheme=0):
+            got = DV.dmscg(L, dist, s, lams, 5, hbm=True, ldx=s.ncol + 3)
+            DV.assert_dmscg_model("fs_dist_mscg scheme 0 m3 cap 5 on binary_F262145", got, DV.dmscg_model(s, "m3", 5, t_csr))
+            _assert_same_solve("binary_F262145 vs fs_mscg", got, SV.mscg_run(L, single[0], single[1], s, lams, 5))
         assert [i.iterations for i in got[1]] == [5, 5, 5] and not any(i.converged for i in got[1])
     finally:
         dist.close()
@@ -159,96 +96,96 @@ def test_scheme0_more_than_one_grid_stride_capped(L):
 # ---- 2 ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", SMALL)
 def test_scheme1_strict_is_the_slice_model(L, name):
-    s = ALL[name]
+    s = DV.MSCG_ALL[name]
     F = s.ncol
     n = 0
     for device_t in (False, True):
-        dist = GC.Dist(L, s, 3, device_t)
+        dist = DV.Dist(L, s, 3, device_t)
         try:
             bounds = dist.bounds_t()
             assert bounds[0] == 0 and bounds[-1] == F
-            t_csr = GD._sorted_t(dist, s)
-            if name in RECIPES0:                                     # on the CPU first: the slice tree is told from the whole one
-                whole, sliced = _model(s, "m8", 0, t_csr), _model(s, "m8", 0, t_csr, bounds)
+            t_csr = DV.sorted_t(dist, s)
+            if name in DV.MSCG_RECIPES0:                                     # on the CPU first: the slice tree is told from the whole one
+                whole, sliced = DV.dmscg_model(s, "m8", 0, t_csr), DV.dmscg_model(s, "m8", 0, t_csr, bounds)
                 differ = [int((~M.same_bits(whole.X[i], sliced.X[i])).sum()) for i in range(len(whole.infos))]
                 print(f"{name} bounds {bounds}: entries of {F} that differ between the slice model and the whole model, per shift: {differ}")
                 # (these are the handle's own cuts, not _dist_mscg_model.DIFFERING_BOUNDS: a shift large enough to converge in its
                 # first iterations may keep its bits, the ladder as a whole must not)
                 assert all(a < b for a, b in zip(bounds, bounds[1:])) and sum(d >= 1 for d in differ) >= len(differ) // 2, (name, bounds, differ)
-            with options(strict_order=1, dist_cg_scheme=1):
+            with G.options(strict_order=1, dist_cg_scheme=1):
                 for ladder in LADDERS:
                     for cap in (0, 5):
                         n += 1
                         hbm, ldx = n % 2 == 0, F + 3 * (n // 2 % 2)
-                        got = dmscg(L, dist, s, lams_of(s, ladder), cap, hbm=hbm, ldx=ldx)
+                        got = DV.dmscg(L, dist, s, SV.lams_of(s, ladder), cap, hbm=hbm, ldx=ldx)
                         what = f"fs_dist_mscg scheme 1 {ladder} cap {cap}, bounds {bounds}, {'HBM' if hbm else 'host'} vectors, ldx {ldx}, on {name}"
-                        _assert_model(what, got, _model(s, ladder, cap, t_csr, bounds))
+                        DV.assert_dmscg_model(what, got, DV.dmscg_model(s, ladder, cap, t_csr, bounds))
         finally:
             dist.close()
 
 
 def test_scheme1_with_empty_slices(L):
     """five ranks on the three rows of A': some slices are empty and contribute +0.0"""
-    s = ALL["three_eigenvalues"]
-    dist = GC.Dist(L, s, 5, False)
+    s = DV.MSCG_ALL["three_eigenvalues"]
+    dist = DV.Dist(L, s, 5, False)
     try:
         bounds = dist.bounds_t()
         assert any(a == b for a, b in zip(bounds, bounds[1:])), bounds
-        t_csr = GD._sorted_t(dist, s)
-        with options(strict_order=1, dist_cg_scheme=1):
+        t_csr = DV.sorted_t(dist, s)
+        with G.options(strict_order=1, dist_cg_scheme=1):
             for ladder in LADDERS:
                 for cap in (0, 2):
-                    got = dmscg(L, dist, s, lams_of(s, ladder), cap, hbm=cap == 2)
-                    _assert_model(f"fs_dist_mscg scheme 1 {ladder} cap {cap}, bounds {bounds}", got, _model(s, ladder, cap, t_csr, bounds))
+                    got = DV.dmscg(L, dist, s, SV.lams_of(s, ladder), cap, hbm=cap == 2)
+                    DV.assert_dmscg_model(f"fs_dist_mscg scheme 1 {ladder} cap {cap}, bounds {bounds}", got, DV.dmscg_model(s, ladder, cap, t_csr, bounds))
     finally:
         dist.close()
 
 
 def test_scheme1_more_than_one_grid_stride_capped(L):
-    s = ALL["binary_F262145"]
-    dist = GC.Dist(L, s, 3, True)
+    s = DV.MSCG_ALL["binary_F262145"]
+    dist = DV.Dist(L, s, 3, True)
     try:
         bounds = dist.bounds_t()
-        t_csr = GD._sorted_t(dist, s)
-        with options(strict_order=1, dist_cg_scheme=1):
-            got = dmscg(L, dist, s, lams_of(s, "m3"), 5, ldx=s.ncol + 3)
-        _assert_model(f"fs_dist_mscg scheme 1 m3 cap 5 on binary_F262145, bounds {bounds}", got, _model(s, "m3", 5, t_csr, bounds))
+        t_csr = DV.sorted_t(dist, s)
+        with G.options(strict_order=1, dist_cg_scheme=1):
+            got = DV.dmscg(L, dist, s, SV.lams_of(s, "m3"), 5, ldx=s.ncol + 3)
+        DV.assert_dmscg_model(f"fs_dist_mscg scheme 1 m3 cap 5 on binary_F262145, bounds {bounds}", got, DV.dmscg_model(s, "m3", 5, t_csr, bounds))
     finally:
         dist.close()
 
 
 # ---- 3 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(RECIPES0))
+@pytest.mark.parametrize("name", list(DV.MSCG_RECIPES0))
 def test_large_shifts_freeze_on_slices(L, name):
-    s = RECIPES0[name]
+    s = DV.MSCG_RECIPES0[name]
     lams = [s.lam, s.lam + 1e6, s.lam + 1e9]
-    dist = GC.Dist(L, s, 3, False)
+    dist = DV.Dist(L, s, 3, False)
     try:
         bounds = dist.bounds_t()
-        t_csr = GD._sorted_t(dist, s)
-        with options(strict_order=1, dist_cg_scheme=1):
-            got = dmscg(L, dist, s, lams, tol=1e-14, hbm=True)
+        t_csr = DV.sorted_t(dist, s)
+        with G.options(strict_order=1, dist_cg_scheme=1):
+            got = DV.dmscg(L, dist, s, lams, tol=1e-14, hbm=True)
         X, infos, st, shifts = got
         print(f"{name}: counts {[i.iterations for i in infos]}, rnorm {[i.rnorm for i in infos]}")
         assert np.isfinite(X).all() and all(np.isfinite(v).all() for v in shifts.values()), name
         assert all(i.converged == 1 for i in infos), (name, [(i.iterations, i.converged) for i in infos])
-        _assert_model(f"fs_dist_mscg scheme 1 large shifts on {name}", got, _model(s, "large", 0, t_csr, bounds, lams=lams, tol=1e-14))
+        DV.assert_dmscg_model(f"fs_dist_mscg scheme 1 large shifts on {name}", got, DV.dmscg_model(s, "large", 0, t_csr, bounds, lams=lams, tol=1e-14))
     finally:
         dist.close()
 
 
 # ---- 4 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mode", GC.MODES)
+@pytest.mark.parametrize("mode", G.SOLVER_MODES)
 def test_one_lambda_is_fs_dist_pcg_without_preconditioner(L, mode):
     for name in SMALL:
-        s = ALL[name]
-        dist = GC.Dist(L, s, 3, False)
+        s = DV.MSCG_ALL[name]
+        dist = DV.Dist(L, s, 3, False)
         try:
             for scheme in (0, 1):
                 for cap in (0, 5):
-                    with GC._mode(mode), options(dist_cg_scheme=scheme):
-                        xp, ip, stp = GD.dpcg(L, dist, s, max_iter=cap)
-                        X, infos, st, _ = dmscg(L, dist, s, [s.lam], cap)
+                    with G.mode_options(mode), G.options(dist_cg_scheme=scheme):
+                        xp, ip, stp = DV.dpcg(L, dist, s, max_iter=cap)
+                        X, infos, st, _ = DV.dmscg(L, dist, s, [s.lam], cap)
                     want = dict(stp)
                     if ip.converged == 1 and ip.iterations == 0 and M.same_bits(xp, np.zeros(s.ncol)).all():
                         for k in ("rsq", "alpha", "beta"):           # done before the first iteration: fs_pcg never writes these
@@ -258,26 +195,26 @@ def test_one_lambda_is_fs_dist_pcg_without_preconditioner(L, mode):
                     what = (name, mode, scheme, cap)
                     bad = M.mismatch(X[0], xp, infos[0].iterations, ip.iterations, st, want)
                     assert bad is None, (what, bad)
-                    GM._assert_infos(what, infos, [S.Info(ip.iterations, ip.converged, ip.rnorm, ip.bnorm)])
+                    SV.assert_infos(what, infos, [S.Info(ip.iterations, ip.converged, ip.rnorm, ip.bnorm)])
         finally:
             dist.close()
 
 
 # ---- 5 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mode", GC.MODES)
+@pytest.mark.parametrize("mode", G.SOLVER_MODES)
 def test_columns_of_the_smallest_lambda_are_fs_dist_cg(L, mode):
     for name in SMALL:
-        s = ALL[name]
+        s = DV.MSCG_ALL[name]
         if not np.any(s.b != 0):
             continue
-        dist = GC.Dist(L, s, 3, False)
+        dist = DV.Dist(L, s, 3, False)
         try:
             for scheme in (0, 1):
-                with GC._mode(mode), options(dist_cg_scheme=scheme):
+                with G.mode_options(mode), G.options(dist_cg_scheme=scheme):
                     xc, itc, stc = dist.cg(False)
                     for ladder in ("m3", "m8"):
-                        lams = lams_of(s, ladder)
-                        X, infos, st, shifts = dmscg(L, dist, s, lams)
+                        lams = SV.lams_of(s, ladder)
+                        X, infos, st, shifts = DV.dmscg(L, dist, s, lams)
                         cols = [i for i, lam in enumerate(lams) if lam == min(lams)]
                         assert min(lams) == s.lam and len(cols) == {"m3": 2, "m8": 1}[ladder]
                         for i in cols:
@@ -293,10 +230,10 @@ def assert_default_mode_bars(L, dist, s):
     """the ladder of eight in the default mode, both schemes, on any handle with a transposed side"""
     lams = [s.lam * f for f in S.LADDER]
     for scheme in (0, 1):
-        with options(dist_cg_scheme=scheme):
-            runs = [dmscg(L, dist, s, lams, hbm=scheme == 1) for _ in range(2)]
+        with G.options(dist_cg_scheme=scheme):
+            runs = [DV.dmscg(L, dist, s, lams, hbm=scheme == 1) for _ in range(2)]
         X, infos, _, _ = runs[0]
-        res = [GM._residual(s, lam, X[i]) for i, lam in enumerate(lams)]
+        res = [SV.residual(s, X[i], lam) for i, lam in enumerate(lams)]
         print(f"{s.name} scheme {scheme}: counts {[i.iterations for i in infos]}, true residuals / tol {[round(r / s.tol, 2) for r in res]}")
         for i, lam in enumerate(lams):
             what = (s.name, scheme, i, lam, infos[i].iterations, res[i])
@@ -306,10 +243,10 @@ def assert_default_mode_bars(L, dist, s):
         assert M.same_bits(runs[1][0], X).all() and [i.iterations for i in runs[1][1]] == [i.iterations for i in infos], (s.name, scheme)
 
 
-@pytest.mark.parametrize("name", list(RECIPES0))
+@pytest.mark.parametrize("name", list(DV.MSCG_RECIPES0))
 def test_default_mode_ladder_within_the_bars(L, name):
-    s = RECIPES0[name]
-    dist = GC.Dist(L, s, 3, False)
+    s = DV.MSCG_RECIPES0[name]
+    dist = DV.Dist(L, s, 3, False)
     try:
         assert_default_mode_bars(L, dist, s)
     finally:
@@ -317,34 +254,28 @@ def test_default_mode_ladder_within_the_bars(L, name):
 
 
 # ---- 7 ---------------------------------------------------------------------------------------------------------------------
-PRODUCT_SET = ("three_eigenvalues", "cap_tol0", "fixture_100x50") + tuple(RECIPES0)
+PRODUCT_SET = ("three_eigenvalues", "cap_tol0", "fixture_100x50") + tuple(DV.MSCG_RECIPES0)
 
 
 @pytest.mark.parametrize("name", PRODUCT_SET)
 def test_sharded_products_per_solve(L, name):
     """fs_debug_dist_products() per solve, strict mode, three ranks: per_iter x min(cap, st[iter] + 2) with per_iter = 2 sharded products
     (replicate) or 1 (slices: A' is the rank's own shard); none for a solve that is done at its start"""
-    s = ALL[name]
+    s = DV.MSCG_ALL[name]
     F = s.ncol
-    dist = GC.Dist(L, s, 3, False)
-
-    def counted(f):
-        before = L.fs_debug_dist_products()
-        out = f()
-        return L.fs_debug_dist_products() - before, out
-
+    dist = DV.Dist(L, s, 3, False)
     try:
         for scheme, per_iter in ((0, 2), (1, 1)):
-            with options(strict_order=1, dist_cg_scheme=scheme):
+            with G.options(strict_order=1, dist_cg_scheme=scheme):
                 for ladder in ("m1", "m8"):
                     for max_iter in (0, 2):
-                        n, (X, infos, st, _) = counted(lambda: dmscg(L, dist, s, lams_of(s, ladder), max_iter))
+                        n, (X, infos, st, _) = DV.counted(L, lambda: DV.dmscg(L, dist, s, SV.lams_of(s, ladder), max_iter))
                         at_start = st["done"] == 1.0 and st["iter"] == 0.0 and bool(M.same_bits(X, np.zeros(X.shape)).all())
                         what = (name, scheme, ladder, max_iter, n, st["iter"], st["done"], at_start)
                         print(*what)
-                        assert n == per_iter * GD._loops(max_iter or F, int(st["iter"]), at_start), what
+                        assert n == per_iter * DV.loops(max_iter or F, int(st["iter"]), at_start), what
                 for tol, b in ((s.tol, np.zeros(F)), (1.0, s.b), (2.5, s.b)):        # done at the start: b = 0, tol >= 1
-                    n, (X, infos, st, _) = counted(lambda: dmscg(L, dist, s, lams_of(s, "m3"), tol=tol, b=b))
+                    n, (X, infos, st, _) = DV.counted(L, lambda: DV.dmscg(L, dist, s, SV.lams_of(s, "m3"), tol=tol, b=b))
                     assert n == 0, (name, scheme, tol, n)
                     assert all(i.converged == 1 and i.iterations == 0 for i in infos) and M.same_bits(X, np.zeros(X.shape)).all(), (name, scheme, tol)
     finally:
@@ -354,12 +285,8 @@ def test_sharded_products_per_solve(L, name):
 # ---- 8 ---------------------------------------------------------------------------------------------------------------------
 def test_statuses(L):
     from libfastsparse_amd import capi
-    s = RECIPES0["control_seed0"]
-    dist = GC.Dist(L, s, 3, False)
-    rp, cc, vv = s.a_csr()
-    M_not = L.fs_dist_csr_create(dist.D, s.nrow, s.ncol, len(cc), rp.ctypes.data, cc.ctypes.data, vv.ctypes.data)   # no transposed side
-    assert M_not
-    try:
+    s = DV.MSCG_RECIPES0["control_seed0"]
+    with contextlib.closing(DV.Dist(L, s, 3, False)) as dist, DV.handle_without_transpose(L, dist, s) as M_not:
         F, m = s.ncol, 3
         b, X = s.b.copy(), np.full(16 * F, np.nan)
         bits = X.view(np.int64).copy()
@@ -372,7 +299,7 @@ def test_statuses(L):
             return L.fs_dist_mscg(M_, X_, ldx, b_, m_, arr, tol, max_iter, info)
 
         for scheme in (0, 1):
-            with options(dist_cg_scheme=scheme):
+            with G.options(dist_cg_scheme=scheme):
                 bad = {"NULL M": call(M_=None), "NULL X": call(X_=None), "NULL b": call(b_=None), "NULL lambda": call(lam=None),
                        "m 0": call(m_=0), "m -1": call(m_=-1), "m 17": call(m_=17), "ldx < F": call(ldx=F - 1), "ldx 0": call(ldx=0),
                        "tol < 0": call(tol=-1e-8), "tol NaN": call(tol=float("nan")), "tol -inf": call(tol=float("-inf")),
@@ -382,7 +309,7 @@ def test_statuses(L):
                 assert all(rc == FS_ERR_ARG for rc in bad.values()), (scheme, bad)
                 assert L.fs_last_error()
                 assert call(M_=M_not) == FS_ERR_NO_TRANSPOSE
-                assert np.array_equal(X.view(np.int64), bits), "a refused call wrote to X"
+                SV.refused_call_leaves(X, bits)
                 assert call(tol=0.0, max_iter=2) == FS_OK            # tol = 0 is legal: the cap ends it (info NULL is legal too)
                 assert call(m_=16) == FS_OK
                 infos = (capi.PcgInfo * m)()
@@ -390,66 +317,63 @@ def test_statuses(L):
                 assert [i.iterations for i in infos] == [2, 2, 2] and not any(i.converged for i in infos)
                 assert call(lam=[-0.25, s.lam, 0.0], max_iter=3) == FS_OK   # a negative lambda is the caller's business
                 X.view(np.int64)[:] = bits
-    finally:
-        L.fs_dist_matrix_destroy(M_not)
-        dist.close()
 
 
 def test_a_product_error_is_passed_through(L):
     """fs_matrix_release_csr on ONE rank's shard of A': under strict_order a product reads the plain CSR, so the solve ends with
     FS_ERR_RELEASED and the product's message, X untouched; outside strict_order the kept copy serves and the solve is the one from
     before the release"""
-    s = G.RECIPES["scaled_seed0"]                                    # (the system test_gpu_dist_pcg.py releases a shard of; plain CG
-    lams = lams_of(s, "m3")                                          # does not converge on it: the solves run under a cap)
+    s = SV.RECIPES["scaled_seed0"]                                    # (the system test_gpu_dist_pcg.py releases a shard of; plain CG
+    lams = SV.lams_of(s, "m3")                                          # does not converge on it: the solves run under a cap)
     arr = (C.c_double * len(lams))(*lams)
-    with options(binning=2, bin_flags=64):                           # kept two-pass copies: there is something to release for
-        dist = GC.Dist(L, s, 3, False)
+    with G.options(binning=2, bin_flags=64):                           # kept two-pass copies: there is something to release for
+        dist = DV.Dist(L, s, 3, False)
     try:
         before = {}
         for scheme in (0, 1):
-            with options(dist_cg_scheme=scheme):
-                before[scheme] = dmscg(L, dist, s, lams, 20)
+            with G.options(dist_cg_scheme=scheme):
+                before[scheme] = DV.dmscg(L, dist, s, lams, 20)
                 assert np.isfinite(before[scheme][0]).all()
         assert L.fs_matrix_release_csr(L.fs_dist_matrix_shard(dist.M, 1, 1)) == 1
         for scheme in (0, 1):
             X = np.full(len(lams) * s.ncol, np.nan)
             bits = X.view(np.int64).copy()
-            with options(strict_order=1, dist_cg_scheme=scheme):
+            with G.options(strict_order=1, dist_cg_scheme=scheme):
                 assert L.fs_dist_mscg(dist.M, X.ctypes.data, s.ncol, s.b.ctypes.data, len(lams), arr, s.tol, 20, None) == FS_ERR_RELEASED, scheme
                 assert b"fs_matrix_release_csr" in L.fs_last_error()
-            assert np.array_equal(X.view(np.int64), bits), (scheme, "a refused solve wrote to X")
-            with options(dist_cg_scheme=scheme):
-                after = dmscg(L, dist, s, lams, 20)                  # the kept copy needs no plain array
+            SV.refused_call_leaves(X, bits, (scheme, "a refused solve wrote to X"))
+            with G.options(dist_cg_scheme=scheme):
+                after = DV.dmscg(L, dist, s, lams, 20)                  # the kept copy needs no plain array
             _assert_same_solve(("after the release", scheme), after, before[scheme])
     finally:
         dist.close()
 
 
 # ---- 9 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(RECIPES0))
+@pytest.mark.parametrize("name", list(DV.MSCG_RECIPES0))
 def test_guard_zones(L, name):
     """X (packed and padded) and b in HBM inside guard zones, 16-byte aligned and 8 bytes off: guards untouched, b unchanged, the gaps
     between the x_i keep their bits, and the solution does not depend on where X lies"""
     import torch
     from libfastsparse_amd import capi
     mem = LC.TorchMem()
-    s = RECIPES0[name]
+    s = DV.MSCG_RECIPES0[name]
     F = s.ncol
-    dist = GC.Dist(L, s, 3, False)
+    dist = DV.Dist(L, s, 3, False)
     try:
         gx, gb = LC.Guarded(mem, "X of fs_dist_mscg", 8 * (F + 3)), LC.Guarded(mem, "b of fs_dist_mscg", F)
         for scheme in (0, 1):
             for ladder, cap in (("m1", 0), ("m3", 0), ("m8", 0), ("m8", 5)):
-                lams = lams_of(s, ladder)
+                lams = SV.lams_of(s, ladder)
                 m = len(lams)
                 ref = None
                 for ldx in (F, F + 3):
                     for off in (0, 1):
                         mem.put(gb.place(F, off ^ (ldx & 1)), s.b)
                         n = (m - 1) * ldx + F
-                        mem.fill_bits(gx.place(n, off), GAP_BITS)
+                        mem.fill_bits(gx.place(n, off), SV.GAP_BITS)
                         infos = (capi.PcgInfo * m)()
-                        with options(dist_cg_scheme=scheme):
+                        with G.options(dist_cg_scheme=scheme):
                             capi.check(L.fs_dist_mscg(dist.M, gx.view.data_ptr(), ldx, gb.view.data_ptr(), m, (C.c_double * m)(*lams), s.tol, cap,
                                                       infos), "fs_dist_mscg")
                         torch.cuda.synchronize()
@@ -457,10 +381,8 @@ def test_guard_zones(L, name):
                         bad = mem.first_bad_guard([gx, gb])
                         assert bad is None, (what, bad.first_broken())
                         assert mem.eq(gb.view, mem.const(s.b)), (what, "b changed")
-                        got = mem.get(gx.view)
-                        X = np.stack([got[i * ldx:i * ldx + F] for i in range(m)])
-                        gaps = np.concatenate([got[i * ldx + F:(i + 1) * ldx] for i in range(m - 1)] + [np.zeros(0)])
-                        assert (gaps.view(np.int64) == GAP_BITS).all(), (what, "a gap between the x_i was written")
+                        X, gaps = SV.split_rows_and_gaps(mem.get(gx.view), m, F, ldx)
+                        assert (gaps.view(np.int64) == SV.GAP_BITS).all(), (what, "a gap between the x_i was written")
                         assert np.isfinite(X).all(), what
                         if not cap:
                             assert all(i.converged == 1 for i in infos), (what, [i.iterations for i in infos])
@@ -475,49 +397,23 @@ def test_interleaved_solves_share_the_work_space_and_give_it_back(L):
     """solves of fs_dist_cg, fs_dist_pcg, fs_dist_pcgn and fs_dist_mscg (m3, then m8: the work space grows; both schemes) interleaved
     on one handle keep their bits; after fs_dist_matrix_destroy free device memory is back where it was before the handle existed,
     within one solve's work space"""
-    import torch
-    import test_gpu_pcgn as GN
-    s = RECIPES0["control_seed0"]
-    B2 = GN.columns(s, 2)
+    s = DV.MSCG_RECIPES0["control_seed0"]
+    B2 = SV.columns(s, 2)
     ranks = 3
 
     def kinds(dist):
-        def with_scheme(scheme, f):
-            def run():
-                with options(dist_cg_scheme=scheme):
-                    return f()
-            return run
-        m3, m8 = lams_of(s, "m3"), lams_of(s, "m8")
-        return [with_scheme(0, lambda: dist.cg(False)[0]), with_scheme(0, lambda: dmscg(L, dist, s, m3)[0]),
-                with_scheme(1, lambda: GD.dpcg(L, dist, s, P.PRECOND_JACOBI)[0]), with_scheme(1, lambda: dmscg(L, dist, s, m3, hbm=True)[0]),
-                lambda: GD.dpcgn(L, dist, s, B2, P.PRECOND_JACOBI)[0], with_scheme(0, lambda: dmscg(L, dist, s, m8, ldx=s.ncol + 3)[0]),
-                with_scheme(1, lambda: dist.cg(False)[0]), with_scheme(1, lambda: dmscg(L, dist, s, m8)[0]),
-                with_scheme(0, lambda: GD.dpcg(L, dist, s, P.PRECOND_JACOBI)[0]), with_scheme(1, lambda: dmscg(L, dist, s, m3, max_iter=5)[0])]
+        m3, m8 = SV.lams_of(s, "m3"), SV.lams_of(s, "m8")
+        return [DV.with_scheme(0, lambda: dist.cg(False)[0]), DV.with_scheme(0, lambda: DV.dmscg(L, dist, s, m3)[0]),
+                DV.with_scheme(1, lambda: DV.dpcg(L, dist, s, P.PRECOND_JACOBI)[0]), DV.with_scheme(1, lambda: DV.dmscg(L, dist, s, m3, hbm=True)[0]),
+                lambda: DV.dpcgn(L, dist, s, B2, P.PRECOND_JACOBI)[0], DV.with_scheme(0, lambda: DV.dmscg(L, dist, s, m8, ldx=s.ncol + 3)[0]),
+                DV.with_scheme(1, lambda: dist.cg(False)[0]), DV.with_scheme(1, lambda: DV.dmscg(L, dist, s, m8)[0]),
+                DV.with_scheme(0, lambda: DV.dpcg(L, dist, s, P.PRECOND_JACOBI)[0]), DV.with_scheme(1, lambda: DV.dmscg(L, dist, s, m3, max_iter=5)[0])]
 
-    def cycle(check):
-        dist = GC.Dist(L, s, ranks, False)
-        try:
-            fs = kinds(dist)
-            first = [f() for f in fs]
-            if check:
-                order = np.random.default_rng(5).permutation(len(fs) * 2) % len(fs)
-                for i in order:
-                    assert M.same_bits(fs[i](), first[i]).all(), f"solve kind {i} changed its bits between other solves"
-        finally:
-            dist.close()
-
-    cycle(True)                                                      # (warm-up: whatever the process keeps for good exists now)
-    torch.cuda.synchronize()
-    free0 = torch.cuda.mem_get_info()[0]
-    cycle(False)
-    torch.cuda.synchronize()
-    free1 = torch.cuda.mem_get_info()[0]
     # one solve's work space, the larger scheme (replicate): per rank the m x_i and the nslots P_i of the m8 ladder, F doubles each
     # rounded up to even, and the per-shift array
     m, nslots = 8, 7
     one_solve = 8 * ranks * ((m + nslots) * (s.ncol + 1) + S.MAX_SHIFTS * S.MS_STRIDE)
-    print(f"free device memory: {free0} bytes before the handle, {free1} after its destroy; allowance {one_solve}")
-    assert free0 - free1 <= one_solve, (free0, free1, one_solve)
+    DV.interleaved_then_memory_back(L, s, ranks, kinds, 5, one_solve)
 
 
 # ---- 10 --------------------------------------------------------------------------------------------------------------------
@@ -526,18 +422,17 @@ def test_pair_handle(L, route, ranks):
     """fs_dist_matrix_pair(A, At): A' in the caller's entry order, cut where the caller cut it (an empty slice in front and a one-row
     slice with the caller's cuts on three ranks, empty slices in the middle on five): both schemes are the models on that A' and those
     bounds"""
-    import test_gpu_dist_pair as GP
     for name in DPair.RECIPES0[1:] + ("binary_F65", "valued", "lambda0_empty_column"):
-        s = GP.SYSTEMS[name]
-        pd = GP.PairDist(L, s, ranks, route)
+        s = DV.PAIR_SYSTEMS[name]
+        pd = DV.PairDist(L, s, ranks, route)
         try:
             bounds = pd.bounds_t()
             t = pd.t_csr()
             for scheme in (0, 1):
-                with options(strict_order=1, dist_cg_scheme=scheme):
+                with G.options(strict_order=1, dist_cg_scheme=scheme):
                     for ladder, cap in (("m3", 0), ("m8", 0), ("m8", 5)):
-                        got = dmscg(L, pd, s, lams_of(s, ladder), cap, hbm=cap == 5, ldx=s.ncol + 3 * scheme)
+                        got = DV.dmscg(L, pd, s, SV.lams_of(s, ladder), cap, hbm=cap == 5, ldx=s.ncol + 3 * scheme)
                         what = f"fs_dist_mscg scheme {scheme} {ladder} cap {cap} on a pair, route {route}, bounds {bounds}, on {name}"
-                        _assert_model(what, got, _model(s, ladder, cap, t, bounds if scheme == 1 else None))
+                        DV.assert_dmscg_model(what, got, DV.dmscg_model(s, ladder, cap, t, bounds if scheme == 1 else None))
         finally:
             pd.close()

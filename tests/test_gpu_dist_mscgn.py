@@ -1,6 +1,6 @@
 """fs_dist_mscgn on virtual ranks of one device (fs_dist_create(n, [0] * n)), against the CPU model (tests/_dist_mscgn_model.py: column
-j is the model of fs_dist_mscg on B[:, j]), against fs_mscgn on one device and against the other sharded solvers, in the idioms of
-test_gpu_dist_mscg.py and test_gpu_dist_pcgn_lambdas.py.  A' of every model is dist.t_csr(): the shards' own rows, downloaded.
+j is the model of fs_dist_mscg on B[:, j]), against fs_mscgn on one device and against the other sharded solvers, on the harness of
+tests/_solvers.py and tests/_dist_solvers.py.  A' of every model is dist.t_csr(): the shards' own rows, downloaded.
 
 1  strict_order, scheme 0, on 1 and 3 ranks, A' built on the host and on the device: the whole model's bits (X, infos, rank 0's
    per-column st[] / ms[]) and those of a single-device fs_mscgn on the same CSRs -- k in (1, 2, 3, 4, 5, 8, 17, 32) (the step kernel
@@ -19,6 +19,7 @@ test_gpu_dist_mscg.py and test_gpu_dist_pcgn_lambdas.py.  A' of every model is d
 8  statuses, with X untouched by every refused call; a product's own error is passed through.
 9  guard zones, interleaved solves on one handle, device memory given back.
 10 a pair handle: both schemes are the models on the caller's A' order and the caller's cuts (DIFFERING_BOUNDS)."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -26,89 +27,33 @@ import pytest
 
 import _cg_model as M
 import _dist_mscgn_model as DN
+import _dist_solvers as DV
+import _gpu as G
 import _lifecycle as LC
 import _mscg_model as S
 import _pcg_model as P
 import _pcgn_model as N
-import test_gpu_cg as GC
-import test_gpu_dist_mscg as GDM
-import test_gpu_dist_pcg as GD
-import test_gpu_dist_pcgn_lambdas as GDL
-import test_gpu_mscg as GM
-import test_gpu_mscgn as GMN
-import test_gpu_pcg as G
-import test_gpu_pcgn as GN
+import _solvers as SV
+from _gpu import FS_ERR_ARG, FS_ERR_NO_TRANSPOSE, FS_ERR_RELEASED, FS_OK, L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-FS_OK, FS_ERR_ARG, FS_ERR_NO_TRANSPOSE, FS_ERR_RELEASED = 0, -2, -4, -5
-RECIPES0 = GDM.RECIPES0
-KS = GD.KS
-LADDERS = GM.LADDERS
 COMBOS = [(ladder, cap) for ladder in ("m1", "m3", "m8", "m16") for cap in (0, 5)]
-lams_of = GM.lams_of
-options = GC.options
-GAP_BITS = LC.PREFILLS["nan"]
 _CACHE = {}
 
 
 def test_the_cases_cover_what_they_should():
-    assert KS == (1, 2, 3, 4, 5, 8, 17, 32) and set(LADDERS) == {"m1", "m3", "m8", "m16"}
-    assert {len(LADDERS[l]) for l in LADDERS} == {1, 3, 8, 16} and LADDERS["m3"].count(min(LADDERS["m3"])) == 2
-    assert tuple(sorted(LADDERS["m8"])) == tuple(sorted(S.LADDER)) and LADDERS["m8"] != tuple(S.LADDER)          # shuffled
-    seen = {c for i in range(len(KS)) for c in _combos(i)}
+    assert DV.KS == (1, 2, 3, 4, 5, 8, 17, 32) and set(SV.LADDERS) == {"m1", "m3", "m8", "m16"}
+    assert {len(SV.LADDERS[l]) for l in SV.LADDERS} == {1, 3, 8, 16} and SV.LADDERS["m3"].count(min(SV.LADDERS["m3"])) == 2
+    assert tuple(sorted(SV.LADDERS["m8"])) == tuple(sorted(S.LADDER)) and SV.LADDERS["m8"] != tuple(S.LADDER)          # shuffled
+    seen = {c for i in range(len(DV.KS)) for c in _combos(i)}
     assert seen == set(COMBOS)                                        # every ladder under both caps, over the ks
-    assert M.RED_THREADS // S.MAX_SHIFTS == 16 and any(k > 16 for k in KS) and 17 in KS     # the step kernel's columns per pass
+    assert M.RED_THREADS // S.MAX_SHIFTS == 16 and any(k > 16 for k in DV.KS) and 17 in DV.KS     # the step kernel's columns per pass
 
 
 def _combos(i):
     """the two (ladder, cap) of the i-th k: over the eight ks every ladder meets both caps"""
     return COMBOS[i % 8], COMBOS[(i + 5) % 8]
-
-
-@pytest.fixture(scope="module")
-def L():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    from libfastsparse_amd import capi
-    lib = capi.lib()
-    lib.fs_debug_last_cg_state.argtypes = [C.c_void_p]
-    lib.fs_debug_last_mscg_state.argtypes = [C.c_void_p, C.c_int]
-    lib.fs_debug_last_pcgn_state.argtypes = [C.c_void_p, C.c_int]
-    lib.fs_debug_last_mscgn_state.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    lib.fs_debug_dist_products.restype = C.c_long
-    lib.fs_debug_dist_products.argtypes = []
-    return lib
-
-
-def dmscgn(L, dist, s, B, lams, max_iter=0, tol=None, hbm=False, ldx=None):
-    """fs_dist_mscgn through capi.dist_mscgn: X (m, F, k), infos[i][j], per column rank 0's (st[] by name, per-shift array by name),
-    and the solve's st[] by fs_pcg's names.  X lies in one buffer of (m - 1) ldx + F k doubles, host memory or HBM; the gaps between
-    the panels must keep their bits"""
-    from libfastsparse_amd import capi
-    m, (F, k) = len(lams), B.shape
-    ne = F * k
-    ldx = ne if ldx is None else ldx
-    n = (m - 1) * ldx + ne
-    if hbm:
-        import torch
-        buf = torch.empty(max(n, 1), dtype=torch.float64, device="cuda")
-        buf.view(torch.int64).fill_(GAP_BITS)
-        X = buf.as_strided((m, F, k), (ldx, k, 1))
-    else:
-        buf = np.full(max(n, 1), GAP_BITS, np.int64).view(np.float64)
-        X = np.lib.stride_tricks.as_strided(buf, (m, F, k), (ldx * 8, k * 8, 8))
-    infos = capi.dist_mscgn(dist.M, X, GD._put(B, hbm), lams, s.tol if tol is None else tol, max_iter)
-    cols = []
-    for j in range(k):
-        st, raw = np.full(M.CG_STATE_DOUBLES, np.nan), np.full(S.MAX_SHIFTS * S.MS_STRIDE, np.nan)
-        assert L.fs_debug_last_mscgn_state(j, st.ctypes.data, raw.ctypes.data, raw.size) == m * S.MS_STRIDE
-        cols.append((S.state_from_device(st), S.shifts_from_device(raw, m)))
-    got = GD._np(buf)
-    gaps = np.concatenate([got[i * ldx + ne:(i + 1) * ldx] for i in range(m - 1)] + [np.zeros(0)])
-    assert (gaps.view(np.int64) == GAP_BITS).all(), "a gap between the panels was written"
-    X = np.stack([got[i * ldx:i * ldx + ne].reshape(F, k) for i in range(m)])
-    return X, infos, cols, P.state_from_device(G._raw_state(L))
 
 
 def _model(s, B, lams, cap, t_csr, bounds=None, tol=None):
@@ -121,7 +66,7 @@ def _assert_model(what, got, model, columns=None):
     assert X.shape == model.X.shape and len(infos) == X.shape[0] and all(len(r) == k for r in infos), what
     for j in (range(k) if columns is None else columns):
         c = model.columns[j]
-        GMN._assert_column(f"{what}, column {j}", X[:, :, j], [row[j] for row in infos], cols[j], c.X, c.infos, c.state, c.shifts)
+        SV.assert_ladder_column(f"{what}, column {j}", X[:, :, j], [row[j] for row in infos], cols[j], c.X, c.infos, c.state, c.shifts)
     if columns is None:
         assert st["iter"] == max(c.state["iter"] for c in model.columns), (what, st)
         assert st["done"] == float(all(c.state["done"] == 1.0 for c in model.columns)), (what, st)
@@ -131,13 +76,9 @@ def _assert_same_solve(what, got, want):
     """two device solves: X, the infos and every column's state and per-shift array, bit for bit (want: dmscgn's or mscgn_run's)"""
     assert M.same_bits(got[0], want[0]).all(), (what, int((~M.same_bits(got[0], want[0])).sum()))
     for j in range(got[0].shape[2]):
-        GM._assert_infos((what, j), [row[j] for row in got[1]], [S.Info(r[j].iterations, r[j].converged, r[j].rnorm, r[j].bnorm) for r in want[1]])
+        SV.assert_infos((what, j), [row[j] for row in got[1]], [S.Info(r[j].iterations, r[j].converged, r[j].rnorm, r[j].bnorm) for r in want[1]])
         bad = M.mismatch(np.zeros(0), np.zeros(0), None, None, got[2][j][0], want[2][j][0]) or S.shifts_mismatch(got[2][j][1], want[2][j][1])
         assert bad is None, (what, j, bad)
-
-
-def _nonzero_columns(B):
-    return [j for j in range(B.shape[1]) if B[:, j].any()]
 
 
 def _kernels(k):
@@ -145,25 +86,25 @@ def _kernels(k):
 
 
 # ---- 1 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("k", DV.KS)
 def test_scheme0_strict_is_fs_mscgn_and_the_model(L, k):
-    s, B = GD._panel(k)
+    s, B = DV.panel(k)
     ne = s.ncol * k
-    single = GD._single_handles(L, s)
+    single = SV.single_handles(L, s)
     n = 0
     for ranks, device_t in ((1, False), (3, True), (3, False)):
-        dist = GC.Dist(L, s, ranks, device_t)
+        dist = DV.Dist(L, s, ranks, device_t)
         try:
-            t_csr = GD._sorted_t(dist, s)
-            for ladder, cap in _combos(KS.index(k)):
-                lams = lams_of(s, ladder)
+            t_csr = DV.sorted_t(dist, s)
+            for ladder, cap in _combos(DV.KS.index(k)):
+                lams = SV.lams_of(s, ladder)
                 model = _model(s, B, lams, cap, t_csr)
                 for kernel in _kernels(k):
                     n += 1
                     hbm, ldx = n % 2 == 1, ne + 3 * (n // 2 % 2)
-                    with options(strict_order=1, pcgn_kernel=kernel, dist_cg_scheme=0):
-                        got = dmscgn(L, dist, s, B, lams, cap, hbm=hbm, ldx=ldx)
-                        one = GMN.mscgn_run(L, single[0], single[1], s, B, lams, cap)
+                    with G.options(strict_order=1, pcgn_kernel=kernel, dist_cg_scheme=0):
+                        got = DV.dmscgn(L, dist, s, B, lams, cap, hbm=hbm, ldx=ldx)
+                        one = SV.mscgn_run(L, single[0], single[1], s, B, lams, cap)
                     what = (f"fs_dist_mscgn scheme 0 k {k} {ladder} cap {cap}, {ranks} ranks, {'device' if device_t else 'host'} A', "
                             f"pcgn_kernel {kernel}, {'HBM' if hbm else 'host'} panels, ldx {ldx}")
                     _assert_model(what, got, model)
@@ -175,29 +116,29 @@ def test_scheme0_strict_is_fs_mscgn_and_the_model(L, k):
 
 
 # ---- 2 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("k", KS)
+@pytest.mark.parametrize("k", DV.KS)
 def test_scheme1_strict_is_the_slice_model(L, k):
-    s, B = GD._panel(k)
+    s, B = DV.panel(k)
     ne = s.ncol * k
     n = 0
     for device_t in (False, True):
-        dist = GC.Dist(L, s, 3, device_t)
+        dist = DV.Dist(L, s, 3, device_t)
         try:
             bounds = dist.bounds_t()
             assert bounds[0] == 0 and bounds[-1] == s.ncol and all(a < b for a, b in zip(bounds, bounds[1:]))
-            t_csr = GD._sorted_t(dist, s)
-            for ladder, cap in _combos(KS.index(k)):
-                lams = lams_of(s, ladder)
+            t_csr = DV.sorted_t(dist, s)
+            for ladder, cap in _combos(DV.KS.index(k)):
+                lams = SV.lams_of(s, ladder)
                 whole, sliced = _model(s, B, lams, cap, t_csr), _model(s, B, lams, cap, t_csr, bounds)
-                nz = _nonzero_columns(B)                             # on the CPU first: the slice tree is told from the whole one
+                nz = SV.nonzero_columns(B)                             # on the CPU first: the slice tree is told from the whole one
                 differ = DN.differing_columns(sliced, whole)
                 print(f"k {k} {ladder} cap {cap} bounds {bounds}: {len(differ)} of {len(nz)} non-zero columns differ between the slice model and the whole model")
                 assert set(differ) <= set(nz) and 2 * len(differ) >= len(nz), (k, ladder, cap, bounds, differ)
                 for kernel in _kernels(k):
                     n += 1
                     hbm, ldx = n % 2 == 0, ne + 3
-                    with options(strict_order=1, pcgn_kernel=kernel, dist_cg_scheme=1):
-                        got = dmscgn(L, dist, s, B, lams, cap, hbm=hbm, ldx=ldx)
+                    with G.options(strict_order=1, pcgn_kernel=kernel, dist_cg_scheme=1):
+                        got = DV.dmscgn(L, dist, s, B, lams, cap, hbm=hbm, ldx=ldx)
                     _assert_model(f"fs_dist_mscgn scheme 1 k {k} {ladder} cap {cap}, bounds {bounds}, pcgn_kernel {kernel}, "
                                   f"{'HBM' if hbm else 'host'} panels, ldx {ldx}", got, sliced)
         finally:
@@ -207,19 +148,19 @@ def test_scheme1_strict_is_the_slice_model(L, k):
 @pytest.mark.parametrize("k", (3, 5, 17))
 def test_scheme1_odd_k_on_slices_of_odd_length(L, k):
     """ne = rows k is odd on a slice: the flat pair kernels take a slice as a panel of fewer rows, 8 bytes at a time"""
-    s = GD.ALL["binary_F65"]
-    B = GN.columns(s, k)
-    dist = GC.Dist(L, s, 3, False)
+    s = DV.ALL["binary_F65"]
+    B = SV.columns(s, k)
+    dist = DV.Dist(L, s, 3, False)
     try:
         bounds = dist.bounds_t()
         rows = [b - a for a, b in zip(bounds, bounds[1:])]
         assert sum(r % 2 for r in rows) >= 1 and all((r * k) % 2 == r % 2 for r in rows), rows
-        t_csr = GD._sorted_t(dist, s)
+        t_csr = DV.sorted_t(dist, s)
         for ladder, cap in (("m3", 0), ("m8", 5)):
-            lams = lams_of(s, ladder)
+            lams = SV.lams_of(s, ladder)
             for kernel in _kernels(k):
-                with options(strict_order=1, pcgn_kernel=kernel, dist_cg_scheme=1):
-                    got = dmscgn(L, dist, s, B, lams, cap, hbm=cap == 5, ldx=s.ncol * k + 3)
+                with G.options(strict_order=1, pcgn_kernel=kernel, dist_cg_scheme=1):
+                    got = DV.dmscgn(L, dist, s, B, lams, cap, hbm=cap == 5, ldx=s.ncol * k + 3)
                 _assert_model(f"fs_dist_mscgn scheme 1 k {k} {ladder} cap {cap}, slices of {rows} rows", got, _model(s, B, lams, cap, t_csr, bounds))
     finally:
         dist.close()
@@ -227,19 +168,19 @@ def test_scheme1_odd_k_on_slices_of_odd_length(L, k):
 
 def test_scheme1_with_empty_slices(L):
     """five ranks on the three rows of A': some slices are empty and contribute +0.0"""
-    s = GD.ALL["three_eigenvalues"]
-    dist = GC.Dist(L, s, 5, False)
+    s = DV.ALL["three_eigenvalues"]
+    dist = DV.Dist(L, s, 5, False)
     try:
         bounds = dist.bounds_t()
         assert len(bounds) == 6 and any(a == b for a, b in zip(bounds, bounds[1:])), bounds
-        t_csr = GD._sorted_t(dist, s)
+        t_csr = DV.sorted_t(dist, s)
         for k in (1, 3, 8):
-            B = GN.columns(s, k)
+            B = SV.columns(s, k)
             for ladder, cap in (("m3", 0), ("m8", 2)):
-                lams = lams_of(s, ladder)
+                lams = SV.lams_of(s, ladder)
                 for kernel in _kernels(k):
-                    with options(strict_order=1, pcgn_kernel=kernel, dist_cg_scheme=1):
-                        got = dmscgn(L, dist, s, B, lams, cap, hbm=cap == 2, ldx=s.ncol * k + 3)
+                    with G.options(strict_order=1, pcgn_kernel=kernel, dist_cg_scheme=1):
+                        got = DV.dmscgn(L, dist, s, B, lams, cap, hbm=cap == 2, ldx=s.ncol * k + 3)
                     _assert_model(f"fs_dist_mscgn scheme 1 k {k} {ladder} cap {cap}, bounds {bounds}", got, _model(s, B, lams, cap, t_csr, bounds))
     finally:
         dist.close()
@@ -247,22 +188,22 @@ def test_scheme1_with_empty_slices(L):
 
 # ---- 3 ---------------------------------------------------------------------------------------------------------------------
 def test_large_panels_capped(L):
-    s = GD.ALL["binary_F262145"]
+    s = DV.ALL["binary_F262145"]
     F, k = s.ncol, 2
     i = np.arange(F, dtype=np.float64)
     B = np.ascontiguousarray(np.stack([s.b, s.b * 1.125 + np.cos(i * 0.015)], 1))
-    lams = lams_of(s, "m3")
+    lams = SV.lams_of(s, "m3")
     # (a workgroup owns 256 rows, 2 elements per thread in the flat kernels: the whole panel of scheme 0 runs into a second grid
     #  stride of the kernels that take sums and of the flat ones, a slice of a third of it stays within one)
     assert F > M.RED_BLOCKS * M.RED_THREADS
-    dist = GC.Dist(L, s, 3, False)
+    dist = DV.Dist(L, s, 3, False)
     try:
         bounds = dist.bounds_t()
         assert [b - a for a, b in zip(bounds, bounds[1:])] == [87381, 87382, 87382] or min(b - a for a, b in zip(bounds, bounds[1:])) > 65536, bounds
-        t_csr = GD._sorted_t(dist, s)
+        t_csr = DV.sorted_t(dist, s)
         for scheme in (0, 1):
-            with options(strict_order=1, dist_cg_scheme=scheme):
-                got = dmscgn(L, dist, s, B, lams, 3, hbm=scheme == 1, ldx=F * k + 3 * scheme)
+            with G.options(strict_order=1, dist_cg_scheme=scheme):
+                got = DV.dmscgn(L, dist, s, B, lams, 3, hbm=scheme == 1, ldx=F * k + 3 * scheme)
             assert np.isfinite(got[0]).all(), scheme
             _assert_model(f"fs_dist_mscgn scheme {scheme} k 2 m3 cap 3 on binary_F262145, bounds {bounds}", got,
                           _model(s, B, lams, 3, t_csr, bounds if scheme == 1 else None))
@@ -276,22 +217,22 @@ def _repeats(a, b):
     return bool(M.same_bits(a[0], b[0]).all()) and [i.iterations for i in a[1]] == [i.iterations for i in b[1]]
 
 
-@pytest.mark.parametrize("mode", GC.MODES)
+@pytest.mark.parametrize("mode", G.SOLVER_MODES)
 def test_one_lambda_is_fs_dist_pcgn_lambdas_and_fs_dist_pcgn(L, mode):
     for name in ("valued", "binary_F65", "control_seed0"):
-        s = GD.ALL[name]
-        dist = GC.Dist(L, s, 3, False)
+        s = DV.ALL[name]
+        dist = DV.Dist(L, s, 3, False)
         try:
             for k in (1, 3, 8):
-                B = GN.columns(s, k)
+                B = SV.columns(s, k)
                 for cap in (0, 5):
                     for scheme in (1, 0):
-                        with GC._mode(mode), options(dist_cg_scheme=scheme):
+                        with G.mode_options(mode), G.options(dist_cg_scheme=scheme):
                             if scheme == 1:
-                                want, again = [GDL.dnl(L, dist, s, B, [s.lam] * k, P.PRECOND_NONE, max_iter=cap) for _ in range(2)]
+                                want, again = [DV.dnl(L, dist, s, B, [s.lam] * k, P.PRECOND_NONE, max_iter=cap) for _ in range(2)]
                             else:
-                                want, again = [GD.dpcgn(L, dist, s, B, P.PRECOND_NONE, max_iter=cap) for _ in range(2)]
-                            X, infos, cols, _ = dmscgn(L, dist, s, B, [s.lam], cap)
+                                want, again = [DV.dpcgn(L, dist, s, B, P.PRECOND_NONE, max_iter=cap) for _ in range(2)]
+                            X, infos, cols, _ = DV.dmscgn(L, dist, s, B, [s.lam], cap)
                         what = (name, mode, scheme, k, cap)
                         repeats = _repeats(want, again)
                         assert repeats or (mode == "cg_fixed_order=0" and k > 1), (what, "the right-hand solver does not repeat its bits")
@@ -307,42 +248,42 @@ def test_one_lambda_is_fs_dist_pcgn_lambdas_and_fs_dist_pcgn(L, mode):
             dist.close()
 
 
-@pytest.mark.parametrize("mode", GC.MODES)
+@pytest.mark.parametrize("mode", G.SOLVER_MODES)
 def test_one_column_is_fs_dist_mscg(L, mode):
     for name, ladder, cap in (("fixture_100x50", "m8", 0), ("binary_F65", "m3", 5), ("valued", "m8", 0), ("zero_rhs", "m3", 0),
                               ("control_seed0", "m8", 0), ("powerlaw_seed0", "m3", 0), ("lambda0_empty_column", "m8", 5)):
-        s = GDM.ALL[name]
-        lams = lams_of(s, ladder)
-        dist = GC.Dist(L, s, 3, False)
+        s = DV.MSCG_ALL[name]
+        lams = SV.lams_of(s, ladder)
+        dist = DV.Dist(L, s, 3, False)
         try:
             for scheme in (0, 1):
-                with GC._mode(mode), options(dist_cg_scheme=scheme):
-                    x, info, st, shifts = GDM.dmscg(L, dist, s, lams, cap)
-                    X, infos, cols, _ = dmscgn(L, dist, s, s.b.reshape(-1, 1), lams, cap, hbm=scheme == 1)
-                GMN._assert_column(f"fs_dist_mscgn with k = 1 vs fs_dist_mscg [{mode}] scheme {scheme} {ladder} cap {cap} on {name}", X[:, :, 0],
-                                   [row[0] for row in infos], cols[0], x, info, GMN._written(st), shifts)
+                with G.mode_options(mode), G.options(dist_cg_scheme=scheme):
+                    x, info, st, shifts = DV.dmscg(L, dist, s, lams, cap)
+                    X, infos, cols, _ = DV.dmscgn(L, dist, s, s.b.reshape(-1, 1), lams, cap, hbm=scheme == 1)
+                SV.assert_ladder_column(f"fs_dist_mscgn with k = 1 vs fs_dist_mscg [{mode}] scheme {scheme} {ladder} cap {cap} on {name}", X[:, :, 0],
+                                   [row[0] for row in infos], cols[0], x, info, SV.written(st), shifts)
         finally:
             dist.close()
 
 
-@pytest.mark.parametrize("mode", GC.MODES)
+@pytest.mark.parametrize("mode", G.SOLVER_MODES)
 def test_pairs_of_the_smallest_lambda_are_fs_dist_cg(L, mode):
     """k = 1 in every mode (the products are the single-vector ones); k = 4 where the k-column product has the single-vector product's
     bits: strict_order"""
     for name in ("fixture_100x50", "valued", "control_seed0"):
-        s = GD.ALL[name]
-        dist = GC.Dist(L, s, 3, False)
+        s = DV.ALL[name]
+        dist = DV.Dist(L, s, 3, False)
         try:
             for k in ((1, 4) if mode == "strict_order" else (1,)):
-                B = GN.columns(s, k)
+                B = SV.columns(s, k)
                 for scheme in (0, 1):
                     for ladder in ("m3", "m8"):
-                        lams = lams_of(s, ladder)
+                        lams = SV.lams_of(s, ladder)
                         base = [i for i, lam in enumerate(lams) if lam == min(lams)]
                         assert min(lams) == s.lam and len(base) == {"m3": 2, "m8": 1}[ladder]
-                        with GC._mode(mode), options(dist_cg_scheme=scheme):
-                            X, infos, cols, _ = dmscgn(L, dist, s, B, lams)
-                            for j in _nonzero_columns(B):
+                        with G.mode_options(mode), G.options(dist_cg_scheme=scheme):
+                            X, infos, cols, _ = DV.dmscgn(L, dist, s, B, lams)
+                            for j in SV.nonzero_columns(B):
                                 xc, itc, stc = dist.cg(False, b=B[:, j])
                                 for i in base:
                                     what = (name, mode, scheme, k, ladder, i, j)
@@ -353,17 +294,17 @@ def test_pairs_of_the_smallest_lambda_are_fs_dist_cg(L, mode):
 
 
 # ---- 5 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(RECIPES0))
+@pytest.mark.parametrize("name", list(DV.MSCG_RECIPES0))
 def test_large_shifts_freeze_on_slices(L, name):
-    s = RECIPES0[name]
+    s = DV.MSCG_RECIPES0[name]
     lams = [s.lam, s.lam + 1e6, s.lam + 1e9]
-    B = GN.columns(s, 4)
-    dist = GC.Dist(L, s, 3, False)
+    B = SV.columns(s, 4)
+    dist = DV.Dist(L, s, 3, False)
     try:
         bounds = dist.bounds_t()
-        t_csr = GD._sorted_t(dist, s)
-        with options(strict_order=1, dist_cg_scheme=1):
-            got = dmscgn(L, dist, s, B, lams, tol=1e-14, hbm=True)
+        t_csr = DV.sorted_t(dist, s)
+        with G.options(strict_order=1, dist_cg_scheme=1):
+            got = DV.dmscgn(L, dist, s, B, lams, tol=1e-14, hbm=True)
             X, infos, cols, _ = got
             counts = [[i.iterations for i in row] for row in infos]
             print(f"{name}: counts {counts}")
@@ -372,7 +313,7 @@ def test_large_shifts_freeze_on_slices(L, name):
             _assert_model(f"fs_dist_mscgn scheme 1 large shifts on {name}", got, _model(s, B, lams, 0, t_csr, bounds, tol=1e-14))
             assert max(counts[2]) + 2 < max(counts[0]) and max(counts[1]) + 2 < max(counts[0]), counts
             for i in (2, 1):                                         # the solve capped where shift i lost its last pair: its panel is final there
-                capped = dmscgn(L, dist, s, B, lams, max(counts[i]) + 1, tol=1e-14)
+                capped = DV.dmscgn(L, dist, s, B, lams, max(counts[i]) + 1, tol=1e-14)
                 assert [c.iterations for c in capped[1][i]] == counts[i] and all(c.converged == 1 for c in capped[1][i]), (i, counts[i])
                 assert M.same_bits(capped[0][i], X[i]).all(), (name, i, "a shift without a live pair was written again")
     finally:
@@ -380,20 +321,20 @@ def test_large_shifts_freeze_on_slices(L, name):
 
 
 def test_a_nan_column_stays_in_its_column(L):
-    s = GD.ALL["binary_F65"]
-    lams = lams_of(s, "m3")
-    B = GN.columns(s, 5)
+    s = DV.ALL["binary_F65"]
+    lams = SV.lams_of(s, "m3")
+    B = SV.columns(s, 5)
     clean = B.copy()
     B[7, 3] = np.nan
-    dist = GC.Dist(L, s, 3, False)
+    dist = DV.Dist(L, s, 3, False)
     try:
         bounds = dist.bounds_t()
-        t_csr = GD._sorted_t(dist, s)
+        t_csr = DV.sorted_t(dist, s)
         for scheme in (0, 1):
-            with options(strict_order=1, dist_cg_scheme=scheme):
-                want = dmscgn(L, dist, s, clean, lams, 5)
-                got = dmscgn(L, dist, s, B, lams, 5, hbm=scheme == 1)            # FS_OK: the ranks agree about the NaN column too
-                alone = GDM.dmscg(L, dist, s, lams, 5, b=B[:, 3])
+            with G.options(strict_order=1, dist_cg_scheme=scheme):
+                want = DV.dmscgn(L, dist, s, clean, lams, 5)
+                got = DV.dmscgn(L, dist, s, B, lams, 5, hbm=scheme == 1)            # FS_OK: the ranks agree about the NaN column too
+                alone = DV.dmscg(L, dist, s, lams, 5, b=B[:, 3])
             X, infos, cols, st = got
             for j in (0, 1, 2, 4):
                 what = (scheme, j)
@@ -410,17 +351,17 @@ def test_a_nan_column_stays_in_its_column(L):
 
 
 # ---- 6 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(RECIPES0))
+@pytest.mark.parametrize("name", list(DV.MSCG_RECIPES0))
 def test_default_mode_ladder_within_the_bars(L, name):
-    s = RECIPES0[name]
-    lams = lams_of(s, "m8")
-    B = GN.columns(s, 4)
+    s = DV.MSCG_RECIPES0[name]
+    lams = SV.lams_of(s, "m8")
+    B = SV.columns(s, 4)
     am, atm, _, _ = M.csr_products(s.nrow, s.ncol, s.a_csr(), s.t_csr_coo())
-    dist = GC.Dist(L, s, 3, False)
+    dist = DV.Dist(L, s, 3, False)
     try:
         for scheme in (0, 1):
-            with options(dist_cg_scheme=scheme):
-                runs = [dmscgn(L, dist, s, B, lams, hbm=bool(run)) for run in range(2)]
+            with G.options(dist_cg_scheme=scheme):
+                runs = [DV.dmscgn(L, dist, s, B, lams, hbm=bool(run)) for run in range(2)]
             X, infos, _, _ = runs[0]
             for i, lam in enumerate(lams):
                 for j in range(4):
@@ -442,29 +383,23 @@ def test_default_mode_ladder_within_the_bars(L, name):
 # ---- 7 ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ("three_eigenvalues", "fixture_100x50", "control_seed0"))
 def test_sharded_products_per_solve(L, name):
-    s = GDM.ALL[name]
+    s = DV.MSCG_ALL[name]
     F = s.ncol
-    dist = GC.Dist(L, s, 3, False)
-
-    def counted(f):
-        before = L.fs_debug_dist_products()
-        out = f()
-        return L.fs_debug_dist_products() - before, out
-
+    dist = DV.Dist(L, s, 3, False)
     try:
         for scheme, per_iter in ((0, 2), (1, 1)):
-            with options(strict_order=1, dist_cg_scheme=scheme):
+            with G.options(strict_order=1, dist_cg_scheme=scheme):
                 for k in (1, 3):
-                    B = GN.columns(s, k)
+                    B = SV.columns(s, k)
                     for ladder, max_iter in (("m1", 0), ("m8", 0), ("m3", 2)):
-                        n, (X, infos, _, st) = counted(lambda: dmscgn(L, dist, s, B, lams_of(s, ladder), max_iter))
+                        n, (X, infos, _, st) = DV.counted(L, lambda: DV.dmscgn(L, dist, s, B, SV.lams_of(s, ladder), max_iter))
                         at_start = st["done"] == 1.0 and st["iter"] == 0.0 and bool(M.same_bits(X, np.zeros(X.shape)).all())
                         what = (name, scheme, k, ladder, max_iter, n, st["iter"], st["done"], at_start)
                         print(*what)
                         assert st["iter"] == max(i.iterations for row in infos for i in row), what
-                        assert n == per_iter * GD._loops(max_iter or F, int(st["iter"]), at_start), what
+                        assert n == per_iter * DV.loops(max_iter or F, int(st["iter"]), at_start), what
                     for tol, Bz in ((s.tol, np.zeros_like(B)), (1.0, B), (2.5, B)):          # done at the start: B = 0, tol >= 1
-                        n, (X, infos, _, st) = counted(lambda: dmscgn(L, dist, s, Bz, lams_of(s, "m3"), tol=tol, hbm=tol == 1.0))
+                        n, (X, infos, _, st) = DV.counted(L, lambda: DV.dmscgn(L, dist, s, Bz, SV.lams_of(s, "m3"), tol=tol, hbm=tol == 1.0))
                         assert n == 0, (name, scheme, k, tol, n)
                         assert all(i.converged == 1 and i.iterations == 0 for row in infos for i in row), (name, scheme, k, tol)
                         assert M.same_bits(X, np.zeros(X.shape)).all() and not np.signbit(X).any() and st["iter"] == 0.0, (name, scheme, k, tol)
@@ -475,15 +410,11 @@ def test_sharded_products_per_solve(L, name):
 # ---- 8 ---------------------------------------------------------------------------------------------------------------------
 def test_statuses(L):
     from libfastsparse_amd import capi
-    s = RECIPES0["control_seed0"]
-    dist = GC.Dist(L, s, 3, False)
-    rp, cc, vv = s.a_csr()
-    M_not = L.fs_dist_csr_create(dist.D, s.nrow, s.ncol, len(cc), rp.ctypes.data, cc.ctypes.data, vv.ctypes.data)   # no transposed side
-    assert M_not
-    try:
+    s = DV.MSCG_RECIPES0["control_seed0"]
+    with contextlib.closing(DV.Dist(L, s, 3, False)) as dist, DV.handle_without_transpose(L, dist, s) as M_not:
         F, k, m = s.ncol, 3, 3
-        B = GN.columns(s, k)
-        X = (GAP_BITS + np.arange(16 * (F * k + 3), dtype=np.int64)).view(np.float64)      # quiet NaNs, each tagged with its place
+        B = SV.columns(s, k)
+        X = (SV.GAP_BITS + np.arange(16 * (F * k + 3), dtype=np.int64)).view(np.float64)      # quiet NaNs, each tagged with its place
         bits = X.view(np.int64).copy()
         lams = [s.lam * 3, s.lam, s.lam * 10]
 
@@ -494,7 +425,7 @@ def test_statuses(L):
             return L.fs_dist_mscgn(M_, X_, ldx, b_, k_, m_, arr, tol, max_iter, info)
 
         for scheme in (0, 1):
-            with options(dist_cg_scheme=scheme):
+            with G.options(dist_cg_scheme=scheme):
                 bad = {"NULL M": call(M_=None), "NULL X": call(X_=None), "NULL B": call(b_=None), "NULL lambda": call(lam=None),
                        "k 0": call(k_=0), "k -1": call(k_=-1), "k 33": call(k_=N.MAX_RHS + 1, ldx=F * 33), "m 0": call(m_=0), "m -1": call(m_=-1),
                        "m 17": call(m_=17), "ldx < F k": call(ldx=F * k - 1), "ldx F": call(ldx=F), "ldx 0": call(ldx=0),
@@ -506,7 +437,7 @@ def test_statuses(L):
                 assert all(rc == FS_ERR_ARG for rc in bad.values()), (scheme, bad)
                 assert L.fs_last_error()
                 assert call(M_=M_not) == FS_ERR_NO_TRANSPOSE
-                assert np.array_equal(X.view(np.int64), bits), "a refused call wrote to X"
+                SV.refused_call_leaves(X, bits)
                 assert call(tol=0.0, max_iter=2) == FS_OK            # tol = 0 is legal: the cap ends it (info NULL is legal too)
                 assert call(m_=16, ldx=F * k + 3) == FS_OK
                 infos = (capi.PcgInfo * (m * k))()
@@ -514,38 +445,35 @@ def test_statuses(L):
                 assert [i.iterations for i in infos] == [2, 2, 0] * 3 and [i.converged for i in infos] == [0, 0, 1] * 3
                 assert call(lam=[-0.25, s.lam, 0.0], max_iter=3) == FS_OK   # a negative lambda is the caller's business
                 X.view(np.int64)[:] = bits
-    finally:
-        L.fs_dist_matrix_destroy(M_not)
-        dist.close()
 
 
 def test_a_product_error_is_passed_through(L):
     """fs_matrix_release_csr on ONE rank's shard of A': under strict_order a product reads the plain CSR, so the solve ends with
     FS_ERR_RELEASED and the product's message, X untouched; outside strict_order the kept copy serves and the solve is the one from
     before the release"""
-    s = G.RECIPES["scaled_seed0"]                                    # (plain CG does not converge on it: the solves run under a cap)
-    lams = lams_of(s, "m3")
+    s = SV.RECIPES["scaled_seed0"]                                    # (plain CG does not converge on it: the solves run under a cap)
+    lams = SV.lams_of(s, "m3")
     arr = (C.c_double * len(lams))(*lams)
     k = 2
-    B = GN.columns(s, k)
-    with options(binning=2, bin_flags=64):                           # kept two-pass copies: there is something to release for
-        dist = GC.Dist(L, s, 3, False)
+    B = SV.columns(s, k)
+    with G.options(binning=2, bin_flags=64):                           # kept two-pass copies: there is something to release for
+        dist = DV.Dist(L, s, 3, False)
     try:
         before = {}
         for scheme in (0, 1):
-            with options(dist_cg_scheme=scheme):
-                before[scheme] = dmscgn(L, dist, s, B, lams, 20)
+            with G.options(dist_cg_scheme=scheme):
+                before[scheme] = DV.dmscgn(L, dist, s, B, lams, 20)
                 assert np.isfinite(before[scheme][0]).all()
         assert L.fs_matrix_release_csr(L.fs_dist_matrix_shard(dist.M, 1, 1)) == 1
         for scheme in (0, 1):
             X = np.full(len(lams) * s.ncol * k, np.nan)
             bits = X.view(np.int64).copy()
-            with options(strict_order=1, dist_cg_scheme=scheme):
+            with G.options(strict_order=1, dist_cg_scheme=scheme):
                 assert L.fs_dist_mscgn(dist.M, X.ctypes.data, s.ncol * k, B.ctypes.data, k, len(lams), arr, s.tol, 20, None) == FS_ERR_RELEASED, scheme
                 assert b"fs_matrix_release_csr" in L.fs_last_error()
-            assert np.array_equal(X.view(np.int64), bits), (scheme, "a refused solve wrote to X")
-            with options(dist_cg_scheme=scheme):
-                after = dmscgn(L, dist, s, B, lams, 20)              # the kept copy needs no plain array
+            SV.refused_call_leaves(X, bits, (scheme, "a refused solve wrote to X"))
+            with G.options(dist_cg_scheme=scheme):
+                after = DV.dmscgn(L, dist, s, B, lams, 20)              # the kept copy needs no plain array
             _assert_same_solve(("after the release", scheme), after, before[scheme])
     finally:
         dist.close()
@@ -559,25 +487,25 @@ def test_guard_zones(L, k):
     import torch
     from libfastsparse_amd import capi
     mem = LC.TorchMem()
-    s = RECIPES0["powerlaw_seed0"]
+    s = DV.MSCG_RECIPES0["powerlaw_seed0"]
     F = s.ncol
     ne = F * k
-    B = GN.columns(s, k)
-    dist = GC.Dist(L, s, 3, False)
+    B = SV.columns(s, k)
+    dist = DV.Dist(L, s, 3, False)
     try:
         gx, gb = LC.Guarded(mem, "X of fs_dist_mscgn", 8 * (ne + 3)), LC.Guarded(mem, "B of fs_dist_mscgn", ne)
         for scheme in (0, 1):
             for ladder, cap in (("m1", 0), ("m3", 5), ("m8", 0)):
-                lams = lams_of(s, ladder)
+                lams = SV.lams_of(s, ladder)
                 m = len(lams)
                 ref = None
                 for ldx in (ne, ne + 3):
                     for off in (0, 1):
                         mem.put(gb.place(ne, off ^ (ldx & 1)), B.reshape(-1))
                         n = (m - 1) * ldx + ne
-                        mem.fill_bits(gx.place(n, off), GAP_BITS)
+                        mem.fill_bits(gx.place(n, off), SV.GAP_BITS)
                         infos = (capi.PcgInfo * (m * k))()
-                        with options(dist_cg_scheme=scheme):
+                        with G.options(dist_cg_scheme=scheme):
                             capi.check(L.fs_dist_mscgn(dist.M, gx.view.data_ptr(), ldx, gb.view.data_ptr(), k, m, (C.c_double * m)(*lams), s.tol, cap,
                                                        infos), "fs_dist_mscgn")
                         torch.cuda.synchronize()
@@ -585,10 +513,8 @@ def test_guard_zones(L, k):
                         bad = mem.first_bad_guard([gx, gb])
                         assert bad is None, (what, bad.first_broken())
                         assert mem.eq(gb.view, mem.const(B.reshape(-1))), (what, "B changed")
-                        got = mem.get(gx.view)
-                        X = np.stack([got[i * ldx:i * ldx + ne] for i in range(m)])
-                        gaps = np.concatenate([got[i * ldx + ne:(i + 1) * ldx] for i in range(m - 1)] + [np.zeros(0)])
-                        assert (gaps.view(np.int64) == GAP_BITS).all(), (what, "a gap between the panels was written")
+                        X, gaps = SV.split_rows_and_gaps(mem.get(gx.view), m, ne, ldx)
+                        assert (gaps.view(np.int64) == SV.GAP_BITS).all(), (what, "a gap between the panels was written")
                         assert np.isfinite(X).all(), what
                         if not cap:
                             assert all(i.converged == 1 for i in infos), (what, [i.iterations for i in infos])
@@ -604,19 +530,20 @@ def test_interleaved_solves_share_the_work_space_and_give_it_back(L):
     re-made, not overrun), both schemes, interleaved on one handle under strict_order: each has its own model's bits, first and again
     between the others; after fs_dist_matrix_destroy free device memory is back where it was before the handle existed, within one
     solve's work space"""
-    import torch
     import _dist_pcgn_lambdas_model as DNL
     import _pcgn_lambdas_model as NL
-    s = RECIPES0["control_seed0"]
-    B3, B5, B8 = GN.columns(s, 3), GN.columns(s, 5), GN.columns(s, 8)
-    m3, m8, l5 = lams_of(s, "m3"), lams_of(s, "m8"), NL.rungs(s, 5)
+    s = DV.MSCG_RECIPES0["control_seed0"]
+    B3, B5, B8 = SV.columns(s, 3), SV.columns(s, 5), SV.columns(s, 8)
+    m3, m8, l5 = SV.lams_of(s, "m3"), SV.lams_of(s, "m8"), NL.rungs(s, 5)
     ranks = 3
 
-    def kinds(dist, t_csr, bounds):
+    def kinds(dist):
+        t_csr, bounds = DV.sorted_t(dist, s), dist.bounds_t()
+
         def mn(scheme, B, lams, cap, **kw):
             def run():
-                with options(strict_order=1, dist_cg_scheme=scheme):
-                    got = dmscgn(L, dist, s, B, lams, cap, **kw)
+                with G.options(strict_order=1, dist_cg_scheme=scheme):
+                    got = DV.dmscgn(L, dist, s, B, lams, cap, **kw)
                 _assert_model(("interleaved fs_dist_mscgn", scheme, B.shape[1], len(lams), cap), got,
                               _model(s, B, lams, cap, t_csr, bounds if scheme == 1 else None))
                 return got[0]
@@ -624,61 +551,42 @@ def test_interleaved_solves_share_the_work_space_and_give_it_back(L):
 
         def ms(scheme, lams):
             def run():
-                with options(strict_order=1, dist_cg_scheme=scheme):
-                    got = GDM.dmscg(L, dist, s, lams)
-                GDM._assert_model(("interleaved fs_dist_mscg", scheme), got, GDM._model(s, "m3", 0, t_csr, bounds if scheme == 1 else None, lams=lams))
+                with G.options(strict_order=1, dist_cg_scheme=scheme):
+                    got = DV.dmscg(L, dist, s, lams)
+                DV.assert_dmscg_model(("interleaved fs_dist_mscg", scheme), got, DV.dmscg_model(s, "m3", 0, t_csr, bounds if scheme == 1 else None, lams=lams))
                 return got[0]
             return run
 
         def nl(scheme):
             def run():
-                with options(strict_order=1, dist_cg_scheme=scheme):
-                    got = GDL.dnl(L, dist, s, B5, l5, P.PRECOND_JACOBI)
-                GDL._assert_model(("interleaved fs_dist_pcgn_lambdas", scheme), got,
-                                  DNL.run(s, B5, l5, P.PRECOND_JACOBI, t_csr=t_csr, bounds=bounds if scheme == 1 else None, cache=GDL._CACHE))
+                with G.options(strict_order=1, dist_cg_scheme=scheme):
+                    got = DV.dnl(L, dist, s, B5, l5, P.PRECOND_JACOBI)
+                DV.assert_dnl_model(("interleaved fs_dist_pcgn_lambdas", scheme), got,
+                                  DNL.run(s, B5, l5, P.PRECOND_JACOBI, t_csr=t_csr, bounds=bounds if scheme == 1 else None, cache=DV.DNL_CACHE))
                 return got[0]
             return run
 
         return [mn(1, B3, m3, 0), ms(1, m3), nl(1), mn(1, B8, m8, 0, hbm=True), mn(0, B3, m3, 5, ldx=s.ncol * 3 + 3), ms(0, m3), nl(0),
                 mn(0, B8, m8, 0), mn(1, B3, m8, 5)]
 
-    def cycle(check):
-        dist = GC.Dist(L, s, ranks, False)
-        try:
-            fs = kinds(dist, GD._sorted_t(dist, s), dist.bounds_t()) if check else None
-            if check:
-                first = [f() for f in fs]
-                order = np.random.default_rng(7).permutation(len(fs) * 2) % len(fs)
-                for i in order:
-                    assert M.same_bits(fs[i](), first[i]).all(), f"solve kind {i} changed its bits between other solves"
-            else:
-                for scheme in (1, 0):
-                    with options(dist_cg_scheme=scheme):
-                        dmscgn(L, dist, s, B3, m3)
-                        dmscgn(L, dist, s, B8, m8)
-        finally:
-            dist.close()
+    def unchecked(dist):
+        for scheme in (1, 0):
+            with G.options(dist_cg_scheme=scheme):
+                DV.dmscgn(L, dist, s, B3, m3)
+                DV.dmscgn(L, dist, s, B8, m8)
 
-    cycle(True)                                                      # (warm-up: whatever the process keeps for good exists now)
-    torch.cuda.synchronize()
-    free0 = torch.cuda.mem_get_info()[0]
-    cycle(False)
-    torch.cuda.synchronize()
-    free1 = torch.cuda.mem_get_info()[0]
     # one solve's work space, the larger scheme (replicate), k = 8, the m8 ladder: per rank the m X_i and the nslots P_i of F k doubles,
     # R, B, X of fs_dist_pcgn's, the partials and the scalars
     k, m, nslots = 8, 8, 7
     one_solve = 8 * ranks * ((m + nslots + 3) * k * s.ncol + 2048 * k + 9344)
-    print(f"free device memory: {free0} bytes before the handle, {free1} after its destroy; allowance {one_solve}")
-    assert free0 - free1 <= one_solve, (free0, free1, one_solve)
+    DV.interleaved_then_memory_back(L, s, ranks, kinds, 7, one_solve, unchecked=unchecked)
 
 
 # ---- 10 --------------------------------------------------------------------------------------------------------------------
-class _CutPair(GC.Dist):
+class _CutPair(DV.Dist):
     """fs_dist_matrix_pair(A, At): A from s.a_csr(), At from s.t_csr_coo() -- the caller's entry order -- cut at the caller's `bounds`"""
 
     def __init__(self, L, s, bounds):
-        import test_gpu_dist_pair as GP
         from libfastsparse_amd import capi
         ranks = len(bounds) - 1
         self.L, self.s, self.ranks = L, s, ranks
@@ -690,7 +598,7 @@ class _CutPair(GC.Dist):
             rp, cc, vv = self.csr
             self.A = L.fs_dist_csr_create(self.D, s.nrow, s.ncol, len(cc), rp.ctypes.data, cc.ctypes.data, None if vv is None else vv.ctypes.data)
             assert self.A, L.fs_last_error()
-            self.At = GP.from_shards(L, self.D, s.ncol, s.nrow, s.t_csr_coo(), [b - a for a, b in zip(bounds, bounds[1:])], capi.FS_HOST)
+            self.At = DV.from_shards(L, self.D, s.ncol, s.nrow, s.t_csr_coo(), [b - a for a, b in zip(bounds, bounds[1:])], capi.FS_HOST)
             self.M = capi.dist_matrix_pair(self.A, self.At)
         except BaseException:
             self.close()
@@ -720,15 +628,15 @@ def test_pair_handle(L, name):
         assert DPair.same_arrays(t, s.t_csr_coo()), (name, "the shards of A' are not the caller's arrays")
         for k, ladder, cap in ((8, "m3", 0), (3, "m8", 5)):
             B = np.ascontiguousarray(B8[:, :k])
-            lams = lams_of(s, ladder)
+            lams = SV.lams_of(s, ladder)
             whole, sliced = _model(s, B, lams, cap, t), _model(s, B, lams, cap, t, bounds)
-            nz = _nonzero_columns(B)
+            nz = SV.nonzero_columns(B)
             differ = DN.differing_columns(sliced, whole)
             print(f"{name} k {k} {ladder} cap {cap}: columns whose bits differ between the schemes' models {differ} of the non-zero {nz}")
             assert 2 * len(differ) >= len(nz), (name, k, ladder, cap, differ)
             for scheme in (0, 1):
-                with options(strict_order=1, dist_cg_scheme=scheme):
-                    got = dmscgn(L, pd, s, B, lams, cap, hbm=scheme == 1, ldx=s.ncol * k + 3 * scheme)
+                with G.options(strict_order=1, dist_cg_scheme=scheme):
+                    got = DV.dmscgn(L, pd, s, B, lams, cap, hbm=scheme == 1, ldx=s.ncol * k + 3 * scheme)
                 _assert_model(f"fs_dist_mscgn scheme {scheme} k {k} {ladder} cap {cap} on a pair, bounds {bounds}, on {name}", got,
                               sliced if scheme == 1 else whole)
     finally:

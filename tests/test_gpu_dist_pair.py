@@ -1,11 +1,11 @@
 """fs_dist_matrix_pair(A, At): a third sharded handle on the shards of two others -- direct side A's, transposed side the caller's own
-At -- on every sharded path, on virtual ranks of one device (fs_dist_create(n, [0] * n)), in the idioms of test_gpu_cg.py and
-test_gpu_dist_pcg.py.  What a pair has that a built transpose has not: rows of A' in the CALLER's entry order (System.t_csr_coo();
+At -- on every sharded path, on virtual ranks of one device (fs_dist_create(n, [0] * n)), on the harness of tests/_solvers.py and
+tests/_dist_solvers.py.  What a pair has that a built transpose has not: rows of A' in the CALLER's entry order (System.t_csr_coo();
 a built transpose sorts them), the caller's cuts of A' (empty shards in the middle, one-row shards), sides shared by two handles
 each, and a life of its own.  tests/test_dist_pair_model.py shows on the CPU that the models used here tell the two transposes and
 the two kinds of cuts apart.
 
-0  PairDist: test_gpu_cg.Dist's surface on a pair, three routes to A and At; the shards of A' are the caller's arrays, array for array.
+0  PairDist (tests/_dist_solvers.py): Dist's surface on a pair, three routes to A and At; the shards of A' are the caller's arrays, array for array.
 1  (on the CPU: tests/test_dist_pair_model.py)
 2  products: strict_order bit for bit against the oracle on the caller's A'; the exact sets in the other three modes; arbitrary
    data within 1e-12 row-scaled; the direct side through the pair is the direct side through A.
@@ -24,22 +24,18 @@ import pytest
 
 import _cg_model as M
 import _dist_pair as DPair
+import _dist_solvers as DV
 import _exact as E
+import _gpu as G
 import _lifecycle as LC
 import _pcg_model as P
 import _pcgn_model as N
-import test_gpu_cg as GC
-import test_gpu_dist_pcg as GD
-import test_gpu_pcg as G
-import test_gpu_pcgn as GN
-from test_gpu_dist_pcg import CASES, _case_args, _model, _np, _put, dpcg, dpcgn
+import _solvers as SV
+from _gpu import FS_ERR_RELEASED, FS_OK, L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-FS_OK, FS_ERR_RELEASED = GD.FS_OK, GD.FS_ERR_RELEASED
 TOL = 1e-12                                              # the project's bar for a product in the default mode, row-scaled
-options = GC.options
-SYSTEMS = {n: GD.ALL[n] for n in DPair.NAMED + DPair.RECIPES0}
 # fs_dist_pcg runs on the recipes and on the named systems whose model is quick
 PCG_SET = DPair.RECIPES0 + ("binary_F65", "cap_tol0", "lambda0_empty_column", "valued", "zero_rhs", "three_eigenvalues")
 EXACT_SETS = ("wide_range", "subnormal", "subnormal_pattern", "zeros")
@@ -47,113 +43,7 @@ KS = (2, 4, 5)
 _SINGLE = {}
 
 
-@pytest.fixture(scope="module")
-def L():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    from libfastsparse_amd import capi
-    lib = capi.lib()
-    lib.fs_debug_last_cg_state.argtypes = [C.c_void_p]
-    lib.fs_debug_last_pcgn_state.argtypes = [C.c_void_p, C.c_int]
-    lib.fs_debug_dist_parts.argtypes = [C.c_void_p, C.c_int]
-    return lib
-
-
 # ---- 0 ---------------------------------------------------------------------------------------------------------------------
-def dev_rows(nrow, ranks):
-    """route `dev`: the rows of A per rank, an empty shard in the middle"""
-    return [nrow] if ranks == 1 else [nrow // 2, 0, nrow - nrow // 2] + [0] * (ranks - 3)
-
-
-def from_shards(L, D, nrow, ncol, csr, rows, space):
-    """fs_dist_csr_create_from_shards on the CSR cut into `rows` rows per rank: local row_ptr from 0, global column ids; the arrays
-    in host memory, or (FS_DEVICE) uploaded with torch"""
-    import torch
-    from libfastsparse_amd import capi
-    rp, cc, vv = csr
-    n = len(rows)
-    cut = [0] + [int(v) for v in np.cumsum(rows)]
-    assert cut[-1] == nrow
-    keep, ptrs, nnzs = [], ([], [], []), []
-    for r in range(n):
-        lo, hi = int(rp[cut[r]]), int(rp[cut[r + 1]])
-        nnzs.append(hi - lo)
-        arrays = (np.ascontiguousarray(rp[cut[r]:cut[r + 1] + 1] - lo, np.int32), np.ascontiguousarray(cc[lo:hi], np.int32),
-                  None if vv is None else np.ascontiguousarray(vv[lo:hi], np.float64))
-        for a, out in zip(arrays, ptrs):
-            if a is not None and space == capi.FS_DEVICE:
-                a = torch.from_numpy(a).cuda()
-            keep.append(a)
-            out.append(capi._ptr(a))
-    if space == capi.FS_DEVICE:
-        torch.cuda.synchronize()
-    vp = C.c_void_p * n
-    h = L.fs_dist_csr_create_from_shards(D, nrow, ncol, (C.c_int * n)(*rows), (C.c_int64 * n)(*nnzs), vp(*ptrs[0]), vp(*ptrs[1]),
-                                         None if vv is None else vp(*ptrs[2]), space)
-    assert h, L.fs_last_error()
-    return h
-
-
-class PairDist(GC.Dist):
-    """test_gpu_cg.Dist on a pair: .M = fs_dist_matrix_pair(.A, .At) on fs_dist_create(ranks).  Routes:
-      coo   A fs_dist_csr_create from s.a_csr(); At fs_dist_coo_create(D, ncol, nrow, nnz, s.cols, s.rows, s.vals): the rows of A' in
-            the caller's entry order, s.t_csr_coo(), cut by non-zeros
-      cuts  the same A; At fs_dist_csr_create_from_shards (host arrays) from s.t_csr_coo() with the caller's cuts, _dist_pair.cut_rows
-      dev   A fs_dist_csr_create_from_shards from arrays uploaded with torch, an empty shard in the middle; At as in `coo`
-    s: a _cg_model.System, or anything with its nrow, ncol, rows, cols, vals, a_csr() and t_csr_coo()"""
-
-    def __init__(self, L, s, ranks, route):
-        from libfastsparse_amd import capi
-        assert route in DPair.ROUTES, route
-        self.L, self.s, self.ranks, self.route = L, s, ranks, route
-        self.csr, self.t_want = s.a_csr(), s.t_csr_coo()
-        self.A = self.At = self.M = None
-        self.D = L.fs_dist_create(ranks, (C.c_int * ranks)(*([0] * ranks)))
-        assert self.D, L.fs_last_error()
-        try:
-            rp, cc, vv = self.csr
-            vals = None if s.vals is None else s.vals.ctypes.data
-            if route == "dev":
-                self.A = from_shards(L, self.D, s.nrow, s.ncol, self.csr, dev_rows(s.nrow, ranks), capi.FS_DEVICE)
-            else:
-                self.A = L.fs_dist_csr_create(self.D, s.nrow, s.ncol, len(cc), rp.ctypes.data, cc.ctypes.data, None if vv is None else vv.ctypes.data)
-            assert self.A, L.fs_last_error()
-            if route == "cuts":
-                self.At = from_shards(L, self.D, s.ncol, s.nrow, self.t_want, DPair.cut_rows(s.ncol, ranks), capi.FS_HOST)
-            else:
-                self.At = L.fs_dist_coo_create(self.D, s.ncol, s.nrow, s.rows.size, s.cols.ctypes.data, s.rows.ctypes.data, vals)
-            assert self.At, L.fs_last_error()
-            self.M = capi.dist_matrix_pair(self.A, self.At)
-        except BaseException:
-            self.close()
-            raise
-
-    def bounds_of(self, h):
-        b = (C.c_int * (self.ranks + 1))()
-        assert self.L.fs_dist_matrix_bounds(h, b) == 0
-        return list(b)
-
-    def bounds_t(self):
-        """the pair's cuts of A' are At's own cuts of its rows: the caller's, or (fs_dist_coo_create) the cut by non-zeros"""
-        b = super().bounds_t()
-        want = DPair.cut_bounds(self.s.ncol, self.ranks) if self.route == "cuts" else DPair.nnz_bounds(self.t_want[0], self.ranks)
-        assert b == self.bounds_of(self.At) == want, (self.route, b, self.bounds_of(self.At), want)
-        return b
-
-    def t_csr(self):
-        """the pair's transposed shards, downloaded: the caller's A' array for array -- the caller's order, not a sorted one"""
-        t = super().t_csr()
-        assert DPair.same_arrays(t, self.t_want), (getattr(self.s, "name", "?"), self.route, self.ranks, "the shards of A' are not the caller's arrays")
-        return t
-
-    def close(self):
-        for h in (self.M, self.A, self.At):
-            if h:
-                self.L.fs_dist_matrix_destroy(h)
-        self.M = self.A = self.At = None
-        self.L.fs_dist_destroy(self.D)
-
-
 def _fits(s, route, ranks):
     """(three unknowns have no room for five ranks' cuts [2, 0, F - 5, 0, 3])"""
     return not (route == "cuts" and ranks == 5 and s.ncol < 5)
@@ -182,10 +72,10 @@ def _exact(name):
 @pytest.mark.parametrize("ranks", [1, 3, 5])
 @pytest.mark.parametrize("route", DPair.ROUTES)
 def test_the_shards_are_the_callers_arrays(L, route, ranks):
-    for name, s in SYSTEMS.items():
+    for name, s in DV.PAIR_SYSTEMS.items():
         if not _fits(s, route, ranks):
             continue
-        pd = PairDist(L, s, ranks, route)
+        pd = DV.PairDist(L, s, ranks, route)
         try:
             bounds = pd.bounds_t()
             assert bounds[0] == 0 and bounds[-1] == s.ncol
@@ -199,7 +89,7 @@ def test_the_shards_are_the_callers_arrays(L, route, ranks):
 
 # ---- 2 ---------------------------------------------------------------------------------------------------------------------
 def _nan(shape, hbm):
-    return _put(np.full(shape, np.nan), hbm)
+    return G.put(np.full(shape, np.nan), hbm)
 
 
 def _call(L, f, *a):
@@ -214,30 +104,30 @@ def _products(L, h, csr, t_csr, nrow, ncol, x, u, X, U, lam, hbm, same):
     from oracle import pyoracle as O
     (arp, acc, avv), (trp, tcc, tvv) = csr, t_csr
     out = {}
-    xi, ui = _put(x, hbm), _put(u, hbm)
+    xi, ui = G.put(x, hbm), G.put(u, hbm)
     z = _nan(ncol, hbm)
     _call(L, L.fs_dist_spmv_t, h, z, ui)
-    out["spmv_t"] = (_np(z), O.csr_mul(ncol, trp, tcc, tvv, u))
+    out["spmv_t"] = (G.to_numpy(z), O.csr_mul(ncol, trp, tcc, tvv, u))
     y = _nan(nrow, hbm)
     _call(L, L.fs_dist_spmv, h, y, xi)
     yw = O.csr_mul(nrow, arp, acc, avv, x)
-    out["spmv"] = (_np(y), yw)
+    out["spmv"] = (G.to_numpy(y), yw)
     for l in (0.0, lam):
         z = _nan(ncol, hbm)
         _call(L, L.fs_dist_ata, h, z, xi, C.c_double(l))
         w = O.csr_mul(ncol, trp, tcc, tvv, yw)
-        out[f"ata lambda {l}"] = (_np(z), w + np.float64(l) * x if l != 0.0 else w)        # (fs_axpy: z += lambda x, two roundings)
+        out[f"ata lambda {l}"] = (G.to_numpy(z), w + np.float64(l) * x if l != 0.0 else w)        # (fs_axpy: z += lambda x, two roundings)
     for k, Xk in X.items():
         Uk = U[k]
-        Xi, Ui = _put(Xk, hbm), _put(Uk, hbm)
+        Xi, Ui = G.put(Xk, hbm), G.put(Uk, hbm)
         Z = _nan((ncol, k), hbm)
         _call(L, L.fs_dist_spmm_t, h, Z, Ui, k)
-        out[f"spmm_t k {k}"] = (_np(Z), O.csr_mul_n(ncol, trp, tcc, tvv, Uk, k))
+        out[f"spmm_t k {k}"] = (G.to_numpy(Z), O.csr_mul_n(ncol, trp, tcc, tvv, Uk, k))
         Y = _nan((nrow, k), hbm)
         _call(L, L.fs_dist_spmm, h, Y, Xi, k)
-        out[f"spmm k {k}"] = (_np(Y), O.csr_mul_n(nrow, arp, acc, avv, Xk, k))
-        assert same(_np(Xi), Xk) and same(_np(Ui), Uk), (k, "an input changed")
-    assert same(_np(xi), x) and same(_np(ui), u), "an input changed"
+        out[f"spmm k {k}"] = (G.to_numpy(Y), O.csr_mul_n(nrow, arp, acc, avv, Xk, k))
+        assert same(G.to_numpy(Xi), Xk) and same(G.to_numpy(Ui), Uk), (k, "an input changed")
+    assert same(G.to_numpy(xi), x) and same(G.to_numpy(ui), u), "an input changed"
     assert all(g.shape == w.shape for g, w in out.values())
     return out
 
@@ -278,16 +168,16 @@ def _direct_is_As(L, pd, x, X):
 def test_products_strict_add_in_the_callers_order(L, route, ranks):
     from oracle import pyoracle as O
     for name in DPair.NAMED:
-        s = SYSTEMS[name]
+        s = DV.PAIR_SYSTEMS[name]
         if not _fits(s, route, ranks):
             continue
         rng = np.random.default_rng([2, ranks, s.ncol])
         x, u = rng.standard_normal(s.ncol), rng.standard_normal(s.nrow)
         X, U = {k: rng.standard_normal((s.ncol, k)) for k in KS}, {k: rng.standard_normal((s.nrow, k)) for k in KS}
-        pd = PairDist(L, s, ranks, route)
+        pd = DV.PairDist(L, s, ranks, route)
         try:
             t = pd.t_csr()
-            with options(strict_order=1):
+            with G.options(strict_order=1):
                 for hbm in (False, True):
                     for what, (got, want) in _products(L, pd.M, pd.csr, t, s.nrow, s.ncol, x, u, X, U, 0.75, hbm, E.bits_equal).items():
                         assert E.bits_equal(got, want), (name, route, ranks, hbm, what, E.first_mismatch(got, want))
@@ -301,7 +191,7 @@ def test_products_strict_add_in_the_callers_order(L, route, ranks):
 
 
 @pytest.mark.parametrize("name", EXACT_SETS)
-@pytest.mark.parametrize("mode", [m for m in GC.MODES if m != "strict_order"])
+@pytest.mark.parametrize("mode", [m for m in G.SOLVER_MODES if m != "strict_order"])
 def test_products_are_exact_on_the_exact_sets(L, mode, name):
     s = _exact(name)
     d, r = s.d, s.r
@@ -311,29 +201,29 @@ def test_products_are_exact_on_the_exact_sets(L, mode, name):
     except AssertionError:                                   # (A'A x + lam x is exact only on some sets: exact_sum says on which)
         ata_lam = []
     for route, ranks in itertools.product(DPair.ROUTES, (3, 5)):
-        pd = PairDist(L, s, ranks, route)
+        pd = DV.PairDist(L, s, ranks, route)
         try:
             pd.bounds_t()
             pd.t_csr()
-            with GC._mode(mode):
+            with G.mode_options(mode):
                 for hbm in (False, True):
                     j = 1 + int(hbm) + ranks
                     calls = [(L.fs_dist_spmv_t, 1, 1), (L.fs_dist_spmv, 0, 1)] + [(f, side, k) for k in KS for f, side in
                                                                               ((L.fs_dist_spmm_t, 1), (L.fs_dist_spmm, 0))]
                     for f, side, k in calls:
                         xin, want = r.run("in", side, j, k), r.run("out", side, j, k)
-                        vi, vo = _put(xin, hbm), _nan(want.size, hbm)
+                        vi, vo = G.put(xin, hbm), _nan(want.size, hbm)
                         _call(L, f, pd.M, vo, vi, *([k] if k > 1 else []))
                         what = (name, mode, route, ranks, hbm, f.__name__, k)
-                        assert E.bits_equal(_np(vo), want), (what, E.first_mismatch(_np(vo), want))
-                        assert E.bits_equal(_np(vi), xin), (what, "the input changed")
+                        assert E.bits_equal(G.to_numpy(vo), want), (what, E.first_mismatch(G.to_numpy(vo), want))
+                        assert E.bits_equal(G.to_numpy(vi), xin), (what, "the input changed")
                     for jj, want in enumerate(r.ata):
                         for l, w in [(0.0, want)] + ([(lam, ata_lam[jj])] if ata_lam else []):
                             xin = r.run("in", 0, jj, 1)
-                            vi, vo = _put(xin, hbm), _nan(w.size, hbm)
+                            vi, vo = G.put(xin, hbm), _nan(w.size, hbm)
                             _call(L, L.fs_dist_ata, pd.M, vo, vi, C.c_double(l))
-                            assert E.bits_equal(_np(vo), w), (name, mode, route, ranks, hbm, "ata", l, E.first_mismatch(_np(vo), w))
-                            assert E.bits_equal(_np(vi), xin)
+                            assert E.bits_equal(G.to_numpy(vo), w), (name, mode, route, ranks, hbm, "ata", l, E.first_mismatch(G.to_numpy(vo), w))
+                            assert E.bits_equal(G.to_numpy(vi), xin)
                 if r.ata:
                     x = r.run("in", 0, 0, 1)
                     for rank, (y, z) in enumerate(_resident(L, pd, d.nrow, d.ncol, x)):
@@ -350,11 +240,11 @@ def test_products_on_arbitrary_data_default_mode(L, route, ranks):
     |A'| |e| of A' y: both are at most 1e-12 |A'| (|A| |x|) up to second order, so the bar is twice that, plus one rounding of
     z + lambda x"""
     from oracle import pyoracle as O
-    s = SYSTEMS["valued"]
+    s = DV.PAIR_SYSTEMS["valued"]
     rng = np.random.default_rng([3, ranks])
     x, u = rng.standard_normal(s.ncol), rng.standard_normal(s.nrow)
     X, U = {k: rng.standard_normal((s.ncol, k)) for k in KS}, {k: rng.standard_normal((s.nrow, k)) for k in KS}
-    pd = PairDist(L, s, ranks, route)
+    pd = DV.PairDist(L, s, ranks, route)
     try:
         t = pd.t_csr()
         (arp, acc, avv), (trp, tcc, tvv) = pd.csr, t
@@ -383,8 +273,8 @@ def _single_handles(L, s):
     from libfastsparse_amd import capi
     if s.name not in _SINGLE:
         (arp, acc, avv), (trp, tcc, tvv) = s.a_csr(), s.t_csr_coo()
-        A = capi.Matrix.from_csr(s.nrow, s.ncol, G._d(arp), G._d(acc), None if avv is None else G._d(avv))
-        At = capi.Matrix.from_csr(s.ncol, s.nrow, G._d(trp), G._d(tcc), None if tvv is None else G._d(tvv))
+        A = capi.Matrix.from_csr(s.nrow, s.ncol, G.to_device(arp), G.to_device(acc), None if avv is None else G.to_device(avv))
+        At = capi.Matrix.from_csr(s.ncol, s.nrow, G.to_device(trp), G.to_device(tcc), None if tvv is None else G.to_device(tvv))
         _SINGLE[s.name] = (A, At)
     return _SINGLE[s.name]
 
@@ -396,28 +286,28 @@ def _model_bounds(pd):
 
 def _fs_cg2_on(L, A, At, s):
     from libfastsparse_amd import capi
-    x, it = G._nan(2 * s.ncol), C.c_int(-1)
-    capi.check(L.fs_cg2(A.h, At.h, x.data_ptr(), G._d(s.B.reshape(-1)).data_ptr(), s.lam, s.tol, C.byref(it), capi.current_stream()), "fs_cg2")
-    return x.cpu().numpy().reshape(-1, 2), it.value, GC._state(L, True)
+    x, it = G.nan_vector(2 * s.ncol), C.c_int(-1)
+    capi.check(L.fs_cg2(A.h, At.h, x.data_ptr(), G.to_device(s.B.reshape(-1)).data_ptr(), s.lam, s.tol, C.byref(it), capi.current_stream()), "fs_cg2")
+    return x.cpu().numpy().reshape(-1, 2), it.value, SV.cg_state(L, True)
 
 
 @pytest.mark.parametrize("route,ranks", [("coo", 3), ("cuts", 3), ("dev", 3), ("cuts", 5), ("coo", 1)])
 def test_cg_scheme0_strict_is_the_model_and_fs_cg(L, route, ranks):
     for name in DPair.NAMED:
-        s = SYSTEMS[name]
+        s = DV.PAIR_SYSTEMS[name]
         if not _fits(s, route, ranks):
             continue
-        pd = PairDist(L, s, ranks, route)
+        pd = DV.PairDist(L, s, ranks, route)
         try:
             pd.t_csr()
-            with options(strict_order=1, dist_cg_scheme=0):
+            with G.options(strict_order=1, dist_cg_scheme=0):
                 for two in ((False, True) if s.two else (False,)):
                     x, it, st = pd.cg(two)
                     entry = f"fs_dist_cg{'2' if two else ''} scheme 0 on a pair, route {route}, {ranks} ranks"
-                    GC._assert_model(entry, s, two, x, it, st, GC._model(s, two, "coo"))
+                    SV.assert_cg_model(entry, s, two, x, it, st, SV.cg_model(s, two, "coo"))
                     if route == "coo" and ranks == 3:
                         A, At = _single_handles(L, s)
-                        xs, its, sts = _fs_cg2_on(L, A, At, s) if two else G.fs_cg_on(L, A, At, s)
+                        xs, its, sts = _fs_cg2_on(L, A, At, s) if two else SV.fs_cg_on(L, A, At, s)
                         bad = M.mismatch(x, xs, it, its, st, sts)
                         assert bad is None, f"{entry} vs fs_cg{'2' if two else ''} on {name}: {bad}"
         finally:
@@ -429,16 +319,16 @@ def test_cg_scheme1_strict_slices_by_the_pairs_cuts(L, route, ranks):
     """the slice model on pair.bounds_t(): with the caller's cuts an empty slice in front and a one-row slice (three ranks), empty
     slices in the middle (five)"""
     for name in DPair.NAMED:
-        s = SYSTEMS[name]
+        s = DV.PAIR_SYSTEMS[name]
         if not _fits(s, route, ranks):
             continue
-        pd = PairDist(L, s, ranks, route)
+        pd = DV.PairDist(L, s, ranks, route)
         try:
             bounds = _model_bounds(pd)
             pd.t_csr()
-            with options(strict_order=1, dist_cg_scheme=1):
+            with G.options(strict_order=1, dist_cg_scheme=1):
                 x, it, st = pd.cg(False)
-            GC._assert_model(f"fs_dist_cg scheme 1 on a pair, route {route}, bounds {bounds}", s, False, x, it, st, GC._model(s, False, "coo", bounds))
+            SV.assert_cg_model(f"fs_dist_cg scheme 1 on a pair, route {route}, bounds {bounds}", s, False, x, it, st, SV.cg_model(s, False, "coo", bounds))
         finally:
             pd.close()
 
@@ -447,7 +337,7 @@ def _single_gram_diag(L, s, lam):
     from libfastsparse_amd import capi
     key = ("gram", s.name, lam)
     if key not in _SINGLE:
-        one = G._nan(s.ncol)
+        one = G.nan_vector(s.ncol)
         capi.gram_diag(_single_handles(L, s)[1], lam, one, capi.current_stream())
         _SINGLE[key] = one.cpu().numpy()
     return _SINGLE[key]
@@ -457,10 +347,10 @@ def _single_gram_diag(L, s, lam):
 @pytest.mark.parametrize("route", DPair.ROUTES)
 def test_gram_diag_is_fs_gram_diag_on_the_callers_at(L, route, ranks):
     from libfastsparse_amd import capi
-    for name, s in SYSTEMS.items():
+    for name, s in DV.PAIR_SYSTEMS.items():
         if not _fits(s, route, ranks):
             continue
-        pd = PairDist(L, s, ranks, route)
+        pd = DV.PairDist(L, s, ranks, route)
         try:
             t = pd.t_csr()
             for lam in (s.lam, 0.0, 0.75):
@@ -469,36 +359,36 @@ def test_gram_diag_is_fs_gram_diag_on_the_callers_at(L, route, ranks):
                 for hbm in (False, True):
                     d = _nan(s.ncol, hbm)
                     capi.dist_gram_diag(pd.M, lam, d)
-                    ok = M.same_bits(_np(d), want)
+                    ok = M.same_bits(G.to_numpy(d), want)
                     assert ok.all(), (name, route, ranks, lam, hbm, int((~ok).sum()), int(np.flatnonzero(~ok)[0]))
                 if lam == 0.0 and name == "lambda0_empty_column":
-                    assert np.diff(t[0])[5] == 0 and _np(d)[5] == 0.0 and not np.signbit(_np(d)[5])
+                    assert np.diff(t[0])[5] == 0 and G.to_numpy(d)[5] == 0.0 and not np.signbit(G.to_numpy(d)[5])
         finally:
             pd.close()
 
 
 @pytest.mark.parametrize("name", PCG_SET)
 def test_pcg_scheme0_strict_is_fs_pcg_on_the_callers_at(L, name):
-    s = SYSTEMS[name]
+    s = DV.PAIR_SYSTEMS[name]
     for route, ranks in (("coo", 3), ("cuts", 5), ("dev", 3), ("cuts", 1)):
         if not _fits(s, route, ranks):
             continue
-        pd = PairDist(L, s, ranks, route)
+        pd = DV.PairDist(L, s, ranks, route)
         try:
             t = pd.t_csr()
-            with options(strict_order=1, dist_cg_scheme=0):
-                for case in range(len(CASES)):
-                    what, precond, x0, max_iter, diag = _case_args(s, case, t)
+            with G.options(strict_order=1, dist_cg_scheme=0):
+                for case in range(len(SV.CASES)):
+                    what, precond, x0, max_iter, diag = DV.case_args(s, case, t)
                     hbm = (case + ranks) % 2 == 1
-                    x, info, st = dpcg(L, pd, s, precond, x0, max_iter, diag, hbm=hbm)
-                    model = _model(s, case, t)
+                    x, info, st = DV.dpcg(L, pd, s, precond, x0, max_iter, diag, hbm=hbm)
+                    model = DV.dpcg_model(s, case, t)
                     entry = f"fs_dist_pcg scheme 0 on a pair, {what}, route {route}, {ranks} ranks, {'HBM' if hbm else 'host'} vectors"
                     bad = M.mismatch(x, model.x, info.iterations, model.iterations, st, model.state)
                     assert bad is None, f"{entry} on {name}: {bad}"
-                    G._assert_info((name, entry), info, model)
+                    SV.assert_info((name, entry), info, model)
                     if route == "coo":
                         A, At = _single_handles(L, s)
-                        xs, infos, _ = G.pcg_run(L, A, At, s, precond, x0, max_iter, diag)
+                        xs, infos, _ = SV.pcg_run(L, A, At, s, precond, x0, max_iter, diag)
                         assert M.same_bits(x, xs).all() and (info.iterations, info.converged) == (infos.iterations, infos.converged), entry
                         assert M.same_bits(info.rnorm, infos.rnorm)[0] and M.same_bits(info.bnorm, infos.bnorm)[0], entry
         finally:
@@ -506,58 +396,58 @@ def test_pcg_scheme0_strict_is_fs_pcg_on_the_callers_at(L, name):
 
 
 @pytest.mark.parametrize("name,route,ranks", [(n, ro, ra) for n in PCG_SET for ro, ra in (("coo", 3), ("cuts", 3), ("cuts", 5))
-                                              if _fits(SYSTEMS[n], ro, ra)])
+                                              if _fits(DV.PAIR_SYSTEMS[n], ro, ra)])
 def test_pcg_scheme1_strict_slices_by_the_pairs_cuts(L, name, route, ranks):
-    s = SYSTEMS[name]
-    pd = PairDist(L, s, ranks, route)
+    s = DV.PAIR_SYSTEMS[name]
+    pd = DV.PairDist(L, s, ranks, route)
     try:
         bounds = _model_bounds(pd)
         t = pd.t_csr()
-        with options(strict_order=1, dist_cg_scheme=1):
-            for case in range(len(CASES)):
-                what, precond, x0, max_iter, diag = _case_args(s, case, t)
+        with G.options(strict_order=1, dist_cg_scheme=1):
+            for case in range(len(SV.CASES)):
+                what, precond, x0, max_iter, diag = DV.case_args(s, case, t)
                 hbm = case % 2 == 1
-                x, info, st = dpcg(L, pd, s, precond, x0, max_iter, diag, hbm=hbm)
-                model = _model(s, case, t, bounds)
+                x, info, st = DV.dpcg(L, pd, s, precond, x0, max_iter, diag, hbm=hbm)
+                model = DV.dpcg_model(s, case, t, bounds)
                 bad = M.mismatch(x, model.x, info.iterations, model.iterations, st, model.state)
                 assert bad is None, f"fs_dist_pcg scheme 1 on a pair, {what}, route {route}, bounds {bounds}, on {name}: {bad}"
-                G._assert_info((name, what, bounds), info, model)
+                SV.assert_info((name, what, bounds), info, model)
     finally:
         pd.close()
 
 
-@pytest.mark.parametrize("k", GD.KS)
+@pytest.mark.parametrize("k", DV.KS)
 def test_pcgn_columns_are_fs_pcgn_and_the_model(L, k):
-    s, B = GD._panel(k)
-    case = k % len(CASES)
+    s, B = DV.panel(k)
+    case = k % len(SV.CASES)
     single = _single_handles(L, s)
     for route, ranks in (("coo", 3), ("cuts", 5)):
-        pd = PairDist(L, s, ranks, route)
+        pd = DV.PairDist(L, s, ranks, route)
         try:
             t = pd.t_csr()
-            what, precond, x0, max_iter, diag = _case_args(s, case, t)
-            X0 = GN.x0_columns(s, B) if x0 is not None else None
+            what, precond, x0, max_iter, diag = DV.case_args(s, case, t)
+            X0 = SV.x0_columns(s, B) if x0 is not None else None
             key = ("pcgn on the caller's A'", k, case)
             if key not in _SINGLE:
                 am, atm, _, _ = M.csr_products(s.nrow, s.ncol, s.a_csr(), t)
                 dinv = None if precond == P.PRECOND_NONE else P.dinv_of(P.gram_diag(t, s.lam) if precond == P.PRECOND_JACOBI else diag)
                 _SINGLE[key] = N.pcgn(s.ncol, am, atm, B, s.lam, s.tol, max_iter, dinv, X0)
             model = _SINGLE[key]
-            with options(strict_order=1):
-                X, infos, st, cs = dpcgn(L, pd, s, B, precond, X0, max_iter, diag, hbm=ranks == 3)
-                Xs, infos_s, _, cs_s = GN.pcgn_run(L, single[0], single[1], s, B, precond, X0, max_iter, diag)
-                with options(dist_cg_scheme=1):                  # replicated whatever the scheme says
-                    X1, infos1, _, _ = dpcgn(L, pd, s, B, precond, X0, max_iter, diag)
+            with G.options(strict_order=1):
+                X, infos, st, cs = DV.dpcgn(L, pd, s, B, precond, X0, max_iter, diag, hbm=ranks == 3)
+                Xs, infos_s, _, cs_s = SV.pcgn_run(L, single[0], single[1], s, B, precond, X0, max_iter, diag)
+                with G.options(dist_cg_scheme=1):                  # replicated whatever the scheme says
+                    X1, infos1, _, _ = DV.dpcgn(L, pd, s, B, precond, X0, max_iter, diag)
                 if k == 1:                                       # one column is fs_dist_pcg
-                    with options(dist_cg_scheme=0):
-                        x, info, _ = dpcg(L, pd, s, precond, None if X0 is None else X0[:, 0], max_iter, diag, b=B[:, 0])
+                    with G.options(dist_cg_scheme=0):
+                        x, info, _ = DV.dpcg(L, pd, s, precond, None if X0 is None else X0[:, 0], max_iter, diag, b=B[:, 0])
                     assert M.same_bits(X[:, 0], x).all() and (infos[0].iterations, infos[0].converged) == (info.iterations, info.converged)
                     assert M.same_bits(infos[0].rnorm, info.rnorm)[0] and M.same_bits(infos[0].bnorm, info.bnorm)[0]
             assert len(infos) == k
             assert M.same_bits(X1, X).all() and [i.iterations for i in infos1] == [i.iterations for i in infos], (k, route)
             for j in range(k):
-                GN._assert_column((k, route, ranks, what, j, "model"), X[:, j], infos[j], cs[j], model.X[:, j], model.infos[j], model.columns[j].state)
-                GN._assert_column((k, route, ranks, what, j, "fs_pcgn"), X[:, j], infos[j], cs[j], Xs[:, j], N.Info(infos_s[j].iterations,
+                SV.assert_column((k, route, ranks, what, j, "model"), X[:, j], infos[j], cs[j], model.X[:, j], model.infos[j], model.columns[j].state)
+                SV.assert_column((k, route, ranks, what, j, "fs_pcgn"), X[:, j], infos[j], cs[j], Xs[:, j], N.Info(infos_s[j].iterations,
                                   infos_s[j].converged, infos_s[j].rnorm, infos_s[j].bnorm))
                 assert all(M.same_bits(cs[j][f], cs_s[j][f])[0] for f in N.PN), (k, route, j, cs[j], cs_s[j])
             assert st["iter"] == max(i.iterations for i in infos), (k, route, st)
@@ -567,20 +457,20 @@ def test_pcgn_columns_are_fs_pcgn_and_the_model(L, k):
 
 @pytest.mark.parametrize("route", ["coo", "cuts"])
 def test_default_mode_within_the_bars_of_built_transposes(L, route):
-    """Jacobi and no preconditioner on the column-scaled recipe, both schemes: test_gpu_dist_pcg.py's bars, by its own function.  A
+    """Jacobi and no preconditioner on the column-scaled recipe, both schemes: test_gpu_dist_pcg.py's bars, by the function they share.  A
     caller's diagonal that is Jacobi's own d gives Jacobi's bits (the bar of test_released_shard_of_the_transpose there)"""
     from libfastsparse_amd import capi
-    s = SYSTEMS["scaled_seed0"]
-    pd = PairDist(L, s, 3, route)
+    s = DV.PAIR_SYSTEMS["scaled_seed0"]
+    pd = DV.PairDist(L, s, 3, route)
     try:
         pd.t_csr()
-        GD.assert_default_mode_bars(L, pd, s)
+        DV.assert_default_mode_bars(L, pd, s)
         kept = np.full(s.ncol, np.nan)
         capi.dist_gram_diag(pd.M, s.lam, kept)
         for scheme in (0, 1):
-            with options(dist_cg_scheme=scheme):
-                xj, ij, _ = dpcg(L, pd, s, P.PRECOND_JACOBI)
-                xd, idg, _ = dpcg(L, pd, s, P.PRECOND_DIAG, diag=kept)
+            with G.options(dist_cg_scheme=scheme):
+                xj, ij, _ = DV.dpcg(L, pd, s, P.PRECOND_JACOBI)
+                xd, idg, _ = DV.dpcg(L, pd, s, P.PRECOND_DIAG, diag=kept)
             assert idg.converged == 1 and idg.iterations == ij.iterations and M.same_bits(xd, xj).all(), (route, scheme)
     finally:
         pd.close()
@@ -588,9 +478,9 @@ def test_default_mode_within_the_bars_of_built_transposes(L, route):
 
 # ---- 4 ---------------------------------------------------------------------------------------------------------------------
 def test_what_the_handle_reports(L):
-    s = SYSTEMS["binary_F65"]
+    s = DV.PAIR_SYSTEMS["binary_F65"]
     for route in DPair.ROUTES:
-        pd = PairDist(L, s, 3, route)
+        pd = DV.PairDist(L, s, 3, route)
         try:
             assert L.fs_dist_matrix_has_transpose(pd.M) == 1 and L.fs_dist_matrix_has_transpose(pd.A) == 0
             assert L.fs_dist_matrix_nnz(pd.M) == L.fs_dist_matrix_nnz(pd.A) == s.rows.size
@@ -616,8 +506,8 @@ def test_what_the_handle_reports(L):
 
 def test_refusals_leak_nothing(L):
     import torch
-    s = SYSTEMS["binary_F65"]
-    pd, other = PairDist(L, s, 3, "coo"), PairDist(L, s, 3, "coo")
+    s = DV.PAIR_SYSTEMS["binary_F65"]
+    pd, other = DV.PairDist(L, s, 3, "coo"), DV.PairDist(L, s, 3, "coo")
     try:
         ok = L.fs_dist_matrix_pair(pd.A, pd.At)              # (warm-up: whatever the process keeps for good exists now)
         assert ok
@@ -644,23 +534,23 @@ def test_released_shard_of_the_transpose_reached_through_at(L):
     """fs_matrix_release_csr on ONE rank's shard of the shared side, through At: the pair's Jacobi is refused before anything is
     written; a diagonal kept from before still solves, with the same bits"""
     from libfastsparse_amd import capi
-    s = SYSTEMS["scaled_seed0"]
-    with options(binning=2, bin_flags=64):                           # kept two-pass copies: there is something to release for
-        pd = PairDist(L, s, 3, "coo")
+    s = DV.PAIR_SYSTEMS["scaled_seed0"]
+    with G.options(binning=2, bin_flags=64):                           # kept two-pass copies: there is something to release for
+        pd = DV.PairDist(L, s, 3, "coo")
     try:
         kept = np.full(s.ncol, np.nan)
         capi.dist_gram_diag(pd.M, s.lam, kept)
-        B = GN.columns(s, 2)
+        B = SV.columns(s, 2)
         before = {}
         for scheme in (0, 1):
-            with options(dist_cg_scheme=scheme):
-                before[scheme] = dpcg(L, pd, s, P.PRECOND_JACOBI)
+            with G.options(dist_cg_scheme=scheme):
+                before[scheme] = DV.dpcg(L, pd, s, P.PRECOND_JACOBI)
                 assert before[scheme][1].converged == 1
-        X_before = dpcgn(L, pd, s, B, P.PRECOND_JACOBI)[0]
+        X_before = DV.dpcgn(L, pd, s, B, P.PRECOND_JACOBI)[0]
         assert L.fs_matrix_release_csr(L.fs_dist_matrix_shard(pd.At, 1, 0)) == 1
         prm = capi.PcgParams(s.tol, 0, P.PRECOND_JACOBI, 0, None)
         for scheme in (0, 1):
-            with options(dist_cg_scheme=scheme):
+            with G.options(dist_cg_scheme=scheme):
                 x, X, d = np.full(s.ncol, np.nan), np.full(B.shape, np.nan), np.full(s.ncol, np.nan)
                 bits, Bits = x.view(np.int64).copy(), X.view(np.int64).copy()
                 assert L.fs_dist_pcg(pd.M, x.ctypes.data, s.b.ctypes.data, s.lam, C.byref(prm), None) == FS_ERR_RELEASED
@@ -668,10 +558,10 @@ def test_released_shard_of_the_transpose_reached_through_at(L):
                 assert L.fs_dist_pcgn(pd.M, X.ctypes.data, B.ctypes.data, 2, s.lam, C.byref(prm), None) == FS_ERR_RELEASED
                 assert L.fs_dist_gram_diag(pd.M, s.lam, d.ctypes.data) == FS_ERR_RELEASED
                 assert np.array_equal(x.view(np.int64), bits) and np.array_equal(X.view(np.int64), Bits) and np.isnan(d).all()
-                x_diag, info_diag, _ = dpcg(L, pd, s, P.PRECOND_DIAG, diag=kept)   # Jacobi's own d, kept: the same dinv, the same bits
+                x_diag, info_diag, _ = DV.dpcg(L, pd, s, P.PRECOND_DIAG, diag=kept)   # Jacobi's own d, kept: the same dinv, the same bits
                 assert info_diag.converged == 1 and info_diag.iterations == before[scheme][1].iterations, scheme
                 assert M.same_bits(x_diag, before[scheme][0]).all(), scheme
-        assert M.same_bits(dpcgn(L, pd, s, B, P.PRECOND_DIAG, diag=kept)[0], X_before).all()
+        assert M.same_bits(DV.dpcgn(L, pd, s, B, P.PRECOND_DIAG, diag=kept)[0], X_before).all()
     finally:
         pd.close()
 
@@ -708,7 +598,7 @@ def test_three_handles_that_share_shards_walked_together(L, name):
     H = {}
     log = []
     try:
-        with options(binning=2, bin_rows=32 if big else 256, strict_order=int(big)):
+        with G.options(binning=2, bin_rows=32 if big else 256, strict_order=int(big)):
             H["A"] = L.fs_dist_csr_create(D, d.nrow, d.ncol, d.nnz, d.rp.ctypes.data, d.cols.ctypes.data, vals)
             assert H["A"], L.fs_last_error()
             H["At"] = L.fs_dist_coo_create(D, d.ncol, d.nrow, d.nnz, d.cols.ctypes.data, d.rows.ctypes.data, vals)
@@ -718,7 +608,7 @@ def test_three_handles_that_share_shards_walked_together(L, name):
         vec = {(where, role): LC.Guarded(mem[where], f"{role} vector in {where}", n * max(ks)) for where in ("hbm", "host") for role in ("in", "out")}
         # what a handle can do: (operation, side of the references, entry point's transposed flag)
         can = {"A": ("spmv", "spmm"), "At": ("spmv", "spmm"), "P": ("spmv", "spmm", "spmv_t", "spmm_t", "ata")}
-        with options(**{k: L.fs_get_option(k.encode()) for k in FLIPS}):
+        with G.options(**{k: L.fs_get_option(k.encode()) for k in FLIPS}):
             capi.set_option("strict_order", 1)
             for step in range(20 if big else 60):
                 forced = OPENING[step] if step < len(OPENING) else None
@@ -778,7 +668,7 @@ def test_two_host_threads_on_handles_that_share_a_side(L):
     thread its own vectors; every result is the single-threaded one bit for bit (the shape of test_two_host_threads_share_matrices)"""
     from oracle import pyoracle as O
     s = LC.pair_system("exact").s
-    pd = PairDist(L, s, 3, "coo")
+    pd = DV.PairDist(L, s, 3, "coo")
     errors = []
     try:
         t = pd.t_csr()

@@ -4,7 +4,6 @@ On these data every product and every partial sum is exact, so every order of ad
 ranks -- must give the exact sum, with +0.0 for a zero sum, in the default mode, under "reproducible" and under "strict_order"
 alike.  The 1e-12 row-scaled bar of the parity tests cannot see a dropped 2^-46 term, a flushed subnormal or a -0.0; these tests
 can.  Each test also asserts that the path it is named for really ran (kernel_name, spmm_plan, the debug hooks)."""
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -12,11 +11,10 @@ import pytest
 
 import _cases
 import _exact as E
+from _exact import PATHS
+from _gpu import PRODUCT_MODES as MODES, mode_options as _mode, options, to_device as _d
 
 pytestmark = pytest.mark.gpu
-
-MODES = ("default", "reproducible", "strict_order")
-FS_ERR_ARG = -2
 
 
 @pytest.fixture(scope="module")
@@ -25,33 +23,6 @@ def hip():
     assert torch.cuda.is_available(), "gpu tests need a GPU"
     import _hipbackend as H
     return H
-
-
-@contextlib.contextmanager
-def options(**kw):
-    """set library options, restore the values they had on the way out (an option without a getter would be "restored" to
-    FS_ERR_ARG and stay so for the rest of the process: refused)"""
-    from libfastsparse_amd import capi
-    L = capi.lib()
-    old = {k: L.fs_get_option(k.encode()) for k in kw}
-    assert all(v != FS_ERR_ARG for v in old.values()), old
-    try:
-        for k, v in kw.items():
-            capi.set_option(k, v)
-        yield
-    finally:
-        for k, v in old.items():
-            capi.set_option(k, v)
-
-
-def _mode(mode):
-    """"default" is arrival order, said so: a process started with FS_REPRODUCIBLE=1 runs these tests as well"""
-    return options(**({"reproducible": 0} if mode == "default" else {mode: 1}))
-
-
-def _d(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _poisoned(shape, fill):
@@ -66,16 +37,6 @@ def _eq(got, want, what):
 SETS = {d.name: d for d in (E.wide_range(), E.long_rows(profile="heavy", nrow=4000, seed=6), E.subnormal(), E.subnormal_pattern(),
                             E.zeros(), E.zeros(valued=False))}
 EXPECT = {n: (d.y(), d.z()) for n, d in SETS.items()}
-
-# forced copy -> (options at creation, kernel name)
-PATHS = {
-    "stream": (dict(binning=0, ldsx=0, tiling=0), "stream"),
-    "two-pass": (dict(binning=2, bin_flags=64), "two-pass"),
-    "two-pass one-byte": (dict(binning=2, bin_flags=128), "two-pass"),
-    "long rows": (dict(binning=2, long_rows=2, long_min_len=32), "two-pass"),      # (a copy of >= 4 M entries: test_long_rows_are_exact)
-    "lds-staged": (dict(ldsx=2, binning=0, tiling=0), "lds-staged"),
-    "tiled cut rows": (dict(tiling=2, binning=0, ldsx=0, tile_rows=64, tile_cols=128, tile_split=5), "tiled"),
-}
 
 
 def _build(d, path):

@@ -15,7 +15,8 @@ import pytest
 import _cg_model as M
 import _exact as E
 import _lifecycle as LC
-from test_gpu_exact import PATHS, options
+from _exact import PATHS
+from _gpu import options
 
 pytestmark = pytest.mark.gpu
 

@@ -1,4 +1,4 @@
-"""fs_mscg against the CPU model of its device arithmetic (tests/_mscg_model.py), in the idioms of test_gpu_pcg.py.
+"""fs_mscg against the CPU model of its device arithmetic (tests/_mscg_model.py), on the harness of tests/_solvers.py.
 
 1  strict_order: X, every fs_pcg_info and the per-shift state have the model's bits -- one lambda, three with the minimum twice, the
    ladder of eight (shuffled) and sixteen; also under a cap of 5; also on more than one grid stride.
@@ -16,75 +16,36 @@ import numpy as np
 import pytest
 
 import _cg_model as M
+import _gpu as G
 import _lifecycle as LC
 import _mscg_model as S
 import _pcg_model as P
-import test_gpu_pcg as G
+import _solvers as SV
+from _gpu import FS_ERR_ARG, FS_ERR_RELEASED, FS_OK, L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-FS_OK, FS_ERR_ARG, FS_ERR_RELEASED = 0, -2, -5
-MODES = G.MODES
-RECIPES = {s.name: s for s in (P.recipe(k, seed) for k in ("control", "powerlaw") for seed in (0, 1, 2))}
-ALL = dict(G.ALL, **RECIPES)
-STRICT_SET = list(G.DIAG_SET) + [n for n in RECIPES if n not in G.DIAG_SET]
-SHUFFLE8 = (5, 2, 7, 0, 3, 6, 1, 4)
+STRICT_SET = list(SV.DIAG_SET) + [n for n in SV.MSCG_RECIPES if n not in SV.DIAG_SET]
 # factors on the system's own lambda (offsets where that is 0): one; three with the minimum twice; the ladder, shuffled; sixteen
-LADDERS = {"m1": (1.0,), "m3": (3.0, 1.0, 1.0), "m8": tuple(S.LADDER[k] for k in SHUFFLE8),
-           "m16": tuple(float(f) for f in (7, 1, 2, 1e5, 3, 50, 1, 20, 1e3, 4, 300, 1e7, 5, 3, 12, 1.5))}
-STRICT_CASES = [(n, l, cap) for n in STRICT_SET for l in LADDERS for cap in (0, 5)] + [("binary_F262145", "m8", 0), ("binary_F262145", "m3", 5)]
-
-
-def lams_of(s, ladder):
-    return [s.lam * f if s.lam else (f - 1.0) * 0.125 for f in LADDERS[ladder]]
-
-
-@pytest.fixture(scope="module")
-def L():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    from libfastsparse_amd import capi
-    lib = capi.lib()
-    lib.fs_debug_last_cg_state.argtypes = [C.c_void_p]
-    lib.fs_debug_last_mscg_state.argtypes = [C.c_void_p, C.c_int]
-    return lib
-
-
-def mscg_run(L, A, At, s, lams, max_iter=0, tol=None, ldx=None):
-    """fs_mscg through capi.mscg: X (m, F), the infos, st[] by name, the per-shift array by name"""
-    from libfastsparse_amd import capi
-    m, F = len(lams), s.ncol
-    ldx = F if ldx is None else ldx
-    X = G._nan(m * ldx).as_strided((m, F), (ldx, 1))
-    infos = capi.mscg(A, At, X, G._d(s.b), lams, s.tol if tol is None else tol, max_iter, capi.current_stream())
-    raw = np.full(S.MAX_SHIFTS * S.MS_STRIDE, np.nan)
-    assert L.fs_debug_last_mscg_state(raw.ctypes.data, raw.size) == m * S.MS_STRIDE
-    return X.cpu().numpy(), infos, S.state_from_device(G._raw_state(L)), S.shifts_from_device(raw, m)
-
-
-def _assert_infos(what, infos, want):
-    assert len(infos) == len(want), what
-    for i, (g, w) in enumerate(zip(infos, want)):
-        assert g.iterations == w.iterations and g.converged == w.converged, (what, i, g.iterations, g.converged, w)
-        assert M.same_bits(g.rnorm, w.rnorm)[0] and M.same_bits(g.bnorm, w.bnorm)[0], (what, i, g.rnorm, g.bnorm, w)
+STRICT_CASES = [(n, l, cap) for n in STRICT_SET for l in SV.LADDERS for cap in (0, 5)] + [("binary_F262145", "m8", 0), ("binary_F262145", "m3", 5)]
 
 
 # ---- 1 ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,ladder,cap", STRICT_CASES, ids=[f"{n}-{l}-cap{c}" for n, l, c in STRICT_CASES])
 def test_fs_mscg_strict_is_the_model(L, name, ladder, cap):
-    s = ALL[name]
-    lams = lams_of(s, ladder)
+    s = SV.MSCG_ALL[name]
+    lams = SV.lams_of(s, ladder)
     model = S.run(s, lams, max_iter=cap)
     with G.options(strict_order=1):
-        A, At = G.handles(L, s)
-        X, infos, st, shifts = mscg_run(L, A, At, s, lams, cap)
+        A, At = SV.handles(L, s)
+        X, infos, st, shifts = SV.mscg_run(L, A, At, s, lams, cap)
     what = f"fs_mscg {ladder} cap {cap} on {name}"
     print(f"{what}: counts {[i.iterations for i in infos]} (model {[i.iterations for i in model.infos]})")
     bad = M.mismatch(X, model.X, [i.iterations for i in infos], [i.iterations for i in model.infos], st, model.state)
     assert bad is None, f"{what}: {bad}"
     bad = S.shifts_mismatch(shifts, model.shifts)
     assert bad is None, f"{what}: {bad}"
-    _assert_infos(what, infos, model.infos)
+    SV.assert_infos(what, infos, model.infos)
     if cap:
         assert all(i.iterations <= cap for i in infos)
     if name == "zero_rhs":
@@ -92,19 +53,19 @@ def test_fs_mscg_strict_is_the_model(L, name, ladder, cap):
 
 
 # ---- 2 ---------------------------------------------------------------------------------------------------------------------
-BASE_SET = [n for n in STRICT_SET if np.any(ALL[n].b != 0)]
+BASE_SET = [n for n in STRICT_SET if np.any(SV.MSCG_ALL[n].b != 0)]
 
 
 @pytest.mark.parametrize("name", BASE_SET)
-@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("mode", G.SOLVER_MODES)
 def test_columns_of_the_smallest_lambda_are_fs_cg(L, mode, name):
-    s = ALL[name]
-    with G._mode(mode):
-        A, At = G.handles(L, s)
-        xc, itc, stc = G.fs_cg_on(L, A, At, s)
+    s = SV.MSCG_ALL[name]
+    with G.mode_options(mode):
+        A, At = SV.handles(L, s)
+        xc, itc, stc = SV.fs_cg_on(L, A, At, s)
         for ladder in ("m3", "m8", "m16"):
-            lams = lams_of(s, ladder)
-            X, infos, st, shifts = mscg_run(L, A, At, s, lams)
+            lams = SV.lams_of(s, ladder)
+            X, infos, st, shifts = SV.mscg_run(L, A, At, s, lams)
             cols = [i for i, lam in enumerate(lams) if lam == min(lams)]
             assert min(lams) == s.lam and len(cols) == {"m3": 2, "m8": 1, "m16": 2}[ladder]
             want = {k: stc[k] for k in ("alpha", "beta", "stop", "rsq", "done", "iter")}
@@ -123,13 +84,13 @@ def test_the_base_set_is_whole():
 # ---- 3 ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cap", (0, 5))
 @pytest.mark.parametrize("name", STRICT_SET)
-@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("mode", G.SOLVER_MODES)
 def test_one_lambda_is_fs_pcg_without_preconditioner(L, mode, name, cap):
-    s = ALL[name]
-    with G._mode(mode):
-        A, At = G.handles(L, s)
-        xp, ip, stp = G.pcg_run(L, A, At, s, max_iter=cap)
-        X, infos, st, _ = mscg_run(L, A, At, s, [s.lam], cap)
+    s = SV.MSCG_ALL[name]
+    with G.mode_options(mode):
+        A, At = SV.handles(L, s)
+        xp, ip, stp = SV.pcg_run(L, A, At, s, max_iter=cap)
+        X, infos, st, _ = SV.mscg_run(L, A, At, s, [s.lam], cap)
     want = dict(stp)
     if stp["bb"] == 0.0:                                            # done before the first iteration: fs_pcg never writes these
         for k in ("rsq", "alpha", "beta"):
@@ -138,34 +99,29 @@ def test_one_lambda_is_fs_pcg_without_preconditioner(L, mode, name, cap):
         want.pop("beta")                                            # (never written by either)
     bad = M.mismatch(X[0], xp, infos[0].iterations, ip.iterations, st, want)
     assert bad is None, f"fs_mscg with one lambda vs fs_pcg [{mode}] cap {cap} on {name}: {bad}"
-    _assert_infos((mode, name, cap), infos, [S.Info(ip.iterations, ip.converged, ip.rnorm, ip.bnorm)])
+    SV.assert_infos((mode, name, cap), infos, [S.Info(ip.iterations, ip.converged, ip.rnorm, ip.bnorm)])
     if name == "zero_rhs":
         assert infos[0].converged == 1 and infos[0].iterations == 0 and M.same_bits(X, np.zeros(X.shape)).all()
 
 
 # ---- 4 ---------------------------------------------------------------------------------------------------------------------
-def _residual(s, lam, x):
-    am, atm, _, _ = M.csr_products(s.nrow, s.ncol, s.a_csr(), s.t_csr_coo())
-    return float(np.linalg.norm(atm(am(x)) + lam * x - s.b) / np.linalg.norm(s.b))
-
-
-@pytest.mark.parametrize("name", list(RECIPES))
+@pytest.mark.parametrize("name", list(SV.MSCG_RECIPES))
 def test_default_modes_ladder_within_the_bars(L, name):
     from libfastsparse_amd import capi
-    s = RECIPES[name]
-    lams = lams_of(s, "m8")
+    s = SV.MSCG_RECIPES[name]
+    lams = SV.lams_of(s, "m8")
     bn = np.linalg.norm(s.b)
     for mode in ("default", "cg_fixed_order=0"):
-        with G._mode(mode):
-            A, At = G.handles(L, s)
-            runs = [mscg_run(L, A, At, s, lams) for _ in range(2)]
+        with G.mode_options(mode):
+            A, At = SV.handles(L, s)
+            runs = [SV.mscg_run(L, A, At, s, lams) for _ in range(2)]
             singles = []
             for lam in lams:
-                x = G._nan(s.ncol)
-                info = capi.pcg(A, At, x, G._d(s.b), lam, s.tol, precond=P.PRECOND_NONE, stream=capi.current_stream())
+                x = G.nan_vector(s.ncol)
+                info = capi.pcg(A, At, x, G.to_device(s.b), lam, s.tol, precond=P.PRECOND_NONE, stream=capi.current_stream())
                 singles.append((x.cpu().numpy(), info))
         X, infos, _, _ = runs[0]
-        res = [_residual(s, lam, X[i]) for i, lam in enumerate(lams)]
+        res = [SV.residual(s, X[i], lam) for i, lam in enumerate(lams)]
         print(f"{name} [{mode}]: counts {[i.iterations for i in infos]}, separate fs_pcg {[i.iterations for _, i in singles]}, "
               f"true residuals / tol {[round(r / s.tol, 2) for r in res]}")
         for i, lam in enumerate(lams):
@@ -175,7 +131,7 @@ def test_default_modes_ladder_within_the_bars(L, name):
             assert infos[i].rnorm <= s.tol * infos[i].bnorm, what
             xs, si = singles[i]
             assert si.converged == 1, what
-            assert np.linalg.norm(X[i] - xs) <= (res[i] + _residual(s, lam, xs)) * bn / lam * 1.01, what
+            assert np.linalg.norm(X[i] - xs) <= (res[i] + SV.residual(s, xs, lam)) * bn / lam * 1.01, what
         if mode == "default":                                       # fixed-order products: a solve repeats its bits
             assert M.same_bits(runs[1][0], X).all() and [i.iterations for i in runs[1][1]] == [i.iterations for i in infos], name
 
@@ -183,11 +139,11 @@ def test_default_modes_ladder_within_the_bars(L, name):
 # ---- 5 ---------------------------------------------------------------------------------------------------------------------
 def test_statuses(L):
     from libfastsparse_amd import capi
-    s = RECIPES["control_seed0"]
-    A, At = G.handles(L, s)
+    s = SV.MSCG_RECIPES["control_seed0"]
+    A, At = SV.handles(L, s)
     st = capi.current_stream()
     F, m = s.ncol, 3
-    b, X = G._d(s.b), G._nan(16 * F)
+    b, X = G.to_device(s.b), G.nan_vector(16 * F)
     bits = X.cpu().numpy().view(np.int64).copy()
     lams = [s.lam * 3, s.lam, s.lam * 10]
 
@@ -204,7 +160,7 @@ def test_statuses(L):
            "lambda -inf": call(lam=[1.0, 2.0, float("-inf")])}
     assert all(rc == FS_ERR_ARG for rc in bad.values()), bad
     assert L.fs_last_error()
-    assert np.array_equal(X.cpu().numpy().view(np.int64), bits), "a refused call wrote to X"
+    SV.refused_call_leaves(X, bits)
     assert call(tol=0.0, max_iter=2) == FS_OK                        # tol = 0 is legal: the cap ends it (info NULL is legal too)
     assert call(m_=16) == FS_OK
     infos = (capi.PcgInfo * m)()
@@ -218,27 +174,27 @@ def test_a_product_error_is_passed_through(L):
     A' the solve ends with FS_ERR_RELEASED and the product's message; outside strict_order the kept copy serves and the solve is
     the one from before the release, and after fs_matrix_restore_csr the strict solve runs again"""
     from libfastsparse_amd import capi
-    s = RECIPES["powerlaw_seed0"]
+    s = SV.MSCG_RECIPES["powerlaw_seed0"]
     st = capi.current_stream()
     trp, tcc, tvv = s.t_csr_coo()
-    lams = lams_of(s, "m3")
-    A, _ = G.handles(L, s)
+    lams = SV.lams_of(s, "m3")
+    A, _ = SV.handles(L, s)
     with G.options(binning=2, bin_flags=64):                         # a kept two-pass copy: there is something to release for
-        At = capi.Matrix.from_csr(s.ncol, s.nrow, G._d(trp), G._d(tcc), None if tvv is None else G._d(tvv))
+        At = capi.Matrix.from_csr(s.ncol, s.nrow, G.to_device(trp), G.to_device(tcc), None if tvv is None else G.to_device(tvv))
     assert At.kernel_name() == "two-pass"
-    X_before, infos_before, _, _ = mscg_run(L, A, At, s, lams)
+    X_before, infos_before, _, _ = SV.mscg_run(L, A, At, s, lams)
     assert all(i.converged == 1 for i in infos_before)
     assert At.release_csr() == 1
-    X = G._nan(len(lams) * s.ncol)
+    X = G.nan_vector(len(lams) * s.ncol)
     arr = (C.c_double * len(lams))(*lams)
     with G.options(strict_order=1):
-        assert L.fs_mscg(A.h, At.h, X.data_ptr(), s.ncol, G._d(s.b).data_ptr(), len(lams), arr, s.tol, 0, None, st) == FS_ERR_RELEASED
+        assert L.fs_mscg(A.h, At.h, X.data_ptr(), s.ncol, G.to_device(s.b).data_ptr(), len(lams), arr, s.tol, 0, None, st) == FS_ERR_RELEASED
         assert b"fs_matrix_release_csr" in L.fs_last_error()
-    X_after, infos_after, _, _ = mscg_run(L, A, At, s, lams)         # the kept copy needs no plain array
+    X_after, infos_after, _, _ = SV.mscg_run(L, A, At, s, lams)         # the kept copy needs no plain array
     assert M.same_bits(X_after, X_before).all() and [i.iterations for i in infos_after] == [i.iterations for i in infos_before]
-    At.restore_csr(G._d(trp), G._d(tcc), None if tvv is None else G._d(tvv))
+    At.restore_csr(G.to_device(trp), G.to_device(tcc), None if tvv is None else G.to_device(tvv))
     with G.options(strict_order=1):
-        X_strict, infos_strict, _, _ = mscg_run(L, A, At, s, lams)
+        X_strict, infos_strict, _, _ = SV.mscg_run(L, A, At, s, lams)
     assert all(i.converged == 1 for i in infos_strict) and np.isfinite(X_strict).all()
 
 
@@ -251,12 +207,12 @@ def test_guard_zones(L):
     st = capi.current_stream()
     gap_bits = LC.PREFILLS["nan"]
     for name in ("control_seed0", "powerlaw_seed0", "binary_F257"):
-        s = ALL[name]
+        s = SV.MSCG_ALL[name]
         F = s.ncol
-        A, At = G.handles(L, s)
+        A, At = SV.handles(L, s)
         gx, gb = LC.Guarded(mem, "X of fs_mscg", 16 * (F + 3)), LC.Guarded(mem, "b of fs_mscg", F)
         for ladder, cap in (("m1", 0), ("m3", 0), ("m8", 0), ("m8", 5), ("m16", 0)):
-            lams = lams_of(s, ladder)
+            lams = SV.lams_of(s, ladder)
             m = len(lams)
             ref = None
             for ldx in (F, F + 3):
@@ -272,9 +228,7 @@ def test_guard_zones(L):
                     bad = mem.first_bad_guard([gx, gb])
                     assert bad is None, (what, bad.first_broken())
                     assert mem.eq(gb.view, mem.const(s.b)), (what, "b changed")
-                    got = mem.get(gx.view)
-                    X = np.stack([got[i * ldx:i * ldx + F] for i in range(m)])
-                    gaps = np.concatenate([got[i * ldx + F:(i + 1) * ldx] for i in range(m - 1)] + [np.zeros(0)])
+                    X, gaps = SV.split_rows_and_gaps(mem.get(gx.view), m, F, ldx)
                     assert (gaps.view(np.int64) == gap_bits).all(), (what, "a gap between columns was written")
                     assert np.isfinite(X).all(), what
                     if not cap:

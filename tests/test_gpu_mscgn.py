@@ -1,5 +1,5 @@
 """fs_mscgn against the CPU model of its columns (tests/_mscgn_model.py: column j is the model of fs_mscg on B[:, j]), against fs_mscg
-and against fs_pcgn on the device, in the idioms of test_gpu_mscg.py and test_gpu_pcgn.py.
+and against fs_pcgn on the device, on the harness of tests/_solvers.py.
 
 1  strict_order: X, every fs_pcg_info and every column's st[] / ms[] have the model's bits -- k in {1, 2, 3, 4, 5, 7, 8, 16, 17, 32}, one
    lambda, three with the minimum twice, the ladder of eight (shuffled) and sixteen, caps 0 and 5; a duplicate column has identical
@@ -23,23 +23,16 @@ import numpy as np
 import pytest
 
 import _cg_model as M
+import _gpu as G
 import _lifecycle as LC
 import _mscg_model as S
 import _mscgn_model as SN
 import _pcg_model as P
-import test_gpu_mscg as GM
-import test_gpu_pcg as G
-import test_gpu_pcgn as GN
+import _solvers as SV
+from _gpu import FS_ERR_ARG, FS_ERR_RELEASED, FS_OK, L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-FS_OK, FS_ERR_ARG, FS_ERR_RELEASED = 0, -2, -5
-ALL = GM.ALL
-LADDERS = GM.LADDERS
-lams_of = GM.lams_of
-columns = GN.columns
-KS = GN.KS
-KERNELS = GN.KERNELS
 SYSTEMS10 = ("fixture_100x50", "binary_F1", "binary_F63", "binary_F64", "binary_F65", "binary_F257", "valued", "three_eigenvalues",
              "zero_rhs", "lambda0_empty_column")
 # (system, k, ladder, cap): every k and every ladder meets two systems or more, every system two values of k or more
@@ -59,44 +52,17 @@ _COUNTS_SEEN = []                                                      # per str
 
 
 def test_the_strict_set_covers_what_it_should():
-    for k in KS:
+    for k in SV.KS:
         assert len({n for n, kk, _, _ in STRICT_SET if kk == k}) >= 2, k
-    for ladder in LADDERS:
+    for ladder in SV.LADDERS:
         assert len({n for n, _, l, _ in STRICT_SET if l == ladder}) >= 2, ladder
     for name in SYSTEMS10:
         assert len({k for n, k, _, _ in STRICT_SET if n == name}) >= 2, name
-    assert {n for n, _, _, _ in STRICT_SET} == set(SYSTEMS10) and {k for _, k, _, _ in STRICT_SET} == set(KS)
-    assert {c for _, _, _, c in STRICT_SET} == {0, 5} and set(LADDERS) == {"m1", "m3", "m8", "m16"}
-    assert {len(LADDERS[l]) for l in LADDERS} == {1, 3, 8, 16} and LADDERS["m3"].count(min(LADDERS["m3"])) == 2
-    s = ALL[LARGE_CASE[0]]
+    assert {n for n, _, _, _ in STRICT_SET} == set(SYSTEMS10) and {k for _, k, _, _ in STRICT_SET} == set(SV.KS)
+    assert {c for _, _, _, c in STRICT_SET} == {0, 5} and set(SV.LADDERS) == {"m1", "m3", "m8", "m16"}
+    assert {len(SV.LADDERS[l]) for l in SV.LADDERS} == {1, 3, 8, 16} and SV.LADDERS["m3"].count(min(SV.LADDERS["m3"])) == 2
+    s = SV.MSCG_ALL[LARGE_CASE[0]]
     assert s.ncol > M.RED_BLOCKS * M.RED_THREADS and LARGE_CASE[1:3] == (2, "m3")
-
-
-@pytest.fixture(scope="module")
-def L():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    from libfastsparse_amd import capi
-    lib = capi.lib()
-    lib.fs_debug_last_cg_state.argtypes = [C.c_void_p]
-    lib.fs_debug_last_mscg_state.argtypes = [C.c_void_p, C.c_int]
-    lib.fs_debug_last_pcgn_state.argtypes = [C.c_void_p, C.c_int]
-    lib.fs_debug_last_mscgn_state.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    return lib
-
-
-def mscgn_run(L, A, At, s, B, lams, max_iter=0, tol=None):
-    """fs_mscgn through capi.mscgn: X (m, F, k), infos[i][j], and per column (st[] by name, the per-shift array by name)"""
-    from libfastsparse_amd import capi
-    m, (F, k) = len(lams), B.shape
-    X = G._nan(m * F * k).view(m, F, k)
-    infos = capi.mscgn(A, At, X, G._d(B), lams, s.tol if tol is None else tol, max_iter, capi.current_stream())
-    cols = []
-    for j in range(k):
-        st, raw = np.full(M.CG_STATE_DOUBLES, np.nan), np.full(S.MAX_SHIFTS * S.MS_STRIDE, np.nan)
-        assert L.fs_debug_last_mscgn_state(j, st.ctypes.data, raw.ctypes.data, raw.size) == m * S.MS_STRIDE
-        cols.append((S.state_from_device(st), S.shifts_from_device(raw, m)))
-    return X.cpu().numpy(), infos, cols
 
 
 def _with_b(s, b):
@@ -105,44 +71,23 @@ def _with_b(s, b):
     return t
 
 
-def _assert_column(what, X, infos, col, want_X, want_infos, want_state, want_shifts):
-    """column j of a solve: X (m, F), its m infos, (st, shifts) against fs_mscg's (the model's or the device's)"""
-    st, shifts = col
-    bad = M.mismatch(X, want_X, [i.iterations for i in infos], [i.iterations for i in want_infos], st, want_state)
-    assert bad is None, f"{what}: {bad}"
-    bad = S.shifts_mismatch(shifts, want_shifts)
-    assert bad is None, f"{what}: {bad}"
-    GM._assert_infos(what, infos, want_infos)
-
-
 def _column_infos(infos, j):
     return [row[j] for row in infos]
 
 
-def _written(st):
-    """the scalars of a device st[] of fs_mscg that such a solve is sure to have written: one that is done at the start writes no
-    alpha, one without a second iteration no beta (those slots hold what the allocation held)"""
-    never = set()
-    if st["iter"] == 0.0:
-        never.add("beta")
-        if st["done"] == 1.0 and M.same_bits(st["rr"], st["bb"])[0]:
-            never.add("alpha")
-    return {key: v for key, v in st.items() if key not in never}
-
-
 # ---- 1 ---------------------------------------------------------------------------------------------------------------------
 def _strict_case(L, name, k, ladder, cap, kernel):
-    s = ALL[name]
-    lams = lams_of(s, ladder)
-    B = columns(s, k)
+    s = SV.MSCG_ALL[name]
+    lams = SV.lams_of(s, ladder)
+    B = SV.columns(s, k)
     model = SN.run(s, B, lams, max_iter=cap, cache=_MODEL_CACHE)
     with G.options(strict_order=1, pcgn_kernel=kernel):
-        A, At = G.handles(L, s)
-        X, infos, cols = mscgn_run(L, A, At, s, B, lams, cap)
+        A, At = SV.handles(L, s)
+        X, infos, cols = SV.mscgn_run(L, A, At, s, B, lams, cap)
     assert X.shape == (len(lams), s.ncol, k) and len(infos) == len(lams) and all(len(r) == k for r in infos)
     for j in range(k):
         c = model.columns[j]
-        _assert_column(f"fs_mscgn {ladder} cap {cap} k {k} on {name}, column {j}", X[:, :, j], _column_infos(infos, j), cols[j], c.X, c.infos,
+        SV.assert_ladder_column(f"fs_mscgn {ladder} cap {cap} k {k} on {name}, column {j}", X[:, :, j], _column_infos(infos, j), cols[j], c.X, c.infos,
                        c.state, c.shifts)
         if cap:
             assert all(i.iterations <= cap for i in _column_infos(infos, j))
@@ -156,14 +101,14 @@ def _strict_case(L, name, k, ladder, cap, kernel):
     _COUNTS_SEEN.append([infos[base][j].iterations for j in range(k)])
 
 
-@pytest.mark.parametrize("kernel", KERNELS, ids=[f"pcgn_kernel{v}" for v in KERNELS])
+@pytest.mark.parametrize("kernel", SV.KERNELS, ids=[f"pcgn_kernel{v}" for v in SV.KERNELS])
 @pytest.mark.parametrize("name,k,ladder,cap", STRICT_SET, ids=[f"{n}-k{k}-{l}-cap{c}" for n, k, l, c in STRICT_SET])
 def test_fs_mscgn_strict_is_the_model(L, name, k, ladder, cap, kernel):
     _strict_case(L, name, k, ladder, cap, kernel)
 
 
 def test_fs_mscgn_strict_is_the_model_on_more_than_one_grid_stride(L):
-    for kernel in KERNELS:
+    for kernel in SV.KERNELS:
         _strict_case(L, *LARGE_CASE, kernel)
 
 
@@ -175,50 +120,50 @@ def test_columns_finish_at_different_iterations(L):
 
 
 # ---- 2 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kernel", KERNELS, ids=[f"pcgn_kernel{v}" for v in KERNELS])
+@pytest.mark.parametrize("kernel", SV.KERNELS, ids=[f"pcgn_kernel{v}" for v in SV.KERNELS])
 @pytest.mark.parametrize("name,k,ladder,cap", [("fixture_100x50", 5, "m8", 0), ("valued", 3, "m16", 0), ("binary_F257", 4, "m3", 5),
                                                ("powerlaw_seed0", 7, "m8", 0)])
 def test_columns_are_fs_mscg_on_the_same_handles(L, name, k, ladder, cap, kernel):
-    s = ALL[name]
-    lams = lams_of(s, ladder)
-    B = columns(s, k)
+    s = SV.MSCG_ALL[name]
+    lams = SV.lams_of(s, ladder)
+    B = SV.columns(s, k)
     with G.options(strict_order=1, pcgn_kernel=kernel):
-        A, At = G.handles(L, s)
-        alone = [GM.mscg_run(L, A, At, _with_b(s, B[:, j]), lams, cap) for j in range(k)]
-        X, infos, cols = mscgn_run(L, A, At, s, B, lams, cap)
+        A, At = SV.handles(L, s)
+        alone = [SV.mscg_run(L, A, At, _with_b(s, B[:, j]), lams, cap) for j in range(k)]
+        X, infos, cols = SV.mscgn_run(L, A, At, s, B, lams, cap)
     for j, (x, info, st, shifts) in enumerate(alone):
-        _assert_column(f"column {j} of fs_mscgn {ladder} cap {cap} vs fs_mscg on {name}", X[:, :, j], _column_infos(infos, j), cols[j], x, info,
-                       _written(st), shifts)
+        SV.assert_ladder_column(f"column {j} of fs_mscgn {ladder} cap {cap} vs fs_mscg on {name}", X[:, :, j], _column_infos(infos, j), cols[j], x, info,
+                       SV.written(st), shifts)
 
 
 # ---- 3 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mode", G.MODES)
+@pytest.mark.parametrize("mode", G.SOLVER_MODES)
 def test_one_column_is_fs_mscg(L, mode):
     for name, ladder, cap in (("fixture_100x50", "m8", 0), ("binary_F65", "m3", 5), ("valued", "m16", 0), ("zero_rhs", "m3", 0),
                               ("control_seed0", "m8", 0), ("powerlaw_seed0", "m8", 0), ("lambda0_empty_column", "m8", 5)):
-        s = ALL[name]
-        lams = lams_of(s, ladder)
-        with G._mode(mode):
-            A, At = G.handles(L, s)
-            x, info, st, shifts = GM.mscg_run(L, A, At, s, lams, cap)
-            X, infos, cols = mscgn_run(L, A, At, s, s.b.reshape(-1, 1), lams, cap)
-        _assert_column(f"fs_mscgn with k = 1 vs fs_mscg [{mode}] {ladder} cap {cap} on {name}", X[:, :, 0], _column_infos(infos, 0), cols[0], x,
-                       info, _written(st), shifts)
+        s = SV.MSCG_ALL[name]
+        lams = SV.lams_of(s, ladder)
+        with G.mode_options(mode):
+            A, At = SV.handles(L, s)
+            x, info, st, shifts = SV.mscg_run(L, A, At, s, lams, cap)
+            X, infos, cols = SV.mscgn_run(L, A, At, s, s.b.reshape(-1, 1), lams, cap)
+        SV.assert_ladder_column(f"fs_mscgn with k = 1 vs fs_mscg [{mode}] {ladder} cap {cap} on {name}", X[:, :, 0], _column_infos(infos, 0), cols[0], x,
+                       info, SV.written(st), shifts)
 
 
 # ---- 4 ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("cap", (0, 5))
 @pytest.mark.parametrize("k", (1, 3, 8))
-@pytest.mark.parametrize("mode", G.MODES)
+@pytest.mark.parametrize("mode", G.SOLVER_MODES)
 def test_one_lambda_is_fs_pcgn_without_preconditioner(L, mode, k, cap):
     for name in ("fixture_100x50", "binary_F257", "scaled_seed0", "powerlaw_seed0"):
-        s = ALL[name]
-        B = columns(s, k)
-        with G._mode(mode):
-            A, At = G.handles(L, s)
-            Xp, ip, _, cs = GN.pcgn_run(L, A, At, s, B, P.PRECOND_NONE, max_iter=cap)
-            Xq, iq, _, _ = GN.pcgn_run(L, A, At, s, B, P.PRECOND_NONE, max_iter=cap)
-            X, infos, cols = mscgn_run(L, A, At, s, B, [s.lam], cap)
+        s = SV.MSCG_ALL[name]
+        B = SV.columns(s, k)
+        with G.mode_options(mode):
+            A, At = SV.handles(L, s)
+            Xp, ip, _, cs = SV.pcgn_run(L, A, At, s, B, P.PRECOND_NONE, max_iter=cap)
+            Xq, iq, _, _ = SV.pcgn_run(L, A, At, s, B, P.PRECOND_NONE, max_iter=cap)
+            X, infos, cols = SV.mscgn_run(L, A, At, s, B, [s.lam], cap)
         repeats = M.same_bits(Xp, Xq).all() and [i.iterations for i in ip] == [i.iterations for i in iq]
         assert repeats or (mode == "cg_fixed_order=0" and k > 1), (mode, name, k, "fs_pcgn does not repeat its bits")
         if not repeats:                                                # nothing to be equal to
@@ -235,16 +180,16 @@ def test_one_lambda_is_fs_pcgn_without_preconditioner(L, mode, k, cap):
 
 
 # ---- 5 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", list(GM.RECIPES))
+@pytest.mark.parametrize("name", list(SV.MSCG_RECIPES))
 def test_default_modes_ladder_within_the_bars(L, name):
-    s = GM.RECIPES[name]
-    lams = lams_of(s, "m8")
-    B = columns(s, 4)
+    s = SV.MSCG_RECIPES[name]
+    lams = SV.lams_of(s, "m8")
+    B = SV.columns(s, 4)
     am, atm, _, _ = M.csr_products(s.nrow, s.ncol, s.a_csr(), s.t_csr_coo())
     for mode in ("default", "cg_fixed_order=0"):
-        with G._mode(mode):
-            A, At = G.handles(L, s)
-            runs = [mscgn_run(L, A, At, s, B, lams) for _ in range(2)]
+        with G.mode_options(mode):
+            A, At = SV.handles(L, s)
+            runs = [SV.mscgn_run(L, A, At, s, B, lams) for _ in range(2)]
         X, infos, _ = runs[0]
         for i, lam in enumerate(lams):
             for j in range(4):
@@ -263,20 +208,20 @@ def test_default_modes_ladder_within_the_bars(L, name):
 
 # ---- 6 ---------------------------------------------------------------------------------------------------------------------
 def test_a_nan_column_stays_in_its_column(L):
-    s = ALL["binary_F257"]
-    lams = lams_of(s, "m3")
-    B = columns(s, 5)
+    s = SV.MSCG_ALL["binary_F257"]
+    lams = SV.lams_of(s, "m3")
+    B = SV.columns(s, 5)
     B[7, 3] = np.nan
     with G.options(strict_order=1):
-        A, At = G.handles(L, s)
-        alone = {j: GM.mscg_run(L, A, At, _with_b(s, B[:, j]), lams, 5) for j in range(5)}
-        for kernel in KERNELS:
+        A, At = SV.handles(L, s)
+        alone = {j: SV.mscg_run(L, A, At, _with_b(s, B[:, j]), lams, 5) for j in range(5)}
+        for kernel in SV.KERNELS:
             with G.options(pcgn_kernel=kernel):
-                X, infos, cols = mscgn_run(L, A, At, s, B, lams, 5)
+                X, infos, cols = SV.mscgn_run(L, A, At, s, B, lams, 5)
             for j, (x, info, st, shifts) in alone.items():
                 what = (s.name, kernel, j)
                 assert M.same_bits(X[:, :, j], x).all(), what
-                GM._assert_infos(what, _column_infos(infos, j), info)
+                SV.assert_infos(what, _column_infos(infos, j), info)
                 assert S.shifts_mismatch(cols[j][1], shifts) is None, what
                 if j != 3:
                     assert np.isfinite(X[:, :, j]).all(), what
@@ -288,13 +233,13 @@ def test_a_nan_column_stays_in_its_column(L):
 # ---- 7 ---------------------------------------------------------------------------------------------------------------------
 def test_statuses(L):
     from libfastsparse_amd import capi
-    s = GM.RECIPES["control_seed0"]
-    A, At = G.handles(L, s)
+    s = SV.MSCG_RECIPES["control_seed0"]
+    A, At = SV.handles(L, s)
     st = capi.current_stream()
     F, k, m = s.ncol, 3, 3
-    B = G._d(columns(s, k))
+    B = G.to_device(SV.columns(s, k))
     bits = LC.PREFILLS["nan"] + np.arange(16 * (F * k + 3), dtype=np.int64)       # quiet NaNs, each tagged with its place
-    X = G._d(bits.view(np.float64))
+    X = G.to_device(bits.view(np.float64))
     lams = [s.lam * 3, s.lam, s.lam * 10]
 
     def call(A_=A.h, At_=At.h, X_=X.data_ptr(), ldx=F * k, b_=B.data_ptr(), k_=k, m_=m, lam="default", tol=1e-8, max_iter=0, info=None):
@@ -310,7 +255,7 @@ def test_statuses(L):
            "lambda inf": call(lam=[float("inf"), 1.0, 2.0]), "lambda -inf": call(lam=[1.0, 2.0, float("-inf")])}
     assert all(rc == FS_ERR_ARG for rc in bad.values()), bad
     assert L.fs_last_error()
-    assert np.array_equal(X.cpu().numpy().view(np.int64), bits), "a refused call wrote to X"
+    SV.refused_call_leaves(X, bits)
     assert call(tol=0.0, max_iter=2) == FS_OK                          # tol = 0 is legal: the cap ends it (info NULL is legal too)
     assert call(m_=16, ldx=F * k + 3) == FS_OK
     infos = (capi.PcgInfo * (m * k))()
@@ -323,36 +268,36 @@ def test_released_handles(L):
     """FS_ERR_RELEASED before anything is written to X: under strict_order after fs_matrix_release_csr on a kept two-pass A'; for a k
     that was never prepared before the release.  After fs_matrix_restore_csr the same bits return."""
     from libfastsparse_amd import capi
-    s = GM.RECIPES["powerlaw_seed0"]
+    s = SV.MSCG_RECIPES["powerlaw_seed0"]
     st = capi.current_stream()
     trp, tcc, tvv = s.t_csr_coo()
-    lams = lams_of(s, "m3")
+    lams = SV.lams_of(s, "m3")
     arr = (C.c_double * len(lams))(*lams)
     k = 3
-    B = columns(s, k)
-    A, _ = G.handles(L, s)
+    B = SV.columns(s, k)
+    A, _ = SV.handles(L, s)
     with G.options(binning=2, bin_flags=64):                           # a kept two-pass copy: there is something to release for
-        At = capi.Matrix.from_csr(s.ncol, s.nrow, G._d(trp), G._d(tcc), None if tvv is None else G._d(tvv))
+        At = capi.Matrix.from_csr(s.ncol, s.nrow, G.to_device(trp), G.to_device(tcc), None if tvv is None else G.to_device(tvv))
     assert At.kernel_name() == "two-pass"
-    X_before, infos_before, _ = mscgn_run(L, A, At, s, B, lams)        # prepares k = 3
+    X_before, infos_before, _ = SV.mscgn_run(L, A, At, s, B, lams)        # prepares k = 3
     assert all(i.converged == 1 for row in infos_before for i in row)
     assert At.release_csr() == 1
-    X = G._nan(len(lams) * s.ncol * 4)
+    X = G.nan_vector(len(lams) * s.ncol * 4)
     bits = X.cpu().numpy().view(np.int64).copy()
-    Bd, B4 = G._d(B), G._d(columns(s, 4))
+    Bd, B4 = G.to_device(B), G.to_device(SV.columns(s, 4))
     with G.options(strict_order=1):
         assert L.fs_mscgn(A.h, At.h, X.data_ptr(), s.ncol * k, Bd.data_ptr(), k, len(lams), arr, s.tol, 0, None, st) == FS_ERR_RELEASED
         assert b"fs_matrix_release_csr" in L.fs_last_error()
-    assert np.array_equal(X.cpu().numpy().view(np.int64), bits), "the refused strict solve wrote to X"
+    SV.refused_call_leaves(X, bits, "the refused strict solve wrote to X")
     # k = 4 was never prepared on this A': fs_matrix_prepare needs the plain arrays
     assert L.fs_mscgn(A.h, At.h, X.data_ptr(), s.ncol * 4, B4.data_ptr(), 4, len(lams), arr, s.tol, 3, None, st) == FS_ERR_RELEASED
-    assert np.array_equal(X.cpu().numpy().view(np.int64), bits), "the refused k = 4 solve wrote to X"
-    X_after, infos_after, _ = mscgn_run(L, A, At, s, B, lams)          # the kept copy needs no plain array
+    SV.refused_call_leaves(X, bits, "the refused k = 4 solve wrote to X")
+    X_after, infos_after, _ = SV.mscgn_run(L, A, At, s, B, lams)          # the kept copy needs no plain array
     assert M.same_bits(X_after, X_before).all()
     assert [[i.iterations for i in row] for row in infos_after] == [[i.iterations for i in row] for row in infos_before]
-    At.restore_csr(G._d(trp), G._d(tcc), None if tvv is None else G._d(tvv))
+    At.restore_csr(G.to_device(trp), G.to_device(tcc), None if tvv is None else G.to_device(tvv))
     with G.options(strict_order=1):
-        X_strict, infos_strict, _ = mscgn_run(L, A, At, s, B, lams)
+        X_strict, infos_strict, _ = SV.mscgn_run(L, A, At, s, B, lams)
     assert all(i.converged == 1 for row in infos_strict for i in row) and np.isfinite(X_strict).all()
 
 
@@ -366,14 +311,14 @@ def test_guard_zones(L):
     st = capi.current_stream()
     gap_bits = LC.PREFILLS["nan"]
     for name in ("control_seed0", "binary_F257"):
-        s = ALL[name]
+        s = SV.MSCG_ALL[name]
         F = s.ncol
-        A, At = G.handles(L, s)
+        A, At = SV.handles(L, s)
         gx, gb = LC.Guarded(mem, "X of fs_mscgn", 16 * (F * 4 + 3)), LC.Guarded(mem, "B of fs_mscgn", F * 4)
-        for kernel, k, ladder, cap in [(v, k, l, c) for v in KERNELS for k in (3, 4) for l, c in (("m1", 0), ("m3", 0), ("m8", 5), ("m16", 0))]:
-            lams = lams_of(s, ladder)
+        for kernel, k, ladder, cap in [(v, k, l, c) for v in SV.KERNELS for k in (3, 4) for l, c in (("m1", 0), ("m3", 0), ("m8", 5), ("m16", 0))]:
+            lams = SV.lams_of(s, ladder)
             m = len(lams)
-            B = columns(s, k)
+            B = SV.columns(s, k)
             ne = F * k
             ref = None
             for ldx in (ne, ne + 3):
@@ -390,9 +335,7 @@ def test_guard_zones(L):
                     bad = mem.first_bad_guard([gx, gb])
                     assert bad is None, (what, bad.first_broken())
                     assert mem.eq(gb.view, mem.const(B.reshape(-1))), (what, "B changed")
-                    got = mem.get(gx.view)
-                    X = np.stack([got[i * ldx:i * ldx + ne] for i in range(m)])
-                    gaps = np.concatenate([got[i * ldx + ne:(i + 1) * ldx] for i in range(m - 1)] + [np.zeros(0)])
+                    X, gaps = SV.split_rows_and_gaps(mem.get(gx.view), m, ne, ldx)
                     assert (gaps.view(np.int64) == gap_bits).all(), (what, "a gap between panels was written")
                     assert np.isfinite(X).all(), what
                     if not cap:
@@ -407,18 +350,18 @@ def test_guard_zones(L):
 def test_the_solve_prepares_the_products_and_leaks_no_work_space(L):
     import torch
     from libfastsparse_amd import capi
-    s = GM.RECIPES["powerlaw_seed0"]
+    s = SV.MSCG_RECIPES["powerlaw_seed0"]
     arp, acc, avv = s.a_csr()
     trp, tcc, tvv = s.t_csr_coo()
-    lams = lams_of(s, "m8")
+    lams = SV.lams_of(s, "m8")
     # a matrix this small keeps and extends the two-pass copy only under binning = 2; the solver's own options are the defaults
     with G.options(binning=2, bin_flags=64):
-        A = capi.Matrix.from_csr(s.nrow, s.ncol, G._d(arp), G._d(acc), None if avv is None else G._d(avv))
-        At = capi.Matrix.from_csr(s.ncol, s.nrow, G._d(trp), G._d(tcc), None if tvv is None else G._d(tvv))
+        A = capi.Matrix.from_csr(s.nrow, s.ncol, G.to_device(arp), G.to_device(acc), None if avv is None else G.to_device(avv))
+        At = capi.Matrix.from_csr(s.ncol, s.nrow, G.to_device(trp), G.to_device(tcc), None if tvv is None else G.to_device(tvv))
         assert A.kernel_name() == "two-pass" and At.kernel_name() == "two-pass"
         assert A.spmm_plan(4) != "k-column two-pass" and At.spmm_plan(4) != "k-column two-pass"
-        B = G._d(columns(s, 4))
-        X = G._nan(len(lams) * s.ncol * 4).view(len(lams), s.ncol, 4)
+        B = G.to_device(SV.columns(s, 4))
+        X = G.nan_vector(len(lams) * s.ncol * 4).view(len(lams), s.ncol, 4)
         free = []
         for _ in range(3):
             infos = capi.mscgn(A, At, X, B, lams, s.tol, 0, capi.current_stream())

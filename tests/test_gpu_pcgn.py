@@ -1,8 +1,8 @@
 """fs_pcgn against the CPU model of its columns (tests/_pcgn_model.py: column j is the model of fs_pcg on B[:, j]) and against fs_pcg
-on the device, in the idioms of test_gpu_pcg.py.
+on the device, on the harness of tests/_solvers.py.
 
 1  strict_order: X, every fs_pcg_info and the per-column state have the model's bits -- k in {1, 2, 3, 4, 5, 7, 8, 16, 17, 32}, the cases
-   of test_gpu_pcg.py (none, Jacobi, a caller's diagonal, warm starts, caps); a duplicate column has identical bits, a zero column is
+   of _solvers.CASES (none, Jacobi, a caller's diagonal, warm starts, caps); a duplicate column has identical bits, a zero column is
    x = +0.0 in 0 iterations.
 2  strict_order: column j is fs_pcg on the same handles with B[:, j], bit for bit -- on more than one grid stride per column, and from
    a warm start whose columns freeze at different iterations, one of them before the first product.
@@ -20,18 +20,15 @@ import numpy as np
 import pytest
 
 import _cg_model as M
+import _gpu as G
 import _lifecycle as LC
 import _pcg_model as P
 import _pcgn_model as N
-import test_gpu_pcg as G
+import _solvers as SV
+from _gpu import FS_ERR_ARG, FS_ERR_RELEASED, FS_OK, L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-FS_OK, FS_ERR_ARG, FS_ERR_RELEASED = 0, -2, -5
-ALL = G.ALL
-CASES = G.CASES
-KS = (1, 2, 3, 4, 5, 7, 8, 16, 17, 32)
-KERNELS = (1, 2)                                     # option "pcgn_kernel": a lane per row; the panels staged through LDS (0: auto)
 # (system, k, case of CASES): every k meets no preconditioner, Jacobi and a caller's diagonal; every system meets two values of k or more.
 # The wide panels go to the systems whose model is quick (the model solves every distinct column in Python)
 STRICT_SET = [("fixture_100x50", 1, 0), ("fixture_100x50", 8, 1), ("fixture_100x50", 32, 2),
@@ -52,92 +49,30 @@ _MODEL_CACHE = {}
 
 
 def test_the_strict_set_covers_what_it_should():
-    met = {(k, CASES[c][1]) for _, k, c in STRICT_SET}
-    assert met == {(k, p) for k in KS for p in (P.PRECOND_NONE, P.PRECOND_JACOBI, P.PRECOND_DIAG)}
+    met = {(k, SV.CASES[c][1]) for _, k, c in STRICT_SET}
+    assert met == {(k, p) for k in SV.KS for p in (P.PRECOND_NONE, P.PRECOND_JACOBI, P.PRECOND_DIAG)}
     for name in SYSTEMS12:
         assert len({k for n, k, _ in STRICT_SET if n == name}) >= 2, name
     assert {n for n, _, _ in STRICT_SET} == set(SYSTEMS12)
-    assert {c for _, _, c in STRICT_SET} == set(range(len(CASES)))
-
-
-@pytest.fixture(scope="module")
-def L():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    from libfastsparse_amd import capi
-    lib = capi.lib()
-    lib.fs_debug_last_cg_state.argtypes = [C.c_void_p]
-    lib.fs_debug_last_pcgn_state.argtypes = [C.c_void_p, C.c_int]
-    return lib
-
-
-def columns(s, k):
-    """B (F, k): column 0 the system's b; from k >= 2 column 1 its bit-identical duplicate; from k >= 3 column 2 zero; the others
-    deterministic and distinct"""
-    i = np.arange(s.ncol, dtype=np.float64)
-    B = np.empty((s.ncol, k))
-    for j in range(k):
-        B[:, j] = s.b * (1.0 + 0.25 * j) + np.sin(i * (0.11 * j) + 0.3 * j) * (0.5 + 0.125 * j)
-    B[:, 0] = s.b
-    if k >= 2:
-        B[:, 1] = s.b
-    if k >= 3:
-        B[:, 2] = 0.0
-    return B
-
-
-def x0_columns(s, B):
-    """a warm start per column, in the scale of that column (a zero column starts from +0.0)"""
-    i = np.arange(s.ncol, dtype=np.float64)
-    X0 = np.zeros(B.shape)
-    for j in range(B.shape[1]):
-        nb = np.linalg.norm(B[:, j])
-        if nb:
-            X0[:, j] = 0.5 * np.sin(i * 0.37 + 0.2 + (0.0 if j < 2 else j)) * nb / max(1.0, np.sqrt(s.ncol))
-    return X0
-
-
-def pcgn_run(L, A, At, s, B, precond=P.PRECOND_NONE, X0=None, max_iter=0, diag=None, tol=None):
-    """fs_pcgn through capi.pcgn: X (F, k), the infos, st[] by name, the per-column scalars by name"""
-    from libfastsparse_amd import capi
-    k = B.shape[1]
-    Bd = G._d(B)
-    X = G._nan(s.ncol * k).view(s.ncol, k) if X0 is None else G._d(X0)
-    dd = None if diag is None else G._d(diag)
-    infos = capi.pcgn(A, At, X, Bd, s.lam, s.tol if tol is None else tol, max_iter=max_iter, precond=precond, warm_start=X0 is not None,
-                      diag=dd, stream=capi.current_stream())
-    raw = np.full(N.MAX_RHS * N.PN_STRIDE, np.nan)
-    assert L.fs_debug_last_pcgn_state(raw.ctypes.data, raw.size) == k * N.PN_STRIDE
-    return X.cpu().numpy(), infos, P.state_from_device(G._raw_state(L)), N.state_from_device(raw, k)
-
-
-def _assert_column(what, x, info, cs, want_x, want_info, want_state=None):
-    ok = M.same_bits(x, want_x)
-    assert ok.all(), (what, int((~ok).sum()), int(np.flatnonzero(~ok)[0]), x[~ok][:3], np.asarray(want_x)[~ok][:3])
-    assert info.iterations == want_info.iterations and info.converged == want_info.converged, (what, info.iterations, info.converged, want_info)
-    assert M.same_bits(info.rnorm, want_info.rnorm)[0] and M.same_bits(info.bnorm, want_info.bnorm)[0], (what, info.rnorm, info.bnorm, want_info)
-    assert cs["count"] == want_info.iterations and cs["converged"] == want_info.converged, (what, cs)
-    for key, name in (("rr", "rr"), ("bb", "bb"), ("stop", "stop"), ("rsq", "rz"), ("alpha", "alpha"), ("beta", "beta")):
-        if want_state is not None and key in want_state:
-            assert M.same_bits(cs[name], want_state[key])[0], (what, key, cs[name], want_state[key])
+    assert {c for _, _, c in STRICT_SET} == set(range(len(SV.CASES)))
 
 
 # ---- 1 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kernel", KERNELS, ids=[f"pcgn_kernel{v}" for v in KERNELS])
-@pytest.mark.parametrize("name,k,case", STRICT_SET, ids=[f"{n}-k{k}-{CASES[c][0]}" for n, k, c in STRICT_SET])
+@pytest.mark.parametrize("kernel", SV.KERNELS, ids=[f"pcgn_kernel{v}" for v in SV.KERNELS])
+@pytest.mark.parametrize("name,k,case", STRICT_SET, ids=[f"{n}-k{k}-{SV.CASES[c][0]}" for n, k, c in STRICT_SET])
 def test_fs_pcgn_strict_is_the_model(L, name, k, case, kernel):
-    s = ALL[name]
-    what, precond, warm, max_iter = CASES[case]
-    diag = G._caller_diag(s) if precond == P.PRECOND_DIAG else None
-    B = columns(s, k)
-    X0 = x0_columns(s, B) if warm else None
+    s = SV.ALL[name]
+    what, precond, warm, max_iter = SV.CASES[case]
+    diag = SV.caller_diag(s) if precond == P.PRECOND_DIAG else None
+    B = SV.columns(s, k)
+    X0 = SV.x0_columns(s, B) if warm else None
     model = N.run(s, B, precond, max_iter=max_iter, X0=X0, diag=diag, cache=_MODEL_CACHE)
     with G.options(strict_order=1, pcgn_kernel=kernel):
-        A, At = G.handles(L, s)
-        X, infos, st, cs = pcgn_run(L, A, At, s, B, precond, X0, max_iter, diag)
+        A, At = SV.handles(L, s)
+        X, infos, st, cs = SV.pcgn_run(L, A, At, s, B, precond, X0, max_iter, diag)
     assert len(infos) == k
     for j in range(k):
-        _assert_column((name, k, what, j), X[:, j], infos[j], cs[j], model.X[:, j], model.infos[j], model.columns[j].state)
+        SV.assert_column((name, k, what, j), X[:, j], infos[j], cs[j], model.X[:, j], model.infos[j], model.columns[j].state)
         if max_iter:
             assert infos[j].iterations <= max_iter
     if k >= 2:
@@ -152,59 +87,59 @@ def test_fs_pcgn_strict_is_the_model(L, name, k, case, kernel):
 def _pcg_column(L, A, At, s, b, precond, x0=None, max_iter=0, tol=None):
     """fs_pcg on one column: x, its info, and the scalars of st[] that such a solve is sure to have written (a solve that is done at
     the start writes neither r.z nor alpha, one without a second iteration no beta: those slots hold what the allocation held)"""
-    x, info, st = G.pcg_run(L, A, At, s, precond, x0, max_iter, tol=tol, b=b)
+    x, info, st = SV.pcg_run(L, A, At, s, precond, x0, max_iter, tol=tol, b=b)
     if info.iterations == 0:
         st = {k: v for k, v in st.items() if k not in ("rsq", "alpha", "beta")}
     return x, N.Info(info.iterations, info.converged, info.rnorm, info.bnorm), st
 
 
 def test_columns_are_fs_pcg_on_more_than_one_grid_stride(L):
-    s = ALL["binary_F262145"]
+    s = SV.ALL["binary_F262145"]
     assert s.ncol > M.RED_BLOCKS * M.RED_THREADS
     i = np.arange(s.ncol, dtype=np.float64)
     B = np.stack([s.b, np.cos(i * 0.013) + 0.5 * s.b, np.sin(i * 0.7) * 3.0], 1)
     with G.options(strict_order=1):
-        A, At = G.handles(L, s)
+        A, At = SV.handles(L, s)
         alone = [_pcg_column(L, A, At, s, B[:, j], P.PRECOND_JACOBI) for j in range(3)]
-        for kernel in KERNELS:
+        for kernel in SV.KERNELS:
             with G.options(pcgn_kernel=kernel):
-                X, infos, _, cs = pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI)
+                X, infos, _, cs = SV.pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI)
             for j, (x, info, st) in enumerate(alone):
                 assert info.converged == 1 and info.iterations > 0
-                _assert_column((s.name, kernel, j), X[:, j], infos[j], cs[j], x, info, st)
+                SV.assert_column((s.name, kernel, j), X[:, j], infos[j], cs[j], x, info, st)
 
 
 def test_warm_columns_freeze_at_different_iterations(L):
     """X0 columns from fs_pcg: not run at all, capped at 3, run to a hundredth of tol -- the last is done before the first product"""
-    s = ALL["valued"]
+    s = SV.ALL["valued"]
     i = np.arange(s.ncol, dtype=np.float64)
     B = np.stack([s.b, s.b * 0.5 + np.cos(i * 0.05), np.sin(i * 0.3) + 0.25 * s.b], 1)
     with G.options(strict_order=1):
-        A, At = G.handles(L, s)
+        A, At = SV.handles(L, s)
         X0 = np.zeros(B.shape)
         X0[:, 1] = _pcg_column(L, A, At, s, B[:, 1], P.PRECOND_JACOBI, max_iter=3)[0]
         X0[:, 2] = _pcg_column(L, A, At, s, B[:, 2], P.PRECOND_JACOBI, tol=s.tol * 1e-2)[0]
         alone = [_pcg_column(L, A, At, s, B[:, j], P.PRECOND_JACOBI, x0=X0[:, j]) for j in range(3)]
-        for kernel in KERNELS:
+        for kernel in SV.KERNELS:
             with G.options(pcgn_kernel=kernel):
-                X, infos, _, cs = pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI, X0=X0)
+                X, infos, _, cs = SV.pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI, X0=X0)
             for j, (x, info, st) in enumerate(alone):
-                _assert_column((s.name, kernel, j), X[:, j], infos[j], cs[j], x, info, st)
+                SV.assert_column((s.name, kernel, j), X[:, j], infos[j], cs[j], x, info, st)
     assert infos[2].iterations == 0 and infos[2].converged == 1 and M.same_bits(X[:, 2], X0[:, 2]).all()
     assert infos[0].iterations > infos[1].iterations > 0, [i.iterations for i in infos]
 
 
 # ---- 3 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mode", G.MODES)
+@pytest.mark.parametrize("mode", G.SOLVER_MODES)
 def test_one_column_is_fs_pcg(L, mode):
-    assert len(G.PLAIN_SET) >= 20
-    for name in G.PLAIN_SET:
-        s = ALL[name]
+    assert len(SV.PLAIN_SET) >= 20
+    for name in SV.PLAIN_SET:
+        s = SV.ALL[name]
         for precond in (P.PRECOND_NONE, P.PRECOND_JACOBI):
-            with G._mode(mode):
-                A, At = G.handles(L, s)
-                xp, ip, stp = G.pcg_run(L, A, At, s, precond)
-                X, infos, st, cs = pcgn_run(L, A, At, s, s.b.reshape(-1, 1), precond)
+            with G.mode_options(mode):
+                A, At = SV.handles(L, s)
+                xp, ip, stp = SV.pcg_run(L, A, At, s, precond)
+                X, infos, st, cs = SV.pcgn_run(L, A, At, s, s.b.reshape(-1, 1), precond)
             want = dict(stp)
             if ip.iterations == 0:
                 want.pop("beta")                                    # (never written: whatever the allocation held)
@@ -230,9 +165,9 @@ def test_default_modes_eight_columns_within_the_bars(L, kind):
     am, atm, _, _ = M.csr_products(s.nrow, s.ncol, s.a_csr(), s.t_csr_coo())
     assert all(i.converged == 1 for i in model.infos)
     for mode in ("default", "cg_fixed_order=0"):
-        with G._mode(mode):
-            A, At = G.handles(L, s)
-            runs = [pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI) for _ in range(2)]
+        with G.mode_options(mode):
+            A, At = SV.handles(L, s)
+            runs = [SV.pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI) for _ in range(2)]
         X, infos, _, _ = runs[0]
         for j in range(8):
             info = infos[j]
@@ -252,18 +187,18 @@ def test_default_modes_eight_columns_within_the_bars(L, kind):
 
 # ---- 5 ---------------------------------------------------------------------------------------------------------------------
 def test_a_nan_column_stays_in_its_column(L):
-    s = ALL["binary_F257"]
-    B = columns(s, 5)
+    s = SV.ALL["binary_F257"]
+    B = SV.columns(s, 5)
     B[7, 3] = np.nan
     with G.options(strict_order=1):
-        A, At = G.handles(L, s)
+        A, At = SV.handles(L, s)
         alone = {j: _pcg_column(L, A, At, s, B[:, j], P.PRECOND_JACOBI, max_iter=5) for j in (0, 1, 2, 4)}
-        for kernel in KERNELS:
+        for kernel in SV.KERNELS:
             with G.options(pcgn_kernel=kernel):
-                X, infos, st, cs = pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI, max_iter=5)
+                X, infos, st, cs = SV.pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI, max_iter=5)
             assert infos[3].converged == 0 and infos[3].iterations == 5 and cs[3]["live"] == 1.0, (kernel, infos[3].iterations, infos[3].converged, cs[3])
             for j, (x, info, stj) in alone.items():
-                _assert_column((s.name, kernel, j), X[:, j], infos[j], cs[j], x, info, stj)
+                SV.assert_column((s.name, kernel, j), X[:, j], infos[j], cs[j], x, info, stj)
                 assert np.isfinite(X[:, j]).all()
             assert st["done"] == 0.0 and st["iter"] == 5.0
 
@@ -271,12 +206,12 @@ def test_a_nan_column_stays_in_its_column(L):
 # ---- 6 ---------------------------------------------------------------------------------------------------------------------
 def test_statuses(L):
     from libfastsparse_amd import capi
-    s = G.RECIPES["scaled_seed0"]
-    A, At = G.handles(L, s)
+    s = SV.RECIPES["scaled_seed0"]
+    A, At = SV.handles(L, s)
     st = capi.current_stream()
     k = 3
-    B = G._d(columns(s, k))
-    X, d = G._nan(s.ncol * N.MAX_RHS), G._d(G._caller_diag(s))
+    B = G.to_device(SV.columns(s, k))
+    X, d = G.nan_vector(s.ncol * N.MAX_RHS), G.to_device(SV.caller_diag(s))
     x_bits = X.cpu().numpy().view(np.int64).copy()
 
     def call(A_=A.h, At_=At.h, x_=X.data_ptr(), b_=B.data_ptr(), k_=k, prm="default", info=None, **kw):
@@ -292,7 +227,7 @@ def test_statuses(L):
            "tol < 0": call(tol=-1e-8), "tol NaN": call(tol=float("nan")), "tol -inf": call(tol=float("-inf"))}
     assert all(rc == FS_ERR_ARG for rc in bad.values()), bad
     assert L.fs_last_error()
-    assert np.array_equal(X.cpu().numpy().view(np.int64), x_bits), "a refused call wrote to X"
+    SV.refused_call_leaves(X, x_bits)
     assert call(tol=0.0, max_iter=2) == FS_OK                        # tol = 0 is legal: the cap ends it; info NULL is legal too
     infos = (capi.PcgInfo * k)()
     assert call(tol=0.0, max_iter=2, info=infos) == FS_OK
@@ -304,30 +239,30 @@ def test_released_handles(L):
     """FS_ERR_RELEASED before anything is written to X: Jacobi after fs_matrix_release_csr on a kept two-pass A'; a k that was never
     prepared before the release.  After fs_matrix_restore_csr the same bits return."""
     from libfastsparse_amd import capi
-    s = G.RECIPES["scaled_seed0"]
+    s = SV.RECIPES["scaled_seed0"]
     st = capi.current_stream()
     trp, tcc, tvv = s.t_csr_coo()
     k = 3
-    B = columns(s, k)
-    A, _ = G.handles(L, s)
+    B = SV.columns(s, k)
+    A, _ = SV.handles(L, s)
     with G.options(binning=2, bin_flags=64):                         # a kept two-pass copy: there is something to release for
-        At = capi.Matrix.from_csr(s.ncol, s.nrow, G._d(trp), G._d(tcc), G._d(tvv))
+        At = capi.Matrix.from_csr(s.ncol, s.nrow, G.to_device(trp), G.to_device(tcc), G.to_device(tvv))
     assert At.kernel_name() == "two-pass"
-    X_before, infos_before, _, _ = pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI)          # prepares k = 3
+    X_before, infos_before, _, _ = SV.pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI)          # prepares k = 3
     assert all(i.converged == 1 for i in infos_before)
     assert At.release_csr() == 1
-    X = G._nan(s.ncol * 4)
+    X = G.nan_vector(s.ncol * 4)
     bits = X.cpu().numpy().view(np.int64).copy()
-    Bd, B4 = G._d(B), G._d(columns(s, 4))
+    Bd, B4 = G.to_device(B), G.to_device(SV.columns(s, 4))
     jac, none = capi.PcgParams(s.tol, 0, P.PRECOND_JACOBI, 0, None), capi.PcgParams(s.tol, 3, P.PRECOND_NONE, 0, None)
     assert L.fs_pcgn(A.h, At.h, X.data_ptr(), Bd.data_ptr(), k, s.lam, C.byref(jac), None, st) == FS_ERR_RELEASED
     assert b"fs_matrix_release_csr" in L.fs_last_error()
-    assert np.array_equal(X.cpu().numpy().view(np.int64), bits), "the refused Jacobi solve wrote to X"
+    SV.refused_call_leaves(X, bits, "the refused Jacobi solve wrote to X")
     # k = 4 was never prepared on this A': fs_matrix_prepare needs the plain arrays
     assert L.fs_pcgn(A.h, At.h, X.data_ptr(), B4.data_ptr(), 4, s.lam, C.byref(none), None, st) == FS_ERR_RELEASED
-    assert np.array_equal(X.cpu().numpy().view(np.int64), bits), "the refused k = 4 solve wrote to X"
-    At.restore_csr(G._d(trp), G._d(tcc), G._d(tvv))
-    X_after, infos_after, _, _ = pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI)
+    SV.refused_call_leaves(X, bits, "the refused k = 4 solve wrote to X")
+    At.restore_csr(G.to_device(trp), G.to_device(tcc), G.to_device(tvv))
+    X_after, infos_after, _, _ = SV.pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI)
     assert [i.iterations for i in infos_after] == [i.iterations for i in infos_before] and M.same_bits(X_after, X_before).all()
 
 
@@ -340,15 +275,15 @@ def test_guard_zones(L):
     mem = LC.TorchMem()
     st = capi.current_stream()
     for name in ("scaled_seed0", "binary_F257"):
-        s = ALL[name]
-        A, At = G.handles(L, s)
-        diag = G._caller_diag(s)
+        s = SV.ALL[name]
+        A, At = SV.handles(L, s)
+        diag = SV.caller_diag(s)
         n = s.ncol * 4
         gx, gb, gd = LC.Guarded(mem, "X of fs_pcgn", n), LC.Guarded(mem, "B of fs_pcgn", n), LC.Guarded(mem, "diag of fs_pcgn", s.ncol)
-        for kernel, k in [(v, k) for v in KERNELS for k in (3, 4)]:
-            B = columns(s, k)
-            X0 = x0_columns(s, B)
-            for what, precond, warm, max_iter in CASES:
+        for kernel, k in [(v, k) for v in SV.KERNELS for k in (3, 4)]:
+            B = SV.columns(s, k)
+            X0 = SV.x0_columns(s, B)
+            for what, precond, warm, max_iter in SV.CASES:
                 aligned = None
                 for off in (0, 1):
                     mem.put(gb.place(s.ncol * k, off), B.reshape(-1))
@@ -380,16 +315,16 @@ def test_guard_zones(L):
 # ---- 8 ---------------------------------------------------------------------------------------------------------------------
 def test_the_solve_prepares_the_k_column_products(L):
     from libfastsparse_amd import capi
-    s = G.RECIPES["powerlaw_seed0"]
+    s = SV.RECIPES["powerlaw_seed0"]
     arp, acc, avv = s.a_csr()
     trp, tcc, tvv = s.t_csr_coo()
     # a matrix this small keeps and extends the two-pass copy only under binning = 2; the solver's own options are the defaults
     with G.options(binning=2, bin_flags=64):
-        A = capi.Matrix.from_csr(s.nrow, s.ncol, G._d(arp), G._d(acc), None if avv is None else G._d(avv))
-        At = capi.Matrix.from_csr(s.ncol, s.nrow, G._d(trp), G._d(tcc), None if tvv is None else G._d(tvv))
+        A = capi.Matrix.from_csr(s.nrow, s.ncol, G.to_device(arp), G.to_device(acc), None if avv is None else G.to_device(avv))
+        At = capi.Matrix.from_csr(s.ncol, s.nrow, G.to_device(trp), G.to_device(tcc), None if tvv is None else G.to_device(tvv))
         assert A.kernel_name() == "two-pass" and At.kernel_name() == "two-pass"
         assert A.spmm_plan(4) != "k-column two-pass" and At.spmm_plan(4) != "k-column two-pass"
-        B = columns(s, 4)
-        _, infos, _, _ = pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI)
+        B = SV.columns(s, 4)
+        _, infos, _, _ = SV.pcgn_run(L, A, At, s, B, P.PRECOND_JACOBI)
         assert all(i.converged == 1 for i in infos)
         assert A.spmm_plan(4) == "k-column two-pass" and At.spmm_plan(4) == "k-column two-pass"

@@ -1,6 +1,6 @@
 """Option "pcgn_compact": fs_pcgn and fs_pcgn_lambdas move their live columns into narrower panels (include/fastsparse_hip.h, fs_pcgn,
-"Narrowing"; the schedule is libfastsparse_amd/csrc/fs_pcgn_plan.h, modelled in tests/_pcgn_plan_model.py).  In the idioms of
-test_gpu_pcgn_lambdas.py.
+"Narrowing"; the schedule is libfastsparse_amd/csrc/fs_pcgn_plan.h, modelled in tests/_pcgn_plan_model.py).  On the harness of
+tests/_solvers.py.
 
 1  strict_order, option 1 against option 0 in the same test: X, every fs_pcg_info, st[] and cs[] bit for bit, and
    capi.pcgn_segments() equal to the plan model fed with the solve's own counts; both forms of the kernels where k > 4.  The
@@ -18,34 +18,25 @@ import numpy as np
 import pytest
 
 import _cg_model as M
+import _gpu as G
 import _lifecycle as LC
 import _pcg_model as P
 import _pcgn_lambdas_model as NL
 import _pcgn_model as N
 import _pcgn_plan_model as PM
-import test_gpu_cg as GC
-import test_gpu_pcg as G
-import test_gpu_pcgn as T
-import test_gpu_pcgn_lambdas as TL
+import _solvers as SV
+from _gpu import FS_ERR_ARG, FS_ERR_RELEASED, FS_OK
 
 pytestmark = pytest.mark.gpu
 
-FS_OK, FS_ERR_ARG, FS_ERR_RELEASED = 0, -2, -5
-ALL = G.ALL
-CASES = G.CASES
 NONE, JACOBI, DIAG = P.PRECOND_NONE, P.PRECOND_JACOBI, P.PRECOND_DIAG
-CASE = {name: i for i, (name, _, _, _) in enumerate(CASES)}
+CASE = {name: i for i, (name, _, _, _) in enumerate(SV.CASES)}
 
 
 @pytest.fixture(scope="module")
 def L():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    from libfastsparse_amd import capi
-    lib = capi.lib()
+    lib = G.gpu_lib()
     assert lib.fs_get_option(b"pcgn_compact") == 0, "the default of option pcgn_compact is 0"
-    lib.fs_debug_last_cg_state.argtypes = [C.c_void_p]
-    lib.fs_debug_last_pcgn_state.argtypes = [C.c_void_p, C.c_int]
     return lib
 
 
@@ -58,16 +49,16 @@ def solve(L, A, At, s, B, lams, compact, precond=NONE, X0=None, max_iter=0, diag
     from libfastsparse_amd import capi
     with G.options(pcgn_compact=compact):
         if lams is None:
-            got = T.pcgn_run(L, A, At, s, B, precond, X0, max_iter, diag)
+            got = SV.pcgn_run(L, A, At, s, B, precond, X0, max_iter, diag)
         else:
-            got = TL.lambdas_run(L, A, At, s, B, lams, precond, X0, max_iter, diag)
-    return got, G._raw_state(L)[N.ST_PCGN["live_mask"]], capi.pcgn_segments()
+            got = SV.lambdas_run(L, A, At, s, B, lams, precond, X0, max_iter, diag)
+    return got, SV.raw_state(L)[N.ST_PCGN["live_mask"]], capi.pcgn_segments()
 
 
 def assert_same_solve(what, one, zero):
     """option 1 against option 0: X, the infos, st[] and cs[] bit for bit"""
     (got, mask, _), (want, mask_w, segs_w) = one, zero
-    TL._same_solve(what, got, want)
+    SV.same_solve(what, got, want)
     for name in got[2]:
         assert M.same_bits(got[2][name], want[2][name])[0], (what, "st", name, got[2][name], want[2][name])
     assert mask == mask_w, (what, "live mask", mask, mask_w)
@@ -86,15 +77,15 @@ def assert_plan(what, one, k, cap, usable=None):
 # ---- 1 ---------------------------------------------------------------------------------------------------------------------
 def _both(L, s, B, lams, kernel, precond=NONE, X0=None, max_iter=0, diag=None):
     with G.options(strict_order=1, pcgn_kernel=kernel):
-        A, At = G.handles(L, s)
+        A, At = SV.handles(L, s)
         zero = solve(L, A, At, s, B, lams, 0, precond, X0, max_iter, diag)
         one = solve(L, A, At, s, B, lams, 1, precond, X0, max_iter, diag)
     return one, zero
 
 
-@pytest.mark.parametrize("kernel", T.KERNELS, ids=[f"pcgn_kernel{v}" for v in T.KERNELS])
+@pytest.mark.parametrize("kernel", SV.KERNELS, ids=[f"pcgn_kernel{v}" for v in SV.KERNELS])
 def test_strict_the_powerlaw_ladder(L, kernel):
-    s, lams, B, model = TL._ladder("powerlaw_seed0")
+    s, lams, B, model = SV.ladder("powerlaw_seed0")
     one, zero = _both(L, s, B, lams, kernel, JACOBI)
     assert_same_solve((s.name, kernel), one, zero)
     segs = assert_plan((s.name, kernel), one, 8, s.ncol)
@@ -104,7 +95,7 @@ def test_strict_the_powerlaw_ladder(L, kernel):
 
 
 def test_strict_two_rungs_reach_width_one(L):
-    s, lams, B, model = TL._ladder("powerlaw_seed0")
+    s, lams, B, model = SV.ladder("powerlaw_seed0")
     one, zero = _both(L, s, np.ascontiguousarray(B[:, :2]), [lams[0], lams[7]], 0, JACOBI)
     assert_same_solve((s.name, "two rungs"), one, zero)
     segs = assert_plan((s.name, "two rungs"), one, 2, s.ncol)
@@ -114,23 +105,23 @@ def test_strict_two_rungs_reach_width_one(L):
 
 STRICT = [("fixture_100x50", 32, "diag"), ("binary_F257", 17, "jacobi"), ("binary_F65", 5, "jacobi-cap5"), ("valued", 8, "jacobi-warm"),
           ("valued", 8, "diag-warm-cap3")]
-STRICT_RUNS = [(n, k, c, v) for n, k, c in STRICT for v in T.KERNELS]
+STRICT_RUNS = [(n, k, c, v) for n, k, c in STRICT for v in SV.KERNELS]
 
 
 @pytest.mark.parametrize("name,k,case,kernel", STRICT_RUNS, ids=[f"{n}-k{k}-{c}-pcgn_kernel{v}" for n, k, c, v in STRICT_RUNS])
 def test_strict_option_1_is_option_0(L, name, k, case, kernel):
-    s = ALL[name]
-    what, precond, warm, max_iter = CASES[CASE[case]]
-    diag = G._caller_diag(s) if precond == DIAG else None
+    s = SV.ALL[name]
+    what, precond, warm, max_iter = SV.CASES[CASE[case]]
+    diag = SV.caller_diag(s) if precond == DIAG else None
     lams = NL.rungs(s, k)
-    B = T.columns(s, k)
+    B = SV.columns(s, k)
     X0 = None
     done0 = (3, 4, 5, 6) if warm else ()                          # columns that start from a solution: converged at the start
     if warm:
-        X0 = T.x0_columns(s, B)
+        X0 = SV.x0_columns(s, B)
         with G.options(strict_order=1):
-            A, At = G.handles(L, s)
-            tight = TL.lambdas_run(L, A, At, s, B, lams, precond, None, 0, diag, tol=s.tol * 1e-3)
+            A, At = SV.handles(L, s)
+            tight = SV.lambdas_run(L, A, At, s, B, lams, precond, None, 0, diag, tol=s.tol * 1e-3)
         assert all(tight[1][j].converged == 1 for j in done0)
         X0[:, done0] = tight[0][:, done0]
     one, zero = _both(L, s, B, lams, kernel, precond, X0, max_iter, diag)
@@ -149,16 +140,16 @@ def test_strict_option_1_is_option_0(L, name, k, case, kernel):
 
 def test_strict_fs_pcgn_with_one_lambda(L):
     """fs_pcgn keeps its scalar-lambda kernels in every segment; columns scaled by powers of ten, so that their sums differ"""
-    s = ALL["valued"]
-    B = T.columns(s, 8) * (10.0 ** np.arange(-4, 4))[None, :]
-    for kernel in T.KERNELS:
+    s = SV.ALL["valued"]
+    B = SV.columns(s, 8) * (10.0 ** np.arange(-4, 4))[None, :]
+    for kernel in SV.KERNELS:
         one, zero = _both(L, s, B, None, kernel, JACOBI)
         assert_same_solve((s.name, "fs_pcgn", kernel), one, zero)
         assert_plan((s.name, "fs_pcgn", kernel), one, 8, s.ncol)
 
 
 def test_strict_a_repack_before_the_first_iteration_on_more_than_one_grid_stride(L):
-    s = ALL["binary_F262145"]
+    s = SV.ALL["binary_F262145"]
     assert s.ncol > M.RED_BLOCKS * M.RED_THREADS
     B = np.stack([s.b, np.zeros(s.ncol)], 1)
     one, zero = _both(L, s, B, [s.lam, s.lam * 30.0], 0, JACOBI, max_iter=3)
@@ -173,11 +164,11 @@ def test_strict_a_repack_before_the_first_iteration_on_more_than_one_grid_stride
 @pytest.mark.parametrize("mode", ("default", "reproducible"))
 @pytest.mark.parametrize("name", ("scaled_seed0", "powerlaw_seed0"))
 def test_the_ladders_with_option_1_within_the_bars(L, name, mode):
-    s, lams, B, model = TL._ladder(name)
+    s, lams, B, model = SV.ladder(name)
     am, atm, _, _ = M.csr_products(s.nrow, s.ncol, s.a_csr(), s.t_csr_coo())
     assert all(i.converged == 1 for i in model.infos)
-    with G._mode(mode):
-        A, At = G.handles(L, s)
+    with G.mode_options(mode):
+        A, At = SV.handles(L, s)
         runs = [solve(L, A, At, s, B, lams, 1, JACOBI) for _ in range(2)]
     (X, infos, _, _), _, segs = runs[0]
     nb = np.linalg.norm(s.b)
@@ -199,14 +190,14 @@ def test_the_ladders_with_option_1_within_the_bars(L, name, mode):
 
 
 # ---- 3 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mode", GC.MODES)
+@pytest.mark.parametrize("mode", G.SOLVER_MODES)
 def test_nothing_finishes_early_one_segment_and_the_bits_of_option_0(L, mode):
-    s = ALL["valued"]
+    s = SV.ALL["valued"]
     for k in (4, 8):
         B = np.ascontiguousarray(np.repeat(s.b[:, None], k, 1))
         for lams in ([s.lam * 3.0] * k, None):
-            with G._mode(mode):
-                A, At = G.handles(L, s)
+            with G.mode_options(mode):
+                A, At = SV.handles(L, s)
                 zero, again = [solve(L, A, At, s, B, lams, 0, JACOBI) for _ in range(2)]
                 one = solve(L, A, At, s, B, lams, 1, JACOBI)
             if mode != "cg_fixed_order=0" or M.same_bits(again[0][0], zero[0][0]).all():   # where option 0 repeats its own bits
@@ -218,12 +209,12 @@ def test_nothing_finishes_early_one_segment_and_the_bits_of_option_0(L, mode):
 # ---- 4 ---------------------------------------------------------------------------------------------------------------------
 def test_statuses(L):
     from libfastsparse_amd import capi
-    s = G.RECIPES["scaled_seed0"]
-    A, At = G.handles(L, s)
+    s = SV.RECIPES["scaled_seed0"]
+    A, At = SV.handles(L, s)
     st = capi.current_stream()
     k = 3
-    B = G._d(T.columns(s, k))
-    X, d = G._nan(s.ncol * N.MAX_RHS), G._d(G._caller_diag(s))
+    B = G.to_device(SV.columns(s, k))
+    X, d = G.nan_vector(s.ncol * N.MAX_RHS), G.to_device(SV.caller_diag(s))
     x_bits = X.cpu().numpy().view(np.int64).copy()
     good = NL.rungs(s, k)
 
@@ -247,7 +238,7 @@ def test_statuses(L):
                "fs_pcgn At of A's shape": call(At_=A.h, lams="fs_pcgn"), "fs_pcgn precond 3": call(precond=3, lams="fs_pcgn"),
                "fs_pcgn tol < 0": call(tol=-1e-8, lams="fs_pcgn")}
         assert all(rc == FS_ERR_ARG for rc in bad.values()), bad
-        assert np.array_equal(X.cpu().numpy().view(np.int64), x_bits), "a refused call wrote to X"
+        SV.refused_call_leaves(X, x_bits)
         infos = (capi.PcgInfo * k)()
         assert call(tol=0.0, max_iter=2, info=infos) == FS_OK          # tol = 0 is legal: the cap ends it
         assert [i.iterations for i in infos] == [2, 2, 0] and [i.converged for i in infos] == [0, 0, 1]
@@ -263,7 +254,7 @@ def test_a_released_handle_solves_on_the_rungs_it_has(L):
     solve does -- fs_matrix_prepare on both sides, and the plan fs_spmm would run -- and feeds the answer to the plan model.
     k = 4 where the released handle still multiplies four columns, else k = 3."""
     from libfastsparse_amd import capi
-    s = G.RECIPES["scaled_seed0"]
+    s = SV.RECIPES["scaled_seed0"]
     st = capi.current_stream()
     trp, tcc, tvv = s.t_csr_coo()
     r = NL.rungs(s, 8)
@@ -271,8 +262,8 @@ def test_a_released_handle_solves_on_the_rungs_it_has(L):
     row_kernels = (1, 4)                                             # plans of fs_matrix_spmm_plan that read the plain CSR
 
     def pair():
-        A, _ = G.handles(L, s)
-        At = capi.Matrix.from_csr(s.ncol, s.nrow, G._d(trp), G._d(tcc), G._d(tvv))
+        A, _ = SV.handles(L, s)
+        At = capi.Matrix.from_csr(s.ncol, s.nrow, G.to_device(trp), G.to_device(tcc), G.to_device(tvv))
         assert At.kernel_name() == "two-pass"
         return A, At
 
@@ -302,13 +293,13 @@ def test_a_released_handle_solves_on_the_rungs_it_has(L):
         segs_full = assert_plan("full ladder", full, k, s.ncol)
         assert len(segs_full) >= 2, segs_full
         # Jacobi needs the plain CSR of A' itself: refused before anything is written, with option 1 as without
-        X = G._nan(s.ncol * k)
+        X = G.nan_vector(s.ncol * k)
         bits = X.cpu().numpy().view(np.int64).copy()
         jac = capi.PcgParams(s.tol, 0, JACOBI, 0, None)
         with G.options(pcgn_compact=1):
-            assert L.fs_pcgn_lambdas(A.h, At.h, X.data_ptr(), G._d(B).data_ptr(), k, (C.c_double * k)(*lams), C.byref(jac), None,
+            assert L.fs_pcgn_lambdas(A.h, At.h, X.data_ptr(), G.to_device(B).data_ptr(), k, (C.c_double * k)(*lams), C.byref(jac), None,
                                      st) == FS_ERR_RELEASED
-        assert np.array_equal(X.cpu().numpy().view(np.int64), bits), "the refused Jacobi solve wrote to X"
+        SV.refused_call_leaves(X, bits, "the refused Jacobi solve wrote to X")
 
 
 def test_guard_zones(L):
@@ -318,22 +309,22 @@ def test_guard_zones(L):
     from libfastsparse_amd import capi
     mem = LC.TorchMem()
     st = capi.current_stream()
-    s = ALL["binary_F257"]
-    A, At = G.handles(L, s)
-    diag = G._caller_diag(s)
+    s = SV.ALL["binary_F257"]
+    A, At = SV.handles(L, s)
+    diag = SV.caller_diag(s)
     n = s.ncol * 5
     gx, gb, gd = (LC.Guarded(mem, "X of fs_pcgn_lambdas", n), LC.Guarded(mem, "B of fs_pcgn_lambdas", n),
                   LC.Guarded(mem, "diag of fs_pcgn_lambdas", s.ncol))
     narrowed = 0
-    for kernel, k in [(v, k) for v in T.KERNELS for k in (3, 5)]:
-        B = T.columns(s, k)
-        X0 = T.x0_columns(s, B)
+    for kernel, k in [(v, k) for v in SV.KERNELS for k in (3, 5)]:
+        B = SV.columns(s, k)
+        X0 = SV.x0_columns(s, B)
         lams = NL.rungs(s, k)
         host = np.full(k + 16, np.nan)
         host.view(np.int64)[:] = LC.guard_bits(0x1A3B)
         host[8:8 + k] = lams
         host_bits = host.view(np.int64).copy()
-        for what, precond, warm, max_iter in CASES:
+        for what, precond, warm, max_iter in SV.CASES:
             aligned = None
             for off in (0, 1):
                 mem.put(gb.place(s.ncol * k, off), B.reshape(-1))
@@ -368,13 +359,13 @@ def test_guard_zones(L):
 def test_no_device_memory_is_kept(L):
     import torch
     from libfastsparse_amd import capi
-    s = G.RECIPES["powerlaw_seed0"]
-    A, At = G.handles(L, s)
+    s = SV.RECIPES["powerlaw_seed0"]
+    A, At = SV.handles(L, s)
     st = capi.current_stream()
     k = 8
     lams = NL.rungs(s, k)
-    B = G._d(np.repeat(s.b[:, None], k, 1))
-    X, d = torch.empty_like(B), G._d(G._caller_diag(s))
+    B = G.to_device(np.repeat(s.b[:, None], k, 1))
+    X, d = torch.empty_like(B), G.to_device(SV.caller_diag(s))
 
     def solves():
         for precond in (JACOBI, NONE, DIAG):

@@ -1,9 +1,9 @@
 """fs_pcgn_lambdas against the CPU model of its columns (tests/_pcgn_lambdas_model.py: column j is the model of fs_pcg at lambda_j on
-B[:, j]), against fs_pcg on the device at that column's lambda, and against fs_pcgn, in the idioms of test_gpu_pcgn.py.
+B[:, j]), against fs_pcg on the device at that column's lambda, and against fs_pcgn, on the harness of tests/_solvers.py.
 
 1  strict_order: X, every fs_pcg_info and the per-column state have the model's bits AND those of fs_pcg on the device at lambda_j
    (FS_PRECOND_DIAG fed gram_diag(lambda_j) where the case is Jacobi) -- k in {1, 2, 3, 4, 5, 8, 16, 17, 32}, both forms of the
-   kernels for k > 4, the cases of test_gpu_pcg.py, six systems (F = 257 with KMAX = 16 / 32: staged tiles of 128 / 64 rows and a
+   kernels for k > 4, the cases of _solvers.CASES, six systems (F = 257 with KMAX = 16 / 32: staged tiles of 128 / 64 rows and a
    ragged last tile; F = 65: less than a tile; lambda0_empty_column: one rung exactly 0.0).
 2  all lambdas equal: X, the infos and cs[] are fs_pcgn's bit for bit, in every mode in which fs_pcgn repeats its own bits.
 3  every mode: k = 1 IS fs_pcg at lambda[0], bit for bit.
@@ -20,19 +20,16 @@ import numpy as np
 import pytest
 
 import _cg_model as M
+import _gpu as G
 import _lifecycle as LC
 import _pcg_model as P
 import _pcgn_lambdas_model as NL
 import _pcgn_model as N
-import test_gpu_cg as GC
-import test_gpu_pcg as G
-import test_gpu_pcgn as T
+import _solvers as SV
+from _gpu import FS_ERR_ARG, FS_ERR_RELEASED, FS_OK, L  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-FS_OK, FS_ERR_ARG, FS_ERR_RELEASED = 0, -2, -5
-ALL = G.ALL
-CASES = G.CASES
 KS = (1, 2, 3, 4, 5, 8, 16, 17, 32)
 NONE, JACOBI, DIAG = P.PRECOND_NONE, P.PRECOND_JACOBI, P.PRECOND_DIAG
 # (system, k, case of CASES): every k meets no preconditioner, Jacobi and a caller's diagonal; every system meets two values of k or
@@ -51,84 +48,49 @@ _MODEL_CACHE = {}
 
 
 def test_the_strict_set_covers_what_it_should():
-    met = {(k, CASES[c][1]) for _, k, c in STRICT_SET}
+    met = {(k, SV.CASES[c][1]) for _, k, c in STRICT_SET}
     assert met >= {(k, p) for k in KS for p in (NONE, JACOBI, DIAG)}
     for name in SYSTEMS6:
         assert len({k for n, k, _ in STRICT_SET if n == name}) >= 2, name
     assert {n for n, _, _ in STRICT_SET} == set(SYSTEMS6)
-    assert {c for _, _, c in STRICT_SET} == set(range(len(CASES)))
+    assert {c for _, _, c in STRICT_SET} == set(range(len(SV.CASES)))
     assert ("binary_F257", 16) in {(n, k) for n, k, _ in STRICT_SET} and ("binary_F257", 32) in {(n, k) for n, k, _ in STRICT_SET}
-    assert 0.0 in NL.rungs(ALL["lambda0_empty_column"], 2) and len(set(NL.rungs(ALL["lambda0_empty_column"], 32))) == 32
-
-
-@pytest.fixture(scope="module")
-def L():
-    import torch
-    assert torch.cuda.is_available(), "gpu tests need a GPU"
-    from libfastsparse_amd import capi
-    lib = capi.lib()
-    lib.fs_debug_last_cg_state.argtypes = [C.c_void_p]
-    lib.fs_debug_last_pcgn_state.argtypes = [C.c_void_p, C.c_int]
-    return lib
-
-
-def lambdas_run(L, A, At, s, B, lams, precond=NONE, X0=None, max_iter=0, diag=None, tol=None):
-    """fs_pcgn_lambdas through capi.pcgn_lambdas: X (F, k), the infos, st[] by name, the per-column scalars by name"""
-    from libfastsparse_amd import capi
-    k = B.shape[1]
-    Bd = G._d(B)
-    X = G._nan(s.ncol * k).view(s.ncol, k) if X0 is None else G._d(X0)
-    dd = None if diag is None else G._d(diag)
-    infos = capi.pcgn_lambdas(A, At, X, Bd, lams, s.tol if tol is None else tol, max_iter=max_iter, precond=precond,
-                              warm_start=X0 is not None, diag=dd, stream=capi.current_stream())
-    raw = np.full(N.MAX_RHS * N.PN_STRIDE, np.nan)
-    assert L.fs_debug_last_pcgn_state(raw.ctypes.data, raw.size) == k * N.PN_STRIDE
-    return X.cpu().numpy(), infos, P.state_from_device(G._raw_state(L)), N.state_from_device(raw, k)
+    assert 0.0 in NL.rungs(SV.ALL["lambda0_empty_column"], 2) and len(set(NL.rungs(SV.ALL["lambda0_empty_column"], 32))) == 32
 
 
 def pcg_at(L, A, At, s, b, lam, precond=NONE, x0=None, max_iter=0, diag=None, tol=None):
     """fs_pcg on one column at `lam`: x, its info, and the scalars of st[] that such a solve is sure to have written"""
     from libfastsparse_amd import capi
-    x = G._nan(s.ncol) if x0 is None else G._d(x0)
-    dd = None if diag is None else G._d(diag)
-    info = capi.pcg(A, At, x, G._d(b), lam, s.tol if tol is None else tol, max_iter=max_iter, precond=precond, warm_start=x0 is not None,
+    x = G.nan_vector(s.ncol) if x0 is None else G.to_device(x0)
+    dd = None if diag is None else G.to_device(diag)
+    info = capi.pcg(A, At, x, G.to_device(b), lam, s.tol if tol is None else tol, max_iter=max_iter, precond=precond, warm_start=x0 is not None,
                     diag=dd, stream=capi.current_stream())
-    st = P.state_from_device(G._raw_state(L))
+    st = P.state_from_device(SV.raw_state(L))
     if info.iterations == 0:
         st = {k: v for k, v in st.items() if k not in ("rsq", "alpha", "beta")}
     return x.cpu().numpy(), N.Info(info.iterations, info.converged, info.rnorm, info.bnorm), st
 
 
-def _same_solve(what, got, want):
-    (X, infos, _, cs), (Xw, infos_w, _, cs_w) = got, want
-    assert M.same_bits(X, Xw).all(), (what, "X")
-    for j, (a, b) in enumerate(zip(infos, infos_w)):
-        assert (a.iterations, a.converged) == (b.iterations, b.converged), (what, j, a.iterations, b.iterations)
-        assert M.same_bits(a.rnorm, b.rnorm)[0] and M.same_bits(a.bnorm, b.bnorm)[0], (what, j)
-        for name in N.PN:
-            assert M.same_bits(cs[j][name], cs_w[j][name])[0], (what, j, name, cs[j][name], cs_w[j][name])
-
-
 # ---- 1 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name,k,case,kernel", STRICT_RUNS, ids=[f"{n}-k{k}-{CASES[c][0]}-pcgn_kernel{v}" for n, k, c, v in STRICT_RUNS])
+@pytest.mark.parametrize("name,k,case,kernel", STRICT_RUNS, ids=[f"{n}-k{k}-{SV.CASES[c][0]}-pcgn_kernel{v}" for n, k, c, v in STRICT_RUNS])
 def test_strict_columns_are_the_model_and_fs_pcg(L, name, k, case, kernel):
-    s = ALL[name]
-    what, precond, warm, max_iter = CASES[case]
-    diag = G._caller_diag(s) if precond == DIAG else None
+    s = SV.ALL[name]
+    what, precond, warm, max_iter = SV.CASES[case]
+    diag = SV.caller_diag(s) if precond == DIAG else None
     lams = NL.rungs(s, k)
-    B = T.columns(s, k)
-    X0 = T.x0_columns(s, B) if warm else None
+    B = SV.columns(s, k)
+    X0 = SV.x0_columns(s, B) if warm else None
     model = NL.run(s, B, lams, precond, max_iter=max_iter, X0=X0, diag=diag, cache=_MODEL_CACHE)
     t_csr = s.t_csr_coo()
     with G.options(strict_order=1, pcgn_kernel=kernel):
-        A, At = G.handles(L, s)
-        X, infos, st, cs = lambdas_run(L, A, At, s, B, lams, precond, X0, max_iter, diag)
+        A, At = SV.handles(L, s)
+        X, infos, st, cs = SV.lambdas_run(L, A, At, s, B, lams, precond, X0, max_iter, diag)
         alone = [pcg_at(L, A, At, s, B[:, j], lams[j], DIAG if precond == JACOBI else precond, None if X0 is None else X0[:, j], max_iter,
                         P.gram_diag(t_csr, lams[j]) if precond == JACOBI else diag) for j in range(k)]
     assert len(infos) == k
     for j in range(k):
-        T._assert_column((name, k, what, j, "model"), X[:, j], infos[j], cs[j], model.X[:, j], model.infos[j], model.columns[j].state)
-        T._assert_column((name, k, what, j, "fs_pcg"), X[:, j], infos[j], cs[j], *alone[j])
+        SV.assert_column((name, k, what, j, "model"), X[:, j], infos[j], cs[j], model.X[:, j], model.infos[j], model.columns[j].state)
+        SV.assert_column((name, k, what, j, "fs_pcg"), X[:, j], infos[j], cs[j], *alone[j])
         if max_iter:
             assert infos[j].iterations <= max_iter
     if k >= 3:
@@ -139,33 +101,33 @@ def test_strict_columns_are_the_model_and_fs_pcg(L, name, k, case, kernel):
 # ---- 2 ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", ("default", "reproducible", "strict_order"))
 def test_equal_lambdas_are_fs_pcgn(L, mode):
-    s = ALL["valued"]
+    s = SV.ALL["valued"]
     for k in (1, 4, 8, 17):
-        B = T.columns(s, k)
+        B = SV.columns(s, k)
         for precond in (JACOBI, NONE):
-            with G._mode(mode):
-                A, At = G.handles(L, s)
-                first, again = [T.pcgn_run(L, A, At, s, B, precond) for _ in range(2)]
-                _same_solve((mode, k, precond, "fs_pcgn repeats its bits"), again, first)
-                got = lambdas_run(L, A, At, s, B, [s.lam] * k, precond)
-            _same_solve((mode, k, precond), got, first)
+            with G.mode_options(mode):
+                A, At = SV.handles(L, s)
+                first, again = [SV.pcgn_run(L, A, At, s, B, precond) for _ in range(2)]
+                SV.same_solve((mode, k, precond, "fs_pcgn repeats its bits"), again, first)
+                got = SV.lambdas_run(L, A, At, s, B, [s.lam] * k, precond)
+            SV.same_solve((mode, k, precond), got, first)
             assert all(i.converged == 1 for i in got[1])
 
 
 # ---- 3 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mode", GC.MODES)
+@pytest.mark.parametrize("mode", G.SOLVER_MODES)
 def test_one_column_is_fs_pcg_at_its_lambda(L, mode):
     for name in ("fixture_100x50", "binary_F65", "binary_F257", "valued", "lambda0_empty_column", "scaled_seed0", "powerlaw_seed0"):
-        s = ALL[name]
+        s = SV.ALL[name]
         lam = NL.rungs(s, 2)[1]
         assert lam != s.lam
         for precond in (NONE, JACOBI):
             cap = 40 if precond == NONE else 0                          # (plain CG on the column-scaled system: the cap ends it)
-            with G._mode(mode):
-                A, At = G.handles(L, s)
+            with G.mode_options(mode):
+                A, At = SV.handles(L, s)
                 x, info, stp = pcg_at(L, A, At, s, s.b, lam, precond, max_iter=cap)
-                X, infos, st, cs = lambdas_run(L, A, At, s, s.b.reshape(-1, 1), [lam], precond, max_iter=cap)
-            T._assert_column((mode, name, precond), X[:, 0], infos[0], cs[0], x, info, stp)
+                X, infos, st, cs = SV.lambdas_run(L, A, At, s, s.b.reshape(-1, 1), [lam], precond, max_iter=cap)
+            SV.assert_column((mode, name, precond), X[:, 0], infos[0], cs[0], x, info, stp)
             want = {k: v for k, v in stp.items() if k in ("rsq", "alpha", "beta", "stop", "done", "iter", "rr", "bb")}
             if info.iterations == 0:
                 want.pop("beta", None)
@@ -175,41 +137,28 @@ def test_one_column_is_fs_pcg_at_its_lambda(L, mode):
 
 # ---- 4 ---------------------------------------------------------------------------------------------------------------------
 def test_columns_are_fs_pcg_on_more_than_one_grid_stride(L):
-    s = ALL["binary_F262145"]
+    s = SV.ALL["binary_F262145"]
     assert s.ncol > M.RED_BLOCKS * M.RED_THREADS
     i = np.arange(s.ncol, dtype=np.float64)
     B = np.stack([s.b, np.cos(i * 0.013) + 0.5 * s.b], 1)
     lams = [s.lam, s.lam * 30.0]
     with G.options(strict_order=1):
-        A, At = G.handles(L, s)
+        A, At = SV.handles(L, s)
         alone = [pcg_at(L, A, At, s, B[:, j], lams[j], JACOBI, max_iter=3) for j in range(2)]
-        X, infos, _, cs = lambdas_run(L, A, At, s, B, lams, JACOBI, max_iter=3)
+        X, infos, _, cs = SV.lambdas_run(L, A, At, s, B, lams, JACOBI, max_iter=3)
     for j, (x, info, st) in enumerate(alone):
-        T._assert_column((s.name, j), X[:, j], infos[j], cs[j], x, info, st)
+        SV.assert_column((s.name, j), X[:, j], infos[j], cs[j], x, info, st)
         assert infos[j].iterations == 3 and infos[j].converged == 0, (j, infos[j].iterations, infos[j].converged)
 
 
 # ---- 5 ---------------------------------------------------------------------------------------------------------------------
-_LADDERS = {}
-
-
-def _ladder(name):
-    """the recipe's 8 rungs, B = b in every column, and the model's Jacobi solves (computed once, shared by tests 5 and 6)"""
-    if name not in _LADDERS:
-        s = G.RECIPES[name]
-        lams = NL.rungs(s, 8)
-        B = np.ascontiguousarray(np.repeat(s.b[:, None], 8, 1))
-        _LADDERS[name] = (s, lams, B, NL.run(s, B, lams, JACOBI))
-    return _LADDERS[name]
-
-
 @pytest.mark.parametrize("name", ("scaled_seed0", "powerlaw_seed0"))
 def test_the_ladder_in_default_mode_within_the_bars(L, name):
-    s, lams, B, model = _ladder(name)
+    s, lams, B, model = SV.ladder(name)
     am, atm, _, _ = M.csr_products(s.nrow, s.ncol, s.a_csr(), s.t_csr_coo())
     assert all(i.converged == 1 for i in model.infos)
-    A, At = G.handles(L, s)
-    runs = [lambdas_run(L, A, At, s, B, lams, JACOBI) for _ in range(2)]
+    A, At = SV.handles(L, s)
+    runs = [SV.lambdas_run(L, A, At, s, B, lams, JACOBI) for _ in range(2)]
     X, infos, _, _ = runs[0]
     nb = np.linalg.norm(s.b)
     for j, lam in enumerate(lams):
@@ -227,29 +176,29 @@ def test_the_ladder_in_default_mode_within_the_bars(L, name):
 
 
 # ---- 6 ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kernel", T.KERNELS, ids=[f"pcgn_kernel{v}" for v in T.KERNELS])
+@pytest.mark.parametrize("kernel", SV.KERNELS, ids=[f"pcgn_kernel{v}" for v in SV.KERNELS])
 def test_frozen_columns_are_not_written_again(L, kernel):
-    s, lams, B, model = _ladder("powerlaw_seed0")
+    s, lams, B, model = SV.ladder("powerlaw_seed0")
     with G.options(strict_order=1, pcgn_kernel=kernel):
-        A, At = G.handles(L, s)
-        X, infos, st, cs = lambdas_run(L, A, At, s, B, lams, JACOBI)
+        A, At = SV.handles(L, s)
+        X, infos, st, cs = SV.lambdas_run(L, A, At, s, B, lams, JACOBI)
         x, info, stj = pcg_at(L, A, At, s, s.b, lams[7], JACOBI)
     counts = [i.iterations for i in infos]
     assert counts == [i.iterations for i in model.infos] and all(i.converged == 1 for i in infos), counts
     assert len(set(counts)) >= 3, counts
     assert 2 * counts[7] < max(counts) and st["iter"] == max(counts), counts          # final long before the last column
-    T._assert_column((s.name, kernel, "the largest rung"), X[:, 7], infos[7], cs[7], x, info, stj)
+    SV.assert_column((s.name, kernel, "the largest rung"), X[:, 7], infos[7], cs[7], x, info, stj)
 
 
 # ---- 7 ---------------------------------------------------------------------------------------------------------------------
 def test_statuses(L):
     from libfastsparse_amd import capi
-    s = G.RECIPES["scaled_seed0"]
-    A, At = G.handles(L, s)
+    s = SV.RECIPES["scaled_seed0"]
+    A, At = SV.handles(L, s)
     st = capi.current_stream()
     k = 3
-    B = G._d(T.columns(s, k))
-    X, d = G._nan(s.ncol * N.MAX_RHS), G._d(G._caller_diag(s))
+    B = G.to_device(SV.columns(s, k))
+    X, d = G.nan_vector(s.ncol * N.MAX_RHS), G.to_device(SV.caller_diag(s))
     x_bits = X.cpu().numpy().view(np.int64).copy()
     good = NL.rungs(s, k)
 
@@ -269,7 +218,7 @@ def test_statuses(L):
            "tol < 0": call(tol=-1e-8), "tol NaN": call(tol=float("nan")), "tol -inf": call(tol=float("-inf"))}
     assert all(rc == FS_ERR_ARG for rc in bad.values()), bad
     assert call(lams=good[:2] + [float("nan")]) == FS_ERR_ARG and b"fs_pcgn_lambdas: a lambda is NaN or infinite" in L.fs_last_error()
-    assert np.array_equal(X.cpu().numpy().view(np.int64), x_bits), "a refused call wrote to X"
+    SV.refused_call_leaves(X, x_bits)
     assert call(lams=good[:2] + [float("nan")], k_=2, tol=0.0, max_iter=1) == FS_OK     # only the first k lambdas are read
     assert call(tol=0.0, max_iter=2) == FS_OK                        # tol = 0 is legal: the cap ends it; info NULL is legal too
     infos = (capi.PcgInfo * k)()
@@ -282,32 +231,32 @@ def test_released_handles(L):
     """FS_ERR_RELEASED before anything is written to X: Jacobi after fs_matrix_release_csr on a kept two-pass A'.  A diagonal kept
     from before the release still serves FS_PRECOND_DIAG, for the k that was prepared before the release"""
     from libfastsparse_amd import capi
-    s = G.RECIPES["scaled_seed0"]
+    s = SV.RECIPES["scaled_seed0"]
     st = capi.current_stream()
     trp, tcc, tvv = s.t_csr_coo()
     k = 3
-    B = T.columns(s, k)
+    B = SV.columns(s, k)
     lams = NL.rungs(s, k)
-    A, _ = G.handles(L, s)
+    A, _ = SV.handles(L, s)
     with G.options(binning=2, bin_flags=64):                         # a kept two-pass copy: there is something to release for
-        At = capi.Matrix.from_csr(s.ncol, s.nrow, G._d(trp), G._d(tcc), G._d(tvv))
+        At = capi.Matrix.from_csr(s.ncol, s.nrow, G.to_device(trp), G.to_device(tcc), G.to_device(tvv))
     assert At.kernel_name() == "two-pass"
-    kept = G._nan(s.ncol)
+    kept = G.nan_vector(s.ncol)
     capi.gram_diag(At, s.lam, kept, st)
     kept = kept.cpu().numpy()
-    _, infos_before, _, _ = lambdas_run(L, A, At, s, B, lams, JACOBI)                  # prepares k = 3
+    _, infos_before, _, _ = SV.lambdas_run(L, A, At, s, B, lams, JACOBI)                  # prepares k = 3
     assert all(i.converged == 1 for i in infos_before)
-    X_diag_before, infos_diag_before, _, _ = lambdas_run(L, A, At, s, B, lams, DIAG, diag=kept)
+    X_diag_before, infos_diag_before, _, _ = SV.lambdas_run(L, A, At, s, B, lams, DIAG, diag=kept)
     assert At.release_csr() == 1
-    X = G._nan(s.ncol * 4)
+    X = G.nan_vector(s.ncol * 4)
     bits = X.cpu().numpy().view(np.int64).copy()
-    Bd = G._d(B)
+    Bd = G.to_device(B)
     jac = capi.PcgParams(s.tol, 0, JACOBI, 0, None)
     lam_c = (C.c_double * k)(*lams)
     assert L.fs_pcgn_lambdas(A.h, At.h, X.data_ptr(), Bd.data_ptr(), k, lam_c, C.byref(jac), None, st) == FS_ERR_RELEASED
     assert b"fs_matrix_release_csr" in L.fs_last_error()
-    assert np.array_equal(X.cpu().numpy().view(np.int64), bits), "the refused Jacobi solve wrote to X"
-    X_diag, infos_diag, _, _ = lambdas_run(L, A, At, s, B, lams, DIAG, diag=kept)
+    SV.refused_call_leaves(X, bits, "the refused Jacobi solve wrote to X")
+    X_diag, infos_diag, _, _ = SV.lambdas_run(L, A, At, s, B, lams, DIAG, diag=kept)
     assert [i.iterations for i in infos_diag] == [i.iterations for i in infos_diag_before] and M.same_bits(X_diag, X_diag_before).all()
     assert all(i.converged == 1 for i in infos_diag)
 
@@ -322,21 +271,21 @@ def test_guard_zones(L):
     mem = LC.TorchMem()
     st = capi.current_stream()
     for name in ("scaled_seed0", "binary_F257"):
-        s = ALL[name]
-        A, At = G.handles(L, s)
-        diag = G._caller_diag(s)
+        s = SV.ALL[name]
+        A, At = SV.handles(L, s)
+        diag = SV.caller_diag(s)
         n = s.ncol * 5
         gx, gb, gd = (LC.Guarded(mem, "X of fs_pcgn_lambdas", n), LC.Guarded(mem, "B of fs_pcgn_lambdas", n),
                       LC.Guarded(mem, "diag of fs_pcgn_lambdas", s.ncol))
-        for kernel, k in [(v, k) for v in T.KERNELS for k in (3, 4, 5)]:
-            B = T.columns(s, k)
-            X0 = T.x0_columns(s, B)
+        for kernel, k in [(v, k) for v in SV.KERNELS for k in (3, 4, 5)]:
+            B = SV.columns(s, k)
+            X0 = SV.x0_columns(s, B)
             lams = NL.rungs(s, k)
             host = np.full(k + 16, np.nan)
             host.view(np.int64)[:] = LC.guard_bits(0x1A3B)
             host[8:8 + k] = lams
             host_bits = host.view(np.int64).copy()
-            for what, precond, warm, max_iter in CASES:
+            for what, precond, warm, max_iter in SV.CASES:
                 aligned = None
                 for off in (0, 1):
                     mem.put(gb.place(s.ncol * k, off), B.reshape(-1))
@@ -369,13 +318,13 @@ def test_guard_zones(L):
 def test_no_device_memory_is_kept(L):
     import torch
     from libfastsparse_amd import capi
-    s = G.RECIPES["powerlaw_seed0"]
-    A, At = G.handles(L, s)
+    s = SV.RECIPES["powerlaw_seed0"]
+    A, At = SV.handles(L, s)
     st = capi.current_stream()
     k = 8
     lams = NL.rungs(s, k)
-    B = G._d(np.repeat(s.b[:, None], k, 1))
-    X, d = torch.empty_like(B), G._d(G._caller_diag(s))
+    B = G.to_device(np.repeat(s.b[:, None], k, 1))
+    X, d = torch.empty_like(B), G.to_device(SV.caller_diag(s))
 
     def solves():
         for precond in (JACOBI, NONE, DIAG):

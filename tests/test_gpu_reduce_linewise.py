@@ -7,11 +7,12 @@ stream of whole rounds and the same plus one group of 16, several panels and ban
 255 (dummy entries of the one-byte ids), and copies forced to two-byte and to one-byte ids.
 
 Integer-valued data are exactly summable, so both policies must give the same bits, those of the exact sums; on other data a product stays within 1e-12 x row length of the strict_order product (|a|, |x| <= 1)."""
-import contextlib
 import ctypes as C
 
 import numpy as np
 import pytest
+
+from _gpu import options as _options, to_device as _d
 
 pytestmark = pytest.mark.gpu
 
@@ -72,25 +73,6 @@ SHAPES = {"short": _short, "whole rounds": _whole_rounds, "whole rounds + group"
           "panels and bands": _panels_and_bands, "row gaps": _row_gaps}
 # padded stream length of the single-cell shapes (checked against the copy: the shapes are what the names say)
 STREAM = {"short": 4000, "whole rounds": 2 * ROUND, "whole rounds + group": 2 * ROUND + 16}
-
-
-@contextlib.contextmanager
-def _options(**kw):
-    from libfastsparse_amd import capi
-    L = capi.lib()
-    old = {k: L.fs_get_option(k.encode()) for k in kw}
-    try:
-        for k, v in kw.items():
-            capi.set_option(k, v)
-        yield
-    finally:
-        for k, v in old.items():
-            capi.set_option(k, v)
-
-
-def _d(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _layout(A, transposed):

@@ -10,7 +10,6 @@ result, and then checks:
       kernel adds in storage order in every mode, so wherever it runs its bits are the oracle's.
 Then: layout branches of the row kernel, degenerate matrices, the drop-in's k-column entry points and a captured graph."""
 import collections
-import contextlib
 import ctypes as C
 
 import numpy as np
@@ -18,9 +17,8 @@ import pytest
 
 import _cases
 import _exact as E
+from _gpu import PRODUCT_MODES as MODES, mode_options as _mode, options, to_device as _d
 
-MODES = ("default", "reproducible", "strict_order")
-FS_ERR_ARG = -2
 ROW, BINNED_K, BINNED_COLS, MFMA, LDSX_COLUMNS, LDSX_STRIDED, TILED_STRIDED = range(1, 8)   # fs_matrix_spmm_plan codes
 
 # forced copy -> (options around fs_csr_create AND fs_matrix_build_transpose, fs_matrix_spmv_kernel name)
@@ -93,31 +91,6 @@ def hip():
     L.fs_debug_last_spmm_wide.argtypes = []
     L.fs_debug_tiled_layout.argtypes = [C.c_void_p, C.c_int]
     return L
-
-
-@contextlib.contextmanager
-def options(**kw):
-    """set library options, restore the values they had on the way out (an option without a getter is refused)"""
-    from libfastsparse_amd import capi
-    L = capi.lib()
-    old = {k: L.fs_get_option(k.encode()) for k in kw}
-    assert all(v != FS_ERR_ARG for v in old.values()), old
-    try:
-        for k, v in kw.items():
-            capi.set_option(k, v)
-        yield
-    finally:
-        for k, v in old.items():
-            capi.set_option(k, v)
-
-
-def _mode(mode):
-    return options(**({} if mode == "default" else {mode: 1}))
-
-
-def _d(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _poisoned(shape, fill):
