@@ -228,7 +228,9 @@ int fs_axpy(int n, double a, const double *x, double *y, fs_stream_t stream);
 
 /* ---- preconditioned solve (no counterpart in the reference: bsbm_cg is unpreconditioned, starts from 0, reports a count) ---- */
 /* d[j] = lambda + sum of v^2 over row j of At (v = 1 for a pattern-only matrix): the diagonal of A'A + lambda I, column j of A
- * taken from the transpose handle the caller of fs_cg already holds.  d: fs_matrix_nrow(At) doubles in HBM.  Stream-ordered, no
+ * taken from the transpose handle the caller of fs_cg already holds -- where no (row, column) pair is stored twice.  Entries that
+ * repeat a pair (fs_coo_create keeps them apart) are squared one by one: v1^2 + v2^2 where A'A has (v1 + v2)^2.  d stays positive,
+ * and as a preconditioner it changes the path of a solve, not what it converges to.  d: fs_matrix_nrow(At) doubles in HBM.  Stream-ordered, no
  * allocation.  Reads the plain CSR: FS_ERR_RELEASED after fs_matrix_release_csr.  The sum has a fixed shape and repeats its bits:
  * one wave per row; lane l starts at +0.0 and adds v * v (one multiply, one add, never fused) of entries l, l + 64, ... in
  * increasing order; the 64 lanes are folded by the __shfl_xor butterfly (32, 16, ..., 1); lambda is added last. */
