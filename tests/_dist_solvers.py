@@ -396,3 +396,251 @@ def interleaved_then_memory_back(L, s, ranks, kinds, seed, allowance, unchecked=
     free1 = torch.cuda.mem_get_info()[0]
     print(f"free device memory: {free0} bytes before the handle, {free1} after its destroy; allowance {allowance}")
     assert free0 - free1 <= allowance, (free0, free1, allowance)
+
+
+class CutPair(Dist):
+    """fs_dist_matrix_pair(A, At): A from s.a_csr(), At from s.t_csr_coo() -- the caller's entry order -- cut at the caller's `bounds`"""
+
+    def __init__(self, L, s, bounds):
+        from libfastsparse_amd import capi
+        ranks = len(bounds) - 1
+        self.L, self.s, self.ranks = L, s, ranks
+        self.csr = s.a_csr()
+        self.A = self.At = self.M = None
+        self.D = L.fs_dist_create(ranks, (C.c_int * ranks)(*([0] * ranks)))
+        assert self.D, L.fs_last_error()
+        try:
+            rp, cc, vv = self.csr
+            self.A = L.fs_dist_csr_create(self.D, s.nrow, s.ncol, len(cc), rp.ctypes.data, cc.ctypes.data, None if vv is None else vv.ctypes.data)
+            assert self.A, L.fs_last_error()
+            self.At = from_shards(L, self.D, s.ncol, s.nrow, s.t_csr_coo(), [b - a for a, b in zip(bounds, bounds[1:])], capi.FS_HOST)
+            self.M = capi.dist_matrix_pair(self.A, self.At)
+        except BaseException:
+            self.close()
+            raise
+
+    def close(self):
+        for h in (self.M, self.A, self.At):
+            if h:
+                self.L.fs_dist_matrix_destroy(h)
+        self.M = self.A = self.At = None
+        self.L.fs_dist_destroy(self.D)
+
+
+def assert_dmscgn_model(what, got, model, columns=None):
+    """dmscgn's outcome against _dist_mscgn_model.run's: every column's X, infos, st[] and per-shift array, then the solve's st[]"""
+    X, infos, cols, st = got
+    k = X.shape[2]
+    assert X.shape == model.X.shape and len(infos) == X.shape[0] and all(len(r) == k for r in infos), what
+    for j in (range(k) if columns is None else columns):
+        c = model.columns[j]
+        SV.assert_ladder_column(f"{what}, column {j}", X[:, :, j], [row[j] for row in infos], cols[j], c.X, c.infos, c.state, c.shifts)
+    if columns is None:
+        assert st["iter"] == max(c.state["iter"] for c in model.columns), (what, st)
+        assert st["done"] == float(all(c.state["done"] == 1.0 for c in model.columns)), (what, st)
+
+
+# ---- sharded solves on dirty work space (tests/test_gpu_dist_dirty_work.py) -------------------------------------------------
+SOLVERS = ("cg", "cg2", "pcg", "pcgn", "pcgn_lambdas", "mscg", "mscgn")
+READS_SCHEME = ("cg", "pcg", "pcgn_lambdas", "mscg", "mscgn")        # fs_dist_cg2 and fs_dist_pcgn are replicated whatever it says
+K_COLUMN = ("cg2", "pcgn", "pcgn_lambdas", "mscgn")
+LADDER = ("mscg", "mscgn")
+PCG_FAMILY = ("pcg", "pcgn", "pcgn_lambdas")
+MN_SCALARS = 9344                                                    # the header's "9344 doubles of scalars" of fs_dist_mscgn
+
+
+def work_space_per_rank(solver, F, nrow, bounds, k=1, m=1, nslots=0, scheme=0):
+    """the doubles of every device buffer a sharded solve keeps on its handle, all ranks' (include/fastsparse_hip.h, "Work space per
+    rank", with the sizes ensure_cg_work / ensure_pn_work / ensure_ladder_work / ensure_k of fs_dist.hip ask for): what poison_heap
+    fills before a solve that makes, or re-makes, them"""
+    n = len(bounds) - 1
+    rows = [b - a for a, b in zip(bounds, bounds[1:])]
+    slices = scheme == 1 and n > 1 and solver in READS_SCHEME
+    kk = 2 if solver == "cg2" else k if solver in K_COLUMN else 1
+    out = [F, nrow]                                                  # fs_dist_x / _y / _z
+    if solver in ("cg", "pcg", "mscg"):                              # CgWork: sol, r, b, p, q, dinv with room for a window; the sums
+        out += [F + max(rows) + 1, M.CG_PART_DOUBLES, 3 * DP.SEND_DOUBLES, DP.SEND_DOUBLES * n + 1, M.CG_STATE_DOUBLES]
+    if kk > 1 or solver in K_COLUMN:                                 # KWork: the whole P, T, Q of the k-column products; fs_dist_cg2's own
+        out += [F * kk, nrow * kk, M.CG_PART_DOUBLES, 4, M.CG_STATE_DOUBLES]
+    if solver in ("pcgn", "pcgn_lambdas", "mscgn"):                  # PnWork
+        for r in (rows if slices else [F]):
+            out += [max(r, 1) * k, max(r, 1)]
+        out += [2 * M.RED_BLOCKS * k, N.MAX_RHS * N.PN_STRIDE, M.CG_STATE_DOUBLES]
+        if slices:
+            out += [2 * 2 * N.MAX_RHS, n * 2 * N.MAX_RHS]
+    if solver in LADDER:                                             # LadderWork: m x_i, nslots P_i of ld doubles, the scalars
+        ld = ((max(rows) if slices else F) * (k if solver == "mscgn" else 1) + 1) & ~1
+        out += [ld * m, ld * max(nslots, 1), S.MAX_SHIFTS * S.MS_STRIDE if solver == "mscg" else MN_SCALARS]
+    return sorted({v for v in out if v > 0})
+
+
+class DirtyFrame:
+    """One sharded handle and the caller's vectors of its solves, every vector inside guard zones (LC.Guarded) in host memory or in
+    HBM.  solve(): one call of a sharded solver by its C entry point; after it the guards of X, B and diag are intact, B and diag
+    are unchanged, the gaps between the panels of X keep their bits, and a refused call leaves all of X with its prefill.
+    check(): the outcome against the solver's model bit for bit -- X, the infos, rank 0's state from the debug hooks."""
+
+    def __init__(self, L, dist, s, t_csr, bounds, kmax=8):
+        import _lifecycle as LC
+        self.LC, self.L, self.dist, self.s, self.t_csr, self.bounds = LC, L, dist, s, t_csr, [int(b) for b in bounds]
+        F = s.ncol
+        self.F = F
+        self.mems = {False: LC.NumpyMem(), True: LC.TorchMem()}
+        self.vec = {(hbm, role): LC.Guarded(mem, f"{role} of a sharded solve in {'HBM' if hbm else 'host memory'}", cap)
+                    for hbm, mem in self.mems.items() for role, cap in (("X", S.MAX_SHIFTS * (F * kmax + 3)), ("B", F * kmax), ("diag", F))}
+        self.products = M.csr_products(s.nrow, s.ncol, s.a_csr(), t_csr)
+        self.tkey = (s.name, t_csr[1].tobytes(), None if t_csr[2] is None else t_csr[2].tobytes())
+        self.solves = 0
+
+    def solve(self, solver, B, lam=None, lams=None, tol=None, cap=0, precond=P.PRECOND_NONE, X0=None, diag=None, hbm=False, pad=0, raw=None):
+        """(status, X as the solver's model shapes it or None, the infos or [count])"""
+        from libfastsparse_amd import capi
+        import torch
+        LC, L, s, F = self.LC, self.L, self.s, self.F
+        hbm = hbm and solver not in ("cg", "cg2")                    # (fs_dist_cg / _cg2 take host vectors)
+        B = np.ascontiguousarray(B, np.float64)
+        k = B.shape[1] if B.ndim == 2 else 1
+        m = len(lams) if solver in LADDER else 1
+        ne = F * k
+        ldx = ne + pad if solver in LADDER else ne
+        nx = (m - 1) * ldx + ne
+        gx, gb, gd = (self.vec[(hbm, role)] for role in ("X", "B", "diag"))
+        mem = self.mems[hbm]
+        before = np.full(nx, LC.PREFILLS["nan"], np.int64).view(np.float64)
+        if X0 is not None:
+            before = np.ascontiguousarray(X0, np.float64).reshape(-1).copy()
+        off8 = self.solves & 1
+        self.solves += 1
+        mem.put(gx.place(nx, off8), before)
+        mem.put(gb.place(B.size, off8 if k > 1 else (self.solves >> 1) & 1), B.reshape(-1))
+        ins = [(gb, B.reshape(-1), "B")]
+        if diag is not None:
+            mem.put(gd.place(F, (self.solves >> 2) & 1), diag)
+            ins.append((gd, np.ascontiguousarray(diag, np.float64), "diag"))
+        if hbm:
+            torch.cuda.synchronize()
+        tol = s.tol if tol is None else tol
+        lam = s.lam if lam is None else lam
+        a = dict(M=self.dist.M, X=mem.ptr(gx.view), B=mem.ptr(gb.view), k=k, m=m, ldx=ldx, tol=tol, cap=cap, precond=precond,
+                 lams=None if lams is None else [float(v) for v in lams])
+        a.update(raw or {})
+        prm = capi.PcgParams(float(a["tol"]), int(a["cap"]), int(a["precond"]), int(X0 is not None), None if diag is None else mem.ptr(gd.view))
+        infos = (capi.PcgInfo * max(m * k, 1))()
+        arr = None if a["lams"] is None else (C.c_double * max(len(a["lams"]), 1))(*a["lams"])
+        it = C.c_int(-1)
+        if solver in ("cg", "cg2"):
+            rc = getattr(L, "fs_dist_" + solver)(a["M"], a["X"], a["B"], lam, a["tol"], C.byref(it))
+        elif solver == "pcg":
+            rc = L.fs_dist_pcg(a["M"], a["X"], a["B"], lam, C.byref(prm), infos)
+        elif solver == "pcgn":
+            rc = L.fs_dist_pcgn(a["M"], a["X"], a["B"], a["k"], lam, C.byref(prm), infos)
+        elif solver == "pcgn_lambdas":
+            rc = L.fs_dist_pcgn_lambdas(a["M"], a["X"], a["B"], a["k"], arr, C.byref(prm), infos)
+        elif solver == "mscg":
+            rc = L.fs_dist_mscg(a["M"], a["X"], a["ldx"], a["B"], a["m"], arr, a["tol"], a["cap"], infos)
+        else:
+            rc = L.fs_dist_mscgn(a["M"], a["X"], a["ldx"], a["B"], a["k"], a["m"], arr, a["tol"], a["cap"], infos)
+        what = f"fs_dist_{solver}"
+        for g in (gx, gb, gd):
+            assert g.guards_ok(), (what, g.first_broken())
+        for g, want, name in ins:
+            assert g.mem.eq(g.view, g.mem.const(want)), (what, f"the caller's {name} was modified")
+        got = mem.get(gx.view)
+        if rc != 0:
+            assert np.array_equal(got.view(np.int64), before.view(np.int64)), (what, rc, "a refused call wrote to X")
+            return rc, None, None
+        if solver in LADDER:
+            gaps = np.ones(nx, bool)
+            for i in range(m):
+                gaps[i * ldx:i * ldx + ne] = False
+            assert np.array_equal(got.view(np.int64)[gaps], before.view(np.int64)[gaps]), (what, "a gap between the panels of X was written")
+            X = np.stack([got[i * ldx:i * ldx + ne] for i in range(m)])
+            X = X.reshape(m, F, k) if solver == "mscgn" else X
+            out = [list(infos[i * k:(i + 1) * k]) for i in range(m)] if solver == "mscgn" else list(infos)[:m]
+        elif solver in ("cg", "cg2"):
+            X, out = (got.reshape(F, 2) if solver == "cg2" else got), [it.value]
+        else:
+            X, out = (got.reshape(F, k) if solver != "pcg" else got), list(infos)[:k]
+        return rc, X, out
+
+    def column(self, kind, b, lam, lams, tol, cap, dinv, x0, bounds):
+        """one column's model (_dist_pcg_model.pcg, _dist_mscg_model.mscg), kept by its arguments"""
+        key = (self.tkey, kind, b.tobytes(), float(lam), None if lams is None else tuple(float(v) for v in lams), float(tol), cap,
+               None if dinv is None else dinv.tobytes(), None if x0 is None else x0.tobytes(), None if bounds is None else tuple(bounds))
+        if key not in _DIRTY_MODELS:
+            am, atm, _, _ = self.products
+            _DIRTY_MODELS[key] = (DP.pcg(self.F, am, atm, b, lam, tol, cap, dinv, x0, bounds) if kind == "pcg" else
+                                  DS.mscg(self.F, am, atm, b, lams, tol, cap, bounds))
+        return _DIRTY_MODELS[key]
+
+    def check(self, what, solver, scheme, X, infos, B, lam=None, lams=None, tol=None, cap=0, precond=P.PRECOND_NONE, X0=None, diag=None):
+        """the solve just made against its model, bit for bit: X, the infos, rank 0's state from the debug hooks"""
+        import _mscgn_model as SN
+        import _pcgn_lambdas_model as NL
+        L, s, F = self.L, self.s, self.F
+        tol = s.tol if tol is None else tol
+        lam = s.lam if lam is None else lam
+        B = np.ascontiguousarray(B, np.float64)
+        k = B.shape[1] if B.ndim == 2 else 1
+        bounds = self.bounds if scheme == 1 and self.dist.ranks > 1 and solver in READS_SCHEME else None
+        am, atm, am2, atm2 = self.products
+        if solver == "cg":
+            key = (self.tkey, "cg", B.tobytes(), float(lam), float(tol), None if bounds is None else tuple(bounds))
+            if key not in _DIRTY_MODELS:
+                _DIRTY_MODELS[key] = M.cg(F, am, atm, B, lam, tol, "device", bounds)
+            model = _DIRTY_MODELS[key]
+            bad = M.mismatch(X, model.x, infos[0], model.iterations, SV.cg_state(L, False), model.state)
+            assert bad is None, f"{what}: {bad}"
+        elif solver == "cg2":
+            key = (self.tkey, "cg2", B.tobytes(), float(lam), float(tol))
+            if key not in _DIRTY_MODELS:
+                _DIRTY_MODELS[key] = M.cg2(F, am2, atm2, B, lam, tol)
+            model = _DIRTY_MODELS[key]
+            bad = M.mismatch(X, model.x, infos[0], model.iterations, SV.cg_state(L, True), model.state)
+            assert bad is None, f"{what}: {bad}"
+        elif solver in PCG_FAMILY:
+            Bc = B.reshape(F, k)
+            X0c = None if X0 is None else np.ascontiguousarray(X0, np.float64).reshape(F, k)
+            ls = [lam] * k if solver != "pcgn_lambdas" else list(lams)
+            cols = [self.column("pcg", np.ascontiguousarray(Bc[:, j]), ls[j], None, tol, cap, NL.dinv_of_column(self.t_csr, ls[j], precond, diag),
+                                None if X0c is None else np.ascontiguousarray(X0c[:, j]), bounds) for j in range(k)]
+            st = P.state_from_device(SV.raw_state(L))
+            if solver == "pcg":
+                bad = M.mismatch(X, cols[0].x, infos[0].iterations, cols[0].iterations, st, cols[0].state)
+                assert bad is None, f"{what}: {bad}"
+                SV.assert_info(what, infos[0], cols[0])
+            else:
+                raw = np.full(N.MAX_RHS * N.PN_STRIDE, np.nan)
+                assert L.fs_debug_last_pcgn_state(raw.ctypes.data, raw.size) == k * N.PN_STRIDE
+                model = N.ResultN(np.stack([c.x for c in cols], 1), [N.info_of(c) for c in cols], cols)
+                assert_dnl_model(what, (X, infos, st, N.state_from_device(raw, k)), model)
+        elif solver == "mscg":
+            model = self.column("mscg", B.reshape(F), 0.0, lams, tol, cap, None, None, bounds)
+            raw = np.full(S.MAX_SHIFTS * S.MS_STRIDE, np.nan)
+            assert L.fs_debug_last_mscg_state(raw.ctypes.data, raw.size) == len(lams) * S.MS_STRIDE
+            assert_dmscg_model(what, (X, infos, S.state_from_device(SV.raw_state(L)), S.shifts_from_device(raw, len(lams))), model)
+        else:
+            Bc = B.reshape(F, k)
+            cols = [self.column("mscg", np.ascontiguousarray(Bc[:, j]), 0.0, lams, tol, cap, None, None, bounds) for j in range(k)]
+            assert_dmscgn_model(what, (X, infos, SV.mscgn_state(L, k, len(lams)), P.state_from_device(SV.raw_state(L))), SN._gather(cols, len(lams)))
+
+    def resident_products_exact(self, what):
+        """fs_dist_x / _y / _z are the solvers' work vectors: upload an integer x again, then fs_dist_spmv_resident and
+        fs_dist_spmv_t_resident are exact on every rank"""
+        L, s, dist = self.L, self.s, self.dist
+        am, atm, _, _ = self.products
+        x = (np.arange(s.ncol) * 7 % 23 - 11).astype(np.float64)
+        y = am(x)
+        z = atm(y)
+        for r in range(dist.ranks):
+            assert L.fs_copy_to_device(L.fs_dist_x(dist.M, r), x.ctypes.data, 8 * s.ncol) == 0
+        assert L.fs_dist_spmv_resident(dist.M) == 0, L.fs_last_error()
+        assert L.fs_dist_spmv_t_resident(dist.M) == 0, L.fs_last_error()
+        for r in range(dist.ranks):
+            gy, gz = np.full(s.nrow, np.nan), np.full(s.ncol, np.nan)
+            assert L.fs_copy_to_host(gy.ctypes.data, L.fs_dist_y(dist.M, r), 8 * s.nrow) == 0
+            assert L.fs_copy_to_host(gz.ctypes.data, L.fs_dist_z(dist.M, r), 8 * s.ncol) == 0
+            assert np.array_equal(gy.view(np.int64), y.view(np.int64)) and np.array_equal(gz.view(np.int64), z.view(np.int64)), (what, r)
+
+
+_DIRTY_MODELS = {}

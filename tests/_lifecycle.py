@@ -6,8 +6,9 @@ release_csr / restore_csr / download, option flips, stream changes, handles dest
 exactly summable sets of tests/_exact.py, so ONE bar -- equality of bits -- serves every mode and every order of additions.
 
 Solver pairs: next to these handles a walk keeps two pairs (A, At) of SEPARATE handles, as fs_cg takes them (At made from the
-transposed arrays), which live through the same operations and, besides, through fs_gram_diag, fs_cg, fs_cg2, fs_pcg, fs_mscg and
-fs_pcgn.  One pair holds a system of _cg_model.ExactFamily (binary, or its twin with values +-2), on which every solve is exact in
+transposed arrays), which live through the same operations and, besides, through fs_gram_diag, fs_cg, fs_cg2, fs_pcg, fs_mscg,
+fs_pcgn, fs_pcgn_lambdas and fs_mscgn (the k-column solves in whatever form option "pcgn_kernel" has been flipped to, fs_pcgn and fs_pcgn_lambdas narrowing
+or not as option "pcgn_compact" says: their segments are those of tests/_pcgn_plan_model.py on the widths the Model says are usable).  One pair holds a system of _cg_model.ExactFamily (binary, or its twin with values +-2), on which every solve is exact in
 whatever mode the flips have left; the other the general system binary_F257, for solves under strict_order that are compared with
 the models bit for bit (x, counts, info and the state of the fs_debug_last_*_state hooks).  Products on the pairs use
 integer-valued vectors.  After every solver operation: guards, inputs unchanged, the expected bits -- or, on an error, x still its
@@ -42,6 +43,7 @@ import _exact as E
 import _mscg_model as S
 import _pcg_model as P
 import _pcgn_model as N
+import _pcgn_plan_model as PM
 
 GUARD = 4096                        # doubles on either side of a vector: 32 KiB, wider than one 1024-thread store of doubles
 FS_OK, FS_ERR_ARG, FS_ERR_NO_TRANSPOSE, FS_ERR_RELEASED = 0, -2, -4, -5
@@ -54,7 +56,8 @@ PREFILLS = {"nan": QNAN | 0x0F0F00000001, "-0.0": -(1 << 63)}
 ROW_PLAN, KCOL_PLAN, MFMA_PLAN, LDSX_COLUMNS_PLAN = 1, 2, 4, 5
 
 FLIPS = {"reproducible": (0, 1), "strict_order": (0, 1), "cg_fixed_order": (1, 0), "spmv_kernel": (0, 1, 2, 3, "own"),
-         "spmm_kernel": (0, 1, 2, 3), "spmm_wide": (0, -1, 1), "ata_kernel": (0, 2), "tiled_flags": (0, 4)}   # first value: default
+         "spmm_kernel": (0, 1, 2, 3), "spmm_wide": (0, -1, 1), "ata_kernel": (0, 2), "tiled_flags": (0, 4),
+         "pcgn_kernel": (0, 1, 2), "pcgn_compact": (0, 1)}          # first value: default
 
 # forced copies beyond the PATHS table of test_gpu_exact.py: the builder's own choice
 AUTO = "auto"
@@ -63,10 +66,16 @@ OPS = {"spmv": 10, "spmv_t": 10, "spmm": 12, "spmm_t": 12, "ata": 6, "spmv_part"
        "dev_then_host": 3, "prepare": 6, "release_prepared": 4, "prepare_roundtrip": 2, "release_csr": 5, "restore_csr": 5, "download": 2,
        "flip": 10, "stream": 4, "churn": 2, "build_transpose": 3, "bad_arg": 2,
        # on the handles of a solver pair only (elsewhere their weight is 0)
-       "gram_diag": 5, "cg": 6, "cg2": 5, "pcg": 8, "mscg": 5, "pcgn": 8, "solve_strict": 8, "solve_bad_arg": 4}
-SOLVER_OPS = ("gram_diag", "cg", "cg2", "pcg", "mscg", "pcgn", "solve_strict", "solve_bad_arg")
-EXACT_ONLY = ("cg", "cg2", "pcg", "mscg", "pcgn")      # solves that need the exact family
+       "gram_diag": 5, "cg": 6, "cg2": 5, "pcg": 8, "mscg": 5, "pcgn": 8, "pcgn_lambdas": 7, "mscgn": 5, "solve_strict": 8,
+       "solve_bad_arg": 4}
+SOLVER_OPS = ("gram_diag", "cg", "cg2", "pcg", "mscg", "pcgn", "pcgn_lambdas", "mscgn", "solve_strict", "solve_bad_arg")
+EXACT_ONLY = ("cg", "cg2", "pcg", "mscg", "pcgn", "pcgn_lambdas", "mscgn")      # solves that need the exact family
 PCGN_KS = (1, 2, 3, 4, 5, 8, 16, 17, 32)
+MSCGN_KS = (1, 2, 3, 5, 8)
+LADDERS = ("mscg", "mscgn")                            # X is m vectors / panels ldx doubles apart
+K_COLUMNS = ("pcgn", "pcgn_lambdas", "mscgn")          # B is a row-major F x k panel
+NARROWING = ("pcgn", "pcgn_lambdas")                   # the solvers that read option "pcgn_compact"
+MSCGN_SCALARS = 9344                                   # fs_mscgn's scalars (the header's figure), in one block with its 2048 k partials
 POISON_TAG = 0x7E57AB1E                                # the tag of poison_heap's NaN
 
 
@@ -361,9 +370,16 @@ def solve_model(ps, solver, b, lam, tol, max_iter=0, precond=P.PRECOND_NONE, x0=
     elif solver == "mscg":
         r = S.mscg(F, am, atm, b, lams, tol, max_iter, tree)
         out = Solved(r.X, [i.iterations for i in r.infos], list(r.infos), r.state, r.shifts)
-    else:
+    elif solver == "mscgn":                                   # column j IS fs_mscg on B[:, j] (tests/_mscgn_model.py)
         B = np.asarray(b, np.float64).reshape(F, -1)
-        cols = [solve_model(ps, "pcg", np.ascontiguousarray(B[:, j]), lam, tol, max_iter, precond,
+        cols = [solve_model(ps, "mscg", np.ascontiguousarray(B[:, j]), lam, tol, max_iter, lams=lams, tree=tree) for j in range(B.shape[1])]
+        pairs = [(i, j) for i in range(len(lams)) for j in range(B.shape[1])]          # info[i * k + j]
+        out = Solved(np.stack([c.x for c in cols], 2), [cols[j].iters[i] for i, j in pairs], [cols[j].infos[i] for i, j in pairs],
+                     cols[0].state, [(c.state, c.extra) for c in cols])
+    else:                                                     # fs_pcgn; fs_pcgn_lambdas: column j IS fs_pcg at lams[j]
+        B = np.asarray(b, np.float64).reshape(F, -1)
+        lam_of = (lambda j: lam) if solver == "pcgn" else (lambda j: lams[j])
+        cols = [solve_model(ps, "pcg", np.ascontiguousarray(B[:, j]), lam_of(j), tol, max_iter, precond,
                             None if x0 is None else np.ascontiguousarray(np.asarray(x0).reshape(F, -1)[:, j]), diag, None, tree)
                 for j in range(B.shape[1])]
         out = Solved(np.stack([c.x for c in cols], 1), [c.iters[0] for c in cols], [c.infos[0] for c in cols], cols[0].state,
@@ -389,6 +405,26 @@ def exact_cases(fam):
                             dict(b=B.reshape(-1), precond=precond, diag=diag, x0=fam.x0(B, "mixed").reshape(-1) if start == "mixed" else None)))
     for name, lams in fam.ladders.items():
         out.append(("mscg", f"fs_mscg {name}", dict(b=s.b, lams=list(lams))))
+    # fs_pcgn_lambdas: a lambda per column, every d + lambda_j a power of two (the rungs of the ladders of 3 and 16, duplicates included), so
+    # column j is x = b_j / (d + lambda_j) at iteration 0 like fs_pcg; a zero column (panel: column k // 2); warm columns that take
+    # turns -- exact, 2 x exact (r = -b: one pass), cold
+    for pname, precond in (("none", P.PRECOND_NONE), ("jacobi", P.PRECOND_JACOBI), ("diag", P.PRECOND_DIAG)):
+        for k in PCGN_KS:
+            B = fam.panel(k)
+            rungs = fam.ladders["m3"] + fam.ladders["m16"]
+            lams = [rungs[j % len(rungs)] for j in range(k)]
+            X0 = np.zeros(B.shape)
+            for j in range(k):
+                X0[:, j] = B[:, j] * ((1.0, 2.0, 0.0)[j % 3] / (fam.d + lams[j]))
+            for start in ("cold", "mixed"):
+                out.append(("pcgn_lambdas", f"fs_pcgn_lambdas k {k} {pname} {start}",
+                            dict(b=B.reshape(-1), precond=precond, diag=fam.diag if precond == P.PRECOND_DIAG else None, lams=lams,
+                                 x0=X0.reshape(-1) if start == "mixed" else None)))
+    # fs_mscgn: the ladders of 1, 3 and 8 lambdas (the smallest twice, another rung twice) for k right-hand sides
+    ladders = {"m1": fam.ladders["m1"], "m3": fam.ladders["m3"], "m8": fam.ladders["m16"][:8]}
+    for k in MSCGN_KS:
+        for name, lams in ladders.items():
+            out.append(("mscgn", f"fs_mscgn k {k} {name}", dict(b=fam.panel(k).reshape(-1), lams=list(lams))))
     return out
 
 
@@ -419,19 +455,52 @@ def _strict_cases(ps):
             ("mscg", "fs_mscg ladder of 8 cap 12", dict(b=s.b, lams=[s.lam * f for f in (1e3, 10.0, 1e6, 1.0, 30.0, 1e4, 3.0, 1.0)], max_iter=12, tol=1e-6)),
             ("pcgn", "fs_pcgn k 5 jacobi warm cap 12", dict(b=B5.reshape(-1), precond=P.PRECOND_JACOBI, x0=X5.reshape(-1), max_iter=12, tol=1e-4)),
             ("pcgn", "fs_pcgn k 3 diag warm cap 4", dict(b=np.ascontiguousarray(B5[:, 2:5]).reshape(-1), precond=P.PRECOND_DIAG, diag=dg,
-                                                         x0=X3.reshape(-1), max_iter=4, tol=s.tol))]
+                                                         x0=X3.reshape(-1), max_iter=4, tol=s.tol)),
+            # (the lambdas: the system's own where X5 holds that lambda's iterates, so that the warm columns freeze as in fs_pcgn)
+            ("pcgn_lambdas", "fs_pcgn_lambdas k 5 jacobi warm cap 12",
+             dict(b=B5.reshape(-1), precond=P.PRECOND_JACOBI, x0=X5.reshape(-1), max_iter=12, tol=1e-4, lams=[s.lam * 30.0, s.lam, s.lam, s.lam, s.lam * 1e3])),
+            ("pcgn_lambdas", "fs_pcgn_lambdas k 3 diag cap 4",
+             dict(b=np.ascontiguousarray(B5[:, 2:5]).reshape(-1), precond=P.PRECOND_DIAG, diag=dg, x0=X3.reshape(-1), max_iter=4, tol=s.tol,
+                  lams=[s.lam, s.lam * 10.0, s.lam])),
+            ("mscgn", "fs_mscgn k 3 ladder of 8 cap 12",
+             dict(b=np.ascontiguousarray(B5[:, (0, 2, 3)]).reshape(-1), lams=[s.lam * f for f in (1e3, 10.0, 1e6, 1.0, 30.0, 1e4, 3.0, 1.0)], max_iter=12, tol=1e-6)),
+            ("mscgn", "fs_mscgn k 1 m 3", dict(b=s.b, lams=[s.lam * 3.0, s.lam, s.lam], max_iter=12, tol=1e-6))]
 
 
-def work_space(solver, F, Nrow, k=1, pre=False, nslots=0):
-    """the doubles of every device buffer a solve asks for (include/fastsparse_hip.h: 3 k F + k N, F for dinv, one F per shift with
-    sigma != 0, 2048 k and 512 for fs_pcgn; the partial sums kRedBlocks * 3, the sums and st[] of every solver)"""
+def repacking_cases(ps):
+    """the solves of exact_cases (exact family) or strict_cases (general system) that narrow under option "pcgn_compact" when every
+    rung is usable, as (solver, index among that solver's exact cases / among the strict cases, what): Jacobi panels of 2, 3, 5
+    and 17 columns whose zero and converged columns freeze at the start; the k = 5 solves whose columns freeze at different
+    iterations.  tests/test_lifecycle_model.py holds each against the plan model"""
+    if ps.fam is None:
+        return [(sv, i, what) for i, (sv, what, kw) in enumerate(strict_cases(ps)) if sv in NARROWING and kw["b"].size // ps.s.ncol == 5]
+    out = []
+    for solver in NARROWING:
+        cases = [c for c in exact_cases(ps.fam) if c[0] == solver]
+        out += [(solver, j, what) for j, (_, what, kw) in enumerate(cases) if kw["b"].size // ps.fam.F in (2, 3, 5, 17) and "jacobi" in what
+                and "k 2 jacobi mixed" not in what]              # (both columns frozen at the start: done before the first iteration)
+    return out
+
+
+def work_space(solver, F, Nrow, k=1, pre=False, nslots=0, widths=()):
+    """the doubles of every device buffer a solve asks for, one entry per allocation of fs_cg.hip (SolveFrame::alloc and the callers'
+    own blocks): r, p, q (k F each), tmp (k N), the partial sums kRedBlocks * 3, the sums, st[]; F for dinv / s; fs_mscg: one
+    block of ((F + 1) & ~1) nslots directions and its per-shift scalars; fs_pcgn, fs_pcgn_lambdas: one block of 2048 k partials and 512
+    scalars; fs_mscgn: one block of ((F k + 1) & ~1) nslots direction panels, one of 2048 k partials and 9344 scalars; narrowing
+    (widths: the two widest usable widths below k, w1 > w2, w2 = 0 when there is one): X, R, P at w1, X at w2 and 512 scalars.
+    tests/test_lifecycle_model.py holds the sums against the header's formulas ("Work space per solve")"""
     out = [k * F, k * F, k * F, k * Nrow, M.RED_BLOCKS * 3, 4, M.CG_STATE_DOUBLES]
     if pre:
         out.append(F)
     if solver == "mscg":
         out += [((F + 1) & ~1) * nslots, S.MAX_SHIFTS * S.MS_STRIDE]
-    if solver == "pcgn":
+    if solver in ("pcgn", "pcgn_lambdas"):
         out.append(2 * M.RED_BLOCKS * k + N.MAX_RHS * N.PN_STRIDE)
+    if solver == "mscgn":
+        out += [((F * k + 1) & ~1) * nslots, 2 * M.RED_BLOCKS * k + MSCGN_SCALARS]
+    if widths:
+        w1, w2 = widths
+        out += [w1 * F] * 3 + [w2 * F, N.MAX_RHS * N.PN_STRIDE]
     return [n for n in out if n > 0]
 
 
@@ -477,6 +546,19 @@ class Model:
         if self.released[0] and self.choice(0, o) < 6:
             return FS_ERR_RELEASED, builds
         return None, builds             # then the status of the A' product, known once A' exists
+
+    def prepare_refused(self, side, needs):
+        """fs_matrix_prepare answers FS_ERR_RELEASED: one-time work that reads the plain arrays (fs_debug_spmm_needs bits 0, 1) is
+        left and the side gave them back"""
+        return self.released[side] and bool(needs & 3)
+
+    def width_usable(self, side, w, needs, plan, o):
+        """option "pcgn_compact": a side lets a solve narrow to w columns -- its prepare(w) is not refused (needs: before the
+        solve) and the product of w columns (plan: what fs_matrix_spmm_plan says after the solve's own prepare; w = 1: the
+        single-vector product) does not read plain arrays that were given back"""
+        if w == 1:
+            return self.product(side, o) == FS_OK
+        return not self.prepare_refused(side, needs) and self.multi(side, plan) == FS_OK
 
     def release_csr(self):
         sides = [s for s in (0, 1) if (s == 0 or self.has_t) and self.kept[s] >= 6 and not self.released[s]]
@@ -530,7 +612,7 @@ class Walk:
         self.o = {}                     # the flippable options as the walk has set them
         self.neutral = {}
         self.counts = {"ops": {}, "status": {}, "k": [set(), set()], "nparts": {}, "host_behind_device": 0, "restore": set(),
-                       "recovered": 0, "part_between": 0, "poison_seen": 0, "poison_probed": 0, "poisoned": 0, "solves": {},
+                       "recovered": 0, "part_between": 0, "poison_seen": 0, "poison_probed": 0, "poisoned": 0, "repacked": 0, "solves": {},
                        "solver_status": {}}
         self.pairs = []
 
@@ -1017,7 +1099,7 @@ class Walk:
         pair = Pair(ps, HA, HT)
         HA.pair = HT.pair = pair
         F = ps.s.ncol
-        for role, cap in (("x", max(N.MAX_RHS * F, S.MAX_SHIFTS * (F + 3))), ("b", N.MAX_RHS * F), ("diag", F), ("d", F)):
+        for role, cap in (("x", max(N.MAX_RHS * F, S.MAX_SHIFTS * (F + 3), 8 * (max(MSCGN_KS) * F + 3))), ("b", N.MAX_RHS * F), ("diag", F), ("d", F)):
             HA.vec["solve " + role] = Guarded(self.b.mem, f"{role} of the solvers on {HA.name}", cap)
         self.pairs.append(pair)
         return pair
@@ -1042,11 +1124,27 @@ class Walk:
         if k == 1:
             return FS_ERR_RELEASED if any(h.model.product(0, self.o) != FS_OK for h in (pair.A, pair.At)) else FS_OK
         for h in (pair.A, pair.At):
-            if h.model.released[0] and (self.b.spmm_needs(h.A, k, 0, {}) & 3):
+            if h.model.prepare_refused(0, self.b.spmm_needs(h.A, k, 0, {})):
                 h.model.prepared[0].add(k)                  # (refused half way: see op_prepare)
                 return FS_ERR_RELEASED
             h.model.prepared[0].add(k)
         return None
+
+    def usable_widths(self, pair, k, needs):
+        """after a solve under option "pcgn_compact" that answered FS_OK: the rungs below k it may have narrowed to, from the Models of
+        the two handles (a refused width is silent).  needs: {w: fs_debug_spmm_needs of both handles before the solve}.  The solve
+        ran fs_matrix_prepare for every rung from 2 on, on A and, where A's went through, on At"""
+        usable = []
+        for w in sorted(needs, reverse=True):
+            hs = (pair.A, pair.At)
+            if w >= 2:
+                pair.A.model.prepared[0].add(w)
+                if not pair.A.model.prepare_refused(0, needs[w][0]):
+                    pair.At.model.prepared[0].add(w)
+            plans = [self.b.spmm_plan(h.A, w, 0) if w >= 2 else None for h in hs]
+            if all(h.model.width_usable(0, w, nd, pl, self.o) for h, nd, pl in zip(hs, needs[w], plans)):
+                usable.append(w)
+        return usable
 
     def run_solver(self, pair, solver, what, kw, want_x=None, x0=None, ldx=None, off8=None, k=1, jacobi=False, want=None, poison=None,
                    null=(), raw=None):
@@ -1055,33 +1153,41 @@ class Walk:
         the ones derived from kw (the bad arguments).  Returns (status, Solved or None)."""
         b_, mem, s = self.b, self.b.mem, pair.ps.s
         F, hA = s.ncol, pair.A
-        m = len(kw["lams"]) if solver == "mscg" else 1
-        ldx = F if ldx is None else ldx
+        m = len(kw["lams"]) if solver in LADDERS else 1
+        ne = F * k if solver == "mscgn" else F                 # one vector / panel of X
+        ldx = ne if ldx is None else ldx
         off8 = int(self.rng.integers(2)) if off8 is None else off8
-        nx = (m - 1) * ldx + F if solver == "mscg" else F * (2 if solver == "cg2" else k)
+        nx = (m - 1) * ldx + ne if solver in LADDERS else F * (2 if solver == "cg2" else k)
         gx, gb, gd = hA.vec["solve x"], hA.vec["solve b"], hA.vec["solve diag"]
         before_x = np.full(nx, PREFILLS["nan"], np.int64).view(np.float64)
         if x0 is not None:
             before_x = np.array(x0, np.float64).reshape(-1)
         mem.put(gx.place(nx, off8), before_x)
         b = np.ascontiguousarray(kw["b"], np.float64).reshape(-1)
-        mem.put(gb.place(b.size, off8 if solver in ("pcgn", "cg2") else int(self.rng.integers(2))), b)
+        mem.put(gb.place(b.size, off8 if solver in K_COLUMNS + ("cg2",) else int(self.rng.integers(2))), b)
         ins = [(gb, b, "b")]
         diag = kw.get("diag")
         if diag is not None:
             mem.put(gd.place(F, int(self.rng.integers(2))), diag)
             ins.append((gd, diag, "diag"))
         args = dict(lam=kw.get("lam", s.lam), tol=kw.get("tol", s.tol), max_iter=kw.get("max_iter", 0), precond=kw.get("precond", P.PRECOND_NONE),
-                    warm=x0 is not None, diag=None if diag is None else gd.view, k=m if solver == "mscg" else k, lams=kw.get("lams", ()), ldx=ldx, null=null)
+                    warm=x0 is not None, diag=None if diag is None else gd.view, k=m if solver == "mscg" else k, lams=kw.get("lams", ()), ldx=ldx, null=null,
+                    m=m)
         args.update(raw or {})
         if want is None:
             want = self.products_status(pair, 2 if solver == "cg2" else k, jacobi)
         kk = 2 if solver == "cg2" else k                    # the columns of the solve's products
         needs = [self.b.spmm_needs(h.A, kk, 0, {}) if kk >= 2 else 0 for h in (pair.A, pair.At)]
+        narrows = solver in NARROWING and self.o["pcgn_compact"] == 1
+        rungs = [w for w in PM.RUNGS if w < k] if narrows else []
+        wneeds = {w: [self.b.spmm_needs(h.A, w, 0, {}) if w >= 2 else 0 for h in (pair.A, pair.At)] for w in rungs}
         before = self.pair_state(pair)
         if poison if poison is not None else bool(self.rng.integers(2)):
-            nslots = len([v for v in kw.get("lams", ()) if v != min(kw["lams"])])
-            self.poison(pair, work_space(solver, F, s.nrow, 2 if solver == "cg2" else k, args["precond"] != P.PRECOND_NONE, nslots))
+            nslots = len([v for v in kw["lams"] if v != min(kw["lams"])]) if solver in LADDERS else 0
+            sizes = work_space(solver, F, s.nrow, 2 if solver == "cg2" else k, args["precond"] != P.PRECOND_NONE, nslots,
+                               widths=(rungs[-1], rungs[-2] if len(rungs) > 1 else 0) if rungs else ())
+            # (which rungs are usable is known behind the solve: the panels of every rung it could settle on, besides the widest two)
+            self.poison(pair, sizes + [w * F for w in rungs])
         self.note(f"{what} on {hA.name} / {pair.At.name}, x {nx} doubles 8 * {off8} off, ldx {ldx}")
         self.counts["solves"][solver] = self.counts["solves"].get(solver, 0) + 1
         rc, res = self.call(b_.solve, solver, pair.A.A, pair.At.A, gx.view, gb.view, **args)
@@ -1099,13 +1205,13 @@ class Walk:
         else:
             model = solve_model(pair.ps, solver, b, args["lam"], args["tol"], args["max_iter"], args["precond"], x0, diag, kw.get("lams"))
             full = before_x.copy()
-            if solver == "mscg":
+            if solver in LADDERS:
                 gaps = np.ones(nx, bool)
                 for i in range(m):
-                    full[i * ldx:i * ldx + F] = model.x[i]
-                    gaps[i * ldx:i * ldx + F] = False
+                    full[i * ldx:i * ldx + ne] = np.ascontiguousarray(model.x[i]).reshape(-1)
+                    gaps[i * ldx:i * ldx + ne] = False
                 if not np.array_equal(got.view(np.int64)[gaps], before_x.view(np.int64)[gaps]):
-                    self.fail("gap written", f"{what}: a gap between the vectors of X (ldx {ldx}, F {F}) was written, first at "
+                    self.fail("gap written", f"{what}: a gap between the vectors of X (ldx {ldx}, {ne} doubles each) was written, first at "
                               f"{int(np.flatnonzero(gaps & (got.view(np.int64) != before_x.view(np.int64)))[0])}")
             else:
                 full = np.ascontiguousarray(model.x).reshape(-1)
@@ -1116,20 +1222,36 @@ class Walk:
             for j, (g, w) in enumerate(zip(res["infos"] or [], model.infos or [])):
                 if (g[0], g[1]) != (w.iterations, w.converged) or not (M.same_bits(g[2], w.rnorm)[0] and M.same_bits(g[3], w.bnorm)[0]):
                     self.fail("not exact", f"{what}: fs_pcg_info[{j}] = {g}, the model {tuple(w)}")
+            if solver in NARROWING:
+                self.check_segments(pair, what, k, self.usable_widths(pair, k, wneeds), model, args["max_iter"] or F)
         after = self.pair_state(pair)
         if after[0] != before[0]:
             self.fail("option", f"{what} changed options: {[(n, before[0][n], after[0][n]) for n in FLIPS if before[0][n] != after[0][n]]}")
         if after[1] != before[1]:
             self.fail("bookkeeping", f"fs_matrix_spmv_kernel of the pair was {before[1]} before {what} and is {after[1]} after it (a scope "
                       "that was not given back?)")
-        for h, b0, b1, nd in zip((pair.A, pair.At), before[2], after[2], needs):
+        for i, (h, b0, b1, nd) in enumerate(zip((pair.A, pair.At), before[2], after[2], needs)):
             grew = rc == FS_OK and kk >= 2 and (nd & 5)
-            if b1[2] < b0[2] or (b1[2] != b0[2] and not (kk >= 2 and (nd & 5))) or b1[1] < b0[1] or b1[1] > h.base_bytes[1] + self.b.lazy_growth(h.A):
+            may_grow = (kk >= 2 and (nd & 5)) or (rc == FS_OK and any(wneeds[w][i] & 5 for w in wneeds))    # (the rungs' one-time work)
+            if b1[2] < b0[2] or (b1[2] != b0[2] and not may_grow) or b1[1] < b0[1] or b1[1] > h.base_bytes[1] + self.b.lazy_growth(h.A):
                 self.fail("device bytes", f"{h.name} reported {b0} before {what} and {b1} after it (prepare needs {nd}, after creation {h.base_bytes})")
             if grew and (self.b.spmm_needs(h.A, kk, 0, {}) & 5):
                 self.fail("bookkeeping", f"after {what} fs_matrix_prepare({kk}) still has work on {h.name}: the solve did not do its one-time work")
         pair.A.prove = pair.At.prove = True                 # the next product on either handle: exact
         return rc, model
+
+    def check_segments(self, pair, what, k, usable, model, cap):
+        """fs_debug_last_pcgn_segments of the solve just made against tests/_pcgn_plan_model.py on the model's counts: one segment of
+        all k columns without option "pcgn_compact"; with it the schedule on the usable widths.  A column is frozen by the start
+        kernels where its model never took r.z"""
+        segs = self.b.last_segments()
+        want = PM.plan(k, usable, model.iters, ["rsq" not in st for st in model.extra], cap)
+        self.log[-1] += f", usable widths {usable}, segments {segs}"
+        if segs != want:
+            self.fail("segments", f"{what}: fs_debug_last_pcgn_segments says {segs}, the plan model on the usable widths {usable} and "
+                      f"the counts {model.iters} says {want} (options {self.o})")
+        if any(w < k for _, w, _ in segs):
+            self.counts["repacked"] += 1
 
     def op_gram_diag(self, H):
         pair = H.pair
@@ -1160,12 +1282,15 @@ class Walk:
         pair = H.pair
         fam = pair.ps.fam
         cases = [c for c in exact_cases(fam) if c[0] == solver]
+        if pick is None and solver in NARROWING and self.o["pcgn_compact"] == 1 and self.rng.integers(2):
+            # half of the solves of a walk that narrows: panels of 3, 5 and 17 columns, which freeze columns at the start and so repack
+            cases = [c for c in cases if c[2]["b"].size // fam.F in (3, 5, 17)]
         _, what, kw = cases[int(self.rng.integers(len(cases))) if pick is None else pick % len(cases)]
         kw = dict(kw, lam=fam.s.lam, tol=fam.s.tol)
         if kw.get("precond") == P.PRECOND_DIAG and pair.saved_diag is not None and self.rng.integers(2):
             kw["diag"], what = pair.saved_diag, what + " (the diagonal of an earlier fs_gram_diag)"
-        k = kw["b"].size // fam.F if solver == "pcgn" else 1
-        ldx = fam.F + 3 * int(self.rng.integers(2)) if solver == "mscg" else None
+        k = kw["b"].size // fam.F if solver in K_COLUMNS else 1
+        ldx = fam.F * k + 3 * int(self.rng.integers(2)) if solver in LADDERS else None
         return self.run_solver(pair, solver, what, kw, x0=kw.get("x0"), ldx=ldx, k=k, jacobi=kw.get("precond") == P.PRECOND_JACOBI, poison=poison)
 
     def op_cg(self, H):
@@ -1183,6 +1308,12 @@ class Walk:
     def op_pcgn(self, H):
         self.exact_solve(H, "pcgn")
 
+    def op_pcgn_lambdas(self, H):
+        self.exact_solve(H, "pcgn_lambdas")
+
+    def op_mscgn(self, H):
+        self.exact_solve(H, "mscgn")
+
     def op_solve_strict(self, H, pick=None, poison=None):
         """strict_order on through the walk's own flip (the Model knows), one solver on the general system against its model, x,
         counts, info and the state of the debug hooks bit for bit; then the option as it was"""
@@ -1192,8 +1323,9 @@ class Walk:
         try:
             cases = strict_cases(pair.ps)
             solver, what, kw = cases[int(self.rng.integers(len(cases))) if pick is None else pick % len(cases)]
-            k = kw["b"].size // pair.ps.s.ncol if solver == "pcgn" else 1
-            rc, model = self.run_solver(pair, solver, what + " under strict_order", kw, x0=kw.get("x0"), k=k,
+            k = kw["b"].size // pair.ps.s.ncol if solver in K_COLUMNS else 1
+            ldx = pair.ps.s.ncol * k + 3 * int(self.rng.integers(2)) if solver == "mscgn" else None
+            rc, model = self.run_solver(pair, solver, what + " under strict_order", kw, x0=kw.get("x0"), k=k, ldx=ldx,
                                         jacobi=kw.get("precond") == P.PRECOND_JACOBI, poison=poison)
             if rc == FS_OK:
                 bad = self.state_mismatch(solver, model, len(kw.get("lams", ())), k)
@@ -1204,16 +1336,22 @@ class Walk:
         return rc
 
     def state_mismatch(self, solver, model, m, k):
-        st = self.b.last_state(solver, m if solver == "mscg" else k)
+        st = self.b.last_state(solver, m if solver == "mscg" else k, m)
         if st is None:
             return None
         state, extra = st
-        bad = M.mismatch(np.zeros(0), np.zeros(0), None, None, state, model.state if solver != "pcgn" else None)
+        bad = M.mismatch(np.zeros(0), np.zeros(0), None, None, state, model.state if solver not in K_COLUMNS else None)
         if bad or solver in ("cg", "pcg"):
             return bad
+        if solver == "mscgn":                               # fs_debug_last_mscgn_state(j): every column against its fs_mscg model
+            for j, (want_st, want_sh) in enumerate(model.extra):
+                bad = M.mismatch(np.zeros(0), np.zeros(0), None, None, extra[j][0], want_st) or S.shifts_mismatch(extra[j][1], want_sh)
+                if bad:
+                    return f"column {j}: {bad}"
+            return None
         if solver == "mscg":
             return S.shifts_mismatch(extra, model.extra)
-        for j, want in enumerate(model.extra):              # fs_pcgn: the scalars of every column against its fs_pcg model
+        for j, want in enumerate(model.extra):              # fs_pcgn, fs_pcgn_lambdas: the scalars of every column against its fs_pcg model
             for key, name in (("rr", "rr"), ("bb", "bb"), ("stop", "stop"), ("rsq", "rz"), ("alpha", "alpha"), ("beta", "beta")):
                 if key in want and not M.same_bits(extra[j][name], want[key])[0]:
                     return f"column {j} {name}: got {float(extra[j][name])!r} want {float(want[key])!r}"
@@ -1231,22 +1369,36 @@ class Walk:
                 ("mscg", "tol NaN", dict(tol=float("nan"))), ("mscg", "tol < 0", dict(tol=-1.0)),
                 ("mscg", "lambda NaN", dict(lams=[1.0, float("nan"), 5.0])), ("mscg", "lambda inf", dict(lams=[float("inf"), 1.0, 5.0])),
                 ("pcg", "precond = 3", dict(precond=3)), ("pcgn", "precond = 3", dict(precond=3)),
-                ("pcg", "DIAG with NULL diag", dict(precond=P.PRECOND_DIAG)), ("pcgn", "DIAG with NULL diag", dict(precond=P.PRECOND_DIAG))]
+                ("pcg", "DIAG with NULL diag", dict(precond=P.PRECOND_DIAG)), ("pcgn", "DIAG with NULL diag", dict(precond=P.PRECOND_DIAG)),
+                # fs_pcgn_lambdas and fs_mscgn
+                ("pcgn_lambdas", "NULL A", dict(null=("A",))), ("mscgn", "NULL A", dict(null=("A",))),
+                ("pcgn_lambdas", "NULL At", dict(null=("At",))), ("mscgn", "NULL At", dict(null=("At",))),
+                ("pcgn_lambdas", "NULL x", dict(null=("x",))), ("mscgn", "NULL x", dict(null=("x",))),
+                ("pcgn_lambdas", "NULL b", dict(null=("b",))), ("mscgn", "NULL b", dict(null=("b",))),
+                ("pcgn_lambdas", "NULL lambda", dict(null=("lambda",))), ("mscgn", "NULL lambda", dict(null=("lambda",))),
+                ("pcgn_lambdas", "NULL prm", dict(null=("prm",))), ("pcgn_lambdas", "A twice", dict(twice=True)), ("mscgn", "A twice", dict(twice=True)),
+                ("pcgn_lambdas", "k = 0", dict(k=0)), ("pcgn_lambdas", "k = 33", dict(k=33)), ("mscgn", "k = 0", dict(k=0)), ("mscgn", "k = 33", dict(k=33)),
+                ("mscgn", "m = 0", dict(m=0)), ("mscgn", "m = 17", dict(m=17)), ("mscgn", "ldx < F k", dict(ldx=-1)),
+                ("pcgn_lambdas", "lambda NaN", dict(lams=[1.0, float("nan"), 5.0])), ("pcgn_lambdas", "lambda inf", dict(lams=[float("inf"), 1.0, 5.0])),
+                ("mscgn", "lambda NaN", dict(lams=[1.0, float("nan"), 5.0])), ("mscgn", "lambda -inf", dict(lams=[1.0, 5.0, float("-inf")])),
+                ("pcgn_lambdas", "tol < 0", dict(tol=-1e-8)), ("pcgn_lambdas", "tol NaN", dict(tol=float("nan"))),
+                ("mscgn", "tol < 0", dict(tol=-1.0)), ("mscgn", "tol NaN", dict(tol=float("nan"))),
+                ("pcgn_lambdas", "precond = 3", dict(precond=3)), ("pcgn_lambdas", "DIAG with NULL diag", dict(precond=P.PRECOND_DIAG))]
 
     def op_solve_bad_arg(self, H, pick=None):
         pair = H.pair
         s = pair.ps.s
         solver, what, raw = self.BAD_ARGS[int(self.rng.integers(len(self.BAD_ARGS))) if pick is None else pick % len(self.BAD_ARGS)]
         raw = dict(raw)
-        k = 3 if solver == "pcgn" else 1
+        k = 3 if solver in K_COLUMNS else 1
         i = np.arange(s.ncol * max(k, 2), dtype=np.float64)
         kw = dict(b=(i % 7 - 3.0)[:s.ncol * (2 if solver == "cg2" else k)], lam=s.lam, tol=1e-6, max_iter=2)
-        if solver == "mscg":
+        if solver in LADDERS + ("pcgn_lambdas",):
             kw["lams"] = [s.lam + 4.0, s.lam, s.lam + 12.0]
-            if "k" in raw or "lams" in raw:
+            if solver == "mscg" and ("k" in raw or "lams" in raw) or solver == "mscgn" and "m" in raw:
                 raw.setdefault("lams", [s.lam] * 17)
             if raw.get("ldx") == -1:
-                raw["ldx"] = s.ncol - 1
+                raw["ldx"] = s.ncol * k - 1
         twice = raw.pop("twice", False)
         if twice:
             pair = Pair(pair.ps, pair.A, pair.A)            # At not of the transposed shape
@@ -1477,9 +1629,9 @@ class HipBackend:
     def gram_diag(self, At, lam, d):
         self.capi.gram_diag(At, lam, d, self.stream())
 
-    def solve(self, solver, A, At, x, b, lam=0.0, tol=1e-6, max_iter=0, precond=0, warm=False, diag=None, k=1, lams=(), ldx=0, null=()):
+    def solve(self, solver, A, At, x, b, lam=0.0, tol=1e-6, max_iter=0, precond=0, warm=False, diag=None, k=1, lams=(), ldx=0, null=(), m=1):
         """one solver call; null names arguments handed over as NULL.  {"iters": [...], "infos": [(iterations, converged, rnorm,
-        bnorm), ...] or None}; a negative status raises like every binding"""
+        bnorm), ...] or None} (fs_mscgn: info[i * k + j]); a negative status raises like every binding"""
         C, L, capi = self.C, self.L, self.capi
         pa, pt = None if "A" in null else A.h, None if "At" in null else At.h
         px, pb = None if "x" in null else x.data_ptr(), None if "b" in null else b.data_ptr()
@@ -1490,22 +1642,39 @@ class HipBackend:
             return {"iters": [it.value], "infos": None}
         prm = capi.PcgParams(tol, max_iter, precond, int(warm), None if diag is None else diag.data_ptr())
         pp = None if "prm" in null else C.byref(prm)
-        n = 1 if solver == "pcg" else max(k, 1)
+        n = 1 if solver == "pcg" else max(k, 1) * max(m, 1) if solver == "mscgn" else max(k, 1)
         infos = (capi.PcgInfo * max(n, len(lams), 1))()
+        # (room for every lambda a refused k or m could make the library look at)
+        arr = None if "lambda" in null else (C.c_double * max(len(lams), 64))(*lams)
         if solver == "pcg":
             rc = L.fs_pcg(pa, pt, px, pb, lam, pp, infos, st)
         elif solver == "pcgn":
             rc = L.fs_pcgn(pa, pt, px, pb, k, lam, pp, infos, st)
+        elif solver == "pcgn_lambdas":
+            rc = L.fs_pcgn_lambdas(pa, pt, px, pb, k, arr, pp, infos, st)
+        elif solver == "mscgn":
+            rc = L.fs_mscgn(pa, pt, px, ldx, pb, k, m, arr, tol, max_iter, infos, st)
         else:
-            arr = None if "lambda" in null else (C.c_double * max(len(lams), 1))(*lams)
             rc = L.fs_mscg(pa, pt, px, ldx, pb, k, arr, tol, max_iter, infos, st)
         capi.check(rc, "fs_" + solver)
         out = [(i.iterations, i.converged, i.rnorm, i.bnorm) for i in list(infos)[:n]]
         return {"iters": [i[0] for i in out], "infos": out}
 
-    def last_state(self, solver, n):
-        """(st[] by name, the per-shift / per-column scalars by name) of the last solve, from the fs_debug_last_*_state hooks"""
+    def last_segments(self):
+        return self.capi.pcgn_segments()
+
+    def last_state(self, solver, n, m=1):
+        """(st[] by name, the per-shift / per-column scalars by name) of the last solve, from the fs_debug_last_*_state hooks;
+        fs_mscgn: per column (its st[] by name, its per-shift array by name), from fs_debug_last_mscgn_state(j)"""
         C, L = self.C, self.L
+        if solver == "mscgn":
+            L.fs_debug_last_mscgn_state.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+            cols = []
+            for j in range(n):
+                st, raw = np.full(M.CG_STATE_DOUBLES, np.nan), np.full(S.MAX_SHIFTS * S.MS_STRIDE, np.nan)
+                assert L.fs_debug_last_mscgn_state(j, st.ctypes.data, raw.ctypes.data, raw.size) == m * S.MS_STRIDE
+                cols.append((S.state_from_device(st), S.shifts_from_device(raw, m)))
+            return None, cols
         L.fs_debug_last_cg_state.argtypes = [C.c_void_p]
         st = np.full(M.CG_STATE_DOUBLES, np.nan)
         assert L.fs_debug_last_cg_state(st.ctypes.data) == M.CG_STATE_DOUBLES
@@ -1523,26 +1692,31 @@ class HipBackend:
         return P.state_from_device(st), N.state_from_device(raw, n)
 
     def poison_heap(self, sizes):
-        """fs_device_alloc every size a solve is about to ask for and two neighbours of it, fill with a quiet NaN tagged as poison,
-        fs_device_free -- not through torch, whose allocator never hands memory back.  Then the probe: allocate the largest size
-        again and count the doubles that still carry the poison.  (doubles seen, doubles probed)"""
-        L = self.L
-        self.torch.cuda.synchronize()
-        want = sorted({n + d for n in sizes for d in (0, 2, 64)})
-        host = np.full(max(want), guard_bits(POISON_TAG), np.int64)
-        ptrs = []
-        for n in want:
-            p = L.fs_device_alloc(8 * n)
-            assert p, "fs_device_alloc failed"
-            ptrs.append(p)
-            assert L.fs_copy_to_device(p, host.ctypes.data, 8 * n) == 0
-        for p in reversed(ptrs):
-            L.fs_device_free(p)
-        n = max(sizes)
+        return poison_heap(self.L, sizes)
+
+
+def poison_heap(L, sizes):
+    """fs_device_alloc every size a solve is about to ask for and two neighbours of it, fill with a quiet NaN tagged as poison,
+    fs_device_free -- not through torch, whose allocator never hands memory back.  Then the probe: allocate the largest size
+    again and count the doubles that still carry the poison.  (doubles seen, doubles probed).  L: capi.lib(); also the sharded
+    suites' (tests/_dist_solvers.py)"""
+    import torch
+    torch.cuda.synchronize()
+    want = sorted({n + d for n in sizes for d in (0, 2, 64)})
+    host = np.full(max(want), guard_bits(POISON_TAG), np.int64)
+    ptrs = []
+    for n in want:
         p = L.fs_device_alloc(8 * n)
         assert p, "fs_device_alloc failed"
-        back = np.zeros(n, np.int64)
-        rc = L.fs_copy_to_host(back.ctypes.data, p, 8 * n)
+        ptrs.append(p)
+        assert L.fs_copy_to_device(p, host.ctypes.data, 8 * n) == 0
+    for p in reversed(ptrs):
         L.fs_device_free(p)
-        assert rc == 0
-        return int((back == host[0]).sum()), n
+    n = max(sizes)
+    p = L.fs_device_alloc(8 * n)
+    assert p, "fs_device_alloc failed"
+    back = np.zeros(n, np.int64)
+    rc = L.fs_copy_to_host(back.ctypes.data, p, 8 * n)
+    L.fs_device_free(p)
+    assert rc == 0
+    return int((back == host[0]).sum()), n

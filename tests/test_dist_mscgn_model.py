@@ -150,3 +150,37 @@ def test_one_slice_that_is_the_whole_panel_and_the_cache():
     assert not any(a is b for a, b in zip(other.columns, want.columns))
     sorted_t = DN.run(s, B, lams, max_iter=5, t_csr=s.t_csr_sorted(), cache=_CACHE)                # and so are the arrays of A'
     assert not any(a is b for a, b in zip(sorted_t.columns, want.columns))
+
+
+@pytest.mark.parametrize("F,nrow,bounds,k,m", [(300, 2000, [0, 100, 200, 300], 5, 8), (3, 3, [0, 1, 2, 3, 3, 3], 3, 3)])
+def test_the_poisoned_sizes_are_the_headers_work_space_per_rank(F, nrow, bounds, k, m):
+    """_dist_solvers.work_space_per_rank -- what the dirty-work suite poisons before a sharded solve makes its work space -- holds
+    every term of include/fastsparse_hip.h, "Work space per rank" (fs_dist_pcgn_lambdas, fs_dist_mscgn; fs_dist_mscg's (m + nslots) F
+    divided by the ranks), with the sizes the sources give the constants: a size that is off makes the poison miss silently"""
+    import _dist_solvers as DV
+    text = " ".join(open(os.path.join(M.ROOT, "include", "fastsparse_hip.h")).read().split())
+    for words in ("Work space per rank: five slices of n_r k * doubles (X, R, B, Q, and P in the send buffer), the whole P (ncol k) and T (nrow k), the slice of s / dinv, the partials, "
+                  "* two send slots of 2 FS_PCGN_MAX_RHS doubles and N times that for the gathered values",
+                  "m + nslots panels of n_r k doubles * (rounded up to an even count) for the X_i and the P_i",
+                  "2048 k doubles of partial sums, two send slots of 2 FS_PCGN_MAX_RHS doubles and N times * that for the gathered values; 9344 doubles of scalars",
+                  "as is the * (m + nslots) F work space"):
+        assert words in text, words
+    src = open(os.path.join(M.CSRC, "fs_common.h")).read() + open(os.path.join(M.CSRC, "fs_dist.hip")).read()
+    for line in ("constexpr size_t pcgn_part_doubles(int k) { return (size_t)1024 * 2 * (size_t)k; }", "constexpr int kPcgnSendDoubles = 2 * FS_PCGN_MAX_RHS;",
+                 "const size_t fl = (size_t)(F ? F : 1) + (size_t)M->t.plan.max_rows + 1;"):
+        assert line in src, line
+    n = len(bounds) - 1
+    rows = [b - a for a, b in zip(bounds, bounds[1:])]
+    even = lambda v: (v + 1) & ~1
+    nslots, send = m - 1, 2 * N.MAX_RHS
+    nl = DV.work_space_per_rank("pcgn_lambdas", F, nrow, bounds, k, scheme=1)
+    assert {max(r, 1) * k for r in rows} | {F * k, nrow * k} | {max(r, 1) for r in rows} | {2048 * k, 2 * send, n * send} <= set(nl), nl
+    whole = DV.work_space_per_rank("pcgn_lambdas", F, nrow, bounds, k, scheme=0)
+    assert {F * k, nrow * k, F, 2048 * k} <= set(whole) and 2 * send not in whole, whole
+    assert DV.work_space_per_rank("pcgn", F, nrow, bounds, k, scheme=1) == DV.work_space_per_rank("pcgn", F, nrow, bounds, k, scheme=0)
+    for scheme, n_r in ((0, F), (1, max(rows))):
+        mn = DV.work_space_per_rank("mscgn", F, nrow, bounds, k, m, nslots, scheme)
+        assert {even(n_r * k) * m, even(n_r * k) * nslots, 9344, 2048 * k, F * k, nrow * k} <= set(mn), (scheme, mn)
+        ms = DV.work_space_per_rank("mscg", F, nrow, bounds, 1, m, nslots, scheme)
+        assert {even(n_r) * m, even(n_r) * nslots, S.MAX_SHIFTS * S.MS_STRIDE, F + max(rows) + 1, M.CG_PART_DOUBLES} <= set(ms), (scheme, ms)
+    assert DV.MN_SCALARS == 9344 and 2 * M.RED_BLOCKS == 2048

@@ -60,16 +60,7 @@ def _model(s, B, lams, cap, t_csr, bounds=None, tol=None):
     return DN.run(s, B, lams, max_iter=cap, tol=tol, t_csr=t_csr, bounds=bounds, cache=_CACHE)
 
 
-def _assert_model(what, got, model, columns=None):
-    X, infos, cols, st = got
-    k = X.shape[2]
-    assert X.shape == model.X.shape and len(infos) == X.shape[0] and all(len(r) == k for r in infos), what
-    for j in (range(k) if columns is None else columns):
-        c = model.columns[j]
-        SV.assert_ladder_column(f"{what}, column {j}", X[:, :, j], [row[j] for row in infos], cols[j], c.X, c.infos, c.state, c.shifts)
-    if columns is None:
-        assert st["iter"] == max(c.state["iter"] for c in model.columns), (what, st)
-        assert st["done"] == float(all(c.state["done"] == 1.0 for c in model.columns)), (what, st)
+_assert_model = DV.assert_dmscgn_model
 
 
 def _assert_same_solve(what, got, want):
@@ -583,33 +574,7 @@ def test_interleaved_solves_share_the_work_space_and_give_it_back(L):
 
 
 # ---- 10 --------------------------------------------------------------------------------------------------------------------
-class _CutPair(DV.Dist):
-    """fs_dist_matrix_pair(A, At): A from s.a_csr(), At from s.t_csr_coo() -- the caller's entry order -- cut at the caller's `bounds`"""
-
-    def __init__(self, L, s, bounds):
-        from libfastsparse_amd import capi
-        ranks = len(bounds) - 1
-        self.L, self.s, self.ranks = L, s, ranks
-        self.csr = s.a_csr()
-        self.A = self.At = self.M = None
-        self.D = L.fs_dist_create(ranks, (C.c_int * ranks)(*([0] * ranks)))
-        assert self.D, L.fs_last_error()
-        try:
-            rp, cc, vv = self.csr
-            self.A = L.fs_dist_csr_create(self.D, s.nrow, s.ncol, len(cc), rp.ctypes.data, cc.ctypes.data, None if vv is None else vv.ctypes.data)
-            assert self.A, L.fs_last_error()
-            self.At = DV.from_shards(L, self.D, s.ncol, s.nrow, s.t_csr_coo(), [b - a for a, b in zip(bounds, bounds[1:])], capi.FS_HOST)
-            self.M = capi.dist_matrix_pair(self.A, self.At)
-        except BaseException:
-            self.close()
-            raise
-
-    def close(self):
-        for h in (self.M, self.A, self.At):
-            if h:
-                self.L.fs_dist_matrix_destroy(h)
-        self.M = self.A = self.At = None
-        self.L.fs_dist_destroy(self.D)
+_CutPair = DV.CutPair
 
 
 @pytest.mark.parametrize("name", list(DN.DIFFERING_BOUNDS))

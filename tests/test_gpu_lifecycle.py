@@ -4,8 +4,9 @@ The other GPU tests run one fixed script on a fresh handle.  Here a handle lives
 kind, prepare / release, release_csr / restore_csr, option flips, stream changes, neighbours created and destroyed -- and after
 every operation the guards of all vectors are untouched, the inputs unchanged, the outputs exact, the statuses what the header
 promises and the bookkeeping what the debug hooks saw.  Two solver pairs (A, At) live through the same walks and through
-fs_gram_diag, fs_cg, fs_cg2, fs_pcg, fs_mscg and fs_pcgn, half of the solves on work space that was poisoned just before (see
-tests/_lifecycle.py).  tests/test_lifecycle_model.py shows on a numpy stand-in that these checks catch the faults they are meant
+fs_gram_diag, fs_cg, fs_cg2, fs_pcg, fs_mscg, fs_pcgn, fs_pcgn_lambdas and fs_mscgn, with options "pcgn_kernel" and "pcgn_compact"
+among the flips (the segments of a narrowing solve against the plan model on the widths usable at that moment),
+half of the solves on work space that was poisoned just before (see tests/_lifecycle.py).  tests/test_lifecycle_model.py shows on a numpy stand-in that these checks catch the faults they are meant
 for, and that the seeds used here reach every operation."""
 import ctypes as C
 
@@ -60,10 +61,11 @@ def _count_poison(w):
 
 def test_solvers_on_poisoned_work_space(backend):
     """every solver right behind poison_heap: freed device memory of the sizes the solve is about to ask for holds a tagged NaN, so a
-    work vector (r, p, q, tmp, part, red, st, dinv, the directions of fs_mscg, the partials and scalars of fs_pcgn) that is read
-    before it is written puts that tag into x.  The exact family in the default mode (both twins: every fs_pcg start and
-    preconditioner, the ladders with ldx > F, fs_pcgn at every k with columns frozen from the start), the general system under
-    strict_order against the models, state included.  The bar is the walks': exact bits"""
+    work vector (r, p, q, tmp, part, red, st, dinv / s, the directions of fs_mscg, the partials and scalars of fs_pcgn and
+    fs_pcgn_lambdas, the direction panels, partials and 9344 scalars of fs_mscgn) that is read before it is written puts that tag
+    into x.  The exact family in the default mode (both twins: every fs_pcg start and preconditioner, the ladders with ldx > F,
+    fs_pcgn and fs_pcgn_lambdas at every k with columns frozen from the start, fs_mscgn at every k and ladder, packed and padded
+    panels), the general system under strict_order against the models, state included.  The bar is the walks': exact bits"""
     w = LC.Walk(backend, LC.data_sets()["wide_range_odd"], LC.AUTO, seed=11, steps=0, copies=COPIES)
     with w.session():
         w.create(first=True)
@@ -73,7 +75,7 @@ def test_solvers_on_poisoned_work_space(backend):
             nth = {}
             for solver, what, _ in cases:
                 j = nth[solver] = nth.get(solver, -1) + 1
-                if solver == "pcgn" and (j + valued) % 5:             # (a fifth of the 54 panels per twin: every k is met)
+                if solver in ("pcgn", "pcgn_lambdas") and (j + valued) % 5:      # (a fifth of the 54 panels per twin: every k is met)
                     continue
                 w.step += 1
                 rc, _ = w.exact_solve(pair.A, solver, poison=True, pick=j)
@@ -82,14 +84,34 @@ def test_solvers_on_poisoned_work_space(backend):
                     w.recover(h)
             w.step += 1
             w.op_gram_diag(pair.A)
+        exact = pair
         pair = w.create_pair("general")
         for i in range(len(LC.strict_cases(pair.ps))):
             w.step += 1
             assert w.op_solve_strict(pair.A, pick=i, poison=True) == LC.FS_OK
             for h in (pair.A, pair.At):
                 w.recover(h)
-        met = {kw["b"].size // pair.ps.s.ncol for sv, _, kw in LC.strict_cases(pair.ps) if sv == "pcgn"}
-        assert met == {3, 5} and w.counts["poisoned"] >= 40, (met, w.counts["poisoned"])
+        met = {sv: {kw["b"].size // pair.ps.s.ncol for s2, _, kw in LC.strict_cases(pair.ps) if s2 == sv} for sv in LC.K_COLUMNS}
+        assert met == {"pcgn": {3, 5}, "pcgn_lambdas": {3, 5}, "mscgn": {1, 3}} and w.counts["poisoned"] >= 100, (met, w.counts["poisoned"])
+        assert w.counts["solves"]["pcgn_lambdas"] >= 6 and w.counts["solves"]["mscgn"] >= 6, w.counts["solves"]
+        print(f"poisoned solves: {w.counts['solves']}")
+        # option "pcgn_compact": solves that really repack (LC.repacking_cases; the choice is checked on the CPU with the models), on
+        # poisoned work space -- the narrow panels X, R, P at w1, X at w2 and the 512 scalars are bare allocations whose padding
+        # columns must read +0.0.  run_solver holds the segments against the plan model
+        assert w.counts["repacked"] == 0
+        w.flip("pcgn_compact", 1)
+        before = dict(w.counts["solves"])
+        for solver, i, what in LC.repacking_cases(pair.ps):
+            w.step += 1
+            assert w.op_solve_strict(pair.A, pick=i, poison=True) == LC.FS_OK, what
+        for solver, j, what in LC.repacking_cases(exact.ps):
+            w.step += 1
+            rc, _ = w.exact_solve(exact.A, solver, poison=True, pick=j)
+            assert rc == LC.FS_OK, what
+        ran = sum(w.counts["solves"][sv] - before[sv] for sv in LC.NARROWING)
+        w.flip("pcgn_compact", 0)
+        print(f"pcgn_compact = 1: {w.counts['repacked']} of {ran} poisoned fs_pcgn / fs_pcgn_lambdas solves repacked")
+        assert w.counts["repacked"] == ran >= 6, (w.counts["repacked"], ran)
     _count_poison(w)
     print(f"poison probes: {w.counts['poison_seen']} of {w.counts['poison_probed']} doubles still held the poison")
 

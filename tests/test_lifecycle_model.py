@@ -17,7 +17,7 @@ import _pcg_model as P
 COPIES = ["stream", "two-pass", "two-pass one-byte", "long rows", "lds-staged", "tiled cut rows", LC.AUTO]
 CODES = {"stream": 1, "two-pass": 7, "two-pass one-byte": 7, "long rows": 7, "lds-staged": 8, "tiled cut rows": 6, LC.AUTO: 1}
 DEFAULTS = {"reproducible": 0, "strict_order": 0, "cg_fixed_order": 1, "spmv_kernel": 0, "spmm_kernel": 0, "spmm_wide": 0, "ata_kernel": 0,
-            "tiled_flags": 0, "binning": 1}
+            "tiled_flags": 0, "binning": 1, "pcgn_compact": 0, "pcgn_kernel": 0}
 SEEDS = (1, 2)                      # the seeds of tests/test_gpu_lifecycle.py
 STEPS = 150
 
@@ -412,14 +412,19 @@ class StandIn:
         if Mx.released[0] and (Mx.kernel_code(0) < 6 if k == 1 else Mx.spmm_plan(k, 0) in (LC.ROW_PLAN, LC.MFMA_PLAN)):
             _raise(LC.FS_ERR_RELEASED, what)
 
-    def solve(self, solver, A, At, x, b, lam=0.0, tol=1e-6, max_iter=0, precond=0, warm=False, diag=None, k=1, lams=(), ldx=0, null=()):
+    def solve(self, solver, A, At, x, b, lam=0.0, tol=1e-6, max_iter=0, precond=0, warm=False, diag=None, k=1, lams=(), ldx=0, null=(), m=1):
         what, fault, answers = "fs_" + solver, self.fault, False
         if null or (At is not None and A is not None and (At.d.nrow, At.d.ncol) != (A.d.ncol, A.d.nrow)):
             _raise(LC.FS_ERR_ARG, what)
         F = A.d.ncol
         if solver == "pcgn" and not 1 <= k <= 32 or solver == "mscg" and (not 1 <= k <= 16 or ldx < F or not np.isfinite(lams).all()):
             _raise(LC.FS_ERR_ARG, what)
-        if solver in ("pcg", "pcgn", "mscg") and not tol >= 0.0 or solver in ("pcg", "pcgn") and (precond not in (0, 1, 2) or precond == 2 and diag is None):
+        if solver == "pcgn_lambdas" and (not 1 <= k <= 32 or not np.isfinite(lams[:k]).all()):
+            _raise(LC.FS_ERR_ARG, what)
+        if solver == "mscgn" and (not 1 <= k <= 32 or not 1 <= m <= 16 or ldx < F * k or not np.isfinite(lams[:m]).all()):
+            _raise(LC.FS_ERR_ARG, what)
+        pcgs = ("pcg", "pcgn", "pcgn_lambdas")
+        if solver in pcgs + ("mscg", "mscgn") and not tol >= 0.0 or solver in pcgs and (precond not in (0, 1, 2) or precond == 2 and diag is None):
             _raise(LC.FS_ERR_ARG, what)
         if precond == P.PRECOND_JACOBI and At.released[0]:
             if fault == "jacobi on a released At zeroes x":
@@ -428,7 +433,7 @@ class StandIn:
             if fault != "jacobi on a released At answers":
                 _raise(LC.FS_ERR_RELEASED, what)
             answers = True
-        kk = 2 if solver == "cg2" else k if solver == "pcgn" else 1
+        kk = 2 if solver == "cg2" else k if solver in LC.K_COLUMNS else 1
         if kk >= 2:
             unprepared = fault == "pcgn leaves k unprepared" and ((A.spmm_needs(kk, 0) | At.spmm_needs(kk, 0)) & 5)
             if fault != "pcgn leaves k unprepared":
@@ -438,9 +443,32 @@ class StandIn:
         self._ready(At, kk, what)
         if kk >= 2 and unprepared or answers:
             self.fired()
+        usable = []                                         # option "pcgn_compact": the rungs below k, settled before x is written
+        if solver in LC.NARROWING and self.opt["pcgn_compact"]:
+            for w in (16, 8, 4, 2, 1):
+                if w >= k:
+                    continue
+                try:
+                    if w >= 2:
+                        A.prepare(w)
+                        At.prepare(w)
+                    self._ready(A, w, what)
+                    self._ready(At, w, what)
+                except StandInError as ex:                  # a refused width is silent
+                    assert f"({LC.FS_ERR_RELEASED})" in str(ex), ex
+                    if fault == "a refused width is reported as an error":
+                        self.fired()
+                        raise
+                    continue
+                usable.append(w)
         ps = A.d.system
         x0 = np.array(x) if warm else None
-        r = LC.solve_model(ps, solver, np.array(b), lam, tol, max_iter, precond, x0, None if diag is None else np.array(diag), list(lams) or None)
+        lams = list(lams) or None
+        if fault == "pcgn_lambdas takes lambda[0] for every column" and solver == "pcgn_lambdas" and any(
+                l != lams[0] and np.asarray(b).reshape(F, k)[:, j].any() for j, l in enumerate(lams)):
+            self.fired()
+            lams = [lams[0]] * k
+        r = LC.solve_model(ps, solver, np.array(b), lam, tol, max_iter, precond, x0, None if diag is None else np.array(diag), lams)
         pool, self.pool = self.pool, np.zeros(1)            # the work space of this solve: whatever its last owner left
         if solver == "mscg":
             for i in range(k):
@@ -448,14 +476,37 @@ class StandIn:
             if fault == "mscg writes into the gap" and ldx > F and k > 1:
                 self.fired()
                 x[F] = 0.0
+        elif solver == "mscgn":
+            for i in range(m):
+                x[i * ldx:i * ldx + F * k] = np.ascontiguousarray(r.x[i]).reshape(-1)
+            if fault == "mscgn writes into the gap between panels" and ldx > F * k and m > 1:
+                self.fired()
+                x[F * k + 1] = 0.0
+            if fault == "mscgn writes a frozen pair" and k >= 2:
+                self.fired()
+                x[(m - 1) * ldx:(m - 1) * ldx + F * k].reshape(F, k)[3, k // 2] = -0.0      # (the zero column: its pairs are frozen from the start)
         else:
             x[...] = np.ascontiguousarray(r.x).reshape(-1)
-        if fault == "work space read before it is written" and x[0] != 0.0 and pool.view(np.int64)[0] != 0:
+        reads = {"work space read before it is written": True, "pcgn_lambdas reads work space before it is written": solver == "pcgn_lambdas",
+                 "mscgn reads work space before it is written": solver == "mscgn"}.get(fault, False)
+        if reads and x[0] != 0.0 and pool.view(np.int64)[0] != 0:
             self.fired()
             x[0] = x[0] + pool[0]
         if fault == "pcgn writes a frozen column" and solver == "pcgn" and k >= 2:
             self.fired()
             x.reshape(F, k)[3, k // 2] = -0.0               # (the zero column: frozen from the start)
+        if solver in LC.NARROWING:
+            segs = self.segments = LC.PM.plan(k, usable, r.iters, ["rsq" not in st for st in r.extra], max_iter or F)
+            narrow = [sg for sg in segs if sg[1] < k]
+            if fault == "narrowing writes a column that was left behind" and narrow:
+                j = min(j for j in range(k) if not narrow[-1][2] >> j & 1)
+                self.fired()
+                col = x.reshape(F, k)[:, j]
+                col[3] = -0.0 if col.view(np.int64)[3] != LC.PREFILLS["-0.0"] else 1.0
+            padded = any(w > bin(mask).count("1") for _, w, mask in narrow)
+            if fault == "narrowing leaves a padding column unzeroed" and padded and x[0] != 0.0 and pool.view(np.int64)[0] != 0:
+                self.fired()
+                x[0] = x[0] + pool[0]
         base, off = _where(x)
         if fault == "solver stores past x" and self.calls >= 3:
             self.fired()
@@ -470,7 +521,10 @@ class StandIn:
         infos = None if r.infos is None else [(i.iterations, i.converged, i.rnorm, i.bnorm) for i in r.infos]
         return {"iters": list(r.iters), "infos": infos}
 
-    def last_state(self, solver, n):
+    def last_segments(self):
+        return list(self.segments)
+
+    def last_state(self, solver, n, m=1):
         return None                                         # (the stand-in's scalars ARE the model's)
 
     def poison_heap(self, sizes):
@@ -541,6 +595,21 @@ FAULTS = {
     "scope left on": (("option", "bookkeeping"), "reproducible"),
     "work space read before it is written": (("guard value read",), "a guard value of poison"),
     "mscg writes into the gap": (("gap written",), "a gap between the vectors of X"),
+    # fs_pcgn_lambdas and fs_mscgn
+    "mscgn writes into the gap between panels": (("gap written",), "a gap between the vectors of X"),
+    "mscgn writes a frozen pair": (("not exact",), "fs_mscgn"),
+    "pcgn_lambdas takes lambda[0] for every column": (("not exact",), "fs_pcgn_lambdas"),
+    "pcgn_lambdas reads work space before it is written": (("guard value read",), "a guard value of poison"),
+    "mscgn reads work space before it is written": (("guard value read",), "a guard value of poison"),
+    # option "pcgn_compact"
+    "narrowing writes a column that was left behind": (("not exact",), "fs_pcgn"),
+}
+# faults that need several rare things at once (option "pcgn_compact" on, a panel with padding right behind the poison; a released
+# pair that still solves k and cannot prepare a rung): no seeded walk of 150 steps meets them twice, so a driven walk does --
+# fault -> (kind, words, the step of DRIVEN at which it first matters)
+DRIVEN_FAULTS = {
+    "narrowing leaves a padding column unzeroed": (("guard value read",), "a guard value of poison", 4),
+    "a refused width is reported as an error": (("status",), "FS_ERR_RELEASED", 3),
 }
 RARE = ("jacobi on a released At answers", "jacobi on a released At zeroes x", "pcgn leaves k unprepared")     # (need a released pair)
 
@@ -574,6 +643,48 @@ def test_an_injected_fault_fails_the_walk_at_the_step_where_it_first_matters(set
         else:
             assert lib.first_fired is None, (fault, seed, "the fault fired at step", lib.first_fired, "and the walk passed")
     assert caught >= 2, (fault, caught)
+
+
+def _driven_walk(lib, sets):
+    """pairs on LDS-staged copies: 5 columns before and, under option "pcgn_compact", after fs_matrix_release_csr -- the released pair
+    still multiplies 5 columns (its sweeps were timed before the release) and 2, but cannot prepare 4: a refused width, silently,
+    and the solve is FS_OK on one segment; then on another pair 17 columns right behind the poison (15 live ones in a panel of
+    16: a padding column)"""
+    w = LC.Walk(lib, sets["wide_range"], "lds-staged", seed=1, steps=0, copies=["lds-staged"])
+
+    def step(f, *a, **kw):
+        w.step += 1
+        lib.begin_step(w.step)
+        return f(*a, **kw)
+
+    with w.session():
+        w.create(first=True)
+        pair, other = w.create_pair("exact"), w.create_pair("exact", valued=True)
+        names = [c[1] for c in LC.exact_cases(pair.ps.fam) if c[0] == "pcgn"]
+        rc, _ = step(w.exact_solve, pair.A, "pcgn", poison=False, pick=names.index("fs_pcgn k 5 none cold"))   # 0
+        assert rc == LC.FS_OK
+        step(w.op_release_csr, pair.A)                                                                        # 1
+        w.op_release_csr(pair.At)
+        step(w.flip, "pcgn_compact", 1)                                                                       # 2
+        rc, _ = step(w.exact_solve, pair.A, "pcgn", poison=True, pick=names.index("fs_pcgn k 5 none cold"))    # 3
+        assert rc == LC.FS_OK and "usable widths [2, 1], segments [(0, 5, 31)]" in w.log[-1], w.log[-1]
+        rc, _ = step(w.exact_solve, other.A, "pcgn", poison=True, pick=names.index("fs_pcgn k 17 none cold"))  # 4
+        assert rc == LC.FS_OK and w.counts["repacked"] == 1 and "segments [(0, 16," in w.log[-1], w.log[-1]
+    return w
+
+
+def test_the_honest_stand_in_passes_the_driven_walk(sets):
+    _driven_walk(StandIn(), sets)
+
+
+@pytest.mark.parametrize("fault", list(DRIVEN_FAULTS))
+def test_a_rare_narrowing_fault_fails_the_driven_walk_at_the_step_where_it_first_matters(sets, fault):
+    kind, words, at = DRIVEN_FAULTS[fault]
+    lib = StandIn(fault)
+    with pytest.raises(LC.WalkFailure) as ex:
+        _driven_walk(lib, sets)
+    assert ex.value.kind in kind and words in str(ex.value), (fault, ex.value.kind, str(ex.value)[:600])
+    assert ex.value.step == lib.first_fired == at, (fault, ex.value.step, lib.first_fired, at)
 
 
 def test_the_operation_mix_reaches_everything(sets, gpu_walks):
@@ -632,6 +743,9 @@ def test_the_exact_family_is_exact_in_any_order_of_additions(valued):
     cases = LC.exact_cases(fam)
     assert {c[0] for c in cases} == set(LC.EXACT_ONLY)
     assert {kw["b"].size // fam.F for sv, _, kw in cases if sv == "pcgn"} == set(LC.PCGN_KS)
+    assert {kw["b"].size // fam.F for sv, _, kw in cases if sv == "pcgn_lambdas"} == set(LC.PCGN_KS)
+    assert {(kw["b"].size // fam.F, len(kw["lams"])) for sv, _, kw in cases if sv == "mscgn"} == {(k, m) for k in LC.MSCGN_KS for m in (1, 3, 8)}
+    assert all(len(set(kw["lams"])) < len(kw["lams"]) for sv, _, kw in cases if sv in ("pcgn_lambdas", "mscgn") and len(kw["lams"]) >= 3), "duplicates"
     assert fam.c == 2.0 ** int(np.log2(fam.c)) and all(np.log2(fam.d + l) % 1 == 0 for ls in fam.ladders.values() for l in ls)
     assert fam.ladders["m16"].count(min(fam.ladders["m16"])) >= 2 and len(fam.ladders["m16"]) == 16
     assert np.array_equal(P.gram_diag(ps.t_csr, fam.s.lam), np.full(fam.F, fam.c)) and (valued == (fam.s.vals is not None))
@@ -644,9 +758,16 @@ def test_the_exact_family_is_exact_in_any_order_of_additions(valued):
             assert (a.iterations, a.converged) == (b.iterations, b.converged) == (0, 1), (what, a, b)
             assert M.same_bits(a.rnorm, b.rnorm)[0] and M.same_bits(a.bnorm, b.bnorm)[0], (what, a, b)
         B = kw["b"]
-        want = np.stack([B / (fam.d + l) for l in kw["lams"]]) if solver == "mscg" else B / fam.c
+        if solver == "mscg":
+            want = np.stack([B / (fam.d + l) for l in kw["lams"]])
+        elif solver == "mscgn":
+            want = np.stack([B.reshape(fam.F, -1) / (fam.d + l) for l in kw["lams"]])
+        elif solver == "pcgn_lambdas":
+            want = B.reshape(fam.F, -1) / (fam.d + np.array(kw["lams"]))[None, :]
+        else:
+            want = B / fam.c
         assert M.same_bits(dev.x, want).all(), (what, "x is not b / 2^e")
-        if solver == "pcgn":
+        if solver in ("pcgn", "pcgn_lambdas"):
             X = dev.x.reshape(fam.F, -1)
             k = X.shape[1]
             assert k == 1 or (M.same_bits(X[:, k // 2], np.zeros(fam.F)).all() and not kw["b"].reshape(fam.F, k)[:, k // 2].any()), (what, "the zero column")
@@ -663,9 +784,9 @@ def test_the_strict_solves_freeze_at_different_iterations():
             assert 2 <= r.iters[0] <= 20 and r.state["done"] == 1.0, (what, r.iters)
         else:
             assert 0 < kw["max_iter"] <= 12 and max(r.iters) <= kw["max_iter"], (what, r.iters)
-        if solver == "mscg" or "jacobi" in what and solver == "pcgn":
+        if solver == "mscg" or "ladder of 8" in what or "jacobi" in what and solver in ("pcgn", "pcgn_lambdas"):
             assert len(set(r.iters)) >= 3, (what, r.iters)
-            if solver == "pcgn":
+            if solver in ("pcgn", "pcgn_lambdas"):
                 assert r.infos[3].iterations == 0 and r.infos[3].converged == 1, "a column that is done before the first product"
 
 
@@ -688,8 +809,66 @@ def test_the_solver_operations_reach_everything(sets, gpu_walks):
             assert w.counts["poison_seen"] == w.counts["poisoned"]            # (the stand-in's probe sees its one double)
         missing = [o for o in LC.SOLVER_OPS if ops.get(o, 0) < 5]
         assert not missing, (name, missing, ops)
-        assert all(solves.get(sv, 0) >= 5 for sv in ("cg", "cg2", "pcg", "mscg", "pcgn")), (name, solves)
+        assert all(solves.get(sv, 0) >= 5 for sv in ("cg", "cg2", "pcg", "mscg", "pcgn", "pcgn_lambdas", "mscgn")), (name, solves)
         for sv in ("gram_diag", "pcg", "pcgn"):
             assert status.get((sv, LC.FS_ERR_RELEASED), 0) >= 1 and status.get((sv, LC.FS_OK), 0) >= 5, (name, sv, status)
+        for sv in ("pcgn_lambdas", "mscgn"):                # (the solves of solve_strict and solve_bad_arg count under their solver)
+            assert status.get((sv, LC.FS_OK), 0) >= 10, (name, sv, status)
+            assert status.get((sv, LC.FS_ERR_RELEASED), 0) >= 1 and status.get((sv, LC.FS_ERR_ARG), 0) >= 1, (name, sv, status)
         assert sum(v for (sv, rc), v in status.items() if rc == LC.FS_ERR_ARG) >= 5, (name, status)
         assert total // 4 <= poisoned <= 3 * total // 4, (name, poisoned, total)
+
+
+@pytest.mark.parametrize("F,nrow,k,m", [(2000, 6000, 5, 8), (257, 517, 17, 3)])
+def test_work_space_is_the_headers_formulas(F, nrow, k, m):
+    """LC.work_space -- what poison_heap fills -- against include/fastsparse_hip.h, "Work space per solve": a size that is off makes
+    the poison miss silently.  Besides the header's terms every solve has three small blocks (the partial sums 3 kRedBlocks, the 4
+    sums, st[]) and fs_mscg its per-shift scalars; a direction (panel) is rounded up to an even count of doubles"""
+    import _mscg_model as S
+    import _pcgn_model as N
+    import os
+    text = " ".join(open(os.path.join(M.ROOT, "include", "fastsparse_hip.h")).read().split())
+    for words in ("Work space per solve: 3 F + N doubles and one direction of F per shift with sigma != 0",
+                  "Work space per solve: 3 k F + k N doubles, F more with a preconditioner, 2048 k for the * partial sums and 512 for the per-column scalars",
+                  "Work space per solve: 3 k F + k N doubles (R, P, Q, T), one F x k direction panel per shift with sigma != 0, 2048 k doubles for * the partial sums and 9344 for the scalars",
+                  "Work space with the option: 3 w1 F + w2 F doubles more", "and 512 doubles for the scalars in original numbering"):
+        assert words in text, words
+    fixed = 3 * M.RED_BLOCKS + 4 + M.CG_STATE_DOUBLES
+    even = lambda n: (n + 1) & ~1
+    nslots = m - 1
+    total = lambda *a, **kw: sum(LC.work_space(*a, **kw))
+    assert total("cg", F, nrow) == 3 * F + nrow + fixed
+    assert total("cg2", F, nrow, 2) == 2 * (3 * F + nrow) + fixed
+    assert total("pcg", F, nrow) == 3 * F + nrow + fixed and total("pcg", F, nrow, 1, True) == 4 * F + nrow + fixed
+    assert total("mscg", F, nrow, 1, False, nslots) == 3 * F + nrow + even(F) * nslots + S.MAX_SHIFTS * S.MS_STRIDE + fixed
+    for solver in ("pcgn", "pcgn_lambdas"):
+        assert total(solver, F, nrow, k) == 3 * k * F + k * nrow + 2048 * k + 512 + fixed
+        assert total(solver, F, nrow, k, True) == 3 * k * F + k * nrow + F + 2048 * k + 512 + fixed
+        w1, w2 = [w for w in (16, 8, 4, 2, 1) if w < k][:2]
+        assert total(solver, F, nrow, k, True, widths=(w1, w2)) == 3 * k * F + k * nrow + F + 2048 * k + 512 + fixed + 3 * w1 * F + w2 * F + 512
+    assert total("mscgn", F, nrow, k, False, nslots) == 3 * k * F + k * nrow + even(F * k) * nslots + 2048 * k + 9344 + fixed
+    assert N.MAX_RHS * N.PN_STRIDE == 512 and 2 * M.RED_BLOCKS == 2048 and LC.MSCGN_SCALARS == 9344
+    # one entry per allocation: the blocks the solvers carve up themselves are one size each
+    assert 2048 * k + 512 in LC.work_space("pcgn_lambdas", F, nrow, k) and 2048 * k + 9344 in LC.work_space("mscgn", F, nrow, k, False, nslots)
+    assert even(F * k) * nslots in LC.work_space("mscgn", F, nrow, k, False, nslots)
+
+
+@pytest.mark.parametrize("kind", ("exact", "general"))
+def test_the_repacking_cases_repack(kind):
+    """the solves tests/test_gpu_lifecycle.py runs under option "pcgn_compact" on poisoned work space really narrow: by the models'
+    counts the plan holds a segment narrower than k -- and, over the cases, panels with padding columns and more than one repack"""
+    ps = LC.pair_system(kind)
+    picks = LC.repacking_cases(ps)
+    assert len(picks) >= (14 if kind == "exact" else 2) and {sv for sv, _, _ in picks} == set(LC.NARROWING), picks
+    padded = repacks = 0
+    for solver, i, what in picks:
+        cases = LC.strict_cases(ps) if kind == "general" else [c for c in LC.exact_cases(ps.fam) if c[0] == solver]
+        sv, name, kw = cases[i]
+        assert (sv, name) == (solver, what)
+        r = LC.solve_model(ps, solver, **dict(dict(lam=ps.s.lam, tol=ps.s.tol), **kw))
+        k = len(r.iters)
+        segs = LC.PM.plan(k, [w for w in LC.PM.RUNGS if w < k], r.iters, ["rsq" not in st for st in r.extra], kw.get("max_iter") or ps.s.ncol)
+        assert any(w < k for _, w, _ in segs), (what, r.iters, segs)
+        padded += any(w > bin(mask).count("1") for _, w, mask in segs)
+        repacks += len(segs) > 1
+    assert padded >= 1 and (kind == "exact" or repacks >= 2), (kind, padded, repacks)
